@@ -17,7 +17,12 @@ Workload at N = 1: BASELINE.json configs[1] (50 M reads, 1 read group, Q0-41); w
 every rank holds --reads reads (configs[3] at N = 8).  Inputs are generated on the device and
 are resident in HBM before the timed region.  Prints ONE JSON line on rank 0.
 
-The line's `extra` object (N = 1 only, --no-extra skips it) carries the numbers of the other
+A plain run does only what the headline needs: set up, warm up, time the K steps, write the outputs
+(--dump-outputs DIR) and print the line.  --full adds everything next to it: the CPU figures (before
+the first GPU call), the timed layout pass, the check of the output against the persistent apply
+kernel (`verified`) and the `extra` object.
+
+The line's `extra` object (--full, N = 1 only, --no-extra skips it) carries the numbers of the other
 configurations and of the rows next to the path, each measured in this same process after the timed
 region: BASELINE config 3 (8 read groups) with its layout passes, the one-read-per-row layout, the
 kernels of the truth-set / aligned-read rows (K4, K5, K6), the in-process FASTQ file path, and the CPU
@@ -37,6 +42,7 @@ sys.path.insert(0, os.path.join(ROOT, 'kbbq-py_amd'))
 
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 READ_LEN = 150
+DUMP_READS = 1 << 16           # --dump-outputs: reads in the sample of new qualities (65536 x 150 float32 = 39 MB)
 KERNEL_SOURCES = ('kbbq_kernels.h', 'kbbq_kernels_v3.h', 'kbbq_k2_tile.h')      # where K1 / K2 live: what profiles/pmc_traffic.json is keyed to
 
 
@@ -52,6 +58,13 @@ def parse_args(argv=None):
                     help='device layout of the resident batch: mate-pair rows with 4-bit sequence planes, mate-pair rows '
                          '(304 B per 2 x 150 bp), or one read per row (2 x 160 B)')
     ap.add_argument('--no-extra', action='store_true', help='skip the `extra` object (other configurations, N = 1 only)')
+    ap.add_argument('--full', action='store_true',
+                    help='everything next to the headline: the CPU baselines, the output check against the persistent kernel, the '
+                         'layout pass timing and (N = 1) the `extra` object.  Without it a run sets up, warms up, times the steps '
+                         'and prints the line')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last step computed as DIR/<name>.npy (rank 0): the count tables '
+                         '(float64) and the new qualities of a fixed, seeded sample of %d input reads (float32, input order)' % DUMP_READS)
     return ap.parse_args(argv)
 
 
@@ -72,6 +85,10 @@ def child_command(args, port):
            '--layout', args.layout]
     if args.no_extra:
         cmd.append('--no-extra')
+    if args.full:
+        cmd.append('--full')
+    if args.dump_outputs:
+        cmd += ['--dump-outputs', os.path.abspath(args.dump_outputs)]
     return cmd
 
 
@@ -219,7 +236,7 @@ def gbs(nbytes, ms):
 class Resident:
     """A device-resident synthetic batch in the layout the product would pick, with the cost of the layout passes."""
 
-    def __init__(self, dev, torch, rank, n, world, R, layout, single_end=False):
+    def __init__(self, dev, torch, rank, n, world, R, layout, single_end=False, time_layout=True):
         S = READ_LEN
         self.dev, self.torch, self.R, self.S, self.n = dev, torch, R, S, n
         batch = dev.ReadBatch.synthetic(rank * n, n, world * n, seed=1, nrg=R)
@@ -229,7 +246,10 @@ class Resident:
         self.layout_ms = {}
         self.name = 'one read per row, pitch %d' % batch.pitch
         ev = lambda: torch.cuda.Event(enable_timing=True)
-        if layout != 'reads':
+        if layout != 'reads' and not time_layout:
+            batch = dev.lay_out(batch, R, S, packed=(layout == 'packed'))
+            self.name = batch.describe()
+        elif layout != 'reads':
             first = dev.lay_out(batch, R, S, packed=(layout == 'packed'))       # the process's first launches: code load, allocations
             del first
             a, b = ev(), ev()
@@ -300,6 +320,27 @@ class Resident:
         else:
             ok = torch.equal(got[:, :S], want[:, :S])
         return bool(ok) and bool((want[:, :S] != chk.qual[:, :S]).any().item())      # and the kernel did change qualities
+
+    def outputs(self, reads=DUMP_READS):
+        """What the last step handed its caller (--dump-outputs): the count tables, and the new qualities of a fixed, seeded
+        sample of input reads as self.out holds them, in input order -- the same reads whatever the layout, so two builds
+        compare output for output."""
+        import numpy as np
+        torch, b, S = self.torch, self.batch, self.S
+        idx = np.sort(np.random.default_rng(2024).choice(self.n, size=min(reads, self.n), replace=False))
+        two = isinstance(b, self.dev.PairBatch)
+        unit = idx // 2 if two else idx                  # mate-pair rows: reads 2p and 2p + 1 are the two halves of row p
+        if b.perm is not None:                           # rows grouped by read group: row i holds pair / read perm[i] of the input
+            perm = b.perm.cpu().numpy()
+            inv = np.empty_like(perm)
+            inv[perm] = np.arange(perm.size, dtype=perm.dtype)
+            unit = inv[unit]
+        col = ((idx % 2) * (S + 1) if two else np.zeros_like(idx))[:, None] + np.arange(S)[None, :]
+        if idx.size and (int(unit.max()) >= self.out.shape[0] or int(col.max()) >= self.out.shape[1]):
+            raise RuntimeError('bench.py: the output sample falls outside the output plane')
+        rows = self.out[torch.from_numpy(unit).to(self.out.device)].cpu().numpy()
+        return {'tables': self.tables.buf.cpu().numpy().astype(np.float64),
+                'qualities': np.take_along_axis(rows, col, 1).astype(np.float32)}
 
 
 def timed_steps(torch, dist, use_dist, dev, parallel, res, steps, warmup, rehearse, restore_order=False):
@@ -833,7 +874,7 @@ def run_rank(args):
     # the CPU figures come FIRST: the all-core leg forks worker processes, which must not inherit a HIP context or the
     # runtime's threads (nothing GPU-side has been imported or initialised yet)
     cpu_base = None
-    if world == 1 and rank == 0 and args.cpu_sample > 0:
+    if args.full and world == 1 and rank == 0 and args.cpu_sample > 0:
         assert 'torch' not in sys.modules
         cpu_base = cpu_port_one_core(args.cpu_sample)
         if not args.no_extra:
@@ -864,8 +905,8 @@ def run_rank(args):
     host_binding = parallel.bind_host_threads(local) if use_dist else None     # threads = CPUs / LOCAL_WORLD_SIZE, on the GPU's NUMA node
 
     n, R, S = args.reads, args.rgs, READ_LEN
-    res = Resident(dev, torch, rank, n, world, R, args.layout)
-    res.free_rows()
+    res = Resident(dev, torch, rank, n, world, R, args.layout, time_layout=args.full)
+    res.free_rows(check_reads=1_000_000 if args.full else 0)
     elapsed, k1_avg, k2_avg, k1_n, k2_n, ar_ms = timed_steps(torch, dist, use_dist, dev, parallel, res, args.steps,
                                                               args.warmup, rehearse)
     t = torch.tensor([elapsed], dtype=torch.float64, device='cpu' if rehearse or not use_dist else 'cuda')
@@ -886,6 +927,7 @@ def run_rank(args):
         dist.all_gather_object(every, verified)
         verified_ranks = every
         verified = None if any(v is None for v in every) else all(every)
+    dumped = res.outputs() if args.dump_outputs and rank == 0 else None
     layout_name = res.name
     layout_pass_ms = res.layout_ms.get('lay_out')
     layout_key = res.batch.layout_key() if hasattr(res.batch, 'layout_key') else ('reads' if args.layout == 'reads' else 'pairs')
@@ -927,9 +969,9 @@ def run_rank(args):
                                                         bases_per_rank * world / ((step_ms + layout_pass_ms) * 1e-3)),
                        'parallelism': 'reads sharded x%d, 1 allreduce of count tables' % world},
             'verified': verified, 'verified_per_rank': verified_ranks,
-            'verified_how': 'after the timed region, on EVERY rank (the line carries the AND): the new qualities of the first 1 M reads of '
-                            "the rank's resident batch (in the headline's layout, as the last step left them) == the persistent apply "
-                            'kernel on the same reads as character rows, one read per row',
+            'verified_how': ('after the timed region, on EVERY rank (the line carries the AND): the new qualities of the first 1 M reads of '
+                             "the rank's resident batch (in the headline's layout, as the last step left them) == the persistent apply "
+                             'kernel on the same reads as character rows, one read per row') if args.full else 'not checked (--full checks it)',
             'host_binding': host_binding,
             'ranks_seen': ranks_seen, 'backend': backend,
             'allreduce_ms_per_step': ar_ms,
@@ -959,8 +1001,13 @@ def run_rank(args):
             base['host_cores'] = host_cores()
             base['measured'] = 'before the first GPU call of this process (the worker pool of the all-core leg is forked from a process without a HIP context)'
             res_line['cpu_baseline'] = base
-        if world == 1 and not args.no_extra:
+        if args.full and world == 1 and not args.no_extra:
             res_line['extra'] = build_extra(torch, dev, parallel, args, args.layout)
+        if dumped is not None:
+            import numpy as np
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            for name, arr in dumped.items():
+                np.save(os.path.join(args.dump_outputs, name + '.npy'), arr)
         sys.stdout.flush()
         os.dup2(saved_stdout, 1)
         print(json.dumps(res_line), flush=True)

@@ -22,6 +22,7 @@ cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
 run() {  # run NAME TIMEOUT CMD...
   local name=$1 limit=$2; shift 2
   local log=gpurun_out/${name}_$TAG.log
+  OUTDIR=${log%/*}
   echo "== $name: $*" > $log
   timeout -k 10 $limit "$@" >> $log 2>&1
   local rc=$?
@@ -79,7 +80,7 @@ for step in "$@"; do
                && rm -rf gpurun_out/stats_$TAG gpurun_out/stats_${TAG}_extra \
                && run prof_headline 600 rocprofv3 --kernel-trace --stats -d gpurun_out/stats_$TAG -o s --output-format csv -- python3 bench.py --steps 20 --warmup 5 --no-extra --cpu-sample 0 \
                && grep '^{' gpurun_out/prof_headline_$TAG.log | tail -1 > gpurun_out/bench_under_rocprof_$TAG.json \
-               && run prof_extra 900 rocprofv3 --kernel-trace --stats -d gpurun_out/stats_${TAG}_extra -o s --output-format csv -- python3 bench.py --steps 20 --warmup 5 --cpu-sample 0 \
+               && run prof_extra 900 rocprofv3 --kernel-trace --stats -d $OUTDIR/stats_${TAG}_extra -o s --output-format csv -- python3 bench.py --full --steps 20 --warmup 5 --cpu-sample 0 \
                && cp $(find gpurun_out/stats_$TAG -name 's_kernel_stats.csv' | head -1) gpurun_out/bench_kernel_stats_$TAG.csv \
                && cp $(find gpurun_out/stats_$TAG -name 's_kernel_trace.csv' | head -1) gpurun_out/bench_kernel_trace_$TAG.csv \
                && cp $(find gpurun_out/stats_${TAG}_extra -name 's_kernel_stats.csv' | head -1) gpurun_out/bench_with_extra_kernel_stats_$TAG.csv \

@@ -729,7 +729,7 @@ def test_bench_prints_one_json_line_with_the_contract_fields(dev):
     roofline and cpu_baseline objects; a small run (the default sizes are the driver's business)."""
     import json, os, subprocess, sys
     from conftest import ROOT
-    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '2', '--warmup', '1',
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--full', '--gpus', '1', '--steps', '2', '--warmup', '1',
                         '--reads', '400000', '--cpu-sample', '20000'], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.split('\n') if ln.strip()]
@@ -766,6 +766,34 @@ def test_bench_prints_one_json_line_with_the_contract_fields(dev):
     assert pp['run']['sequential'] and pp['run']['spooled'] and st['value'] > 1e6
     assert extra['config3_8rg']['verified'] is True and extra['single_end_150']['verified'] is True
     assert extra['from_input_order_rows']['ms_per_step'] == extra['layout_reads']['ms_per_step']
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_its_outputs(dev, tmp_path):
+    """A plain bench.py run is the headline alone (no CPU figures, no `extra`, no output check); --steps sets the timed steps;
+    --dump-outputs writes the count tables and the new qualities of the sampled reads, which are the same whatever the
+    layout (mate-pair rows on 4-bit planes grouped by read group, one character row per read grouped by read group)."""
+    import json, os, subprocess, sys
+    from conftest import ROOT
+    got = []
+    for layout in ('packed', 'reads'):
+        out = tmp_path / layout
+        r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1', '--reads', '400000',
+                            '--rgs', '8', '--layout', layout, '--dump-outputs', str(out)], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.split('\n') if ln.strip()]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        assert d['steps'] == 3 and d['unit'] == 'bases/s' and d['dtype'] == 'u8' and d['higher_is_better'] is True
+        assert abs(d['value'] - 400000 * 150 / (d['ms_per_step'] / 1e3)) / d['value'] < 1e-6
+        assert 'extra' not in d and 'cpu_baseline' not in d and d['verified'] is None
+        files = sorted(os.listdir(out))
+        assert files == ['qualities.npy', 'tables.npy'] and sum(os.path.getsize(out / f) for f in files) < 64 << 20
+        got.append({f[:-4]: np.load(out / f) for f in files})
+    for g in got:
+        q = g['qualities']
+        assert q.dtype == np.float32 and q.shape == (1 << 16, 150) and q.min() >= 33 and q.max() <= 33 + 93
+        assert g['tables'].dtype == np.float64 and g['tables'].sum() > 0
+    assert np.array_equal(got[0]['tables'], got[1]['tables']) and np.array_equal(got[0]['qualities'], got[1]['qualities'])
 
 
 def test_bench_launches_its_own_two_rank_job(dev):

@@ -141,7 +141,7 @@ def test_bench_with_several_ranks_checks_every_rank(dev):
     """`python bench.py --gpus RANKS` through its own launcher (gloo rehearsal on the shared GPU): one JSON line, every rank
     verified its own batch and the line carries the AND, every rank reports its share of the host threads."""
     env = dict(os.environ); env.pop('RANK', None); env.pop('WORLD_SIZE', None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', str(RANKS), '--steps', '2', '--warmup', '1',
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--full', '--gpus', str(RANKS), '--steps', '2', '--warmup', '1',
                         '--reads', '200000'], capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.split('\n') if ln.strip()]
@@ -162,7 +162,7 @@ def test_one_rank_over_rccl(dev, oracle, tmp_path):
     env['HSA_ENABLE_IPC_MODE_LEGACY'] = '0'
     s_ = socket.socket(); s_.bind(('127.0.0.1', 0)); port = s_.getsockname()[1]; s_.close()
     launch = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '1', '--master-addr', '127.0.0.1', '--master-port', str(port)]
-    r = subprocess.run(launch + [os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1', '--reads', '400000',
+    r = subprocess.run(launch + [os.path.join(ROOT, 'bench.py'), '--full', '--gpus', '1', '--steps', '3', '--warmup', '1', '--reads', '400000',
                                  '--no-extra', '--cpu-sample', '0'], capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads([ln for ln in r.stdout.split('\n') if ln.startswith('{')][-1])

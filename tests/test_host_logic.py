@@ -762,6 +762,46 @@ def test_bench_parent_launches_a_child_job_without_touching_the_gpu(monkeypatch,
         bench.main(['--gpus', '4', '--no-extra'])
 
 
+def test_bench_output_sample_is_the_same_reads_in_every_layout():
+    """bench.py --dump-outputs: Resident.outputs() takes the new qualities of one seeded sample of input reads out of one read
+    per row and out of mate-pair rows, each as they are and grouped through a permutation -- here on CPU tensors laid out by
+    hand (row i of a grouped plane is pair / read perm[i] of the input)."""
+    import importlib, sys, types
+    import torch
+    sys.path.insert(0, ROOT)
+    bench = importlib.import_module('bench')
+    n, S, k = 1000, 150, 64
+    rng = np.random.default_rng(1)
+    want = rng.integers(33, 75, (n, S), dtype=np.uint8)       # new qualities of read i, input order
+    want[:, 0], want[:, 1] = np.arange(n) % 256, np.arange(n) // 256
+
+    class ReadBatch:
+        perm = None
+
+    class PairBatch:
+        perm = None
+
+    def outputs(batch, plane, perm=None):
+        r = bench.Resident.__new__(bench.Resident)
+        if perm is not None:
+            batch.perm, plane = torch.from_numpy(perm), plane[perm]
+        r.torch, r.dev, r.batch, r.S, r.n = torch, types.SimpleNamespace(PairBatch=PairBatch), batch, S, n
+        r.out, r.tables = torch.from_numpy(plane), types.SimpleNamespace(buf=torch.arange(7, dtype=torch.int64))
+        return r.outputs(k)
+    rows = np.zeros((n, 160), np.uint8)
+    rows[:, :S] = want
+    pairs = np.zeros((n // 2, 304), np.uint8)
+    pairs[:, :S], pairs[:, S + 1:2 * S + 1] = want[0::2], want[1::2]
+    got = [outputs(ReadBatch(), rows), outputs(ReadBatch(), rows, rng.permutation(n)),
+           outputs(PairBatch(), pairs), outputs(PairBatch(), pairs, rng.permutation(n // 2))]
+    q = got[0]['qualities']
+    idx = q[:, 0].astype(np.int64) + 256 * q[:, 1].astype(np.int64)
+    assert q.dtype == np.float32 and q.shape == (k, S) and np.array_equal(q, want[idx]) and np.all(np.diff(idx) > 0)
+    for g in got:
+        assert np.array_equal(g['qualities'], q)
+        assert g['tables'].dtype == np.float64 and np.array_equal(g['tables'], np.arange(7))
+
+
 def test_empty_bgzip_fastq_is_zero_reads(tmp_path):
     """An empty file written by bgzip is ONLY the 28-byte EOF block (isize 0): zero reads, as the reference sees it."""
     eof = bytes.fromhex('1f8b08040000000000ff0600424302001b0003000000000000000000')
