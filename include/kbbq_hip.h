@@ -204,6 +204,42 @@ int kbbq_apply(kbbq_ctx* ctx, const uint8_t* seq, const uint8_t* qual, const uin
                const int64_t* meanq, const int64_t* rgdq, const int64_t* qdq,
                const int64_t* posdq, const int64_t* dinucdq, uint8_t* qual_out);
 
+/* ---- ApplyBQSR on aligned rows ----------------------------------------
+ * Replaces gatk.applybqsr.recalibrate_bamread (gatk/applybqsr.py:46-78) for every alignment of a batch at once.  Rows are the
+ * SAM reader's character planes (kbbq_sam_fill: SEQ, QUAL, OQ; pitch a multiple of 16, 16-byte aligned, zero padded) in
+ * ALIGNED orientation, as they sit in the file; the output plane (new quality + 33, zero beyond the length) is aligned too.
+ * One uint32 of metadata per row:
+ *     bits  0..15  length L (0: nothing to do, the row's output is zero)
+ *     bits 16..27  read-group index (< R <= 4096)
+ *     bit  28      the SOURCE qualities (the ones recalibrated) are the OQ plane, else the QUAL plane
+ *     bit  29      the CONTEXT qualities are the OQ plane, else the QUAL plane
+ *     bit  30      reverse strand (FLAG 16)      bit 31  second in pair (FLAG 128)
+ * Base i (j = i forward, L - 1 - i reverse): q = source - 33; q < minscore keeps its byte; otherwise
+ *     new q = trunc(meanq[rg] + rgdq[rg] + qdq[rg][q] + dinucdq[rg][q][ctx] + posdq[rg][q][cycle])   (no clipping)
+ * with cycle j (first of pair) or -(j + 1) wrapping on S2 (second), and ctx the dinucleotide in sequencing orientation from the
+ * context plane with a fixed minscore of 6 (reverse rows complemented, letters other than ACGT -> N; none at j = 0, next to N or
+ * below 6: column 16).  q >= Qt or j >= S2 on a recalibrated base -> KBBQ_E_INDEX; a forward row with a letter outside ACGTN
+ * in a looked-up dinucleotide -> KBBQ_E_TYPE (it wins a tie); new q + 33 outside 0..255 -> KBBQ_E_RANGE; all through
+ * kbbq_ctx_status with the row's index.
+ * The model, `mode`:
+ *   KBBQ_ALIGNED_LUT  the int16 canonical rows of kbbq_build_lut's blob (the first kbbq_lut_count(R, Qt, S2) entries; Qt <= 95):
+ *                     exact for integer models, and for float models whose every truncated sum the caller has proven to be
+ *                     cycle entry + context entry
+ *   KBBQ_ALIGNED_F64  float64, one row of 18 + S2 doubles per (rg, q): [ meanq + rgdq + qdq (summed in that order),
+ *                     dinucdq[0..16], posdq[0..S2-1] ]; the kernel evaluates (row[0] + row[1 + ctx]) + row[18 + cycle]
+ *                     and truncates -- the reference's float64 sum, left to right (Qt <= 223)
+ * d_qual / d_oq may be the same plane, and either may be NULL when no row selects it.                                   */
+#define KBBQ_ALIGNED_LUT 0
+#define KBBQ_ALIGNED_F64 1
+int kbbq_apply_aligned_dev(kbbq_ctx* ctx, const uint8_t* d_seq, const uint8_t* d_qual, const uint8_t* d_oq,
+                           const uint32_t* d_meta, int64_t n, int pitch, int R, int Qt, int S2, int minscore,
+                           const void* d_model, int mode, uint8_t* d_out);
+/* Host-buffer form: the model (model_bytes bytes, as above) is uploaded once, the rows travel through the page-locked slabs of
+ * kbbq_apply.  On an error *bad_read (may be NULL) receives the offending row's index in the WHOLE input, else -1.        */
+int kbbq_apply_aligned(kbbq_ctx* ctx, const uint8_t* seq, const uint8_t* qual, const uint8_t* oq, const uint32_t* meta,
+                       int64_t n, int pitch, int R, int Qt, int S2, int minscore, const void* model, size_t model_bytes,
+                       int mode, uint8_t* out, int64_t* bad_read);
+
 /* ---- K3: delta-Q model solve ------------------------------------------
  * Replaces compare_reads.gatk_delta_q (compare_reads.py:235-260) and, fused,
  * applybqsr.get_delta_qs (gatk/applybqsr.py:80-103).  Split of labour (DESIGN.md
@@ -533,6 +569,12 @@ int kbbq_text_open(const char* path, kbbq_text** out, const uint8_t** data, size
 int kbbq_text_close(kbbq_text* t);
 int kbbq_sam_fill(const kbbq_sam* f, int64_t first, int64_t n, int pitch, int which, uint8_t* plane);
 int kbbq_sam_text(const kbbq_sam* f, int what, int64_t i, const char** p, int64_t* len);
+/* kbbq_sam_render: alignments [first, first + n) as SAM lines ('\n'-terminated), each its own text with the QUAL field
+ * replaced by row r of `qplane` (the field's own length; a '*' QUAL is kept) -- what applybqsr writes.  set_oq: append
+ * "\tOQ:Z:<QUAL as read>" to a record without an OQ tag (an existing tag is kept).  out == NULL: *used = the bytes needed;
+ * otherwise out holds cap bytes (KBBQ_E_ARG when they do not suffice) and *used = the bytes written.                     */
+int kbbq_sam_render(const kbbq_sam* f, int64_t first, int64_t n, const uint8_t* qplane, int pitch, int set_oq,
+                    uint8_t* out, size_t cap, size_t* used);
 
 
 /* ---- host FASTQ ingest / egress (no GPU) ----------------------------------

@@ -6,6 +6,7 @@
 #include "kbbq_layout_kernels.h"
 #include "kbbq_aligned_kernels.h"
 #include "kbbq_k2_tile.h"
+#include "kbbq_apply_aligned.h"
 #include "../../include/kbbq_hip.h"
 #include "host_threads.h"
 
@@ -2150,6 +2151,149 @@ int kbbq_apply(kbbq_ctx* c, const uint8_t* seq, const uint8_t* qual, const uint3
         return rc ? rc : fail(KBBQ_E_HIP, "kbbq_apply: a status reported by the pipelined run did not reproduce slab by slab");
     }
     for (int b = 0; b < 2; ++b) { rc = stage_out((int)((k + b) & 1)); if (rc) return stage_drain(c, rc); }     // the older of the two first
+    return KBBQ_OK;
+}
+
+// ---- ApplyBQSR on aligned rows (kbbq_apply_aligned.h) -----------------------------------------------------------------------
+int kbbq_apply_aligned_dev(kbbq_ctx* c, const uint8_t* d_seq, const uint8_t* d_qual, const uint8_t* d_oq, const uint32_t* d_meta,
+                           int64_t n, int pitch, int R, int Qt, int S2, int minscore, const void* d_model, int mode, uint8_t* d_out)
+{
+    if (!c) return fail(KBBQ_E_ARG, "ctx is NULL");
+    if (!d_qual) d_qual = d_oq;
+    if (!d_oq) d_oq = d_qual;
+    int rc = check_planes("kbbq_apply_aligned_dev", n, pitch, d_seq, d_qual, d_out);
+    if (rc) return rc;
+    if ((uintptr_t)d_oq & 15) return fail(KBBQ_E_ARG, "kbbq_apply_aligned_dev: planes must be 16-byte aligned");
+    if (n > 0 && (!d_seq || !d_qual || !d_meta || !d_out || !d_model)) return fail(KBBQ_E_ARG, "kbbq_apply_aligned_dev: NULL argument");
+    if (mode != KBBQ_ALIGNED_LUT && mode != KBBQ_ALIGNED_F64) return fail(KBBQ_E_ARG, "kbbq_apply_aligned_dev: bad mode %d", mode);
+    if (R <= 0 || R > 4096 || Qt <= 0 || Qt > (mode == KBBQ_ALIGNED_LUT ? 95 : 223) || S2 <= 0 || S2 > 65536)
+        return fail(KBBQ_E_ARG, "kbbq_apply_aligned_dev: bad table shape R=%d Qt=%d S2=%d (R <= 4096)", R, Qt, S2);
+    if (minscore < 0 || minscore > 222) return fail(KBBQ_E_ARG, "kbbq_apply_aligned_dev: minscore out of range");
+    if ((uintptr_t)d_model & 15) return fail(KBBQ_E_ARG, "kbbq_apply_aligned_dev: the model must be 16-byte aligned");
+    if (n == 0) return KBBQ_OK;
+    HIPCHK(hipSetDevice(c->device));
+    AaParams p;
+    p.cpr = pitch / 16; p.pitch = pitch; p.Qt = Qt; p.S2 = S2; p.minscore = minscore;
+    p.lut = reinterpret_cast<const int16_t*>(d_model); p.rs = lut_row_stride(S2);
+    p.f64 = reinterpret_cast<const double*>(d_model); p.rs64 = AA_F64_FIXED + S2;
+    p.status = c->d_status;
+    // launches of at most 2^31 chunks (32-bit chunk numbers in the kernel)
+    const int64_t per = std::max<int64_t>(1, ((int64_t)1 << 31) / p.cpr);
+    for (int64_t lo = 0; lo < n; lo += per) {
+        const int64_t m = std::min(per, n - lo);
+        const size_t off = (size_t)lo * pitch;
+        p.seq = d_seq + off; p.qual = d_qual + off; p.oq = d_oq + off; p.meta = d_meta + lo; p.out = d_out + off;
+        p.nchunks = (u32)(m * p.cpr); p.row0 = lo;
+        const unsigned grid = (unsigned)(((int64_t)p.nchunks + AA_THREADS - 1) / AA_THREADS);
+        {
+            Timed t(c, 1);
+            if (mode == KBBQ_ALIGNED_LUT) hipLaunchKernelGGL(kaa_apply<AA_LUT>, dim3(grid), dim3(AA_THREADS), 0, c->stream, p);
+            else hipLaunchKernelGGL(kaa_apply<AA_F64>, dim3(grid), dim3(AA_THREADS), 0, c->stream, p);
+        }
+        HIPCHK(hipGetLastError());
+    }
+    return KBBQ_OK;
+}
+
+int kbbq_apply_aligned(kbbq_ctx* c, const uint8_t* seq, const uint8_t* qual, const uint8_t* oq, const uint32_t* meta,
+                       int64_t n, int pitch, int R, int Qt, int S2, int minscore, const void* model, size_t model_bytes,
+                       int mode, uint8_t* out, int64_t* bad_read)
+{
+    if (bad_read) *bad_read = -1;
+    if (!c) return fail(KBBQ_E_ARG, "ctx is NULL");
+    if (n < 0 || pitch <= 0 || (pitch & 15)) return fail(KBBQ_E_ARG, "kbbq_apply_aligned: bad n/pitch");
+    if (!qual) qual = oq;
+    if (!oq) oq = qual;
+    if (n > 0 && (!seq || !qual || !meta || !out)) return fail(KBBQ_E_ARG, "kbbq_apply_aligned: NULL plane");
+    if (!model || !model_bytes) return fail(KBBQ_E_ARG, "kbbq_apply_aligned: no model");
+    if (n == 0) return KBBQ_OK;
+    HIPCHK(hipSetDevice(c->device));
+    DevBuf dm;
+    HIPCHK(dm.alloc(model_bytes));
+    HIPCHK(hipMemcpyAsync(dm.p, model, model_bytes, hipMemcpyHostToDevice, c->stream));
+    // a slab: seq | qual | oq | out | meta (one quality plane when both are the same array)
+    const bool one_q = qual == oq;
+    const int planes = one_q ? 3 : 4;
+    const size_t slab = stage_slab_rows(pitch, planes, n);
+    const size_t plane = slab * (size_t)pitch, set = (size_t)planes * plane + slab * 4;
+    int rc = stage_prepare(c, set);
+    if (rc) return rc;
+    const size_t o_out = (size_t)(planes - 1) * plane, o_meta = (size_t)planes * plane;
+    auto launch = [&](int b, int64_t m) {
+        uint8_t* d = (uint8_t*)c->stage_dev[b];
+        return kbbq_apply_aligned_dev(c, d, d + plane, d + (one_q ? plane : 2 * plane), (const uint32_t*)(d + o_meta), m, pitch,
+                                      R, Qt, S2, minscore, dm.p, mode, d + o_out);
+    };
+    auto stage_in = [&](int b, int64_t lo, int64_t m) {
+        uint8_t* h = (uint8_t*)c->stage_host[b];
+        const size_t off = (size_t)lo * pitch, nb = (size_t)m * pitch;
+        threaded_copy(h, seq + off, nb); threaded_copy(h + plane, qual + off, nb);
+        if (!one_q) threaded_copy(h + 2 * plane, oq + off, nb);
+        memcpy(h + o_meta, meta + lo, (size_t)m * 4);
+    };
+    auto upload = [&](int b, int64_t m, hipStream_t st) -> int {
+        HIPCHK(hipMemcpyAsync(c->stage_dev[b], c->stage_host[b], o_out, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync((uint8_t*)c->stage_dev[b] + o_meta, (uint8_t*)c->stage_host[b] + o_meta, (size_t)m * 4, hipMemcpyHostToDevice, st));
+        return KBBQ_OK;
+    };
+    struct Out { int64_t lo, m; };
+    Out pending[2] = {{0, 0}, {0, 0}};
+    auto stage_out = [&](int b) -> int {
+        if (!pending[b].m) return KBBQ_OK;
+        HIPCHK(hipEventSynchronize(c->stage_down[b]));
+        threaded_copy(out + (size_t)pending[b].lo * pitch, (uint8_t*)c->stage_host[b] + o_out, (size_t)pending[b].m * pitch);
+        pending[b].m = 0;
+        return KBBQ_OK;
+    };
+    // the slab order of kbbq_apply: upload k + 1 (upload stream) | kernel k | download k - 1 (download stream)
+    int64_t k = 0;
+    auto pipelined = [&]() -> int {
+        for (int64_t lo = 0; lo < n; lo += (int64_t)slab, ++k) {
+            const int b = (int)(k & 1);
+            const int64_t m = std::min<int64_t>((int64_t)slab, n - lo);
+            int r2 = stage_out(b);
+            if (r2) return r2;
+            stage_in(b, lo, m);
+            r2 = upload(b, m, c->stage_stream);
+            if (r2) return r2;
+            HIPCHK(hipEventRecord(c->stage_up[b], c->stage_stream));
+            HIPCHK(hipStreamWaitEvent(c->stream, c->stage_up[b], 0));
+            r2 = launch(b, m);
+            if (r2) return r2;
+            HIPCHK(hipEventRecord(c->stage_used[b], c->stream));
+            HIPCHK(hipStreamWaitEvent(c->stage_down_stream, c->stage_used[b], 0));
+            HIPCHK(hipMemcpyAsync((uint8_t*)c->stage_host[b] + o_out, (uint8_t*)c->stage_dev[b] + o_out, (size_t)m * pitch, hipMemcpyDeviceToHost, c->stage_down_stream));
+            HIPCHK(hipEventRecord(c->stage_down[b], c->stage_down_stream));
+            pending[b] = {lo, m};
+        }
+        return KBBQ_OK;
+    };
+    rc = pipelined();
+    if (rc) return stage_drain(c, rc);
+    rc = kbbq_ctx_status(c, nullptr);
+    if (rc) {
+        // the status words hold the smallest index of every kind over all slabs: the slabs again, one by one (first_offender),
+        // with the offending alignment's index in the whole input handed back
+        (void)stage_drain(c, rc);
+        for (int64_t lo = 0; lo < n; lo += (int64_t)slab) {
+            const int64_t m = std::min<int64_t>((int64_t)slab, n - lo);
+            stage_in(0, lo, m);
+            int r2 = upload(0, m, c->stream);
+            if (!r2) r2 = launch(0, m);
+            if (r2) return r2;
+            int64_t idx = -1;
+            r2 = kbbq_ctx_status(c, &idx);
+            if (r2) {
+                if (idx < 0) return r2;
+                if (bad_read) *bad_read = lo + idx;
+                const std::string what = g_err;
+                const size_t colon = what.find(": ");
+                return fail(r2, "read %lld%s", (long long)(lo + idx), colon == std::string::npos ? "" : what.c_str() + colon);
+            }
+        }
+        return fail(KBBQ_E_HIP, "kbbq_apply_aligned: a status reported by the pipelined run did not reproduce slab by slab");
+    }
+    for (int b = 0; b < 2; ++b) { rc = stage_out((int)((k + b) & 1)); if (rc) return stage_drain(c, rc); }
     return KBBQ_OK;
 }
 

@@ -516,6 +516,47 @@ int kbbq_sam_text(const kbbq_sam* f, int what, int64_t i, const char** p, int64_
     return KBBQ_OK;
 }
 
+// applybqsr's output: every alignment line as read, its QUAL field replaced by the new qualities (row r of qplane, the field's own
+// length) and, with set_oq, "\tOQ:Z:<QUAL as read>" appended to a record that has no OQ tag -- GATK keeps an existing one.  Two
+// passes in parallel: the size of every line, then every line at its offset.
+int kbbq_sam_render(const kbbq_sam* f, int64_t first, int64_t n, const uint8_t* qplane, int pitch, int set_oq,
+                    uint8_t* out, size_t cap, size_t* used)
+{
+    if (!f || !used || (n > 0 && !qplane)) return kbbq_set_error_(KBBQ_E_ARG, "kbbq_sam_render: NULL argument");
+    if (first < 0 || n < 0 || first + n > (int64_t)f->line0.size() || pitch <= 0)
+        return kbbq_set_error_(KBBQ_E_ARG, "kbbq_sam_render: bad range / pitch");
+    auto star = [&](int64_t i) { return f->qual_len[i] == 1 && f->buf[f->qual0[i]] == '*'; };
+    auto adds_oq = [&](int64_t i) { return set_oq && !f->oq_len[i] && !star(i); };
+    for (int64_t r = 0; r < n; ++r)
+        if (!star(first + r) && f->qual_len[first + r] > (uint32_t)pitch)
+            return kbbq_set_error_(KBBQ_E_ARG, "kbbq_sam_render: a QUAL field is wider than the plane's pitch");
+    std::vector<size_t> at((size_t)n + 1, 0);
+    for (int64_t r = 0; r < n; ++r) {
+        const int64_t i = first + r;
+        at[(size_t)r + 1] = at[(size_t)r] + f->linelen[i] + 1 + (adds_oq(i) ? 6 + (size_t)f->qual_len[i] : 0);
+    }
+    *used = at[(size_t)n];
+    if (!out) return KBBQ_OK;
+    if (cap < at[(size_t)n]) return kbbq_set_error_(KBBQ_E_ARG, "kbbq_sam_render: output buffer too small");
+    par_for(n, threads_for(at[(size_t)n]), [&](int64_t lo, int64_t hi) {
+        for (int64_t r = lo; r < hi; ++r) {
+            const int64_t i = first + r;
+            const uint8_t* line = f->buf + f->line0[i];
+            uint8_t* o = out + at[(size_t)r];
+            memcpy(o, line, f->linelen[i]);
+            if (!star(i)) memcpy(o + (f->qual0[i] - f->line0[i]), qplane + (size_t)r * pitch, f->qual_len[i]);
+            o += f->linelen[i];
+            if (adds_oq(i)) {
+                memcpy(o, "\tOQ:Z:", 6);
+                memcpy(o + 6, f->buf + f->qual0[i], f->qual_len[i]);
+                o += 6 + f->qual_len[i];
+            }
+            *o = '\n';
+        }
+    });
+    return KBBQ_OK;
+}
+
 // benchmark.py:102-124: FASTQ reads are matched to alignments by name -- the FASTQ name up to its first '_'
 // against QNAME + "/1" | "/2" (second-in-pair flag); of several alignments with one name the LAST wins (a dict
 // in the reference).  idx[i] = alignment of FASTQ read i, or -1 (the reference's KeyError).

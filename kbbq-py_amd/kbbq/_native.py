@@ -23,6 +23,7 @@ KBBQ_E_NAME = -6
 KBBQ_E_LUT = -7
 KBBQ_E_MEANQ = -8
 APPLY_CHECKED, APPLY_FAST = 0, 1
+ALIGNED_LUT, ALIGNED_F64 = 0, 1
 ROWS_PAIRS, ROWS_NIBBLES, ROWS_TWINS = 1, 2, 4
 
 NQ = 43
@@ -72,6 +73,8 @@ PROTOTYPES = {
     'kbbq_apply_dev': (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _vp, _i, _vp]),
     'kbbq_apply': (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _i,
                         _vp, _vp, _vp, _vp, _vp, _vp]),
+    'kbbq_apply_aligned_dev': (_i, [_vp] * 5 + [_i64, _i, _i, _i, _i, _i, _vp, _i, _vp]),
+    'kbbq_apply_aligned': (_i, [_vp] * 5 + [_i64, _i, _i, _i, _i, _i, _vp, _sz, _i, _vp, _c.POINTER(_i64)]),
     'kbbq_delta_q_dev': (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
     'kbbq_combiln_host': (_i, [_vp, _vp, _i64, _vp, _i]),
     'kbbq_solve_prep_host': (_i, [_vp, _i, _i, _vp, _vp, _i]),
@@ -122,6 +125,7 @@ PROTOTYPES = {
     'kbbq_text_close': (_i, [_vp]),
     'kbbq_sam_fill': (_i, [_vp, _i64, _i64, _i, _i, _vp]),
     'kbbq_sam_text': (_i, [_vp, _i, _i64, _vp, _vp]),
+    'kbbq_sam_render': (_i, [_vp, _i64, _i64, _vp, _i, _i, _vp, _sz, _c.POINTER(_sz)]),
     'kbbq_sam_match_fastq': (_i, [_vp, _vp, _vp]),
     'kbbq_canonical_reads_dev': (_i, [_vp] * 9 + [_i64, _i, _i, _i, _i] + [_vp] * 4),
     'kbbq_canonical_reads_rows_dev': (_i, [_vp] * 9 + [_i64, _i, _i, _i, _i, _i] + [_vp] * 4),

@@ -3,7 +3,9 @@ kbbq.gatk.applybqsr -- get_delta_qs is on the hot path (reference
 kbbq/gatk/applybqsr.py:80-103); table_to_vectors (:14-44) turns a stored GATK report back
 into the nine model vectors.  The per-read ApplyBQSR emulation on
 aligned reads (:46-78) is host NumPy, one read at a time, as in the reference (it has no batch
-caller there; reads come from kbbq.aln or pysam).
+caller there; reads come from kbbq.aln or pysam).  recalibrate_alignments is the batch form on the GPU (every alignment of
+an aln.AlignmentFile through kbbq_apply_aligned: csrc/kbbq_apply_aligned.h) and apply_report the report -> SAM flow of the
+`kbbq applybqsr` command.
 """
 import numpy as np
 
@@ -131,3 +133,235 @@ def recalibrate_bamread(read, meanq, globaldeltaq, qscoredeltaq, positiondeltaq,
                   + positiondeltaq[rg, q, cycle]).astype(np.int_)
     return out
 
+
+
+# ---- the batch path: every alignment of a file on the GPU -------------------------------------------------------------------
+
+LAST_RUN = {}                  # what the last recalibrate_alignments / write_alignments call did: model form, alignments
+_ROWS = 1 << 20                # alignments per host slab (planes of SEQ / QUAL / OQ / output)
+_MAX_RG = 4096                 # read groups the kernel's row word holds
+
+
+def _model(meanq, rgdq, qdq, posdq, dndq, minscore):
+    """The five model arrays -> (mode, host blob, R, Qt, S2) for kbbq_apply_aligned.  An integer model is kbbq_build_lut's blob,
+    as the FASTQ path uses it.  A float model (a report's EstimatedQReported, float deltas) is folded into the same integer rows
+    only when that is proven exact: for every (rg, q, context, cycle) cell, trunc((base + dinuc) + pos) -- the reference's float64
+    sum, base = meanq + rgdq + qdq -- must equal cycle entry + context entry.  Otherwise the kernel sums the float64 rows itself."""
+    from .. import _native as N
+    meanq, rgdq, qdq, posdq, dndq = (np.asarray(x) for x in (meanq, rgdq, qdq, posdq, dndq))
+    R, Qt = qdq.shape
+    S2, D = posdq.shape[2], dndq.shape[2]
+    if D not in (16, 17) or meanq.shape != (R,) or rgdq.shape != (R,) or posdq.shape[:2] != (R, Qt) or dndq.shape[:2] != (R, Qt):
+        raise ValueError('model arrays of inconsistent shapes')
+    if R > _MAX_RG:
+        raise ValueError('at most %d read groups' % _MAX_RG)
+    if D == 16:                                                  # index -1 aliases the last column, as in the reference
+        dndq = np.concatenate([dndq, dndq[..., 15:16]], axis=-1)
+    lib = N.load()
+    integer = all(x.dtype.kind in 'iub' for x in (meanq, rgdq, qdq, posdq, dndq))
+    if integer and Qt <= 95:
+        blob = np.zeros((lib.kbbq_lut_bytes(R, Qt, S2) + 15) // 16 * 16, dtype=np.uint8)
+        args = [np.ascontiguousarray(x, dtype=np.int64) for x in (meanq, rgdq, qdq, posdq, dndq)]
+        flags = __import__('ctypes').c_int(0)
+        rc = lib.kbbq_build_lut(R, Qt, S2, 17, minscore, *[N.ptr(a) for a in args], N.ptr(blob), __import__('ctypes').byref(flags))
+        if rc == N.KBBQ_OK:
+            return N.ALIGNED_LUT, blob, R, Qt, S2
+        if rc != N.KBBQ_E_RANGE:                                 # (an entry beyond int16: the float64 rows below hold it exactly)
+            N.check(rc)
+    base = meanq[:, None] + rgdq[:, None] + qdq                 # [R, Qt], summed as the reference sums it
+    dn = dndq.astype(np.result_type(base, dndq))
+    if not integer and Qt <= 95:
+        rs = lib.kbbq_lut_row_stride(S2)
+        lut = np.zeros((R, Qt, rs), dtype=np.int16)
+        exact = True
+        for r in range(R):
+            full = np.trunc((base[r][:, None, None] + dn[r][:, :, None]) + posdq[r][:, None, :])      # [Qt, 17, S2]
+            cyc = full[:, 16, :]
+            ctx = full[:, :, 0] - cyc[:, :1]
+            if (not np.array_equal(full, cyc[:, None, :] + ctx[:, :, None]) or np.abs(cyc).max() > 32767
+                    or np.abs(ctx).max() > 32767):
+                exact = False
+                break
+            lut[r, :, :S2] = cyc
+            five = np.full((Qt, 5, 5), 16)
+            five[:, :4, :4] = np.arange(16).reshape(4, 4)
+            lut[r, :, S2:S2 + 25] = np.take_along_axis(ctx, five.reshape(Qt, 25), axis=1)
+        if exact:
+            return N.ALIGNED_LUT, lut.view(np.uint8).reshape(-1), R, Qt, S2
+    if Qt > 223:
+        raise ValueError('at most 223 quality levels')
+    rows = np.concatenate([base[..., None].astype(np.float64), dn.astype(np.float64), posdq.astype(np.float64)], axis=-1)
+    return N.ALIGNED_F64, np.ascontiguousarray(rows).view(np.uint8).reshape(-1), R, Qt, S2
+
+
+def _rows(bam, rg_to_int, R, use_oq, lo, hi):
+    """Row words and bookkeeping of alignments [lo, hi) (include/kbbq_hip.h, kbbq_apply_aligned).  A record whose source
+    qualities are '*' or absent passes through (length 0 here; its QUAL as read goes out); a record without an OQ tag takes
+    its context from the source plane.  KeyError for a recalibrated record whose RG is missing or unknown, ValueError for one
+    whose SEQ, QUAL and OQ lengths disagree -- each with .read_index."""
+    b = bam.batch()
+    sl = slice(lo, hi)
+    L = b.qlen[sl].astype(np.int64)
+    qual_len, oq_len = b.qual_len[sl].astype(np.int64), b.oq_len[sl].astype(np.int64)
+    has_oq = oq_len >= 0
+    src_len = oq_len if use_oq else qual_len
+    passthrough = (~has_oq) if use_oq else (qual_len == 0)
+    passthrough |= L == 0
+    names = b.rg_ids
+    model_rg = np.array([rg_to_int.get(x, -1) for x in names] + [-1, -1], dtype=np.int64)      # [-2] / [-1]: unknown / missing
+    rg = model_rg[b.rg[sl]]
+    bad_rg = ~passthrough & (rg < 0)
+    if (~passthrough & (rg >= R)).any():
+        k = int(np.flatnonzero(~passthrough & (rg >= R))[0])
+        exc = IndexError('index %d is out of bounds for axis 0 with size %d' % (int(rg[k]), R))
+        exc.read_index = lo + k
+        raise exc
+    bad_len = ~passthrough & ((src_len != L) | (has_oq & (oq_len != L)))
+    first_bad = min([int(np.flatnonzero(x)[0]) for x in (bad_rg, bad_len) if x.any()] or [hi - lo])
+    if first_bad < hi - lo:                                  # (the error, and how many records before it can still run)
+        k = first_bad
+        if bad_len[k]:
+            exc = ValueError('alignment %d: SEQ, QUAL and OQ lengths differ' % (lo + k))
+        else:
+            tag = b.rg[lo + k]
+            exc = KeyError("tag 'RG' not present" if tag == -1 else names[tag] if tag >= 0
+                           else b.line(lo + k).split('RG:Z:')[1].split('\t')[0])
+        exc.read_index = lo + k
+        return k, exc
+    flag = b.flag[sl].astype(np.uint32)
+    meta = (np.where(passthrough, 0, L).astype(np.uint32) | (np.maximum(rg, 0).astype(np.uint32) << 16)
+            | (np.uint32(1 << 28) if use_oq else np.uint32(0)) | (has_oq.astype(np.uint32) << 29)
+            | (((flag & 16) != 0).astype(np.uint32) << 30) | (((flag & 128) != 0).astype(np.uint32) << 31))
+    return meta, passthrough
+
+
+def _recalibrated_slabs(bam, model, rg_to_int, use_oq, minscore, lo, hi):
+    """(first alignment, count, output plane [count, pitch] of QUAL characters, lengths) for slabs of alignments [lo, hi): the
+    kernel's new qualities + 33, pass-through records holding their QUAL as read."""
+    import ctypes
+    from .. import _device as dev
+    from .. import _native as N
+    mode, blob, R, Qt, S2 = model
+    b = bam.batch()
+    pitch = max(16, (int(b.maxlen) + 15) // 16 * 16)
+    ctx = None
+    for first in range(lo, hi, _ROWS):
+        m = min(_ROWS, hi - first)
+        rows = _rows(bam, rg_to_int, R, use_oq, first, first + m)
+        stop = None
+        if isinstance(rows[1], Exception):                   # a record the reference would reject: the ones before it still run
+            k, stop = rows
+            if k > 0:
+                rows = _rows(bam, rg_to_int, R, use_oq, first, first + k)
+            m = k
+        if m > 0:
+            meta, passthrough = rows
+            seq = b.plane(0, pitch, first, m)
+            has_oq = bool((b.oq_len[first:first + m] >= 0).any())
+            oq = b.plane(2, pitch, first, m) if (use_oq or has_oq) else None
+            qual = b.plane(1, pitch, first, m) if (not use_oq or passthrough.any()) else None
+            out = np.empty((m, pitch), dtype=np.uint8)
+            if ctx is None:
+                ctx = dev.context()
+            bad = ctypes.c_int64(-1)
+            rc = N.load().kbbq_apply_aligned(ctx.handle, N.ptr(seq), N.ptr(qual if not use_oq else oq), N.ptr(oq), N.ptr(meta),
+                                             m, pitch, R, Qt, S2, minscore, N.ptr(blob), blob.nbytes, mode, N.ptr(out),
+                                             ctypes.byref(bad))
+            try:
+                N.check(rc)
+            except Exception as exc:
+                exc.read_index = first + int(bad.value) if bad.value >= 0 else first
+                raise
+            if passthrough.any():
+                out[passthrough] = qual[passthrough]
+            lens = np.where(passthrough, b.qual_len[first:first + m], b.qlen[first:first + m]).astype(np.int64)
+            yield first, m, out, lens
+        if stop is not None:
+            raise stop
+
+
+def recalibrate_alignments(bam, meanq, rgdq, qdq, posdq, dndq, rg_to_int, use_oq=True, minscore=6):
+    """New qualities of every alignment of an aln.AlignmentFile (SAM or BAM) on the GPU (kbbq_apply_aligned), as one flat int
+    array and offsets [n + 1]: alignment i's are quals[offsets[i]:offsets[i + 1]], equal to recalibrate_bamread(read_i, ...)
+    for every read the reference can process.  The same exceptions as the per-read function (IndexError, TypeError, KeyError),
+    for the first offending alignment, with .read_index.  Beyond the reference: a record without an OQ tag takes its context from
+    the source qualities (the reference: KeyError), and one whose source qualities are '*' or absent is passed through (its QUAL as
+    read).  New qualities outside -33..222 cannot be written as SAM: ValueError, as on the FASTQ path."""
+    model = _model(meanq, rgdq, qdq, posdq, dndq, minscore)
+    quals, lens = [], []
+    n = len(bam)
+    for first, m, out, ln in _recalibrated_slabs(bam, model, rg_to_int, use_oq, minscore, 0, n):
+        quals.append(out[np.arange(out.shape[1]) < ln[:, None]].astype(np.int_) - 33)
+        lens.append(ln)
+    LAST_RUN.clear()
+    LAST_RUN.update(mode='lut' if model[0] == 0 else 'f64', alignments=n)
+    lens = np.concatenate(lens) if lens else np.zeros(0, np.int64)
+    offsets = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(lens, out=offsets[1:])
+    return (np.concatenate(quals) if quals else np.zeros(0, np.int_)), offsets
+
+
+def write_alignments(bam, meanq, rgdq, qdq, posdq, dndq, rg_to_int, sink, use_oq=False, set_oq=False, minscore=6,
+                     rows=None, header=True):
+    """Recalibrated SAM text of alignments rows = (lo, hi) (all by default) to the binary file `sink`: the header lines as read
+    (header=True), then every alignment line as read with its QUAL replaced and, with set_oq, an OQ tag holding the QUAL as
+    read added where there is none (csrc/sam_host.cpp kbbq_sam_render)."""
+    import ctypes
+    from .. import _native as N
+    from .._egress import _Reserve
+    lib = N.load()
+    b = bam.batch()
+    lo, hi = (0, len(bam)) if rows is None else rows
+    model = _model(meanq, rgdq, qdq, posdq, dndq, minscore)
+    reserve = _Reserve(sink)
+    if header:
+        text = ''.join(line + '\n' for line in bam.header).encode('latin-1')
+        reserve.ahead(len(text))
+        sink.write(text)
+    for first, m, out, _ in _recalibrated_slabs(bam, model, rg_to_int, use_oq, minscore, lo, hi):
+        need = ctypes.c_size_t(0)
+        N.check(lib.kbbq_sam_render(b._native, first, m, N.ptr(out), out.shape[1], int(bool(set_oq)), None, 0, ctypes.byref(need)))
+        buf = np.empty(max(need.value, 1), dtype=np.uint8)
+        N.check(lib.kbbq_sam_render(b._native, first, m, N.ptr(out), out.shape[1], int(bool(set_oq)), N.ptr(buf), buf.nbytes,
+                                    ctypes.byref(need)))
+        reserve.ahead(need.value)
+        sink.write(memoryview(buf)[:need.value])
+    LAST_RUN.clear()
+    LAST_RUN.update(mode='lut' if model[0] == 0 else 'f64', alignments=hi - lo)
+
+
+def report_model(bam, report_path):
+    """A stored GATK report -> (meanq, rgdq, qdq, posdq, dndq, rg_to_int) for the read groups of bam's header (reference
+    tests/test_gatk_applybqsr.py:123-134: the report names read groups by their PU)."""
+    from .. import recaltable
+    rg_to_pu = utils.get_rg_to_pu(bam)
+    rg_to_int = {r: i for i, r in enumerate(rg_to_pu)}
+    report = recaltable.RecalibrationReport.fromfile(report_path)
+    meanq, *vectors = table_to_vectors(report, list(rg_to_pu.values()))
+    return (meanq,) + tuple(get_delta_qs(meanq, *vectors)) + (rg_to_int,)
+
+
+def apply_report(bam, report_path, use_oq=False, set_oq=False, output=None):
+    """`kbbq applybqsr`: report -> model (table_to_vectors, get_delta_qs on the device) -> kbbq_apply_aligned -> SAM text, to
+    `output` or stdout.  Under torch.distributed.run every rank takes parallel.shard_range of the alignments and writes
+    output.rankNNNN, the header in rank 0's file only, so that the files concatenated in rank order are the single-process
+    output.  BAM output is not written: an output name ending in .bam is refused."""
+    import sys
+    from .. import aln, parallel
+    if output is not None and str(output).lower().endswith('.bam'):
+        raise ValueError('applybqsr writes SAM text; BAM output (%s) is not supported' % output)
+    if not isinstance(bam, aln.AlignmentFile):
+        bam = aln.AlignmentFile(bam)
+    world, rank = parallel.world_rank()
+    if world > 1 and output is None:
+        raise ValueError('several ranks need -o: every rank writes OUTPUT.rankNNNN')
+    *model, rg_to_int = report_model(bam, report_path)
+    lo, hi = parallel.shard_range(len(bam), rank, world) if world > 1 else (0, len(bam))
+    kw = dict(use_oq=use_oq, set_oq=set_oq, rows=(lo, hi), header=rank == 0)
+    if output is None:
+        sys.stdout.flush()
+        write_alignments(bam, *model, rg_to_int, sys.stdout.buffer, **kw)
+        sys.stdout.flush()
+        return
+    with open(output if world == 1 else '%s.rank%04d' % (output, rank), 'wb') as sink:
+        write_alignments(bam, *model, rg_to_int, sink, **kw)

@@ -2,6 +2,8 @@
 """
 kbbq command line -- the `recalibrate` sub-command of the reference CLI
 and the `benchmark` sub-command (reference kbbq/main.py:26-89).  `plot` is out of scope here.
+`bqsr` (alignments -> GATK report) and `applybqsr` (report -> recalibrated SAM) are this build's own: the reference has the
+functions (kbbq/gatk/bqsr.py, applybqsr.py) but no command for them.
 """
 import argparse
 
@@ -37,7 +39,21 @@ def benchmark(args):
                   label=args.label, use_oq=args.use_oq, bedfh=args.bedfile)
 
 
-def main():
+def applybqsr(args):
+    from . import parallel
+    from .gatk import applybqsr as _apply
+    parallel.init_from_env()          # one process per GPU under torch.distributed.run; no-op otherwise
+    _apply.apply_report(args.bam, args.gatkreport, use_oq=args.use_oq, set_oq=args.set_oq, output=args.output)
+
+
+def bqsr(args):
+    from . import benchmark as _bm
+    from . import aln
+    from .gatk import bqsr as _bqsr
+    _bqsr.bam_to_report(aln.AlignmentFile(args.bam), args.reference, _bm.get_var_sites(args.vcf)).write(args.gatkreport)
+
+
+def main(argv=None):
     parser = argparse.ArgumentParser(description='K-mer Based Base Quality score recalibration (MI355X build)')
     parser.add_argument('-v', '--version', action='version', version=__version__)
     sub = parser.add_subparsers(title='command', description='valid commands')
@@ -75,7 +91,24 @@ def main():
                     help='BED file of confident regions. Sites outside the given regions will be skipped.')
     bp.set_defaults(command=benchmark)
 
-    args = parser.parse_args()
+    ap = sub.add_parser('applybqsr', description='Recalibrate alignments with a GATK recalibration report (SAM output)')
+    ap.add_argument('-b', '--bam', required=True, help='SAM or BAM file to recalibrate')
+    ap.add_argument('-g', '--gatkreport', required=True, help='GATK recalibration report (kbbq bqsr, GATK BaseRecalibrator)')
+    ap.add_argument('-o', '--output', default=None,
+                    help='Write the recalibrated SAM to this file instead of stdout (SAM text only; a .bam name is refused); '
+                         'under torch.distributed.run every rank writes FILE.rankNNNN, to be concatenated in rank order.')
+    ap.add_argument('-u', '--use-oq', action='store_true', help='Recalibrate the OQ tag\'s qualities instead of QUAL.')
+    ap.add_argument('-s', '--set-oq', action='store_true', help="Keep the qualities as read in an 'OQ' tag where there is none.")
+    ap.set_defaults(command=applybqsr)
+
+    qp = sub.add_parser('bqsr', description='Build a GATK recalibration report from alignments (BaseRecalibrator)')
+    qp.add_argument('-b', '--bam', required=True, help='SAM or BAM file (qualities from the OQ tag)')
+    qp.add_argument('-r', '--reference', required=True, help='FASTA file containing the reference genome')
+    qp.add_argument('-v', '--vcf', required=True, help='VCF file of known variable sites (skipped)')
+    qp.add_argument('-g', '--gatkreport', required=True, help='Write the report to this file')
+    qp.set_defaults(command=bqsr)
+
+    args = parser.parse_args(argv)
     args.command(args)
 
 
