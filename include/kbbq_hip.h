@@ -331,7 +331,7 @@ int    kbbq_solve_dev(kbbq_ctx* ctx, const int64_t* d_tables, int R, int S2, int
  * Implementation (csrc/kbbq_aligned_kernels.h): the first four CIGAR operations of every read are copied into one
  * 16-byte record per read (context-owned scratch), a lane walks them in registers and fetches the one reference
  * window its chunk needs; chunks on an operation boundary, reads with more operations and malformed input take the
- * sequential walk.  KBBQ_K4=v1 in the environment selects the first form (A/B timing).          */
+ * sequential walk.                                                                             */
 int kbbq_find_errors_dev(kbbq_ctx* ctx, const uint8_t* d_seq, const uint32_t* d_len, int64_t nreads, int pitch,
                          const int64_t* d_ref_start, const int32_t* d_ref_len,
                          const uint32_t* d_cig_off, const uint32_t* d_cig_n, const uint32_t* d_cigar,

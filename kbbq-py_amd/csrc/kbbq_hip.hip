@@ -31,6 +31,9 @@ static int fail(int code, const char* fmt, ...)
     return code;
 }
 
+// an environment switch that a test or bench.py sets: is it `value`?
+static bool env_is(const char* name, const char* value) { const char* v = getenv(name); return v && !strcmp(v, value); }
+
 // used by fastq_host.cpp
 int kbbq_set_error_(int code, const char* msg) { g_err = msg ? msg : ""; return code; }
 
@@ -57,7 +60,7 @@ struct kbbq_ctx {
     size_t ops4_bytes = 0;
     void* d_tally = nullptr;          // kbbq_tally_aligned_dev: [count | flags words of the reads | rows K4 still has to look at] (grown on demand)
     size_t tally_bytes = 0;
-    // kbbq_accumulate / kbbq_apply (host buffers): two page-locked staging slabs and their device twins, a copy stream and
+    // host-buffer entry points (stage_run): two page-locked staging slabs and their device twins, a copy stream and
     // the events that order host copy -> upload -> kernel -> download slab by slab (grown on demand, kept for the next call)
     void* stage_host[2] = {nullptr, nullptr}; void* stage_dev[2] = {nullptr, nullptr}; size_t stage_bytes = 0;
     hipStream_t stage_stream = nullptr;      // uploads
@@ -73,6 +76,14 @@ struct kbbq_ctx {
 };
 
 #define KBBQ_NSTATUS 8
+
+// Tuned launch constants (measured in earlier rounds: DESIGN.md, profiles/)
+constexpr size_t K2T_ROW_LUT_MAX = 52 << 10;  // short-lived K2 on one-read-per-row planes: a read group's LUT of up to 52 KB
+constexpr int K2V3_FRONTS = 8;               // sequential fronts of the persistent K2 traversal (K2v3Params::parts)
+constexpr int K2T_XCD_TILES = 1;             // short-lived K2: every XCD walks a contiguous eighth of the planes (K2tParams::xcd_tiles)
+constexpr int K2T_XCD = 8;                   // k2t_order: the read groups' workgroups of one position on the same XCD
+constexpr int K7_FRONTS = 8;                 // sequential fronts of k7_lay_out (LayOutParams::parts)
+constexpr int TALLY_K4_SHARE = 8;            // kbbq_tally_aligned_dev: K4's grid is sized for 1 / 8 of the reads
 static const u64 ST_INIT[KBBQ_NSTATUS] = {~0ull, ~0ull, ~0ull, ~0ull, ~0ull, ~0ull, ~0ull, ~0ull};
 
 extern "C" {
@@ -133,41 +144,28 @@ int kbbq_ctx_create(int device, kbbq_ctx** out)
     if (e != hipSuccess) { (void)hipFree(c->d_status); (void)hipStreamDestroy(c->own_stream); delete c; return fail(KBBQ_E_HIP, "hipMemcpy(status): %s", hipGetErrorString(e)); }
     lap("hipMalloc + hipMemcpy");
     // allow the full 160 KiB of LDS as dynamic shared memory
-    (void)hipFuncSetAttribute((const void*)k1_accumulate<false>, hipFuncAttributeMaxDynamicSharedMemorySize, c->lds_bytes);
-    lap("first hipFuncSetAttribute");
-    (void)hipFuncSetAttribute((const void*)k1_accumulate<true>, hipFuncAttributeMaxDynamicSharedMemorySize, c->lds_bytes);
-    (void)hipFuncSetAttribute((const void*)k1v3_accumulate<false>, hipFuncAttributeMaxDynamicSharedMemorySize, c->lds_bytes);
-    (void)hipFuncSetAttribute((const void*)k1v3_accumulate<true>, hipFuncAttributeMaxDynamicSharedMemorySize, c->lds_bytes);
-    (void)hipFuncSetAttribute((const void*)(k1v3_accumulate<false, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, c->lds_bytes);
-    (void)hipFuncSetAttribute((const void*)(k1v3_accumulate<true, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, c->lds_bytes);
-    (void)hipFuncSetAttribute((const void*)(k1v3_accumulate<false, K1V3_DNREP, true>), hipFuncAttributeMaxDynamicSharedMemorySize, c->lds_bytes);
-    (void)hipFuncSetAttribute((const void*)(k1v3_accumulate<true, K1V3_DNREP, true>), hipFuncAttributeMaxDynamicSharedMemorySize, c->lds_bytes);
-    (void)hipFuncSetAttribute((const void*)(k1v3_accumulate<false, 8, true>), hipFuncAttributeMaxDynamicSharedMemorySize, c->lds_bytes);
-    (void)hipFuncSetAttribute((const void*)(k1v3_accumulate<true, 8, true>), hipFuncAttributeMaxDynamicSharedMemorySize, c->lds_bytes);
-#define KBBQ_KM_ATTR(KJ_) \
-    (void)hipFuncSetAttribute((const void*)(k1v3_accumulate<false, K1V3_DNREP, true, KJ_>), hipFuncAttributeMaxDynamicSharedMemorySize, c->lds_bytes); \
-    (void)hipFuncSetAttribute((const void*)(k1v3_accumulate<true, K1V3_DNREP, true, KJ_>), hipFuncAttributeMaxDynamicSharedMemorySize, c->lds_bytes);
-    KBBQ_KM_ATTR(13) KBBQ_KM_ATTR(19)
-#undef KBBQ_KM_ATTR
-    (void)hipFuncSetAttribute((const void*)(k2v3_apply<false>), hipFuncAttributeMaxDynamicSharedMemorySize, c->lds_bytes);
-    (void)hipFuncSetAttribute((const void*)(k2v3_apply<true>), hipFuncAttributeMaxDynamicSharedMemorySize, c->lds_bytes);
-    (void)hipFuncSetAttribute((const void*)k2t_apply<true>, hipFuncAttributeMaxDynamicSharedMemorySize, c->lds_bytes);
-    (void)hipFuncSetAttribute((const void*)k2t_apply<false>, hipFuncAttributeMaxDynamicSharedMemorySize, c->lds_bytes);
-    (void)hipFuncSetAttribute((const void*)k2t_bands, hipFuncAttributeMaxDynamicSharedMemorySize, c->lds_bytes);
-    (void)hipFuncSetAttribute((const void*)(k1v3_aligned<false, K1V3_DNREP>), hipFuncAttributeMaxDynamicSharedMemorySize, c->lds_bytes);
-    (void)hipFuncSetAttribute((const void*)(k1v3_aligned<true, K1V3_DNREP>), hipFuncAttributeMaxDynamicSharedMemorySize, c->lds_bytes);
-    (void)hipFuncSetAttribute((const void*)(k1v3_aligned<false, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, c->lds_bytes);
-    (void)hipFuncSetAttribute((const void*)(k1v3_aligned<true, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, c->lds_bytes);
-    (void)hipFuncSetAttribute((const void*)(k1v3_aligned_ref<false, K1V3_DNREP>), hipFuncAttributeMaxDynamicSharedMemorySize, c->lds_bytes);
-    (void)hipFuncSetAttribute((const void*)(k1v3_aligned_ref<true, K1V3_DNREP>), hipFuncAttributeMaxDynamicSharedMemorySize, c->lds_bytes);
-    (void)hipFuncSetAttribute((const void*)(k1v3_aligned_ref<false, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, c->lds_bytes);
-    (void)hipFuncSetAttribute((const void*)(k1v3_aligned_ref<true, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, c->lds_bytes);
-    (void)hipFuncSetAttribute((const void*)(k1v3_bands<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, c->lds_bytes);
-    (void)hipFuncSetAttribute((const void*)(k1v3_bands<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, c->lds_bytes);
-    (void)hipFuncSetAttribute((const void*)(k1v3_bands<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, c->lds_bytes);
-    (void)hipFuncSetAttribute((const void*)(k1v3_bands<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, c->lds_bytes);
-    (void)hipFuncSetAttribute((const void*)k2_apply<int16_t, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, c->lds_bytes);
-    (void)hipFuncSetAttribute((const void*)k2_apply<int8_t, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, c->lds_bytes);
+    static const void* const full_lds[] = {
+        (const void*)k1_accumulate<false>, (const void*)k1_accumulate<true>,
+        (const void*)k1v3_accumulate<false>, (const void*)k1v3_accumulate<true>,
+        (const void*)(k1v3_accumulate<false, 8>), (const void*)(k1v3_accumulate<true, 8>),
+        (const void*)(k1v3_accumulate<false, K1V3_DNREP, true>), (const void*)(k1v3_accumulate<true, K1V3_DNREP, true>),
+        (const void*)(k1v3_accumulate<false, 8, true>), (const void*)(k1v3_accumulate<true, 8, true>),
+        (const void*)(k1v3_accumulate<false, K1V3_DNREP, true, 13>), (const void*)(k1v3_accumulate<true, K1V3_DNREP, true, 13>),
+        (const void*)(k1v3_accumulate<false, K1V3_DNREP, true, 19>), (const void*)(k1v3_accumulate<true, K1V3_DNREP, true, 19>),
+        (const void*)(k2v3_apply<false>), (const void*)(k2v3_apply<true>),
+        (const void*)k2t_apply<true>, (const void*)k2t_apply<false>, (const void*)k2t_bands,
+        (const void*)(k1v3_aligned<false, K1V3_DNREP>), (const void*)(k1v3_aligned<true, K1V3_DNREP>),
+        (const void*)(k1v3_aligned<false, 8>), (const void*)(k1v3_aligned<true, 8>),
+        (const void*)(k1v3_aligned_ref<false, K1V3_DNREP>), (const void*)(k1v3_aligned_ref<true, K1V3_DNREP>),
+        (const void*)(k1v3_aligned_ref<false, 8>), (const void*)(k1v3_aligned_ref<true, 8>),
+        (const void*)(k1v3_bands<false, false>), (const void*)(k1v3_bands<true, false>),
+        (const void*)(k1v3_bands<false, true>), (const void*)(k1v3_bands<true, true>),
+        (const void*)k2_apply<int16_t, true, true>, (const void*)k2_apply<int8_t, true, false>,
+    };
+    for (size_t i = 0; i < sizeof full_lds / sizeof full_lds[0]; ++i) {
+        (void)hipFuncSetAttribute(full_lds[i], hipFuncAttributeMaxDynamicSharedMemorySize, c->lds_bytes);
+        if (i == 0) lap("first hipFuncSetAttribute");
+    }
     (void)hipGetLastError();
     lap("the other attributes");
     *out = c;
@@ -459,7 +457,7 @@ int kbbq_accumulate_dev(kbbq_ctx* c, const uint8_t* d_seq, const uint8_t* d_cseq
 
 // what accumulate_rows would launch (kernel parameters, LDS bytes, template variant): kbbq_accumulate_bands_dev collects
 // these for all length bands and launches them as ONE kernel
-struct K1Setup { K1v3Params q; int dn = 0; bool km = false; bool split = false; size_t lds = 0; int64_t iters = 0; int threads = K1V3_THREADS; };
+struct K1Setup { K1v3Params q; int dn = 0; bool km = false; bool split = false; size_t lds = 0; int64_t iters = 0; };
 static int accumulate_rows(kbbq_ctx* c, const char* who, const uint8_t* d_seq, const uint8_t* d_cseq, const uint8_t* d_qual,
                            const uint32_t* d_meta, int64_t nrows, int pitch, int pairs, int R, int S2, int minscore,
                            int dinuc_minscore, const int64_t* d_seg, int64_t* d_tables, bool* fits, int S_band = 0, int S_min = 0, int nib = 0,
@@ -490,13 +488,10 @@ int kbbq_accumulate_band_dev(kbbq_ctx* c, const uint8_t* d_seq, const uint8_t* d
 
     const int64_t nblocks = (nreads + 63) / 64;
     const bool split = dinuc_minscore > minscore;
-    const char* force = getenv("KBBQ_K1");              // "v1" forces the first kernel (A/B timing)
-    if (!(force && !strcmp(force, "v1"))) {
-        bool fits = false;
-        rc = accumulate_rows(c, "kbbq_accumulate_dev", d_seq, d_cseq, d_qual, d_meta, nreads, pitch, 0, R, S2, minscore,
-                             dinuc_minscore, nullptr, d_tables, &fits, S_band, S_min);
-        if (rc || fits) return rc;                      // launched (or a real error); otherwise the tables do not fit the LDS
-    }
+    bool fits = false;
+    rc = accumulate_rows(c, "kbbq_accumulate_dev", d_seq, d_cseq, d_qual, d_meta, nreads, pitch, 0, R, S2, minscore,
+                         dinuc_minscore, nullptr, d_tables, &fits, S_band, S_min);
+    if (rc || fits) return rc;                          // launched (or a real error); otherwise the tables do not fit the LDS
     K1Params p;
     p.seq = d_seq; p.cseq = d_cseq; p.qual = d_qual; p.meta = d_meta;
     p.nreads = nreads; p.pitch = pitch; p.cpr = pitch / 16; p.cpr_magic = magic_for(p.cpr);
@@ -598,18 +593,19 @@ int kbbq_build_lut(int R, int Qt, int S2, int D, int minscore, const int64_t* me
     return KBBQ_OK;
 }
 
-// K2 on one-read-per-row planes: when the rows are narrower than the tables' S2 columns, the LUT of the columns they
-// can reach (k3_fill_row_lut) in context-owned scratch, written on the launch stream in front of the apply kernel.
-// Returns the cycle width Sb the LUT was built for (S2: the blob's own full LUT is used, *lut untouched).
-static int narrowed_row_lut(kbbq_ctx* c, const void* d_lut_blob, int R, int Qt, int S2, int pitch, int minscore, const int8_t** lut)
+// K2 on one-read-per-row planes of this pitch: the cycle width Sb of the LUT, the columns such rows can reach
+// (KBBQ_K2_ROWLUT=0: the tables' full S2, A/B timing)
+static int row_lut_width(int pitch, int S2) { return env_is("KBBQ_K2_ROWLUT", "0") ? S2 : std::min(pitch, S2); }
+
+// ... when Sb < S2, that narrowed LUT (k3_fill_row_lut) in context-owned scratch, written on the launch stream in front of
+// the apply kernel (Sb == S2: the blob's own full LUT is used, *lut untouched).  False: no scratch for it.
+static bool narrowed_row_lut(kbbq_ctx* c, const void* d_lut_blob, int R, int Qt, int S2, int Sb, int minscore, const int8_t** lut)
 {
-    const char* off = getenv("KBBQ_K2_ROWLUT");                                    // "0": the full LUT (A/B timing)
-    const int Sb = std::min(pitch, S2);
-    if (Sb >= S2 || (off && !strcmp(off, "0"))) return S2;
+    if (Sb >= S2) return true;
     const size_t need = (size_t)R * (33 + Qt) * full_lut_row_bytes(Sb);
     if (c->rowlut_bytes < need) {
-        if (c->d_rowlut) { if (hipStreamSynchronize(c->stream) != hipSuccess) return S2; (void)hipFree(c->d_rowlut); c->d_rowlut = nullptr; c->rowlut_bytes = 0; }
-        if (hipMalloc(&c->d_rowlut, need) != hipSuccess) { c->d_rowlut = nullptr; return S2; }
+        if (c->d_rowlut) { if (hipStreamSynchronize(c->stream) != hipSuccess) return false; (void)hipFree(c->d_rowlut); c->d_rowlut = nullptr; c->rowlut_bytes = 0; }
+        if (hipMalloc(&c->d_rowlut, need) != hipSuccess) { c->d_rowlut = nullptr; return false; }
         c->rowlut_bytes = need;
     }
     RowLutParams f;
@@ -618,7 +614,7 @@ static int narrowed_row_lut(kbbq_ctx* c, const void* d_lut_blob, int R, int Qt, 
     f.out = reinterpret_cast<int8_t*>(c->d_rowlut);
     hipLaunchKernelGGL(k3_fill_row_lut, dim3((unsigned)(R * (33 + Qt))), dim3(256), 0, c->stream, f);
     *lut = f.out;
-    return Sb;
+    return true;
 }
 
 static int apply_rows(kbbq_ctx* c, const char* who, const uint8_t* d_seq, const uint8_t* d_qual, const uint32_t* d_meta,
@@ -640,37 +636,32 @@ int kbbq_apply_dev(kbbq_ctx* c, const uint8_t* d_seq, const uint8_t* d_qual, con
     if (nreads == 0) return KBBQ_OK;
     HIPCHK(hipSetDevice(c->device));
     const int64_t nblocks = (nreads + 63) / 64;
-    const char* force = getenv("KBBQ_K2");              // "v1" forces the first kernel (A/B timing)
 
     // the LUT of the columns rows of this pitch can reach (narrowed_row_lut): a band of short reads under wide tables
-    const int Sb0 = (getenv("KBBQ_K2_ROWLUT") && !strcmp(getenv("KBBQ_K2_ROWLUT"), "0")) ? S2 : std::min(pitch, S2);
-    const size_t full_bytes = (size_t)R * (33 + Qt) * full_lut_row_bytes(Sb0);
-    if (mode == KBBQ_APPLY_FAST && R == 1 && Qt == KQ && !(S2 & 1) && S2 <= 65534 && !(force && !strcmp(force, "v1"))) {
+    const int Sb = row_lut_width(pitch, S2);
+    const size_t full_bytes = (size_t)R * (33 + Qt) * full_lut_row_bytes(Sb);
+    if (mode == KBBQ_APPLY_FAST && R == 1 && Qt == KQ && !(S2 & 1) && S2 <= 65534) {
         // one read group, rows as a caller holds them (one character row per read): the short-lived kernel (kbbq_k2_tile.h) when
         // apply_rows' conditions for it hold -- it falls through to the persistent kernel itself otherwise.  What it cannot serve
         // (a foreign letter, q > 42, a read longer than the LUT) it reports as KBBQ_E_LUT: the caller's KBBQ_APPLY_CHECKED run
         // decides, as for a LUT that is not range-safe.
-        const char* tile = getenv("KBBQ_K2_TILE");
-        const char* tile_chars = getenv("KBBQ_K2_TILE_CHARS");
         const int cpr = pitch / 16;
-        const size_t rg_bytes = (size_t)(33 + KQ) * full_lut_row_bytes(Sb0);
-        if (!(tile && !strcmp(tile, "0")) && !(tile_chars && !strcmp(tile_chars, "0")) && cpr >= 2 && cpr <= 4096
-            && rg_bytes <= (size_t)(getenv("KBBQ_K2_TILE_LUT_KB") ? atoi(getenv("KBBQ_K2_TILE_LUT_KB")) : 52) << 10)
+        const size_t rg_bytes = (size_t)(33 + KQ) * full_lut_row_bytes(Sb);
+        if (!env_is("KBBQ_K2_TILE", "0") && !env_is("KBBQ_K2_TILE_CHARS", "0") && cpr >= 2 && cpr <= 4096 && rg_bytes <= K2T_ROW_LUT_MAX)
             return apply_rows(c, "kbbq_apply_dev", d_seq, d_qual, d_meta, nreads, pitch, 0, R, S2, minscore, d_lut, nullptr, nullptr, d_out, 0, nullptr);
     }
-    if (mode == KBBQ_APPLY_FAST && full_bytes <= (size_t)c->lds_bytes && !(force && !strcmp(force, "v1"))) {
+    if (mode == KBBQ_APPLY_FAST && full_bytes <= (size_t)c->lds_bytes) {
         K2v3Params q;
         q.seq = d_seq; q.qual = d_qual; q.meta = d_meta; q.nreads = nreads; q.pitch = pitch;
         q.cpr = pitch / 16; q.cpr_magic = magic_for(q.cpr);
         q.R = R; q.Qt = Qt; q.S2 = S2; q.minscore = minscore; q.qlo = 33u + (u32)minscore;
         q.lut16 = reinterpret_cast<const int16_t*>(d_lut); q.rs16 = lut_row_stride(S2);
         q.full = reinterpret_cast<const int8_t*>(d_lut) + lut_full_offset(R, Qt, S2);
-        const int Sb = narrowed_row_lut(c, d_lut, R, Qt, S2, pitch, minscore, &q.full);
-        if (Sb != Sb0) return fail(KBBQ_E_HIP, "kbbq_apply_dev: no scratch for the narrowed LUT");
+        if (!narrowed_row_lut(c, d_lut, R, Qt, S2, Sb, minscore, &q.full)) return fail(KBBQ_E_HIP, "kbbq_apply_dev: no scratch for the narrowed LUT");
         q.full_bytes = (int)full_bytes;
         q.rb = (u32)full_lut_row_bytes(Sb); q.W = (u32)full_lut_width(Sb); q.ctx_off = 2u * q.W;
         q.maxlen = Sb; q.pairs = 0; q.seg = nullptr; q.rpb = 64; q.perm = nullptr;
-        { const char* x = getenv("KBBQ_K2_PARTS"); q.parts = x ? atoi(x) : 8; }      // fronts of the persistent traversal (0 / 1: one)
+        q.parts = K2V3_FRONTS;
         q.out = d_out; q.status = c->d_status;
 #ifdef K2V3_PER_CU
         int per_cu = K2V3_PER_CU;
@@ -866,16 +857,14 @@ int kbbq_gammaln_dev(kbbq_ctx* c, const double* d_x, int64_t n, const double* d_
     return KBBQ_OK;
 }
 
-// workgroups of a streaming kernel with a grid-stride loop: `per_cu` per CU, or what the environment variable says (timing
-// experiments; 0 = no bound, i.e. one work item per thread).  Measured in three interleaved rounds (scripts/gpu_grids.sh,
+// workgroups of a streaming kernel with a grid-stride loop: `per_cu` per CU.  Measured in three interleaved rounds (scripts/gpu_grids.sh,
 // DESIGN.md section 6): 64 per CU -- four generations of workgroups per CU slot -- beat the 8-16 these kernels
 // started with by 6-13 % (K4 1.95 -> 1.83 ms, K5 1.12 -> 0.98, K6 2.66 -> 2.37 per 16 M reads), 256 did for the layout pass
 // (9.46 -> 8.42 ms per 50 M reads); one item per thread loses again where a workgroup has set-up work (K4's queue, K5's
 // LDS counters and their flush: 13 ms).
-static int bounded_grid(int64_t want, const kbbq_ctx* c, int per_cu, const char* env)
+static int bounded_grid(int64_t want, const kbbq_ctx* c, int per_cu)
 {
-    if (const char* v = getenv(env)) per_cu = atoi(v);
-    const int64_t cap = per_cu > 0 ? (int64_t)c->cus * per_cu : (int64_t)0x7FFFFFFF;
+    const int64_t cap = (int64_t)c->cus * per_cu;
     return (int)std::max<int64_t>(1, std::min<int64_t>(want, cap));
 }
 
@@ -909,7 +898,7 @@ int kbbq_pack_pairs_dev(kbbq_ctx* c, const uint8_t* d_seq, const uint8_t* d_cseq
     p.fill[0] = 'N'; p.fill[1] = 'N'; p.fill[2] = 0;
     p.meta = d_meta; p.pmeta = d_pmeta; p.npairs = npairs; p.pitch = pitch; p.ppitch = pair_pitch(S2); p.S = S2 / 2; p.unpack = 0;
     const int64_t nchunks = npairs * (p.ppitch / 16);
-    const int gx = bounded_grid((nchunks + 255) / 256, c, 256, "KBBQ_K7_GRID");
+    const int gx = bounded_grid((nchunks + 255) / 256, c, 256);
     hipLaunchKernelGGL(k7_pack_pairs, dim3((unsigned)gx), dim3(256), 0, c->stream, p);
     HIPCHK(hipGetLastError());
     return KBBQ_OK;
@@ -929,10 +918,33 @@ int kbbq_unpack_pairs_dev(kbbq_ctx* c, const uint8_t* d_pplane, int64_t npairs, 
     p.fill[0] = p.fill[1] = p.fill[2] = 0;
     p.meta = nullptr; p.pmeta = nullptr; p.npairs = npairs; p.pitch = pitch; p.ppitch = pair_pitch(S2); p.S = S2 / 2; p.unpack = 1;
     const int64_t nchunks = 2 * npairs * (pitch / 16);
-    const int gx = bounded_grid((nchunks + 255) / 256, c, 256, "KBBQ_K7_GRID");
+    const int gx = bounded_grid((nchunks + 255) / 256, c, 256);
     hipLaunchKernelGGL(k7_pack_pairs, dim3((unsigned)gx), dim3(256), 0, c->stream, p);
     HIPCHK(hipGetLastError());
     return KBBQ_OK;
+}
+
+// K1's LDS beside `dn` copies of the context table, once the cycle rows are laid out (q.row_bytes, q.slack_bytes): several
+// trash rows first (K1v3Params::ntrash: the padding behind every read's last base is the hotter spot), then copies of the cycle
+// table for rows of up to 12 chunks (K1v3Params::pos_copies: wider rows spread a wave's lanes over enough columns), as many of
+// 8 / 4 / 2 and 4 / 2 as the LDS holds; KBBQ_K1_NTRASH / KBBQ_K1_POSCOPIES cap them (=1: none).  Returns the LDS bytes.
+static size_t k1_lds_plan(K1v3Params& q, int dn, const kbbq_ctx* c)
+{
+    auto bytes_for = [&](int nt, int pc) {
+        const size_t rows = (size_t)q.nrows - 1 + nt;
+        return rows * 128 * dn + (size_t)pc * (rows * q.row_bytes + q.slack_bytes);
+    };
+    const char* nt_env = getenv("KBBQ_K1_NTRASH");
+    const char* pc_env = getenv("KBBQ_K1_POSCOPIES");
+    const int most_t = nt_env ? atoi(nt_env) : 8, most = pc_env ? atoi(pc_env) : 4;
+    q.ntrash = 1; q.pos_copies = 1;
+    for (int nt = 8; nt >= 2; nt >>= 1)
+        if (nt <= most_t && bytes_for(nt, 1) <= (size_t)c->lds_bytes) { q.ntrash = nt; break; }
+    if (q.cpr <= 12)
+        for (int pc = 4; pc >= 2; pc >>= 1)
+            if (pc <= most && bytes_for(q.ntrash, pc) <= (size_t)c->lds_bytes) { q.pos_copies = pc; break; }
+    q.pos_copy_bytes = (u32)((size_t)(q.nrows - 1 + q.ntrash) * q.row_bytes + q.slack_bytes);
+    return bytes_for(q.ntrash, q.pos_copies);
 }
 
 // K1 (table-driven kernel) on one-read-per-row or mate-pair rows, optionally grouped by read group
@@ -972,42 +984,20 @@ static int accumulate_rows(kbbq_ctx* c, const char* who, const uint8_t* d_seq, c
     const int trim = (!pairs && S_min > 0) ? std::min(S_min, S) : 0;
     int dn = 0; size_t lds3 = 0;
     // mate-pair rows of 19 or 13 chunks (2 x 150, 2 x 100 bp) on 4-bit planes: the chunk-position-major cycle table (kernel comment), the
-    // 13-chunk form with several trash rows (K1v3Params::ntrash; 19 chunks were measured with 4 and 8 of them: nothing; KBBQ_K1_KM_NTRASH
-    // overrides).  Measured for the other lengths instruments emit (scripts/time_km_widths.py): 2 x 100 bp 1.37 -> 1.31 ms per 3 Gbases; 2 x 50 bp
-    // (7 chunks) is FASTER position-major with its copies of the cycle table (1.52 against 1.64 ms); 2 x 75 / 2 x 125 / 2 x 250 bp never
-    // take mate-pair rows (2 S + 1 rounds up to twice the single read's pitch: no bytes saved).  KBBQ_K1_KM=0: none, =19: only 19 chunks.
-    const char* km_off = getenv("KBBQ_K1_KM");
-    const bool km_width = q.cpr == 19 || (q.cpr == 13 && !(km_off && !strcmp(km_off, "19")));
-    const bool km = pairs && nib && km_width && !(km_off && !strcmp(km_off, "0"));
-    bool km_ok = false; int km_ntrash = 1;                 // the form applies AND its tables fit
+    // 13-chunk form with 8 trash rows (K1v3Params::ntrash; 19 chunks were measured with 4 and 8 of them: nothing).  Measured for the other
+    // lengths instruments emit (profiles/): 2 x 100 bp 1.37 -> 1.31 ms per 3 Gbases; 2 x 50 bp (7 chunks) is FASTER position-major with its
+    // copies of the cycle table (1.52 against 1.64 ms); 2 x 75 / 2 x 125 / 2 x 250 bp never take mate-pair rows (2 S + 1 rounds up to
+    // twice the single read's pitch: no bytes saved).
+    const bool km = pairs && nib && (q.cpr == 19 || q.cpr == 13);
+    bool km_ok = false;                                    // the form applies AND its tables fit
     if (km) {
         q.row_bytes = (u32)(((16 * q.cpr + 31) & ~31) * 4);
-        q.minlen = 0; q.slack_bytes = 0; q.ntrash = 1; q.pos_copies = 1;
+        q.minlen = 0; q.slack_bytes = 0; q.pos_copies = 1;
         q.dn_flush_iters = std::max(1, 65535 / ((K1V3_THREADS / K1V3_DNREP) * 16 * q.cpr));
-        const char* kt = getenv("KBBQ_K1_KM_NTRASH");
-        int want_t = kt ? atoi(kt) : (q.cpr == 19 ? 1 : 8);
-        for (int nt = 8; nt >= 1; nt >>= 1) {
-            if (nt > want_t) continue;
+        for (int nt = q.cpr == 19 ? 1 : 8; nt >= 1; nt >>= 1) {
             const size_t rows = (size_t)q.nrows - 1 + nt;
             lds3 = rows * 128 * K1V3_DNREP + rows * q.row_bytes;
-            if (lds3 <= (size_t)c->lds_bytes) { dn = K1V3_DNREP; km_ok = true; km_ntrash = nt; break; }
-        }
-    }
-    // An experiment kept behind KBBQ_K1_TWO=1 (round 3; measured, not adopted): narrow rows (the short bands of a mixed-length
-    // input) run K1 at half the rate of wide ones -- a 64-row block is a few steps of work behind two dependent loads -- and
-    // their tables are small: with 8 copies of the context table TWO workgroups of 12 waves fit a CU's LDS and registers (24
-    // waves per CU instead of 16; two 16-wave workgroups never fitted: 72 registers allow 7 waves per SIMD).  Config 5's K1:
-    // 1.80-1.85 ms against 1.74-1.75 merged, 1.97 against 1.90 a launch per band -- the halved copies cost more than the waves bring.
-    int threads = K1V3_THREADS, per_cu = 1;
-    {
-        const char* two_env = getenv("KBBQ_K1_TWO");
-        const int cut = trim, words = (3 * S - cut) | 1;
-        const size_t lds_two = (size_t)q.nrows * 128 * 8 + (size_t)q.nrows * words * 4 + (size_t)(S + 32) * 4;
-        if (!km && !pairs && two_env && !strcmp(two_env, "1") && 2 * (lds_two + 1024) <= (size_t)c->lds_bytes
-            && (768 / 8) * 16 * q.cpr <= 65535) {
-            q.row_bytes = (u32)words * 4u; q.minlen = cut; q.slack_bytes = (u32)(S + 32) * 4u;
-            q.dn_flush_iters = std::max(1, 65535 / ((768 / 8) * 16 * q.cpr));
-            lds3 = lds_two; dn = 8; threads = 768; per_cu = 2;
+            if (lds3 <= (size_t)c->lds_bytes) { dn = K1V3_DNREP; km_ok = true; q.ntrash = nt; q.pos_copy_bytes = (u32)(rows * q.row_bytes); break; }
         }
     }
     for (int attempt = 0; attempt < (trim ? 3 : 1) && !dn; ++attempt) {
@@ -1025,39 +1015,17 @@ static int accumulate_rows(kbbq_ctx* c, const char* who, const uint8_t* d_seq, c
         if (fits) { *fits = false; return KBBQ_OK; }     // the caller has another kernel for this shape
         return fail(KBBQ_E_LUT, "%s: %d-base reads with minscore %d do not fit the LDS tables; use plain one-read-per-row planes", who, S, minscore);
     }
-    // copies of the cycle table for narrow rows (kernel comment at K1v3Params::pos_copies): as many of 4 / 2 as the LDS holds beside
-    // the context table, for rows of up to 12 chunks (wider rows spread a wave's lanes over enough columns); KBBQ_K1_POSCOPIES=1: none
-    // ... and several trash rows (K1v3Params::ntrash) first: the padding behind every read's last base is the hotter spot
-    q.pos_copies = 1; q.ntrash = 1;
-    q.pos_copy_bytes = (u32)q.nrows * q.row_bytes + q.slack_bytes;
-    if (km_ok) { q.ntrash = km_ntrash; q.pos_copy_bytes = (u32)((size_t)(q.nrows - 1 + q.ntrash) * q.row_bytes); }
-    if (!km_ok && per_cu == 1) {
-        const char* nt_env = getenv("KBBQ_K1_NTRASH");
-        const int most_t = nt_env ? atoi(nt_env) : 8;
-        auto bytes_for = [&](int nt, int pc) {
-            const size_t rows = (size_t)q.nrows - 1 + nt;
-            return rows * 128 * dn + (size_t)pc * (rows * q.row_bytes + q.slack_bytes);
-        };
-        for (int nt = 8; nt >= 2; nt >>= 1)
-            if (nt <= most_t && bytes_for(nt, 1) <= (size_t)c->lds_bytes) { q.ntrash = nt; break; }
-        const char* pc_env = getenv("KBBQ_K1_POSCOPIES");
-        const int most = pc_env ? atoi(pc_env) : 4;
-        if (q.cpr <= 12)
-            for (int pc = 4; pc >= 2; pc >>= 1)
-                if (pc <= most && bytes_for(q.ntrash, pc) <= (size_t)c->lds_bytes) { q.pos_copies = pc; break; }
-        q.pos_copy_bytes = (u32)((size_t)(q.nrows - 1 + q.ntrash) * q.row_bytes + q.slack_bytes);
-        lds3 = bytes_for(q.ntrash, q.pos_copies);
-    }
+    if (!km_ok) lds3 = k1_lds_plan(q, dn, c);
     const bool split = dinuc_minscore > minscore;
     const int64_t nblocks = (nrows + 63) / 64;
-    const int64_t iters = (nblocks + (threads / 64) - 1) / (threads / 64);
+    const int64_t iters = (nblocks + (K1V3_THREADS / 64) - 1) / (K1V3_THREADS / 64);
     if (setup_only) {
         setup_only->q = q; setup_only->dn = dn; setup_only->km = km_ok; setup_only->split = split;
-        setup_only->lds = lds3; setup_only->iters = iters; setup_only->threads = threads;
+        setup_only->lds = lds3; setup_only->iters = iters;
         return KBBQ_OK;
     }
-    int gx = (int)std::min<int64_t>(iters, std::max(1, c->cus * per_cu / R));
-    dim3 grid((unsigned)gx, (unsigned)R, 1), block((unsigned)threads, 1, 1);
+    int gx = (int)std::min<int64_t>(iters, std::max(1, c->cus / R));
+    dim3 grid((unsigned)gx, (unsigned)R, 1), block(K1V3_THREADS, 1, 1);
     {
         Timed t(c, 0);
         if (km_ok) {
@@ -1145,7 +1113,7 @@ static int apply_rows(kbbq_ctx* c, const char* who, const uint8_t* d_seq, const 
     if (pairs && pitch != pair_pitch(S2)) return fail(KBBQ_E_ARG, "%s: mate-pair rows of %d-base reads have pitch %d, not %d", who, S2 / 2, pair_pitch(S2), pitch);
     K2v3Params q;
     // one read per row: the LUT of the columns rows of this pitch can reach (narrowed_row_lut)
-    const int Sb = pairs || (getenv("KBBQ_K2_ROWLUT") && !strcmp(getenv("KBBQ_K2_ROWLUT"), "0")) ? S2 : std::min(pitch, S2);
+    const int Sb = pairs ? S2 : row_lut_width(pitch, S2);
     q.rb = (u32)(pairs ? pair_lut_row_bytes(S2) : full_lut_row_bytes(Sb));
     const size_t rg_bytes = (size_t)(33 + KQ) * q.rb;
     const size_t all_bytes = rg_bytes * (size_t)R;
@@ -1163,14 +1131,14 @@ static int apply_rows(kbbq_ctx* c, const char* who, const uint8_t* d_seq, const 
     q.full_bytes = (int)all_bytes;
     if (pairs) { q.W = 0u; q.ctx_off = (u32)pair_pitch(S2); q.maxlen = S2 + 1; }
     else {
-        if (narrowed_row_lut(c, d_lut_blob, R, KQ, S2, pitch, minscore, &q.full) != Sb) return fail(KBBQ_E_HIP, "%s: no scratch for the narrowed LUT", who);
+        if (!narrowed_row_lut(c, d_lut_blob, R, KQ, S2, Sb, minscore, &q.full)) return fail(KBBQ_E_HIP, "%s: no scratch for the narrowed LUT", who);
         q.W = (u32)full_lut_width(Sb); q.ctx_off = 2u * q.W; q.maxlen = Sb;
     }
     q.pairs = pairs; q.seg = reinterpret_cast<const long long*>(d_seg);
     q.perm = reinterpret_cast<const long long*>(d_perm);
     q.out = d_out; q.status = c->d_status;
     int per_cu = std::max(1, std::min<int>((int)(c->lds_bytes / lds), (K2V3_WAVES * 4 * 64) / K2V3_THREADS));
-    { const char* x = getenv("KBBQ_K2_PARTS"); q.parts = x ? atoi(x) : 8; }      // fronts of the persistent traversal (0 / 1: one)
+    q.parts = K2V3_FRONTS;
     q.rpb = 64;      // the persistent kernel's wave block; smaller blocks were measured slower (profiles/r01_traversal_microbench.md)
     const int64_t nblocks = (nrows + q.rpb - 1) / q.rpb;
     const int64_t want = (nblocks + (K2V3_THREADS / 64) - 1) / (K2V3_THREADS / 64);
@@ -1179,26 +1147,23 @@ static int apply_rows(kbbq_ctx* c, const char* who, const uint8_t* d_seq, const 
 
     // mate-pair rows on 4-bit planes: short-lived workgroups (kbbq_k2_tile.h) unless KBBQ_K2_TILE=0 (A/B timing); everything
     // else, and LUTs of one group beyond a third of the LDS, keeps the persistent kernel
-    const char* tile = getenv("KBBQ_K2_TILE");
     // (one read per row: while two workgroups' copies of the narrowed LUT fit a CU -- rows of up to ~300 bases; measured up to
     //  there, scripts/gpu_tilekb.sh: config 5's K2 0.651 -> 0.687 of roofline going from a 32 KB to a 52 KB limit)
     // character planes (round 4; KBBQ_K2_TILE_CHARS=0: the persistent kernel as before): the same kernel with 16-byte sequence loads
-    const char* tile_chars = getenv("KBBQ_K2_TILE_CHARS");
-    const bool planes_ok = nib || !(tile_chars && !strcmp(tile_chars, "0"));
-    if (!(tile && !strcmp(tile, "0")) && planes_ok && (R == 1 || d_seg) && q.cpr >= 2 && q.cpr <= 4096
-        && (pairs ? rg_bytes * 3 <= (size_t)c->lds_bytes : rg_bytes <= (size_t)(getenv("KBBQ_K2_TILE_LUT_KB") ? atoi(getenv("KBBQ_K2_TILE_LUT_KB")) : 52) << 10)) {
+    const bool planes_ok = nib || !env_is("KBBQ_K2_TILE_CHARS", "0");
+    if (!env_is("KBBQ_K2_TILE", "0") && planes_ok && (R == 1 || d_seg) && q.cpr >= 2 && q.cpr <= 4096
+        && (pairs ? rg_bytes * 3 <= (size_t)c->lds_bytes : rg_bytes <= K2T_ROW_LUT_MAX)) {
         K2tParams t;
         t.seq = d_seq; t.qual = d_qual; t.meta = d_meta; t.nchunks = nrows * q.cpr; t.cpr = q.cpr; t.cpr_magic = q.cpr_magic;
         t.Qt = KQ; t.S2 = S2; t.maxlen = q.maxlen; t.lut = q.full; t.lut_bytes = (int)((rg_bytes + 15) & ~(size_t)15);
         t.rb = q.rb; t.ctx_off = q.ctx_off; t.W = q.W; t.seg = reinterpret_cast<const long long*>(d_seg); t.R = R; t.wg_start = nullptr; t.order = nullptr;
         t.perm = reinterpret_cast<const long long*>(d_perm); t.pitch = pitch; t.out = d_out; t.status = c->d_status;
-        { const char* x = getenv("KBBQ_K2_XCD_TILES"); t.xcd_tiles = x ? std::max(0, atoi(x)) : 1; }
+        t.xcd_tiles = K2T_XCD_TILES;
         const int64_t per_wg = (int64_t)(K2T_THREADS / 64) * 64 * K2T_STEPS;
         int64_t gt = (t.nchunks + per_wg - 1) / per_wg;
         if (d_seg) {
             gt += R;                                     // every group rounds its last workgroup up
-            const char* ord = getenv("KBBQ_K2_ORDER");  // "0": group after group (A/B timing)
-            const bool interleave = d_perm && R > 1 && !(ord && !strcmp(ord, "0"));
+            const bool interleave = d_perm && R > 1;
             const int64_t ints = (int64_t)(R + 1) + 1 + (interleave ? 2 * gt : 0);
             if (ints > 0x7FFFFFFF) return fail(KBBQ_E_ARG, "%s: too many workgroups", who);
             if (c->wgplan_n < (int)ints) {
@@ -1211,7 +1176,7 @@ static int apply_rows(kbbq_ctx* c, const char* who, const uint8_t* d_seq, const 
             t.wg_start = c->d_wgplan;
             if (interleave) {
                 K2tOrderParams op; op.wg_start = c->d_wgplan; op.R = R;
-                { const char* x = getenv("KBBQ_K2_XCD"); op.xcd = x ? atoi(x) : 8; }      // "0": ranks as they are (A/B timing)
+                op.xcd = K2T_XCD;
                 op.order = reinterpret_cast<int2*>(c->d_wgplan + ((R + 2) & ~1));           // 8-byte aligned behind the starts
                 hipLaunchKernelGGL(k2t_order, dim3((unsigned)((gt + 255) / 256)), dim3(256), 0, c->stream, op);
                 t.order = op.order;
@@ -1336,7 +1301,7 @@ int kbbq_accumulate_bands_dev(kbbq_ctx* c, const kbbq_band* bands, int nbands, i
     // which bands the merged kernel (k1v3_bands) takes: the table-driven K1 fits their LDS geometry, position-major cycle
     // table (not the chunk-position-major form of 2 x 150 bp mate-pair rows), all on 4-bit planes or all on character planes
     std::vector<K1Setup> setups; std::vector<int> merged, alone;
-    const char* off = getenv("KBBQ_K1_BANDS");                       // "0": a launch per band (A/B timing)
+    const bool merge = !env_is("KBBQ_K1_BANDS", "0");                // "0": a launch per band (A/B timing)
     int nib_of_merge = -1;
     for (int i = 0; i < nbands; ++i) {
         const kbbq_band& b = bands[i];
@@ -1345,7 +1310,7 @@ int kbbq_accumulate_bands_dev(kbbq_ctx* c, const kbbq_band* bands, int nbands, i
         if (rc) return rc;
         const int pairs = (b.flags & KBBQ_ROWS_PAIRS) ? 1 : 0, nib = (b.flags & KBBQ_ROWS_NIBBLES) ? 1 : 0;
         K1Setup su; bool fits = false;
-        bool can = !(off && !strcmp(off, "0")) && (int)merged.size() < K1V3_MAX_BANDS;
+        bool can = merge && (int)merged.size() < K1V3_MAX_BANDS;
         if (can) {
             if (pairs) { rc = check_pairs("kbbq_accumulate_bands_dev", b.nrows, S2); if (rc) return rc; }
             rc = accumulate_rows(c, "kbbq_accumulate_bands_dev", b.d_seq, b.d_cseq, b.d_qual, b.d_meta, b.nrows, b.pitch, pairs, R, S2, minscore,
@@ -1357,82 +1322,69 @@ int kbbq_accumulate_bands_dev(kbbq_ctx* c, const kbbq_band* bands, int nbands, i
         if (can) { nib_of_merge = nib; merged.push_back(i); setups.push_back(su); }
         else alone.push_back(i);
     }
-    // two kinds of bands: narrow rows whose tables let two 12-wave workgroups share a CU (accumulate_rows), and the rest
-    // (one 16-wave workgroup per CU); each kind with at least two bands is ONE launch, anything else goes alone
-    std::vector<std::vector<size_t>> groups(2);
-    for (size_t k = 0; k < merged.size(); ++k) groups[setups[k].threads == K1V3_THREADS ? 0 : 1].push_back(k);
-    for (auto& grp : groups) {
-        const int G = grp.empty() ? 1 : std::max(1, c->cus * (setups[grp[0]].threads == K1V3_THREADS ? 1 : 2) / std::max(R, 1));
-        if (grp.size() < 2 || (int)grp.size() > G) { for (size_t k : grp) alone.push_back(merged[k]); grp.clear(); }
-    }
+    // at least two bands, no more than one 16-wave workgroup per CU and read group gives each of them: ONE launch; anything else goes alone
+    const int G = std::max(1, c->cus / std::max(R, 1));
+    if (merged.size() < 2 || (int)merged.size() > G) { for (int i : merged) alone.push_back(i); merged.clear(); }
     for (int i : alone) {
         int rc = band_accumulate_alone(c, bands[i], R, S2, minscore, dinuc_minscore, d_tables);
         if (rc) return rc;
     }
     HIPCHK(hipSetDevice(c->device));
-    const char* rc_env = getenv("KBBQ_K1_BAND_ROWCOST");
-    const double row_cost = rc_env ? std::max(0.0, atof(rc_env)) : 1.25;     // the knobs are clamped: a zero or negative weight would leave every band one workgroup
+    if (merged.empty()) return KBBQ_OK;
+    // a band's share of the workgroups follows its work: chunks to bin plus a per-row term (a 64-row block pays the sidecar
+    // -> row address -> first chunk latency whatever its width: narrow rows run at half the rate of wide ones) ...
+    constexpr double row_cost = 1.25;
     // ... and a chunk of a WIDE row costs more than a chunk of a narrow one (larger tables to zero and flush, 8 instead of 16 copies
     // of the context table, more cycle columns for the same lanes): with equal cost per chunk the widest band of BASELINE config 5
     // ended 25 % after the narrowest (KBBQ_K1_BANDS_DBG=1 prints every band's workgroup end times): + 1 % per chunk of row width
-    const char* sl_env = getenv("KBBQ_K1_BAND_SLOPE");
-    const double slope = sl_env ? std::max(0.0, atof(sl_env)) : 0.01;
-    const char* d8_env = getenv("KBBQ_K1_BAND_DN8");          // a band on 8 copies of the context table: twice the same-address atomics there
-    const double dn8_cost = d8_env ? std::max(1.0, atof(d8_env)) : 1.06;
-    for (auto& grp : groups) {
-        if (grp.empty()) continue;
-        const int threads = setups[grp[0]].threads;
-        const int G = std::max(1, c->cus * (threads == K1V3_THREADS ? 1 : 2) / std::max(R, 1));
-        K1BandsParams t;
-        memset(&t, 0, sizeof t);
-        t.nbands = (int)grp.size();
-        // a band's share of the workgroups follows its work: chunks to bin plus a per-row term (a 64-row block pays the sidecar
-        // -> row address -> first chunk latency whatever its width: narrow rows run at half the rate of wide ones)
-        std::vector<double> weight; std::vector<int64_t> cap; std::vector<int> share;
-        size_t lds = 0;
-        for (size_t k : grp) {
-            const K1Setup& su = setups[k];
-            weight.push_back((double)su.q.nreads * (su.q.cpr + row_cost) * (1.0 + slope * su.q.cpr) * (su.dn == K1V3_DNREP ? 1.0 : dn8_cost));
-            cap.push_back(std::max<int64_t>(1, su.iters));
-            lds = std::max(lds, su.lds);
+    constexpr double slope = 0.01;
+    constexpr double dn8_cost = 1.06;                     // a band on 8 copies of the context table: twice the same-address atomics there
+    K1BandsParams t;
+    memset(&t, 0, sizeof t);
+    t.nbands = (int)merged.size();
+    std::vector<double> weight; std::vector<int64_t> cap; std::vector<int> share;
+    size_t lds = 0;
+    for (const K1Setup& su : setups) {
+        weight.push_back((double)su.q.nreads * (su.q.cpr + row_cost) * (1.0 + slope * su.q.cpr) * (su.dn == K1V3_DNREP ? 1.0 : dn8_cost));
+        cap.push_back(std::max<int64_t>(1, su.iters));
+        lds = std::max(lds, su.lds);
+    }
+    share_workgroups(weight, cap, G, share);
+    int run = 0;
+    for (size_t j = 0; j < setups.size(); ++j) {
+        t.wg_start[j] = run; run += share[j];
+        t.dn[j] = setups[j].dn; t.band[j] = setups[j].q;
+    }
+    t.wg_start[setups.size()] = run;
+    const bool split = setups[0].split;
+    dim3 grid((unsigned)run, (unsigned)R, 1), block(K1V3_THREADS, 1, 1);
+    unsigned long long* dbg = nullptr;                    // KBBQ_K1_BANDS_DBG=1: when did every band's workgroups start and end?
+    if (getenv("KBBQ_K1_BANDS_DBG")) { HIPCHK(hipMalloc((void**)&dbg, sizeof(unsigned long long) * 2 * (size_t)run)); t.dbg = dbg; }
+    {
+        Timed tm(c, 0);
+        if (nib_of_merge) {
+            if (split) hipLaunchKernelGGL((k1v3_bands<true, true>), grid, block, lds, c->stream, t);
+            else hipLaunchKernelGGL((k1v3_bands<false, true>), grid, block, lds, c->stream, t);
+        } else {
+            if (split) hipLaunchKernelGGL((k1v3_bands<true, false>), grid, block, lds, c->stream, t);
+            else hipLaunchKernelGGL((k1v3_bands<false, false>), grid, block, lds, c->stream, t);
         }
-        share_workgroups(weight, cap, G, share);
-        int run = 0;
-        for (size_t j = 0; j < grp.size(); ++j) {
-            t.wg_start[j] = run; run += share[j];
-            t.dn[j] = setups[grp[j]].dn; t.band[j] = setups[grp[j]].q;
-        }
-        t.wg_start[grp.size()] = run;
-        const bool split = setups[grp[0]].split;
-        dim3 grid((unsigned)run, (unsigned)R, 1), block((unsigned)threads, 1, 1);
-        unsigned long long* dbg = nullptr;                    // KBBQ_K1_BANDS_DBG=1: when did every band's workgroups start and end?
-        if (getenv("KBBQ_K1_BANDS_DBG")) { HIPCHK(hipMalloc((void**)&dbg, sizeof(unsigned long long) * 2 * (size_t)run)); t.dbg = dbg; }
-        {
-            Timed tm(c, 0);
-            if (nib_of_merge) {
-                if (split) hipLaunchKernelGGL((k1v3_bands<true, true>), grid, block, lds, c->stream, t);
-                else hipLaunchKernelGGL((k1v3_bands<false, true>), grid, block, lds, c->stream, t);
-            } else {
-                if (split) hipLaunchKernelGGL((k1v3_bands<true, false>), grid, block, lds, c->stream, t);
-                else hipLaunchKernelGGL((k1v3_bands<false, false>), grid, block, lds, c->stream, t);
+    }
+    HIPCHK(hipGetLastError());
+    if (dbg) {
+        std::vector<unsigned long long> h(2 * (size_t)run);
+        HIPCHK(hipStreamSynchronize(c->stream));
+        HIPCHK(hipMemcpy(h.data(), dbg, h.size() * sizeof h[0], hipMemcpyDeviceToHost));
+        (void)hipFree(dbg);
+        unsigned long long t0 = ~0ull;
+        for (int w = 0; w < run; ++w) t0 = std::min(t0, h[(size_t)w]);
+        for (int j = 0; j < t.nbands; ++j) {
+            unsigned long long s1 = 0, e0 = ~0ull, e1 = 0;
+            for (int w = t.wg_start[j]; w < t.wg_start[j + 1]; ++w) {
+                s1 = std::max(s1, h[(size_t)w] - t0); e0 = std::min(e0, h[(size_t)run + w] - t0); e1 = std::max(e1, h[(size_t)run + w] - t0);
             }
-        }
-        HIPCHK(hipGetLastError());
-        if (dbg) {
-            std::vector<unsigned long long> h(2 * (size_t)run);
-            HIPCHK(hipStreamSynchronize(c->stream));
-            HIPCHK(hipMemcpy(h.data(), dbg, h.size() * sizeof h[0], hipMemcpyDeviceToHost));
-            (void)hipFree(dbg);
-            unsigned long long t0 = ~0ull;
-            for (int w = 0; w < run; ++w) t0 = std::min(t0, h[(size_t)w]);
-            for (size_t j = 0; j < grp.size(); ++j) {
-                unsigned long long s1 = 0, e0 = ~0ull, e1 = 0;
-                for (int w = t.wg_start[j]; w < t.wg_start[j + 1]; ++w) {
-                    s1 = std::max(s1, h[(size_t)w] - t0); e0 = std::min(e0, h[(size_t)run + w] - t0); e1 = std::max(e1, h[(size_t)run + w] - t0);
-                }
-                fprintf(stderr, "[k1v3_bands] band %zu pitch %3d rows %9lld: %3d workgroups, last start %7.1f us, ends %7.1f .. %7.1f us\n", j, t.band[j].pitch,
-                        (long long)t.band[j].nreads, t.wg_start[j + 1] - t.wg_start[j], s1 / 100.0, e0 / 100.0, e1 / 100.0);
-            }
+            fprintf(stderr, "[k1v3_bands] band %d pitch %3d rows %9lld: %3d workgroups, last start %7.1f us, ends %7.1f .. %7.1f us\n", j, t.band[j].pitch,
+                    (long long)t.band[j].nreads, t.wg_start[j + 1] - t.wg_start[j], s1 / 100.0, e0 / 100.0, e1 / 100.0);
         }
     }
     return KBBQ_OK;
@@ -1453,9 +1405,7 @@ int kbbq_apply_bands_dev(kbbq_ctx* c, const kbbq_band* bands, int nbands, int R,
     if (R <= 0 || R > 32767 || S2 <= 0 || (S2 & 1) || S2 > 65534 || minscore < 0 || minscore > 222) return fail(KBBQ_E_ARG, "kbbq_apply_bands_dev: bad shape");
     // the merged kernel (k2t_bands) takes what the short-lived kernel takes of one-read-per-row 4-bit planes with one read
     // group: rows of 2..4096 chunks whose pitch-narrowed LUT is small (apply_rows' own test); the rest goes band by band
-    const char* off = getenv("KBBQ_K2_BANDS");
-    const char* tile = getenv("KBBQ_K2_TILE");
-    const size_t lut_cap = (size_t)(getenv("KBBQ_K2_TILE_LUT_KB") ? atoi(getenv("KBBQ_K2_TILE_LUT_KB")) : 52) << 10;
+    const bool tile = !env_is("KBBQ_K2_TILE", "0");
     std::vector<int> merged, alone;
     for (int i = 0; i < nbands; ++i) {
         const kbbq_band& b = bands[i];
@@ -1464,9 +1414,9 @@ int kbbq_apply_bands_dev(kbbq_ctx* c, const kbbq_band* bands, int nbands, int R,
         if (rc) return rc;
         const int cpr = b.pitch / 16;
         const int Sb = std::min(b.pitch, S2);
-        const bool can = !(off && !strcmp(off, "0")) && !(tile && !strcmp(tile, "0")) && (int)merged.size() < K2T_MAX_BANDS && R == 1
+        const bool can = tile && (int)merged.size() < K2T_MAX_BANDS && R == 1
                          && b.flags == KBBQ_ROWS_NIBBLES && !b.d_seg && !b.d_perm && b.pitch > 0 && !(b.pitch & 15) && cpr >= 2 && cpr <= 4096
-                         && (size_t)(33 + KQ) * full_lut_row_bytes(Sb) <= lut_cap
+                         && (size_t)(33 + KQ) * full_lut_row_bytes(Sb) <= K2T_ROW_LUT_MAX
                          && !(((uintptr_t)b.d_seq | (uintptr_t)b.d_qual | (uintptr_t)b.d_out) & 15) && b.d_seq && b.d_qual && b.d_meta && b.d_out;
         (can ? merged : alone).push_back(i);
     }
@@ -1504,7 +1454,7 @@ int kbbq_apply_bands_dev(kbbq_ctx* c, const kbbq_band* bands, int nbands, int R,
         q.rb = (u32)full_lut_row_bytes(Sb); q.W = (u32)full_lut_width(Sb); q.ctx_off = 2u * q.W;
         q.lut = f.out; q.lut_bytes = (int)((((size_t)(33 + KQ) * q.rb) + 15) & ~(size_t)15);
         q.seg = nullptr; q.wg_start = nullptr; q.order = nullptr; q.R = R; q.perm = nullptr; q.pitch = b.pitch; q.out = b.d_out; q.status = c->d_status;
-        { const char* x = getenv("KBBQ_K2_XCD_TILES"); q.xcd_tiles = x ? std::max(0, atoi(x)) : 1; }
+        q.xcd_tiles = K2T_XCD_TILES;
         lds = std::max(lds, (size_t)q.lut_bytes);
         t.wg_start[k] = (int)run;
         run += (q.nchunks + per_wg - 1) / per_wg;
@@ -1593,8 +1543,8 @@ int kbbq_lay_out_dev(kbbq_ctx* c, const uint8_t* d_seq, const uint8_t* d_cseq, c
     p.nrows = pairs ? (nreads + 1) / 2 : nreads; p.nsrc = nreads; p.pitch = pitch; p.dpitch = pairs ? pair_pitch(S2) : pitch; p.S = pairs ? S2 / 2 : 0;
     p.pairs = pairs; p.nib = nib; p.status = c->d_status;
     const int rpb7 = (p.dpitch / 16) <= 256 ? 256 / (p.dpitch / 16) : 1;      // destination rows per workgroup iteration
-    const int gx = bounded_grid((p.nrows + rpb7 - 1) / rpb7, c, 256, "KBBQ_K7_GRID");
-    { const char* x = getenv("KBBQ_K7_PARTS"); p.parts = x ? atoi(x) : 8; }
+    const int gx = bounded_grid((p.nrows + rpb7 - 1) / rpb7, c, 256);
+    p.parts = K7_FRONTS;
     hipLaunchKernelGGL(k7_lay_out, dim3((unsigned)std::max(gx, 1)), dim3(256), 0, c->stream, p);
     HIPCHK(hipGetLastError());
     return KBBQ_OK;
@@ -1666,14 +1616,7 @@ int kbbq_find_errors_dev(kbbq_ctx* c, const uint8_t* d_seq, const uint32_t* d_le
     if (((uintptr_t)d_seq | (uintptr_t)d_err | (uintptr_t)d_skip) & 15)
         return fail(KBBQ_E_ARG, "kbbq_find_errors_dev: planes must be 16-byte aligned");
     const int rpb4 = (pitch / 16) <= 256 ? 256 / (pitch / 16) : 1;              // reads per workgroup iteration
-    const int gx = bounded_grid((nreads + rpb4 - 1) / rpb4, c, 64, "KBBQ_K4_GRID");
-    const char* force = getenv("KBBQ_K4");              // "v1" forces the first form (A/B timing): needs both output planes
-    if (force && !strcmp(force, "v1") && d_skip) {
-        if (d_skipmask) hipLaunchKernelGGL(k4_find_errors<false>, dim3((unsigned)std::max(gx, 1)), dim3(256), 0, c->stream, p);
-        else hipLaunchKernelGGL(k4_find_errors<true>, dim3((unsigned)std::max(gx, 1)), dim3(256), 0, c->stream, p);
-        HIPCHK(hipGetLastError());
-        return KBBQ_OK;
-    }
+    const int gx = bounded_grid((nreads + rpb4 - 1) / rpb4, c, 64);
     int rc4 = k4_records(c, p, nullptr, nullptr, nullptr, nullptr, 0);
     if (rc4) return rc4;
     K4v2Params q; q.base = p; q.recs = (const K4Rec*)c->d_ops4; q.idle16 = reinterpret_cast<const uint8_t*>(c->d_status);
@@ -1719,7 +1662,7 @@ int kbbq_canonical_reads_rows_dev(kbbq_ctx* c, const uint8_t* d_seq, const uint8
     p.out_seq = d_out_seq; p.out_cseq = d_out_cseq; p.out_qual = d_out_qual; p.out_meta = d_out_meta;
     p.status = c->d_status;
     const int rpb6 = (pitch / 16) <= 256 ? 256 / (pitch / 16) : 1;
-    const int gx = bounded_grid((nreads + rpb6 - 1) / rpb6, c, 64, "KBBQ_K6_GRID");
+    const int gx = bounded_grid((nreads + rpb6 - 1) / rpb6, c, 64);
     if (layout & KBBQ_ROWS_NIBBLES) hipLaunchKernelGGL(k6_canonical_reads<true>, dim3((unsigned)std::max(gx, 1)), dim3(256), 0, c->stream, p);
     else hipLaunchKernelGGL(k6_canonical_reads<false>, dim3((unsigned)std::max(gx, 1)), dim3(256), 0, c->stream, p);
     HIPCHK(hipGetLastError());
@@ -1771,23 +1714,7 @@ static int accumulate_aligned(kbbq_ctx* c, const uint8_t* d_seq, const uint8_t* 
     }
     if (!dn) return fail(KBBQ_E_LUT, "kbbq_accumulate_aligned_dev: %d-base reads with minscore %d do not fit the LDS tables; tally through kbbq_canonical_reads_rows_dev", S, minscore);
     if (dry_run) return KBBQ_OK;                      // the caller only asked whether this shape is served
-    {   // several trash rows, then copies of the cycle table for short reads, as the LDS allows (accumulate_rows)
-        q.pos_copies = 1; q.ntrash = 1;
-        auto bytes_for = [&](int nt, int pc) {
-            const size_t rows = (size_t)q.nrows - 1 + nt;
-            return rows * 128 * dn + (size_t)pc * (rows * q.row_bytes + q.slack_bytes);
-        };
-        const char* nt_env = getenv("KBBQ_K1_NTRASH");
-        const char* pc_env = getenv("KBBQ_K1_POSCOPIES");
-        const int most_t = nt_env ? atoi(nt_env) : 8, most = pc_env ? atoi(pc_env) : 4;
-        for (int nt = 8; nt >= 2; nt >>= 1)
-            if (nt <= most_t && bytes_for(nt, 1) <= (size_t)c->lds_bytes) { q.ntrash = nt; break; }
-        if (q.cpr <= 12)
-            for (int pc = 4; pc >= 2; pc >>= 1)
-                if (pc <= most && bytes_for(q.ntrash, pc) <= (size_t)c->lds_bytes) { q.pos_copies = pc; break; }
-        q.pos_copy_bytes = (u32)((size_t)(q.nrows - 1 + q.ntrash) * q.row_bytes + q.slack_bytes);
-        lds3 = bytes_for(q.ntrash, q.pos_copies);
-    }
+    lds3 = k1_lds_plan(q, dn, c);                     // trash rows and copies of the cycle table, as accumulate_rows
     const bool split = dinuc_minscore > minscore;
     const int64_t nblocks = (nreads + 63) / 64;
     const int64_t iters = (nblocks + (K1V3_THREADS / 64) - 1) / (K1V3_THREADS / 64);
@@ -1872,11 +1799,9 @@ int kbbq_tally_aligned_dev(kbbq_ctx* c, const uint8_t* d_seq, const uint8_t* d_o
     rc = k4_records(c, p, d_flags, aflags2, rows, count, pitch);
     if (rc) return rc;
     {   // K4 over the listed reads only: their number is on the device, the grid is sized for a share of the reads (a workgroup
-        // beyond the list's end finds nothing to do) -- KBBQ_TALLY_K4_SHARE: 1 / share of the reads' grid, default 8
+        // beyond the list's end finds nothing to do)
         const int rpb4 = (pitch / 16) <= 256 ? 256 / (pitch / 16) : 1;
-        const char* sh = getenv("KBBQ_TALLY_K4_SHARE");
-        const int share = sh && atoi(sh) > 0 ? atoi(sh) : 8;
-        const int gx = bounded_grid(((nreads + share - 1) / share + rpb4 - 1) / rpb4, c, 64, "KBBQ_K4_GRID");
+        const int gx = bounded_grid(((nreads + TALLY_K4_SHARE - 1) / TALLY_K4_SHARE + rpb4 - 1) / rpb4, c, 64);
         K4v2Params q; q.base = p; q.recs = (const K4Rec*)c->d_ops4; q.idle16 = reinterpret_cast<const uint8_t*>(c->d_status);
         q.rows = rows; q.nrows = count;
         hipLaunchKernelGGL(k4v2_find_errors<true>, dim3((unsigned)std::max(gx, 1)), dim3(256), 0, c->stream, q);
@@ -1900,7 +1825,7 @@ int kbbq_count_q_dev(kbbq_ctx* c, const uint8_t* d_qual, const uint8_t* d_err, c
     p.cpr = pitch / 16; p.cpr_magic = magic_for(p.cpr); p.qoffset = qoffset;
     p.counts = reinterpret_cast<u64*>(d_counts512); p.status = c->d_status;
     const int64_t nchunks = nreads * p.cpr;
-    const int gx = bounded_grid((nchunks + 255) / 256, c, 64, "KBBQ_K5_GRID");
+    const int gx = bounded_grid((nchunks + 255) / 256, c, 64);
     hipLaunchKernelGGL(k5_count_q, dim3((unsigned)std::max(gx, 1)), dim3(256), 0, c->stream, p);
     HIPCHK(hipGetLastError());
     return KBBQ_OK;
@@ -1979,8 +1904,10 @@ static int stage_drain(kbbq_ctx* c, int rc)
 
 // The status words hold the SMALLEST flagged read index of every kind over all launches since they were last read; slabs number
 // their reads from 0, so after a pipelined run that flagged something the slabs are looked at again one by one (input errors
-// are the rare case): the first slab that reproduces a status decides, its read index made file-wide.
-static int first_offender(kbbq_ctx* c, int64_t nreads, size_t slab, const std::function<int(int64_t, int64_t)>& run_slab)
+// are the rare case): the first slab that reproduces a status decides, its read index made file-wide (and handed back in
+// *bad_read when the caller asks for it).
+static int first_offender(kbbq_ctx* c, int64_t nreads, size_t slab, const std::function<int(int64_t, int64_t)>& run_slab,
+                          int64_t* bad_read)
 {
     for (int64_t lo = 0; lo < nreads; lo += (int64_t)slab) {
         const int64_t m = std::min<int64_t>((int64_t)slab, nreads - lo);
@@ -1990,6 +1917,7 @@ static int first_offender(kbbq_ctx* c, int64_t nreads, size_t slab, const std::f
         rc = kbbq_ctx_status(c, &idx);
         if (rc) {
             if (idx >= 0) {
+                if (bad_read) *bad_read = lo + idx;
                 const std::string what = g_err;
                 const size_t colon = what.find(": ");
                 return fail(rc, "read %lld%s", (long long)(lo + idx), colon == std::string::npos ? "" : what.c_str() + colon);
@@ -1997,6 +1925,85 @@ static int first_offender(kbbq_ctx* c, int64_t nreads, size_t slab, const std::f
             return rc;
         }
     }
+    return KBBQ_OK;
+}
+
+// The pipelined run of a host-buffer entry point.  A slab holds the input planes `in`, the output plane (when `out` is given),
+// then the meta words; `launch(d, plane, m)` runs the kernel on the m rows of device slab d, whose planes are `plane` bytes apart.
+// Order of a slab k in buffers b = k & 1: [host] wait for slab k - 2 (with an output plane: for its download, whose rows then
+// go to the caller -- everything of slab k - 2 on these buffers has finished, kernel included; without one: for its upload,
+// and the upload stream waits for its kernel) -> host copy in -> upload (upload stream) -> kernel (launch stream, behind the
+// upload's event) -> download (DOWNLOAD stream, behind the kernel's event).  Uploads and downloads are on different streams,
+// so slab k + 1 goes up while slab k's kernel runs and slab k's (or k - 1's) output comes back: both directions of PCIe busy
+// at once (with both on one in-order stream the order was strictly U k, K k, D k, U k + 1).
+static int stage_run(kbbq_ctx* c, const char* who, std::initializer_list<const uint8_t*> in, const uint32_t* meta, uint8_t* out,
+                     int64_t n, int pitch, const std::function<int(uint8_t*, size_t, int64_t)>& launch, int64_t* bad_read = nullptr)
+{
+    const int planes = (int)in.size() + (out ? 1 : 0);
+    const size_t slab = stage_slab_rows(pitch, planes, n);
+    const size_t plane = slab * (size_t)pitch, o_out = in.size() * plane, o_meta = (size_t)planes * plane;
+    int rc = stage_prepare(c, o_meta + slab * 4);
+    if (rc) return rc;
+    auto stage_in = [&](int b, int64_t lo, int64_t m) {
+        uint8_t* h = (uint8_t*)c->stage_host[b];
+        const size_t off = (size_t)lo * pitch, nb = (size_t)m * pitch;
+        size_t at = 0;
+        for (const uint8_t* p : in) { threaded_copy(h + at, p + off, nb); at += plane; }
+        memcpy(h + o_meta, meta + lo, (size_t)m * 4);
+    };
+    auto upload = [&](int b, int64_t m, hipStream_t st) -> int {        // the input planes, then the meta words
+        HIPCHK(hipMemcpyAsync(c->stage_dev[b], c->stage_host[b], o_out, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync((uint8_t*)c->stage_dev[b] + o_meta, (uint8_t*)c->stage_host[b] + o_meta, (size_t)m * 4, hipMemcpyHostToDevice, st));
+        return KBBQ_OK;
+    };
+    struct Out { int64_t lo, m; };
+    Out pending[2] = {{0, 0}, {0, 0}};                                   // downloads in flight, by buffer
+    auto stage_out = [&](int b) -> int {                                 // wait for buffer b's download and hand its rows to the caller
+        if (!pending[b].m) return KBBQ_OK;
+        HIPCHK(hipEventSynchronize(c->stage_down[b]));
+        threaded_copy(out + (size_t)pending[b].lo * pitch, (uint8_t*)c->stage_host[b] + o_out, (size_t)pending[b].m * pitch);
+        pending[b].m = 0;
+        return KBBQ_OK;
+    };
+    int64_t k = 0;
+    auto pipelined = [&]() -> int {
+        for (int64_t lo = 0; lo < n; lo += (int64_t)slab, ++k) {
+            const int b = (int)(k & 1);
+            const int64_t m = std::min<int64_t>((int64_t)slab, n - lo);
+            int r2 = stage_out(b);                                            // slab k - 2 (same buffers): downloaded -> the caller's rows
+            if (r2) return r2;
+            if (!out && k >= 2) HIPCHK(hipEventSynchronize(c->stage_up[b]));  // the page-locked slab has been uploaded: free again
+            stage_in(b, lo, m);
+            if (!out && k >= 2) HIPCHK(hipStreamWaitEvent(c->stage_stream, c->stage_used[b], 0));   // the device slab's kernel has run
+            r2 = upload(b, m, c->stage_stream);
+            if (r2) return r2;
+            HIPCHK(hipEventRecord(c->stage_up[b], c->stage_stream));
+            HIPCHK(hipStreamWaitEvent(c->stream, c->stage_up[b], 0));
+            r2 = launch((uint8_t*)c->stage_dev[b], plane, m);
+            if (r2) return r2;
+            HIPCHK(hipEventRecord(c->stage_used[b], c->stream));
+            if (!out) continue;
+            HIPCHK(hipStreamWaitEvent(c->stage_down_stream, c->stage_used[b], 0));
+            HIPCHK(hipMemcpyAsync((uint8_t*)c->stage_host[b] + o_out, (uint8_t*)c->stage_dev[b] + o_out, (size_t)m * pitch, hipMemcpyDeviceToHost, c->stage_down_stream));
+            HIPCHK(hipEventRecord(c->stage_down[b], c->stage_down_stream));
+            pending[b] = {lo, m};
+        }
+        return KBBQ_OK;
+    };
+    rc = pipelined();
+    if (rc) return stage_drain(c, rc);
+    rc = kbbq_ctx_status(c, nullptr);
+    if (rc) {
+        // something was flagged: which read of the WHOLE input comes first?
+        (void)stage_drain(c, rc);
+        rc = first_offender(c, n, slab, [&](int64_t lo, int64_t m) {
+            stage_in(0, lo, m);
+            int r2 = upload(0, m, c->stream);
+            return r2 ? r2 : launch((uint8_t*)c->stage_dev[0], plane, m);
+        }, bad_read);
+        return rc ? rc : fail(KBBQ_E_HIP, "%s: a status reported by the pipelined run did not reproduce slab by slab", who);
+    }
+    for (int b = 0; b < 2; ++b) { rc = stage_out((int)((k + b) & 1)); if (rc) return stage_drain(c, rc); }     // the older of the two first
     return KBBQ_OK;
 }
 
@@ -2013,50 +2020,11 @@ int kbbq_accumulate(kbbq_ctx* c, const uint8_t* seq, const uint8_t* cseq, const 
     DevBuf dt;
     HIPCHK(dt.alloc(kbbq_tables_count(R, S2) * 8));
     HIPCHK(hipMemsetAsync(dt.p, 0, kbbq_tables_count(R, S2) * 8, c->stream));
-    const size_t slab = stage_slab_rows(pitch, 3, nreads);
-    const size_t plane = slab * (size_t)pitch, set = 3 * plane + slab * 4;
-    int rc = stage_prepare(c, set);
-    if (rc) return rc;
-    auto launch = [&](int b, int64_t m) {
-        const uint8_t* d = (const uint8_t*)c->stage_dev[b];
+    // a slab: seq | cseq | qual | meta; when a read is flagged nothing reaches the caller's tables
+    int rc = stage_run(c, "kbbq_accumulate", {seq, cseq, qual}, meta, nullptr, nreads, pitch, [&](uint8_t* d, size_t plane, int64_t m) {
         return kbbq_accumulate_dev(c, d, d + plane, d + 2 * plane, (const uint32_t*)(d + 3 * plane), m, pitch, R, S2, minscore, (int64_t*)dt.p);
-    };
-    auto stage_in = [&](int b, int64_t lo, int64_t m) {
-        uint8_t* h = (uint8_t*)c->stage_host[b];
-        const size_t off = (size_t)lo * pitch, nb = (size_t)m * pitch;
-        threaded_copy(h, seq + off, nb); threaded_copy(h + plane, cseq + off, nb); threaded_copy(h + 2 * plane, qual + off, nb);
-        memcpy(h + 3 * plane, meta + lo, (size_t)m * 4);
-    };
-    auto pipelined = [&]() -> int {
-        int64_t k = 0;
-        for (int64_t lo = 0; lo < nreads; lo += (int64_t)slab, ++k) {
-            const int b = (int)(k & 1);
-            const int64_t m = std::min<int64_t>((int64_t)slab, nreads - lo);
-            if (k >= 2) HIPCHK(hipEventSynchronize(c->stage_up[b]));              // the page-locked slab has been uploaded: free again
-            stage_in(b, lo, m);
-            if (k >= 2) HIPCHK(hipStreamWaitEvent(c->stage_stream, c->stage_used[b], 0));   // the device slab's kernel has run
-            HIPCHK(hipMemcpyAsync(c->stage_dev[b], c->stage_host[b], set, hipMemcpyHostToDevice, c->stage_stream));
-            HIPCHK(hipEventRecord(c->stage_up[b], c->stage_stream));
-            HIPCHK(hipStreamWaitEvent(c->stream, c->stage_up[b], 0));
-            const int r2 = launch(b, m);
-            if (r2) return r2;
-            HIPCHK(hipEventRecord(c->stage_used[b], c->stream));
-        }
-        return KBBQ_OK;
-    };
-    rc = pipelined();
-    if (rc) return stage_drain(c, rc);
-    rc = kbbq_ctx_status(c, nullptr);
-    if (rc) {
-        // something was flagged: which read of the WHOLE input comes first?  (nothing reaches the caller's tables)
-        HIPCHK(hipStreamSynchronize(c->stage_stream));
-        rc = first_offender(c, nreads, slab, [&](int64_t lo, int64_t m) {
-            stage_in(0, lo, m);
-            HIPCHK(hipMemcpyAsync(c->stage_dev[0], c->stage_host[0], set, hipMemcpyHostToDevice, c->stream));
-            return launch(0, m);
-        });
-        return rc ? rc : fail(KBBQ_E_HIP, "kbbq_accumulate: a status reported by the pipelined run did not reproduce slab by slab");
-    }
+    });
+    if (rc) return rc;
     std::vector<int64_t> h(kbbq_tables_count(R, S2));
     HIPCHK(hipMemcpyAsync(h.data(), dt.p, h.size() * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -2081,77 +2049,11 @@ int kbbq_apply(kbbq_ctx* c, const uint8_t* seq, const uint8_t* qual, const uint3
     DevBuf dl;
     HIPCHK(dl.alloc(lut.size() * 8));
     HIPCHK(hipMemcpyAsync(dl.p, lut.data(), lut.size() * 8, hipMemcpyHostToDevice, c->stream));
-    // a slab: seq | qual | out | meta (the output plane travels back from the same device slab)
-    const size_t slab = stage_slab_rows(pitch, 3, nreads);
-    const size_t plane = slab * (size_t)pitch, set = 3 * plane + slab * 4;
-    rc = stage_prepare(c, set);
-    if (rc) return rc;
     const int mode = flags ? KBBQ_APPLY_CHECKED : KBBQ_APPLY_FAST;
-    auto launch = [&](int b, int64_t m) {
-        uint8_t* d = (uint8_t*)c->stage_dev[b];
+    // a slab: seq | qual | out | meta (the output plane travels back from the same device slab)
+    return stage_run(c, "kbbq_apply", {seq, qual}, meta, qual_out, nreads, pitch, [&](uint8_t* d, size_t plane, int64_t m) {
         return kbbq_apply_dev(c, d, d + plane, (const uint32_t*)(d + 3 * plane), m, pitch, R, Qt, S2, minscore, dl.p, mode, d + 2 * plane);
-    };
-    auto stage_in = [&](int b, int64_t lo, int64_t m) {
-        uint8_t* h = (uint8_t*)c->stage_host[b];
-        const size_t off = (size_t)lo * pitch, nb = (size_t)m * pitch;
-        threaded_copy(h, seq + off, nb); threaded_copy(h + plane, qual + off, nb);
-        memcpy(h + 3 * plane, meta + lo, (size_t)m * 4);
-    };
-    auto upload = [&](int b, int64_t m, hipStream_t st) -> int {        // seq + qual, then the sidecars (the output plane lies between)
-        HIPCHK(hipMemcpyAsync(c->stage_dev[b], c->stage_host[b], 2 * plane, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync((uint8_t*)c->stage_dev[b] + 3 * plane, (uint8_t*)c->stage_host[b] + 3 * plane, (size_t)m * 4, hipMemcpyHostToDevice, st));
-        return KBBQ_OK;
-    };
-    struct Out { int64_t lo, m; };
-    Out pending[2] = {{0, 0}, {0, 0}};                                   // downloads in flight, by buffer
-    auto stage_out = [&](int b) -> int {                                 // wait for buffer b's download and hand its rows to the caller
-        if (!pending[b].m) return KBBQ_OK;
-        HIPCHK(hipEventSynchronize(c->stage_down[b]));
-        threaded_copy(qual_out + (size_t)pending[b].lo * pitch, (uint8_t*)c->stage_host[b] + 2 * plane, (size_t)pending[b].m * pitch);
-        pending[b].m = 0;
-        return KBBQ_OK;
-    };
-    // Order of a slab k in buffers b = k & 1: [host] wait for slab k - 2's download (stage_out: everything of slab k - 2 on these
-    // buffers has then finished, kernel included) -> host copy in -> upload (upload stream) -> kernel (launch stream, behind the
-    // upload's event) -> download (DOWNLOAD stream, behind the kernel's event).  Uploads and downloads are on different streams,
-    // so slab k + 1 goes up while slab k's kernel runs and slab k's (or k - 1's) new qualities come back: both directions of
-    // PCIe busy at once (with both on one in-order stream the order was strictly U k, K k, D k, U k + 1).
-    int64_t k = 0;
-    auto pipelined = [&]() -> int {
-        for (int64_t lo = 0; lo < nreads; lo += (int64_t)slab, ++k) {
-            const int b = (int)(k & 1);
-            const int64_t m = std::min<int64_t>((int64_t)slab, nreads - lo);
-            int r2 = stage_out(b);                                            // slab k - 2 (same buffers): downloaded -> the caller's rows
-            if (r2) return r2;
-            stage_in(b, lo, m);
-            r2 = upload(b, m, c->stage_stream);
-            if (r2) return r2;
-            HIPCHK(hipEventRecord(c->stage_up[b], c->stage_stream));
-            HIPCHK(hipStreamWaitEvent(c->stream, c->stage_up[b], 0));
-            r2 = launch(b, m);
-            if (r2) return r2;
-            HIPCHK(hipEventRecord(c->stage_used[b], c->stream));
-            HIPCHK(hipStreamWaitEvent(c->stage_down_stream, c->stage_used[b], 0));
-            HIPCHK(hipMemcpyAsync((uint8_t*)c->stage_host[b] + 2 * plane, (uint8_t*)c->stage_dev[b] + 2 * plane, (size_t)m * pitch, hipMemcpyDeviceToHost, c->stage_down_stream));
-            HIPCHK(hipEventRecord(c->stage_down[b], c->stage_down_stream));
-            pending[b] = {lo, m};
-        }
-        return KBBQ_OK;
-    };
-    rc = pipelined();
-    if (rc) return stage_drain(c, rc);
-    rc = kbbq_ctx_status(c, nullptr);
-    if (rc) {
-        (void)stage_drain(c, rc);
-        rc = first_offender(c, nreads, slab, [&](int64_t lo, int64_t m) {
-            stage_in(0, lo, m);
-            int r2 = upload(0, m, c->stream);
-            return r2 ? r2 : launch(0, m);
-        });
-        return rc ? rc : fail(KBBQ_E_HIP, "kbbq_apply: a status reported by the pipelined run did not reproduce slab by slab");
-    }
-    for (int b = 0; b < 2; ++b) { rc = stage_out((int)((k + b) & 1)); if (rc) return stage_drain(c, rc); }     // the older of the two first
-    return KBBQ_OK;
+    });
 }
 
 // ---- ApplyBQSR on aligned rows (kbbq_apply_aligned.h) -----------------------------------------------------------------------
@@ -2211,90 +2113,14 @@ int kbbq_apply_aligned(kbbq_ctx* c, const uint8_t* seq, const uint8_t* qual, con
     DevBuf dm;
     HIPCHK(dm.alloc(model_bytes));
     HIPCHK(hipMemcpyAsync(dm.p, model, model_bytes, hipMemcpyHostToDevice, c->stream));
-    // a slab: seq | qual | oq | out | meta (one quality plane when both are the same array)
-    const bool one_q = qual == oq;
-    const int planes = one_q ? 3 : 4;
-    const size_t slab = stage_slab_rows(pitch, planes, n);
-    const size_t plane = slab * (size_t)pitch, set = (size_t)planes * plane + slab * 4;
-    int rc = stage_prepare(c, set);
-    if (rc) return rc;
-    const size_t o_out = (size_t)(planes - 1) * plane, o_meta = (size_t)planes * plane;
-    auto launch = [&](int b, int64_t m) {
-        uint8_t* d = (uint8_t*)c->stage_dev[b];
-        return kbbq_apply_aligned_dev(c, d, d + plane, d + (one_q ? plane : 2 * plane), (const uint32_t*)(d + o_meta), m, pitch,
-                                      R, Qt, S2, minscore, dm.p, mode, d + o_out);
+    // a slab: seq | qual | (oq) | out | meta (one quality plane when both are the same array)
+    const int nq = qual == oq ? 1 : 2;
+    auto launch = [&](uint8_t* d, size_t plane, int64_t m) {
+        return kbbq_apply_aligned_dev(c, d, d + plane, d + nq * plane, (const uint32_t*)(d + (nq + 2) * plane), m, pitch,
+                                      R, Qt, S2, minscore, dm.p, mode, d + (nq + 1) * plane);
     };
-    auto stage_in = [&](int b, int64_t lo, int64_t m) {
-        uint8_t* h = (uint8_t*)c->stage_host[b];
-        const size_t off = (size_t)lo * pitch, nb = (size_t)m * pitch;
-        threaded_copy(h, seq + off, nb); threaded_copy(h + plane, qual + off, nb);
-        if (!one_q) threaded_copy(h + 2 * plane, oq + off, nb);
-        memcpy(h + o_meta, meta + lo, (size_t)m * 4);
-    };
-    auto upload = [&](int b, int64_t m, hipStream_t st) -> int {
-        HIPCHK(hipMemcpyAsync(c->stage_dev[b], c->stage_host[b], o_out, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync((uint8_t*)c->stage_dev[b] + o_meta, (uint8_t*)c->stage_host[b] + o_meta, (size_t)m * 4, hipMemcpyHostToDevice, st));
-        return KBBQ_OK;
-    };
-    struct Out { int64_t lo, m; };
-    Out pending[2] = {{0, 0}, {0, 0}};
-    auto stage_out = [&](int b) -> int {
-        if (!pending[b].m) return KBBQ_OK;
-        HIPCHK(hipEventSynchronize(c->stage_down[b]));
-        threaded_copy(out + (size_t)pending[b].lo * pitch, (uint8_t*)c->stage_host[b] + o_out, (size_t)pending[b].m * pitch);
-        pending[b].m = 0;
-        return KBBQ_OK;
-    };
-    // the slab order of kbbq_apply: upload k + 1 (upload stream) | kernel k | download k - 1 (download stream)
-    int64_t k = 0;
-    auto pipelined = [&]() -> int {
-        for (int64_t lo = 0; lo < n; lo += (int64_t)slab, ++k) {
-            const int b = (int)(k & 1);
-            const int64_t m = std::min<int64_t>((int64_t)slab, n - lo);
-            int r2 = stage_out(b);
-            if (r2) return r2;
-            stage_in(b, lo, m);
-            r2 = upload(b, m, c->stage_stream);
-            if (r2) return r2;
-            HIPCHK(hipEventRecord(c->stage_up[b], c->stage_stream));
-            HIPCHK(hipStreamWaitEvent(c->stream, c->stage_up[b], 0));
-            r2 = launch(b, m);
-            if (r2) return r2;
-            HIPCHK(hipEventRecord(c->stage_used[b], c->stream));
-            HIPCHK(hipStreamWaitEvent(c->stage_down_stream, c->stage_used[b], 0));
-            HIPCHK(hipMemcpyAsync((uint8_t*)c->stage_host[b] + o_out, (uint8_t*)c->stage_dev[b] + o_out, (size_t)m * pitch, hipMemcpyDeviceToHost, c->stage_down_stream));
-            HIPCHK(hipEventRecord(c->stage_down[b], c->stage_down_stream));
-            pending[b] = {lo, m};
-        }
-        return KBBQ_OK;
-    };
-    rc = pipelined();
-    if (rc) return stage_drain(c, rc);
-    rc = kbbq_ctx_status(c, nullptr);
-    if (rc) {
-        // the status words hold the smallest index of every kind over all slabs: the slabs again, one by one (first_offender),
-        // with the offending alignment's index in the whole input handed back
-        (void)stage_drain(c, rc);
-        for (int64_t lo = 0; lo < n; lo += (int64_t)slab) {
-            const int64_t m = std::min<int64_t>((int64_t)slab, n - lo);
-            stage_in(0, lo, m);
-            int r2 = upload(0, m, c->stream);
-            if (!r2) r2 = launch(0, m);
-            if (r2) return r2;
-            int64_t idx = -1;
-            r2 = kbbq_ctx_status(c, &idx);
-            if (r2) {
-                if (idx < 0) return r2;
-                if (bad_read) *bad_read = lo + idx;
-                const std::string what = g_err;
-                const size_t colon = what.find(": ");
-                return fail(r2, "read %lld%s", (long long)(lo + idx), colon == std::string::npos ? "" : what.c_str() + colon);
-            }
-        }
-        return fail(KBBQ_E_HIP, "kbbq_apply_aligned: a status reported by the pipelined run did not reproduce slab by slab");
-    }
-    for (int b = 0; b < 2; ++b) { rc = stage_out((int)((k + b) & 1)); if (rc) return stage_drain(c, rc); }
-    return KBBQ_OK;
+    if (nq == 1) return stage_run(c, "kbbq_apply_aligned", {seq, qual}, meta, out, n, pitch, launch, bad_read);
+    return stage_run(c, "kbbq_apply_aligned", {seq, qual, oq}, meta, out, n, pitch, launch, bad_read);
 }
 
 } // extern "C"

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
-"""PCIe-inclusive rate of the host-buffer entry points (kbbq_accumulate / kbbq_apply: a caller's NumPy planes in pageable memory,
-rows staged slab by slab through page-locked buffers) beside the same rows uploaded whole (torch copies of pageable arrays) and
-then tallied / applied by the device-plane entry points.  usage (GPU box): python scripts/time_host_entry.py [reads]"""
+"""PCIe-inclusive rate of the host-buffer entry points (kbbq_accumulate / kbbq_apply / kbbq_apply_aligned: a caller's NumPy planes
+in pageable memory, rows staged slab by slab through page-locked buffers) beside the same rows uploaded whole (torch copies of
+pageable arrays) and then tallied / applied by the device-plane entry points.  kbbq_apply_aligned runs on the same rows as
+alignments (both strands, first and second of pair), once with one quality plane and once with a separate OQ plane; its output
+is compared with kbbq_apply_aligned_dev's.  usage (GPU box): python scripts/time_host_entry.py [reads]"""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, 'kbbq-py_amd'))
@@ -27,6 +29,18 @@ from kbbq import _solve
 vec = _solve.vectors_from_tables(*want_tabs, 42)
 dqs = applybqsr.get_delta_qs(*vec)
 a = [np.ascontiguousarray(x, dtype=np.int64) for x in (vec[0],) + tuple(dqs)]
+# the rows as alignments: source and context qualities from the OQ plane (bits 28, 29), random strand / mate bits
+ameta = (meta & 0xFFFF) | np.uint32(3 << 28) | (np.random.default_rng(1).integers(0, 4, n, dtype=np.uint32) << np.uint32(30))
+amode, ablob, aR, aQt, aS2 = applybqsr._model(*a, 6)
+oq = qual.copy()                                                  # another plane, the same values: the four-plane slabs
+d = [torch.from_numpy(x).cuda() for x in (seq, qual, ameta.view(np.int32), ablob)]
+d_out = torch.empty_like(d[0])
+N.check(lib.kbbq_apply_aligned_dev(ctx.handle, N.ptr(d[0]), N.ptr(d[1]), N.ptr(d[1]), N.ptr(d[2]), n, pitch, aR, aQt, aS2, 6,
+                                   N.ptr(d[3]), amode, N.ptr(d_out)))
+ctx.status()
+want_aligned = d_out.cpu().numpy()
+del d, d_out
+torch.cuda.empty_cache()
 for rep in range(3):
     tabs = [np.zeros_like(x) for x in want_tabs]
     t0 = time.perf_counter()
@@ -40,6 +54,16 @@ for rep in range(3):
     print('slabs:  kbbq_accumulate %.3f s = %.1f Gbases/s (%.1f GB/s of planes in)   kbbq_apply %.3f s = %.1f Gbases/s (%.1f GB/s in, %.1f out)   same results %s'
           % (t1 - t0, bases / (t1 - t0) / 1e9, 3 * seq.nbytes / (t1 - t0) / 1e9, t3 - t2, bases / (t3 - t2) / 1e9, 2 * seq.nbytes / (t3 - t2) / 1e9,
              seq.nbytes / (t3 - t2) / 1e9, ok), flush=True)
+    aligned = []
+    for src in (qual, oq):
+        o = np.empty_like(qual)
+        t0 = time.perf_counter()
+        N.check(lib.kbbq_apply_aligned(ctx.handle, N.ptr(seq), N.ptr(qual), N.ptr(src), N.ptr(ameta), n, pitch, aR, aQt, aS2, 6,
+                                       N.ptr(ablob), ablob.nbytes, amode, N.ptr(o), None))
+        aligned.append((time.perf_counter() - t0, np.array_equal(o, want_aligned)))
+    (ta, oka), (tb, okb) = aligned
+    print('slabs:  kbbq_apply_aligned %.3f s = %.1f Gbases/s (one quality plane)   %.3f s = %.1f Gbases/s (separate OQ)   same results %s'
+          % (ta, bases / ta / 1e9, tb, bases / tb / 1e9, oka and okb), flush=True)
     t0 = time.perf_counter()
     bb = dev.ReadBatch.from_host(seq, qual, meta.view(np.int32), cseq=cseq)
     tt = dev.Tables(R, S2)

@@ -243,3 +243,70 @@ def test_command_line(dev, oracle, tmp_path):
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     joined = b''.join(open('%s.rank%04d' % (out, k), 'rb').read() for k in range(3))
     assert joined == open(tmp_path / 'o1.sam', 'rb').read()
+
+
+def _synthetic_alignments(n, L, R, seed, separate_oq):
+    """n alignments of L bases on host character planes (as scripts/time_applybqsr.py builds them on the device): both strands,
+    first and second of pair, R read groups; the source qualities are QUAL with the context from a separate OQ plane, or one
+    plane that is both."""
+    rng = np.random.default_rng(seed)
+    pitch = (L + 15) // 16 * 16
+    col = np.arange(pitch)[None, :] < L
+    seq = np.where(col, np.frombuffer(b'ACGT', np.uint8)[rng.integers(0, 4, (n, pitch))], 0).astype(np.uint8)
+    qual = np.where(col, rng.integers(33 + 2, 33 + 42, (n, pitch)), 0).astype(np.uint8)
+    oq = np.where(col, rng.integers(33 + 2, 33 + 42, (n, pitch)), 0).astype(np.uint8) if separate_oq else qual
+    flags, rg = rng.integers(0, 4, n), rng.integers(0, R, n)
+    meta = (L | (rg << 16) | (0 if separate_oq else 1 << 28) | (1 << 29) | ((flags & 1) << 30) | ((flags >> 1) << 31)).astype(np.uint32)
+    return seq, qual, oq, meta
+
+
+@pytest.mark.parametrize('separate_oq', [False, True])
+@pytest.mark.parametrize('kind', ['int', 'float'])
+def test_host_buffer_aligned_entry_runs_slab_by_slab(dev, monkeypatch, separate_oq, kind):
+    """kbbq_apply_aligned moves a caller's rows through the page-locked slabs of kbbq_apply: with slabs of about two thousand
+    rows -- KBBQ_STAGE_MB -- the bytes are those of a single-slab run and of kbbq_apply_aligned_dev on the same rows, and a row the
+    kernel flags is reported with its index in the WHOLE input, in the message and in *bad_read."""
+    import ctypes
+    import re
+    import torch
+    from kbbq import _native as N
+    from kbbq.gatk import applybqsr
+    n, L, R = 30_001, 150, 3
+    seq, qual, oq, meta = _synthetic_alignments(n, L, R, 11 + separate_oq, separate_oq)
+    pitch = seq.shape[1]
+    mode, blob, R_, Qt, S2 = applybqsr._model(*_random_model(13, R, L, kind), 6)
+    assert mode == (N.ALIGNED_LUT if kind == 'int' else N.ALIGNED_F64)
+    ctx, lib = dev.context(), N.load()
+
+    def run(q, o, bad=None):
+        out = np.full_like(seq, 0xEE)
+        bad_read = ctypes.c_int64(-2)
+        rc = lib.kbbq_apply_aligned(ctx.handle, N.ptr(seq), N.ptr(q), N.ptr(o), N.ptr(meta), n, pitch, R_, Qt, S2, 6,
+                                    N.ptr(blob), blob.nbytes, mode, N.ptr(out), ctypes.byref(bad_read))
+        if bad is None:
+            N.check(rc)
+            assert bad_read.value == -1
+            return out
+        with pytest.raises(IndexError) as e:
+            N.check(rc)
+        assert int(re.search(r'read (\d+)', str(e.value)).group(1)) == bad and bad_read.value == bad
+        return None
+
+    monkeypatch.delenv('KBBQ_STAGE_MB', raising=False)                # one slab (the default 96 MB)
+    whole = run(qual, oq)
+    monkeypatch.setenv('KBBQ_STAGE_MB', '1')                          # 1 MB per slab: ~2 100 rows of 160 bytes x 3 planes
+    for _ in range(2):                                                # a second call re-uses the staging
+        assert np.array_equal(run(qual, oq), whole)
+    assert not (whole == 0xEE).any() and (whole[:, L:] == 0).all()
+    d = [torch.from_numpy(x).cuda() for x in (seq, qual, oq, meta.view(np.int32), blob)]
+    d_out = torch.full_like(d[0], 0xEE)
+    N.check(lib.kbbq_apply_aligned_dev(ctx.handle, N.ptr(d[0]), N.ptr(d[1]), N.ptr(d[2] if separate_oq else d[1]), N.ptr(d[3]), n,
+                                       pitch, R_, Qt, S2, 6, N.ptr(d[4]), mode, N.ptr(d_out)))
+    ctx.status()
+    assert np.array_equal(d_out.cpu().numpy(), whole)
+    # a quality above 42 (IndexError of the reference) in a late slab, an earlier slab clean; then a second one before it
+    bad = qual.copy()
+    for first in (25_000, 7_777):
+        bad[first, 3] = 33 + 43                                       # the source plane (with one plane: source and context)
+        run(bad, oq if separate_oq else bad, first)
+    ctx.status()                                                      # nothing left behind
