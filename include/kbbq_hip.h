@@ -56,6 +56,7 @@ extern "C" {
 #define KBBQ_E_NAME     -6   /* corrected read name does not start with the read name    */
 #define KBBQ_E_LUT      -7   /* a device-built LUT needs kbbq_apply_dev(KBBQ_APPLY_CHECKED)  */
 #define KBBQ_E_MEANQ    -8   /* kbbq_solve_device_dev: meanq sits on a truncation boundary, solve with the host's longdouble meanq */
+#define KBBQ_E_FULL     -9   /* k-mer table full: an insert found no free slot (kbbq_kmer_count*): give the table more slots */
 
 #define KBBQ_APPLY_CHECKED 0 /* per-base range test, int16 LUT                            */
 #define KBBQ_APPLY_FAST    1 /* table-driven int8 LUT, no per-base tests (LUT flags == 0) */
@@ -686,6 +687,40 @@ int kbbq_synth_dev(kbbq_ctx* ctx, uint8_t* d_seq, uint8_t* d_cseq, uint8_t* d_qu
  * counts since the last reset (synchronises).  which: 0 = K1, 1 = K2.       */
 int kbbq_ctx_timing(kbbq_ctx* ctx, int enable);
 int kbbq_ctx_kernel_ms(kbbq_ctx* ctx, int which, double* total_ms, int64_t* launches, int reset);
+
+/* ---- k-mer counting and single-substitution correction (kbbq correct; csrc/kbbq_kmer.h) ---------------------------------------
+ * The step the reference leaves to an external corrector (docs/tutorials/recalibration.rst, "Correcting Reads"): its output is
+ * the second file of `kbbq recalibrate -f`.  Rows are a seq plane and meta words as above (only the length bits are read).
+ * A base is A C G T (uppercase); any other byte, and every byte at or beyond the read's length, is a break.  A k-mer is a
+ * window of k (8..32) bases without a break, keyed by its canonical 2k-bit code (the smaller of forward and reverse complement,
+ * first base in the high bits).
+ * Table: open addressing, `slots` a power of two, uint64 keys (all ones = empty) and uint32 counts, kbbq_kmer_table_bytes(slots)
+ * bytes of device memory.  kbbq_kmer_table_info hands out the device arrays (keys[slots], counts[slots]) and the geometry.
+ * kbbq_kmer_count_dev ADDS every k-mer of the rows to the table (slabs and batches compose); counts are exact.  An insert that
+ * finds no free slot within a bounded probe sequence sets a status word: kbbq_ctx_status then returns KBBQ_E_FULL (read index
+ * -1), and the table's content is not a valid count -- nothing is dropped silently.
+ * kbbq_kmer_histogram_dev writes d_hist[257] (uint64): d_hist[c] = distinct k-mers with count c (1..255), d_hist[256] = those
+ * with count >= 256, d_hist[0] = 0.  The caller picks the solid threshold from it (kbbq/kmer.py solid_threshold).
+ * kbbq_kmer_correct_dev: a k-mer is solid when its count is >= min_count.  Base i is trusted when a solid k-mer covers it or
+ * none covers it; an untrusted A/C/G/T base becomes the other base b whose substitution makes the most covering k-mers solid,
+ * when that number is >= 1 and strictly larger than for the other two; every base is judged against the read as given.  d_out
+ * (16-byte aligned, the input's layout) receives the corrected plane, breaks and padding as read; d_changed (may be NULL) the
+ * number of changed bases per read.
+ * kbbq_kmer_count / kbbq_kmer_correct: the same from host buffers, slab by slab through page-locked staging (KBBQ_STAGE_MB);
+ * `changed` (host, may be NULL) receives the per-read counts.  The kernel launches are not timed by kbbq_ctx_timing.         */
+typedef struct kbbq_kmer_table kbbq_kmer_table;
+size_t kbbq_kmer_table_bytes(int64_t slots);
+int kbbq_kmer_table_create_dev(kbbq_ctx* ctx, int k, int64_t slots, kbbq_kmer_table** out);
+int kbbq_kmer_table_free_dev(kbbq_ctx* ctx, kbbq_kmer_table* table);
+int kbbq_kmer_table_info(const kbbq_kmer_table* table, int* k, int64_t* slots, void** d_keys, void** d_counts);
+int kbbq_kmer_count_dev(kbbq_ctx* ctx, kbbq_kmer_table* table, const uint8_t* d_seq, const uint32_t* d_meta, int64_t nreads,
+                        int pitch);
+int kbbq_kmer_histogram_dev(kbbq_ctx* ctx, const kbbq_kmer_table* table, uint64_t* d_hist);
+int kbbq_kmer_correct_dev(kbbq_ctx* ctx, const kbbq_kmer_table* table, const uint8_t* d_seq, const uint32_t* d_meta,
+                          int64_t nreads, int pitch, int min_count, uint8_t* d_out, uint32_t* d_changed);
+int kbbq_kmer_count(kbbq_ctx* ctx, kbbq_kmer_table* table, const uint8_t* seq, const uint32_t* meta, int64_t nreads, int pitch);
+int kbbq_kmer_correct(kbbq_ctx* ctx, const kbbq_kmer_table* table, const uint8_t* seq, const uint32_t* meta, int64_t nreads,
+                      int pitch, int min_count, uint8_t* out, uint32_t* changed);
 
 #ifdef __cplusplus
 }

@@ -7,6 +7,7 @@
 #include "kbbq_aligned_kernels.h"
 #include "kbbq_k2_tile.h"
 #include "kbbq_apply_aligned.h"
+#include "kbbq_kmer.h"
 #include "../../include/kbbq_hip.h"
 #include "host_threads.h"
 
@@ -234,9 +235,13 @@ int kbbq_ctx_status(kbbq_ctx* c, int64_t* read_index)
     HIPCHK(hipMemcpyAsync(st, c->d_status, sizeof st, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     if (read_index) *read_index = -1;
-    if (st[0] == ~0ull && st[1] == ~0ull && st[2] == ~0ull && st[3] == ~0ull && st[ST_MEANQ] == ~0ull) return KBBQ_OK;
+    if (st[0] == ~0ull && st[1] == ~0ull && st[2] == ~0ull && st[3] == ~0ull && st[ST_MEANQ] == ~0ull && st[ST_KMER] == ~0ull)
+        return KBBQ_OK;
     HIPCHK(hipMemcpyAsync(c->d_status, ST_INIT, sizeof ST_INIT, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
+    if (st[ST_KMER] != ~0ull)
+        return fail(KBBQ_E_FULL, "k-mer table full: an insert found no free slot within %d probes (give the table more slots)",
+                    KM_MAX_PROBES);
     // the reference stops at the FIRST offending read; within one read the dinucleotide
     // lookup (TypeError, recalibrate.py:94) runs before the table indexing (IndexError, :114)
     if (st[0] == ~0ull && st[1] == ~0ull && st[2] == ~0ull && st[ST_MEANQ] != ~0ull) {
@@ -1993,6 +1998,7 @@ static int stage_run(kbbq_ctx* c, const char* who, std::initializer_list<const u
     rc = pipelined();
     if (rc) return stage_drain(c, rc);
     rc = kbbq_ctx_status(c, nullptr);
+    if (rc == KBBQ_E_FULL) return stage_drain(c, rc);                  // the table, not a read: nothing to look for slab by slab
     if (rc) {
         // something was flagged: which read of the WHOLE input comes first?
         (void)stage_drain(c, rc);
@@ -2121,6 +2127,168 @@ int kbbq_apply_aligned(kbbq_ctx* c, const uint8_t* seq, const uint8_t* qual, con
     };
     if (nq == 1) return stage_run(c, "kbbq_apply_aligned", {seq, qual}, meta, out, n, pitch, launch, bad_read);
     return stage_run(c, "kbbq_apply_aligned", {seq, qual, oq}, meta, out, n, pitch, launch, bad_read);
+}
+
+// ---- k-mer counting and correction (kbbq_kmer.h) ------------------------------------------------------------------------------
+struct kbbq_kmer_table {
+    int k = 0;
+    int64_t slots = 0;
+    u64* keys = nullptr;              // [slots], KM_EMPTY where free
+    u32* counts = nullptr;            // [slots]
+};
+
+size_t kbbq_kmer_table_bytes(int64_t slots) { return slots > 0 ? (size_t)slots * 12 : 0; }
+
+int kbbq_kmer_table_create_dev(kbbq_ctx* c, int k, int64_t slots, kbbq_kmer_table** out)
+{
+    if (!c || !out) return fail(KBBQ_E_ARG, "kbbq_kmer_table_create_dev: NULL argument");
+    *out = nullptr;
+    if (k < 8 || k > 32) return fail(KBBQ_E_ARG, "kbbq_kmer_table_create_dev: k must be in 8..32, got %d", k);
+    if (slots < 16 || (slots & (slots - 1)) || slots > ((int64_t)1 << 40))
+        return fail(KBBQ_E_ARG, "kbbq_kmer_table_create_dev: slots must be a power of two in 16..2^40, got %lld", (long long)slots);
+    HIPCHK(hipSetDevice(c->device));
+    kbbq_kmer_table* t = new kbbq_kmer_table;
+    t->k = k; t->slots = slots;
+    hipError_t e = hipMalloc((void**)&t->keys, (size_t)slots * 8);
+    if (e == hipSuccess) e = hipMalloc((void**)&t->counts, (size_t)slots * 4);
+    if (e == hipSuccess) e = hipMemsetAsync(t->keys, 0xFF, (size_t)slots * 8, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(t->counts, 0, (size_t)slots * 4, c->stream);
+    if (e != hipSuccess) {
+        (void)kbbq_kmer_table_free_dev(c, t);
+        return fail(KBBQ_E_HIP, "kbbq_kmer_table_create_dev: %lld slots (%zu bytes): %s", (long long)slots,
+                    kbbq_kmer_table_bytes(slots), hipGetErrorString(e));
+    }
+    *out = t;
+    return KBBQ_OK;
+}
+
+int kbbq_kmer_table_free_dev(kbbq_ctx* c, kbbq_kmer_table* t)
+{
+    if (!t) return KBBQ_OK;
+    if (c) { (void)hipSetDevice(c->device); (void)hipStreamSynchronize(c->stream); }
+    if (t->keys) (void)hipFree(t->keys);
+    if (t->counts) (void)hipFree(t->counts);
+    delete t;
+    return KBBQ_OK;
+}
+
+int kbbq_kmer_table_info(const kbbq_kmer_table* t, int* k, int64_t* slots, void** d_keys, void** d_counts)
+{
+    if (!t) return fail(KBBQ_E_ARG, "kbbq_kmer_table_info: table is NULL");
+    if (k) *k = t->k;
+    if (slots) *slots = t->slots;
+    if (d_keys) *d_keys = t->keys;
+    if (d_counts) *d_counts = t->counts;
+    return KBBQ_OK;
+}
+
+// rows per workgroup and LDS words per row-chunk of the count / correct kernels
+static int kmer_geometry(kbbq_ctx* c, const char* who, const kbbq_kmer_table* t, const uint8_t* d_seq, const uint32_t* d_meta,
+                         int64_t n, int pitch, KmerParams& p, int lds_words, size_t* lds)
+{
+    if (!c || !t) return fail(KBBQ_E_ARG, "%s: NULL ctx or table", who);
+    int rc = check_planes(who, n, pitch, d_seq, d_seq, d_seq);
+    if (rc) return rc;
+    if (n > 0 && !d_meta) return fail(KBBQ_E_ARG, "%s: NULL meta", who);
+    p.seq = d_seq; p.meta = d_meta; p.nrows = n; p.pitch = pitch; p.cpr = pitch / 16; p.k = t->k;
+    p.rows_per_wg = std::max(1, KM_THREADS / p.cpr);
+    p.keys = t->keys; p.counts = t->counts; p.mask = (u64)t->slots - 1; p.status = c->d_status;
+    p.min_count = 1; p.out = nullptr; p.changed = nullptr;
+    *lds = ((size_t)lds_words * p.rows_per_wg * p.cpr + p.rows_per_wg) * 4;
+    if (*lds > (size_t)c->lds_bytes) return fail(KBBQ_E_ARG, "%s: pitch %d needs %zu bytes of LDS", who, pitch, *lds);
+    return KBBQ_OK;
+}
+
+// launches of at most 2^20 workgroups
+static int kmer_launches(const KmerParams& p, const std::function<void(const KmerParams&, unsigned)>& launch)
+{
+    const int64_t per = ((int64_t)1 << 20) * p.rows_per_wg;
+    for (int64_t lo = 0; lo < p.nrows; lo += per) {
+        KmerParams q = p;
+        const int64_t m = std::min(per, p.nrows - lo);
+        q.seq = p.seq + (size_t)lo * p.pitch; q.meta = p.meta + lo; q.nrows = m;
+        if (p.out) q.out = p.out + (size_t)lo * p.pitch;
+        if (p.changed) q.changed = p.changed + lo;
+        launch(q, (unsigned)((m + p.rows_per_wg - 1) / p.rows_per_wg));
+        HIPCHK(hipGetLastError());
+    }
+    return KBBQ_OK;
+}
+
+int kbbq_kmer_count_dev(kbbq_ctx* c, kbbq_kmer_table* t, const uint8_t* d_seq, const uint32_t* d_meta, int64_t n, int pitch)
+{
+    KmerParams p; size_t lds = 0;
+    int rc = kmer_geometry(c, "kbbq_kmer_count_dev", t, d_seq, d_meta, n, pitch, p, 2, &lds);
+    if (rc || n == 0) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    return kmer_launches(p, [&](const KmerParams& q, unsigned grid) {
+        hipLaunchKernelGGL(km_count, dim3(grid), dim3(KM_THREADS), lds, c->stream, q);
+    });
+}
+
+int kbbq_kmer_histogram_dev(kbbq_ctx* c, const kbbq_kmer_table* t, uint64_t* d_hist)
+{
+    if (!c || !t || !d_hist) return fail(KBBQ_E_ARG, "kbbq_kmer_histogram_dev: NULL argument");
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipMemsetAsync(d_hist, 0, KM_HIST * 8, c->stream));
+    const unsigned grid = (unsigned)std::min<int64_t>((t->slots + KM_THREADS - 1) / KM_THREADS, (int64_t)c->cus * 8);
+    hipLaunchKernelGGL(km_histogram, dim3(grid), dim3(KM_THREADS), 0, c->stream, t->keys, t->counts, (u64)t->slots,
+                       reinterpret_cast<u64*>(d_hist));
+    HIPCHK(hipGetLastError());
+    return KBBQ_OK;
+}
+
+int kbbq_kmer_correct_dev(kbbq_ctx* c, const kbbq_kmer_table* t, const uint8_t* d_seq, const uint32_t* d_meta, int64_t n, int pitch,
+                          int min_count, uint8_t* d_out, uint32_t* d_changed)
+{
+    KmerParams p; size_t lds = 0;
+    int rc = kmer_geometry(c, "kbbq_kmer_correct_dev", t, d_seq, d_meta, n, pitch, p, 3, &lds);
+    if (rc) return rc;
+    if (min_count < 1) return fail(KBBQ_E_ARG, "kbbq_kmer_correct_dev: min_count must be >= 1, got %d", min_count);
+    if (n > 0 && (!d_out || ((uintptr_t)d_out & 15))) return fail(KBBQ_E_ARG, "kbbq_kmer_correct_dev: d_out NULL or not 16-byte aligned");
+    if (n == 0) return KBBQ_OK;
+    HIPCHK(hipSetDevice(c->device));
+    p.min_count = (u32)min_count; p.out = d_out; p.changed = d_changed;
+    return kmer_launches(p, [&](const KmerParams& q, unsigned grid) {
+        hipLaunchKernelGGL(km_correct, dim3(grid), dim3(KM_THREADS), lds, c->stream, q);
+    });
+}
+
+int kbbq_kmer_count(kbbq_ctx* c, kbbq_kmer_table* t, const uint8_t* seq, const uint32_t* meta, int64_t n, int pitch)
+{
+    if (!c || !t) return fail(KBBQ_E_ARG, "kbbq_kmer_count: NULL ctx or table");
+    if (n < 0 || pitch <= 0 || (pitch & 15)) return fail(KBBQ_E_ARG, "kbbq_kmer_count: bad n/pitch");
+    if (n > 0 && (!seq || !meta)) return fail(KBBQ_E_ARG, "kbbq_kmer_count: NULL plane");
+    if (n == 0) return KBBQ_OK;
+    HIPCHK(hipSetDevice(c->device));
+    // a slab: seq | meta
+    return stage_run(c, "kbbq_kmer_count", {seq}, meta, nullptr, n, pitch, [&](uint8_t* d, size_t plane, int64_t m) {
+        return kbbq_kmer_count_dev(c, t, d, (const uint32_t*)(d + plane), m, pitch);
+    });
+}
+
+int kbbq_kmer_correct(kbbq_ctx* c, const kbbq_kmer_table* t, const uint8_t* seq, const uint32_t* meta, int64_t n, int pitch,
+                      int min_count, uint8_t* out, uint32_t* changed)
+{
+    if (!c || !t) return fail(KBBQ_E_ARG, "kbbq_kmer_correct: NULL ctx or table");
+    if (n < 0 || pitch <= 0 || (pitch & 15)) return fail(KBBQ_E_ARG, "kbbq_kmer_correct: bad n/pitch");
+    if (n > 0 && (!seq || !meta || !out)) return fail(KBBQ_E_ARG, "kbbq_kmer_correct: NULL plane");
+    if (n == 0) return KBBQ_OK;
+    HIPCHK(hipSetDevice(c->device));
+    DevBuf dc;
+    if (changed) HIPCHK(dc.alloc((size_t)n * 4));
+    // a slab: seq | out | meta; the slabs run in order, `done` rows before this one
+    int64_t done = 0;
+    int rc = stage_run(c, "kbbq_kmer_correct", {seq}, meta, out, n, pitch, [&](uint8_t* d, size_t plane, int64_t m) {
+        if (done + m > n) return fail(KBBQ_E_HIP, "kbbq_kmer_correct: more rows launched than given");
+        uint32_t* dch = changed ? (uint32_t*)dc.p + done : nullptr;
+        done += m;
+        return kbbq_kmer_correct_dev(c, t, d, (const uint32_t*)(d + 2 * plane), m, pitch, min_count, d + plane, dch);
+    });
+    if (rc || !changed) return rc;
+    HIPCHK(hipMemcpyAsync(changed, dc.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return KBBQ_OK;
 }
 
 } // extern "C"

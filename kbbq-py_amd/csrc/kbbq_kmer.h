@@ -1,0 +1,269 @@
+// kbbq_kmer.h -- k-mer counting and single-substitution error correction (kbbq correct, kbbq/kmer.py).
+//
+// Bases A C G T (uppercase only) code as 0 1 2 3; every other byte, and every byte at or beyond the read's length, is a break.
+// A k-mer (8 <= k <= 32) is a window of k bases of one read without a break; its key is the smaller of the 2k-bit forward code
+// and the reverse-complement code, first base in the high bits.  The all-ones word is never canonical for k <= 32 (its reverse
+// complement is 0), so it marks an empty slot.
+//
+// Table: open addressing over `slots` (a power of two) slots, structure of arrays: keys uint64[slots] (empty = all ones) and
+// counts uint32[slots], 12 bytes a slot.  A key's home slot is a 64-bit mix of the key; probing is linear.  Keys are written
+// once (empty -> key, by a 64-bit compare-and-swap) and never change, so a plain load that returns a key is final and only an
+// empty slot needs the compare-and-swap.  Counts are exact: the table does not depend on thread order.  An insert that finds
+// neither its key nor an empty slot within KM_MAX_PROBES probes sets status word ST_KMER and that lane stops inserting; a
+// workgroup that starts with the word set inserts nothing.  At the default load factor (<= 0.5) such a run of 512 occupied
+// slots does not occur; a table that is too small fails with KBBQ_E_FULL instead of dropping k-mers.  A lookup stops at its
+// key, an empty slot or after the same KM_MAX_PROBES probes: every key a successful count inserted lies within that reach.
+//
+// Work (count and correct): a workgroup takes whole rows, floor(256 / chunks per row) of them (one row when a row has more
+// than 256 chunks), and every thread one 16-byte chunk at a time.  Pass 1 turns each chunk into a 32-bit code word and a
+// 16-bit break mask in LDS; a thread then reads the words of the next two chunks of its row from LDS (every window starting
+// in its chunk ends at most 46 bases later) and handles the 16 windows that start in its chunk.  Correct keeps one
+// (solid, valid) bit pair per window in LDS; base i is trusted when a solid window starts in [i - k + 1, i] -- one mask test
+// over the words of the base's own chunk and the two before it -- or when no valid window does.  Only untrusted A/C/G/T bases
+// look up the 3 x (covering windows) substituted k-mers.  Every base is judged against the read as read (no cascade).
+#pragma once
+#include "kbbq_kernels.h"
+
+#define ST_KMER 5                     // status word: a k-mer insert found no free slot (kbbq_ctx_status -> KBBQ_E_FULL)
+
+constexpr int KM_THREADS = 256;
+constexpr int KM_MAX_PROBES = 512;
+constexpr u64 KM_EMPTY = ~0ull;
+constexpr int KM_HIST = 257;          // h[c], c = 1..255; h[256]: count >= 256; h[0] stays 0
+
+struct KmerParams {
+    const uint8_t* seq; const u32* meta; int64_t nrows; int pitch; int cpr; int rows_per_wg; int k;
+    u64* keys; u32* counts; u64 mask;
+    u32 min_count;                    // correct: a k-mer is solid when its count is >= min_count
+    uint8_t* out; u32* changed;       // correct: the corrected plane; per-read count of changed bases (may be NULL)
+    u64* status;
+};
+
+__device__ __forceinline__ u64 km_hash(u64 x)
+{
+    x ^= x >> 30; x *= 0xbf58476d1ce4e5b9ull;
+    x ^= x >> 27; x *= 0x94d049bb133111ebull;
+    return x ^ (x >> 31);
+}
+
+// reverse complement of a 2k-bit forward code
+__device__ __forceinline__ u64 km_revcomp(u64 f, int k)
+{
+    u64 y = __builtin_bitreverse64(~f);                                   // complement, groups reversed (bits swapped in each)
+    y = ((y >> 1) & 0x5555555555555555ull) | ((y & 0x5555555555555555ull) << 1);
+    return y >> (64 - 2 * k);
+}
+
+__device__ __forceinline__ u64 km_canonical(u64 f, int k)
+{
+    const u64 r = km_revcomp(f, k);
+    return f < r ? f : r;
+}
+
+__device__ __forceinline__ u64 km_load_key(const u64* p)
+{
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// count of `key`, 0 when absent
+__device__ __forceinline__ u32 km_lookup(const KmerParams& p, u64 key)
+{
+    u64 s = km_hash(key) & p.mask;
+    for (int i = 0; i < KM_MAX_PROBES; ++i) {
+        const u64 cur = km_load_key(p.keys + s);
+        if (cur == key) return p.counts[s];
+        if (cur == KM_EMPTY) return 0;
+        s = (s + 1) & p.mask;
+    }
+    return 0;
+}
+
+__device__ __forceinline__ bool km_insert(const KmerParams& p, u64 key)
+{
+    u64 s = km_hash(key) & p.mask;
+    for (int i = 0; i < KM_MAX_PROBES; ++i) {
+        u64 cur = km_load_key(p.keys + s);
+        if (cur == KM_EMPTY) {
+            cur = atomicCAS(p.keys + s, KM_EMPTY, key);
+            if (cur == KM_EMPTY) cur = key;                               // this lane claimed the slot
+        }
+        if (cur == key) { atomicAdd(p.counts + s, 1u); return true; }
+        s = (s + 1) & p.mask;
+    }
+    return false;
+}
+
+// Pass 1: the code word (base t of the chunk in bits 31 - 2t .. 30 - 2t) and break mask (bit t) of every chunk of the
+// workgroup's rows.  Returns the number of rows this workgroup holds.
+__device__ __forceinline__ int km_load_chunks(const KmerParams& p, int64_t row0, u32* code, u32* brk)
+{
+    const int nr = (int)(p.nrows - row0 < p.rows_per_wg ? p.nrows - row0 : p.rows_per_wg);
+    for (int e = threadIdx.x; e < nr * p.cpr; e += KM_THREADS) {
+        const int r = e / p.cpr, ch = e - r * p.cpr;
+        const int64_t row = row0 + r;
+        const int L = (int)(p.meta[row] & 0xFFFFu);
+        const uint4 v = *reinterpret_cast<const uint4*>(p.seq + (size_t)row * p.pitch + (size_t)ch * 16);
+        const u32 w[4] = {v.x, v.y, v.z, v.w};
+        u32 c = 0, b = 0;
+        #pragma unroll
+        for (int t = 0; t < 16; ++t) {
+            const u32 x = (w[t >> 2] >> (8 * (t & 3))) & 0xFFu;
+            const u32 cv = x == 'A' ? 0u : x == 'C' ? 1u : x == 'G' ? 2u : 3u;
+            const bool base = (x == 'A' || x == 'C' || x == 'G' || x == 'T') && ch * 16 + t < L;
+            c |= (base ? cv : 0u) << (30 - 2 * t);
+            b |= (base ? 0u : 1u) << t;
+        }
+        code[e] = c; brk[e] = b;
+    }
+    return nr;
+}
+
+// the code words of chunks ch .. ch + n - 1 of a row as one big-endian 128-bit word (chunks past the row: code 0, all breaks)
+__device__ __forceinline__ unsigned __int128 km_words(const KmerParams& p, const u32* code, const u32* brk, int e_row, int ch,
+                                                      int n, u64* breaks)
+{
+    unsigned __int128 x = 0; u64 b = 0;
+    for (int i = 0; i < n; ++i) {
+        const int c = ch + i;
+        const bool in = c >= 0 && c < p.cpr;
+        x |= (unsigned __int128)(in ? code[e_row + c] : 0u) << (96 - 32 * i);
+        b |= (u64)(in ? brk[e_row + c] : 0xFFFFu) << (16 * i);
+    }
+    *breaks = b;
+    return x;
+}
+
+// forward code of the window that starts `o` bases into a 128-bit word
+__device__ __forceinline__ u64 km_window(unsigned __int128 x, int o, int k)
+{
+    return (u64)((x << (2 * o)) >> (128 - 2 * k));
+}
+
+__global__ __launch_bounds__(KM_THREADS) void km_count(KmerParams p)
+{
+    extern __shared__ u32 km_lds[];
+    const int E = p.rows_per_wg * p.cpr;
+    u32* code = km_lds; u32* brk = km_lds + E;
+    const int64_t row0 = (int64_t)blockIdx.x * p.rows_per_wg;
+    const int nr = km_load_chunks(p, row0, code, brk);
+    __syncthreads();
+    if (__hip_atomic_load(p.status + ST_KMER, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != ~0ull) return;   // the table is full
+    const u64 kmask = (1ull << p.k) - 1;
+    for (int e = threadIdx.x; e < nr * p.cpr; e += KM_THREADS) {
+        const int r = e / p.cpr, ch = e - r * p.cpr;
+        u64 b;
+        const unsigned __int128 x = km_words(p, code, brk, r * p.cpr, ch, 3, &b);
+        for (int o = 0; o < 16; ++o) {
+            if ((b >> o) & kmask) continue;
+            if (!km_insert(p, km_canonical(km_window(x, o, p.k), p.k))) {
+                atomicMin(p.status + ST_KMER, (u64)(row0 + r));
+                return;
+            }
+        }
+    }
+}
+
+// h[min(count, 256)] += 1 for every occupied slot
+__global__ __launch_bounds__(KM_THREADS) void km_histogram(const u64* keys, const u32* counts, u64 slots, u64* hist)
+{
+    __shared__ u32 h[KM_HIST];
+    for (int i = threadIdx.x; i < KM_HIST; i += KM_THREADS) h[i] = 0;
+    __syncthreads();
+    const u64 stride = (u64)gridDim.x * KM_THREADS;
+    for (u64 s = (u64)blockIdx.x * KM_THREADS + threadIdx.x; s < slots; s += stride)
+        if (keys[s] != KM_EMPTY) atomicAdd(&h[min(counts[s], 256u)], 1u);
+    __syncthreads();
+    for (int i = threadIdx.x; i < KM_HIST; i += KM_THREADS)
+        if (h[i]) atomicAdd(hist + i, (u64)h[i]);
+}
+
+__device__ __forceinline__ bool km_solid(const KmerParams& p, u64 f)
+{
+    return km_lookup(p, km_canonical(f, p.k)) >= p.min_count;
+}
+
+__global__ __launch_bounds__(KM_THREADS) void km_correct(KmerParams p)
+{
+    extern __shared__ u32 km_lds[];
+    const int E = p.rows_per_wg * p.cpr;
+    u32* code = km_lds; u32* brk = km_lds + E; u32* sv = km_lds + 2 * E; u32* nchg = km_lds + 3 * E;
+    const int64_t row0 = (int64_t)blockIdx.x * p.rows_per_wg;
+    for (int i = threadIdx.x; i < p.rows_per_wg; i += KM_THREADS) nchg[i] = 0;
+    const int nr = km_load_chunks(p, row0, code, brk);
+    __syncthreads();
+    const int k = p.k;
+    const u64 kmask = (1ull << k) - 1;
+    // pass 2: (solid << 16 | valid) of the 16 windows starting in every chunk
+    for (int e = threadIdx.x; e < nr * p.cpr; e += KM_THREADS) {
+        const int r = e / p.cpr, ch = e - r * p.cpr;
+        u64 b;
+        const unsigned __int128 x = km_words(p, code, brk, r * p.cpr, ch, 3, &b);
+        u32 valid = 0, solid = 0;
+        for (int o = 0; o < 16; ++o) {
+            if ((b >> o) & kmask) continue;
+            valid |= 1u << o;
+            if (km_solid(p, km_window(x, o, k))) solid |= 1u << o;
+        }
+        sv[e] = solid << 16 | valid;
+    }
+    __syncthreads();
+    // pass 3: trust, substitution, output
+    for (int e = threadIdx.x; e < nr * p.cpr; e += KM_THREADS) {
+        const int r = e / p.cpr, ch = e - r * p.cpr;
+        const int64_t row = row0 + r;
+        u64 V = 0, S = 0;                                                 // bit i: the window starting at base 16 (ch - 2) + i
+        for (int i = 0; i < 3; ++i) {
+            const int c = ch - 2 + i;
+            const u32 w = c >= 0 ? sv[r * p.cpr + c] : 0u;
+            V |= (u64)(w & 0xFFFFu) << (16 * i);
+            S |= (u64)(w >> 16) << (16 * i);
+        }
+        uint8_t* dst = p.out + (size_t)row * p.pitch + (size_t)ch * 16;
+        uint4 v = *reinterpret_cast<const uint4*>(p.seq + (size_t)row * p.pitch + (size_t)ch * 16);
+        const u32 brk_own = brk[e];
+        u32 w[4] = {v.x, v.y, v.z, v.w};
+        int changed = 0;
+        bool have_words = false;
+        unsigned __int128 xa = 0, xb = 0;                                // chunks ch - 2 .. ch + 1 and ch .. ch + 3
+        for (int t = 0; t < 16; ++t) {
+            if ((brk_own >> t) & 1u) continue;                            // a break: never changed
+            const int pp = 32 + t;                                        // the base's index in the 48-bit window masks
+            const u64 cover = kmask << (pp - k + 1);
+            if ((S & cover) || !(V & cover)) continue;                    // trusted
+            if (!have_words) {
+                u64 unused;
+                xa = km_words(p, code, brk, r * p.cpr, ch - 2, 4, &unused);
+                xb = km_words(p, code, brk, r * p.cpr, ch, 4, &unused);
+                have_words = true;
+            }
+            const u32 orig = (code[e] >> (30 - 2 * t)) & 3u;
+            int s[4] = {0, 0, 0, 0};
+            for (u32 alt = 0; alt < 4; ++alt) {
+                if (alt == orig) continue;
+                for (u64 m = V & cover; m; m &= m - 1) {
+                    const int j = __builtin_ctzll(m);                     // a valid covering window
+                    const u64 f = (j < 32 ? km_window(xa, j, k) : km_window(xb, j - 32, k)) ^ ((u64)(orig ^ alt) << (2 * (k - 1 - (pp - j))));
+                    s[alt] += km_solid(p, f) ? 1 : 0;
+                }
+            }
+            int best = -1, bs = 0; bool tie = false;
+            for (int alt = 0; alt < 4; ++alt) {
+                if (alt == (int)orig) continue;
+                if (s[alt] > bs) { bs = s[alt]; best = alt; tie = false; }
+                else if (s[alt] == bs && bs > 0) tie = true;
+            }
+            if (best < 0 || tie) continue;
+            const u32 letter = best == 0 ? 'A' : best == 1 ? 'C' : best == 2 ? 'G' : 'T';
+            const int sh = 8 * (t & 3);
+            w[t >> 2] = (w[t >> 2] & ~(0xFFu << sh)) | (letter << sh);
+            ++changed;
+        }
+        v.x = w[0]; v.y = w[1]; v.z = w[2]; v.w = w[3];
+        *reinterpret_cast<uint4*>(dst) = v;
+        if (changed) atomicAdd(&nchg[r], (u32)changed);
+    }
+    if (p.changed) {
+        __syncthreads();
+        for (int i = threadIdx.x; i < nr; i += KM_THREADS) p.changed[row0 + i] = nchg[i];
+    }
+}

@@ -22,6 +22,7 @@ KBBQ_E_RANGE = -5
 KBBQ_E_NAME = -6
 KBBQ_E_LUT = -7
 KBBQ_E_MEANQ = -8
+KBBQ_E_FULL = -9
 APPLY_CHECKED, APPLY_FAST = 0, 1
 ALIGNED_LUT, ALIGNED_F64 = 0, 1
 ROWS_PAIRS, ROWS_NIBBLES, ROWS_TWINS = 1, 2, 4
@@ -164,6 +165,15 @@ PROTOTYPES = {
                             _i, _i, _i, _i, _i, _vp]),
     'kbbq_ctx_timing': (_i, [_vp, _i]),
     'kbbq_ctx_kernel_ms': (_i, [_vp, _i, _c.POINTER(_c.c_double), _c.POINTER(_i64), _i]),
+    'kbbq_kmer_table_bytes': (_sz, [_i64]),
+    'kbbq_kmer_table_create_dev': (_i, [_vp, _i, _i64, _c.POINTER(_vp)]),
+    'kbbq_kmer_table_free_dev': (_i, [_vp, _vp]),
+    'kbbq_kmer_table_info': (_i, [_vp, _c.POINTER(_i), _c.POINTER(_i64), _c.POINTER(_vp), _c.POINTER(_vp)]),
+    'kbbq_kmer_count_dev': (_i, [_vp, _vp, _vp, _vp, _i64, _i]),
+    'kbbq_kmer_histogram_dev': (_i, [_vp, _vp, _vp]),
+    'kbbq_kmer_correct_dev': (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _vp, _vp]),
+    'kbbq_kmer_count': (_i, [_vp, _vp, _vp, _vp, _i64, _i]),
+    'kbbq_kmer_correct': (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _vp, _vp]),
 }
 
 
@@ -187,6 +197,10 @@ class KbbqHipError(RuntimeError):
 
 class LutNeedsCheckedApply(KbbqHipError):
     """kbbq_ctx_status: the device-built LUT is not usable by the table-driven apply kernel."""
+
+
+class KmerTableFull(KbbqHipError):
+    """kbbq_ctx_status: a k-mer insert found no free slot; the table needs more slots (kbbq/kmer.py)."""
 
 
 class MeanqNeedsHost(KbbqHipError):
@@ -255,6 +269,8 @@ def check(rc):
         raise LutNeedsCheckedApply(msg)
     if rc == KBBQ_E_MEANQ:
         raise MeanqNeedsHost(msg)
+    if rc == KBBQ_E_FULL:
+        raise KmerTableFull(msg)
     raise KbbqHipError(msg or ('libkbbq_hip error %d' % rc))
 
 

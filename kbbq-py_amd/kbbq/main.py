@@ -3,7 +3,8 @@
 kbbq command line -- the `recalibrate` sub-command of the reference CLI
 and the `benchmark` sub-command (reference kbbq/main.py:26-89).  `plot` is out of scope here.
 `bqsr` (alignments -> GATK report) and `applybqsr` (report -> recalibrated SAM) are this build's own: the reference has the
-functions (kbbq/gatk/bqsr.py, applybqsr.py) but no command for them.
+functions (kbbq/gatk/bqsr.py, applybqsr.py) but no command for them.  So is `correct` (k-mer error correction, kbbq/kmer.py):
+the reference's tutorial leaves that step to an external corrector.
 """
 import argparse
 
@@ -51,6 +52,19 @@ def bqsr(args):
     from . import aln
     from .gatk import bqsr as _bqsr
     _bqsr.bam_to_report(aln.AlignmentFile(args.bam), args.reference, _bm.get_var_sites(args.vcf)).write(args.gatkreport)
+
+
+def correct(args):
+    import os
+    import sys
+    if int(os.environ.get('WORLD_SIZE', '1')) > 1:
+        sys.exit('kbbq correct: runs on one GPU only -- counting k-mers across ranks would need an exchange of tables; '
+                 'run it without torch.distributed.run')
+    from . import kmer
+    if 'torch' not in sys.modules and not os.environ.get('KBBQ_USE_TORCH'):
+        from . import _device
+        _device.use_native_memory()          # as `recalibrate` on one GPU: no torch import
+    kmer.main_correct(args.fastq, output=args.output, k=args.kmer, min_count=args.min_count, slots=args.slots)
 
 
 def main(argv=None):
@@ -107,6 +121,18 @@ def main(argv=None):
     qp.add_argument('-v', '--vcf', required=True, help='VCF file of known variable sites (skipped)')
     qp.add_argument('-g', '--gatkreport', required=True, help='Write the report to this file')
     qp.set_defaults(command=bqsr)
+
+    cp = sub.add_parser('correct', description='Correct substitution errors of a FASTQ file with k-mer counts (GPU); the output '
+                        'is the error-corrected file `recalibrate -f` takes')
+    cp.add_argument('-f', '--fastq', required=True, help='FASTQ file to correct (plain or .gz)')
+    cp.add_argument('-k', '--kmer', type=int, default=31, help='k-mer length, 8..32 (default 31)')
+    cp.add_argument('--min-count', type=int, default=None,
+                    help='k-mers seen at least this often are solid (default: the first valley of the count histogram)')
+    cp.add_argument('--slots', type=int, default=None,
+                    help='hash table slots, a power of two (default: every k-mer of the input at a load factor of 0.5, '
+                         'capped by the device budget)')
+    cp.add_argument('-o', '--output', default=None, help='Write the corrected FASTQ to this file instead of stdout')
+    cp.set_defaults(command=correct)
 
     args = parser.parse_args(argv)
     args.command(args)
