@@ -707,7 +707,17 @@ int kbbq_ctx_kernel_ms(kbbq_ctx* ctx, int which, double* total_ms, int64_t* laun
  * (16-byte aligned, the input's layout) receives the corrected plane, breaks and padding as read; d_changed (may be NULL) the
  * number of changed bases per read.
  * kbbq_kmer_count / kbbq_kmer_correct: the same from host buffers, slab by slab through page-locked staging (KBBQ_STAGE_MB);
- * `changed` (host, may be NULL) receives the per-read counts.  The kernel launches are not timed by kbbq_ctx_timing.         */
+ * `changed` (host, may be NULL) receives the per-read counts.  The kernel launches are not timed by kbbq_ctx_timing.
+ * Ranks (kbbq/kmer.py count_kmers_ranks): every rank counts its reads into a local table, sends each key to its owner and merges
+ * what it receives into the table of the keys it owns.  kbbq_kmer_owner(key, W) = (uint32)(((mix(key ^ 0x9E3779B97F4A7C15) >>
+ * 32) * W) >> 32), mix being the table's slot hash; the home slot uses the low bits of mix(key), the owner the high bits of
+ * another mix, so the keys of one owner spread over every home slot of its table.  kbbq_kmer_table_clear_dev empties a table.
+ * kbbq_kmer_select_sizes_dev (synchronous) writes h_sizes[b] = occupied slots with count >= min_count whose owner among
+ * `nbuckets` (1..1024) is b; nbuckets = 1 counts them all.  kbbq_kmer_select_dev (synchronous) writes them: bucket b's keys and
+ * counts to d_keys / d_counts [h_offsets[b], h_offsets[b] + h_sizes[b]), any order inside a bucket -- with h_offsets the
+ * exclusive scan of h_sizes, one dense buffer in bucket order.  kbbq_kmer_merge_dev ADDS n (key, count) pairs (device arrays)
+ * to a table with the probing of kbbq_kmer_count_dev; a pair that finds no free slot makes kbbq_ctx_status return KBBQ_E_FULL
+ * as a count does.                                                                                                         */
 typedef struct kbbq_kmer_table kbbq_kmer_table;
 size_t kbbq_kmer_table_bytes(int64_t slots);
 int kbbq_kmer_table_create_dev(kbbq_ctx* ctx, int k, int64_t slots, kbbq_kmer_table** out);
@@ -721,6 +731,12 @@ int kbbq_kmer_correct_dev(kbbq_ctx* ctx, const kbbq_kmer_table* table, const uin
 int kbbq_kmer_count(kbbq_ctx* ctx, kbbq_kmer_table* table, const uint8_t* seq, const uint32_t* meta, int64_t nreads, int pitch);
 int kbbq_kmer_correct(kbbq_ctx* ctx, const kbbq_kmer_table* table, const uint8_t* seq, const uint32_t* meta, int64_t nreads,
                       int pitch, int min_count, uint8_t* out, uint32_t* changed);
+int kbbq_kmer_table_clear_dev(kbbq_ctx* ctx, kbbq_kmer_table* table);
+int kbbq_kmer_select_sizes_dev(kbbq_ctx* ctx, const kbbq_kmer_table* table, int nbuckets, uint32_t min_count, int64_t* h_sizes);
+int kbbq_kmer_select_dev(kbbq_ctx* ctx, const kbbq_kmer_table* table, int nbuckets, uint32_t min_count, const int64_t* h_offsets,
+                         uint64_t* d_keys, uint32_t* d_counts);
+int kbbq_kmer_merge_dev(kbbq_ctx* ctx, kbbq_kmer_table* table, const uint64_t* d_keys, const uint32_t* d_counts, int64_t n);
+uint32_t kbbq_kmer_owner(uint64_t key, int nbuckets);
 
 #ifdef __cplusplus
 }

@@ -2254,6 +2254,74 @@ int kbbq_kmer_correct_dev(kbbq_ctx* c, const kbbq_kmer_table* t, const uint8_t* 
     });
 }
 
+int kbbq_kmer_table_clear_dev(kbbq_ctx* c, kbbq_kmer_table* t)
+{
+    if (!c || !t) return fail(KBBQ_E_ARG, "kbbq_kmer_table_clear_dev: NULL ctx or table");
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipMemsetAsync(t->keys, 0xFF, (size_t)t->slots * 8, c->stream));
+    HIPCHK(hipMemsetAsync(t->counts, 0, (size_t)t->slots * 4, c->stream));
+    return KBBQ_OK;
+}
+
+uint32_t kbbq_kmer_owner(uint64_t key, int nbuckets) { return nbuckets > 0 ? km_owner(key, (u32)nbuckets) : 0u; }
+
+static unsigned kmer_select_grid(const kbbq_ctx* c, const kbbq_kmer_table* t)
+{
+    const int64_t tiles = (t->slots / 4 + KM_THREADS * KM_SEL_QUADS - 1) / (KM_THREADS * KM_SEL_QUADS);
+    return (unsigned)std::min<int64_t>(tiles, (int64_t)c->cus * 8);
+}
+
+int kbbq_kmer_select_sizes_dev(kbbq_ctx* c, const kbbq_kmer_table* t, int nbuckets, uint32_t min_count, int64_t* h_sizes)
+{
+    if (!c || !t || !h_sizes) return fail(KBBQ_E_ARG, "kbbq_kmer_select_sizes_dev: NULL argument");
+    if (nbuckets < 1 || nbuckets > KM_MAX_BUCKETS)
+        return fail(KBBQ_E_ARG, "kbbq_kmer_select_sizes_dev: nbuckets must be in 1..%d, got %d", KM_MAX_BUCKETS, nbuckets);
+    HIPCHK(hipSetDevice(c->device));
+    DevBuf d;
+    HIPCHK(d.alloc((size_t)nbuckets * 8));
+    HIPCHK(hipMemsetAsync(d.p, 0, (size_t)nbuckets * 8, c->stream));
+    hipLaunchKernelGGL(km_select_sizes, dim3(kmer_select_grid(c, t)), dim3(KM_THREADS), 0, c->stream, t->keys, t->counts,
+                       (u64)t->slots, min_count, (u32)nbuckets, (u64*)d.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(h_sizes, d.p, (size_t)nbuckets * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return KBBQ_OK;
+}
+
+int kbbq_kmer_select_dev(kbbq_ctx* c, const kbbq_kmer_table* t, int nbuckets, uint32_t min_count, const int64_t* h_offsets,
+                         uint64_t* d_keys, uint32_t* d_counts)
+{
+    if (!c || !t || !h_offsets) return fail(KBBQ_E_ARG, "kbbq_kmer_select_dev: NULL argument");
+    if (nbuckets < 1 || nbuckets > KM_MAX_BUCKETS)
+        return fail(KBBQ_E_ARG, "kbbq_kmer_select_dev: nbuckets must be in 1..%d, got %d", KM_MAX_BUCKETS, nbuckets);
+    for (int b = 0; b < nbuckets; ++b)
+        if (h_offsets[b] < 0) return fail(KBBQ_E_ARG, "kbbq_kmer_select_dev: offset %d is negative", b);
+    HIPCHK(hipSetDevice(c->device));
+    std::vector<u64> cur((size_t)nbuckets * KM_CURSOR_STRIDE, 0);
+    for (int b = 0; b < nbuckets; ++b) cur[(size_t)b * KM_CURSOR_STRIDE] = (u64)h_offsets[b];
+    DevBuf d;
+    HIPCHK(d.alloc(cur.size() * 8));
+    HIPCHK(hipMemcpyAsync(d.p, cur.data(), cur.size() * 8, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(km_select_scatter, dim3(kmer_select_grid(c, t)), dim3(KM_THREADS), 0, c->stream, t->keys, t->counts,
+                       (u64)t->slots, min_count, (u32)nbuckets, (u64*)d.p, (u64*)d_keys, (u32*)d_counts);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(c->stream));          // the cursors (and the caller's offsets) are released on return
+    return KBBQ_OK;
+}
+
+int kbbq_kmer_merge_dev(kbbq_ctx* c, kbbq_kmer_table* t, const uint64_t* d_keys, const uint32_t* d_counts, int64_t n)
+{
+    if (!c || !t) return fail(KBBQ_E_ARG, "kbbq_kmer_merge_dev: NULL ctx or table");
+    if (n < 0 || (n > 0 && (!d_keys || !d_counts))) return fail(KBBQ_E_ARG, "kbbq_kmer_merge_dev: bad pairs");
+    if (n == 0) return KBBQ_OK;
+    HIPCHK(hipSetDevice(c->device));
+    const unsigned grid = (unsigned)std::min<int64_t>((n + KM_THREADS - 1) / KM_THREADS, (int64_t)c->cus * 32);
+    hipLaunchKernelGGL(km_merge, dim3(grid), dim3(KM_THREADS), 0, c->stream, (const u64*)d_keys, (const u32*)d_counts, n,
+                       t->keys, t->counts, (u64)t->slots - 1, c->d_status);
+    HIPCHK(hipGetLastError());
+    return KBBQ_OK;
+}
+
 int kbbq_kmer_count(kbbq_ctx* c, kbbq_kmer_table* t, const uint8_t* seq, const uint32_t* meta, int64_t n, int pitch)
 {
     if (!c || !t) return fail(KBBQ_E_ARG, "kbbq_kmer_count: NULL ctx or table");

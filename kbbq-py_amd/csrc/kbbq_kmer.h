@@ -21,6 +21,11 @@
 // (solid, valid) bit pair per window in LDS; base i is trusted when a solid window starts in [i - k + 1, i] -- one mask test
 // over the words of the base's own chunk and the two before it -- or when no valid window does.  Only untrusted A/C/G/T bases
 // look up the 3 x (covering windows) substituted k-mers.  Every base is judged against the read as read (no cascade).
+//
+// Ranks (kbbq/kmer.py count_kmers_ranks): the owner of a canonical key among W ranks is km_owner(key, W), the high 32 bits of
+// the same mix taken of the key XOR a constant, scaled to 0..W-1.  It shares no bits with the home slot (km_hash(key) & mask),
+// so the keys one rank owns spread over all home slots of its table.  km_select_sizes / km_select_scatter sort the occupied
+// slots with count >= min_count into buckets by owner (one bucket: compaction), km_merge adds (key, count) pairs to a table.
 #pragma once
 #include "kbbq_kernels.h"
 
@@ -39,7 +44,7 @@ struct KmerParams {
     u64* status;
 };
 
-__device__ __forceinline__ u64 km_hash(u64 x)
+__host__ __device__ __forceinline__ u64 km_hash(u64 x)
 {
     x ^= x >> 30; x *= 0xbf58476d1ce4e5b9ull;
     x ^= x >> 27; x *= 0x94d049bb133111ebull;
@@ -265,5 +270,113 @@ __global__ __launch_bounds__(KM_THREADS) void km_correct(KmerParams p)
     if (p.changed) {
         __syncthreads();
         for (int i = threadIdx.x; i < nr; i += KM_THREADS) p.changed[row0 + i] = nchg[i];
+    }
+}
+
+// ---- ranks: partition, exchange and merge ----------------------------------------------------------------------------------
+constexpr int KM_MAX_BUCKETS = 1024;  // owners of one select; the per-bucket counters live in LDS
+constexpr int KM_SEL_QUADS = 4;       // 4-slot quads per thread and tile: a tile is KM_THREADS * 16 slots
+constexpr int KM_CURSOR_STRIDE = 16;  // u64 words between two buckets' cursors: one 128-byte line each
+
+__host__ __device__ __forceinline__ u32 km_owner(u64 key, u32 nbuckets)
+{
+    return (u32)(((km_hash(key ^ 0x9E3779B97F4A7C15ull) >> 32) * (u64)nbuckets) >> 32);
+}
+
+// The 16 slots of thread `tid` in tile `tile`: quads tile * KM_THREADS * KM_SEL_QUADS + j * KM_THREADS + tid, each read with
+// two 16-byte loads of keys and one of counts.  tag[i] = bucket << 16 | rank within the tile's bucket for a kept slot, ~0 else.
+// LDS: cnt[nbuckets] counts the kept slots of the tile per bucket (added to, not cleared here).
+__device__ __forceinline__ void km_select_tile(const u64* keys, const u32* counts, u64 quads, u64 tile, u32 min_count,
+                                               u32 nbuckets, u32* cnt, u64 (&key)[4 * KM_SEL_QUADS],
+                                               u32 (&val)[4 * KM_SEL_QUADS], u32 (&tag)[4 * KM_SEL_QUADS])
+{
+    #pragma unroll
+    for (int j = 0; j < KM_SEL_QUADS; ++j) {
+        const u64 q = (tile * KM_SEL_QUADS + j) * KM_THREADS + threadIdx.x;
+        ulonglong2 ka = make_ulonglong2(KM_EMPTY, KM_EMPTY), kb = ka;
+        uint4 c = make_uint4(0, 0, 0, 0);
+        if (q < quads) {
+            ka = *reinterpret_cast<const ulonglong2*>(keys + 4 * q);
+            kb = *reinterpret_cast<const ulonglong2*>(keys + 4 * q + 2);
+            c = *reinterpret_cast<const uint4*>(counts + 4 * q);
+        }
+        key[4 * j] = ka.x; key[4 * j + 1] = ka.y; key[4 * j + 2] = kb.x; key[4 * j + 3] = kb.y;
+        val[4 * j] = c.x; val[4 * j + 1] = c.y; val[4 * j + 2] = c.z; val[4 * j + 3] = c.w;
+    }
+    #pragma unroll
+    for (int i = 0; i < 4 * KM_SEL_QUADS; ++i) {
+        tag[i] = ~0u;
+        if (key[i] == KM_EMPTY || val[i] < min_count) continue;
+        const u32 b = nbuckets > 1 ? km_owner(key[i], nbuckets) : 0u;
+        tag[i] = b << 16 | atomicAdd(cnt + b, 1u);
+    }
+}
+
+// sizes[b] += kept slots of bucket b (sizes zeroed by the caller); one global add per non-empty bucket per workgroup
+__global__ __launch_bounds__(KM_THREADS) void km_select_sizes(const u64* keys, const u32* counts, u64 slots, u32 min_count,
+                                                              u32 nbuckets, u64* sizes)
+{
+    __shared__ u32 cnt[KM_MAX_BUCKETS];
+    for (u32 i = threadIdx.x; i < nbuckets; i += KM_THREADS) cnt[i] = 0;
+    __syncthreads();
+    const u64 quads = slots / 4, tiles = (quads + KM_THREADS * KM_SEL_QUADS - 1) / (KM_THREADS * KM_SEL_QUADS);
+    u64 key[4 * KM_SEL_QUADS]; u32 val[4 * KM_SEL_QUADS], tag[4 * KM_SEL_QUADS];
+    for (u64 t = blockIdx.x; t < tiles; t += gridDim.x)
+        km_select_tile(keys, counts, quads, t, min_count, nbuckets, cnt, key, val, tag);
+    __syncthreads();
+    for (u32 i = threadIdx.x; i < nbuckets; i += KM_THREADS)
+        if (cnt[i]) atomicAdd(sizes + i, (u64)cnt[i]);
+}
+
+// The kept slots of bucket b go to out_keys / out_counts [cursor[b * KM_CURSOR_STRIDE], ...): per tile, one returning add per
+// non-empty bucket reserves the tile's run and every kept slot writes at run + its rank.  Order inside a bucket varies.
+__global__ __launch_bounds__(KM_THREADS) void km_select_scatter(const u64* keys, const u32* counts, u64 slots, u32 min_count,
+                                                                u32 nbuckets, u64* cursor, u64* out_keys, u32* out_counts)
+{
+    __shared__ u32 cnt[KM_MAX_BUCKETS];
+    __shared__ u64 base[KM_MAX_BUCKETS];
+    const u64 quads = slots / 4, tiles = (quads + KM_THREADS * KM_SEL_QUADS - 1) / (KM_THREADS * KM_SEL_QUADS);
+    u64 key[4 * KM_SEL_QUADS]; u32 val[4 * KM_SEL_QUADS], tag[4 * KM_SEL_QUADS];
+    for (u64 t = blockIdx.x; t < tiles; t += gridDim.x) {
+        for (u32 i = threadIdx.x; i < nbuckets; i += KM_THREADS) cnt[i] = 0;
+        __syncthreads();
+        km_select_tile(keys, counts, quads, t, min_count, nbuckets, cnt, key, val, tag);
+        __syncthreads();
+        for (u32 i = threadIdx.x; i < nbuckets; i += KM_THREADS)
+            if (cnt[i]) base[i] = atomicAdd(cursor + (size_t)i * KM_CURSOR_STRIDE, (u64)cnt[i]);
+        __syncthreads();
+        #pragma unroll
+        for (int i = 0; i < 4 * KM_SEL_QUADS; ++i) {
+            if (tag[i] == ~0u) continue;
+            const u64 at = base[tag[i] >> 16] + (tag[i] & 0xFFFFu);
+            out_keys[at] = key[i];
+            out_counts[at] = val[i];
+        }
+        __syncthreads();                                              // base and cnt are reused by the next tile
+    }
+}
+
+// counts[key] += c for n (key, count) pairs, the table as km_count's; a pair that finds neither its key nor an empty slot sets
+// ST_KMER to its index (the lowest such) and a workgroup that starts a stride with the word set stops
+__global__ __launch_bounds__(KM_THREADS) void km_merge(const u64* in_keys, const u32* in_counts, int64_t n, u64* keys, u32* counts,
+                                                       u64 mask, u64* status)
+{
+    const int64_t stride = (int64_t)gridDim.x * KM_THREADS;
+    for (int64_t i = (int64_t)blockIdx.x * KM_THREADS + threadIdx.x; i < n; i += stride) {
+        if (__hip_atomic_load(status + ST_KMER, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != ~0ull) return;
+        const u64 key = in_keys[i];
+        const u32 c = in_counts[i];
+        u64 s = km_hash(key) & mask;
+        bool done = false;
+        for (int j = 0; j < KM_MAX_PROBES; ++j) {
+            u64 cur = km_load_key(keys + s);
+            if (cur == KM_EMPTY) {
+                cur = atomicCAS(keys + s, KM_EMPTY, key);
+                if (cur == KM_EMPTY) cur = key;
+            }
+            if (cur == key) { atomicAdd(counts + s, c); done = true; break; }
+            s = (s + 1) & mask;
+        }
+        if (!done) { atomicMin(status + ST_KMER, (u64)i); return; }
     }
 }

@@ -174,6 +174,11 @@ PROTOTYPES = {
     'kbbq_kmer_correct_dev': (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _vp, _vp]),
     'kbbq_kmer_count': (_i, [_vp, _vp, _vp, _vp, _i64, _i]),
     'kbbq_kmer_correct': (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _vp, _vp]),
+    'kbbq_kmer_table_clear_dev': (_i, [_vp, _vp]),
+    'kbbq_kmer_select_sizes_dev': (_i, [_vp, _vp, _i, _c.c_uint32, _vp]),
+    'kbbq_kmer_select_dev': (_i, [_vp, _vp, _i, _c.c_uint32, _vp, _vp, _vp]),
+    'kbbq_kmer_merge_dev': (_i, [_vp, _vp, _vp, _vp, _i64]),
+    'kbbq_kmer_owner': (_c.c_uint32, [_u64, _i]),
 }
 
 

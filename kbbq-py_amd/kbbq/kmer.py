@@ -10,8 +10,14 @@ solid.  The rule, base by base, is in include/kbbq_hip.h; tests/kmer_model.py is
 Planes are [n, pitch] uint8 seq planes with uint32 meta words (length in bits 0..15).  NumPy arrays go through the host-buffer
 entry points (slab by slab through page-locked staging, any size); tensors on the GPU through the _dev ones.  There is no
 CPU fallback.
+
+Several ranks (one process per GPU under torch.distributed.run): every rank counts its own reads into a local table, sends each
+key to the rank that owns it (owner(), a hash of the key that shares no bits with its home slot) and merges what it receives
+into its owner table; the histogram is summed over ranks, every rank gathers the solid k-mers of all owner tables into a solid
+table and corrects its own reads against it.  The rank files concatenated are the single-process output, byte for byte.
 """
 import ctypes
+import os
 import sys
 
 import numpy as np
@@ -22,6 +28,26 @@ HIST = 257
 MIN_SLOTS = 1 << 10
 SLOT_BYTES = 12
 LOAD_FACTOR = 0.5
+MAX_BUCKETS = 1024                    # owners of one select (csrc/kbbq_kmer.h KM_MAX_BUCKETS)
+OWNER_SALT = 0x9E3779B97F4A7C15
+
+
+def _mix(x):
+    """The table's 64-bit slot hash (km_hash) of uint64 arrays, wrapping as the device does."""
+    x = x ^ (x >> np.uint64(30))
+    x = x * np.uint64(0xbf58476d1ce4e5b9)
+    x = x ^ (x >> np.uint64(27))
+    x = x * np.uint64(0x94d049bb133111eb)
+    return x ^ (x >> np.uint64(31))
+
+
+def owner(keys, world):
+    """The rank (0..world-1) that owns each canonical key: the high 32 bits of the slot hash of key ^ OWNER_SALT, scaled to
+    `world` (km_owner).  uint32 array of the keys' shape."""
+    k = np.asarray(keys, dtype=np.uint64)
+    with np.errstate(over='ignore'):
+        h = _mix(k ^ np.uint64(OWNER_SALT))
+    return (((h >> np.uint64(32)) * np.uint64(int(world))) >> np.uint64(32)).astype(np.uint32)
 
 
 def _on_device(x):
@@ -92,6 +118,10 @@ class KmerTable:
         except Exception:
             pass
 
+    def clear(self):
+        """Empty every slot (asynchronous on the context's stream)."""
+        N.check(N.load().kbbq_kmer_table_clear_dev(self.ctx.handle, self._h))
+
     def entries(self):
         """(keys uint64, counts uint32) of the occupied slots, sorted by key."""
         lib = N.load()
@@ -132,6 +162,43 @@ def count_kmers(seq_plane, meta, k=31, slots=None, table=None):
             seq_plane = np.ascontiguousarray(seq_plane, dtype=np.uint8)
             meta = np.ascontiguousarray(meta, dtype=np.uint32)
             N.check(lib.kbbq_kmer_count(ctx.handle, table.handle, N.ptr(seq_plane), N.ptr(meta), n, pitch))
+    except N.KmerTableFull as exc:
+        raise _full(table, exc) from None
+    return table
+
+
+def select(table, nbuckets=1, min_count=1):
+    """The occupied slots with count >= min_count, sorted into `nbuckets` (1..MAX_BUCKETS) buckets by owner(key, nbuckets):
+    (keys int64, counts int32, sizes) with keys / counts device tensors holding bucket 0's pairs, then bucket 1's, ... (any
+    order inside a bucket; the keys' bits are uint64) and sizes an int64 NumPy array of the bucket sizes."""
+    from . import _device as dev
+    nbuckets, min_count = int(nbuckets), int(min_count)
+    if not 1 <= nbuckets <= MAX_BUCKETS:
+        raise ValueError('nbuckets must be in 1..%d, got %d' % (MAX_BUCKETS, nbuckets))
+    lib = N.load()
+    ctx = table.ctx
+    sizes = np.zeros(nbuckets, dtype=np.int64)
+    N.check(lib.kbbq_kmer_select_sizes_dev(ctx.handle, table.handle, nbuckets, min_count, N.ptr(sizes)))
+    offsets = np.zeros(nbuckets, dtype=np.int64)
+    np.cumsum(sizes[:-1], out=offsets[1:])
+    total = int(sizes.sum())
+    T = dev._torch()
+    keys = T.empty(max(total, 1), dtype=T.int64, device='cuda')
+    counts = T.empty(max(total, 1), dtype=T.int32, device='cuda')
+    N.check(lib.kbbq_kmer_select_dev(ctx.handle, table.handle, nbuckets, min_count, N.ptr(offsets), N.ptr(keys), N.ptr(counts)))
+    return keys[:total], counts[:total], sizes
+
+
+def merge(table, keys, counts):
+    """Add (key, count) pairs (device tensors of int64 / int32, as select returns) to `table`.  A table that fills raises
+    KmerTableFull."""
+    n = int(keys.shape[0])
+    if int(counts.shape[0]) != n:
+        raise ValueError('merge: %d keys but %d counts' % (n, int(counts.shape[0])))
+    ctx = table.ctx
+    try:
+        N.check(N.load().kbbq_kmer_merge_dev(ctx.handle, table.handle, N.ptr(keys) if n else None, N.ptr(counts) if n else None, n))
+        ctx.status()
     except N.KmerTableFull as exc:
         raise _full(table, exc) from None
     return table
@@ -197,9 +264,12 @@ def correct_reads(seq_plane, meta, k=31, min_count=None, slots=None):
         table.close()
 
 
-def correct_fastq(path, out, k=31, min_count=None, slots=None):
+def correct_fastq(path, out, k=31, min_count=None, slots=None, local_slots=None):
     """Correct every read of a FASTQ file (plain or .gz) and write '@' + name, the corrected sequence, '+' and the qualities
-    as read to `out` (a path, or a text stream).  Returns correct_reads' info."""
+    as read to `out` (a path, or a text stream).  Returns correct_reads' info.  In a process group of several ranks (or of
+    one with KBBQ_DIST_ALWAYS=1) this is correct_fastq_ranks."""
+    if _ranks() is not None:
+        return correct_fastq_ranks(path, out, k=k, min_count=min_count, slots=slots, local_slots=local_slots)
     from . import fastx
     fq = fastx.NativeFastq(path)
     try:
@@ -221,9 +291,229 @@ def correct_fastq(path, out, k=31, min_count=None, slots=None):
     return info
 
 
-def main_correct(path, output=None, k=31, min_count=None, slots=None):
-    """`kbbq correct`: the corrected FASTQ to `output` or stdout; the threshold and the changed bases to stderr."""
-    info = correct_fastq(path, output if output else sys.stdout, k=k, min_count=min_count, slots=slots)
+def main_correct(path, output=None, k=31, min_count=None, slots=None, local_slots=None):
+    """`kbbq correct`: the corrected FASTQ to `output` or stdout; the threshold and the changed bases to stderr (once, by rank
+    0, with the figures of all ranks)."""
+    ranks = _ranks()
+    if ranks is None:
+        info = correct_fastq(path, output if output else sys.stdout, k=k, min_count=min_count, slots=slots)
+        changed = int(np.asarray(info['changed'], dtype=np.int64).sum())
+    else:
+        try:
+            info = correct_fastq_ranks(path, output if output else sys.stdout, k=k, min_count=min_count, slots=slots,
+                                       local_slots=local_slots)
+        except Exception as exc:
+            if not getattr(exc, 'every_rank', False):
+                raise
+            # every rank has this error: each says so before any leaves (a launcher ends the job at the first rank that exits)
+            from . import parallel
+            sys.stderr.write('kbbq correct: rank %d: %s: %s\n' % (ranks[1], type(exc).__name__, exc))
+            sys.stderr.flush()
+            parallel.barrier()
+            sys.exit(1)
+        changed = info['changed_bases']
+        if ranks[1] != 0:
+            return info
     sys.stderr.write('kbbq correct: k=%d min_count=%d reads=%d changed_bases=%d\n'
-                     % (info['k'], info['min_count'], info['reads'], int(np.asarray(info['changed'], dtype=np.int64).sum())))
+                     % (info['k'], info['min_count'], info['reads'], changed))
     return info
+
+
+# ---- several ranks ----------------------------------------------------------------------------------------------------------
+
+def _ranks():
+    """(world, rank) when this process is a rank of a process group of several (or of one, with KBBQ_DIST_ALWAYS=1), else
+    None.  A process that has not imported torch has no process group."""
+    from . import parallel
+    if parallel._dist() is None:
+        return None
+    world, rank = parallel.world_rank()
+    return (world, rank) if world > 1 or os.environ.get('KBBQ_DIST_ALWAYS') else None
+
+
+def _agree(exc, index=0):
+    """parallel.raise_first_error after a data-dependent step; what it raises is marked as every rank's (main_correct)."""
+    from . import parallel
+    try:
+        parallel.raise_first_error(exc, index)
+    except Exception as e:
+        e.every_rank = True
+        raise
+
+
+def _rounds(meta, k, cap):
+    """Contiguous row ranges [lo, hi) of at most `cap` k-mer windows each (a row with more windows is a range of its own)."""
+    w = np.maximum((np.asarray(meta, dtype=np.uint32).astype(np.int64) & 0xFFFF) - k + 1, 0)
+    cum = np.cumsum(w)
+    out, lo = [], 0
+    while lo < len(w):
+        before = int(cum[lo - 1]) if lo else 0
+        hi = max(int(np.searchsorted(cum, before + cap, side='right')), lo + 1)
+        out.append((lo, hi))
+        lo = hi
+    return out
+
+
+def count_kmers_ranks(seq_plane, meta, k=31, slots=None, local_slots=None, windows=None):
+    """This rank's OWNER table: the global count of every k-mer whose owner() is this rank.  Every rank calls it with its own
+    rows (host arrays).  The rows are counted into a local table of `local_slots` slots (default: the shard's windows at a
+    load factor of 0.5, capped by half the device budget) in rounds of contiguous rows that fit it; after every round the
+    occupied slots go to their owners in one exchange and are merged there.  The owner table has `slots` slots (default: the
+    global windows / world * 9/8 at a load factor of 0.5, capped by the budget); `windows` is the global number of windows
+    (summed over the ranks when None).  A table that fills on any rank raises on every rank."""
+    from . import _device as dev
+    from . import parallel
+    world, _ = parallel.world_rank()
+    meta = np.ascontiguousarray(meta, dtype=np.uint32)
+    mine = kmer_total(meta, k)
+    if windows is None:
+        windows = int(parallel.sum_over_ranks(np.array([mine], dtype=np.int64))[0])
+    owned = local = exc = None
+    try:
+        budget = dev.device_budget()
+        if local_slots is None:
+            local_slots = default_slots(mine, budget // 2)
+        rounds = _rounds(meta, k, max(int(int(local_slots) * LOAD_FACTOR), 1))
+        if slots is None:
+            slots = default_slots(-(-int(windows) // world) * 9 // 8, budget)
+        owned = KmerTable(k, slots)
+        if rounds:
+            local = KmerTable(k, local_slots)
+    except Exception as e:                   # noqa: BLE001 -- every rank must reach the agreement
+        exc, rounds = e, []
+    _agree(exc)
+    nrounds = parallel.max_over_ranks(len(rounds))
+    T = dev._torch()
+    for i in range(nrounds):
+        exc = None
+        if i < len(rounds):
+            lo, hi = rounds[i]
+            try:
+                if i:
+                    local.clear()
+                count_kmers(seq_plane[lo:hi], meta[lo:hi], table=local)
+            except Exception as e:           # noqa: BLE001
+                exc = e
+        _agree(exc)
+        if i < len(rounds):
+            keys, counts, sizes = select(local, world, 1)
+        else:                                # this rank's reads are done: it joins with nothing to send
+            keys = T.empty(0, dtype=T.int64, device='cuda')
+            counts = T.empty(0, dtype=T.int32, device='cuda')
+            sizes = np.zeros(world, dtype=np.int64)
+        keys, got = parallel.all_to_all_rows(keys, sizes)
+        counts, _ = parallel.all_to_all_rows(counts, sizes, got)
+        exc = None
+        try:
+            merge(owned, keys, counts)
+        except Exception as e:               # noqa: BLE001
+            exc = e
+        del keys, counts
+        _agree(exc)
+    if local is not None:
+        local.close()
+    return owned
+
+
+def kmer_histogram_ranks(table):
+    """kmer_histogram of the owner tables of all ranks, summed: the histogram of the whole input."""
+    from . import parallel
+    return parallel.sum_over_ranks(kmer_histogram(table))
+
+
+def solid_table(owned, min_count):
+    """The k-mers with count >= min_count of every rank's owner table, gathered into a table of their own on every rank (sized
+    for them at a load factor of 0.5).  Closes `owned`.  Correcting against it at min_count decides every base as the whole
+    table would: a solid key carries its global count, every other key is absent (count 0 < min_count)."""
+    from . import _device as dev
+    from . import parallel
+    keys, counts, _ = select(owned, 1, min_count)
+    k = owned.k
+    owned.close()
+    keys = parallel.all_gather_rows(keys)
+    counts = parallel.all_gather_rows(counts)
+    table = exc = None
+    try:
+        table = merge(KmerTable(k, default_slots(int(keys.shape[0]), dev.device_budget())), keys, counts)
+    except Exception as e:                   # noqa: BLE001
+        exc = e
+    _agree(exc)
+    return table
+
+
+def _read_shard(path, rank, world):
+    """(names, seq plane, qual plane, meta) of this rank's records.  A plain file: the records that start in this rank's
+    byte range, cut at record starts (kbbq_fastq_sync_offset) -- nobody reads the whole file.  A .gz file: every rank
+    inflates all of it and takes parallel.shard_range of the records."""
+    from . import fastx
+    from . import parallel
+    lib = N.load()
+    if fastx._is_gzip(path):
+        fq = fastx.NativeFastq(path)
+    else:
+        size = os.path.getsize(path)
+
+        def cut(r):
+            if r <= 0 or r >= world:
+                return 0 if r <= 0 else size
+            off = int(lib.kbbq_fastq_sync_offset(str(path).encode(), size * r // world))
+            if off < 0:
+                N.check(N.KBBQ_E_ARG)
+            return off
+        lo_b = cut(rank)
+        fq = fastx.NativeFastq.open_range(path, lo_b, max(cut(rank + 1), lo_b), 0, 0)
+    try:
+        n, S = fq.scan(None, False)[:2]
+        lo, hi = parallel.shard_range(n, rank, world) if fastx._is_gzip(path) else (0, n)
+        seq, _, qual, meta = fq.fill(None, False, hi - lo, fastx.pitch_for(S), first=lo)
+        names = [fq.name(i) for i in range(lo, hi)]
+    finally:
+        fq.close()
+    return names, seq, qual, meta
+
+
+def correct_fastq_ranks(path, out, k=31, min_count=None, slots=None, local_slots=None):
+    """correct_fastq on every rank of the process group: each rank reads, counts and corrects its own records and writes them
+    to `out`.rankNNNN (`out` itself with one rank) or, for a stream, to `out` in rank order.  The threshold comes from the
+    global histogram; info carries this rank's per-read changes and the global 'reads' and 'changed_bases'."""
+    from . import fastx
+    from . import parallel
+    world, rank = parallel.world_rank()
+    shard = exc = None
+    try:
+        shard = _read_shard(path, rank, world)
+    except Exception as e:                   # noqa: BLE001
+        exc = e
+    _agree(exc)
+    names, seq, qual, meta = shard
+    everyone = parallel.all_gather_object((len(names), kmer_total(meta, k)))
+    reads, windows = sum(x[0] for x in everyone), sum(x[1] for x in everyone)
+    owned = count_kmers_ranks(seq, meta, k=k, slots=slots, local_slots=local_slots, windows=windows)
+    hist = None
+    if min_count is None:
+        hist = kmer_histogram_ranks(owned)
+        t = solid_threshold(hist)
+    else:
+        t = int(min_count)
+    if t < 1:
+        raise ValueError('min_count must be >= 1, got %d' % t)
+    table = solid_table(owned, t)
+    fixed = changed = exc = None
+    try:
+        fixed, changed = correct_with(table, seq, meta, t)
+    except Exception as e:                   # noqa: BLE001
+        exc = e
+    finally:
+        table.close()
+    _agree(exc)
+    total = int(parallel.sum_over_ranks(np.array([changed.astype(np.int64).sum()], dtype=np.int64))[0])
+    text = fastx.format_fastq(names, fixed, qual, meta & 0xFFFF)
+    if isinstance(out, str):
+        with open(out if world == 1 else '%s.rank%04d' % (out, rank), 'w', encoding='latin-1', newline='') as fh:
+            fh.write(text)
+    else:
+        def write():
+            out.write(text)
+            out.flush()
+        parallel.in_rank_order(write)
+    return dict(k=k, min_count=t, hist=hist, changed=changed, reads=reads, changed_bases=total)

@@ -57,14 +57,18 @@ def bqsr(args):
 def correct(args):
     import os
     import sys
-    if int(os.environ.get('WORLD_SIZE', '1')) > 1:
-        sys.exit('kbbq correct: runs on one GPU only -- counting k-mers across ranks would need an exchange of tables; '
-                 'run it without torch.distributed.run')
+    if 'RANK' in os.environ:
+        from . import parallel
+        parallel.init_from_env()             # one process per GPU under torch.distributed.run; no-op for a single rank
+    elif int(os.environ.get('WORLD_SIZE', '1')) > 1:
+        sys.exit('kbbq correct: WORLD_SIZE > 1 but no RANK: start one process per GPU with torch.distributed.run, or run '
+                 'it on one GPU without WORLD_SIZE')
     from . import kmer
     if 'torch' not in sys.modules and not os.environ.get('KBBQ_USE_TORCH'):
         from . import _device
         _device.use_native_memory()          # as `recalibrate` on one GPU: no torch import
-    kmer.main_correct(args.fastq, output=args.output, k=args.kmer, min_count=args.min_count, slots=args.slots)
+    kmer.main_correct(args.fastq, output=args.output, k=args.kmer, min_count=args.min_count, slots=args.slots,
+                      local_slots=args.local_slots)
 
 
 def main(argv=None):
@@ -130,8 +134,15 @@ def main(argv=None):
                     help='k-mers seen at least this often are solid (default: the first valley of the count histogram)')
     cp.add_argument('--slots', type=int, default=None,
                     help='hash table slots, a power of two (default: every k-mer of the input at a load factor of 0.5, '
-                         'capped by the device budget)')
-    cp.add_argument('-o', '--output', default=None, help='Write the corrected FASTQ to this file instead of stdout')
+                         'capped by the device budget); under torch.distributed.run: the slots of every rank\'s share of the '
+                         'k-mers (default: the input\'s k-mers / ranks * 9/8 at a load factor of 0.5)')
+    cp.add_argument('--local-slots', type=int, default=None,
+                    help='under torch.distributed.run: slots of the table every rank counts its own reads into before they go '
+                         'to the ranks that own them, a power of two (default: the rank\'s k-mers at a load factor of 0.5, '
+                         'capped by half the device budget); a smaller table counts the reads in several rounds')
+    cp.add_argument('-o', '--output', default=None,
+                    help='Write the corrected FASTQ to this file instead of stdout; under torch.distributed.run every rank '
+                         'writes FILE.rankNNNN, to be concatenated in rank order.')
     cp.set_defaults(command=correct)
 
     args = parser.parse_args(argv)

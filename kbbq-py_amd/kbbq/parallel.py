@@ -197,3 +197,108 @@ def max_over_ranks(value):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         return int(t.item())
     return int(value)
+
+
+EXCHANGE_BYTES = 256 << 20   # what one all-to-all or all-gather call moves per rank at most: RCCL's all_to_all_single returned
+                             # corrupt rows beyond ~1 GB in one call ("Ranks"); larger exchanges go in pieces
+
+
+def _exchange_device(dist, like):
+    """Where a collective's tensors live: the GPU under nccl (RCCL), the host under gloo."""
+    return like.device if dist.get_backend() == 'nccl' else 'cpu'
+
+
+def _rows_per_call(t, world):
+    row = t.element_size()
+    for d in t.shape[1:]:
+        row *= int(d)
+    return max(1, EXCHANGE_BYTES // (max(row, 1) * world))
+
+
+def sum_over_ranks(values):
+    """Element-wise SUM over all ranks of an int64 vector (NumPy in, NumPy out); without a process group: the values."""
+    v = np.ascontiguousarray(values, dtype=np.int64)
+    dist = _dist()
+    if dist is None:
+        return v.copy()
+    import torch
+    t = torch.from_numpy(v.copy())
+    if dist.get_backend() == 'nccl':
+        t = t.cuda()
+    dist.all_reduce(t, op=dist.ReduceOp.SUM)
+    return t.cpu().numpy()
+
+
+def all_to_all_rows(send, sizes, recv_sizes=None):
+    """Rows sizes[0] of `send` (a tensor, rows along its first axis) to rank 0, the next sizes[1] to rank 1, ...; returns
+    (the rows every rank sent to this one, in rank order, on send's device; recv_sizes).  The split sizes travel first, in an
+    all-to-all of one int64 per rank, unless `recv_sizes` (what a previous call with the same sizes returned) is given.
+    Device tensors under nccl, host copies under gloo; calls of at most EXCHANGE_BYTES per rank (every rank makes as many).
+    Without a process group: (send, sizes)."""
+    sizes = [int(x) for x in sizes]
+    dist = _dist()
+    if dist is None:
+        return send[:sum(sizes)], sizes
+    import torch
+    world = dist.get_world_size()
+    if len(sizes) != world or sum(sizes) != int(send.shape[0]):
+        raise ValueError('all_to_all_rows: %d split sizes summing to %d for %d ranks and %d rows'
+                         % (len(sizes), sum(sizes), world, int(send.shape[0])))
+    where = _exchange_device(dist, send)
+    if recv_sizes is None:
+        mine = torch.tensor(sizes, dtype=torch.int64, device=where)
+        theirs = torch.empty_like(mine)
+        dist.all_to_all_single(theirs, mine)
+        recv_sizes = [int(x) for x in theirs.tolist()]
+    recv_sizes = [int(x) for x in recv_sizes]
+    per = _rows_per_call(send, world)
+    calls = max_over_ranks(-(-max(sizes + recv_sizes) // per))
+    src = send.to(where)
+    got = torch.empty((sum(recv_sizes),) + tuple(send.shape[1:]), dtype=send.dtype, device=where)
+    s_off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    r_off = np.concatenate([[0], np.cumsum(recv_sizes)]).astype(np.int64)
+    for c in range(calls):
+        lo = c * per
+        s_n = [min(max(x - lo, 0), per) for x in sizes]
+        r_n = [min(max(x - lo, 0), per) for x in recv_sizes]
+        piece = torch.cat([src[s_off[j] + lo:s_off[j] + lo + s_n[j]] for j in range(world)])
+        into = torch.empty((sum(r_n),) + tuple(send.shape[1:]), dtype=send.dtype, device=where)
+        dist.all_to_all_single(into, piece, output_split_sizes=r_n, input_split_sizes=s_n)
+        at = 0
+        for j in range(world):
+            got[r_off[j] + lo:r_off[j] + lo + r_n[j]] = into[at:at + r_n[j]]
+            at += r_n[j]
+    return got.to(send.device), recv_sizes
+
+
+def all_gather_rows(rows):
+    """The rows (a tensor, rows along its first axis) of rank 0, then rank 1, ... on every rank, on rows' device.  The row
+    counts are gathered first; every call carries the same number of rows from every rank (padded), at most EXCHANGE_BYTES
+    per rank.  Without a process group: rows."""
+    dist = _dist()
+    if dist is None:
+        return rows
+    import torch
+    world = dist.get_world_size()
+    where = _exchange_device(dist, rows)
+    n = torch.tensor([int(rows.shape[0])], dtype=torch.int64, device=where)
+    ns = [torch.empty_like(n) for _ in range(world)]
+    dist.all_gather(ns, n)
+    ns = [int(x.item()) for x in ns]
+    tail = tuple(rows.shape[1:])
+    out = torch.empty((sum(ns),) + tail, dtype=rows.dtype, device=where)
+    off = np.concatenate([[0], np.cumsum(ns)]).astype(np.int64)
+    mine = rows.to(where)
+    me = dist.get_rank()
+    per = _rows_per_call(rows, world)
+    for lo in range(0, max(ns), per):
+        m = min(per, max(ns) - lo)
+        pad = torch.zeros((m,) + tail, dtype=rows.dtype, device=where)
+        have = min(max(ns[me] - lo, 0), m)
+        pad[:have] = mine[lo:lo + have]
+        parts = [torch.empty_like(pad) for _ in range(world)]
+        dist.all_gather(parts, pad)
+        for j in range(world):
+            c = min(max(ns[j] - lo, 0), m)
+            out[off[j] + lo:off[j] + lo + c] = parts[j][:c]
+    return out.to(rows.device)
