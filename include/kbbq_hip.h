@@ -738,6 +738,49 @@ int kbbq_kmer_select_dev(kbbq_ctx* ctx, const kbbq_kmer_table* table, int nbucke
 int kbbq_kmer_merge_dev(kbbq_ctx* ctx, kbbq_kmer_table* table, const uint64_t* d_keys, const uint32_t* d_counts, int64_t n);
 uint32_t kbbq_kmer_owner(uint64_t key, int nbuckets);
 
+/* ---- prefilter: k-mers seen once stay out of the table (kbbq correct --prefilter; csrc/kbbq_kmer.h) ---------------------------
+ * Nothing after the count looks at a k-mer seen once (the threshold starts at 2), and most distinct k-mers of real reads are
+ * such.  A k-mer filter is two device arrays of `words` (a power of two) uint64 words, `seen` and `twice`, zero when created;
+ * kbbq_kmer_filter_bytes(words) = 16 * words.  A canonical key has one word index and one mask of up to 4 bits, the same in
+ * both arrays:
+ *     h    = mix(key ^ 0xD6E8FEB86659FD93)        mix: the table's slot hash; a salt of its own (not the owner's)
+ *     word = (h >> 24) & (words - 1)
+ *     mask = OR over j = 0..3 of  1 << ((h >> 6 j) & 63)
+ * Pass 1, kbbq_kmer_prefilter_dev, for every k-mer window of the rows (the windows kbbq_kmer_count_dev counts): OR mask into
+ * seen[word]; if the value before held every bit of mask (the key, or a false positive, came before), OR mask into twice[word],
+ * and where that OR set a new bit add one to the filter's `admitted` counter.  Both tests read the value one atomic returned
+ * (or a load that already showed the whole mask: bits are only ever set), so of all occurrences of a key at most one finds its
+ * mask incomplete: EVERY k-mer that occurs twice or more ends up in `twice`, whatever the thread order -- no false negatives.
+ * `seen` after the pass is the OR of the masks of all distinct keys and does not depend on order; `twice` and `admitted` do
+ * (which once-seen keys slip in as false positives varies).  `admitted` can undercount the keys in `twice` by those whose mask
+ * other keys had completed there.  Passes over several row sets compose, as counting does.
+ * Pass 2, kbbq_kmer_count_filtered_dev: kbbq_kmer_count_dev for the windows whose mask is wholly in twice[word]; any other
+ * window is skipped.  Run after pass 1 has seen ALL rows, the table holds every k-mer of count >= 2 with its exact count,
+ * some k-mers with exact count 1 (false positives) and nothing else: the histogram from c = 2 up, the threshold, the solid set
+ * and kbbq_kmer_correct_dev's output at min_count >= 2 equal the unfiltered ones bit for bit.  h[1] counts the admitted
+ * singletons only, so min_count = 1 has no meaning with a filtered table.  A table that fills reports KBBQ_E_FULL as above.
+ * kbbq_kmer_filter_admitted is synchronous.  kbbq_kmer_filter_release_seen_dev (synchronous) frees `seen` once pass 1 is
+ * over -- before the table is allocated, sized from `admitted` -- after which kbbq_kmer_filter_info returns NULL for it and
+ * the filter takes no further pass 1 or clear.  kbbq_kmer_filter_clear_dev zeroes both arrays and the counter.
+ * kbbq_kmer_prefilter / kbbq_kmer_count_filtered: the same from host buffers, each one more pass over the page-locked slabs
+ * of kbbq_kmer_count.                                                                                                       */
+typedef struct kbbq_kmer_filter kbbq_kmer_filter;
+size_t kbbq_kmer_filter_bytes(int64_t words);
+int kbbq_kmer_filter_create_dev(kbbq_ctx* ctx, int64_t words, kbbq_kmer_filter** out);
+int kbbq_kmer_filter_free_dev(kbbq_ctx* ctx, kbbq_kmer_filter* filter);
+int kbbq_kmer_filter_clear_dev(kbbq_ctx* ctx, kbbq_kmer_filter* filter);
+int kbbq_kmer_filter_info(const kbbq_kmer_filter* filter, int64_t* words, void** d_seen, void** d_twice);
+int kbbq_kmer_filter_admitted(kbbq_ctx* ctx, const kbbq_kmer_filter* filter, int64_t* admitted);
+int kbbq_kmer_filter_release_seen_dev(kbbq_ctx* ctx, kbbq_kmer_filter* filter);
+int kbbq_kmer_prefilter_dev(kbbq_ctx* ctx, kbbq_kmer_filter* filter, int k, const uint8_t* d_seq, const uint32_t* d_meta,
+                            int64_t nreads, int pitch);
+int kbbq_kmer_count_filtered_dev(kbbq_ctx* ctx, kbbq_kmer_table* table, const kbbq_kmer_filter* filter, const uint8_t* d_seq,
+                                 const uint32_t* d_meta, int64_t nreads, int pitch);
+int kbbq_kmer_prefilter(kbbq_ctx* ctx, kbbq_kmer_filter* filter, int k, const uint8_t* seq, const uint32_t* meta, int64_t nreads,
+                        int pitch);
+int kbbq_kmer_count_filtered(kbbq_ctx* ctx, kbbq_kmer_table* table, const kbbq_kmer_filter* filter, const uint8_t* seq,
+                             const uint32_t* meta, int64_t nreads, int pitch);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2182,20 +2182,30 @@ int kbbq_kmer_table_info(const kbbq_kmer_table* t, int* k, int64_t* slots, void*
     return KBBQ_OK;
 }
 
-// rows per workgroup and LDS words per row-chunk of the count / correct kernels
+// rows per workgroup and LDS words per row-chunk of the kernels that walk k-mer windows; the table's fields stay unset
+static int kmer_rows(kbbq_ctx* c, const char* who, int k, const uint8_t* d_seq, const uint32_t* d_meta, int64_t n, int pitch,
+                     KmerParams& p, int lds_words, size_t* lds)
+{
+    int rc = check_planes(who, n, pitch, d_seq, d_seq, d_seq);
+    if (rc) return rc;
+    if (n > 0 && !d_meta) return fail(KBBQ_E_ARG, "%s: NULL meta", who);
+    p.seq = d_seq; p.meta = d_meta; p.nrows = n; p.pitch = pitch; p.cpr = pitch / 16; p.k = k;
+    p.rows_per_wg = std::max(1, KM_THREADS / p.cpr);
+    p.keys = nullptr; p.counts = nullptr; p.mask = 0; p.status = c->d_status;
+    p.min_count = 1; p.out = nullptr; p.changed = nullptr;
+    *lds = ((size_t)lds_words * p.rows_per_wg * p.cpr + p.rows_per_wg) * 4;
+    if (*lds > (size_t)c->lds_bytes) return fail(KBBQ_E_ARG, "%s: pitch %d needs %zu bytes of LDS", who, pitch, *lds);
+    return KBBQ_OK;
+}
+
+// ... of the count / correct kernels
 static int kmer_geometry(kbbq_ctx* c, const char* who, const kbbq_kmer_table* t, const uint8_t* d_seq, const uint32_t* d_meta,
                          int64_t n, int pitch, KmerParams& p, int lds_words, size_t* lds)
 {
     if (!c || !t) return fail(KBBQ_E_ARG, "%s: NULL ctx or table", who);
-    int rc = check_planes(who, n, pitch, d_seq, d_seq, d_seq);
+    int rc = kmer_rows(c, who, t->k, d_seq, d_meta, n, pitch, p, lds_words, lds);
     if (rc) return rc;
-    if (n > 0 && !d_meta) return fail(KBBQ_E_ARG, "%s: NULL meta", who);
-    p.seq = d_seq; p.meta = d_meta; p.nrows = n; p.pitch = pitch; p.cpr = pitch / 16; p.k = t->k;
-    p.rows_per_wg = std::max(1, KM_THREADS / p.cpr);
-    p.keys = t->keys; p.counts = t->counts; p.mask = (u64)t->slots - 1; p.status = c->d_status;
-    p.min_count = 1; p.out = nullptr; p.changed = nullptr;
-    *lds = ((size_t)lds_words * p.rows_per_wg * p.cpr + p.rows_per_wg) * 4;
-    if (*lds > (size_t)c->lds_bytes) return fail(KBBQ_E_ARG, "%s: pitch %d needs %zu bytes of LDS", who, pitch, *lds);
+    p.keys = t->keys; p.counts = t->counts; p.mask = (u64)t->slots - 1;
     return KBBQ_OK;
 }
 
@@ -2357,6 +2367,155 @@ int kbbq_kmer_correct(kbbq_ctx* c, const kbbq_kmer_table* t, const uint8_t* seq,
     HIPCHK(hipMemcpyAsync(changed, dc.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     return KBBQ_OK;
+}
+
+// ---- prefilter: k-mers seen once stay out of the table (kbbq_kmer.h) ----------------------------------------------------------
+struct kbbq_kmer_filter {
+    int64_t words = 0;
+    u64* seen = nullptr;              // [words]; NULL after kbbq_kmer_filter_release_seen_dev
+    u64* twice = nullptr;             // [words]
+    u64* admitted = nullptr;          // one counter
+};
+
+size_t kbbq_kmer_filter_bytes(int64_t words) { return words > 0 ? (size_t)words * 16 : 0; }
+
+int kbbq_kmer_filter_create_dev(kbbq_ctx* c, int64_t words, kbbq_kmer_filter** out)
+{
+    if (!c || !out) return fail(KBBQ_E_ARG, "kbbq_kmer_filter_create_dev: NULL argument");
+    *out = nullptr;
+    if (words < 1 || (words & (words - 1)) || words > ((int64_t)1 << 40))
+        return fail(KBBQ_E_ARG, "kbbq_kmer_filter_create_dev: words must be a power of two in 1..2^40, got %lld", (long long)words);
+    HIPCHK(hipSetDevice(c->device));
+    kbbq_kmer_filter* f = new kbbq_kmer_filter;
+    f->words = words;
+    hipError_t e = hipMalloc((void**)&f->seen, (size_t)words * 8);
+    if (e == hipSuccess) e = hipMalloc((void**)&f->twice, (size_t)words * 8);
+    if (e == hipSuccess) e = hipMalloc((void**)&f->admitted, 8);
+    if (e == hipSuccess) e = hipMemsetAsync(f->seen, 0, (size_t)words * 8, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(f->twice, 0, (size_t)words * 8, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(f->admitted, 0, 8, c->stream);
+    if (e != hipSuccess) {
+        (void)kbbq_kmer_filter_free_dev(c, f);
+        return fail(KBBQ_E_HIP, "kbbq_kmer_filter_create_dev: %lld words (%zu bytes): %s", (long long)words,
+                    kbbq_kmer_filter_bytes(words), hipGetErrorString(e));
+    }
+    *out = f;
+    return KBBQ_OK;
+}
+
+int kbbq_kmer_filter_free_dev(kbbq_ctx* c, kbbq_kmer_filter* f)
+{
+    if (!f) return KBBQ_OK;
+    if (c) { (void)hipSetDevice(c->device); (void)hipStreamSynchronize(c->stream); }
+    if (f->seen) (void)hipFree(f->seen);
+    if (f->twice) (void)hipFree(f->twice);
+    if (f->admitted) (void)hipFree(f->admitted);
+    delete f;
+    return KBBQ_OK;
+}
+
+int kbbq_kmer_filter_release_seen_dev(kbbq_ctx* c, kbbq_kmer_filter* f)
+{
+    if (!c || !f) return fail(KBBQ_E_ARG, "kbbq_kmer_filter_release_seen_dev: NULL ctx or filter");
+    if (!f->seen) return KBBQ_OK;
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->stream));            // the last prefilter pass has run
+    HIPCHK(hipFree(f->seen));
+    f->seen = nullptr;
+    return KBBQ_OK;
+}
+
+int kbbq_kmer_filter_clear_dev(kbbq_ctx* c, kbbq_kmer_filter* f)
+{
+    if (!c || !f) return fail(KBBQ_E_ARG, "kbbq_kmer_filter_clear_dev: NULL ctx or filter");
+    if (!f->seen) return fail(KBBQ_E_ARG, "kbbq_kmer_filter_clear_dev: the filter's `seen` array has been released");
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipMemsetAsync(f->seen, 0, (size_t)f->words * 8, c->stream));
+    HIPCHK(hipMemsetAsync(f->twice, 0, (size_t)f->words * 8, c->stream));
+    HIPCHK(hipMemsetAsync(f->admitted, 0, 8, c->stream));
+    return KBBQ_OK;
+}
+
+int kbbq_kmer_filter_info(const kbbq_kmer_filter* f, int64_t* words, void** d_seen, void** d_twice)
+{
+    if (!f) return fail(KBBQ_E_ARG, "kbbq_kmer_filter_info: filter is NULL");
+    if (words) *words = f->words;
+    if (d_seen) *d_seen = f->seen;
+    if (d_twice) *d_twice = f->twice;
+    return KBBQ_OK;
+}
+
+int kbbq_kmer_filter_admitted(kbbq_ctx* c, const kbbq_kmer_filter* f, int64_t* admitted)
+{
+    if (!c || !f || !admitted) return fail(KBBQ_E_ARG, "kbbq_kmer_filter_admitted: NULL argument");
+    HIPCHK(hipSetDevice(c->device));
+    u64 v = 0;
+    HIPCHK(hipMemcpyAsync(&v, f->admitted, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    *admitted = (int64_t)v;
+    return KBBQ_OK;
+}
+
+static KmerFilterParams kmer_filter_params(const kbbq_kmer_filter* f)
+{
+    KmerFilterParams q;
+    q.seen = f->seen; q.twice = f->twice; q.wmask = (u64)f->words - 1; q.admitted = f->admitted;
+    return q;
+}
+
+int kbbq_kmer_prefilter_dev(kbbq_ctx* c, kbbq_kmer_filter* f, int k, const uint8_t* d_seq, const uint32_t* d_meta, int64_t n, int pitch)
+{
+    if (!c || !f) return fail(KBBQ_E_ARG, "kbbq_kmer_prefilter_dev: NULL ctx or filter");
+    if (k < 8 || k > 32) return fail(KBBQ_E_ARG, "kbbq_kmer_prefilter_dev: k must be in 8..32, got %d", k);
+    if (!f->seen) return fail(KBBQ_E_ARG, "kbbq_kmer_prefilter_dev: the filter's `seen` array has been released");
+    KmerParams p; size_t lds = 0;
+    int rc = kmer_rows(c, "kbbq_kmer_prefilter_dev", k, d_seq, d_meta, n, pitch, p, 2, &lds);
+    if (rc || n == 0) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    const KmerFilterParams fp = kmer_filter_params(f);
+    return kmer_launches(p, [&](const KmerParams& q, unsigned grid) {
+        hipLaunchKernelGGL(km_prefilter, dim3(grid), dim3(KM_THREADS), lds, c->stream, q, fp);
+    });
+}
+
+int kbbq_kmer_count_filtered_dev(kbbq_ctx* c, kbbq_kmer_table* t, const kbbq_kmer_filter* f, const uint8_t* d_seq,
+                                 const uint32_t* d_meta, int64_t n, int pitch)
+{
+    if (!f) return fail(KBBQ_E_ARG, "kbbq_kmer_count_filtered_dev: filter is NULL");
+    KmerParams p; size_t lds = 0;
+    int rc = kmer_geometry(c, "kbbq_kmer_count_filtered_dev", t, d_seq, d_meta, n, pitch, p, 2, &lds);
+    if (rc || n == 0) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    const KmerFilterParams fp = kmer_filter_params(f);
+    return kmer_launches(p, [&](const KmerParams& q, unsigned grid) {
+        hipLaunchKernelGGL(km_count_filtered, dim3(grid), dim3(KM_THREADS), lds, c->stream, q, fp);
+    });
+}
+
+int kbbq_kmer_prefilter(kbbq_ctx* c, kbbq_kmer_filter* f, int k, const uint8_t* seq, const uint32_t* meta, int64_t n, int pitch)
+{
+    if (!c || !f) return fail(KBBQ_E_ARG, "kbbq_kmer_prefilter: NULL ctx or filter");
+    if (n < 0 || pitch <= 0 || (pitch & 15)) return fail(KBBQ_E_ARG, "kbbq_kmer_prefilter: bad n/pitch");
+    if (n > 0 && (!seq || !meta)) return fail(KBBQ_E_ARG, "kbbq_kmer_prefilter: NULL plane");
+    if (n == 0) return KBBQ_OK;
+    HIPCHK(hipSetDevice(c->device));
+    // a slab: seq | meta
+    return stage_run(c, "kbbq_kmer_prefilter", {seq}, meta, nullptr, n, pitch, [&](uint8_t* d, size_t plane, int64_t m) {
+        return kbbq_kmer_prefilter_dev(c, f, k, d, (const uint32_t*)(d + plane), m, pitch);
+    });
+}
+
+int kbbq_kmer_count_filtered(kbbq_ctx* c, kbbq_kmer_table* t, const kbbq_kmer_filter* f, const uint8_t* seq, const uint32_t* meta,
+                             int64_t n, int pitch)
+{
+    if (!c || !t || !f) return fail(KBBQ_E_ARG, "kbbq_kmer_count_filtered: NULL ctx, table or filter");
+    if (n < 0 || pitch <= 0 || (pitch & 15)) return fail(KBBQ_E_ARG, "kbbq_kmer_count_filtered: bad n/pitch");
+    if (n > 0 && (!seq || !meta)) return fail(KBBQ_E_ARG, "kbbq_kmer_count_filtered: NULL plane");
+    if (n == 0) return KBBQ_OK;
+    HIPCHK(hipSetDevice(c->device));
+    return stage_run(c, "kbbq_kmer_count_filtered", {seq}, meta, nullptr, n, pitch, [&](uint8_t* d, size_t plane, int64_t m) {
+        return kbbq_kmer_count_filtered_dev(c, t, f, d, (const uint32_t*)(d + plane), m, pitch);
+    });
 }
 
 } // extern "C"

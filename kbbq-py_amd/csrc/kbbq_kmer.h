@@ -26,6 +26,15 @@
 // the same mix taken of the key XOR a constant, scaled to 0..W-1.  It shares no bits with the home slot (km_hash(key) & mask),
 // so the keys one rank owns spread over all home slots of its table.  km_select_sizes / km_select_scatter sort the occupied
 // slots with count >= min_count into buckets by owner (one bucket: compaction), km_merge adds (key, count) pairs to a table.
+//
+// Prefilter (kbbq correct --prefilter): a filter is two arrays of `words` (a power of two) 64-bit words, `seen` and `twice`.
+// A canonical key has one word index and one mask of up to 4 bits, the same in both arrays (km_filter_index).  km_prefilter
+// ORs the mask into seen[word]; a key whose mask was whole there before its OR (the key, or a false positive, came before) ORs it
+// into twice[word], and an OR into `twice` that set a new bit adds one to `admitted`.  Both tests of a window read the value
+// ONE atomic returned, so of the occurrences of a key at most one finds its mask incomplete: every key that occurs twice or
+// more is in `twice`, whatever the thread order.  Bits are only ever set, so a relaxed load that shows the whole mask is
+// final and the atomic is skipped.  km_count_filtered is km_count for the windows whose mask is whole in `twice`: the table
+// then holds every key of count >= 2 with its exact count and some keys of count 1 (false positives), nothing else.
 #pragma once
 #include "kbbq_kernels.h"
 
@@ -161,6 +170,86 @@ __global__ __launch_bounds__(KM_THREADS) void km_count(KmerParams p)
         for (int o = 0; o < 16; ++o) {
             if ((b >> o) & kmask) continue;
             if (!km_insert(p, km_canonical(km_window(x, o, p.k), p.k))) {
+                atomicMin(p.status + ST_KMER, (u64)(row0 + r));
+                return;
+            }
+        }
+    }
+}
+
+// ---- prefilter: keys seen once stay out of the table ---------------------------------------------------------------------------
+constexpr u64 KM_FILTER_SALT = 0xD6E8FEB86659FD93ull;
+
+struct KmerFilterParams {
+    u64* seen; u64* twice; u64 wmask;  // words - 1
+    u64* admitted;                     // OR-operations into `twice` that set a new bit
+};
+
+// word index and mask of a canonical key: 4 six-bit fields of the low 24 bits of the mix pick the bits, the bits above the word
+__host__ __device__ __forceinline__ u64 km_filter_index(u64 key, u64 wmask, u64* mask)
+{
+    const u64 h = km_hash(key ^ KM_FILTER_SALT);
+    *mask = 1ull << (h & 63) | 1ull << ((h >> 6) & 63) | 1ull << ((h >> 12) & 63) | 1ull << ((h >> 18) & 63);
+    return (h >> 24) & wmask;
+}
+
+// OR `mask` into *p unless a load shows it whole already; the value before (a load that shows the mask whole is that value)
+__device__ __forceinline__ u64 km_filter_or(u64* p, u64 mask)
+{
+    const u64 cur = km_load_key(p);
+    return (cur & mask) == mask ? cur : atomicOr(p, mask);
+}
+
+__global__ __launch_bounds__(KM_THREADS) void km_prefilter(KmerParams p, KmerFilterParams f)
+{
+    extern __shared__ u32 km_lds[];
+    const int E = p.rows_per_wg * p.cpr;
+    u32* code = km_lds; u32* brk = km_lds + E; u32* adm = km_lds + 2 * E;
+    const int64_t row0 = (int64_t)blockIdx.x * p.rows_per_wg;
+    if (threadIdx.x == 0) *adm = 0;
+    const int nr = km_load_chunks(p, row0, code, brk);
+    __syncthreads();
+    const u64 kmask = (1ull << p.k) - 1;
+    u32 mine = 0;
+    for (int e = threadIdx.x; e < nr * p.cpr; e += KM_THREADS) {
+        const int r = e / p.cpr, ch = e - r * p.cpr;
+        u64 b;
+        const unsigned __int128 x = km_words(p, code, brk, r * p.cpr, ch, 3, &b);
+        for (int o = 0; o < 16; ++o) {
+            if ((b >> o) & kmask) continue;
+            u64 m;
+            const u64 w = km_filter_index(km_canonical(km_window(x, o, p.k), p.k), f.wmask, &m);
+            if ((km_filter_or(f.seen + w, m) & m) != m) continue;         // first of its mask
+            if ((km_filter_or(f.twice + w, m) & m) != m) ++mine;
+        }
+    }
+    if (mine) atomicAdd(adm, mine);
+    __syncthreads();
+    if (threadIdx.x == 0 && *adm) atomicAdd(f.admitted, (u64)*adm);
+}
+
+// km_count of the windows whose mask is whole in `twice`
+__global__ __launch_bounds__(KM_THREADS) void km_count_filtered(KmerParams p, KmerFilterParams f)
+{
+    extern __shared__ u32 km_lds[];
+    const int E = p.rows_per_wg * p.cpr;
+    u32* code = km_lds; u32* brk = km_lds + E;
+    const int64_t row0 = (int64_t)blockIdx.x * p.rows_per_wg;
+    const int nr = km_load_chunks(p, row0, code, brk);
+    __syncthreads();
+    if (__hip_atomic_load(p.status + ST_KMER, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != ~0ull) return;   // the table is full
+    const u64 kmask = (1ull << p.k) - 1;
+    for (int e = threadIdx.x; e < nr * p.cpr; e += KM_THREADS) {
+        const int r = e / p.cpr, ch = e - r * p.cpr;
+        u64 b;
+        const unsigned __int128 x = km_words(p, code, brk, r * p.cpr, ch, 3, &b);
+        for (int o = 0; o < 16; ++o) {
+            if ((b >> o) & kmask) continue;
+            const u64 key = km_canonical(km_window(x, o, p.k), p.k);
+            u64 m;
+            const u64 w = km_filter_index(key, f.wmask, &m);
+            if ((f.twice[w] & m) != m) continue;                          // seen once
+            if (!km_insert(p, key)) {
                 atomicMin(p.status + ST_KMER, (u64)(row0 + r));
                 return;
             }

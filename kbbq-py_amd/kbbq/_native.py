@@ -179,6 +179,17 @@ PROTOTYPES = {
     'kbbq_kmer_select_dev': (_i, [_vp, _vp, _i, _c.c_uint32, _vp, _vp, _vp]),
     'kbbq_kmer_merge_dev': (_i, [_vp, _vp, _vp, _vp, _i64]),
     'kbbq_kmer_owner': (_c.c_uint32, [_u64, _i]),
+    'kbbq_kmer_filter_bytes': (_sz, [_i64]),
+    'kbbq_kmer_filter_create_dev': (_i, [_vp, _i64, _c.POINTER(_vp)]),
+    'kbbq_kmer_filter_free_dev': (_i, [_vp, _vp]),
+    'kbbq_kmer_filter_clear_dev': (_i, [_vp, _vp]),
+    'kbbq_kmer_filter_info': (_i, [_vp, _c.POINTER(_i64), _c.POINTER(_vp), _c.POINTER(_vp)]),
+    'kbbq_kmer_filter_admitted': (_i, [_vp, _vp, _c.POINTER(_i64)]),
+    'kbbq_kmer_filter_release_seen_dev': (_i, [_vp, _vp]),
+    'kbbq_kmer_prefilter_dev': (_i, [_vp, _vp, _i, _vp, _vp, _i64, _i]),
+    'kbbq_kmer_count_filtered_dev': (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i]),
+    'kbbq_kmer_prefilter': (_i, [_vp, _vp, _i, _vp, _vp, _i64, _i]),
+    'kbbq_kmer_count_filtered': (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i]),
 }
 
 

@@ -15,6 +15,13 @@ Several ranks (one process per GPU under torch.distributed.run): every rank coun
 key to the rank that owns it (owner(), a hash of the key that shares no bits with its home slot) and merges what it receives
 into its owner table; the histogram is summed over ranks, every rank gathers the solid k-mers of all owner tables into a solid
 table and corrects its own reads against it.  The rank files concatenated are the single-process output, byte for byte.
+
+Prefilter (`prefilter=True`, one process): most distinct k-mers of real reads are errors seen once, and nothing after the count
+looks at them.  A first pass over the reads marks every k-mer in a two-array bit filter (KmerFilter: `seen`, and `twice` for a
+key whose bits were all in `seen` before); the count then skips every window that is not in `twice`.  The filter has no false
+negatives, so every k-mer seen twice or more is counted exactly and the output is byte-identical; the table, sized from the
+filter's `admitted` counter, is several times smaller.  h[1] of a filtered table counts only the once-seen keys the filter let
+through, so min_count must be >= 2.
 """
 import ctypes
 import os
@@ -30,6 +37,8 @@ SLOT_BYTES = 12
 LOAD_FACTOR = 0.5
 MAX_BUCKETS = 1024                    # owners of one select (csrc/kbbq_kmer.h KM_MAX_BUCKETS)
 OWNER_SALT = 0x9E3779B97F4A7C15
+FILTER_SALT = 0xD6E8FEB86659FD93      # the prefilter's own salt (csrc/kbbq_kmer.h KM_FILTER_SALT)
+FILTER_WORD_BYTES = 16                # a word of `seen` and one of `twice`
 
 
 def _mix(x):
@@ -48,6 +57,33 @@ def owner(keys, world):
     with np.errstate(over='ignore'):
         h = _mix(k ^ np.uint64(OWNER_SALT))
     return (((h >> np.uint64(32)) * np.uint64(int(world))) >> np.uint64(32)).astype(np.uint32)
+
+
+def filter_index(keys, words):
+    """(word index, mask) of each canonical key in a filter of `words` (a power of two) 64-bit words (km_filter_index):
+    h = mix(key ^ FILTER_SALT), word = (h >> 24) & (words - 1), mask = the OR of 1 << ((h >> 6 j) & 63) for j = 0..3.
+    uint64 arrays of the keys' shape."""
+    words = int(words)
+    if words < 1 or words & (words - 1):
+        raise ValueError('words must be a power of two >= 1, got %d' % words)
+    k = np.asarray(keys, dtype=np.uint64)
+    with np.errstate(over='ignore'):
+        h = _mix(k ^ np.uint64(FILTER_SALT))
+    mask = np.zeros(k.shape, dtype=np.uint64)
+    for j in range(4):
+        mask |= np.uint64(1) << ((h >> np.uint64(6 * j)) & np.uint64(63))
+    return (h >> np.uint64(24)) & np.uint64(words - 1), mask
+
+
+def filter_words(total, bits=4):
+    """Words of each filter array for `total` k-mer windows: the smallest power of two with words * 64 >= bits * total."""
+    total, bits = int(total), int(bits)
+    if not 1 <= bits <= 64:
+        raise ValueError('filter_bits must be in 1..64, got %d' % bits)
+    words = 1
+    while words * 64 < bits * total:
+        words *= 2
+    return words
 
 
 def _on_device(x):
@@ -137,31 +173,139 @@ class KmerTable:
         return keys[order], counts[order]
 
 
+class KmerFilter:
+    """A device k-mer filter (kbbq_kmer_filter): `words` (a power of two) 64-bit words of `seen` and of `twice`, and the
+    `admitted` counter."""
+
+    def __init__(self, words, ctx=None):
+        from . import _device as dev
+        words = int(words)
+        if words < 1 or words & (words - 1):
+            raise ValueError('words must be a power of two >= 1, got %d' % words)
+        budget = dev.device_budget()
+        need = int(N.load().kbbq_kmer_filter_bytes(words))
+        if need > budget:
+            raise ValueError('a k-mer filter of words=%d (%d bytes) does not fit the device budget of %d bytes '
+                             '(KBBQ_DEVICE_BUDGET): give fewer filter bits' % (words, need, budget))
+        self.ctx = ctx or _ctx()
+        self.words = words
+        self._seen = True
+        self._h = ctypes.c_void_p()
+        N.check(N.load().kbbq_kmer_filter_create_dev(self.ctx.handle, words, ctypes.byref(self._h)))
+
+    @property
+    def handle(self):
+        return self._h
+
+    @property
+    def nbytes(self):
+        """Device bytes held now: both arrays, or `twice` alone after release_seen."""
+        full = int(N.load().kbbq_kmer_filter_bytes(self.words))
+        return full if self._seen else full // 2
+
+    @property
+    def admitted(self):
+        """OR-operations into `twice` that set a new bit so far: the keys the filtered count will insert, less the few whose
+        mask other keys had completed (synchronises)."""
+        v = ctypes.c_int64(0)
+        N.check(N.load().kbbq_kmer_filter_admitted(self.ctx.handle, self._h, ctypes.byref(v)))
+        return int(v.value)
+
+    def close(self):
+        h = self.__dict__.pop('_h', None)
+        if h:
+            N.load().kbbq_kmer_filter_free_dev(self.ctx.handle, h)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def clear(self):
+        """Zero both arrays and the counter (asynchronous on the context's stream)."""
+        N.check(N.load().kbbq_kmer_filter_clear_dev(self.ctx.handle, self._h))
+
+    def release_seen(self):
+        """Free `seen` once the last prefilter pass has been given: the filtered count reads `twice` alone."""
+        N.check(N.load().kbbq_kmer_filter_release_seen_dev(self.ctx.handle, self._h))
+        self._seen = False
+
+    def download(self):
+        """(seen, twice) as uint64 arrays of `words` words; seen is None after release_seen."""
+        lib = N.load()
+        ds, dt = ctypes.c_void_p(), ctypes.c_void_p()
+        N.check(lib.kbbq_kmer_filter_info(self._h, None, ctypes.byref(ds), ctypes.byref(dt)))
+        out = []
+        for d in (ds, dt):
+            if not d.value:
+                out.append(None)
+                continue
+            a = np.empty(self.words, dtype=np.uint64)
+            N.check(lib.kbbq_dev_download(self.ctx.handle, N.ptr(a), d, a.nbytes))
+            out.append(a)
+        return tuple(out)
+
+
+def _host_meta(meta):
+    return meta.cpu().numpy() if _on_device(meta) else meta
+
+
+def prefilter_kmers(seq_plane, meta, k=31, filter=None, bits=4):
+    """Pass every k-mer of the rows through `filter` (a new one of filter_words(kmer_total, bits) words when None) and return
+    it.  Several calls compose; the filtered count comes after the last."""
+    n, pitch = int(seq_plane.shape[0]), int(seq_plane.shape[1])
+    k = int(k)
+    if not 8 <= k <= 32:
+        raise ValueError('k must be in 8..32, got %d' % k)
+    if filter is None:
+        filter = KmerFilter(filter_words(kmer_total(_host_meta(meta), k), bits))
+    lib = N.load()
+    ctx = filter.ctx
+    if _on_device(seq_plane):
+        N.check(lib.kbbq_kmer_prefilter_dev(ctx.handle, filter.handle, k, N.ptr(seq_plane), N.ptr(meta), n, pitch))
+        ctx.status()
+    else:
+        seq_plane = np.ascontiguousarray(seq_plane, dtype=np.uint8)
+        meta = np.ascontiguousarray(meta, dtype=np.uint32)
+        N.check(lib.kbbq_kmer_prefilter(ctx.handle, filter.handle, k, N.ptr(seq_plane), N.ptr(meta), n, pitch))
+    return filter
+
+
 def _full(table, exc):
     return N.KmerTableFull('%s -- the table of slots=%d is too small for these reads: give more slots'
                            % (exc, table.slots))
 
 
-def count_kmers(seq_plane, meta, k=31, slots=None, table=None):
+def count_kmers(seq_plane, meta, k=31, slots=None, table=None, filter=None):
     """Count every k-mer of the rows into `table` (a new one of `slots` slots when None; default: kmer_total at a load factor
     of at most 0.5, capped by the device budget) and return it.  Counting adds: several calls compose.  A table that fills
-    raises KmerTableFull."""
+    raises KmerTableFull.  With `filter` (a KmerFilter that has seen all the rows, prefilter_kmers) only the k-mers in its
+    `twice` array are counted, and the default table is sized from filter.admitted instead of kmer_total."""
     from . import _device as dev
     n, pitch = int(seq_plane.shape[0]), int(seq_plane.shape[1])
     if table is None:
         if slots is None:
-            slots = default_slots(kmer_total(meta.cpu().numpy() if _on_device(meta) else meta, k), dev.device_budget())
+            total = filter.admitted if filter is not None else kmer_total(_host_meta(meta), k)
+            slots = default_slots(total, dev.device_budget())
         table = KmerTable(k, slots)
     lib = N.load()
     ctx = table.ctx
     try:
         if _on_device(seq_plane):
-            N.check(lib.kbbq_kmer_count_dev(ctx.handle, table.handle, N.ptr(seq_plane), N.ptr(meta), n, pitch))
+            if filter is not None:
+                N.check(lib.kbbq_kmer_count_filtered_dev(ctx.handle, table.handle, filter.handle, N.ptr(seq_plane), N.ptr(meta),
+                                                         n, pitch))
+            else:
+                N.check(lib.kbbq_kmer_count_dev(ctx.handle, table.handle, N.ptr(seq_plane), N.ptr(meta), n, pitch))
             ctx.status()
         else:
             seq_plane = np.ascontiguousarray(seq_plane, dtype=np.uint8)
             meta = np.ascontiguousarray(meta, dtype=np.uint32)
-            N.check(lib.kbbq_kmer_count(ctx.handle, table.handle, N.ptr(seq_plane), N.ptr(meta), n, pitch))
+            if filter is not None:
+                N.check(lib.kbbq_kmer_count_filtered(ctx.handle, table.handle, filter.handle, N.ptr(seq_plane), N.ptr(meta), n, pitch))
+            else:
+                N.check(lib.kbbq_kmer_count(ctx.handle, table.handle, N.ptr(seq_plane), N.ptr(meta), n, pitch))
     except N.KmerTableFull as exc:
         raise _full(table, exc) from None
     return table
@@ -249,25 +393,57 @@ def correct_with(table, seq_plane, meta, min_count):
     return out, changed[:n]
 
 
-def correct_reads(seq_plane, meta, k=31, min_count=None, slots=None):
+def _check_prefilter(min_count, filter_bits):
+    """The prefilter's rules, checked before any work on the GPU and, under ranks, before any collective."""
+    if min_count is not None and int(min_count) < 2:
+        raise ValueError('min_count must be >= 2 with the prefilter, got %d: k-mers seen once are not counted' % int(min_count))
+    if not 1 <= int(filter_bits) <= 64:
+        raise ValueError('filter_bits must be in 1..64, got %d' % int(filter_bits))
+    if _ranks() is not None:
+        raise ValueError('the prefilter does not run across ranks yet: a k-mer seen once on each of two ranks is not seen '
+                         'once, so the filter belongs at the rank that owns the key; run on one GPU, or without the prefilter')
+
+
+def correct_reads(seq_plane, meta, k=31, min_count=None, slots=None, prefilter=False, filter_bits=4):
     """Count, pick the threshold (min_count, else the histogram's first valley) and correct.  Returns (corrected plane in
-    the input's layout and kind, info) with info = {'k', 'min_count', 'hist', 'changed' (per read), 'slots', 'table_bytes'}."""
-    table = count_kmers(seq_plane, meta, k=k, slots=slots)
+    the input's layout and kind, info) with info = {'k', 'min_count', 'hist', 'changed' (per read), 'slots', 'table_bytes',
+    'prefilter', 'filter_bytes', 'admitted'}.  With `prefilter` a KmerFilter of `filter_bits` bits per k-mer window and array
+    keeps most k-mers seen once out of the table: the same plane, threshold and hist[2:]; hist[1] is the number of once-seen
+    k-mers that got in; the table, unless `slots` is given, is sized from the filter's `admitted` after `seen` is freed;
+    min_count must be >= 2.  filter_bytes is the filter's size during its pass (both arrays); admitted is None without."""
+    filt = None
+    filter_bytes, admitted = 0, None
+    if prefilter:
+        _check_prefilter(min_count, filter_bits)
+        filt = prefilter_kmers(seq_plane, meta, k=k, bits=filter_bits)
+    table = None
     try:
+        if filt is not None:
+            filter_bytes, admitted = filt.nbytes, filt.admitted
+            filt.release_seen()
+        table = count_kmers(seq_plane, meta, k=k, slots=slots, filter=filt)
+        if filt is not None:
+            filt.close()
         hist = kmer_histogram(table)
         t = int(min_count) if min_count is not None else solid_threshold(hist)
         if t < 1:
             raise ValueError('min_count must be >= 1, got %d' % t)
         out, changed = correct_with(table, seq_plane, meta, t)
-        return out, dict(k=table.k, min_count=t, hist=hist, changed=changed, slots=table.slots, table_bytes=table.nbytes)
+        return out, dict(k=table.k, min_count=t, hist=hist, changed=changed, slots=table.slots, table_bytes=table.nbytes,
+                         prefilter=bool(prefilter), filter_bytes=filter_bytes, admitted=admitted)
     finally:
-        table.close()
+        if filt is not None:
+            filt.close()
+        if table is not None:
+            table.close()
 
 
-def correct_fastq(path, out, k=31, min_count=None, slots=None, local_slots=None):
+def correct_fastq(path, out, k=31, min_count=None, slots=None, local_slots=None, prefilter=False, filter_bits=4):
     """Correct every read of a FASTQ file (plain or .gz) and write '@' + name, the corrected sequence, '+' and the qualities
     as read to `out` (a path, or a text stream).  Returns correct_reads' info.  In a process group of several ranks (or of
-    one with KBBQ_DIST_ALWAYS=1) this is correct_fastq_ranks."""
+    one with KBBQ_DIST_ALWAYS=1) this is correct_fastq_ranks, which has no prefilter."""
+    if prefilter:
+        _check_prefilter(min_count, filter_bits)
     if _ranks() is not None:
         return correct_fastq_ranks(path, out, k=k, min_count=min_count, slots=slots, local_slots=local_slots)
     from . import fastx
@@ -279,7 +455,7 @@ def correct_fastq(path, out, k=31, min_count=None, slots=None, local_slots=None)
         names = fq.names()
     finally:
         fq.close()
-    fixed, info = correct_reads(seq, meta, k=k, min_count=min_count, slots=slots)
+    fixed, info = correct_reads(seq, meta, k=k, min_count=min_count, slots=slots, prefilter=prefilter, filter_bits=filter_bits)
     text = fastx.format_fastq(names, fixed, qual, meta & 0xFFFF)
     if isinstance(out, str):
         with open(out, 'w', encoding='latin-1', newline='') as fh:
@@ -291,12 +467,15 @@ def correct_fastq(path, out, k=31, min_count=None, slots=None, local_slots=None)
     return info
 
 
-def main_correct(path, output=None, k=31, min_count=None, slots=None, local_slots=None):
+def main_correct(path, output=None, k=31, min_count=None, slots=None, local_slots=None, prefilter=False, filter_bits=4):
     """`kbbq correct`: the corrected FASTQ to `output` or stdout; the threshold and the changed bases to stderr (once, by rank
-    0, with the figures of all ranks)."""
+    0, with the figures of all ranks); with the prefilter also the admitted k-mers and the table's slots."""
+    if prefilter:
+        _check_prefilter(min_count, filter_bits)         # every rank refuses, before its first collective
     ranks = _ranks()
     if ranks is None:
-        info = correct_fastq(path, output if output else sys.stdout, k=k, min_count=min_count, slots=slots)
+        info = correct_fastq(path, output if output else sys.stdout, k=k, min_count=min_count, slots=slots,
+                             prefilter=prefilter, filter_bits=filter_bits)
         changed = int(np.asarray(info['changed'], dtype=np.int64).sum())
     else:
         try:
@@ -314,8 +493,9 @@ def main_correct(path, output=None, k=31, min_count=None, slots=None, local_slot
         changed = info['changed_bases']
         if ranks[1] != 0:
             return info
-    sys.stderr.write('kbbq correct: k=%d min_count=%d reads=%d changed_bases=%d\n'
-                     % (info['k'], info['min_count'], info['reads'], changed))
+    sys.stderr.write('kbbq correct: k=%d min_count=%d reads=%d changed_bases=%d%s\n'
+                     % (info['k'], info['min_count'], info['reads'], changed,
+                        ' prefilter=1 admitted=%d slots=%d' % (info['admitted'], info['slots']) if prefilter else ''))
     return info
 
 

@@ -68,7 +68,7 @@ def correct(args):
         from . import _device
         _device.use_native_memory()          # as `recalibrate` on one GPU: no torch import
     kmer.main_correct(args.fastq, output=args.output, k=args.kmer, min_count=args.min_count, slots=args.slots,
-                      local_slots=args.local_slots)
+                      local_slots=args.local_slots, prefilter=args.prefilter, filter_bits=args.filter_bits)
 
 
 def main(argv=None):
@@ -140,6 +140,12 @@ def main(argv=None):
                     help='under torch.distributed.run: slots of the table every rank counts its own reads into before they go '
                          'to the ranks that own them, a power of two (default: the rank\'s k-mers at a load factor of 0.5, '
                          'capped by half the device budget); a smaller table counts the reads in several rounds')
+    cp.add_argument('--prefilter', action='store_true',
+                    help='keep most k-mers seen once out of the table with a bit filter passed over the reads first: the same '
+                         'output from a table several times smaller, sized from the filter unless --slots is given; needs '
+                         '--min-count >= 2 where given; one GPU only (not under torch.distributed.run)')
+    cp.add_argument('--filter-bits', type=int, default=4,
+                    help='with --prefilter: bits per k-mer of the input in each of the filter\'s two arrays, 1..64 (default 4)')
     cp.add_argument('-o', '--output', default=None,
                     help='Write the corrected FASTQ to this file instead of stdout; under torch.distributed.run every rank '
                          'writes FILE.rankNNNN, to be concatenated in rank order.')

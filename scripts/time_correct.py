@@ -3,7 +3,11 @@
 sampled from both strands of a random genome sized for `--depth` x coverage, `--err` uniform substitutions.  Count
 (kbbq_kmer_count_dev into a fresh table), histogram (kbbq_kmer_histogram_dev) and correct (kbbq_kmer_correct_dev) are each
 timed once per repetition after a warm-up on the same table.  Prints one JSON line: ms per step, k-mer windows per second of
-the count and of the correct step, the table's slots and bytes, its distinct k-mers, the threshold and the changed bases."""
+the count and of the correct step, the table's slots and bytes, its distinct k-mers, the threshold and the changed bases.
+With `--prefilter` a second leg on the same reads follows under the key "prefilter": km_prefilter into a fresh filter, `seen`
+released, a table sized from the filter's `admitted` (or `--prefilter-slots`), the filtered count, histogram and correct, each
+timed the same way, with the filter's bytes and the device bytes in use at their peak (kbbq_dev_mem_info, planes excluded)
+beside the plain leg's; the leg fails unless its threshold, hist[2:] and corrected plane equal the plain leg's."""
 import argparse
 import ctypes
 import json
@@ -20,6 +24,9 @@ ap.add_argument('--err', type=float, default=0.01)
 ap.add_argument('-k', type=int, default=31)
 ap.add_argument('--slots', type=int, default=0, help='table slots (default: distinct k-mers expected at a load factor <= 0.5)')
 ap.add_argument('--reps', type=int, default=3)
+ap.add_argument('--prefilter', action='store_true', help='add the prefiltered leg')
+ap.add_argument('--filter-bits', type=int, default=4)
+ap.add_argument('--prefilter-slots', type=int, default=0, help='table slots of the prefiltered leg (default: from `admitted`)')
 args = ap.parse_args()
 
 import numpy as np
@@ -51,7 +58,21 @@ windows = n * max(L - k + 1, 0)
 distinct = G + windows * args.err * k                  # the genome's k-mers and those an error makes
 slots = args.slots or 1 << int(np.ceil(np.log2(distinct * 2)))
 out = torch.empty_like(seq)
+out2 = torch.empty_like(seq) if args.prefilter else None   # the prefiltered leg's plane, compared with the plain one
 lib = N.load()
+
+
+def in_use(ctx):
+    free, total = ctypes.c_size_t(0), ctypes.c_size_t(0)
+    N.check(lib.kbbq_dev_mem_info(ctx.handle, ctypes.byref(free), ctypes.byref(total)))
+    return total.value - free.value
+
+
+def rep_base():
+    """Device bytes in use before a repetition allocates anything: the planes, the runtime's own, torch's cached blocks."""
+    torch.cuda.synchronize()
+    torch.cuda.empty_cache()
+    return in_use(kmer._ctx())
 
 
 def timed(fn):
@@ -68,8 +89,10 @@ res = {'reads': n, 'len': L, 'k': k, 'genome': G, 'err': args.err, 'slots': slot
 ms = {'count': [], 'histogram': [], 'correct': []}
 dh = torch.zeros(257, dtype=torch.int64, device='cuda')
 for rep in range(args.reps + 1):
+    base = rep_base()
     table = kmer.KmerTable(k, slots)
     torch.cuda.synchronize()
+    res['peak_bytes'] = in_use(table.ctx) - base
     c = timed(lambda: N.check(lib.kbbq_kmer_count_dev(table.ctx.handle, table.handle, N.ptr(seq), N.ptr(meta), n, pitch)))
     table.ctx.status()
     h = timed(lambda: N.check(lib.kbbq_kmer_histogram_dev(table.ctx.handle, table.handle, N.ptr(dh))))
@@ -87,4 +110,46 @@ res['distinct'] = int(hist.sum())
 res['load_factor'] = round(res['distinct'] / slots, 3)
 res['min_count'] = t
 res['changed_bases'] = int((out != seq).sum().item())
+if args.prefilter:
+    from kbbq import _device as dev
+    plain_out, plain_hist, plain_t = out, hist, t
+    out = out2
+    words = kmer.filter_words(windows, args.filter_bits)
+    ms = {'prefilter': [], 'count_filtered': [], 'histogram': [], 'correct': []}
+    leg = {'filter_bits': args.filter_bits, 'filter_words': words, 'filter_bytes': int(lib.kbbq_kmer_filter_bytes(words))}
+    for rep in range(args.reps + 1):
+        base = rep_base()
+        filt = kmer.KmerFilter(words)
+        torch.cuda.synchronize()
+        peak = in_use(filt.ctx) - base
+        ctx = filt.ctx
+        f = timed(lambda: N.check(lib.kbbq_kmer_prefilter_dev(ctx.handle, filt.handle, k, N.ptr(seq), N.ptr(meta), n, pitch)))
+        admitted = filt.admitted
+        filt.release_seen()
+        pslots = args.prefilter_slots or kmer.default_slots(admitted, dev.device_budget())
+        table = kmer.KmerTable(k, pslots)
+        torch.cuda.synchronize()
+        peak = max(peak, in_use(ctx) - base)
+        c = timed(lambda: N.check(lib.kbbq_kmer_count_filtered_dev(ctx.handle, table.handle, filt.handle, N.ptr(seq), N.ptr(meta),
+                                                                   n, pitch)))
+        ctx.status()
+        filt.close()
+        h = timed(lambda: N.check(lib.kbbq_kmer_histogram_dev(ctx.handle, table.handle, N.ptr(dh))))
+        hist = dh.cpu().numpy()
+        t = kmer.solid_threshold(hist)
+        x = timed(lambda: N.check(lib.kbbq_kmer_correct_dev(ctx.handle, table.handle, N.ptr(seq), N.ptr(meta), n, pitch, t,
+                                                             N.ptr(out), None)))
+        table.close()
+        if rep:
+            for key, v in zip(ms, (f, c, h, x)):
+                ms[key].append(v)
+    leg.update({'ms_' + key: round(float(np.median(v)), 3) for key, v in ms.items()})
+    leg.update(slots=pslots, table_bytes=int(lib.kbbq_kmer_table_bytes(pslots)), admitted=admitted, peak_bytes=peak,
+               entries=int(hist.sum()), admitted_singletons=int(hist[1]), load_factor=round(int(hist.sum()) / pslots, 3),
+               min_count=t, prefilter_kmers_per_s=windows / (leg['ms_prefilter'] * 1e-3),
+               count_filtered_kmers_per_s=windows / (leg['ms_count_filtered'] * 1e-3))
+    assert t == plain_t and np.array_equal(hist[2:], plain_hist[2:]), 'the prefiltered leg found another histogram'
+    assert torch.equal(out, plain_out), 'the prefiltered leg corrected differently'
+    leg['singletons'] = int(plain_hist[1])
+    res['prefilter'] = leg
 print(json.dumps(res))
