@@ -1,8 +1,7 @@
-// kbbq_aligned_kernels.h -- K4, second form: compare_reads.find_read_errors (compare_reads.py:84-139) without the
-// wave-lock-step CIGAR walk.
+// kbbq_aligned_kernels.h -- K4: compare_reads.find_read_errors (compare_reads.py:84-139) without a wave-lock-step CIGAR walk.
 //
-// What bounded the first form (kbbq_kernels_v3.h k4_find_errors; profiles/r01_pmc_aligned.md): the
-// reference / mask window of a chunk was fetched at the offset that is right when NO insertion or deletion precedes
+// What bounded the first form of this kernel (every lane walked its read's CIGAR in order; DESIGN_HISTORY.md,
+// profiles/r01_pmc_aligned.md): the reference / mask window of a chunk was fetched at the offset that is right when NO insertion or deletion precedes
 // the chunk; every chunk behind an indel found out inside the walk that it needed another window and fetched it there,
 // a dependent load that parks the whole wave -- 0.61 ms when every read is one M block, 0.78 ms with 5 % indel reads.
 //
@@ -15,7 +14,7 @@
 //     the CIGAR: the chunk is "simple"; its reference window starts at ref_start + refidx + (in_lo - readidx) and
 //     is fetched right away -- the correct window, whatever precedes the chunk;
 //   * anything else (an operation boundary inside the chunk, more than four operations, a shape error): the chunk
-//     takes the sequential walk of the first form, unchanged (k4_walk_chunk), which carries the reference's exact
+//     takes the sequential walk, operation by operation (k4_walk_chunk), which carries the reference's exact
 //     semantics: an insertion's both-neighbours test, a deletion OR-ing into the base before it, Python's [-1]
 //     wraps, ValueError / IndexError on malformed input.  That walk is ~500 vector instructions and a lane that takes
 //     it holds its whole wave: with one such chunk per indel read (0.5 % of the chunks at 5 % indel reads) 28 % of the
@@ -152,7 +151,9 @@ __global__ __launch_bounds__(256) void k4_read_records(K4RecParams p)
     if (listing) flush();
 }
 
-// the sequential walk of the first form for ONE chunk (compare_reads.py:100-137), operation by operation in CIGAR order
+// the sequential walk for ONE chunk (compare_reads.py:100-137): the lane applies every operation's effect to its own 16
+// positions in CIGAR order, which is exactly the reference's sequential semantics (an M assigns, a later D/N ORs into the base
+// before it, Python's index -1 wraps: skips[-1], subset[-1])
 template <bool FUSED>
 __device__ __forceinline__ void k4_walk_chunk(const K4Params& p, long long r, int n, int rl, long long g0, const u32* ops, u32 nc,
                                            const u32 (&sw)[4], int in_lo, int cnt, u32 (&ev)[4], u32 (&kv)[4])

@@ -1,5 +1,8 @@
 // kbbq_hip.hip -- C ABI of libkbbq_hip.so (see include/kbbq_hip.h).
 // gfx950 only.  Host side: launch geometry, device staging, status decoding.
+// K1 / K2 launch through one layer: the kernel tables (K1_VARIANTS, LDS_KERNELS) and launch_lds; K1's LDS geometry is k1_geometry +
+// k1_lds_plan + launch_k1, K2's choice between persistent and short-lived workgroups k2_tile_serves; k2v3_params / k2t_params /
+// fill_row_lut / k4_params fill the parameter structs, grow_scratch grows the context's device scratch.
 #include "kbbq_kernels.h"
 #include "kbbq_kernels_v3.h"
 #include "kbbq_solve_kernels.h"
@@ -46,6 +49,8 @@ int kbbq_set_error_(int code, const char* msg) { g_err = msg ? msg : ""; return 
                         __FILE__, __LINE__);                                           \
     } while (0)
 
+struct DevScratch { void* p = nullptr; size_t bytes = 0; };
+
 struct kbbq_ctx {
     int device = 0;
     int cus = 0;
@@ -55,20 +60,17 @@ struct kbbq_ctx {
     hipStream_t stream = nullptr;
     u64* d_status = nullptr;          // [KBBQ_NSTATUS]
     int* d_stats = nullptr;           // [K7_NSTATS] scratch of kbbq_meta_stats_dev
-    int* d_wgplan = nullptr;          // K2 (short-lived workgroups): first workgroup of every read group
-    int wgplan_n = 0;
-    void* d_ops4 = nullptr;           // K4: one 32-byte record of the first CIGAR operations per read (grown on demand)
-    size_t ops4_bytes = 0;
-    void* d_tally = nullptr;          // kbbq_tally_aligned_dev: [count | flags words of the reads | rows K4 still has to look at] (grown on demand)
-    size_t tally_bytes = 0;
+    // device scratch of the context's own, grown on demand (grow_scratch)
+    DevScratch wgplan;                // K2 (short-lived workgroups): first workgroup of every read group
+    DevScratch ops4;                  // K4: one 32-byte record of the first CIGAR operations per read
+    DevScratch tally;                 // kbbq_tally_aligned_dev: [count | flags words of the reads | rows K4 still has to look at]
+    DevScratch rowlut;                // K2 on one-read-per-row planes: the LUT narrowed to the rows' pitch
     // host-buffer entry points (stage_run): two page-locked staging slabs and their device twins, a copy stream and
     // the events that order host copy -> upload -> kernel -> download slab by slab (grown on demand, kept for the next call)
     void* stage_host[2] = {nullptr, nullptr}; void* stage_dev[2] = {nullptr, nullptr}; size_t stage_bytes = 0;
     hipStream_t stage_stream = nullptr;      // uploads
     hipStream_t stage_down_stream = nullptr; // downloads (kbbq_apply): a stream of their own, so that slab k + 1 goes up while slab k comes back
     hipEvent_t stage_up[2] = {nullptr, nullptr}, stage_used[2] = {nullptr, nullptr}, stage_down[2] = {nullptr, nullptr};
-    void* d_rowlut = nullptr;         // K2 on one-read-per-row planes: the LUT narrowed to the rows' pitch (grown on demand)
-    size_t rowlut_bytes = 0;
     bool timing = false;
     // per-kernel event pairs recorded while timing is on
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev[2];
@@ -86,6 +88,47 @@ constexpr int K2T_XCD = 8;                   // k2t_order: the read groups' work
 constexpr int K7_FRONTS = 8;                 // sequential fronts of k7_lay_out (LayOutParams::parts)
 constexpr int TALLY_K4_SHARE = 8;            // kbbq_tally_aligned_dev: K4's grid is sized for 1 / 8 of the reads
 static const u64 ST_INIT[KBBQ_NSTATUS] = {~0ull, ~0ull, ~0ull, ~0ull, ~0ull, ~0ull, ~0ull, ~0ull};
+
+// ---- kernels launched with dynamic LDS ---------------------------------------------------------------------------------
+// Each of them is named HERE and nowhere else: launch_lds takes a kernel's address from these tables, and kbbq_ctx_create walks the
+// same tables to allow every one of them the full LDS as dynamic shared memory.  An instance that is not listed is not
+// instantiated and cannot be selected.
+// K1 (table-driven): form x copies of the context table (DN) x 4-bit planes (NIB) x chunk-position-major cycle table of KJ chunks,
+// each without and with SPLIT (a dinucleotide threshold above the counting one)
+enum K1Form { K1_ROWS, K1_ALIGNED, K1_ALIGNED_REF, K1_BANDS };
+struct K1Variant { K1Form form; int dn, nib, kj; const void* kernel[2]; };       // kernel[split]
+#define K1_SPLITS(K, ...) {(const void*)(K<false, __VA_ARGS__>), (const void*)(K<true, __VA_ARGS__>)}
+static const K1Variant K1_VARIANTS[] = {
+    {K1_ROWS, K1V3_DNREP, 0, 0, K1_SPLITS(k1v3_accumulate, K1V3_DNREP)},
+    {K1_ROWS, 8, 0, 0, K1_SPLITS(k1v3_accumulate, 8)},
+    {K1_ROWS, K1V3_DNREP, 1, 0, K1_SPLITS(k1v3_accumulate, K1V3_DNREP, true)},
+    {K1_ROWS, 8, 1, 0, K1_SPLITS(k1v3_accumulate, 8, true)},
+    {K1_ROWS, K1V3_DNREP, 1, 13, K1_SPLITS(k1v3_accumulate, K1V3_DNREP, true, 13)},
+    {K1_ROWS, K1V3_DNREP, 1, 19, K1_SPLITS(k1v3_accumulate, K1V3_DNREP, true, 19)},
+    {K1_ALIGNED, K1V3_DNREP, 0, 0, K1_SPLITS(k1v3_aligned, K1V3_DNREP)},
+    {K1_ALIGNED, 8, 0, 0, K1_SPLITS(k1v3_aligned, 8)},
+    {K1_ALIGNED_REF, K1V3_DNREP, 0, 0, K1_SPLITS(k1v3_aligned_ref, K1V3_DNREP)},
+    {K1_ALIGNED_REF, 8, 0, 0, K1_SPLITS(k1v3_aligned_ref, 8)},
+    {K1_BANDS, 0, 0, 0, K1_SPLITS(k1v3_bands, false)},                          // every band brings its own DN (K1BandsParams::dn)
+    {K1_BANDS, 0, 1, 0, K1_SPLITS(k1v3_bands, true)},
+};
+#undef K1_SPLITS
+
+static const void* k1_kernel(K1Form form, bool split, int dn, int nib, int kj)
+{
+    for (const K1Variant& v : K1_VARIANTS)
+        if (v.form == form && v.dn == dn && v.nib == nib && v.kj == kj) return v.kernel[split];
+    return nullptr;                                                             // launch_lds reports it
+}
+
+// the others: the round-1 kernels (tables beyond the LDS, KBBQ_APPLY_CHECKED) and K2
+enum LdsKernel { LK_K1_PLAIN, LK_K1_PLAIN_SPLIT, LK_K2V3, LK_K2V3_NIB, LK_K2T, LK_K2T_NIB, LK_K2T_BANDS, LK_K2_LDS16, LK_K2_LDS8, LK_COUNT };
+static const void* const LDS_KERNELS[LK_COUNT] = {
+    (const void*)k1_accumulate<false>, (const void*)k1_accumulate<true>,
+    (const void*)k2v3_apply<false>, (const void*)k2v3_apply<true>,
+    (const void*)k2t_apply<false>, (const void*)k2t_apply<true>, (const void*)k2t_bands,
+    (const void*)k2_apply<int16_t, true, true>, (const void*)k2_apply<int8_t, true, false>,
+};
 
 extern "C" {
 
@@ -144,29 +187,14 @@ int kbbq_ctx_create(int device, kbbq_ctx** out)
     e = hipMemcpy(c->d_status, ST_INIT, sizeof ST_INIT, hipMemcpyHostToDevice);
     if (e != hipSuccess) { (void)hipFree(c->d_status); (void)hipStreamDestroy(c->own_stream); delete c; return fail(KBBQ_E_HIP, "hipMemcpy(status): %s", hipGetErrorString(e)); }
     lap("hipMalloc + hipMemcpy");
-    // allow the full 160 KiB of LDS as dynamic shared memory
-    static const void* const full_lds[] = {
-        (const void*)k1_accumulate<false>, (const void*)k1_accumulate<true>,
-        (const void*)k1v3_accumulate<false>, (const void*)k1v3_accumulate<true>,
-        (const void*)(k1v3_accumulate<false, 8>), (const void*)(k1v3_accumulate<true, 8>),
-        (const void*)(k1v3_accumulate<false, K1V3_DNREP, true>), (const void*)(k1v3_accumulate<true, K1V3_DNREP, true>),
-        (const void*)(k1v3_accumulate<false, 8, true>), (const void*)(k1v3_accumulate<true, 8, true>),
-        (const void*)(k1v3_accumulate<false, K1V3_DNREP, true, 13>), (const void*)(k1v3_accumulate<true, K1V3_DNREP, true, 13>),
-        (const void*)(k1v3_accumulate<false, K1V3_DNREP, true, 19>), (const void*)(k1v3_accumulate<true, K1V3_DNREP, true, 19>),
-        (const void*)(k2v3_apply<false>), (const void*)(k2v3_apply<true>),
-        (const void*)k2t_apply<true>, (const void*)k2t_apply<false>, (const void*)k2t_bands,
-        (const void*)(k1v3_aligned<false, K1V3_DNREP>), (const void*)(k1v3_aligned<true, K1V3_DNREP>),
-        (const void*)(k1v3_aligned<false, 8>), (const void*)(k1v3_aligned<true, 8>),
-        (const void*)(k1v3_aligned_ref<false, K1V3_DNREP>), (const void*)(k1v3_aligned_ref<true, K1V3_DNREP>),
-        (const void*)(k1v3_aligned_ref<false, 8>), (const void*)(k1v3_aligned_ref<true, 8>),
-        (const void*)(k1v3_bands<false, false>), (const void*)(k1v3_bands<true, false>),
-        (const void*)(k1v3_bands<false, true>), (const void*)(k1v3_bands<true, true>),
-        (const void*)k2_apply<int16_t, true, true>, (const void*)k2_apply<int8_t, true, false>,
+    // allow the full 160 KiB of LDS as dynamic shared memory to every kernel that is launched with dynamic LDS
+    // (the first call loads the code object: KBBQ_CTX_DBG shows it apart)
+    auto full_lds = [&](const void* kernel) {
+        (void)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, c->lds_bytes);
+        if (kernel == LDS_KERNELS[0]) lap("first hipFuncSetAttribute");
     };
-    for (size_t i = 0; i < sizeof full_lds / sizeof full_lds[0]; ++i) {
-        (void)hipFuncSetAttribute(full_lds[i], hipFuncAttributeMaxDynamicSharedMemorySize, c->lds_bytes);
-        if (i == 0) lap("first hipFuncSetAttribute");
-    }
+    for (const void* kernel : LDS_KERNELS) full_lds(kernel);
+    for (const K1Variant& v : K1_VARIANTS) { full_lds(v.kernel[0]); full_lds(v.kernel[1]); }
     (void)hipGetLastError();
     lap("the other attributes");
     *out = c;
@@ -181,9 +209,8 @@ int kbbq_ctx_destroy(kbbq_ctx* c)
         for (auto& pr : c->ev[w]) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
     if (c->d_status) (void)hipFree(c->d_status);
     if (c->d_stats) (void)hipFree(c->d_stats);
-    if (c->d_ops4) (void)hipFree(c->d_ops4);
-    if (c->d_rowlut) (void)hipFree(c->d_rowlut);
-    if (c->d_tally) (void)hipFree(c->d_tally);
+    for (DevScratch* s : {&c->wgplan, &c->ops4, &c->tally, &c->rowlut})
+        if (s->p) (void)hipFree(s->p);
     for (int b = 0; b < 2; ++b) {
         if (c->stage_host[b]) (void)hipHostFree(c->stage_host[b]);
         if (c->stage_dev[b]) (void)hipFree(c->stage_dev[b]);
@@ -193,7 +220,6 @@ int kbbq_ctx_destroy(kbbq_ctx* c)
     }
     if (c->stage_stream) (void)hipStreamDestroy(c->stage_stream);
     if (c->stage_down_stream) (void)hipStreamDestroy(c->stage_down_stream);
-    if (c->d_wgplan) (void)hipFree(c->d_wgplan);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     delete c;
     return KBBQ_OK;
@@ -259,16 +285,6 @@ int kbbq_ctx_status(kbbq_ctx* c, int64_t* read_index)
                      : code == KBBQ_E_INDEX ? "quality/read-group/cycle beyond the tables (reference: IndexError)"
                                             : "recalibrated quality + 33 outside 0..255";
     return fail(code, "read %lld: %s", (long long)best, what);
-}
-
-// diagnostic builds only (-DK4_DEBUG_COUNT): the raw status words
-int kbbq_debug_status_words_(kbbq_ctx* c, uint64_t* out8)
-{
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipMemcpyAsync(out8, c->d_status, sizeof ST_INIT, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    HIPCHK(hipMemcpyAsync(c->d_status, ST_INIT, sizeof ST_INIT, hipMemcpyHostToDevice, c->stream));
-    return KBBQ_OK;
 }
 
 int kbbq_dev_alloc(kbbq_ctx* c, size_t bytes, void** dptr)
@@ -450,6 +466,31 @@ struct Timed {
     }
 };
 
+// the one launch of a kernel with dynamic LDS: `kernel` comes from K1_VARIANTS (k1_kernel) or LDS_KERNELS, all of which take one
+// parameter struct; `which`: the timer the launch counts for (kbbq_ctx_kernel_ms: 0 = K1, 1 = K2)
+static int launch_lds(kbbq_ctx* c, int which, const void* kernel, dim3 grid, dim3 block, size_t lds, const void* params)
+{
+    if (!kernel) return fail(KBBQ_E_HIP, "libkbbq_hip has no instance of K1 for this launch (K1_VARIANTS)");
+    void* args[] = {const_cast<void*>(params)};
+    {
+        Timed t(c, which);
+        (void)hipLaunchKernel(kernel, grid, block, args, lds, c->stream);
+    }
+    HIPCHK(hipGetLastError());
+    return KBBQ_OK;
+}
+
+// context-owned device scratch of at least `need` bytes (contents are not kept).  The buffer it replaces may still be in use by
+// what the stream holds: it is freed behind a synchronisation.
+static int grow_scratch(kbbq_ctx* c, DevScratch& s, size_t need)
+{
+    if (s.bytes >= need) return KBBQ_OK;
+    if (s.p) { HIPCHK(hipStreamSynchronize(c->stream)); (void)hipFree(s.p); s.p = nullptr; s.bytes = 0; }
+    HIPCHK(hipMalloc(&s.p, need));
+    s.bytes = need;
+    return KBBQ_OK;
+}
+
 extern "C" {
 
 int kbbq_accumulate_dev(kbbq_ctx* c, const uint8_t* d_seq, const uint8_t* d_cseq,
@@ -462,7 +503,7 @@ int kbbq_accumulate_dev(kbbq_ctx* c, const uint8_t* d_seq, const uint8_t* d_cseq
 
 // what accumulate_rows would launch (kernel parameters, LDS bytes, template variant): kbbq_accumulate_bands_dev collects
 // these for all length bands and launches them as ONE kernel
-struct K1Setup { K1v3Params q; int dn = 0; bool km = false; bool split = false; size_t lds = 0; int64_t iters = 0; };
+struct K1Setup { K1v3Params q; int dn = 0; int kj = 0; size_t lds = 0; };        // dn / kj: K1_VARIANTS; lds: bytes of dynamic LDS
 static int accumulate_rows(kbbq_ctx* c, const char* who, const uint8_t* d_seq, const uint8_t* d_cseq, const uint8_t* d_qual,
                            const uint32_t* d_meta, int64_t nrows, int pitch, int pairs, int R, int S2, int minscore,
                            int dinuc_minscore, const int64_t* d_seg, int64_t* d_tables, bool* fits, int S_band = 0, int S_min = 0, int nib = 0,
@@ -511,14 +552,7 @@ int kbbq_accumulate_band_dev(kbbq_ctx* c, const uint8_t* d_seq, const uint8_t* d
     per_cu = std::max(per_cu, 1);
     const int64_t iters = (nblocks + (K1_THREADS / 64) - 1) / (K1_THREADS / 64);
     int gx = (int)std::min<int64_t>(iters, std::max(1, c->cus * per_cu / R));
-    dim3 grid((unsigned)gx, (unsigned)R, 1), block(K1_THREADS, 1, 1);
-    {
-        Timed t(c, 0);
-        if (split) hipLaunchKernelGGL(k1_accumulate<true>, grid, block, lds, c->stream, p);
-        else hipLaunchKernelGGL(k1_accumulate<false>, grid, block, lds, c->stream, p);
-    }
-    HIPCHK(hipGetLastError());
-    return KBBQ_OK;
+    return launch_lds(c, 0, LDS_KERNELS[split ? LK_K1_PLAIN_SPLIT : LK_K1_PLAIN], dim3((unsigned)gx, (unsigned)R, 1), dim3(K1_THREADS), lds, &p);
 }
 
 // host twin of k3_fill_full_lut (same rules; the GPU test compares the two blobs byte for byte)
@@ -602,24 +636,77 @@ int kbbq_build_lut(int R, int Qt, int S2, int D, int minscore, const int64_t* me
 // (KBBQ_K2_ROWLUT=0: the tables' full S2, A/B timing)
 static int row_lut_width(int pitch, int S2) { return env_is("KBBQ_K2_ROWLUT", "0") ? S2 : std::min(pitch, S2); }
 
-// ... when Sb < S2, that narrowed LUT (k3_fill_row_lut) in context-owned scratch, written on the launch stream in front of
-// the apply kernel (Sb == S2: the blob's own full LUT is used, *lut untouched).  False: no scratch for it.
-static bool narrowed_row_lut(kbbq_ctx* c, const void* d_lut_blob, int R, int Qt, int S2, int Sb, int minscore, const int8_t** lut)
+// the LUT of cycle width Sb (k3_fill_row_lut) written to `dst`, on the launch stream in front of the apply kernel that reads it
+static const int8_t* fill_row_lut(kbbq_ctx* c, const void* d_lut_blob, int R, int Qt, int S2, int Sb, int minscore, void* dst)
 {
-    if (Sb >= S2) return true;
-    const size_t need = (size_t)R * (33 + Qt) * full_lut_row_bytes(Sb);
-    if (c->rowlut_bytes < need) {
-        if (c->d_rowlut) { if (hipStreamSynchronize(c->stream) != hipSuccess) return false; (void)hipFree(c->d_rowlut); c->d_rowlut = nullptr; c->rowlut_bytes = 0; }
-        if (hipMalloc(&c->d_rowlut, need) != hipSuccess) { c->d_rowlut = nullptr; return false; }
-        c->rowlut_bytes = need;
-    }
     RowLutParams f;
     f.lut16 = reinterpret_cast<const int16_t*>(d_lut_blob); f.rs16 = lut_row_stride(S2); f.R = R; f.Qt = Qt; f.S2 = S2; f.Sb = Sb;
     f.minscore = std::min(std::max(minscore, 0), Qt);
-    f.out = reinterpret_cast<int8_t*>(c->d_rowlut);
+    f.out = reinterpret_cast<int8_t*>(dst);
     hipLaunchKernelGGL(k3_fill_row_lut, dim3((unsigned)(R * (33 + Qt))), dim3(256), 0, c->stream, f);
-    *lut = f.out;
+    return f.out;
+}
+
+// ... when Sb < S2, that narrowed LUT in context-owned scratch (Sb == S2: the blob's own full LUT is used, *lut untouched).
+// False: no scratch for it.
+static bool narrowed_row_lut(kbbq_ctx* c, const void* d_lut_blob, int R, int Qt, int S2, int Sb, int minscore, const int8_t** lut)
+{
+    if (Sb >= S2) return true;
+    if (grow_scratch(c, c->rowlut, (size_t)R * (33 + Qt) * full_lut_row_bytes(Sb))) return false;
+    *lut = fill_row_lut(c, d_lut_blob, R, Qt, S2, Sb, minscore, c->rowlut.p);
     return true;
+}
+
+// Does K2 run with short-lived workgroups (kbbq_k2_tile.h) on rows of `cpr` chunks, `rg_bytes` of LUT per read group?  Mate-pair
+// rows and one-read-per-row planes, 4-bit and character planes (round 4; KBBQ_K2_TILE_CHARS=0: the persistent kernel as before),
+// one read group or rows grouped by read group, unless KBBQ_K2_TILE=0 (A/B timing); everything else, and LUTs of one group beyond
+// a third of the LDS, keeps the persistent kernel
+// (one read per row: while two workgroups' copies of the narrowed LUT fit a CU -- rows of up to ~300 bases; measured up to
+//  there, scripts/gpu_tilekb.sh: config 5's K2 0.651 -> 0.687 of roofline going from a 32 KB to a 52 KB limit)
+static bool k2_tile_serves(const kbbq_ctx* c, int pairs, int nib, int R, bool grouped, int cpr, size_t rg_bytes)
+{
+    if (env_is("KBBQ_K2_TILE", "0") || (!nib && env_is("KBBQ_K2_TILE_CHARS", "0"))) return false;
+    if ((R != 1 && !grouped) || cpr < 2 || cpr > 4096) return false;
+    return pairs ? rg_bytes * 3 <= (size_t)c->lds_bytes : rg_bytes <= K2T_ROW_LUT_MAX;
+}
+
+// K2v3Params of rows whose LUT has Qt quality rows and, one read per row, the cycle width Sb (mate-pair rows: their own LUT,
+// d_pair_lut).  q.full is the blob's full LUT: the caller narrows it (narrowed_row_lut, fill_row_lut) when Sb < S2.
+static K2v3Params k2v3_params(kbbq_ctx* c, const uint8_t* d_seq, const uint8_t* d_qual, const uint32_t* d_meta, int64_t nrows, int pitch,
+                              int pairs, int R, int Qt, int S2, int Sb, int minscore, const void* d_lut_blob, const void* d_pair_lut,
+                              const int64_t* d_seg, const int64_t* d_perm, uint8_t* d_out)
+{
+    K2v3Params q;
+    q.seq = d_seq; q.qual = d_qual; q.meta = d_meta; q.nreads = nrows; q.pitch = pitch;
+    q.cpr = pitch / 16; q.cpr_magic = magic_for(q.cpr);
+    q.R = R; q.Qt = Qt; q.S2 = S2; q.minscore = minscore; q.qlo = 33u + (u32)minscore;
+    q.lut16 = reinterpret_cast<const int16_t*>(d_lut_blob); q.rs16 = lut_row_stride(S2);
+    q.full = pairs ? reinterpret_cast<const int8_t*>(d_pair_lut)
+                   : reinterpret_cast<const int8_t*>(d_lut_blob) + lut_full_offset(R, Qt, S2);
+    q.rb = (u32)(pairs ? pair_lut_row_bytes(S2) : full_lut_row_bytes(Sb));
+    q.full_bytes = (int)((size_t)R * (33 + Qt) * q.rb);
+    if (pairs) { q.W = 0u; q.ctx_off = (u32)pair_pitch(S2); q.maxlen = S2 + 1; }
+    else { q.W = (u32)full_lut_width(Sb); q.ctx_off = 2u * q.W; q.maxlen = Sb; }
+    q.pairs = pairs; q.seg = reinterpret_cast<const long long*>(d_seg);
+    q.perm = reinterpret_cast<const long long*>(d_perm);
+    q.parts = K2V3_FRONTS;
+    q.rpb = 64;      // the persistent kernel's wave block; smaller blocks were measured slower (profiles/r01_traversal_microbench.md)
+    q.out = d_out; q.status = c->d_status;
+    return q;
+}
+
+// the persistent K2 on these rows: every read group's LUT in the LDS, or -- rows grouped by read group -- a slice of the grid
+// per group with that group's
+static int launch_k2v3(kbbq_ctx* c, const K2v3Params& q, int nib)
+{
+    const int slices = q.seg ? q.R : 1;
+    const size_t lds = (size_t)(33 + q.Qt) * q.rb * (size_t)(q.seg ? 1 : q.R);
+    // resident workgroups per CU: LDS copies of the LUT, and the register allocation's waves per SIMD
+    const int per_cu = std::max(1, std::min<int>((int)(c->lds_bytes / lds), (K2V3_WAVES * 4 * 64) / K2V3_THREADS));
+    const int64_t nblocks = (q.nreads + q.rpb - 1) / q.rpb;
+    const int64_t want = (nblocks + (K2V3_THREADS / 64) - 1) / (K2V3_THREADS / 64);
+    const int gx = (int)std::min<int64_t>(want, std::max<int64_t>(1, (int64_t)c->cus * per_cu / slices));
+    return launch_lds(c, 1, LDS_KERNELS[nib ? LK_K2V3_NIB : LK_K2V3], dim3((unsigned)std::max(gx, 1), (unsigned)slices, 1), dim3(K2V3_THREADS), lds, &q);
 }
 
 static int apply_rows(kbbq_ctx* c, const char* who, const uint8_t* d_seq, const uint8_t* d_qual, const uint32_t* d_meta,
@@ -645,43 +732,17 @@ int kbbq_apply_dev(kbbq_ctx* c, const uint8_t* d_seq, const uint8_t* d_qual, con
     // the LUT of the columns rows of this pitch can reach (narrowed_row_lut): a band of short reads under wide tables
     const int Sb = row_lut_width(pitch, S2);
     const size_t full_bytes = (size_t)R * (33 + Qt) * full_lut_row_bytes(Sb);
-    if (mode == KBBQ_APPLY_FAST && R == 1 && Qt == KQ && !(S2 & 1) && S2 <= 65534) {
-        // one read group, rows as a caller holds them (one character row per read): the short-lived kernel (kbbq_k2_tile.h) when
-        // apply_rows' conditions for it hold -- it falls through to the persistent kernel itself otherwise.  What it cannot serve
-        // (a foreign letter, q > 42, a read longer than the LUT) it reports as KBBQ_E_LUT: the caller's KBBQ_APPLY_CHECKED run
-        // decides, as for a LUT that is not range-safe.
-        const int cpr = pitch / 16;
-        const size_t rg_bytes = (size_t)(33 + KQ) * full_lut_row_bytes(Sb);
-        if (!env_is("KBBQ_K2_TILE", "0") && !env_is("KBBQ_K2_TILE_CHARS", "0") && cpr >= 2 && cpr <= 4096 && rg_bytes <= K2T_ROW_LUT_MAX)
-            return apply_rows(c, "kbbq_apply_dev", d_seq, d_qual, d_meta, nreads, pitch, 0, R, S2, minscore, d_lut, nullptr, nullptr, d_out, 0, nullptr);
-    }
+    // one read group, rows as a caller holds them (one character row per read): the short-lived kernel through apply_rows when it
+    // serves them.  What it cannot serve (a foreign letter, q > 42, a read longer than the LUT) it reports as KBBQ_E_LUT: the
+    // caller's KBBQ_APPLY_CHECKED run decides, as for a LUT that is not range-safe.
+    if (mode == KBBQ_APPLY_FAST && R == 1 && Qt == KQ && !(S2 & 1) && S2 <= 65534
+        && k2_tile_serves(c, 0, 0, R, false, pitch / 16, (size_t)(33 + KQ) * full_lut_row_bytes(Sb)))
+        return apply_rows(c, "kbbq_apply_dev", d_seq, d_qual, d_meta, nreads, pitch, 0, R, S2, minscore, d_lut, nullptr, nullptr, d_out, 0, nullptr);
     if (mode == KBBQ_APPLY_FAST && full_bytes <= (size_t)c->lds_bytes) {
-        K2v3Params q;
-        q.seq = d_seq; q.qual = d_qual; q.meta = d_meta; q.nreads = nreads; q.pitch = pitch;
-        q.cpr = pitch / 16; q.cpr_magic = magic_for(q.cpr);
-        q.R = R; q.Qt = Qt; q.S2 = S2; q.minscore = minscore; q.qlo = 33u + (u32)minscore;
-        q.lut16 = reinterpret_cast<const int16_t*>(d_lut); q.rs16 = lut_row_stride(S2);
-        q.full = reinterpret_cast<const int8_t*>(d_lut) + lut_full_offset(R, Qt, S2);
+        // the persistent kernel as apply_rows launches it, for any Qt and an odd S2 too (apply_rows takes neither)
+        K2v3Params q = k2v3_params(c, d_seq, d_qual, d_meta, nreads, pitch, 0, R, Qt, S2, Sb, minscore, d_lut, nullptr, nullptr, nullptr, d_out);
         if (!narrowed_row_lut(c, d_lut, R, Qt, S2, Sb, minscore, &q.full)) return fail(KBBQ_E_HIP, "kbbq_apply_dev: no scratch for the narrowed LUT");
-        q.full_bytes = (int)full_bytes;
-        q.rb = (u32)full_lut_row_bytes(Sb); q.W = (u32)full_lut_width(Sb); q.ctx_off = 2u * q.W;
-        q.maxlen = Sb; q.pairs = 0; q.seg = nullptr; q.rpb = 64; q.perm = nullptr;
-        q.parts = K2V3_FRONTS;
-        q.out = d_out; q.status = c->d_status;
-#ifdef K2V3_PER_CU
-        int per_cu = K2V3_PER_CU;
-#else
-        // resident workgroups per CU: LDS copies of the LUT, and the register allocation's waves per SIMD
-        int per_cu = std::max(1, std::min<int>((int)(c->lds_bytes / full_bytes), (K2V3_WAVES * 4 * 64) / K2V3_THREADS));
-#endif
-        const int64_t want = (nblocks + (K2V3_THREADS / 64) - 1) / (K2V3_THREADS / 64);
-        int gx = (int)std::min<int64_t>(want, (int64_t)c->cus * per_cu);
-        {
-            Timed t(c, 1);
-            hipLaunchKernelGGL(k2v3_apply<false>, dim3((unsigned)std::max(gx, 1)), dim3(K2V3_THREADS), full_bytes, c->stream, q);
-        }
-        HIPCHK(hipGetLastError());
-        return KBBQ_OK;
+        return launch_k2v3(c, q, 0);
     }
 
     K2Params p;
@@ -709,11 +770,10 @@ int kbbq_apply_dev(kbbq_ctx* c, const uint8_t* d_seq, const uint8_t* d_qual, con
     const int64_t want = (nblocks + (threads / 64) - 1) / (threads / 64);
     int gx = (int)std::min<int64_t>(want, (int64_t)c->cus * per_cu);
     dim3 grid((unsigned)std::max(gx, 1), 1, 1), block((unsigned)threads, 1, 1);
+    if (in_lds) return launch_lds(c, 1, LDS_KERNELS[fast ? LK_K2_LDS8 : LK_K2_LDS16], grid, block, lds, &p);
     {
         Timed t(c, 1);
-        if (!in_lds) hipLaunchKernelGGL((k2_apply<int16_t, false, true>), grid, block, 0, c->stream, p);
-        else if (fast) hipLaunchKernelGGL((k2_apply<int8_t, true, false>), grid, block, lds, c->stream, p);
-        else hipLaunchKernelGGL((k2_apply<int16_t, true, true>), grid, block, lds, c->stream, p);
+        hipLaunchKernelGGL((k2_apply<int16_t, false, true>), grid, block, 0, c->stream, p);       // the LUT stays in global memory: no LDS
     }
     HIPCHK(hipGetLastError());
     return KBBQ_OK;
@@ -952,6 +1012,32 @@ static size_t k1_lds_plan(K1v3Params& q, int dn, const kbbq_ctx* c)
     return bytes_for(q.ntrash, q.pos_copies);
 }
 
+// One attempt at K1's LDS geometry: `copies` of the context table beside cycle rows of 3S - cut words (3S words serve reads
+// of any length: one word per first-in-pair position [0, S) and per second-in-pair index S + 2(S - len) + pos <= 3S - len - 1).
+// False: the tables do not fit the LDS, or the 16-bit packed context counts could overflow between two flushes.
+static bool k1_geometry(K1v3Params& q, const kbbq_ctx* c, int copies, int cut, int minlen)
+{
+    q.row_bytes = (u32)((3 * q.S - cut) | 1) * 4u;
+    q.minlen = minlen;
+    // bytes past a read's end (quality 0) land on the trash row, the last one, at indexes up to 3S - cut - 1 + 15
+    q.slack_bytes = (u32)(q.S + 32) * 4u;
+    q.dn_flush_iters = std::max(1, 65535 / ((K1V3_THREADS / copies) * 16 * q.cpr));
+    const size_t lds = (size_t)q.nrows * 128 * copies + (size_t)q.nrows * q.row_bytes + q.slack_bytes;
+    return lds <= (size_t)c->lds_bytes && (K1V3_THREADS / copies) * 16 * q.cpr <= 65535;
+}
+
+static bool k1_split(const K1v3Params& q) { return q.type_minscore > q.minscore; }
+// iterations one workgroup per read group would make over the rows: no launch has more workgroups per group than this
+static int64_t k1_iters(const K1v3Params& q) { return ((q.nreads + 63) / 64 + (K1V3_THREADS / 64) - 1) / (K1V3_THREADS / 64); }
+
+// K1 on the rows of su.q: one 16-wave workgroup per CU, the read groups side by side in grid.y
+static int launch_k1(kbbq_ctx* c, K1Form form, const K1Setup& su, int nib)
+{
+    const int gx = (int)std::min<int64_t>(k1_iters(su.q), std::max(1, c->cus / su.q.R));
+    return launch_lds(c, 0, k1_kernel(form, k1_split(su.q), su.dn, nib, su.kj), dim3((unsigned)gx, (unsigned)su.q.R, 1), dim3(K1V3_THREADS),
+                      su.lds, &su.q);
+}
+
 // K1 (table-driven kernel) on one-read-per-row or mate-pair rows, optionally grouped by read group
 static int accumulate_rows(kbbq_ctx* c, const char* who, const uint8_t* d_seq, const uint8_t* d_cseq, const uint8_t* d_qual,
                            const uint32_t* d_meta, int64_t nrows, int pitch, int pairs, int R, int S2, int minscore,
@@ -971,7 +1057,8 @@ static int accumulate_rows(kbbq_ctx* c, const char* who, const uint8_t* d_seq, c
     if (nrows == 0) return KBBQ_OK;
     HIPCHK(hipSetDevice(c->device));
     const int S = S_band ? S_band : S2 / 2;          // the LDS tables are laid out for the longest read of THIS batch
-    K1v3Params q;
+    K1Setup su;
+    K1v3Params& q = su.q;
     q.aflags = nullptr; q.aclip = nullptr; q.atrim = nullptr;
     q.seq = d_seq; q.cseq = d_cseq; q.qual = d_qual; q.meta = d_meta;
     q.nreads = nrows; q.pitch = pitch; q.cpr = pitch / 16; q.cpr_magic = magic_for(q.cpr);
@@ -982,82 +1069,38 @@ static int accumulate_rows(kbbq_ctx* c, const char* who, const uint8_t* d_seq, c
     q.seg = reinterpret_cast<const long long*>(d_seg);
     q.tables = reinterpret_cast<u64*>(d_tables); q.status = c->d_status;
     q.genome = nullptr; q.ag0 = nullptr;
-    // LDS geometry.  A cycle row has one word per first-in-pair position [0, S) and per second-in-pair index
-    // S + 2(S - len) + pos <= 3S - len - 1: 3S words serve any length.  When that does not fit (reads of ~200 bases
-    // and more), a band whose shortest read is S_min needs only 3S - S_min words, and 8 copies of the context table
-    // instead of 16 free the rest: reads of up to ~300 bases still run this kernel.
+    // LDS geometry (k1_geometry).  When 3S words per cycle row do not fit (reads of ~200 bases and more), a band whose shortest
+    // read is S_min needs only 3S - S_min words, and 8 copies of the context table instead of 16 free the rest: reads of up to
+    // ~300 bases still run this kernel.
     const int trim = (!pairs && S_min > 0) ? std::min(S_min, S) : 0;
-    int dn = 0; size_t lds3 = 0;
     // mate-pair rows of 19 or 13 chunks (2 x 150, 2 x 100 bp) on 4-bit planes: the chunk-position-major cycle table (kernel comment), the
     // 13-chunk form with 8 trash rows (K1v3Params::ntrash; 19 chunks were measured with 4 and 8 of them: nothing).  Measured for the other
     // lengths instruments emit (profiles/): 2 x 100 bp 1.37 -> 1.31 ms per 3 Gbases; 2 x 50 bp (7 chunks) is FASTER position-major with its
     // copies of the cycle table (1.52 against 1.64 ms); 2 x 75 / 2 x 125 / 2 x 250 bp never take mate-pair rows (2 S + 1 rounds up to
     // twice the single read's pitch: no bytes saved).
-    const bool km = pairs && nib && (q.cpr == 19 || q.cpr == 13);
-    bool km_ok = false;                                    // the form applies AND its tables fit
-    if (km) {
+    if (pairs && nib && (q.cpr == 19 || q.cpr == 13)) {
         q.row_bytes = (u32)(((16 * q.cpr + 31) & ~31) * 4);
         q.minlen = 0; q.slack_bytes = 0; q.pos_copies = 1;
         q.dn_flush_iters = std::max(1, 65535 / ((K1V3_THREADS / K1V3_DNREP) * 16 * q.cpr));
-        for (int nt = q.cpr == 19 ? 1 : 8; nt >= 1; nt >>= 1) {
+        for (int nt = q.cpr == 19 ? 1 : 8; nt >= 1 && !su.dn; nt >>= 1) {
             const size_t rows = (size_t)q.nrows - 1 + nt;
-            lds3 = rows * 128 * K1V3_DNREP + rows * q.row_bytes;
-            if (lds3 <= (size_t)c->lds_bytes) { dn = K1V3_DNREP; km_ok = true; q.ntrash = nt; q.pos_copy_bytes = (u32)(rows * q.row_bytes); break; }
+            su.lds = rows * 128 * K1V3_DNREP + rows * q.row_bytes;
+            if (su.lds > (size_t)c->lds_bytes) continue;
+            su.dn = K1V3_DNREP; su.kj = q.cpr;                // the form applies AND its tables fit
+            q.ntrash = nt; q.pos_copy_bytes = (u32)(rows * q.row_bytes);
         }
     }
-    for (int attempt = 0; attempt < (trim ? 3 : 1) && !dn; ++attempt) {
+    for (int attempt = 0; attempt < (trim ? 3 : 1) && !su.dn; ++attempt) {
         const int copies = attempt == 2 ? 8 : K1V3_DNREP, cut = attempt ? trim : 0;
-        const int words = (3 * S - cut) | 1;
-        q.row_bytes = (u32)words * 4u;
-        q.minlen = cut;
-        // bytes past a read's end (quality 0) land on the trash row, the last one, at indexes up to 3S - cut - 1 + 15
-        q.slack_bytes = (u32)(S + 32) * 4u;
-        q.dn_flush_iters = std::max(1, 65535 / ((K1V3_THREADS / copies) * 16 * q.cpr));
-        lds3 = (size_t)q.nrows * 128 * copies + (size_t)q.nrows * q.row_bytes + q.slack_bytes;
-        if (lds3 <= (size_t)c->lds_bytes && (K1V3_THREADS / copies) * 16 * q.cpr <= 65535) dn = copies;
+        if (k1_geometry(q, c, copies, cut, cut)) su.dn = copies;
     }
-    if (!dn) {
+    if (!su.dn) {
         if (fits) { *fits = false; return KBBQ_OK; }     // the caller has another kernel for this shape
         return fail(KBBQ_E_LUT, "%s: %d-base reads with minscore %d do not fit the LDS tables; use plain one-read-per-row planes", who, S, minscore);
     }
-    if (!km_ok) lds3 = k1_lds_plan(q, dn, c);
-    const bool split = dinuc_minscore > minscore;
-    const int64_t nblocks = (nrows + 63) / 64;
-    const int64_t iters = (nblocks + (K1V3_THREADS / 64) - 1) / (K1V3_THREADS / 64);
-    if (setup_only) {
-        setup_only->q = q; setup_only->dn = dn; setup_only->km = km_ok; setup_only->split = split;
-        setup_only->lds = lds3; setup_only->iters = iters;
-        return KBBQ_OK;
-    }
-    int gx = (int)std::min<int64_t>(iters, std::max(1, c->cus / R));
-    dim3 grid((unsigned)gx, (unsigned)R, 1), block(K1V3_THREADS, 1, 1);
-    {
-        Timed t(c, 0);
-        if (km_ok) {
-#define KBBQ_KM_LAUNCH(KJ_) case KJ_: \
-                if (split) hipLaunchKernelGGL((k1v3_accumulate<true, K1V3_DNREP, true, KJ_>), grid, block, lds3, c->stream, q); \
-                else hipLaunchKernelGGL((k1v3_accumulate<false, K1V3_DNREP, true, KJ_>), grid, block, lds3, c->stream, q); \
-                break;
-            switch (q.cpr) { KBBQ_KM_LAUNCH(13) KBBQ_KM_LAUNCH(19) }
-#undef KBBQ_KM_LAUNCH
-        } else if (nib) {
-            if (dn == K1V3_DNREP) {
-                if (split) hipLaunchKernelGGL((k1v3_accumulate<true, K1V3_DNREP, true>), grid, block, lds3, c->stream, q);
-                else hipLaunchKernelGGL((k1v3_accumulate<false, K1V3_DNREP, true>), grid, block, lds3, c->stream, q);
-            } else {
-                if (split) hipLaunchKernelGGL((k1v3_accumulate<true, 8, true>), grid, block, lds3, c->stream, q);
-                else hipLaunchKernelGGL((k1v3_accumulate<false, 8, true>), grid, block, lds3, c->stream, q);
-            }
-        } else if (dn == K1V3_DNREP) {
-            if (split) hipLaunchKernelGGL((k1v3_accumulate<true, K1V3_DNREP>), grid, block, lds3, c->stream, q);
-            else hipLaunchKernelGGL((k1v3_accumulate<false, K1V3_DNREP>), grid, block, lds3, c->stream, q);
-        } else {
-            if (split) hipLaunchKernelGGL((k1v3_accumulate<true, 8>), grid, block, lds3, c->stream, q);
-            else hipLaunchKernelGGL((k1v3_accumulate<false, 8>), grid, block, lds3, c->stream, q);
-        }
-    }
-    HIPCHK(hipGetLastError());
-    return KBBQ_OK;
+    if (!su.kj) su.lds = k1_lds_plan(q, su.dn, c);
+    if (setup_only) { *setup_only = su; return KBBQ_OK; }
+    return launch_k1(c, K1_ROWS, su, nib);
 }
 
 int kbbq_accumulate_pairs_dev(kbbq_ctx* c, const uint8_t* d_pseq, const uint8_t* d_pcseq, const uint8_t* d_pqual,
@@ -1105,6 +1148,18 @@ int kbbq_pair_lut_rows_dev(kbbq_ctx* c, const void* d_lut_blob, int R, int S2, i
     return KBBQ_OK;
 }
 
+// the short-lived kernel's parameters for the rows and the LUT of `q` (no workgroup plan: one read group, all rows)
+static K2tParams k2t_params(const K2v3Params& q)
+{
+    K2tParams t;
+    t.seq = q.seq; t.qual = q.qual; t.meta = q.meta; t.nchunks = q.nreads * q.cpr; t.cpr = q.cpr; t.cpr_magic = q.cpr_magic;
+    t.Qt = q.Qt; t.S2 = q.S2; t.maxlen = q.maxlen; t.lut = q.full; t.lut_bytes = (int)(((size_t)(33 + q.Qt) * q.rb + 15) & ~(size_t)15);
+    t.rb = q.rb; t.ctx_off = q.ctx_off; t.W = q.W; t.seg = q.seg; t.R = q.R; t.wg_start = nullptr; t.order = nullptr;
+    t.perm = q.perm; t.pitch = q.pitch; t.out = q.out; t.status = q.status;
+    t.xcd_tiles = K2T_XCD_TILES;
+    return t;
+}
+
 // K2 (table-driven kernel) on one-read-per-row or mate-pair rows, optionally grouped by read group
 static int apply_rows(kbbq_ctx* c, const char* who, const uint8_t* d_seq, const uint8_t* d_qual, const uint32_t* d_meta,
                       int64_t nrows, int pitch, int pairs, int R, int S2, int minscore, const void* d_lut_blob,
@@ -1116,92 +1171,41 @@ static int apply_rows(kbbq_ctx* c, const char* who, const uint8_t* d_seq, const 
     if (S2 <= 0 || (S2 & 1) || S2 > 65534) return fail(KBBQ_E_ARG, "%s: S2 must be positive and even (%d)", who, S2);
     if (minscore < 0 || minscore > 222) return fail(KBBQ_E_ARG, "%s: minscore out of range", who);
     if (pairs && pitch != pair_pitch(S2)) return fail(KBBQ_E_ARG, "%s: mate-pair rows of %d-base reads have pitch %d, not %d", who, S2 / 2, pair_pitch(S2), pitch);
-    K2v3Params q;
     // one read per row: the LUT of the columns rows of this pitch can reach (narrowed_row_lut)
     const int Sb = pairs ? S2 : row_lut_width(pitch, S2);
-    q.rb = (u32)(pairs ? pair_lut_row_bytes(S2) : full_lut_row_bytes(Sb));
+    K2v3Params q = k2v3_params(c, d_seq, d_qual, d_meta, nrows, pitch, pairs, R, KQ, S2, Sb, minscore, d_lut_blob, d_pair_lut, d_seg, d_perm, d_out);
     const size_t rg_bytes = (size_t)(33 + KQ) * q.rb;
-    const size_t all_bytes = rg_bytes * (size_t)R;
-    const size_t lds = d_seg ? rg_bytes : all_bytes;
+    const size_t lds = d_seg ? rg_bytes : rg_bytes * (size_t)R;
     if (lds > (size_t)c->lds_bytes)
         return fail(KBBQ_E_LUT, "%s: the apply LUT (%zu B) does not fit the LDS; group the rows by read group or use kbbq_apply_dev", who, lds);
     if (nrows == 0) return KBBQ_OK;
     HIPCHK(hipSetDevice(c->device));
-    q.seq = d_seq; q.qual = d_qual; q.meta = d_meta; q.nreads = nrows; q.pitch = pitch;
-    q.cpr = pitch / 16; q.cpr_magic = magic_for(q.cpr);
-    q.R = R; q.Qt = KQ; q.S2 = S2; q.minscore = minscore; q.qlo = 33u + (u32)minscore;
-    q.lut16 = reinterpret_cast<const int16_t*>(d_lut_blob); q.rs16 = lut_row_stride(S2);
-    q.full = pairs ? reinterpret_cast<const int8_t*>(d_pair_lut)
-                   : reinterpret_cast<const int8_t*>(d_lut_blob) + lut_full_offset(R, KQ, S2);
-    q.full_bytes = (int)all_bytes;
-    if (pairs) { q.W = 0u; q.ctx_off = (u32)pair_pitch(S2); q.maxlen = S2 + 1; }
-    else {
-        if (!narrowed_row_lut(c, d_lut_blob, R, KQ, S2, Sb, minscore, &q.full)) return fail(KBBQ_E_HIP, "%s: no scratch for the narrowed LUT", who);
-        q.W = (u32)full_lut_width(Sb); q.ctx_off = 2u * q.W; q.maxlen = Sb;
-    }
-    q.pairs = pairs; q.seg = reinterpret_cast<const long long*>(d_seg);
-    q.perm = reinterpret_cast<const long long*>(d_perm);
-    q.out = d_out; q.status = c->d_status;
-    int per_cu = std::max(1, std::min<int>((int)(c->lds_bytes / lds), (K2V3_WAVES * 4 * 64) / K2V3_THREADS));
-    q.parts = K2V3_FRONTS;
-    q.rpb = 64;      // the persistent kernel's wave block; smaller blocks were measured slower (profiles/r01_traversal_microbench.md)
-    const int64_t nblocks = (nrows + q.rpb - 1) / q.rpb;
-    const int64_t want = (nblocks + (K2V3_THREADS / 64) - 1) / (K2V3_THREADS / 64);
-    const int slices = d_seg ? R : 1;
-    int gx = (int)std::min<int64_t>(want, std::max<int64_t>(1, (int64_t)c->cus * per_cu / slices));
+    if (!pairs && !narrowed_row_lut(c, d_lut_blob, R, KQ, S2, Sb, minscore, &q.full)) return fail(KBBQ_E_HIP, "%s: no scratch for the narrowed LUT", who);
+    if (!k2_tile_serves(c, pairs, nib, R, d_seg != nullptr, q.cpr, rg_bytes)) return launch_k2v3(c, q, nib);
 
-    // mate-pair rows on 4-bit planes: short-lived workgroups (kbbq_k2_tile.h) unless KBBQ_K2_TILE=0 (A/B timing); everything
-    // else, and LUTs of one group beyond a third of the LDS, keeps the persistent kernel
-    // (one read per row: while two workgroups' copies of the narrowed LUT fit a CU -- rows of up to ~300 bases; measured up to
-    //  there, scripts/gpu_tilekb.sh: config 5's K2 0.651 -> 0.687 of roofline going from a 32 KB to a 52 KB limit)
-    // character planes (round 4; KBBQ_K2_TILE_CHARS=0: the persistent kernel as before): the same kernel with 16-byte sequence loads
-    const bool planes_ok = nib || !env_is("KBBQ_K2_TILE_CHARS", "0");
-    if (!env_is("KBBQ_K2_TILE", "0") && planes_ok && (R == 1 || d_seg) && q.cpr >= 2 && q.cpr <= 4096
-        && (pairs ? rg_bytes * 3 <= (size_t)c->lds_bytes : rg_bytes <= K2T_ROW_LUT_MAX)) {
-        K2tParams t;
-        t.seq = d_seq; t.qual = d_qual; t.meta = d_meta; t.nchunks = nrows * q.cpr; t.cpr = q.cpr; t.cpr_magic = q.cpr_magic;
-        t.Qt = KQ; t.S2 = S2; t.maxlen = q.maxlen; t.lut = q.full; t.lut_bytes = (int)((rg_bytes + 15) & ~(size_t)15);
-        t.rb = q.rb; t.ctx_off = q.ctx_off; t.W = q.W; t.seg = reinterpret_cast<const long long*>(d_seg); t.R = R; t.wg_start = nullptr; t.order = nullptr;
-        t.perm = reinterpret_cast<const long long*>(d_perm); t.pitch = pitch; t.out = d_out; t.status = c->d_status;
-        t.xcd_tiles = K2T_XCD_TILES;
-        const int64_t per_wg = (int64_t)(K2T_THREADS / 64) * 64 * K2T_STEPS;
-        int64_t gt = (t.nchunks + per_wg - 1) / per_wg;
-        if (d_seg) {
-            gt += R;                                     // every group rounds its last workgroup up
-            const bool interleave = d_perm && R > 1;
-            const int64_t ints = (int64_t)(R + 1) + 1 + (interleave ? 2 * gt : 0);
-            if (ints > 0x7FFFFFFF) return fail(KBBQ_E_ARG, "%s: too many workgroups", who);
-            if (c->wgplan_n < (int)ints) {
-                if (c->d_wgplan) { HIPCHK(hipStreamSynchronize(c->stream)); (void)hipFree(c->d_wgplan); c->d_wgplan = nullptr; c->wgplan_n = 0; }
-                HIPCHK(hipMalloc((void**)&c->d_wgplan, (size_t)ints * sizeof(int)));
-                c->wgplan_n = (int)ints;
-            }
-            K2tPlanParams pl; pl.seg = t.seg; pl.R = R; pl.cpr = q.cpr; pl.wg_start = c->d_wgplan;
-            hipLaunchKernelGGL(k2t_plan, dim3(1), dim3(64), 0, c->stream, pl);
-            t.wg_start = c->d_wgplan;
-            if (interleave) {
-                K2tOrderParams op; op.wg_start = c->d_wgplan; op.R = R;
-                op.xcd = K2T_XCD;
-                op.order = reinterpret_cast<int2*>(c->d_wgplan + ((R + 2) & ~1));           // 8-byte aligned behind the starts
-                hipLaunchKernelGGL(k2t_order, dim3((unsigned)((gt + 255) / 256)), dim3(256), 0, c->stream, op);
-                t.order = op.order;
-            }
+    K2tParams t = k2t_params(q);
+    const int64_t per_wg = (int64_t)(K2T_THREADS / 64) * 64 * K2T_STEPS;
+    int64_t gt = (t.nchunks + per_wg - 1) / per_wg;
+    if (d_seg) {
+        gt += R;                                     // every group rounds its last workgroup up
+        const bool interleave = d_perm && R > 1;
+        const int64_t ints = (int64_t)(R + 1) + 1 + (interleave ? 2 * gt : 0);
+        if (ints > 0x7FFFFFFF) return fail(KBBQ_E_ARG, "%s: too many workgroups", who);
+        rc = grow_scratch(c, c->wgplan, (size_t)ints * sizeof(int));
+        if (rc) return rc;
+        int* wg_start = reinterpret_cast<int*>(c->wgplan.p);
+        K2tPlanParams pl; pl.seg = t.seg; pl.R = R; pl.cpr = q.cpr; pl.wg_start = wg_start;
+        hipLaunchKernelGGL(k2t_plan, dim3(1), dim3(64), 0, c->stream, pl);
+        t.wg_start = wg_start;
+        if (interleave) {
+            K2tOrderParams op; op.wg_start = wg_start; op.R = R;
+            op.xcd = K2T_XCD;
+            op.order = reinterpret_cast<int2*>(wg_start + ((R + 2) & ~1));           // 8-byte aligned behind the starts
+            hipLaunchKernelGGL(k2t_order, dim3((unsigned)((gt + 255) / 256)), dim3(256), 0, c->stream, op);
+            t.order = op.order;
         }
-        {
-            Timed tm(c, 1);
-            if (nib) hipLaunchKernelGGL(k2t_apply<true>, dim3((unsigned)gt), dim3(K2T_THREADS), (size_t)t.lut_bytes, c->stream, t);
-            else hipLaunchKernelGGL(k2t_apply<false>, dim3((unsigned)gt), dim3(K2T_THREADS), (size_t)t.lut_bytes, c->stream, t);
-        }
-        HIPCHK(hipGetLastError());
-        return KBBQ_OK;
     }
-    {
-        Timed t(c, 1);
-        if (nib) hipLaunchKernelGGL(k2v3_apply<true>, dim3((unsigned)std::max(gx, 1), (unsigned)slices, 1), dim3(K2V3_THREADS), lds, c->stream, q);
-        else hipLaunchKernelGGL(k2v3_apply<false>, dim3((unsigned)std::max(gx, 1), (unsigned)slices, 1), dim3(K2V3_THREADS), lds, c->stream, q);
-    }
-    HIPCHK(hipGetLastError());
-    return KBBQ_OK;
+    return launch_lds(c, 1, LDS_KERNELS[nib ? LK_K2T_NIB : LK_K2T], dim3((unsigned)gt), dim3(K2T_THREADS), (size_t)t.lut_bytes, &t);
 }
 
 int kbbq_apply_pairs_dev(kbbq_ctx* c, const uint8_t* d_pseq, const uint8_t* d_pqual, const uint32_t* d_pmeta,
@@ -1322,7 +1326,7 @@ int kbbq_accumulate_bands_dev(kbbq_ctx* c, const kbbq_band* bands, int nbands, i
                                  dinuc_minscore, b.d_seg, d_tables, &fits, pairs ? 0 : b.S_band, pairs ? 0 : b.S_min, nib,
                                  (b.flags & KBBQ_ROWS_TWINS) ? 1 : 0, &su);
             if (rc) return rc;
-            can = fits && !su.km && (nib_of_merge < 0 || nib_of_merge == nib);
+            can = fits && !su.kj && (nib_of_merge < 0 || nib_of_merge == nib);
         }
         if (can) { nib_of_merge = nib; merged.push_back(i); setups.push_back(su); }
         else alone.push_back(i);
@@ -1351,7 +1355,7 @@ int kbbq_accumulate_bands_dev(kbbq_ctx* c, const kbbq_band* bands, int nbands, i
     size_t lds = 0;
     for (const K1Setup& su : setups) {
         weight.push_back((double)su.q.nreads * (su.q.cpr + row_cost) * (1.0 + slope * su.q.cpr) * (su.dn == K1V3_DNREP ? 1.0 : dn8_cost));
-        cap.push_back(std::max<int64_t>(1, su.iters));
+        cap.push_back(std::max<int64_t>(1, k1_iters(su.q)));
         lds = std::max(lds, su.lds);
     }
     share_workgroups(weight, cap, G, share);
@@ -1361,21 +1365,11 @@ int kbbq_accumulate_bands_dev(kbbq_ctx* c, const kbbq_band* bands, int nbands, i
         t.dn[j] = setups[j].dn; t.band[j] = setups[j].q;
     }
     t.wg_start[setups.size()] = run;
-    const bool split = setups[0].split;
-    dim3 grid((unsigned)run, (unsigned)R, 1), block(K1V3_THREADS, 1, 1);
     unsigned long long* dbg = nullptr;                    // KBBQ_K1_BANDS_DBG=1: when did every band's workgroups start and end?
     if (getenv("KBBQ_K1_BANDS_DBG")) { HIPCHK(hipMalloc((void**)&dbg, sizeof(unsigned long long) * 2 * (size_t)run)); t.dbg = dbg; }
-    {
-        Timed tm(c, 0);
-        if (nib_of_merge) {
-            if (split) hipLaunchKernelGGL((k1v3_bands<true, true>), grid, block, lds, c->stream, t);
-            else hipLaunchKernelGGL((k1v3_bands<false, true>), grid, block, lds, c->stream, t);
-        } else {
-            if (split) hipLaunchKernelGGL((k1v3_bands<true, false>), grid, block, lds, c->stream, t);
-            else hipLaunchKernelGGL((k1v3_bands<false, false>), grid, block, lds, c->stream, t);
-        }
-    }
-    HIPCHK(hipGetLastError());
+    int rc = launch_lds(c, 0, k1_kernel(K1_BANDS, k1_split(setups[0].q), 0, nib_of_merge, 0), dim3((unsigned)run, (unsigned)R, 1),
+                        dim3(K1V3_THREADS), lds, &t);
+    if (rc) return rc;
     if (dbg) {
         std::vector<unsigned long long> h(2 * (size_t)run);
         HIPCHK(hipStreamSynchronize(c->stream));
@@ -1408,20 +1402,20 @@ int kbbq_apply_bands_dev(kbbq_ctx* c, const kbbq_band* bands, int nbands, int R,
     if (!c) return fail(KBBQ_E_ARG, "ctx is NULL");
     if (nbands < 0 || (nbands > 0 && !bands) || !d_lut_blob) return fail(KBBQ_E_ARG, "kbbq_apply_bands_dev: bad argument");
     if (R <= 0 || R > 32767 || S2 <= 0 || (S2 & 1) || S2 > 65534 || minscore < 0 || minscore > 222) return fail(KBBQ_E_ARG, "kbbq_apply_bands_dev: bad shape");
-    // the merged kernel (k2t_bands) takes what the short-lived kernel takes of one-read-per-row 4-bit planes with one read
-    // group: rows of 2..4096 chunks whose pitch-narrowed LUT is small (apply_rows' own test); the rest goes band by band
-    const bool tile = !env_is("KBBQ_K2_TILE", "0");
+    // the merged kernel (k2t_bands) takes what the short-lived kernel takes (k2_tile_serves) of one-read-per-row 4-bit planes
+    // with one read group; the rest goes band by band.
+    // Unlike apply_rows, the LUT's cycle width is min(pitch, S2) whatever KBBQ_K2_ROWLUT says, only R == 1 merges (not rows
+    // grouped by read group), and pointers and alignment are tested here: a band that fails them goes alone and is reported there.
     std::vector<int> merged, alone;
     for (int i = 0; i < nbands; ++i) {
         const kbbq_band& b = bands[i];
         if (b.nrows == 0) continue;
         int rc = layout_flags_ok("kbbq_apply_bands_dev", b.flags);
         if (rc) return rc;
-        const int cpr = b.pitch / 16;
         const int Sb = std::min(b.pitch, S2);
-        const bool can = tile && (int)merged.size() < K2T_MAX_BANDS && R == 1
-                         && b.flags == KBBQ_ROWS_NIBBLES && !b.d_seg && !b.d_perm && b.pitch > 0 && !(b.pitch & 15) && cpr >= 2 && cpr <= 4096
-                         && (size_t)(33 + KQ) * full_lut_row_bytes(Sb) <= K2T_ROW_LUT_MAX
+        const bool can = (int)merged.size() < K2T_MAX_BANDS && R == 1
+                         && b.flags == KBBQ_ROWS_NIBBLES && !b.d_seg && !b.d_perm && b.pitch > 0 && !(b.pitch & 15)
+                         && k2_tile_serves(c, 0, 1, R, false, b.pitch / 16, (size_t)(33 + KQ) * full_lut_row_bytes(Sb))
                          && !(((uintptr_t)b.d_seq | (uintptr_t)b.d_qual | (uintptr_t)b.d_out) & 15) && b.d_seq && b.d_qual && b.d_meta && b.d_out;
         (can ? merged : alone).push_back(i);
     }
@@ -1435,11 +1429,8 @@ int kbbq_apply_bands_dev(kbbq_ctx* c, const kbbq_band* bands, int nbands, int R,
     // every band's LUT, narrowed to the columns rows of its pitch can reach, side by side in the context's scratch
     std::vector<size_t> lut_off; size_t need = 0;
     for (int i : merged) { lut_off.push_back(need); need += ((size_t)R * (33 + KQ) * full_lut_row_bytes(std::min(bands[i].pitch, S2)) + 255) & ~(size_t)255; }
-    if (c->rowlut_bytes < need) {
-        if (c->d_rowlut) { HIPCHK(hipStreamSynchronize(c->stream)); (void)hipFree(c->d_rowlut); c->d_rowlut = nullptr; c->rowlut_bytes = 0; }
-        HIPCHK(hipMalloc(&c->d_rowlut, need));
-        c->rowlut_bytes = need;
-    }
+    int rc = grow_scratch(c, c->rowlut, need);
+    if (rc) return rc;
     K2tBandsParams t;
     memset(&t, 0, sizeof t);
     t.nbands = (int)merged.size();
@@ -1448,30 +1439,16 @@ int kbbq_apply_bands_dev(kbbq_ctx* c, const kbbq_band* bands, int nbands, int R,
     for (size_t k = 0; k < merged.size(); ++k) {
         const kbbq_band& b = bands[merged[k]];
         const int Sb = std::min(b.pitch, S2);
-        RowLutParams f;
-        f.lut16 = reinterpret_cast<const int16_t*>(d_lut_blob); f.rs16 = lut_row_stride(S2); f.R = R; f.Qt = KQ; f.S2 = S2; f.Sb = Sb;
-        f.minscore = std::min(std::max(minscore, 0), KQ);
-        f.out = reinterpret_cast<int8_t*>(c->d_rowlut) + lut_off[k];
-        hipLaunchKernelGGL(k3_fill_row_lut, dim3((unsigned)(R * (33 + KQ))), dim3(256), 0, c->stream, f);
-        K2tParams& q = t.band[k];
-        q.seq = b.d_seq; q.qual = b.d_qual; q.meta = b.d_meta; q.cpr = b.pitch / 16; q.cpr_magic = magic_for(q.cpr);
-        q.nchunks = b.nrows * q.cpr; q.Qt = KQ; q.S2 = S2; q.maxlen = Sb;
-        q.rb = (u32)full_lut_row_bytes(Sb); q.W = (u32)full_lut_width(Sb); q.ctx_off = 2u * q.W;
-        q.lut = f.out; q.lut_bytes = (int)((((size_t)(33 + KQ) * q.rb) + 15) & ~(size_t)15);
-        q.seg = nullptr; q.wg_start = nullptr; q.order = nullptr; q.R = R; q.perm = nullptr; q.pitch = b.pitch; q.out = b.d_out; q.status = c->d_status;
-        q.xcd_tiles = K2T_XCD_TILES;
+        K2v3Params rows = k2v3_params(c, b.d_seq, b.d_qual, b.d_meta, b.nrows, b.pitch, 0, R, KQ, S2, Sb, minscore, d_lut_blob, nullptr, nullptr, nullptr, b.d_out);
+        rows.full = fill_row_lut(c, d_lut_blob, R, KQ, S2, Sb, minscore, reinterpret_cast<char*>(c->rowlut.p) + lut_off[k]);
+        const K2tParams& q = t.band[k] = k2t_params(rows);
         lds = std::max(lds, (size_t)q.lut_bytes);
         t.wg_start[k] = (int)run;
         run += (q.nchunks + per_wg - 1) / per_wg;
         if (run > 0x7FFFFFFF) return fail(KBBQ_E_ARG, "kbbq_apply_bands_dev: too many workgroups");
     }
     t.wg_start[merged.size()] = (int)run;
-    {
-        Timed tm(c, 1);
-        hipLaunchKernelGGL(k2t_bands, dim3((unsigned)run), dim3(K2T_THREADS), lds, c->stream, t);
-    }
-    HIPCHK(hipGetLastError());
-    return KBBQ_OK;
+    return launch_lds(c, 1, LDS_KERNELS[LK_K2T_BANDS], dim3((unsigned)run), dim3(K2T_THREADS), lds, &t);
 }
 
 int kbbq_meta_stats_dev(kbbq_ctx* c, const uint32_t* d_meta, int64_t nreads, int32_t* h_stats8)
@@ -1581,18 +1558,30 @@ int kbbq_unpack_nibbles_dev(kbbq_ctx* c, const uint8_t* d_nib, int64_t nbases, u
     return KBBQ_OK;
 }
 
+// K4's view of a batch of aligned reads; skipmask == NULL: bit 7 of a reference byte is its site flag; skip == NULL: ONE plane of
+// flags (err)
+static K4Params k4_params(kbbq_ctx* c, const uint8_t* d_seq, const uint32_t* d_len, int64_t nreads, int pitch, const int64_t* d_ref_start,
+                          const int32_t* d_ref_len, const uint32_t* d_cig_off, const uint32_t* d_cig_n, const uint32_t* d_cigar,
+                          const uint8_t* d_genome, const uint8_t* d_skipmask, int64_t genome_len, const uint8_t* d_flip, uint8_t* d_err,
+                          uint8_t* d_skip)
+{
+    K4Params p;
+    p.seq = d_seq; p.len = d_len; p.nreads = nreads; p.pitch = pitch;
+    p.ref_start = (const long long*)d_ref_start; p.ref_len = d_ref_len;
+    p.cig_off = d_cig_off; p.cig_n = d_cig_n; p.cigar = d_cigar;
+    p.genome = d_genome; p.skipmask = d_skipmask; p.genome_len = genome_len; p.flip = d_flip; p.err = d_err; p.skip = d_skip;
+    p.status = c->d_status;
+    return p;
+}
+
 // the first four operations of every read inline, one 32-byte record per read (context-owned scratch); with aflags_out also
 // the classification kbbq_tally_aligned_dev needs (K4RecParams)
 static int k4_records(kbbq_ctx* c, const K4Params& p, const u32* aflags_in, u32* aflags_out, u32* rows, u32* nrows, int pitch)
 {
-    const size_t need = (size_t)p.nreads * sizeof(K4Rec);
-    if (c->ops4_bytes < need) {
-        if (c->d_ops4) { HIPCHK(hipStreamSynchronize(c->stream)); (void)hipFree(c->d_ops4); c->d_ops4 = nullptr; c->ops4_bytes = 0; }
-        HIPCHK(hipMalloc(&c->d_ops4, need));
-        c->ops4_bytes = need;
-    }
+    int rc = grow_scratch(c, c->ops4, (size_t)p.nreads * sizeof(K4Rec));
+    if (rc) return rc;
     K4RecParams ip; ip.len = p.len; ip.ref_len = p.ref_len; ip.cig_off = p.cig_off; ip.cig_n = p.cig_n; ip.cigar = p.cigar;
-    ip.nreads = p.nreads; ip.recs = (K4Rec*)c->d_ops4;
+    ip.nreads = p.nreads; ip.recs = (K4Rec*)c->ops4.p;
     ip.aflags_in = aflags_in; ip.aflags_out = aflags_out; ip.rows = rows; ip.nrows = nrows;
     ip.ref_start = p.ref_start; ip.genome_len = p.genome_len; ip.pitch = pitch;
     int gi = (int)std::min<int64_t>((p.nreads + 255) / 256, (int64_t)c->cus * 16);
@@ -1612,19 +1601,15 @@ int kbbq_find_errors_dev(kbbq_ctx* c, const uint8_t* d_seq, const uint32_t* d_le
     if (nreads < 0 || pitch <= 0 || (pitch & 15) || genome_len < 0) return fail(KBBQ_E_ARG, "kbbq_find_errors_dev: bad nreads/pitch/genome_len");
     if (nreads == 0) return KBBQ_OK;
     HIPCHK(hipSetDevice(c->device));
-    K4Params p;
-    p.seq = d_seq; p.len = d_len; p.nreads = nreads; p.pitch = pitch;
-    p.ref_start = (const long long*)d_ref_start; p.ref_len = d_ref_len;
-    p.cig_off = d_cig_off; p.cig_n = d_cig_n; p.cigar = d_cigar;
-    p.genome = d_genome; p.skipmask = d_skipmask; p.genome_len = genome_len; p.flip = d_flip; p.err = d_err; p.skip = d_skip;
-    p.status = c->d_status;
+    const K4Params p = k4_params(c, d_seq, d_len, nreads, pitch, d_ref_start, d_ref_len, d_cig_off, d_cig_n, d_cigar, d_genome, d_skipmask,
+                                 genome_len, d_flip, d_err, d_skip);
     if (((uintptr_t)d_seq | (uintptr_t)d_err | (uintptr_t)d_skip) & 15)
         return fail(KBBQ_E_ARG, "kbbq_find_errors_dev: planes must be 16-byte aligned");
     const int rpb4 = (pitch / 16) <= 256 ? 256 / (pitch / 16) : 1;              // reads per workgroup iteration
     const int gx = bounded_grid((nreads + rpb4 - 1) / rpb4, c, 64);
     int rc4 = k4_records(c, p, nullptr, nullptr, nullptr, nullptr, 0);
     if (rc4) return rc4;
-    K4v2Params q; q.base = p; q.recs = (const K4Rec*)c->d_ops4; q.idle16 = reinterpret_cast<const uint8_t*>(c->d_status);
+    K4v2Params q; q.base = p; q.recs = (const K4Rec*)c->ops4.p; q.idle16 = reinterpret_cast<const uint8_t*>(c->d_status);
     q.rows = nullptr; q.nrows = nullptr;
     if (d_skipmask) hipLaunchKernelGGL(k4v2_find_errors<false>, dim3((unsigned)std::max(gx, 1)), dim3(256), 0, c->stream, q);
     else hipLaunchKernelGGL(k4v2_find_errors<true>, dim3((unsigned)std::max(gx, 1)), dim3(256), 0, c->stream, q);
@@ -1694,7 +1679,8 @@ static int accumulate_aligned(kbbq_ctx* c, const uint8_t* d_seq, const uint8_t* 
     if (!d_seq || !d_oq || !d_flagplane || !d_clip || !d_trim || !d_flags || !d_tables) return fail(KBBQ_E_ARG, "kbbq_accumulate_aligned_dev: NULL pointer");
     if (S < 32) return fail(KBBQ_E_LUT, "kbbq_accumulate_aligned_dev: reads of %d bases (< 32) are tallied through kbbq_canonical_reads_rows_dev", S);
     HIPCHK(hipSetDevice(c->device));
-    K1v3Params q;
+    K1Setup su;
+    K1v3Params& q = su.q;
     memset(&q, 0, sizeof q);
     q.seq = d_seq; q.cseq = d_flagplane; q.qual = d_oq; q.meta = nullptr;
     q.aflags = d_flags; q.aclip = d_clip; q.atrim = d_trim;
@@ -1706,45 +1692,15 @@ static int accumulate_aligned(kbbq_ctx* c, const uint8_t* d_seq, const uint8_t* 
     q.maxlen = S; q.gap = 0; q.twins = 0; q.seg = nullptr;
     q.tables = reinterpret_cast<u64*>(d_tables); q.status = c->d_status;
     // LDS geometry as accumulate_rows: 3S words per cycle row (every read has length S: [0, S) read 1, [S, 2S) read 2 mirrored);
-    // 16 copies of the context table, or 8 when that does not fit
-    int dn = 0; size_t lds3 = 0;
-    for (int copies : {K1V3_DNREP, 8}) {
-        const int words = (3 * S) | 1;
-        // minlen = S: the flush walks columns [0, 2S) only -- the words behind them take the uncounted bytes in front of a read's
-        // first aligned base (kernel comment) and are never read
-        q.row_bytes = (u32)words * 4u; q.minlen = S; q.slack_bytes = (u32)(S + 32) * 4u;
-        q.dn_flush_iters = std::max(1, 65535 / ((K1V3_THREADS / copies) * 16 * q.cpr));
-        lds3 = (size_t)q.nrows * 128 * copies + (size_t)q.nrows * q.row_bytes + q.slack_bytes;
-        if (lds3 <= (size_t)c->lds_bytes && (K1V3_THREADS / copies) * 16 * q.cpr <= 65535) { dn = copies; break; }
-    }
-    if (!dn) return fail(KBBQ_E_LUT, "kbbq_accumulate_aligned_dev: %d-base reads with minscore %d do not fit the LDS tables; tally through kbbq_canonical_reads_rows_dev", S, minscore);
+    // 16 copies of the context table, or 8 when that does not fit.
+    // minlen = S: the flush walks columns [0, 2S) only -- the words behind them take the uncounted bytes in front of a read's
+    // first aligned base (kernel comment) and are never read
+    for (int copies : {K1V3_DNREP, 8})
+        if (k1_geometry(q, c, copies, 0, S)) { su.dn = copies; break; }
+    if (!su.dn) return fail(KBBQ_E_LUT, "kbbq_accumulate_aligned_dev: %d-base reads with minscore %d do not fit the LDS tables; tally through kbbq_canonical_reads_rows_dev", S, minscore);
     if (dry_run) return KBBQ_OK;                      // the caller only asked whether this shape is served
-    lds3 = k1_lds_plan(q, dn, c);                     // trash rows and copies of the cycle table, as accumulate_rows
-    const bool split = dinuc_minscore > minscore;
-    const int64_t nblocks = (nreads + 63) / 64;
-    const int64_t iters = (nblocks + (K1V3_THREADS / 64) - 1) / (K1V3_THREADS / 64);
-    const int gx = (int)std::min<int64_t>(iters, std::max(1, c->cus / R));
-    dim3 grid((unsigned)gx, (unsigned)R, 1), block(K1V3_THREADS, 1, 1);
-    {
-        Timed t(c, 0);
-        if (d_genome) {
-            if (dn == K1V3_DNREP) {
-                if (split) hipLaunchKernelGGL((k1v3_aligned_ref<true, K1V3_DNREP>), grid, block, lds3, c->stream, q);
-                else hipLaunchKernelGGL((k1v3_aligned_ref<false, K1V3_DNREP>), grid, block, lds3, c->stream, q);
-            } else {
-                if (split) hipLaunchKernelGGL((k1v3_aligned_ref<true, 8>), grid, block, lds3, c->stream, q);
-                else hipLaunchKernelGGL((k1v3_aligned_ref<false, 8>), grid, block, lds3, c->stream, q);
-            }
-        } else if (dn == K1V3_DNREP) {
-            if (split) hipLaunchKernelGGL((k1v3_aligned<true, K1V3_DNREP>), grid, block, lds3, c->stream, q);
-            else hipLaunchKernelGGL((k1v3_aligned<false, K1V3_DNREP>), grid, block, lds3, c->stream, q);
-        } else {
-            if (split) hipLaunchKernelGGL((k1v3_aligned<true, 8>), grid, block, lds3, c->stream, q);
-            else hipLaunchKernelGGL((k1v3_aligned<false, 8>), grid, block, lds3, c->stream, q);
-        }
-    }
-    HIPCHK(hipGetLastError());
-    return KBBQ_OK;
+    su.lds = k1_lds_plan(q, su.dn, c);                // trash rows and copies of the cycle table, as accumulate_rows
+    return launch_k1(c, d_genome ? K1_ALIGNED_REF : K1_ALIGNED, su, 0);
 }
 
 int kbbq_accumulate_aligned_dev(kbbq_ctx* c, const uint8_t* d_seq, const uint8_t* d_oq, const uint8_t* d_flagplane,
@@ -1785,29 +1741,21 @@ int kbbq_tally_aligned_dev(kbbq_ctx* c, const uint8_t* d_seq, const uint8_t* d_o
                                 d_tables, d_genome, d_ref_start, true);
     if (rc) return rc;
     HIPCHK(hipSetDevice(c->device));
-    const size_t need = 16 + 2 * (size_t)nreads * sizeof(u32);
-    if (c->tally_bytes < need) {
-        if (c->d_tally) { HIPCHK(hipStreamSynchronize(c->stream)); (void)hipFree(c->d_tally); c->d_tally = nullptr; c->tally_bytes = 0; }
-        HIPCHK(hipMalloc(&c->d_tally, need));
-        c->tally_bytes = need;
-    }
-    u32* count = reinterpret_cast<u32*>(c->d_tally);
+    rc = grow_scratch(c, c->tally, 16 + 2 * (size_t)nreads * sizeof(u32));
+    if (rc) return rc;
+    u32* count = reinterpret_cast<u32*>(c->tally.p);
     u32* aflags2 = count + 4;
     u32* rows = aflags2 + nreads;
     HIPCHK(hipMemsetAsync(count, 0, 16, c->stream));
-    K4Params p;
-    p.seq = d_seq; p.len = d_len; p.nreads = nreads; p.pitch = pitch;
-    p.ref_start = (const long long*)d_ref_start; p.ref_len = d_ref_len;
-    p.cig_off = d_cig_off; p.cig_n = d_cig_n; p.cigar = d_cigar;
-    p.genome = d_genome; p.skipmask = nullptr; p.genome_len = genome_len; p.flip = nullptr; p.err = d_flagplane; p.skip = nullptr;
-    p.status = c->d_status;
+    const K4Params p = k4_params(c, d_seq, d_len, nreads, pitch, d_ref_start, d_ref_len, d_cig_off, d_cig_n, d_cigar, d_genome, nullptr,
+                                 genome_len, nullptr, d_flagplane, nullptr);
     rc = k4_records(c, p, d_flags, aflags2, rows, count, pitch);
     if (rc) return rc;
     {   // K4 over the listed reads only: their number is on the device, the grid is sized for a share of the reads (a workgroup
         // beyond the list's end finds nothing to do)
         const int rpb4 = (pitch / 16) <= 256 ? 256 / (pitch / 16) : 1;
         const int gx = bounded_grid(((nreads + TALLY_K4_SHARE - 1) / TALLY_K4_SHARE + rpb4 - 1) / rpb4, c, 64);
-        K4v2Params q; q.base = p; q.recs = (const K4Rec*)c->d_ops4; q.idle16 = reinterpret_cast<const uint8_t*>(c->d_status);
+        K4v2Params q; q.base = p; q.recs = (const K4Rec*)c->ops4.p; q.idle16 = reinterpret_cast<const uint8_t*>(c->d_status);
         q.rows = rows; q.nrows = count;
         hipLaunchKernelGGL(k4v2_find_errors<true>, dim3((unsigned)std::max(gx, 1)), dim3(256), 0, c->stream, q);
         HIPCHK(hipGetLastError());
