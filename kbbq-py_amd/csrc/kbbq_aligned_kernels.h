@@ -37,6 +37,63 @@
 #pragma once
 #include "kbbq_kernels_v3.h"
 
+// ---------------------------------------------------------------- K4 / K5: benchmark path
+// (SURVEY.md 8(f) #1).  K4 restates compare_reads.find_read_errors (compare_reads.py:84-139):
+// a CIGAR walk that compares the read with the reference and marks sites to skip; K5 is the
+// two np.bincount calls of benchmark.calculate_q (benchmark.py:76-91) over the unskipped bases.
+struct K4Params {
+    const uint8_t* seq; const u32* len; long long nreads; int pitch;
+    const long long* ref_start;      // offset of reference_start in `genome` / `skipmask`
+    const int* ref_len;              // reference_end - reference_start (the read's reference window)
+    const u32* cig_off; const u32* cig_n; const u32* cigar;   // per read: first op, op count; ops = len << 4 | op
+    const uint8_t* genome; const uint8_t* skipmask; const uint8_t* flip;     // skipmask == NULL: bit 7 of a genome byte is its skip flag
+    long long genome_len;            // bytes in genome / skipmask
+    uint8_t* err; uint8_t* skip; u64* status;
+};
+
+// load16_any (kbbq_kernels_v3.h) for windows that may run past the end of the array (`limit` = its size in bytes): bytes past
+// the end read as zero.  Only the last chunk of the last rows / of the genome ever takes the byte path.
+__device__ __forceinline__ void load16_upto(const uint8_t* base, long long off, long long limit, u32 out[4])
+{
+    if (off + 16 <= limit) { load16_any(base, off, out); return; }
+    out[0] = out[1] = out[2] = out[3] = 0u;
+    for (int b = 0; b < 16 && off + b < limit; ++b) out[b >> 2] |= (u32)base[off + b] << (8 * (b & 3));
+}
+
+__device__ __forceinline__ void set_byte(u32 v[4], int i, u32 val)      // i in 0..15, slow paths only
+{
+    const u32 m = 0xFFu << (8 * (i & 3)), x = (val & 0xFFu) << (8 * (i & 3));
+    v[0] = (i >> 2) == 0 ? (v[0] & ~m) | x : v[0];
+    v[1] = (i >> 2) == 1 ? (v[1] & ~m) | x : v[1];
+    v[2] = (i >> 2) == 2 ? (v[2] & ~m) | x : v[2];
+    v[3] = (i >> 2) == 3 ? (v[3] & ~m) | x : v[3];
+}
+
+__device__ __forceinline__ u32 get_byte(const u32 v[4], int i)
+{
+    const u32 w = (i >> 2) == 0 ? v[0] : (i >> 2) == 1 ? v[1] : (i >> 2) == 2 ? v[2] : v[3];
+    return (w >> (8 * (i & 3))) & 0xFFu;
+}
+
+// 0xFF in the bytes of word w (of a 16-byte vector) whose position p = 4w + k lies in [lo, hi)
+__device__ __forceinline__ u32 range_mask(int lo, int hi, int w) { return byte_mask(hi, w) & ~byte_mask(lo, w); }
+
+__device__ __forceinline__ void shr_bytes16(u32 v[4], int nb)            // byte i <- byte i + nb (0 <= nb <= 15), zero fill
+{
+    const int ws = nb >> 2; const u32 bs = (u32)(nb & 3) * 8u;
+    const u32 a0 = ws == 0 ? v[0] : ws == 1 ? v[1] : ws == 2 ? v[2] : v[3];
+    const u32 a1 = ws == 0 ? v[1] : ws == 1 ? v[2] : ws == 2 ? v[3] : 0u;
+    const u32 a2 = ws == 0 ? v[2] : ws == 1 ? v[3] : 0u;
+    const u32 a3 = ws == 0 ? v[3] : 0u;
+    v[0] = __builtin_amdgcn_alignbit(a1, a0, bs); v[1] = __builtin_amdgcn_alignbit(a2, a1, bs);
+    v[2] = __builtin_amdgcn_alignbit(a3, a2, bs); v[3] = a3 >> bs;
+}
+
+// K4 itself is k4v2_find_errors (below): lane <-> one 16-byte OUTPUT chunk of one read.  For reverse-strand
+// reads the OUTPUT is reversed (benchmark.py:70-72): the lane's input positions are then [n-16j-16, n-16j) and its 16 result
+// bytes are byte-reversed.
+struct K4Item { long long rb; int j; };              // a thread's work item: first read of the workgroup's block, chunk of the row
+
 #define K4_INLINE_OPS 4
 #define K4_NOT_SIMPLE 0x7FFFFFFF
 
@@ -343,11 +400,7 @@ __global__ __launch_bounds__(256) void k4v2_find_errors(K4v2Params q)
         const int cnt = out_hi - out_lo, in_lo = f ? n - out_hi : out_lo;
         u32 sw[4], ev[4] = {0u, 0u, 0u, 0u}, kv[4] = {0u, 0u, 0u, 0u};
         load16_any(p.seq + (size_t)r * p.pitch, in_lo, sw);
-#ifndef K4_ABL_NOWALK
         k4_walk_chunk<FUSED>(p, r, n, rl, p.ref_start[r], p.cigar + p.cig_off[r], p.cig_n[r], sw, in_lo, cnt, ev, kv);
-#else
-        ev[0] = sw[0]; kv[0] = (u32)rl;
-#endif
         if (f) {                                                           // output byte i = input byte cnt-1-i
             reverse16(ev); reverse16(kv);
             shr_bytes16(ev, 16 - cnt); shr_bytes16(kv, 16 - cnt);
@@ -430,12 +483,10 @@ __global__ __launch_bounds__(256) void k4v2_find_errors(K4v2Params q)
                     }
                 } else {
                     // not here: queued for the dense pass below (or, queue full, walked at once)
-#ifndef K4_ABL_NOQUEUE
                     const u32 slot_q = atomicAdd(&queued, 1u);
                     if (slot_q < K4_QUEUE) queue[slot_q] = make_uint2((u32)r, (u32)((u64)r >> 32) | ((u32)j << 24));
                     else walk_and_store(r, j);
                     store = false;
-#endif
                 }
             }
             if (store) {
@@ -455,10 +506,263 @@ __global__ __launch_bounds__(256) void k4v2_find_errors(K4v2Params q)
     // the dense pass over the chunks that need the sequential walk
     __syncthreads();
     const u32 nq = queued < K4_QUEUE ? queued : K4_QUEUE;
-#ifndef K4_ABL_NOTAIL
     for (u32 i = threadIdx.x; i < nq; i += blockDim.x) {
         const uint2 e = queue[i];
         walk_and_store((long long)(((u64)(e.y & 0x00FFFFFFu) << 32) | e.x), (int)(e.y >> 24));
     }
-#endif
+}
+
+// ---------------------------------------------------------------- K6 (BAM-sourced tally)
+// gatk/bqsr.py:52-123 tallies aligned reads with strand-aware covariates: the cycle and the
+// dinucleotide context are those of the base in SEQUENCING orientation over the aligned part
+// (bqsr.py:23-50), and a base is skipped when K4 flagged its site, when its original quality is
+// below minscore, when it lies past the adaptor boundary (bqsr.py:158-206, host: a per-read
+// range) or when it is 'N' (bqsr.py:86-88).  K6 rewrites every read into that orientation --
+// aligned part only, reverse-strand reads reverse-complemented (unknown letters -> 'N', as
+// Dinucleotide.complement.get(x, 'N')), padded with uncounted bases to the common length S,
+// skipped bases given quality byte 0, errors expressed as cseq != seq -- and the result goes
+// through the SAME tally kernel as the FASTQ path (K1): canonical position = cycle, sidecar
+// `second` bit = is_read2 (column 2S-1-c), context from the canonical neighbours.
+// lane <-> one 16-byte OUTPUT chunk; input windows are unaligned (load16_any).
+struct K6Params {
+    const uint8_t* seq; const uint8_t* oq; const uint8_t* err; const uint8_t* skip;   // [nreads, pitch]
+    const u32* len;                  // query length (must be S: checked on the host)
+    const u32* clip;                 // query_alignment_start | query_alignment_end << 16
+    const u32* trim;                 // skipped range lo | hi << 16 (lo == hi: none)
+    const u32* flags;                // bit 0 reverse, bit 1 read 2, bits 16.. read group
+    long long nreads; int pitch; int S; u32 qlo; u32 dlo;
+    uint8_t* out_seq; uint8_t* out_cseq; uint8_t* out_qual; u32* out_meta;
+    u64* status;
+};
+
+__device__ __forceinline__ u32 complement4(u32 w)
+{
+    const u32 h = (w >> 1) & 0x07070707u;
+    const u32 expect = __builtin_amdgcn_perm(0x4E000000u, 0x47544341u, h);
+    const u32 comp = __builtin_amdgcn_perm(0x4E4E4E4Eu, 0x43414754u, h);       // A->T C->G T->A G->C, else N
+    const u32 bad = nonzero_bytes(expect ^ w) * 0xFFu;                          // not exactly A C G T N
+    return (comp & ~bad) | (0x4E4E4E4Eu & bad);
+}
+
+__device__ __forceinline__ bool is_acgt(u32 ch) { return ch == 'A' || ch == 'C' || ch == 'G' || ch == 'T'; }
+
+// Work items of a thread: (read block rb, chunk j) with j = j0, j0 + 256, ... inside a row and rb advancing by the
+// grid.  They are software-pipelined two deep -- the per-read fields of item i + 2 and the four 16-byte windows of
+// item i + 1 are in flight while item i is computed and stored -- because the chain  fields -> windows -> stores
+// is what a wave otherwise waits through once per item.
+struct K6Item { long long rb; int j; };
+struct K6Meta { u32 fl, clip, trim; bool valid; };
+struct K6Win { u32 s[4], q[4], e[4], k[4]; int cnt, i0; bool has; };
+
+// NIB: out_seq / out_cseq are 4-bit planes (pitch / 2 bytes per row, the layout of KBBQ_ROWS_NIBBLES): K6 writes 2 B/base
+// instead of 3 and K1 reads 2 instead of 3.  A corrected base differs from its base in the low code bit (an N of a
+// reverse-strand read that was another letter IS counted by cycle and quality: its corrected code is 5, which only K1's
+// comparison ever sees).  A letter outside ACGTN (only a forward-strand read can carry one into the output) cannot be
+// packed: ST_LUT, and the caller repeats the pass with character planes -- which is also where the reference's
+// TypeError is decided, so this form does not look for it.
+template <bool NIB>
+__global__ __launch_bounds__(256) void k6_canonical_reads(K6Params p)
+{
+    const int cpr = p.pitch >> 4;
+    const int rpb = cpr <= 256 ? 256 / cpr : 0;
+    const int slot = cpr <= 256 ? (int)threadIdx.x / cpr : 0;
+    const int j0 = (int)threadIdx.x - slot * cpr;
+    const long long step = rpb ? rpb : 1;
+    const long long gstep = (long long)gridDim.x * step;
+    const bool idle = (rpb && slot >= rpb) || j0 >= cpr;
+    const long long plane = p.nreads * (long long)p.pitch;
+    auto next = [&](K6Item it) { it.j += 256; if (it.j >= cpr) { it.j = j0; it.rb += gstep; } return it; };
+    auto live = [&](const K6Item& it) { return !idle && it.rb + slot < p.nreads; };
+    auto fetch_meta = [&](const K6Item& it, K6Meta& m) {
+        m.valid = live(it);
+        const long long r = m.valid ? it.rb + slot : 0;
+        m.fl = p.flags[r]; m.clip = p.clip[r]; m.trim = p.trim[r];
+    };
+    auto fetch_win = [&](const K6Item& it, const K6Meta& m, K6Win& w) {
+        w.has = false; w.cnt = 0; w.i0 = 0;
+        if (!m.valid) return;
+        const int qs = (int)(m.clip & 0xFFFFu), qe = (int)(m.clip >> 16);
+        const int L = qe - qs, c0 = 16 * it.j;
+        if (c0 >= L) return;
+        // input window [i0, i0 + 16): the chunk's bases in INPUT order occupy its first cnt bytes
+        // (a reverse-strand chunk is byte-reversed afterwards; a partial one then shifted down)
+        w.has = true;
+        w.cnt = L - c0 < 16 ? L - c0 : 16;
+        w.i0 = (m.fl & 1u) ? (w.cnt == 16 ? qe - c0 - 16 : qs) : qs + c0;
+        const long long at = (it.rb + slot) * (long long)p.pitch + w.i0;
+        load16_upto(p.seq, at, plane, w.s);
+        load16_upto(p.oq, at, plane, w.q);
+        load16_upto(p.err, at, plane, w.e);
+        if (p.skip) load16_upto(p.skip, at, plane, w.k);
+        else {                                                     // one plane of flags: bit 0 error, bit 1 skip
+#pragma unroll
+            for (int x = 0; x < 4; ++x) { w.k[x] = w.e[x] & 0x02020202u; w.e[x] &= 0x01010101u; }
+        }
+    };
+    K6Item it0{(long long)blockIdx.x * step, j0};
+    K6Item it1 = next(it0), it2 = next(it1);
+    K6Meta m0, m1, m2;
+    K6Win w0, w1;
+    fetch_meta(it0, m0); fetch_meta(it1, m1);
+    fetch_win(it0, m0, w0);
+    while (live(it0)) {
+        fetch_meta(it2, m2);
+        fetch_win(it1, m1, w1);
+        {
+            const long long r = it0.rb + slot;
+            const int j = it0.j;
+            const u32 fl = m0.fl;
+            const bool rev = (fl & 1u) != 0;
+            const int tlo = (int)(m0.trim & 0xFFFFu), thi = (int)(m0.trim >> 16);
+            const int c0 = 16 * j;
+            u32 os[4] = {0x4E4E4E4Eu, 0x4E4E4E4Eu, 0x4E4E4E4Eu, 0x4E4E4E4Eu};
+            u32 oc[4] = {0x4E4E4E4Eu, 0x4E4E4E4Eu, 0x4E4E4E4Eu, 0x4E4E4E4Eu};
+            u32 oqv[4] = {0u, 0u, 0u, 0u};
+            const size_t row = (size_t)r * p.pitch;
+            if (j == 0) p.out_meta[r] = (u32)p.S | ((fl >> 16) << 16) | ((fl & 2u) ? 0x80000000u : 0u);
+            if (w0.has) {
+                const int cnt = w0.cnt, i0 = w0.i0;
+                const u32 (&s)[4] = w0.s; const u32 (&q)[4] = w0.q; const u32 (&e)[4] = w0.e; const u32 (&k)[4] = w0.k;
+                bool odd = false;
+#pragma unroll
+                for (int w = 0; w < 4; ++w) {
+                    const u32 below = (~((q[w] | 0x80808080u) - p.qlo * 0x01010101u) >> 7) & 0x01010101u;   // q < minscore
+                    const u32 trimmed = range_mask(tlo - i0, thi - i0, w) & 0x01010101u;
+                    const u32 isn = nonzero_bytes(s[w] ^ 0x4E4E4E4Eu) ^ 0x01010101u;
+                    const u32 sk = (nonzero_bytes(k[w]) | below | trimmed | isn) * 0xFFu;
+                    u32 code, code5, expect;
+                    decode4x(s[w], code, code5, expect);
+                    odd |= ((expect ^ s[w]) & byte_mask(cnt, w)) != 0u;
+                    os[w] = rev ? complement4(s[w]) : s[w];
+                    oc[w] = os[w] ^ (nonzero_bytes(e[w]) << 7);                    // an error: cseq differs from seq
+                    oqv[w] = q[w] & ~sk;
+                }
+                if (NIB) {
+                    if (odd && !rev) flag(p.status, ST_LUT, r);
+                } else if (odd && !rev) {
+                    // the reference's TypeError (compare_reads.py:281-293 via bqsr.py:43-45) is decided on the
+                    // ORIGINAL qualities, before any skipping: a looked-up pair with a letter outside ACGT
+                    u32 prev = (c0 >= 1) ? p.seq[row + i0 - 1] : 'N';
+                    for (int b = 0; b < cnt; ++b) {
+                        const u32 cur = (s[b >> 2] >> (8 * (b & 3))) & 0xFFu, qq = (q[b >> 2] >> (8 * (b & 3))) & 0xFFu;
+                        if (c0 + b >= 1 && qq >= p.dlo && cur != 'N' && prev != 'N' && !(is_acgt(cur) && is_acgt(prev)))
+                            flag(p.status, ST_TYPE, r);
+                        prev = cur;
+                    }
+                }
+                if (rev) {
+                    reverse16(os); reverse16(oc); reverse16(oqv);
+                    if (cnt < 16) { shr_bytes16(os, 16 - cnt); shr_bytes16(oc, 16 - cnt); shr_bytes16(oqv, 16 - cnt); }
+                }
+                if (cnt < 16) {
+#pragma unroll
+                    for (int w = 0; w < 4; ++w) {                                  // past the aligned part: uncounted padding
+                        const u32 vm = byte_mask(cnt, w);
+                        os[w] = (os[w] & vm) | (0x4E4E4E4Eu & ~vm);
+                        oc[w] = (oc[w] & vm) | (0x4E4E4E4Eu & ~vm);
+                        oqv[w] &= vm;
+                    }
+                }
+            }
+            const size_t off = row + (size_t)16 * j;
+            if (NIB) {
+                u32 cs[4], cc[4], bad = 0u;
+#pragma unroll
+                for (int w = 0; w < 4; ++w) {
+                    cs[w] = chars_to_codes(os[w], bad);
+                    cc[w] = cs[w] ^ nonzero_bytes(os[w] ^ oc[w]);
+                }
+                const size_t noff = (row >> 1) + (size_t)8 * j;
+                *reinterpret_cast<uint2*>(p.out_seq + noff) = make_uint2(cs[0] | (cs[1] << 4), cs[2] | (cs[3] << 4));
+                *reinterpret_cast<uint2*>(p.out_cseq + noff) = make_uint2(cc[0] | (cc[1] << 4), cc[2] | (cc[3] << 4));
+            } else {
+                *reinterpret_cast<uint4*>(p.out_seq + off) = make_uint4(os[0], os[1], os[2], os[3]);
+                *reinterpret_cast<uint4*>(p.out_cseq + off) = make_uint4(oc[0], oc[1], oc[2], oc[3]);
+            }
+            *reinterpret_cast<uint4*>(p.out_qual + off) = make_uint4(oqv[0], oqv[1], oqv[2], oqv[3]);
+        }
+        it0 = it1; m0 = m1; w0 = w1;
+        it1 = it2; m1 = m2;
+        it2 = next(it2);
+    }
+}
+
+// ---------------------------------------------------------------- K5
+struct K5Params {
+    const uint8_t* qual; const uint8_t* err; const uint8_t* skip; const u32* len;
+    long long nreads; int pitch; int cpr; u32 cpr_magic; int qoffset;
+    u64* counts;                     // [0..255] totals, [256..511] errors
+    u64* status;
+};
+
+// lane <-> 16-byte chunk.  LDS: [257 bins][16 copies] u32, errs << 16 | total (copy = lane & 15: the 40-odd bins in
+// use are hot; copies cut the same-address collisions of a wave's atomic 16-fold), bin 256 = trash (skipped sites,
+// bytes past the read, values below the offset) so that every byte costs exactly one unconditional LDS atomic.
+// 16-bit halves: a copy receives at most 16 lanes x 16 bytes per workgroup iteration -> flushed every 255 iterations.
+#define K5_THREADS 256
+#define K5_COPIES 16
+#define K5_FLUSH_ITERS (65535 / ((K5_THREADS / K5_COPIES) * 16))
+__global__ __launch_bounds__(K5_THREADS) void k5_count_q(K5Params p)
+{
+    __shared__ u32 h[257 * K5_COPIES];
+    for (int i = threadIdx.x; i < 257 * K5_COPIES; i += blockDim.x) h[i] = 0u;
+    __syncthreads();
+    const long long nchunks = p.nreads * p.cpr;
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    const long long iters = (nchunks + stride - 1) / stride;                 // the same for every thread: barriers are safe
+    const u32 copy = threadIdx.x & (K5_COPIES - 1);
+    auto flush = [&]() {
+        __syncthreads();
+        for (int b = threadIdx.x; b < 256; b += blockDim.x) {
+            u32 t = 0u, e = 0u;
+            for (int c = 0; c < K5_COPIES; ++c) { const u32 v = h[b * K5_COPIES + c]; h[b * K5_COPIES + c] = 0u; t += v & 0xFFFFu; e += v >> 16; }
+            if (t) atomicAdd(&p.counts[b], (u64)t);
+            if (e) atomicAdd(&p.counts[256 + b], (u64)e);
+        }
+        __syncthreads();
+    };
+    int since = 0;
+    // the loads of the NEXT chunk are issued before the current one is binned (one step of software prefetch)
+    struct Chunk { uint4 q, e, s; long long r; int nb; };
+    auto fetch = [&](long long ch, Chunk& c) {
+        c.nb = 0; c.r = 0;
+        if (ch >= nchunks) return;
+        c.r = ch / p.cpr;
+        const int j = (int)(ch - c.r * p.cpr);
+        c.nb = (int)p.len[c.r] - 16 * j;
+        if (c.nb <= 0) return;
+        const size_t off = (size_t)c.r * p.pitch + (size_t)16 * j;
+        c.q = *reinterpret_cast<const uint4*>(p.qual + off);
+        c.e = *reinterpret_cast<const uint4*>(p.err + off);
+        if (p.skip) c.s = *reinterpret_cast<const uint4*>(p.skip + off);
+        else {                                                     // one plane of flags: bit 0 error, bit 1 skip
+            c.s = make_uint4(c.e.x & 0x02020202u, c.e.y & 0x02020202u, c.e.z & 0x02020202u, c.e.w & 0x02020202u);
+            c.e = make_uint4(c.e.x & 0x01010101u, c.e.y & 0x01010101u, c.e.z & 0x01010101u, c.e.w & 0x01010101u);
+        }
+    };
+    long long ch = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    Chunk cur, nxt;
+    fetch(ch, cur);
+    for (long long it = 0; it < iters; ++it, ch += stride) {
+        fetch(ch + stride, nxt);
+        if (cur.nb > 0) {
+            const int nb = cur.nb;
+            const u32 q[4] = {cur.q.x, cur.q.y, cur.q.z, cur.q.w}, e[4] = {cur.e.x, cur.e.y, cur.e.z, cur.e.w}, s[4] = {cur.s.x, cur.s.y, cur.s.z, cur.s.w};
+            bool negative = false;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                const int sh = 8 * (i & 3);
+                const int qq = (int)((q[i >> 2] >> sh) & 0xFFu) - p.qoffset;
+                const bool counted = i < nb && ((s[i >> 2] >> sh) & 0xFFu) == 0u;
+                negative |= counted && qq < 0;                               // np.bincount rejects negative values: ValueError
+                const u32 bin = (counted && qq >= 0) ? (u32)qq : 256u;
+                const u32 inc = ((e[i >> 2] >> sh) & 0xFFu) ? 0x10001u : 1u;
+                atomicAdd(&h[bin * K5_COPIES + copy], inc);
+            }
+            if (negative) flag(p.status, ST_RANGE, cur.r);
+        }
+        cur = nxt;
+        if (++since == K5_FLUSH_ITERS) { flush(); since = 0; }
+    }
+    flush();
 }

@@ -5,10 +5,11 @@
 // fill_row_lut / k4_params fill the parameter structs, grow_scratch grows the context's device scratch.
 #include "kbbq_kernels.h"
 #include "kbbq_kernels_v3.h"
-#include "kbbq_solve_kernels.h"
-#include "kbbq_layout_kernels.h"
-#include "kbbq_aligned_kernels.h"
 #include "kbbq_k2_tile.h"
+#include "kbbq_solve_kernels.h"
+#include "kbbq_lut_kernels.h"
+#include "kbbq_aligned_kernels.h"
+#include "kbbq_layout_kernels.h"
 #include "kbbq_apply_aligned.h"
 #include "kbbq_kmer.h"
 #include "../../include/kbbq_hip.h"

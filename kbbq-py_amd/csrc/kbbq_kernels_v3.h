@@ -24,15 +24,9 @@
 
 #define K1V3_THREADS 1024        // one workgroup per CU: the replicated context table needs ~150 KB of LDS
 #define K1V3_DNREP 16            // copies of the context-count table (copy = lane & (DN - 1)); long reads use 8 to fit the LDS
-#ifndef K2V3_THREADS
 #define K2V3_THREADS 512
-#endif
-#ifndef K2V3_NBUF
 #define K2V3_NBUF 2             // chunk buffers in the prefetch ring
-#endif
-#ifndef K2V3_WAVES
 #define K2V3_WAVES 4            // waves per SIMD the register allocation aims at
-#endif
 #define K1V3_FLUSH_ITERS 48          // 48 * 16 waves * 64 reads = 49,152 reads per workgroup between flushes (< 65,535)
 
 struct K1v3Params {
@@ -182,6 +176,10 @@ struct K1Chunk { u32 s[4], c[4], q[4]; u32 mk; u32 off; int k; int j; int nb; u3
 // [qs, qe), inside the trimmed range, where K4 set the skip flag or where it is N (bqsr.py:86-88); bases outside the
 // aligned part are no context either (code 4).  The error flag is K4's bit 0.  A forward read with a letter outside ACGTN
 // is reported (ST_LUT): the caller repeats the tally through K6's character planes, where the reference's TypeError is decided.
+// (The stages below -- the two flushes, the compaction, fetch, the decoders, the binning loop -- are lambdas over the body's
+//  locals and stay so for now: written as __forceinline__ functions over explicit state, even the two flushes alone, every one
+//  of the 24 instances came out with other instructions and other register counts (profiles/r06_kernel_headers.md section 4).
+//  Cutting them out is a change to measure on the device, not one to make under "identical device code".)
 template <bool SPLIT, int DN, bool NIB, int KJ, bool ALN = false, bool REF = false>
 __device__ __forceinline__ void k1v3_body(const K1v3Params& p, u32* lds, const int bx, const int gx, const int g)
 {
@@ -358,11 +356,7 @@ __device__ __forceinline__ void k1v3_body(const K1v3Params& p, u32* lds, const i
                     if constexpr (REF) { ch.g0lo = bperm(ag0lo, k); ch.g0hi = bperm(ag0hi, k); }
                 }
                 // lanes without work re-read the block's first chunk (valid memory, result unused)
-#ifndef KBBQ_ABL_NOLOAD
                 const u32 rowoff = ch.nb > 0 ? __umul24(ch.off, (u32)p.pitch) + (u32)(16 * ch.jj) : 0u;
-#else
-                const u32 rowoff = (u32)lane * 16u;      // timing only: every step re-reads the same cached KiB
-#endif
                 if constexpr (NIB) {
                     const uint2 sv = *reinterpret_cast<const uint2*>(bseq + (rowoff >> 1));
                     const uint2 cv = *reinterpret_cast<const uint2*>(bcseq + (rowoff >> 1));
@@ -383,16 +377,7 @@ __device__ __forceinline__ void k1v3_body(const K1v3Params& p, u32* lds, const i
                     ch.s[0] = sv.x; ch.s[1] = sv.y; ch.s[2] = sv.z; ch.s[3] = sv.w;
                     ch.c[0] = cv.x; ch.c[1] = cv.y; ch.c[2] = cv.z; ch.c[3] = cv.w;
                 }
-#ifdef KBBQ_Q6_PROBE
-                uint4 qv;                                            // TIMING ONLY (wrong results): see kbbq_k2_tile.h
-                {
-                    const uint3 q3 = *reinterpret_cast<const uint3*>(bqual + ((rowoff >> 2) * 3u));
-                    qv.x = (q3.x & 0x1F1F1F1Fu) + 0x27272727u; qv.y = (q3.y & 0x1F1F1F1Fu) + 0x27272727u; qv.z = (q3.z & 0x1F1F1F1Fu) + 0x27272727u;
-                    qv.w = (((q3.x >> 6) & 0x03030303u) | ((q3.y >> 4) & 0x0C0C0C0Cu) | ((q3.z >> 2) & 0x10101010u)) + 0x27272727u;
-                }
-#else
                 const uint4 qv = *reinterpret_cast<const uint4*>(bqual + rowoff);
-#endif
                 ch.q[0] = qv.x; ch.q[1] = qv.y; ch.q[2] = qv.z; ch.q[3] = qv.w;
             };
             auto process = [&](const K1Chunk& ch) {
@@ -522,11 +507,7 @@ __device__ __forceinline__ void k1v3_body(const K1v3Params& p, u32* lds, const i
                                 constexpr int b = decltype(bsel)::value;
                                 const u32 qi = (qn >> (8 * b)) & 0xFFu;                 // 255 - quality byte
                                 const u32 tq = qi < tcl ? qi : tcl;                    // below minscore (and padding): a trash row
-#ifndef KBBQ_K1_PLAIN_INC
                                 const u32 inc = k1_increment<b>(xwd, zero, both);      // recalibrate.py:13-20: errs << 16 | total
-#else
-                                const u32 inc = ((xwd >> (8 * b)) & 0xFFu) != 0u ? 0x10001u : 1u;
-#endif
                                 u32 a;
                                 if constexpr (ALN) {
                                     const int co = colA + 4 * (4 * wd + b);
@@ -534,21 +515,13 @@ __device__ __forceinline__ void k1v3_body(const K1v3Params& p, u32* lds, const i
                                 } else {
                                     a = __umul24(tq, row_bytes) + A + (u32)(KJ > 0 ? 4 * KJ * (4 * wd + b) : 4 * (4 * wd + b));
                                 }
-#ifndef KBBQ_ABL_NOPOS
                                 atomicAdd(reinterpret_cast<u32*>(reinterpret_cast<char*>(lds) + a), inc);   // recalibrate.py:116-117
-#else
-                                asm volatile("" :: "v"(a), "v"(inc));
-#endif
                                 u32 slot = (d5 >> (8 * b)) & 0xFFu;
                                 if (SPLIT) slot = qi <= 255u - p.dlo ? slot : 24u;             // context needs q >= its own threshold
                                 const u32 trow = tq * dnt_row + dnt_base;                      // constant powers of two: two shift-adds,
                                 const u32 ad = slot * (4u * DN) + trow;                // the LDS base is inside dnt_base
-#ifndef KBBQ_ABL_NODN
                                 __hip_atomic_fetch_add(reinterpret_cast<lds_u32*>(ad), inc, __ATOMIC_RELAXED,
                                                        __HIP_MEMORY_SCOPE_WORKGROUP);          // recalibrate.py:118-119
-#else
-                                asm volatile("" :: "v"(ad), "v"(inc));
-#endif
                             };
                             one_base(std::integral_constant<int, 0>{}); one_base(std::integral_constant<int, 1>{});
                             one_base(std::integral_constant<int, 2>{}); one_base(std::integral_constant<int, 3>{});
@@ -658,6 +631,22 @@ __host__ __device__ __forceinline__ int full_lut_row_bytes(int S2)
     return rb;
 }
 
+// ---------------------------------------------------------------- mate-pair rows
+// Optional device layout for paired reads of one length S (2 x 150 bp): ONE row per pair,
+//     [mate 1: S bytes][separator][mate 2: S bytes][padding to a multiple of 16]
+// separator and padding are 'N' (seq, cseq) / 0 (qual), i.e. uncounted bases.  2S + 1 = 301 -> pitch 304
+// instead of 2 x 160: 5 % fewer bytes through HBM for the same bases, and K1 / K2 run unchanged on the
+// rows as if they were single reads: byte offset b IS the stored cycle index (K1's table keeps
+// second-in-pair cycles mirrored from S upwards, here from S + 1; K2's pair LUT likewise), and the 'N'
+// separator gives mate 2's first base "no previous base" exactly like position 0 of a read.
+__host__ __device__ __forceinline__ int pair_pitch(int S2) { return (S2 + 1 + 15) & ~15; }
+__host__ __device__ __forceinline__ int pair_lut_row_bytes(int S2)
+{
+    int rb = pair_pitch(S2) + 32;
+    if (((rb >> 2) & 1) == 0) rb += 4;        // odd number of dwords per row
+    return rb;
+}
+
 struct K2Chunk { u32 s[4], q[4]; u32 mk; u32 dlo, dhi; int kk; int k; int j; int nb; bool act0; };
 
 struct K2v3Params {
@@ -737,11 +726,7 @@ __global__ __launch_bounds__(K2V3_THREADS) __attribute__((amdgpu_waves_per_eu(K2
             ch.mk = bperm(m, ch.k);
             if (p.perm) { ch.dlo = bperm((u32)pm, ch.k); ch.dhi = bperm((u32)(pm >> 32), ch.k); }
             ch.nb = ch.act0 ? ((int)(ch.mk & 0xFFFFu) - 16 * ch.j) : 0;
-#ifndef KBBQ_ABL_NOLOAD
             const u32 rowoff = ch.nb > 0 ? __umul24((u32)ch.k, (u32)p.pitch) + (u32)(16 * ch.j) : 0u;
-#else
-            const u32 rowoff = (u32)lane * 16u;
-#endif
             if constexpr (NIB) {
                 const uint2 sv = *reinterpret_cast<const uint2*>(bseq + (rowoff >> 1));
                 ch.s[0] = sv.x; ch.s[1] = sv.y;
@@ -786,13 +771,6 @@ __global__ __launch_bounds__(K2V3_THREADS) __attribute__((amdgpu_waves_per_eu(K2
                 carry_char = (u32)__builtin_amdgcn_readlane((int)last_char, 63);
             }
             if (j == 0) { prev_code5 = 20u; prev_char = 0u; }
-#ifdef KBBQ_ABL_COPY
-            if (ch.act0) {      // timing-only build: the kernel's memory traffic with (almost) no work
-                *reinterpret_cast<uint4*>(bout + (__umul24((u32)k, (u32)p.pitch) + (u32)pos0)) =
-                    make_uint4(ch.q[0] ^ ch.s[0], ch.q[1] ^ ch.s[1], ch.q[2] ^ ch.s[NIB ? 0 : 2], ch.q[3] ^ ch.s[NIB ? 1 : 3]);
-                return;
-            }
-#endif
             if (ch.act0) {
                 u32 o[4] = {0u, 0u, 0u, 0u};
                 if (act) {
@@ -832,12 +810,8 @@ __global__ __launch_bounds__(K2V3_THREADS) __attribute__((amdgpu_waves_per_eu(K2
                                 const u32 qb = (ch.q[wd] >> (8 * b)) & 0xFFu;
                                 const u32 rowq = __umul24(qb, rb);
                                 const u32 dd = (d5[wd] >> (8 * b)) & 0xFFu;
-#ifndef KBBQ_ABL_NOLUT
                                 v1[b] = *reinterpret_cast<const int8_t*>(reinterpret_cast<const char*>(lds) + (rowq + A + (u32)(4 * wd + b)));
                                 v2[b] = *reinterpret_cast<const int8_t*>(reinterpret_cast<const char*>(lds) + (rowq + C + dd));
-#else
-                                v1[b] = (int)(rowq + A); v2[b] = (int)(C + dd);
-#endif
                             }
                             // FAST mode is only legal for range-safe LUTs (flags == 0): every sum is 0..255
 #pragma unroll
@@ -874,526 +848,4 @@ __global__ __launch_bounds__(K2V3_THREADS) __attribute__((amdgpu_waves_per_eu(K2
             }
         }
     }
-}
-
-// Builds the full int8 LUT from the canonical int16 LUT and reports whether it is usable:
-// flags[0] |= 1 when some value does not fit int8, flags[0] |= 2 when some (cycle, context)
-// combination of a row could leave 0..255 (then the checked kernel must be used).
-struct LutFillParams {
-    const int16_t* lut16; int rs16; int R; int Qt; int S2; int minscore;
-    int8_t* full; int8_t* compact8; int* flags; u64* status;
-};
-
-// one workgroup per row (read group, raw quality byte): the row of the full LUT, and for a model row also
-// its int8 copy of the canonical row and its range check (block-wide min / max)
-__global__ __launch_bounds__(256) void k3_fill_full_lut(LutFillParams p)
-{
-    __shared__ int red[4][4];
-    const int rb = full_lut_row_bytes(p.S2);
-    const int NR = 33 + p.Qt;
-    const int row = blockIdx.x;                       // r * NR + qb
-    const int r = row / NR, qb = row - r * NR;
-    const int W = full_lut_width(p.S2);
-    const bool model = qb >= 33 + p.minscore;
-    const int16_t* src = p.lut16 + ((size_t)r * p.Qt + (qb >= 33 ? qb - 33 : 0)) * p.rs16;
-    int bad = 0;
-    int8_t* dst = p.full + (size_t)row * rb;
-    for (int x = threadIdx.x; x < rb; x += blockDim.x) {
-        int v = 0;
-        if (!model) {
-            if (x < 2 * W) v = qb == 0 ? -33 : qb - 33;                   // padding -> 0 ; uncounted -> unchanged
-        } else {
-            if (x < p.S2) v = src[x];
-            else if (x >= W && x < W + p.S2) v = src[p.S2 - 1 - (x - W)];   // mirrored copy for second-in-pair
-            else if (x >= 2 * W && x < 2 * W + 25) v = src[p.S2 + (x - 2 * W)];
-        }
-        if (v < -128 || v > 127) bad |= 1;
-        dst[x] = (int8_t)v;
-    }
-    if (qb >= 33) {
-        // int8 copy of the canonical row (same row stride, one byte per entry)
-        int8_t* c8 = p.compact8 + ((size_t)r * p.Qt + (qb - 33)) * p.rs16;
-        for (int x = threadIdx.x; x < p.rs16; x += blockDim.x) {
-            const int v = src[x];
-            if (v < -128 || v > 127) bad |= 1;
-            c8[x] = (int8_t)v;
-        }
-    }
-    if (model) {
-        // range safety of the row: min/max over cycles + min/max over contexts must stay in 0..255 after +33
-        int lo1 = 32767, hi1 = -32768, lo2 = 32767, hi2 = -32768;
-        for (int x = threadIdx.x; x < p.S2; x += blockDim.x) { const int v = src[x]; lo1 = v < lo1 ? v : lo1; hi1 = v > hi1 ? v : hi1; }
-        for (int x = threadIdx.x; x < 25; x += blockDim.x) { const int v = src[p.S2 + x]; lo2 = v < lo2 ? v : lo2; hi2 = v > hi2 ? v : hi2; }
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            int o;
-            o = __shfl_xor(lo1, off); lo1 = o < lo1 ? o : lo1;
-            o = __shfl_xor(hi1, off); hi1 = o > hi1 ? o : hi1;
-            o = __shfl_xor(lo2, off); lo2 = o < lo2 ? o : lo2;
-            o = __shfl_xor(hi2, off); hi2 = o > hi2 ? o : hi2;
-        }
-        const int w = threadIdx.x >> 6;
-        if ((threadIdx.x & 63) == 0) { red[w][0] = lo1; red[w][1] = hi1; red[w][2] = lo2; red[w][3] = hi2; }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            for (int k = 1; k < (int)(blockDim.x >> 6); ++k) {
-                lo1 = red[k][0] < lo1 ? red[k][0] : lo1; hi1 = red[k][1] > hi1 ? red[k][1] : hi1;
-                lo2 = red[k][2] < lo2 ? red[k][2] : lo2; hi2 = red[k][3] > hi2 ? red[k][3] : hi2;
-            }
-            if (lo1 + lo2 + 33 < 0 || hi1 + hi2 + 33 > 255) bad |= 2;
-        }
-    }
-    if (bad) { atomicOr(p.flags, bad); atomicMin(&p.status[ST_LUT], 0ull); }
-}
-
-// The full LUT narrowed to the cycle columns rows of one pitch can reach (K2 on one-read-per-row planes): a read in a
-// row of `pitch` bytes has at most Sb = min(pitch, S2) bases, so of a model row's S2 cycle entries only [0, Sb) (first
-// in pair) and [S2 - Sb, S2) (second in pair: column S2 - 1 - pos) are ever indexed.  Same geometry as the full LUT with
-// Sb in place of S2 (full_lut_width / full_lut_row_bytes): W = Sb + 16, [0, W) forward, [W, 2W) mirrored, 25 contexts at
-// 2W.  A length band of a mixed-length input (tables of 600 columns, rows of 48 bytes) stages 12 KB instead of 96 KB:
-// the LDS then holds several workgroups per CU again, and the short-lived K2 (kbbq_k2_tile.h) can afford the staging.
-struct RowLutParams { const int16_t* lut16; int rs16; int R; int Qt; int S2; int Sb; int minscore; int8_t* out; };
-
-__global__ __launch_bounds__(256) void k3_fill_row_lut(RowLutParams p)
-{
-    const int rb = full_lut_row_bytes(p.Sb), W = full_lut_width(p.Sb);
-    const int NR = 33 + p.Qt;
-    const int row = blockIdx.x;                       // r * NR + qb
-    const int r = row / NR, qb = row - r * NR;
-    const bool model = qb >= 33 + p.minscore;
-    const int16_t* src = p.lut16 + ((size_t)r * p.Qt + (qb >= 33 ? qb - 33 : 0)) * p.rs16;
-    int8_t* dst = p.out + (size_t)row * rb;
-    for (int x = threadIdx.x; x < rb; x += blockDim.x) {
-        int v = 0;
-        if (!model) {
-            if (x < 2 * W) v = qb == 0 ? -33 : qb - 33;                   // padding -> 0 ; uncounted -> unchanged
-        } else {
-            if (x < p.Sb) v = src[x];
-            else if (x >= W && x < W + p.Sb) v = src[p.S2 - 1 - (x - W)];   // second in pair: column S2 - 1 - pos
-            else if (x >= 2 * W && x < 2 * W + 25) v = src[p.S2 + (x - 2 * W)];
-        }
-        dst[x] = (int8_t)v;                            // the blob's flags said every value fits (FAST mode only)
-    }
-}
-
-// ---------------------------------------------------------------- K4 / K5: benchmark path
-// (SURVEY.md 8(f) #1).  K4 restates compare_reads.find_read_errors (compare_reads.py:84-139):
-// a CIGAR walk that compares the read with the reference and marks sites to skip; K5 is the
-// two np.bincount calls of benchmark.calculate_q (benchmark.py:76-91) over the unskipped bases.
-struct K4Params {
-    const uint8_t* seq; const u32* len; long long nreads; int pitch;
-    const long long* ref_start;      // offset of reference_start in `genome` / `skipmask`
-    const int* ref_len;              // reference_end - reference_start (the read's reference window)
-    const u32* cig_off; const u32* cig_n; const u32* cigar;   // per read: first op, op count; ops = len << 4 | op
-    const uint8_t* genome; const uint8_t* skipmask; const uint8_t* flip;     // skipmask == NULL: bit 7 of a genome byte is its skip flag
-    long long genome_len;            // bytes in genome / skipmask
-    uint8_t* err; uint8_t* skip; u64* status;
-};
-
-// the same, for windows that may run past the end of the array (`limit` = its size in bytes): bytes past
-// the end read as zero.  Only the last chunk of the last rows / of the genome ever takes the byte path.
-__device__ __forceinline__ void load16_upto(const uint8_t* base, long long off, long long limit, u32 out[4])
-{
-    if (off + 16 <= limit) { load16_any(base, off, out); return; }
-    out[0] = out[1] = out[2] = out[3] = 0u;
-    for (int b = 0; b < 16 && off + b < limit; ++b) out[b >> 2] |= (u32)base[off + b] << (8 * (b & 3));
-}
-
-
-__device__ __forceinline__ void set_byte(u32 v[4], int i, u32 val)      // i in 0..15, slow paths only
-{
-    const u32 m = 0xFFu << (8 * (i & 3)), x = (val & 0xFFu) << (8 * (i & 3));
-    v[0] = (i >> 2) == 0 ? (v[0] & ~m) | x : v[0];
-    v[1] = (i >> 2) == 1 ? (v[1] & ~m) | x : v[1];
-    v[2] = (i >> 2) == 2 ? (v[2] & ~m) | x : v[2];
-    v[3] = (i >> 2) == 3 ? (v[3] & ~m) | x : v[3];
-}
-
-__device__ __forceinline__ u32 get_byte(const u32 v[4], int i)
-{
-    const u32 w = (i >> 2) == 0 ? v[0] : (i >> 2) == 1 ? v[1] : (i >> 2) == 2 ? v[2] : v[3];
-    return (w >> (8 * (i & 3))) & 0xFFu;
-}
-
-// 0xFF in the bytes of word w (of a 16-byte vector) whose position p = 4w + k lies in [lo, hi)
-__device__ __forceinline__ u32 range_mask(int lo, int hi, int w) { return byte_mask(hi, w) & ~byte_mask(lo, w); }
-
-
-__device__ __forceinline__ void shr_bytes16(u32 v[4], int nb)            // byte i <- byte i + nb (0 <= nb <= 15), zero fill
-{
-    const int ws = nb >> 2; const u32 bs = (u32)(nb & 3) * 8u;
-    const u32 a0 = ws == 0 ? v[0] : ws == 1 ? v[1] : ws == 2 ? v[2] : v[3];
-    const u32 a1 = ws == 0 ? v[1] : ws == 1 ? v[2] : ws == 2 ? v[3] : 0u;
-    const u32 a2 = ws == 0 ? v[2] : ws == 1 ? v[3] : 0u;
-    const u32 a3 = ws == 0 ? v[3] : 0u;
-    v[0] = __builtin_amdgcn_alignbit(a1, a0, bs); v[1] = __builtin_amdgcn_alignbit(a2, a1, bs);
-    v[2] = __builtin_amdgcn_alignbit(a3, a2, bs); v[3] = a3 >> bs;
-}
-
-// K4 itself is k4v2_find_errors (kbbq_aligned_kernels.h): lane <-> one 16-byte OUTPUT chunk of one read.  For reverse-strand
-// reads the OUTPUT is reversed (benchmark.py:70-72): the lane's input positions are then [n-16j-16, n-16j) and its 16 result
-// bytes are byte-reversed.
-struct K4Item { long long rb; int j; };              // a thread's work item: first read of the workgroup's block, chunk of the row
-
-// ---------------------------------------------------------------- K6 (BAM-sourced tally)
-// gatk/bqsr.py:52-123 tallies aligned reads with strand-aware covariates: the cycle and the
-// dinucleotide context are those of the base in SEQUENCING orientation over the aligned part
-// (bqsr.py:23-50), and a base is skipped when K4 flagged its site, when its original quality is
-// below minscore, when it lies past the adaptor boundary (bqsr.py:158-206, host: a per-read
-// range) or when it is 'N' (bqsr.py:86-88).  K6 rewrites every read into that orientation --
-// aligned part only, reverse-strand reads reverse-complemented (unknown letters -> 'N', as
-// Dinucleotide.complement.get(x, 'N')), padded with uncounted bases to the common length S,
-// skipped bases given quality byte 0, errors expressed as cseq != seq -- and the result goes
-// through the SAME tally kernel as the FASTQ path (K1): canonical position = cycle, sidecar
-// `second` bit = is_read2 (column 2S-1-c), context from the canonical neighbours.
-// lane <-> one 16-byte OUTPUT chunk; input windows are unaligned (load16_any).
-struct K6Params {
-    const uint8_t* seq; const uint8_t* oq; const uint8_t* err; const uint8_t* skip;   // [nreads, pitch]
-    const u32* len;                  // query length (must be S: checked on the host)
-    const u32* clip;                 // query_alignment_start | query_alignment_end << 16
-    const u32* trim;                 // skipped range lo | hi << 16 (lo == hi: none)
-    const u32* flags;                // bit 0 reverse, bit 1 read 2, bits 16.. read group
-    long long nreads; int pitch; int S; u32 qlo; u32 dlo;
-    uint8_t* out_seq; uint8_t* out_cseq; uint8_t* out_qual; u32* out_meta;
-    u64* status;
-};
-
-__device__ __forceinline__ u32 complement4(u32 w)
-{
-    const u32 h = (w >> 1) & 0x07070707u;
-    const u32 expect = __builtin_amdgcn_perm(0x4E000000u, 0x47544341u, h);
-    const u32 comp = __builtin_amdgcn_perm(0x4E4E4E4Eu, 0x43414754u, h);       // A->T C->G T->A G->C, else N
-    const u32 bad = nonzero_bytes(expect ^ w) * 0xFFu;                          // not exactly A C G T N
-    return (comp & ~bad) | (0x4E4E4E4Eu & bad);
-}
-
-__device__ __forceinline__ bool is_acgt(u32 ch) { return ch == 'A' || ch == 'C' || ch == 'G' || ch == 'T'; }
-
-// Work items of a thread: (read block rb, chunk j) with j = j0, j0 + 256, ... inside a row and rb advancing by the
-// grid.  They are software-pipelined two deep -- the per-read fields of item i + 2 and the four 16-byte windows of
-// item i + 1 are in flight while item i is computed and stored -- because the chain  fields -> windows -> stores
-// is what a wave otherwise waits through once per item.
-struct K6Item { long long rb; int j; };
-struct K6Meta { u32 fl, clip, trim; bool valid; };
-struct K6Win { u32 s[4], q[4], e[4], k[4]; int cnt, i0; bool has; };
-
-// NIB: out_seq / out_cseq are 4-bit planes (pitch / 2 bytes per row, the layout of KBBQ_ROWS_NIBBLES): K6 writes 2 B/base
-// instead of 3 and K1 reads 2 instead of 3.  A corrected base differs from its base in the low code bit (an N of a
-// reverse-strand read that was another letter IS counted by cycle and quality: its corrected code is 5, which only K1's
-// comparison ever sees).  A letter outside ACGTN (only a forward-strand read can carry one into the output) cannot be
-// packed: ST_LUT, and the caller repeats the pass with character planes -- which is also where the reference's
-// TypeError is decided, so this form does not look for it.
-template <bool NIB>
-__global__ __launch_bounds__(256) void k6_canonical_reads(K6Params p)
-{
-    const int cpr = p.pitch >> 4;
-    const int rpb = cpr <= 256 ? 256 / cpr : 0;
-    const int slot = cpr <= 256 ? (int)threadIdx.x / cpr : 0;
-    const int j0 = (int)threadIdx.x - slot * cpr;
-    const long long step = rpb ? rpb : 1;
-    const long long gstep = (long long)gridDim.x * step;
-    const bool idle = (rpb && slot >= rpb) || j0 >= cpr;
-    const long long plane = p.nreads * (long long)p.pitch;
-    auto next = [&](K6Item it) { it.j += 256; if (it.j >= cpr) { it.j = j0; it.rb += gstep; } return it; };
-    auto live = [&](const K6Item& it) { return !idle && it.rb + slot < p.nreads; };
-    auto fetch_meta = [&](const K6Item& it, K6Meta& m) {
-        m.valid = live(it);
-        const long long r = m.valid ? it.rb + slot : 0;
-        m.fl = p.flags[r]; m.clip = p.clip[r]; m.trim = p.trim[r];
-    };
-    auto fetch_win = [&](const K6Item& it, const K6Meta& m, K6Win& w) {
-        w.has = false; w.cnt = 0; w.i0 = 0;
-        if (!m.valid) return;
-        const int qs = (int)(m.clip & 0xFFFFu), qe = (int)(m.clip >> 16);
-        const int L = qe - qs, c0 = 16 * it.j;
-        if (c0 >= L) return;
-        // input window [i0, i0 + 16): the chunk's bases in INPUT order occupy its first cnt bytes
-        // (a reverse-strand chunk is byte-reversed afterwards; a partial one then shifted down)
-        w.has = true;
-        w.cnt = L - c0 < 16 ? L - c0 : 16;
-        w.i0 = (m.fl & 1u) ? (w.cnt == 16 ? qe - c0 - 16 : qs) : qs + c0;
-        const long long at = (it.rb + slot) * (long long)p.pitch + w.i0;
-        load16_upto(p.seq, at, plane, w.s);
-        load16_upto(p.oq, at, plane, w.q);
-        load16_upto(p.err, at, plane, w.e);
-        if (p.skip) load16_upto(p.skip, at, plane, w.k);
-        else {                                                     // one plane of flags: bit 0 error, bit 1 skip
-#pragma unroll
-            for (int x = 0; x < 4; ++x) { w.k[x] = w.e[x] & 0x02020202u; w.e[x] &= 0x01010101u; }
-        }
-    };
-    K6Item it0{(long long)blockIdx.x * step, j0};
-    K6Item it1 = next(it0), it2 = next(it1);
-    K6Meta m0, m1, m2;
-    K6Win w0, w1;
-    fetch_meta(it0, m0); fetch_meta(it1, m1);
-    fetch_win(it0, m0, w0);
-    while (live(it0)) {
-        fetch_meta(it2, m2);
-        fetch_win(it1, m1, w1);
-        {
-            const long long r = it0.rb + slot;
-            const int j = it0.j;
-            const u32 fl = m0.fl;
-            const bool rev = (fl & 1u) != 0;
-            const int tlo = (int)(m0.trim & 0xFFFFu), thi = (int)(m0.trim >> 16);
-            const int c0 = 16 * j;
-            u32 os[4] = {0x4E4E4E4Eu, 0x4E4E4E4Eu, 0x4E4E4E4Eu, 0x4E4E4E4Eu};
-            u32 oc[4] = {0x4E4E4E4Eu, 0x4E4E4E4Eu, 0x4E4E4E4Eu, 0x4E4E4E4Eu};
-            u32 oqv[4] = {0u, 0u, 0u, 0u};
-            const size_t row = (size_t)r * p.pitch;
-            if (j == 0) p.out_meta[r] = (u32)p.S | ((fl >> 16) << 16) | ((fl & 2u) ? 0x80000000u : 0u);
-            if (w0.has) {
-                const int cnt = w0.cnt, i0 = w0.i0;
-                const u32 (&s)[4] = w0.s; const u32 (&q)[4] = w0.q; const u32 (&e)[4] = w0.e; const u32 (&k)[4] = w0.k;
-                bool odd = false;
-#pragma unroll
-                for (int w = 0; w < 4; ++w) {
-                    const u32 below = (~((q[w] | 0x80808080u) - p.qlo * 0x01010101u) >> 7) & 0x01010101u;   // q < minscore
-                    const u32 trimmed = range_mask(tlo - i0, thi - i0, w) & 0x01010101u;
-                    const u32 isn = nonzero_bytes(s[w] ^ 0x4E4E4E4Eu) ^ 0x01010101u;
-                    const u32 sk = (nonzero_bytes(k[w]) | below | trimmed | isn) * 0xFFu;
-                    u32 code, code5, expect;
-                    decode4x(s[w], code, code5, expect);
-                    odd |= ((expect ^ s[w]) & byte_mask(cnt, w)) != 0u;
-                    os[w] = rev ? complement4(s[w]) : s[w];
-                    oc[w] = os[w] ^ (nonzero_bytes(e[w]) << 7);                    // an error: cseq differs from seq
-                    oqv[w] = q[w] & ~sk;
-                }
-                if (NIB) {
-                    if (odd && !rev) flag(p.status, ST_LUT, r);
-                } else if (odd && !rev) {
-                    // the reference's TypeError (compare_reads.py:281-293 via bqsr.py:43-45) is decided on the
-                    // ORIGINAL qualities, before any skipping: a looked-up pair with a letter outside ACGT
-                    u32 prev = (c0 >= 1) ? p.seq[row + i0 - 1] : 'N';
-                    for (int b = 0; b < cnt; ++b) {
-                        const u32 cur = (s[b >> 2] >> (8 * (b & 3))) & 0xFFu, qq = (q[b >> 2] >> (8 * (b & 3))) & 0xFFu;
-                        if (c0 + b >= 1 && qq >= p.dlo && cur != 'N' && prev != 'N' && !(is_acgt(cur) && is_acgt(prev)))
-                            flag(p.status, ST_TYPE, r);
-                        prev = cur;
-                    }
-                }
-                if (rev) {
-                    reverse16(os); reverse16(oc); reverse16(oqv);
-                    if (cnt < 16) { shr_bytes16(os, 16 - cnt); shr_bytes16(oc, 16 - cnt); shr_bytes16(oqv, 16 - cnt); }
-                }
-                if (cnt < 16) {
-#pragma unroll
-                    for (int w = 0; w < 4; ++w) {                                  // past the aligned part: uncounted padding
-                        const u32 vm = byte_mask(cnt, w);
-                        os[w] = (os[w] & vm) | (0x4E4E4E4Eu & ~vm);
-                        oc[w] = (oc[w] & vm) | (0x4E4E4E4Eu & ~vm);
-                        oqv[w] &= vm;
-                    }
-                }
-            }
-            const size_t off = row + (size_t)16 * j;
-            if (NIB) {
-                u32 cs[4], cc[4], bad = 0u;
-#pragma unroll
-                for (int w = 0; w < 4; ++w) {
-                    cs[w] = chars_to_codes(os[w], bad);
-                    cc[w] = cs[w] ^ nonzero_bytes(os[w] ^ oc[w]);
-                }
-                const size_t noff = (row >> 1) + (size_t)8 * j;
-                *reinterpret_cast<uint2*>(p.out_seq + noff) = make_uint2(cs[0] | (cs[1] << 4), cs[2] | (cs[3] << 4));
-                *reinterpret_cast<uint2*>(p.out_cseq + noff) = make_uint2(cc[0] | (cc[1] << 4), cc[2] | (cc[3] << 4));
-            } else {
-                *reinterpret_cast<uint4*>(p.out_seq + off) = make_uint4(os[0], os[1], os[2], os[3]);
-                *reinterpret_cast<uint4*>(p.out_cseq + off) = make_uint4(oc[0], oc[1], oc[2], oc[3]);
-            }
-            *reinterpret_cast<uint4*>(p.out_qual + off) = make_uint4(oqv[0], oqv[1], oqv[2], oqv[3]);
-        }
-        it0 = it1; m0 = m1; w0 = w1;
-        it1 = it2; m1 = m2;
-        it2 = next(it2);
-    }
-}
-
-// ---------------------------------------------------------------- mate-pair rows
-// Optional device layout for paired reads of one length S (2 x 150 bp): ONE row per pair,
-//     [mate 1: S bytes][separator][mate 2: S bytes][padding to a multiple of 16]
-// separator and padding are 'N' (seq, cseq) / 0 (qual), i.e. uncounted bases.  2S + 1 = 301 -> pitch 304
-// instead of 2 x 160: 5 % fewer bytes through HBM for the same bases, and K1 / K2 run unchanged on the
-// rows as if they were single reads: byte offset b IS the stored cycle index (K1's table keeps
-// second-in-pair cycles mirrored from S upwards, here from S + 1; K2's pair LUT likewise), and the 'N'
-// separator gives mate 2's first base "no previous base" exactly like position 0 of a read.
-__host__ __device__ __forceinline__ int pair_pitch(int S2) { return (S2 + 1 + 15) & ~15; }
-__host__ __device__ __forceinline__ int pair_lut_row_bytes(int S2)
-{
-    int rb = pair_pitch(S2) + 32;
-    if (((rb >> 2) & 1) == 0) rb += 4;        // odd number of dwords per row
-    return rb;
-}
-
-struct PairLutParams {
-    const int16_t* lut16; int rs16; int R; int Qt; int S2; int minscore;
-    int twins;                       // rows of two first-in-pair reads: the second half looks up the forward columns too
-    int8_t* out;
-};
-
-// one workgroup per row (read group, raw quality byte) of the pair LUT
-__global__ __launch_bounds__(256) void k3_fill_pair_lut(PairLutParams p)
-{
-    const int rb = pair_lut_row_bytes(p.S2), cyc = pair_pitch(p.S2), S = p.S2 >> 1;
-    const int NR = 33 + p.Qt;
-    const int row = blockIdx.x;
-    const int r = row / NR, qb = row - r * NR;
-    const bool model = qb >= 33 + p.minscore;
-    const int16_t* src = p.lut16 + ((size_t)r * p.Qt + (qb >= 33 ? qb - 33 : 0)) * p.rs16;
-    int8_t* dst = p.out + (size_t)row * rb;
-    for (int x = threadIdx.x; x < rb; x += blockDim.x) {
-        int v = 0;
-        if (!model) {
-            if (x < cyc) v = qb == 0 ? -33 : qb - 33;                     // padding -> 0 ; uncounted -> unchanged
-        } else {
-            if (x < S) v = src[x];                                        // mate 1: column = position
-            else if (x > S && x <= p.S2) v = src[p.twins ? x - S - 1 : p.S2 - 1 - (x - S - 1)]; // mate 2, position i = x-S-1: column 2S-1-i (twins: i)
-            else if (x >= cyc && x < cyc + 25) v = src[p.S2 + (x - cyc)];
-        }
-        dst[x] = (int8_t)v;
-    }
-}
-
-struct PairPackParams {
-    const uint8_t* src[3]; uint8_t* dst[3]; uint8_t fill[3];
-    const u32* meta; u32* pmeta;
-    long long npairs; int pitch; int ppitch; int S; int unpack;
-};
-
-// lane <-> 16-byte chunk of a destination row.  pack: two reads -> one pair row (three planes);
-// unpack: one pair row -> two rows of one plane (the K2 output).
-__global__ __launch_bounds__(256) void k7_pack_pairs(PairPackParams p)
-{
-    const int S = p.S;
-    if (!p.unpack) {
-        const int cpr = p.ppitch >> 4;
-        const long long nchunks = p.npairs * cpr;
-        for (long long ch = (long long)blockIdx.x * blockDim.x + threadIdx.x; ch < nchunks;
-             ch += (long long)gridDim.x * blockDim.x) {
-            const long long pr = ch / cpr;
-            const int j = (int)(ch - pr * cpr);
-            if (j == 0) p.pmeta[pr] = (u32)(2 * S + 1) | (p.meta[2 * pr] & 0x7FFF0000u);
-            const long long limit = 2 * p.npairs * (long long)p.pitch;
-#pragma unroll
-            for (int pl = 0; pl < 3; ++pl) {
-                if (!p.src[pl]) continue;
-                const u32 f4 = p.fill[pl] * 0x01010101u;
-                u32 a[4], b[4], o[4];
-                // bytes [16j, 16j+16) of the pair row: mate 1 from offset 16j, mate 2 from offset 16j - S - 1
-                load16_upto(p.src[pl], (2 * pr) * (long long)p.pitch + 16 * j, limit, a);
-                const long long off2 = (2 * pr + 1) * (long long)p.pitch + (16 * j - S - 1);
-                if (16 * j + 15 > S) {
-                    if (16 * j - S - 1 >= 0) load16_upto(p.src[pl], off2, limit, b);
-                    else {                                                   // the chunk holding the separator
-                        b[0] = b[1] = b[2] = b[3] = 0u;
-                        for (int k = S + 1 - 16 * j; k < 16; ++k)
-                            b[k >> 2] |= (u32)p.src[pl][off2 + k] << (8 * (k & 3));
-                    }
-                } else { b[0] = b[1] = b[2] = b[3] = 0u; }
-#pragma unroll
-                for (int w = 0; w < 4; ++w) {
-                    const u32 m1 = byte_mask(S - 16 * j, w);                         // bytes of mate 1
-                    const u32 m2 = range_mask(S + 1 - 16 * j, 2 * S + 1 - 16 * j, w);   // bytes of mate 2
-                    o[w] = (a[w] & m1) | (b[w] & m2) | (f4 & ~(m1 | m2));
-                }
-                *reinterpret_cast<uint4*>(p.dst[pl] + pr * (long long)p.ppitch + 16 * j) = make_uint4(o[0], o[1], o[2], o[3]);
-            }
-        }
-    } else {
-        const int cpr = p.pitch >> 4;
-        const long long nchunks = 2 * p.npairs * cpr;
-        const long long limit = p.npairs * (long long)p.ppitch;
-        for (long long ch = (long long)blockIdx.x * blockDim.x + threadIdx.x; ch < nchunks;
-             ch += (long long)gridDim.x * blockDim.x) {
-            const long long rd = ch / cpr;
-            const int j = (int)(ch - rd * cpr);
-            const long long pr = rd >> 1;
-            const int base = (rd & 1) ? S + 1 : 0;
-            u32 a[4];
-            load16_upto(p.src[0], pr * (long long)p.ppitch + base + 16 * j, limit, a);
-#pragma unroll
-            for (int w = 0; w < 4; ++w) a[w] &= byte_mask(S - 16 * j, w);            // past the read: zero, as K2 writes
-            *reinterpret_cast<uint4*>(p.dst[0] + rd * (long long)p.pitch + 16 * j) = make_uint4(a[0], a[1], a[2], a[3]);
-        }
-    }
-}
-
-struct K5Params {
-    const uint8_t* qual; const uint8_t* err; const uint8_t* skip; const u32* len;
-    long long nreads; int pitch; int cpr; u32 cpr_magic; int qoffset;
-    u64* counts;                     // [0..255] totals, [256..511] errors
-    u64* status;
-};
-
-// lane <-> 16-byte chunk.  LDS: [257 bins][16 copies] u32, errs << 16 | total (copy = lane & 15: the 40-odd bins in
-// use are hot; copies cut the same-address collisions of a wave's atomic 16-fold), bin 256 = trash (skipped sites,
-// bytes past the read, values below the offset) so that every byte costs exactly one unconditional LDS atomic.
-// 16-bit halves: a copy receives at most 16 lanes x 16 bytes per workgroup iteration -> flushed every 255 iterations.
-#define K5_THREADS 256
-#define K5_COPIES 16
-#define K5_FLUSH_ITERS (65535 / ((K5_THREADS / K5_COPIES) * 16))
-__global__ __launch_bounds__(K5_THREADS) void k5_count_q(K5Params p)
-{
-    __shared__ u32 h[257 * K5_COPIES];
-    for (int i = threadIdx.x; i < 257 * K5_COPIES; i += blockDim.x) h[i] = 0u;
-    __syncthreads();
-    const long long nchunks = p.nreads * p.cpr;
-    const long long stride = (long long)gridDim.x * blockDim.x;
-    const long long iters = (nchunks + stride - 1) / stride;                 // the same for every thread: barriers are safe
-    const u32 copy = threadIdx.x & (K5_COPIES - 1);
-    auto flush = [&]() {
-        __syncthreads();
-        for (int b = threadIdx.x; b < 256; b += blockDim.x) {
-            u32 t = 0u, e = 0u;
-            for (int c = 0; c < K5_COPIES; ++c) { const u32 v = h[b * K5_COPIES + c]; h[b * K5_COPIES + c] = 0u; t += v & 0xFFFFu; e += v >> 16; }
-            if (t) atomicAdd(&p.counts[b], (u64)t);
-            if (e) atomicAdd(&p.counts[256 + b], (u64)e);
-        }
-        __syncthreads();
-    };
-    int since = 0;
-    // the loads of the NEXT chunk are issued before the current one is binned (one step of software prefetch)
-    struct Chunk { uint4 q, e, s; long long r; int nb; };
-    auto fetch = [&](long long ch, Chunk& c) {
-        c.nb = 0; c.r = 0;
-        if (ch >= nchunks) return;
-        c.r = ch / p.cpr;
-        const int j = (int)(ch - c.r * p.cpr);
-        c.nb = (int)p.len[c.r] - 16 * j;
-        if (c.nb <= 0) return;
-        const size_t off = (size_t)c.r * p.pitch + (size_t)16 * j;
-        c.q = *reinterpret_cast<const uint4*>(p.qual + off);
-        c.e = *reinterpret_cast<const uint4*>(p.err + off);
-        if (p.skip) c.s = *reinterpret_cast<const uint4*>(p.skip + off);
-        else {                                                     // one plane of flags: bit 0 error, bit 1 skip
-            c.s = make_uint4(c.e.x & 0x02020202u, c.e.y & 0x02020202u, c.e.z & 0x02020202u, c.e.w & 0x02020202u);
-            c.e = make_uint4(c.e.x & 0x01010101u, c.e.y & 0x01010101u, c.e.z & 0x01010101u, c.e.w & 0x01010101u);
-        }
-    };
-    long long ch = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    Chunk cur, nxt;
-    fetch(ch, cur);
-    for (long long it = 0; it < iters; ++it, ch += stride) {
-        fetch(ch + stride, nxt);
-        if (cur.nb > 0) {
-            const int nb = cur.nb;
-            const u32 q[4] = {cur.q.x, cur.q.y, cur.q.z, cur.q.w}, e[4] = {cur.e.x, cur.e.y, cur.e.z, cur.e.w}, s[4] = {cur.s.x, cur.s.y, cur.s.z, cur.s.w};
-            bool negative = false;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const int sh = 8 * (i & 3);
-                const int qq = (int)((q[i >> 2] >> sh) & 0xFFu) - p.qoffset;
-                const bool counted = i < nb && ((s[i >> 2] >> sh) & 0xFFu) == 0u;
-                negative |= counted && qq < 0;                               // np.bincount rejects negative values: ValueError
-                const u32 bin = (counted && qq >= 0) ? (u32)qq : 256u;
-                const u32 inc = ((e[i >> 2] >> sh) & 0xFFu) ? 0x10001u : 1u;
-                atomicAdd(&h[bin * K5_COPIES + copy], inc);
-            }
-            if (negative) flag(p.status, ST_RANGE, cur.r);
-        }
-        cur = nxt;
-        if (++since == K5_FLUSH_ITERS) { flush(); since = 0; }
-    }
-    flush();
 }

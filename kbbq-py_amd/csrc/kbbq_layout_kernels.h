@@ -13,6 +13,7 @@
 // reference line to cite beyond the sidecar rules of compare_reads.py:304-318.
 #pragma once
 #include "kbbq_kernels_v3.h"
+#include "kbbq_aligned_kernels.h"      // the byte-window helpers (load16_upto, range_mask, shr_bytes16)
 
 // ---------------------------------------------------------------- sidecar statistics
 // stats[0] shortest non-empty read   stats[1] longest read   stats[2] largest read-group id
@@ -322,4 +323,69 @@ struct AddTablesParams { long long* dst; const long long* src; long long n; };
 __global__ __launch_bounds__(256) void k7_add_tables(AddTablesParams p)
 {
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < p.n; i += (long long)gridDim.x * blockDim.x) p.dst[i] += p.src[i];
+}
+
+// ---------------------------------------------------------------- mate-pair rows on their own (layout: kbbq_kernels_v3.h pair_pitch)
+struct PairPackParams {
+    const uint8_t* src[3]; uint8_t* dst[3]; uint8_t fill[3];
+    const u32* meta; u32* pmeta;
+    long long npairs; int pitch; int ppitch; int S; int unpack;
+};
+
+// lane <-> 16-byte chunk of a destination row.  pack: two reads -> one pair row (three planes);
+// unpack: one pair row -> two rows of one plane (the K2 output).
+__global__ __launch_bounds__(256) void k7_pack_pairs(PairPackParams p)
+{
+    const int S = p.S;
+    if (!p.unpack) {
+        const int cpr = p.ppitch >> 4;
+        const long long nchunks = p.npairs * cpr;
+        for (long long ch = (long long)blockIdx.x * blockDim.x + threadIdx.x; ch < nchunks;
+             ch += (long long)gridDim.x * blockDim.x) {
+            const long long pr = ch / cpr;
+            const int j = (int)(ch - pr * cpr);
+            if (j == 0) p.pmeta[pr] = (u32)(2 * S + 1) | (p.meta[2 * pr] & 0x7FFF0000u);
+            const long long limit = 2 * p.npairs * (long long)p.pitch;
+#pragma unroll
+            for (int pl = 0; pl < 3; ++pl) {
+                if (!p.src[pl]) continue;
+                const u32 f4 = p.fill[pl] * 0x01010101u;
+                u32 a[4], b[4], o[4];
+                // bytes [16j, 16j+16) of the pair row: mate 1 from offset 16j, mate 2 from offset 16j - S - 1
+                load16_upto(p.src[pl], (2 * pr) * (long long)p.pitch + 16 * j, limit, a);
+                const long long off2 = (2 * pr + 1) * (long long)p.pitch + (16 * j - S - 1);
+                if (16 * j + 15 > S) {
+                    if (16 * j - S - 1 >= 0) load16_upto(p.src[pl], off2, limit, b);
+                    else {                                                   // the chunk holding the separator
+                        b[0] = b[1] = b[2] = b[3] = 0u;
+                        for (int k = S + 1 - 16 * j; k < 16; ++k)
+                            b[k >> 2] |= (u32)p.src[pl][off2 + k] << (8 * (k & 3));
+                    }
+                } else { b[0] = b[1] = b[2] = b[3] = 0u; }
+#pragma unroll
+                for (int w = 0; w < 4; ++w) {
+                    const u32 m1 = byte_mask(S - 16 * j, w);                         // bytes of mate 1
+                    const u32 m2 = range_mask(S + 1 - 16 * j, 2 * S + 1 - 16 * j, w);   // bytes of mate 2
+                    o[w] = (a[w] & m1) | (b[w] & m2) | (f4 & ~(m1 | m2));
+                }
+                *reinterpret_cast<uint4*>(p.dst[pl] + pr * (long long)p.ppitch + 16 * j) = make_uint4(o[0], o[1], o[2], o[3]);
+            }
+        }
+    } else {
+        const int cpr = p.pitch >> 4;
+        const long long nchunks = 2 * p.npairs * cpr;
+        const long long limit = p.npairs * (long long)p.ppitch;
+        for (long long ch = (long long)blockIdx.x * blockDim.x + threadIdx.x; ch < nchunks;
+             ch += (long long)gridDim.x * blockDim.x) {
+            const long long rd = ch / cpr;
+            const int j = (int)(ch - rd * cpr);
+            const long long pr = rd >> 1;
+            const int base = (rd & 1) ? S + 1 : 0;
+            u32 a[4];
+            load16_upto(p.src[0], pr * (long long)p.ppitch + base + 16 * j, limit, a);
+#pragma unroll
+            for (int w = 0; w < 4; ++w) a[w] &= byte_mask(S - 16 * j, w);            // past the read: zero, as K2 writes
+            *reinterpret_cast<uint4*>(p.dst[0] + rd * (long long)p.pitch + 16 * j) = make_uint4(a[0], a[1], a[2], a[3]);
+        }
+    }
 }

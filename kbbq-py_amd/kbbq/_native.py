@@ -10,7 +10,7 @@ import ctypes
 import os
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-# KBBQ_HIP_LIB selects another build of the same ABI (timing-only ablation builds, scripts/)
+# KBBQ_HIP_LIB selects another build of the same ABI (make OUT=...: e.g. the parent commit's library beside this one's)
 LIB_PATH = os.environ.get('KBBQ_HIP_LIB') or os.path.join(HERE, 'libkbbq_hip.so')
 
 KBBQ_OK = 0

@@ -56,7 +56,7 @@ for step in "$@"; do
                  i=0
                  for SET in FETCH_SIZE WRITE_SIZE; do
                    i=$((i+1)); mkdir -p $OUT/traffic/$LAY
-                   timeout -k 10 300 rocprofv3 --pmc $SET -d $OUT/traffic/$LAY/p$i -o p$i --output-format csv -- python3 $PWD/scripts/prof_kernels.py --reads 20000000 --reps 2 $A > $OUT/traffic/$LAY/p$i.log 2>&1 || ok=0
+                   timeout -k 10 300 rocprofv3 --pmc $SET -d $OUT/traffic/$LAY/p$i -o p$i --output-format csv -- python3 $PWD/scripts/prof_kernels.py --reads 20000000 --reps 2 $A > $OUT/traffic/$LAY/p$i.log 2>&1 || { ok=0; break 2; }   # a failed pass ends the step: nothing more is started on the GPU
                  done
                done
                [ $ok -eq 1 ] && python scripts/pmc_traffic_json.py $OUT/traffic 20000000 > $OUT/pmc_traffic.json && cp $OUT/pmc_traffic.json profiles/pmc_traffic.json \
@@ -68,7 +68,7 @@ for step in "$@"; do
                             "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_LDS_ADDR_CONFLICT SQ_LDS_UNALIGNED_STALL SQ_INSTS_BRANCH SQ_THREAD_CYCLES_VALU" \
                             "TCP_PENDING_STALL_CYCLES_sum TCP_TCC_READ_REQ_LATENCY_sum TCP_TCC_READ_REQ_sum" "GRBM_GUI_ACTIVE GRBM_COUNT"; do
                    i=$((i+1)); mkdir -p $OUT/table
-                   timeout -k 10 300 rocprofv3 --pmc $SET -d $OUT/table/p$i -o p$i --output-format csv -- python3 $PWD/scripts/prof_kernels.py --reads 20000000 --reps 2 --packed > $OUT/table/p$i.log 2>&1 || ok=0
+                   timeout -k 10 300 rocprofv3 --pmc $SET -d $OUT/table/p$i -o p$i --output-format csv -- python3 $PWD/scripts/prof_kernels.py --reads 20000000 --reps 2 --packed > $OUT/table/p$i.log 2>&1 || { ok=0; break; }
                  done
                  [ $ok -eq 1 ] && python scripts/pmc_summary.py $OUT/table > gpurun_out/pmc_table_$TAG.md
                fi

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Kernel timing (HIP events) of K1/K2 on a resident synthetic batch; honours KBBQ_ABLATE_* (timing-only builds)."""
+"""Kernel timing (HIP events) of K1/K2 on a resident synthetic batch, in any layout (KBBQ_HIP_LIB: another build of the library)."""
 import argparse, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, 'kbbq-py_amd'))
@@ -38,6 +38,6 @@ for _ in range(args.reps):
 torch.cuda.synchronize()
 k1, n1 = ctx.kernel_ms(0); k2, n2 = ctx.kernel_ms(1)
 bases = args.reads * args.len
-print('ABLATE K1=%s K2=%s reads=%d rgs=%d len=%d: K1 %.3f ms (%.0f GB/s alg)  K2 %.3f ms (%.0f GB/s alg)' % (
-    os.environ.get('KBBQ_ABLATE_K1', '0'), os.environ.get('KBBQ_ABLATE_K2', '0'), args.reads, args.rgs, args.len,
+print('lib=%s reads=%d rgs=%d len=%d: K1 %.3f ms (%.0f GB/s alg)  K2 %.3f ms (%.0f GB/s alg)' % (
+    os.path.basename(os.environ.get('KBBQ_HIP_LIB') or 'libkbbq_hip.so'), args.reads, args.rgs, args.len,
     k1 / n1, 3 * bases / (k1 / n1) / 1e6, k2 / n2, 3 * bases / (k2 / n2) / 1e6))
