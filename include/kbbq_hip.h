@@ -781,6 +781,30 @@ int kbbq_kmer_prefilter(kbbq_ctx* ctx, kbbq_kmer_filter* filter, int k, const ui
 int kbbq_kmer_count_filtered(kbbq_ctx* ctx, kbbq_kmer_table* table, const kbbq_kmer_filter* filter, const uint8_t* seq,
                              const uint32_t* meta, int64_t nreads, int pitch);
 
+/* ---- the k-mer calls on resident rows (kbbq recalibrate -c; csrc/kbbq_kmer.h "Row readers") ----------------------------------
+ * The recalibrate file path keeps its reads on the device in the layouts of kbbq_accumulate_rows_dev: mate-pair or twin rows,
+ * 4-bit sequence planes, rows grouped by read group.  These four are the calls above on such rows, `flags` the KBBQ_ROWS_* of
+ * that call, so that reads are counted and corrected where they lie and K1 takes the corrected plane as its d_cseq.
+ * KBBQ_ROWS_NIBBLES: d_seq (and d_out) are 4-bit planes -- row stride pitch / 2, 8 bytes per 16-base chunk, 8-byte aligned,
+ * nibble order and codes (A0 T1 G2 C3, 4 = N / separator / padding) as documented above.  A code >= 4 is a break, and so is every
+ * position at or beyond the row's length (the sidecar's low 16 bits).  The k-mer code stays the table's own (A0 C1 G2 T3,
+ * canonical = the smaller of forward and reverse complement): keys, counts, the histogram and the filter words are those the
+ * character calls produce for the same bases, and one table may be counted from rows of both kinds.  d_out receives the
+ * corrected plane in the same 4-bit layout, breaks and padding as read.
+ * KBBQ_ROWS_PAIRS / KBBQ_ROWS_TWINS need nothing of their own: a row's sidecar length is 2S + 1 and the separator is a break, so
+ * no window spans two reads.  The flags are checked as kbbq_accumulate_rows_dev checks them (TWINS only with PAIRS) and pitch
+ * must be a multiple of 16, which every kbbq_pair_pitch is; d_changed is per ROW (a mate-pair row counts both mates).
+ * Without KBBQ_ROWS_NIBBLES the calls ARE the character calls above on the same rows.  Grouping by read group only orders the
+ * rows: d_seg / d_perm are not needed here.                                                                                */
+int kbbq_kmer_count_rows_dev(kbbq_ctx* ctx, kbbq_kmer_table* table, const uint8_t* d_seq, const uint32_t* d_meta, int64_t nrows,
+                             int pitch, int flags);
+int kbbq_kmer_prefilter_rows_dev(kbbq_ctx* ctx, kbbq_kmer_filter* filter, int k, const uint8_t* d_seq, const uint32_t* d_meta,
+                                 int64_t nrows, int pitch, int flags);
+int kbbq_kmer_count_filtered_rows_dev(kbbq_ctx* ctx, kbbq_kmer_table* table, const kbbq_kmer_filter* filter, const uint8_t* d_seq,
+                                      const uint32_t* d_meta, int64_t nrows, int pitch, int flags);
+int kbbq_kmer_correct_rows_dev(kbbq_ctx* ctx, const kbbq_kmer_table* table, const uint8_t* d_seq, const uint32_t* d_meta,
+                               int64_t nrows, int pitch, int flags, int min_count, uint8_t* d_out, uint32_t* d_changed);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2131,14 +2131,16 @@ int kbbq_kmer_table_info(const kbbq_kmer_table* t, int* k, int64_t* slots, void*
     return KBBQ_OK;
 }
 
-// rows per workgroup and LDS words per row-chunk of the kernels that walk k-mer windows; the table's fields stay unset
+// rows per workgroup and LDS words per row-chunk of the kernels that walk k-mer windows; the table's fields stay unset.
+// nib: 4-bit planes -- `pitch` bases a row in pitch / 2 bytes, rows 8-byte aligned
 static int kmer_rows(kbbq_ctx* c, const char* who, int k, const uint8_t* d_seq, const uint32_t* d_meta, int64_t n, int pitch,
-                     KmerParams& p, int lds_words, size_t* lds)
+                     KmerParams& p, int lds_words, size_t* lds, bool nib = false)
 {
-    int rc = check_planes(who, n, pitch, d_seq, d_seq, d_seq);
+    int rc = check_planes(who, n, pitch, nib ? nullptr : d_seq, nullptr, nullptr);
     if (rc) return rc;
-    if (n > 0 && !d_meta) return fail(KBBQ_E_ARG, "%s: NULL meta", who);
-    p.seq = d_seq; p.meta = d_meta; p.nrows = n; p.pitch = pitch; p.cpr = pitch / 16; p.k = k;
+    if (nib && ((uintptr_t)d_seq & 7)) return fail(KBBQ_E_ARG, "%s: 4-bit planes must be 8-byte aligned", who);
+    if (n > 0 && (!d_seq || !d_meta)) return fail(KBBQ_E_ARG, "%s: NULL plane or meta", who);
+    p.seq = d_seq; p.meta = d_meta; p.nrows = n; p.pitch = nib ? pitch / 2 : pitch; p.cpr = pitch / 16; p.k = k;
     p.rows_per_wg = std::max(1, KM_THREADS / p.cpr);
     p.keys = nullptr; p.counts = nullptr; p.mask = 0; p.status = c->d_status;
     p.min_count = 1; p.out = nullptr; p.changed = nullptr;
@@ -2149,10 +2151,10 @@ static int kmer_rows(kbbq_ctx* c, const char* who, int k, const uint8_t* d_seq, 
 
 // ... of the count / correct kernels
 static int kmer_geometry(kbbq_ctx* c, const char* who, const kbbq_kmer_table* t, const uint8_t* d_seq, const uint32_t* d_meta,
-                         int64_t n, int pitch, KmerParams& p, int lds_words, size_t* lds)
+                         int64_t n, int pitch, KmerParams& p, int lds_words, size_t* lds, bool nib = false)
 {
     if (!c || !t) return fail(KBBQ_E_ARG, "%s: NULL ctx or table", who);
-    int rc = kmer_rows(c, who, t->k, d_seq, d_meta, n, pitch, p, lds_words, lds);
+    int rc = kmer_rows(c, who, t->k, d_seq, d_meta, n, pitch, p, lds_words, lds, nib);
     if (rc) return rc;
     p.keys = t->keys; p.counts = t->counts; p.mask = (u64)t->slots - 1;
     return KBBQ_OK;
@@ -2174,15 +2176,41 @@ static int kmer_launches(const KmerParams& p, const std::function<void(const Kme
     return KBBQ_OK;
 }
 
-int kbbq_kmer_count_dev(kbbq_ctx* c, kbbq_kmer_table* t, const uint8_t* d_seq, const uint32_t* d_meta, int64_t n, int pitch)
+static int kmer_count_rows(kbbq_ctx* c, const char* who, kbbq_kmer_table* t, const uint8_t* d_seq, const uint32_t* d_meta, int64_t n,
+                           int pitch, bool nib)
 {
     KmerParams p; size_t lds = 0;
-    int rc = kmer_geometry(c, "kbbq_kmer_count_dev", t, d_seq, d_meta, n, pitch, p, 2, &lds);
+    int rc = kmer_geometry(c, who, t, d_seq, d_meta, n, pitch, p, 2, &lds, nib);
     if (rc || n == 0) return rc;
     HIPCHK(hipSetDevice(c->device));
     return kmer_launches(p, [&](const KmerParams& q, unsigned grid) {
-        hipLaunchKernelGGL(km_count, dim3(grid), dim3(KM_THREADS), lds, c->stream, q);
+        if (nib) hipLaunchKernelGGL(km_count<true>, dim3(grid), dim3(KM_THREADS), lds, c->stream, q);
+        else hipLaunchKernelGGL(km_count<false>, dim3(grid), dim3(KM_THREADS), lds, c->stream, q);
     });
+}
+
+int kbbq_kmer_count_dev(kbbq_ctx* c, kbbq_kmer_table* t, const uint8_t* d_seq, const uint32_t* d_meta, int64_t n, int pitch)
+{
+    return kmer_count_rows(c, "kbbq_kmer_count_dev", t, d_seq, d_meta, n, pitch, false);
+}
+
+// the KBBQ_ROWS_* flags of the k-mer calls on resident rows: is the plane a 4-bit one?  Two reads to a row need nothing of
+// their own (the separator is a break); their pitch holds at least 2 x 1 bases and the separator, as any multiple of 16 does
+static int kmer_row_flags(const char* who, int flags, bool* nib)
+{
+    int rc = layout_flags_ok(who, flags);
+    if (rc) return rc;
+    *nib = (flags & KBBQ_ROWS_NIBBLES) != 0;
+    return KBBQ_OK;
+}
+
+int kbbq_kmer_count_rows_dev(kbbq_ctx* c, kbbq_kmer_table* t, const uint8_t* d_seq, const uint32_t* d_meta, int64_t nrows, int pitch,
+                             int flags)
+{
+    bool nib = false;
+    int rc = kmer_row_flags("kbbq_kmer_count_rows_dev", flags, &nib);
+    if (rc) return rc;
+    return kmer_count_rows(c, "kbbq_kmer_count_rows_dev", t, d_seq, d_meta, nrows, pitch, nib);
 }
 
 int kbbq_kmer_histogram_dev(kbbq_ctx* c, const kbbq_kmer_table* t, uint64_t* d_hist)
@@ -2197,20 +2225,37 @@ int kbbq_kmer_histogram_dev(kbbq_ctx* c, const kbbq_kmer_table* t, uint64_t* d_h
     return KBBQ_OK;
 }
 
-int kbbq_kmer_correct_dev(kbbq_ctx* c, const kbbq_kmer_table* t, const uint8_t* d_seq, const uint32_t* d_meta, int64_t n, int pitch,
-                          int min_count, uint8_t* d_out, uint32_t* d_changed)
+static int kmer_correct_rows(kbbq_ctx* c, const char* who, const kbbq_kmer_table* t, const uint8_t* d_seq, const uint32_t* d_meta,
+                             int64_t n, int pitch, bool nib, int min_count, uint8_t* d_out, uint32_t* d_changed)
 {
     KmerParams p; size_t lds = 0;
-    int rc = kmer_geometry(c, "kbbq_kmer_correct_dev", t, d_seq, d_meta, n, pitch, p, 3, &lds);
+    int rc = kmer_geometry(c, who, t, d_seq, d_meta, n, pitch, p, 3, &lds, nib);
     if (rc) return rc;
-    if (min_count < 1) return fail(KBBQ_E_ARG, "kbbq_kmer_correct_dev: min_count must be >= 1, got %d", min_count);
-    if (n > 0 && (!d_out || ((uintptr_t)d_out & 15))) return fail(KBBQ_E_ARG, "kbbq_kmer_correct_dev: d_out NULL or not 16-byte aligned");
+    if (min_count < 1) return fail(KBBQ_E_ARG, "%s: min_count must be >= 1, got %d", who, min_count);
+    if (n > 0 && (!d_out || ((uintptr_t)d_out & (nib ? 7 : 15))))
+        return fail(KBBQ_E_ARG, "%s: d_out NULL or not %d-byte aligned", who, nib ? 8 : 16);
     if (n == 0) return KBBQ_OK;
     HIPCHK(hipSetDevice(c->device));
     p.min_count = (u32)min_count; p.out = d_out; p.changed = d_changed;
     return kmer_launches(p, [&](const KmerParams& q, unsigned grid) {
-        hipLaunchKernelGGL(km_correct, dim3(grid), dim3(KM_THREADS), lds, c->stream, q);
+        if (nib) hipLaunchKernelGGL(km_correct<true>, dim3(grid), dim3(KM_THREADS), lds, c->stream, q);
+        else hipLaunchKernelGGL(km_correct<false>, dim3(grid), dim3(KM_THREADS), lds, c->stream, q);
     });
+}
+
+int kbbq_kmer_correct_dev(kbbq_ctx* c, const kbbq_kmer_table* t, const uint8_t* d_seq, const uint32_t* d_meta, int64_t n, int pitch,
+                          int min_count, uint8_t* d_out, uint32_t* d_changed)
+{
+    return kmer_correct_rows(c, "kbbq_kmer_correct_dev", t, d_seq, d_meta, n, pitch, false, min_count, d_out, d_changed);
+}
+
+int kbbq_kmer_correct_rows_dev(kbbq_ctx* c, const kbbq_kmer_table* t, const uint8_t* d_seq, const uint32_t* d_meta, int64_t nrows,
+                               int pitch, int flags, int min_count, uint8_t* d_out, uint32_t* d_changed)
+{
+    bool nib = false;
+    int rc = kmer_row_flags("kbbq_kmer_correct_rows_dev", flags, &nib);
+    if (rc) return rc;
+    return kmer_correct_rows(c, "kbbq_kmer_correct_rows_dev", t, d_seq, d_meta, nrows, pitch, nib, min_count, d_out, d_changed);
 }
 
 int kbbq_kmer_table_clear_dev(kbbq_ctx* c, kbbq_kmer_table* t)
@@ -2412,33 +2457,65 @@ static KmerFilterParams kmer_filter_params(const kbbq_kmer_filter* f)
     return q;
 }
 
-int kbbq_kmer_prefilter_dev(kbbq_ctx* c, kbbq_kmer_filter* f, int k, const uint8_t* d_seq, const uint32_t* d_meta, int64_t n, int pitch)
+static int kmer_prefilter_rows(kbbq_ctx* c, const char* who, kbbq_kmer_filter* f, int k, const uint8_t* d_seq, const uint32_t* d_meta,
+                               int64_t n, int pitch, bool nib)
 {
-    if (!c || !f) return fail(KBBQ_E_ARG, "kbbq_kmer_prefilter_dev: NULL ctx or filter");
-    if (k < 8 || k > 32) return fail(KBBQ_E_ARG, "kbbq_kmer_prefilter_dev: k must be in 8..32, got %d", k);
-    if (!f->seen) return fail(KBBQ_E_ARG, "kbbq_kmer_prefilter_dev: the filter's `seen` array has been released");
+    if (!c || !f) return fail(KBBQ_E_ARG, "%s: NULL ctx or filter", who);
+    if (k < 8 || k > 32) return fail(KBBQ_E_ARG, "%s: k must be in 8..32, got %d", who, k);
+    if (!f->seen) return fail(KBBQ_E_ARG, "%s: the filter's `seen` array has been released", who);
     KmerParams p; size_t lds = 0;
-    int rc = kmer_rows(c, "kbbq_kmer_prefilter_dev", k, d_seq, d_meta, n, pitch, p, 2, &lds);
+    int rc = kmer_rows(c, who, k, d_seq, d_meta, n, pitch, p, 2, &lds, nib);
     if (rc || n == 0) return rc;
     HIPCHK(hipSetDevice(c->device));
     const KmerFilterParams fp = kmer_filter_params(f);
     return kmer_launches(p, [&](const KmerParams& q, unsigned grid) {
-        hipLaunchKernelGGL(km_prefilter, dim3(grid), dim3(KM_THREADS), lds, c->stream, q, fp);
+        if (nib) hipLaunchKernelGGL(km_prefilter<true>, dim3(grid), dim3(KM_THREADS), lds, c->stream, q, fp);
+        else hipLaunchKernelGGL(km_prefilter<false>, dim3(grid), dim3(KM_THREADS), lds, c->stream, q, fp);
+    });
+}
+
+int kbbq_kmer_prefilter_dev(kbbq_ctx* c, kbbq_kmer_filter* f, int k, const uint8_t* d_seq, const uint32_t* d_meta, int64_t n, int pitch)
+{
+    return kmer_prefilter_rows(c, "kbbq_kmer_prefilter_dev", f, k, d_seq, d_meta, n, pitch, false);
+}
+
+int kbbq_kmer_prefilter_rows_dev(kbbq_ctx* c, kbbq_kmer_filter* f, int k, const uint8_t* d_seq, const uint32_t* d_meta, int64_t nrows,
+                                 int pitch, int flags)
+{
+    bool nib = false;
+    int rc = kmer_row_flags("kbbq_kmer_prefilter_rows_dev", flags, &nib);
+    if (rc) return rc;
+    return kmer_prefilter_rows(c, "kbbq_kmer_prefilter_rows_dev", f, k, d_seq, d_meta, nrows, pitch, nib);
+}
+
+static int kmer_count_filtered_rows(kbbq_ctx* c, const char* who, kbbq_kmer_table* t, const kbbq_kmer_filter* f, const uint8_t* d_seq,
+                                    const uint32_t* d_meta, int64_t n, int pitch, bool nib)
+{
+    if (!f) return fail(KBBQ_E_ARG, "%s: filter is NULL", who);
+    KmerParams p; size_t lds = 0;
+    int rc = kmer_geometry(c, who, t, d_seq, d_meta, n, pitch, p, 2, &lds, nib);
+    if (rc || n == 0) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    const KmerFilterParams fp = kmer_filter_params(f);
+    return kmer_launches(p, [&](const KmerParams& q, unsigned grid) {
+        if (nib) hipLaunchKernelGGL(km_count_filtered<true>, dim3(grid), dim3(KM_THREADS), lds, c->stream, q, fp);
+        else hipLaunchKernelGGL(km_count_filtered<false>, dim3(grid), dim3(KM_THREADS), lds, c->stream, q, fp);
     });
 }
 
 int kbbq_kmer_count_filtered_dev(kbbq_ctx* c, kbbq_kmer_table* t, const kbbq_kmer_filter* f, const uint8_t* d_seq,
                                  const uint32_t* d_meta, int64_t n, int pitch)
 {
-    if (!f) return fail(KBBQ_E_ARG, "kbbq_kmer_count_filtered_dev: filter is NULL");
-    KmerParams p; size_t lds = 0;
-    int rc = kmer_geometry(c, "kbbq_kmer_count_filtered_dev", t, d_seq, d_meta, n, pitch, p, 2, &lds);
-    if (rc || n == 0) return rc;
-    HIPCHK(hipSetDevice(c->device));
-    const KmerFilterParams fp = kmer_filter_params(f);
-    return kmer_launches(p, [&](const KmerParams& q, unsigned grid) {
-        hipLaunchKernelGGL(km_count_filtered, dim3(grid), dim3(KM_THREADS), lds, c->stream, q, fp);
-    });
+    return kmer_count_filtered_rows(c, "kbbq_kmer_count_filtered_dev", t, f, d_seq, d_meta, n, pitch, false);
+}
+
+int kbbq_kmer_count_filtered_rows_dev(kbbq_ctx* c, kbbq_kmer_table* t, const kbbq_kmer_filter* f, const uint8_t* d_seq,
+                                      const uint32_t* d_meta, int64_t nrows, int pitch, int flags)
+{
+    bool nib = false;
+    int rc = kmer_row_flags("kbbq_kmer_count_filtered_rows_dev", flags, &nib);
+    if (rc) return rc;
+    return kmer_count_filtered_rows(c, "kbbq_kmer_count_filtered_rows_dev", t, f, d_seq, d_meta, nrows, pitch, nib);
 }
 
 int kbbq_kmer_prefilter(kbbq_ctx* c, kbbq_kmer_filter* f, int k, const uint8_t* seq, const uint32_t* meta, int64_t n, int pitch)

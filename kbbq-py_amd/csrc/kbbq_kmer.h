@@ -35,6 +35,14 @@
 // more is in `twice`, whatever the thread order.  Bits are only ever set, so a relaxed load that shows the whole mask is
 // final and the atomic is skipped.  km_count_filtered is km_count for the windows whose mask is whole in `twice`: the table
 // then holds every key of count >= 2 with its exact count and some keys of count 1 (false positives), nothing else.
+//
+// Row readers: the kernels that walk windows are templates over NIB, and only pass 1 (km_load_chunks) and km_correct's load
+// and store of the chunk it rewrites read it.  NIB = false: character planes, 16 bytes a chunk.  NIB = true: the 4-bit sequence planes the
+// recalibrate file path keeps resident (include/kbbq_hip.h KBBQ_ROWS_NIBBLES: codes A0 T1 G2 C3, 4 = N / separator / padding;
+// 8 bytes a chunk, word w holds bases 8w..8w+3 in the low nibbles of its bytes and 8w+4..8w+7 in the high ones).  A nibble
+// >= 4 is a break; the other codes map to the table's A0 C1 G2 T3 by swapping 1 and 3, so keys, counts and filter words are
+// those of the character kernels on the same bases.  KmerParams.pitch is the plane's row stride in BYTES (half the bases of a
+// row with NIB), cpr the 16-base chunks of a row.  A mate-pair row is one row: its separator is a break, no window spans it.
 #pragma once
 #include "kbbq_kernels.h"
 
@@ -46,10 +54,10 @@ constexpr u64 KM_EMPTY = ~0ull;
 constexpr int KM_HIST = 257;          // h[c], c = 1..255; h[256]: count >= 256; h[0] stays 0
 
 struct KmerParams {
-    const uint8_t* seq; const u32* meta; int64_t nrows; int pitch; int cpr; int rows_per_wg; int k;
+    const uint8_t* seq; const u32* meta; int64_t nrows; int pitch; int cpr; int rows_per_wg; int k;   // pitch: row stride, bytes
     u64* keys; u32* counts; u64 mask;
     u32 min_count;                    // correct: a k-mer is solid when its count is >= min_count
-    uint8_t* out; u32* changed;       // correct: the corrected plane; per-read count of changed bases (may be NULL)
+    uint8_t* out; u32* changed;       // correct: the corrected plane; per-row count of changed bases (may be NULL)
     u64* status;
 };
 
@@ -107,8 +115,15 @@ __device__ __forceinline__ bool km_insert(const KmerParams& p, u64 key)
     return false;
 }
 
+// the table's code (A0 C1 G2 T3) of a plane nibble 0..3 (A0 T1 G2 C3) and back: 1 and 3 change places
+__device__ __forceinline__ u32 km_nib_swap(u32 n) { return n ^ ((n & 1u) << 1); }
+
+// bit offset of base t (0..7) of a word of a 4-bit plane
+__device__ __forceinline__ int km_nib_shift(int t) { return 8 * (t & 3) + 4 * ((t >> 2) & 1); }
+
 // Pass 1: the code word (base t of the chunk in bits 31 - 2t .. 30 - 2t) and break mask (bit t) of every chunk of the
 // workgroup's rows.  Returns the number of rows this workgroup holds.
+template <bool NIB>
 __device__ __forceinline__ int km_load_chunks(const KmerParams& p, int64_t row0, u32* code, u32* brk)
 {
     const int nr = (int)(p.nrows - row0 < p.rows_per_wg ? p.nrows - row0 : p.rows_per_wg);
@@ -116,16 +131,28 @@ __device__ __forceinline__ int km_load_chunks(const KmerParams& p, int64_t row0,
         const int r = e / p.cpr, ch = e - r * p.cpr;
         const int64_t row = row0 + r;
         const int L = (int)(p.meta[row] & 0xFFFFu);
-        const uint4 v = *reinterpret_cast<const uint4*>(p.seq + (size_t)row * p.pitch + (size_t)ch * 16);
-        const u32 w[4] = {v.x, v.y, v.z, v.w};
         u32 c = 0, b = 0;
-        #pragma unroll
-        for (int t = 0; t < 16; ++t) {
-            const u32 x = (w[t >> 2] >> (8 * (t & 3))) & 0xFFu;
-            const u32 cv = x == 'A' ? 0u : x == 'C' ? 1u : x == 'G' ? 2u : 3u;
-            const bool base = (x == 'A' || x == 'C' || x == 'G' || x == 'T') && ch * 16 + t < L;
-            c |= (base ? cv : 0u) << (30 - 2 * t);
-            b |= (base ? 0u : 1u) << t;
+        if constexpr (NIB) {
+            const uint2 v = *reinterpret_cast<const uint2*>(p.seq + (size_t)row * p.pitch + (size_t)ch * 8);
+            const u32 w[2] = {v.x, v.y};
+            #pragma unroll
+            for (int t = 0; t < 16; ++t) {
+                const u32 x = (w[t >> 3] >> km_nib_shift(t & 7)) & 0xFu;
+                const bool base = x < 4u && ch * 16 + t < L;
+                c |= (base ? km_nib_swap(x) : 0u) << (30 - 2 * t);
+                b |= (base ? 0u : 1u) << t;
+            }
+        } else {
+            const uint4 v = *reinterpret_cast<const uint4*>(p.seq + (size_t)row * p.pitch + (size_t)ch * 16);
+            const u32 w[4] = {v.x, v.y, v.z, v.w};
+            #pragma unroll
+            for (int t = 0; t < 16; ++t) {
+                const u32 x = (w[t >> 2] >> (8 * (t & 3))) & 0xFFu;
+                const u32 cv = x == 'A' ? 0u : x == 'C' ? 1u : x == 'G' ? 2u : 3u;
+                const bool base = (x == 'A' || x == 'C' || x == 'G' || x == 'T') && ch * 16 + t < L;
+                c |= (base ? cv : 0u) << (30 - 2 * t);
+                b |= (base ? 0u : 1u) << t;
+            }
         }
         code[e] = c; brk[e] = b;
     }
@@ -153,13 +180,14 @@ __device__ __forceinline__ u64 km_window(unsigned __int128 x, int o, int k)
     return (u64)((x << (2 * o)) >> (128 - 2 * k));
 }
 
+template <bool NIB>
 __global__ __launch_bounds__(KM_THREADS) void km_count(KmerParams p)
 {
     extern __shared__ u32 km_lds[];
     const int E = p.rows_per_wg * p.cpr;
     u32* code = km_lds; u32* brk = km_lds + E;
     const int64_t row0 = (int64_t)blockIdx.x * p.rows_per_wg;
-    const int nr = km_load_chunks(p, row0, code, brk);
+    const int nr = km_load_chunks<NIB>(p, row0, code, brk);
     __syncthreads();
     if (__hip_atomic_load(p.status + ST_KMER, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != ~0ull) return;   // the table is full
     const u64 kmask = (1ull << p.k) - 1;
@@ -200,6 +228,7 @@ __device__ __forceinline__ u64 km_filter_or(u64* p, u64 mask)
     return (cur & mask) == mask ? cur : atomicOr(p, mask);
 }
 
+template <bool NIB>
 __global__ __launch_bounds__(KM_THREADS) void km_prefilter(KmerParams p, KmerFilterParams f)
 {
     extern __shared__ u32 km_lds[];
@@ -207,7 +236,7 @@ __global__ __launch_bounds__(KM_THREADS) void km_prefilter(KmerParams p, KmerFil
     u32* code = km_lds; u32* brk = km_lds + E; u32* adm = km_lds + 2 * E;
     const int64_t row0 = (int64_t)blockIdx.x * p.rows_per_wg;
     if (threadIdx.x == 0) *adm = 0;
-    const int nr = km_load_chunks(p, row0, code, brk);
+    const int nr = km_load_chunks<NIB>(p, row0, code, brk);
     __syncthreads();
     const u64 kmask = (1ull << p.k) - 1;
     u32 mine = 0;
@@ -229,13 +258,14 @@ __global__ __launch_bounds__(KM_THREADS) void km_prefilter(KmerParams p, KmerFil
 }
 
 // km_count of the windows whose mask is whole in `twice`
+template <bool NIB>
 __global__ __launch_bounds__(KM_THREADS) void km_count_filtered(KmerParams p, KmerFilterParams f)
 {
     extern __shared__ u32 km_lds[];
     const int E = p.rows_per_wg * p.cpr;
     u32* code = km_lds; u32* brk = km_lds + E;
     const int64_t row0 = (int64_t)blockIdx.x * p.rows_per_wg;
-    const int nr = km_load_chunks(p, row0, code, brk);
+    const int nr = km_load_chunks<NIB>(p, row0, code, brk);
     __syncthreads();
     if (__hip_atomic_load(p.status + ST_KMER, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != ~0ull) return;   // the table is full
     const u64 kmask = (1ull << p.k) - 1;
@@ -276,6 +306,7 @@ __device__ __forceinline__ bool km_solid(const KmerParams& p, u64 f)
     return km_lookup(p, km_canonical(f, p.k)) >= p.min_count;
 }
 
+template <bool NIB>
 __global__ __launch_bounds__(KM_THREADS) void km_correct(KmerParams p)
 {
     extern __shared__ u32 km_lds[];
@@ -283,7 +314,7 @@ __global__ __launch_bounds__(KM_THREADS) void km_correct(KmerParams p)
     u32* code = km_lds; u32* brk = km_lds + E; u32* sv = km_lds + 2 * E; u32* nchg = km_lds + 3 * E;
     const int64_t row0 = (int64_t)blockIdx.x * p.rows_per_wg;
     for (int i = threadIdx.x; i < p.rows_per_wg; i += KM_THREADS) nchg[i] = 0;
-    const int nr = km_load_chunks(p, row0, code, brk);
+    const int nr = km_load_chunks<NIB>(p, row0, code, brk);
     __syncthreads();
     const int k = p.k;
     const u64 kmask = (1ull << k) - 1;
@@ -312,10 +343,17 @@ __global__ __launch_bounds__(KM_THREADS) void km_correct(KmerParams p)
             V |= (u64)(w & 0xFFFFu) << (16 * i);
             S |= (u64)(w >> 16) << (16 * i);
         }
-        uint8_t* dst = p.out + (size_t)row * p.pitch + (size_t)ch * 16;
-        uint4 v = *reinterpret_cast<const uint4*>(p.seq + (size_t)row * p.pitch + (size_t)ch * 16);
+        constexpr int CB = NIB ? 8 : 16;                                  // bytes of a chunk in the plane
+        const size_t at = (size_t)row * p.pitch + (size_t)ch * CB;
+        u32 w[4] = {0, 0, 0, 0};                                         // the chunk as read: 4 words of characters, 2 of nibbles
+        if constexpr (NIB) {
+            const uint2 v = *reinterpret_cast<const uint2*>(p.seq + at);
+            w[0] = v.x; w[1] = v.y;
+        } else {
+            const uint4 v = *reinterpret_cast<const uint4*>(p.seq + at);
+            w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
+        }
         const u32 brk_own = brk[e];
-        u32 w[4] = {v.x, v.y, v.z, v.w};
         int changed = 0;
         bool have_words = false;
         unsigned __int128 xa = 0, xb = 0;                                // chunks ch - 2 .. ch + 1 and ch .. ch + 3
@@ -347,13 +385,18 @@ __global__ __launch_bounds__(KM_THREADS) void km_correct(KmerParams p)
                 else if (s[alt] == bs && bs > 0) tie = true;
             }
             if (best < 0 || tie) continue;
-            const u32 letter = best == 0 ? 'A' : best == 1 ? 'C' : best == 2 ? 'G' : 'T';
-            const int sh = 8 * (t & 3);
-            w[t >> 2] = (w[t >> 2] & ~(0xFFu << sh)) | (letter << sh);
+            if constexpr (NIB) {
+                const int sh = km_nib_shift(t & 7);
+                w[t >> 3] = (w[t >> 3] & ~(0xFu << sh)) | (km_nib_swap((u32)best) << sh);
+            } else {
+                const u32 letter = best == 0 ? 'A' : best == 1 ? 'C' : best == 2 ? 'G' : 'T';
+                const int sh = 8 * (t & 3);
+                w[t >> 2] = (w[t >> 2] & ~(0xFFu << sh)) | (letter << sh);
+            }
             ++changed;
         }
-        v.x = w[0]; v.y = w[1]; v.z = w[2]; v.w = w[3];
-        *reinterpret_cast<uint4*>(dst) = v;
+        if constexpr (NIB) *reinterpret_cast<uint2*>(p.out + at) = make_uint2(w[0], w[1]);
+        else *reinterpret_cast<uint4*>(p.out + at) = make_uint4(w[0], w[1], w[2], w[3]);
         if (changed) atomicAdd(&nchg[r], (u32)changed);
     }
     if (p.changed) {

@@ -190,6 +190,10 @@ PROTOTYPES = {
     'kbbq_kmer_count_filtered_dev': (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i]),
     'kbbq_kmer_prefilter': (_i, [_vp, _vp, _i, _vp, _vp, _i64, _i]),
     'kbbq_kmer_count_filtered': (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i]),
+    'kbbq_kmer_count_rows_dev': (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i]),
+    'kbbq_kmer_prefilter_rows_dev': (_i, [_vp, _vp, _i, _vp, _vp, _i64, _i, _i]),
+    'kbbq_kmer_count_filtered_rows_dev': (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i, _i]),
+    'kbbq_kmer_correct_rows_dev': (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _vp, _vp]),
 }
 
 

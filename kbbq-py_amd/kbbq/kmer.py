@@ -9,7 +9,9 @@ solid.  The rule, base by base, is in include/kbbq_hip.h; tests/kmer_model.py is
 
 Planes are [n, pitch] uint8 seq planes with uint32 meta words (length in bits 0..15).  NumPy arrays go through the host-buffer
 entry points (slab by slab through page-locked staging, any size); tensors on the GPU through the _dev ones.  There is no
-CPU fallback.
+CPU fallback.  count_batch / prefilter_batch / correct_batch take _device.ReadBatch / PairBatch objects instead, in any layout
+the recalibrate file path keeps reads in (4-bit planes, two reads to a row, rows grouped by read group), through the
+kbbq_kmer_*_rows_dev calls: `kbbq recalibrate -c` corrects its reads where they lie (recalibrate.recalibrate_corrected).
 
 Several ranks (one process per GPU under torch.distributed.run): every rank counts its own reads into a local table, sends each
 key to the rank that owns it (owner(), a hash of the key that shares no bits with its home slot) and merges what it receives
@@ -391,6 +393,80 @@ def correct_with(table, seq_plane, meta, min_count):
     N.check(lib.kbbq_kmer_correct(ctx.handle, table.handle, N.ptr(seq_plane), N.ptr(meta), n, pitch, int(min_count),
                                   N.ptr(out), N.ptr(changed)))
     return out, changed[:n]
+
+
+# ---- device batches in the recalibrate path's layouts ------------------------------------------------------------------------
+
+def batch_windows(batch, k):
+    """K-mer windows of a _device.ReadBatch / PairBatch of any layout (what sizes its table and filter).  A row of two reads
+    is counted as its two reads of S bases, not as the one row of 2S + 1 its sidecar describes."""
+    from . import _device as dev
+    if isinstance(batch, dev.PairBatch):
+        # an upper bound by one read for twin rows of an odd number of reads (the last row's second half is padding)
+        return 2 * batch.n * max(batch.S - int(k) + 1, 0)
+    if batch.n == 0:
+        return 0
+    return kmer_total(batch.meta[:batch.n].cpu().numpy().view(np.uint32), k)
+
+
+def _batch_rows(batch):
+    """(seq, meta, rows, pitch, KBBQ_ROWS_* flags) of a device batch for the kbbq_kmer_*_rows_dev calls."""
+    from . import _device as dev
+    return N.ptr(batch.seq), N.ptr(batch.meta), int(batch.n), int(batch.pitch), dev._row_flags(batch)
+
+
+def prefilter_batch(batch, k, filter=None, bits=4):
+    """prefilter_kmers for the rows of a device batch in whatever layout it has (layout_key() reads / reads_nib / pairs /
+    pairs_nib, twins, rows grouped by read group): the same `seen` words as the character planes of the same reads give."""
+    k = int(k)
+    if not 8 <= k <= 32:
+        raise ValueError('k must be in 8..32, got %d' % k)
+    if filter is None:
+        filter = KmerFilter(filter_words(batch_windows(batch, k), bits))
+    seq, meta, n, pitch, flags = _batch_rows(batch)
+    ctx = filter.ctx
+    N.check(N.load().kbbq_kmer_prefilter_rows_dev(ctx.handle, filter.handle, k, seq, meta, n, pitch, flags))
+    ctx.status()
+    return filter
+
+
+def count_batch(batch, k=31, table=None, slots=None, filter=None):
+    """count_kmers for the rows of a device batch in whatever layout it has: the reads are counted where they lie.  Keys and
+    counts are those of the character planes of the same reads, so batches of different layouts compose in one table."""
+    from . import _device as dev
+    if table is None:
+        if slots is None:
+            slots = default_slots(filter.admitted if filter is not None else batch_windows(batch, k), dev.device_budget())
+        table = KmerTable(k, slots)
+    seq, meta, n, pitch, flags = _batch_rows(batch)
+    lib = N.load()
+    ctx = table.ctx
+    try:
+        if filter is not None:
+            N.check(lib.kbbq_kmer_count_filtered_rows_dev(ctx.handle, table.handle, filter.handle, seq, meta, n, pitch, flags))
+        else:
+            N.check(lib.kbbq_kmer_count_rows_dev(ctx.handle, table.handle, seq, meta, n, pitch, flags))
+        ctx.status()
+    except N.KmerTableFull as exc:
+        raise _full(table, exc) from None
+    return table
+
+
+def correct_batch(table, batch, min_count):
+    """Correct the rows of a device batch against a counted table into batch.cseq (allocated here when the batch was made
+    without one) in the batch's own layout: K1 takes it as it is.  Returns `changed`, the changed bases per ROW as an int32
+    device array (a row of two reads counts both)."""
+    from . import _device as dev
+    T = dev._torch()
+    if batch.cseq is None:
+        batch.cseq = T.empty_like(batch.seq)
+    seq, meta, n, pitch, flags = _batch_rows(batch)
+    changed = T.empty((max(n, 1),), dtype=T.int32, device=batch.seq.device)
+    ctx = table.ctx
+    N.check(N.load().kbbq_kmer_correct_rows_dev(ctx.handle, table.handle, seq, meta, n, pitch, flags, int(min_count),
+                                                N.ptr(batch.cseq), N.ptr(changed)))
+    ctx.status()
+    return changed[:n]
 
 
 def _check_prefilter(min_count, filter_bits):

@@ -4,7 +4,8 @@ kbbq command line -- the `recalibrate` sub-command of the reference CLI
 and the `benchmark` sub-command (reference kbbq/main.py:26-89).  `plot` is out of scope here.
 `bqsr` (alignments -> GATK report) and `applybqsr` (report -> recalibrated SAM) are this build's own: the reference has the
 functions (kbbq/gatk/bqsr.py, applybqsr.py) but no command for them.  So is `correct` (k-mer error correction, kbbq/kmer.py):
-the reference's tutorial leaves that step to an external corrector.
+the reference's tutorial leaves that step to an external corrector; `recalibrate -c FASTQ` is `correct` and `recalibrate -f` in
+one run over one file (kbbq/recalibrate.py recalibrate_corrected).
 """
 import argparse
 
@@ -18,6 +19,12 @@ _ENDS_WITH_THE_COMMAND = False               # set by `python -m kbbq.main`: the
 def recalibrate(args):
     import os
     from . import parallel
+    kopts = None
+    if args.correct is not None:
+        kopts = dict(k=31 if args.kmer is None else args.kmer, min_count=args.min_count, slots=args.slots, prefilter=args.prefilter,
+                     filter_bits=4 if args.filter_bits is None else args.filter_bits)
+        # every rank of a launcher refuses here, before it joins the process group
+        _recal.check_corrected(args.correct, args.gatkreport, kopts['k'], kopts['min_count'], kopts['prefilter'], kopts['filter_bits'])
     world, _ = parallel.init_from_env()          # one process per GPU under torch.distributed.run; no-op otherwise
     if world == 1 and 'torch' not in __import__('sys').modules and not os.environ.get('KBBQ_USE_TORCH'):
         # one GPU: nothing of PyTorch is needed -- device memory, page-locked slabs, copies and events come from the library's
@@ -28,6 +35,16 @@ def recalibrate(args):
             # this process ends right after its last byte (_leave): what it holds goes with it instead of being returned piece by piece
             _hipmem.cuda.keep_released_memory(True)
             fastx.LEAVE_OPEN = True
+    if kopts is not None:
+        import sys
+        from ._trace import stage
+        with stage('[recalibrate_corrected, wall]'):
+            info = _recal.recalibrate_corrected(args.correct, infer_rg=args.infer_rg, gatkreport=args.gatkreport, output=args.output,
+                                                **kopts)
+        sys.stderr.write('kbbq recalibrate: k=%d min_count=%d reads=%d changed_bases=%d%s\n'
+                         % (info['k'], info['min_count'], info['reads'], info['changed_bases'],
+                            ' prefilter=1 admitted=%d slots=%d' % (info['admitted'], info['slots']) if kopts['prefilter'] else ''))
+        return
     _recal.recalibrate(bam=args.bam, fastq=args.fastq, infer_rg=args.infer_rg,
                        use_oq=args.use_oq, set_oq=args.set_oq, gatkreport=args.gatkreport, output=args.output)
 
@@ -84,6 +101,20 @@ def main(argv=None):
     src.add_argument('-b', '--bam', help='BAM to recalibrate')
     src.add_argument('-f', '--fastq', nargs=2,
                      help='FASTQ file to recalibrate and an error-corrected version of it.')
+    src.add_argument('-c', '--correct', metavar='FASTQ',
+                     help='FASTQ file to recalibrate against its own k-mer correction, made on the GPU in the same run (not in '
+                          'the reference): `kbbq correct` and `recalibrate -f` in one command, the same output, one GPU.')
+    rp.add_argument('-k', '--kmer', type=int, default=None, help='with -c: k-mer length, 8..32 (default 31)')
+    rp.add_argument('--min-count', type=int, default=None,
+                    help='with -c: k-mers seen at least this often are solid (default: the first valley of the count histogram)')
+    rp.add_argument('--slots', type=int, default=None,
+                    help='with -c: hash table slots, a power of two (default: every k-mer of the input at a load factor of 0.5, '
+                         'capped by what the device budget leaves beside the resident reads)')
+    rp.add_argument('--prefilter', action='store_true',
+                    help='with -c: keep most k-mers seen once out of the table (as `kbbq correct --prefilter`); needs '
+                         '--min-count >= 2 where given')
+    rp.add_argument('--filter-bits', type=int, default=None,
+                    help='with -c --prefilter: bits per k-mer of the input in each of the filter\'s two arrays, 1..64 (default 4)')
     rp.add_argument('-u', '--use-oq', action='store_true',
                     help='Use the OQ tag for quality scores (BAM input only).')
     rp.add_argument('-s', '--set-oq', action='store_true',
@@ -152,6 +183,11 @@ def main(argv=None):
     cp.set_defaults(command=correct)
 
     args = parser.parse_args(argv)
+    if args.command is recalibrate and args.correct is None:
+        given = [flag for flag, v in (('-k/--kmer', args.kmer), ('--min-count', args.min_count), ('--slots', args.slots),
+                                      ('--prefilter', args.prefilter or None), ('--filter-bits', args.filter_bits)) if v is not None]
+        if given:
+            rp.error('%s: only with -c/--correct' % ', '.join(given))
     args.command(args)
 
 

@@ -83,13 +83,20 @@ def world_rank():
     return 1, 0
 
 
+def launched_from_env():
+    """Would init_from_env join a process group?  A launcher's RANK with WORLD_SIZE > 1 (KBBQ_DIST_ALWAYS=1: join the group
+    even as its only rank -- the RCCL path on a one-GPU box).  Reads the environment only."""
+    import os
+    return 'RANK' in os.environ and (int(os.environ.get('WORLD_SIZE', '1')) > 1 or bool(os.environ.get('KBBQ_DIST_ALWAYS')))
+
+
 def init_from_env():
     """One process per GPU under torch.distributed.run: bind cuda:LOCAL_RANK and join the RCCL group
     (backend "nccl" is RCCL on ROCm; KBBQ_DIST_BACKEND=gloo lets several ranks share one GPU for
     rehearsals).  No-op outside a launcher or when already initialised."""
     import os
-    if 'RANK' not in os.environ or (int(os.environ.get('WORLD_SIZE', '1')) <= 1 and not os.environ.get('KBBQ_DIST_ALWAYS')):
-        return world_rank()                  # (KBBQ_DIST_ALWAYS=1: join the group even as its only rank -- the RCCL path on a one-GPU box)
+    if not launched_from_env():
+        return world_rank()
     import torch
     import torch.distributed as dist
     if dist.is_initialized():

@@ -50,11 +50,12 @@ def _vectors_from_tables(pos_errs, pos_total, dinuc_errs, dinuc_total, maxscore)
 LAST_RUN = {}            # what the most recent recalibrate_fastq did per length band (layouts, bytes uploaded): bench.py, traces
 
 
-def _tally_local(packed, minscore, maxscore):
+def _tally_local(packed, minscore, maxscore, band_rows=fastx.band_rows):
     """K1 over this rank's packed reads, length band by length band -> device Tables (zero tables when the rank has
     no reads).  Each band is tallied in the layout the packer wrote it in (fastx._fill_bands); whatever that path reports
     (bad input, a shape it does not serve) is redone one read per row, which carries the reference's exact error semantics.  The read index
-    of a kernel-reported error is made relative to the rank's first read."""
+    of a kernel-reported error is made relative to the rank's first read.  band_rows: what makes a band's one-read-per-row
+    batch for that redoing (recalibrate_corrected: fastx.band_rows, then the corrected plane from the k-mer table)."""
     if maxscore != 42:
         raise ValueError('the Q axis of the device tables is fixed at 43 (maxscore = 42)')
     R, S = max(packed['R'], 0), packed['S']
@@ -80,7 +81,7 @@ def _tally_local(packed, minscore, maxscore):
                 return
             except (IndexError, TypeError, ValueError, dev.N.LutNeedsCheckedApply):
                 band['laid'] = None          # bad input or an unsupported shape: the row-per-read kernel decides
-        dev.accumulate(fastx.band_rows(band), tables, minscore, **hints)
+        dev.accumulate(band_rows(band), tables, minscore, **hints)
 
     # several length bands (a mixed-length input, BASELINE config 5): ONE launch over all of them, each band on its share of
     # the workgroups (kbbq_accumulate_bands_dev); whatever any band's kernel reports sends them all band by band below, where
@@ -291,7 +292,6 @@ def _recalibrate_mapped(fastq, infer_rg, gatkreport, output, world, rank, shard,
             parallel.barrier()
     with stage('solve', sync=True):
         lut, shape = dev.solve_lut(tables)
-    R = shape[0]
     if packed is not None and packed['total'] == text.total:
         # pass 2 walks the same reads with the same first-appearance read groups (:141-148):
         # the planes of pass 1 are still on the device
@@ -307,7 +307,12 @@ def _recalibrate_mapped(fastq, infer_rg, gatkreport, output, world, rank, shard,
 
     if single.get('streamed'):
         return _emit_streamed(text, single, lut, shape, output, world, rank)
+    _apply_and_emit(text, single, lut, shape, output, world, rank)
 
+
+def _apply_and_emit(text, single, lut, shape, output, world, rank):
+    """Pass 2 over resident bands: K2 on every band of `single` in its layout, then the records of `text` to stdout or `output`."""
+    R = shape[0]
     if single['R'] != R:
         # pass 2 met read groups the model does not have (recalibrate.py:143-151: an IndexError at the first such read) or
         # fewer than it has: rows gathered by THEIR read-group segments do not fit the model's -- one read per row decides
@@ -359,6 +364,136 @@ def _recalibrate_mapped(fastq, infer_rg, gatkreport, output, world, rank, shard,
     else:
         with open(output if world == 1 else '%s.rank%04d' % (output, rank), 'wb') as sink:
             _egress.emit_records(text, single['first'], single['bands'], outs, sink=sink)
+
+
+TWO_COMMANDS = ('run the two commands instead: `kbbq correct -f reads.fq -o reads.cor.fq`, then '
+                '`kbbq recalibrate -f reads.fq reads.cor.fq`')
+
+
+def check_corrected(path, gatkreport=None, k=31, min_count=None, prefilter=False, filter_bits=4):
+    """What recalibrate_corrected refuses, before any device work and, under a launcher, before the process group exists."""
+    from . import kmer
+    if not 8 <= int(k) <= 32:
+        raise ValueError('k must be in 8..32, got %d' % int(k))
+    if min_count is not None and int(min_count) < 1:
+        raise ValueError('min_count must be >= 1, got %d' % int(min_count))
+    if parallel.launched_from_env() or kmer._ranks() is not None:
+        raise ValueError('recalibrate -c does not run across ranks yet (every rank would need the k-mers of all reads): '
+                         'on one GPU, or ' + TWO_COMMANDS + ', both of which run under a launcher')
+    if prefilter:
+        kmer._check_prefilter(min_count, filter_bits)
+    if fastx.is_sequential_input(path) or os.environ.get('KBBQ_SEQUENTIAL'):
+        raise ValueError('recalibrate -c keeps the reads on the device between correction and recalibration and takes inputs '
+                         'that can be mapped only (not pipes, standard input, KBBQ_SEQUENTIAL or .gz files of '
+                         'KBBQ_GZ_STREAM_BYTES and more): ' + TWO_COMMANDS)
+    if gatkreport is not None and os.path.exists(gatkreport):
+        raise ValueError('the report %s exists: its model replaces pass 1, so there is nothing to correct the reads for; '
+                         'give -f with the report, or the name of a report to write' % gatkreport)
+
+
+def recalibrate_corrected(path, infer_rg=False, gatkreport=None, output=None, k=31, min_count=None, slots=None, prefilter=False,
+                          filter_bits=4):
+    """`kbbq correct` and `kbbq recalibrate -f reads corrected` in one run over ONE file: the reads go to the device once, in
+    the layout pass 2 uses (fastx.pack_single), their k-mers are counted and the reads corrected where they lie
+    (kmer.count_batch / correct_batch: the corrected plane is each band's cseq), and the tally, the solve, the apply and the
+    writer run over the same resident planes.  Nothing is written or read between correction and recalibration.  The output
+    is, byte for byte, that of the two commands.  Returns info: k, min_count, hist, reads, changed_bases, slots (and
+    admitted with the prefilter).  gatkreport: the model of the tally is saved there; an existing report is refused.
+    One process, mapped inputs, reads that fit the device budget: anything else raises ValueError naming the two commands."""
+    check_corrected(path, gatkreport, k, min_count, prefilter, filter_bits)
+    done_with = []
+    try:
+        return _recalibrate_corrected(path, infer_rg, gatkreport, output, int(k), min_count, slots, prefilter, filter_bits, done_with)
+    finally:
+        for reader in done_with:
+            fastx.close_later(reader)
+
+
+def _batch_bytes(batch):
+    return sum(int(x.numel()) * int(x.element_size()) for x in (batch.seq, batch.cseq, batch.qual, batch.meta,
+                                                               getattr(batch, 'out_plane', None)) if x is not None)
+
+
+def _recalibrate_corrected(path, infer_rg, gatkreport, output, k, min_count, slots, prefilter, filter_bits, done_with):
+    from . import kmer
+    scan = fastx.PairScan(path, None, infer_rg)
+    _warm_up()
+    text = scan.result()[0]
+    done_with.append(text)
+    info = dict(k=k, min_count=int(min_count or 0), hist=np.zeros(kmer.HIST, dtype=np.int64), reads=int(text.n), changed_bases=0,
+                slots=0)
+    if prefilter:
+        info['admitted'] = 0
+    if text.n == 0:
+        return info
+    budget = dev.device_budget()
+    single = fastx.pack_single(text, infer_rg, None, bands=True, to_device=True, budget=budget)
+    if single.get('streamed'):
+        raise ValueError('%d reads of up to %d bases do not fit the device budget of %d bytes (KBBQ_DEVICE_BUDGET) and would be '
+                         'streamed, but recalibrate -c corrects the reads where they lie: ' % (single['n'], single['S'], budget)
+                         + TWO_COMMANDS)
+    rows = [b['laid'] if b.get('laid') is not None else b['batch'] for b in single['bands']]
+    windows = sum(kmer.batch_windows(r, k) for r in rows)
+    # what the planes hold once every band has its corrected plane beside the others
+    resident = sum(_batch_bytes(r) + (0 if r.cseq is not None else int(r.seq.numel())) for r in rows)
+    # ... and room for the one-read-per-row planes (seq, cseq, qual, sidecar) of the largest band a layout's kernel may refuse,
+    # which are made while the table is still there (corrected_rows below); pass 1 of `-f` redoes bands one at a time too
+    resident += max(int(b['n']) * (3 * int(b['pitch']) + 4) for b in single['bands'] if b.get('laid') is not None) \
+        if any(b.get('laid') is not None for b in single['bands']) else 0
+    table = filt = None
+    try:
+        try:
+            if prefilter:
+                with stage('k-mer prefilter', sync=True):
+                    filt = kmer.KmerFilter(kmer.filter_words(windows, filter_bits))
+                    for r in rows:
+                        kmer.prefilter_batch(r, k, filter=filt)
+                    info['admitted'] = filt.admitted
+                    filt.release_seen()
+            if slots is None:
+                slots = kmer.default_slots(info['admitted'] if prefilter else windows,
+                                           budget - resident - (filt.nbytes if filt is not None else 0))
+            with stage('k-mer count', sync=True):
+                table = kmer.KmerTable(k, slots)
+                for r in rows:
+                    kmer.count_batch(r, k, table=table, filter=filt)
+        except (ValueError, dev.N.KmerTableFull) as exc:
+            if 'slots' not in str(exc):
+                raise
+            raise type(exc)('%s -- the k-mer table shares the device budget (KBBQ_DEVICE_BUDGET) with %d bytes of resident reads: '
+                            'give --slots, or --prefilter for a table several times smaller' % (exc, resident)) from None
+        if filt is not None:
+            filt.close()
+            filt = None
+        info['slots'] = table.slots
+        info['hist'] = hist = kmer.kmer_histogram(table)
+        t = int(min_count) if min_count is not None else kmer.solid_threshold(hist)
+        info['min_count'] = t
+        with stage('k-mer correct', sync=True):
+            for r in rows:
+                info['changed_bases'] += int(kmer.correct_batch(table, r, t).cpu().numpy().astype(np.int64).sum())
+
+        def corrected_rows(band):
+            # a band whose layout the tally refuses is redone one character row per read; its corrected characters come from the
+            # character kernels on those rows, which is why the table lives until the tally is over
+            batch = fastx.band_rows(band)
+            if batch.cseq is None:
+                kmer.correct_batch(table, batch, t)
+            return batch
+        tables = _tally_local(single, 6, 42, band_rows=corrected_rows)
+    finally:
+        if filt is not None:
+            filt.close()
+        if table is not None:
+            table.close()
+    if tables is None:
+        raise IndexError('index 0 is out of bounds for axis 0 with size 0')   # no read was tallied
+    if gatkreport is not None:
+        save_model(tables, single['rg_to_int'], gatkreport)
+    with stage('solve', sync=True):
+        lut, shape = dev.solve_lut(tables)
+    _apply_and_emit(text, single, lut, shape, output, 1, 0)
+    return info
 
 
 def _prefetched(items, depth=1):
