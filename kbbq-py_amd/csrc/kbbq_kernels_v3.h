@@ -530,7 +530,97 @@ __device__ __forceinline__ void k1v3_body(const K1v3Params& p, u32* lds, const i
                 }
             };
 
-            if (total > 0) {
+            bool walk = total > 0;
+            if constexpr (NIB && KJ > 0) {
+                // A UNIFORM block: all 64 rows inside the slice, every meta word that of a complete pair of the launch's common
+                // length in read group g (from the meta load above and one ballot; wave-uniform) has its own loop.  What `fetch` / `process` work out per chunk is a constant here: the compaction
+                // is the identity (row slot = k, no bperm), every row has KJ chunks of which each holds counted bases
+                // (len = maxlen > 16 (KJ - 1); act, fits_tables: true), the pitch is 16 KJ bytes, so the chunk of lane l at
+                // step s is chunk 64 s + l of the block and its loads are 16 (8) bytes at 1024 (512) s + 16 (8) l.  What is
+                // left per chunk: j and k of the chunk that is binned (one of each: the steps are binned in order), the
+                // carry of the previous base, the data's own screens -- and the 16 bases.
+                static_assert((KJ & 1) != 0, "the loop below fetches steps in twos and bins the last one alone");
+                if (__ballot(myread < seg_hi && m == ((u32)p.maxlen | ((u32)g << 16))) == ~0ull) {
+                    walk = false;
+                    constexpr int DK = 64 / KJ, DJ = 64 - DK * KJ;
+                    int j4 = 4 * lane_j0, k = lane_k0;                   // 4 j: the chunk's word in a table row
+                    const u32 at = 16u * (u32)lane;
+                    auto fetch_u = [&](K1Chunk& ch, int s) {
+                        const u32 o = at + 1024u * (u32)s;
+                        const uint2 sv = *reinterpret_cast<const uint2*>(bseq + (o >> 1));
+                        const uint2 cv = *reinterpret_cast<const uint2*>(bcseq + (o >> 1));
+                        const uint4 qv = *reinterpret_cast<const uint4*>(bqual + o);
+                        ch.s[0] = sv.x; ch.s[1] = sv.y; ch.c[0] = cv.x; ch.c[1] = cv.y;
+                        ch.q[0] = qv.x; ch.q[1] = qv.y; ch.q[2] = qv.z; ch.q[3] = qv.w;
+                    };
+                    auto process_u = [&](const K1Chunk& ch) {
+                        u32 code[4], code5[4], xw[4], hiq = 0u;
+                        code[0] = nib_lo(ch.s[0]); code[1] = nib_hi(ch.s[0]); code[2] = nib_lo(ch.s[1]); code[3] = nib_hi(ch.s[1]);
+                        const u32 x0 = ch.s[0] ^ ch.c[0], x1 = ch.s[1] ^ ch.c[1];
+                        xw[0] = nib_lo(x0); xw[1] = nib_hi(x0); xw[2] = nib_lo(x1); xw[3] = nib_hi(x1);
+                        const u32 badbits = nib_invalid(ch.s[0]) | nib_invalid(ch.s[1]);
+#pragma unroll
+                        for (int wd = 0; wd < 4; ++wd) {
+                            code5[wd] = (code[wd] << 2) + code[wd];
+                            hiq |= (ch.q[wd] + 0x34343434u) | ch.q[wd];
+                        }
+                        hiq &= 0x80808080u;
+                        const u32 last_code5 = code5[3] >> 24;
+                        u32 prev_code5 = wave_shr1(last_code5, carry_code);
+                        carry_code = (u32)__builtin_amdgcn_readlane((int)last_code5, 63);
+                        if (j4 == 0) prev_code5 = 20u;
+                        if (hiq | badbits) {                                 // a flagged chunk reports what `process` reports and counts nothing
+                            if (hiq) flag(p.status, ST_INDEX, read0 + k);
+                            if (badbits) flag(p.status, ST_LUT, 0);
+                        } else {
+                            // the 16 bases, as `process` bins them (KJ > 0, not ALN)
+                            const u32 A = pos_base + (u32)j4;
+                            const u32 tcl = tclamp + (u32)(k & (ntrash - 1));
+                            const u32 (&qv)[4] = ch.q;
+                            u32 pc5 = prev_code5 << 24;
+#pragma unroll
+                            for (int wd = 0; wd < 4; ++wd) {
+                                const u32 pw5 = __builtin_amdgcn_alignbyte(code5[wd], pc5, 3);
+                                const u32 d5 = pw5 + code[wd];                    // 5*prev + cur per byte, <= 24
+                                pc5 = code5[wd];
+                                const u32 xwd = xw[wd];
+                                const u32 qn = ~qv[wd];
+                                const u32 zero = 0u, both = 0x10001u;
+                                auto one_base = [&](auto bsel) {
+                                    constexpr int b = decltype(bsel)::value;
+                                    const u32 qi = (qn >> (8 * b)) & 0xFFu;         // 255 - quality byte
+                                    const u32 tq = qi < tcl ? qi : tcl;            // below minscore (and padding): a trash row
+                                    const u32 inc = k1_increment<b>(xwd, zero, both);
+                                    const u32 a = __umul24(tq, row_bytes) + A + (u32)(4 * KJ * (4 * wd + b));
+                                    atomicAdd(reinterpret_cast<u32*>(reinterpret_cast<char*>(lds) + a), inc);   // recalibrate.py:116-117
+                                    u32 slot = (d5 >> (8 * b)) & 0xFFu;
+                                    if (SPLIT) slot = qi <= 255u - p.dlo ? slot : 24u;
+                                    const u32 ad = slot * (4u * DN) + tq * dnt_row + dnt_base;
+                                    __hip_atomic_fetch_add(reinterpret_cast<lds_u32*>(ad), inc, __ATOMIC_RELAXED,
+                                                           __HIP_MEMORY_SCOPE_WORKGROUP);          // recalibrate.py:118-119
+                                };
+                                one_base(std::integral_constant<int, 0>{}); one_base(std::integral_constant<int, 1>{});
+                                one_base(std::integral_constant<int, 2>{}); one_base(std::integral_constant<int, 3>{});
+                            }
+                        }
+                        const int jn = j4 + 4 * DJ;
+                        const bool wrap = jn >= 4 * KJ;
+                        j4 = wrap ? jn - 4 * KJ : jn;
+                        k += DK + (wrap ? 1 : 0);
+                    };
+                    K1Chunk ca, cb;
+                    fetch_u(ca, 0);
+#pragma unroll 1
+                    for (int s = 0; s + 1 < KJ; s += 2) {
+                        fetch_u(cb, s + 1);
+                        process_u(ca);
+                        fetch_u(ca, s + 2);
+                        process_u(cb);
+                    }
+                    process_u(ca);
+                }
+            }
+            if (walk) {
                 // one step in flight while the previous one is binned; fetches are unconditional
                 // (past the end they re-read the block's first chunk) so that the outstanding
                 // loads can be counted (s_waitcnt vmcnt(3)) instead of drained
