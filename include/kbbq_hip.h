@@ -706,6 +706,17 @@ int kbbq_ctx_kernel_ms(kbbq_ctx* ctx, int which, double* total_ms, int64_t* laun
  * when that number is >= 1 and strictly larger than for the other two; every base is judged against the read as given.  d_out
  * (16-byte aligned, the input's layout) receives the corrected plane, breaks and padding as read; d_changed (may be NULL) the
  * number of changed bases per read.
+ * N rule (kbbq correct --fix-n): kbbq_kmer_correct_ex_dev / kbbq_kmer_correct_ex / kbbq_kmer_correct_rows_ex_dev are the calls
+ * without _ex plus `int opts`, a word of KBBQ_KMER_* bits (not the KBBQ_ROWS_* flags); opts = 0 IS the call without _ex, an
+ * unknown bit returns KBBQ_E_ARG before anything is launched.  With KBBQ_KMER_FIX_N an 'N' at base i of a read (the character
+ * 'N' alone; lower case and other letters stay breaks and stay as read) is handled as follows.  Its candidate windows are the
+ * windows [s, s + k) with s <= i < s + k that lie inside the read and hold no other base outside A/C/G/T.  For each letter x of
+ * A C G T, count the candidate windows whose canonical k-mer, with x written at i and every other base as read, has a count
+ * >= min_count.  The N takes the letter with the strictly largest count if that count is >= 1; on a tie, or when no letter makes
+ * a solid k-mer, it stays N.  Everything is judged against the read as given: a fixed N validates no window for its neighbours,
+ * an untrusted A/C/G/T base beside an N is decided exactly as without the option (the N is a break for it), and the result does
+ * not depend on thread order.  A fixed N is a changed base in d_changed.  Counting, the prefilter, the histogram and the
+ * threshold know nothing of the option: an N is a break for them and the table is the same table.
  * kbbq_kmer_count / kbbq_kmer_correct: the same from host buffers, slab by slab through page-locked staging (KBBQ_STAGE_MB);
  * `changed` (host, may be NULL) receives the per-read counts.  The kernel launches are not timed by kbbq_ctx_timing.
  * Ranks (kbbq/kmer.py count_kmers_ranks): every rank counts its reads into a local table, sends each key to its owner and merges
@@ -731,6 +742,11 @@ int kbbq_kmer_correct_dev(kbbq_ctx* ctx, const kbbq_kmer_table* table, const uin
 int kbbq_kmer_count(kbbq_ctx* ctx, kbbq_kmer_table* table, const uint8_t* seq, const uint32_t* meta, int64_t nreads, int pitch);
 int kbbq_kmer_correct(kbbq_ctx* ctx, const kbbq_kmer_table* table, const uint8_t* seq, const uint32_t* meta, int64_t nreads,
                       int pitch, int min_count, uint8_t* out, uint32_t* changed);
+#define KBBQ_KMER_FIX_N 1
+int kbbq_kmer_correct_ex_dev(kbbq_ctx* ctx, const kbbq_kmer_table* table, const uint8_t* d_seq, const uint32_t* d_meta,
+                             int64_t nreads, int pitch, int min_count, uint8_t* d_out, uint32_t* d_changed, int opts);
+int kbbq_kmer_correct_ex(kbbq_ctx* ctx, const kbbq_kmer_table* table, const uint8_t* seq, const uint32_t* meta, int64_t nreads,
+                         int pitch, int min_count, uint8_t* out, uint32_t* changed, int opts);
 int kbbq_kmer_table_clear_dev(kbbq_ctx* ctx, kbbq_kmer_table* table);
 int kbbq_kmer_select_sizes_dev(kbbq_ctx* ctx, const kbbq_kmer_table* table, int nbuckets, uint32_t min_count, int64_t* h_sizes);
 int kbbq_kmer_select_dev(kbbq_ctx* ctx, const kbbq_kmer_table* table, int nbuckets, uint32_t min_count, const int64_t* h_offsets,
@@ -795,7 +811,12 @@ int kbbq_kmer_count_filtered(kbbq_ctx* ctx, kbbq_kmer_table* table, const kbbq_k
  * no window spans two reads.  The flags are checked as kbbq_accumulate_rows_dev checks them (TWINS only with PAIRS) and pitch
  * must be a multiple of 16, which every kbbq_pair_pitch is; d_changed is per ROW (a mate-pair row counts both mates).
  * Without KBBQ_ROWS_NIBBLES the calls ARE the character calls above on the same rows.  Grouping by read group only orders the
- * rows: d_seg / d_perm are not needed here.                                                                                */
+ * rows: d_seg / d_perm are not needed here.
+ * kbbq_kmer_correct_rows_ex_dev: kbbq_kmer_correct_rows_dev plus `opts` (KBBQ_KMER_FIX_N, above; `flags` keeps its meaning and its
+ * refusals).  On a 4-bit plane an N is code 4 inside the row's length, and a fixed one is stored as its letter's plane code.
+ * With KBBQ_ROWS_PAIRS the base at (length - 1) / 2 of a row is the separator of its two reads (an 'N' / code 4 too): it is
+ * never fixed, and since every window across it holds that break no N takes a letter from the other read.  The padding half
+ * of a twin row of one read is Ns beside Ns and stays as it is.                                                             */
 int kbbq_kmer_count_rows_dev(kbbq_ctx* ctx, kbbq_kmer_table* table, const uint8_t* d_seq, const uint32_t* d_meta, int64_t nrows,
                              int pitch, int flags);
 int kbbq_kmer_prefilter_rows_dev(kbbq_ctx* ctx, kbbq_kmer_filter* filter, int k, const uint8_t* d_seq, const uint32_t* d_meta,
@@ -804,6 +825,8 @@ int kbbq_kmer_count_filtered_rows_dev(kbbq_ctx* ctx, kbbq_kmer_table* table, con
                                       const uint32_t* d_meta, int64_t nrows, int pitch, int flags);
 int kbbq_kmer_correct_rows_dev(kbbq_ctx* ctx, const kbbq_kmer_table* table, const uint8_t* d_seq, const uint32_t* d_meta,
                                int64_t nrows, int pitch, int flags, int min_count, uint8_t* d_out, uint32_t* d_changed);
+int kbbq_kmer_correct_rows_ex_dev(kbbq_ctx* ctx, const kbbq_kmer_table* table, const uint8_t* d_seq, const uint32_t* d_meta,
+                                  int64_t nrows, int pitch, int flags, int min_count, uint8_t* d_out, uint32_t* d_changed, int opts);
 
 #ifdef __cplusplus
 }

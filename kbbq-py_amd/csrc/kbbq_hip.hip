@@ -2225,11 +2225,27 @@ int kbbq_kmer_histogram_dev(kbbq_ctx* c, const kbbq_kmer_table* t, uint64_t* d_h
     return KBBQ_OK;
 }
 
-static int kmer_correct_rows(kbbq_ctx* c, const char* who, const kbbq_kmer_table* t, const uint8_t* d_seq, const uint32_t* d_meta,
-                             int64_t n, int pitch, bool nib, int min_count, uint8_t* d_out, uint32_t* d_changed)
+// the `opts` word of the kbbq_kmer_correct*_ex calls (not the KBBQ_ROWS_* flags): checked before anything is launched
+static int kmer_correct_opts(const char* who, int opts)
 {
+    if (opts & ~KBBQ_KMER_FIX_N) return fail(KBBQ_E_ARG, "%s: unknown bits in opts 0x%x (KBBQ_KMER_FIX_N = %d)", who, opts, KBBQ_KMER_FIX_N);
+    return KBBQ_OK;
+}
+
+// km_correct's instantiations: [4-bit planes][KM_FIXN_*]
+static void (*const KM_CORRECT[2][3])(KmerParams) = {
+    {km_correct<false, KM_FIXN_OFF>, km_correct<false, KM_FIXN_READS>, km_correct<false, KM_FIXN_PAIRS>},
+    {km_correct<true, KM_FIXN_OFF>, km_correct<true, KM_FIXN_READS>, km_correct<true, KM_FIXN_PAIRS>},
+};
+
+// pairs: two reads to a row (KBBQ_ROWS_PAIRS), which the N rule alone needs to know -- their separator is no N
+static int kmer_correct_rows(kbbq_ctx* c, const char* who, const kbbq_kmer_table* t, const uint8_t* d_seq, const uint32_t* d_meta,
+                             int64_t n, int pitch, bool nib, bool pairs, int min_count, uint8_t* d_out, uint32_t* d_changed, int opts)
+{
+    int rc = kmer_correct_opts(who, opts);
+    if (rc) return rc;
     KmerParams p; size_t lds = 0;
-    int rc = kmer_geometry(c, who, t, d_seq, d_meta, n, pitch, p, 3, &lds, nib);
+    rc = kmer_geometry(c, who, t, d_seq, d_meta, n, pitch, p, 3, &lds, nib);
     if (rc) return rc;
     if (min_count < 1) return fail(KBBQ_E_ARG, "%s: min_count must be >= 1, got %d", who, min_count);
     if (n > 0 && (!d_out || ((uintptr_t)d_out & (nib ? 7 : 15))))
@@ -2237,25 +2253,45 @@ static int kmer_correct_rows(kbbq_ctx* c, const char* who, const kbbq_kmer_table
     if (n == 0) return KBBQ_OK;
     HIPCHK(hipSetDevice(c->device));
     p.min_count = (u32)min_count; p.out = d_out; p.changed = d_changed;
+    const auto kernel = KM_CORRECT[nib ? 1 : 0][!(opts & KBBQ_KMER_FIX_N) ? KM_FIXN_OFF : pairs ? KM_FIXN_PAIRS : KM_FIXN_READS];
     return kmer_launches(p, [&](const KmerParams& q, unsigned grid) {
-        if (nib) hipLaunchKernelGGL(km_correct<true>, dim3(grid), dim3(KM_THREADS), lds, c->stream, q);
-        else hipLaunchKernelGGL(km_correct<false>, dim3(grid), dim3(KM_THREADS), lds, c->stream, q);
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(KM_THREADS), lds, c->stream, q);
     });
+}
+
+int kbbq_kmer_correct_ex_dev(kbbq_ctx* c, const kbbq_kmer_table* t, const uint8_t* d_seq, const uint32_t* d_meta, int64_t n, int pitch,
+                             int min_count, uint8_t* d_out, uint32_t* d_changed, int opts)
+{
+    return kmer_correct_rows(c, "kbbq_kmer_correct_ex_dev", t, d_seq, d_meta, n, pitch, false, false, min_count, d_out, d_changed, opts);
 }
 
 int kbbq_kmer_correct_dev(kbbq_ctx* c, const kbbq_kmer_table* t, const uint8_t* d_seq, const uint32_t* d_meta, int64_t n, int pitch,
                           int min_count, uint8_t* d_out, uint32_t* d_changed)
 {
-    return kmer_correct_rows(c, "kbbq_kmer_correct_dev", t, d_seq, d_meta, n, pitch, false, min_count, d_out, d_changed);
+    return kmer_correct_rows(c, "kbbq_kmer_correct_dev", t, d_seq, d_meta, n, pitch, false, false, min_count, d_out, d_changed, 0);
+}
+
+static int kmer_correct_rows_flags(kbbq_ctx* c, const char* who, const kbbq_kmer_table* t, const uint8_t* d_seq, const uint32_t* d_meta,
+                                   int64_t nrows, int pitch, int flags, int min_count, uint8_t* d_out, uint32_t* d_changed, int opts)
+{
+    int rc = kmer_correct_opts(who, opts);
+    if (rc) return rc;
+    bool nib = false;
+    rc = kmer_row_flags(who, flags, &nib);
+    if (rc) return rc;
+    return kmer_correct_rows(c, who, t, d_seq, d_meta, nrows, pitch, nib, (flags & KBBQ_ROWS_PAIRS) != 0, min_count, d_out, d_changed, opts);
+}
+
+int kbbq_kmer_correct_rows_ex_dev(kbbq_ctx* c, const kbbq_kmer_table* t, const uint8_t* d_seq, const uint32_t* d_meta, int64_t nrows,
+                                  int pitch, int flags, int min_count, uint8_t* d_out, uint32_t* d_changed, int opts)
+{
+    return kmer_correct_rows_flags(c, "kbbq_kmer_correct_rows_ex_dev", t, d_seq, d_meta, nrows, pitch, flags, min_count, d_out, d_changed, opts);
 }
 
 int kbbq_kmer_correct_rows_dev(kbbq_ctx* c, const kbbq_kmer_table* t, const uint8_t* d_seq, const uint32_t* d_meta, int64_t nrows,
                                int pitch, int flags, int min_count, uint8_t* d_out, uint32_t* d_changed)
 {
-    bool nib = false;
-    int rc = kmer_row_flags("kbbq_kmer_correct_rows_dev", flags, &nib);
-    if (rc) return rc;
-    return kmer_correct_rows(c, "kbbq_kmer_correct_rows_dev", t, d_seq, d_meta, nrows, pitch, nib, min_count, d_out, d_changed);
+    return kmer_correct_rows_flags(c, "kbbq_kmer_correct_rows_dev", t, d_seq, d_meta, nrows, pitch, flags, min_count, d_out, d_changed, 0);
 }
 
 int kbbq_kmer_table_clear_dev(kbbq_ctx* c, kbbq_kmer_table* t)
@@ -2339,28 +2375,42 @@ int kbbq_kmer_count(kbbq_ctx* c, kbbq_kmer_table* t, const uint8_t* seq, const u
     });
 }
 
-int kbbq_kmer_correct(kbbq_ctx* c, const kbbq_kmer_table* t, const uint8_t* seq, const uint32_t* meta, int64_t n, int pitch,
-                      int min_count, uint8_t* out, uint32_t* changed)
+static int kmer_correct_host(kbbq_ctx* c, const char* who, const kbbq_kmer_table* t, const uint8_t* seq, const uint32_t* meta, int64_t n,
+                             int pitch, int min_count, uint8_t* out, uint32_t* changed, int opts)
 {
-    if (!c || !t) return fail(KBBQ_E_ARG, "kbbq_kmer_correct: NULL ctx or table");
-    if (n < 0 || pitch <= 0 || (pitch & 15)) return fail(KBBQ_E_ARG, "kbbq_kmer_correct: bad n/pitch");
-    if (n > 0 && (!seq || !meta || !out)) return fail(KBBQ_E_ARG, "kbbq_kmer_correct: NULL plane");
+    int orc = kmer_correct_opts(who, opts);
+    if (orc) return orc;
+    if (!c || !t) return fail(KBBQ_E_ARG, "%s: NULL ctx or table", who);
+    if (n < 0 || pitch <= 0 || (pitch & 15)) return fail(KBBQ_E_ARG, "%s: bad n/pitch", who);
+    if (n > 0 && (!seq || !meta || !out)) return fail(KBBQ_E_ARG, "%s: NULL plane", who);
     if (n == 0) return KBBQ_OK;
     HIPCHK(hipSetDevice(c->device));
     DevBuf dc;
     if (changed) HIPCHK(dc.alloc((size_t)n * 4));
     // a slab: seq | out | meta; the slabs run in order, `done` rows before this one
     int64_t done = 0;
-    int rc = stage_run(c, "kbbq_kmer_correct", {seq}, meta, out, n, pitch, [&](uint8_t* d, size_t plane, int64_t m) {
-        if (done + m > n) return fail(KBBQ_E_HIP, "kbbq_kmer_correct: more rows launched than given");
+    int rc = stage_run(c, who, {seq}, meta, out, n, pitch, [&](uint8_t* d, size_t plane, int64_t m) {
+        if (done + m > n) return fail(KBBQ_E_HIP, "%s: more rows launched than given", who);
         uint32_t* dch = changed ? (uint32_t*)dc.p + done : nullptr;
         done += m;
-        return kbbq_kmer_correct_dev(c, t, d, (const uint32_t*)(d + 2 * plane), m, pitch, min_count, d + plane, dch);
+        return kmer_correct_rows(c, who, t, d, (const uint32_t*)(d + 2 * plane), m, pitch, false, false, min_count, d + plane, dch, opts);
     });
     if (rc || !changed) return rc;
     HIPCHK(hipMemcpyAsync(changed, dc.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     return KBBQ_OK;
+}
+
+int kbbq_kmer_correct_ex(kbbq_ctx* c, const kbbq_kmer_table* t, const uint8_t* seq, const uint32_t* meta, int64_t n, int pitch,
+                         int min_count, uint8_t* out, uint32_t* changed, int opts)
+{
+    return kmer_correct_host(c, "kbbq_kmer_correct_ex", t, seq, meta, n, pitch, min_count, out, changed, opts);
+}
+
+int kbbq_kmer_correct(kbbq_ctx* c, const kbbq_kmer_table* t, const uint8_t* seq, const uint32_t* meta, int64_t n, int pitch,
+                      int min_count, uint8_t* out, uint32_t* changed)
+{
+    return kmer_correct_host(c, "kbbq_kmer_correct", t, seq, meta, n, pitch, min_count, out, changed, 0);
 }
 
 // ---- prefilter: k-mers seen once stay out of the table (kbbq_kmer.h) ----------------------------------------------------------

@@ -22,6 +22,14 @@
 // over the words of the base's own chunk and the two before it -- or when no valid window does.  Only untrusted A/C/G/T bases
 // look up the 3 x (covering windows) substituted k-mers.  Every base is judged against the read as read (no cascade).
 //
+// N rule (km_correct<NIB, FIXN != KM_FIXN_OFF>; include/kbbq_hip.h KBBQ_KMER_FIX_N): an 'N' (4-bit planes: code 4) inside the read
+// takes the letter that makes the most of its candidate windows solid -- the windows that cover it, lie inside the read and hold
+// no other break -- when that number is >= 1 and strictly the largest of the four.  Which of a chunk's breaks are Ns comes from
+// the chunk pass 3 has in registers anyway (it rewrites it), "no other break" from the break masks of chunks ch - 2 .. ch + 2
+// already in LDS: the form keeps nothing more there.  KM_FIXN_PAIRS: the rows hold two reads (KBBQ_ROWS_PAIRS), and the base
+// at (length - 1) / 2 is their separator, never an N.  Counting, the filter and the substitution rule see an N as the break
+// it is, fixed or not.
+//
 // Ranks (kbbq/kmer.py count_kmers_ranks): the owner of a canonical key among W ranks is km_owner(key, W), the high 32 bits of
 // the same mix taken of the key XOR a constant, scaled to 0..W-1.  It shares no bits with the home slot (km_hash(key) & mask),
 // so the keys one rank owns spread over all home slots of its table.  km_select_sizes / km_select_scatter sort the occupied
@@ -52,6 +60,7 @@ constexpr int KM_THREADS = 256;
 constexpr int KM_MAX_PROBES = 512;
 constexpr u64 KM_EMPTY = ~0ull;
 constexpr int KM_HIST = 257;          // h[c], c = 1..255; h[256]: count >= 256; h[0] stays 0
+constexpr int KM_FIXN_OFF = 0, KM_FIXN_READS = 1, KM_FIXN_PAIRS = 2;   // km_correct's N rule: off, one read a row, two reads a row
 
 struct KmerParams {
     const uint8_t* seq; const u32* meta; int64_t nrows; int pitch; int cpr; int rows_per_wg; int k;   // pitch: row stride, bytes
@@ -306,7 +315,18 @@ __device__ __forceinline__ bool km_solid(const KmerParams& p, u64 f)
     return km_lookup(p, km_canonical(f, p.k)) >= p.min_count;
 }
 
-template <bool NIB>
+// the 16 break masks of chunks ch .. ch + n - 1 of a row (n <= 8), chunk ch in the low bits; chunks past the row: all breaks
+__device__ __forceinline__ unsigned __int128 km_breaks(const KmerParams& p, const u32* brk, int e_row, int ch, int n)
+{
+    unsigned __int128 b = 0;
+    for (int i = 0; i < n; ++i) {
+        const int c = ch + i;
+        b |= (unsigned __int128)(c >= 0 && c < p.cpr ? brk[e_row + c] : 0xFFFFu) << (16 * i);
+    }
+    return b;
+}
+
+template <bool NIB, int FIXN = KM_FIXN_OFF>
 __global__ __launch_bounds__(KM_THREADS) void km_correct(KmerParams p)
 {
     extern __shared__ u32 km_lds[];
@@ -357,7 +377,58 @@ __global__ __launch_bounds__(KM_THREADS) void km_correct(KmerParams p)
         int changed = 0;
         bool have_words = false;
         unsigned __int128 xa = 0, xb = 0;                                // chunks ch - 2 .. ch + 1 and ch .. ch + 3
+        u32 ns = 0;                                                       // N rule: bit t, base t of the chunk is an N of the read
+        if constexpr (FIXN != KM_FIXN_OFF) {
+            #pragma unroll
+            for (int t = 0; t < 16; ++t) {
+                const bool n = NIB ? ((w[t >> 3] >> km_nib_shift(t & 7)) & 0xFu) == 4u : ((w[t >> 2] >> (8 * (t & 3))) & 0xFFu) == 'N';
+                ns |= (n ? 1u : 0u) << t;
+            }
+            ns &= brk_own;
+            if (ns) {                                                     // ... inside the read, and not the separator of two reads
+                const int L = (int)(p.meta[row] & 0xFFFFu), first = ch * 16;
+                ns &= L - first >= 16 ? 0xFFFFu : L > first ? (1u << (L - first)) - 1u : 0u;
+                const int sep = FIXN == KM_FIXN_PAIRS ? ((L - 1) >> 1) - first : -1;
+                if (sep >= 0 && sep < 16) ns &= ~(1u << sep);
+            }
+        }
         for (int t = 0; t < 16; ++t) {
+            if constexpr (FIXN != KM_FIXN_OFF) {
+                if ((ns >> t) & 1u) {
+                    if (!have_words) {
+                        u64 unused;
+                        xa = km_words(p, code, brk, r * p.cpr, ch - 2, 4, &unused);
+                        xb = km_words(p, code, brk, r * p.cpr, ch, 4, &unused);
+                        have_words = true;
+                    }
+                    const unsigned __int128 B = km_breaks(p, brk, r * p.cpr, ch - 2, 5);   // bit i: base 16 (ch - 2) + i
+                    const int pp = 32 + t;
+                    int s[4] = {0, 0, 0, 0};
+                    for (int j = pp - k + 1; j <= pp; ++j) {              // a candidate window: this N is its only break
+                        if (((u64)(B >> j) & kmask) != 1ull << (pp - j)) continue;
+                        const u64 f = j < 32 ? km_window(xa, j, k) : km_window(xb, j - 32, k);   // a break's code is 0
+                        #pragma unroll
+                        for (u32 x = 0; x < 4; ++x) s[x] += km_solid(p, f | (u64)x << (2 * (k - 1 - (pp - j)))) ? 1 : 0;
+                    }
+                    int best = -1, bs = 0; bool tie = false;
+                    #pragma unroll
+                    for (int x = 0; x < 4; ++x) {
+                        if (s[x] > bs) { bs = s[x]; best = x; tie = false; }
+                        else if (s[x] == bs && bs > 0) tie = true;
+                    }
+                    if (best < 0 || tie) continue;
+                    if constexpr (NIB) {
+                        const int sh = km_nib_shift(t & 7);
+                        w[t >> 3] = (w[t >> 3] & ~(0xFu << sh)) | (km_nib_swap((u32)best) << sh);
+                    } else {
+                        const u32 letter = best == 0 ? 'A' : best == 1 ? 'C' : best == 2 ? 'G' : 'T';
+                        const int sh = 8 * (t & 3);
+                        w[t >> 2] = (w[t >> 2] & ~(0xFFu << sh)) | (letter << sh);
+                    }
+                    ++changed;
+                    continue;
+                }
+            }
             if ((brk_own >> t) & 1u) continue;                            // a break: never changed
             const int pp = 32 + t;                                        // the base's index in the 48-bit window masks
             const u64 cover = kmask << (pp - k + 1);

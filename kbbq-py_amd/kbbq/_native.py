@@ -26,6 +26,7 @@ KBBQ_E_FULL = -9
 APPLY_CHECKED, APPLY_FAST = 0, 1
 ALIGNED_LUT, ALIGNED_F64 = 0, 1
 ROWS_PAIRS, ROWS_NIBBLES, ROWS_TWINS = 1, 2, 4
+KMER_FIX_N = 1                        # the `opts` word of the kbbq_kmer_correct*_ex calls
 
 NQ = 43
 NDINUC = 16
@@ -174,6 +175,8 @@ PROTOTYPES = {
     'kbbq_kmer_correct_dev': (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _vp, _vp]),
     'kbbq_kmer_count': (_i, [_vp, _vp, _vp, _vp, _i64, _i]),
     'kbbq_kmer_correct': (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _vp, _vp]),
+    'kbbq_kmer_correct_ex_dev': (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _vp, _vp, _i]),
+    'kbbq_kmer_correct_ex': (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _vp, _vp, _i]),
     'kbbq_kmer_table_clear_dev': (_i, [_vp, _vp]),
     'kbbq_kmer_select_sizes_dev': (_i, [_vp, _vp, _i, _c.c_uint32, _vp]),
     'kbbq_kmer_select_dev': (_i, [_vp, _vp, _i, _c.c_uint32, _vp, _vp, _vp]),
@@ -194,6 +197,7 @@ PROTOTYPES = {
     'kbbq_kmer_prefilter_rows_dev': (_i, [_vp, _vp, _i, _vp, _vp, _i64, _i, _i]),
     'kbbq_kmer_count_filtered_rows_dev': (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i, _i]),
     'kbbq_kmer_correct_rows_dev': (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _vp, _vp]),
+    'kbbq_kmer_correct_rows_ex_dev': (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _vp, _vp, _i]),
 }
 
 

@@ -5,7 +5,9 @@ The reference has no corrector of its own: its tutorial (docs/tutorials/recalibr
 external one and feeds its output to `kbbq recalibrate -f reads.fq reads.cor.fq`.  `kbbq correct` makes that file here:
 every k-mer of every read is counted exactly in a device hash table, the first valley of the count histogram is the solid
 threshold, and an untrusted base (no solid k-mer covers it) takes the one other base that makes the most covering k-mers
-solid.  The rule, base by base, is in include/kbbq_hip.h; tests/kmer_model.py is a CPU model of it.
+solid.  The rule, base by base, is in include/kbbq_hip.h; tests/kmer_model.py is a CPU model of it.  With `fix_n` (`kbbq correct
+--fix-n`) an N takes the letter that makes the most of the windows it alone breaks solid (the N rule of include/kbbq_hip.h;
+tests/kmer_fixn_model.py); counting and the threshold do not change.
 
 Planes are [n, pitch] uint8 seq planes with uint32 meta words (length in bits 0..15).  NumPy arrays go through the host-buffer
 entry points (slab by slab through page-locked staging, any size); tensors on the GPU through the _dev ones.  There is no
@@ -374,24 +376,26 @@ def solid_threshold(hist):
     raise ValueError('the k-mer count histogram has no valley in 2..255: give min_count')
 
 
-def correct_with(table, seq_plane, meta, min_count):
-    """(corrected plane, per-read changed-base counts uint32) of the rows against a counted table."""
+def correct_with(table, seq_plane, meta, min_count, fix_n=False):
+    """(corrected plane, per-read changed-base counts uint32) of the rows against a counted table.  fix_n: Ns are decided by the
+    N rule (KBBQ_KMER_FIX_N) and a fixed N counts as a changed base."""
     lib = N.load()
     ctx = table.ctx
     n, pitch = int(seq_plane.shape[0]), int(seq_plane.shape[1])
+    opts = N.KMER_FIX_N if fix_n else 0
     if _on_device(seq_plane):
         out = seq_plane.new_empty(seq_plane.shape)
         changed = seq_plane.new_empty((max(n, 1),), dtype=__import__('torch').int32)
-        N.check(lib.kbbq_kmer_correct_dev(ctx.handle, table.handle, N.ptr(seq_plane), N.ptr(meta), n, pitch, int(min_count),
-                                          N.ptr(out), N.ptr(changed)))
+        N.check(lib.kbbq_kmer_correct_ex_dev(ctx.handle, table.handle, N.ptr(seq_plane), N.ptr(meta), n, pitch, int(min_count),
+                                             N.ptr(out), N.ptr(changed), opts))
         ctx.status()
         return out, changed[:n]
     seq_plane = np.ascontiguousarray(seq_plane, dtype=np.uint8)
     meta = np.ascontiguousarray(meta, dtype=np.uint32)
     out = np.empty_like(seq_plane)
     changed = np.zeros(max(n, 1), dtype=np.uint32)
-    N.check(lib.kbbq_kmer_correct(ctx.handle, table.handle, N.ptr(seq_plane), N.ptr(meta), n, pitch, int(min_count),
-                                  N.ptr(out), N.ptr(changed)))
+    N.check(lib.kbbq_kmer_correct_ex(ctx.handle, table.handle, N.ptr(seq_plane), N.ptr(meta), n, pitch, int(min_count),
+                                     N.ptr(out), N.ptr(changed), opts))
     return out, changed[:n]
 
 
@@ -452,10 +456,11 @@ def count_batch(batch, k=31, table=None, slots=None, filter=None):
     return table
 
 
-def correct_batch(table, batch, min_count):
+def correct_batch(table, batch, min_count, fix_n=False):
     """Correct the rows of a device batch against a counted table into batch.cseq (allocated here when the batch was made
     without one) in the batch's own layout: K1 takes it as it is.  Returns `changed`, the changed bases per ROW as an int32
-    device array (a row of two reads counts both)."""
+    device array (a row of two reads counts both).  fix_n: the N rule, in every layout (a fixed N of a 4-bit plane is its
+    letter's code; the separator of a row of two reads is no N)."""
     from . import _device as dev
     T = dev._torch()
     if batch.cseq is None:
@@ -463,8 +468,8 @@ def correct_batch(table, batch, min_count):
     seq, meta, n, pitch, flags = _batch_rows(batch)
     changed = T.empty((max(n, 1),), dtype=T.int32, device=batch.seq.device)
     ctx = table.ctx
-    N.check(N.load().kbbq_kmer_correct_rows_dev(ctx.handle, table.handle, seq, meta, n, pitch, flags, int(min_count),
-                                                N.ptr(batch.cseq), N.ptr(changed)))
+    N.check(N.load().kbbq_kmer_correct_rows_ex_dev(ctx.handle, table.handle, seq, meta, n, pitch, flags, int(min_count),
+                                                   N.ptr(batch.cseq), N.ptr(changed), N.KMER_FIX_N if fix_n else 0))
     ctx.status()
     return changed[:n]
 
@@ -480,10 +485,11 @@ def _check_prefilter(min_count, filter_bits):
                          'once, so the filter belongs at the rank that owns the key; run on one GPU, or without the prefilter')
 
 
-def correct_reads(seq_plane, meta, k=31, min_count=None, slots=None, prefilter=False, filter_bits=4):
+def correct_reads(seq_plane, meta, k=31, min_count=None, slots=None, prefilter=False, filter_bits=4, fix_n=False):
     """Count, pick the threshold (min_count, else the histogram's first valley) and correct.  Returns (corrected plane in
     the input's layout and kind, info) with info = {'k', 'min_count', 'hist', 'changed' (per read), 'slots', 'table_bytes',
-    'prefilter', 'filter_bytes', 'admitted'}.  With `prefilter` a KmerFilter of `filter_bits` bits per k-mer window and array
+    'prefilter', 'filter_bytes', 'admitted', 'fix_n'}.  fix_n: Ns are decided by the N rule against the same table (the
+    prefilter only keeps keys of count 1 out, and the rule asks for count >= min_count >= 2 then).  With `prefilter` a KmerFilter of `filter_bits` bits per k-mer window and array
     keeps most k-mers seen once out of the table: the same plane, threshold and hist[2:]; hist[1] is the number of once-seen
     k-mers that got in; the table, unless `slots` is given, is sized from the filter's `admitted` after `seen` is freed;
     min_count must be >= 2.  filter_bytes is the filter's size during its pass (both arrays); admitted is None without."""
@@ -504,9 +510,9 @@ def correct_reads(seq_plane, meta, k=31, min_count=None, slots=None, prefilter=F
         t = int(min_count) if min_count is not None else solid_threshold(hist)
         if t < 1:
             raise ValueError('min_count must be >= 1, got %d' % t)
-        out, changed = correct_with(table, seq_plane, meta, t)
+        out, changed = correct_with(table, seq_plane, meta, t, fix_n=fix_n)
         return out, dict(k=table.k, min_count=t, hist=hist, changed=changed, slots=table.slots, table_bytes=table.nbytes,
-                         prefilter=bool(prefilter), filter_bytes=filter_bytes, admitted=admitted)
+                         prefilter=bool(prefilter), filter_bytes=filter_bytes, admitted=admitted, fix_n=bool(fix_n))
     finally:
         if filt is not None:
             filt.close()
@@ -514,14 +520,14 @@ def correct_reads(seq_plane, meta, k=31, min_count=None, slots=None, prefilter=F
             table.close()
 
 
-def correct_fastq(path, out, k=31, min_count=None, slots=None, local_slots=None, prefilter=False, filter_bits=4):
+def correct_fastq(path, out, k=31, min_count=None, slots=None, local_slots=None, prefilter=False, filter_bits=4, fix_n=False):
     """Correct every read of a FASTQ file (plain or .gz) and write '@' + name, the corrected sequence, '+' and the qualities
     as read to `out` (a path, or a text stream).  Returns correct_reads' info.  In a process group of several ranks (or of
     one with KBBQ_DIST_ALWAYS=1) this is correct_fastq_ranks, which has no prefilter."""
     if prefilter:
         _check_prefilter(min_count, filter_bits)
     if _ranks() is not None:
-        return correct_fastq_ranks(path, out, k=k, min_count=min_count, slots=slots, local_slots=local_slots)
+        return correct_fastq_ranks(path, out, k=k, min_count=min_count, slots=slots, local_slots=local_slots, fix_n=fix_n)
     from . import fastx
     fq = fastx.NativeFastq(path)
     try:
@@ -531,7 +537,8 @@ def correct_fastq(path, out, k=31, min_count=None, slots=None, local_slots=None,
         names = fq.names()
     finally:
         fq.close()
-    fixed, info = correct_reads(seq, meta, k=k, min_count=min_count, slots=slots, prefilter=prefilter, filter_bits=filter_bits)
+    fixed, info = correct_reads(seq, meta, k=k, min_count=min_count, slots=slots, prefilter=prefilter, filter_bits=filter_bits,
+                                fix_n=fix_n)
     text = fastx.format_fastq(names, fixed, qual, meta & 0xFFFF)
     if isinstance(out, str):
         with open(out, 'w', encoding='latin-1', newline='') as fh:
@@ -543,20 +550,20 @@ def correct_fastq(path, out, k=31, min_count=None, slots=None, local_slots=None,
     return info
 
 
-def main_correct(path, output=None, k=31, min_count=None, slots=None, local_slots=None, prefilter=False, filter_bits=4):
+def main_correct(path, output=None, k=31, min_count=None, slots=None, local_slots=None, prefilter=False, filter_bits=4, fix_n=False):
     """`kbbq correct`: the corrected FASTQ to `output` or stdout; the threshold and the changed bases to stderr (once, by rank
-    0, with the figures of all ranks); with the prefilter also the admitted k-mers and the table's slots."""
+    0, with the figures of all ranks); with fix_n ` fix_n=1`; with the prefilter also the admitted k-mers and the table's slots."""
     if prefilter:
         _check_prefilter(min_count, filter_bits)         # every rank refuses, before its first collective
     ranks = _ranks()
     if ranks is None:
         info = correct_fastq(path, output if output else sys.stdout, k=k, min_count=min_count, slots=slots,
-                             prefilter=prefilter, filter_bits=filter_bits)
+                             prefilter=prefilter, filter_bits=filter_bits, fix_n=fix_n)
         changed = int(np.asarray(info['changed'], dtype=np.int64).sum())
     else:
         try:
             info = correct_fastq_ranks(path, output if output else sys.stdout, k=k, min_count=min_count, slots=slots,
-                                       local_slots=local_slots)
+                                       local_slots=local_slots, fix_n=fix_n)
         except Exception as exc:
             if not getattr(exc, 'every_rank', False):
                 raise
@@ -569,8 +576,8 @@ def main_correct(path, output=None, k=31, min_count=None, slots=None, local_slot
         changed = info['changed_bases']
         if ranks[1] != 0:
             return info
-    sys.stderr.write('kbbq correct: k=%d min_count=%d reads=%d changed_bases=%d%s\n'
-                     % (info['k'], info['min_count'], info['reads'], changed,
+    sys.stderr.write('kbbq correct: k=%d min_count=%d reads=%d changed_bases=%d%s%s\n'
+                     % (info['k'], info['min_count'], info['reads'], changed, ' fix_n=1' if fix_n else '',
                         ' prefilter=1 admitted=%d slots=%d' % (info['admitted'], info['slots']) if prefilter else ''))
     return info
 
@@ -728,10 +735,11 @@ def _read_shard(path, rank, world):
     return names, seq, qual, meta
 
 
-def correct_fastq_ranks(path, out, k=31, min_count=None, slots=None, local_slots=None):
+def correct_fastq_ranks(path, out, k=31, min_count=None, slots=None, local_slots=None, fix_n=False):
     """correct_fastq on every rank of the process group: each rank reads, counts and corrects its own records and writes them
     to `out`.rankNNNN (`out` itself with one rank) or, for a stream, to `out` in rank order.  The threshold comes from the
-    global histogram; info carries this rank's per-read changes and the global 'reads' and 'changed_bases'."""
+    global histogram; info carries this rank's per-read changes and the global 'reads' and 'changed_bases'.  fix_n: every rank
+    decides its Ns against the gathered solid table at min_count = t, as one process would against the whole table."""
     from . import fastx
     from . import parallel
     world, rank = parallel.world_rank()
@@ -756,7 +764,7 @@ def correct_fastq_ranks(path, out, k=31, min_count=None, slots=None, local_slots
     table = solid_table(owned, t)
     fixed = changed = exc = None
     try:
-        fixed, changed = correct_with(table, seq, meta, t)
+        fixed, changed = correct_with(table, seq, meta, t, fix_n=fix_n)
     except Exception as e:                   # noqa: BLE001
         exc = e
     finally:
@@ -772,4 +780,4 @@ def correct_fastq_ranks(path, out, k=31, min_count=None, slots=None, local_slots
             out.write(text)
             out.flush()
         parallel.in_rank_order(write)
-    return dict(k=k, min_count=t, hist=hist, changed=changed, reads=reads, changed_bases=total)
+    return dict(k=k, min_count=t, hist=hist, changed=changed, reads=reads, changed_bases=total, fix_n=bool(fix_n))

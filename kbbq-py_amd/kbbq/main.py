@@ -23,6 +23,8 @@ def recalibrate(args):
     if args.correct is not None:
         kopts = dict(k=31 if args.kmer is None else args.kmer, min_count=args.min_count, slots=args.slots, prefilter=args.prefilter,
                      filter_bits=4 if args.filter_bits is None else args.filter_bits)
+        if args.fix_n:                           # without the flag the call is the one it was
+            kopts['fix_n'] = True
         # every rank of a launcher refuses here, before it joins the process group
         _recal.check_corrected(args.correct, args.gatkreport, kopts['k'], kopts['min_count'], kopts['prefilter'], kopts['filter_bits'])
     world, _ = parallel.init_from_env()          # one process per GPU under torch.distributed.run; no-op otherwise
@@ -41,8 +43,8 @@ def recalibrate(args):
         with stage('[recalibrate_corrected, wall]'):
             info = _recal.recalibrate_corrected(args.correct, infer_rg=args.infer_rg, gatkreport=args.gatkreport, output=args.output,
                                                 **kopts)
-        sys.stderr.write('kbbq recalibrate: k=%d min_count=%d reads=%d changed_bases=%d%s\n'
-                         % (info['k'], info['min_count'], info['reads'], info['changed_bases'],
+        sys.stderr.write('kbbq recalibrate: k=%d min_count=%d reads=%d changed_bases=%d%s%s\n'
+                         % (info['k'], info['min_count'], info['reads'], info['changed_bases'], ' fix_n=1' if kopts.get('fix_n') else '',
                             ' prefilter=1 admitted=%d slots=%d' % (info['admitted'], info['slots']) if kopts['prefilter'] else ''))
         return
     _recal.recalibrate(bam=args.bam, fastq=args.fastq, infer_rg=args.infer_rg,
@@ -85,7 +87,7 @@ def correct(args):
         from . import _device
         _device.use_native_memory()          # as `recalibrate` on one GPU: no torch import
     kmer.main_correct(args.fastq, output=args.output, k=args.kmer, min_count=args.min_count, slots=args.slots,
-                      local_slots=args.local_slots, prefilter=args.prefilter, filter_bits=args.filter_bits)
+                      local_slots=args.local_slots, prefilter=args.prefilter, filter_bits=args.filter_bits, fix_n=args.fix_n)
 
 
 def main(argv=None):
@@ -115,6 +117,9 @@ def main(argv=None):
                          '--min-count >= 2 where given')
     rp.add_argument('--filter-bits', type=int, default=None,
                     help='with -c --prefilter: bits per k-mer of the input in each of the filter\'s two arrays, 1..64 (default 4)')
+    rp.add_argument('--fix-n', action='store_true',
+                    help='with -c: give every N the letter that makes the most of the k-mers it alone breaks solid (as `kbbq '
+                         'correct --fix-n`)')
     rp.add_argument('-u', '--use-oq', action='store_true',
                     help='Use the OQ tag for quality scores (BAM input only).')
     rp.add_argument('-s', '--set-oq', action='store_true',
@@ -177,6 +182,9 @@ def main(argv=None):
                          '--min-count >= 2 where given; one GPU only (not under torch.distributed.run)')
     cp.add_argument('--filter-bits', type=int, default=4,
                     help='with --prefilter: bits per k-mer of the input in each of the filter\'s two arrays, 1..64 (default 4)')
+    cp.add_argument('--fix-n', action='store_true',
+                    help='give every N the letter (A, C, G or T) that makes the most of the k-mers it alone breaks solid; an N '
+                         'stays N on a tie or when no letter makes a solid k-mer; a fixed N counts as a changed base')
     cp.add_argument('-o', '--output', default=None,
                     help='Write the corrected FASTQ to this file instead of stdout; under torch.distributed.run every rank '
                          'writes FILE.rankNNNN, to be concatenated in rank order.')
@@ -185,7 +193,8 @@ def main(argv=None):
     args = parser.parse_args(argv)
     if args.command is recalibrate and args.correct is None:
         given = [flag for flag, v in (('-k/--kmer', args.kmer), ('--min-count', args.min_count), ('--slots', args.slots),
-                                      ('--prefilter', args.prefilter or None), ('--filter-bits', args.filter_bits)) if v is not None]
+                                      ('--prefilter', args.prefilter or None), ('--filter-bits', args.filter_bits),
+                                      ('--fix-n', args.fix_n or None)) if v is not None]
         if given:
             rp.error('%s: only with -c/--correct' % ', '.join(given))
     args.command(args)

@@ -7,7 +7,9 @@ the count and of the correct step, the table's slots and bytes, its distinct k-m
 With `--prefilter` a second leg on the same reads follows under the key "prefilter": km_prefilter into a fresh filter, `seen`
 released, a table sized from the filter's `admitted` (or `--prefilter-slots`), the filtered count, histogram and correct, each
 timed the same way, with the filter's bytes and the device bytes in use at their peak (kbbq_dev_mem_info, planes excluded)
-beside the plain leg's; the leg fails unless its threshold, hist[2:] and corrected plane equal the plain leg's."""
+beside the plain leg's; the leg fails unless its threshold, hist[2:] and corrected plane equal the plain leg's.
+With `--fix-n` every repetition also times kbbq_kmer_correct_ex_dev with KBBQ_KMER_FIX_N on the same table ("ms_correct_fix_n",
+"fixed_n"); `--n-rate` sets that share of the bases to N before anything is counted."""
 import argparse
 import ctypes
 import json
@@ -27,6 +29,8 @@ ap.add_argument('--reps', type=int, default=3)
 ap.add_argument('--prefilter', action='store_true', help='add the prefiltered leg')
 ap.add_argument('--filter-bits', type=int, default=4)
 ap.add_argument('--prefilter-slots', type=int, default=0, help='table slots of the prefiltered leg (default: from `admitted`)')
+ap.add_argument('--fix-n', action='store_true', help='also time the correct step with the N rule (KBBQ_KMER_FIX_N)')
+ap.add_argument('--n-rate', type=float, default=0.0, help='share of the bases set to N')
 args = ap.parse_args()
 
 import numpy as np
@@ -52,6 +56,8 @@ for lo in range(0, n, step):                         # slices: the index tensors
     err = torch.rand((m, L), device='cuda', generator=g) < args.err
     b = torch.where(err, (b + torch.randint(1, 4, (m, L), device='cuda', generator=g, dtype=torch.uint8)) % 4, b)
     seq[lo:lo + m, :L] = acgt[b.long()]
+    if args.n_rate > 0:
+        seq[lo:lo + m, :L].masked_fill_(torch.rand((m, L), device='cuda', generator=g) < args.n_rate, ord('N'))
 del genome
 meta = torch.full((n,), L, dtype=torch.int32, device='cuda')
 windows = n * max(L - k + 1, 0)
@@ -59,6 +65,7 @@ distinct = G + windows * args.err * k                  # the genome's k-mers and
 slots = args.slots or 1 << int(np.ceil(np.log2(distinct * 2)))
 out = torch.empty_like(seq)
 out2 = torch.empty_like(seq) if args.prefilter else None   # the prefiltered leg's plane, compared with the plain one
+out_n = torch.empty_like(seq) if args.fix_n else None     # the plane of the correct step with the N rule
 lib = N.load()
 
 
@@ -87,6 +94,8 @@ def timed(fn):
 res = {'reads': n, 'len': L, 'k': k, 'genome': G, 'err': args.err, 'slots': slots,
        'table_bytes': int(lib.kbbq_kmer_table_bytes(slots))}
 ms = {'count': [], 'histogram': [], 'correct': []}
+if args.fix_n:
+    ms['correct_fix_n'] = []
 dh = torch.zeros(257, dtype=torch.int64, device='cuda')
 for rep in range(args.reps + 1):
     base = rep_base()
@@ -100,9 +109,14 @@ for rep in range(args.reps + 1):
     t = kmer.solid_threshold(hist)
     x = timed(lambda: N.check(lib.kbbq_kmer_correct_dev(table.ctx.handle, table.handle, N.ptr(seq), N.ptr(meta), n, pitch, t,
                                                          N.ptr(out), None)))
+    if args.fix_n:
+        xn = timed(lambda: N.check(lib.kbbq_kmer_correct_ex_dev(table.ctx.handle, table.handle, N.ptr(seq), N.ptr(meta), n, pitch, t,
+                                                                N.ptr(out_n), None, N.KMER_FIX_N)))
     table.close()
     if rep:                                            # the first round is the warm-up
         ms['count'].append(c); ms['histogram'].append(h); ms['correct'].append(x)
+        if args.fix_n:
+            ms['correct_fix_n'].append(xn)
 res.update({'ms_' + key: round(float(np.median(v)), 3) for key, v in ms.items()})
 res['count_kmers_per_s'] = windows / (res['ms_count'] * 1e-3)
 res['correct_kmers_per_s'] = windows / (res['ms_correct'] * 1e-3)
@@ -110,6 +124,13 @@ res['distinct'] = int(hist.sum())
 res['load_factor'] = round(res['distinct'] / slots, 3)
 res['min_count'] = t
 res['changed_bases'] = int((out != seq).sum().item())
+res['ms_correct_all'] = [round(v, 3) for v in ms['correct']]
+if args.fix_n:
+    res['n_rate'] = args.n_rate
+    res['n_bases'] = int((seq[:, :L] == ord('N')).sum().item())
+    res['fixed_n'] = int(((out_n != seq) & (seq == ord('N'))).sum().item())
+    res['ms_correct_fix_n_all'] = [round(v, 3) for v in ms['correct_fix_n']]
+    assert torch.equal(out_n[seq != ord('N')], out[seq != ord('N')]), 'the N rule changed a base that is no N'
 if args.prefilter:
     from kbbq import _device as dev
     plain_out, plain_hist, plain_t = out, hist, t
