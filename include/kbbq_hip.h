@@ -25,7 +25,8 @@
  * `pitch` bytes per read, pitch a multiple of 16, rows 16-byte aligned.  Bytes
  * are the FASTQ characters (qual is phred+33).  Bytes at and beyond the read
  * length MUST be zero in the qual plane and SHOULD be 'N' in seq / cseq (any other
- * value is still handled correctly, through a slower exact check of that chunk).
+ * value is still handled correctly, through a slower exact check of that chunk -- or, on kbbq_apply_dev's fast route at one
+ * read group, through the KBBQ_APPLY_CHECKED re-run described at kbbq_apply).
  * One uint32 of metadata per read:
  *     bits  0..15  length          (<= pitch)
  *     bits 16..30  read-group id   (first-appearance order, recalibrate.py:59-64)
@@ -157,7 +158,10 @@ int kbbq_accumulate_band_dev(kbbq_ctx* ctx, const uint8_t* d_seq, const uint8_t*
  * the rows travel slab by slab through page-locked staging of the context's own -- host threads copy slab k + 1 while the
  * copy engine uploads slab k and the kernel runs on slab k - 1 -- so device memory is two slabs whatever the input's size
  * (KBBQ_STAGE_MB: staging bytes per slab, default 96 MB) and the call runs at the PCIe rate of its 3 planes.  A read the
- * kernel flags is reported with its index in the WHOLE input; nothing is added to the caller's arrays then.            */
+ * kernel flags is reported with its index in the WHOLE input; nothing is added to the caller's arrays then.  A read whose
+ * read-group id is >= R is KBBQ_E_INDEX here (the reference indexes the group axis, recalibrate.py:111-117); the "_dev" forms
+ * leave such a read uncounted without a status -- every read group walks the rows for its own reads -- so their callers keep
+ * ids below R (kbbq_meta_stats_dev reports the largest).                                                               */
 int kbbq_accumulate(kbbq_ctx* ctx, const uint8_t* seq, const uint8_t* cseq,
                     const uint8_t* qual, const uint32_t* meta,
                     int64_t nreads, int pitch, int R, int S2, int minscore,
@@ -199,7 +203,12 @@ int kbbq_apply_dev(kbbq_ctx* ctx, const uint8_t* d_seq, const uint8_t* d_qual,
                    const void* d_lut_blob, int mode, uint8_t* d_qual_out);
 /* Host-buffer form: LUT built on the host (kbbq_build_lut), rows through the same page-locked slabs as kbbq_accumulate --
  * upload of slab k + 1, kernel on slab k and download of slab k - 1 overlap (PCIe is full duplex).  On an error status the
- * read index is that of the WHOLE input and the contents of qual_out are unspecified.                                  */
+ * read index is that of the WHOLE input and the contents of qual_out are unspecified.
+ * KBBQ_E_LUT never reaches the caller of this form.  kbbq_apply_dev(KBBQ_APPLY_FAST) with ONE read group runs a kernel that
+ * only REPORTS rows it does not serve (a quality >= Qt, a letter outside ACGTN, a read longer than S2, a read group other than
+ * 0, a byte other than 'N' in the seq padding of a read's last 16-byte chunk) as KBBQ_E_LUT without a read index; a caller of
+ * kbbq_apply_dev re-runs with KBBQ_APPLY_CHECKED (kbbq/_device.py apply does), and kbbq_apply does so itself, over the whole
+ * input: the status is then KBBQ_OK with every row's output, or the reference's KBBQ_E_INDEX / KBBQ_E_TYPE with "read N".   */
 int kbbq_apply(kbbq_ctx* ctx, const uint8_t* seq, const uint8_t* qual, const uint32_t* meta,
                int64_t nreads, int pitch, int R, int Qt, int S2, int D, int minscore,
                const int64_t* meanq, const int64_t* rgdq, const int64_t* qdq,

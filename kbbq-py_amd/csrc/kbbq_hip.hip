@@ -734,8 +734,10 @@ int kbbq_apply_dev(kbbq_ctx* c, const uint8_t* d_seq, const uint8_t* d_qual, con
     const int Sb = row_lut_width(pitch, S2);
     const size_t full_bytes = (size_t)R * (33 + Qt) * full_lut_row_bytes(Sb);
     // one read group, rows as a caller holds them (one character row per read): the short-lived kernel through apply_rows when it
-    // serves them.  What it cannot serve (a foreign letter, q > 42, a read longer than the LUT) it reports as KBBQ_E_LUT: the
-    // caller's KBBQ_APPLY_CHECKED run decides, as for a LUT that is not range-safe.
+    // serves them.  What it cannot serve (a foreign letter, q > 42, a read longer than the LUT, a read group other than 0 -- and,
+    // because it screens whole 16-byte chunks, a byte other than 'N' in the sequence padding of a read's last chunk) it reports as
+    // KBBQ_E_LUT with no read index: a KBBQ_APPLY_CHECKED run over the same rows decides, as for a LUT that is not range-safe.
+    // Who re-runs: the caller of this entry point (kbbq/_device.py apply); kbbq_apply does it itself (stage_run's `exact`).
     if (mode == KBBQ_APPLY_FAST && R == 1 && Qt == KQ && !(S2 & 1) && S2 <= 65534
         && k2_tile_serves(c, 0, 0, R, false, pitch / 16, (size_t)(33 + KQ) * full_lut_row_bytes(Sb)))
         return apply_rows(c, "kbbq_apply_dev", d_seq, d_qual, d_meta, nreads, pitch, 0, R, S2, minscore, d_lut, nullptr, nullptr, d_out, 0, nullptr);
@@ -1890,8 +1892,15 @@ static int first_offender(kbbq_ctx* c, int64_t nreads, size_t slab, const std::f
 // upload's event) -> download (DOWNLOAD stream, behind the kernel's event).  Uploads and downloads are on different streams,
 // so slab k + 1 goes up while slab k's kernel runs and slab k's (or k - 1's) output comes back: both directions of PCIe busy
 // at once (with both on one in-order stream the order was strictly U k, K k, D k, U k + 1).
+// `exact` (optional): the launch's kernel may answer KBBQ_E_LUT -- rows its fast form does not serve, no read named.  The entry
+// point must not hand that to its caller: exact() switches `launch` to the form that decides (false: it already is that form)
+// and the WHOLE input runs again -- such rows are the rare case -- so that clean rows with odd padding get their output and bad
+// ones the reference's error with the read's index, here and slab by slab in first_offender.
+// `see_meta` (optional): called with every slab's sidecar words (words, first read, count) as the slab is staged.
 static int stage_run(kbbq_ctx* c, const char* who, std::initializer_list<const uint8_t*> in, const uint32_t* meta, uint8_t* out,
-                     int64_t n, int pitch, const std::function<int(uint8_t*, size_t, int64_t)>& launch, int64_t* bad_read = nullptr)
+                     int64_t n, int pitch, const std::function<int(uint8_t*, size_t, int64_t)>& launch, int64_t* bad_read = nullptr,
+                     const std::function<bool()>& exact = nullptr,
+                     const std::function<void(const uint32_t*, int64_t, int64_t)>& see_meta = nullptr)
 {
     const int planes = (int)in.size() + (out ? 1 : 0);
     const size_t slab = stage_slab_rows(pitch, planes, n);
@@ -1904,6 +1913,7 @@ static int stage_run(kbbq_ctx* c, const char* who, std::initializer_list<const u
         size_t at = 0;
         for (const uint8_t* p : in) { threaded_copy(h + at, p + off, nb); at += plane; }
         memcpy(h + o_meta, meta + lo, (size_t)m * 4);
+        if (see_meta) see_meta(reinterpret_cast<const uint32_t*>(h + o_meta), lo, m);   // the slab's words, just copied: while earlier slabs upload and run
     };
     auto upload = [&](int b, int64_t m, hipStream_t st) -> int {        // the input planes, then the meta words
         HIPCHK(hipMemcpyAsync(c->stage_dev[b], c->stage_host[b], o_out, hipMemcpyHostToDevice, st));
@@ -1944,9 +1954,15 @@ static int stage_run(kbbq_ctx* c, const char* who, std::initializer_list<const u
         }
         return KBBQ_OK;
     };
-    rc = pipelined();
-    if (rc) return stage_drain(c, rc);
-    rc = kbbq_ctx_status(c, nullptr);
+    for (int pass = 0; ; ++pass) {
+        k = 0;
+        rc = pipelined();
+        if (rc) return stage_drain(c, rc);
+        rc = kbbq_ctx_status(c, nullptr);
+        if (rc != KBBQ_E_LUT || pass || !exact || !exact()) break;
+        (void)stage_drain(c, rc);                                      // the fast run's last downloads: not the caller's rows
+        pending[0].m = pending[1].m = 0;
+    }
     if (rc == KBBQ_E_FULL) return stage_drain(c, rc);                  // the table, not a read: nothing to look for slab by slab
     if (rc) {
         // something was flagged: which read of the WHOLE input comes first?
@@ -1975,11 +1991,19 @@ int kbbq_accumulate(kbbq_ctx* c, const uint8_t* seq, const uint8_t* cseq, const 
     DevBuf dt;
     HIPCHK(dt.alloc(kbbq_tables_count(R, S2) * 8));
     HIPCHK(hipMemsetAsync(dt.p, 0, kbbq_tables_count(R, S2) * 8, c->stream));
+    // K1 gives each of the R read groups its own walk over the rows and never meets a read of any other group: the reference's
+    // IndexError for it (recalibrate.py:111-117 index the group axis) is found here, on every slab's sidecars as the slab is staged.
+    // A read the kernels flag before it comes first; the read itself comes before anything else about it (the group is indexed first).
+    int64_t stray = -1, bad = -1;
     // a slab: seq | cseq | qual | meta; when a read is flagged nothing reaches the caller's tables
     int rc = stage_run(c, "kbbq_accumulate", {seq, cseq, qual}, meta, nullptr, nreads, pitch, [&](uint8_t* d, size_t plane, int64_t m) {
         return kbbq_accumulate_dev(c, d, d + plane, d + 2 * plane, (const uint32_t*)(d + 3 * plane), m, pitch, R, S2, minscore, (int64_t*)dt.p);
+    }, &bad, nullptr, [&](const uint32_t* w, int64_t lo, int64_t m) {
+        if (stray >= 0 && stray < lo) return;
+        for (int64_t i = 0; i < m; ++i) if ((int)((w[i] >> 16) & 0x7FFFu) >= R) { if (stray < 0 || lo + i < stray) stray = lo + i; return; }
     });
-    if (rc) return rc;
+    if (rc && (stray < 0 || bad < 0 || bad < stray)) return rc;
+    if (stray >= 0) return fail(KBBQ_E_INDEX, "read %lld: quality/read-group/cycle beyond the tables (reference: IndexError)", (long long)stray);
     std::vector<int64_t> h(kbbq_tables_count(R, S2));
     HIPCHK(hipMemcpyAsync(h.data(), dt.p, h.size() * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -2004,11 +2028,12 @@ int kbbq_apply(kbbq_ctx* c, const uint8_t* seq, const uint8_t* qual, const uint3
     DevBuf dl;
     HIPCHK(dl.alloc(lut.size() * 8));
     HIPCHK(hipMemcpyAsync(dl.p, lut.data(), lut.size() * 8, hipMemcpyHostToDevice, c->stream));
-    const int mode = flags ? KBBQ_APPLY_CHECKED : KBBQ_APPLY_FAST;
-    // a slab: seq | qual | out | meta (the output plane travels back from the same device slab)
+    int mode = flags ? KBBQ_APPLY_CHECKED : KBBQ_APPLY_FAST;
+    // a slab: seq | qual | out | meta (the output plane travels back from the same device slab).  Rows the fast kernel of one read
+    // group only reports (kbbq_apply_dev) run again in checked mode: the caller sees their output or the reference's error, never KBBQ_E_LUT
     return stage_run(c, "kbbq_apply", {seq, qual}, meta, qual_out, nreads, pitch, [&](uint8_t* d, size_t plane, int64_t m) {
         return kbbq_apply_dev(c, d, d + plane, (const uint32_t*)(d + 3 * plane), m, pitch, R, Qt, S2, minscore, dl.p, mode, d + 2 * plane);
-    });
+    }, nullptr, [&]() { const bool was_fast = mode == KBBQ_APPLY_FAST; mode = KBBQ_APPLY_CHECKED; return was_fast; });
 }
 
 // ---- ApplyBQSR on aligned rows (kbbq_apply_aligned.h) -----------------------------------------------------------------------

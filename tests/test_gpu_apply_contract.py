@@ -1,0 +1,465 @@
+"""
+The public contract of the apply / accumulate entry points at ONE read group (-m gpu).
+
+With one read group kbbq_apply_dev(KBBQ_APPLY_FAST) runs the short-lived tile kernel (csrc/kbbq_k2_tile.h, k2t_apply<false>): the
+route of the default case -- no --infer-rg, one read per character row.  That kernel only REPORTS rows it does not serve
+(KBBQ_E_LUT, no read index) and screens whole 16-byte chunks, the padding of a read's last chunk included.  These tests pin
+what a caller of kbbq_apply, kbbq_accumulate and compare_reads.recalibrate_fastq sees on that route, on the persistent kernel
+at one read group (KBBQ_K2_TILE=0) and at several read groups (the control):
+
+  1. clean rows: the oracle's bytes, at the row counts that reach the tile kernel's XCD remap, its remainder and its clamped loads;
+  2. bad rows: the exception the oracle raises, "read N" of the whole input, nothing added to the caller's tables, a clean status
+     afterwards -- never LutNeedsCheckedApply;
+  3. bytes of seq / cseq beyond a read's length do not matter (qual stays zero there, as include/kbbq_hip.h requires).
+
+Every expectation is the oracle's (oracle.accumulate, oracle.get_delta_qs, oracle.apply) or a NumPy statement of the contract.
+"""
+import os
+import re
+
+import numpy as np
+import pytest
+
+from conftest import ROOT
+
+pytestmark = pytest.mark.gpu
+
+MINSCORE = 6
+# csrc/kbbq_k2_tile.h: a workgroup of K2T_THREADS threads = 16 waves, every wave takes K2T_STEPS steps of 64 chunks (one per lane).
+# Read out of the header, so that ROWS is re-examined (test_row_counts_reach_the_tile_kernels_geometry) when they change.
+with open(os.path.join(ROOT, 'kbbq-py_amd', 'csrc', 'kbbq_k2_tile.h')) as _fh:
+    K2T_THREADS, K2T_STEPS = (int(re.search(r'^#define %s (\d+)' % k, _text, re.M).group(1))
+                              for _text in [_fh.read()] for k in ('K2T_THREADS', 'K2T_STEPS'))
+WAVE_CHUNKS = 64 * K2T_STEPS                              # 256 chunks of 16 bytes per wave
+WG_CHUNKS = (K2T_THREADS // 64) * WAVE_CHUNKS             # 4096 chunks per workgroup
+PITCHES = [16, 32, 48, 160, 304]
+# rows per pitch.  32: 16384 + 2048 * 3 + 37 rows = 8 whole workgroups (the XCD remap), 3 more whole ones and 74 chunks of a
+# twelfth (tiles % 8 = 4: the workgroups that keep their tiles; its first wave is partly, the other 15 wholly past the end).
+# 160: 4506 rows = 45060 chunks = 11 workgroups and 4 chunks (tiles = 12 again).  48 and 304: fewer than 8 workgroups (no
+# remap at all: 3 and 5 tiles).  16: one chunk a row, which k2_tile_serves sends to the persistent kernel.
+ROWS = {16: 700, 32: 16384 + 2048 * 3 + 37, 48: 3000, 160: 4506, 304: 1000}
+
+
+@pytest.fixture(scope='module')
+def dev():
+    import torch
+    assert torch.cuda.is_available(), 'these tests need the MI355X'
+    from kbbq import _device
+    ctx = _device.context()
+    assert 'gfx950' in ctx.name
+    return _device
+
+
+def _inside(meta, pitch):
+    return np.arange(pitch)[None, :] < (meta & 0xFFFF).astype(np.int64)[:, None]
+
+
+def _mixed_planes(seed, n, pitch, R):
+    """Hand-made rows: lengths 1..pitch with every multiple of 16 and L == pitch among them, qualities 0..42 (those below
+    minscore pass through), about half the reads second in pair, N bases, 5 % corrected sites; 'N' / 0 beyond the length.
+    Lengths are NON-DECREASING: the reference (and the oracle) refuse a read shorter than one before it (recalibrate.py:89-101).
+    For the same reason length 0, which the oracle accepts, can only stand in front: the first three rows are empty."""
+    rng = np.random.default_rng(seed)
+    lens = rng.integers(1, pitch + 1, n)
+    lens[:pitch // 16] = 16 * np.arange(1, pitch // 16 + 1)
+    lens[pitch // 16:pitch // 16 + 3] = 0
+    lens[-5:] = pitch
+    lens.sort()
+    inside = np.arange(pitch)[None, :] < lens[:, None]
+    acgt = np.frombuffer(b'ACGT', dtype=np.uint8)
+    seq = acgt[rng.integers(0, 4, (n, pitch))]
+    seq[rng.random((n, pitch)) < 0.03] = ord('N')
+    cseq = seq.copy()
+    e = rng.random((n, pitch)) < 0.05
+    cseq[e] = acgt[rng.integers(0, 4, int(e.sum()))]
+    qual = (33 + rng.integers(0, 43, (n, pitch))).astype(np.uint8)
+    seq[~inside] = ord('N'); cseq[~inside] = ord('N'); qual[~inside] = 0
+    meta = (lens.astype(np.uint32) | (rng.integers(0, R, n).astype(np.uint32) << np.uint32(16))
+            | ((rng.random(n) < 0.5).astype(np.uint32) << np.uint32(31)))
+    return seq, cseq, qual, meta
+
+
+_cases = {}
+
+
+def _case(oracle, pitch, R):
+    """Rows of this pitch, the oracle's tables and model for them and the oracle's new qualities: computed once, never changed."""
+    key = (pitch, R)
+    if key not in _cases:
+        n = ROWS[pitch] if R == 1 else min(ROWS[pitch], 1500)
+        seq, cseq, qual, meta = _mixed_planes(1000 * R + pitch, n, pitch, R)
+        want = oracle.accumulate(seq, cseq, qual, meta, R, pitch, minscore=MINSCORE)
+        dqs = oracle.get_delta_qs(*want)
+        ref = oracle.apply(seq, qual, meta, want[0], *dqs, minscore=MINSCORE)
+        for a in (seq, cseq, qual, meta, ref) + tuple(want) + tuple(dqs):
+            a.setflags(write=False)
+        _cases[key] = dict(n=n, pitch=pitch, R=R, S2=2 * pitch, seq=seq, cseq=cseq, qual=qual, meta=meta, want=want, dqs=dqs,
+                           ref=ref, inside=_inside(meta, pitch))
+    return _cases[key]
+
+
+def _model_args(meanq, dqs):
+    return [np.ascontiguousarray(x, dtype=np.int64) for x in (meanq,) + tuple(dqs)]
+
+
+def _host_apply(dev, seq, qual, meta, model, fill=0xEE):
+    """kbbq_apply on host planes; model = the five int64 arrays."""
+    from kbbq import _native as N
+    R, Qt, S2 = model[3].shape
+    out = np.full_like(qual, fill)
+    N.check(N.load().kbbq_apply(dev.context().handle, N.ptr(seq), N.ptr(qual), N.ptr(meta), seq.shape[0], seq.shape[1], R, Qt, S2,
+                                model[4].shape[2], MINSCORE, *[N.ptr(x) for x in model], N.ptr(out)))
+    return out
+
+
+def _host_accumulate(dev, seq, cseq, qual, meta, R, S2, tabs=None):
+    from kbbq import _native as N
+    if tabs is None:
+        tabs = [np.zeros((R, 43, S2), np.int64), np.zeros((R, 43, S2), np.int64), np.zeros((R, 43, 16), np.int64), np.zeros((R, 43, 16), np.int64)]
+    N.check(N.load().kbbq_accumulate(dev.context().handle, N.ptr(seq), N.ptr(cseq), N.ptr(qual), N.ptr(meta), seq.shape[0], seq.shape[1],
+                                     R, S2, MINSCORE, *[N.ptr(t) for t in tabs]))
+    return tabs
+
+
+# ------------------------------------------------------------------ 1. clean rows on the tile route
+def test_row_counts_reach_the_tile_kernels_geometry():
+    """The NumPy statement of what ROWS is chosen for (csrc/kbbq_k2_tile.h k2t_body: `tiles -= tiles % 8`, the clamped loads)."""
+    deep = 0
+    for pitch, n in ROWS.items():
+        chunks = n * (pitch // 16)
+        tiles = -(-chunks // WG_CHUNKS)
+        if tiles >= 9 and 1 <= tiles % 8 <= 7 and chunks % WAVE_CHUNKS and chunks % WG_CHUNKS < WAVE_CHUNKS:
+            deep += 1                # 8 whole workgroups, a remainder of workgroups, a last wave partly past the end
+    assert deep >= 2 and ROWS[32] * 2 == 8 * WG_CHUNKS + 3 * WG_CHUNKS + 74
+
+
+@pytest.mark.parametrize('pitch', PITCHES)
+def test_one_read_group_apply_matches_oracle(dev, oracle, pitch, monkeypatch):
+    """kbbq_apply (host planes) and dev.apply on a ReadBatch (device planes) at R = 1, base for base against oracle.apply with the
+    model oracle.accumulate / get_delta_qs give for the same rows: on the tile route, on the persistent kernel (KBBQ_K2_TILE=0)
+    and in KBBQ_APPLY_CHECKED mode."""
+    from kbbq import _native as N
+    c = _case(oracle, pitch, 1)
+    model = _model_args(c['want'][0], c['dqs'])
+    lut, shape = dev.build_lut(*model, minscore=MINSCORE)
+    assert shape == (1, 43, 2 * pitch, N.APPLY_FAST)             # a range-safe LUT: kbbq_apply and dev.apply start in fast mode
+    d_lut = dev.lut_to_device(lut)
+    batch = dev.ReadBatch.from_host(c['seq'], c['qual'], c['meta'])
+    ins, want = c['inside'], c['ref'][c['inside']]
+    assert (c['qual'][ins] < 33 + MINSCORE).any() and (c['meta'] >> 31).sum() > c['n'] // 4
+    for env in ({}, {'KBBQ_K2_TILE': '0'}):
+        for k, v in env.items():
+            monkeypatch.setenv(k, v)
+        out = _host_apply(dev, c['seq'], c['qual'], c['meta'], model)
+        assert np.array_equal(out[ins].astype(np.int32) - 33, want), ('kbbq_apply', env)
+        d_out = dev.apply(batch, d_lut, shape, minscore=MINSCORE)[:c['n']].cpu().numpy()
+        assert np.array_equal(d_out[ins].astype(np.int32) - 33, want), ('dev.apply', env)
+        assert not d_out[~ins].any()
+        for k in env:
+            monkeypatch.delenv(k)
+    chk = dev.apply(batch, d_lut, shape[:3] + (N.APPLY_CHECKED,), minscore=MINSCORE)[:c['n']].cpu().numpy()
+    assert np.array_equal(chk[ins].astype(np.int32) - 33, want), 'checked mode'
+    dev.context().status()
+
+
+def _stage_slabs(n, pitch, mb):
+    """Slabs kbbq_apply moves n rows in (csrc/kbbq_hip.hip stage_slab_rows: seq, qual and out planes + the sidecar word a row)."""
+    rows = max(((mb << 20) // (pitch * 3 + 4)) // 64 * 64, 64)
+    return -(-n // min(rows, n))
+
+
+@pytest.mark.parametrize('pitch', PITCHES)
+def test_clean_rows_are_served_by_one_fast_launch(dev, oracle, pitch, monkeypatch):
+    """The callers above re-run in checked mode when the fast kernel reports KBBQ_E_LUT, so their bytes do not show WHICH kernel
+    gave them.  Here without that net: one fast launch of kbbq_apply_dev (dev.apply, check=False) leaves a clean status and the
+    oracle's bytes -- the tile kernel flags no clean row, whatever the XCD remap, the clamped loads and the chunk-wide screen do --
+    and kbbq_apply launches K2 once per slab, not twice.  That the launch IS the tile kernel from two chunks a row on shows on a
+    bad quality: the tile kernel only reports it (LutNeedsCheckedApply on the status), the persistent kernel -- one chunk a
+    row, or KBBQ_K2_TILE=0 -- names the read as the reference does (include/kbbq_hip.h, kbbq_apply_dev)."""
+    from kbbq import _native as N
+    c = _case(oracle, pitch, 1)
+    model = _model_args(c['want'][0], c['dqs'])
+    lut, shape = dev.build_lut(*model, minscore=MINSCORE)
+    assert shape[3] == N.APPLY_FAST
+    d_lut = dev.lut_to_device(lut)
+    ctx = dev.context()
+    ins, want = c['inside'], c['ref'][c['inside']]
+    batch = dev.ReadBatch.from_host(c['seq'], c['qual'], c['meta'])
+    ctx.status()
+    ctx.kernel_ms(1, reset=True); ctx.timing(True)
+    out = dev.apply(batch, d_lut, shape, minscore=MINSCORE, check=False)
+    ctx.timing(False)
+    ctx.status()                                                       # nothing flagged, nothing to re-run
+    assert ctx.kernel_ms(1, reset=True)[1] == 1
+    assert np.array_equal(out[:c['n']].cpu().numpy()[ins].astype(np.int32) - 33, want)
+    for mb in (96, 1):
+        monkeypatch.setenv('KBBQ_STAGE_MB', str(mb))
+        ctx.timing(True)
+        got = _host_apply(dev, c['seq'], c['qual'], c['meta'], model)
+        ctx.timing(False)
+        assert ctx.kernel_ms(1, reset=True)[1] == _stage_slabs(c['n'], pitch, mb), mb
+        assert np.array_equal(got[ins].astype(np.int32) - 33, want), mb
+    assert _stage_slabs(ROWS[32], 32, 1) == 3 and _stage_slabs(ROWS[160], 160, 1) == 3
+    # which kernel: a quality of 43 in the last read (its length is the pitch)
+    bad = c['qual'].copy()
+    bad[-1, pitch - 1] = 33 + 43
+    bad_batch = dev.ReadBatch.from_host(c['seq'], bad, c['meta'])
+    for env, tile in (({}, pitch >= 32), ({'KBBQ_K2_TILE': '0'}, False), ({'KBBQ_K2_TILE_CHARS': '0'}, False)):
+        for k, v in env.items():
+            monkeypatch.setenv(k, v)
+        dev.apply(bad_batch, d_lut, shape, minscore=MINSCORE, check=False)
+        with pytest.raises(N.LutNeedsCheckedApply if tile else IndexError) as e:
+            ctx.status()
+        assert tile or _read_of(e.value) == c['n'] - 1
+        for k in env:
+            monkeypatch.delenv(k)
+    ctx.status()
+
+
+# ------------------------------------------------------------------ 2. the error contract
+ERR_N, ERR_PITCH, ERR_L = 5000, 160, 150
+# KBBQ_STAGE_MB=1: a slab is 1 MiB / (160 bytes x 3 planes + 4) = 2166 rows, rounded down to a multiple of 64 -- for kbbq_accumulate
+# (seq, cseq, qual) and kbbq_apply (seq, qual, out) alike.  5000 rows: slabs [0, 2112), [2112, 4224), [4224, 5000).
+SLAB = (1 << 20) // (ERR_PITCH * 3 + 4) // 64 * 64
+ERR_ROWS = [0, SLAB - 1, SLAB, ERR_N - 1]                  # row 0, the last row of a slab, the first of the next, the last row
+ERR_BASES = [0, 15, 16, ERR_L - 1]
+ROUTES = {'tile': (1, {}), 'persistent': (1, {'KBBQ_K2_TILE': '0'}), 'two_groups': (2, {})}
+DEFECTS = ['q43', 'qhigh', 'X', 'a', 'quiet', 'long', 'rg']
+
+_err_inputs = {}
+
+
+def _err_input(oracle, R, short):
+    """Clean oracle-synth rows (150 bases, pitch 160; `short`: the same rows cut to 60 bases, for tables narrower than a planted
+    150-base read) with the oracle's model for them."""
+    key = (R, short)
+    if key not in _err_inputs:
+        seq, cseq, qual, meta = oracle.synth(0, ERR_N, ERR_N, 4242 + R, nrg=R)
+        full = (seq.copy(), cseq.copy(), qual.copy(), meta.copy())
+        S = ERR_L
+        if short:
+            S = 60
+            seq[:, S:] = ord('N'); cseq[:, S:] = ord('N'); qual[:, S:] = 0
+            meta = (meta & ~np.uint32(0xFFFF)) | np.uint32(S)
+        want = oracle.accumulate(seq, cseq, qual, meta, R, S, minscore=MINSCORE)
+        dqs = oracle.get_delta_qs(*want)
+        _err_inputs[key] = dict(R=R, S2=2 * S, planes=(seq, cseq, qual, meta), full=full, model=_model_args(want[0], dqs))
+    return _err_inputs[key]
+
+
+def _plant(inp, kind, row, base):
+    """A copy of the clean planes with one defect in `row` at `base`."""
+    seq, cseq, qual, meta = (x.copy() for x in inp['planes'])
+    R = inp['R']
+    if kind == 'q43':                                   # quality 43 = Qt
+        qual[row, base] = 33 + 43
+    elif kind == 'qhigh':                               # a quality byte with the high bit set
+        qual[row, base] = 0xC8
+    elif kind in ('X', 'a', 'quiet'):
+        lo, hi = max(base - 1, 0), min(base + 2, ERR_L)
+        seq[row, lo:hi] = ord('G'); cseq[row, lo:hi] = ord('G')
+        seq[row, base] = ord('a') if kind == 'a' else ord('X')
+        qual[row, lo:hi] = 33 + 30                      # looked up: a foreign letter in a dinucleotide
+        if kind == 'quiet':                             # its own quality and its successor's below minscore: never looked up
+            qual[row, base:hi] = 33 + 2
+    elif kind == 'long':                                # the 150-base original of the row among rows cut to 60: beyond the tables
+        for dst, src in zip((seq, cseq, qual, meta), inp['full']):
+            dst[row] = src[row]
+        qual[row, 60:ERR_L] = np.maximum(qual[row, 60:ERR_L], 33 + MINSCORE)
+    elif kind == 'rg':                                  # read-group id R: 1 under R = 1
+        meta[row] = (meta[row] & ~np.uint32(0x7FFF << 16)) | np.uint32(R << 16)
+    return seq, cseq, qual, meta
+
+
+def _oracle_verdict(fn):
+    """(exception class, read index) the oracle answers with, or (None, its result)."""
+    try:
+        return None, fn()
+    except (IndexError, TypeError) as e:
+        return type(e), int(re.search(r'read (\d+)', str(e)).group(1))
+
+
+def _read_of(exc):
+    m = re.search(r'read (\d+)', str(exc))
+    assert m, 'no read index in %r' % str(exc)
+    return int(m.group(1))
+
+
+def _check_entries(dev, oracle, inp, planes, first_bad):
+    """kbbq_apply and kbbq_accumulate on `planes` against the oracle on the same planes; first_bad: the lowest planted row."""
+    seq, cseq, qual, meta = planes
+    R, S2, model = inp['R'], inp['S2'], inp['model']
+    ctx = dev.context()
+    ins = _inside(meta, seq.shape[1])
+    cls, got = _oracle_verdict(lambda: oracle.apply(seq, qual, meta, *model, minscore=MINSCORE))
+    if cls is None:
+        out = _host_apply(dev, seq, qual, meta, model)
+        assert np.array_equal(out[ins].astype(np.int32) - 33, got[ins])
+    else:
+        assert got == first_bad                          # the first offending read of the whole input
+        with pytest.raises(cls) as e:
+            _host_apply(dev, seq, qual, meta, model)
+        assert _read_of(e.value) == first_bad
+    ctx.status()
+    cls, got = _oracle_verdict(lambda: oracle.accumulate(seq, cseq, qual, meta, R, S2 // 2, minscore=MINSCORE))
+    sentinel = [np.full((R, 43, S2), 7, np.int64), np.full((R, 43, S2), 5, np.int64), np.full((R, 43, 16), 3, np.int64), np.full((R, 43, 16), 1, np.int64)]
+    tabs = [t.copy() for t in sentinel]
+    if cls is None:
+        _host_accumulate(dev, seq, cseq, qual, meta, R, S2, tabs)
+        for t, s, w in zip(tabs, sentinel, got[5:]):
+            assert np.array_equal(t - s, w)
+    else:
+        assert got == first_bad
+        with pytest.raises(cls) as e:
+            _host_accumulate(dev, seq, cseq, qual, meta, R, S2, tabs)
+        assert _read_of(e.value) == first_bad
+        assert all(np.array_equal(t, s) for t, s in zip(tabs, sentinel))          # a refused call adds nothing
+    ctx.status()
+    return cls
+
+
+@pytest.mark.parametrize('kind', DEFECTS)
+@pytest.mark.parametrize('route', list(ROUTES))
+def test_bad_input_raises_what_the_oracle_raises(dev, oracle, route, kind, monkeypatch):
+    """One defect in otherwise clean rows, at base 0 / 15 / 16 / L - 1 of row 0, of the last row of a slab, of the first row of the
+    next slab and of the last row: kbbq_apply and kbbq_accumulate raise the oracle's exception with the oracle's read index."""
+    R, env = ROUTES[route]
+    monkeypatch.setenv('KBBQ_STAGE_MB', '1')
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    assert SLAB == 2112 and 2 * SLAB < ERR_N                           # three slabs
+    inp = _err_input(oracle, R, kind == 'long')
+    seen = set()
+    for row in ERR_ROWS:
+        for base in (ERR_BASES if kind not in ('rg', 'long') else ERR_BASES[:1]):      # (these two are defects of the whole read)
+            seen.add(_check_entries(dev, oracle, inp, _plant(inp, kind, row, base), row))
+    want = {'q43': {IndexError}, 'qhigh': {IndexError}, 'X': {TypeError}, 'a': {TypeError}, 'quiet': {None}, 'long': {IndexError},
+            'rg': {IndexError}}[kind]
+    assert seen == want                                                # the oracle's own answers are the ones the case is about
+
+
+@pytest.mark.parametrize('route', list(ROUTES))
+def test_first_of_several_bad_reads_is_reported(dev, oracle, route, monkeypatch):
+    """Two defective reads: the lower index is reported, whichever slab holds it and whichever kind it is."""
+    R, env = ROUTES[route]
+    monkeypatch.setenv('KBBQ_STAGE_MB', '1')
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    inp = _err_input(oracle, R, False)
+
+    def both(a, b):
+        planes = _plant(inp, *a)
+        for dst, src in zip(planes, _plant(inp, *b)):
+            dst[b[1]] = src[b[1]]
+        return planes
+    cases = [(('q43', 3000, 7), ('q43', SLAB - 1, 149), IndexError),           # the later slab's read was planted first
+             (('qhigh', 4300, 16), ('q43', 4250, 0), IndexError),              # both in the last slab
+             (('X', 4300, 20), ('q43', 2500, 3), IndexError),                  # an IndexError read before a TypeError read
+             (('q43', ERR_N - 1, 15), ('a', 100, 149), TypeError)]             # ... and a TypeError read before an IndexError read
+    for a, b, cls in cases:
+        assert _check_entries(dev, oracle, inp, both(a, b), min(a[1], b[1])) is cls
+
+
+@pytest.mark.parametrize('kind', DEFECTS)
+@pytest.mark.parametrize('route', list(ROUTES))
+def test_recalibrate_fastq_of_one_bad_read(dev, oracle, route, kind, monkeypatch):
+    """compare_reads.recalibrate_fastq, the drop-in for the reference's per-read function: one read through kbbq_apply with R
+    taken from the model.  The oracle's exception for that read (read 0), or the oracle's qualities."""
+    from kbbq import compare_reads, fastx
+    R, env = ROUTES[route]
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    inp = _err_input(oracle, R, kind == 'long')
+    model = inp['model']
+    for row in (0, 1):                                                 # first and second in pair
+        for base in (ERR_BASES if kind not in ('rg', 'long') else ERR_BASES[:1]):
+            seq, _, qual, meta = (x[row:row + 1] for x in _plant(inp, kind, row, base))
+            L = int(meta[0] & 0xFFFF)
+            read = fastx.FastxRecord('r', seq[0, :L].tobytes().decode('latin-1'), qual[0, :L].tobytes().decode('latin-1'))
+            call = lambda: compare_reads.recalibrate_fastq(read, *model, np.array([(int(meta[0]) >> 16) & 0x7FFF]),
+                                                           compare_reads.Dinucleotide.dinuc_to_int,
+                                                           secondinpair=bool(meta[0] >> 31), minscore=MINSCORE)
+            cls, got = _oracle_verdict(lambda: oracle.apply(seq, qual, meta, *model, minscore=MINSCORE))
+            assert (cls is None) == (kind == 'quiet')
+            if cls is None:
+                assert np.array_equal(call(), got[0, :L])
+            else:
+                assert got == 0
+                with pytest.raises(cls) as e:
+                    call()
+                assert _read_of(e.value) == 0
+            dev.context().status()
+
+
+# ------------------------------------------------------------------ 3. bytes beyond a read's length do not matter
+FILLS = ['zero', 'A_vs_C', 'n', 'ff', 'random']
+
+
+def _padded(c, fill):
+    """seq / cseq of case `c` with another filling beyond every read's length (qual stays zero: include/kbbq_hip.h)."""
+    seq, cseq = c['seq'].copy(), c['cseq'].copy()
+    out = ~c['inside']
+    if fill == 'zero':                                   # what kbbq_sam_fill writes
+        seq[out] = 0; cseq[out] = 0
+    elif fill == 'A_vs_C':                               # a would-be corrected site
+        seq[out] = ord('A'); cseq[out] = ord('C')
+    elif fill == 'n':
+        seq[out] = ord('n'); cseq[out] = ord('n')
+    elif fill == 'ff':
+        seq[out] = 0xFF; cseq[out] = 0xFF
+    else:
+        rng = np.random.default_rng(5)
+        seq[out] = rng.integers(0, 256, int(out.sum())); cseq[out] = rng.integers(0, 256, int(out.sum()))
+    return seq, cseq
+
+
+@pytest.mark.parametrize('R', [1, 3])
+@pytest.mark.parametrize('pitch', PITCHES)
+def test_padding_of_host_planes_does_not_matter(dev, oracle, pitch, R):
+    """kbbq_accumulate and kbbq_apply at one and at three read groups: the tables of oracle.accumulate and the bytes of oracle.apply
+    on the 'N'-padded planes, whatever fills seq / cseq beyond the reads."""
+    c = _case(oracle, pitch, R)
+    model = _model_args(c['want'][0], c['dqs'])
+    ins = c['inside']
+    for fill in FILLS:
+        seq, cseq = _padded(c, fill)
+        tabs = _host_accumulate(dev, seq, cseq, c['qual'], c['meta'], R, c['S2'])
+        for t, w, k in zip(tabs, c['want'][5:], ('pos_errs', 'pos_total', 'dinuc_errs', 'dinuc_total')):
+            assert np.array_equal(t, w), (fill, k)
+        out = _host_apply(dev, seq, c['qual'], c['meta'], model)
+        assert np.array_equal(out[ins].astype(np.int32) - 33, c['ref'][ins]), fill
+    dev.context().status()
+
+
+@pytest.mark.parametrize('pitch', PITCHES)
+def test_padding_of_device_planes_does_not_matter(dev, oracle, pitch):
+    """dev.accumulate / dev.apply on a ReadBatch at one read group, and on what dev.lay_out(packed=True) makes of it (4-bit planes,
+    or the character planes kept): the same tables and bytes."""
+    from kbbq import _native as N
+    c = _case(oracle, pitch, 1)
+    n, ins = c['n'], c['inside']
+    lut, shape = dev.build_lut(*_model_args(c['want'][0], c['dqs']), minscore=MINSCORE)
+    d_lut = dev.lut_to_device(lut)
+    want_tabs = c['want'][5:]
+    for fill in FILLS:
+        seq, cseq = _padded(c, fill)
+        batch = dev.ReadBatch.from_host(seq, c['qual'], c['meta'], cseq=cseq)
+        for name, b in (('rows', batch), ('laid out', dev.lay_out(batch, 1, packed=True))):
+            t = dev.Tables(1, c['S2'])
+            if b.nib and pitch == 304:
+                # 4-bit rows of reads from 1 to 304 bases: a shape the table-driven K1 refuses before it launches anything, whatever
+                # pads them -- 3 x 304 cycle columns and no shortest-read promise do not fit the LDS (csrc/kbbq_hip.hip
+                # accumulate_rows) -- with the layout entry points' documented answer.  K2 serves such rows: checked below.
+                with pytest.raises(N.LutNeedsCheckedApply, match='do not fit the LDS tables'):
+                    dev.accumulate(b, t, MINSCORE)
+                assert not t.buf.any()
+            else:
+                dev.accumulate(b, t, MINSCORE)
+                for g, w in zip(t.to_host(), want_tabs):
+                    assert np.array_equal(g, w), (fill, name)
+            out = dev.apply(b, d_lut, shape, minscore=MINSCORE, restore_order=True)
+            if isinstance(b, dev.PairBatch):
+                out = b.unpack(out, pitch)
+            out = out[:n].cpu().numpy()
+            assert np.array_equal(out[ins].astype(np.int32) - 33, c['ref'][ins]), (fill, name)
+    dev.context().status()
