@@ -726,6 +726,13 @@ int kbbq_ctx_kernel_ms(kbbq_ctx* ctx, int which, double* total_ms, int64_t* laun
  * an untrusted A/C/G/T base beside an N is decided exactly as without the option (the N is a break for it), and the result does
  * not depend on thread order.  A fixed N is a changed base in d_changed.  Counting, the prefilter, the histogram and the
  * threshold know nothing of the option: an N is a break for them and the table is the same table.
+ * kbbq_kmer_flag_dev: the decision of kbbq_kmer_correct_dev as a flag plane, for callers that want to know WHICH bases the solid
+ * k-mers contradict and not what they become (kbbq bqsr --kmers: the errors of a recalibration tally).  Same arguments and
+ * refusals (pitch a multiple of 16, min_count >= 1, NULL table / planes, nreads == 0 does nothing); d_flags (16-byte aligned,
+ * [nreads, pitch]) receives 1 at every base where kbbq_kmer_correct_dev would write a byte different from d_seq's and 0
+ * everywhere else -- breaks (N included: there is no N rule here), trusted bases, ties, padding up to pitch.  Every byte of every
+ * row is written: the plane needs no clearing.  d_changed (may be NULL) as above.  The plane is, bit for bit, the one plane of
+ * flags kbbq_accumulate_aligned_dev and kbbq_canonical_reads_rows_dev(d_skip = NULL) read: bit 0 error, bit 1 (skip) never set.
  * kbbq_kmer_count / kbbq_kmer_correct: the same from host buffers, slab by slab through page-locked staging (KBBQ_STAGE_MB);
  * `changed` (host, may be NULL) receives the per-read counts.  The kernel launches are not timed by kbbq_ctx_timing.
  * Ranks (kbbq/kmer.py count_kmers_ranks): every rank counts its reads into a local table, sends each key to its owner and merges
@@ -748,6 +755,8 @@ int kbbq_kmer_count_dev(kbbq_ctx* ctx, kbbq_kmer_table* table, const uint8_t* d_
 int kbbq_kmer_histogram_dev(kbbq_ctx* ctx, const kbbq_kmer_table* table, uint64_t* d_hist);
 int kbbq_kmer_correct_dev(kbbq_ctx* ctx, const kbbq_kmer_table* table, const uint8_t* d_seq, const uint32_t* d_meta,
                           int64_t nreads, int pitch, int min_count, uint8_t* d_out, uint32_t* d_changed);
+int kbbq_kmer_flag_dev(kbbq_ctx* ctx, const kbbq_kmer_table* table, const uint8_t* d_seq, const uint32_t* d_meta,
+                       int64_t nreads, int pitch, int min_count, uint8_t* d_flags, uint32_t* d_changed);
 int kbbq_kmer_count(kbbq_ctx* ctx, kbbq_kmer_table* table, const uint8_t* seq, const uint32_t* meta, int64_t nreads, int pitch);
 int kbbq_kmer_correct(kbbq_ctx* ctx, const kbbq_kmer_table* table, const uint8_t* seq, const uint32_t* meta, int64_t nreads,
                       int pitch, int min_count, uint8_t* out, uint32_t* changed);

@@ -2264,8 +2264,10 @@ static void (*const KM_CORRECT[2][3])(KmerParams) = {
 };
 
 // pairs: two reads to a row (KBBQ_ROWS_PAIRS), which the N rule alone needs to know -- their separator is no N
+// flag_form: d_out is a flag plane (kbbq_kmer_flag_dev; character rows, opts 0)
 static int kmer_correct_rows(kbbq_ctx* c, const char* who, const kbbq_kmer_table* t, const uint8_t* d_seq, const uint32_t* d_meta,
-                             int64_t n, int pitch, bool nib, bool pairs, int min_count, uint8_t* d_out, uint32_t* d_changed, int opts)
+                             int64_t n, int pitch, bool nib, bool pairs, int min_count, uint8_t* d_out, uint32_t* d_changed, int opts,
+                             bool flag_form = false)
 {
     int rc = kmer_correct_opts(who, opts);
     if (rc) return rc;
@@ -2278,7 +2280,8 @@ static int kmer_correct_rows(kbbq_ctx* c, const char* who, const kbbq_kmer_table
     if (n == 0) return KBBQ_OK;
     HIPCHK(hipSetDevice(c->device));
     p.min_count = (u32)min_count; p.out = d_out; p.changed = d_changed;
-    const auto kernel = KM_CORRECT[nib ? 1 : 0][!(opts & KBBQ_KMER_FIX_N) ? KM_FIXN_OFF : pairs ? KM_FIXN_PAIRS : KM_FIXN_READS];
+    const auto kernel = flag_form ? km_correct<false, KM_FIXN_OFF, true>
+                                  : KM_CORRECT[nib ? 1 : 0][!(opts & KBBQ_KMER_FIX_N) ? KM_FIXN_OFF : pairs ? KM_FIXN_PAIRS : KM_FIXN_READS];
     return kmer_launches(p, [&](const KmerParams& q, unsigned grid) {
         hipLaunchKernelGGL(kernel, dim3(grid), dim3(KM_THREADS), lds, c->stream, q);
     });
@@ -2294,6 +2297,16 @@ int kbbq_kmer_correct_dev(kbbq_ctx* c, const kbbq_kmer_table* t, const uint8_t* 
                           int min_count, uint8_t* d_out, uint32_t* d_changed)
 {
     return kmer_correct_rows(c, "kbbq_kmer_correct_dev", t, d_seq, d_meta, n, pitch, false, false, min_count, d_out, d_changed, 0);
+}
+
+int kbbq_kmer_flag_dev(kbbq_ctx* c, const kbbq_kmer_table* t, const uint8_t* d_seq, const uint32_t* d_meta, int64_t n, int pitch,
+                       int min_count, uint8_t* d_flags, uint32_t* d_changed)
+{
+    // kbbq_kmer_correct_dev's refusals; those of the numbers alone come first, so that they need no context to be decided
+    int rc = check_planes("kbbq_kmer_flag_dev", n, pitch, d_seq, d_flags, nullptr);
+    if (rc) return rc;
+    if (min_count < 1) return fail(KBBQ_E_ARG, "kbbq_kmer_flag_dev: min_count must be >= 1, got %d", min_count);
+    return kmer_correct_rows(c, "kbbq_kmer_flag_dev", t, d_seq, d_meta, n, pitch, false, false, min_count, d_flags, d_changed, 0, true);
 }
 
 static int kmer_correct_rows_flags(kbbq_ctx* c, const char* who, const kbbq_kmer_table* t, const uint8_t* d_seq, const uint32_t* d_meta,

@@ -30,6 +30,12 @@
 // at (length - 1) / 2 is their separator, never an N.  Counting, the filter and the substitution rule see an N as the break
 // it is, fixed or not.
 //
+// Flag form (km_correct<false, KM_FIXN_OFF, true>; include/kbbq_hip.h kbbq_kmer_flag_dev): the same decision with another
+// store stage (km_put).  KmerParams.out is a flag plane of the input's geometry, one byte a base: 1 where the correction would
+// write another letter, 0 everywhere else -- breaks, trusted bases, ties, padding.  A thread starts from a chunk of zeros
+// instead of the chunk as read (pass 1 has the codes it needs in LDS) and stores its 16 bytes whatever they hold, so every
+// byte of the plane is written: 1 B/base out, where a corrected plane would be written, read back and compared.
+//
 // Ranks (kbbq/kmer.py count_kmers_ranks): the owner of a canonical key among W ranks is km_owner(key, W), the high 32 bits of
 // the same mix taken of the key XOR a constant, scaled to 0..W-1.  It shares no bits with the home slot (km_hash(key) & mask),
 // so the keys one rank owns spread over all home slots of its table.  km_select_sizes / km_select_scatter sort the occupied
@@ -66,7 +72,7 @@ struct KmerParams {
     const uint8_t* seq; const u32* meta; int64_t nrows; int pitch; int cpr; int rows_per_wg; int k;   // pitch: row stride, bytes
     u64* keys; u32* counts; u64 mask;
     u32 min_count;                    // correct: a k-mer is solid when its count is >= min_count
-    uint8_t* out; u32* changed;       // correct: the corrected plane; per-row count of changed bases (may be NULL)
+    uint8_t* out; u32* changed;       // correct: the corrected plane (flag form: the flag plane); per-row count of changed bases (may be NULL)
     u64* status;
 };
 
@@ -326,9 +332,27 @@ __device__ __forceinline__ unsigned __int128 km_breaks(const KmerParams& p, cons
     return b;
 }
 
-template <bool NIB, int FIXN = KM_FIXN_OFF>
+// km_correct's store stage: base t of the chunk `w` (4 words of characters, 2 of nibbles) takes the table's code `best`.
+// FLAGS: `w` is the chunk of the flag plane instead, one byte a base, and the base's byte becomes 1.
+template <bool NIB, bool FLAGS>
+__device__ __forceinline__ void km_put(u32 (&w)[4], int t, u32 best)
+{
+    if constexpr (FLAGS) {
+        w[t >> 2] |= 1u << (8 * (t & 3));
+    } else if constexpr (NIB) {
+        const int sh = km_nib_shift(t & 7);
+        w[t >> 3] = (w[t >> 3] & ~(0xFu << sh)) | (km_nib_swap(best) << sh);
+    } else {
+        const u32 letter = best == 0 ? 'A' : best == 1 ? 'C' : best == 2 ? 'G' : 'T';
+        const int sh = 8 * (t & 3);
+        w[t >> 2] = (w[t >> 2] & ~(0xFFu << sh)) | (letter << sh);
+    }
+}
+
+template <bool NIB, int FIXN = KM_FIXN_OFF, bool FLAGS = false>
 __global__ __launch_bounds__(KM_THREADS) void km_correct(KmerParams p)
 {
+    static_assert(!FLAGS || (!NIB && FIXN == KM_FIXN_OFF), "the flag form: character rows, no N rule");
     extern __shared__ u32 km_lds[];
     const int E = p.rows_per_wg * p.cpr;
     u32* code = km_lds; u32* brk = km_lds + E; u32* sv = km_lds + 2 * E; u32* nchg = km_lds + 3 * E;
@@ -366,7 +390,8 @@ __global__ __launch_bounds__(KM_THREADS) void km_correct(KmerParams p)
         constexpr int CB = NIB ? 8 : 16;                                  // bytes of a chunk in the plane
         const size_t at = (size_t)row * p.pitch + (size_t)ch * CB;
         u32 w[4] = {0, 0, 0, 0};                                         // the chunk as read: 4 words of characters, 2 of nibbles
-        if constexpr (NIB) {
+        if constexpr (FLAGS) {                                           // ... or of the flag plane: all 0, nothing to read
+        } else if constexpr (NIB) {
             const uint2 v = *reinterpret_cast<const uint2*>(p.seq + at);
             w[0] = v.x; w[1] = v.y;
         } else {
@@ -417,14 +442,7 @@ __global__ __launch_bounds__(KM_THREADS) void km_correct(KmerParams p)
                         else if (s[x] == bs && bs > 0) tie = true;
                     }
                     if (best < 0 || tie) continue;
-                    if constexpr (NIB) {
-                        const int sh = km_nib_shift(t & 7);
-                        w[t >> 3] = (w[t >> 3] & ~(0xFu << sh)) | (km_nib_swap((u32)best) << sh);
-                    } else {
-                        const u32 letter = best == 0 ? 'A' : best == 1 ? 'C' : best == 2 ? 'G' : 'T';
-                        const int sh = 8 * (t & 3);
-                        w[t >> 2] = (w[t >> 2] & ~(0xFFu << sh)) | (letter << sh);
-                    }
+                    km_put<NIB, FLAGS>(w, t, (u32)best);
                     ++changed;
                     continue;
                 }
@@ -456,14 +474,7 @@ __global__ __launch_bounds__(KM_THREADS) void km_correct(KmerParams p)
                 else if (s[alt] == bs && bs > 0) tie = true;
             }
             if (best < 0 || tie) continue;
-            if constexpr (NIB) {
-                const int sh = km_nib_shift(t & 7);
-                w[t >> 3] = (w[t >> 3] & ~(0xFu << sh)) | (km_nib_swap((u32)best) << sh);
-            } else {
-                const u32 letter = best == 0 ? 'A' : best == 1 ? 'C' : best == 2 ? 'G' : 'T';
-                const int sh = 8 * (t & 3);
-                w[t >> 2] = (w[t >> 2] & ~(0xFFu << sh)) | (letter << sh);
-            }
+            km_put<NIB, FLAGS>(w, t, (u32)best);
             ++changed;
         }
         if constexpr (NIB) *reinterpret_cast<uint2*>(p.out + at) = make_uint2(w[0], w[1]);

@@ -174,6 +174,7 @@ PROTOTYPES = {
     'kbbq_kmer_histogram_dev': (_i, [_vp, _vp, _vp]),
     'kbbq_kmer_correct_dev': (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _vp, _vp]),
     'kbbq_kmer_count': (_i, [_vp, _vp, _vp, _vp, _i64, _i]),
+    'kbbq_kmer_flag_dev': (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _vp, _vp]),
     'kbbq_kmer_correct': (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _vp, _vp]),
     'kbbq_kmer_correct_ex_dev': (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _vp, _vp, _i]),
     'kbbq_kmer_correct_ex': (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _vp, _vp, _i]),

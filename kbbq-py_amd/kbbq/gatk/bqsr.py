@@ -11,6 +11,10 @@ the adaptor trimming :131-206): K4 flags errors / known sites by CIGAR walk, K6 
 read into sequencing orientation with the skipped bases uncounted, and K1 -- the very kernel of
 the FASTQ path -- tallies.  Host work per read: the CIGAR-derived scalars (clip ends, adaptor
 index); the per-read covariate functions exist for API parity and run on the host.
+
+K-mer-sourced tally (bam_to_kmer_covariates, bam_to_report_kmers; `kbbq bqsr --kmers`, not in the reference): the same tally
+with the error flags written by the k-mer correction's decision over the alignments' own sequences (kbbq.kmer.flag_errors)
+instead of K4 -- no FASTA, no VCF.  Both sources end in _tally_flag_plane.
 """
 import numpy as np
 import pandas as pd
@@ -133,6 +137,48 @@ def trim_bamread(read, boundary=_UNSET):
 
 
 # ---------------------------------------------------------------- the tally (device)
+def _tally_flag_plane(tables, d_seq, d_qual, err, skip, d_len, d_clip, d_trim, d_flags, m, pitch, S, R, minscore, fused):
+    """Tally `m` aligned reads of the common length S into `tables`, given their flags: `err` is one plane of flags (bit 0 error,
+    bit 1 skip; `skip` None) or the error plane of a pair (err, skip) -- whoever wrote it, K4's CIGAR walk against a reference
+    (bam_to_bqsr_covariates) or the k-mers of the reads themselves (bam_to_kmer_covariates).  d_qual: quality characters."""
+    from .. import _device as dev
+    from .. import _native as N
+    ctx = dev.context()
+
+    def canonical(nib):
+        batch = dev.ReadBatch(m, pitch, with_corrected=True, nib=nib)
+        N.check(N.load().kbbq_canonical_reads_rows_dev(
+            ctx.handle, N.ptr(d_seq), N.ptr(d_qual), N.ptr(err), N.ptr(skip), N.ptr(d_len), N.ptr(d_clip),
+            N.ptr(d_trim), N.ptr(d_flags), m, pitch, S, minscore, 6, N.ROWS_NIBBLES if nib else 0,
+            N.ptr(batch.seq), N.ptr(batch.cseq), N.ptr(batch.qual), N.ptr(batch.meta)))
+        ctx.status()
+        return batch
+    # K6 fused into K1 (kbbq_accumulate_aligned_dev): the tally straight from the reads as aligned, nothing written but the
+    # tables -- unless a forward read carries a letter outside ACGTN or the tables do not fit the LDS beside it (both
+    # reported before / without anything reaching `tables`: the attempt counts into tables of its own); then, as before:
+    if fused:
+        try:
+            part = dev.Tables(R, 2 * S)
+            N.check(N.load().kbbq_accumulate_aligned_dev(ctx.handle, N.ptr(d_seq), N.ptr(d_qual), N.ptr(err), N.ptr(d_clip), N.ptr(d_trim),
+                                                         N.ptr(d_flags), m, pitch, S, R, minscore, 6, N.ptr(part.buf)))
+            ctx.status()
+            tables.add(part)
+            return
+        except N.LutNeedsCheckedApply:
+            pass
+    # 4-bit sequence planes between K6 and K1 (one byte per base less to write and to read) unless a forward read
+    # carries a letter outside ACGTN, the reads are longer than K1's packed form takes, or K1's tables for this
+    # minscore do not fit beside it (both refusals come before anything is counted)
+    # (tallied into tables of its own and added on success only: a refusal that arrives after the launch must not
+    #  leave counts behind that the character-plane pass would add again)
+    try:
+        part = dev.Tables(R, 2 * S)
+        dev.accumulate(canonical(S <= dev.PACKED_READS), part, minscore, dinuc_minscore=6)
+        tables.add(part)
+    except N.LutNeedsCheckedApply:
+        dev.accumulate(canonical(False), tables, minscore, dinuc_minscore=6)
+
+
 def bam_to_bqsr_covariates(bamfileobj, fastafilename, var_pos, minscore=6, maxscore=42):
     """The nine model vectors from aligned reads, a FASTA reference and known variant sites
     (reference bqsr.py:52-123): K4 -> K6 -> K1.  Every read must have the first read's length
@@ -229,45 +275,122 @@ def bam_to_bqsr_covariates(bamfileobj, fastafilename, var_pos, minscore=6, maxsc
             except N.LutNeedsCheckedApply:
                 pass
         err, skip = benchmark._find_errors(u, genome, fused=True)
-
-        def canonical(nib):
-            batch = dev.ReadBatch(m, pitch, with_corrected=True, nib=nib)
-            N.check(N.load().kbbq_canonical_reads_rows_dev(
-                ctx.handle, N.ptr(d_seq), N.ptr(d_oq), N.ptr(err), N.ptr(skip), N.ptr(d_len), N.ptr(d_clip),
-                N.ptr(d_trim), N.ptr(d_flags), m, pitch, S, minscore, 6, N.ROWS_NIBBLES if nib else 0,
-                N.ptr(batch.seq), N.ptr(batch.cseq), N.ptr(batch.qual), N.ptr(batch.meta)))
-            ctx.status()
-            return batch
-        # K6 fused into K1 (kbbq_accumulate_aligned_dev): the tally straight from the reads as aligned, nothing written but the
-        # tables -- unless a forward read carries a letter outside ACGTN or the tables do not fit the LDS beside it (both
-        # reported before / without anything reaching `tables`: the attempt counts into tables of its own); then, as before:
-        if mode != '0' and fits:
-            try:
-                part = dev.Tables(max(R, 1), 2 * S)
-                N.check(N.load().kbbq_accumulate_aligned_dev(ctx.handle, N.ptr(d_seq), N.ptr(d_oq), N.ptr(err), N.ptr(d_clip), N.ptr(d_trim),
-                                                             N.ptr(d_flags), m, pitch, S, max(R, 1), minscore, 6, N.ptr(part.buf)))
-                ctx.status()
-                tables.add(part)
-                return
-            except N.LutNeedsCheckedApply:
-                pass
-        # 4-bit sequence planes between K6 and K1 (one byte per base less to write and to read) unless a forward read
-        # carries a letter outside ACGTN, the reads are longer than K1's packed form takes, or K1's tables for this
-        # minscore do not fit beside it (both refusals come before anything is counted)
-        # (tallied into tables of its own and added on success only: a refusal that arrives after the launch must not
-        #  leave counts behind that the character-plane pass would add again)
-        try:
-            part = dev.Tables(max(R, 1), 2 * S)
-            dev.accumulate(canonical(S <= dev.PACKED_READS), part, minscore, dinuc_minscore=6)
-            tables.add(part)
-        except N.LutNeedsCheckedApply:
-            dev.accumulate(canonical(False), tables, minscore, dinuc_minscore=6)
+        _tally_flag_plane(tables, d_seq, d_oq, err, skip, d_len, d_clip, d_trim, d_flags, m, pitch, S, max(R, 1), minscore,
+                          mode != '0' and fits)
     benchmark._on_all_ranks(shard if m else (lambda: None), lo)
     if world > 1:
         parallel.allreduce_tables(tables.buf)
     if bad_length is not None:
         raise IndexError('boolean index did not match indexed array along axis 0; size of axis is %d but size of '
                          'corresponding boolean axis is %d' % (S, int(lens[bad_length])))
+    return _solve.vectors_from_tables(*tables.to_host(), maxscore)
+
+
+def _kmer_inputs(bamfileobj, k, min_count, prefilter, filter_bits, use_oq, maxscore):
+    """Everything bam_to_kmer_covariates refuses, decided on the reader's host arrays before any device call (and, in a process
+    group, before any collective).  Returns (batch, n, S)."""
+    from .. import aln, kmer
+    if maxscore != 42:
+        raise ValueError('the Q axis of the device tables is fixed at 43 (maxscore = 42)')
+    if kmer._ranks() is not None:
+        raise ValueError('bqsr --kmers does not run across ranks yet: the k-mer table of the alignments is counted and read on '
+                         'one GPU; run `kbbq bqsr -r -v` under ranks, or `--kmers` on one GPU')
+    if not 8 <= int(k) <= 32:
+        raise ValueError('k must be in 8..32, got %d' % int(k))
+    if min_count is not None and int(min_count) < 1:
+        raise ValueError('min_count must be >= 1, got %d' % int(min_count))
+    if prefilter:
+        kmer._check_prefilter(min_count, filter_bits)
+    if not isinstance(bamfileobj, aln.AlignmentFile):
+        raise TypeError('bam_to_kmer_covariates takes a kbbq.aln.AlignmentFile (its batch() arrays), got %s' % type(bamfileobj).__name__)
+    b = bamfileobj.batch()
+    n = b.n
+    if n == 0:
+        raise StopIteration                                                    # as bam_to_bqsr_covariates
+    if int(b.rg.min()) < 0:
+        i = int(np.flatnonzero(b.rg < 0)[0])
+        raise KeyError("tag 'RG' not present" if b.rg[i] == -1 else b._text(1, i).split('RG:Z:')[1].split('\t')[0])
+    name = lambda i: 'record %d (%s)' % (i, b._text(0, i))
+    have = b.oq_len if use_oq else b.qual_len
+    if use_oq and int(have.min()) < 0:
+        raise KeyError("tag 'OQ' not present in %s" % name(int(np.flatnonzero(have < 0)[0])))
+    if not use_oq and int(have.min()) == 0:
+        i = int(np.flatnonzero(have == 0)[0])
+        raise ValueError("%s has QUAL '*': bqsr --kmers needs a quality for every base (-u takes them from the OQ tag)" % name(i))
+    S = int(b.qlen[0])
+    wrong = np.flatnonzero(b.qlen != S)
+    if wrong.size:
+        i = int(wrong[0])
+        raise ValueError('%s has %d bases but record 0 has %d: the tally has one cycle axis of 2 S, so bqsr --kmers needs records '
+                         'of one query length' % (name(i), int(b.qlen[i]), S))
+    wrong = np.flatnonzero(have != S)
+    if wrong.size:
+        i = int(wrong[0])
+        raise ValueError('%s has %d qualities for %d bases' % (name(i), int(have[i]), S))
+    if not 1 <= S <= 0xFFFF:
+        raise ValueError('records of %d bases: a row holds 1..65535' % S)
+    return b, n, S
+
+
+def bam_to_kmer_covariates(bamfileobj, k=31, min_count=None, slots=None, prefilter=False, filter_bits=4, use_oq=False,
+                           minscore=6, maxscore=42, info=None):
+    """The nine model vectors from aligned reads alone -- no reference, no known sites (`kbbq bqsr --kmers`).  A base is an error
+    where the k-mer correction of kbbq.kmer would change it: every k-mer of SEQ of every record is counted (soft clips too:
+    they are sequenced bases; keys are canonical, so the alignment's strand does not matter), a k-mer is solid at min_count
+    (default: the first valley of the count histogram) and kbbq_kmer_flag_dev writes the correction's decision as the plane
+    of flags the aligned tally reads.  The tally is bam_to_bqsr_covariates' own: the aligned part only, in sequencing
+    orientation, without the bases below minscore, in the adaptor-trimmed range or N.  Qualities are QUAL, or the OQ tag with
+    use_oq.  Secondary, supplementary and duplicate records are counted and tallied like any other, as bam_to_bqsr_covariates
+    does.  All records must have one query length; one GPU (ValueError in a process group, before any collective).
+    prefilter / filter_bits / slots: as kbbq.kmer.correct_reads.  `info`, a dict, receives k, min_count, reads, flagged_bases,
+    slots, prefilter and admitted."""
+    from .. import _device as dev
+    from .. import _solve, fastx, kmer
+    b, n, S = _kmer_inputs(bamfileobj, k, min_count, prefilter, filter_bits, use_oq, maxscore)
+    k = int(k)
+    T = dev._torch()
+    rg_to_int = {rg: i for i, rg in enumerate(utils.get_rg_to_pu(bamfileobj))}
+    R = max(len(rg_to_int), 1)
+    lens = b.qlen.astype(np.uint32)
+    clip = b.clip.copy()
+    rev = (b.flag & 16) != 0
+    trim = b.adaptor_trim()                    # boundary + CIGAR walk per alignment, in the reader (csrc/sam_host.cpp)
+    flags = (rev.astype(np.uint32) | (((b.flag & 128) != 0).astype(np.uint32) << 1) | (b.rg.astype(np.uint32) << 16))
+    pitch = fastx.pitch_for(S)
+    budget = dev.device_budget()
+    up = lambda a: T.from_numpy(np.ascontiguousarray(a)).cuda()
+    d_seq, d_qual = up(b.plane(0, pitch)), up(b.plane(2 if use_oq else 1, pitch))
+    d_len, d_clip, d_trim, d_flags = (up(x.view(np.int32)) for x in (lens, clip, trim, flags))
+    resident = 3 * n * pitch + 20 * n          # SEQ, qualities and the flag plane; the per-read words
+    windows = kmer.kmer_total(lens, k)
+    filt = table = None
+    admitted = None
+    try:
+        if prefilter:
+            filt = kmer.prefilter_kmers(d_seq, d_len, k=k, filter=kmer.KmerFilter(kmer.filter_words(windows, filter_bits)))
+            admitted = filt.admitted
+            filt.release_seen()
+        if slots is None:
+            slots = kmer.default_slots(admitted if prefilter else windows, budget - resident - (filt.nbytes if filt is not None else 0))
+        table = kmer.count_kmers(d_seq, d_len, k=k, slots=slots, filter=filt)
+        if filt is not None:
+            filt.close()
+        t = int(min_count) if min_count is not None else kmer.solid_threshold(kmer.kmer_histogram(table))
+        err, changed = kmer.flag_errors(table, d_seq, d_len, t)
+        nslots = table.slots
+    finally:
+        if filt is not None:
+            filt.close()
+        if table is not None:
+            table.close()
+    tables = dev.Tables(R, 2 * S)
+    fits = pitch == (S + 15) // 16 * 16 and S <= 32767
+    import os
+    _tally_flag_plane(tables, d_seq, d_qual, err, None, d_len, d_clip, d_trim, d_flags, n, pitch, S, R, minscore,
+                      os.environ.get('KBBQ_TALLY_FUSED', '2') != '0' and fits)
+    if info is not None:
+        info.update(k=k, min_count=t, reads=n, flagged_bases=int(changed.cpu().numpy().astype(np.int64).sum()), slots=nslots,
+                    prefilter=bool(prefilter), admitted=admitted)
     return _solve.vectors_from_tables(*tables.to_host(), maxscore)
 
 
@@ -389,4 +512,13 @@ def bam_to_report(bamfileobj, fastafilename, var_pos):
     bqsr.py:368-371)."""
     rgs = list(utils.get_rg_to_pu(bamfileobj).values())
     vectors = bam_to_bqsr_covariates(bamfileobj, fastafilename, var_pos)
+    return vectors_to_report(*vectors, rgs)
+
+
+def bam_to_report_kmers(bamfileobj, k=31, min_count=None, slots=None, prefilter=False, filter_bits=4, use_oq=False, info=None):
+    """Aligned reads -> recalibration report without a reference or known sites: the errors are what the k-mers of the reads'
+    own sequences contradict (bam_to_kmer_covariates); read groups are named by their PU as in bam_to_report."""
+    rgs = list(utils.get_rg_to_pu(bamfileobj).values())
+    vectors = bam_to_kmer_covariates(bamfileobj, k=k, min_count=min_count, slots=slots, prefilter=prefilter,
+                                     filter_bits=filter_bits, use_oq=use_oq, info=info)
     return vectors_to_report(*vectors, rgs)

@@ -67,9 +67,26 @@ def applybqsr(args):
 
 
 def bqsr(args):
-    from . import benchmark as _bm
     from . import aln
     from .gatk import bqsr as _bqsr
+    if args.kmers:
+        import os
+        import sys
+        from . import kmer, parallel
+        parallel.init_from_env()             # under a launcher every rank joins its group, and bam_to_kmer_covariates refuses on each
+        if kmer._ranks() is None and 'torch' not in sys.modules and not os.environ.get('KBBQ_USE_TORCH'):
+            from . import _device
+            _device.use_native_memory()      # as `correct` on one GPU: no torch import
+        info = {}
+        _bqsr.bam_to_report_kmers(aln.AlignmentFile(args.bam), k=31 if args.kmer is None else args.kmer, min_count=args.min_count,
+                                  slots=args.slots, prefilter=args.prefilter,
+                                  filter_bits=4 if args.filter_bits is None else args.filter_bits, use_oq=args.use_oq,
+                                  info=info).write(args.gatkreport)
+        sys.stderr.write('kbbq bqsr: k=%d min_count=%d reads=%d flagged_bases=%d%s\n'
+                         % (info['k'], info['min_count'], info['reads'], info['flagged_bases'],
+                            ' prefilter=1 admitted=%d slots=%d' % (info['admitted'], info['slots']) if args.prefilter else ''))
+        return
+    from . import benchmark as _bm
     _bqsr.bam_to_report(aln.AlignmentFile(args.bam), args.reference, _bm.get_var_sites(args.vcf)).write(args.gatkreport)
 
 
@@ -155,11 +172,28 @@ def main(argv=None):
     ap.add_argument('-s', '--set-oq', action='store_true', help="Keep the qualities as read in an 'OQ' tag where there is none.")
     ap.set_defaults(command=applybqsr)
 
-    qp = sub.add_parser('bqsr', description='Build a GATK recalibration report from alignments (BaseRecalibrator)')
-    qp.add_argument('-b', '--bam', required=True, help='SAM or BAM file (qualities from the OQ tag)')
-    qp.add_argument('-r', '--reference', required=True, help='FASTA file containing the reference genome')
-    qp.add_argument('-v', '--vcf', required=True, help='VCF file of known variable sites (skipped)')
+    qp = sub.add_parser('bqsr', description='Build a GATK recalibration report from alignments (BaseRecalibrator): errors are '
+                        'differences from a reference outside known sites (-r -v), or what the k-mers of the alignments\' own '
+                        'sequences contradict (--kmers: no reference, no known sites)')
+    qp.add_argument('-b', '--bam', required=True, help='SAM or BAM file (qualities from the OQ tag; with --kmers from QUAL unless -u)')
+    qp.add_argument('-r', '--reference', default=None, help='FASTA file containing the reference genome (needed without --kmers)')
+    qp.add_argument('-v', '--vcf', default=None, help='VCF file of known variable sites (skipped; needed without --kmers)')
     qp.add_argument('-g', '--gatkreport', required=True, help='Write the report to this file')
+    qp.add_argument('--kmers', action='store_true',
+                    help='take the errors from the k-mer correction of the alignments\' own sequences (as `kbbq correct` decides '
+                         'them) instead of a reference and known sites; all records of one query length, one GPU')
+    qp.add_argument('-k', '--kmer', type=int, default=None, help='with --kmers: k-mer length, 8..32 (default 31)')
+    qp.add_argument('--min-count', type=int, default=None,
+                    help='with --kmers: k-mers seen at least this often are solid (default: the first valley of the count histogram)')
+    qp.add_argument('--slots', type=int, default=None,
+                    help='with --kmers: hash table slots, a power of two (default: every k-mer of the input at a load factor of '
+                         '0.5, capped by what the device budget leaves beside the resident alignments)')
+    qp.add_argument('--prefilter', action='store_true',
+                    help='with --kmers: keep most k-mers seen once out of the table (as `kbbq correct --prefilter`); needs '
+                         '--min-count >= 2 where given')
+    qp.add_argument('--filter-bits', type=int, default=None,
+                    help='with --kmers --prefilter: bits per k-mer of the input in each of the filter\'s two arrays, 1..64 (default 4)')
+    qp.add_argument('-u', '--use-oq', action='store_true', help='with --kmers: qualities from the OQ tag instead of QUAL')
     qp.set_defaults(command=bqsr)
 
     cp = sub.add_parser('correct', description='Correct substitution errors of a FASTQ file with k-mer counts (GPU); the output '
@@ -197,6 +231,20 @@ def main(argv=None):
                                       ('--fix-n', args.fix_n or None)) if v is not None]
         if given:
             rp.error('%s: only with -c/--correct' % ', '.join(given))
+    if args.command is bqsr:
+        if args.kmers:
+            given = [flag for flag, v in (('-r/--reference', args.reference), ('-v/--vcf', args.vcf)) if v is not None]
+            if given:
+                qp.error('%s: not with --kmers (its errors come from the alignments\' own k-mers)' % ', '.join(given))
+        else:
+            given = [flag for flag, v in (('-k/--kmer', args.kmer), ('--min-count', args.min_count), ('--slots', args.slots),
+                                          ('--prefilter', args.prefilter or None), ('--filter-bits', args.filter_bits),
+                                          ('-u/--use-oq', args.use_oq or None)) if v is not None]
+            if given:
+                qp.error('%s: only with --kmers' % ', '.join(given))
+            missing = [flag for flag, v in (('-r/--reference', args.reference), ('-v/--vcf', args.vcf)) if v is None]
+            if missing:
+                qp.error('the following arguments are required: %s' % ', '.join(missing))
     args.command(args)
 
 

@@ -9,7 +9,10 @@ released, a table sized from the filter's `admitted` (or `--prefilter-slots`), t
 timed the same way, with the filter's bytes and the device bytes in use at their peak (kbbq_dev_mem_info, planes excluded)
 beside the plain leg's; the leg fails unless its threshold, hist[2:] and corrected plane equal the plain leg's.
 With `--fix-n` every repetition also times kbbq_kmer_correct_ex_dev with KBBQ_KMER_FIX_N on the same table ("ms_correct_fix_n",
-"fixed_n"); `--n-rate` sets that share of the bases to N before anything is counted."""
+"fixed_n"); `--n-rate` sets that share of the bases to N before anything is counted.
+With `--flags` every repetition also times kbbq_kmer_flag_dev (the decision as a flag plane, `kbbq bqsr --kmers`) on the same
+table right after kbbq_kmer_correct_dev ("ms_flags", "flagged_bases"); the leg fails unless the plane is 1 exactly where the
+corrected plane differs from the input."""
 import argparse
 import ctypes
 import json
@@ -30,6 +33,7 @@ ap.add_argument('--prefilter', action='store_true', help='add the prefiltered le
 ap.add_argument('--filter-bits', type=int, default=4)
 ap.add_argument('--prefilter-slots', type=int, default=0, help='table slots of the prefiltered leg (default: from `admitted`)')
 ap.add_argument('--fix-n', action='store_true', help='also time the correct step with the N rule (KBBQ_KMER_FIX_N)')
+ap.add_argument('--flags', action='store_true', help='also time the flag form of the correct step (kbbq_kmer_flag_dev)')
 ap.add_argument('--n-rate', type=float, default=0.0, help='share of the bases set to N')
 args = ap.parse_args()
 
@@ -66,6 +70,7 @@ slots = args.slots or 1 << int(np.ceil(np.log2(distinct * 2)))
 out = torch.empty_like(seq)
 out2 = torch.empty_like(seq) if args.prefilter else None   # the prefiltered leg's plane, compared with the plain one
 out_n = torch.empty_like(seq) if args.fix_n else None     # the plane of the correct step with the N rule
+flags = torch.empty_like(seq) if args.flags else None     # the plane of the flag form
 lib = N.load()
 
 
@@ -96,6 +101,8 @@ res = {'reads': n, 'len': L, 'k': k, 'genome': G, 'err': args.err, 'slots': slot
 ms = {'count': [], 'histogram': [], 'correct': []}
 if args.fix_n:
     ms['correct_fix_n'] = []
+if args.flags:
+    ms['flags'] = []
 dh = torch.zeros(257, dtype=torch.int64, device='cuda')
 for rep in range(args.reps + 1):
     base = rep_base()
@@ -112,9 +119,14 @@ for rep in range(args.reps + 1):
     if args.fix_n:
         xn = timed(lambda: N.check(lib.kbbq_kmer_correct_ex_dev(table.ctx.handle, table.handle, N.ptr(seq), N.ptr(meta), n, pitch, t,
                                                                 N.ptr(out_n), None, N.KMER_FIX_N)))
+    if args.flags:
+        xf = timed(lambda: N.check(lib.kbbq_kmer_flag_dev(table.ctx.handle, table.handle, N.ptr(seq), N.ptr(meta), n, pitch, t,
+                                                          N.ptr(flags), None)))
     table.close()
     if rep:                                            # the first round is the warm-up
         ms['count'].append(c); ms['histogram'].append(h); ms['correct'].append(x)
+        if args.flags:
+            ms['flags'].append(xf)
         if args.fix_n:
             ms['correct_fix_n'].append(xn)
 res.update({'ms_' + key: round(float(np.median(v)), 3) for key, v in ms.items()})
@@ -131,6 +143,11 @@ if args.fix_n:
     res['fixed_n'] = int(((out_n != seq) & (seq == ord('N'))).sum().item())
     res['ms_correct_fix_n_all'] = [round(v, 3) for v in ms['correct_fix_n']]
     assert torch.equal(out_n[seq != ord('N')], out[seq != ord('N')]), 'the N rule changed a base that is no N'
+if args.flags:
+    res['ms_flags_all'] = [round(v, 3) for v in ms['flags']]
+    res['flags_kmers_per_s'] = windows / (res['ms_flags'] * 1e-3)
+    res['flagged_bases'] = int(flags.sum(dtype=torch.int64).item())
+    assert torch.equal(flags, (out != seq).to(torch.uint8)), 'the flag form decided differently from the correction'
 if args.prefilter:
     from kbbq import _device as dev
     plain_out, plain_hist, plain_t = out, hist, t
