@@ -732,7 +732,19 @@ int kbbq_ctx_kernel_ms(kbbq_ctx* ctx, int which, double* total_ms, int64_t* laun
  * [nreads, pitch]) receives 1 at every base where kbbq_kmer_correct_dev would write a byte different from d_seq's and 0
  * everywhere else -- breaks (N included: there is no N rule here), trusted bases, ties, padding up to pitch.  Every byte of every
  * row is written: the plane needs no clearing.  d_changed (may be NULL) as above.  The plane is, bit for bit, the one plane of
- * flags kbbq_accumulate_aligned_dev and kbbq_canonical_reads_rows_dev(d_skip = NULL) read: bit 0 error, bit 1 (skip) never set.
+ * flags kbbq_accumulate_aligned_dev and kbbq_canonical_reads_rows_dev(d_skip = NULL) read: bit 0 error, bit 1 (skip) set only
+ * by kbbq_kmer_flag_ex_dev with KBBQ_KMER_FLAG_UNRESOLVED.
+ * kbbq_kmer_flag_ex_dev: kbbq_kmer_flag_dev plus `d_unresolved` and `int opts`, a word of KBBQ_KMER_* bits; opts = 0 with
+ * d_unresolved = NULL IS kbbq_kmer_flag_dev.  An unknown bit, or KBBQ_KMER_FIX_N (the flag form has no N rule), returns
+ * KBBQ_E_ARG before anything is launched.  The rule above has three outcomes for an A/C/G/T base inside the read: TRUSTED (a solid
+ * k-mer covers it, or no k-mer window covers it at all), ERROR (untrusted, and one substitution makes strictly the most covering
+ * k-mers solid, >= 1) and UNRESOLVED (untrusted -- at least one window covers it, none is solid -- and no substitution wins: a
+ * tie, or none makes a solid k-mer).  An unresolved base is one the k-mers contradict without naming its replacement: two errors
+ * within k bases of each other, a region too thinly covered to have solid k-mers, contamination.  With
+ * KBBQ_KMER_FLAG_UNRESOLVED the byte of an unresolved base is 2 (the tally's skip bit: the base then counts neither as an error
+ * nor as an observation); errors stay 1, trusted bases, breaks (N included) and padding stay 0, no byte is 3 and every byte of
+ * every row is still written.  The decision does not depend on thread order.  d_changed keeps its meaning (bytes set to 1);
+ * d_unresolved (uint32 per read, may be NULL) receives the number of bytes set to 2 in the read -- all zeros with opts = 0.
  * kbbq_kmer_count / kbbq_kmer_correct: the same from host buffers, slab by slab through page-locked staging (KBBQ_STAGE_MB);
  * `changed` (host, may be NULL) receives the per-read counts.  The kernel launches are not timed by kbbq_ctx_timing.
  * Ranks (kbbq/kmer.py count_kmers_ranks): every rank counts its reads into a local table, sends each key to its owner and merges
@@ -761,6 +773,10 @@ int kbbq_kmer_count(kbbq_ctx* ctx, kbbq_kmer_table* table, const uint8_t* seq, c
 int kbbq_kmer_correct(kbbq_ctx* ctx, const kbbq_kmer_table* table, const uint8_t* seq, const uint32_t* meta, int64_t nreads,
                       int pitch, int min_count, uint8_t* out, uint32_t* changed);
 #define KBBQ_KMER_FIX_N 1
+#define KBBQ_KMER_FLAG_UNRESOLVED 2
+int kbbq_kmer_flag_ex_dev(kbbq_ctx* ctx, const kbbq_kmer_table* table, const uint8_t* d_seq, const uint32_t* d_meta,
+                          int64_t nreads, int pitch, int min_count, uint8_t* d_flags, uint32_t* d_changed,
+                          uint32_t* d_unresolved, int opts);
 int kbbq_kmer_correct_ex_dev(kbbq_ctx* ctx, const kbbq_kmer_table* table, const uint8_t* d_seq, const uint32_t* d_meta,
                              int64_t nreads, int pitch, int min_count, uint8_t* d_out, uint32_t* d_changed, int opts);
 int kbbq_kmer_correct_ex(kbbq_ctx* ctx, const kbbq_kmer_table* table, const uint8_t* seq, const uint32_t* meta, int64_t nreads,

@@ -2168,7 +2168,7 @@ static int kmer_rows(kbbq_ctx* c, const char* who, int k, const uint8_t* d_seq, 
     p.seq = d_seq; p.meta = d_meta; p.nrows = n; p.pitch = nib ? pitch / 2 : pitch; p.cpr = pitch / 16; p.k = k;
     p.rows_per_wg = std::max(1, KM_THREADS / p.cpr);
     p.keys = nullptr; p.counts = nullptr; p.mask = 0; p.status = c->d_status;
-    p.min_count = 1; p.out = nullptr; p.changed = nullptr;
+    p.min_count = 1; p.out = nullptr; p.changed = nullptr; p.unresolved = nullptr;
     *lds = ((size_t)lds_words * p.rows_per_wg * p.cpr + p.rows_per_wg) * 4;
     if (*lds > (size_t)c->lds_bytes) return fail(KBBQ_E_ARG, "%s: pitch %d needs %zu bytes of LDS", who, pitch, *lds);
     return KBBQ_OK;
@@ -2195,6 +2195,7 @@ static int kmer_launches(const KmerParams& p, const std::function<void(const Kme
         q.seq = p.seq + (size_t)lo * p.pitch; q.meta = p.meta + lo; q.nrows = m;
         if (p.out) q.out = p.out + (size_t)lo * p.pitch;
         if (p.changed) q.changed = p.changed + lo;
+        if (p.unresolved) q.unresolved = p.unresolved + lo;
         launch(q, (unsigned)((m + p.rows_per_wg - 1) / p.rows_per_wg));
         HIPCHK(hipGetLastError());
     }
@@ -2263,13 +2264,17 @@ static void (*const KM_CORRECT[2][3])(KmerParams) = {
     {km_correct<true, KM_FIXN_OFF>, km_correct<true, KM_FIXN_READS>, km_correct<true, KM_FIXN_PAIRS>},
 };
 
+// ... of the flag form: [KBBQ_KMER_FLAG_UNRESOLVED]
+static void (*const KM_FLAG[2])(KmerParams) = {km_correct<false, KM_FIXN_OFF, true>, km_correct<false, KM_FIXN_OFF, true, true>};
+
 // pairs: two reads to a row (KBBQ_ROWS_PAIRS), which the N rule alone needs to know -- their separator is no N
-// flag_form: d_out is a flag plane (kbbq_kmer_flag_dev; character rows, opts 0)
+// flag_form: d_out is a flag plane (kbbq_kmer_flag_dev / kbbq_kmer_flag_ex_dev; character rows).  Its opts are its own:
+// 0 or KBBQ_KMER_FLAG_UNRESOLVED, checked by the caller; d_unresolved (may be NULL) then receives the per-row count of 2s
 static int kmer_correct_rows(kbbq_ctx* c, const char* who, const kbbq_kmer_table* t, const uint8_t* d_seq, const uint32_t* d_meta,
                              int64_t n, int pitch, bool nib, bool pairs, int min_count, uint8_t* d_out, uint32_t* d_changed, int opts,
-                             bool flag_form = false)
+                             bool flag_form = false, uint32_t* d_unresolved = nullptr)
 {
-    int rc = kmer_correct_opts(who, opts);
+    int rc = flag_form ? KBBQ_OK : kmer_correct_opts(who, opts);
     if (rc) return rc;
     KmerParams p; size_t lds = 0;
     rc = kmer_geometry(c, who, t, d_seq, d_meta, n, pitch, p, 3, &lds, nib);
@@ -2280,7 +2285,10 @@ static int kmer_correct_rows(kbbq_ctx* c, const char* who, const kbbq_kmer_table
     if (n == 0) return KBBQ_OK;
     HIPCHK(hipSetDevice(c->device));
     p.min_count = (u32)min_count; p.out = d_out; p.changed = d_changed;
-    const auto kernel = flag_form ? km_correct<false, KM_FIXN_OFF, true>
+    const bool unres = flag_form && (opts & KBBQ_KMER_FLAG_UNRESOLVED);
+    if (unres) p.unresolved = d_unresolved;
+    else if (d_unresolved) HIPCHK(hipMemsetAsync(d_unresolved, 0, (size_t)n * 4, c->stream));     // no byte is 2 without the option
+    const auto kernel = flag_form ? KM_FLAG[unres ? 1 : 0]
                                   : KM_CORRECT[nib ? 1 : 0][!(opts & KBBQ_KMER_FIX_N) ? KM_FIXN_OFF : pairs ? KM_FIXN_PAIRS : KM_FIXN_READS];
     return kmer_launches(p, [&](const KmerParams& q, unsigned grid) {
         hipLaunchKernelGGL(kernel, dim3(grid), dim3(KM_THREADS), lds, c->stream, q);
@@ -2299,14 +2307,29 @@ int kbbq_kmer_correct_dev(kbbq_ctx* c, const kbbq_kmer_table* t, const uint8_t* 
     return kmer_correct_rows(c, "kbbq_kmer_correct_dev", t, d_seq, d_meta, n, pitch, false, false, min_count, d_out, d_changed, 0);
 }
 
+static int kmer_flag_rows(kbbq_ctx* c, const char* who, const kbbq_kmer_table* t, const uint8_t* d_seq, const uint32_t* d_meta, int64_t n,
+                          int pitch, int min_count, uint8_t* d_flags, uint32_t* d_changed, uint32_t* d_unresolved, int opts)
+{
+    if (opts & ~KBBQ_KMER_FLAG_UNRESOLVED)
+        return fail(KBBQ_E_ARG, "%s: opts 0x%x: the flag form takes KBBQ_KMER_FLAG_UNRESOLVED (%d) alone%s", who, opts,
+                    KBBQ_KMER_FLAG_UNRESOLVED, (opts & KBBQ_KMER_FIX_N) ? " (it has no N rule)" : "");
+    // kbbq_kmer_correct_dev's refusals; those of the numbers alone come first, so that they need no context to be decided
+    int rc = check_planes(who, n, pitch, d_seq, d_flags, nullptr);
+    if (rc) return rc;
+    if (min_count < 1) return fail(KBBQ_E_ARG, "%s: min_count must be >= 1, got %d", who, min_count);
+    return kmer_correct_rows(c, who, t, d_seq, d_meta, n, pitch, false, false, min_count, d_flags, d_changed, opts, true, d_unresolved);
+}
+
 int kbbq_kmer_flag_dev(kbbq_ctx* c, const kbbq_kmer_table* t, const uint8_t* d_seq, const uint32_t* d_meta, int64_t n, int pitch,
                        int min_count, uint8_t* d_flags, uint32_t* d_changed)
 {
-    // kbbq_kmer_correct_dev's refusals; those of the numbers alone come first, so that they need no context to be decided
-    int rc = check_planes("kbbq_kmer_flag_dev", n, pitch, d_seq, d_flags, nullptr);
-    if (rc) return rc;
-    if (min_count < 1) return fail(KBBQ_E_ARG, "kbbq_kmer_flag_dev: min_count must be >= 1, got %d", min_count);
-    return kmer_correct_rows(c, "kbbq_kmer_flag_dev", t, d_seq, d_meta, n, pitch, false, false, min_count, d_flags, d_changed, 0, true);
+    return kmer_flag_rows(c, "kbbq_kmer_flag_dev", t, d_seq, d_meta, n, pitch, min_count, d_flags, d_changed, nullptr, 0);
+}
+
+int kbbq_kmer_flag_ex_dev(kbbq_ctx* c, const kbbq_kmer_table* t, const uint8_t* d_seq, const uint32_t* d_meta, int64_t n, int pitch,
+                          int min_count, uint8_t* d_flags, uint32_t* d_changed, uint32_t* d_unresolved, int opts)
+{
+    return kmer_flag_rows(c, "kbbq_kmer_flag_ex_dev", t, d_seq, d_meta, n, pitch, min_count, d_flags, d_changed, d_unresolved, opts);
 }
 
 static int kmer_correct_rows_flags(kbbq_ctx* c, const char* who, const kbbq_kmer_table* t, const uint8_t* d_seq, const uint32_t* d_meta,

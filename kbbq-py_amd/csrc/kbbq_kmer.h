@@ -35,6 +35,12 @@
 // write another letter, 0 everywhere else -- breaks, trusted bases, ties, padding.  A thread starts from a chunk of zeros
 // instead of the chunk as read (pass 1 has the codes it needs in LDS) and stores its 16 bytes whatever they hold, so every
 // byte of the plane is written: 1 B/base out, where a corrected plane would be written, read back and compared.
+// UNRES (km_correct<false, KM_FIXN_OFF, true, true>; kbbq_kmer_flag_ex_dev with KBBQ_KMER_FLAG_UNRESOLVED): the third outcome of
+// the rule gets a value of its own.  An A/C/G/T base that at least one valid window covers, none of them solid, and for which
+// the substitution loop names no strict winner >= 1 (a tie, or no substitution makes a solid k-mer) becomes 2 -- the skip bit
+// of the aligned tally's flag plane -- at the one point where that loop gives up (km_flag).  A byte is 0, 1 or 2, never 3.
+// The row's counter in LDS then holds the 1s in its low and the 2s in its high 16 bits (a row has at most 65535 bases, and a
+// base is one or the other), so the form keeps nothing more in LDS; KmerParams.unresolved receives the high half.
 //
 // Ranks (kbbq/kmer.py count_kmers_ranks): the owner of a canonical key among W ranks is km_owner(key, W), the high 32 bits of
 // the same mix taken of the key XOR a constant, scaled to 0..W-1.  It shares no bits with the home slot (km_hash(key) & mask),
@@ -74,6 +80,7 @@ struct KmerParams {
     u32 min_count;                    // correct: a k-mer is solid when its count is >= min_count
     uint8_t* out; u32* changed;       // correct: the corrected plane (flag form: the flag plane); per-row count of changed bases (may be NULL)
     u64* status;
+    u32* unresolved;                  // flag form with UNRES: per-row count of bases set to 2 (may be NULL)
 };
 
 __host__ __device__ __forceinline__ u64 km_hash(u64 x)
@@ -332,13 +339,16 @@ __device__ __forceinline__ unsigned __int128 km_breaks(const KmerParams& p, cons
     return b;
 }
 
+// the byte of base t of a chunk of the flag plane (all 0 before) becomes v: 1 error, 2 unresolved
+__device__ __forceinline__ void km_flag(u32 (&w)[4], int t, u32 v) { w[t >> 2] |= v << (8 * (t & 3)); }
+
 // km_correct's store stage: base t of the chunk `w` (4 words of characters, 2 of nibbles) takes the table's code `best`.
 // FLAGS: `w` is the chunk of the flag plane instead, one byte a base, and the base's byte becomes 1.
 template <bool NIB, bool FLAGS>
 __device__ __forceinline__ void km_put(u32 (&w)[4], int t, u32 best)
 {
     if constexpr (FLAGS) {
-        w[t >> 2] |= 1u << (8 * (t & 3));
+        km_flag(w, t, 1u);
     } else if constexpr (NIB) {
         const int sh = km_nib_shift(t & 7);
         w[t >> 3] = (w[t >> 3] & ~(0xFu << sh)) | (km_nib_swap(best) << sh);
@@ -349,10 +359,11 @@ __device__ __forceinline__ void km_put(u32 (&w)[4], int t, u32 best)
     }
 }
 
-template <bool NIB, int FIXN = KM_FIXN_OFF, bool FLAGS = false>
+template <bool NIB, int FIXN = KM_FIXN_OFF, bool FLAGS = false, bool UNRES = false>
 __global__ __launch_bounds__(KM_THREADS) void km_correct(KmerParams p)
 {
     static_assert(!FLAGS || (!NIB && FIXN == KM_FIXN_OFF), "the flag form: character rows, no N rule");
+    static_assert(!UNRES || FLAGS, "unresolved bases are a value of the flag plane: the flag form only");
     extern __shared__ u32 km_lds[];
     const int E = p.rows_per_wg * p.cpr;
     u32* code = km_lds; u32* brk = km_lds + E; u32* sv = km_lds + 2 * E; u32* nchg = km_lds + 3 * E;
@@ -399,7 +410,7 @@ __global__ __launch_bounds__(KM_THREADS) void km_correct(KmerParams p)
             w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
         }
         const u32 brk_own = brk[e];
-        int changed = 0;
+        int changed = 0, unres = 0;
         bool have_words = false;
         unsigned __int128 xa = 0, xb = 0;                                // chunks ch - 2 .. ch + 1 and ch .. ch + 3
         u32 ns = 0;                                                       // N rule: bit t, base t of the chunk is an N of the read
@@ -473,15 +484,30 @@ __global__ __launch_bounds__(KM_THREADS) void km_correct(KmerParams p)
                 if (s[alt] > bs) { bs = s[alt]; best = alt; tie = false; }
                 else if (s[alt] == bs && bs > 0) tie = true;
             }
-            if (best < 0 || tie) continue;
+            if (best < 0 || tie) {                                        // untrusted, and no substitution wins: unresolved
+                if constexpr (UNRES) { km_flag(w, t, 2u); ++unres; }
+                continue;
+            }
             km_put<NIB, FLAGS>(w, t, (u32)best);
             ++changed;
         }
         if constexpr (NIB) *reinterpret_cast<uint2*>(p.out + at) = make_uint2(w[0], w[1]);
         else *reinterpret_cast<uint4*>(p.out + at) = make_uint4(w[0], w[1], w[2], w[3]);
-        if (changed) atomicAdd(&nchg[r], (u32)changed);
+        if constexpr (UNRES) {
+            if (changed | unres) atomicAdd(&nchg[r], (u32)changed | (u32)unres << 16);
+        } else {
+            if (changed) atomicAdd(&nchg[r], (u32)changed);
+        }
     }
-    if (p.changed) {
+    if constexpr (UNRES) {
+        if (p.changed || p.unresolved) {
+            __syncthreads();
+            for (int i = threadIdx.x; i < nr; i += KM_THREADS) {
+                if (p.changed) p.changed[row0 + i] = nchg[i] & 0xFFFFu;
+                if (p.unresolved) p.unresolved[row0 + i] = nchg[i] >> 16;
+            }
+        }
+    } else if (p.changed) {
         __syncthreads();
         for (int i = threadIdx.x; i < nr; i += KM_THREADS) p.changed[row0 + i] = nchg[i];
     }

@@ -27,6 +27,7 @@ APPLY_CHECKED, APPLY_FAST = 0, 1
 ALIGNED_LUT, ALIGNED_F64 = 0, 1
 ROWS_PAIRS, ROWS_NIBBLES, ROWS_TWINS = 1, 2, 4
 KMER_FIX_N = 1                        # the `opts` word of the kbbq_kmer_correct*_ex calls
+KMER_FLAG_UNRESOLVED = 2              # ... and of kbbq_kmer_flag_ex_dev: unresolved bases become 2 in the flag plane
 
 NQ = 43
 NDINUC = 16
@@ -175,6 +176,7 @@ PROTOTYPES = {
     'kbbq_kmer_correct_dev': (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _vp, _vp]),
     'kbbq_kmer_count': (_i, [_vp, _vp, _vp, _vp, _i64, _i]),
     'kbbq_kmer_flag_dev': (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _vp, _vp]),
+    'kbbq_kmer_flag_ex_dev': (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _vp, _vp, _vp, _i]),
     'kbbq_kmer_correct': (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _vp, _vp]),
     'kbbq_kmer_correct_ex_dev': (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _vp, _vp, _i]),
     'kbbq_kmer_correct_ex': (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _vp, _vp, _i]),

@@ -333,7 +333,7 @@ def _kmer_inputs(bamfileobj, k, min_count, prefilter, filter_bits, use_oq, maxsc
 
 
 def bam_to_kmer_covariates(bamfileobj, k=31, min_count=None, slots=None, prefilter=False, filter_bits=4, use_oq=False,
-                           minscore=6, maxscore=42, info=None):
+                           minscore=6, maxscore=42, info=None, skip_unresolved=False):
     """The nine model vectors from aligned reads alone -- no reference, no known sites (`kbbq bqsr --kmers`).  A base is an error
     where the k-mer correction of kbbq.kmer would change it: every k-mer of SEQ of every record is counted (soft clips too:
     they are sequenced bases; keys are canonical, so the alignment's strand does not matter), a k-mer is solid at min_count
@@ -343,7 +343,12 @@ def bam_to_kmer_covariates(bamfileobj, k=31, min_count=None, slots=None, prefilt
     use_oq.  Secondary, supplementary and duplicate records are counted and tallied like any other, as bam_to_bqsr_covariates
     does.  All records must have one query length; one GPU (ValueError in a process group, before any collective).
     prefilter / filter_bits / slots: as kbbq.kmer.correct_reads.  `info`, a dict, receives k, min_count, reads, flagged_bases,
-    slots, prefilter and admitted."""
+    slots, prefilter and admitted.
+    skip_unresolved: an untrusted base for which the correction names no replacement (a tie, or no substitution makes a solid
+    k-mer: two errors within k bases, thin coverage, contamination) is left out of the tally -- neither an error nor an
+    observation, as a base at a known site is in bam_to_bqsr_covariates -- instead of counted as correct.  The flag plane then
+    carries 2, the tally's skip bit, at those bases (kbbq_kmer_flag_ex_dev); `info` also receives skipped_bases, their number
+    over all bases of SEQ, before the tally's own exclusions as flagged_bases is."""
     from .. import _device as dev
     from .. import _solve, fastx, kmer
     b, n, S = _kmer_inputs(bamfileobj, k, min_count, prefilter, filter_bits, use_oq, maxscore)
@@ -376,7 +381,10 @@ def bam_to_kmer_covariates(bamfileobj, k=31, min_count=None, slots=None, prefilt
         if filt is not None:
             filt.close()
         t = int(min_count) if min_count is not None else kmer.solid_threshold(kmer.kmer_histogram(table))
-        err, changed = kmer.flag_errors(table, d_seq, d_len, t)
+        if skip_unresolved:
+            err, changed, skipped = kmer.flag_errors(table, d_seq, d_len, t, unresolved=True)
+        else:
+            err, changed = kmer.flag_errors(table, d_seq, d_len, t)
         nslots = table.slots
     finally:
         if filt is not None:
@@ -391,6 +399,8 @@ def bam_to_kmer_covariates(bamfileobj, k=31, min_count=None, slots=None, prefilt
     if info is not None:
         info.update(k=k, min_count=t, reads=n, flagged_bases=int(changed.cpu().numpy().astype(np.int64).sum()), slots=nslots,
                     prefilter=bool(prefilter), admitted=admitted)
+        if skip_unresolved:
+            info.update(skipped_bases=int(skipped.cpu().numpy().astype(np.int64).sum()))
     return _solve.vectors_from_tables(*tables.to_host(), maxscore)
 
 
@@ -515,10 +525,12 @@ def bam_to_report(bamfileobj, fastafilename, var_pos):
     return vectors_to_report(*vectors, rgs)
 
 
-def bam_to_report_kmers(bamfileobj, k=31, min_count=None, slots=None, prefilter=False, filter_bits=4, use_oq=False, info=None):
+def bam_to_report_kmers(bamfileobj, k=31, min_count=None, slots=None, prefilter=False, filter_bits=4, use_oq=False, info=None,
+                        skip_unresolved=False):
     """Aligned reads -> recalibration report without a reference or known sites: the errors are what the k-mers of the reads'
-    own sequences contradict (bam_to_kmer_covariates); read groups are named by their PU as in bam_to_report."""
+    own sequences contradict (bam_to_kmer_covariates); read groups are named by their PU as in bam_to_report.  skip_unresolved:
+    bases the k-mers contradict without naming a replacement are left out of the tally (bam_to_kmer_covariates)."""
     rgs = list(utils.get_rg_to_pu(bamfileobj).values())
     vectors = bam_to_kmer_covariates(bamfileobj, k=k, min_count=min_count, slots=slots, prefilter=prefilter,
-                                     filter_bits=filter_bits, use_oq=use_oq, info=info)
+                                     filter_bits=filter_bits, use_oq=use_oq, info=info, skip_unresolved=skip_unresolved)
     return vectors_to_report(*vectors, rgs)

@@ -399,11 +399,14 @@ def correct_with(table, seq_plane, meta, min_count, fix_n=False):
     return out, changed[:n]
 
 
-def flag_errors(table, seq_plane, meta, min_count):
+def flag_errors(table, seq_plane, meta, min_count, unresolved=False):
     """(flag plane uint8 [n, pitch], per-read flagged-base counts int32) of device rows against a counted table
     (kbbq_kmer_flag_dev): 1 exactly where correct_with would write another letter, 0 everywhere else, padding included.
     The plane is the one plane of flags the aligned tally reads (bit 0 error; gatk.bqsr.bam_to_kmer_covariates).  Device
-    tensors in, device tensors out; there is no host-buffer form."""
+    tensors in, device tensors out; there is no host-buffer form.
+    unresolved: (flag plane, flagged-base counts, unresolved-base counts int32) of kbbq_kmer_flag_ex_dev with
+    KBBQ_KMER_FLAG_UNRESOLVED -- an untrusted A/C/G/T base for which no substitution wins (a tie, or none makes a solid k-mer)
+    is 2 in the plane, the tally's skip bit; every other byte is what it is without the option."""
     from . import _device as dev
     if not _on_device(seq_plane):
         raise TypeError('flag_errors takes device planes (correct_with takes host buffers too)')
@@ -412,6 +415,12 @@ def flag_errors(table, seq_plane, meta, min_count):
     n, pitch = int(seq_plane.shape[0]), int(seq_plane.shape[1])
     flags = T.empty((max(n, 1), pitch), dtype=T.uint8, device=seq_plane.device)
     changed = T.empty((max(n, 1),), dtype=T.int32, device=seq_plane.device)
+    if unresolved:
+        skipped = T.empty((max(n, 1),), dtype=T.int32, device=seq_plane.device)
+        N.check(N.load().kbbq_kmer_flag_ex_dev(ctx.handle, table.handle, N.ptr(seq_plane), N.ptr(meta), n, pitch, int(min_count),
+                                               N.ptr(flags), N.ptr(changed), N.ptr(skipped), N.KMER_FLAG_UNRESOLVED))
+        ctx.status()
+        return flags[:n], changed[:n], skipped[:n]
     N.check(N.load().kbbq_kmer_flag_dev(ctx.handle, table.handle, N.ptr(seq_plane), N.ptr(meta), n, pitch, int(min_count),
                                         N.ptr(flags), N.ptr(changed)))
     ctx.status()

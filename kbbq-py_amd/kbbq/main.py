@@ -78,12 +78,14 @@ def bqsr(args):
             from . import _device
             _device.use_native_memory()      # as `correct` on one GPU: no torch import
         info = {}
+        skip = dict(skip_unresolved=True) if args.skip_unresolved else {}      # without the flag the call is what it was
         _bqsr.bam_to_report_kmers(aln.AlignmentFile(args.bam), k=31 if args.kmer is None else args.kmer, min_count=args.min_count,
                                   slots=args.slots, prefilter=args.prefilter,
                                   filter_bits=4 if args.filter_bits is None else args.filter_bits, use_oq=args.use_oq,
-                                  info=info).write(args.gatkreport)
-        sys.stderr.write('kbbq bqsr: k=%d min_count=%d reads=%d flagged_bases=%d%s\n'
+                                  info=info, **skip).write(args.gatkreport)
+        sys.stderr.write('kbbq bqsr: k=%d min_count=%d reads=%d flagged_bases=%d%s%s\n'
                          % (info['k'], info['min_count'], info['reads'], info['flagged_bases'],
+                            ' skipped_bases=%d' % info['skipped_bases'] if skip else '',
                             ' prefilter=1 admitted=%d slots=%d' % (info['admitted'], info['slots']) if args.prefilter else ''))
         return
     from . import benchmark as _bm
@@ -194,6 +196,10 @@ def main(argv=None):
     qp.add_argument('--filter-bits', type=int, default=None,
                     help='with --kmers --prefilter: bits per k-mer of the input in each of the filter\'s two arrays, 1..64 (default 4)')
     qp.add_argument('-u', '--use-oq', action='store_true', help='with --kmers: qualities from the OQ tag instead of QUAL')
+    qp.add_argument('--skip-unresolved', action='store_true',
+                    help='with --kmers: leave a base out of the tally (neither error nor observation) when the k-mers contradict '
+                         'it but name no replacement -- two errors within k bases, thin coverage, contamination -- instead of '
+                         'counting it as correct')
     qp.set_defaults(command=bqsr)
 
     cp = sub.add_parser('correct', description='Correct substitution errors of a FASTQ file with k-mer counts (GPU); the output '
@@ -239,7 +245,8 @@ def main(argv=None):
         else:
             given = [flag for flag, v in (('-k/--kmer', args.kmer), ('--min-count', args.min_count), ('--slots', args.slots),
                                           ('--prefilter', args.prefilter or None), ('--filter-bits', args.filter_bits),
-                                          ('-u/--use-oq', args.use_oq or None)) if v is not None]
+                                          ('-u/--use-oq', args.use_oq or None),
+                                          ('--skip-unresolved', args.skip_unresolved or None)) if v is not None]
             if given:
                 qp.error('%s: only with --kmers' % ', '.join(given))
             missing = [flag for flag, v in (('-r/--reference', args.reference), ('-v/--vcf', args.vcf)) if v is None]

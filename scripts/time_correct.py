@@ -12,7 +12,10 @@ With `--fix-n` every repetition also times kbbq_kmer_correct_ex_dev with KBBQ_KM
 "fixed_n"); `--n-rate` sets that share of the bases to N before anything is counted.
 With `--flags` every repetition also times kbbq_kmer_flag_dev (the decision as a flag plane, `kbbq bqsr --kmers`) on the same
 table right after kbbq_kmer_correct_dev ("ms_flags", "flagged_bases"); the leg fails unless the plane is 1 exactly where the
-corrected plane differs from the input."""
+corrected plane differs from the input.
+With `--unresolved` (needs `--flags`) every repetition also times kbbq_kmer_flag_ex_dev with KBBQ_KMER_FLAG_UNRESOLVED right
+after kbbq_kmer_flag_dev ("ms_flags_unresolved", "unresolved_bases"); the leg fails unless its plane with every 2 turned to 0
+is kbbq_kmer_flag_dev's and its per-read counts add up to the plane's 1s and 2s."""
 import argparse
 import ctypes
 import json
@@ -34,8 +37,12 @@ ap.add_argument('--filter-bits', type=int, default=4)
 ap.add_argument('--prefilter-slots', type=int, default=0, help='table slots of the prefiltered leg (default: from `admitted`)')
 ap.add_argument('--fix-n', action='store_true', help='also time the correct step with the N rule (KBBQ_KMER_FIX_N)')
 ap.add_argument('--flags', action='store_true', help='also time the flag form of the correct step (kbbq_kmer_flag_dev)')
+ap.add_argument('--unresolved', action='store_true',
+                help='with --flags: also time the flag form with unresolved bases as 2 (kbbq_kmer_flag_ex_dev)')
 ap.add_argument('--n-rate', type=float, default=0.0, help='share of the bases set to N')
 args = ap.parse_args()
+if args.unresolved and not args.flags:
+    ap.error('--unresolved: only with --flags')
 
 import numpy as np
 import torch
@@ -71,6 +78,7 @@ out = torch.empty_like(seq)
 out2 = torch.empty_like(seq) if args.prefilter else None   # the prefiltered leg's plane, compared with the plain one
 out_n = torch.empty_like(seq) if args.fix_n else None     # the plane of the correct step with the N rule
 flags = torch.empty_like(seq) if args.flags else None     # the plane of the flag form
+flags_u = torch.empty_like(seq) if args.unresolved else None      # ... with unresolved bases as 2
 lib = N.load()
 
 
@@ -103,6 +111,10 @@ if args.fix_n:
     ms['correct_fix_n'] = []
 if args.flags:
     ms['flags'] = []
+if args.unresolved:
+    ms['flags_unresolved'] = []
+    n_err = torch.empty((n,), dtype=torch.int32, device='cuda')
+    n_unres = torch.empty((n,), dtype=torch.int32, device='cuda')
 dh = torch.zeros(257, dtype=torch.int64, device='cuda')
 for rep in range(args.reps + 1):
     base = rep_base()
@@ -122,11 +134,17 @@ for rep in range(args.reps + 1):
     if args.flags:
         xf = timed(lambda: N.check(lib.kbbq_kmer_flag_dev(table.ctx.handle, table.handle, N.ptr(seq), N.ptr(meta), n, pitch, t,
                                                           N.ptr(flags), None)))
+    if args.unresolved:
+        xu = timed(lambda: N.check(lib.kbbq_kmer_flag_ex_dev(table.ctx.handle, table.handle, N.ptr(seq), N.ptr(meta), n, pitch, t,
+                                                             N.ptr(flags_u), N.ptr(n_err), N.ptr(n_unres),
+                                                             N.KMER_FLAG_UNRESOLVED)))
     table.close()
     if rep:                                            # the first round is the warm-up
         ms['count'].append(c); ms['histogram'].append(h); ms['correct'].append(x)
         if args.flags:
             ms['flags'].append(xf)
+        if args.unresolved:
+            ms['flags_unresolved'].append(xu)
         if args.fix_n:
             ms['correct_fix_n'].append(xn)
 res.update({'ms_' + key: round(float(np.median(v)), 3) for key, v in ms.items()})
@@ -148,6 +166,12 @@ if args.flags:
     res['flags_kmers_per_s'] = windows / (res['ms_flags'] * 1e-3)
     res['flagged_bases'] = int(flags.sum(dtype=torch.int64).item())
     assert torch.equal(flags, (out != seq).to(torch.uint8)), 'the flag form decided differently from the correction'
+if args.unresolved:
+    res['ms_flags_unresolved_all'] = [round(v, 3) for v in ms['flags_unresolved']]
+    res['unresolved_bases'] = int((flags_u == 2).sum(dtype=torch.int64).item())
+    assert torch.equal(torch.where(flags_u == 2, torch.zeros_like(flags_u), flags_u), flags), 'the option changed a byte that is no 2'
+    assert int(n_err.sum(dtype=torch.int64).item()) == res['flagged_bases'], 'd_changed does not add up to the 1s'
+    assert int(n_unres.sum(dtype=torch.int64).item()) == res['unresolved_bases'], 'd_unresolved does not add up to the 2s'
 if args.prefilter:
     from kbbq import _device as dev
     plain_out, plain_hist, plain_t = out, hist, t
