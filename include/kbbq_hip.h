@@ -407,6 +407,29 @@ int kbbq_tally_aligned_dev(kbbq_ctx* ctx, const uint8_t* d_seq, const uint8_t* d
                            uint8_t* d_flagplane, int R, int minscore, int dinuc_minscore, int64_t* d_tables);
 int kbbq_count_q_dev(kbbq_ctx* ctx, const uint8_t* d_qual, const uint8_t* d_err, const uint8_t* d_skip,
                      const uint32_t* d_len, int64_t nreads, int pitch, int qoffset, int64_t* d_counts512);
+/* kbbq_flag_confusion_dev: the joint tally of TWO answers to "which base is an error" by reported quality -- what
+ * `kbbq benchmark --kmers` prints.  d_qual, d_truth and d_kflags are [nreads, pitch] byte planes of the same rows in the same
+ * orientation, 16-byte aligned, pitch a positive multiple of 16; d_len the reads' lengths.
+ *   d_truth   kbbq_find_errors_dev's ONE plane of flags: bit 0 error, bit 1 skip;
+ *   d_kflags  the plane of kbbq_kmer_flag_ex_dev (KBBQ_KMER_FLAG_UNRESOLVED): 0 trusted, 1 error, 2 unresolved;
+ *   d_qual    quality bytes; a base's quality is byte - qoffset (33 for characters, 0 for values).
+ * A base is counted when it lies inside its read (i < d_len[r]) and its skip bit is clear; it ADDS one to
+ *   d_counts1536[q][e][k]   (int64 [256][2][3], C order)   e = bit 0 of the truth byte,
+ *                                                           k = 1 if bit 0 of the kflags byte is set, else 2 if bit 1 is, else 0.
+ * Nothing else is looked at: bytes at or beyond a read's length and bytes of skipped bases may hold anything.  A COUNTED base
+ * whose byte is below qoffset is counted nowhere and makes kbbq_ctx_status return KBBQ_E_RANGE with its read, as
+ * kbbq_count_q_dev does; the same byte at a skipped base or behind the read does not.
+ * Summed over k the counts are kbbq_count_q_dev's: counts[q][0][*] + counts[q][1][*] its totals, counts[q][1][*] its errors.
+ * ONE CALL TAKES AT MOST KBBQ_CONFUSION_MAX_BASES = 2^32 - 1 BASES (nreads * pitch): the kernel counts in 32-bit words of LDS
+ * that it flushes once, and a word receives at most one increment per byte of the planes, so none can wrap below that bound.
+ * More rows: KBBQ_E_ARG naming the limit -- cut them into several calls; they add into the same counts.
+ * Refused on the arguments alone, before any HIP call (KBBQ_E_ARG, the function's name in kbbq_last_error()): a NULL ctx, plane,
+ * d_len or d_counts1536; nreads < 0; a pitch that is not a positive multiple of 16; planes not 16-byte aligned; a qoffset
+ * outside 0..255; the limit.
+ * nreads == 0 returns KBBQ_OK and launches nothing.                                                                   */
+#define KBBQ_CONFUSION_MAX_BASES 4294967295ull
+int kbbq_flag_confusion_dev(kbbq_ctx* ctx, const uint8_t* d_qual, const uint8_t* d_truth, const uint8_t* d_kflags,
+                            const uint32_t* d_len, int64_t nreads, int pitch, int qoffset, int64_t* d_counts1536);
 
 /* ---- mate-pair rows: an optional device layout for paired reads of one length S --------------
  * One row per pair: [mate 1: S bytes][separator][mate 2: S bytes][padding to a multiple of 16];

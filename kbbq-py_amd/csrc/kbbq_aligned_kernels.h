@@ -766,3 +766,78 @@ __global__ __launch_bounds__(K5_THREADS) void k5_count_q(K5Params p)
     }
     flush();
 }
+
+// ---------------------------------------------------------------- K5J: K5 with a second flag plane
+// The joint tally of K4's one plane of flags (bit 0 error, bit 1 skip) and the plane of kbbq_kmer_flag_ex_dev (0 trusted,
+// 1 error, 2 unresolved; bit 0 wins over bit 1) by quality: counts[q][truth error][k-mer class], 256 x 2 x 3.
+// K5's shape: lane <-> 16-byte chunk, three 16-byte loads per chunk (3 B/base), the next chunk's loads issued before the current
+// one is binned, bin 256 = trash (skipped sites, bytes past the read, values below the offset) so that every byte of a chunk
+// that holds a base costs exactly one unconditional LDS atomic.
+// LDS: [257 bins][6 cells][8 copies] u32 = 49,344 bytes, copy = lane & 7.  The counters are FULL 32-bit words and are flushed
+// once: a counter receives at most one increment per byte the workgroup reads, the launch reads at most nreads * pitch bytes,
+// and kbbq_flag_confusion_dev refuses nreads * pitch > 2^32 - 1 -- no counter can wrap, whatever the grid and the data.
+#define K5J_THREADS 256
+#define K5J_COPIES 8
+#define K5J_CELLS 6
+#define K5J_WG_PER_CU 3              // what 160 KB of LDS hold of these workgroups: the grid is resident, every workgroup zeroes and flushes once
+struct K5JParams {
+    const uint8_t* qual; const uint8_t* truth; const uint8_t* kflags; const u32* len;
+    long long nreads; int pitch; int cpr; int qoffset;
+    u64* counts;                     // [256][2][3]
+    u64* status;
+};
+
+__global__ __launch_bounds__(K5J_THREADS) void k5j_flag_confusion(K5JParams p)
+{
+    __shared__ u32 h[257 * K5J_CELLS * K5J_COPIES];
+    for (int i = threadIdx.x; i < 257 * K5J_CELLS * K5J_COPIES; i += blockDim.x) h[i] = 0u;
+    __syncthreads();
+    const long long nchunks = p.nreads * p.cpr;                              // < 2^28 (the launch bound above)
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    const u32 copy = threadIdx.x & (K5J_COPIES - 1);
+    struct Chunk { uint4 q, t, k; long long r; int nb; };
+    auto fetch = [&](long long ch, Chunk& c) {
+        c.nb = 0; c.r = 0;
+        if (ch >= nchunks) return;
+        const u32 r = (u32)ch / (u32)p.cpr;
+        const int j = (int)((u32)ch - r * (u32)p.cpr);
+        c.r = r;
+        c.nb = (int)p.len[r] - 16 * j;
+        if (c.nb <= 0) return;
+        const size_t off = (size_t)r * p.pitch + (size_t)16 * j;
+        c.q = *reinterpret_cast<const uint4*>(p.qual + off);
+        c.t = *reinterpret_cast<const uint4*>(p.truth + off);
+        c.k = *reinterpret_cast<const uint4*>(p.kflags + off);
+    };
+    long long ch = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    Chunk cur, nxt;
+    fetch(ch, cur);
+    for (; ch < nchunks; ch += stride) {
+        fetch(ch + stride, nxt);
+        if (cur.nb > 0) {
+            const int nb = cur.nb;
+            const u32 q[4] = {cur.q.x, cur.q.y, cur.q.z, cur.q.w}, t[4] = {cur.t.x, cur.t.y, cur.t.z, cur.t.w}, k[4] = {cur.k.x, cur.k.y, cur.k.z, cur.k.w};
+            bool negative = false;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                const int sh = 8 * (i & 3);
+                const int qq = (int)((q[i >> 2] >> sh) & 0xFFu) - p.qoffset;
+                const u32 tb = t[i >> 2] >> sh, kb = k[i >> 2] >> sh;
+                const bool counted = i < nb && (tb & 2u) == 0u;
+                negative |= counted && qq < 0;                               // as K5: np.bincount rejects negative values
+                const u32 bin = (counted && qq >= 0) ? (u32)qq : 256u;
+                const u32 cell = (tb & 1u) * 3u + ((kb & 1u) ? 1u : (kb & 2u));
+                atomicAdd(&h[(bin * K5J_CELLS + cell) * K5J_COPIES + copy], 1u);
+            }
+            if (negative) flag(p.status, ST_RANGE, cur.r);
+        }
+        cur = nxt;
+    }
+    __syncthreads();
+    for (int b = threadIdx.x; b < 256 * K5J_CELLS; b += blockDim.x) {        // the LDS cell index IS the index into counts
+        u64 v = 0ull;
+#pragma unroll
+        for (int c = 0; c < K5J_COPIES; ++c) v += h[b * K5J_COPIES + c];
+        if (v) atomicAdd(&p.counts[b], v);
+    }
+}

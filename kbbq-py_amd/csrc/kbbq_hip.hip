@@ -1787,6 +1787,34 @@ int kbbq_count_q_dev(kbbq_ctx* c, const uint8_t* d_qual, const uint8_t* d_err, c
     return KBBQ_OK;
 }
 
+int kbbq_flag_confusion_dev(kbbq_ctx* c, const uint8_t* d_qual, const uint8_t* d_truth, const uint8_t* d_kflags,
+                            const uint32_t* d_len, int64_t nreads, int pitch, int qoffset, int64_t* d_counts1536)
+{
+    if (!c) return fail(KBBQ_E_ARG, "ctx is NULL");
+    if (!d_qual || !d_truth || !d_kflags) return fail(KBBQ_E_ARG, "kbbq_flag_confusion_dev: NULL plane");
+    if (!d_len || !d_counts1536) return fail(KBBQ_E_ARG, "kbbq_flag_confusion_dev: NULL d_len or d_counts1536");
+    int rc = check_planes("kbbq_flag_confusion_dev", nreads, pitch, d_qual, d_truth, d_kflags);
+    if (rc) return rc;
+    // byte - qoffset indexes 257 bins: a negative offset would carry it past them
+    if (qoffset < 0 || qoffset > 255) return fail(KBBQ_E_ARG, "kbbq_flag_confusion_dev: qoffset must be in 0..255, got %d", qoffset);
+    // the kernel's LDS counters are 32 bits wide and flushed once: one increment per byte read at most
+    if (nreads > (int64_t)(KBBQ_CONFUSION_MAX_BASES / (uint64_t)pitch))
+        return fail(KBBQ_E_ARG, "kbbq_flag_confusion_dev: nreads * pitch = %lld * %d exceeds %llu bases per call (32-bit counters): "
+                    "split the rows over several calls, which add into the same counts", (long long)nreads, pitch,
+                    (unsigned long long)KBBQ_CONFUSION_MAX_BASES);
+    if (nreads == 0) return KBBQ_OK;
+    HIPCHK(hipSetDevice(c->device));
+    K5JParams p;
+    p.qual = d_qual; p.truth = d_truth; p.kflags = d_kflags; p.len = d_len; p.nreads = nreads; p.pitch = pitch;
+    p.cpr = pitch / 16; p.qoffset = qoffset;
+    p.counts = reinterpret_cast<u64*>(d_counts1536); p.status = c->d_status;
+    const int64_t nchunks = nreads * p.cpr;
+    const int gx = bounded_grid((nchunks + K5J_THREADS - 1) / K5J_THREADS, c, K5J_WG_PER_CU);
+    hipLaunchKernelGGL(k5j_flag_confusion, dim3((unsigned)gx), dim3(K5J_THREADS), 0, c->stream, p);
+    HIPCHK(hipGetLastError());
+    return KBBQ_OK;
+}
+
 // ---- host-buffer entry points: stage, run, fetch -------------------------
 struct DevBuf {
     void* p = nullptr;

@@ -28,6 +28,7 @@ ALIGNED_LUT, ALIGNED_F64 = 0, 1
 ROWS_PAIRS, ROWS_NIBBLES, ROWS_TWINS = 1, 2, 4
 KMER_FIX_N = 1                        # the `opts` word of the kbbq_kmer_correct*_ex calls
 KMER_FLAG_UNRESOLVED = 2              # ... and of kbbq_kmer_flag_ex_dev: unresolved bases become 2 in the flag plane
+CONFUSION_MAX_BASES = (1 << 32) - 1   # KBBQ_CONFUSION_MAX_BASES: nreads * pitch of one kbbq_flag_confusion_dev call
 
 NQ = 43
 NDINUC = 16
@@ -95,6 +96,7 @@ PROTOTYPES = {
     'kbbq_accumulate_aligned_dev': (_i, [_vp] * 7 + [_i64, _i, _i, _i, _i, _i, _vp]),
     'kbbq_tally_aligned_dev': (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i] + [_vp] * 6 + [_i64] + [_vp] * 4 + [_i, _i, _i, _vp]),
     'kbbq_count_q_dev': (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _vp]),
+    'kbbq_flag_confusion_dev': (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _vp]),
     'kbbq_pair_pitch': (_i, [_i]),
     'kbbq_pair_lut_bytes': (_sz, [_i, _i, _i]),
     'kbbq_pack_pairs_dev': (_i, [_vp] * 5 + [_i64, _i, _i] + [_vp] * 4),

@@ -429,11 +429,177 @@ def print_benchmark(actual_q, label, nbases):
         print(pq, aq, label, nb, sep="\t")
 
 
-def benchmark(bamfile, fafile, vcffile, fastqfile=None, label=None, use_oq=False, bedfh=None):
-    """Run the benchmark and print it.  With a FASTQ, its reads are matched to the alignments by name."""
+# ---------------------------------------------------------------------------
+# benchmark --kmers: the k-mer rule's flags against the truth set's
+# ---------------------------------------------------------------------------
+CONFUSION_BASES_PER_LAUNCH = (1 << 32) - 1     # KBBQ_CONFUSION_MAX_BASES: what one kbbq_flag_confusion_dev call takes (nreads * pitch)
+
+KMER_COLUMNS = ('#predicted_q', 'bases', 'errors', 'flagged', 'flagged_errors', 'unresolved', 'unresolved_errors', 'actual_q',
+                'kmer_q', 'kmer_q_skip', 'label')
+
+
+def kmer_confusion(qual, truth, kflags, lens, pitch, qoffset):
+    """The joint tally of K4's one plane of flags (`truth`: bit 0 error, bit 1 skip) and the k-mer rule's plane (`kflags`:
+    kbbq.kmer.flag_errors(unresolved=True): 0 trusted, 1 error, 2 unresolved) by quality: an int64 host array
+    joint[q][truth error][k-mer class] of shape (256, 2, 3) over the bases inside their reads whose skip bit is clear
+    (kbbq_flag_confusion_dev).  qual / truth / kflags: device planes [n, pitch] of the same rows; lens: host array.  The rows
+    go in launches of at most CONFUSION_BASES_PER_LAUNCH bases (the kernel's counters are 32 bits wide), which all add into
+    the same device counters.  A counted base whose quality byte is below qoffset: ValueError with its read."""
+    from . import _device as dev
+    from . import _native as N
+    torch = dev._torch()
+    n = len(lens)
+    counts = torch.zeros(256 * 2 * 3, dtype=torch.int64, device='cuda')
+    if n:
+        d_len = torch.from_numpy(np.ascontiguousarray(np.asarray(lens).astype(np.uint32)).view(np.int32)).cuda()
+        step = max(1, int(CONFUSION_BASES_PER_LAUNCH) // int(pitch))
+        ctx = dev.context()
+        lib = N.load()
+        for lo in range(0, n, step):
+            hi = min(lo + step, n)
+            N.check(lib.kbbq_flag_confusion_dev(ctx.handle, N.ptr(qual[lo:hi]), N.ptr(truth[lo:hi]), N.ptr(kflags[lo:hi]),
+                                                N.ptr(d_len[lo:hi]), hi - lo, pitch, qoffset, N.ptr(counts)))
+            try:
+                ctx.status()
+            except ValueError as exc:
+                i = getattr(exc, 'read_index', -1)
+                if lo == 0 or i < 0:
+                    raise
+                raise _at(ValueError('read %d: a counted base has a quality byte below the offset %d (row %d of the launch that '
+                                     'began at read %d)' % (lo + i, qoffset, i, lo)), lo + i) from None
+    return counts.cpu().numpy().reshape(256, 2, 3).copy()
+
+
+def _kmer_benchmark_inputs(bamfile, k, min_count, prefilter, filter_bits):
+    """Everything benchmark_kmers refuses on its arguments, before any device call and, in a process group, before any
+    collective (as gatk.bqsr._kmer_inputs)."""
+    from . import kmer
+    if kmer._ranks() is not None:
+        raise ValueError('benchmark --kmers does not run across ranks yet: the k-mer table of the alignments is counted and '
+                         'read on one GPU; run `kbbq benchmark` without --kmers under ranks, or with --kmers on one GPU')
+    if not 8 <= int(k) <= 32:
+        raise ValueError('k must be in 8..32, got %d' % int(k))
+    if min_count is not None and int(min_count) < 1:
+        raise ValueError('min_count must be >= 1, got %d' % int(min_count))
+    if prefilter:
+        kmer._check_prefilter(min_count, filter_bits)
+    if not isinstance(bamfile, aln.AlignmentFile):
+        raise TypeError('benchmark_kmers takes a kbbq.aln.AlignmentFile (its batch() arrays), got %s' % type(bamfile).__name__)
+    return bamfile.batch()
+
+
+def benchmark_kmers(bamfile, ref, var_sites, k=31, min_count=None, slots=None, prefilter=False, filter_bits=4, use_oq=False,
+                    bedfh=None, info=None):
+    """How good is the k-mer rule on a truth set?  joint[q][truth error][k-mer class], int64 (256, 2, 3): every base of the
+    alignments that benchmark_bam counts (not at a variant site, inside the BED, not soft-clipped), by its reported quality
+    (QUAL, or the OQ tag with use_oq), by whether it differs from the reference (K4, exactly as benchmark_bam flags it) and
+    by what the k-mers of the alignments' own sequences say about it: 0 trusted, 1 error, 2 unresolved (untrusted, and no
+    substitution wins) -- the decisions `kbbq bqsr --kmers [--skip-unresolved]` tallies.
+    The k-mers are counted from the SEQ plane uploaded for K4: every base of every record, soft clips included, canonical
+    keys; then as gatk.bqsr.bam_to_kmer_covariates: optional prefilter, a table of default_slots within the device budget less
+    the four resident planes (or `slots`), the count histogram's first valley unless min_count is given, flag_errors with
+    unresolved bases.  Records may have any lengths (a record shorter than k has no k-mer: all its bases are class 0).
+    One GPU; bamfile is a kbbq.aln.AlignmentFile.  `info`, a dict, receives k, min_count, reads, slots, prefilter, admitted,
+    bases, errors, flagged, flagged_errors, unresolved and unresolved_errors (totals over the counted bases)."""
+    from . import _device as dev
+    from . import kmer
+    b = _kmer_benchmark_inputs(bamfile, k, min_count, prefilter, filter_bits)
+    k = int(k)
+    torch = dev._torch()
+    fullskips = get_full_skips(ref, var_sites, bedfh)
+    genome = _Genome(ref, fullskips)
+    keep = {}
+    truth, _, lens, pitch = _flag_batch(bamfile, genome, flip_reverse=False, keep=keep, fused=True)
+    qual = _qual_chars_dev(bamfile, lens, pitch, use_oq)
+    n = len(lens)
+    t, nslots, admitted = (int(min_count) if min_count is not None else 0), 0, None
+    if n:
+        d_seq = keep['seq']
+        d_len = torch.from_numpy(np.ascontiguousarray(lens.astype(np.uint32)).view(np.int32)).cuda()
+        budget = dev.device_budget()
+        resident = 4 * n * pitch + 20 * n           # SEQ, qualities, the truth flags and the k-mer flags; the per-read words
+        windows = kmer.kmer_total(lens, k)
+        filt = table = None
+        try:
+            if prefilter:
+                filt = kmer.prefilter_kmers(d_seq, d_len, k=k, filter=kmer.KmerFilter(kmer.filter_words(windows, filter_bits)))
+                admitted = filt.admitted
+                filt.release_seen()
+            if slots is None:
+                slots = kmer.default_slots(admitted if prefilter else windows,
+                                           budget - resident - (filt.nbytes if filt is not None else 0))
+            table = kmer.count_kmers(d_seq, d_len, k=k, slots=slots, filter=filt)
+            if filt is not None:
+                filt.close()
+            t = int(min_count) if min_count is not None else kmer.solid_threshold(kmer.kmer_histogram(table))
+            kflags, _, _ = kmer.flag_errors(table, d_seq, d_len, t, unresolved=True)
+            nslots = table.slots
+        finally:
+            if filt is not None:
+                filt.close()
+            if table is not None:
+                table.close()
+        joint = kmer_confusion(qual, truth, kflags, lens, pitch, 33)
+    else:
+        joint = np.zeros((256, 2, 3), dtype=np.int64)
+    if info is not None:
+        info.update(k=k, min_count=t, reads=n, slots=nslots, prefilter=bool(prefilter), admitted=admitted, **kmer_totals(joint))
+    return joint
+
+
+def kmer_totals(joint):
+    """The totals of a joint array over all qualities: bases, errors, flagged, flagged_errors, unresolved, unresolved_errors."""
+    J = np.asarray(joint).sum(axis=0)
+    return dict(bases=int(J.sum()), errors=int(J[1].sum()), flagged=int(J[:, 1].sum()), flagged_errors=int(J[1, 1]),
+                unresolved=int(J[:, 2].sum()), unresolved_errors=int(J[1, 2]))
+
+
+def kmer_summary(info):
+    """The one line `kbbq benchmark --kmers` writes to stderr (without the newline); a ratio whose denominator is 0 prints 0.0000."""
+    ratio = lambda a, b: (a / b) if b else 0.0
+    line = ('kbbq benchmark: k=%d min_count=%d reads=%d bases=%d errors=%d flagged=%d flagged_errors=%d unresolved=%d '
+            'unresolved_errors=%d precision=%.4f recall=%.4f'
+            % (info['k'], info['min_count'], info['reads'], info['bases'], info['errors'], info['flagged'], info['flagged_errors'],
+               info['unresolved'], info['unresolved_errors'], ratio(info['flagged_errors'], info['flagged']),
+               ratio(info['flagged_errors'], info['errors'])))
+    if info.get('prefilter'):
+        line += ' prefilter=1 admitted=%d slots=%d' % (info['admitted'], info['slots'])
+    return line
+
+
+def print_benchmark_kmers(joint, label):
+    """A header line, then one tab-separated row per quality with bases != 0, ascending.  With J = joint[q]: bases J.sum(),
+    errors J[1].sum(), flagged J[:, 1].sum(), flagged_errors J[1, 1], unresolved J[:, 2].sum(), unresolved_errors J[1, 2];
+    actual_q = p_to_q(errors / bases), what `benchmark` prints; kmer_q = p_to_q(flagged / bases), the quality `bqsr --kmers`
+    tallies; kmer_q_skip = p_to_q(flagged / (bases - unresolved)), 0 where that denominator is 0, what `--skip-unresolved`
+    tallies."""
+    joint = np.asarray(joint)
+    print(*KMER_COLUMNS, sep='\t')
+    for q in np.flatnonzero(joint.sum(axis=(1, 2))):
+        J = joint[q]
+        bases, errors, flagged, unresolved = int(J.sum()), int(J[1].sum()), int(J[:, 1].sum()), int(J[:, 2].sum())
+        p_to_q = lambda a, b: int(compare_reads.p_to_q(np.true_divide(a, b)))
+        print(int(q), bases, errors, flagged, int(J[1, 1]), unresolved, int(J[1, 2]), p_to_q(errors, bases), p_to_q(flagged, bases),
+              p_to_q(flagged, bases - unresolved) if bases != unresolved else 0, label, sep='\t')
+
+
+def benchmark(bamfile, fafile, vcffile, fastqfile=None, label=None, use_oq=False, bedfh=None, kmers=None):
+    """Run the benchmark and print it.  With a FASTQ, its reads are matched to the alignments by name.  kmers: a dict of
+    benchmark_kmers' options (k, min_count, slots, prefilter, filter_bits) -- print the k-mer rule's flags against the truth
+    set's instead (print_benchmark_kmers) and one summary line on stderr."""
+    if kmers is not None and fastqfile is not None:
+        raise ValueError('benchmark --kmers takes the alignments alone (-b), not a FASTQ joined by name (-f)')
     bam = aln.AlignmentFile(bamfile, 'r')
     ref = get_ref_dict(fafile)
     var_sites = get_var_sites(vcffile)
+    if kmers is not None:
+        import sys
+        info = {}
+        joint = benchmark_kmers(bam, ref, var_sites, use_oq=use_oq, bedfh=bedfh, info=info, **kmers)
+        print_benchmark_kmers(joint, bamfile if label is None else label)
+        sys.stdout.flush()
+        sys.stderr.write(kmer_summary(info) + '\n')
+        return
     if fastqfile is not None:
         actual_q, nbases = benchmark_fastq(fastqfile, bam, ref, var_sites, bedfh)
         label = (fastqfile if label is None else label)

@@ -55,8 +55,12 @@ def benchmark(args):
     from . import benchmark as _bm
     from . import parallel
     parallel.init_from_env()          # one process per GPU under torch.distributed.run; no-op otherwise
+    kmers = {}
+    if args.kmers:                                                             # without the flag the call is what it was
+        kmers = dict(kmers=dict(k=31 if args.kmer is None else args.kmer, min_count=args.min_count, slots=args.slots,
+                                prefilter=args.prefilter, filter_bits=4 if args.filter_bits is None else args.filter_bits))
     _bm.benchmark(bamfile=args.bam, fafile=args.reference, vcffile=args.vcf, fastqfile=args.fastq,
-                  label=args.label, use_oq=args.use_oq, bedfh=args.bedfile)
+                  label=args.label, use_oq=args.use_oq, bedfh=args.bedfile, **kmers)
 
 
 def applybqsr(args):
@@ -162,6 +166,22 @@ def main(argv=None):
     bp.add_argument('-u', '--use-oq', action='store_true', help='Use the OQ tag for quality scores')
     bp.add_argument('-d', '--bedfile', type=argparse.FileType('r'),
                     help='BED file of confident regions. Sites outside the given regions will be skipped.')
+    bp.add_argument('--kmers', action='store_true',
+                    help='score the k-mer rule of `kbbq correct` / `bqsr --kmers` against the truth set: per reported quality, '
+                         'the bases the alignments\' own k-mers flag as errors or leave unresolved beside the true errors, and '
+                         'the quality each reading of the flags implies; a summary with precision and recall on stderr; one '
+                         'GPU, not with -f')
+    bp.add_argument('-k', '--kmer', type=int, default=None, help='with --kmers: k-mer length, 8..32 (default 31)')
+    bp.add_argument('--min-count', type=int, default=None,
+                    help='with --kmers: k-mers seen at least this often are solid (default: the first valley of the count histogram)')
+    bp.add_argument('--slots', type=int, default=None,
+                    help='with --kmers: hash table slots, a power of two (default: every k-mer of the input at a load factor of '
+                         '0.5, capped by what the device budget leaves beside the resident alignments)')
+    bp.add_argument('--prefilter', action='store_true',
+                    help='with --kmers: keep most k-mers seen once out of the table (as `kbbq correct --prefilter`); needs '
+                         '--min-count >= 2 where given')
+    bp.add_argument('--filter-bits', type=int, default=None,
+                    help='with --kmers --prefilter: bits per k-mer of the input in each of the filter\'s two arrays, 1..64 (default 4)')
     bp.set_defaults(command=benchmark)
 
     ap = sub.add_parser('applybqsr', description='Recalibrate alignments with a GATK recalibration report (SAM output)')
@@ -237,6 +257,16 @@ def main(argv=None):
                                       ('--fix-n', args.fix_n or None)) if v is not None]
         if given:
             rp.error('%s: only with -c/--correct' % ', '.join(given))
+    if args.command is benchmark:
+        if args.kmers:
+            if args.fastq is not None:
+                bp.error('-f/--fastq: not with --kmers (the k-mers are those of the alignments\' own sequences)')
+        else:
+            given = [flag for flag, v in (('-k/--kmer', args.kmer), ('--min-count', args.min_count), ('--slots', args.slots),
+                                          ('--prefilter', args.prefilter or None), ('--filter-bits', args.filter_bits))
+                     if v is not None]
+            if given:
+                bp.error('%s: only with --kmers' % ', '.join(given))
     if args.command is bqsr:
         if args.kmers:
             given = [flag for flag, v in (('-r/--reference', args.reference), ('-v/--vcf', args.vcf)) if v is not None]
