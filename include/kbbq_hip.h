@@ -768,6 +768,21 @@ int kbbq_ctx_kernel_ms(kbbq_ctx* ctx, int which, double* total_ms, int64_t* laun
  * nor as an observation); errors stay 1, trusted bases, breaks (N included) and padding stay 0, no byte is 3 and every byte of
  * every row is still written.  The decision does not depend on thread order.  d_changed keeps its meaning (bytes set to 1);
  * d_unresolved (uint32 per read, may be NULL) receives the number of bytes set to 2 in the read -- all zeros with opts = 0.
+ * Passes (kbbq correct --passes P): kbbq_kmer_correct_passes_dev / kbbq_kmer_correct_passes / kbbq_kmer_correct_rows_passes_dev /
+ * kbbq_kmer_flag_passes_dev are kbbq_kmer_correct_ex_dev / kbbq_kmer_correct_ex / kbbq_kmer_correct_rows_ex_dev /
+ * kbbq_kmer_flag_ex_dev plus `int passes` (1..8), with every refusal of those calls; passes outside 1..8 returns KBBQ_E_ARG before
+ * anything is launched, and passes = 1 IS the call without it (the same kernel).  Let C(row) be the rule above on one row --
+ * the substitution rule, and with KBBQ_KMER_FIX_N the N rule -- against the table at min_count.  The table, and so every count,
+ * comes from the reads as read: nothing is recounted between passes.  r_0 is the row as read and r_p = C(r_(p-1)): within a pass
+ * every base is judged against r_(p-1) (no cascade inside a pass), an N fixed in pass p is an ordinary base from pass p + 1 on,
+ * an N that stayed N may be fixed by a later pass once its windows have become solid, and the separator of a row of two reads
+ * is never an N.  A pass that changes nothing in a row ends that row, later passes would repeat it.  The result is r_P and does not
+ * depend on thread order.  Corrected form: d_out receives r_P, breaks and padding as read; d_changed the number of bases inside
+ * the read where r_P differs from r_0 (not the sum of the passes' changes: a base changed and changed back counts nothing).
+ * Flag form: 1 where r_P differs from r_0; with KBBQ_KMER_FLAG_UNRESOLVED 2 where the base is unchanged (r_P == r_0) and was
+ * unresolved in the last evaluation of its row -- pass P, or the pass that found the fixed point; 0 elsewhere.  No byte is 3 and
+ * every byte of every row is written; d_changed counts the 1s and d_unresolved the 2s.  A row is carried through its passes in
+ * LDS: a pitch whose rows do not fit there returns KBBQ_E_ARG naming the bytes (8 words per 16 bases, where one pass needs 3).
  * kbbq_kmer_count / kbbq_kmer_correct: the same from host buffers, slab by slab through page-locked staging (KBBQ_STAGE_MB);
  * `changed` (host, may be NULL) receives the per-read counts.  The kernel launches are not timed by kbbq_ctx_timing.
  * Ranks (kbbq/kmer.py count_kmers_ranks): every rank counts its reads into a local table, sends each key to its owner and merges
@@ -804,6 +819,13 @@ int kbbq_kmer_correct_ex_dev(kbbq_ctx* ctx, const kbbq_kmer_table* table, const 
                              int64_t nreads, int pitch, int min_count, uint8_t* d_out, uint32_t* d_changed, int opts);
 int kbbq_kmer_correct_ex(kbbq_ctx* ctx, const kbbq_kmer_table* table, const uint8_t* seq, const uint32_t* meta, int64_t nreads,
                          int pitch, int min_count, uint8_t* out, uint32_t* changed, int opts);
+int kbbq_kmer_correct_passes_dev(kbbq_ctx* ctx, const kbbq_kmer_table* table, const uint8_t* d_seq, const uint32_t* d_meta,
+                                 int64_t nreads, int pitch, int min_count, uint8_t* d_out, uint32_t* d_changed, int opts, int passes);
+int kbbq_kmer_correct_passes(kbbq_ctx* ctx, const kbbq_kmer_table* table, const uint8_t* seq, const uint32_t* meta, int64_t nreads,
+                             int pitch, int min_count, uint8_t* out, uint32_t* changed, int opts, int passes);
+int kbbq_kmer_flag_passes_dev(kbbq_ctx* ctx, const kbbq_kmer_table* table, const uint8_t* d_seq, const uint32_t* d_meta,
+                              int64_t nreads, int pitch, int min_count, uint8_t* d_flags, uint32_t* d_changed,
+                              uint32_t* d_unresolved, int opts, int passes);
 int kbbq_kmer_table_clear_dev(kbbq_ctx* ctx, kbbq_kmer_table* table);
 int kbbq_kmer_select_sizes_dev(kbbq_ctx* ctx, const kbbq_kmer_table* table, int nbuckets, uint32_t min_count, int64_t* h_sizes);
 int kbbq_kmer_select_dev(kbbq_ctx* ctx, const kbbq_kmer_table* table, int nbuckets, uint32_t min_count, const int64_t* h_offsets,
@@ -884,6 +906,10 @@ int kbbq_kmer_correct_rows_dev(kbbq_ctx* ctx, const kbbq_kmer_table* table, cons
                                int64_t nrows, int pitch, int flags, int min_count, uint8_t* d_out, uint32_t* d_changed);
 int kbbq_kmer_correct_rows_ex_dev(kbbq_ctx* ctx, const kbbq_kmer_table* table, const uint8_t* d_seq, const uint32_t* d_meta,
                                   int64_t nrows, int pitch, int flags, int min_count, uint8_t* d_out, uint32_t* d_changed, int opts);
+/* ... plus `passes` (Passes, above): every layout, the N rule included */
+int kbbq_kmer_correct_rows_passes_dev(kbbq_ctx* ctx, const kbbq_kmer_table* table, const uint8_t* d_seq, const uint32_t* d_meta,
+                                      int64_t nrows, int pitch, int flags, int min_count, uint8_t* d_out, uint32_t* d_changed, int opts,
+                                      int passes);
 
 #ifdef __cplusplus
 }

@@ -2295,18 +2295,39 @@ static void (*const KM_CORRECT[2][3])(KmerParams) = {
 // ... of the flag form: [KBBQ_KMER_FLAG_UNRESOLVED]
 static void (*const KM_FLAG[2])(KmerParams) = {km_correct<false, KM_FIXN_OFF, true>, km_correct<false, KM_FIXN_OFF, true, true>};
 
+// km_correct_passes' instantiations, as the two tables above (the kbbq_kmer_*_passes* calls with passes >= 2)
+static void (*const KM_CORRECT_PASSES[2][3])(KmerParams, int) = {
+    {km_correct_passes<false, KM_FIXN_OFF>, km_correct_passes<false, KM_FIXN_READS>, km_correct_passes<false, KM_FIXN_PAIRS>},
+    {km_correct_passes<true, KM_FIXN_OFF>, km_correct_passes<true, KM_FIXN_READS>, km_correct_passes<true, KM_FIXN_PAIRS>},
+};
+static void (*const KM_FLAG_PASSES[2])(KmerParams, int) = {km_correct_passes<false, KM_FIXN_OFF, true>,
+                                                           km_correct_passes<false, KM_FIXN_OFF, true, true>};
+
+// the `passes` of the kbbq_kmer_*_passes* calls: checked before anything else
+static int kmer_passes_ok(const char* who, int passes)
+{
+    if (passes < 1 || passes > KM_MAX_PASSES) return fail(KBBQ_E_ARG, "%s: passes must be in 1..%d, got %d", who, KM_MAX_PASSES, passes);
+    return KBBQ_OK;
+}
+
 // pairs: two reads to a row (KBBQ_ROWS_PAIRS), which the N rule alone needs to know -- their separator is no N
 // flag_form: d_out is a flag plane (kbbq_kmer_flag_dev / kbbq_kmer_flag_ex_dev; character rows).  Its opts are its own:
 // 0 or KBBQ_KMER_FLAG_UNRESOLVED, checked by the caller; d_unresolved (may be NULL) then receives the per-row count of 2s
+// passes: 1 launches km_correct, 2..KM_MAX_PASSES km_correct_passes (checked by the caller: kmer_passes_ok)
 static int kmer_correct_rows(kbbq_ctx* c, const char* who, const kbbq_kmer_table* t, const uint8_t* d_seq, const uint32_t* d_meta,
                              int64_t n, int pitch, bool nib, bool pairs, int min_count, uint8_t* d_out, uint32_t* d_changed, int opts,
-                             bool flag_form = false, uint32_t* d_unresolved = nullptr)
+                             bool flag_form = false, uint32_t* d_unresolved = nullptr, int passes = 1)
 {
     int rc = flag_form ? KBBQ_OK : kmer_correct_opts(who, opts);
     if (rc) return rc;
     KmerParams p; size_t lds = 0;
     rc = kmer_geometry(c, who, t, d_seq, d_meta, n, pitch, p, 3, &lds, nib);
     if (rc) return rc;
+    if (passes > 1) {                                   // the row in two copies, its first state and the marks: kbbq_kmer.h
+        lds = ((size_t)KM_PASS_WORDS * p.rows_per_wg * p.cpr + 2 * (size_t)p.rows_per_wg + 1) * 4;
+        if (lds > (size_t)c->lds_bytes)
+            return fail(KBBQ_E_ARG, "%s: pitch %d needs %zu bytes of LDS with passes = %d (> %d)", who, pitch, lds, passes, c->lds_bytes);
+    }
     if (min_count < 1) return fail(KBBQ_E_ARG, "%s: min_count must be >= 1, got %d", who, min_count);
     if (n > 0 && (!d_out || ((uintptr_t)d_out & (nib ? 7 : 15))))
         return fail(KBBQ_E_ARG, "%s: d_out NULL or not %d-byte aligned", who, nib ? 8 : 16);
@@ -2318,6 +2339,15 @@ static int kmer_correct_rows(kbbq_ctx* c, const char* who, const kbbq_kmer_table
     else if (d_unresolved) HIPCHK(hipMemsetAsync(d_unresolved, 0, (size_t)n * 4, c->stream));     // no byte is 2 without the option
     const auto kernel = flag_form ? KM_FLAG[unres ? 1 : 0]
                                   : KM_CORRECT[nib ? 1 : 0][!(opts & KBBQ_KMER_FIX_N) ? KM_FIXN_OFF : pairs ? KM_FIXN_PAIRS : KM_FIXN_READS];
+    if (passes > 1) {
+        const int fixn = !(opts & KBBQ_KMER_FIX_N) ? KM_FIXN_OFF : pairs ? KM_FIXN_PAIRS : KM_FIXN_READS;
+        const auto fused = flag_form ? KM_FLAG_PASSES[unres ? 1 : 0] : KM_CORRECT_PASSES[nib ? 1 : 0][fixn];
+        if (lds > 64 * 1024)                            // beyond what a kernel may take without asking
+            HIPCHK(hipFuncSetAttribute((const void*)fused, hipFuncAttributeMaxDynamicSharedMemorySize, c->lds_bytes));
+        return kmer_launches(p, [&](const KmerParams& q, unsigned grid) {
+            hipLaunchKernelGGL(fused, dim3(grid), dim3(KM_THREADS), lds, c->stream, q, passes);
+        });
+    }
     return kmer_launches(p, [&](const KmerParams& q, unsigned grid) {
         hipLaunchKernelGGL(kernel, dim3(grid), dim3(KM_THREADS), lds, c->stream, q);
     });
@@ -2336,7 +2366,7 @@ int kbbq_kmer_correct_dev(kbbq_ctx* c, const kbbq_kmer_table* t, const uint8_t* 
 }
 
 static int kmer_flag_rows(kbbq_ctx* c, const char* who, const kbbq_kmer_table* t, const uint8_t* d_seq, const uint32_t* d_meta, int64_t n,
-                          int pitch, int min_count, uint8_t* d_flags, uint32_t* d_changed, uint32_t* d_unresolved, int opts)
+                          int pitch, int min_count, uint8_t* d_flags, uint32_t* d_changed, uint32_t* d_unresolved, int opts, int passes = 1)
 {
     if (opts & ~KBBQ_KMER_FLAG_UNRESOLVED)
         return fail(KBBQ_E_ARG, "%s: opts 0x%x: the flag form takes KBBQ_KMER_FLAG_UNRESOLVED (%d) alone%s", who, opts,
@@ -2345,7 +2375,7 @@ static int kmer_flag_rows(kbbq_ctx* c, const char* who, const kbbq_kmer_table* t
     int rc = check_planes(who, n, pitch, d_seq, d_flags, nullptr);
     if (rc) return rc;
     if (min_count < 1) return fail(KBBQ_E_ARG, "%s: min_count must be >= 1, got %d", who, min_count);
-    return kmer_correct_rows(c, who, t, d_seq, d_meta, n, pitch, false, false, min_count, d_flags, d_changed, opts, true, d_unresolved);
+    return kmer_correct_rows(c, who, t, d_seq, d_meta, n, pitch, false, false, min_count, d_flags, d_changed, opts, true, d_unresolved, passes);
 }
 
 int kbbq_kmer_flag_dev(kbbq_ctx* c, const kbbq_kmer_table* t, const uint8_t* d_seq, const uint32_t* d_meta, int64_t n, int pitch,
@@ -2360,15 +2390,44 @@ int kbbq_kmer_flag_ex_dev(kbbq_ctx* c, const kbbq_kmer_table* t, const uint8_t* 
     return kmer_flag_rows(c, "kbbq_kmer_flag_ex_dev", t, d_seq, d_meta, n, pitch, min_count, d_flags, d_changed, d_unresolved, opts);
 }
 
+int kbbq_kmer_flag_passes_dev(kbbq_ctx* c, const kbbq_kmer_table* t, const uint8_t* d_seq, const uint32_t* d_meta, int64_t n, int pitch,
+                              int min_count, uint8_t* d_flags, uint32_t* d_changed, uint32_t* d_unresolved, int opts, int passes)
+{
+    int rc = kmer_passes_ok("kbbq_kmer_flag_passes_dev", passes);
+    if (rc) return rc;
+    return kmer_flag_rows(c, "kbbq_kmer_flag_passes_dev", t, d_seq, d_meta, n, pitch, min_count, d_flags, d_changed, d_unresolved, opts,
+                          passes);
+}
+
+int kbbq_kmer_correct_passes_dev(kbbq_ctx* c, const kbbq_kmer_table* t, const uint8_t* d_seq, const uint32_t* d_meta, int64_t n, int pitch,
+                                 int min_count, uint8_t* d_out, uint32_t* d_changed, int opts, int passes)
+{
+    int rc = kmer_passes_ok("kbbq_kmer_correct_passes_dev", passes);
+    if (rc) return rc;
+    return kmer_correct_rows(c, "kbbq_kmer_correct_passes_dev", t, d_seq, d_meta, n, pitch, false, false, min_count, d_out, d_changed, opts,
+                             false, nullptr, passes);
+}
+
 static int kmer_correct_rows_flags(kbbq_ctx* c, const char* who, const kbbq_kmer_table* t, const uint8_t* d_seq, const uint32_t* d_meta,
-                                   int64_t nrows, int pitch, int flags, int min_count, uint8_t* d_out, uint32_t* d_changed, int opts)
+                                   int64_t nrows, int pitch, int flags, int min_count, uint8_t* d_out, uint32_t* d_changed, int opts,
+                                   int passes = 1)
 {
     int rc = kmer_correct_opts(who, opts);
     if (rc) return rc;
     bool nib = false;
     rc = kmer_row_flags(who, flags, &nib);
     if (rc) return rc;
-    return kmer_correct_rows(c, who, t, d_seq, d_meta, nrows, pitch, nib, (flags & KBBQ_ROWS_PAIRS) != 0, min_count, d_out, d_changed, opts);
+    return kmer_correct_rows(c, who, t, d_seq, d_meta, nrows, pitch, nib, (flags & KBBQ_ROWS_PAIRS) != 0, min_count, d_out, d_changed, opts,
+                             false, nullptr, passes);
+}
+
+int kbbq_kmer_correct_rows_passes_dev(kbbq_ctx* c, const kbbq_kmer_table* t, const uint8_t* d_seq, const uint32_t* d_meta, int64_t nrows,
+                                      int pitch, int flags, int min_count, uint8_t* d_out, uint32_t* d_changed, int opts, int passes)
+{
+    int rc = kmer_passes_ok("kbbq_kmer_correct_rows_passes_dev", passes);
+    if (rc) return rc;
+    return kmer_correct_rows_flags(c, "kbbq_kmer_correct_rows_passes_dev", t, d_seq, d_meta, nrows, pitch, flags, min_count, d_out, d_changed,
+                                   opts, passes);
 }
 
 int kbbq_kmer_correct_rows_ex_dev(kbbq_ctx* c, const kbbq_kmer_table* t, const uint8_t* d_seq, const uint32_t* d_meta, int64_t nrows,
@@ -2465,7 +2524,7 @@ int kbbq_kmer_count(kbbq_ctx* c, kbbq_kmer_table* t, const uint8_t* seq, const u
 }
 
 static int kmer_correct_host(kbbq_ctx* c, const char* who, const kbbq_kmer_table* t, const uint8_t* seq, const uint32_t* meta, int64_t n,
-                             int pitch, int min_count, uint8_t* out, uint32_t* changed, int opts)
+                             int pitch, int min_count, uint8_t* out, uint32_t* changed, int opts, int passes = 1)
 {
     int orc = kmer_correct_opts(who, opts);
     if (orc) return orc;
@@ -2482,7 +2541,8 @@ static int kmer_correct_host(kbbq_ctx* c, const char* who, const kbbq_kmer_table
         if (done + m > n) return fail(KBBQ_E_HIP, "%s: more rows launched than given", who);
         uint32_t* dch = changed ? (uint32_t*)dc.p + done : nullptr;
         done += m;
-        return kmer_correct_rows(c, who, t, d, (const uint32_t*)(d + 2 * plane), m, pitch, false, false, min_count, d + plane, dch, opts);
+        return kmer_correct_rows(c, who, t, d, (const uint32_t*)(d + 2 * plane), m, pitch, false, false, min_count, d + plane, dch, opts,
+                                 false, nullptr, passes);
     });
     if (rc || !changed) return rc;
     HIPCHK(hipMemcpyAsync(changed, dc.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
@@ -2494,6 +2554,14 @@ int kbbq_kmer_correct_ex(kbbq_ctx* c, const kbbq_kmer_table* t, const uint8_t* s
                          int min_count, uint8_t* out, uint32_t* changed, int opts)
 {
     return kmer_correct_host(c, "kbbq_kmer_correct_ex", t, seq, meta, n, pitch, min_count, out, changed, opts);
+}
+
+int kbbq_kmer_correct_passes(kbbq_ctx* c, const kbbq_kmer_table* t, const uint8_t* seq, const uint32_t* meta, int64_t n, int pitch,
+                             int min_count, uint8_t* out, uint32_t* changed, int opts, int passes)
+{
+    int rc = kmer_passes_ok("kbbq_kmer_correct_passes", passes);
+    if (rc) return rc;
+    return kmer_correct_host(c, "kbbq_kmer_correct_passes", t, seq, meta, n, pitch, min_count, out, changed, opts, passes);
 }
 
 int kbbq_kmer_correct(kbbq_ctx* c, const kbbq_kmer_table* t, const uint8_t* seq, const uint32_t* meta, int64_t n, int pitch,

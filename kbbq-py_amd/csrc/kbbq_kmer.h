@@ -513,6 +513,233 @@ __global__ __launch_bounds__(KM_THREADS) void km_correct(KmerParams p)
     }
 }
 
+// ---- several passes of the rule over rows held in LDS (kbbq correct --passes; include/kbbq_hip.h kbbq_kmer_*_passes*) ----------
+// r_0 is the row as read and r_p = C(r_(p-1)), C being km_correct's rule (with FIXN the N rule too) against the same table at
+// the same min_count: nothing is recounted.  km_correct's work split and pass 1; then the row lives in LDS until it is stored:
+//   code0 / brk0      the chunk as read (brk0's high half: the Ns of the read the N rule may fix -- inside the read, no separator)
+//   codeA/brkA, codeB/brkB   r_(p-1) and r_p: a pass reads one copy and writes the other, the copies swap after a barrier, so no
+//                     base sees a decision of its own pass
+//   sv                (solid << 16 | valid) of the 16 windows starting in the chunk, as km_correct's
+//   mark              low half: the bases of the chunk the row's last pass changed; high half: those it left unresolved
+//   nchg[row]         km_correct's counters;  last[row]: the last pass that changed the row;  wglast: ... any row of the workgroup
+// From pass 2 on a window is looked up again only when a base the pass before changed lies in it (a fixed N changes validity
+// too, and is such a base); every other window keeps its bits.  A row whose pass p - 1 changed nothing is skipped from pass p on
+// (both copies hold it then), and the workgroup leaves the loop after a pass in which none of its rows changed: every thread
+// reads that from wglast after the barrier, so the trip count is uniform and every __syncthreads() is reached by all threads.
+// The store stage writes km_put's form wherever the final copy differs from code0 / brk0, and with UNRES 2 where it does not
+// and the row's last pass left the base unresolved; the per-row counts are those of the final plane, not sums over passes.
+// The plane is read by km_load_chunks and, where a chunk's other bytes are needed (its Ns at the start with FIXN, the chunk
+// that is rewritten at the end unless FLAGS), the same 16 bytes once more, as km_correct reads them; nothing goes through
+// global memory between passes.
+constexpr int KM_MAX_PASSES = 8;
+constexpr int KM_PASS_WORDS = 8;      // LDS words per chunk of km_correct_passes; 2 more per row and 1 per workgroup
+
+template <bool NIB, int FIXN = KM_FIXN_OFF, bool FLAGS = false, bool UNRES = false>
+__global__ __launch_bounds__(KM_THREADS) void km_correct_passes(KmerParams p, int passes)
+{
+    static_assert(!FLAGS || (!NIB && FIXN == KM_FIXN_OFF), "the flag form: character rows, no N rule");
+    static_assert(!UNRES || FLAGS, "unresolved bases are a value of the flag plane: the flag form only");
+    extern __shared__ u32 km_lds[];
+    const int E = p.rows_per_wg * p.cpr;
+    u32* code0 = km_lds; u32* brk0 = km_lds + E;
+    u32* cc = km_lds + 2 * E; u32* cb = km_lds + 3 * E;                  // r_(p-1)
+    u32* nc = km_lds + 4 * E; u32* nb = km_lds + 5 * E;                  // r_p
+    u32* sv = km_lds + 6 * E; u32* mark = km_lds + 7 * E;
+    u32* nchg = km_lds + 8 * E;
+    int* last = reinterpret_cast<int*>(nchg + p.rows_per_wg);
+    int* wglast = last + p.rows_per_wg;
+    constexpr int CB = NIB ? 8 : 16;                                      // bytes of a chunk in the plane
+    const int64_t row0 = (int64_t)blockIdx.x * p.rows_per_wg;
+    for (int i = threadIdx.x; i < p.rows_per_wg; i += KM_THREADS) { nchg[i] = 0; last[i] = -1; }
+    if (threadIdx.x == 0) *wglast = -1;
+    const int nr = km_load_chunks<NIB>(p, row0, code0, brk0);
+    for (int e = threadIdx.x; e < nr * p.cpr; e += KM_THREADS) {          // the elements this thread loaded itself
+        cc[e] = code0[e]; cb[e] = brk0[e]; mark[e] = 0;
+        if constexpr (FIXN != KM_FIXN_OFF) {
+            const int r = e / p.cpr, ch = e - r * p.cpr;
+            const int64_t row = row0 + r;
+            const size_t at = (size_t)row * p.pitch + (size_t)ch * CB;
+            u32 w[4] = {0, 0, 0, 0};
+            if constexpr (NIB) {
+                const uint2 v = *reinterpret_cast<const uint2*>(p.seq + at);
+                w[0] = v.x; w[1] = v.y;
+            } else {
+                const uint4 v = *reinterpret_cast<const uint4*>(p.seq + at);
+                w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
+            }
+            u32 ns = 0;
+            #pragma unroll
+            for (int t = 0; t < 16; ++t) {
+                const bool n = NIB ? ((w[t >> 3] >> km_nib_shift(t & 7)) & 0xFu) == 4u : ((w[t >> 2] >> (8 * (t & 3))) & 0xFFu) == 'N';
+                ns |= (n ? 1u : 0u) << t;
+            }
+            ns &= brk0[e];
+            if (ns) {
+                const int L = (int)(p.meta[row] & 0xFFFFu), first = ch * 16;
+                ns &= L - first >= 16 ? 0xFFFFu : L > first ? (1u << (L - first)) - 1u : 0u;
+                const int sep = FIXN == KM_FIXN_PAIRS ? ((L - 1) >> 1) - first : -1;
+                if (sep >= 0 && sep < 16) ns &= ~(1u << sep);
+            }
+            brk0[e] |= ns << 16;
+        }
+    }
+    __syncthreads();
+    const int k = p.k;
+    const u64 kmask = (1ull << k) - 1;
+    for (int pass = 0; pass < passes; ++pass) {
+        // the window bits of r_(p-1): all of them in the first pass, then those over a base the pass before changed
+        for (int e = threadIdx.x; e < nr * p.cpr; e += KM_THREADS) {
+            const int r = e / p.cpr, ch = e - r * p.cpr;
+            if (pass > 0 && last[r] < pass - 1) continue;                 // the row is finished
+            u64 dirty = ~0ull;
+            u32 valid = 0, solid = 0;
+            if (pass > 0) {
+                dirty = 0;
+                for (int i = 0; i < 3; ++i)
+                    if (ch + i < p.cpr) dirty |= (u64)(mark[e + i] & 0xFFFFu) << (16 * i);
+                if (!dirty) continue;
+                valid = sv[e] & 0xFFFFu; solid = sv[e] >> 16;
+            }
+            u64 b;
+            const unsigned __int128 x = km_words(p, cc, cb, r * p.cpr, ch, 3, &b);
+            for (int o = 0; o < 16; ++o) {
+                if (!((dirty >> o) & kmask)) continue;
+                valid &= ~(1u << o); solid &= ~(1u << o);
+                if ((b >> o) & kmask) continue;
+                valid |= 1u << o;
+                if (km_solid(p, km_window(x, o, k))) solid |= 1u << o;
+            }
+            sv[e] = solid << 16 | valid;
+        }
+        __syncthreads();
+        // trust and the two rules on r_(p-1); the decisions go to r_p
+        for (int e = threadIdx.x; e < nr * p.cpr; e += KM_THREADS) {
+            const int r = e / p.cpr, ch = e - r * p.cpr;
+            if (pass > 0 && last[r] < pass - 1) continue;                 // (a row changed in this pass reads as `pass`: not finished)
+            u64 V = 0, S = 0;                                             // bit i: the window starting at base 16 (ch - 2) + i
+            for (int i = 0; i < 3; ++i) {
+                const int c = ch - 2 + i;
+                const u32 w = c >= 0 ? sv[r * p.cpr + c] : 0u;
+                V |= (u64)(w & 0xFFFFu) << (16 * i);
+                S |= (u64)(w >> 16) << (16 * i);
+            }
+            const u32 code_own = cc[e], brk_own = cb[e];
+            u32 code_new = code_own, brk_new = brk_own, chg = 0, unres = 0;
+            bool have_words = false;
+            unsigned __int128 xa = 0, xb = 0;                            // chunks ch - 2 .. ch + 1 and ch .. ch + 3
+            u32 ns = 0;                                                   // N rule: the Ns of the read that are still Ns
+            if constexpr (FIXN != KM_FIXN_OFF) ns = (brk0[e] >> 16) & brk_own;
+            for (int t = 0; t < 16; ++t) {
+                if constexpr (FIXN != KM_FIXN_OFF) {
+                    if ((ns >> t) & 1u) {
+                        if (!have_words) {
+                            u64 unused;
+                            xa = km_words(p, cc, cb, r * p.cpr, ch - 2, 4, &unused);
+                            xb = km_words(p, cc, cb, r * p.cpr, ch, 4, &unused);
+                            have_words = true;
+                        }
+                        const unsigned __int128 B = km_breaks(p, cb, r * p.cpr, ch - 2, 5);   // bit i: base 16 (ch - 2) + i
+                        const int pp = 32 + t;
+                        int s[4] = {0, 0, 0, 0};
+                        for (int j = pp - k + 1; j <= pp; ++j) {          // a candidate window: this N is its only break
+                            if (((u64)(B >> j) & kmask) != 1ull << (pp - j)) continue;
+                            const u64 f = j < 32 ? km_window(xa, j, k) : km_window(xb, j - 32, k);   // a break's code is 0
+                            #pragma unroll
+                            for (u32 x = 0; x < 4; ++x) s[x] += km_solid(p, f | (u64)x << (2 * (k - 1 - (pp - j)))) ? 1 : 0;
+                        }
+                        int best = -1, bs = 0; bool tie = false;
+                        #pragma unroll
+                        for (int x = 0; x < 4; ++x) {
+                            if (s[x] > bs) { bs = s[x]; best = x; tie = false; }
+                            else if (s[x] == bs && bs > 0) tie = true;
+                        }
+                        if (best < 0 || tie) continue;
+                        code_new |= (u32)best << (30 - 2 * t);           // an ordinary base from the next pass on
+                        brk_new &= ~(1u << t);
+                        chg |= 1u << t;
+                        continue;
+                    }
+                }
+                if ((brk_own >> t) & 1u) continue;                        // a break: never changed
+                const int pp = 32 + t;                                    // the base's index in the 48-bit window masks
+                const u64 cover = kmask << (pp - k + 1);
+                if ((S & cover) || !(V & cover)) continue;                // trusted
+                if (!have_words) {
+                    u64 unused;
+                    xa = km_words(p, cc, cb, r * p.cpr, ch - 2, 4, &unused);
+                    xb = km_words(p, cc, cb, r * p.cpr, ch, 4, &unused);
+                    have_words = true;
+                }
+                const u32 orig = (code_own >> (30 - 2 * t)) & 3u;
+                int s[4] = {0, 0, 0, 0};
+                for (u32 alt = 0; alt < 4; ++alt) {
+                    if (alt == orig) continue;
+                    for (u64 m = V & cover; m; m &= m - 1) {
+                        const int j = __builtin_ctzll(m);                 // a valid covering window
+                        const u64 f = (j < 32 ? km_window(xa, j, k) : km_window(xb, j - 32, k)) ^ ((u64)(orig ^ alt) << (2 * (k - 1 - (pp - j))));
+                        s[alt] += km_solid(p, f) ? 1 : 0;
+                    }
+                }
+                int best = -1, bs = 0; bool tie = false;
+                for (int alt = 0; alt < 4; ++alt) {
+                    if (alt == (int)orig) continue;
+                    if (s[alt] > bs) { bs = s[alt]; best = alt; tie = false; }
+                    else if (s[alt] == bs && bs > 0) tie = true;
+                }
+                if (best < 0 || tie) {                                    // untrusted, and no substitution wins: unresolved
+                    if constexpr (UNRES) unres |= 1u << t;
+                    continue;
+                }
+                code_new ^= (orig ^ (u32)best) << (30 - 2 * t);
+                chg |= 1u << t;
+            }
+            nc[e] = code_new; nb[e] = brk_new; mark[e] = chg | unres << 16;
+            if (chg) { last[r] = pass; *wglast = pass; }
+        }
+        __syncthreads();
+        { u32* x = cc; cc = nc; nc = x; x = cb; cb = nb; nb = x; }
+        if (*wglast != pass) break;                                       // uniform: written before the barrier, next after the one above
+    }
+    // store: km_put wherever r_P differs from r_0
+    for (int e = threadIdx.x; e < nr * p.cpr; e += KM_THREADS) {
+        const int r = e / p.cpr, ch = e - r * p.cpr;
+        const size_t at = (size_t)(row0 + r) * p.pitch + (size_t)ch * CB;
+        u32 w[4] = {0, 0, 0, 0};                                         // the chunk as read, or of the flag plane: all 0
+        if constexpr (FLAGS) {
+        } else if constexpr (NIB) {
+            const uint2 v = *reinterpret_cast<const uint2*>(p.seq + at);
+            w[0] = v.x; w[1] = v.y;
+        } else {
+            const uint4 v = *reinterpret_cast<const uint4*>(p.seq + at);
+            w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
+        }
+        const u32 code_end = cc[e];
+        const u32 dcode = code0[e] ^ code_end, dbrk = (brk0[e] ^ cb[e]) & 0xFFFFu, un = UNRES ? mark[e] >> 16 : 0u;
+        int changed = 0, unres = 0;
+        if (dcode | dbrk | un) {
+            for (int t = 0; t < 16; ++t) {
+                if (((dcode >> (30 - 2 * t)) & 3u) | ((dbrk >> t) & 1u)) {
+                    km_put<NIB, FLAGS>(w, t, (code_end >> (30 - 2 * t)) & 3u);
+                    ++changed;
+                } else if ((un >> t) & 1u) {
+                    km_flag(w, t, 2u);
+                    ++unres;
+                }
+            }
+        }
+        if constexpr (NIB) *reinterpret_cast<uint2*>(p.out + at) = make_uint2(w[0], w[1]);
+        else *reinterpret_cast<uint4*>(p.out + at) = make_uint4(w[0], w[1], w[2], w[3]);
+        if (changed | unres) atomicAdd(&nchg[r], (u32)changed | (u32)unres << 16);
+    }
+    if (p.changed || p.unresolved) {
+        __syncthreads();
+        for (int i = threadIdx.x; i < nr; i += KM_THREADS) {
+            if (p.changed) p.changed[row0 + i] = nchg[i] & 0xFFFFu;
+            if (p.unresolved) p.unresolved[row0 + i] = nchg[i] >> 16;
+        }
+    }
+}
+
 // ---- ranks: partition, exchange and merge ----------------------------------------------------------------------------------
 constexpr int KM_MAX_BUCKETS = 1024;  // owners of one select; the per-bucket counters live in LDS
 constexpr int KM_SEL_QUADS = 4;       // 4-slot quads per thread and tile: a tile is KM_THREADS * 16 slots

@@ -27,6 +27,7 @@ APPLY_CHECKED, APPLY_FAST = 0, 1
 ALIGNED_LUT, ALIGNED_F64 = 0, 1
 ROWS_PAIRS, ROWS_NIBBLES, ROWS_TWINS = 1, 2, 4
 KMER_FIX_N = 1                        # the `opts` word of the kbbq_kmer_correct*_ex calls
+KMER_MAX_PASSES = 8                   # the `passes` of the kbbq_kmer_*_passes* calls: 1..8
 KMER_FLAG_UNRESOLVED = 2              # ... and of kbbq_kmer_flag_ex_dev: unresolved bases become 2 in the flag plane
 CONFUSION_MAX_BASES = (1 << 32) - 1   # KBBQ_CONFUSION_MAX_BASES: nreads * pitch of one kbbq_flag_confusion_dev call
 
@@ -182,6 +183,9 @@ PROTOTYPES = {
     'kbbq_kmer_correct': (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _vp, _vp]),
     'kbbq_kmer_correct_ex_dev': (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _vp, _vp, _i]),
     'kbbq_kmer_correct_ex': (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _vp, _vp, _i]),
+    'kbbq_kmer_correct_passes_dev': (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _vp, _vp, _i, _i]),
+    'kbbq_kmer_correct_passes': (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _vp, _vp, _i, _i]),
+    'kbbq_kmer_flag_passes_dev': (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _vp, _vp, _vp, _i, _i]),
     'kbbq_kmer_table_clear_dev': (_i, [_vp, _vp]),
     'kbbq_kmer_select_sizes_dev': (_i, [_vp, _vp, _i, _c.c_uint32, _vp]),
     'kbbq_kmer_select_dev': (_i, [_vp, _vp, _i, _c.c_uint32, _vp, _vp, _vp]),
@@ -203,6 +207,7 @@ PROTOTYPES = {
     'kbbq_kmer_count_filtered_rows_dev': (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i, _i]),
     'kbbq_kmer_correct_rows_dev': (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _vp, _vp]),
     'kbbq_kmer_correct_rows_ex_dev': (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _vp, _vp, _i]),
+    'kbbq_kmer_correct_rows_passes_dev': (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _vp, _vp, _i, _i]),
 }
 
 

@@ -489,7 +489,7 @@ def _kmer_benchmark_inputs(bamfile, k, min_count, prefilter, filter_bits):
 
 
 def benchmark_kmers(bamfile, ref, var_sites, k=31, min_count=None, slots=None, prefilter=False, filter_bits=4, use_oq=False,
-                    bedfh=None, info=None):
+                    bedfh=None, info=None, passes=1):
     """How good is the k-mer rule on a truth set?  joint[q][truth error][k-mer class], int64 (256, 2, 3): every base of the
     alignments that benchmark_bam counts (not at a variant site, inside the BED, not soft-clipped), by its reported quality
     (QUAL, or the OQ tag with use_oq), by whether it differs from the reference (K4, exactly as benchmark_bam flags it) and
@@ -500,9 +500,12 @@ def benchmark_kmers(bamfile, ref, var_sites, k=31, min_count=None, slots=None, p
     the four resident planes (or `slots`), the count histogram's first valley unless min_count is given, flag_errors with
     unresolved bases.  Records may have any lengths (a record shorter than k has no k-mer: all its bases are class 0).
     One GPU; bamfile is a kbbq.aln.AlignmentFile.  `info`, a dict, receives k, min_count, reads, slots, prefilter, admitted,
-    bases, errors, flagged, flagged_errors, unresolved and unresolved_errors (totals over the counted bases)."""
+    bases, errors, flagged, flagged_errors, unresolved and unresolved_errors (totals over the counted bases).
+    passes: the classes of `passes` passes of the rule (flag_errors(passes=...): 1 where the last pass ends on another letter,
+    2 where the base is unchanged and its row's last evaluation left it unresolved); `info` then receives passes too."""
     from . import _device as dev
     from . import kmer
+    passes = kmer.check_passes(passes)
     b = _kmer_benchmark_inputs(bamfile, k, min_count, prefilter, filter_bits)
     k = int(k)
     torch = dev._torch()
@@ -532,7 +535,7 @@ def benchmark_kmers(bamfile, ref, var_sites, k=31, min_count=None, slots=None, p
             if filt is not None:
                 filt.close()
             t = int(min_count) if min_count is not None else kmer.solid_threshold(kmer.kmer_histogram(table))
-            kflags, _, _ = kmer.flag_errors(table, d_seq, d_len, t, unresolved=True)
+            kflags, _, _ = kmer.flag_errors(table, d_seq, d_len, t, unresolved=True, **kmer._passes_kw(passes))
             nslots = table.slots
         finally:
             if filt is not None:
@@ -544,6 +547,8 @@ def benchmark_kmers(bamfile, ref, var_sites, k=31, min_count=None, slots=None, p
         joint = np.zeros((256, 2, 3), dtype=np.int64)
     if info is not None:
         info.update(k=k, min_count=t, reads=n, slots=nslots, prefilter=bool(prefilter), admitted=admitted, **kmer_totals(joint))
+        if passes != 1:
+            info.update(passes=passes)
     return joint
 
 
@@ -562,6 +567,8 @@ def kmer_summary(info):
             % (info['k'], info['min_count'], info['reads'], info['bases'], info['errors'], info['flagged'], info['flagged_errors'],
                info['unresolved'], info['unresolved_errors'], ratio(info['flagged_errors'], info['flagged']),
                ratio(info['flagged_errors'], info['errors'])))
+    if info.get('passes', 1) > 1:
+        line += ' passes=%d' % info['passes']
     if info.get('prefilter'):
         line += ' prefilter=1 admitted=%d slots=%d' % (info['admitted'], info['slots'])
     return line
@@ -585,7 +592,7 @@ def print_benchmark_kmers(joint, label):
 
 def benchmark(bamfile, fafile, vcffile, fastqfile=None, label=None, use_oq=False, bedfh=None, kmers=None):
     """Run the benchmark and print it.  With a FASTQ, its reads are matched to the alignments by name.  kmers: a dict of
-    benchmark_kmers' options (k, min_count, slots, prefilter, filter_bits) -- print the k-mer rule's flags against the truth
+    benchmark_kmers' options (k, min_count, slots, prefilter, filter_bits, passes) -- print the k-mer rule's flags against the truth
     set's instead (print_benchmark_kmers) and one summary line on stderr."""
     if kmers is not None and fastqfile is not None:
         raise ValueError('benchmark --kmers takes the alignments alone (-b), not a FASTQ joined by name (-f)')

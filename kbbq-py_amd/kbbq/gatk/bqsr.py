@@ -333,7 +333,7 @@ def _kmer_inputs(bamfileobj, k, min_count, prefilter, filter_bits, use_oq, maxsc
 
 
 def bam_to_kmer_covariates(bamfileobj, k=31, min_count=None, slots=None, prefilter=False, filter_bits=4, use_oq=False,
-                           minscore=6, maxscore=42, info=None, skip_unresolved=False):
+                           minscore=6, maxscore=42, info=None, skip_unresolved=False, passes=1):
     """The nine model vectors from aligned reads alone -- no reference, no known sites (`kbbq bqsr --kmers`).  A base is an error
     where the k-mer correction of kbbq.kmer would change it: every k-mer of SEQ of every record is counted (soft clips too:
     they are sequenced bases; keys are canonical, so the alignment's strand does not matter), a k-mer is solid at min_count
@@ -348,9 +348,13 @@ def bam_to_kmer_covariates(bamfileobj, k=31, min_count=None, slots=None, prefilt
     k-mer: two errors within k bases, thin coverage, contamination) is left out of the tally -- neither an error nor an
     observation, as a base at a known site is in bam_to_bqsr_covariates -- instead of counted as correct.  The flag plane then
     carries 2, the tally's skip bit, at those bases (kbbq_kmer_flag_ex_dev); `info` also receives skipped_bases, their number
-    over all bases of SEQ, before the tally's own exclusions as flagged_bases is."""
+    over all bases of SEQ, before the tally's own exclusions as flagged_bases is.
+    passes: the flags of `passes` passes of the correction (kbbq_kmer_flag_passes_dev) -- an error where the last pass ends on
+    another letter than SEQ's, unresolved where the base is unchanged and its row's last evaluation left it so; `info` then
+    receives passes too."""
     from .. import _device as dev
     from .. import _solve, fastx, kmer
+    passes = kmer.check_passes(passes)
     b, n, S = _kmer_inputs(bamfileobj, k, min_count, prefilter, filter_bits, use_oq, maxscore)
     k = int(k)
     T = dev._torch()
@@ -382,9 +386,9 @@ def bam_to_kmer_covariates(bamfileobj, k=31, min_count=None, slots=None, prefilt
             filt.close()
         t = int(min_count) if min_count is not None else kmer.solid_threshold(kmer.kmer_histogram(table))
         if skip_unresolved:
-            err, changed, skipped = kmer.flag_errors(table, d_seq, d_len, t, unresolved=True)
+            err, changed, skipped = kmer.flag_errors(table, d_seq, d_len, t, unresolved=True, **kmer._passes_kw(passes))
         else:
-            err, changed = kmer.flag_errors(table, d_seq, d_len, t)
+            err, changed = kmer.flag_errors(table, d_seq, d_len, t, **kmer._passes_kw(passes))
         nslots = table.slots
     finally:
         if filt is not None:
@@ -401,6 +405,8 @@ def bam_to_kmer_covariates(bamfileobj, k=31, min_count=None, slots=None, prefilt
                     prefilter=bool(prefilter), admitted=admitted)
         if skip_unresolved:
             info.update(skipped_bases=int(skipped.cpu().numpy().astype(np.int64).sum()))
+        if passes != 1:
+            info.update(passes=passes)
     return _solve.vectors_from_tables(*tables.to_host(), maxscore)
 
 
@@ -526,11 +532,12 @@ def bam_to_report(bamfileobj, fastafilename, var_pos):
 
 
 def bam_to_report_kmers(bamfileobj, k=31, min_count=None, slots=None, prefilter=False, filter_bits=4, use_oq=False, info=None,
-                        skip_unresolved=False):
+                        skip_unresolved=False, passes=1):
     """Aligned reads -> recalibration report without a reference or known sites: the errors are what the k-mers of the reads'
     own sequences contradict (bam_to_kmer_covariates); read groups are named by their PU as in bam_to_report.  skip_unresolved:
     bases the k-mers contradict without naming a replacement are left out of the tally (bam_to_kmer_covariates)."""
     rgs = list(utils.get_rg_to_pu(bamfileobj).values())
     vectors = bam_to_kmer_covariates(bamfileobj, k=k, min_count=min_count, slots=slots, prefilter=prefilter,
-                                     filter_bits=filter_bits, use_oq=use_oq, info=info, skip_unresolved=skip_unresolved)
+                                     filter_bits=filter_bits, use_oq=use_oq, info=info, skip_unresolved=skip_unresolved,
+                                     **({} if passes == 1 else dict(passes=passes)))
     return vectors_to_report(*vectors, rgs)

@@ -7,7 +7,9 @@ every k-mer of every read is counted exactly in a device hash table, the first v
 threshold, and an untrusted base (no solid k-mer covers it) takes the one other base that makes the most covering k-mers
 solid.  The rule, base by base, is in include/kbbq_hip.h; tests/kmer_model.py is a CPU model of it.  With `fix_n` (`kbbq correct
 --fix-n`) an N takes the letter that makes the most of the windows it alone breaks solid (the N rule of include/kbbq_hip.h;
-tests/kmer_fixn_model.py); counting and the threshold do not change.
+tests/kmer_fixn_model.py); counting and the threshold do not change.  With `passes` = P > 1 (`kbbq correct --passes P`) the rule is applied to its own
+output P times, row by row, against the same table (nothing is recounted): an error beside a read end, or beside another
+error, is out of the rule's reach until its neighbour is corrected, and is within it afterwards (tests/kmer_passes_model.py).
 
 Planes are [n, pitch] uint8 seq planes with uint32 meta words (length in bits 0..15).  NumPy arrays go through the host-buffer
 entry points (slab by slab through page-locked staging, any size); tensors on the GPU through the _dev ones.  There is no
@@ -376,9 +378,19 @@ def solid_threshold(hist):
     raise ValueError('the k-mer count histogram has no valley in 2..255: give min_count')
 
 
-def correct_with(table, seq_plane, meta, min_count, fix_n=False):
+def check_passes(passes):
+    """`passes` as an int in 1..8 (KBBQ_E_ARG's range), else ValueError: checked before any device call and, under ranks, before
+    any collective."""
+    if isinstance(passes, bool) or int(passes) != passes or not 1 <= int(passes) <= N.KMER_MAX_PASSES:
+        raise ValueError('passes must be an integer in 1..%d, got %r' % (N.KMER_MAX_PASSES, passes))
+    return int(passes)
+
+
+def correct_with(table, seq_plane, meta, min_count, fix_n=False, passes=1):
     """(corrected plane, per-read changed-base counts uint32) of the rows against a counted table.  fix_n: Ns are decided by the
-    N rule (KBBQ_KMER_FIX_N) and a fixed N counts as a changed base."""
+    N rule (KBBQ_KMER_FIX_N) and a fixed N counts as a changed base.  passes: the rule applied to its own output that many
+    times, a row at a time (kbbq_kmer_correct_passes*); the counts are then the bases that differ from the rows as read."""
+    passes = check_passes(passes)
     lib = N.load()
     ctx = table.ctx
     n, pitch = int(seq_plane.shape[0]), int(seq_plane.shape[1])
@@ -386,28 +398,39 @@ def correct_with(table, seq_plane, meta, min_count, fix_n=False):
     if _on_device(seq_plane):
         out = seq_plane.new_empty(seq_plane.shape)
         changed = seq_plane.new_empty((max(n, 1),), dtype=__import__('torch').int32)
-        N.check(lib.kbbq_kmer_correct_ex_dev(ctx.handle, table.handle, N.ptr(seq_plane), N.ptr(meta), n, pitch, int(min_count),
-                                             N.ptr(out), N.ptr(changed), opts))
+        if passes > 1:
+            N.check(lib.kbbq_kmer_correct_passes_dev(ctx.handle, table.handle, N.ptr(seq_plane), N.ptr(meta), n, pitch,
+                                                     int(min_count), N.ptr(out), N.ptr(changed), opts, passes))
+        else:
+            N.check(lib.kbbq_kmer_correct_ex_dev(ctx.handle, table.handle, N.ptr(seq_plane), N.ptr(meta), n, pitch, int(min_count),
+                                                 N.ptr(out), N.ptr(changed), opts))
         ctx.status()
         return out, changed[:n]
     seq_plane = np.ascontiguousarray(seq_plane, dtype=np.uint8)
     meta = np.ascontiguousarray(meta, dtype=np.uint32)
     out = np.empty_like(seq_plane)
     changed = np.zeros(max(n, 1), dtype=np.uint32)
-    N.check(lib.kbbq_kmer_correct_ex(ctx.handle, table.handle, N.ptr(seq_plane), N.ptr(meta), n, pitch, int(min_count),
-                                     N.ptr(out), N.ptr(changed), opts))
+    if passes > 1:
+        N.check(lib.kbbq_kmer_correct_passes(ctx.handle, table.handle, N.ptr(seq_plane), N.ptr(meta), n, pitch, int(min_count),
+                                             N.ptr(out), N.ptr(changed), opts, passes))
+    else:
+        N.check(lib.kbbq_kmer_correct_ex(ctx.handle, table.handle, N.ptr(seq_plane), N.ptr(meta), n, pitch, int(min_count),
+                                         N.ptr(out), N.ptr(changed), opts))
     return out, changed[:n]
 
 
-def flag_errors(table, seq_plane, meta, min_count, unresolved=False):
+def flag_errors(table, seq_plane, meta, min_count, unresolved=False, passes=1):
     """(flag plane uint8 [n, pitch], per-read flagged-base counts int32) of device rows against a counted table
     (kbbq_kmer_flag_dev): 1 exactly where correct_with would write another letter, 0 everywhere else, padding included.
     The plane is the one plane of flags the aligned tally reads (bit 0 error; gatk.bqsr.bam_to_kmer_covariates).  Device
     tensors in, device tensors out; there is no host-buffer form.
     unresolved: (flag plane, flagged-base counts, unresolved-base counts int32) of kbbq_kmer_flag_ex_dev with
     KBBQ_KMER_FLAG_UNRESOLVED -- an untrusted A/C/G/T base for which no substitution wins (a tie, or none makes a solid k-mer)
-    is 2 in the plane, the tally's skip bit; every other byte is what it is without the option."""
+    is 2 in the plane, the tally's skip bit; every other byte is what it is without the option.
+    passes > 1 (kbbq_kmer_flag_passes_dev): 1 where `passes` passes of the correction end on another letter than the read's, 2
+    (with `unresolved`) where the base is unchanged and the last evaluation of its row left it unresolved."""
     from . import _device as dev
+    passes = check_passes(passes)
     if not _on_device(seq_plane):
         raise TypeError('flag_errors takes device planes (correct_with takes host buffers too)')
     T = dev._torch()
@@ -415,6 +438,13 @@ def flag_errors(table, seq_plane, meta, min_count, unresolved=False):
     n, pitch = int(seq_plane.shape[0]), int(seq_plane.shape[1])
     flags = T.empty((max(n, 1), pitch), dtype=T.uint8, device=seq_plane.device)
     changed = T.empty((max(n, 1),), dtype=T.int32, device=seq_plane.device)
+    if passes > 1:
+        skipped = T.empty((max(n, 1),), dtype=T.int32, device=seq_plane.device)
+        N.check(N.load().kbbq_kmer_flag_passes_dev(ctx.handle, table.handle, N.ptr(seq_plane), N.ptr(meta), n, pitch, int(min_count),
+                                                   N.ptr(flags), N.ptr(changed), N.ptr(skipped),
+                                                   N.KMER_FLAG_UNRESOLVED if unresolved else 0, passes))
+        ctx.status()
+        return (flags[:n], changed[:n], skipped[:n]) if unresolved else (flags[:n], changed[:n])
     if unresolved:
         skipped = T.empty((max(n, 1),), dtype=T.int32, device=seq_plane.device)
         N.check(N.load().kbbq_kmer_flag_ex_dev(ctx.handle, table.handle, N.ptr(seq_plane), N.ptr(meta), n, pitch, int(min_count),
@@ -484,22 +514,32 @@ def count_batch(batch, k=31, table=None, slots=None, filter=None):
     return table
 
 
-def correct_batch(table, batch, min_count, fix_n=False):
+def correct_batch(table, batch, min_count, fix_n=False, passes=1):
     """Correct the rows of a device batch against a counted table into batch.cseq (allocated here when the batch was made
     without one) in the batch's own layout: K1 takes it as it is.  Returns `changed`, the changed bases per ROW as an int32
     device array (a row of two reads counts both).  fix_n: the N rule, in every layout (a fixed N of a 4-bit plane is its
-    letter's code; the separator of a row of two reads is no N)."""
+    letter's code; the separator of a row of two reads is no N).  passes: as correct_with's, in every layout."""
     from . import _device as dev
+    passes = check_passes(passes)
     T = dev._torch()
     if batch.cseq is None:
         batch.cseq = T.empty_like(batch.seq)
     seq, meta, n, pitch, flags = _batch_rows(batch)
     changed = T.empty((max(n, 1),), dtype=T.int32, device=batch.seq.device)
     ctx = table.ctx
-    N.check(N.load().kbbq_kmer_correct_rows_ex_dev(ctx.handle, table.handle, seq, meta, n, pitch, flags, int(min_count),
-                                                   N.ptr(batch.cseq), N.ptr(changed), N.KMER_FIX_N if fix_n else 0))
+    if passes > 1:
+        N.check(N.load().kbbq_kmer_correct_rows_passes_dev(ctx.handle, table.handle, seq, meta, n, pitch, flags, int(min_count),
+                                                           N.ptr(batch.cseq), N.ptr(changed), N.KMER_FIX_N if fix_n else 0, passes))
+    else:
+        N.check(N.load().kbbq_kmer_correct_rows_ex_dev(ctx.handle, table.handle, seq, meta, n, pitch, flags, int(min_count),
+                                                       N.ptr(batch.cseq), N.ptr(changed), N.KMER_FIX_N if fix_n else 0))
     ctx.status()
     return changed[:n]
+
+
+def _passes_kw(passes):
+    """The keyword for a callee: none at passes = 1, whose calls are the ones they were before the option."""
+    return dict(passes=passes) if passes != 1 else {}
 
 
 def _check_prefilter(min_count, filter_bits):
@@ -513,14 +553,16 @@ def _check_prefilter(min_count, filter_bits):
                          'once, so the filter belongs at the rank that owns the key; run on one GPU, or without the prefilter')
 
 
-def correct_reads(seq_plane, meta, k=31, min_count=None, slots=None, prefilter=False, filter_bits=4, fix_n=False):
+def correct_reads(seq_plane, meta, k=31, min_count=None, slots=None, prefilter=False, filter_bits=4, fix_n=False, passes=1):
     """Count, pick the threshold (min_count, else the histogram's first valley) and correct.  Returns (corrected plane in
     the input's layout and kind, info) with info = {'k', 'min_count', 'hist', 'changed' (per read), 'slots', 'table_bytes',
-    'prefilter', 'filter_bytes', 'admitted', 'fix_n'}.  fix_n: Ns are decided by the N rule against the same table (the
+    'prefilter', 'filter_bytes', 'admitted', 'fix_n', 'passes'}.  passes: the rule applied that many times to each row against
+    the one table counted from the reads as read (the prefilter composes: the lookups only ask count >= min_count >= 2).  fix_n: Ns are decided by the N rule against the same table (the
     prefilter only keeps keys of count 1 out, and the rule asks for count >= min_count >= 2 then).  With `prefilter` a KmerFilter of `filter_bits` bits per k-mer window and array
     keeps most k-mers seen once out of the table: the same plane, threshold and hist[2:]; hist[1] is the number of once-seen
     k-mers that got in; the table, unless `slots` is given, is sized from the filter's `admitted` after `seen` is freed;
     min_count must be >= 2.  filter_bytes is the filter's size during its pass (both arrays); admitted is None without."""
+    passes = check_passes(passes)
     filt = None
     filter_bytes, admitted = 0, None
     if prefilter:
@@ -538,9 +580,9 @@ def correct_reads(seq_plane, meta, k=31, min_count=None, slots=None, prefilter=F
         t = int(min_count) if min_count is not None else solid_threshold(hist)
         if t < 1:
             raise ValueError('min_count must be >= 1, got %d' % t)
-        out, changed = correct_with(table, seq_plane, meta, t, fix_n=fix_n)
+        out, changed = correct_with(table, seq_plane, meta, t, fix_n=fix_n, **_passes_kw(passes))
         return out, dict(k=table.k, min_count=t, hist=hist, changed=changed, slots=table.slots, table_bytes=table.nbytes,
-                         prefilter=bool(prefilter), filter_bytes=filter_bytes, admitted=admitted, fix_n=bool(fix_n))
+                         prefilter=bool(prefilter), filter_bytes=filter_bytes, admitted=admitted, fix_n=bool(fix_n), passes=passes)
     finally:
         if filt is not None:
             filt.close()
@@ -548,14 +590,17 @@ def correct_reads(seq_plane, meta, k=31, min_count=None, slots=None, prefilter=F
             table.close()
 
 
-def correct_fastq(path, out, k=31, min_count=None, slots=None, local_slots=None, prefilter=False, filter_bits=4, fix_n=False):
+def correct_fastq(path, out, k=31, min_count=None, slots=None, local_slots=None, prefilter=False, filter_bits=4, fix_n=False,
+                  passes=1):
     """Correct every read of a FASTQ file (plain or .gz) and write '@' + name, the corrected sequence, '+' and the qualities
     as read to `out` (a path, or a text stream).  Returns correct_reads' info.  In a process group of several ranks (or of
     one with KBBQ_DIST_ALWAYS=1) this is correct_fastq_ranks, which has no prefilter."""
+    passes = check_passes(passes)
     if prefilter:
         _check_prefilter(min_count, filter_bits)
     if _ranks() is not None:
-        return correct_fastq_ranks(path, out, k=k, min_count=min_count, slots=slots, local_slots=local_slots, fix_n=fix_n)
+        return correct_fastq_ranks(path, out, k=k, min_count=min_count, slots=slots, local_slots=local_slots, fix_n=fix_n,
+                                   **_passes_kw(passes))
     from . import fastx
     fq = fastx.NativeFastq(path)
     try:
@@ -566,7 +611,7 @@ def correct_fastq(path, out, k=31, min_count=None, slots=None, local_slots=None,
     finally:
         fq.close()
     fixed, info = correct_reads(seq, meta, k=k, min_count=min_count, slots=slots, prefilter=prefilter, filter_bits=filter_bits,
-                                fix_n=fix_n)
+                                fix_n=fix_n, **_passes_kw(passes))
     text = fastx.format_fastq(names, fixed, qual, meta & 0xFFFF)
     if isinstance(out, str):
         with open(out, 'w', encoding='latin-1', newline='') as fh:
@@ -578,20 +623,23 @@ def correct_fastq(path, out, k=31, min_count=None, slots=None, local_slots=None,
     return info
 
 
-def main_correct(path, output=None, k=31, min_count=None, slots=None, local_slots=None, prefilter=False, filter_bits=4, fix_n=False):
+def main_correct(path, output=None, k=31, min_count=None, slots=None, local_slots=None, prefilter=False, filter_bits=4, fix_n=False,
+                 passes=1):
     """`kbbq correct`: the corrected FASTQ to `output` or stdout; the threshold and the changed bases to stderr (once, by rank
-    0, with the figures of all ranks); with fix_n ` fix_n=1`; with the prefilter also the admitted k-mers and the table's slots."""
+    0, with the figures of all ranks); with fix_n ` fix_n=1`; with passes = P > 1 ` passes=P`; with the prefilter also the
+    admitted k-mers and the table's slots."""
+    passes = check_passes(passes)                        # every rank refuses, before its first collective
     if prefilter:
         _check_prefilter(min_count, filter_bits)         # every rank refuses, before its first collective
     ranks = _ranks()
     if ranks is None:
         info = correct_fastq(path, output if output else sys.stdout, k=k, min_count=min_count, slots=slots,
-                             prefilter=prefilter, filter_bits=filter_bits, fix_n=fix_n)
+                             prefilter=prefilter, filter_bits=filter_bits, fix_n=fix_n, **_passes_kw(passes))
         changed = int(np.asarray(info['changed'], dtype=np.int64).sum())
     else:
         try:
             info = correct_fastq_ranks(path, output if output else sys.stdout, k=k, min_count=min_count, slots=slots,
-                                       local_slots=local_slots, fix_n=fix_n)
+                                       local_slots=local_slots, fix_n=fix_n, **_passes_kw(passes))
         except Exception as exc:
             if not getattr(exc, 'every_rank', False):
                 raise
@@ -604,8 +652,9 @@ def main_correct(path, output=None, k=31, min_count=None, slots=None, local_slot
         changed = info['changed_bases']
         if ranks[1] != 0:
             return info
-    sys.stderr.write('kbbq correct: k=%d min_count=%d reads=%d changed_bases=%d%s%s\n'
+    sys.stderr.write('kbbq correct: k=%d min_count=%d reads=%d changed_bases=%d%s%s%s\n'
                      % (info['k'], info['min_count'], info['reads'], changed, ' fix_n=1' if fix_n else '',
+                        ' passes=%d' % passes if passes > 1 else '',
                         ' prefilter=1 admitted=%d slots=%d' % (info['admitted'], info['slots']) if prefilter else ''))
     return info
 
@@ -763,13 +812,15 @@ def _read_shard(path, rank, world):
     return names, seq, qual, meta
 
 
-def correct_fastq_ranks(path, out, k=31, min_count=None, slots=None, local_slots=None, fix_n=False):
+def correct_fastq_ranks(path, out, k=31, min_count=None, slots=None, local_slots=None, fix_n=False, passes=1):
     """correct_fastq on every rank of the process group: each rank reads, counts and corrects its own records and writes them
     to `out`.rankNNNN (`out` itself with one rank) or, for a stream, to `out` in rank order.  The threshold comes from the
     global histogram; info carries this rank's per-read changes and the global 'reads' and 'changed_bases'.  fix_n: every rank
-    decides its Ns against the gathered solid table at min_count = t, as one process would against the whole table."""
+    decides its Ns against the gathered solid table at min_count = t, as one process would against the whole table.  passes:
+    solidity is all the passes ask of the table too, so the rank files concatenated stay the one-process output."""
     from . import fastx
     from . import parallel
+    passes = check_passes(passes)
     world, rank = parallel.world_rank()
     shard = exc = None
     try:
@@ -792,7 +843,7 @@ def correct_fastq_ranks(path, out, k=31, min_count=None, slots=None, local_slots
     table = solid_table(owned, t)
     fixed = changed = exc = None
     try:
-        fixed, changed = correct_with(table, seq, meta, t, fix_n=fix_n)
+        fixed, changed = correct_with(table, seq, meta, t, fix_n=fix_n, **_passes_kw(passes))
     except Exception as e:                   # noqa: BLE001
         exc = e
     finally:
@@ -808,4 +859,5 @@ def correct_fastq_ranks(path, out, k=31, min_count=None, slots=None, local_slots
             out.write(text)
             out.flush()
         parallel.in_rank_order(write)
-    return dict(k=k, min_count=t, hist=hist, changed=changed, reads=reads, changed_bases=total, fix_n=bool(fix_n))
+    return dict(k=k, min_count=t, hist=hist, changed=changed, reads=reads, changed_bases=total, fix_n=bool(fix_n),
+                passes=passes)

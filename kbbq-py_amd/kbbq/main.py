@@ -13,6 +13,22 @@ from . import __version__
 from . import recalibrate as _recal
 
 
+def _passes(text):
+    """--passes P: an integer in 1..8 (the range of the kbbq_kmer_*_passes* calls)."""
+    try:
+        value = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError('%r is not an integer' % text) from None
+    if not 1 <= value <= 8:
+        raise argparse.ArgumentTypeError('must be in 1..8, got %d' % value)
+    return value
+
+
+_PASSES_HELP = ('%s: apply the k-mer rule to its own output this many times, 1..8 (default 1), read by read against the one table '
+                'counted from the reads as read: an error next to a read end or to another error is corrected once its '
+                'neighbour is')
+
+
 _ENDS_WITH_THE_COMMAND = False               # set by `python -m kbbq.main`: the process ends (main._leave) when the command has run
 
 
@@ -25,6 +41,8 @@ def recalibrate(args):
                      filter_bits=4 if args.filter_bits is None else args.filter_bits)
         if args.fix_n:                           # without the flag the call is the one it was
             kopts['fix_n'] = True
+        if args.passes is not None:
+            kopts['passes'] = args.passes
         # every rank of a launcher refuses here, before it joins the process group
         _recal.check_corrected(args.correct, args.gatkreport, kopts['k'], kopts['min_count'], kopts['prefilter'], kopts['filter_bits'])
     world, _ = parallel.init_from_env()          # one process per GPU under torch.distributed.run; no-op otherwise
@@ -43,8 +61,9 @@ def recalibrate(args):
         with stage('[recalibrate_corrected, wall]'):
             info = _recal.recalibrate_corrected(args.correct, infer_rg=args.infer_rg, gatkreport=args.gatkreport, output=args.output,
                                                 **kopts)
-        sys.stderr.write('kbbq recalibrate: k=%d min_count=%d reads=%d changed_bases=%d%s%s\n'
+        sys.stderr.write('kbbq recalibrate: k=%d min_count=%d reads=%d changed_bases=%d%s%s%s\n'
                          % (info['k'], info['min_count'], info['reads'], info['changed_bases'], ' fix_n=1' if kopts.get('fix_n') else '',
+                            ' passes=%d' % kopts['passes'] if kopts.get('passes', 1) > 1 else '',
                             ' prefilter=1 admitted=%d slots=%d' % (info['admitted'], info['slots']) if kopts['prefilter'] else ''))
         return
     _recal.recalibrate(bam=args.bam, fastq=args.fastq, infer_rg=args.infer_rg,
@@ -59,6 +78,8 @@ def benchmark(args):
     if args.kmers:                                                             # without the flag the call is what it was
         kmers = dict(kmers=dict(k=31 if args.kmer is None else args.kmer, min_count=args.min_count, slots=args.slots,
                                 prefilter=args.prefilter, filter_bits=4 if args.filter_bits is None else args.filter_bits))
+        if args.passes is not None:
+            kmers['kmers']['passes'] = args.passes
     _bm.benchmark(bamfile=args.bam, fafile=args.reference, vcffile=args.vcf, fastqfile=args.fastq,
                   label=args.label, use_oq=args.use_oq, bedfh=args.bedfile, **kmers)
 
@@ -83,13 +104,15 @@ def bqsr(args):
             _device.use_native_memory()      # as `correct` on one GPU: no torch import
         info = {}
         skip = dict(skip_unresolved=True) if args.skip_unresolved else {}      # without the flag the call is what it was
+        more = dict(passes=args.passes) if args.passes is not None else {}     # ... and without this option
         _bqsr.bam_to_report_kmers(aln.AlignmentFile(args.bam), k=31 if args.kmer is None else args.kmer, min_count=args.min_count,
                                   slots=args.slots, prefilter=args.prefilter,
                                   filter_bits=4 if args.filter_bits is None else args.filter_bits, use_oq=args.use_oq,
-                                  info=info, **skip).write(args.gatkreport)
-        sys.stderr.write('kbbq bqsr: k=%d min_count=%d reads=%d flagged_bases=%d%s%s\n'
+                                  info=info, **skip, **more).write(args.gatkreport)
+        sys.stderr.write('kbbq bqsr: k=%d min_count=%d reads=%d flagged_bases=%d%s%s%s\n'
                          % (info['k'], info['min_count'], info['reads'], info['flagged_bases'],
                             ' skipped_bases=%d' % info['skipped_bases'] if skip else '',
+                            ' passes=%d' % args.passes if (args.passes or 1) > 1 else '',
                             ' prefilter=1 admitted=%d slots=%d' % (info['admitted'], info['slots']) if args.prefilter else ''))
         return
     from . import benchmark as _bm
@@ -109,8 +132,9 @@ def correct(args):
     if 'torch' not in sys.modules and not os.environ.get('KBBQ_USE_TORCH'):
         from . import _device
         _device.use_native_memory()          # as `recalibrate` on one GPU: no torch import
+    more = dict(passes=args.passes) if args.passes is not None else {}         # without the option the call is what it was
     kmer.main_correct(args.fastq, output=args.output, k=args.kmer, min_count=args.min_count, slots=args.slots,
-                      local_slots=args.local_slots, prefilter=args.prefilter, filter_bits=args.filter_bits, fix_n=args.fix_n)
+                      local_slots=args.local_slots, prefilter=args.prefilter, filter_bits=args.filter_bits, fix_n=args.fix_n, **more)
 
 
 def main(argv=None):
@@ -143,6 +167,7 @@ def main(argv=None):
     rp.add_argument('--fix-n', action='store_true',
                     help='with -c: give every N the letter that makes the most of the k-mers it alone breaks solid (as `kbbq '
                          'correct --fix-n`)')
+    rp.add_argument('--passes', type=_passes, default=None, metavar='P', help=_PASSES_HELP % 'with -c')
     rp.add_argument('-u', '--use-oq', action='store_true',
                     help='Use the OQ tag for quality scores (BAM input only).')
     rp.add_argument('-s', '--set-oq', action='store_true',
@@ -182,6 +207,7 @@ def main(argv=None):
                          '--min-count >= 2 where given')
     bp.add_argument('--filter-bits', type=int, default=None,
                     help='with --kmers --prefilter: bits per k-mer of the input in each of the filter\'s two arrays, 1..64 (default 4)')
+    bp.add_argument('--passes', type=_passes, default=None, metavar='P', help=_PASSES_HELP % 'with --kmers')
     bp.set_defaults(command=benchmark)
 
     ap = sub.add_parser('applybqsr', description='Recalibrate alignments with a GATK recalibration report (SAM output)')
@@ -220,6 +246,7 @@ def main(argv=None):
                     help='with --kmers: leave a base out of the tally (neither error nor observation) when the k-mers contradict '
                          'it but name no replacement -- two errors within k bases, thin coverage, contamination -- instead of '
                          'counting it as correct')
+    qp.add_argument('--passes', type=_passes, default=None, metavar='P', help=_PASSES_HELP % 'with --kmers')
     qp.set_defaults(command=bqsr)
 
     cp = sub.add_parser('correct', description='Correct substitution errors of a FASTQ file with k-mer counts (GPU); the output '
@@ -245,6 +272,7 @@ def main(argv=None):
     cp.add_argument('--fix-n', action='store_true',
                     help='give every N the letter (A, C, G or T) that makes the most of the k-mers it alone breaks solid; an N '
                          'stays N on a tie or when no letter makes a solid k-mer; a fixed N counts as a changed base')
+    cp.add_argument('--passes', type=_passes, default=None, metavar='P', help=_PASSES_HELP % 'the whole rule (with --fix-n the N rule too)')
     cp.add_argument('-o', '--output', default=None,
                     help='Write the corrected FASTQ to this file instead of stdout; under torch.distributed.run every rank '
                          'writes FILE.rankNNNN, to be concatenated in rank order.')
@@ -254,7 +282,7 @@ def main(argv=None):
     if args.command is recalibrate and args.correct is None:
         given = [flag for flag, v in (('-k/--kmer', args.kmer), ('--min-count', args.min_count), ('--slots', args.slots),
                                       ('--prefilter', args.prefilter or None), ('--filter-bits', args.filter_bits),
-                                      ('--fix-n', args.fix_n or None)) if v is not None]
+                                      ('--fix-n', args.fix_n or None), ('--passes', args.passes)) if v is not None]
         if given:
             rp.error('%s: only with -c/--correct' % ', '.join(given))
     if args.command is benchmark:
@@ -263,8 +291,8 @@ def main(argv=None):
                 bp.error('-f/--fastq: not with --kmers (the k-mers are those of the alignments\' own sequences)')
         else:
             given = [flag for flag, v in (('-k/--kmer', args.kmer), ('--min-count', args.min_count), ('--slots', args.slots),
-                                          ('--prefilter', args.prefilter or None), ('--filter-bits', args.filter_bits))
-                     if v is not None]
+                                          ('--prefilter', args.prefilter or None), ('--filter-bits', args.filter_bits),
+                                          ('--passes', args.passes)) if v is not None]
             if given:
                 bp.error('%s: only with --kmers' % ', '.join(given))
     if args.command is bqsr:
@@ -276,7 +304,8 @@ def main(argv=None):
             given = [flag for flag, v in (('-k/--kmer', args.kmer), ('--min-count', args.min_count), ('--slots', args.slots),
                                           ('--prefilter', args.prefilter or None), ('--filter-bits', args.filter_bits),
                                           ('-u/--use-oq', args.use_oq or None),
-                                          ('--skip-unresolved', args.skip_unresolved or None)) if v is not None]
+                                          ('--skip-unresolved', args.skip_unresolved or None), ('--passes', args.passes))
+                     if v is not None]
             if given:
                 qp.error('%s: only with --kmers' % ', '.join(given))
             missing = [flag for flag, v in (('-r/--reference', args.reference), ('-v/--vcf', args.vcf)) if v is None]

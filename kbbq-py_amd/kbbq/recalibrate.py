@@ -392,7 +392,7 @@ def check_corrected(path, gatkreport=None, k=31, min_count=None, prefilter=False
 
 
 def recalibrate_corrected(path, infer_rg=False, gatkreport=None, output=None, k=31, min_count=None, slots=None, prefilter=False,
-                          filter_bits=4, fix_n=False):
+                          filter_bits=4, fix_n=False, passes=1):
     """`kbbq correct` and `kbbq recalibrate -f reads corrected` in one run over ONE file: the reads go to the device once, in
     the layout pass 2 uses (fastx.pack_single), their k-mers are counted and the reads corrected where they lie
     (kmer.count_batch / correct_batch: the corrected plane is each band's cseq), and the tally, the solve, the apply and the
@@ -400,12 +400,15 @@ def recalibrate_corrected(path, infer_rg=False, gatkreport=None, output=None, k=
     is, byte for byte, that of the two commands.  Returns info: k, min_count, hist, reads, changed_bases, slots (and
     admitted with the prefilter) and fix_n.  fix_n: the N rule of `kbbq correct --fix-n` in every band's own layout -- a fixed N
     reaches K1 as the difference from the original's N it is in the two-file form.  gatkreport: the model of the tally is saved there; an existing report is refused.
+    passes: `kbbq correct --passes P` in every band's own layout (kmer.correct_batch); info carries it.
     One process, mapped inputs, reads that fit the device budget: anything else raises ValueError naming the two commands."""
+    from . import kmer
+    passes = kmer.check_passes(passes)
     check_corrected(path, gatkreport, k, min_count, prefilter, filter_bits)
     done_with = []
     try:
         return _recalibrate_corrected(path, infer_rg, gatkreport, output, int(k), min_count, slots, prefilter, filter_bits, done_with,
-                                      bool(fix_n))
+                                      bool(fix_n), passes)
     finally:
         for reader in done_with:
             fastx.close_later(reader)
@@ -416,14 +419,16 @@ def _batch_bytes(batch):
                                                                getattr(batch, 'out_plane', None)) if x is not None)
 
 
-def _recalibrate_corrected(path, infer_rg, gatkreport, output, k, min_count, slots, prefilter, filter_bits, done_with, fix_n=False):
+def _recalibrate_corrected(path, infer_rg, gatkreport, output, k, min_count, slots, prefilter, filter_bits, done_with, fix_n=False,
+                           passes=1):
     from . import kmer
+    more = kmer._passes_kw(passes)
     scan = fastx.PairScan(path, None, infer_rg)
     _warm_up()
     text = scan.result()[0]
     done_with.append(text)
     info = dict(k=k, min_count=int(min_count or 0), hist=np.zeros(kmer.HIST, dtype=np.int64), reads=int(text.n), changed_bases=0,
-                slots=0, fix_n=fix_n)
+                slots=0, fix_n=fix_n, passes=passes)
     if prefilter:
         info['admitted'] = 0
     if text.n == 0:
@@ -473,14 +478,14 @@ def _recalibrate_corrected(path, infer_rg, gatkreport, output, k, min_count, slo
         info['min_count'] = t
         with stage('k-mer correct', sync=True):
             for r in rows:
-                info['changed_bases'] += int(kmer.correct_batch(table, r, t, fix_n=fix_n).cpu().numpy().astype(np.int64).sum())
+                info['changed_bases'] += int(kmer.correct_batch(table, r, t, fix_n=fix_n, **more).cpu().numpy().astype(np.int64).sum())
 
         def corrected_rows(band):
             # a band whose layout the tally refuses is redone one character row per read; its corrected characters come from the
             # character kernels on those rows, which is why the table lives until the tally is over
             batch = fastx.band_rows(band)
             if batch.cseq is None:
-                kmer.correct_batch(table, batch, t, fix_n=fix_n)
+                kmer.correct_batch(table, batch, t, fix_n=fix_n, **more)
             return batch
         tables = _tally_local(single, 6, 42, band_rows=corrected_rows)
     finally:

@@ -7,6 +7,8 @@
 2. The stage times of the command's Python path (kbbq.benchmark.benchmark with kmers=...) on a truth set generated here (SAM text,
    FASTA, VCF): reader, reference and sites, upload + K4, qualities, the k-mer stages, the joint tally, the table.
 
+With --passes P the command runs with `--passes P` (the k-mer flags of P passes of the rule).
+
 No oracle and no file of the repository's is read; everything is generated from --seed."""
 import argparse, contextlib, io, os, shutil, sys, tempfile, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -19,6 +21,7 @@ ap.add_argument('--records', type=int, default=200_000, help='alignments of the 
 ap.add_argument('--genome', type=int, default=1_000_000, help='bases of the generated reference')
 ap.add_argument('-k', '--kmer', type=int, default=31)
 ap.add_argument('--seed', type=int, default=1)
+ap.add_argument('--passes', type=int, default=None, help='run the command with --passes P (1..8)')
 a = ap.parse_args()
 import numpy as np, torch
 from kbbq import _device as dev, _native as N
@@ -110,12 +113,13 @@ if a.records:
         out, err = io.StringIO(), io.StringIO()
         t0 = time.perf_counter()
         with contextlib.redirect_stdout(out), contextlib.redirect_stderr(err):
-            bm.benchmark(sam, fa, vcf, label='timing', kmers=dict(k=a.kmer))
+            bm.benchmark(sam, fa, vcf, label='timing', kmers=dict(k=a.kmer, **({} if a.passes is None else dict(passes=a.passes))))
         return time.perf_counter() - t0, err.getvalue().strip()
     run()                                                      # warm: code objects, the page cache
     total, line = run()
     print(line)
-    print('kbbq benchmark --kmers -k %d on %d records x %d bases, genome %d: %.1f ms' % (a.kmer, m, L, G, total * 1e3))
+    print('kbbq benchmark --kmers -k %d%s on %d records x %d bases, genome %d: %.1f ms'
+          % (a.kmer, '' if a.passes is None else ' --passes %d' % a.passes, m, L, G, total * 1e3))
     for name, dt in stages:
         print('  %-48s %8.2f ms  %4.1f %%' % (name, dt * 1e3, 100 * dt / total))
     print('  %-48s %8.2f ms  %4.1f %%' % ('(between the stages)', (total - sum(dt for _, dt in stages)) * 1e3,

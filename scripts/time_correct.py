@@ -15,7 +15,12 @@ table right after kbbq_kmer_correct_dev ("ms_flags", "flagged_bases"); the leg f
 corrected plane differs from the input.
 With `--unresolved` (needs `--flags`) every repetition also times kbbq_kmer_flag_ex_dev with KBBQ_KMER_FLAG_UNRESOLVED right
 after kbbq_kmer_flag_dev ("ms_flags_unresolved", "unresolved_bases"); the leg fails unless its plane with every 2 turned to 0
-is kbbq_kmer_flag_dev's and its per-read counts add up to the plane's 1s and 2s."""
+is kbbq_kmer_flag_dev's and its per-read counts add up to the plane's 1s and 2s.
+With `--passes P` (2..8) every repetition also times, for p = 2 .. P, kbbq_kmer_correct_passes_dev with passes = p
+("ms_correct_passes"[p]) and its yardstick, p successive kbbq_kmer_correct_dev launches that feed their plane back through
+global memory against the same table ("ms_correct_repeated"[p]); the leg fails unless the two planes are equal.  With `--flags
+--unresolved` also kbbq_kmer_flag_passes_dev with KBBQ_KMER_FLAG_UNRESOLVED ("ms_flags_unresolved_passes"[p], with the 1s and 2s
+of its plane); the leg fails unless its 1s are where the corrected plane of p passes differs from the input."""
 import argparse
 import ctypes
 import json
@@ -39,10 +44,14 @@ ap.add_argument('--fix-n', action='store_true', help='also time the correct step
 ap.add_argument('--flags', action='store_true', help='also time the flag form of the correct step (kbbq_kmer_flag_dev)')
 ap.add_argument('--unresolved', action='store_true',
                 help='with --flags: also time the flag form with unresolved bases as 2 (kbbq_kmer_flag_ex_dev)')
+ap.add_argument('--passes', type=int, default=1,
+                help='also time 2 .. P passes of the correct step in one launch (kbbq_kmer_correct_passes_dev) and as P launches')
 ap.add_argument('--n-rate', type=float, default=0.0, help='share of the bases set to N')
 args = ap.parse_args()
 if args.unresolved and not args.flags:
     ap.error('--unresolved: only with --flags')
+if not 1 <= args.passes <= 8:
+    ap.error('--passes: 1..8')
 
 import numpy as np
 import torch
@@ -79,6 +88,8 @@ out2 = torch.empty_like(seq) if args.prefilter else None   # the prefiltered leg
 out_n = torch.empty_like(seq) if args.fix_n else None     # the plane of the correct step with the N rule
 flags = torch.empty_like(seq) if args.flags else None     # the plane of the flag form
 flags_u = torch.empty_like(seq) if args.unresolved else None      # ... with unresolved bases as 2
+out_p = torch.empty_like(seq) if args.passes > 1 else None # the plane of several passes in one launch
+ping = [torch.empty_like(seq), torch.empty_like(seq)] if args.passes > 1 else None        # ... and of as many launches
 lib = N.load()
 
 
@@ -115,6 +126,24 @@ if args.unresolved:
     ms['flags_unresolved'] = []
     n_err = torch.empty((n,), dtype=torch.int32, device='cuda')
     n_unres = torch.empty((n,), dtype=torch.int32, device='cuda')
+PASSES = list(range(2, args.passes + 1))
+ms_fused, ms_repeated, ms_flags_fused = {p: [] for p in PASSES}, {p: [] for p in PASSES}, {p: [] for p in PASSES}
+changed_p, flagged_p, unresolved_p = {}, {}, {}
+if PASSES and args.unresolved:
+    p_err = torch.empty((n,), dtype=torch.int32, device='cuda')
+    p_unres = torch.empty((n,), dtype=torch.int32, device='cuda')
+
+
+def repeated(table, t, p):
+    """p launches of the one-pass kernel, each on the plane of the one before; the last plane."""
+    src = seq
+    for i in range(p):
+        dst = ping[i & 1]
+        N.check(lib.kbbq_kmer_correct_dev(table.ctx.handle, table.handle, N.ptr(src), N.ptr(meta), n, pitch, t, N.ptr(dst), None))
+        src = dst
+    return src
+
+
 dh = torch.zeros(257, dtype=torch.int64, device='cuda')
 for rep in range(args.reps + 1):
     base = rep_base()
@@ -138,6 +167,28 @@ for rep in range(args.reps + 1):
         xu = timed(lambda: N.check(lib.kbbq_kmer_flag_ex_dev(table.ctx.handle, table.handle, N.ptr(seq), N.ptr(meta), n, pitch, t,
                                                              N.ptr(flags_u), N.ptr(n_err), N.ptr(n_unres),
                                                              N.KMER_FLAG_UNRESOLVED)))
+    for p in PASSES:
+        xp = timed(lambda: N.check(lib.kbbq_kmer_correct_passes_dev(table.ctx.handle, table.handle, N.ptr(seq), N.ptr(meta), n, pitch,
+                                                                    t, N.ptr(out_p), None, 0, p)))
+        xr = timed(lambda: repeated(table, t, p))
+        assert torch.equal(out_p, ping[(p - 1) & 1]), '%d passes in one launch are not %d launches' % (p, p)
+        changed_p[p] = int((out_p != seq).sum().item())
+        if args.unresolved:
+            xq = timed(lambda: N.check(lib.kbbq_kmer_flag_passes_dev(table.ctx.handle, table.handle, N.ptr(seq), N.ptr(meta), n, pitch,
+                                                                     t, N.ptr(flags_u), N.ptr(p_err), N.ptr(p_unres),
+                                                                     N.KMER_FLAG_UNRESOLVED, p)))
+            assert torch.equal(flags_u == 1, out_p != seq), 'the flag form of %d passes decided differently from the correction' % p
+            flagged_p[p] = int(p_err.sum(dtype=torch.int64).item())
+            unresolved_p[p] = int(p_unres.sum(dtype=torch.int64).item())
+            assert unresolved_p[p] == int((flags_u == 2).sum(dtype=torch.int64).item()), 'd_unresolved does not add up to the 2s'
+        if rep:
+            ms_fused[p].append(xp); ms_repeated[p].append(xr)
+            if args.unresolved:
+                ms_flags_fused[p].append(xq)
+    if PASSES and args.unresolved:                     # the plane the checks below read is the one-pass one
+        N.check(lib.kbbq_kmer_flag_ex_dev(table.ctx.handle, table.handle, N.ptr(seq), N.ptr(meta), n, pitch, t, N.ptr(flags_u),
+                                          N.ptr(n_err), N.ptr(n_unres), N.KMER_FLAG_UNRESOLVED))
+        torch.cuda.synchronize()
     table.close()
     if rep:                                            # the first round is the warm-up
         ms['count'].append(c); ms['histogram'].append(h); ms['correct'].append(x)
@@ -172,6 +223,15 @@ if args.unresolved:
     assert torch.equal(torch.where(flags_u == 2, torch.zeros_like(flags_u), flags_u), flags), 'the option changed a byte that is no 2'
     assert int(n_err.sum(dtype=torch.int64).item()) == res['flagged_bases'], 'd_changed does not add up to the 1s'
     assert int(n_unres.sum(dtype=torch.int64).item()) == res['unresolved_bases'], 'd_unresolved does not add up to the 2s'
+if PASSES:
+    spread = lambda v: [round(float(np.median(v)), 3), round(min(v), 3), round(max(v), 3)]       # median, fastest, slowest
+    res['ms_correct_passes'] = {str(p): spread(ms_fused[p]) for p in PASSES}
+    res['ms_correct_repeated'] = {str(p): spread(ms_repeated[p]) for p in PASSES}
+    res['changed_bases_passes'] = {str(p): changed_p[p] for p in PASSES}
+    if args.unresolved:
+        res['ms_flags_unresolved_passes'] = {str(p): spread(ms_flags_fused[p]) for p in PASSES}
+        res['flagged_bases_passes'] = {str(p): flagged_p[p] for p in PASSES}
+        res['unresolved_bases_passes'] = {str(p): unresolved_p[p] for p in PASSES}
 if args.prefilter:
     from kbbq import _device as dev
     plain_out, plain_hist, plain_t = out, hist, t
