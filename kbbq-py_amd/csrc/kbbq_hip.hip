@@ -2184,10 +2184,10 @@ int kbbq_kmer_table_info(const kbbq_kmer_table* t, int* k, int64_t* slots, void*
     return KBBQ_OK;
 }
 
-// rows per workgroup and LDS words per row-chunk of the kernels that walk k-mer windows; the table's fields stay unset.
-// nib: 4-bit planes -- `pitch` bases a row in pitch / 2 bytes, rows 8-byte aligned
+// rows per workgroup and dynamic LDS of a kernel that walks k-mer windows and carves its LDS as `l`; the table's fields stay
+// unset.  nib: 4-bit planes -- `pitch` bases a row in pitch / 2 bytes, rows 8-byte aligned.  passes: km_correct_passes', else 1
 static int kmer_rows(kbbq_ctx* c, const char* who, int k, const uint8_t* d_seq, const uint32_t* d_meta, int64_t n, int pitch,
-                     KmerParams& p, int lds_words, size_t* lds, bool nib = false)
+                     bool nib, KmLds l, int passes, KmerParams& p, size_t* lds)
 {
     int rc = check_planes(who, n, pitch, nib ? nullptr : d_seq, nullptr, nullptr);
     if (rc) return rc;
@@ -2197,25 +2197,31 @@ static int kmer_rows(kbbq_ctx* c, const char* who, int k, const uint8_t* d_seq, 
     p.rows_per_wg = std::max(1, KM_THREADS / p.cpr);
     p.keys = nullptr; p.counts = nullptr; p.mask = 0; p.status = c->d_status;
     p.min_count = 1; p.out = nullptr; p.changed = nullptr; p.unresolved = nullptr;
-    *lds = ((size_t)lds_words * p.rows_per_wg * p.cpr + p.rows_per_wg) * 4;
-    if (*lds > (size_t)c->lds_bytes) return fail(KBBQ_E_ARG, "%s: pitch %d needs %zu bytes of LDS", who, pitch, *lds);
-    return KBBQ_OK;
+    *lds = km_lds_bytes(l, p.rows_per_wg, p.cpr);
+    if (*lds <= (size_t)c->lds_bytes) return KBBQ_OK;
+    if (passes > 1)
+        return fail(KBBQ_E_ARG, "%s: pitch %d needs %zu bytes of LDS with passes = %d (> %d)", who, pitch, *lds, passes, c->lds_bytes);
+    return fail(KBBQ_E_ARG, "%s: pitch %d needs %zu bytes of LDS", who, pitch, *lds);
 }
 
 // ... of the count / correct kernels
 static int kmer_geometry(kbbq_ctx* c, const char* who, const kbbq_kmer_table* t, const uint8_t* d_seq, const uint32_t* d_meta,
-                         int64_t n, int pitch, KmerParams& p, int lds_words, size_t* lds, bool nib = false)
+                         int64_t n, int pitch, bool nib, KmLds l, int passes, KmerParams& p, size_t* lds)
 {
     if (!c || !t) return fail(KBBQ_E_ARG, "%s: NULL ctx or table", who);
-    int rc = kmer_rows(c, who, t->k, d_seq, d_meta, n, pitch, p, lds_words, lds, nib);
+    int rc = kmer_rows(c, who, t->k, d_seq, d_meta, n, pitch, nib, l, passes, p, lds);
     if (rc) return rc;
     p.keys = t->keys; p.counts = t->counts; p.mask = (u64)t->slots - 1;
     return KBBQ_OK;
 }
 
-// launches of at most 2^20 workgroups
-static int kmer_launches(const KmerParams& p, const std::function<void(const KmerParams&, unsigned)>& launch)
+// the instantiation of a window kernel for the rows' reader
+#define KM_READER(K, nib) ((nib) ? (const void*)K<true> : (const void*)K<false>)
+
+// launches of at most 2^20 workgroups.  `extra`: the kernel's second parameter (KmerFilterParams, passes), if it has one
+static int kmer_launches(kbbq_ctx* c, const KmerParams& p, const void* kernel, size_t lds, const void* extra)
 {
+    HIPCHK(hipSetDevice(c->device));
     const int64_t per = ((int64_t)1 << 20) * p.rows_per_wg;
     for (int64_t lo = 0; lo < p.nrows; lo += per) {
         KmerParams q = p;
@@ -2224,8 +2230,9 @@ static int kmer_launches(const KmerParams& p, const std::function<void(const Kme
         if (p.out) q.out = p.out + (size_t)lo * p.pitch;
         if (p.changed) q.changed = p.changed + lo;
         if (p.unresolved) q.unresolved = p.unresolved + lo;
-        launch(q, (unsigned)((m + p.rows_per_wg - 1) / p.rows_per_wg));
-        HIPCHK(hipGetLastError());
+        void* args[] = {&q, const_cast<void*>(extra)};  // hipLaunchKernel reads one entry per kernel parameter: `extra` goes unread by
+                                                        // a one-parameter kernel and must be set for a two-parameter one
+        HIPCHK(hipLaunchKernel(kernel, dim3((unsigned)((m + p.rows_per_wg - 1) / p.rows_per_wg)), dim3(KM_THREADS), args, lds, c->stream));
     }
     return KBBQ_OK;
 }
@@ -2234,13 +2241,9 @@ static int kmer_count_rows(kbbq_ctx* c, const char* who, kbbq_kmer_table* t, con
                            int pitch, bool nib)
 {
     KmerParams p; size_t lds = 0;
-    int rc = kmer_geometry(c, who, t, d_seq, d_meta, n, pitch, p, 2, &lds, nib);
+    int rc = kmer_geometry(c, who, t, d_seq, d_meta, n, pitch, nib, KM_LDS_COUNT, 1, p, &lds);
     if (rc || n == 0) return rc;
-    HIPCHK(hipSetDevice(c->device));
-    return kmer_launches(p, [&](const KmerParams& q, unsigned grid) {
-        if (nib) hipLaunchKernelGGL(km_count<true>, dim3(grid), dim3(KM_THREADS), lds, c->stream, q);
-        else hipLaunchKernelGGL(km_count<false>, dim3(grid), dim3(KM_THREADS), lds, c->stream, q);
-    });
+    return kmer_launches(c, p, KM_READER(km_count, nib), lds, nullptr);
 }
 
 int kbbq_kmer_count_dev(kbbq_ctx* c, kbbq_kmer_table* t, const uint8_t* d_seq, const uint32_t* d_meta, int64_t n, int pitch)
@@ -2279,29 +2282,33 @@ int kbbq_kmer_histogram_dev(kbbq_ctx* c, const kbbq_kmer_table* t, uint64_t* d_h
     return KBBQ_OK;
 }
 
+// Which of the correction kernels a call wants.  passes: 1 km_correct, 2..KM_MAX_PASSES km_correct_passes.
+// pairs (KBBQ_ROWS_PAIRS) matter to the N rule alone: the separator of two reads is no N.
+struct KmerForm { bool nib; int fixn; bool flags, unres; int passes; };
+
+static KmerForm kmer_form_rows(bool nib, bool pairs, int opts, int passes)
+{
+    return {nib, !(opts & KBBQ_KMER_FIX_N) ? KM_FIXN_OFF : pairs ? KM_FIXN_PAIRS : KM_FIXN_READS, false, false, passes};
+}
+
+// ... and the kernel of a form: [several passes][reader x KM_FIXN_*, the flag form, the flag form with unresolved bases]
+#define KM_FORMS(K) {(const void*)K<false, KM_FIXN_OFF>, (const void*)K<false, KM_FIXN_READS>, (const void*)K<false, KM_FIXN_PAIRS>, \
+                     (const void*)K<true, KM_FIXN_OFF>, (const void*)K<true, KM_FIXN_READS>, (const void*)K<true, KM_FIXN_PAIRS>,    \
+                     (const void*)K<false, KM_FIXN_OFF, true>, (const void*)K<false, KM_FIXN_OFF, true, true>}
+static const void* const KM_CORRECT[2][8] = {KM_FORMS(km_correct), KM_FORMS(km_correct_passes)};
+
+static const void* kmer_correct_kernel(const KmerForm& f, KmLds* l)
+{
+    *l = f.passes > 1 ? KM_LDS_PASSES : KM_LDS_CORRECT;
+    return KM_CORRECT[f.passes > 1][f.flags ? 6 + (f.unres ? 1 : 0) : (f.nib ? 3 : 0) + f.fixn];
+}
+
 // the `opts` word of the kbbq_kmer_correct*_ex calls (not the KBBQ_ROWS_* flags): checked before anything is launched
 static int kmer_correct_opts(const char* who, int opts)
 {
     if (opts & ~KBBQ_KMER_FIX_N) return fail(KBBQ_E_ARG, "%s: unknown bits in opts 0x%x (KBBQ_KMER_FIX_N = %d)", who, opts, KBBQ_KMER_FIX_N);
     return KBBQ_OK;
 }
-
-// km_correct's instantiations: [4-bit planes][KM_FIXN_*]
-static void (*const KM_CORRECT[2][3])(KmerParams) = {
-    {km_correct<false, KM_FIXN_OFF>, km_correct<false, KM_FIXN_READS>, km_correct<false, KM_FIXN_PAIRS>},
-    {km_correct<true, KM_FIXN_OFF>, km_correct<true, KM_FIXN_READS>, km_correct<true, KM_FIXN_PAIRS>},
-};
-
-// ... of the flag form: [KBBQ_KMER_FLAG_UNRESOLVED]
-static void (*const KM_FLAG[2])(KmerParams) = {km_correct<false, KM_FIXN_OFF, true>, km_correct<false, KM_FIXN_OFF, true, true>};
-
-// km_correct_passes' instantiations, as the two tables above (the kbbq_kmer_*_passes* calls with passes >= 2)
-static void (*const KM_CORRECT_PASSES[2][3])(KmerParams, int) = {
-    {km_correct_passes<false, KM_FIXN_OFF>, km_correct_passes<false, KM_FIXN_READS>, km_correct_passes<false, KM_FIXN_PAIRS>},
-    {km_correct_passes<true, KM_FIXN_OFF>, km_correct_passes<true, KM_FIXN_READS>, km_correct_passes<true, KM_FIXN_PAIRS>},
-};
-static void (*const KM_FLAG_PASSES[2])(KmerParams, int) = {km_correct_passes<false, KM_FIXN_OFF, true>,
-                                                           km_correct_passes<false, KM_FIXN_OFF, true, true>};
 
 // the `passes` of the kbbq_kmer_*_passes* calls: checked before anything else
 static int kmer_passes_ok(const char* who, int passes)
@@ -2310,122 +2317,109 @@ static int kmer_passes_ok(const char* who, int passes)
     return KBBQ_OK;
 }
 
-// pairs: two reads to a row (KBBQ_ROWS_PAIRS), which the N rule alone needs to know -- their separator is no N
-// flag_form: d_out is a flag plane (kbbq_kmer_flag_dev / kbbq_kmer_flag_ex_dev; character rows).  Its opts are its own:
-// 0 or KBBQ_KMER_FLAG_UNRESOLVED, checked by the caller; d_unresolved (may be NULL) then receives the per-row count of 2s
-// passes: 1 launches km_correct, 2..KM_MAX_PASSES km_correct_passes (checked by the caller: kmer_passes_ok)
+// d_out: the corrected plane, with f.flags the flag plane; d_unresolved (may be NULL): the per-row count of 2s of the flag form,
+// zeroed here when the form writes none.  The caller has checked its opts and passes.
 static int kmer_correct_rows(kbbq_ctx* c, const char* who, const kbbq_kmer_table* t, const uint8_t* d_seq, const uint32_t* d_meta,
-                             int64_t n, int pitch, bool nib, bool pairs, int min_count, uint8_t* d_out, uint32_t* d_changed, int opts,
-                             bool flag_form = false, uint32_t* d_unresolved = nullptr, int passes = 1)
+                             int64_t n, int pitch, int min_count, uint8_t* d_out, uint32_t* d_changed, uint32_t* d_unresolved,
+                             const KmerForm& f)
 {
-    int rc = flag_form ? KBBQ_OK : kmer_correct_opts(who, opts);
+    KmerParams p; size_t lds = 0; KmLds l;
+    const void* kernel = kmer_correct_kernel(f, &l);
+    int rc = kmer_geometry(c, who, t, d_seq, d_meta, n, pitch, f.nib, l, f.passes, p, &lds);
     if (rc) return rc;
-    KmerParams p; size_t lds = 0;
-    rc = kmer_geometry(c, who, t, d_seq, d_meta, n, pitch, p, 3, &lds, nib);
-    if (rc) return rc;
-    if (passes > 1) {                                   // the row in two copies, its first state and the marks: kbbq_kmer.h
-        lds = ((size_t)KM_PASS_WORDS * p.rows_per_wg * p.cpr + 2 * (size_t)p.rows_per_wg + 1) * 4;
-        if (lds > (size_t)c->lds_bytes)
-            return fail(KBBQ_E_ARG, "%s: pitch %d needs %zu bytes of LDS with passes = %d (> %d)", who, pitch, lds, passes, c->lds_bytes);
-    }
     if (min_count < 1) return fail(KBBQ_E_ARG, "%s: min_count must be >= 1, got %d", who, min_count);
-    if (n > 0 && (!d_out || ((uintptr_t)d_out & (nib ? 7 : 15))))
-        return fail(KBBQ_E_ARG, "%s: d_out NULL or not %d-byte aligned", who, nib ? 8 : 16);
+    if (n > 0 && (!d_out || ((uintptr_t)d_out & (f.nib ? 7 : 15))))
+        return fail(KBBQ_E_ARG, "%s: d_out NULL or not %d-byte aligned", who, f.nib ? 8 : 16);
     if (n == 0) return KBBQ_OK;
-    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipSetDevice(c->device));                    // for the memset and the attribute; kmer_launches sets it for the other paths
     p.min_count = (u32)min_count; p.out = d_out; p.changed = d_changed;
-    const bool unres = flag_form && (opts & KBBQ_KMER_FLAG_UNRESOLVED);
-    if (unres) p.unresolved = d_unresolved;
+    if (f.unres) p.unresolved = d_unresolved;
     else if (d_unresolved) HIPCHK(hipMemsetAsync(d_unresolved, 0, (size_t)n * 4, c->stream));     // no byte is 2 without the option
-    const auto kernel = flag_form ? KM_FLAG[unres ? 1 : 0]
-                                  : KM_CORRECT[nib ? 1 : 0][!(opts & KBBQ_KMER_FIX_N) ? KM_FIXN_OFF : pairs ? KM_FIXN_PAIRS : KM_FIXN_READS];
-    if (passes > 1) {
-        const int fixn = !(opts & KBBQ_KMER_FIX_N) ? KM_FIXN_OFF : pairs ? KM_FIXN_PAIRS : KM_FIXN_READS;
-        const auto fused = flag_form ? KM_FLAG_PASSES[unres ? 1 : 0] : KM_CORRECT_PASSES[nib ? 1 : 0][fixn];
-        if (lds > 64 * 1024)                            // beyond what a kernel may take without asking
-            HIPCHK(hipFuncSetAttribute((const void*)fused, hipFuncAttributeMaxDynamicSharedMemorySize, c->lds_bytes));
-        return kmer_launches(p, [&](const KmerParams& q, unsigned grid) {
-            hipLaunchKernelGGL(fused, dim3(grid), dim3(KM_THREADS), lds, c->stream, q, passes);
-        });
-    }
-    return kmer_launches(p, [&](const KmerParams& q, unsigned grid) {
-        hipLaunchKernelGGL(kernel, dim3(grid), dim3(KM_THREADS), lds, c->stream, q);
-    });
+    if (f.passes > 1 && lds > 64 * 1024)                // beyond what a kernel may take without asking
+        HIPCHK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, c->lds_bytes));
+    return kmer_launches(c, p, kernel, lds, &f.passes);
+}
+
+// character rows, one read a row: opts and passes are checked here
+static int kmer_correct_reads(kbbq_ctx* c, const char* who, const kbbq_kmer_table* t, const uint8_t* d_seq, const uint32_t* d_meta,
+                              int64_t n, int pitch, int min_count, uint8_t* d_out, uint32_t* d_changed, int opts, int passes)
+{
+    int rc = kmer_passes_ok(who, passes);
+    if (!rc) rc = kmer_correct_opts(who, opts);
+    if (rc) return rc;
+    return kmer_correct_rows(c, who, t, d_seq, d_meta, n, pitch, min_count, d_out, d_changed, nullptr, kmer_form_rows(false, false, opts, passes));
 }
 
 int kbbq_kmer_correct_ex_dev(kbbq_ctx* c, const kbbq_kmer_table* t, const uint8_t* d_seq, const uint32_t* d_meta, int64_t n, int pitch,
                              int min_count, uint8_t* d_out, uint32_t* d_changed, int opts)
 {
-    return kmer_correct_rows(c, "kbbq_kmer_correct_ex_dev", t, d_seq, d_meta, n, pitch, false, false, min_count, d_out, d_changed, opts);
+    return kmer_correct_reads(c, "kbbq_kmer_correct_ex_dev", t, d_seq, d_meta, n, pitch, min_count, d_out, d_changed, opts, 1);
 }
 
 int kbbq_kmer_correct_dev(kbbq_ctx* c, const kbbq_kmer_table* t, const uint8_t* d_seq, const uint32_t* d_meta, int64_t n, int pitch,
                           int min_count, uint8_t* d_out, uint32_t* d_changed)
 {
-    return kmer_correct_rows(c, "kbbq_kmer_correct_dev", t, d_seq, d_meta, n, pitch, false, false, min_count, d_out, d_changed, 0);
-}
-
-static int kmer_flag_rows(kbbq_ctx* c, const char* who, const kbbq_kmer_table* t, const uint8_t* d_seq, const uint32_t* d_meta, int64_t n,
-                          int pitch, int min_count, uint8_t* d_flags, uint32_t* d_changed, uint32_t* d_unresolved, int opts, int passes = 1)
-{
-    if (opts & ~KBBQ_KMER_FLAG_UNRESOLVED)
-        return fail(KBBQ_E_ARG, "%s: opts 0x%x: the flag form takes KBBQ_KMER_FLAG_UNRESOLVED (%d) alone%s", who, opts,
-                    KBBQ_KMER_FLAG_UNRESOLVED, (opts & KBBQ_KMER_FIX_N) ? " (it has no N rule)" : "");
-    // kbbq_kmer_correct_dev's refusals; those of the numbers alone come first, so that they need no context to be decided
-    int rc = check_planes(who, n, pitch, d_seq, d_flags, nullptr);
-    if (rc) return rc;
-    if (min_count < 1) return fail(KBBQ_E_ARG, "%s: min_count must be >= 1, got %d", who, min_count);
-    return kmer_correct_rows(c, who, t, d_seq, d_meta, n, pitch, false, false, min_count, d_flags, d_changed, opts, true, d_unresolved, passes);
-}
-
-int kbbq_kmer_flag_dev(kbbq_ctx* c, const kbbq_kmer_table* t, const uint8_t* d_seq, const uint32_t* d_meta, int64_t n, int pitch,
-                       int min_count, uint8_t* d_flags, uint32_t* d_changed)
-{
-    return kmer_flag_rows(c, "kbbq_kmer_flag_dev", t, d_seq, d_meta, n, pitch, min_count, d_flags, d_changed, nullptr, 0);
-}
-
-int kbbq_kmer_flag_ex_dev(kbbq_ctx* c, const kbbq_kmer_table* t, const uint8_t* d_seq, const uint32_t* d_meta, int64_t n, int pitch,
-                          int min_count, uint8_t* d_flags, uint32_t* d_changed, uint32_t* d_unresolved, int opts)
-{
-    return kmer_flag_rows(c, "kbbq_kmer_flag_ex_dev", t, d_seq, d_meta, n, pitch, min_count, d_flags, d_changed, d_unresolved, opts);
-}
-
-int kbbq_kmer_flag_passes_dev(kbbq_ctx* c, const kbbq_kmer_table* t, const uint8_t* d_seq, const uint32_t* d_meta, int64_t n, int pitch,
-                              int min_count, uint8_t* d_flags, uint32_t* d_changed, uint32_t* d_unresolved, int opts, int passes)
-{
-    int rc = kmer_passes_ok("kbbq_kmer_flag_passes_dev", passes);
-    if (rc) return rc;
-    return kmer_flag_rows(c, "kbbq_kmer_flag_passes_dev", t, d_seq, d_meta, n, pitch, min_count, d_flags, d_changed, d_unresolved, opts,
-                          passes);
+    return kmer_correct_reads(c, "kbbq_kmer_correct_dev", t, d_seq, d_meta, n, pitch, min_count, d_out, d_changed, 0, 1);
 }
 
 int kbbq_kmer_correct_passes_dev(kbbq_ctx* c, const kbbq_kmer_table* t, const uint8_t* d_seq, const uint32_t* d_meta, int64_t n, int pitch,
                                  int min_count, uint8_t* d_out, uint32_t* d_changed, int opts, int passes)
 {
-    int rc = kmer_passes_ok("kbbq_kmer_correct_passes_dev", passes);
-    if (rc) return rc;
-    return kmer_correct_rows(c, "kbbq_kmer_correct_passes_dev", t, d_seq, d_meta, n, pitch, false, false, min_count, d_out, d_changed, opts,
-                             false, nullptr, passes);
+    return kmer_correct_reads(c, "kbbq_kmer_correct_passes_dev", t, d_seq, d_meta, n, pitch, min_count, d_out, d_changed, opts, passes);
 }
 
+// the flag form.  Its opts are its own: 0 or KBBQ_KMER_FLAG_UNRESOLVED
+static int kmer_flag_rows(kbbq_ctx* c, const char* who, const kbbq_kmer_table* t, const uint8_t* d_seq, const uint32_t* d_meta, int64_t n,
+                          int pitch, int min_count, uint8_t* d_flags, uint32_t* d_changed, uint32_t* d_unresolved, int opts, int passes)
+{
+    int rc = kmer_passes_ok(who, passes);
+    if (rc) return rc;
+    if (opts & ~KBBQ_KMER_FLAG_UNRESOLVED)
+        return fail(KBBQ_E_ARG, "%s: opts 0x%x: the flag form takes KBBQ_KMER_FLAG_UNRESOLVED (%d) alone%s", who, opts,
+                    KBBQ_KMER_FLAG_UNRESOLVED, (opts & KBBQ_KMER_FIX_N) ? " (it has no N rule)" : "");
+    // kbbq_kmer_correct_dev's refusals; those of the numbers alone come first, so that they need no context to be decided
+    rc = check_planes(who, n, pitch, d_seq, d_flags, nullptr);
+    if (rc) return rc;
+    if (min_count < 1) return fail(KBBQ_E_ARG, "%s: min_count must be >= 1, got %d", who, min_count);
+    return kmer_correct_rows(c, who, t, d_seq, d_meta, n, pitch, min_count, d_flags, d_changed, d_unresolved,
+                             {false, KM_FIXN_OFF, true, (opts & KBBQ_KMER_FLAG_UNRESOLVED) != 0, passes});
+}
+
+int kbbq_kmer_flag_dev(kbbq_ctx* c, const kbbq_kmer_table* t, const uint8_t* d_seq, const uint32_t* d_meta, int64_t n, int pitch,
+                       int min_count, uint8_t* d_flags, uint32_t* d_changed)
+{
+    return kmer_flag_rows(c, "kbbq_kmer_flag_dev", t, d_seq, d_meta, n, pitch, min_count, d_flags, d_changed, nullptr, 0, 1);
+}
+
+int kbbq_kmer_flag_ex_dev(kbbq_ctx* c, const kbbq_kmer_table* t, const uint8_t* d_seq, const uint32_t* d_meta, int64_t n, int pitch,
+                          int min_count, uint8_t* d_flags, uint32_t* d_changed, uint32_t* d_unresolved, int opts)
+{
+    return kmer_flag_rows(c, "kbbq_kmer_flag_ex_dev", t, d_seq, d_meta, n, pitch, min_count, d_flags, d_changed, d_unresolved, opts, 1);
+}
+
+int kbbq_kmer_flag_passes_dev(kbbq_ctx* c, const kbbq_kmer_table* t, const uint8_t* d_seq, const uint32_t* d_meta, int64_t n, int pitch,
+                              int min_count, uint8_t* d_flags, uint32_t* d_changed, uint32_t* d_unresolved, int opts, int passes)
+{
+    return kmer_flag_rows(c, "kbbq_kmer_flag_passes_dev", t, d_seq, d_meta, n, pitch, min_count, d_flags, d_changed, d_unresolved, opts, passes);
+}
+
+// resident rows of either reader, one or two reads a row (KBBQ_ROWS_*)
 static int kmer_correct_rows_flags(kbbq_ctx* c, const char* who, const kbbq_kmer_table* t, const uint8_t* d_seq, const uint32_t* d_meta,
                                    int64_t nrows, int pitch, int flags, int min_count, uint8_t* d_out, uint32_t* d_changed, int opts,
-                                   int passes = 1)
+                                   int passes)
 {
-    int rc = kmer_correct_opts(who, opts);
-    if (rc) return rc;
+    int rc = kmer_passes_ok(who, passes);
+    if (!rc) rc = kmer_correct_opts(who, opts);
     bool nib = false;
-    rc = kmer_row_flags(who, flags, &nib);
+    if (!rc) rc = kmer_row_flags(who, flags, &nib);
     if (rc) return rc;
-    return kmer_correct_rows(c, who, t, d_seq, d_meta, nrows, pitch, nib, (flags & KBBQ_ROWS_PAIRS) != 0, min_count, d_out, d_changed, opts,
-                             false, nullptr, passes);
+    return kmer_correct_rows(c, who, t, d_seq, d_meta, nrows, pitch, min_count, d_out, d_changed, nullptr,
+                             kmer_form_rows(nib, (flags & KBBQ_ROWS_PAIRS) != 0, opts, passes));
 }
 
 int kbbq_kmer_correct_rows_passes_dev(kbbq_ctx* c, const kbbq_kmer_table* t, const uint8_t* d_seq, const uint32_t* d_meta, int64_t nrows,
                                       int pitch, int flags, int min_count, uint8_t* d_out, uint32_t* d_changed, int opts, int passes)
 {
-    int rc = kmer_passes_ok("kbbq_kmer_correct_rows_passes_dev", passes);
-    if (rc) return rc;
     return kmer_correct_rows_flags(c, "kbbq_kmer_correct_rows_passes_dev", t, d_seq, d_meta, nrows, pitch, flags, min_count, d_out, d_changed,
                                    opts, passes);
 }
@@ -2433,13 +2427,13 @@ int kbbq_kmer_correct_rows_passes_dev(kbbq_ctx* c, const kbbq_kmer_table* t, con
 int kbbq_kmer_correct_rows_ex_dev(kbbq_ctx* c, const kbbq_kmer_table* t, const uint8_t* d_seq, const uint32_t* d_meta, int64_t nrows,
                                   int pitch, int flags, int min_count, uint8_t* d_out, uint32_t* d_changed, int opts)
 {
-    return kmer_correct_rows_flags(c, "kbbq_kmer_correct_rows_ex_dev", t, d_seq, d_meta, nrows, pitch, flags, min_count, d_out, d_changed, opts);
+    return kmer_correct_rows_flags(c, "kbbq_kmer_correct_rows_ex_dev", t, d_seq, d_meta, nrows, pitch, flags, min_count, d_out, d_changed, opts, 1);
 }
 
 int kbbq_kmer_correct_rows_dev(kbbq_ctx* c, const kbbq_kmer_table* t, const uint8_t* d_seq, const uint32_t* d_meta, int64_t nrows,
                                int pitch, int flags, int min_count, uint8_t* d_out, uint32_t* d_changed)
 {
-    return kmer_correct_rows_flags(c, "kbbq_kmer_correct_rows_dev", t, d_seq, d_meta, nrows, pitch, flags, min_count, d_out, d_changed, 0);
+    return kmer_correct_rows_flags(c, "kbbq_kmer_correct_rows_dev", t, d_seq, d_meta, nrows, pitch, flags, min_count, d_out, d_changed, 0, 1);
 }
 
 int kbbq_kmer_table_clear_dev(kbbq_ctx* c, kbbq_kmer_table* t)
@@ -2524,9 +2518,10 @@ int kbbq_kmer_count(kbbq_ctx* c, kbbq_kmer_table* t, const uint8_t* seq, const u
 }
 
 static int kmer_correct_host(kbbq_ctx* c, const char* who, const kbbq_kmer_table* t, const uint8_t* seq, const uint32_t* meta, int64_t n,
-                             int pitch, int min_count, uint8_t* out, uint32_t* changed, int opts, int passes = 1)
+                             int pitch, int min_count, uint8_t* out, uint32_t* changed, int opts, int passes)
 {
-    int orc = kmer_correct_opts(who, opts);
+    int orc = kmer_passes_ok(who, passes);
+    if (!orc) orc = kmer_correct_opts(who, opts);
     if (orc) return orc;
     if (!c || !t) return fail(KBBQ_E_ARG, "%s: NULL ctx or table", who);
     if (n < 0 || pitch <= 0 || (pitch & 15)) return fail(KBBQ_E_ARG, "%s: bad n/pitch", who);
@@ -2541,8 +2536,8 @@ static int kmer_correct_host(kbbq_ctx* c, const char* who, const kbbq_kmer_table
         if (done + m > n) return fail(KBBQ_E_HIP, "%s: more rows launched than given", who);
         uint32_t* dch = changed ? (uint32_t*)dc.p + done : nullptr;
         done += m;
-        return kmer_correct_rows(c, who, t, d, (const uint32_t*)(d + 2 * plane), m, pitch, false, false, min_count, d + plane, dch, opts,
-                                 false, nullptr, passes);
+        return kmer_correct_rows(c, who, t, d, (const uint32_t*)(d + 2 * plane), m, pitch, min_count, d + plane, dch, nullptr,
+                                 kmer_form_rows(false, false, opts, passes));
     });
     if (rc || !changed) return rc;
     HIPCHK(hipMemcpyAsync(changed, dc.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
@@ -2553,21 +2548,19 @@ static int kmer_correct_host(kbbq_ctx* c, const char* who, const kbbq_kmer_table
 int kbbq_kmer_correct_ex(kbbq_ctx* c, const kbbq_kmer_table* t, const uint8_t* seq, const uint32_t* meta, int64_t n, int pitch,
                          int min_count, uint8_t* out, uint32_t* changed, int opts)
 {
-    return kmer_correct_host(c, "kbbq_kmer_correct_ex", t, seq, meta, n, pitch, min_count, out, changed, opts);
+    return kmer_correct_host(c, "kbbq_kmer_correct_ex", t, seq, meta, n, pitch, min_count, out, changed, opts, 1);
 }
 
 int kbbq_kmer_correct_passes(kbbq_ctx* c, const kbbq_kmer_table* t, const uint8_t* seq, const uint32_t* meta, int64_t n, int pitch,
                              int min_count, uint8_t* out, uint32_t* changed, int opts, int passes)
 {
-    int rc = kmer_passes_ok("kbbq_kmer_correct_passes", passes);
-    if (rc) return rc;
     return kmer_correct_host(c, "kbbq_kmer_correct_passes", t, seq, meta, n, pitch, min_count, out, changed, opts, passes);
 }
 
 int kbbq_kmer_correct(kbbq_ctx* c, const kbbq_kmer_table* t, const uint8_t* seq, const uint32_t* meta, int64_t n, int pitch,
                       int min_count, uint8_t* out, uint32_t* changed)
 {
-    return kmer_correct_host(c, "kbbq_kmer_correct", t, seq, meta, n, pitch, min_count, out, changed, 0);
+    return kmer_correct_host(c, "kbbq_kmer_correct", t, seq, meta, n, pitch, min_count, out, changed, 0, 1);
 }
 
 // ---- prefilter: k-mers seen once stay out of the table (kbbq_kmer.h) ----------------------------------------------------------
@@ -2671,14 +2664,10 @@ static int kmer_prefilter_rows(kbbq_ctx* c, const char* who, kbbq_kmer_filter* f
     if (k < 8 || k > 32) return fail(KBBQ_E_ARG, "%s: k must be in 8..32, got %d", who, k);
     if (!f->seen) return fail(KBBQ_E_ARG, "%s: the filter's `seen` array has been released", who);
     KmerParams p; size_t lds = 0;
-    int rc = kmer_rows(c, who, k, d_seq, d_meta, n, pitch, p, 2, &lds, nib);
+    int rc = kmer_rows(c, who, k, d_seq, d_meta, n, pitch, nib, KM_LDS_PREFILTER, 1, p, &lds);
     if (rc || n == 0) return rc;
-    HIPCHK(hipSetDevice(c->device));
     const KmerFilterParams fp = kmer_filter_params(f);
-    return kmer_launches(p, [&](const KmerParams& q, unsigned grid) {
-        if (nib) hipLaunchKernelGGL(km_prefilter<true>, dim3(grid), dim3(KM_THREADS), lds, c->stream, q, fp);
-        else hipLaunchKernelGGL(km_prefilter<false>, dim3(grid), dim3(KM_THREADS), lds, c->stream, q, fp);
-    });
+    return kmer_launches(c, p, KM_READER(km_prefilter, nib), lds, &fp);
 }
 
 int kbbq_kmer_prefilter_dev(kbbq_ctx* c, kbbq_kmer_filter* f, int k, const uint8_t* d_seq, const uint32_t* d_meta, int64_t n, int pitch)
@@ -2700,14 +2689,10 @@ static int kmer_count_filtered_rows(kbbq_ctx* c, const char* who, kbbq_kmer_tabl
 {
     if (!f) return fail(KBBQ_E_ARG, "%s: filter is NULL", who);
     KmerParams p; size_t lds = 0;
-    int rc = kmer_geometry(c, who, t, d_seq, d_meta, n, pitch, p, 2, &lds, nib);
+    int rc = kmer_geometry(c, who, t, d_seq, d_meta, n, pitch, nib, KM_LDS_COUNT, 1, p, &lds);
     if (rc || n == 0) return rc;
-    HIPCHK(hipSetDevice(c->device));
     const KmerFilterParams fp = kmer_filter_params(f);
-    return kmer_launches(p, [&](const KmerParams& q, unsigned grid) {
-        if (nib) hipLaunchKernelGGL(km_count_filtered<true>, dim3(grid), dim3(KM_THREADS), lds, c->stream, q, fp);
-        else hipLaunchKernelGGL(km_count_filtered<false>, dim3(grid), dim3(KM_THREADS), lds, c->stream, q, fp);
-    });
+    return kmer_launches(c, p, KM_READER(km_count_filtered, nib), lds, &fp);
 }
 
 int kbbq_kmer_count_filtered_dev(kbbq_ctx* c, kbbq_kmer_table* t, const kbbq_kmer_filter* f, const uint8_t* d_seq,

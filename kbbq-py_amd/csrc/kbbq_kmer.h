@@ -14,38 +14,57 @@
 // slots does not occur; a table that is too small fails with KBBQ_E_FULL instead of dropping k-mers.  A lookup stops at its
 // key, an empty slot or after the same KM_MAX_PROBES probes: every key a successful count inserted lies within that reach.
 //
-// Work (count and correct): a workgroup takes whole rows, floor(256 / chunks per row) of them (one row when a row has more
-// than 256 chunks), and every thread one 16-byte chunk at a time.  Pass 1 turns each chunk into a 32-bit code word and a
-// 16-bit break mask in LDS; a thread then reads the words of the next two chunks of its row from LDS (every window starting
-// in its chunk ends at most 46 bases later) and handles the 16 windows that start in its chunk.  Correct keeps one
-// (solid, valid) bit pair per window in LDS; base i is trusted when a solid window starts in [i - k + 1, i] -- one mask test
-// over the words of the base's own chunk and the two before it -- or when no valid window does.  Only untrusted A/C/G/T bases
-// look up the 3 x (covering windows) substituted k-mers.  Every base is judged against the read as read (no cascade).
+// Work split (every kernel that walks windows): a workgroup takes whole rows, floor(256 / chunks per row) of them (one row when
+// a row has more than 256 chunks), and every thread one 16-base chunk at a time.  km_load_chunks turns each chunk into a 32-bit
+// code word and a 16-bit break mask in LDS; a thread then reads the words of the next two chunks of its row from LDS (every
+// window starting in its chunk ends at most 46 bases later) and handles the 16 windows that start in its chunk: km_walk /
+// km_chunk_windows hold that loop, the kernels give it what to do with a window (stage W of km_correct_passes, which skips
+// the windows no changed base lies in before it looks at their breaks, keeps a loop of its own).  Each kernel's dynamic LDS
+// is a KmLds, from which the host takes the byte count and the kernel its pointers.
 //
-// N rule (km_correct<NIB, FIXN != KM_FIXN_OFF>; include/kbbq_hip.h KBBQ_KMER_FIX_N): an 'N' (4-bit planes: code 4) inside the read
-// takes the letter that makes the most of its candidate windows solid -- the windows that cover it, lie inside the read and hold
-// no other break -- when that number is >= 1 and strictly the largest of the four.  Which of a chunk's breaks are Ns comes from
-// the chunk pass 3 has in registers anyway (it rewrites it), "no other break" from the break masks of chunks ch - 2 .. ch + 2
-// already in LDS: the form keeps nothing more there.  KM_FIXN_PAIRS: the rows hold two reads (KBBQ_ROWS_PAIRS), and the base
-// at (length - 1) / 2 is their separator, never an N.  Counting, the filter and the substitution rule see an N as the break
-// it is, fixed or not.
+// Row readers: those kernels are templates over NIB, and only km_load_chunks, km_read_chunk / km_write_chunk / km_chunk_base
+// and km_put know it.
+// NIB = false: character planes, 16 bytes a chunk.  NIB = true: the 4-bit sequence planes the recalibrate file path keeps
+// resident (include/kbbq_hip.h KBBQ_ROWS_NIBBLES: codes A0 T1 G2 C3, 4 = N / separator / padding; 8 bytes a chunk, word w holds
+// bases 8w..8w+3 in the low nibbles of its bytes and 8w+4..8w+7 in the high ones).  A nibble >= 4 is a break; the other codes
+// map to the table's A0 C1 G2 T3 by swapping 1 and 3, so keys, counts and filter words are those of the character kernels on
+// the same bases.  KmerParams.pitch is the plane's row stride in BYTES (half the bases of a row with NIB), cpr the 16-base
+// chunks of a row.  A mate-pair row is one row: its separator is a break, no window spans it.
 //
-// Flag form (km_correct<false, KM_FIXN_OFF, true>; include/kbbq_hip.h kbbq_kmer_flag_dev): the same decision with another
-// store stage (km_put).  KmerParams.out is a flag plane of the input's geometry, one byte a base: 1 where the correction would
-// write another letter, 0 everywhere else -- breaks, trusted bases, ties, padding.  A thread starts from a chunk of zeros
-// instead of the chunk as read (pass 1 has the codes it needs in LDS) and stores its 16 bytes whatever they hold, so every
-// byte of the plane is written: 1 B/base out, where a corrected plane would be written, read back and compared.
-// UNRES (km_correct<false, KM_FIXN_OFF, true, true>; kbbq_kmer_flag_ex_dev with KBBQ_KMER_FLAG_UNRESOLVED): the third outcome of
-// the rule gets a value of its own.  An A/C/G/T base that at least one valid window covers, none of them solid, and for which
-// the substitution loop names no strict winner >= 1 (a tie, or no substitution makes a solid k-mer) becomes 2 -- the skip bit
-// of the aligned tally's flag plane -- at the one point where that loop gives up (km_flag).  A byte is 0, 1 or 2, never 3.
-// The row's counter in LDS then holds the 1s in its low and the 2s in its high 16 bits (a row has at most 65535 bases, and a
-// base is one or the other), so the form keeps nothing more in LDS; KmerParams.unresolved receives the high half.
+// THE RULE (km_decide; stage D of km_correct_passes says the same inline, see there).  A window is valid when it holds no
+// break and solid when its k-mer's count is >= min_count; one (solid, valid) bit pair per window lives in LDS (`sv`).  For
+// base i of a row:
+//   trust         an A/C/G/T base is trusted when a solid window starts in [i - k + 1, i] -- one mask test over the words of the
+//                 base's own chunk and the two before it (km_window_bits) -- or when no valid window does.  A trusted base and a
+//                 break stay as they are.
+//   substitution  an untrusted base takes the letter, of the other three, that makes the most of the valid windows over it
+//                 solid (km_vote_subst), when that number is >= 1 and strictly the largest (km_winner); 3 x (covering windows)
+//                 lookups.  Otherwise it is unresolved and stays.
+//   N rule        (FIXN != KM_FIXN_OFF; KBBQ_KMER_FIX_N) an 'N' (4-bit planes: code 4) inside the read takes the letter that
+//                 makes the most of its candidate windows solid -- the windows that cover it, lie inside the read and hold no
+//                 other break (km_vote_n: the break masks of chunks ch - 2 .. ch + 2 in LDS) -- by the same pick, of all four.
+//                 Which breaks of a chunk are such Ns: km_chunk_ns, from the chunk's bytes.  KM_FIXN_PAIRS: the rows hold two
+//                 reads (KBBQ_ROWS_PAIRS), and the base at (length - 1) / 2 is their separator, never an N.  Counting, the
+//                 filter and the substitution rule see an N as the break it is.
+// Every base is judged against the same state of the row (no cascade inside a pass), so nothing depends on thread order.
+// km_decide returns the letter to write, KM_LEAVE or KM_UNRESOLVED; the two kernels differ in where the decision goes:
+//   km_correct         judges the row as read and puts the decision into the chunk it holds in registers and then stores
+//                      (km_put): the corrected plane, characters or nibbles.  3 LDS words a chunk and a counter a row.
+//   ... FLAGS          (kbbq_kmer_flag_dev) KmerParams.out is a flag plane of the input's geometry, one byte a base: 1 where the
+//                      correction would write another letter, 0 everywhere else -- breaks, trusted bases, ties, padding.  The
+//                      chunk starts as zeros instead of the bytes read and is stored whatever it holds: every byte is written.
+//   ... UNRES          (KBBQ_KMER_FLAG_UNRESOLVED) KM_UNRESOLVED becomes 2 in the flag plane (km_flag), the skip bit of the aligned
+//                      tally.  A byte is 0, 1 or 2, never 3.  The row's counter in LDS holds the 1s in its low and the 2s in its
+//                      high 16 bits (a row has at most 65535 bases, and a base is one or the other); KmerParams.unresolved
+//                      receives the high half.
+//   km_correct_passes  keeps the row in LDS and applies the rule to its own output up to `passes` times: the decisions of a
+//                      pass go to a second copy of the row's code words and break masks.  See the comment at the kernel.
 //
 // Ranks (kbbq/kmer.py count_kmers_ranks): the owner of a canonical key among W ranks is km_owner(key, W), the high 32 bits of
 // the same mix taken of the key XOR a constant, scaled to 0..W-1.  It shares no bits with the home slot (km_hash(key) & mask),
 // so the keys one rank owns spread over all home slots of its table.  km_select_sizes / km_select_scatter sort the occupied
-// slots with count >= min_count into buckets by owner (one bucket: compaction), km_merge adds (key, count) pairs to a table.
+// slots with count >= min_count into buckets by owner (one bucket: compaction), km_merge adds (key, count) pairs to a table
+// through km_insert, as km_count adds 1.
 //
 // Prefilter (kbbq correct --prefilter): a filter is two arrays of `words` (a power of two) 64-bit words, `seen` and `twice`.
 // A canonical key has one word index and one mask of up to 4 bits, the same in both arrays (km_filter_index).  km_prefilter
@@ -55,14 +74,6 @@
 // more is in `twice`, whatever the thread order.  Bits are only ever set, so a relaxed load that shows the whole mask is
 // final and the atomic is skipped.  km_count_filtered is km_count for the windows whose mask is whole in `twice`: the table
 // then holds every key of count >= 2 with its exact count and some keys of count 1 (false positives), nothing else.
-//
-// Row readers: the kernels that walk windows are templates over NIB, and only pass 1 (km_load_chunks) and km_correct's load
-// and store of the chunk it rewrites read it.  NIB = false: character planes, 16 bytes a chunk.  NIB = true: the 4-bit sequence planes the
-// recalibrate file path keeps resident (include/kbbq_hip.h KBBQ_ROWS_NIBBLES: codes A0 T1 G2 C3, 4 = N / separator / padding;
-// 8 bytes a chunk, word w holds bases 8w..8w+3 in the low nibbles of its bytes and 8w+4..8w+7 in the high ones).  A nibble
-// >= 4 is a break; the other codes map to the table's A0 C1 G2 T3 by swapping 1 and 3, so keys, counts and filter words are
-// those of the character kernels on the same bases.  KmerParams.pitch is the plane's row stride in BYTES (half the bases of a
-// row with NIB), cpr the 16-base chunks of a row.  A mate-pair row is one row: its separator is a break, no window spans it.
 #pragma once
 #include "kbbq_kernels.h"
 
@@ -122,26 +133,83 @@ __device__ __forceinline__ u32 km_lookup(const KmerParams& p, u64 key)
     return 0;
 }
 
-__device__ __forceinline__ bool km_insert(const KmerParams& p, u64 key)
+// counts[key] += add; false when neither the key nor an empty slot lies within KM_MAX_PROBES probes
+__device__ __forceinline__ bool km_insert(u64* keys, u32* counts, u64 mask, u64 key, u32 add)
 {
-    u64 s = km_hash(key) & p.mask;
-    for (int i = 0; i < KM_MAX_PROBES; ++i) {
-        u64 cur = km_load_key(p.keys + s);
+    u64 s = km_hash(key) & mask;
+    bool done = false;
+    for (int i = 0; i < KM_MAX_PROBES && !done; ++i) {
+        u64 cur = km_load_key(keys + s);
         if (cur == KM_EMPTY) {
-            cur = atomicCAS(p.keys + s, KM_EMPTY, key);
+            cur = atomicCAS(keys + s, KM_EMPTY, key);
             if (cur == KM_EMPTY) cur = key;                               // this lane claimed the slot
         }
-        if (cur == key) { atomicAdd(p.counts + s, 1u); return true; }
-        s = (s + 1) & p.mask;
+        if (cur == key) { atomicAdd(counts + s, add); done = true; }
+        s = (s + 1) & mask;
     }
-    return false;
+    return done;
 }
+
+// ---- dynamic LDS of the kernels that walk windows: `chunk` arrays of one word per chunk of the workgroup's rows, then `row`
+// arrays of one word per row, then `wg` single words.  The host takes the byte count and the kernels their pointers from here.
+struct KmLds { int chunk, row, wg; };
+constexpr KmLds KM_LDS_COUNT = {2, 0, 0};       // km_count, km_count_filtered: code, brk
+constexpr KmLds KM_LDS_PREFILTER = {2, 0, 1};   // km_prefilter: code, brk; the workgroup's `admitted`
+constexpr KmLds KM_LDS_CORRECT = {3, 1, 0};     // km_correct: code, brk, sv; nchg
+constexpr KmLds KM_LDS_PASSES = {8, 2, 1};      // km_correct_passes: code0, brk0, (code, brk) twice, sv, mark; nchg, last; wglast
+
+__host__ __device__ __forceinline__ size_t km_lds_bytes(KmLds l, int rows_per_wg, int cpr)
+{
+    return ((size_t)l.chunk * rows_per_wg * cpr + (size_t)l.row * rows_per_wg + l.wg) * 4;
+}
+__device__ __forceinline__ u32* km_lds_chunk(u32* lds, const KmerParams& p, int i) { return lds + i * p.rows_per_wg * p.cpr; }
+__device__ __forceinline__ u32* km_lds_row(u32* lds, KmLds l, const KmerParams& p, int i)
+{
+    return lds + l.chunk * p.rows_per_wg * p.cpr + i * p.rows_per_wg;
+}
+__device__ __forceinline__ u32* km_lds_wg(u32* lds, KmLds l, const KmerParams& p) { return km_lds_row(lds, l, p, l.row); }
 
 // the table's code (A0 C1 G2 T3) of a plane nibble 0..3 (A0 T1 G2 C3) and back: 1 and 3 change places
 __device__ __forceinline__ u32 km_nib_swap(u32 n) { return n ^ ((n & 1u) << 1); }
 
 // bit offset of base t (0..7) of a word of a 4-bit plane
 __device__ __forceinline__ int km_nib_shift(int t) { return 8 * (t & 3) + 4 * ((t >> 2) & 1); }
+
+// byte offset in the plane of chunk ch of a row: a chunk is 8 bytes of nibbles or 16 of characters
+template <bool NIB>
+__device__ __forceinline__ size_t km_chunk_at(const KmerParams& p, int64_t row, int ch)
+{
+    return (size_t)row * p.pitch + (size_t)ch * (NIB ? 8 : 16);
+}
+
+// the chunk at `at` as 4 words of characters or 2 of nibbles; FLAGS: a chunk of the flag plane instead, all 0, nothing to read
+template <bool NIB, bool FLAGS = false>
+__device__ __forceinline__ void km_read_chunk(const uint8_t* at, u32 (&w)[4])
+{
+    w[0] = w[1] = w[2] = w[3] = 0;
+    if constexpr (FLAGS) {
+    } else if constexpr (NIB) {
+        const uint2 v = *reinterpret_cast<const uint2*>(at);
+        w[0] = v.x; w[1] = v.y;
+    } else {
+        const uint4 v = *reinterpret_cast<const uint4*>(at);
+        w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
+    }
+}
+
+template <bool NIB>
+__device__ __forceinline__ void km_write_chunk(uint8_t* at, const u32 (&w)[4])
+{
+    if constexpr (NIB) *reinterpret_cast<uint2*>(at) = make_uint2(w[0], w[1]);
+    else *reinterpret_cast<uint4*>(at) = make_uint4(w[0], w[1], w[2], w[3]);
+}
+
+// base t of a chunk as the plane holds it: a character or a nibble
+template <bool NIB>
+__device__ __forceinline__ u32 km_chunk_base(const u32 (&w)[4], int t)
+{
+    return NIB ? (w[t >> 3] >> km_nib_shift(t & 7)) & 0xFu : (w[t >> 2] >> (8 * (t & 3))) & 0xFFu;
+}
 
 // Pass 1: the code word (base t of the chunk in bits 31 - 2t .. 30 - 2t) and break mask (bit t) of every chunk of the
 // workgroup's rows.  Returns the number of rows this workgroup holds.
@@ -202,29 +270,50 @@ __device__ __forceinline__ u64 km_window(unsigned __int128 x, int o, int k)
     return (u64)((x << (2 * o)) >> (128 - 2 * k));
 }
 
+// The window walk.  km_chunk_windows: f(o, forward code) for every window without a break that starts o bases into chunk ch of
+// the row at e_row; f returns whether to go on, and so does the walk.  km_walk: f(r, e, o, forward code) for every such window
+// of the workgroup's nr rows, a thread taking chunks e = threadIdx.x, + KM_THREADS, ... (r: the row in the workgroup).
+template <class F>
+__device__ __forceinline__ bool km_chunk_windows(const KmerParams& p, const u32* code, const u32* brk, int e_row, int ch, F&& f)
+{
+    const u64 kmask = (1ull << p.k) - 1;
+    u64 b;
+    const unsigned __int128 x = km_words(p, code, brk, e_row, ch, 3, &b);
+    for (int o = 0; o < 16; ++o) {
+        if ((b >> o) & kmask) continue;
+        if (!f(o, km_window(x, o, p.k))) return false;
+    }
+    return true;
+}
+
+template <class F>
+__device__ __forceinline__ void km_walk(const KmerParams& p, const u32* code, const u32* brk, int nr, F&& f)
+{
+    for (int e = threadIdx.x; e < nr * p.cpr; e += KM_THREADS) {
+        const int r = e / p.cpr, ch = e - r * p.cpr;
+        if (!km_chunk_windows(p, code, brk, r * p.cpr, ch, [&](int o, u64 w) { return f(r, e, o, w); })) return;
+    }
+}
+
+__device__ __forceinline__ bool km_table_full(const KmerParams& p)
+{
+    return __hip_atomic_load(p.status + ST_KMER, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != ~0ull;
+}
+
 template <bool NIB>
 __global__ __launch_bounds__(KM_THREADS) void km_count(KmerParams p)
 {
     extern __shared__ u32 km_lds[];
-    const int E = p.rows_per_wg * p.cpr;
-    u32* code = km_lds; u32* brk = km_lds + E;
+    u32* code = km_lds_chunk(km_lds, p, 0); u32* brk = km_lds_chunk(km_lds, p, 1);
     const int64_t row0 = (int64_t)blockIdx.x * p.rows_per_wg;
     const int nr = km_load_chunks<NIB>(p, row0, code, brk);
     __syncthreads();
-    if (__hip_atomic_load(p.status + ST_KMER, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != ~0ull) return;   // the table is full
-    const u64 kmask = (1ull << p.k) - 1;
-    for (int e = threadIdx.x; e < nr * p.cpr; e += KM_THREADS) {
-        const int r = e / p.cpr, ch = e - r * p.cpr;
-        u64 b;
-        const unsigned __int128 x = km_words(p, code, brk, r * p.cpr, ch, 3, &b);
-        for (int o = 0; o < 16; ++o) {
-            if ((b >> o) & kmask) continue;
-            if (!km_insert(p, km_canonical(km_window(x, o, p.k), p.k))) {
-                atomicMin(p.status + ST_KMER, (u64)(row0 + r));
-                return;
-            }
-        }
-    }
+    if (km_table_full(p)) return;
+    km_walk(p, code, brk, nr, [&](int r, int, int, u64 f) {
+        if (km_insert(p.keys, p.counts, p.mask, km_canonical(f, p.k), 1u)) return true;
+        atomicMin(p.status + ST_KMER, (u64)(row0 + r));
+        return false;
+    });
 }
 
 // ---- prefilter: keys seen once stay out of the table ---------------------------------------------------------------------------
@@ -254,26 +343,20 @@ template <bool NIB>
 __global__ __launch_bounds__(KM_THREADS) void km_prefilter(KmerParams p, KmerFilterParams f)
 {
     extern __shared__ u32 km_lds[];
-    const int E = p.rows_per_wg * p.cpr;
-    u32* code = km_lds; u32* brk = km_lds + E; u32* adm = km_lds + 2 * E;
+    u32* code = km_lds_chunk(km_lds, p, 0); u32* brk = km_lds_chunk(km_lds, p, 1);
+    u32* adm = km_lds_wg(km_lds, KM_LDS_PREFILTER, p);
     const int64_t row0 = (int64_t)blockIdx.x * p.rows_per_wg;
     if (threadIdx.x == 0) *adm = 0;
     const int nr = km_load_chunks<NIB>(p, row0, code, brk);
     __syncthreads();
-    const u64 kmask = (1ull << p.k) - 1;
     u32 mine = 0;
-    for (int e = threadIdx.x; e < nr * p.cpr; e += KM_THREADS) {
-        const int r = e / p.cpr, ch = e - r * p.cpr;
-        u64 b;
-        const unsigned __int128 x = km_words(p, code, brk, r * p.cpr, ch, 3, &b);
-        for (int o = 0; o < 16; ++o) {
-            if ((b >> o) & kmask) continue;
-            u64 m;
-            const u64 w = km_filter_index(km_canonical(km_window(x, o, p.k), p.k), f.wmask, &m);
-            if ((km_filter_or(f.seen + w, m) & m) != m) continue;         // first of its mask
-            if ((km_filter_or(f.twice + w, m) & m) != m) ++mine;
-        }
-    }
+    km_walk(p, code, brk, nr, [&](int, int, int, u64 fw) {
+        u64 m;
+        const u64 w = km_filter_index(km_canonical(fw, p.k), f.wmask, &m);
+        if ((km_filter_or(f.seen + w, m) & m) != m) return true;          // first of its mask
+        if ((km_filter_or(f.twice + w, m) & m) != m) ++mine;
+        return true;
+    });
     if (mine) atomicAdd(adm, mine);
     __syncthreads();
     if (threadIdx.x == 0 && *adm) atomicAdd(f.admitted, (u64)*adm);
@@ -284,29 +367,20 @@ template <bool NIB>
 __global__ __launch_bounds__(KM_THREADS) void km_count_filtered(KmerParams p, KmerFilterParams f)
 {
     extern __shared__ u32 km_lds[];
-    const int E = p.rows_per_wg * p.cpr;
-    u32* code = km_lds; u32* brk = km_lds + E;
+    u32* code = km_lds_chunk(km_lds, p, 0); u32* brk = km_lds_chunk(km_lds, p, 1);
     const int64_t row0 = (int64_t)blockIdx.x * p.rows_per_wg;
     const int nr = km_load_chunks<NIB>(p, row0, code, brk);
     __syncthreads();
-    if (__hip_atomic_load(p.status + ST_KMER, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != ~0ull) return;   // the table is full
-    const u64 kmask = (1ull << p.k) - 1;
-    for (int e = threadIdx.x; e < nr * p.cpr; e += KM_THREADS) {
-        const int r = e / p.cpr, ch = e - r * p.cpr;
-        u64 b;
-        const unsigned __int128 x = km_words(p, code, brk, r * p.cpr, ch, 3, &b);
-        for (int o = 0; o < 16; ++o) {
-            if ((b >> o) & kmask) continue;
-            const u64 key = km_canonical(km_window(x, o, p.k), p.k);
-            u64 m;
-            const u64 w = km_filter_index(key, f.wmask, &m);
-            if ((f.twice[w] & m) != m) continue;                          // seen once
-            if (!km_insert(p, key)) {
-                atomicMin(p.status + ST_KMER, (u64)(row0 + r));
-                return;
-            }
-        }
-    }
+    if (km_table_full(p)) return;
+    km_walk(p, code, brk, nr, [&](int r, int, int, u64 fw) {
+        const u64 key = km_canonical(fw, p.k);
+        u64 m;
+        const u64 w = km_filter_index(key, f.wmask, &m);
+        if ((f.twice[w] & m) != m) return true;                           // seen once
+        if (km_insert(p.keys, p.counts, p.mask, key, 1u)) return true;
+        atomicMin(p.status + ST_KMER, (u64)(row0 + r));
+        return false;
+    });
 }
 
 // h[min(count, 256)] += 1 for every occupied slot
@@ -339,10 +413,129 @@ __device__ __forceinline__ unsigned __int128 km_breaks(const KmerParams& p, cons
     return b;
 }
 
+// ---- the correction rule, one base at a time --------------------------------------------------------------------------------
+// What a thread holds while it judges the 16 bases of chunk ch of the row whose words start at e_row of code / brk.
+// Positions count from the first base of chunk ch - 2: base t of the chunk is position 32 + t, window j starts at position j.
+struct KmChunk {
+    const u32* code; const u32* brk; int e_row, ch;
+    u32 brk_own;                                     // brk[e_row + ch]
+    u32 ns;                                          // N rule: bit t, base t is an N the rule may fix (km_chunk_ns)
+    u64 V, S;                                        // bit j: window j is valid, is solid (km_window_bits)
+    bool have_words; unsigned __int128 xa, xb;       // the code words of chunks ch - 2 .. ch + 1 and ch .. ch + 3 (km_context)
+};
+
+// bit t: base t of the chunk `w` is an N ('N', code 4 of a 4-bit plane) inside the read and not the separator of two reads
+template <bool NIB, int FIXN>
+__device__ __forceinline__ u32 km_chunk_ns(const KmerParams& p, const u32 (&w)[4], u32 brk_own, int64_t row, int ch)
+{
+    u32 ns = 0;
+    #pragma unroll
+    for (int t = 0; t < 16; ++t) ns |= (km_chunk_base<NIB>(w, t) == (NIB ? 4u : (u32)'N') ? 1u : 0u) << t;
+    ns &= brk_own;
+    if (ns) {
+        const int L = (int)(p.meta[row] & 0xFFFFu), first = ch * 16;
+        ns &= L - first >= 16 ? 0xFFFFu : L > first ? (1u << (L - first)) - 1u : 0u;
+        const int sep = FIXN == KM_FIXN_PAIRS ? ((L - 1) >> 1) - first : -1;
+        if (sep >= 0 && sep < 16) ns &= ~(1u << sep);
+    }
+    return ns;
+}
+
+// the (solid << 16 | valid) words `sv` of chunks ch - 2 .. ch as two 48-bit masks
+__device__ __forceinline__ void km_window_bits(const u32* sv, int e_row, int ch, u64* V, u64* S)
+{
+    *V = 0; *S = 0;
+    for (int i = 0; i < 3; ++i) {
+        const int c = ch - 2 + i;
+        const u32 w = c >= 0 ? sv[e_row + c] : 0u;
+        *V |= (u64)(w & 0xFFFFu) << (16 * i);
+        *S |= (u64)(w >> 16) << (16 * i);
+    }
+}
+
+// xa, xb on first use: most chunks need neither
+__device__ __forceinline__ void km_context(const KmerParams& p, KmChunk& c)
+{
+    if (c.have_words) return;
+    u64 unused;
+    c.xa = km_words(p, c.code, c.brk, c.e_row, c.ch - 2, 4, &unused);
+    c.xb = km_words(p, c.code, c.brk, c.e_row, c.ch, 4, &unused);
+    c.have_words = true;
+}
+
+// forward code of window j with `x` XOR-ed into the base at position pp
+__device__ __forceinline__ u64 km_window_with(const KmerParams& p, const KmChunk& c, int j, int pp, u32 x)
+{
+    return (j < 32 ? km_window(c.xa, j, p.k) : km_window(c.xb, j - 32, p.k)) ^ ((u64)x << (2 * (p.k - 1 - (pp - j))));
+}
+
+// N rule: s[x] = the candidate windows of the N at base t -- it is their only break -- that letter x makes solid
+__device__ __forceinline__ void km_vote_n(const KmerParams& p, const KmChunk& c, int t, int (&s)[4])
+{
+    const u64 kmask = (1ull << p.k) - 1;
+    const unsigned __int128 B = km_breaks(p, c.brk, c.e_row, c.ch - 2, 5);   // bit i: the base at position i
+    const int pp = 32 + t;
+    for (int j = pp - p.k + 1; j <= pp; ++j) {
+        if (((u64)(B >> j) & kmask) != 1ull << (pp - j)) continue;
+        #pragma unroll
+        for (u32 x = 0; x < 4; ++x) s[x] += km_solid(p, km_window_with(p, c, j, pp, x)) ? 1 : 0;   // a break's code is 0
+    }
+}
+
+// substitution rule: s[alt] = the valid windows over base t (`windows`: V & cover) that letter alt in place of orig makes solid
+__device__ __forceinline__ void km_vote_subst(const KmerParams& p, const KmChunk& c, int t, u32 orig, u64 windows, int (&s)[4])
+{
+    for (u32 alt = 0; alt < 4; ++alt) {
+        if (alt == orig) continue;
+        for (u64 m = windows; m; m &= m - 1)
+            s[alt] += km_solid(p, km_window_with(p, c, __builtin_ctzll(m), 32 + t, orig ^ alt)) ? 1 : 0;
+    }
+}
+
+// the letter with the strictly largest score >= 1 (`skip` left out), -1 when there is none
+__device__ __forceinline__ int km_winner(const int (&s)[4], int skip)
+{
+    int best = -1, bs = 0; bool tie = false;
+    #pragma unroll
+    for (int x = 0; x < 4; ++x) {
+        if (x == skip) continue;
+        if (s[x] > bs) { bs = s[x]; best = x; tie = false; }
+        else if (s[x] == bs && bs > 0) tie = true;
+    }
+    return tie ? -1 : best;
+}
+
+// The rule for base t: the table's code 0..3 to write (a fixed N also stops being a break), or
+constexpr int KM_LEAVE = -1;                         // a break, a trusted base, an N no letter wins
+constexpr int KM_UNRESOLVED = -2;                    // an untrusted base no substitution wins
+
+template <int FIXN>
+__device__ __forceinline__ int km_decide(const KmerParams& p, KmChunk& c, int t)
+{
+    if constexpr (FIXN != KM_FIXN_OFF) {
+        if ((c.ns >> t) & 1u) {
+            int s[4] = {0, 0, 0, 0};
+            km_context(p, c);
+            km_vote_n(p, c, t, s);
+            const int best = km_winner(s, -1);
+            return best < 0 ? KM_LEAVE : best;
+        }
+    }
+    if ((c.brk_own >> t) & 1u) return KM_LEAVE;                           // a break: never changed
+    const u64 cover = ((1ull << p.k) - 1) << (32 + t - p.k + 1);
+    if ((c.S & cover) || !(c.V & cover)) return KM_LEAVE;                 // trusted
+    km_context(p, c);
+    const u32 orig = (c.code[c.e_row + c.ch] >> (30 - 2 * t)) & 3u;
+    int s[4] = {0, 0, 0, 0};
+    km_vote_subst(p, c, t, orig, c.V & cover, s);
+    const int best = km_winner(s, (int)orig);
+    return best < 0 ? KM_UNRESOLVED : best;
+}
+
 // the byte of base t of a chunk of the flag plane (all 0 before) becomes v: 1 error, 2 unresolved
 __device__ __forceinline__ void km_flag(u32 (&w)[4], int t, u32 v) { w[t >> 2] |= v << (8 * (t & 3)); }
 
-// km_correct's store stage: base t of the chunk `w` (4 words of characters, 2 of nibbles) takes the table's code `best`.
+// The store stage: base t of the chunk `w` (4 words of characters, 2 of nibbles) takes the table's code `best`.
 // FLAGS: `w` is the chunk of the flag plane instead, one byte a base, and the base's byte becomes 1.
 template <bool NIB, bool FLAGS>
 __device__ __forceinline__ void km_put(u32 (&w)[4], int t, u32 best)
@@ -359,162 +552,66 @@ __device__ __forceinline__ void km_put(u32 (&w)[4], int t, u32 best)
     }
 }
 
+// nchg[row] to KmerParams.changed / .unresolved.  SPLIT: changed bases in the low half, unresolved ones in the high half;
+// else the whole word counts changed bases (up to 65535: the high half is 0) and .unresolved is not looked at
+template <bool SPLIT>
+__device__ __forceinline__ void km_flush_counts(const KmerParams& p, int64_t row0, int nr, const u32* nchg)
+{
+    if (!p.changed && !(SPLIT && p.unresolved)) return;
+    __syncthreads();
+    for (int i = threadIdx.x; i < nr; i += KM_THREADS) {
+        if (p.changed) p.changed[row0 + i] = SPLIT ? nchg[i] & 0xFFFFu : nchg[i];
+        if (SPLIT && p.unresolved) p.unresolved[row0 + i] = nchg[i] >> 16;
+    }
+}
+
 template <bool NIB, int FIXN = KM_FIXN_OFF, bool FLAGS = false, bool UNRES = false>
 __global__ __launch_bounds__(KM_THREADS) void km_correct(KmerParams p)
 {
     static_assert(!FLAGS || (!NIB && FIXN == KM_FIXN_OFF), "the flag form: character rows, no N rule");
     static_assert(!UNRES || FLAGS, "unresolved bases are a value of the flag plane: the flag form only");
     extern __shared__ u32 km_lds[];
-    const int E = p.rows_per_wg * p.cpr;
-    u32* code = km_lds; u32* brk = km_lds + E; u32* sv = km_lds + 2 * E; u32* nchg = km_lds + 3 * E;
+    u32* code = km_lds_chunk(km_lds, p, 0); u32* brk = km_lds_chunk(km_lds, p, 1); u32* sv = km_lds_chunk(km_lds, p, 2);
+    u32* nchg = km_lds_row(km_lds, KM_LDS_CORRECT, p, 0);
     const int64_t row0 = (int64_t)blockIdx.x * p.rows_per_wg;
     for (int i = threadIdx.x; i < p.rows_per_wg; i += KM_THREADS) nchg[i] = 0;
     const int nr = km_load_chunks<NIB>(p, row0, code, brk);
     __syncthreads();
-    const int k = p.k;
-    const u64 kmask = (1ull << k) - 1;
     // pass 2: (solid << 16 | valid) of the 16 windows starting in every chunk
     for (int e = threadIdx.x; e < nr * p.cpr; e += KM_THREADS) {
         const int r = e / p.cpr, ch = e - r * p.cpr;
-        u64 b;
-        const unsigned __int128 x = km_words(p, code, brk, r * p.cpr, ch, 3, &b);
         u32 valid = 0, solid = 0;
-        for (int o = 0; o < 16; ++o) {
-            if ((b >> o) & kmask) continue;
+        km_chunk_windows(p, code, brk, r * p.cpr, ch, [&](int o, u64 f) {
             valid |= 1u << o;
-            if (km_solid(p, km_window(x, o, k))) solid |= 1u << o;
-        }
+            if (km_solid(p, f)) solid |= 1u << o;
+            return true;
+        });
         sv[e] = solid << 16 | valid;
     }
     __syncthreads();
-    // pass 3: trust, substitution, output
+    // pass 3: the rule for every base of the chunk as read; the decisions go into the chunk in registers
     for (int e = threadIdx.x; e < nr * p.cpr; e += KM_THREADS) {
         const int r = e / p.cpr, ch = e - r * p.cpr;
-        const int64_t row = row0 + r;
-        u64 V = 0, S = 0;                                                 // bit i: the window starting at base 16 (ch - 2) + i
-        for (int i = 0; i < 3; ++i) {
-            const int c = ch - 2 + i;
-            const u32 w = c >= 0 ? sv[r * p.cpr + c] : 0u;
-            V |= (u64)(w & 0xFFFFu) << (16 * i);
-            S |= (u64)(w >> 16) << (16 * i);
-        }
-        constexpr int CB = NIB ? 8 : 16;                                  // bytes of a chunk in the plane
-        const size_t at = (size_t)row * p.pitch + (size_t)ch * CB;
-        u32 w[4] = {0, 0, 0, 0};                                         // the chunk as read: 4 words of characters, 2 of nibbles
-        if constexpr (FLAGS) {                                           // ... or of the flag plane: all 0, nothing to read
-        } else if constexpr (NIB) {
-            const uint2 v = *reinterpret_cast<const uint2*>(p.seq + at);
-            w[0] = v.x; w[1] = v.y;
-        } else {
-            const uint4 v = *reinterpret_cast<const uint4*>(p.seq + at);
-            w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
-        }
-        const u32 brk_own = brk[e];
+        const size_t at = km_chunk_at<NIB>(p, row0 + r, ch);
+        u32 w[4];
+        km_read_chunk<NIB, FLAGS>(p.seq + at, w);
+        KmChunk c = {code, brk, r * p.cpr, ch, brk[e], 0, 0, 0, false, 0, 0};
+        km_window_bits(sv, c.e_row, ch, &c.V, &c.S);
+        if constexpr (FIXN != KM_FIXN_OFF) c.ns = km_chunk_ns<NIB, FIXN>(p, w, c.brk_own, row0 + r, ch);
         int changed = 0, unres = 0;
-        bool have_words = false;
-        unsigned __int128 xa = 0, xb = 0;                                // chunks ch - 2 .. ch + 1 and ch .. ch + 3
-        u32 ns = 0;                                                       // N rule: bit t, base t of the chunk is an N of the read
-        if constexpr (FIXN != KM_FIXN_OFF) {
-            #pragma unroll
-            for (int t = 0; t < 16; ++t) {
-                const bool n = NIB ? ((w[t >> 3] >> km_nib_shift(t & 7)) & 0xFu) == 4u : ((w[t >> 2] >> (8 * (t & 3))) & 0xFFu) == 'N';
-                ns |= (n ? 1u : 0u) << t;
-            }
-            ns &= brk_own;
-            if (ns) {                                                     // ... inside the read, and not the separator of two reads
-                const int L = (int)(p.meta[row] & 0xFFFFu), first = ch * 16;
-                ns &= L - first >= 16 ? 0xFFFFu : L > first ? (1u << (L - first)) - 1u : 0u;
-                const int sep = FIXN == KM_FIXN_PAIRS ? ((L - 1) >> 1) - first : -1;
-                if (sep >= 0 && sep < 16) ns &= ~(1u << sep);
-            }
-        }
         for (int t = 0; t < 16; ++t) {
-            if constexpr (FIXN != KM_FIXN_OFF) {
-                if ((ns >> t) & 1u) {
-                    if (!have_words) {
-                        u64 unused;
-                        xa = km_words(p, code, brk, r * p.cpr, ch - 2, 4, &unused);
-                        xb = km_words(p, code, brk, r * p.cpr, ch, 4, &unused);
-                        have_words = true;
-                    }
-                    const unsigned __int128 B = km_breaks(p, brk, r * p.cpr, ch - 2, 5);   // bit i: base 16 (ch - 2) + i
-                    const int pp = 32 + t;
-                    int s[4] = {0, 0, 0, 0};
-                    for (int j = pp - k + 1; j <= pp; ++j) {              // a candidate window: this N is its only break
-                        if (((u64)(B >> j) & kmask) != 1ull << (pp - j)) continue;
-                        const u64 f = j < 32 ? km_window(xa, j, k) : km_window(xb, j - 32, k);   // a break's code is 0
-                        #pragma unroll
-                        for (u32 x = 0; x < 4; ++x) s[x] += km_solid(p, f | (u64)x << (2 * (k - 1 - (pp - j)))) ? 1 : 0;
-                    }
-                    int best = -1, bs = 0; bool tie = false;
-                    #pragma unroll
-                    for (int x = 0; x < 4; ++x) {
-                        if (s[x] > bs) { bs = s[x]; best = x; tie = false; }
-                        else if (s[x] == bs && bs > 0) tie = true;
-                    }
-                    if (best < 0 || tie) continue;
-                    km_put<NIB, FLAGS>(w, t, (u32)best);
-                    ++changed;
-                    continue;
-                }
-            }
-            if ((brk_own >> t) & 1u) continue;                            // a break: never changed
-            const int pp = 32 + t;                                        // the base's index in the 48-bit window masks
-            const u64 cover = kmask << (pp - k + 1);
-            if ((S & cover) || !(V & cover)) continue;                    // trusted
-            if (!have_words) {
-                u64 unused;
-                xa = km_words(p, code, brk, r * p.cpr, ch - 2, 4, &unused);
-                xb = km_words(p, code, brk, r * p.cpr, ch, 4, &unused);
-                have_words = true;
-            }
-            const u32 orig = (code[e] >> (30 - 2 * t)) & 3u;
-            int s[4] = {0, 0, 0, 0};
-            for (u32 alt = 0; alt < 4; ++alt) {
-                if (alt == orig) continue;
-                for (u64 m = V & cover; m; m &= m - 1) {
-                    const int j = __builtin_ctzll(m);                     // a valid covering window
-                    const u64 f = (j < 32 ? km_window(xa, j, k) : km_window(xb, j - 32, k)) ^ ((u64)(orig ^ alt) << (2 * (k - 1 - (pp - j))));
-                    s[alt] += km_solid(p, f) ? 1 : 0;
-                }
-            }
-            int best = -1, bs = 0; bool tie = false;
-            for (int alt = 0; alt < 4; ++alt) {
-                if (alt == (int)orig) continue;
-                if (s[alt] > bs) { bs = s[alt]; best = alt; tie = false; }
-                else if (s[alt] == bs && bs > 0) tie = true;
-            }
-            if (best < 0 || tie) {                                        // untrusted, and no substitution wins: unresolved
-                if constexpr (UNRES) { km_flag(w, t, 2u); ++unres; }
-                continue;
-            }
-            km_put<NIB, FLAGS>(w, t, (u32)best);
-            ++changed;
+            const int d = km_decide<FIXN>(p, c, t);
+            if (d >= 0) { km_put<NIB, FLAGS>(w, t, (u32)d); ++changed; }
+            else if (UNRES && d == KM_UNRESOLVED) { km_flag(w, t, 2u); ++unres; }
         }
-        if constexpr (NIB) *reinterpret_cast<uint2*>(p.out + at) = make_uint2(w[0], w[1]);
-        else *reinterpret_cast<uint4*>(p.out + at) = make_uint4(w[0], w[1], w[2], w[3]);
-        if constexpr (UNRES) {
-            if (changed | unres) atomicAdd(&nchg[r], (u32)changed | (u32)unres << 16);
-        } else {
-            if (changed) atomicAdd(&nchg[r], (u32)changed);
-        }
+        km_write_chunk<NIB>(p.out + at, w);
+        if (changed | unres) atomicAdd(&nchg[r], (u32)changed | (u32)unres << 16);
     }
-    if constexpr (UNRES) {
-        if (p.changed || p.unresolved) {
-            __syncthreads();
-            for (int i = threadIdx.x; i < nr; i += KM_THREADS) {
-                if (p.changed) p.changed[row0 + i] = nchg[i] & 0xFFFFu;
-                if (p.unresolved) p.unresolved[row0 + i] = nchg[i] >> 16;
-            }
-        }
-    } else if (p.changed) {
-        __syncthreads();
-        for (int i = threadIdx.x; i < nr; i += KM_THREADS) p.changed[row0 + i] = nchg[i];
-    }
+    km_flush_counts<UNRES>(p, row0, nr, nchg);
 }
 
 // ---- several passes of the rule over rows held in LDS (kbbq correct --passes; include/kbbq_hip.h kbbq_kmer_*_passes*) ----------
-// r_0 is the row as read and r_p = C(r_(p-1)), C being km_correct's rule (with FIXN the N rule too) against the same table at
+// r_0 is the row as read and r_p = C(r_(p-1)), C being the rule above (with FIXN the N rule too) against the same table at
 // the same min_count: nothing is recounted.  km_correct's work split and pass 1; then the row lives in LDS until it is stored:
 //   code0 / brk0      the chunk as read (brk0's high half: the Ns of the read the N rule may fix -- inside the read, no separator)
 //   codeA/brkA, codeB/brkB   r_(p-1) and r_p: a pass reads one copy and writes the other, the copies swap after a barrier, so no
@@ -531,14 +628,18 @@ __global__ __launch_bounds__(KM_THREADS) void km_correct(KmerParams p)
 // The plane is read by km_load_chunks and, where a chunk's other bytes are needed (its Ns at the start with FIXN, the chunk
 // that is rewritten at the end unless FLAGS), the same 16 bytes once more, as km_correct reads them; nothing goes through
 // global memory between passes.
+// This kernel spells out the rule (stage D), its window loop (stage W), the counter flush and its LDS carving itself, statement
+// for statement what km_decide and the helpers above say: the forms that went through them compiled to other instructions and
+// those that were timed ran 0.8-1.2 % slower.  A change to the rule is made in km_decide AND in stage D here;
+// tests/test_gpu_kmer_passes.py holds the two to each other (passes = 1 against km_correct, P passes against P launches).
 constexpr int KM_MAX_PASSES = 8;
-constexpr int KM_PASS_WORDS = 8;      // LDS words per chunk of km_correct_passes; 2 more per row and 1 per workgroup
 
 template <bool NIB, int FIXN = KM_FIXN_OFF, bool FLAGS = false, bool UNRES = false>
 __global__ __launch_bounds__(KM_THREADS) void km_correct_passes(KmerParams p, int passes)
 {
     static_assert(!FLAGS || (!NIB && FIXN == KM_FIXN_OFF), "the flag form: character rows, no N rule");
     static_assert(!UNRES || FLAGS, "unresolved bases are a value of the flag plane: the flag form only");
+    static_assert(KM_LDS_PASSES.chunk == 8 && KM_LDS_PASSES.row == 2 && KM_LDS_PASSES.wg == 1, "the carving below");
     extern __shared__ u32 km_lds[];
     const int E = p.rows_per_wg * p.cpr;
     u32* code0 = km_lds; u32* brk0 = km_lds + E;
@@ -548,7 +649,6 @@ __global__ __launch_bounds__(KM_THREADS) void km_correct_passes(KmerParams p, in
     u32* nchg = km_lds + 8 * E;
     int* last = reinterpret_cast<int*>(nchg + p.rows_per_wg);
     int* wglast = last + p.rows_per_wg;
-    constexpr int CB = NIB ? 8 : 16;                                      // bytes of a chunk in the plane
     const int64_t row0 = (int64_t)blockIdx.x * p.rows_per_wg;
     for (int i = threadIdx.x; i < p.rows_per_wg; i += KM_THREADS) { nchg[i] = 0; last[i] = -1; }
     if (threadIdx.x == 0) *wglast = -1;
@@ -557,30 +657,9 @@ __global__ __launch_bounds__(KM_THREADS) void km_correct_passes(KmerParams p, in
         cc[e] = code0[e]; cb[e] = brk0[e]; mark[e] = 0;
         if constexpr (FIXN != KM_FIXN_OFF) {
             const int r = e / p.cpr, ch = e - r * p.cpr;
-            const int64_t row = row0 + r;
-            const size_t at = (size_t)row * p.pitch + (size_t)ch * CB;
-            u32 w[4] = {0, 0, 0, 0};
-            if constexpr (NIB) {
-                const uint2 v = *reinterpret_cast<const uint2*>(p.seq + at);
-                w[0] = v.x; w[1] = v.y;
-            } else {
-                const uint4 v = *reinterpret_cast<const uint4*>(p.seq + at);
-                w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
-            }
-            u32 ns = 0;
-            #pragma unroll
-            for (int t = 0; t < 16; ++t) {
-                const bool n = NIB ? ((w[t >> 3] >> km_nib_shift(t & 7)) & 0xFu) == 4u : ((w[t >> 2] >> (8 * (t & 3))) & 0xFFu) == 'N';
-                ns |= (n ? 1u : 0u) << t;
-            }
-            ns &= brk0[e];
-            if (ns) {
-                const int L = (int)(p.meta[row] & 0xFFFFu), first = ch * 16;
-                ns &= L - first >= 16 ? 0xFFFFu : L > first ? (1u << (L - first)) - 1u : 0u;
-                const int sep = FIXN == KM_FIXN_PAIRS ? ((L - 1) >> 1) - first : -1;
-                if (sep >= 0 && sep < 16) ns &= ~(1u << sep);
-            }
-            brk0[e] |= ns << 16;
+            u32 w[4];
+            km_read_chunk<NIB>(p.seq + km_chunk_at<NIB>(p, row0 + r, ch), w);
+            brk0[e] |= km_chunk_ns<NIB, FIXN>(p, w, brk0[e], row0 + r, ch) << 16;
         }
     }
     __syncthreads();
@@ -703,16 +782,9 @@ __global__ __launch_bounds__(KM_THREADS) void km_correct_passes(KmerParams p, in
     // store: km_put wherever r_P differs from r_0
     for (int e = threadIdx.x; e < nr * p.cpr; e += KM_THREADS) {
         const int r = e / p.cpr, ch = e - r * p.cpr;
-        const size_t at = (size_t)(row0 + r) * p.pitch + (size_t)ch * CB;
-        u32 w[4] = {0, 0, 0, 0};                                         // the chunk as read, or of the flag plane: all 0
-        if constexpr (FLAGS) {
-        } else if constexpr (NIB) {
-            const uint2 v = *reinterpret_cast<const uint2*>(p.seq + at);
-            w[0] = v.x; w[1] = v.y;
-        } else {
-            const uint4 v = *reinterpret_cast<const uint4*>(p.seq + at);
-            w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
-        }
+        const size_t at = km_chunk_at<NIB>(p, row0 + r, ch);
+        u32 w[4];                                                        // the chunk as read, or of the flag plane: all 0
+        km_read_chunk<NIB, FLAGS>(p.seq + at, w);
         const u32 code_end = cc[e];
         const u32 dcode = code0[e] ^ code_end, dbrk = (brk0[e] ^ cb[e]) & 0xFFFFu, un = UNRES ? mark[e] >> 16 : 0u;
         int changed = 0, unres = 0;
@@ -727,8 +799,7 @@ __global__ __launch_bounds__(KM_THREADS) void km_correct_passes(KmerParams p, in
                 }
             }
         }
-        if constexpr (NIB) *reinterpret_cast<uint2*>(p.out + at) = make_uint2(w[0], w[1]);
-        else *reinterpret_cast<uint4*>(p.out + at) = make_uint4(w[0], w[1], w[2], w[3]);
+        km_write_chunk<NIB>(p.out + at, w);
         if (changed | unres) atomicAdd(&nchg[r], (u32)changed | (u32)unres << 16);
     }
     if (p.changed || p.unresolved) {
@@ -831,19 +902,6 @@ __global__ __launch_bounds__(KM_THREADS) void km_merge(const u64* in_keys, const
     const int64_t stride = (int64_t)gridDim.x * KM_THREADS;
     for (int64_t i = (int64_t)blockIdx.x * KM_THREADS + threadIdx.x; i < n; i += stride) {
         if (__hip_atomic_load(status + ST_KMER, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != ~0ull) return;
-        const u64 key = in_keys[i];
-        const u32 c = in_counts[i];
-        u64 s = km_hash(key) & mask;
-        bool done = false;
-        for (int j = 0; j < KM_MAX_PROBES; ++j) {
-            u64 cur = km_load_key(keys + s);
-            if (cur == KM_EMPTY) {
-                cur = atomicCAS(keys + s, KM_EMPTY, key);
-                if (cur == KM_EMPTY) cur = key;
-            }
-            if (cur == key) { atomicAdd(counts + s, c); done = true; break; }
-            s = (s + 1) & mask;
-        }
-        if (!done) { atomicMin(status + ST_KMER, (u64)i); return; }
+        if (!km_insert(keys, counts, mask, in_keys[i], in_counts[i])) { atomicMin(status + ST_KMER, (u64)i); return; }
     }
 }

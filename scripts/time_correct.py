@@ -211,7 +211,8 @@ if args.fix_n:
     res['n_bases'] = int((seq[:, :L] == ord('N')).sum().item())
     res['fixed_n'] = int(((out_n != seq) & (seq == ord('N'))).sum().item())
     res['ms_correct_fix_n_all'] = [round(v, 3) for v in ms['correct_fix_n']]
-    assert torch.equal(out_n[seq != ord('N')], out[seq != ord('N')]), 'the N rule changed a base that is no N'
+    # (no boolean indexing: the planes have more than 2^31 elements)
+    assert torch.equal(torch.where(seq != ord('N'), out_n, out), out), 'the N rule changed a base that is no N'
 if args.flags:
     res['ms_flags_all'] = [round(v, 3) for v in ms['flags']]
     res['flags_kmers_per_s'] = windows / (res['ms_flags'] * 1e-3)

@@ -349,6 +349,38 @@ def test_four_bit_planes_two_passes():
         table.close()
 
 
+def test_four_bit_reads_fix_n_two_passes():
+    """One read to a row of 4-bit codes with the N rule at two passes, the one selection of (reader, N rule, one pass / several)
+    no other test reaches.  The hand-built rows with three Ns: one alone mid-read (pass 1 fixes it), one at a read's first base
+    beside errors, and one at base 2 of the read whose base 8 is substituted -- every window over that N holds base 8, so pass 1
+    corrects base 8 and leaves the N, and pass 2 fixes it."""
+    from kbbq import _device as dev
+    from kbbq import kmer
+    seq, meta, cases = PM.hand_rows(pitch=48)
+    seq = seq.copy()
+    late, alone = cases['two_pass'][0], cases['truth'][0]
+    seq[late, 2] = seq[alone, 20] = seq[cases['three_pass_end'][0], 0] = PM.NCH
+    steps = PM.trace(seq, meta, PM.HAND_K, PM.HAND_T, 2, fix_n=True)
+    truth = PM.hand_rows(pitch=48)[0][alone]
+    assert steps[0][0][alone, 20] == truth[20] and steps[0][0][late, 8] == truth[8]
+    assert steps[0][0][late, 2] == PM.NCH and steps[1][0][late, 2] == truth[2]
+    assert int(steps[0][1].sum()) < int(steps[1][1].sum())
+    laid = dev.lay_out(_batch(seq, meta), 1, pairs=False)
+    assert laid.layout_key() == 'reads_nib' and laid.n == seq.shape[0]
+    lens = _host(laid.meta[:laid.n]).view(np.uint32) & 0xFFFF
+    assert np.array_equal(lens, meta & 0xFFFF)           # one read group: the rows are the reads, in their order
+    inside = np.arange(seq.shape[1])[None, :] < lens.astype(np.int64)[:, None]
+    was = _host(laid.chars('seq')[:laid.n])[:, :seq.shape[1]]
+    table = kmer.count_batch(laid, k=PM.HAND_K)
+    try:
+        changed = kmer.correct_batch(table, laid, PM.HAND_T, fix_n=True, passes=2)
+        got = _host(laid.chars('cseq')[:laid.n])[:, :seq.shape[1]]
+        assert np.array_equal(got[inside], steps[1][0][inside]) and np.array_equal(got[~inside], was[~inside])
+        assert np.array_equal(_host(changed).astype(np.int64), steps[1][1])
+    finally:
+        table.close()
+
+
 def test_pair_rows_two_passes():
     """Two reads of 50 bases to a row of 4-bit codes (pitch 112) and of characters: each half of a row is the model's plane of
     the unpacked read, and a row's count is the sum of its two reads'."""
