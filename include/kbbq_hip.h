@@ -895,7 +895,19 @@ int kbbq_kmer_count_filtered(kbbq_ctx* ctx, kbbq_kmer_table* table, const kbbq_k
  * refusals).  On a 4-bit plane an N is code 4 inside the row's length, and a fixed one is stored as its letter's plane code.
  * With KBBQ_ROWS_PAIRS the base at (length - 1) / 2 of a row is the separator of its two reads (an 'N' / code 4 too): it is
  * never fixed, and since every window across it holds that break no N takes a letter from the other read.  The padding half
- * of a twin row of one read is Ns beside Ns and stays as it is.                                                             */
+ * of a twin row of one read is Ns beside Ns and stays as it is.
+ * kbbq_kmer_correct_rows_skip_dev (kbbq recalibrate -c --skip-unresolved): kbbq_kmer_correct_rows_passes_dev -- the same flags,
+ * opts (0 or KBBQ_KMER_FIX_N), passes (1..8), refusals and LDS limit, and bit for bit the same d_out and d_changed -- plus the
+ * rule's third outcome as a second QUALITY plane.  d_qual is the rows' quality plane as read and d_tally_qual the tally plane,
+ * both [nrows, pitch] characters (also beside a 4-bit sequence plane, whose row stride is pitch / 2) and 16-byte aligned.
+ * d_tally_qual receives d_qual with byte 0 at every unresolved base: an untrusted A/C/G/T base no substitution wins, with
+ * passes > 1 a base that ends as it was read and that the last evaluation of its row left unresolved (the 2s of the flag form).
+ * Every byte of every row is written, separator and padding as read (they are breaks, never unresolved); d_qual is not
+ * written.  kbbq_accumulate_rows_dev sends a base whose quality byte is below 33 + minscore to its trash row and looks at the
+ * base's own byte alone for that, so a tally with d_tally_qual in the place of d_qual leaves exactly the unresolved bases out,
+ * as an error and as an observation, and changes nothing for their neighbours.  d_unresolved (per row, may be NULL) receives
+ * their number.  KBBQ_E_ARG before anything is launched: NULL d_qual or d_tally_qual, d_tally_qual == d_qual, a plane that is
+ * not 16-byte aligned, KBBQ_KMER_FLAG_UNRESOLVED (the flag form's bit) or an unknown bit in opts.  nrows == 0 does nothing. */
 int kbbq_kmer_count_rows_dev(kbbq_ctx* ctx, kbbq_kmer_table* table, const uint8_t* d_seq, const uint32_t* d_meta, int64_t nrows,
                              int pitch, int flags);
 int kbbq_kmer_prefilter_rows_dev(kbbq_ctx* ctx, kbbq_kmer_filter* filter, int k, const uint8_t* d_seq, const uint32_t* d_meta,
@@ -910,6 +922,9 @@ int kbbq_kmer_correct_rows_ex_dev(kbbq_ctx* ctx, const kbbq_kmer_table* table, c
 int kbbq_kmer_correct_rows_passes_dev(kbbq_ctx* ctx, const kbbq_kmer_table* table, const uint8_t* d_seq, const uint32_t* d_meta,
                                       int64_t nrows, int pitch, int flags, int min_count, uint8_t* d_out, uint32_t* d_changed, int opts,
                                       int passes);
+int kbbq_kmer_correct_rows_skip_dev(kbbq_ctx* ctx, const kbbq_kmer_table* table, const uint8_t* d_seq, const uint32_t* d_meta,
+                                    int64_t nrows, int pitch, int flags, int min_count, uint8_t* d_out, uint32_t* d_changed, int opts,
+                                    int passes, const uint8_t* d_qual, uint8_t* d_tally_qual, uint32_t* d_unresolved);
 
 #ifdef __cplusplus
 }

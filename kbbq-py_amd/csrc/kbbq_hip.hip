@@ -2218,8 +2218,11 @@ static int kmer_geometry(kbbq_ctx* c, const char* who, const kbbq_kmer_table* t,
 // the instantiation of a window kernel for the rows' reader
 #define KM_READER(K, nib) ((nib) ? (const void*)K<true> : (const void*)K<false>)
 
-// launches of at most 2^20 workgroups.  `extra`: the kernel's second parameter (KmerFilterParams, passes), if it has one
-static int kmer_launches(kbbq_ctx* c, const KmerParams& p, const void* kernel, size_t lds, const void* extra)
+// launches of at most 2^20 workgroups.  The kernel's parameters after its KmerParams, in their order: `extra` (KmerFilterParams,
+// passes) when the kernel has one, then `tally` -- both correction kernels end in a KmerTally, a copy of which moves with the
+// rows of each launch; every other kernel gets nullptr
+static int kmer_launches(kbbq_ctx* c, const KmerParams& p, const void* kernel, size_t lds, const void* extra,
+                         const KmerTally* tally = nullptr)
 {
     HIPCHK(hipSetDevice(c->device));
     const int64_t per = ((int64_t)1 << 20) * p.rows_per_wg;
@@ -2230,8 +2233,12 @@ static int kmer_launches(kbbq_ctx* c, const KmerParams& p, const void* kernel, s
         if (p.out) q.out = p.out + (size_t)lo * p.pitch;
         if (p.changed) q.changed = p.changed + lo;
         if (p.unresolved) q.unresolved = p.unresolved + lo;
-        void* args[] = {&q, const_cast<void*>(extra)};  // hipLaunchKernel reads one entry per kernel parameter: `extra` goes unread by
-                                                        // a one-parameter kernel and must be set for a two-parameter one
+        KmerTally ty = {nullptr, nullptr};
+        if (tally && tally->qual) ty = {tally->qual + (size_t)lo * p.cpr * 16, tally->out + (size_t)lo * p.cpr * 16};
+        void* args[3] = {&q, nullptr, nullptr};         // hipLaunchKernel reads one entry per kernel parameter
+        int na = 1;
+        if (extra) args[na++] = const_cast<void*>(extra);
+        if (tally) args[na++] = &ty;
         HIPCHK(hipLaunchKernel(kernel, dim3((unsigned)((m + p.rows_per_wg - 1) / p.rows_per_wg)), dim3(KM_THREADS), args, lds, c->stream));
     }
     return KBBQ_OK;
@@ -2284,23 +2291,28 @@ int kbbq_kmer_histogram_dev(kbbq_ctx* c, const kbbq_kmer_table* t, uint64_t* d_h
 
 // Which of the correction kernels a call wants.  passes: 1 km_correct, 2..KM_MAX_PASSES km_correct_passes.
 // pairs (KBBQ_ROWS_PAIRS) matter to the N rule alone: the separator of two reads is no N.
-struct KmerForm { bool nib; int fixn; bool flags, unres; int passes; };
+// tally: the corrected form that also writes the tally plane (kbbq_kmer_correct_rows_skip_dev)
+struct KmerForm { bool nib; int fixn; bool flags, unres; int passes; bool tally = false; };
 
 static KmerForm kmer_form_rows(bool nib, bool pairs, int opts, int passes)
 {
     return {nib, !(opts & KBBQ_KMER_FIX_N) ? KM_FIXN_OFF : pairs ? KM_FIXN_PAIRS : KM_FIXN_READS, false, false, passes};
 }
 
-// ... and the kernel of a form: [several passes][reader x KM_FIXN_*, the flag form, the flag form with unresolved bases]
+// ... and the kernel of a form: [several passes][reader x KM_FIXN_*, the flag form, the flag form with unresolved bases,
+// reader x KM_FIXN_* with the tally plane]
 #define KM_FORMS(K) {(const void*)K<false, KM_FIXN_OFF>, (const void*)K<false, KM_FIXN_READS>, (const void*)K<false, KM_FIXN_PAIRS>, \
                      (const void*)K<true, KM_FIXN_OFF>, (const void*)K<true, KM_FIXN_READS>, (const void*)K<true, KM_FIXN_PAIRS>,    \
-                     (const void*)K<false, KM_FIXN_OFF, true>, (const void*)K<false, KM_FIXN_OFF, true, true>}
-static const void* const KM_CORRECT[2][8] = {KM_FORMS(km_correct), KM_FORMS(km_correct_passes)};
+                     (const void*)K<false, KM_FIXN_OFF, true>, (const void*)K<false, KM_FIXN_OFF, true, true>,                       \
+                     (const void*)K<false, KM_FIXN_OFF, false, false, true>, (const void*)K<false, KM_FIXN_READS, false, false, true>, \
+                     (const void*)K<false, KM_FIXN_PAIRS, false, false, true>, (const void*)K<true, KM_FIXN_OFF, false, false, true>,  \
+                     (const void*)K<true, KM_FIXN_READS, false, false, true>, (const void*)K<true, KM_FIXN_PAIRS, false, false, true>}
+static const void* const KM_CORRECT[2][14] = {KM_FORMS(km_correct), KM_FORMS(km_correct_passes)};
 
 static const void* kmer_correct_kernel(const KmerForm& f, KmLds* l)
 {
     *l = f.passes > 1 ? KM_LDS_PASSES : KM_LDS_CORRECT;
-    return KM_CORRECT[f.passes > 1][f.flags ? 6 + (f.unres ? 1 : 0) : (f.nib ? 3 : 0) + f.fixn];
+    return KM_CORRECT[f.passes > 1][f.flags ? 6 + (f.unres ? 1 : 0) : (f.tally ? 8 : 0) + (f.nib ? 3 : 0) + f.fixn];
 }
 
 // the `opts` word of the kbbq_kmer_correct*_ex calls (not the KBBQ_ROWS_* flags): checked before anything is launched
@@ -2317,11 +2329,12 @@ static int kmer_passes_ok(const char* who, int passes)
     return KBBQ_OK;
 }
 
-// d_out: the corrected plane, with f.flags the flag plane; d_unresolved (may be NULL): the per-row count of 2s of the flag form,
-// zeroed here when the form writes none.  The caller has checked its opts and passes.
+// d_out: the corrected plane, with f.flags the flag plane; d_unresolved (may be NULL): the per-row count of 2s of the flag form
+// or of the zeros f.tally writes, zeroed here when the form writes none.  ty: f.tally's planes, checked by the caller.
+// The caller has checked its opts and passes.
 static int kmer_correct_rows(kbbq_ctx* c, const char* who, const kbbq_kmer_table* t, const uint8_t* d_seq, const uint32_t* d_meta,
                              int64_t n, int pitch, int min_count, uint8_t* d_out, uint32_t* d_changed, uint32_t* d_unresolved,
-                             const KmerForm& f)
+                             const KmerForm& f, KmerTally ty = {nullptr, nullptr})
 {
     KmerParams p; size_t lds = 0; KmLds l;
     const void* kernel = kmer_correct_kernel(f, &l);
@@ -2333,11 +2346,12 @@ static int kmer_correct_rows(kbbq_ctx* c, const char* who, const kbbq_kmer_table
     if (n == 0) return KBBQ_OK;
     HIPCHK(hipSetDevice(c->device));                    // for the memset and the attribute; kmer_launches sets it for the other paths
     p.min_count = (u32)min_count; p.out = d_out; p.changed = d_changed;
-    if (f.unres) p.unresolved = d_unresolved;
+    if (f.unres || f.tally) p.unresolved = d_unresolved;
     else if (d_unresolved) HIPCHK(hipMemsetAsync(d_unresolved, 0, (size_t)n * 4, c->stream));     // no byte is 2 without the option
     if (f.passes > 1 && lds > 64 * 1024)                // beyond what a kernel may take without asking
         HIPCHK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, c->lds_bytes));
-    return kmer_launches(c, p, kernel, lds, &f.passes);
+    // km_correct(KmerParams, KmerTally), km_correct_passes(KmerParams, int passes, KmerTally): this is their one launch site
+    return kmer_launches(c, p, kernel, lds, f.passes > 1 ? &f.passes : nullptr, &ty);
 }
 
 // character rows, one read a row: opts and passes are checked here
@@ -2434,6 +2448,28 @@ int kbbq_kmer_correct_rows_dev(kbbq_ctx* c, const kbbq_kmer_table* t, const uint
                                int pitch, int flags, int min_count, uint8_t* d_out, uint32_t* d_changed)
 {
     return kmer_correct_rows_flags(c, "kbbq_kmer_correct_rows_dev", t, d_seq, d_meta, nrows, pitch, flags, min_count, d_out, d_changed, 0, 1);
+}
+
+// kbbq_kmer_correct_rows_passes_dev and the tally plane beside the corrected one
+int kbbq_kmer_correct_rows_skip_dev(kbbq_ctx* c, const kbbq_kmer_table* t, const uint8_t* d_seq, const uint32_t* d_meta, int64_t nrows,
+                                    int pitch, int flags, int min_count, uint8_t* d_out, uint32_t* d_changed, int opts, int passes,
+                                    const uint8_t* d_qual, uint8_t* d_tally_qual, uint32_t* d_unresolved)
+{
+    const char* who = "kbbq_kmer_correct_rows_skip_dev";
+    int rc = kmer_passes_ok(who, passes);
+    if (!rc && (opts & KBBQ_KMER_FLAG_UNRESOLVED))
+        rc = fail(KBBQ_E_ARG, "%s: opts 0x%x: KBBQ_KMER_FLAG_UNRESOLVED (%d) is the flag form's; here unresolved bases go to d_tally_qual",
+                  who, opts, KBBQ_KMER_FLAG_UNRESOLVED);
+    if (!rc) rc = kmer_correct_opts(who, opts);
+    bool nib = false;
+    if (!rc) rc = kmer_row_flags(who, flags, &nib);
+    if (rc) return rc;
+    if (!d_qual || !d_tally_qual) return fail(KBBQ_E_ARG, "%s: d_qual or d_tally_qual is NULL", who);
+    if (d_tally_qual == d_qual) return fail(KBBQ_E_ARG, "%s: d_tally_qual is d_qual: the qualities as read must stay", who);
+    if (((uintptr_t)d_qual | (uintptr_t)d_tally_qual) & 15) return fail(KBBQ_E_ARG, "%s: d_qual or d_tally_qual not 16-byte aligned", who);
+    KmerForm f = kmer_form_rows(nib, (flags & KBBQ_ROWS_PAIRS) != 0, opts, passes);
+    f.tally = true;
+    return kmer_correct_rows(c, who, t, d_seq, d_meta, nrows, pitch, min_count, d_out, d_changed, d_unresolved, f, {d_qual, d_tally_qual});
 }
 
 int kbbq_kmer_table_clear_dev(kbbq_ctx* c, kbbq_kmer_table* t)

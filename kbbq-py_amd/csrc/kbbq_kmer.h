@@ -57,6 +57,12 @@
 //                      tally.  A byte is 0, 1 or 2, never 3.  The row's counter in LDS holds the 1s in its low and the 2s in its
 //                      high 16 bits (a row has at most 65535 bases, and a base is one or the other); KmerParams.unresolved
 //                      receives the high half.
+//   ... TALLY          (kbbq_kmer_correct_rows_skip_dev) the corrected form's own third outcome: the corrected plane is what it is
+//                      without, and KM_UNRESOLVED goes to a second QUALITY plane, the tally plane (KmerTally): the chunk's 16
+//                      quality bytes as read with 0 at every unresolved base (km_tally_chunk).  K1 sends a base of quality byte
+//                      < 33 + minscore to its trash row and looks at the base's own byte alone, so the tally leaves out exactly
+//                      those bases and K1 needs no flag plane.  Quality planes are characters, [nrows, 16 cpr], also beside a
+//                      4-bit sequence plane.  Every byte of every row is written; the counter splits as with UNRES.
 //   km_correct_passes  keeps the row in LDS and applies the rule to its own output up to `passes` times: the decisions of a
 //                      pass go to a second copy of the row's code words and break masks.  See the comment at the kernel.
 //
@@ -91,8 +97,12 @@ struct KmerParams {
     u32 min_count;                    // correct: a k-mer is solid when its count is >= min_count
     uint8_t* out; u32* changed;       // correct: the corrected plane (flag form: the flag plane); per-row count of changed bases (may be NULL)
     u64* status;
-    u32* unresolved;                  // flag form with UNRES: per-row count of bases set to 2 (may be NULL)
+    u32* unresolved;                  // UNRES / TALLY: per-row count of unresolved bases (may be NULL)
 };
+
+// the correction kernels' last parameter, read by the TALLY forms alone: the quality plane as read and the tally plane, both
+// [nrows, 16 cpr] characters and 16-byte aligned
+struct KmerTally { const uint8_t* qual; uint8_t* out; };
 
 __host__ __device__ __forceinline__ u64 km_hash(u64 x)
 {
@@ -552,6 +562,22 @@ __device__ __forceinline__ void km_put(u32 (&w)[4], int t, u32 best)
     }
 }
 
+// TALLY: the 16 quality bytes of a chunk go to the tally plane, 0 where `un` (bit t: base t is unresolved) says so.  seq_at: the
+// chunk's km_chunk_at in the sequence plane; a quality plane has 16 bytes a chunk, so the chunk lies at twice that beside nibbles
+template <bool NIB>
+__device__ __forceinline__ void km_tally_chunk(const KmerTally& q, size_t seq_at, u32 un)
+{
+    const size_t at = NIB ? 2 * seq_at : seq_at;
+    const uint4 v = *reinterpret_cast<const uint4*>(q.qual + at);
+    u32 w[4] = {v.x, v.y, v.z, v.w};
+    #pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const u32 m = (un >> (4 * i)) & 0xFu;                             // bit j -> byte j: 0xFF where the base is unresolved
+        w[i] &= ~((((m & 1u) | (m & 2u) << 7 | (m & 4u) << 14 | (m & 8u) << 21)) * 0xFFu);
+    }
+    *reinterpret_cast<uint4*>(q.out + at) = make_uint4(w[0], w[1], w[2], w[3]);
+}
+
 // nchg[row] to KmerParams.changed / .unresolved.  SPLIT: changed bases in the low half, unresolved ones in the high half;
 // else the whole word counts changed bases (up to 65535: the high half is 0) and .unresolved is not looked at
 template <bool SPLIT>
@@ -565,11 +591,12 @@ __device__ __forceinline__ void km_flush_counts(const KmerParams& p, int64_t row
     }
 }
 
-template <bool NIB, int FIXN = KM_FIXN_OFF, bool FLAGS = false, bool UNRES = false>
-__global__ __launch_bounds__(KM_THREADS) void km_correct(KmerParams p)
+template <bool NIB, int FIXN = KM_FIXN_OFF, bool FLAGS = false, bool UNRES = false, bool TALLY = false>
+__global__ __launch_bounds__(KM_THREADS) void km_correct(KmerParams p, KmerTally q)
 {
     static_assert(!FLAGS || (!NIB && FIXN == KM_FIXN_OFF), "the flag form: character rows, no N rule");
     static_assert(!UNRES || FLAGS, "unresolved bases are a value of the flag plane: the flag form only");
+    static_assert(!TALLY || !FLAGS, "the tally plane goes with the corrected plane: the corrected form only");
     extern __shared__ u32 km_lds[];
     u32* code = km_lds_chunk(km_lds, p, 0); u32* brk = km_lds_chunk(km_lds, p, 1); u32* sv = km_lds_chunk(km_lds, p, 2);
     u32* nchg = km_lds_row(km_lds, KM_LDS_CORRECT, p, 0);
@@ -599,15 +626,18 @@ __global__ __launch_bounds__(KM_THREADS) void km_correct(KmerParams p)
         km_window_bits(sv, c.e_row, ch, &c.V, &c.S);
         if constexpr (FIXN != KM_FIXN_OFF) c.ns = km_chunk_ns<NIB, FIXN>(p, w, c.brk_own, row0 + r, ch);
         int changed = 0, unres = 0;
+        u32 un = 0;                                                       // TALLY: bit t, base t is unresolved
         for (int t = 0; t < 16; ++t) {
             const int d = km_decide<FIXN>(p, c, t);
             if (d >= 0) { km_put<NIB, FLAGS>(w, t, (u32)d); ++changed; }
             else if (UNRES && d == KM_UNRESOLVED) { km_flag(w, t, 2u); ++unres; }
+            else if (TALLY && d == KM_UNRESOLVED) un |= 1u << t;
         }
         km_write_chunk<NIB>(p.out + at, w);
+        if constexpr (TALLY) { km_tally_chunk<NIB>(q, at, un); unres = __popc(un); }
         if (changed | unres) atomicAdd(&nchg[r], (u32)changed | (u32)unres << 16);
     }
-    km_flush_counts<UNRES>(p, row0, nr, nchg);
+    km_flush_counts<UNRES || TALLY>(p, row0, nr, nchg);
 }
 
 // ---- several passes of the rule over rows held in LDS (kbbq correct --passes; include/kbbq_hip.h kbbq_kmer_*_passes*) ----------
@@ -624,7 +654,8 @@ __global__ __launch_bounds__(KM_THREADS) void km_correct(KmerParams p)
 // (both copies hold it then), and the workgroup leaves the loop after a pass in which none of its rows changed: every thread
 // reads that from wglast after the barrier, so the trip count is uniform and every __syncthreads() is reached by all threads.
 // The store stage writes km_put's form wherever the final copy differs from code0 / brk0, and with UNRES 2 where it does not
-// and the row's last pass left the base unresolved; the per-row counts are those of the final plane, not sums over passes.
+// and the row's last pass left the base unresolved (TALLY: those bases are the zeros of the tally plane instead, km_correct's
+// TALLY); the per-row counts are those of the final plane, not sums over passes.
 // The plane is read by km_load_chunks and, where a chunk's other bytes are needed (its Ns at the start with FIXN, the chunk
 // that is rewritten at the end unless FLAGS), the same 16 bytes once more, as km_correct reads them; nothing goes through
 // global memory between passes.
@@ -634,11 +665,12 @@ __global__ __launch_bounds__(KM_THREADS) void km_correct(KmerParams p)
 // tests/test_gpu_kmer_passes.py holds the two to each other (passes = 1 against km_correct, P passes against P launches).
 constexpr int KM_MAX_PASSES = 8;
 
-template <bool NIB, int FIXN = KM_FIXN_OFF, bool FLAGS = false, bool UNRES = false>
-__global__ __launch_bounds__(KM_THREADS) void km_correct_passes(KmerParams p, int passes)
+template <bool NIB, int FIXN = KM_FIXN_OFF, bool FLAGS = false, bool UNRES = false, bool TALLY = false>
+__global__ __launch_bounds__(KM_THREADS) void km_correct_passes(KmerParams p, int passes, KmerTally q)
 {
     static_assert(!FLAGS || (!NIB && FIXN == KM_FIXN_OFF), "the flag form: character rows, no N rule");
     static_assert(!UNRES || FLAGS, "unresolved bases are a value of the flag plane: the flag form only");
+    static_assert(!TALLY || !FLAGS, "the tally plane goes with the corrected plane: the corrected form only");
     static_assert(KM_LDS_PASSES.chunk == 8 && KM_LDS_PASSES.row == 2 && KM_LDS_PASSES.wg == 1, "the carving below");
     extern __shared__ u32 km_lds[];
     const int E = p.rows_per_wg * p.cpr;
@@ -766,7 +798,7 @@ __global__ __launch_bounds__(KM_THREADS) void km_correct_passes(KmerParams p, in
                     else if (s[alt] == bs && bs > 0) tie = true;
                 }
                 if (best < 0 || tie) {                                    // untrusted, and no substitution wins: unresolved
-                    if constexpr (UNRES) unres |= 1u << t;
+                    if constexpr (UNRES || TALLY) unres |= 1u << t;
                     continue;
                 }
                 code_new ^= (orig ^ (u32)best) << (30 - 2 * t);
@@ -786,20 +818,23 @@ __global__ __launch_bounds__(KM_THREADS) void km_correct_passes(KmerParams p, in
         u32 w[4];                                                        // the chunk as read, or of the flag plane: all 0
         km_read_chunk<NIB, FLAGS>(p.seq + at, w);
         const u32 code_end = cc[e];
-        const u32 dcode = code0[e] ^ code_end, dbrk = (brk0[e] ^ cb[e]) & 0xFFFFu, un = UNRES ? mark[e] >> 16 : 0u;
+        const u32 dcode = code0[e] ^ code_end, dbrk = (brk0[e] ^ cb[e]) & 0xFFFFu, un = UNRES || TALLY ? mark[e] >> 16 : 0u;
         int changed = 0, unres = 0;
+        u32 left = 0;                                                     // TALLY: bit t, base t is as read and unresolved
         if (dcode | dbrk | un) {
             for (int t = 0; t < 16; ++t) {
                 if (((dcode >> (30 - 2 * t)) & 3u) | ((dbrk >> t) & 1u)) {
                     km_put<NIB, FLAGS>(w, t, (code_end >> (30 - 2 * t)) & 3u);
                     ++changed;
                 } else if ((un >> t) & 1u) {
-                    km_flag(w, t, 2u);
+                    if constexpr (TALLY) left |= 1u << t;
+                    else km_flag(w, t, 2u);
                     ++unres;
                 }
             }
         }
         km_write_chunk<NIB>(p.out + at, w);
+        if constexpr (TALLY) km_tally_chunk<NIB>(q, at, left);
         if (changed | unres) atomicAdd(&nchg[r], (u32)changed | (u32)unres << 16);
     }
     if (p.changed || p.unresolved) {

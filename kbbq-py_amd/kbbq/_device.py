@@ -221,6 +221,7 @@ class ReadBatch:
     nib = False          # seq / cseq hold one code nibble per base (include/kbbq_hip.h KBBQ_ROWS_NIBBLES)
     seg = None           # rows grouped by read group: int64 [R + 1] on the device
     perm = None          # ... and row i of this batch is row perm[i] of the batch it was made from
+    tally_qual = None    # kmer.correct_batch(skip_unresolved=True): `qual` with byte 0 at every unresolved base, [rows, pitch]
 
     def __init__(self, n, pitch, with_corrected=True, device=None, nib=False):
         torch = _torch()
@@ -319,6 +320,7 @@ class PairBatch:
     nib = False
     seg = None
     perm = None
+    tally_qual = None    # as ReadBatch's
     twins = False        # both reads of a row are first in pair: single-end input packed two to a row (KBBQ_ROWS_TWINS)
 
     def __init__(self, npairs, S, with_corrected=True, device=None, nib=False):

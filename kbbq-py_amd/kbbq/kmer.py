@@ -514,11 +514,15 @@ def count_batch(batch, k=31, table=None, slots=None, filter=None):
     return table
 
 
-def correct_batch(table, batch, min_count, fix_n=False, passes=1):
+def correct_batch(table, batch, min_count, fix_n=False, passes=1, skip_unresolved=False):
     """Correct the rows of a device batch against a counted table into batch.cseq (allocated here when the batch was made
     without one) in the batch's own layout: K1 takes it as it is.  Returns `changed`, the changed bases per ROW as an int32
     device array (a row of two reads counts both).  fix_n: the N rule, in every layout (a fixed N of a 4-bit plane is its
-    letter's code; the separator of a row of two reads is no N).  passes: as correct_with's, in every layout."""
+    letter's code; the separator of a row of two reads is no N).  passes: as correct_with's, in every layout.
+    skip_unresolved (kbbq_kmer_correct_rows_skip_dev): the batch also gets batch.tally_qual, its quality plane with byte 0 at
+    every unresolved base (untrusted, and no substitution wins) -- K1 with that plane in the place of batch.qual tallies those
+    bases neither as errors nor as observations -- and the return is (changed, unresolved), both per row; batch.cseq and
+    `changed` are what they are without."""
     from . import _device as dev
     passes = check_passes(passes)
     T = dev._torch()
@@ -527,6 +531,14 @@ def correct_batch(table, batch, min_count, fix_n=False, passes=1):
     seq, meta, n, pitch, flags = _batch_rows(batch)
     changed = T.empty((max(n, 1),), dtype=T.int32, device=batch.seq.device)
     ctx = table.ctx
+    if skip_unresolved:
+        batch.tally_qual = T.empty_like(batch.qual)
+        unresolved = T.empty((max(n, 1),), dtype=T.int32, device=batch.seq.device)
+        N.check(N.load().kbbq_kmer_correct_rows_skip_dev(ctx.handle, table.handle, seq, meta, n, pitch, flags, int(min_count),
+                                                         N.ptr(batch.cseq), N.ptr(changed), N.KMER_FIX_N if fix_n else 0, passes,
+                                                         N.ptr(batch.qual), N.ptr(batch.tally_qual), N.ptr(unresolved)))
+        ctx.status()
+        return changed[:n], unresolved[:n]
     if passes > 1:
         N.check(N.load().kbbq_kmer_correct_rows_passes_dev(ctx.handle, table.handle, seq, meta, n, pitch, flags, int(min_count),
                                                            N.ptr(batch.cseq), N.ptr(changed), N.KMER_FIX_N if fix_n else 0, passes))

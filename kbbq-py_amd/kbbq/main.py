@@ -43,6 +43,8 @@ def recalibrate(args):
             kopts['fix_n'] = True
         if args.passes is not None:
             kopts['passes'] = args.passes
+        if args.skip_unresolved:
+            kopts['skip_unresolved'] = True
         # every rank of a launcher refuses here, before it joins the process group
         _recal.check_corrected(args.correct, args.gatkreport, kopts['k'], kopts['min_count'], kopts['prefilter'], kopts['filter_bits'])
     world, _ = parallel.init_from_env()          # one process per GPU under torch.distributed.run; no-op otherwise
@@ -61,8 +63,10 @@ def recalibrate(args):
         with stage('[recalibrate_corrected, wall]'):
             info = _recal.recalibrate_corrected(args.correct, infer_rg=args.infer_rg, gatkreport=args.gatkreport, output=args.output,
                                                 **kopts)
-        sys.stderr.write('kbbq recalibrate: k=%d min_count=%d reads=%d changed_bases=%d%s%s%s\n'
-                         % (info['k'], info['min_count'], info['reads'], info['changed_bases'], ' fix_n=1' if kopts.get('fix_n') else '',
+        sys.stderr.write('kbbq recalibrate: k=%d min_count=%d reads=%d changed_bases=%d%s%s%s%s\n'
+                         % (info['k'], info['min_count'], info['reads'], info['changed_bases'],
+                            ' skipped_bases=%d' % info['skipped_bases'] if kopts.get('skip_unresolved') else '',
+                            ' fix_n=1' if kopts.get('fix_n') else '',
                             ' passes=%d' % kopts['passes'] if kopts.get('passes', 1) > 1 else '',
                             ' prefilter=1 admitted=%d slots=%d' % (info['admitted'], info['slots']) if kopts['prefilter'] else ''))
         return
@@ -168,6 +172,10 @@ def main(argv=None):
                     help='with -c: give every N the letter that makes the most of the k-mers it alone breaks solid (as `kbbq '
                          'correct --fix-n`)')
     rp.add_argument('--passes', type=_passes, default=None, metavar='P', help=_PASSES_HELP % 'with -c')
+    rp.add_argument('--skip-unresolved', action='store_true',
+                    help='with -c: leave a base out of the tally (neither error nor observation) when the k-mers contradict it but '
+                         'name no replacement -- two errors within k bases, thin coverage, contamination -- instead of counting '
+                         'it as correct (as `kbbq bqsr --kmers --skip-unresolved`)')
     rp.add_argument('-u', '--use-oq', action='store_true',
                     help='Use the OQ tag for quality scores (BAM input only).')
     rp.add_argument('-s', '--set-oq', action='store_true',
@@ -282,7 +290,8 @@ def main(argv=None):
     if args.command is recalibrate and args.correct is None:
         given = [flag for flag, v in (('-k/--kmer', args.kmer), ('--min-count', args.min_count), ('--slots', args.slots),
                                       ('--prefilter', args.prefilter or None), ('--filter-bits', args.filter_bits),
-                                      ('--fix-n', args.fix_n or None), ('--passes', args.passes)) if v is not None]
+                                      ('--fix-n', args.fix_n or None), ('--passes', args.passes),
+                                      ('--skip-unresolved', args.skip_unresolved or None)) if v is not None]
         if given:
             rp.error('%s: only with -c/--correct' % ', '.join(given))
     if args.command is benchmark:

@@ -392,7 +392,7 @@ def check_corrected(path, gatkreport=None, k=31, min_count=None, prefilter=False
 
 
 def recalibrate_corrected(path, infer_rg=False, gatkreport=None, output=None, k=31, min_count=None, slots=None, prefilter=False,
-                          filter_bits=4, fix_n=False, passes=1):
+                          filter_bits=4, fix_n=False, passes=1, skip_unresolved=False):
     """`kbbq correct` and `kbbq recalibrate -f reads corrected` in one run over ONE file: the reads go to the device once, in
     the layout pass 2 uses (fastx.pack_single), their k-mers are counted and the reads corrected where they lie
     (kmer.count_batch / correct_batch: the corrected plane is each band's cseq), and the tally, the solve, the apply and the
@@ -401,6 +401,13 @@ def recalibrate_corrected(path, infer_rg=False, gatkreport=None, output=None, k=
     admitted with the prefilter) and fix_n.  fix_n: the N rule of `kbbq correct --fix-n` in every band's own layout -- a fixed N
     reaches K1 as the difference from the original's N it is in the two-file form.  gatkreport: the model of the tally is saved there; an existing report is refused.
     passes: `kbbq correct --passes P` in every band's own layout (kmer.correct_batch); info carries it.
+    skip_unresolved: a base the k-mers contradict without naming a replacement (untrusted, and no substitution wins) is left out of
+    the tally, neither error nor observation, instead of counting as correct.  Every band gets a tally plane beside its corrected
+    plane -- its qualities with byte 0 at those bases (kbbq_kmer_correct_rows_skip_dev) -- which K1 reads in the place of the
+    qualities; K1 drops a base of quality below minscore by the base's own byte, so nothing changes for the neighbours.  The
+    solve, K2 and the writer see the qualities as read; the planes (one n x pitch per band) are released before the apply.
+    info['skipped_bases']: the unresolved bases of all reads.  The output is that of `recalibrate -f reads corrected` with the
+    model tallied from a reads file whose unresolved bases have quality '!'.
     One process, mapped inputs, reads that fit the device budget: anything else raises ValueError naming the two commands."""
     from . import kmer
     passes = kmer.check_passes(passes)
@@ -408,7 +415,7 @@ def recalibrate_corrected(path, infer_rg=False, gatkreport=None, output=None, k=
     done_with = []
     try:
         return _recalibrate_corrected(path, infer_rg, gatkreport, output, int(k), min_count, slots, prefilter, filter_bits, done_with,
-                                      bool(fix_n), passes)
+                                      bool(fix_n), passes, bool(skip_unresolved))
     finally:
         for reader in done_with:
             fastx.close_later(reader)
@@ -420,15 +427,19 @@ def _batch_bytes(batch):
 
 
 def _recalibrate_corrected(path, infer_rg, gatkreport, output, k, min_count, slots, prefilter, filter_bits, done_with, fix_n=False,
-                           passes=1):
+                           passes=1, skip=False):
     from . import kmer
     more = kmer._passes_kw(passes)
+    if skip:
+        more['skip_unresolved'] = True
     scan = fastx.PairScan(path, None, infer_rg)
     _warm_up()
     text = scan.result()[0]
     done_with.append(text)
     info = dict(k=k, min_count=int(min_count or 0), hist=np.zeros(kmer.HIST, dtype=np.int64), reads=int(text.n), changed_bases=0,
                 slots=0, fix_n=fix_n, passes=passes)
+    if skip:
+        info['skipped_bases'] = 0
     if prefilter:
         info['admitted'] = 0
     if text.n == 0:
@@ -445,9 +456,17 @@ def _recalibrate_corrected(path, infer_rg, gatkreport, output, k, min_count, slo
     resident = sum(_batch_bytes(r) + (0 if r.cseq is not None else int(r.seq.numel())) for r in rows)
     # ... and room for the one-read-per-row planes (seq, cseq, qual, sidecar) of the largest band a layout's kernel may refuse,
     # which are made while the table is still there (corrected_rows below); pass 1 of `-f` redoes bands one at a time too
-    resident += max(int(b['n']) * (3 * int(b['pitch']) + 4) for b in single['bands'] if b.get('laid') is not None) \
+    # (with skip: the tally plane of every band, and of that band's character rows)
+    if skip:
+        resident += sum(int(r.qual.numel()) for r in rows)
+    resident += max(int(b['n']) * ((4 if skip else 3) * int(b['pitch']) + 4) for b in single['bands'] if b.get('laid') is not None) \
         if any(b.get('laid') is not None for b in single['bands']) else 0
     table = filt = None
+    read_quals = []                   # skip: (batch, its qualities as read) while the tally plane stands in their place
+
+    def tally_plane(batch):
+        read_quals.append((batch, batch.qual))
+        batch.qual, batch.tally_qual = batch.tally_qual, None
     try:
         try:
             if prefilter:
@@ -478,17 +497,26 @@ def _recalibrate_corrected(path, infer_rg, gatkreport, output, k, min_count, slo
         info['min_count'] = t
         with stage('k-mer correct', sync=True):
             for r in rows:
-                info['changed_bases'] += int(kmer.correct_batch(table, r, t, fix_n=fix_n, **more).cpu().numpy().astype(np.int64).sum())
+                counts = kmer.correct_batch(table, r, t, fix_n=fix_n, **more)
+                if skip:
+                    counts, unresolved = counts
+                    info['skipped_bases'] += int(unresolved.cpu().numpy().astype(np.int64).sum())
+                    tally_plane(r)
+                info['changed_bases'] += int(counts.cpu().numpy().astype(np.int64).sum())
 
         def corrected_rows(band):
             # a band whose layout the tally refuses is redone one character row per read; its corrected characters come from the
-            # character kernels on those rows, which is why the table lives until the tally is over
+            # character kernels on those rows, which is why the table lives until the tally is over (skip: its tally plane too)
             batch = fastx.band_rows(band)
             if batch.cseq is None:
                 kmer.correct_batch(table, batch, t, fix_n=fix_n, **more)
+                if skip:
+                    tally_plane(batch)
             return batch
         tables = _tally_local(single, 6, 42, band_rows=corrected_rows)
     finally:
+        for batch, qual in read_quals:                 # the solve, K2 and the writer see the qualities as read; the tally
+            batch.qual = qual                          # planes are released here, before the apply
         if filt is not None:
             filt.close()
         if table is not None:

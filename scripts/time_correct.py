@@ -20,7 +20,11 @@ With `--passes P` (2..8) every repetition also times, for p = 2 .. P, kbbq_kmer_
 ("ms_correct_passes"[p]) and its yardstick, p successive kbbq_kmer_correct_dev launches that feed their plane back through
 global memory against the same table ("ms_correct_repeated"[p]); the leg fails unless the two planes are equal.  With `--flags
 --unresolved` also kbbq_kmer_flag_passes_dev with KBBQ_KMER_FLAG_UNRESOLVED ("ms_flags_unresolved_passes"[p], with the 1s and 2s
-of its plane); the leg fails unless its 1s are where the corrected plane of p passes differs from the input."""
+of its plane); the leg fails unless its 1s are where the corrected plane of p passes differs from the input.
+With `--skip` every repetition also times kbbq_kmer_correct_rows_skip_dev (the corrected plane and, beside it, the tally plane of
+`recalibrate -c --skip-unresolved`: the qualities with byte 0 at every unresolved base) on the same character rows and table
+right after kbbq_kmer_correct_dev ("ms_correct_skip", "skipped_bases", "tally_plane_bytes"); the leg fails unless its corrected
+plane is kbbq_kmer_correct_dev's and its tally plane is the quality plane with as many bytes zeroed as d_unresolved adds up to."""
 import argparse
 import ctypes
 import json
@@ -46,6 +50,8 @@ ap.add_argument('--unresolved', action='store_true',
                 help='with --flags: also time the flag form with unresolved bases as 2 (kbbq_kmer_flag_ex_dev)')
 ap.add_argument('--passes', type=int, default=1,
                 help='also time 2 .. P passes of the correct step in one launch (kbbq_kmer_correct_passes_dev) and as P launches')
+ap.add_argument('--skip', action='store_true',
+                help='also time the correct step that writes the tally plane beside the corrected one (kbbq_kmer_correct_rows_skip_dev)')
 ap.add_argument('--n-rate', type=float, default=0.0, help='share of the bases set to N')
 args = ap.parse_args()
 if args.unresolved and not args.flags:
@@ -90,6 +96,13 @@ flags = torch.empty_like(seq) if args.flags else None     # the plane of the fla
 flags_u = torch.empty_like(seq) if args.unresolved else None      # ... with unresolved bases as 2
 out_p = torch.empty_like(seq) if args.passes > 1 else None # the plane of several passes in one launch
 ping = [torch.empty_like(seq), torch.empty_like(seq)] if args.passes > 1 else None        # ... and of as many launches
+if args.skip:                                           # qualities 2..40 inside the reads, 0 in the padding; the tally plane
+    qual = torch.zeros_like(seq)
+    for lo in range(0, n, step):
+        m = min(step, n - lo)
+        qual[lo:lo + m, :L] = torch.randint(35, 74, (m, L), device='cuda', generator=g, dtype=torch.uint8)
+    out_s, tally = torch.empty_like(seq), torch.empty_like(seq)
+    s_unres = torch.empty((n,), dtype=torch.int32, device='cuda')
 lib = N.load()
 
 
@@ -120,6 +133,8 @@ res = {'reads': n, 'len': L, 'k': k, 'genome': G, 'err': args.err, 'slots': slot
 ms = {'count': [], 'histogram': [], 'correct': []}
 if args.fix_n:
     ms['correct_fix_n'] = []
+if args.skip:
+    ms['correct_skip'] = []
 if args.flags:
     ms['flags'] = []
 if args.unresolved:
@@ -157,6 +172,10 @@ for rep in range(args.reps + 1):
     t = kmer.solid_threshold(hist)
     x = timed(lambda: N.check(lib.kbbq_kmer_correct_dev(table.ctx.handle, table.handle, N.ptr(seq), N.ptr(meta), n, pitch, t,
                                                          N.ptr(out), None)))
+    if args.skip:
+        xs = timed(lambda: N.check(lib.kbbq_kmer_correct_rows_skip_dev(table.ctx.handle, table.handle, N.ptr(seq), N.ptr(meta), n, pitch,
+                                                                       0, t, N.ptr(out_s), None, 0, 1, N.ptr(qual), N.ptr(tally),
+                                                                       N.ptr(s_unres))))
     if args.fix_n:
         xn = timed(lambda: N.check(lib.kbbq_kmer_correct_ex_dev(table.ctx.handle, table.handle, N.ptr(seq), N.ptr(meta), n, pitch, t,
                                                                 N.ptr(out_n), None, N.KMER_FIX_N)))
@@ -198,6 +217,8 @@ for rep in range(args.reps + 1):
             ms['flags_unresolved'].append(xu)
         if args.fix_n:
             ms['correct_fix_n'].append(xn)
+        if args.skip:
+            ms['correct_skip'].append(xs)
 res.update({'ms_' + key: round(float(np.median(v)), 3) for key, v in ms.items()})
 res['count_kmers_per_s'] = windows / (res['ms_count'] * 1e-3)
 res['correct_kmers_per_s'] = windows / (res['ms_correct'] * 1e-3)
@@ -213,6 +234,13 @@ if args.fix_n:
     res['ms_correct_fix_n_all'] = [round(v, 3) for v in ms['correct_fix_n']]
     # (no boolean indexing: the planes have more than 2^31 elements)
     assert torch.equal(torch.where(seq != ord('N'), out_n, out), out), 'the N rule changed a base that is no N'
+if args.skip:
+    res['ms_correct_skip_all'] = [round(v, 3) for v in ms['correct_skip']]
+    res['skipped_bases'] = int(s_unres.sum(dtype=torch.int64).item())
+    res['tally_plane_bytes'] = n * pitch
+    assert torch.equal(out_s, out), 'the corrected plane beside the tally plane is not kbbq_kmer_correct_dev\'s'
+    assert torch.equal(torch.where(tally == 0, torch.zeros_like(qual), qual), tally), 'the tally plane changed a byte it did not zero'
+    assert int(((tally == 0) & (qual != 0)).sum(dtype=torch.int64).item()) == res['skipped_bases'], 'd_unresolved does not add up to the zeros'
 if args.flags:
     res['ms_flags_all'] = [round(v, 3) for v in ms['flags']]
     res['flags_kmers_per_s'] = windows / (res['ms_flags'] * 1e-3)

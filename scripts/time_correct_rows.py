@@ -6,7 +6,10 @@
 substitutions) and against the same table.  The forms: `chars` (one read per row, pitch 160 for 150 bases), `reads_nib` (the
 same rows as 4-bit planes) and `pairs_nib` (two reads to a row, 4-bit planes: what the file path keeps for reads of one
 length).  HIP events, one warm-up, the median and the range of `--reps`; a fresh table for every count.  The run fails unless
-the three tables hold the same histogram and the corrected planes are the same characters.
+the three tables hold the same histogram and the corrected planes are the same characters.  With --skip every repetition also
+times kmer.correct_batch(skip_unresolved=True) on the same table (kbbq_kmer_correct_rows_skip_dev: the tally plane of `recalibrate
+-c --skip-unresolved` beside the corrected plane; "ms_correct_skip", "skipped_bases"); the run fails unless the forms skip the
+same number of bases.
 
 --command FILE: writes `--reads` single-end reads to FILE (unless it exists), then wall time and KBBQ_TIMING stage lines of
 `kbbq recalibrate -c FILE -o out` against `kbbq correct -f FILE -o cor` followed by `kbbq recalibrate -f FILE cor -o out`, each
@@ -30,6 +33,7 @@ ap.add_argument('--err', type=float, default=0.01)
 ap.add_argument('-k', type=int, default=31)
 ap.add_argument('--reps', type=int, default=3)
 ap.add_argument('--kernels', action='store_true')
+ap.add_argument('--skip', action='store_true', help='with --kernels: also time the correction that writes the tally plane')
 ap.add_argument('--command', metavar='FILE', default=None)
 args = ap.parse_args()
 
@@ -88,7 +92,7 @@ def kernels():
         return a.elapsed_time(b)
     hists, planes = {}, {}
     for name, batch in forms.items():
-        count, correct = [], []
+        count, correct, skipping = [], [], []
         for rep in range(args.reps + 1):
             table = kmer.KmerTable(k, slots)
             torch.cuda.synchronize()
@@ -96,19 +100,30 @@ def kernels():
             hist = kmer.kmer_histogram(table)
             t = kmer.solid_threshold(hist)
             x = timed(lambda: kmer.correct_batch(table, batch, t))
+            if args.skip:
+                got = []
+                s = timed(lambda: got.append(kmer.correct_batch(table, batch, t, skip_unresolved=True)))
+                skipped = int(got[0][1].sum(dtype=torch.int64).item())
+                batch.tally_qual = None
             table.close()
             if rep:
                 count.append(c)
                 correct.append(x)
+                if args.skip:
+                    skipping.append(s)
         hists[name] = hist
         planes[name] = batch.chars('cseq')
         res[name] = {'pitch': batch.pitch, 'seq_bytes': int(batch.seq.numel()), 'ms_count': spread(count), 'ms_correct': spread(correct),
                      'min_count': t}
+        if args.skip:
+            res[name].update(ms_correct_skip=spread(skipping), skipped_bases=skipped, tally_plane_bytes=int(batch.qual.numel()))
     ref = planes['chars'][:, :L]
     pairs = planes.pop('pairs_nib')
     assert all(np.array_equal(h, hists['chars']) for h in hists.values()), 'the forms counted different tables'
     assert torch.equal(planes['reads_nib'][:, :L], ref), 'reads_nib corrected differently'
     assert torch.equal(pairs[:, :L], ref[0::2]) and torch.equal(pairs[:n // 2, L + 1:2 * L + 1], ref[1::2]), 'pairs_nib corrected differently'
+    if args.skip:
+        assert len({res[name]['skipped_bases'] for name in forms}) == 1, 'the forms skipped different numbers of bases'
     res['changed_bases'] = int((ref != plain.seq[:, :L]).sum().item())
     print(json.dumps(res), flush=True)
 
