@@ -926,6 +926,33 @@ int kbbq_kmer_correct_rows_skip_dev(kbbq_ctx* ctx, const kbbq_kmer_table* table,
                                     int64_t nrows, int pitch, int flags, int min_count, uint8_t* d_out, uint32_t* d_changed, int opts,
                                     int passes, const uint8_t* d_qual, uint8_t* d_tally_qual, uint32_t* d_unresolved);
 
+/* ---- partitions: one partition of the k-mers at a time (kbbq correct --partitions; csrc/kbbq_kmer.h "partitions") ------------
+ * part(key, P) = kbbq_kmer_owner(key, P), the split the ranks use.  Each call below is its sibling without `_part` -- the same
+ * arguments, refusals, table, probing and KBBQ_E_FULL -- for the windows whose canonical key has part(key, parts) == part, and
+ * for no other window: the rows are read and every window is hashed, but only partition `part` is inserted (the filtered
+ * forms test the partition before they read the filter).  Counting ADDS, and every key lies in exactly one partition: calling
+ * all `parts` partitions into ONE table equals one kbbq_kmer_count_dev of the same rows, and calling partition p alone into an
+ * empty table leaves exactly the keys of partition p there, each with its count over those rows -- so P rounds over all rows,
+ * through a table 1 / P the size that is cleared between them (kbbq_kmer_table_clear_dev), see every key's global count once
+ * (kbbq/kmer.py count_partitioned: the histograms of the rounds add up, kbbq_kmer_select_dev keeps the pairs that can be
+ * solid, kbbq_kmer_merge_dev builds the table the correction reads from them).
+ * parts must be in 1..1024 and part in 0..parts-1: anything else returns KBBQ_E_ARG naming the call, on the two numbers alone
+ * and before any other argument is looked at; then come the sibling's own refusals.  parts == 1 IS the sibling: the same
+ * kernel is launched.                                                                                                       */
+int kbbq_kmer_count_part_dev(kbbq_ctx* ctx, kbbq_kmer_table* table, const uint8_t* d_seq, const uint32_t* d_meta, int64_t nreads,
+                             int pitch, int parts, int part);
+int kbbq_kmer_count_filtered_part_dev(kbbq_ctx* ctx, kbbq_kmer_table* table, const kbbq_kmer_filter* filter, const uint8_t* d_seq,
+                                      const uint32_t* d_meta, int64_t nreads, int pitch, int parts, int part);
+int kbbq_kmer_count_part(kbbq_ctx* ctx, kbbq_kmer_table* table, const uint8_t* seq, const uint32_t* meta, int64_t nreads, int pitch,
+                         int parts, int part);
+int kbbq_kmer_count_filtered_part(kbbq_ctx* ctx, kbbq_kmer_table* table, const kbbq_kmer_filter* filter, const uint8_t* seq,
+                                  const uint32_t* meta, int64_t nreads, int pitch, int parts, int part);
+int kbbq_kmer_count_rows_part_dev(kbbq_ctx* ctx, kbbq_kmer_table* table, const uint8_t* d_seq, const uint32_t* d_meta, int64_t nrows,
+                                  int pitch, int flags, int parts, int part);
+int kbbq_kmer_count_filtered_rows_part_dev(kbbq_ctx* ctx, kbbq_kmer_table* table, const kbbq_kmer_filter* filter,
+                                           const uint8_t* d_seq, const uint32_t* d_meta, int64_t nrows, int pitch, int flags, int parts,
+                                           int part);
+
 #ifdef __cplusplus
 }
 #endif

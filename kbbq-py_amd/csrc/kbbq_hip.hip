@@ -2219,10 +2219,11 @@ static int kmer_geometry(kbbq_ctx* c, const char* who, const kbbq_kmer_table* t,
 #define KM_READER(K, nib) ((nib) ? (const void*)K<true> : (const void*)K<false>)
 
 // launches of at most 2^20 workgroups.  The kernel's parameters after its KmerParams, in their order: `extra` (KmerFilterParams,
-// passes) when the kernel has one, then `tally` -- both correction kernels end in a KmerTally, a copy of which moves with the
-// rows of each launch; every other kernel gets nullptr
+// passes, KmerPartParams) when the kernel has one, `part` (the KmerPartParams of a kernel that has an `extra` before it), then
+// `tally` -- both correction kernels end in a KmerTally, a copy of which moves with the rows of each launch; every other kernel
+// gets nullptr
 static int kmer_launches(kbbq_ctx* c, const KmerParams& p, const void* kernel, size_t lds, const void* extra,
-                         const KmerTally* tally = nullptr)
+                         const KmerTally* tally = nullptr, const KmerPartParams* part = nullptr)
 {
     HIPCHK(hipSetDevice(c->device));
     const int64_t per = ((int64_t)1 << 20) * p.rows_per_wg;
@@ -2235,22 +2236,36 @@ static int kmer_launches(kbbq_ctx* c, const KmerParams& p, const void* kernel, s
         if (p.unresolved) q.unresolved = p.unresolved + lo;
         KmerTally ty = {nullptr, nullptr};
         if (tally && tally->qual) ty = {tally->qual + (size_t)lo * p.cpr * 16, tally->out + (size_t)lo * p.cpr * 16};
-        void* args[3] = {&q, nullptr, nullptr};         // hipLaunchKernel reads one entry per kernel parameter
+        void* args[4] = {&q, nullptr, nullptr, nullptr};   // hipLaunchKernel reads one entry per kernel parameter
         int na = 1;
         if (extra) args[na++] = const_cast<void*>(extra);
+        if (part) args[na++] = const_cast<KmerPartParams*>(part);
         if (tally) args[na++] = &ty;
         HIPCHK(hipLaunchKernel(kernel, dim3((unsigned)((m + p.rows_per_wg - 1) / p.rows_per_wg)), dim3(KM_THREADS), args, lds, c->stream));
     }
     return KBBQ_OK;
 }
 
-static int kmer_count_rows(kbbq_ctx* c, const char* who, kbbq_kmer_table* t, const uint8_t* d_seq, const uint32_t* d_meta, int64_t n,
-                           int pitch, bool nib)
+// the partition of a kbbq_kmer_count*_part* call, refused on the two numbers alone
+static int kmer_part_ok(const char* who, int parts, int part)
 {
+    if (parts < 1 || parts > KM_MAX_BUCKETS) return fail(KBBQ_E_ARG, "%s: parts must be in 1..%d, got %d", who, KM_MAX_BUCKETS, parts);
+    if (part < 0 || part >= parts) return fail(KBBQ_E_ARG, "%s: part must be in 0..%d (parts - 1), got %d", who, parts - 1, part);
+    return KBBQ_OK;
+}
+
+// parts == 1: km_count itself; else the windows of partition `part` of `parts` (km_count_part)
+static int kmer_count_rows(kbbq_ctx* c, const char* who, kbbq_kmer_table* t, const uint8_t* d_seq, const uint32_t* d_meta, int64_t n,
+                           int pitch, bool nib, int parts = 1, int part = 0)
+{
+    int rc = kmer_part_ok(who, parts, part);
+    if (rc) return rc;
     KmerParams p; size_t lds = 0;
-    int rc = kmer_geometry(c, who, t, d_seq, d_meta, n, pitch, nib, KM_LDS_COUNT, 1, p, &lds);
+    rc = kmer_geometry(c, who, t, d_seq, d_meta, n, pitch, nib, KM_LDS_COUNT, 1, p, &lds);
     if (rc || n == 0) return rc;
-    return kmer_launches(c, p, KM_READER(km_count, nib), lds, nullptr);
+    if (parts == 1) return kmer_launches(c, p, KM_READER(km_count, nib), lds, nullptr);
+    const KmerPartParams pp = {(u32)parts, (u32)part};
+    return kmer_launches(c, p, KM_READER(km_count_part, nib), lds, &pp);
 }
 
 int kbbq_kmer_count_dev(kbbq_ctx* c, kbbq_kmer_table* t, const uint8_t* d_seq, const uint32_t* d_meta, int64_t n, int pitch)
@@ -2275,6 +2290,22 @@ int kbbq_kmer_count_rows_dev(kbbq_ctx* c, kbbq_kmer_table* t, const uint8_t* d_s
     int rc = kmer_row_flags("kbbq_kmer_count_rows_dev", flags, &nib);
     if (rc) return rc;
     return kmer_count_rows(c, "kbbq_kmer_count_rows_dev", t, d_seq, d_meta, nrows, pitch, nib);
+}
+
+int kbbq_kmer_count_part_dev(kbbq_ctx* c, kbbq_kmer_table* t, const uint8_t* d_seq, const uint32_t* d_meta, int64_t n, int pitch,
+                             int parts, int part)
+{
+    return kmer_count_rows(c, "kbbq_kmer_count_part_dev", t, d_seq, d_meta, n, pitch, false, parts, part);
+}
+
+int kbbq_kmer_count_rows_part_dev(kbbq_ctx* c, kbbq_kmer_table* t, const uint8_t* d_seq, const uint32_t* d_meta, int64_t nrows,
+                                  int pitch, int flags, int parts, int part)
+{
+    bool nib = false;
+    int rc = kmer_part_ok("kbbq_kmer_count_rows_part_dev", parts, part);
+    if (!rc) rc = kmer_row_flags("kbbq_kmer_count_rows_part_dev", flags, &nib);
+    if (rc) return rc;
+    return kmer_count_rows(c, "kbbq_kmer_count_rows_part_dev", t, d_seq, d_meta, nrows, pitch, nib, parts, part);
 }
 
 int kbbq_kmer_histogram_dev(kbbq_ctx* c, const kbbq_kmer_table* t, uint64_t* d_hist)
@@ -2540,17 +2571,32 @@ int kbbq_kmer_merge_dev(kbbq_ctx* c, kbbq_kmer_table* t, const uint64_t* d_keys,
     return KBBQ_OK;
 }
 
-int kbbq_kmer_count(kbbq_ctx* c, kbbq_kmer_table* t, const uint8_t* seq, const uint32_t* meta, int64_t n, int pitch)
+// kbbq_kmer_count and kbbq_kmer_count_part: `dev`, the device call a slab goes to, is named in a refusal that only it can make
+static int kmer_count_host(kbbq_ctx* c, const char* who, const char* dev, kbbq_kmer_table* t, const uint8_t* seq, const uint32_t* meta,
+                           int64_t n, int pitch, int parts, int part)
 {
-    if (!c || !t) return fail(KBBQ_E_ARG, "kbbq_kmer_count: NULL ctx or table");
-    if (n < 0 || pitch <= 0 || (pitch & 15)) return fail(KBBQ_E_ARG, "kbbq_kmer_count: bad n/pitch");
-    if (n > 0 && (!seq || !meta)) return fail(KBBQ_E_ARG, "kbbq_kmer_count: NULL plane");
+    int rc = kmer_part_ok(who, parts, part);
+    if (rc) return rc;
+    if (!c || !t) return fail(KBBQ_E_ARG, "%s: NULL ctx or table", who);
+    if (n < 0 || pitch <= 0 || (pitch & 15)) return fail(KBBQ_E_ARG, "%s: bad n/pitch", who);
+    if (n > 0 && (!seq || !meta)) return fail(KBBQ_E_ARG, "%s: NULL plane", who);
     if (n == 0) return KBBQ_OK;
     HIPCHK(hipSetDevice(c->device));
     // a slab: seq | meta
-    return stage_run(c, "kbbq_kmer_count", {seq}, meta, nullptr, n, pitch, [&](uint8_t* d, size_t plane, int64_t m) {
-        return kbbq_kmer_count_dev(c, t, d, (const uint32_t*)(d + plane), m, pitch);
+    return stage_run(c, who, {seq}, meta, nullptr, n, pitch, [&](uint8_t* d, size_t plane, int64_t m) {
+        return kmer_count_rows(c, dev, t, d, (const uint32_t*)(d + plane), m, pitch, false, parts, part);
     });
+}
+
+int kbbq_kmer_count(kbbq_ctx* c, kbbq_kmer_table* t, const uint8_t* seq, const uint32_t* meta, int64_t n, int pitch)
+{
+    return kmer_count_host(c, "kbbq_kmer_count", "kbbq_kmer_count_dev", t, seq, meta, n, pitch, 1, 0);
+}
+
+int kbbq_kmer_count_part(kbbq_ctx* c, kbbq_kmer_table* t, const uint8_t* seq, const uint32_t* meta, int64_t n, int pitch, int parts,
+                         int part)
+{
+    return kmer_count_host(c, "kbbq_kmer_count_part", "kbbq_kmer_count_part_dev", t, seq, meta, n, pitch, parts, part);
 }
 
 static int kmer_correct_host(kbbq_ctx* c, const char* who, const kbbq_kmer_table* t, const uint8_t* seq, const uint32_t* meta, int64_t n,
@@ -2720,15 +2766,20 @@ int kbbq_kmer_prefilter_rows_dev(kbbq_ctx* c, kbbq_kmer_filter* f, int k, const 
     return kmer_prefilter_rows(c, "kbbq_kmer_prefilter_rows_dev", f, k, d_seq, d_meta, nrows, pitch, nib);
 }
 
+// parts == 1: km_count_filtered itself; else km_count_filtered_part
 static int kmer_count_filtered_rows(kbbq_ctx* c, const char* who, kbbq_kmer_table* t, const kbbq_kmer_filter* f, const uint8_t* d_seq,
-                                    const uint32_t* d_meta, int64_t n, int pitch, bool nib)
+                                    const uint32_t* d_meta, int64_t n, int pitch, bool nib, int parts = 1, int part = 0)
 {
+    int rc = kmer_part_ok(who, parts, part);
+    if (rc) return rc;
     if (!f) return fail(KBBQ_E_ARG, "%s: filter is NULL", who);
     KmerParams p; size_t lds = 0;
-    int rc = kmer_geometry(c, who, t, d_seq, d_meta, n, pitch, nib, KM_LDS_COUNT, 1, p, &lds);
+    rc = kmer_geometry(c, who, t, d_seq, d_meta, n, pitch, nib, KM_LDS_COUNT, 1, p, &lds);
     if (rc || n == 0) return rc;
     const KmerFilterParams fp = kmer_filter_params(f);
-    return kmer_launches(c, p, KM_READER(km_count_filtered, nib), lds, &fp);
+    if (parts == 1) return kmer_launches(c, p, KM_READER(km_count_filtered, nib), lds, &fp);
+    const KmerPartParams pp = {(u32)parts, (u32)part};
+    return kmer_launches(c, p, KM_READER(km_count_filtered_part, nib), lds, &fp, nullptr, &pp);
 }
 
 int kbbq_kmer_count_filtered_dev(kbbq_ctx* c, kbbq_kmer_table* t, const kbbq_kmer_filter* f, const uint8_t* d_seq,
@@ -2746,6 +2797,22 @@ int kbbq_kmer_count_filtered_rows_dev(kbbq_ctx* c, kbbq_kmer_table* t, const kbb
     return kmer_count_filtered_rows(c, "kbbq_kmer_count_filtered_rows_dev", t, f, d_seq, d_meta, nrows, pitch, nib);
 }
 
+int kbbq_kmer_count_filtered_part_dev(kbbq_ctx* c, kbbq_kmer_table* t, const kbbq_kmer_filter* f, const uint8_t* d_seq,
+                                      const uint32_t* d_meta, int64_t n, int pitch, int parts, int part)
+{
+    return kmer_count_filtered_rows(c, "kbbq_kmer_count_filtered_part_dev", t, f, d_seq, d_meta, n, pitch, false, parts, part);
+}
+
+int kbbq_kmer_count_filtered_rows_part_dev(kbbq_ctx* c, kbbq_kmer_table* t, const kbbq_kmer_filter* f, const uint8_t* d_seq,
+                                           const uint32_t* d_meta, int64_t nrows, int pitch, int flags, int parts, int part)
+{
+    bool nib = false;
+    int rc = kmer_part_ok("kbbq_kmer_count_filtered_rows_part_dev", parts, part);
+    if (!rc) rc = kmer_row_flags("kbbq_kmer_count_filtered_rows_part_dev", flags, &nib);
+    if (rc) return rc;
+    return kmer_count_filtered_rows(c, "kbbq_kmer_count_filtered_rows_part_dev", t, f, d_seq, d_meta, nrows, pitch, nib, parts, part);
+}
+
 int kbbq_kmer_prefilter(kbbq_ctx* c, kbbq_kmer_filter* f, int k, const uint8_t* seq, const uint32_t* meta, int64_t n, int pitch)
 {
     if (!c || !f) return fail(KBBQ_E_ARG, "kbbq_kmer_prefilter: NULL ctx or filter");
@@ -2759,17 +2826,32 @@ int kbbq_kmer_prefilter(kbbq_ctx* c, kbbq_kmer_filter* f, int k, const uint8_t* 
     });
 }
 
+static int kmer_count_filtered_host(kbbq_ctx* c, const char* who, const char* dev, kbbq_kmer_table* t, const kbbq_kmer_filter* f,
+                                    const uint8_t* seq, const uint32_t* meta, int64_t n, int pitch, int parts, int part)
+{
+    int rc = kmer_part_ok(who, parts, part);
+    if (rc) return rc;
+    if (!c || !t || !f) return fail(KBBQ_E_ARG, "%s: NULL ctx, table or filter", who);
+    if (n < 0 || pitch <= 0 || (pitch & 15)) return fail(KBBQ_E_ARG, "%s: bad n/pitch", who);
+    if (n > 0 && (!seq || !meta)) return fail(KBBQ_E_ARG, "%s: NULL plane", who);
+    if (n == 0) return KBBQ_OK;
+    HIPCHK(hipSetDevice(c->device));
+    return stage_run(c, who, {seq}, meta, nullptr, n, pitch, [&](uint8_t* d, size_t plane, int64_t m) {
+        return kmer_count_filtered_rows(c, dev, t, f, d, (const uint32_t*)(d + plane), m, pitch, false, parts, part);
+    });
+}
+
 int kbbq_kmer_count_filtered(kbbq_ctx* c, kbbq_kmer_table* t, const kbbq_kmer_filter* f, const uint8_t* seq, const uint32_t* meta,
                              int64_t n, int pitch)
 {
-    if (!c || !t || !f) return fail(KBBQ_E_ARG, "kbbq_kmer_count_filtered: NULL ctx, table or filter");
-    if (n < 0 || pitch <= 0 || (pitch & 15)) return fail(KBBQ_E_ARG, "kbbq_kmer_count_filtered: bad n/pitch");
-    if (n > 0 && (!seq || !meta)) return fail(KBBQ_E_ARG, "kbbq_kmer_count_filtered: NULL plane");
-    if (n == 0) return KBBQ_OK;
-    HIPCHK(hipSetDevice(c->device));
-    return stage_run(c, "kbbq_kmer_count_filtered", {seq}, meta, nullptr, n, pitch, [&](uint8_t* d, size_t plane, int64_t m) {
-        return kbbq_kmer_count_filtered_dev(c, t, f, d, (const uint32_t*)(d + plane), m, pitch);
-    });
+    return kmer_count_filtered_host(c, "kbbq_kmer_count_filtered", "kbbq_kmer_count_filtered_dev", t, f, seq, meta, n, pitch, 1, 0);
+}
+
+int kbbq_kmer_count_filtered_part(kbbq_ctx* c, kbbq_kmer_table* t, const kbbq_kmer_filter* f, const uint8_t* seq, const uint32_t* meta,
+                                  int64_t n, int pitch, int parts, int part)
+{
+    return kmer_count_filtered_host(c, "kbbq_kmer_count_filtered_part", "kbbq_kmer_count_filtered_part_dev", t, f, seq, meta, n, pitch,
+                                    parts, part);
 }
 
 } // extern "C"

@@ -940,3 +940,51 @@ __global__ __launch_bounds__(KM_THREADS) void km_merge(const u64* in_keys, const
         if (!km_insert(keys, counts, mask, in_keys[i], in_counts[i])) { atomicMin(status + ST_KMER, (u64)i); return; }
     }
 }
+
+// ---- partitions: the count split in time on one GPU (kbbq correct --partitions; kbbq/kmer.py count_partitioned) --------------
+// part(key, P) = km_owner(key, P), the split the ranks use in space.  Round p of P counts, over all rows, exactly the windows
+// whose canonical key has part == p, into a table 1 / P the size: a key lies in one partition, so its count there is its
+// global count, and the rounds' histograms add up to the one table's.  The two kernels are km_count / km_count_filtered with one
+// test in front of the insert -- in the filtered form in front of the load of twice[word] too, so a round reads the filter
+// for its own keys alone.  The grid, the LDS plan (KM_LDS_COUNT), the rows per workgroup and the walk are km_count's; every
+// round hashes every window (canonical key, one mix for the owner), which is what P rounds cost beside one.
+struct KmerPartParams { u32 parts, part; };   // 1 <= parts <= KM_MAX_BUCKETS, part < parts
+
+template <bool NIB>
+__global__ __launch_bounds__(KM_THREADS) void km_count_part(KmerParams p, KmerPartParams q)
+{
+    extern __shared__ u32 km_lds[];
+    u32* code = km_lds_chunk(km_lds, p, 0); u32* brk = km_lds_chunk(km_lds, p, 1);
+    const int64_t row0 = (int64_t)blockIdx.x * p.rows_per_wg;
+    const int nr = km_load_chunks<NIB>(p, row0, code, brk);
+    __syncthreads();
+    if (km_table_full(p)) return;
+    km_walk(p, code, brk, nr, [&](int r, int, int, u64 f) {
+        const u64 key = km_canonical(f, p.k);
+        if (km_owner(key, q.parts) != q.part) return true;                // another round's key
+        if (km_insert(p.keys, p.counts, p.mask, key, 1u)) return true;
+        atomicMin(p.status + ST_KMER, (u64)(row0 + r));
+        return false;
+    });
+}
+
+template <bool NIB>
+__global__ __launch_bounds__(KM_THREADS) void km_count_filtered_part(KmerParams p, KmerFilterParams f, KmerPartParams q)
+{
+    extern __shared__ u32 km_lds[];
+    u32* code = km_lds_chunk(km_lds, p, 0); u32* brk = km_lds_chunk(km_lds, p, 1);
+    const int64_t row0 = (int64_t)blockIdx.x * p.rows_per_wg;
+    const int nr = km_load_chunks<NIB>(p, row0, code, brk);
+    __syncthreads();
+    if (km_table_full(p)) return;
+    km_walk(p, code, brk, nr, [&](int r, int, int, u64 fw) {
+        const u64 key = km_canonical(fw, p.k);
+        if (km_owner(key, q.parts) != q.part) return true;                // another round's key: its filter word is not read
+        u64 m;
+        const u64 w = km_filter_index(key, f.wmask, &m);
+        if ((f.twice[w] & m) != m) return true;                           // seen once
+        if (km_insert(p.keys, p.counts, p.mask, key, 1u)) return true;
+        atomicMin(p.status + ST_KMER, (u64)(row0 + r));
+        return false;
+    });
+}

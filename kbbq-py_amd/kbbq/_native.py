@@ -205,6 +205,12 @@ PROTOTYPES = {
     'kbbq_kmer_count_rows_dev': (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i]),
     'kbbq_kmer_prefilter_rows_dev': (_i, [_vp, _vp, _i, _vp, _vp, _i64, _i, _i]),
     'kbbq_kmer_count_filtered_rows_dev': (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i, _i]),
+    'kbbq_kmer_count_part_dev': (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i]),
+    'kbbq_kmer_count_filtered_part_dev': (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i]),
+    'kbbq_kmer_count_part': (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i]),
+    'kbbq_kmer_count_filtered_part': (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i]),
+    'kbbq_kmer_count_rows_part_dev': (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i]),
+    'kbbq_kmer_count_filtered_rows_part_dev': (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i]),
     'kbbq_kmer_correct_rows_dev': (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _vp, _vp]),
     'kbbq_kmer_correct_rows_ex_dev': (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _vp, _vp, _i]),
     'kbbq_kmer_correct_rows_passes_dev': (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _vp, _vp, _i, _i]),

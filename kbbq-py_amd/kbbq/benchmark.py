@@ -489,7 +489,7 @@ def _kmer_benchmark_inputs(bamfile, k, min_count, prefilter, filter_bits):
 
 
 def benchmark_kmers(bamfile, ref, var_sites, k=31, min_count=None, slots=None, prefilter=False, filter_bits=4, use_oq=False,
-                    bedfh=None, info=None, passes=1):
+                    bedfh=None, info=None, passes=1, partitions=1):
     """How good is the k-mer rule on a truth set?  joint[q][truth error][k-mer class], int64 (256, 2, 3): every base of the
     alignments that benchmark_bam counts (not at a variant site, inside the BED, not soft-clipped), by its reported quality
     (QUAL, or the OQ tag with use_oq), by whether it differs from the reference (K4, exactly as benchmark_bam flags it) and
@@ -502,10 +502,13 @@ def benchmark_kmers(bamfile, ref, var_sites, k=31, min_count=None, slots=None, p
     One GPU; bamfile is a kbbq.aln.AlignmentFile.  `info`, a dict, receives k, min_count, reads, slots, prefilter, admitted,
     bases, errors, flagged, flagged_errors, unresolved and unresolved_errors (totals over the counted bases).
     passes: the classes of `passes` passes of the rule (flag_errors(passes=...): 1 where the last pass ends on another letter,
-    2 where the base is unchanged and its row's last evaluation left it unresolved); `info` then receives passes too."""
+    2 where the base is unchanged and its row's last evaluation left it unresolved); `info` then receives passes too.
+    partitions: as gatk.bqsr.bam_to_kmer_covariates' -- the count in that many rounds (kmer.count_partitioned), the classes read
+    from the solid table: the same joint array; with more than one round `info` receives partitions, kept_pairs and solid_slots."""
     from . import _device as dev
     from . import kmer
     passes = kmer.check_passes(passes)
+    partitions = kmer._check_partitions(partitions)
     b = _kmer_benchmark_inputs(bamfile, k, min_count, prefilter, filter_bits)
     k = int(k)
     torch = dev._torch()
@@ -516,6 +519,7 @@ def benchmark_kmers(bamfile, ref, var_sites, k=31, min_count=None, slots=None, p
     qual = _qual_chars_dev(bamfile, lens, pitch, use_oq)
     n = len(lens)
     t, nslots, admitted = (int(min_count) if min_count is not None else 0), 0, None
+    P = 1
     if n:
         d_seq = keep['seq']
         d_len = torch.from_numpy(np.ascontiguousarray(lens.astype(np.uint32)).view(np.int32)).cuda()
@@ -528,15 +532,23 @@ def benchmark_kmers(bamfile, ref, var_sites, k=31, min_count=None, slots=None, p
                 filt = kmer.prefilter_kmers(d_seq, d_len, k=k, filter=kmer.KmerFilter(kmer.filter_words(windows, filter_bits)))
                 admitted = filt.admitted
                 filt.release_seen()
-            if slots is None:
-                slots = kmer.default_slots(admitted if prefilter else windows,
-                                           budget - resident - (filt.nbytes if filt is not None else 0))
-            table = kmer.count_kmers(d_seq, d_len, k=k, slots=slots, filter=filt)
-            if filt is not None:
-                filt.close()
-            t = int(min_count) if min_count is not None else kmer.solid_threshold(kmer.kmer_histogram(table))
+            total, room = admitted if prefilter else windows, budget - resident - (filt.nbytes if filt is not None else 0)
+            P = kmer.resolve_partitions(partitions, total, room) if partitions != 1 else 1
+            if P > 1:
+                table, _, t, parts_info = kmer.count_partitioned(
+                    lambda tab, p: kmer.count_kmers(d_seq, d_len, k=k, table=tab, filter=filt, parts=P, part=p), k, P,
+                    slots if slots is not None else kmer.partition_slots(total, P, room), min_count, room)
+                if filt is not None:
+                    filt.close()
+            else:
+                if slots is None:
+                    slots = kmer.default_slots(total, room)
+                table = kmer.count_kmers(d_seq, d_len, k=k, slots=slots, filter=filt)
+                if filt is not None:
+                    filt.close()
+                t = int(min_count) if min_count is not None else kmer.solid_threshold(kmer.kmer_histogram(table))
             kflags, _, _ = kmer.flag_errors(table, d_seq, d_len, t, unresolved=True, **kmer._passes_kw(passes))
-            nslots = table.slots
+            nslots = parts_info['slots'] if P > 1 else table.slots
         finally:
             if filt is not None:
                 filt.close()
@@ -549,6 +561,8 @@ def benchmark_kmers(bamfile, ref, var_sites, k=31, min_count=None, slots=None, p
         info.update(k=k, min_count=t, reads=n, slots=nslots, prefilter=bool(prefilter), admitted=admitted, **kmer_totals(joint))
         if passes != 1:
             info.update(passes=passes)
+        if P > 1:
+            info.update(partitions=P, kept_pairs=parts_info['kept_pairs'], solid_slots=parts_info['solid_slots'])
     return joint
 
 
@@ -569,6 +583,8 @@ def kmer_summary(info):
                ratio(info['flagged_errors'], info['errors'])))
     if info.get('passes', 1) > 1:
         line += ' passes=%d' % info['passes']
+    if info.get('partitions', 1) > 1:
+        line += ' partitions=%d' % info['partitions']
     if info.get('prefilter'):
         line += ' prefilter=1 admitted=%d slots=%d' % (info['admitted'], info['slots'])
     return line
@@ -592,7 +608,7 @@ def print_benchmark_kmers(joint, label):
 
 def benchmark(bamfile, fafile, vcffile, fastqfile=None, label=None, use_oq=False, bedfh=None, kmers=None):
     """Run the benchmark and print it.  With a FASTQ, its reads are matched to the alignments by name.  kmers: a dict of
-    benchmark_kmers' options (k, min_count, slots, prefilter, filter_bits, passes) -- print the k-mer rule's flags against the truth
+    benchmark_kmers' options (k, min_count, slots, prefilter, filter_bits, passes, partitions) -- print the k-mer rule's flags against the truth
     set's instead (print_benchmark_kmers) and one summary line on stderr."""
     if kmers is not None and fastqfile is not None:
         raise ValueError('benchmark --kmers takes the alignments alone (-b), not a FASTQ joined by name (-f)')

@@ -333,7 +333,7 @@ def _kmer_inputs(bamfileobj, k, min_count, prefilter, filter_bits, use_oq, maxsc
 
 
 def bam_to_kmer_covariates(bamfileobj, k=31, min_count=None, slots=None, prefilter=False, filter_bits=4, use_oq=False,
-                           minscore=6, maxscore=42, info=None, skip_unresolved=False, passes=1):
+                           minscore=6, maxscore=42, info=None, skip_unresolved=False, passes=1, partitions=1):
     """The nine model vectors from aligned reads alone -- no reference, no known sites (`kbbq bqsr --kmers`).  A base is an error
     where the k-mer correction of kbbq.kmer would change it: every k-mer of SEQ of every record is counted (soft clips too:
     they are sequenced bases; keys are canonical, so the alignment's strand does not matter), a k-mer is solid at min_count
@@ -351,10 +351,15 @@ def bam_to_kmer_covariates(bamfileobj, k=31, min_count=None, slots=None, prefilt
     over all bases of SEQ, before the tally's own exclusions as flagged_bases is.
     passes: the flags of `passes` passes of the correction (kbbq_kmer_flag_passes_dev) -- an error where the last pass ends on
     another letter than SEQ's, unresolved where the base is unchanged and its row's last evaluation left it so; `info` then
-    receives passes too."""
+    receives passes too.
+    partitions: the k-mers counted in that many rounds through a table of `slots` slots (kbbq.kmer.count_partitioned; 'auto':
+    kbbq.kmer.partitions_for within what the budget leaves beside the resident planes) and the flags written against the solid
+    table: the same vectors.  With more than one round `info` receives partitions, kept_pairs and solid_slots too, and its slots
+    is the per-partition table.  Refused in a process group before the group's own refusal."""
     from .. import _device as dev
     from .. import _solve, fastx, kmer
     passes = kmer.check_passes(passes)
+    partitions = kmer._check_partitions(partitions)
     b, n, S = _kmer_inputs(bamfileobj, k, min_count, prefilter, filter_bits, use_oq, maxscore)
     k = int(k)
     T = dev._torch()
@@ -379,17 +384,26 @@ def bam_to_kmer_covariates(bamfileobj, k=31, min_count=None, slots=None, prefilt
             filt = kmer.prefilter_kmers(d_seq, d_len, k=k, filter=kmer.KmerFilter(kmer.filter_words(windows, filter_bits)))
             admitted = filt.admitted
             filt.release_seen()
-        if slots is None:
-            slots = kmer.default_slots(admitted if prefilter else windows, budget - resident - (filt.nbytes if filt is not None else 0))
-        table = kmer.count_kmers(d_seq, d_len, k=k, slots=slots, filter=filt)
-        if filt is not None:
-            filt.close()
-        t = int(min_count) if min_count is not None else kmer.solid_threshold(kmer.kmer_histogram(table))
+        total, room = admitted if prefilter else windows, budget - resident - (filt.nbytes if filt is not None else 0)
+        P = kmer.resolve_partitions(partitions, total, room) if partitions != 1 else 1
+        if P > 1:
+            table, _, t, parts_info = kmer.count_partitioned(
+                lambda tab, p: kmer.count_kmers(d_seq, d_len, k=k, table=tab, filter=filt, parts=P, part=p), k, P,
+                slots if slots is not None else kmer.partition_slots(total, P, room), min_count, room)
+            if filt is not None:
+                filt.close()
+        else:
+            if slots is None:
+                slots = kmer.default_slots(total, room)
+            table = kmer.count_kmers(d_seq, d_len, k=k, slots=slots, filter=filt)
+            if filt is not None:
+                filt.close()
+            t = int(min_count) if min_count is not None else kmer.solid_threshold(kmer.kmer_histogram(table))
         if skip_unresolved:
             err, changed, skipped = kmer.flag_errors(table, d_seq, d_len, t, unresolved=True, **kmer._passes_kw(passes))
         else:
             err, changed = kmer.flag_errors(table, d_seq, d_len, t, **kmer._passes_kw(passes))
-        nslots = table.slots
+        nslots = parts_info['slots'] if P > 1 else table.slots
     finally:
         if filt is not None:
             filt.close()
@@ -407,6 +421,8 @@ def bam_to_kmer_covariates(bamfileobj, k=31, min_count=None, slots=None, prefilt
             info.update(skipped_bases=int(skipped.cpu().numpy().astype(np.int64).sum()))
         if passes != 1:
             info.update(passes=passes)
+        if P > 1:
+            info.update(partitions=P, kept_pairs=parts_info['kept_pairs'], solid_slots=parts_info['solid_slots'])
     return _solve.vectors_from_tables(*tables.to_host(), maxscore)
 
 
@@ -532,12 +548,14 @@ def bam_to_report(bamfileobj, fastafilename, var_pos):
 
 
 def bam_to_report_kmers(bamfileobj, k=31, min_count=None, slots=None, prefilter=False, filter_bits=4, use_oq=False, info=None,
-                        skip_unresolved=False, passes=1):
+                        skip_unresolved=False, passes=1, partitions=1):
     """Aligned reads -> recalibration report without a reference or known sites: the errors are what the k-mers of the reads'
     own sequences contradict (bam_to_kmer_covariates); read groups are named by their PU as in bam_to_report.  skip_unresolved:
-    bases the k-mers contradict without naming a replacement are left out of the tally (bam_to_kmer_covariates)."""
+    bases the k-mers contradict without naming a replacement are left out of the tally (bam_to_kmer_covariates).  partitions: the
+    count in that many rounds (bam_to_kmer_covariates): the same report."""
     rgs = list(utils.get_rg_to_pu(bamfileobj).values())
     vectors = bam_to_kmer_covariates(bamfileobj, k=k, min_count=min_count, slots=slots, prefilter=prefilter,
                                      filter_bits=filter_bits, use_oq=use_oq, info=info, skip_unresolved=skip_unresolved,
-                                     **({} if passes == 1 else dict(passes=passes)))
+                                     **({} if passes == 1 else dict(passes=passes)),
+                                     **({} if partitions == 1 else dict(partitions=partitions)))
     return vectors_to_report(*vectors, rgs)

@@ -28,6 +28,18 @@ key whose bits were all in `seen` before); the count then skips every window tha
 negatives, so every k-mer seen twice or more is counted exactly and the output is byte-identical; the table, sized from the
 filter's `admitted` counter, is several times smaller.  h[1] of a filtered table counts only the once-seen keys the filter let
 through, so min_count must be >= 2.
+
+Partitions (`partitions=P`, `kbbq correct --partitions P|auto`, one process): the count split in time.  THE RULE:
+part(key, P) = owner(key, P) (km_owner; kbbq_kmer_owner on the host).  For p = 0..P-1 the table -- 1/P the size -- is cleared
+(except before the first round) and counts, over ALL rows of the input, exactly the windows whose canonical key has part == p
+(kbbq_kmer_count*_part*).  A key lies in one partition, so its count there is its global count.  After each round
+hist += kmer_histogram(table), and the pairs with count >= keep (select(table, 1, keep)) join the kept pairs on the device;
+keep is min_count when given, else 2, the smallest value solid_threshold can return.  After the last round t is min_count or
+solid_threshold(hist), the partition table is freed, ALL kept pairs are merged into a solid table of
+default_slots(len(kept), budget) (those with keep <= count < t too: no decision reads them, and dropping them would cost a
+pass over the pairs) and the unchanged correct / flag kernels run against it at min_count = t.  The summed histogram (with the
+prefilter: h[2:]), the threshold, every base's decision and every figure printed are those of the one-table path; every round
+hashes every window, which is what the smaller table costs.  count_partitioned is the one statement of it in code.
 """
 import ctypes
 import os
@@ -90,6 +102,76 @@ def filter_words(total, bits=4):
     while words * 64 < bits * total:
         words *= 2
     return words
+
+
+MAX_PARTITIONS = 64                   # of one run (the kernels take up to MAX_BUCKETS)
+
+
+def check_partitions(partitions):
+    """`partitions` as an int in 1..MAX_PARTITIONS or the string 'auto', else ValueError: checked before any device call."""
+    if isinstance(partitions, str):
+        if partitions == 'auto':
+            return partitions
+    elif not isinstance(partitions, bool):
+        try:
+            if int(partitions) == partitions and 1 <= int(partitions) <= MAX_PARTITIONS:
+                return int(partitions)
+        except (TypeError, ValueError):
+            pass
+    raise ValueError("partitions must be an integer in 1..%d or 'auto', got %r" % (MAX_PARTITIONS, partitions))
+
+
+def _wanted_slots(total):
+    """The table for `total` keys at a load factor of at most 0.5, whatever the budget."""
+    want = MIN_SLOTS
+    while want * LOAD_FACTOR < total:
+        want *= 2
+    return want
+
+
+def partition_windows(total, P):
+    """What the table of one of P > 1 partitions is sized for: total / P and the slack of 9/8 that count_kmers_ranks gives owner
+    tables (the partitions are as even as a hash makes them), rounded up."""
+    return -(-int(total) * 9 // (8 * int(P)))
+
+
+def partition_slots(total, P, budget):
+    """The default table of one of P > 1 partitions of `total` windows (with the prefilter: admitted keys): half the budget is
+    its, the other half is for the kept pairs and the solid table."""
+    return default_slots(partition_windows(total, P), int(budget) // 2)
+
+
+def partitions_for(total, budget):
+    """The smallest P in 1..MAX_PARTITIONS whose default per-partition table fits half the budget uncapped (P = 1: `total` at a
+    load factor of 0.5, without slack).  ValueError when MAX_PARTITIONS do not suffice."""
+    total, half = int(total), int(budget) // 2
+    for P in range(1, MAX_PARTITIONS + 1):
+        if _wanted_slots(total if P == 1 else partition_windows(total, P)) * SLOT_BYTES <= half:
+            return P
+    raise ValueError('%d k-mer windows do not fit half the device budget of %d bytes (KBBQ_DEVICE_BUDGET) even in %d partitions '
+                     '(a table of %d bytes each)' % (total, int(budget), MAX_PARTITIONS,
+                                                     _wanted_slots(partition_windows(total, MAX_PARTITIONS)) * SLOT_BYTES))
+
+
+def resolve_partitions(partitions, total, budget):
+    """The number of rounds: `partitions` itself, or partitions_for(total, budget) for 'auto'."""
+    return partitions_for(total, budget) if partitions == 'auto' else int(partitions)
+
+
+def _check_partitions(partitions, launched=False):
+    """check_partitions, and the refusal of anything but 1 in a process group (`launched`: under a launcher whose group does not
+    exist yet): before any work on the GPU and, under ranks, before any collective."""
+    partitions = check_partitions(partitions)
+    if partitions != 1 and (launched or _ranks() is not None):
+        raise ValueError('partitions do not run across ranks: the owner tables of a process group already split the k-mers W ways '
+                         '(every rank holds the keys it owns), and a rank counts its own reads in rounds through a smaller table '
+                         'with --local-slots; run without --partitions, or on one GPU')
+    return partitions
+
+
+def _partitions_kw(partitions):
+    """The keyword for a callee: none at partitions = 1, whose calls are the ones they were before the option."""
+    return dict(partitions=partitions) if partitions != 1 else {}
 
 
 def _on_device(x):
@@ -283,12 +365,25 @@ def _full(table, exc):
                            % (exc, table.slots))
 
 
-def count_kmers(seq_plane, meta, k=31, slots=None, table=None, filter=None):
+def _check_part(parts, part):
+    parts, part = int(parts), int(part)
+    if not 1 <= parts <= MAX_BUCKETS:
+        raise ValueError('parts must be in 1..%d, got %d' % (MAX_BUCKETS, parts))
+    if not 0 <= part < parts:
+        raise ValueError('part must be in 0..%d, got %d' % (parts - 1, part))
+    return parts, part
+
+
+def count_kmers(seq_plane, meta, k=31, slots=None, table=None, filter=None, parts=1, part=0):
     """Count every k-mer of the rows into `table` (a new one of `slots` slots when None; default: kmer_total at a load factor
     of at most 0.5, capped by the device budget) and return it.  Counting adds: several calls compose.  A table that fills
     raises KmerTableFull.  With `filter` (a KmerFilter that has seen all the rows, prefilter_kmers) only the k-mers in its
-    `twice` array are counted, and the default table is sized from filter.admitted instead of kmer_total."""
+    `twice` array are counted, and the default table is sized from filter.admitted instead of kmer_total.  With parts = P > 1
+    only the windows whose key has owner(key, P) == part are counted (kbbq_kmer_count*_part*); parts = 1 is the call without."""
     from . import _device as dev
+    parts, part = _check_part(parts, part)
+    if parts > 1:
+        return _count_kmers_part(seq_plane, meta, k, slots, table, filter, parts, part)
     n, pitch = int(seq_plane.shape[0]), int(seq_plane.shape[1])
     if table is None:
         if slots is None:
@@ -312,6 +407,35 @@ def count_kmers(seq_plane, meta, k=31, slots=None, table=None, filter=None):
                 N.check(lib.kbbq_kmer_count_filtered(ctx.handle, table.handle, filter.handle, N.ptr(seq_plane), N.ptr(meta), n, pitch))
             else:
                 N.check(lib.kbbq_kmer_count(ctx.handle, table.handle, N.ptr(seq_plane), N.ptr(meta), n, pitch))
+    except N.KmerTableFull as exc:
+        raise _full(table, exc) from None
+    return table
+
+
+def _count_kmers_part(seq_plane, meta, k, slots, table, filter, parts, part):
+    """count_kmers for one partition: the same table, sizes and errors through the _part calls."""
+    from . import _device as dev
+    n, pitch = int(seq_plane.shape[0]), int(seq_plane.shape[1])
+    if table is None:
+        if slots is None:
+            total = filter.admitted if filter is not None else kmer_total(_host_meta(meta), k)
+            slots = default_slots(total, dev.device_budget())
+        table = KmerTable(k, slots)
+    lib = N.load()
+    ctx = table.ctx
+    on_device = _on_device(seq_plane)
+    if not on_device:
+        seq_plane = np.ascontiguousarray(seq_plane, dtype=np.uint8)
+        meta = np.ascontiguousarray(meta, dtype=np.uint32)
+    rows = (N.ptr(seq_plane), N.ptr(meta), n, pitch, parts, part)
+    try:
+        if filter is not None:
+            N.check((lib.kbbq_kmer_count_filtered_part_dev if on_device else lib.kbbq_kmer_count_filtered_part)(
+                ctx.handle, table.handle, filter.handle, *rows))
+        else:
+            N.check((lib.kbbq_kmer_count_part_dev if on_device else lib.kbbq_kmer_count_part)(ctx.handle, table.handle, *rows))
+        if on_device:
+            ctx.status()
     except N.KmerTableFull as exc:
         raise _full(table, exc) from None
     return table
@@ -492,10 +616,12 @@ def prefilter_batch(batch, k, filter=None, bits=4):
     return filter
 
 
-def count_batch(batch, k=31, table=None, slots=None, filter=None):
+def count_batch(batch, k=31, table=None, slots=None, filter=None, parts=1, part=0):
     """count_kmers for the rows of a device batch in whatever layout it has: the reads are counted where they lie.  Keys and
-    counts are those of the character planes of the same reads, so batches of different layouts compose in one table."""
+    counts are those of the character planes of the same reads, so batches of different layouts compose in one table.
+    parts, part: as count_kmers' (kbbq_kmer_count*_rows_part_dev)."""
     from . import _device as dev
+    parts, part = _check_part(parts, part)
     if table is None:
         if slots is None:
             slots = default_slots(filter.admitted if filter is not None else batch_windows(batch, k), dev.device_budget())
@@ -504,7 +630,12 @@ def count_batch(batch, k=31, table=None, slots=None, filter=None):
     lib = N.load()
     ctx = table.ctx
     try:
-        if filter is not None:
+        if parts > 1 and filter is not None:
+            N.check(lib.kbbq_kmer_count_filtered_rows_part_dev(ctx.handle, table.handle, filter.handle, seq, meta, n, pitch, flags,
+                                                               parts, part))
+        elif parts > 1:
+            N.check(lib.kbbq_kmer_count_rows_part_dev(ctx.handle, table.handle, seq, meta, n, pitch, flags, parts, part))
+        elif filter is not None:
             N.check(lib.kbbq_kmer_count_filtered_rows_dev(ctx.handle, table.handle, filter.handle, seq, meta, n, pitch, flags))
         else:
             N.check(lib.kbbq_kmer_count_rows_dev(ctx.handle, table.handle, seq, meta, n, pitch, flags))
@@ -549,6 +680,11 @@ def correct_batch(table, batch, min_count, fix_n=False, passes=1, skip_unresolve
     return changed[:n]
 
 
+def partitions_field(info):
+    """` partitions=P` of a command's stderr line when its count took P > 1 rounds, else nothing."""
+    return ' partitions=%d' % info['partitions'] if info.get('partitions', 1) > 1 else ''
+
+
 def _passes_kw(passes):
     """The keyword for a callee: none at passes = 1, whose calls are the ones they were before the option."""
     return dict(passes=passes) if passes != 1 else {}
@@ -565,7 +701,47 @@ def _check_prefilter(min_count, filter_bits):
                          'once, so the filter belongs at the rank that owns the key; run on one GPU, or without the prefilter')
 
 
-def correct_reads(seq_plane, meta, k=31, min_count=None, slots=None, prefilter=False, filter_bits=4, fix_n=False, passes=1):
+def count_partitioned(count_round, k, P, slots, min_count, budget):
+    """The rule of the module docstring's "Partitions", shared by the four commands.  count_round(table, p) counts partition p
+    of P of the WHOLE input (a plane, or every band's rows) into `table`; `slots` is the per-partition table, `budget` what
+    the solid table may take.  Returns (solid table, hist, t, info): the table the correct / flag kernels read at
+    min_count = t, the histogram summed over the rounds, and info = {'partitions', 'slots', 'table_bytes' (the per-partition
+    table), 'kept_pairs', 'solid_slots'}.  A round whose table fills raises count_round's KmerTableFull."""
+    P = int(P)
+    if min_count is not None and int(min_count) < 1:
+        raise ValueError('min_count must be >= 1, got %d' % int(min_count))
+    keep = int(min_count) if min_count is not None else 2
+    hist = np.zeros(HIST, dtype=np.int64)
+    kept = []                                # (keys, counts) of every round, on the device
+    table = KmerTable(k, slots)
+    try:
+        info = dict(partitions=P, slots=table.slots, table_bytes=table.nbytes)
+        for p in range(P):
+            if p:
+                table.clear()
+            count_round(table, p)
+            hist += kmer_histogram(table)
+            keys, counts, _ = select(table, 1, keep)
+            if int(keys.shape[0]):
+                kept.append((keys, counts))
+            del keys, counts
+    finally:
+        table.close()
+    t = int(min_count) if min_count is not None else solid_threshold(hist)
+    npairs = sum(int(keys.shape[0]) for keys, _ in kept)
+    solid = KmerTable(k, default_slots(npairs, budget))
+    try:
+        for keys, counts in kept:
+            merge(solid, keys, counts)
+    except BaseException:
+        solid.close()
+        raise
+    info.update(kept_pairs=npairs, solid_slots=solid.slots)
+    return solid, hist, t, info
+
+
+def correct_reads(seq_plane, meta, k=31, min_count=None, slots=None, prefilter=False, filter_bits=4, fix_n=False, passes=1,
+                  partitions=1):
     """Count, pick the threshold (min_count, else the histogram's first valley) and correct.  Returns (corrected plane in
     the input's layout and kind, info) with info = {'k', 'min_count', 'hist', 'changed' (per read), 'slots', 'table_bytes',
     'prefilter', 'filter_bytes', 'admitted', 'fix_n', 'passes'}.  passes: the rule applied that many times to each row against
@@ -573,8 +749,14 @@ def correct_reads(seq_plane, meta, k=31, min_count=None, slots=None, prefilter=F
     prefilter only keeps keys of count 1 out, and the rule asks for count >= min_count >= 2 then).  With `prefilter` a KmerFilter of `filter_bits` bits per k-mer window and array
     keeps most k-mers seen once out of the table: the same plane, threshold and hist[2:]; hist[1] is the number of once-seen
     k-mers that got in; the table, unless `slots` is given, is sized from the filter's `admitted` after `seen` is freed;
-    min_count must be >= 2.  filter_bytes is the filter's size during its pass (both arrays); admitted is None without."""
+    min_count must be >= 2.  filter_bytes is the filter's size during its pass (both arrays); admitted is None without.
+    partitions = P > 1, or 'auto' where partitions_for gives more than 1 (count_partitioned): the k-mers are counted in P rounds
+    through a table of `slots` slots (default: partition_slots of the windows -- of `admitted` with the prefilter, whose `twice`
+    array lives through all rounds -- in the device budget) and the reads corrected against the solid table of the kept pairs:
+    the same plane, changed, min_count and hist (hist[2:] with the prefilter).  info then has 'partitions', 'kept_pairs' and
+    'solid_slots' too, and 'slots' / 'table_bytes' describe the per-partition table.  P = 1 is the path without the option."""
     passes = check_passes(passes)
+    partitions = _check_partitions(partitions)
     filt = None
     filter_bytes, admitted = 0, None
     if prefilter:
@@ -585,16 +767,30 @@ def correct_reads(seq_plane, meta, k=31, min_count=None, slots=None, prefilter=F
         if filt is not None:
             filter_bytes, admitted = filt.nbytes, filt.admitted
             filt.release_seen()
-        table = count_kmers(seq_plane, meta, k=k, slots=slots, filter=filt)
-        if filt is not None:
-            filt.close()
-        hist = kmer_histogram(table)
-        t = int(min_count) if min_count is not None else solid_threshold(hist)
+        P, more = 1, {}
+        if partitions != 1:
+            from . import _device as dev
+            total = admitted if filt is not None else kmer_total(_host_meta(meta), k)
+            budget = dev.device_budget()
+            P = resolve_partitions(partitions, total, budget)
+        if P > 1:
+            table, hist, t, more = count_partitioned(
+                lambda tab, p: count_kmers(seq_plane, meta, k=k, table=tab, filter=filt, parts=P, part=p), k, P,
+                slots if slots is not None else partition_slots(total, P, budget), min_count, budget)
+            if filt is not None:
+                filt.close()
+        else:
+            table = count_kmers(seq_plane, meta, k=k, slots=slots, filter=filt)
+            if filt is not None:
+                filt.close()
+            hist = kmer_histogram(table)
+            t = int(min_count) if min_count is not None else solid_threshold(hist)
         if t < 1:
             raise ValueError('min_count must be >= 1, got %d' % t)
         out, changed = correct_with(table, seq_plane, meta, t, fix_n=fix_n, **_passes_kw(passes))
-        return out, dict(k=table.k, min_count=t, hist=hist, changed=changed, slots=table.slots, table_bytes=table.nbytes,
-                         prefilter=bool(prefilter), filter_bytes=filter_bytes, admitted=admitted, fix_n=bool(fix_n), passes=passes)
+        return out, dict(dict(k=table.k, min_count=t, hist=hist, changed=changed, slots=table.slots, table_bytes=table.nbytes,
+                              prefilter=bool(prefilter), filter_bytes=filter_bytes, admitted=admitted, fix_n=bool(fix_n),
+                              passes=passes), **more)
     finally:
         if filt is not None:
             filt.close()
@@ -603,11 +799,12 @@ def correct_reads(seq_plane, meta, k=31, min_count=None, slots=None, prefilter=F
 
 
 def correct_fastq(path, out, k=31, min_count=None, slots=None, local_slots=None, prefilter=False, filter_bits=4, fix_n=False,
-                  passes=1):
+                  passes=1, partitions=1):
     """Correct every read of a FASTQ file (plain or .gz) and write '@' + name, the corrected sequence, '+' and the qualities
     as read to `out` (a path, or a text stream).  Returns correct_reads' info.  In a process group of several ranks (or of
-    one with KBBQ_DIST_ALWAYS=1) this is correct_fastq_ranks, which has no prefilter."""
+    one with KBBQ_DIST_ALWAYS=1) this is correct_fastq_ranks, which has no prefilter and no partitions."""
     passes = check_passes(passes)
+    partitions = _check_partitions(partitions)
     if prefilter:
         _check_prefilter(min_count, filter_bits)
     if _ranks() is not None:
@@ -623,7 +820,7 @@ def correct_fastq(path, out, k=31, min_count=None, slots=None, local_slots=None,
     finally:
         fq.close()
     fixed, info = correct_reads(seq, meta, k=k, min_count=min_count, slots=slots, prefilter=prefilter, filter_bits=filter_bits,
-                                fix_n=fix_n, **_passes_kw(passes))
+                                fix_n=fix_n, **_passes_kw(passes), **_partitions_kw(partitions))
     text = fastx.format_fastq(names, fixed, qual, meta & 0xFFFF)
     if isinstance(out, str):
         with open(out, 'w', encoding='latin-1', newline='') as fh:
@@ -636,17 +833,19 @@ def correct_fastq(path, out, k=31, min_count=None, slots=None, local_slots=None,
 
 
 def main_correct(path, output=None, k=31, min_count=None, slots=None, local_slots=None, prefilter=False, filter_bits=4, fix_n=False,
-                 passes=1):
+                 passes=1, partitions=1):
     """`kbbq correct`: the corrected FASTQ to `output` or stdout; the threshold and the changed bases to stderr (once, by rank
-    0, with the figures of all ranks); with fix_n ` fix_n=1`; with passes = P > 1 ` passes=P`; with the prefilter also the
-    admitted k-mers and the table's slots."""
+    0, with the figures of all ranks); with fix_n ` fix_n=1`; with passes = P > 1 ` passes=P`; with more than one partition
+    (given, or resolved from 'auto') ` partitions=P`; with the prefilter also the admitted k-mers and the table's slots."""
     passes = check_passes(passes)                        # every rank refuses, before its first collective
+    partitions = _check_partitions(partitions)           # ... this too: a process group takes no partitions
     if prefilter:
         _check_prefilter(min_count, filter_bits)         # every rank refuses, before its first collective
     ranks = _ranks()
     if ranks is None:
         info = correct_fastq(path, output if output else sys.stdout, k=k, min_count=min_count, slots=slots,
-                             prefilter=prefilter, filter_bits=filter_bits, fix_n=fix_n, **_passes_kw(passes))
+                             prefilter=prefilter, filter_bits=filter_bits, fix_n=fix_n, **_passes_kw(passes),
+                             **_partitions_kw(partitions))
         changed = int(np.asarray(info['changed'], dtype=np.int64).sum())
     else:
         try:
@@ -664,9 +863,9 @@ def main_correct(path, output=None, k=31, min_count=None, slots=None, local_slot
         changed = info['changed_bases']
         if ranks[1] != 0:
             return info
-    sys.stderr.write('kbbq correct: k=%d min_count=%d reads=%d changed_bases=%d%s%s%s\n'
+    sys.stderr.write('kbbq correct: k=%d min_count=%d reads=%d changed_bases=%d%s%s%s%s\n'
                      % (info['k'], info['min_count'], info['reads'], changed, ' fix_n=1' if fix_n else '',
-                        ' passes=%d' % passes if passes > 1 else '',
+                        ' passes=%d' % passes if passes > 1 else '', partitions_field(info),
                         ' prefilter=1 admitted=%d slots=%d' % (info['admitted'], info['slots']) if prefilter else ''))
     return info
 

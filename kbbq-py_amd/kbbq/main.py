@@ -24,6 +24,26 @@ def _passes(text):
     return value
 
 
+def _partitions(text):
+    """--partitions P|auto: an integer in 1..64, or the word auto (kmer.check_partitions)."""
+    if text == 'auto':
+        return text
+    try:
+        value = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError("%r is neither an integer nor 'auto'" % text) from None
+    if not 1 <= value <= 64:
+        raise argparse.ArgumentTypeError('must be in 1..64, got %d' % value)
+    return value
+
+
+_PARTITIONS_HELP = ('%s: count the k-mers in this many rounds, 1..64 (default 1), each over all reads and for one hash partition of '
+                    'the k-mers, through a table 1/P the size (--slots, where given, is that table); the k-mers that can be '
+                    'solid are kept after each round and the reads are corrected against them: the same output, every round '
+                    'hashes every k-mer.  auto: the fewest rounds whose table fits half the device budget (KBBQ_DEVICE_BUDGET).  One GPU '
+                    'only: a process group splits the k-mers over its ranks already (correct --local-slots)')
+
+
 _PASSES_HELP = ('%s: apply the k-mer rule to its own output this many times, 1..8 (default 1), read by read against the one table '
                 'counted from the reads as read: an error next to a read end or to another error is corrected once its '
                 'neighbour is')
@@ -45,8 +65,13 @@ def recalibrate(args):
             kopts['passes'] = args.passes
         if args.skip_unresolved:
             kopts['skip_unresolved'] = True
+        more = {}
+        if args.partitions is not None:
+            kopts['partitions'] = args.partitions
+            more = dict(partitions=args.partitions)
         # every rank of a launcher refuses here, before it joins the process group
-        _recal.check_corrected(args.correct, args.gatkreport, kopts['k'], kopts['min_count'], kopts['prefilter'], kopts['filter_bits'])
+        _recal.check_corrected(args.correct, args.gatkreport, kopts['k'], kopts['min_count'], kopts['prefilter'], kopts['filter_bits'],
+                               **more)
     world, _ = parallel.init_from_env()          # one process per GPU under torch.distributed.run; no-op otherwise
     if world == 1 and 'torch' not in __import__('sys').modules and not os.environ.get('KBBQ_USE_TORCH'):
         # one GPU: nothing of PyTorch is needed -- device memory, page-locked slabs, copies and events come from the library's
@@ -63,11 +88,12 @@ def recalibrate(args):
         with stage('[recalibrate_corrected, wall]'):
             info = _recal.recalibrate_corrected(args.correct, infer_rg=args.infer_rg, gatkreport=args.gatkreport, output=args.output,
                                                 **kopts)
-        sys.stderr.write('kbbq recalibrate: k=%d min_count=%d reads=%d changed_bases=%d%s%s%s%s\n'
+        from .kmer import partitions_field
+        sys.stderr.write('kbbq recalibrate: k=%d min_count=%d reads=%d changed_bases=%d%s%s%s%s%s\n'
                          % (info['k'], info['min_count'], info['reads'], info['changed_bases'],
                             ' skipped_bases=%d' % info['skipped_bases'] if kopts.get('skip_unresolved') else '',
                             ' fix_n=1' if kopts.get('fix_n') else '',
-                            ' passes=%d' % kopts['passes'] if kopts.get('passes', 1) > 1 else '',
+                            ' passes=%d' % kopts['passes'] if kopts.get('passes', 1) > 1 else '', partitions_field(info),
                             ' prefilter=1 admitted=%d slots=%d' % (info['admitted'], info['slots']) if kopts['prefilter'] else ''))
         return
     _recal.recalibrate(bam=args.bam, fastq=args.fastq, infer_rg=args.infer_rg,
@@ -84,6 +110,8 @@ def benchmark(args):
                                 prefilter=args.prefilter, filter_bits=4 if args.filter_bits is None else args.filter_bits))
         if args.passes is not None:
             kmers['kmers']['passes'] = args.passes
+        if args.partitions is not None:
+            kmers['kmers']['partitions'] = args.partitions
     _bm.benchmark(bamfile=args.bam, fafile=args.reference, vcffile=args.vcf, fastqfile=args.fastq,
                   label=args.label, use_oq=args.use_oq, bedfh=args.bedfile, **kmers)
 
@@ -109,14 +137,16 @@ def bqsr(args):
         info = {}
         skip = dict(skip_unresolved=True) if args.skip_unresolved else {}      # without the flag the call is what it was
         more = dict(passes=args.passes) if args.passes is not None else {}     # ... and without this option
+        if args.partitions is not None:
+            more['partitions'] = args.partitions
         _bqsr.bam_to_report_kmers(aln.AlignmentFile(args.bam), k=31 if args.kmer is None else args.kmer, min_count=args.min_count,
                                   slots=args.slots, prefilter=args.prefilter,
                                   filter_bits=4 if args.filter_bits is None else args.filter_bits, use_oq=args.use_oq,
                                   info=info, **skip, **more).write(args.gatkreport)
-        sys.stderr.write('kbbq bqsr: k=%d min_count=%d reads=%d flagged_bases=%d%s%s%s\n'
+        sys.stderr.write('kbbq bqsr: k=%d min_count=%d reads=%d flagged_bases=%d%s%s%s%s\n'
                          % (info['k'], info['min_count'], info['reads'], info['flagged_bases'],
                             ' skipped_bases=%d' % info['skipped_bases'] if skip else '',
-                            ' passes=%d' % args.passes if (args.passes or 1) > 1 else '',
+                            ' passes=%d' % args.passes if (args.passes or 1) > 1 else '', kmer.partitions_field(info),
                             ' prefilter=1 admitted=%d slots=%d' % (info['admitted'], info['slots']) if args.prefilter else ''))
         return
     from . import benchmark as _bm
@@ -137,6 +167,8 @@ def correct(args):
         from . import _device
         _device.use_native_memory()          # as `recalibrate` on one GPU: no torch import
     more = dict(passes=args.passes) if args.passes is not None else {}         # without the option the call is what it was
+    if args.partitions is not None:
+        more['partitions'] = args.partitions
     kmer.main_correct(args.fastq, output=args.output, k=args.kmer, min_count=args.min_count, slots=args.slots,
                       local_slots=args.local_slots, prefilter=args.prefilter, filter_bits=args.filter_bits, fix_n=args.fix_n, **more)
 
@@ -172,6 +204,7 @@ def main(argv=None):
                     help='with -c: give every N the letter that makes the most of the k-mers it alone breaks solid (as `kbbq '
                          'correct --fix-n`)')
     rp.add_argument('--passes', type=_passes, default=None, metavar='P', help=_PASSES_HELP % 'with -c')
+    rp.add_argument('--partitions', type=_partitions, default=None, metavar='P|auto', help=_PARTITIONS_HELP % 'with -c')
     rp.add_argument('--skip-unresolved', action='store_true',
                     help='with -c: leave a base out of the tally (neither error nor observation) when the k-mers contradict it but '
                          'name no replacement -- two errors within k bases, thin coverage, contamination -- instead of counting '
@@ -216,6 +249,7 @@ def main(argv=None):
     bp.add_argument('--filter-bits', type=int, default=None,
                     help='with --kmers --prefilter: bits per k-mer of the input in each of the filter\'s two arrays, 1..64 (default 4)')
     bp.add_argument('--passes', type=_passes, default=None, metavar='P', help=_PASSES_HELP % 'with --kmers')
+    bp.add_argument('--partitions', type=_partitions, default=None, metavar='P|auto', help=_PARTITIONS_HELP % 'with --kmers')
     bp.set_defaults(command=benchmark)
 
     ap = sub.add_parser('applybqsr', description='Recalibrate alignments with a GATK recalibration report (SAM output)')
@@ -255,6 +289,7 @@ def main(argv=None):
                          'it but name no replacement -- two errors within k bases, thin coverage, contamination -- instead of '
                          'counting it as correct')
     qp.add_argument('--passes', type=_passes, default=None, metavar='P', help=_PASSES_HELP % 'with --kmers')
+    qp.add_argument('--partitions', type=_partitions, default=None, metavar='P|auto', help=_PARTITIONS_HELP % 'with --kmers')
     qp.set_defaults(command=bqsr)
 
     cp = sub.add_parser('correct', description='Correct substitution errors of a FASTQ file with k-mer counts (GPU); the output '
@@ -281,6 +316,7 @@ def main(argv=None):
                     help='give every N the letter (A, C, G or T) that makes the most of the k-mers it alone breaks solid; an N '
                          'stays N on a tie or when no letter makes a solid k-mer; a fixed N counts as a changed base')
     cp.add_argument('--passes', type=_passes, default=None, metavar='P', help=_PASSES_HELP % 'the whole rule (with --fix-n the N rule too)')
+    cp.add_argument('--partitions', type=_partitions, default=None, metavar='P|auto', help=_PARTITIONS_HELP % 'one GPU')
     cp.add_argument('-o', '--output', default=None,
                     help='Write the corrected FASTQ to this file instead of stdout; under torch.distributed.run every rank '
                          'writes FILE.rankNNNN, to be concatenated in rank order.')
@@ -291,7 +327,8 @@ def main(argv=None):
         given = [flag for flag, v in (('-k/--kmer', args.kmer), ('--min-count', args.min_count), ('--slots', args.slots),
                                       ('--prefilter', args.prefilter or None), ('--filter-bits', args.filter_bits),
                                       ('--fix-n', args.fix_n or None), ('--passes', args.passes),
-                                      ('--skip-unresolved', args.skip_unresolved or None)) if v is not None]
+                                      ('--skip-unresolved', args.skip_unresolved or None),
+                                      ('--partitions', args.partitions)) if v is not None]
         if given:
             rp.error('%s: only with -c/--correct' % ', '.join(given))
     if args.command is benchmark:
@@ -301,7 +338,7 @@ def main(argv=None):
         else:
             given = [flag for flag, v in (('-k/--kmer', args.kmer), ('--min-count', args.min_count), ('--slots', args.slots),
                                           ('--prefilter', args.prefilter or None), ('--filter-bits', args.filter_bits),
-                                          ('--passes', args.passes)) if v is not None]
+                                          ('--passes', args.passes), ('--partitions', args.partitions)) if v is not None]
             if given:
                 bp.error('%s: only with --kmers' % ', '.join(given))
     if args.command is bqsr:
@@ -313,7 +350,8 @@ def main(argv=None):
             given = [flag for flag, v in (('-k/--kmer', args.kmer), ('--min-count', args.min_count), ('--slots', args.slots),
                                           ('--prefilter', args.prefilter or None), ('--filter-bits', args.filter_bits),
                                           ('-u/--use-oq', args.use_oq or None),
-                                          ('--skip-unresolved', args.skip_unresolved or None), ('--passes', args.passes))
+                                          ('--skip-unresolved', args.skip_unresolved or None), ('--passes', args.passes),
+                                          ('--partitions', args.partitions))
                      if v is not None]
             if given:
                 qp.error('%s: only with --kmers' % ', '.join(given))

@@ -370,9 +370,10 @@ TWO_COMMANDS = ('run the two commands instead: `kbbq correct -f reads.fq -o read
                 '`kbbq recalibrate -f reads.fq reads.cor.fq`')
 
 
-def check_corrected(path, gatkreport=None, k=31, min_count=None, prefilter=False, filter_bits=4):
+def check_corrected(path, gatkreport=None, k=31, min_count=None, prefilter=False, filter_bits=4, partitions=1):
     """What recalibrate_corrected refuses, before any device work and, under a launcher, before the process group exists."""
     from . import kmer
+    kmer._check_partitions(partitions, launched=parallel.launched_from_env())
     if not 8 <= int(k) <= 32:
         raise ValueError('k must be in 8..32, got %d' % int(k))
     if min_count is not None and int(min_count) < 1:
@@ -392,7 +393,7 @@ def check_corrected(path, gatkreport=None, k=31, min_count=None, prefilter=False
 
 
 def recalibrate_corrected(path, infer_rg=False, gatkreport=None, output=None, k=31, min_count=None, slots=None, prefilter=False,
-                          filter_bits=4, fix_n=False, passes=1, skip_unresolved=False):
+                          filter_bits=4, fix_n=False, passes=1, skip_unresolved=False, partitions=1):
     """`kbbq correct` and `kbbq recalibrate -f reads corrected` in one run over ONE file: the reads go to the device once, in
     the layout pass 2 uses (fastx.pack_single), their k-mers are counted and the reads corrected where they lie
     (kmer.count_batch / correct_batch: the corrected plane is each band's cseq), and the tally, the solve, the apply and the
@@ -408,14 +409,18 @@ def recalibrate_corrected(path, infer_rg=False, gatkreport=None, output=None, k=
     solve, K2 and the writer see the qualities as read; the planes (one n x pitch per band) are released before the apply.
     info['skipped_bases']: the unresolved bases of all reads.  The output is that of `recalibrate -f reads corrected` with the
     model tallied from a reads file whose unresolved bases have quality '!'.
+    partitions: `kbbq correct --partitions` (kmer.count_partitioned): every round counts every band's rows for one partition of the
+    k-mers through a table of `slots` slots (default: kmer.partition_slots within what the budget leaves beside the reads), and
+    the table kept until the tally is over is the solid table, against which the bands -- those redone as character rows too --
+    are corrected.  The same bytes; info then carries partitions, kept_pairs and solid_slots, and slots is the per-partition table.
     One process, mapped inputs, reads that fit the device budget: anything else raises ValueError naming the two commands."""
     from . import kmer
     passes = kmer.check_passes(passes)
-    check_corrected(path, gatkreport, k, min_count, prefilter, filter_bits)
+    check_corrected(path, gatkreport, k, min_count, prefilter, filter_bits, **kmer._partitions_kw(partitions))
     done_with = []
     try:
         return _recalibrate_corrected(path, infer_rg, gatkreport, output, int(k), min_count, slots, prefilter, filter_bits, done_with,
-                                      bool(fix_n), passes, bool(skip_unresolved))
+                                      bool(fix_n), passes, bool(skip_unresolved), partitions)
     finally:
         for reader in done_with:
             fastx.close_later(reader)
@@ -427,7 +432,7 @@ def _batch_bytes(batch):
 
 
 def _recalibrate_corrected(path, infer_rg, gatkreport, output, k, min_count, slots, prefilter, filter_bits, done_with, fix_n=False,
-                           passes=1, skip=False):
+                           passes=1, skip=False, partitions=1):
     from . import kmer
     more = kmer._passes_kw(passes)
     if skip:
@@ -476,13 +481,23 @@ def _recalibrate_corrected(path, infer_rg, gatkreport, output, k, min_count, slo
                         kmer.prefilter_batch(r, k, filter=filt)
                     info['admitted'] = filt.admitted
                     filt.release_seen()
-            if slots is None:
-                slots = kmer.default_slots(info['admitted'] if prefilter else windows,
-                                           budget - resident - (filt.nbytes if filt is not None else 0))
-            with stage('k-mer count', sync=True):
-                table = kmer.KmerTable(k, slots)
-                for r in rows:
-                    kmer.count_batch(r, k, table=table, filter=filt)
+            total = info['admitted'] if prefilter else windows
+            room = budget - resident - (filt.nbytes if filt is not None else 0)
+            P = kmer.resolve_partitions(partitions, total, room) if partitions != 1 else 1
+            if P > 1:
+                def count_round(tab, p):
+                    for r in rows:
+                        kmer.count_batch(r, k, table=tab, filter=filt, parts=P, part=p)
+                with stage('k-mer count', sync=True):
+                    table, hist, t, parts_info = kmer.count_partitioned(
+                        count_round, k, P, slots if slots is not None else kmer.partition_slots(total, P, room), min_count, room)
+            else:
+                if slots is None:
+                    slots = kmer.default_slots(total, room)
+                with stage('k-mer count', sync=True):
+                    table = kmer.KmerTable(k, slots)
+                    for r in rows:
+                        kmer.count_batch(r, k, table=table, filter=filt)
         except (ValueError, dev.N.KmerTableFull) as exc:
             if 'slots' not in str(exc):
                 raise
@@ -491,9 +506,12 @@ def _recalibrate_corrected(path, infer_rg, gatkreport, output, k, min_count, slo
         if filt is not None:
             filt.close()
             filt = None
-        info['slots'] = table.slots
-        info['hist'] = hist = kmer.kmer_histogram(table)
-        t = int(min_count) if min_count is not None else kmer.solid_threshold(hist)
+        if P > 1:
+            info.update(parts_info, hist=hist)
+        else:
+            info['slots'] = table.slots
+            info['hist'] = hist = kmer.kmer_histogram(table)
+            t = int(min_count) if min_count is not None else kmer.solid_threshold(hist)
         info['min_count'] = t
         with stage('k-mer correct', sync=True):
             for r in rows:

@@ -24,7 +24,15 @@ of its plane); the leg fails unless its 1s are where the corrected plane of p pa
 With `--skip` every repetition also times kbbq_kmer_correct_rows_skip_dev (the corrected plane and, beside it, the tally plane of
 `recalibrate -c --skip-unresolved`: the qualities with byte 0 at every unresolved base) on the same character rows and table
 right after kbbq_kmer_correct_dev ("ms_correct_skip", "skipped_bases", "tally_plane_bytes"); the leg fails unless its corrected
-plane is kbbq_kmer_correct_dev's and its tally plane is the quality plane with as many bytes zeroed as d_unresolved adds up to."""
+plane is kbbq_kmer_correct_dev's and its tally plane is the quality plane with as many bytes zeroed as d_unresolved adds up to.
+With `--partitions P` (2..64) a leg on the same reads follows under the key "partitions" (`kbbq correct --partitions P`,
+kmer.count_partitioned spelt out call by call so that every step has its own events): per round kbbq_kmer_count_part_dev into
+the per-partition table (`--partition-slots`, default kmer.partition_slots of the windows in the device budget), the histogram
+and kbbq_kmer_select_*_dev of the pairs with count >= 2; then the merge of the kept pairs into the solid table and
+kbbq_kmer_correct_dev against it.  "ms_count_rounds" has the median of every round, "ms_count" their sum, and "peak_bytes" the
+device bytes at their peak, from the allocations made (kbbq_dev_mem_info for the library's, torch's count of live bytes for
+the kept pairs; planes excluded; "peak_bytes_merge": while the solid table is built); the leg fails unless its
+summed histogram, threshold and corrected plane equal the plain leg's."""
 import argparse
 import ctypes
 import json
@@ -52,12 +60,16 @@ ap.add_argument('--passes', type=int, default=1,
                 help='also time 2 .. P passes of the correct step in one launch (kbbq_kmer_correct_passes_dev) and as P launches')
 ap.add_argument('--skip', action='store_true',
                 help='also time the correct step that writes the tally plane beside the corrected one (kbbq_kmer_correct_rows_skip_dev)')
+ap.add_argument('--partitions', type=int, default=1, help='add the leg that counts in this many rounds (kbbq correct --partitions)')
+ap.add_argument('--partition-slots', type=int, default=0, help='slots of that leg\'s per-partition table')
 ap.add_argument('--n-rate', type=float, default=0.0, help='share of the bases set to N')
 args = ap.parse_args()
 if args.unresolved and not args.flags:
     ap.error('--unresolved: only with --flags')
 if not 1 <= args.passes <= 8:
     ap.error('--passes: 1..8')
+if not 1 <= args.partitions <= 64:
+    ap.error('--partitions: 1..64')
 
 import numpy as np
 import torch
@@ -303,4 +315,64 @@ if args.prefilter:
     assert torch.equal(out, plain_out), 'the prefiltered leg corrected differently'
     leg['singletons'] = int(plain_hist[1])
     res['prefilter'] = leg
+if args.partitions > 1:
+    from kbbq import _device as dev
+    P = args.partitions
+    plain_out = out2 if args.prefilter else out        # (the prefiltered leg checked out2 against the plain plane)
+    plain_hist, plain_t = (plain_hist, plain_t) if args.prefilter else (hist, t)
+    out = ping[0] if ping else torch.empty_like(seq)
+    budget = dev.device_budget()
+    qslots = args.partition_slots or kmer.partition_slots(windows, P, budget)
+    ms = {'count_rounds': [[] for _ in range(P)], 'histogram': [], 'select': [], 'merge': [], 'correct': []}
+    def held(ctx):
+        """Device bytes of the allocations made: the library's (the device's bytes in use less what torch has reserved) and the
+        live tensors (the kept pairs come from torch, which may serve them from segments it reserved long before)."""
+        return in_use(ctx) - torch.cuda.memory_reserved() + torch.cuda.memory_allocated()
+
+    for rep in range(args.reps + 1):
+        rep_base()
+        base = held(kmer._ctx())
+        table = kmer.KmerTable(k, qslots)
+        ctx = table.ctx
+        hsum, kept = np.zeros(257, dtype=np.int64), []
+        cs, hs, ss = [], 0.0, 0.0
+        peak = 0
+        for p in range(P):
+            if p:
+                table.clear()
+            cs.append(timed(lambda: N.check(lib.kbbq_kmer_count_part_dev(ctx.handle, table.handle, N.ptr(seq), N.ptr(meta), n, pitch,
+                                                                          P, p))))
+            ctx.status()
+            hs += timed(lambda: N.check(lib.kbbq_kmer_histogram_dev(ctx.handle, table.handle, N.ptr(dh))))
+            hsum += dh.cpu().numpy()
+            got = []
+            ss += timed(lambda: got.append(kmer.select(table, 1, 2)))
+            kept.append(got[0][:2])
+            peak = max(peak, held(ctx) - base)
+        table.close()
+        t = kmer.solid_threshold(hsum)
+        npairs = sum(int(a.shape[0]) for a, _ in kept)
+        solid = kmer.KmerTable(k, kmer.default_slots(npairs, budget))
+        torch.cuda.synchronize()
+        peak_solid = held(ctx) - base
+        peak = max(peak, peak_solid)
+        m = timed(lambda: [kmer.merge(solid, a, b) for a, b in kept])
+        del kept, got
+        x = timed(lambda: N.check(lib.kbbq_kmer_correct_dev(ctx.handle, solid.handle, N.ptr(seq), N.ptr(meta), n, pitch, t,
+                                                             N.ptr(out), None)))
+        solid_slots = solid.slots
+        solid.close()
+        if rep:
+            for p in range(P):
+                ms['count_rounds'][p].append(cs[p])
+            ms['histogram'].append(hs); ms['select'].append(ss); ms['merge'].append(m); ms['correct'].append(x)
+    leg = {'partitions': P, 'slots': qslots, 'table_bytes': int(lib.kbbq_kmer_table_bytes(qslots)), 'kept_pairs': npairs,
+           'solid_slots': solid_slots, 'solid_bytes': int(lib.kbbq_kmer_table_bytes(solid_slots)), 'peak_bytes': peak, 'peak_bytes_merge': peak_solid, 'min_count': t,
+           'ms_count_rounds': [round(float(np.median(v)), 3) for v in ms['count_rounds']]}
+    leg['ms_count'] = round(sum(leg['ms_count_rounds']), 3)
+    leg.update({'ms_' + key: round(float(np.median(ms[key])), 3) for key in ('histogram', 'select', 'merge', 'correct')})
+    leg['ms_correct_all'] = [round(v, 3) for v in ms['correct']]
+    assert t == plain_t and np.array_equal(hsum, plain_hist), 'the partitioned leg found another histogram'
+    assert torch.equal(out, plain_out), 'the partitioned leg corrected differently'
+    res['partitions'] = leg
 print(json.dumps(res))
