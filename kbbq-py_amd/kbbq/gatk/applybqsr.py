@@ -280,6 +280,56 @@ def _recalibrated_slabs(bam, model, rg_to_int, use_oq, minscore, lo, hi):
             raise stop
 
 
+def _resident_slabs(bam, model, rg_to_int, use_oq, minscore, lo, hi, resident):
+    """_recalibrated_slabs for alignments whose planes are on the device already (`resident`: gatk.bqsr._kmer_tally's -- seq and
+    source [n, pitch], and oq, the context plane, where records carry OQ tags and the source is QUAL): the same slabs, row
+    words, pass-through, errors and error order; kbbq_apply_aligned_dev reads the planes where they lie and only the output
+    plane of a slab crosses the bus."""
+    from .. import _device as dev
+    from .. import _native as N
+    mode, blob, R, Qt, S2 = model
+    b = bam.batch()
+    pitch = resident['pitch']
+    if pitch != max(16, (int(b.maxlen) + 15) // 16 * 16):
+        raise ValueError('resident planes of pitch %d for alignments of up to %d bases' % (pitch, int(b.maxlen)))
+    T = dev._torch()
+    d_seq, d_src, d_oq = resident['seq'], resident['source'], resident.get('oq')
+    ctx = d_blob = None
+    for first in range(lo, hi, _ROWS):
+        m = min(_ROWS, hi - first)
+        rows = _rows(bam, rg_to_int, R, use_oq, first, first + m)
+        stop = None
+        if isinstance(rows[1], Exception):                   # a record the reference would reject: the ones before it still run
+            k, stop = rows
+            if k > 0:
+                rows = _rows(bam, rg_to_int, R, use_oq, first, first + k)
+            m = k
+        if m > 0:
+            meta, passthrough = rows
+            has_oq = bool((b.oq_len[first:first + m] >= 0).any())
+            if ctx is None:
+                ctx = dev.context()
+                d_blob = T.from_numpy(blob).cuda()
+            d_meta = T.from_numpy(np.ascontiguousarray(meta).view(np.int32)).cuda()
+            d_out = T.empty((m, pitch), dtype=T.uint8, device='cuda')
+            ctx_plane = d_src if use_oq or not has_oq else d_oq
+            N.check(N.load().kbbq_apply_aligned_dev(ctx.handle, N.ptr(d_seq[first:first + m]), N.ptr(d_src[first:first + m]),
+                                                    N.ptr(ctx_plane[first:first + m]), N.ptr(d_meta), m, pitch, R, Qt, S2, minscore,
+                                                    N.ptr(d_blob), mode, N.ptr(d_out)))
+            try:
+                ctx.status()
+            except Exception as exc:
+                exc.read_index = first + max(getattr(exc, 'read_index', 0), 0)
+                raise
+            out = d_out.cpu().numpy()
+            if passthrough.any():
+                out[passthrough] = b.plane(1, pitch, first, m)[passthrough]
+            lens = np.where(passthrough, b.qual_len[first:first + m], b.qlen[first:first + m]).astype(np.int64)
+            yield first, m, out, lens
+        if stop is not None:
+            raise stop
+
+
 def recalibrate_alignments(bam, meanq, rgdq, qdq, posdq, dndq, rg_to_int, use_oq=True, minscore=6):
     """New qualities of every alignment of an aln.AlignmentFile (SAM or BAM) on the GPU (kbbq_apply_aligned), as one flat int
     array and offsets [n + 1]: alignment i's are quals[offsets[i]:offsets[i + 1]], equal to recalibrate_bamread(read_i, ...)
@@ -302,10 +352,11 @@ def recalibrate_alignments(bam, meanq, rgdq, qdq, posdq, dndq, rg_to_int, use_oq
 
 
 def write_alignments(bam, meanq, rgdq, qdq, posdq, dndq, rg_to_int, sink, use_oq=False, set_oq=False, minscore=6,
-                     rows=None, header=True):
+                     rows=None, header=True, resident=None):
     """Recalibrated SAM text of alignments rows = (lo, hi) (all by default) to the binary file `sink`: the header lines as read
     (header=True), then every alignment line as read with its QUAL replaced and, with set_oq, an OQ tag holding the QUAL as
-    read added where there is none (csrc/sam_host.cpp kbbq_sam_render)."""
+    read added where there is none (csrc/sam_host.cpp kbbq_sam_render).  resident: the alignments' planes where they are on the
+    device already (_resident_slabs), instead of filled and uploaded slab by slab."""
     import ctypes
     from .. import _native as N
     from .._egress import _Reserve
@@ -318,7 +369,9 @@ def write_alignments(bam, meanq, rgdq, qdq, posdq, dndq, rg_to_int, sink, use_oq
         text = ''.join(line + '\n' for line in bam.header).encode('latin-1')
         reserve.ahead(len(text))
         sink.write(text)
-    for first, m, out, _ in _recalibrated_slabs(bam, model, rg_to_int, use_oq, minscore, lo, hi):
+    slabs = (_recalibrated_slabs(bam, model, rg_to_int, use_oq, minscore, lo, hi) if resident is None else
+             _resident_slabs(bam, model, rg_to_int, use_oq, minscore, lo, hi, resident))
+    for first, m, out, _ in slabs:
         need = ctypes.c_size_t(0)
         N.check(lib.kbbq_sam_render(b._native, first, m, N.ptr(out), out.shape[1], int(bool(set_oq)), None, 0, ctypes.byref(need)))
         buf = np.empty(max(need.value, 1), dtype=np.uint8)
@@ -334,9 +387,13 @@ def report_model(bam, report_path):
     """A stored GATK report -> (meanq, rgdq, qdq, posdq, dndq, rg_to_int) for the read groups of bam's header (reference
     tests/test_gatk_applybqsr.py:123-134: the report names read groups by their PU)."""
     from .. import recaltable
+    return _report_model(bam, recaltable.RecalibrationReport.fromfile(report_path))
+
+
+def _report_model(bam, report):
+    """report_model of a report that has been parsed (from a file, or from the text one would hold: RecalibrationReport.fromtext)."""
     rg_to_pu = utils.get_rg_to_pu(bam)
     rg_to_int = {r: i for i, r in enumerate(rg_to_pu)}
-    report = recaltable.RecalibrationReport.fromfile(report_path)
     meanq, *vectors = table_to_vectors(report, list(rg_to_pu.values()))
     return (meanq,) + tuple(get_delta_qs(meanq, *vectors)) + (rg_to_int,)
 

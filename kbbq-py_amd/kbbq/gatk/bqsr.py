@@ -356,12 +356,24 @@ def bam_to_kmer_covariates(bamfileobj, k=31, min_count=None, slots=None, prefilt
     kbbq.kmer.partitions_for within what the budget leaves beside the resident planes) and the flags written against the solid
     table: the same vectors.  With more than one round `info` receives partitions, kept_pairs and solid_slots too, and its slots
     is the per-partition table.  Refused in a process group before the group's own refusal."""
-    from .. import _device as dev
-    from .. import _solve, fastx, kmer
+    from .. import kmer
     passes = kmer.check_passes(passes)
     partitions = kmer._check_partitions(partitions)
-    b, n, S = _kmer_inputs(bamfileobj, k, min_count, prefilter, filter_bits, use_oq, maxscore)
-    k = int(k)
+    inputs = _kmer_inputs(bamfileobj, k, min_count, prefilter, filter_bits, use_oq, maxscore)
+    return _kmer_tally(bamfileobj, inputs, int(k), min_count, slots, prefilter, filter_bits, use_oq, minscore, maxscore, info,
+                       skip_unresolved, passes, partitions)[0]
+
+
+def _kmer_tally(bamfileobj, inputs, k, min_count, slots, prefilter, filter_bits, use_oq, minscore, maxscore, info, skip_unresolved,
+                passes, partitions):
+    """bam_to_kmer_covariates past its refusals (`inputs`: what _kmer_inputs returned; passes and partitions checked): (the nine
+    vectors, resident).  `resident` is what the tally leaves on the device and the per-record arrays beside it, for a caller
+    that goes on with the same alignments (kbbq.recalibrate.recalibrate_bam): batch, n, S, pitch, the device planes seq and
+    source (QUAL, or OQ with use_oq), use_oq, rg_to_int, and planes / h2d_plane_bytes -- the names of the planes uploaded and
+    their bytes.  bam_to_kmer_covariates drops it."""
+    from .. import _device as dev
+    from .. import _solve, fastx, kmer
+    b, n, S = inputs
     T = dev._torch()
     rg_to_int = {rg: i for i, rg in enumerate(utils.get_rg_to_pu(bamfileobj))}
     R = max(len(rg_to_int), 1)
@@ -423,7 +435,9 @@ def bam_to_kmer_covariates(bamfileobj, k=31, min_count=None, slots=None, prefilt
             info.update(passes=passes)
         if P > 1:
             info.update(partitions=P, kept_pairs=parts_info['kept_pairs'], solid_slots=parts_info['solid_slots'])
-    return _solve.vectors_from_tables(*tables.to_host(), maxscore)
+    kept = dict(batch=b, n=n, S=S, pitch=pitch, seq=d_seq, source=d_qual, use_oq=bool(use_oq), rg_to_int=rg_to_int,
+                planes=['SEQ', 'OQ' if use_oq else 'QUAL'], h2d_plane_bytes=2 * n * pitch)
+    return _solve.vectors_from_tables(*tables.to_host(), maxscore), kept
 
 
 # the fixed argument table GATK expects to find (reference bqsr.py:263-281)

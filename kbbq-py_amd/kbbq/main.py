@@ -5,7 +5,8 @@ and the `benchmark` sub-command (reference kbbq/main.py:26-89).  `plot` is out o
 `bqsr` (alignments -> GATK report) and `applybqsr` (report -> recalibrated SAM) are this build's own: the reference has the
 functions (kbbq/gatk/bqsr.py, applybqsr.py) but no command for them.  So is `correct` (k-mer error correction, kbbq/kmer.py):
 the reference's tutorial leaves that step to an external corrector; `recalibrate -c FASTQ` is `correct` and `recalibrate -f` in
-one run over one file (kbbq/recalibrate.py recalibrate_corrected).
+one run over one file (kbbq/recalibrate.py recalibrate_corrected), and `recalibrate -b ALN --kmers` is `bqsr --kmers` and `applybqsr`
+in one run over one parse and one upload of the alignments (recalibrate_bam).
 """
 import argparse
 
@@ -52,9 +53,46 @@ _PASSES_HELP = ('%s: apply the k-mer rule to its own output this many times, 1..
 _ENDS_WITH_THE_COMMAND = False               # set by `python -m kbbq.main`: the process ends (main._leave) when the command has run
 
 
+def _recalibrate_bam_kmers(args):
+    """`recalibrate -b ALN --kmers`: `bqsr --kmers` and `applybqsr` in one run (kbbq/recalibrate.py recalibrate_bam)."""
+    import os
+    import sys
+    from . import kmer, parallel
+    kmers = dict(k=31 if args.kmer is None else args.kmer, min_count=args.min_count, slots=args.slots, prefilter=args.prefilter,
+                 filter_bits=4 if args.filter_bits is None else args.filter_bits)
+    if args.skip_unresolved:                     # without the flag or the option the call is the one without it, as `bqsr`'s
+        kmers['skip_unresolved'] = True
+    if args.passes is not None:
+        kmers['passes'] = args.passes
+    if args.partitions is not None:
+        kmers['partitions'] = args.partitions
+    # every rank of a launcher refuses here, before it joins the process group
+    _recal.check_bam_kmers(args.bam, args.gatkreport, args.output, kmers['k'], kmers['min_count'], kmers['prefilter'],
+                           kmers['filter_bits'], **{key: kmers[key] for key in ('partitions', 'passes') if key in kmers})
+    parallel.init_from_env()
+    from . import aln
+    from ._trace import stage
+    with stage('[recalibrate_bam, wall]'):
+        with stage('parse'):
+            bam = aln.AlignmentFile(args.bam)    # the one parse; what the records are refused for, before the device is touched
+        _recal.check_bam_records(bam, args.use_oq, kmers['k'], kmers['min_count'], kmers['prefilter'], kmers['filter_bits'])
+        if kmer._ranks() is None and 'torch' not in sys.modules and not os.environ.get('KBBQ_USE_TORCH'):
+            from . import _device
+            _device.use_native_memory()          # as `bqsr --kmers` on one GPU: no torch import
+        info = _recal.recalibrate_bam(bam, use_oq=args.use_oq, set_oq=args.set_oq, kmers=kmers, gatkreport=args.gatkreport,
+                                      output=args.output)
+    sys.stderr.write('kbbq recalibrate: k=%d min_count=%d reads=%d flagged_bases=%d%s%s%s%s\n'
+                     % (info['k'], info['min_count'], info['reads'], info['flagged_bases'],
+                        ' skipped_bases=%d' % info['skipped_bases'] if args.skip_unresolved else '',
+                        ' passes=%d' % args.passes if (args.passes or 1) > 1 else '', kmer.partitions_field(info),
+                        ' prefilter=1 admitted=%d slots=%d' % (info['admitted'], info['slots']) if args.prefilter else ''))
+
+
 def recalibrate(args):
     import os
     from . import parallel
+    if args.kmers:
+        return _recalibrate_bam_kmers(args)
     kopts = None
     if args.correct is not None:
         kopts = dict(k=31 if args.kmer is None else args.kmer, min_count=args.min_count, slots=args.slots, prefilter=args.prefilter,
@@ -189,6 +227,11 @@ def main(argv=None):
     src.add_argument('-c', '--correct', metavar='FASTQ',
                      help='FASTQ file to recalibrate against its own k-mer correction, made on the GPU in the same run (not in '
                           'the reference): `kbbq correct` and `recalibrate -f` in one command, the same output, one GPU.')
+    rp.add_argument('--kmers', action='store_true',
+                    help='with -b: recalibrate the alignments from their own k-mers (not in the reference): `kbbq bqsr -b ALN --kmers '
+                         '-g R` and `kbbq applybqsr -b ALN -g R` in one run over one parse and one upload of the file, the same SAM '
+                         'text; takes the k-mer options below except --fix-n, and -u, -s, -g (the report is written there) and -o; '
+                         'all records of one query length, one GPU')
     rp.add_argument('-k', '--kmer', type=int, default=None, help='with -c: k-mer length, 8..32 (default 31)')
     rp.add_argument('--min-count', type=int, default=None,
                     help='with -c: k-mers seen at least this often are solid (default: the first valley of the count histogram)')
@@ -323,7 +366,13 @@ def main(argv=None):
     cp.set_defaults(command=correct)
 
     args = parser.parse_args(argv)
-    if args.command is recalibrate and args.correct is None:
+    if args.command is recalibrate and args.kmers:
+        if args.bam is None:
+            rp.error('--kmers: only with -b/--bam (-c/--correct corrects and recalibrates a FASTQ file)')
+        given = [flag for flag, v in (('--fix-n', args.fix_n), ('--infer-rg', args.infer_rg)) if v]
+        if given:
+            rp.error('%s: not with -b --kmers (FASTQ input only)' % ', '.join(given))
+    elif args.command is recalibrate and args.correct is None:
         given = [flag for flag, v in (('-k/--kmer', args.kmer), ('--min-count', args.min_count), ('--slots', args.slots),
                                       ('--prefilter', args.prefilter or None), ('--filter-bits', args.filter_bits),
                                       ('--fix-n', args.fix_n or None), ('--passes', args.passes),

@@ -827,16 +827,125 @@ def _emit_streamed(text, single, lut, shape, output, world, rank):
         peak.close()
 
 
-def recalibrate_bam(bam, use_oq=False, set_oq=False):
-    """Not implemented in the reference either."""
-    raise NotImplementedError('Recalibrating a bam is not yet implemented. '
-                              'Convert the BAM to FASTQ with `samtools fastq` first.')
+BAM_TWO_COMMANDS = ('run the two commands instead: `kbbq bqsr -b aln.bam --kmers -g model.grp` on one GPU, then '
+                    '`kbbq applybqsr -b aln.bam -g model.grp -o out.sam`, which runs under ranks')
+_BAM_KMERS = 'recalibrate -b --kmers'
 
 
-def recalibrate(bam, fastq, infer_rg=False, use_oq=False, set_oq=False, gatkreport=None, output=None):
+def _as_bam_kmers(exc):
+    """A refusal of `bqsr --kmers` as the same exception naming this command."""
+    text = str(exc.args[0]) if exc.args else ''
+    return type(exc)(text.replace('bqsr --kmers', _BAM_KMERS) if 'bqsr --kmers' in text else '%s: %s' % (_BAM_KMERS, text))
+
+
+def check_bam_kmers(bam, gatkreport=None, output=None, k=31, min_count=None, prefilter=False, filter_bits=4, partitions=1, passes=1):
+    """What recalibrate_bam refuses of its options, before the alignments are read, before any device work and, under a
+    launcher, before the process group exists: a process group, what `bqsr --kmers` refuses of the k-mer options (the same
+    exception types), an output name ending in .bam and a report that exists."""
+    from . import kmer
+    if parallel.launched_from_env() or kmer._ranks() is not None:
+        raise ValueError('%s does not run across ranks yet (the k-mer table of the alignments is counted and read on one '
+                         'GPU): on one GPU, or %s' % (_BAM_KMERS, BAM_TWO_COMMANDS))
+    try:
+        kmer.check_passes(passes)
+        kmer._check_partitions(partitions)
+        if not 8 <= int(k) <= 32:
+            raise ValueError('k must be in 8..32, got %d' % int(k))
+        if min_count is not None and int(min_count) < 1:
+            raise ValueError('min_count must be >= 1, got %d' % int(min_count))
+        if prefilter:
+            kmer._check_prefilter(min_count, filter_bits)
+    except ValueError as exc:
+        raise _as_bam_kmers(exc) from None
+    if output is not None and str(output).lower().endswith('.bam'):
+        raise ValueError('%s writes SAM text; BAM output (%s) is not supported' % (_BAM_KMERS, output))
+    if gatkreport is not None and os.path.exists(gatkreport):
+        raise ValueError('%s: the report %s exists: its model would replace the tally of the alignments\' own k-mers; give the '
+                         'name of a report to write, or apply the report with `kbbq applybqsr`' % (_BAM_KMERS, gatkreport))
+
+
+def check_bam_records(bam, use_oq=False, k=31, min_count=None, prefilter=False, filter_bits=4):
+    """What recalibrate_bam refuses of the records of an aln.AlignmentFile -- what `bqsr --kmers` refuses, with its exception
+    types: several query lengths, a record without RG, QUAL '*' without use_oq, a missing OQ tag with it -- on the reader's
+    host arrays, before any device work.  Returns gatk.bqsr._kmer_inputs' (batch, n, S)."""
+    from .gatk import bqsr
+    try:
+        return bqsr._kmer_inputs(bam, k, min_count, prefilter, filter_bits, use_oq, 42)
+    except (ValueError, KeyError, TypeError) as exc:
+        raise _as_bam_kmers(exc) from None
+
+
+def recalibrate_bam(bam, use_oq=False, set_oq=False, kmers=None, gatkreport=None, output=None):
+    """Without kmers: not implemented, as in the reference.
+    bam: a path, or an aln.AlignmentFile.  kmers (a dict of bam_to_kmer_covariates' k-mer options: k, min_count, slots, prefilter, filter_bits, skip_unresolved, passes,
+    partitions): `kbbq bqsr -b bam --kmers ... [-u] -g R` and `kbbq applybqsr -b bam -g R [-u] [-s] [-o output]` in one run, the
+    same bytes to stdout or `output` -- SAM text, the header as read.  The file is parsed once; SEQ and the source qualities
+    (QUAL, or OQ with use_oq) go to the device once and the count, the flags, the tally (gatk.bqsr._kmer_tally) and the apply
+    (kbbq_apply_aligned_dev, gatk.applybqsr._resident_slabs) read them there; the OQ plane follows for the context when records
+    carry OQ tags and use_oq is not set.  The model is the one `applybqsr` would read from R: the tally's vectors as a report,
+    its text parsed back (EstimatedQReported has four decimals there), get_delta_qs.  gatkreport: that text is written there;
+    a report that exists is refused.  Refusals (check_bam_kmers, then check_bam_records) come before any
+    device work.  Returns `bqsr --kmers`'s info; LAST_RUN['aligned']: alignments, pitch, h2d_plane_bytes and planes, the planes
+    that went to the device."""
+    if kmers is None:
+        raise NotImplementedError('Recalibrating a bam is not yet implemented. '
+                                  'Convert the BAM to FASTQ with `samtools fastq` first.')
+    import sys
+    from . import aln, kmer, recaltable
+    from .gatk import bqsr
+    opts = dict(k=31, min_count=None, slots=None, prefilter=False, filter_bits=4, skip_unresolved=False, passes=1, partitions=1)
+    unknown = sorted(set(kmers) - set(opts))
+    if unknown:
+        raise TypeError('recalibrate_bam: unknown k-mer option %s' % ', '.join(unknown))
+    opts.update(kmers)
+    check_bam_kmers(bam, gatkreport, output, opts['k'], opts['min_count'], opts['prefilter'], opts['filter_bits'],
+                    opts['partitions'], opts['passes'])
+    passes, partitions = kmer.check_passes(opts['passes']), kmer._check_partitions(opts['partitions'])
+    if not isinstance(bam, aln.AlignmentFile):
+        with stage('parse'):
+            bam = aln.AlignmentFile(bam)
+    inputs = check_bam_records(bam, use_oq, opts['k'], opts['min_count'], opts['prefilter'], opts['filter_bits'])
+    info = {}
+    with stage('k-mer tally', sync=True):
+        vectors, resident = bqsr._kmer_tally(bam, inputs, int(opts['k']), opts['min_count'], opts['slots'], opts['prefilter'],
+                                             opts['filter_bits'], use_oq, 6, 42, info, bool(opts['skip_unresolved']), passes, partitions)
+    with stage('solve'):
+        # the bytes of the report decide: what `applybqsr` reads back is the text, not the vectors
+        text = str(bqsr.vectors_to_report(*vectors, list(utils.get_rg_to_pu(bam).values())))
+        if gatkreport is not None:
+            with open(gatkreport, 'w') as fh:
+                fh.write(text)
+        *model, rg_to_int = applybqsr._report_model(bam, recaltable.RecalibrationReport.fromtext(text))
+    b, n, pitch = resident['batch'], resident['n'], resident['pitch']
+    if not use_oq and bool((b.oq_len >= 0).any()):
+        # records with an OQ tag take their context from it (gatk.applybqsr._rows): the one plane not there yet
+        with stage('H2D', sync=True):
+            resident['oq'] = dev._torch().from_numpy(b.plane(2, pitch)).cuda()
+        resident['planes'].append('OQ')
+        resident['h2d_plane_bytes'] += n * pitch
+    kw = dict(use_oq=use_oq, set_oq=set_oq, resident=resident)
+    with stage('apply + render'):
+        if output is None:
+            sys.stdout.flush()
+            applybqsr.write_alignments(bam, *model, rg_to_int, sys.stdout.buffer, **kw)
+            sys.stdout.flush()
+        else:
+            with open(output, 'wb') as sink:
+                applybqsr.write_alignments(bam, *model, rg_to_int, sink, **kw)
+    LAST_RUN.clear()
+    LAST_RUN['aligned'] = dict(alignments=n, pitch=pitch, h2d_plane_bytes=resident['h2d_plane_bytes'], planes=list(resident['planes']))
+    return info
+
+
+def recalibrate(bam, fastq, infer_rg=False, use_oq=False, set_oq=False, gatkreport=None, output=None, kmers=None):
     """Dispatcher of `kbbq recalibrate` (reference recalibrate.py:166-174).  The reference raises NotImplementedError
     for ANY gatkreport; here `-g` works with FASTQ input (a deliberate, documented divergence: SURVEY.md 8(f) #3), and
-    the cases that stay unimplemented -- no FASTQ input, or a BAM -- raise NotImplementedError as the reference does."""
+    the cases that stay unimplemented -- no FASTQ input, or a BAM without kmers -- raise NotImplementedError as the reference
+    does.  kmers: recalibrate_bam's; with it a BAM is recalibrated from its own k-mers, and its info is returned."""
+    if kmers is not None and bam is not None:
+        return recalibrate_bam(bam, use_oq, set_oq, kmers=kmers, gatkreport=gatkreport, output=output)
+    if kmers is not None:
+        raise ValueError('kmers: only with a BAM (recalibrate -b --kmers); -c corrects and recalibrates a FASTQ file')
     if gatkreport is not None and fastq is None:
         raise NotImplementedError('GATKreport reading / creation is only implemented for FASTQ input (-f).')
     if bam is not None:

@@ -36,8 +36,12 @@ class GATKReport:
         """reference recaltable.py:46-66: header `#:GATKReport.v<version>:<ntables>`, tables
         separated by blank lines; a table count that disagrees with the header is a ValueError."""
         with open(filename) as fh:
-            first = fh.readline()
-            body = fh.read()
+            return cls.fromtext(fh.read(), filename)
+
+    @classmethod
+    def fromtext(cls, text, filename='<text>'):
+        """The report a file holding `text` -- what write() writes, str(report) -- would give fromfile."""
+        first, _, body = text.partition('\n')
         _, version, ntables = first.strip().split(':')
         version = version.split(sep='v', maxsplit=1)[-1]
         tables = [GATKTable.fromstring(chunk) for chunk in body.split('\n\n') if chunk != '']
