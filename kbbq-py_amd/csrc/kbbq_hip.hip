@@ -123,11 +123,12 @@ static const void* k1_kernel(K1Form form, bool split, int dn, int nib, int kj)
 }
 
 // the others: the round-1 kernels (tables beyond the LDS, KBBQ_APPLY_CHECKED) and K2
-enum LdsKernel { LK_K1_PLAIN, LK_K1_PLAIN_SPLIT, LK_K2V3, LK_K2V3_NIB, LK_K2T, LK_K2T_NIB, LK_K2T_BANDS, LK_K2_LDS16, LK_K2_LDS8, LK_COUNT };
+enum LdsKernel { LK_K1_PLAIN, LK_K1_PLAIN_SPLIT, LK_K2V3, LK_K2V3_NIB, LK_K2T, LK_K2T_NIB, LK_K2T_BANDS, LK_K2T_PAIR19, LK_K2T_PAIR13, LK_K2_LDS16, LK_K2_LDS8, LK_COUNT };
 static const void* const LDS_KERNELS[LK_COUNT] = {
     (const void*)k1_accumulate<false>, (const void*)k1_accumulate<true>,
     (const void*)k2v3_apply<false>, (const void*)k2v3_apply<true>,
     (const void*)k2t_apply<false>, (const void*)k2t_apply<true>, (const void*)k2t_bands,
+    (const void*)k2t_apply_pair<19>, (const void*)k2t_apply_pair<13>,
     (const void*)k2_apply<int16_t, true, true>, (const void*)k2_apply<int8_t, true, false>,
 };
 
@@ -1208,7 +1209,11 @@ static int apply_rows(kbbq_ctx* c, const char* who, const uint8_t* d_seq, const 
             t.order = op.order;
         }
     }
-    return launch_lds(c, 1, LDS_KERNELS[nib ? LK_K2T_NIB : LK_K2T], dim3((unsigned)gt), dim3(K2T_THREADS), (size_t)t.lut_bytes, &t);
+    // 4-bit mate-pair rows of 19 / 13 chunks: the instance with that geometry compiled in (K1's KJ instances' counterpart)
+    const int kj = (pairs && nib) ? k2t_pair_form(t) : 0;
+    if (kj < 0) return fail(KBBQ_E_ARG, "%s: mate-pair rows of %d chunks do not have the geometry k2t_apply_pair was compiled for", who, q.cpr);
+    const LdsKernel k = kj == 19 ? LK_K2T_PAIR19 : kj == 13 ? LK_K2T_PAIR13 : nib ? LK_K2T_NIB : LK_K2T;
+    return launch_lds(c, 1, LDS_KERNELS[k], dim3((unsigned)gt), dim3(K2T_THREADS), (size_t)t.lut_bytes, &t);
 }
 
 int kbbq_apply_pairs_dev(kbbq_ctx* c, const uint8_t* d_pseq, const uint8_t* d_pqual, const uint32_t* d_pmeta,
