@@ -250,6 +250,35 @@ int kbbq_apply_aligned(kbbq_ctx* ctx, const uint8_t* seq, const uint8_t* qual, c
                        int64_t n, int pitch, int R, int Qt, int S2, int minscore, const void* model, size_t model_bytes,
                        int mode, uint8_t* out, int64_t* bad_read);
 
+/* ---- Static quantized qualities ---------------------------------------
+ * `--static-quantized-quals Q[,Q...]` [--round-down-quantized] of `kbbq recalibrate` and `kbbq applybqsr`: the qualities a
+ * command writes are rounded to a few levels so that the output compresses as its binned input did.  Not in the reference (its
+ * quantize() is the identity); the option names follow GATK's ApplyBQSR, the rule is this project's own:
+ *     levels   a non-empty set of integers minscore <= Q <= 93 (minscore: the 6 of every apply); E = sorted({minscore} U levels)
+ *     the rule is a byte map qmap[256] over OUTPUT bytes b, q = b - 33  (kbbq.gatk.applybqsr.quantize_map builds it):
+ *       b < 33 + minscore        qmap[b] = b: padding zeros, the separator of a mate-pair row, the bases an apply preserves, a
+ *                                new quality below minscore
+ *       q >= E[last]             E[last] + 33
+ *       E[i] <= q < E[i + 1]     E[i] + 33 if 2q <= E[i] + E[i + 1], else E[i + 1] + 33 (nearest, ties down);
+ *                                with round-down: E[i] + 33
+ * Every status (KBBQ_E_RANGE of a new quality outside -33..222, KBBQ_E_INDEX, KBBQ_E_TYPE) is decided BEFORE the map, on the
+ * unquantized value, with the row it is decided for today.
+ * kbbq_quantize_plane_dev: d_plane[i] = d_qmap[d_plane[i]] in place over nbytes, on the context's stream -- the pass that follows
+ *     K2 (kbbq_apply_dev / kbbq_apply_rows_dev / kbbq_apply_bands_dev) on any of its output planes, whatever their layout: every
+ *     one is a byte plane with zero padding, and qmap[0] == 0.  nbytes a multiple of 16, d_plane 16-byte aligned (else
+ *     KBBQ_E_ARG, nothing launched); nbytes == 0 is KBBQ_OK.  d_qmap: 256 bytes on the device.
+ * kbbq_apply_aligned_q_dev / kbbq_apply_aligned_q: kbbq_apply_aligned_dev / kbbq_apply_aligned with the map applied, in the
+ *     same kernel, to every NEW byte that passed the range check (a preserved byte is left alone: the map is the identity
+ *     there).  d_qmap: 256 bytes on the device; qmap: 256 bytes on the host, uploaded once with the model.  A NULL map IS the
+ *     call without _q: the same kernel, the same bytes.                                                                    */
+int kbbq_quantize_plane_dev(kbbq_ctx* ctx, uint8_t* d_plane, int64_t nbytes, const uint8_t* d_qmap);
+int kbbq_apply_aligned_q_dev(kbbq_ctx* ctx, const uint8_t* d_seq, const uint8_t* d_qual, const uint8_t* d_oq,
+                             const uint32_t* d_meta, int64_t n, int pitch, int R, int Qt, int S2, int minscore,
+                             const void* d_model, int mode, uint8_t* d_out, const uint8_t* d_qmap);
+int kbbq_apply_aligned_q(kbbq_ctx* ctx, const uint8_t* seq, const uint8_t* qual, const uint8_t* oq, const uint32_t* meta,
+                         int64_t n, int pitch, int R, int Qt, int S2, int minscore, const void* model, size_t model_bytes,
+                         int mode, uint8_t* out, int64_t* bad_read, const uint8_t* qmap);
+
 /* ---- K3: delta-Q model solve ------------------------------------------
  * Replaces compare_reads.gatk_delta_q (compare_reads.py:235-260) and, fused,
  * applybqsr.get_delta_qs (gatk/applybqsr.py:80-103).  Split of labour (DESIGN.md

@@ -20,8 +20,13 @@
 // Work: one lane per 16-byte chunk, lanes of a wave on consecutive chunks of consecutive rows, every plane read and written
 // with full-width 16-byte accesses; the byte before / after a chunk (the forward / reverse neighbour) comes from the next
 // lane over by DPP (wave_shr:1 / wave_shl:1), from memory only at the wave's two ends.
+// QMAP (static quantized qualities, kbbq_quantize_kernels.h): a new byte that has passed the range check goes through the
+// 256-byte map, staged in LDS once per workgroup, before it is packed into the 16-byte store.  The statuses are decided on the
+// unquantized value; a preserved byte never meets the map (the map is the identity there anyway).  Without QMAP the kernel is
+// the one it was: no LDS, no barrier.
 #pragma once
 #include "kbbq_kernels.h"
+#include "kbbq_quantize_kernels.h"
 
 #define AA_LUT 0
 #define AA_F64 1
@@ -43,6 +48,7 @@ struct AaParams {
     const int16_t* lut; int rs;                          // AA_LUT: canonical rows of kbbq_lut_row_stride(S2) entries
     const double* f64; int rs64;                         // AA_F64: rows of AA_F64_FIXED + S2 doubles
     uint8_t* out; u64* status;
+    const uint8_t* qmap;                                 // QMAP: the 256-byte map of the new bytes
 };
 
 // wave_shl:1 -- every lane receives lane+1's value, lane 63 receives `lane63` (the mirror of kbbq_kernels.h wave_shr1)
@@ -65,9 +71,15 @@ __device__ __forceinline__ int aa_comp_code(u32 c)
 
 __device__ __forceinline__ u32 aa_byte(const u32 (&w)[4], int b) { return (w[b >> 2] >> (8 * (b & 3))) & 0xFFu; }
 
-template <int MODE>
+template <int MODE, bool QMAP = false>
 __global__ __launch_bounds__(AA_THREADS) void kaa_apply(AaParams p)
 {
+    __shared__ uint8_t tab[QMAP ? 256 : 1];
+    if constexpr (QMAP) {
+        static_assert(AA_THREADS == KQ_THREADS, "kq_stage: one table byte per thread");
+        kq_stage(tab, p.qmap);
+        __syncthreads();
+    }
     const u32 c0 = blockIdx.x * AA_THREADS + threadIdx.x;
     const bool live = c0 < p.nchunks;
     const u32 c = live ? c0 : p.nchunks - 1;                 // every lane takes part in the DPP exchanges below
@@ -128,6 +140,7 @@ __global__ __launch_bounds__(AA_THREADS) void kaa_apply(AaParams p)
                 }
                 const int byte = v + 33;
                 if (byte < 0 || byte > 255) { bad_range = true; nq = 0; }
+                else if constexpr (QMAP) nq = tab[byte];
                 else nq = (u32)byte;
             }
         }

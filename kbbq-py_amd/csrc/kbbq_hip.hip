@@ -2070,8 +2070,10 @@ int kbbq_apply(kbbq_ctx* c, const uint8_t* seq, const uint8_t* qual, const uint3
 }
 
 // ---- ApplyBQSR on aligned rows (kbbq_apply_aligned.h) -----------------------------------------------------------------------
-int kbbq_apply_aligned_dev(kbbq_ctx* c, const uint8_t* d_seq, const uint8_t* d_qual, const uint8_t* d_oq, const uint32_t* d_meta,
-                           int64_t n, int pitch, int R, int Qt, int S2, int minscore, const void* d_model, int mode, uint8_t* d_out)
+// d_qmap: the 256-byte map of kbbq_apply_aligned_q_dev, or NULL -- then the launch is kbbq_apply_aligned_dev's, kernel and bytes
+static int apply_aligned_dev(kbbq_ctx* c, const uint8_t* d_seq, const uint8_t* d_qual, const uint8_t* d_oq, const uint32_t* d_meta,
+                             int64_t n, int pitch, int R, int Qt, int S2, int minscore, const void* d_model, int mode, uint8_t* d_out,
+                             const uint8_t* d_qmap)
 {
     if (!c) return fail(KBBQ_E_ARG, "ctx is NULL");
     if (!d_qual) d_qual = d_oq;
@@ -2091,7 +2093,7 @@ int kbbq_apply_aligned_dev(kbbq_ctx* c, const uint8_t* d_seq, const uint8_t* d_q
     p.cpr = pitch / 16; p.pitch = pitch; p.Qt = Qt; p.S2 = S2; p.minscore = minscore;
     p.lut = reinterpret_cast<const int16_t*>(d_model); p.rs = lut_row_stride(S2);
     p.f64 = reinterpret_cast<const double*>(d_model); p.rs64 = AA_F64_FIXED + S2;
-    p.status = c->d_status;
+    p.status = c->d_status; p.qmap = d_qmap;
     // launches of at most 2^31 chunks (32-bit chunk numbers in the kernel)
     const int64_t per = std::max<int64_t>(1, ((int64_t)1 << 31) / p.cpr);
     for (int64_t lo = 0; lo < n; lo += per) {
@@ -2102,7 +2104,11 @@ int kbbq_apply_aligned_dev(kbbq_ctx* c, const uint8_t* d_seq, const uint8_t* d_q
         const unsigned grid = (unsigned)(((int64_t)p.nchunks + AA_THREADS - 1) / AA_THREADS);
         {
             Timed t(c, 1);
-            if (mode == KBBQ_ALIGNED_LUT) hipLaunchKernelGGL(kaa_apply<AA_LUT>, dim3(grid), dim3(AA_THREADS), 0, c->stream, p);
+            if (d_qmap) {
+                if (mode == KBBQ_ALIGNED_LUT) hipLaunchKernelGGL((kaa_apply<AA_LUT, true>), dim3(grid), dim3(AA_THREADS), 0, c->stream, p);
+                else hipLaunchKernelGGL((kaa_apply<AA_F64, true>), dim3(grid), dim3(AA_THREADS), 0, c->stream, p);
+            }
+            else if (mode == KBBQ_ALIGNED_LUT) hipLaunchKernelGGL(kaa_apply<AA_LUT>, dim3(grid), dim3(AA_THREADS), 0, c->stream, p);
             else hipLaunchKernelGGL(kaa_apply<AA_F64>, dim3(grid), dim3(AA_THREADS), 0, c->stream, p);
         }
         HIPCHK(hipGetLastError());
@@ -2110,9 +2116,46 @@ int kbbq_apply_aligned_dev(kbbq_ctx* c, const uint8_t* d_seq, const uint8_t* d_q
     return KBBQ_OK;
 }
 
+int kbbq_apply_aligned_dev(kbbq_ctx* c, const uint8_t* d_seq, const uint8_t* d_qual, const uint8_t* d_oq, const uint32_t* d_meta,
+                           int64_t n, int pitch, int R, int Qt, int S2, int minscore, const void* d_model, int mode, uint8_t* d_out)
+{
+    return apply_aligned_dev(c, d_seq, d_qual, d_oq, d_meta, n, pitch, R, Qt, S2, minscore, d_model, mode, d_out, nullptr);
+}
+
+int kbbq_apply_aligned_q_dev(kbbq_ctx* c, const uint8_t* d_seq, const uint8_t* d_qual, const uint8_t* d_oq, const uint32_t* d_meta,
+                             int64_t n, int pitch, int R, int Qt, int S2, int minscore, const void* d_model, int mode, uint8_t* d_out,
+                             const uint8_t* d_qmap)
+{
+    return apply_aligned_dev(c, d_seq, d_qual, d_oq, d_meta, n, pitch, R, Qt, S2, minscore, d_model, mode, d_out, d_qmap);
+}
+
+// ---- static quantized qualities on a byte plane (kbbq_quantize_kernels.h) ----------------------------------------------------
+int kbbq_quantize_plane_dev(kbbq_ctx* c, uint8_t* d_plane, int64_t nbytes, const uint8_t* d_qmap)
+{
+    if (!c) return fail(KBBQ_E_ARG, "ctx is NULL");
+    if (nbytes < 0 || (nbytes & 15)) return fail(KBBQ_E_ARG, "kbbq_quantize_plane_dev: nbytes must be a multiple of 16, got %lld", (long long)nbytes);
+    if ((uintptr_t)d_plane & 15) return fail(KBBQ_E_ARG, "kbbq_quantize_plane_dev: the plane must be 16-byte aligned");
+    if (nbytes == 0) return KBBQ_OK;
+    if (!d_plane || !d_qmap) return fail(KBBQ_E_ARG, "kbbq_quantize_plane_dev: NULL argument");
+    HIPCHK(hipSetDevice(c->device));
+    const long long nchunks = nbytes / 16;
+    const long long per_wg = (long long)KQ_THREADS * KQ_CHUNKS_PER_LANE;
+    const unsigned grid = (unsigned)std::min<long long>((nchunks + per_wg - 1) / per_wg, 1 << 16);
+    hipLaunchKernelGGL(kq_plane, dim3(grid), dim3(KQ_THREADS), 0, c->stream, d_plane, nchunks, d_qmap);
+    HIPCHK(hipGetLastError());
+    return KBBQ_OK;
+}
+
 int kbbq_apply_aligned(kbbq_ctx* c, const uint8_t* seq, const uint8_t* qual, const uint8_t* oq, const uint32_t* meta,
                        int64_t n, int pitch, int R, int Qt, int S2, int minscore, const void* model, size_t model_bytes,
                        int mode, uint8_t* out, int64_t* bad_read)
+{
+    return kbbq_apply_aligned_q(c, seq, qual, oq, meta, n, pitch, R, Qt, S2, minscore, model, model_bytes, mode, out, bad_read, nullptr);
+}
+
+int kbbq_apply_aligned_q(kbbq_ctx* c, const uint8_t* seq, const uint8_t* qual, const uint8_t* oq, const uint32_t* meta,
+                         int64_t n, int pitch, int R, int Qt, int S2, int minscore, const void* model, size_t model_bytes,
+                         int mode, uint8_t* out, int64_t* bad_read, const uint8_t* qmap)
 {
     if (bad_read) *bad_read = -1;
     if (!c) return fail(KBBQ_E_ARG, "ctx is NULL");
@@ -2124,16 +2167,24 @@ int kbbq_apply_aligned(kbbq_ctx* c, const uint8_t* seq, const uint8_t* qual, con
     if (n == 0) return KBBQ_OK;
     HIPCHK(hipSetDevice(c->device));
     DevBuf dm;
-    HIPCHK(dm.alloc(model_bytes));
+    // the model, and behind it (16-byte aligned) the 256-byte map where there is one: one allocation, uploaded once
+    const size_t map_at = (model_bytes + 15) & ~(size_t)15;
+    HIPCHK(dm.alloc(map_at + (qmap ? 256 : 0)));
     HIPCHK(hipMemcpyAsync(dm.p, model, model_bytes, hipMemcpyHostToDevice, c->stream));
+    const uint8_t* d_qmap = nullptr;
+    if (qmap) {
+        d_qmap = (const uint8_t*)dm.p + map_at;
+        HIPCHK(hipMemcpyAsync((void*)d_qmap, qmap, 256, hipMemcpyHostToDevice, c->stream));
+    }
     // a slab: seq | qual | (oq) | out | meta (one quality plane when both are the same array)
     const int nq = qual == oq ? 1 : 2;
     auto launch = [&](uint8_t* d, size_t plane, int64_t m) {
-        return kbbq_apply_aligned_dev(c, d, d + plane, d + nq * plane, (const uint32_t*)(d + (nq + 2) * plane), m, pitch,
-                                      R, Qt, S2, minscore, dm.p, mode, d + (nq + 1) * plane);
+        return apply_aligned_dev(c, d, d + plane, d + nq * plane, (const uint32_t*)(d + (nq + 2) * plane), m, pitch,
+                                 R, Qt, S2, minscore, dm.p, mode, d + (nq + 1) * plane, d_qmap);
     };
-    if (nq == 1) return stage_run(c, "kbbq_apply_aligned", {seq, qual}, meta, out, n, pitch, launch, bad_read);
-    return stage_run(c, "kbbq_apply_aligned", {seq, qual, oq}, meta, out, n, pitch, launch, bad_read);
+    const char* who = qmap ? "kbbq_apply_aligned_q" : "kbbq_apply_aligned";
+    if (nq == 1) return stage_run(c, who, {seq, qual}, meta, out, n, pitch, launch, bad_read);
+    return stage_run(c, who, {seq, qual, oq}, meta, out, n, pitch, launch, bad_read);
 }
 
 // ---- k-mer counting and correction (kbbq_kmer.h) ------------------------------------------------------------------------------

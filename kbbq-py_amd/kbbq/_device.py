@@ -718,10 +718,28 @@ def accumulate_bands(items, tables, minscore=MINSCORE, check=True, dinuc_minscor
         ctx.status()
 
 
-def apply_bands(items, lut_dev, shape, outs=None, minscore=MINSCORE, check=True, restore_order=False):
+def qmap_to_device(qmap, device=None):
+    """The 256-byte map of static quantized qualities (gatk.applybqsr.quantize_map) on the device, for apply / apply_bands."""
+    qmap = np.ascontiguousarray(qmap)
+    if qmap.dtype != np.uint8 or qmap.shape != (256,):
+        raise ValueError('qmap: the 256-byte map of quantize_map (np.uint8[256])')
+    return lut_to_device(qmap, device)
+
+
+def quantize_plane(ctx, plane, qmap_dev):
+    """plane[i] = qmap[plane[i]] in place on the context's stream (kbbq_quantize_plane_dev): the pass behind K2 on an output
+    plane of any layout.  K2's statuses have been decided on the unquantized bytes by then."""
+    if not getattr(plane, 'is_contiguous', lambda: True)():            # (a _hipmem tensor always is)
+        raise ValueError('quantize_plane: a contiguous byte plane')
+    N.check(N.load().kbbq_quantize_plane_dev(ctx.handle, N.ptr(plane), int(plane.numel()) * int(plane.element_size()),
+                                             N.ptr(qmap_dev)))
+
+
+def apply_bands(items, lut_dev, shape, outs=None, minscore=MINSCORE, check=True, restore_order=False, qmap=None):
     """K2 over all length bands in one launch (kbbq_apply_bands_dev); returns the list of output planes (outs, or fresh
     ones).  The table-driven LUT only (a shape the fast kernels cannot serve raises LutNeedsCheckedApply before anything
-    is launched: apply() band by band has the checked kernel)."""
+    is launched: apply() band by band has the checked kernel).  qmap (qmap_to_device): every output plane goes through the
+    map behind K2, on its stream."""
     torch = _torch()
     R, Qt, S2, mode = shape
     if not items:
@@ -750,6 +768,9 @@ def apply_bands(items, lut_dev, shape, outs=None, minscore=MINSCORE, check=True,
     N.check(lib.kbbq_apply_bands_dev(ctx.handle, arr, len(items), R, S2, minscore, N.ptr(lut_dev)))
     if check:
         ctx.status()
+    if qmap is not None:
+        for out in outs:
+            quantize_plane(ctx, out, qmap)
     return outs
 
 
@@ -771,11 +792,13 @@ def build_lut(meanq, rgdq, qdq, posdq, dinucdq, minscore=MINSCORE):
     return blob, (R, Qt, S2, N.APPLY_FAST if flags.value == 0 else N.APPLY_CHECKED)
 
 
-def apply(batch, lut_dev, shape, out=None, minscore=MINSCORE, check=True, restore_order=False):
+def apply(batch, lut_dev, shape, out=None, minscore=MINSCORE, check=True, restore_order=False, qmap=None):
     """K2 over a device batch: new quality bytes [n, pitch] (compare_reads.py:320-328).
     With check=False the caller must call context().status() itself (and re-run with
     mode APPLY_CHECKED on LutNeedsCheckedApply).  restore_order: rows of a batch grouped by read group are stored
-    through its `perm`, i.e. straight back into the row order before the grouping."""
+    through its `perm`, i.e. straight back into the row order before the grouping.
+    qmap (qmap_to_device): the output plane, whatever its layout and row order, goes through the map of static quantized
+    qualities behind K2, on its stream (kbbq_quantize_plane_dev); K2 itself and what it reports are what they were."""
     torch = _torch()
     R, Qt, S2, mode = shape
     ctx = context(batch.seq.device.index)
@@ -804,6 +827,8 @@ def apply(batch, lut_dev, shape, out=None, minscore=MINSCORE, check=True, restor
                                         N.ptr(batch.seg), N.ptr(perm), N.ptr(out)))
         if check:
             ctx.status()
+        if qmap is not None:
+            quantize_plane(ctx, out, qmap)
         return out
 
     def launch(m):
@@ -817,6 +842,8 @@ def apply(batch, lut_dev, shape, out=None, minscore=MINSCORE, check=True, restor
         except N.LutNeedsCheckedApply:
             launch(N.APPLY_CHECKED)
             ctx.status()
+    if qmap is not None:
+        quantize_plane(ctx, out, qmap)
     return out
 
 

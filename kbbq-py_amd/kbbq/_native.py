@@ -80,6 +80,9 @@ PROTOTYPES = {
                         _vp, _vp, _vp, _vp, _vp, _vp]),
     'kbbq_apply_aligned_dev': (_i, [_vp] * 5 + [_i64, _i, _i, _i, _i, _i, _vp, _i, _vp]),
     'kbbq_apply_aligned': (_i, [_vp] * 5 + [_i64, _i, _i, _i, _i, _i, _vp, _sz, _i, _vp, _c.POINTER(_i64)]),
+    'kbbq_quantize_plane_dev': (_i, [_vp, _vp, _i64, _vp]),
+    'kbbq_apply_aligned_q_dev': (_i, [_vp] * 5 + [_i64, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp]),
+    'kbbq_apply_aligned_q': (_i, [_vp] * 5 + [_i64, _i, _i, _i, _i, _i, _vp, _sz, _i, _vp, _c.POINTER(_i64), _vp]),
     'kbbq_delta_q_dev': (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
     'kbbq_combiln_host': (_i, [_vp, _vp, _i64, _vp, _i]),
     'kbbq_solve_prep_host': (_i, [_vp, _i, _i, _vp, _vp, _i]),

@@ -134,30 +134,32 @@ def tally_range(A, B, infer_rg, lo, hi, tables, minscore, budget):
         dev.release_pinned('ingest')
 
 
-def apply_band(band, lut, shape):
+def apply_band(band, lut, shape, qmap=None):
     """New qualities of a band (or of a slab of one): in the band's own layout (mate-pair rows stay mate-pair rows, stored
     in input order -- the writer reads them as they are) or, when the layout's kernel cannot serve the LUT or the rows, one
-    read per row from the checked kernel.  Sets band['out_flags'] / ['out_S2'] for the writer."""
+    read per row from the checked kernel.  Sets band['out_flags'] / ['out_S2'] for the writer.  qmap: dev.apply's, the
+    device map of static quantized qualities."""
     laid, out = band.get('laid'), None
     band['out_flags'], band['out_S2'] = 0, 0
     if laid is not None:
         try:
-            out = dev.apply(laid, lut, shape, restore_order=True)      # grouped rows: stored straight back in input order
+            out = dev.apply(laid, lut, shape, restore_order=True, qmap=qmap)      # grouped rows: stored straight back in input order
             if isinstance(laid, dev.PairBatch):
                 band['out_flags'], band['out_S2'] = dev.N.ROWS_PAIRS, 2 * laid.S
         except dev.N.LutNeedsCheckedApply:
             out = None                   # a LUT the fast kernel cannot serve: the checked row-per-read kernel
     if out is None:
         band['out_flags'], band['out_S2'] = 0, 0
-        out = dev.apply(fastx.band_rows(band), lut, shape)
+        out = dev.apply(fastx.band_rows(band), lut, shape, qmap=qmap)
     return out
 
 
-def produce_range(A, infer_rg, lo, hi, lut, shape, budget, origin=None, extra=None, device=None):
+def produce_range(A, infer_rg, lo, hi, lut, shape, budget, origin=None, extra=None, device=None, qmap=None):
     """Generator of (band, device plane of new qualities) over reads [lo, hi) of reader A, slab by slab: fill | H2D | K2, each
     slab's input dropped as soon as its kernel has run (the plane lives until the egress pipeline has copied it).  Meant to
     be consumed by _egress.emit_produced on its feeding thread.  band['first'] counts from `origin` (default lo); extra: keys
-    every band gets (a segment's 'text' and 'base').  A kernel-reported error carries the read's index counted from origin."""
+    every band gets (a segment's 'text' and 'base').  A kernel-reported error carries the read's index counted from origin.
+    qmap: apply_band's."""
     torch = dev._torch()
     R, Qt, S2, mode = shape
     origin = lo if origin is None else origin
@@ -180,7 +182,7 @@ def produce_range(A, infer_rg, lo, hi, lut, shape, budget, origin=None, extra=No
                             band['laid'] = None                      # one read per row decides -- an IndexError at the first such read
                     try:
                         with stage('apply'):
-                            out = apply_band(band, lut, shape)
+                            out = apply_band(band, lut, shape, qmap)
                     except REFUSALS as e:
                         if hasattr(e, 'read_index'):
                             e.read_index = band['first'] + max(e.read_index, 0)

@@ -142,6 +142,43 @@ _ROWS = 1 << 20                # alignments per host slab (planes of SEQ / QUAL 
 _MAX_RG = 4096                 # read groups the kernel's row word holds
 
 
+def quantize_map(levels, round_down=False, minscore=6):
+    """The byte map of --static-quantized-quals (include/kbbq_hip.h, "Static quantized qualities") as np.uint8[256].
+    levels: a non-empty collection of integers minscore <= Q <= 93; E = sorted({minscore} U levels).  An output byte b below
+    33 + minscore maps to itself; q = b - 33 at or above E[-1] to E[-1] + 33; E[i] <= q < E[i + 1] to the nearer of the two,
+    ties down -- with round_down always to E[i].  ValueError for empty levels, a level that is not an integer, or one out of
+    range."""
+    import numbers
+    minscore = int(minscore)
+    try:
+        levels = list(levels)
+    except TypeError:
+        raise ValueError('quantization levels must be a collection of integers, got %r' % (levels,)) from None
+    if not levels:
+        raise ValueError('static quantized qualities need at least one level')
+    for q in levels:
+        if isinstance(q, bool) or not isinstance(q, numbers.Integral):
+            raise ValueError('quantization level %r is not an integer' % (q,))
+        if not minscore <= q <= 93:
+            raise ValueError('quantization level %d is outside %d..93' % (q, minscore))
+    E = np.array(sorted({minscore} | {int(q) for q in levels}), dtype=np.int64)
+    q = np.arange(256, dtype=np.int64) - 33
+    lo = E[np.clip(np.searchsorted(E, q, side='right') - 1, 0, len(E) - 1)]
+    hi = E[np.clip(np.searchsorted(E, q, side='right'), 0, len(E) - 1)]          # (== lo at and above the top level)
+    new = lo if round_down else np.where(2 * q <= lo + hi, lo, hi)
+    return (np.where(q < minscore, q, new) + 33).astype(np.uint8)
+
+
+def _check_qmap(quantize):
+    """quantize=None, or the 256-byte map (quantize_map) as a contiguous np.uint8 array."""
+    if quantize is None:
+        return None
+    qmap = np.ascontiguousarray(quantize)
+    if qmap.dtype != np.uint8 or qmap.shape != (256,):
+        raise ValueError('quantize: the 256-byte map of quantize_map (np.uint8[256])')
+    return qmap
+
+
 def _model(meanq, rgdq, qdq, posdq, dndq, minscore):
     """The five model arrays -> (mode, host blob, R, Qt, S2) for kbbq_apply_aligned.  An integer model is kbbq_build_lut's blob,
     as the FASTQ path uses it.  A float model (a report's EstimatedQReported, float deltas) is folded into the same integer rows
@@ -235,9 +272,10 @@ def _rows(bam, rg_to_int, R, use_oq, lo, hi):
     return meta, passthrough
 
 
-def _recalibrated_slabs(bam, model, rg_to_int, use_oq, minscore, lo, hi):
+def _recalibrated_slabs(bam, model, rg_to_int, use_oq, minscore, lo, hi, quantize=None):
     """(first alignment, count, output plane [count, pitch] of QUAL characters, lengths) for slabs of alignments [lo, hi): the
-    kernel's new qualities + 33, pass-through records holding their QUAL as read."""
+    kernel's new qualities + 33, pass-through records holding their QUAL as read.  quantize: the 256-byte map the new
+    qualities go through in the kernel (kbbq_apply_aligned_q); pass-through records are not touched."""
     import ctypes
     from .. import _device as dev
     from .. import _native as N
@@ -264,9 +302,12 @@ def _recalibrated_slabs(bam, model, rg_to_int, use_oq, minscore, lo, hi):
             if ctx is None:
                 ctx = dev.context()
             bad = ctypes.c_int64(-1)
-            rc = N.load().kbbq_apply_aligned(ctx.handle, N.ptr(seq), N.ptr(qual if not use_oq else oq), N.ptr(oq), N.ptr(meta),
-                                             m, pitch, R, Qt, S2, minscore, N.ptr(blob), blob.nbytes, mode, N.ptr(out),
-                                             ctypes.byref(bad))
+            args = (ctx.handle, N.ptr(seq), N.ptr(qual if not use_oq else oq), N.ptr(oq), N.ptr(meta),
+                    m, pitch, R, Qt, S2, minscore, N.ptr(blob), blob.nbytes, mode, N.ptr(out), ctypes.byref(bad))
+            if quantize is None:
+                rc = N.load().kbbq_apply_aligned(*args)
+            else:
+                rc = N.load().kbbq_apply_aligned_q(*args, N.ptr(quantize))
             try:
                 N.check(rc)
             except Exception as exc:
@@ -280,11 +321,11 @@ def _recalibrated_slabs(bam, model, rg_to_int, use_oq, minscore, lo, hi):
             raise stop
 
 
-def _resident_slabs(bam, model, rg_to_int, use_oq, minscore, lo, hi, resident):
+def _resident_slabs(bam, model, rg_to_int, use_oq, minscore, lo, hi, resident, quantize=None):
     """_recalibrated_slabs for alignments whose planes are on the device already (`resident`: gatk.bqsr._kmer_tally's -- seq and
     source [n, pitch], and oq, the context plane, where records carry OQ tags and the source is QUAL): the same slabs, row
     words, pass-through, errors and error order; kbbq_apply_aligned_dev reads the planes where they lie and only the output
-    plane of a slab crosses the bus."""
+    plane of a slab crosses the bus.  quantize: as _recalibrated_slabs (kbbq_apply_aligned_q_dev)."""
     from .. import _device as dev
     from .. import _native as N
     mode, blob, R, Qt, S2 = model
@@ -294,7 +335,7 @@ def _resident_slabs(bam, model, rg_to_int, use_oq, minscore, lo, hi, resident):
         raise ValueError('resident planes of pitch %d for alignments of up to %d bases' % (pitch, int(b.maxlen)))
     T = dev._torch()
     d_seq, d_src, d_oq = resident['seq'], resident['source'], resident.get('oq')
-    ctx = d_blob = None
+    ctx = d_blob = d_qmap = None
     for first in range(lo, hi, _ROWS):
         m = min(_ROWS, hi - first)
         rows = _rows(bam, rg_to_int, R, use_oq, first, first + m)
@@ -310,12 +351,16 @@ def _resident_slabs(bam, model, rg_to_int, use_oq, minscore, lo, hi, resident):
             if ctx is None:
                 ctx = dev.context()
                 d_blob = T.from_numpy(blob).cuda()
+                d_qmap = None if quantize is None else T.from_numpy(quantize).cuda()
             d_meta = T.from_numpy(np.ascontiguousarray(meta).view(np.int32)).cuda()
             d_out = T.empty((m, pitch), dtype=T.uint8, device='cuda')
             ctx_plane = d_src if use_oq or not has_oq else d_oq
-            N.check(N.load().kbbq_apply_aligned_dev(ctx.handle, N.ptr(d_seq[first:first + m]), N.ptr(d_src[first:first + m]),
-                                                    N.ptr(ctx_plane[first:first + m]), N.ptr(d_meta), m, pitch, R, Qt, S2, minscore,
-                                                    N.ptr(d_blob), mode, N.ptr(d_out)))
+            args = (ctx.handle, N.ptr(d_seq[first:first + m]), N.ptr(d_src[first:first + m]), N.ptr(ctx_plane[first:first + m]),
+                    N.ptr(d_meta), m, pitch, R, Qt, S2, minscore, N.ptr(d_blob), mode, N.ptr(d_out))
+            if d_qmap is None:
+                N.check(N.load().kbbq_apply_aligned_dev(*args))
+            else:
+                N.check(N.load().kbbq_apply_aligned_q_dev(*args, N.ptr(d_qmap)))
             try:
                 ctx.status()
             except Exception as exc:
@@ -330,17 +375,19 @@ def _resident_slabs(bam, model, rg_to_int, use_oq, minscore, lo, hi, resident):
             raise stop
 
 
-def recalibrate_alignments(bam, meanq, rgdq, qdq, posdq, dndq, rg_to_int, use_oq=True, minscore=6):
+def recalibrate_alignments(bam, meanq, rgdq, qdq, posdq, dndq, rg_to_int, use_oq=True, minscore=6, quantize=None):
     """New qualities of every alignment of an aln.AlignmentFile (SAM or BAM) on the GPU (kbbq_apply_aligned), as one flat int
     array and offsets [n + 1]: alignment i's are quals[offsets[i]:offsets[i + 1]], equal to recalibrate_bamread(read_i, ...)
     for every read the reference can process.  The same exceptions as the per-read function (IndexError, TypeError, KeyError),
     for the first offending alignment, with .read_index.  Beyond the reference: a record without an OQ tag takes its context from
     the source qualities (the reference: KeyError), and one whose source qualities are '*' or absent is passed through (its QUAL as
-    read).  New qualities outside -33..222 cannot be written as SAM: ValueError, as on the FASTQ path."""
+    read).  New qualities outside -33..222 cannot be written as SAM: ValueError, as on the FASTQ path.
+    quantize: the 256-byte map of quantize_map; every new quality goes through it after the errors above have been decided."""
+    quantize = _check_qmap(quantize)
     model = _model(meanq, rgdq, qdq, posdq, dndq, minscore)
     quals, lens = [], []
     n = len(bam)
-    for first, m, out, ln in _recalibrated_slabs(bam, model, rg_to_int, use_oq, minscore, 0, n):
+    for first, m, out, ln in _recalibrated_slabs(bam, model, rg_to_int, use_oq, minscore, 0, n, quantize):
         quals.append(out[np.arange(out.shape[1]) < ln[:, None]].astype(np.int_) - 33)
         lens.append(ln)
     LAST_RUN.clear()
@@ -352,14 +399,16 @@ def recalibrate_alignments(bam, meanq, rgdq, qdq, posdq, dndq, rg_to_int, use_oq
 
 
 def write_alignments(bam, meanq, rgdq, qdq, posdq, dndq, rg_to_int, sink, use_oq=False, set_oq=False, minscore=6,
-                     rows=None, header=True, resident=None):
+                     rows=None, header=True, resident=None, quantize=None):
     """Recalibrated SAM text of alignments rows = (lo, hi) (all by default) to the binary file `sink`: the header lines as read
     (header=True), then every alignment line as read with its QUAL replaced and, with set_oq, an OQ tag holding the QUAL as
     read added where there is none (csrc/sam_host.cpp kbbq_sam_render).  resident: the alignments' planes where they are on the
-    device already (_resident_slabs), instead of filled and uploaded slab by slab."""
+    device already (_resident_slabs), instead of filled and uploaded slab by slab.  quantize: the 256-byte map of quantize_map
+    for the new QUAL; the OQ tag of set_oq holds the qualities as read."""
     import ctypes
     from .. import _native as N
     from .._egress import _Reserve
+    quantize = _check_qmap(quantize)
     lib = N.load()
     b = bam.batch()
     lo, hi = (0, len(bam)) if rows is None else rows
@@ -369,8 +418,8 @@ def write_alignments(bam, meanq, rgdq, qdq, posdq, dndq, rg_to_int, sink, use_oq
         text = ''.join(line + '\n' for line in bam.header).encode('latin-1')
         reserve.ahead(len(text))
         sink.write(text)
-    slabs = (_recalibrated_slabs(bam, model, rg_to_int, use_oq, minscore, lo, hi) if resident is None else
-             _resident_slabs(bam, model, rg_to_int, use_oq, minscore, lo, hi, resident))
+    slabs = (_recalibrated_slabs(bam, model, rg_to_int, use_oq, minscore, lo, hi, quantize) if resident is None else
+             _resident_slabs(bam, model, rg_to_int, use_oq, minscore, lo, hi, resident, quantize))
     for first, m, out, _ in slabs:
         need = ctypes.c_size_t(0)
         N.check(lib.kbbq_sam_render(b._native, first, m, N.ptr(out), out.shape[1], int(bool(set_oq)), None, 0, ctypes.byref(need)))
@@ -398,13 +447,15 @@ def _report_model(bam, report):
     return (meanq,) + tuple(get_delta_qs(meanq, *vectors)) + (rg_to_int,)
 
 
-def apply_report(bam, report_path, use_oq=False, set_oq=False, output=None):
+def apply_report(bam, report_path, use_oq=False, set_oq=False, output=None, quantize=None):
     """`kbbq applybqsr`: report -> model (table_to_vectors, get_delta_qs on the device) -> kbbq_apply_aligned -> SAM text, to
     `output` or stdout.  Under torch.distributed.run every rank takes parallel.shard_range of the alignments and writes
     output.rankNNNN, the header in rank 0's file only, so that the files concatenated in rank order are the single-process
-    output.  BAM output is not written: an output name ending in .bam is refused."""
+    output.  BAM output is not written: an output name ending in .bam is refused.  quantize: the 256-byte map of quantize_map
+    (--static-quantized-quals); per byte, so the rank files concatenated stay the one-process bytes."""
     import sys
     from .. import aln, parallel
+    quantize = _check_qmap(quantize)
     if output is not None and str(output).lower().endswith('.bam'):
         raise ValueError('applybqsr writes SAM text; BAM output (%s) is not supported' % output)
     if not isinstance(bam, aln.AlignmentFile):
@@ -415,6 +466,8 @@ def apply_report(bam, report_path, use_oq=False, set_oq=False, output=None):
     *model, rg_to_int = report_model(bam, report_path)
     lo, hi = parallel.shard_range(len(bam), rank, world) if world > 1 else (0, len(bam))
     kw = dict(use_oq=use_oq, set_oq=set_oq, rows=(lo, hi), header=rank == 0)
+    if quantize is not None:                                 # without it the call is the one it was
+        kw['quantize'] = quantize
     if output is None:
         sys.stdout.flush()
         write_alignments(bam, *model, rg_to_int, sys.stdout.buffer, **kw)

@@ -38,6 +38,38 @@ def _partitions(text):
     return value
 
 
+def _quant_levels(text):
+    """--static-quantized-quals Q[,Q...]: integers in 6..93 (the minscore of every apply up to the top of the FASTQ scale)."""
+    levels = []
+    for item in text.split(','):
+        try:
+            value = int(item.strip())
+        except ValueError:
+            raise argparse.ArgumentTypeError('%r is not an integer (Q[,Q...])' % item) from None
+        if not 6 <= value <= 93:
+            raise argparse.ArgumentTypeError('levels must be in 6..93, got %d' % value)
+        levels.append(value)
+    return levels
+
+
+def _quantize(parser, args):
+    """The 256-byte map of --static-quantized-quals / --round-down-quantized (gatk.applybqsr.quantize_map) as the `quantize`
+    keyword of the calls below, or nothing -- then every call is the one it was.  An error of the two options is the parser's."""
+    if args.static_quantized_quals is None:
+        if args.round_down_quantized:
+            parser.error('--round-down-quantized: only with --static-quantized-quals')
+        return {}
+    from .gatk.applybqsr import quantize_map
+    levels = sorted({q for given in args.static_quantized_quals for q in given})
+    return dict(quantize=quantize_map(levels, round_down=args.round_down_quantized))
+
+
+_QUANT_HELP = ('round every quality that is written to the nearest of these levels and of 6, the quality below which bases keep '
+               'theirs (ties go down): the output compresses as binned input does.  Comma-separated, 6..93; may be given more '
+               'than once.  Qualities below 6, the model, a report (-g) and an OQ tag (-s) are not touched')
+_ROUND_DOWN_HELP = 'with --static-quantized-quals: round down to the level below instead of to the nearest'
+
+
 _PARTITIONS_HELP = ('%s: count the k-mers in this many rounds, 1..64 (default 1), each over all reads and for one hash partition of '
                     'the k-mers, through a table 1/P the size (--slots, where given, is that table); the k-mers that can be '
                     'solid are kept after each round and the reads are corrected against them: the same output, every round '
@@ -80,7 +112,7 @@ def _recalibrate_bam_kmers(args):
             from . import _device
             _device.use_native_memory()          # as `bqsr --kmers` on one GPU: no torch import
         info = _recal.recalibrate_bam(bam, use_oq=args.use_oq, set_oq=args.set_oq, kmers=kmers, gatkreport=args.gatkreport,
-                                      output=args.output)
+                                      output=args.output, **args.quantize)
     sys.stderr.write('kbbq recalibrate: k=%d min_count=%d reads=%d flagged_bases=%d%s%s%s%s\n'
                      % (info['k'], info['min_count'], info['reads'], info['flagged_bases'],
                         ' skipped_bases=%d' % info['skipped_bases'] if args.skip_unresolved else '',
@@ -125,7 +157,7 @@ def recalibrate(args):
         from ._trace import stage
         with stage('[recalibrate_corrected, wall]'):
             info = _recal.recalibrate_corrected(args.correct, infer_rg=args.infer_rg, gatkreport=args.gatkreport, output=args.output,
-                                                **kopts)
+                                                **kopts, **args.quantize)
         from .kmer import partitions_field
         sys.stderr.write('kbbq recalibrate: k=%d min_count=%d reads=%d changed_bases=%d%s%s%s%s%s\n'
                          % (info['k'], info['min_count'], info['reads'], info['changed_bases'],
@@ -135,7 +167,7 @@ def recalibrate(args):
                             ' prefilter=1 admitted=%d slots=%d' % (info['admitted'], info['slots']) if kopts['prefilter'] else ''))
         return
     _recal.recalibrate(bam=args.bam, fastq=args.fastq, infer_rg=args.infer_rg,
-                       use_oq=args.use_oq, set_oq=args.set_oq, gatkreport=args.gatkreport, output=args.output)
+                       use_oq=args.use_oq, set_oq=args.set_oq, gatkreport=args.gatkreport, output=args.output, **args.quantize)
 
 
 def benchmark(args):
@@ -158,7 +190,7 @@ def applybqsr(args):
     from . import parallel
     from .gatk import applybqsr as _apply
     parallel.init_from_env()          # one process per GPU under torch.distributed.run; no-op otherwise
-    _apply.apply_report(args.bam, args.gatkreport, use_oq=args.use_oq, set_oq=args.set_oq, output=args.output)
+    _apply.apply_report(args.bam, args.gatkreport, use_oq=args.use_oq, set_oq=args.set_oq, output=args.output, **args.quantize)
 
 
 def bqsr(args):
@@ -262,6 +294,9 @@ def main(argv=None):
                          'torch.distributed.run every rank writes FILE.rankNNNN, to be concatenated in rank order.')
     rp.add_argument('--infer-rg', action='store_true',
                     help='Infer the read group from the FASTQ read name (name_RG:Z:id).')
+    rp.add_argument('--static-quantized-quals', type=_quant_levels, action='append', default=None, metavar='Q[,Q...]',
+                    help='(not in the reference) ' + _QUANT_HELP)
+    rp.add_argument('--round-down-quantized', action='store_true', help=_ROUND_DOWN_HELP)
     rp.set_defaults(command=recalibrate)
 
     bp = sub.add_parser('benchmark', description='Benchmark a SAM or FASTQ file using a truth set')
@@ -303,6 +338,9 @@ def main(argv=None):
                          'under torch.distributed.run every rank writes FILE.rankNNNN, to be concatenated in rank order.')
     ap.add_argument('-u', '--use-oq', action='store_true', help='Recalibrate the OQ tag\'s qualities instead of QUAL.')
     ap.add_argument('-s', '--set-oq', action='store_true', help="Keep the qualities as read in an 'OQ' tag where there is none.")
+    ap.add_argument('--static-quantized-quals', type=_quant_levels, action='append', default=None, metavar='Q[,Q...]',
+                    help=_QUANT_HELP)
+    ap.add_argument('--round-down-quantized', action='store_true', help=_ROUND_DOWN_HELP)
     ap.set_defaults(command=applybqsr)
 
     qp = sub.add_parser('bqsr', description='Build a GATK recalibration report from alignments (BaseRecalibrator): errors are '
@@ -366,6 +404,9 @@ def main(argv=None):
     cp.set_defaults(command=correct)
 
     args = parser.parse_args(argv)
+    if args.command is recalibrate or args.command is applybqsr:
+        # decided here: before the device is touched and, under a launcher, before the process group exists
+        args.quantize = _quantize(rp if args.command is recalibrate else ap, args)
     if args.command is recalibrate and args.kmers:
         if args.bam is None:
             rp.error('--kmers: only with -b/--bam (-c/--correct corrects and recalibrates a FASTQ file)')

@@ -241,7 +241,13 @@ def _collective(fn, first=0):
     return res
 
 
-def recalibrate_fastq(fastq, infer_rg=False, gatkreport=None, output=None):
+def _device_qmap(quantize):
+    """The checked 256-byte map of `quantize` on the device (dev.qmap_to_device), or None: what every apply site carries beside
+    `lut, shape`."""
+    return None if quantize is None else dev.qmap_to_device(quantize)
+
+
+def recalibrate_fastq(fastq, infer_rg=False, gatkreport=None, output=None, quantize=None):
     """Recalibrate FASTQ file fastq[0] using its error-corrected version fastq[1];
     the recalibrated FASTQ is printed to stdout.  K1 -> K3 -> K2, tables and LUT stay on
     the device between the kernels.  gatkreport (the reference declares the option and raises
@@ -252,21 +258,25 @@ def recalibrate_fastq(fastq, infer_rg=False, gatkreport=None, output=None):
     the ranks print their records in rank order: the concatenated output is the single-process output.
     output (not in the reference, which only prints): write the records to this file instead of stdout; with several
     ranks every rank writes ITS records to `output`.rankNNNN at the same time (the files, concatenated in rank order,
-    are the single-process output) -- ranks sharing one stdout can only write in turn."""
+    are the single-process output) -- ranks sharing one stdout can only write in turn.
+    quantize (not in the reference): the 256-byte map of gatk.applybqsr.quantize_map (--static-quantized-quals); every quality
+    plane K2 writes goes through it on the device before it is copied back.  Per byte: the model, the report and the rank files'
+    concatenation are what they are without it."""
+    quantize = applybqsr._check_qmap(quantize)
     world, rank = parallel.world_rank()
     if any(fastx.is_sequential_input(p) for p in fastq) or os.environ.get('KBBQ_SEQUENTIAL'):
-        return _recalibrate_sequential(fastq, infer_rg, gatkreport, output)
+        return _recalibrate_sequential(fastq, infer_rg, gatkreport, output, quantize)
     shard = (rank, world) if world > 1 else None
     done_with = []                           # readers to unmap on a helper thread once the last byte is out (or the call has failed)
     try:
-        return _recalibrate_mapped(fastq, infer_rg, gatkreport, output, world, rank, shard, done_with)
+        return _recalibrate_mapped(fastq, infer_rg, gatkreport, output, world, rank, shard, done_with, quantize)
     finally:
         for reader in done_with:
             if reader is not None:
                 fastx.close_later(reader)
 
 
-def _recalibrate_mapped(fastq, infer_rg, gatkreport, output, world, rank, shard, done_with):
+def _recalibrate_mapped(fastq, infer_rg, gatkreport, output, world, rank, shard, done_with, quantize=None):
     """recalibrate_fastq on mapped, indexed inputs (regular files): resident on the device, or slab by slab within the budget."""
     packed, single = None, None
     if gatkreport is not None and os.path.exists(gatkreport):
@@ -292,6 +302,7 @@ def _recalibrate_mapped(fastq, infer_rg, gatkreport, output, world, rank, shard,
             parallel.barrier()
     with stage('solve', sync=True):
         lut, shape = dev.solve_lut(tables)
+        qmap = _device_qmap(quantize)
     if packed is not None and packed['total'] == text.total:
         # pass 2 walks the same reads with the same first-appearance read groups (:141-148):
         # the planes of pass 1 are still on the device
@@ -306,12 +317,13 @@ def _recalibrate_mapped(fastq, infer_rg, gatkreport, output, world, rank, shard,
             single = fastx.pack_single(text, infer_rg, shard, bands=True, to_device=True, budget=dev.device_budget())
 
     if single.get('streamed'):
-        return _emit_streamed(text, single, lut, shape, output, world, rank)
-    _apply_and_emit(text, single, lut, shape, output, world, rank)
+        return _emit_streamed(text, single, lut, shape, output, world, rank, qmap)
+    _apply_and_emit(text, single, lut, shape, output, world, rank, qmap)
 
 
-def _apply_and_emit(text, single, lut, shape, output, world, rank):
-    """Pass 2 over resident bands: K2 on every band of `single` in its layout, then the records of `text` to stdout or `output`."""
+def _apply_and_emit(text, single, lut, shape, output, world, rank, qmap=None):
+    """Pass 2 over resident bands: K2 on every band of `single` in its layout, then the records of `text` to stdout or `output`.
+    qmap: the device map of static quantized qualities (dev.apply / dev.apply_bands)."""
     R = shape[0]
     if single['R'] != R:
         # pass 2 met read groups the model does not have (recalibrate.py:143-151: an IndexError at the first such read) or
@@ -320,14 +332,15 @@ def _apply_and_emit(text, single, lut, shape, output, world, rank):
             band['laid'] = None
 
     def apply_band(band):
-        return _stream.apply_band(band, lut, shape)
+        return _stream.apply_band(band, lut, shape, qmap)
 
     def apply_shard():
         merged = {}
         several = [b for b in single['bands'] if b.get('laid') is not None]
         if len(several) >= 2:                 # all length bands in one launch (kbbq_apply_bands_dev); any trouble: band by band
             try:
-                res = dev.apply_bands([(b['laid'], b['S'], b.get('Smin', 0)) for b in several], lut, shape, restore_order=True)
+                res = dev.apply_bands([(b['laid'], b['S'], b.get('Smin', 0)) for b in several], lut, shape, restore_order=True,
+                                      qmap=qmap)
                 for b, o in zip(several, res):
                     merged[id(b)] = o
                     two = isinstance(b['laid'], dev.PairBatch)
@@ -393,7 +406,7 @@ def check_corrected(path, gatkreport=None, k=31, min_count=None, prefilter=False
 
 
 def recalibrate_corrected(path, infer_rg=False, gatkreport=None, output=None, k=31, min_count=None, slots=None, prefilter=False,
-                          filter_bits=4, fix_n=False, passes=1, skip_unresolved=False, partitions=1):
+                          filter_bits=4, fix_n=False, passes=1, skip_unresolved=False, partitions=1, quantize=None):
     """`kbbq correct` and `kbbq recalibrate -f reads corrected` in one run over ONE file: the reads go to the device once, in
     the layout pass 2 uses (fastx.pack_single), their k-mers are counted and the reads corrected where they lie
     (kmer.count_batch / correct_batch: the corrected plane is each band's cseq), and the tally, the solve, the apply and the
@@ -413,14 +426,16 @@ def recalibrate_corrected(path, infer_rg=False, gatkreport=None, output=None, k=
     k-mers through a table of `slots` slots (default: kmer.partition_slots within what the budget leaves beside the reads), and
     the table kept until the tally is over is the solid table, against which the bands -- those redone as character rows too --
     are corrected.  The same bytes; info then carries partitions, kept_pairs and solid_slots, and slots is the per-partition table.
+    quantize: recalibrate_fastq's -- the written qualities only; the correction, the tally and the model do not see it.
     One process, mapped inputs, reads that fit the device budget: anything else raises ValueError naming the two commands."""
     from . import kmer
+    quantize = applybqsr._check_qmap(quantize)
     passes = kmer.check_passes(passes)
     check_corrected(path, gatkreport, k, min_count, prefilter, filter_bits, **kmer._partitions_kw(partitions))
     done_with = []
     try:
         return _recalibrate_corrected(path, infer_rg, gatkreport, output, int(k), min_count, slots, prefilter, filter_bits, done_with,
-                                      bool(fix_n), passes, bool(skip_unresolved), partitions)
+                                      bool(fix_n), passes, bool(skip_unresolved), partitions, quantize)
     finally:
         for reader in done_with:
             fastx.close_later(reader)
@@ -432,7 +447,7 @@ def _batch_bytes(batch):
 
 
 def _recalibrate_corrected(path, infer_rg, gatkreport, output, k, min_count, slots, prefilter, filter_bits, done_with, fix_n=False,
-                           passes=1, skip=False, partitions=1):
+                           passes=1, skip=False, partitions=1, quantize=None):
     from . import kmer
     more = kmer._passes_kw(passes)
     if skip:
@@ -545,7 +560,7 @@ def _recalibrate_corrected(path, infer_rg, gatkreport, output, k, min_count, slo
         save_model(tables, single['rg_to_int'], gatkreport)
     with stage('solve', sync=True):
         lut, shape = dev.solve_lut(tables)
-    _apply_and_emit(text, single, lut, shape, output, 1, 0)
+    _apply_and_emit(text, single, lut, shape, output, 1, 0, _device_qmap(quantize))
     return info
 
 
@@ -734,8 +749,9 @@ class _Sequential:
                 sb.close()
         return tables
 
-    def pass2(self, lut, shape, output):
-        """Every read of file A (its own first-appearance read groups, recalibrate.py:141-148) through K2 and the writer."""
+    def pass2(self, lut, shape, output, qmap=None):
+        """Every read of file A (its own first-appearance read groups, recalibrate.py:141-148) through K2 and the writer.
+        qmap: the device map of static quantized qualities (_stream.produce_range)."""
         from . import _egress
         torch = dev._torch()
         device = torch.cuda.current_device()
@@ -755,7 +771,7 @@ class _Sequential:
                 rgs = a.rg_names()
                 try:
                     yield from _stream.produce_range(a, infer_rg, a.first, a.first + a.n, lut, shape, budget, origin=a.first,
-                                                     extra=dict(text=a, base=a.first), device=device)
+                                                     extra=dict(text=a, base=a.first), device=device, qmap=qmap)
                 except _stream.REFUSALS as e:
                     if hasattr(e, 'read_index'):
                         e.read_index = a.first + max(e.read_index, 0)
@@ -779,7 +795,7 @@ class _Sequential:
             sa.close()
 
 
-def _recalibrate_sequential(fastq, infer_rg, gatkreport, output):
+def _recalibrate_sequential(fastq, infer_rg, gatkreport, output, quantize=None):
     """recalibrate_fastq for inputs that are read sequentially: same results, same errors at the same reads."""
     run = _Sequential(fastq, infer_rg)
     try:
@@ -796,12 +812,12 @@ def _recalibrate_sequential(fastq, infer_rg, gatkreport, output):
             save_model(tables, run.rg_to_int(), gatkreport)
         with stage('solve', sync=True):
             lut, shape = dev.solve_lut(tables)
-        run.pass2(lut, shape, output)
+        run.pass2(lut, shape, output, _device_qmap(quantize))
     finally:
         run.close()
 
 
-def _emit_streamed(text, single, lut, shape, output, world, rank):
+def _emit_streamed(text, single, lut, shape, output, world, rank, qmap=None):
     """Pass 2 of a shard that is not resident (kbbq/_stream.py): file A's reads are filled again slab by slab and go through
     K2 while the slabs before them are copied back, rendered and written -- fill | H2D | K2 | D2H | format | write.  The
     ranks do not agree on a first error beforehand as the resident pass 2 does: an error stops the rank that meets it where
@@ -812,7 +828,8 @@ def _emit_streamed(text, single, lut, shape, output, world, rank):
     device = torch.cuda.current_device()
     peak = st.get('peak') or _stream.Peak(st['budget'])
     try:
-        produced = _stream.produce_range(st['A'], st['infer_rg'], st['lo'], st['hi'], lut, shape, st['budget'], device=device)
+        produced = _stream.produce_range(st['A'], st['infer_rg'], st['lo'], st['hi'], lut, shape, st['budget'], device=device,
+                                         qmap=qmap)
         widest = fastx.pitch_for(single['S']) * 2 + 16
         if output is None:
             parallel.in_rank_order(lambda: _egress.emit_produced(text, single['first'], produced, widest))
@@ -875,7 +892,7 @@ def check_bam_records(bam, use_oq=False, k=31, min_count=None, prefilter=False, 
         raise _as_bam_kmers(exc) from None
 
 
-def recalibrate_bam(bam, use_oq=False, set_oq=False, kmers=None, gatkreport=None, output=None):
+def recalibrate_bam(bam, use_oq=False, set_oq=False, kmers=None, gatkreport=None, output=None, quantize=None):
     """Without kmers: not implemented, as in the reference.
     bam: a path, or an aln.AlignmentFile.  kmers (a dict of bam_to_kmer_covariates' k-mer options: k, min_count, slots, prefilter, filter_bits, skip_unresolved, passes,
     partitions): `kbbq bqsr -b bam --kmers ... [-u] -g R` and `kbbq applybqsr -b bam -g R [-u] [-s] [-o output]` in one run, the
@@ -885,7 +902,8 @@ def recalibrate_bam(bam, use_oq=False, set_oq=False, kmers=None, gatkreport=None
     carry OQ tags and use_oq is not set.  The model is the one `applybqsr` would read from R: the tally's vectors as a report,
     its text parsed back (EstimatedQReported has four decimals there), get_delta_qs.  gatkreport: that text is written there;
     a report that exists is refused.  Refusals (check_bam_kmers, then check_bam_records) come before any
-    device work.  Returns `bqsr --kmers`'s info; LAST_RUN['aligned']: alignments, pitch, h2d_plane_bytes and planes, the planes
+    device work.  quantize: the 256-byte map of gatk.applybqsr.quantize_map for the written QUAL (write_alignments); the tally,
+    the report and the OQ tag of set_oq do not see it.  Returns `bqsr --kmers`'s info; LAST_RUN['aligned']: alignments, pitch, h2d_plane_bytes and planes, the planes
     that went to the device."""
     if kmers is None:
         raise NotImplementedError('Recalibrating a bam is not yet implemented. '
@@ -893,6 +911,7 @@ def recalibrate_bam(bam, use_oq=False, set_oq=False, kmers=None, gatkreport=None
     import sys
     from . import aln, kmer, recaltable
     from .gatk import bqsr
+    quantize = applybqsr._check_qmap(quantize)
     opts = dict(k=31, min_count=None, slots=None, prefilter=False, filter_bits=4, skip_unresolved=False, passes=1, partitions=1)
     unknown = sorted(set(kmers) - set(opts))
     if unknown:
@@ -924,6 +943,8 @@ def recalibrate_bam(bam, use_oq=False, set_oq=False, kmers=None, gatkreport=None
         resident['planes'].append('OQ')
         resident['h2d_plane_bytes'] += n * pitch
     kw = dict(use_oq=use_oq, set_oq=set_oq, resident=resident)
+    if quantize is not None:                                 # without it the call is the one it was
+        kw['quantize'] = quantize
     with stage('apply + render'):
         if output is None:
             sys.stdout.flush()
@@ -937,13 +958,15 @@ def recalibrate_bam(bam, use_oq=False, set_oq=False, kmers=None, gatkreport=None
     return info
 
 
-def recalibrate(bam, fastq, infer_rg=False, use_oq=False, set_oq=False, gatkreport=None, output=None, kmers=None):
+def recalibrate(bam, fastq, infer_rg=False, use_oq=False, set_oq=False, gatkreport=None, output=None, kmers=None, quantize=None):
     """Dispatcher of `kbbq recalibrate` (reference recalibrate.py:166-174).  The reference raises NotImplementedError
     for ANY gatkreport; here `-g` works with FASTQ input (a deliberate, documented divergence: SURVEY.md 8(f) #3), and
     the cases that stay unimplemented -- no FASTQ input, or a BAM without kmers -- raise NotImplementedError as the reference
-    does.  kmers: recalibrate_bam's; with it a BAM is recalibrated from its own k-mers, and its info is returned."""
+    does.  kmers: recalibrate_bam's; with it a BAM is recalibrated from its own k-mers, and its info is returned.
+    quantize: the 256-byte map of static quantized qualities (gatk.applybqsr.quantize_map) for whatever is written."""
+    more = {} if quantize is None else dict(quantize=quantize)          # without it every call below is the one it was
     if kmers is not None and bam is not None:
-        return recalibrate_bam(bam, use_oq, set_oq, kmers=kmers, gatkreport=gatkreport, output=output)
+        return recalibrate_bam(bam, use_oq, set_oq, kmers=kmers, gatkreport=gatkreport, output=output, **more)
     if kmers is not None:
         raise ValueError('kmers: only with a BAM (recalibrate -b --kmers); -c corrects and recalibrates a FASTQ file')
     if gatkreport is not None and fastq is None:
@@ -952,6 +975,6 @@ def recalibrate(bam, fastq, infer_rg=False, use_oq=False, set_oq=False, gatkrepo
         recalibrate_bam(bam, use_oq, set_oq)
     elif fastq is not None:
         with stage('[recalibrate_fastq, wall]'):
-            recalibrate_fastq(fastq, infer_rg=infer_rg, gatkreport=gatkreport, output=output)
+            recalibrate_fastq(fastq, infer_rg=infer_rg, gatkreport=gatkreport, output=output, **more)
     else:
         raise ValueError('A BAM or FASTQ file should be provided for recalibration.')
