@@ -397,7 +397,11 @@ int kbbq_canonical_reads_dev(kbbq_ctx* ctx, const uint8_t* d_seq, const uint8_t*
                              uint8_t* d_out_qual, uint32_t* d_out_meta);
 /* The same with the layout of the output rows chosen: 0 (character planes, as above) or KBBQ_ROWS_NIBBLES -- d_out_seq /
  * d_out_cseq are then 4-bit planes of nreads * pitch / 2 bytes (the layout kbbq_accumulate_rows_dev takes with that
- * flag; one byte per base less to write here and to read there).  A corrected base differs from its base in the low
+ * flag; one byte per base less to write here and to read there).  What the kernel needs of its input (both layouts, and
+ * kbbq_canonical_reads_dev): rows are `pitch` bytes wide; a row may hold FEWER than S bases; only [clip & 0xFFFF, clip >> 16)
+ * of it is read as bases and counted, and that range's upper end does not exceed the row's own length (an empty range: a row
+ * of uncounted padding); bytes at or behind a row's own length are 0 in d_seq, d_oq and the flag planes.  d_len is not read:
+ * every output row is S bases, the aligned part first, and out_meta says S.  A corrected base differs from its base in the low
  * bit of its code (an N: code 5 in d_out_cseq only).  Rows that cannot be packed -- a letter outside ACGTN on a forward-strand read -- make
  * kbbq_ctx_status return KBBQ_E_LUT: repeat the call with layout 0 (which is also where KBBQ_E_TYPE is decided). */
 int kbbq_canonical_reads_rows_dev(kbbq_ctx* ctx, const uint8_t* d_seq, const uint8_t* d_oq, const uint8_t* d_err,
@@ -408,8 +412,12 @@ int kbbq_canonical_reads_rows_dev(kbbq_ctx* ctx, const uint8_t* d_seq, const uin
 /* kbbq_accumulate_aligned_dev: kbbq_canonical_reads_rows_dev + kbbq_accumulate_rows_dev in ONE kernel (K6 fused into K1): the
  * tally of gatk.bqsr.bam_to_bqsr_covariates (gatk/bqsr.py:52-123) straight from the reads as aligned -- d_seq, d_oq (OQ
  * characters) and d_flagplane (kbbq_find_errors_dev's one plane of flags: bit 0 error, bit 1 skip) are [nreads, pitch]
- * planes of reads of the common length S (pitch = S rounded up to 16); d_clip / d_trim / d_flags per read as for
- * kbbq_canonical_reads_dev.  Counts ADD into d_tables (R, S2 = 2 S).  3 B/base read instead of 3 + 2 written + 2 read
+ * planes of reads of at most S bases (pitch = S rounded up to 16); d_clip / d_trim / d_flags per read as for
+ * kbbq_canonical_reads_dev.  What the kernel needs: rows are `pitch` bytes wide; a row may hold fewer than S bases; only
+ * [clip & 0xFFFF, clip >> 16) of it is counted, and clip's upper end does not exceed the row's own length; bytes at or behind a
+ * row's own length are 0 in all three planes.  The cycle of a base is its position in the aligned part in sequencing
+ * orientation, c = i - (clip & 0xFFFF) or (clip >> 16) - 1 - i on the reverse strand: column c for read 1, S2 - 1 - c for read 2,
+ * whatever the row's length.  Counts ADD into d_tables (R, S2 = 2 S).  3 B/base read instead of 3 + 2 written + 2 read
  * again.  A forward-strand read with a letter outside ACGTN makes kbbq_ctx_status return KBBQ_E_LUT: tally through
  * kbbq_canonical_reads_rows_dev(layout 0), where the reference's TypeError is decided; a shape whose tables do not fit the
  * LDS, and reads shorter than 32 bases, return KBBQ_E_LUT at once (nothing launched). */
@@ -425,7 +433,7 @@ int kbbq_accumulate_aligned_dev(kbbq_ctx* ctx, const uint8_t* d_seq, const uint8
  * runs over the listed reads only and writes THEIR rows of d_flagplane, which the tally kernel reads for them.  d_flagplane:
  * [nreads, pitch] scratch of the caller's (contents on entry irrelevant; rows of listed reads hold their flags afterwards).
  * d_genome: FUSED reference (bit 7 of a byte = the site's skip flag), genome_len bytes.  d_len[i] == S for every read (the
- * caller's promise, as for kbbq_accumulate_aligned_dev).  Counts ADD into d_tables and equal those of the two calls; the
+ * caller's promise: kbbq_accumulate_aligned_dev takes shorter rows, this call does not).  Counts ADD into d_tables and equal those of the two calls; the
  * same statuses arrive through kbbq_ctx_status (KBBQ_E_INDEX / KBBQ_E_RANGE from the CIGAR walk, KBBQ_E_LUT for a forward
  * read with a letter outside ACGTN); a shape the tally kernel does not serve returns KBBQ_E_LUT before anything is launched. */
 int kbbq_tally_aligned_dev(kbbq_ctx* ctx, const uint8_t* d_seq, const uint8_t* d_oq, const uint32_t* d_len, int64_t nreads,

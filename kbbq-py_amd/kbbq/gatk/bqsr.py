@@ -138,9 +138,11 @@ def trim_bamread(read, boundary=_UNSET):
 
 # ---------------------------------------------------------------- the tally (device)
 def _tally_flag_plane(tables, d_seq, d_qual, err, skip, d_len, d_clip, d_trim, d_flags, m, pitch, S, R, minscore, fused):
-    """Tally `m` aligned reads of the common length S into `tables`, given their flags: `err` is one plane of flags (bit 0 error,
+    """Tally `m` aligned reads of at most S bases (rows of pitch_for(S) bytes, 0 at and behind a read's own length) into `tables`
+    of 2 S cycle columns, given their flags: `err` is one plane of flags (bit 0 error,
     bit 1 skip; `skip` None) or the error plane of a pair (err, skip) -- whoever wrote it, K4's CIGAR walk against a reference
-    (bam_to_bqsr_covariates) or the k-mers of the reads themselves (bam_to_kmer_covariates).  d_qual: quality characters."""
+    (bam_to_bqsr_covariates) or the k-mers of the reads themselves (bam_to_kmer_covariates).  d_qual: quality characters.
+    Only [d_clip & 0xFFFF, d_clip >> 16) of a row is counted, and that range ends within the read."""
     from .. import _device as dev
     from .. import _native as N
     ctx = dev.context()
@@ -286,9 +288,18 @@ def bam_to_bqsr_covariates(bamfileobj, fastafilename, var_pos, minscore=6, maxsc
     return _solve.vectors_from_tables(*tables.to_host(), maxscore)
 
 
-def _kmer_inputs(bamfileobj, k, min_count, prefilter, filter_bits, use_oq, maxscore):
+def check_exclude_flags(exclude_flags):
+    """exclude_flags of the k-mer-sourced tally: an integer in 0..0xFFFF, the SAM FLAG bits of the records left out."""
+    if isinstance(exclude_flags, bool) or not isinstance(exclude_flags, (int, np.integer)) or not 0 <= int(exclude_flags) <= 0xFFFF:
+        raise ValueError('exclude_flags must be an integer in 0..0xFFFF (SAM FLAG bits), got %r' % (exclude_flags,))
+    return int(exclude_flags)
+
+
+def _kmer_inputs(bamfileobj, k, min_count, prefilter, filter_bits, use_oq, maxscore, mixed_lengths=False, exclude_flags=0):
     """Everything bam_to_kmer_covariates refuses, decided on the reader's host arrays before any device call (and, in a process
-    group, before any collective).  Returns (batch, n, S)."""
+    group, before any collective).  Returns (batch, n, S); with exclude_flags (batch, n, S, excluded): the boolean mask of the
+    records with FLAG & exclude_flags != 0.  Those are exempt from the refusals of QUAL '*', a missing OQ tag and an empty SEQ --
+    nothing of them is read -- and from no other.  mixed_lengths: S is the longest query length instead of the only one."""
     from .. import aln, kmer
     if maxscore != 42:
         raise ValueError('the Q axis of the device tables is fixed at 43 (maxscore = 42)')
@@ -301,6 +312,7 @@ def _kmer_inputs(bamfileobj, k, min_count, prefilter, filter_bits, use_oq, maxsc
         raise ValueError('min_count must be >= 1, got %d' % int(min_count))
     if prefilter:
         kmer._check_prefilter(min_count, filter_bits)
+    exclude_flags = check_exclude_flags(exclude_flags)
     if not isinstance(bamfileobj, aln.AlignmentFile):
         raise TypeError('bam_to_kmer_covariates takes a kbbq.aln.AlignmentFile (its batch() arrays), got %s' % type(bamfileobj).__name__)
     b = bamfileobj.batch()
@@ -311,29 +323,44 @@ def _kmer_inputs(bamfileobj, k, min_count, prefilter, filter_bits, use_oq, maxsc
         i = int(np.flatnonzero(b.rg < 0)[0])
         raise KeyError("tag 'RG' not present" if b.rg[i] == -1 else b._text(1, i).split('RG:Z:')[1].split('\t')[0])
     name = lambda i: 'record %d (%s)' % (i, b._text(0, i))
+    excluded = (b.flag & exclude_flags) != 0                                   # all False without the option
+    live = ~excluded
     have = b.oq_len if use_oq else b.qual_len
-    if use_oq and int(have.min()) < 0:
-        raise KeyError("tag 'OQ' not present in %s" % name(int(np.flatnonzero(have < 0)[0])))
-    if not use_oq and int(have.min()) == 0:
-        i = int(np.flatnonzero(have == 0)[0])
+    if use_oq and int(have[live].min(initial=0)) < 0:
+        raise KeyError("tag 'OQ' not present in %s" % name(int(np.flatnonzero(live & (have < 0))[0])))
+    if not use_oq and bool((live & (have == 0)).any()):
+        i = int(np.flatnonzero(live & (have == 0))[0])
         raise ValueError("%s has QUAL '*': bqsr --kmers needs a quality for every base (-u takes them from the OQ tag)" % name(i))
-    S = int(b.qlen[0])
-    wrong = np.flatnonzero(b.qlen != S)
-    if wrong.size:
-        i = int(wrong[0])
-        raise ValueError('%s has %d bases but record 0 has %d: the tally has one cycle axis of 2 S, so bqsr --kmers needs records '
-                         'of one query length' % (name(i), int(b.qlen[i]), S))
-    wrong = np.flatnonzero(have != S)
-    if wrong.size:
-        i = int(wrong[0])
-        raise ValueError('%s has %d qualities for %d bases' % (name(i), int(have[i]), S))
+    if mixed_lengths:
+        # one cycle axis of twice the LONGEST record: cycle c is column c, cycle -(c + 1) column 2 S - 1 - c, whatever S >= c + 1
+        S = int(b.qlen.max())
+        wrong = np.flatnonzero((have != b.qlen) & (live | (have > 0)))
+        if wrong.size:
+            i = int(wrong[0])
+            raise ValueError('%s has %d qualities for %d bases' % (name(i), int(have[i]), int(b.qlen[i])))
+        empty = np.flatnonzero(live & (b.qlen == 0))
+        if empty.size:
+            raise ValueError('%s has no bases: a row holds 1..65535' % name(int(empty[0])))
+    else:
+        S = int(b.qlen[0])
+        wrong = np.flatnonzero(b.qlen != S)
+        if wrong.size:
+            i = int(wrong[0])
+            raise ValueError('%s has %d bases but record 0 has %d: the tally has one cycle axis of 2 S, so bqsr --kmers needs records '
+                             'of one query length (--mixed-lengths takes records of several: the axis is then twice the longest)'
+                             % (name(i), int(b.qlen[i]), S))
+        wrong = np.flatnonzero((have != S) & (live | (have > 0)))
+        if wrong.size:
+            i = int(wrong[0])
+            raise ValueError('%s has %d qualities for %d bases' % (name(i), int(have[i]), S))
     if not 1 <= S <= 0xFFFF:
         raise ValueError('records of %d bases: a row holds 1..65535' % S)
-    return b, n, S
+    return (b, n, S, excluded) if exclude_flags else (b, n, S)
 
 
 def bam_to_kmer_covariates(bamfileobj, k=31, min_count=None, slots=None, prefilter=False, filter_bits=4, use_oq=False,
-                           minscore=6, maxscore=42, info=None, skip_unresolved=False, passes=1, partitions=1):
+                           minscore=6, maxscore=42, info=None, skip_unresolved=False, passes=1, partitions=1, mixed_lengths=False,
+                           exclude_flags=0):
     """The nine model vectors from aligned reads alone -- no reference, no known sites (`kbbq bqsr --kmers`).  A base is an error
     where the k-mer correction of kbbq.kmer would change it: every k-mer of SEQ of every record is counted (soft clips too:
     they are sequenced bases; keys are canonical, so the alignment's strand does not matter), a k-mer is solid at min_count
@@ -341,7 +368,8 @@ def bam_to_kmer_covariates(bamfileobj, k=31, min_count=None, slots=None, prefilt
     of flags the aligned tally reads.  The tally is bam_to_bqsr_covariates' own: the aligned part only, in sequencing
     orientation, without the bases below minscore, in the adaptor-trimmed range or N.  Qualities are QUAL, or the OQ tag with
     use_oq.  Secondary, supplementary and duplicate records are counted and tallied like any other, as bam_to_bqsr_covariates
-    does.  All records must have one query length; one GPU (ValueError in a process group, before any collective).
+    does (exclude_flags leaves them out).  All records must have one query length unless mixed_lengths is set; one GPU
+    (ValueError in a process group, before any collective).
     prefilter / filter_bits / slots: as kbbq.kmer.correct_reads.  `info`, a dict, receives k, min_count, reads, flagged_bases,
     slots, prefilter and admitted.
     skip_unresolved: an untrusted base for which the correction names no replacement (a tie, or no substitution makes a solid
@@ -355,30 +383,44 @@ def bam_to_kmer_covariates(bamfileobj, k=31, min_count=None, slots=None, prefilt
     partitions: the k-mers counted in that many rounds through a table of `slots` slots (kbbq.kmer.count_partitioned; 'auto':
     kbbq.kmer.partitions_for within what the budget leaves beside the resident planes) and the flags written against the solid
     table: the same vectors.  With more than one round `info` receives partitions, kept_pairs and solid_slots too, and its slots
-    is the per-partition table.  Refused in a process group before the group's own refusal."""
+    is the per-partition table.  Refused in a process group before the group's own refusal.
+    mixed_lengths: records of several query lengths are taken.  S is then the longest of the file and the cycle axis 2 S: a base
+    at aligned position c of a record of any length counts at column c (read 1) or 2 S - 1 - c (read 2), GATK's cycles c + 1 and
+    -(c + 1).  The planes have the longest record's pitch, shorter rows zero-padded; a record shorter than k has no k-mer, so
+    all its bases are trusted.  On a file of one length the vectors and `info` are those of the call without it.
+    exclude_flags: records with FLAG & exclude_flags != 0 (0xF00: secondary, QC-fail, duplicate, supplementary -- the classes
+    GATK's BaseRecalibrator leaves out) contribute nothing to the k-mer count, the prefilter or the tally: length 0 in the words
+    those kernels read, an empty aligned part in the tally's.  They still count into S and into `info`'s reads; `info` then
+    receives excluded_reads too."""
     from .. import kmer
     passes = kmer.check_passes(passes)
     partitions = kmer._check_partitions(partitions)
-    inputs = _kmer_inputs(bamfileobj, k, min_count, prefilter, filter_bits, use_oq, maxscore)
+    inputs = _kmer_inputs(bamfileobj, k, min_count, prefilter, filter_bits, use_oq, maxscore, mixed_lengths, exclude_flags)
     return _kmer_tally(bamfileobj, inputs, int(k), min_count, slots, prefilter, filter_bits, use_oq, minscore, maxscore, info,
                        skip_unresolved, passes, partitions)[0]
 
 
 def _kmer_tally(bamfileobj, inputs, k, min_count, slots, prefilter, filter_bits, use_oq, minscore, maxscore, info, skip_unresolved,
                 passes, partitions):
-    """bam_to_kmer_covariates past its refusals (`inputs`: what _kmer_inputs returned; passes and partitions checked): (the nine
+    """bam_to_kmer_covariates past its refusals (`inputs`: what _kmer_inputs returned, the mask of excluded records included where
+    it gave one; passes and partitions checked): (the nine
     vectors, resident).  `resident` is what the tally leaves on the device and the per-record arrays beside it, for a caller
     that goes on with the same alignments (kbbq.recalibrate.recalibrate_bam): batch, n, S, pitch, the device planes seq and
     source (QUAL, or OQ with use_oq), use_oq, rg_to_int, and planes / h2d_plane_bytes -- the names of the planes uploaded and
     their bytes.  bam_to_kmer_covariates drops it."""
     from .. import _device as dev
     from .. import _solve, fastx, kmer
-    b, n, S = inputs
+    b, n, S, *excluded = inputs
     T = dev._torch()
     rg_to_int = {rg: i for i, rg in enumerate(utils.get_rg_to_pu(bamfileobj))}
     R = max(len(rg_to_int), 1)
     lens = b.qlen.astype(np.uint32)
     clip = b.clip.copy()
+    if excluded:
+        # an excluded record is a row without bases to the count, the prefilter and the flags, and one without an aligned part to
+        # the tally: no kernel knows (the apply that may follow reads the batch's own words and recalibrates it like any other)
+        lens[excluded[0]] = 0
+        clip[excluded[0]] = 0
     rev = (b.flag & 16) != 0
     trim = b.adaptor_trim()                    # boundary + CIGAR walk per alignment, in the reader (csrc/sam_host.cpp)
     flags = (rev.astype(np.uint32) | (((b.flag & 128) != 0).astype(np.uint32) << 1) | (b.rg.astype(np.uint32) << 16))
@@ -435,7 +477,9 @@ def _kmer_tally(bamfileobj, inputs, k, min_count, slots, prefilter, filter_bits,
             info.update(passes=passes)
         if P > 1:
             info.update(partitions=P, kept_pairs=parts_info['kept_pairs'], solid_slots=parts_info['solid_slots'])
-    kept = dict(batch=b, n=n, S=S, pitch=pitch, seq=d_seq, source=d_qual, use_oq=bool(use_oq), rg_to_int=rg_to_int,
+        if excluded:
+            info.update(excluded_reads=int(excluded[0].sum()))
+    kept =dict(batch=b, n=n, S=S, pitch=pitch, seq=d_seq, source=d_qual, use_oq=bool(use_oq), rg_to_int=rg_to_int,
                 planes=['SEQ', 'OQ' if use_oq else 'QUAL'], h2d_plane_bytes=2 * n * pitch)
     return _solve.vectors_from_tables(*tables.to_host(), maxscore), kept
 
@@ -562,14 +606,17 @@ def bam_to_report(bamfileobj, fastafilename, var_pos):
 
 
 def bam_to_report_kmers(bamfileobj, k=31, min_count=None, slots=None, prefilter=False, filter_bits=4, use_oq=False, info=None,
-                        skip_unresolved=False, passes=1, partitions=1):
+                        skip_unresolved=False, passes=1, partitions=1, mixed_lengths=False, exclude_flags=0):
     """Aligned reads -> recalibration report without a reference or known sites: the errors are what the k-mers of the reads'
     own sequences contradict (bam_to_kmer_covariates); read groups are named by their PU as in bam_to_report.  skip_unresolved:
     bases the k-mers contradict without naming a replacement are left out of the tally (bam_to_kmer_covariates).  partitions: the
-    count in that many rounds (bam_to_kmer_covariates): the same report."""
+    count in that many rounds (bam_to_kmer_covariates): the same report.  mixed_lengths, exclude_flags: bam_to_kmer_covariates'
+    (rows without observations are dropped from a report, so an axis of twice the longest record adds no row)."""
     rgs = list(utils.get_rg_to_pu(bamfileobj).values())
     vectors = bam_to_kmer_covariates(bamfileobj, k=k, min_count=min_count, slots=slots, prefilter=prefilter,
                                      filter_bits=filter_bits, use_oq=use_oq, info=info, skip_unresolved=skip_unresolved,
                                      **({} if passes == 1 else dict(passes=passes)),
-                                     **({} if partitions == 1 else dict(partitions=partitions)))
+                                     **({} if partitions == 1 else dict(partitions=partitions)),
+                                     **(dict(mixed_lengths=True) if mixed_lengths else {}),
+                                     **(dict(exclude_flags=exclude_flags) if exclude_flags else {}))
     return vectors_to_report(*vectors, rgs)

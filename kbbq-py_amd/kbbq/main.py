@@ -38,6 +38,24 @@ def _partitions(text):
     return value
 
 
+def _exclude_flags(text):
+    """-F / --exclude-flags INT: SAM FLAG bits, decimal or 0x.., in 0..0xFFFF."""
+    try:
+        value = int(text, 16) if text.lower().startswith('0x') else int(text, 10)
+    except ValueError:
+        raise argparse.ArgumentTypeError('%r is not an integer (decimal or 0x..)' % text) from None
+    if not 0 <= value <= 0xFFFF:
+        raise argparse.ArgumentTypeError('must be in 0..0xFFFF, got %s' % text)
+    return value
+
+
+_EXCLUDE_HELP = ('%s: leave records with any of these FLAG bits (decimal or 0x..; default 0) out of the k-mer count and the tally '
+                 '-- they teach the model nothing%s.  -F 0xF00 is the set GATK\'s BaseRecalibrator leaves out as far as SAM '
+                 'flags express it: secondary, QC-fail, duplicate and supplementary records')
+_MIXED_HELP = ('%s: take records of several query lengths (trimmed reads, hard-clipped supplementary records): the cycle axis is '
+               'twice the longest record, the rows have its pitch')
+
+
 def _quant_levels(text):
     """--static-quantized-quals Q[,Q...]: integers in 6..93 (the minscore of every apply up to the top of the FASTQ scale)."""
     levels = []
@@ -98,23 +116,29 @@ def _recalibrate_bam_kmers(args):
         kmers['passes'] = args.passes
     if args.partitions is not None:
         kmers['partitions'] = args.partitions
+    if args.mixed_lengths:
+        kmers['mixed_lengths'] = True
+    if args.exclude_flags:
+        kmers['exclude_flags'] = args.exclude_flags
+    records = {key: kmers[key] for key in ('mixed_lengths', 'exclude_flags') if key in kmers}
     # every rank of a launcher refuses here, before it joins the process group
     _recal.check_bam_kmers(args.bam, args.gatkreport, args.output, kmers['k'], kmers['min_count'], kmers['prefilter'],
-                           kmers['filter_bits'], **{key: kmers[key] for key in ('partitions', 'passes') if key in kmers})
+                           kmers['filter_bits'], **{key: kmers[key] for key in ('partitions', 'passes', 'exclude_flags') if key in kmers})
     parallel.init_from_env()
     from . import aln
     from ._trace import stage
     with stage('[recalibrate_bam, wall]'):
         with stage('parse'):
             bam = aln.AlignmentFile(args.bam)    # the one parse; what the records are refused for, before the device is touched
-        _recal.check_bam_records(bam, args.use_oq, kmers['k'], kmers['min_count'], kmers['prefilter'], kmers['filter_bits'])
+        _recal.check_bam_records(bam, args.use_oq, kmers['k'], kmers['min_count'], kmers['prefilter'], kmers['filter_bits'], **records)
         if kmer._ranks() is None and 'torch' not in sys.modules and not os.environ.get('KBBQ_USE_TORCH'):
             from . import _device
             _device.use_native_memory()          # as `bqsr --kmers` on one GPU: no torch import
         info = _recal.recalibrate_bam(bam, use_oq=args.use_oq, set_oq=args.set_oq, kmers=kmers, gatkreport=args.gatkreport,
                                       output=args.output, **args.quantize)
-    sys.stderr.write('kbbq recalibrate: k=%d min_count=%d reads=%d flagged_bases=%d%s%s%s%s\n'
-                     % (info['k'], info['min_count'], info['reads'], info['flagged_bases'],
+    sys.stderr.write('kbbq recalibrate: k=%d min_count=%d reads=%d%s flagged_bases=%d%s%s%s%s\n'
+                     % (info['k'], info['min_count'], info['reads'],
+                        ' excluded_reads=%d' % info['excluded_reads'] if args.exclude_flags else '', info['flagged_bases'],
                         ' skipped_bases=%d' % info['skipped_bases'] if args.skip_unresolved else '',
                         ' passes=%d' % args.passes if (args.passes or 1) > 1 else '', kmer.partitions_field(info),
                         ' prefilter=1 admitted=%d slots=%d' % (info['admitted'], info['slots']) if args.prefilter else ''))
@@ -209,12 +233,17 @@ def bqsr(args):
         more = dict(passes=args.passes) if args.passes is not None else {}     # ... and without this option
         if args.partitions is not None:
             more['partitions'] = args.partitions
+        if args.mixed_lengths:
+            more['mixed_lengths'] = True
+        if args.exclude_flags:
+            more['exclude_flags'] = args.exclude_flags
         _bqsr.bam_to_report_kmers(aln.AlignmentFile(args.bam), k=31 if args.kmer is None else args.kmer, min_count=args.min_count,
                                   slots=args.slots, prefilter=args.prefilter,
                                   filter_bits=4 if args.filter_bits is None else args.filter_bits, use_oq=args.use_oq,
                                   info=info, **skip, **more).write(args.gatkreport)
-        sys.stderr.write('kbbq bqsr: k=%d min_count=%d reads=%d flagged_bases=%d%s%s%s%s\n'
-                         % (info['k'], info['min_count'], info['reads'], info['flagged_bases'],
+        sys.stderr.write('kbbq bqsr: k=%d min_count=%d reads=%d%s flagged_bases=%d%s%s%s%s\n'
+                         % (info['k'], info['min_count'], info['reads'],
+                            ' excluded_reads=%d' % info['excluded_reads'] if args.exclude_flags else '', info['flagged_bases'],
                             ' skipped_bases=%d' % info['skipped_bases'] if skip else '',
                             ' passes=%d' % args.passes if (args.passes or 1) > 1 else '', kmer.partitions_field(info),
                             ' prefilter=1 admitted=%d slots=%d' % (info['admitted'], info['slots']) if args.prefilter else ''))
@@ -263,7 +292,10 @@ def main(argv=None):
                     help='with -b: recalibrate the alignments from their own k-mers (not in the reference): `kbbq bqsr -b ALN --kmers '
                          '-g R` and `kbbq applybqsr -b ALN -g R` in one run over one parse and one upload of the file, the same SAM '
                          'text; takes the k-mer options below except --fix-n, and -u, -s, -g (the report is written there) and -o; '
-                         'all records of one query length, one GPU')
+                         'all records of one query length (unless --mixed-lengths), one GPU')
+    rp.add_argument('--mixed-lengths', action='store_true', help=_MIXED_HELP % 'with -b --kmers')
+    rp.add_argument('-F', '--exclude-flags', type=_exclude_flags, default=None, metavar='INT',
+                    help=_EXCLUDE_HELP % ('with -b --kmers', '; they are still recalibrated and written like any other'))
     rp.add_argument('-k', '--kmer', type=int, default=None, help='with -c: k-mer length, 8..32 (default 31)')
     rp.add_argument('--min-count', type=int, default=None,
                     help='with -c: k-mers seen at least this often are solid (default: the first valley of the count histogram)')
@@ -352,7 +384,10 @@ def main(argv=None):
     qp.add_argument('-g', '--gatkreport', required=True, help='Write the report to this file')
     qp.add_argument('--kmers', action='store_true',
                     help='take the errors from the k-mer correction of the alignments\' own sequences (as `kbbq correct` decides '
-                         'them) instead of a reference and known sites; all records of one query length, one GPU')
+                         'them) instead of a reference and known sites; all records of one query length (unless --mixed-lengths), '
+                         'one GPU')
+    qp.add_argument('--mixed-lengths', action='store_true', help=_MIXED_HELP % 'with --kmers')
+    qp.add_argument('-F', '--exclude-flags', type=_exclude_flags, default=None, metavar='INT', help=_EXCLUDE_HELP % ('with --kmers', ''))
     qp.add_argument('-k', '--kmer', type=int, default=None, help='with --kmers: k-mer length, 8..32 (default 31)')
     qp.add_argument('--min-count', type=int, default=None,
                     help='with --kmers: k-mers seen at least this often are solid (default: the first valley of the count histogram)')
@@ -407,6 +442,11 @@ def main(argv=None):
     if args.command is recalibrate or args.command is applybqsr:
         # decided here: before the device is touched and, under a launcher, before the process group exists
         args.quantize = _quantize(rp if args.command is recalibrate else ap, args)
+    if args.command is recalibrate and not (args.kmers and args.bam is not None):
+        given = [flag for flag, v in (('--mixed-lengths', args.mixed_lengths or None), ('-F/--exclude-flags', args.exclude_flags))
+                 if v is not None]
+        if given:
+            rp.error('%s: only with -b --kmers' % ', '.join(given))
     if args.command is recalibrate and args.kmers:
         if args.bam is None:
             rp.error('--kmers: only with -b/--bam (-c/--correct corrects and recalibrates a FASTQ file)')
@@ -441,7 +481,8 @@ def main(argv=None):
                                           ('--prefilter', args.prefilter or None), ('--filter-bits', args.filter_bits),
                                           ('-u/--use-oq', args.use_oq or None),
                                           ('--skip-unresolved', args.skip_unresolved or None), ('--passes', args.passes),
-                                          ('--partitions', args.partitions))
+                                          ('--partitions', args.partitions), ('--mixed-lengths', args.mixed_lengths or None),
+                                          ('-F/--exclude-flags', args.exclude_flags))
                      if v is not None]
             if given:
                 qp.error('%s: only with --kmers' % ', '.join(given))

@@ -855,11 +855,13 @@ def _as_bam_kmers(exc):
     return type(exc)(text.replace('bqsr --kmers', _BAM_KMERS) if 'bqsr --kmers' in text else '%s: %s' % (_BAM_KMERS, text))
 
 
-def check_bam_kmers(bam, gatkreport=None, output=None, k=31, min_count=None, prefilter=False, filter_bits=4, partitions=1, passes=1):
+def check_bam_kmers(bam, gatkreport=None, output=None, k=31, min_count=None, prefilter=False, filter_bits=4, partitions=1, passes=1,
+                    exclude_flags=0):
     """What recalibrate_bam refuses of its options, before the alignments are read, before any device work and, under a
     launcher, before the process group exists: a process group, what `bqsr --kmers` refuses of the k-mer options (the same
     exception types), an output name ending in .bam and a report that exists."""
     from . import kmer
+    from .gatk import bqsr
     if parallel.launched_from_env() or kmer._ranks() is not None:
         raise ValueError('%s does not run across ranks yet (the k-mer table of the alignments is counted and read on one '
                          'GPU): on one GPU, or %s' % (_BAM_KMERS, BAM_TWO_COMMANDS))
@@ -872,6 +874,7 @@ def check_bam_kmers(bam, gatkreport=None, output=None, k=31, min_count=None, pre
             raise ValueError('min_count must be >= 1, got %d' % int(min_count))
         if prefilter:
             kmer._check_prefilter(min_count, filter_bits)
+        bqsr.check_exclude_flags(exclude_flags)
     except ValueError as exc:
         raise _as_bam_kmers(exc) from None
     if output is not None and str(output).lower().endswith('.bam'):
@@ -881,13 +884,15 @@ def check_bam_kmers(bam, gatkreport=None, output=None, k=31, min_count=None, pre
                          'name of a report to write, or apply the report with `kbbq applybqsr`' % (_BAM_KMERS, gatkreport))
 
 
-def check_bam_records(bam, use_oq=False, k=31, min_count=None, prefilter=False, filter_bits=4):
+def check_bam_records(bam, use_oq=False, k=31, min_count=None, prefilter=False, filter_bits=4, mixed_lengths=False, exclude_flags=0):
     """What recalibrate_bam refuses of the records of an aln.AlignmentFile -- what `bqsr --kmers` refuses, with its exception
-    types: several query lengths, a record without RG, QUAL '*' without use_oq, a missing OQ tag with it -- on the reader's
-    host arrays, before any device work.  Returns gatk.bqsr._kmer_inputs' (batch, n, S)."""
+    types: several query lengths (without mixed_lengths), a record without RG, QUAL '*' without use_oq, a missing OQ tag with it
+    (neither for a record that exclude_flags leaves out) -- on the reader's
+    host arrays, before any device work.  Returns what gatk.bqsr._kmer_inputs returns: (batch, n, S), and the mask of the
+    excluded records behind them with exclude_flags."""
     from .gatk import bqsr
     try:
-        return bqsr._kmer_inputs(bam, k, min_count, prefilter, filter_bits, use_oq, 42)
+        return bqsr._kmer_inputs(bam, k, min_count, prefilter, filter_bits, use_oq, 42, mixed_lengths, exclude_flags)
     except (ValueError, KeyError, TypeError) as exc:
         raise _as_bam_kmers(exc) from None
 
@@ -895,7 +900,8 @@ def check_bam_records(bam, use_oq=False, k=31, min_count=None, prefilter=False, 
 def recalibrate_bam(bam, use_oq=False, set_oq=False, kmers=None, gatkreport=None, output=None, quantize=None):
     """Without kmers: not implemented, as in the reference.
     bam: a path, or an aln.AlignmentFile.  kmers (a dict of bam_to_kmer_covariates' k-mer options: k, min_count, slots, prefilter, filter_bits, skip_unresolved, passes,
-    partitions): `kbbq bqsr -b bam --kmers ... [-u] -g R` and `kbbq applybqsr -b bam -g R [-u] [-s] [-o output]` in one run, the
+    partitions, mixed_lengths, exclude_flags -- a record that exclude_flags leaves out of the model is still recalibrated and
+    written like any other): `kbbq bqsr -b bam --kmers ... [-u] -g R` and `kbbq applybqsr -b bam -g R [-u] [-s] [-o output]` in one run, the
     same bytes to stdout or `output` -- SAM text, the header as read.  The file is parsed once; SEQ and the source qualities
     (QUAL, or OQ with use_oq) go to the device once and the count, the flags, the tally (gatk.bqsr._kmer_tally) and the apply
     (kbbq_apply_aligned_dev, gatk.applybqsr._resident_slabs) read them there; the OQ plane follows for the context when records
@@ -912,18 +918,21 @@ def recalibrate_bam(bam, use_oq=False, set_oq=False, kmers=None, gatkreport=None
     from . import aln, kmer, recaltable
     from .gatk import bqsr
     quantize = applybqsr._check_qmap(quantize)
-    opts = dict(k=31, min_count=None, slots=None, prefilter=False, filter_bits=4, skip_unresolved=False, passes=1, partitions=1)
+    opts = dict(k=31, min_count=None, slots=None, prefilter=False, filter_bits=4, skip_unresolved=False, passes=1, partitions=1,
+                mixed_lengths=False, exclude_flags=0)
     unknown = sorted(set(kmers) - set(opts))
     if unknown:
         raise TypeError('recalibrate_bam: unknown k-mer option %s' % ', '.join(unknown))
     opts.update(kmers)
+    # (without the two options of the records every call below is the one it was)
+    records = {key: opts[key] for key in ('mixed_lengths', 'exclude_flags') if opts[key]}
     check_bam_kmers(bam, gatkreport, output, opts['k'], opts['min_count'], opts['prefilter'], opts['filter_bits'],
-                    opts['partitions'], opts['passes'])
+                    opts['partitions'], opts['passes'], **{key: records[key] for key in ('exclude_flags',) if key in records})
     passes, partitions = kmer.check_passes(opts['passes']), kmer._check_partitions(opts['partitions'])
     if not isinstance(bam, aln.AlignmentFile):
         with stage('parse'):
             bam = aln.AlignmentFile(bam)
-    inputs = check_bam_records(bam, use_oq, opts['k'], opts['min_count'], opts['prefilter'], opts['filter_bits'])
+    inputs = check_bam_records(bam, use_oq, opts['k'], opts['min_count'], opts['prefilter'], opts['filter_bits'], **records)
     info = {}
     with stage('k-mer tally', sync=True):
         vectors, resident = bqsr._kmer_tally(bam, inputs, int(opts['k']), opts['min_count'], opts['slots'], opts['prefilter'],
