@@ -990,6 +990,25 @@ int kbbq_kmer_count_filtered_rows_part_dev(kbbq_ctx* ctx, kbbq_kmer_table* table
                                            const uint8_t* d_seq, const uint32_t* d_meta, int64_t nrows, int pitch, int flags, int parts,
                                            int part);
 
+/* ---- quality gate: count only k-mers of bases with quality >= Q (kbbq correct --kmer-min-qual; csrc/kbbq_kmer.h km_gate) ------
+ * THE RULE.  A base of a row is countable when it is A/C/G/T (as for every count call) and its quality byte in d_qual is
+ * >= qual_byte_min; a window is counted iff all k of its bases are countable.  The call writes d_out, a copy of d_seq in the
+ * same layout with 'N' (KBBQ_ROWS_NIBBLES: code 4) wherever the quality byte is < qual_byte_min and every other byte as read;
+ * every byte of every row is written, padding and separator included.  An 'N' is a break to every count call, so
+ * kbbq_kmer_prefilter*, kbbq_kmer_count*, kbbq_kmer_count_filtered* and their _part forms on d_out (with the same d_meta, pitch
+ * and flags) see exactly the counted windows: counting d_out with any existing count call yields exactly *d_windows insertions.
+ * Nothing after the count knows the gate: the correct / flag calls take d_seq as read.
+ * d_qual is the rows' quality plane, [nrows, pitch] characters (also beside a 4-bit sequence plane, whose row stride is
+ * pitch / 2) at the base's own row and column, 16-byte aligned.  qual_byte_min is a BYTE value: Q + 33 for character qualities,
+ * Q + 0 for a plane of raw Phred values.  *d_windows (a device word, may be NULL: no count) is ADDED to, not set: the caller
+ * zeroes it, so the bands of one input sum into one word.  d_seq and d_qual are not written.
+ * flags are the KBBQ_ROWS_* of the calls above, checked as there; 0 is character rows, one read a row.  KBBQ_E_ARG naming the
+ * call before anything is launched: a NULL plane or meta with nrows > 0, d_out == d_seq, a plane that is not aligned (4-bit
+ * planes 8 bytes, character and quality planes 16), k outside 8..32, qual_byte_min outside 1..255, a pitch whose rows do not
+ * fit the LDS.  nrows == 0 does nothing.  There is no host-buffer form. */
+int kbbq_kmer_gate_rows_dev(kbbq_ctx* ctx, const uint8_t* d_seq, const uint8_t* d_qual, const uint32_t* d_meta, int64_t nrows,
+                            int pitch, int flags, int k, int qual_byte_min, uint8_t* d_out, uint64_t* d_windows);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2277,9 +2277,9 @@ static int kmer_geometry(kbbq_ctx* c, const char* who, const kbbq_kmer_table* t,
 // launches of at most 2^20 workgroups.  The kernel's parameters after its KmerParams, in their order: `extra` (KmerFilterParams,
 // passes, KmerPartParams) when the kernel has one, `part` (the KmerPartParams of a kernel that has an `extra` before it), then
 // `tally` -- both correction kernels end in a KmerTally, a copy of which moves with the rows of each launch; every other kernel
-// gets nullptr
+// gets nullptr.  `gate`: km_gate's one parameter after its KmerParams, whose quality and output planes move with the rows too
 static int kmer_launches(kbbq_ctx* c, const KmerParams& p, const void* kernel, size_t lds, const void* extra,
-                         const KmerTally* tally = nullptr, const KmerPartParams* part = nullptr)
+                         const KmerTally* tally = nullptr, const KmerPartParams* part = nullptr, const KmerGate* gate = nullptr)
 {
     HIPCHK(hipSetDevice(c->device));
     const int64_t per = ((int64_t)1 << 20) * p.rows_per_wg;
@@ -2297,6 +2297,12 @@ static int kmer_launches(kbbq_ctx* c, const KmerParams& p, const void* kernel, s
         if (extra) args[na++] = const_cast<void*>(extra);
         if (part) args[na++] = const_cast<KmerPartParams*>(part);
         if (tally) args[na++] = &ty;
+        KmerGate g = {nullptr, 0, nullptr, nullptr};
+        if (gate) {
+            g = *gate;
+            g.qual = gate->qual + (size_t)lo * p.cpr * 16; g.out = gate->out + (size_t)lo * p.pitch;
+            args[na++] = &g;
+        }
         HIPCHK(hipLaunchKernel(kernel, dim3((unsigned)((m + p.rows_per_wg - 1) / p.rows_per_wg)), dim3(KM_THREADS), args, lds, c->stream));
     }
     return KBBQ_OK;
@@ -2557,6 +2563,31 @@ int kbbq_kmer_correct_rows_skip_dev(kbbq_ctx* c, const kbbq_kmer_table* t, const
     KmerForm f = kmer_form_rows(nib, (flags & KBBQ_ROWS_PAIRS) != 0, opts, passes);
     f.tally = true;
     return kmer_correct_rows(c, who, t, d_seq, d_meta, nrows, pitch, min_count, d_out, d_changed, d_unresolved, f, {d_qual, d_tally_qual});
+}
+
+// the quality gate in front of the count (csrc/kbbq_kmer.h km_gate): arguments checked, then kmer_launches
+int kbbq_kmer_gate_rows_dev(kbbq_ctx* c, const uint8_t* d_seq, const uint8_t* d_qual, const uint32_t* d_meta, int64_t nrows, int pitch,
+                            int flags, int k, int qual_byte_min, uint8_t* d_out, uint64_t* d_windows)
+{
+    const char* who = "kbbq_kmer_gate_rows_dev";
+    if (!c) return fail(KBBQ_E_ARG, "%s: NULL ctx", who);
+    bool nib = false;
+    int rc = kmer_row_flags(who, flags, &nib);
+    if (rc) return rc;
+    if (k < 8 || k > 32) return fail(KBBQ_E_ARG, "%s: k must be in 8..32, got %d", who, k);
+    if (qual_byte_min < 1 || qual_byte_min > 255)
+        return fail(KBBQ_E_ARG, "%s: qual_byte_min must be in 1..255, got %d", who, qual_byte_min);
+    KmerParams p; size_t lds = 0;
+    rc = kmer_rows(c, who, k, d_seq, d_meta, nrows, pitch, nib, KM_LDS_GATE, 1, p, &lds);
+    if (rc) return rc;
+    if (nrows > 0 && (!d_qual || !d_out)) return fail(KBBQ_E_ARG, "%s: NULL plane or meta", who);
+    if (nrows > 0 && d_out == d_seq) return fail(KBBQ_E_ARG, "%s: d_out is d_seq: the rows as read must stay", who);
+    if ((uintptr_t)d_qual & 15) return fail(KBBQ_E_ARG, "%s: d_qual not 16-byte aligned", who);
+    if ((uintptr_t)d_out & (nib ? 7 : 15)) return fail(KBBQ_E_ARG, "%s: d_out not %d-byte aligned", who, nib ? 8 : 16);
+    if ((uintptr_t)d_windows & 7) return fail(KBBQ_E_ARG, "%s: d_windows not 8-byte aligned", who);
+    if (nrows == 0) return KBBQ_OK;
+    const KmerGate g = {d_qual, (u32)qual_byte_min, d_out, reinterpret_cast<u64*>(d_windows)};
+    return kmer_launches(c, p, KM_READER(km_gate, nib), lds, nullptr, nullptr, nullptr, &g);
 }
 
 int kbbq_kmer_table_clear_dev(kbbq_ctx* c, kbbq_kmer_table* t)

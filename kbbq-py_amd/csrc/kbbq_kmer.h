@@ -80,6 +80,10 @@
 // more is in `twice`, whatever the thread order.  Bits are only ever set, so a relaxed load that shows the whole mask is
 // final and the atomic is skipped.  km_count_filtered is km_count for the windows whose mask is whole in `twice`: the table
 // then holds every key of count >= 2 with its exact count and some keys of count 1 (false positives), nothing else.
+//
+// Quality gate (kbbq correct --kmer-min-qual Q): km_gate, at the end of this file, writes a copy of the sequence plane with a
+// break wherever the quality byte is below the threshold and counts the windows that are left; every counting kernel above
+// reads that copy as it reads any plane.
 #pragma once
 #include "kbbq_kernels.h"
 
@@ -987,4 +991,74 @@ __global__ __launch_bounds__(KM_THREADS) void km_count_filtered_part(KmerParams 
         atomicMin(p.status + ST_KMER, (u64)(row0 + r));
         return false;
     });
+}
+
+// ---- quality gate: count only the windows of bases with quality >= Q (kbbq correct --kmer-min-qual; kbbq/kmer.py gate_plane) ----
+// A base is countable when it is A/C/G/T and its quality byte is >= qual_byte_min; a window is counted iff all k of its bases
+// are.  The gate only changes which positions are breaks, so it is a pre-pass: km_gate writes a copy of the sequence plane with
+// 'N' (4-bit planes: code 4) wherever the quality byte is below qual_byte_min -- every other byte as read, every byte of every
+// row written, padding and separator included -- and km_prefilter, km_count, km_count_filtered and the _part forms read that
+// copy unchanged.  Nothing after the count reads it: the correction kernels run on the rows as read.
+// Work split: km_count's.  A thread loads its chunk once (km_read_chunk) and the 16 quality bytes beside it (quality planes are
+// [nrows, 16 cpr] characters, at twice the chunk's offset beside nibbles, as km_tally_chunk's), stores the gated chunk
+// (km_write_chunk) and puts the chunk's break mask -- km_load_chunks' mask of the gated bases -- into LDS.  After the barrier it
+// counts the window starts of its chunk that see no break in k bases, km_chunk_windows' test on the masks of its chunk and the
+// next two; the sums meet in one LDS word and every workgroup makes one 64-bit add to *windows (NULL: no count).  Counting
+// `out` with any count kernel inserts exactly that many windows.
+struct KmerGate { const uint8_t* qual; u32 qual_byte_min; uint8_t* out; u64* windows; };
+constexpr KmLds KM_LDS_GATE = {1, 0, 1};        // km_gate: brk; the workgroup's windows
+
+template <bool NIB>
+__global__ __launch_bounds__(KM_THREADS) void km_gate(KmerParams p, KmerGate g)
+{
+    extern __shared__ u32 km_lds[];
+    u32* brk = km_lds_chunk(km_lds, p, 0);
+    u32* sum = km_lds_wg(km_lds, KM_LDS_GATE, p);
+    const int64_t row0 = (int64_t)blockIdx.x * p.rows_per_wg;
+    const int nr = (int)(p.nrows - row0 < p.rows_per_wg ? p.nrows - row0 : p.rows_per_wg);
+    if (threadIdx.x == 0) *sum = 0;
+    for (int e = threadIdx.x; e < nr * p.cpr; e += KM_THREADS) {
+        const int r = e / p.cpr, ch = e - r * p.cpr;
+        const int64_t row = row0 + r;
+        const int L = (int)(p.meta[row] & 0xFFFFu);
+        const size_t at = km_chunk_at<NIB>(p, row, ch);
+        u32 w[4];
+        km_read_chunk<NIB>(p.seq + at, w);
+        const uint4 qv = *reinterpret_cast<const uint4*>(g.qual + (NIB ? 2 * at : at));
+        const u32 q[4] = {qv.x, qv.y, qv.z, qv.w};
+        u32 b = 0;
+        #pragma unroll
+        for (int t = 0; t < 16; ++t) {
+            const bool low = ((q[t >> 2] >> (8 * (t & 3))) & 0xFFu) < g.qual_byte_min;
+            bool base;
+            if constexpr (NIB) {
+                const int sh = km_nib_shift(t & 7);
+                if (low) w[t >> 3] = (w[t >> 3] & ~(0xFu << sh)) | (4u << sh);
+                base = ((w[t >> 3] >> sh) & 0xFu) < 4u;
+            } else {
+                const int sh = 8 * (t & 3);
+                if (low) w[t >> 2] = (w[t >> 2] & ~(0xFFu << sh)) | ((u32)'N' << sh);
+                const u32 x = (w[t >> 2] >> sh) & 0xFFu;
+                base = x == 'A' || x == 'C' || x == 'G' || x == 'T';
+            }
+            b |= (base && ch * 16 + t < L ? 0u : 1u) << t;
+        }
+        km_write_chunk<NIB>(g.out + at, w);
+        brk[e] = b;
+    }
+    if (!g.windows) return;                                               // uniform: a kernel parameter
+    __syncthreads();
+    const u64 kmask = (1ull << p.k) - 1;
+    u32 mine = 0;
+    for (int e = threadIdx.x; e < nr * p.cpr; e += KM_THREADS) {
+        const int r = e / p.cpr, ch = e - r * p.cpr;
+        // the masks of chunks ch .. ch + 2, past the row all breaks: km_breaks' words, spelled out here because a third caller of
+        // km_breaks moved a register in the N-rule forms of km_correct_passes, and no existing kernel is to change
+        u64 m = 0;
+        for (int i = 0; i < 3; ++i) m |= (u64)(ch + i < p.cpr ? brk[e + i] : 0xFFFFu) << (16 * i);
+        for (int o = 0; o < 16; ++o) mine += ((m >> o) & kmask) ? 0u : 1u;
+    }
+    if (mine) atomicAdd(sum, mine);
+    __syncthreads();
+    if (threadIdx.x == 0 && *sum) atomicAdd(g.windows, (u64)*sum);
 }

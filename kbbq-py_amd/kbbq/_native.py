@@ -218,6 +218,7 @@ PROTOTYPES = {
     'kbbq_kmer_correct_rows_ex_dev': (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _vp, _vp, _i]),
     'kbbq_kmer_correct_rows_passes_dev': (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _vp, _vp, _i, _i]),
     'kbbq_kmer_correct_rows_skip_dev': (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp]),
+    'kbbq_kmer_gate_rows_dev': (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _vp, _vp]),
 }
 
 

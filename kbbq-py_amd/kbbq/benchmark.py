@@ -489,7 +489,7 @@ def _kmer_benchmark_inputs(bamfile, k, min_count, prefilter, filter_bits):
 
 
 def benchmark_kmers(bamfile, ref, var_sites, k=31, min_count=None, slots=None, prefilter=False, filter_bits=4, use_oq=False,
-                    bedfh=None, info=None, passes=1, partitions=1):
+                    bedfh=None, info=None, passes=1, partitions=1, kmer_min_qual=None):
     """How good is the k-mer rule on a truth set?  joint[q][truth error][k-mer class], int64 (256, 2, 3): every base of the
     alignments that benchmark_bam counts (not at a variant site, inside the BED, not soft-clipped), by its reported quality
     (QUAL, or the OQ tag with use_oq), by whether it differs from the reference (K4, exactly as benchmark_bam flags it) and
@@ -504,12 +504,25 @@ def benchmark_kmers(bamfile, ref, var_sites, k=31, min_count=None, slots=None, p
     passes: the classes of `passes` passes of the rule (flag_errors(passes=...): 1 where the last pass ends on another letter,
     2 where the base is unchanged and its row's last evaluation left it unresolved); `info` then receives passes too.
     partitions: as gatk.bqsr.bam_to_kmer_covariates' -- the count in that many rounds (kmer.count_partitioned), the classes read
-    from the solid table: the same joint array; with more than one round `info` receives partitions, kept_pairs and solid_slots."""
+    from the solid table: the same joint array; with more than one round `info` receives partitions, kept_pairs and solid_slots.
+    kmer_min_qual = Q (kmer.gate_plane): only the k-mers whose bases all have quality >= Q -- the plane the confusion reads -- are
+    counted; the prefilter, the count and every partition round read the gated copy of SEQ, which sizes the filter and the
+    default table, and the classes are decided for SEQ as read.  A record with bases and without qualities (QUAL '*', or no OQ
+    tag with use_oq) is refused with a ValueError naming it, before any upload.  `info` then receives kmer_min_qual,
+    counted_windows and windows."""
     from . import _device as dev
     from . import kmer
     passes = kmer.check_passes(passes)
     partitions = kmer._check_partitions(partitions)
+    kmer_min_qual = kmer.check_kmer_min_qual(kmer_min_qual)
     b = _kmer_benchmark_inputs(bamfile, k, min_count, prefilter, filter_bits)
+    if kmer_min_qual is not None and b.n:
+        have = b.oq_len if use_oq else b.qual_len
+        bare = np.flatnonzero((have <= 0) & (b.qlen > 0))
+        if bare.size:
+            i = int(bare[0])
+            raise ValueError('record %d (%s) has no %s: benchmark --kmers --kmer-min-qual needs a quality for every base'
+                             % (i, b._text(0, i), 'OQ tag' if use_oq else "qualities (QUAL '*')"))
     k = int(k)
     torch = dev._torch()
     fullskips = get_full_skips(ref, var_sites, bedfh)
@@ -525,28 +538,33 @@ def benchmark_kmers(bamfile, ref, var_sites, k=31, min_count=None, slots=None, p
         d_len = torch.from_numpy(np.ascontiguousarray(lens.astype(np.uint32)).view(np.int32)).cuda()
         budget = dev.device_budget()
         resident = 4 * n * pitch + 20 * n           # SEQ, qualities, the truth flags and the k-mer flags; the per-read words
-        windows = kmer.kmer_total(lens, k)
+        windows = ungated = kmer.kmer_total(lens, k)
+        counted = d_seq                             # the plane the prefilter and the count read
+        if kmer_min_qual is not None:
+            counted, windows = kmer.gate_plane(d_seq, qual, d_len, k, kmer_min_qual)
+            resident += n * pitch                   # ... until the count is over
         filt = table = None
         try:
             if prefilter:
-                filt = kmer.prefilter_kmers(d_seq, d_len, k=k, filter=kmer.KmerFilter(kmer.filter_words(windows, filter_bits)))
+                filt = kmer.prefilter_kmers(counted, d_len, k=k, filter=kmer.KmerFilter(kmer.filter_words(windows, filter_bits)))
                 admitted = filt.admitted
                 filt.release_seen()
             total, room = admitted if prefilter else windows, budget - resident - (filt.nbytes if filt is not None else 0)
             P = kmer.resolve_partitions(partitions, total, room) if partitions != 1 else 1
             if P > 1:
                 table, _, t, parts_info = kmer.count_partitioned(
-                    lambda tab, p: kmer.count_kmers(d_seq, d_len, k=k, table=tab, filter=filt, parts=P, part=p), k, P,
+                    lambda tab, p: kmer.count_kmers(counted, d_len, k=k, table=tab, filter=filt, parts=P, part=p), k, P,
                     slots if slots is not None else kmer.partition_slots(total, P, room), min_count, room)
                 if filt is not None:
                     filt.close()
             else:
                 if slots is None:
                     slots = kmer.default_slots(total, room)
-                table = kmer.count_kmers(d_seq, d_len, k=k, slots=slots, filter=filt)
+                table = kmer.count_kmers(counted, d_len, k=k, slots=slots, filter=filt)
                 if filt is not None:
                     filt.close()
                 t = int(min_count) if min_count is not None else kmer.solid_threshold(kmer.kmer_histogram(table))
+            del counted
             kflags, _, _ = kmer.flag_errors(table, d_seq, d_len, t, unresolved=True, **kmer._passes_kw(passes))
             nslots = parts_info['slots'] if P > 1 else table.slots
         finally:
@@ -563,6 +581,8 @@ def benchmark_kmers(bamfile, ref, var_sites, k=31, min_count=None, slots=None, p
             info.update(passes=passes)
         if P > 1:
             info.update(partitions=P, kept_pairs=parts_info['kept_pairs'], solid_slots=parts_info['solid_slots'])
+        if kmer_min_qual is not None:
+            info.update(kmer_min_qual=kmer_min_qual, counted_windows=windows if n else 0, windows=ungated if n else 0)
     return joint
 
 
@@ -585,6 +605,8 @@ def kmer_summary(info):
         line += ' passes=%d' % info['passes']
     if info.get('partitions', 1) > 1:
         line += ' partitions=%d' % info['partitions']
+    if info.get('kmer_min_qual') is not None:
+        line += ' kmer_min_qual=%d counted_windows=%d' % (info['kmer_min_qual'], info['counted_windows'])
     if info.get('prefilter'):
         line += ' prefilter=1 admitted=%d slots=%d' % (info['admitted'], info['slots'])
     return line
@@ -608,7 +630,7 @@ def print_benchmark_kmers(joint, label):
 
 def benchmark(bamfile, fafile, vcffile, fastqfile=None, label=None, use_oq=False, bedfh=None, kmers=None):
     """Run the benchmark and print it.  With a FASTQ, its reads are matched to the alignments by name.  kmers: a dict of
-    benchmark_kmers' options (k, min_count, slots, prefilter, filter_bits, passes, partitions) -- print the k-mer rule's flags against the truth
+    benchmark_kmers' options (k, min_count, slots, prefilter, filter_bits, passes, partitions, kmer_min_qual) -- print the k-mer rule's flags against the truth
     set's instead (print_benchmark_kmers) and one summary line on stderr."""
     if kmers is not None and fastqfile is not None:
         raise ValueError('benchmark --kmers takes the alignments alone (-b), not a FASTQ joined by name (-f)')

@@ -40,6 +40,15 @@ default_slots(len(kept), budget) (those with keep <= count < t too: no decision 
 pass over the pairs) and the unchanged correct / flag kernels run against it at min_count = t.  The summed histogram (with the
 prefilter: h[2:]), the threshold, every base's decision and every figure printed are those of the one-table path; every round
 hashes every window, which is what the smaller table costs.  count_partitioned is the one statement of it in code.
+
+Quality gate (`kmer_min_qual=Q`, `--kmer-min-qual Q`; tests/kmer_gate_model.py).  THE RULE: a base is countable when it is A/C/G/T
+and its quality -- the plane the command reads anyway -- is >= Q; a window is counted iff all k of its bases are countable.  One
+kernel in front of the count (km_gate, kbbq_kmer_gate_rows_dev; gate_plane / gate_batch) writes a copy of the sequence plane with
+'N' at every base below Q and returns the number of counted windows; the prefilter, the count, every partition round and a
+rank's local count read that copy through the calls they always made, the filter and the default table are sized from the
+counted windows, and the copy is freed when the count is over.  Nothing after the count knows the option: the histogram is the
+gated table's, the threshold its first valley or min_count, and the correction, flag and passes calls run on the rows as read.
+count_gated is correct_reads' count on the gated plane; the other commands put the plane into the counts they already had.
 """
 import ctypes
 import os
@@ -601,25 +610,118 @@ def _batch_rows(batch):
     return N.ptr(batch.seq), N.ptr(batch.meta), int(batch.n), int(batch.pitch), dev._row_flags(batch)
 
 
-def prefilter_batch(batch, k, filter=None, bits=4):
+# ---- the quality gate ---------------------------------------------------------------------------------------------------------
+
+MAX_MIN_QUAL = 93                     # the top of the FASTQ scale: '~' - 33
+
+
+def check_kmer_min_qual(min_qual, have_qual=True):
+    """`min_qual` as an int in 1..MAX_MIN_QUAL, or None when it is None (no gate), else ValueError: checked before any device
+    call and, under ranks, before any collective.  have_qual: False when the caller has no qualities to gate by."""
+    if min_qual is None:
+        return None
+    ok = False
+    if not isinstance(min_qual, (bool, str, bytes)):
+        try:
+            ok = int(min_qual) == min_qual and 1 <= int(min_qual) <= MAX_MIN_QUAL
+        except (TypeError, ValueError):
+            ok = False
+    if not ok:
+        raise ValueError('kmer_min_qual must be an integer in 1..%d, got %r' % (MAX_MIN_QUAL, min_qual))
+    if not have_qual:
+        raise ValueError('kmer_min_qual=%d needs the qualities of the reads: there is no quality plane to gate by' % int(min_qual))
+    return int(min_qual)
+
+
+def _gate_rows(ctx, seq, qual, meta, n, pitch, flags, k, byte_min, out, windows):
+    N.check(N.load().kbbq_kmer_gate_rows_dev(ctx.handle, seq, qual, meta, n, pitch, flags, int(k), int(byte_min), out, windows))
+    ctx.status()
+
+
+def _to_device(T, a, dtype=None):
+    """A host array as a device tensor of the backend in use; a device tensor as it is."""
+    if _on_device(a):
+        return a
+    a = np.ascontiguousarray(a, dtype=dtype)
+    if a.dtype == np.uint32:
+        a = a.view(np.int32)
+    t = T.empty(a.shape if a.size else (1,) + a.shape[1:], dtype=getattr(T, a.dtype.name), device='cuda')
+    if a.size:
+        t[:a.shape[0]].copy_(T.from_numpy(a))
+    return t
+
+
+def gate_plane(seq_plane, qual_plane, meta, k, min_qual, qual_offset=33, windows=None):
+    """The quality gate of character rows, one read a row (kbbq_kmer_gate_rows_dev, flags 0): (gated plane, counted windows).
+    The gated plane is a device copy of seq_plane with 'N' wherever the byte of qual_plane is < min_qual + qual_offset
+    (qual_offset: 33 for character qualities, 0 for a plane of raw Phred values), so every count and prefilter call on it --
+    with the same meta -- sees exactly the windows whose k bases are all A/C/G/T of quality >= min_qual; counted windows is
+    their number.  Host arrays are uploaded (there is no host-buffer form); seq_plane itself is never written.
+    windows: a zeroed one-word int64 device tensor to add to instead of a new one (several planes of one input); the return is
+    then its value after this plane."""
+    from . import _device as dev
+    min_qual = check_kmer_min_qual(min_qual, qual_plane is not None)
+    T = dev._torch()
+    n, pitch = int(seq_plane.shape[0]), int(seq_plane.shape[1])
+    seq, qual, meta = _to_device(T, seq_plane, np.uint8), _to_device(T, qual_plane, np.uint8), _to_device(T, meta, np.uint32)
+    out = T.empty((max(n, 1), pitch), dtype=T.uint8, device='cuda')
+    if windows is None:
+        windows = T.zeros(1, dtype=T.int64, device='cuda')
+    _gate_rows(_ctx(), N.ptr(seq), N.ptr(qual), N.ptr(meta), n, pitch, 0, k, min_qual + int(qual_offset), N.ptr(out), N.ptr(windows))
+    return out[:n], int(windows.cpu().numpy()[0])
+
+
+def gate_batch(batch, k, min_qual, windows=None, qual=None):
+    """gate_plane for the rows of a device batch in whatever layout it has: (gated plane in the layout of batch.seq, counted
+    windows).  The qualities are batch.qual (characters, offset 33) unless `qual` names another plane of that geometry.
+    prefilter_batch / count_batch read the gated plane through their `plane` argument; batch.seq is not written."""
+    from . import _device as dev
+    min_qual = check_kmer_min_qual(min_qual)
+    T = dev._torch()
+    out = T.empty_like(batch.seq)
+    if windows is None:
+        windows = T.zeros(1, dtype=T.int64, device='cuda')
+    seq, meta, n, pitch, flags = _batch_rows(batch)
+    _gate_rows(_ctx(), seq, N.ptr(batch.qual if qual is None else qual), meta, n, pitch, flags, k, min_qual + 33, N.ptr(out),
+               N.ptr(windows))
+    return out, int(windows.cpu().numpy()[0])
+
+
+def min_qual_field(info):
+    """` kmer_min_qual=Q counted_windows=N` of a command's stderr line when its count was gated, else nothing."""
+    if info.get('kmer_min_qual') is None:
+        return ''
+    return ' kmer_min_qual=%d counted_windows=%d' % (info['kmer_min_qual'], info['counted_windows'])
+
+
+def _min_qual_kw(kmer_min_qual, **more):
+    """The keywords for a callee: none without the gate, whose calls are the ones they were before the option."""
+    return dict(kmer_min_qual=kmer_min_qual, **more) if kmer_min_qual is not None else {}
+
+
+def prefilter_batch(batch, k, filter=None, bits=4, plane=None):
     """prefilter_kmers for the rows of a device batch in whatever layout it has (layout_key() reads / reads_nib / pairs /
-    pairs_nib, twins, rows grouped by read group): the same `seen` words as the character planes of the same reads give."""
+    pairs_nib, twins, rows grouped by read group): the same `seen` words as the character planes of the same reads give.
+    plane: a plane of batch.seq's layout to read in its place (gate_batch's)."""
     k = int(k)
     if not 8 <= k <= 32:
         raise ValueError('k must be in 8..32, got %d' % k)
     if filter is None:
         filter = KmerFilter(filter_words(batch_windows(batch, k), bits))
     seq, meta, n, pitch, flags = _batch_rows(batch)
+    if plane is not None:
+        seq = N.ptr(plane)
     ctx = filter.ctx
     N.check(N.load().kbbq_kmer_prefilter_rows_dev(ctx.handle, filter.handle, k, seq, meta, n, pitch, flags))
     ctx.status()
     return filter
 
 
-def count_batch(batch, k=31, table=None, slots=None, filter=None, parts=1, part=0):
+def count_batch(batch, k=31, table=None, slots=None, filter=None, parts=1, part=0, plane=None):
     """count_kmers for the rows of a device batch in whatever layout it has: the reads are counted where they lie.  Keys and
     counts are those of the character planes of the same reads, so batches of different layouts compose in one table.
-    parts, part: as count_kmers' (kbbq_kmer_count*_rows_part_dev)."""
+    parts, part: as count_kmers' (kbbq_kmer_count*_rows_part_dev).  plane: a plane of batch.seq's layout to read in its place
+    (gate_batch's; the default table is still sized from the batch's windows: give `slots`)."""
     from . import _device as dev
     parts, part = _check_part(parts, part)
     if table is None:
@@ -627,6 +729,8 @@ def count_batch(batch, k=31, table=None, slots=None, filter=None, parts=1, part=
             slots = default_slots(filter.admitted if filter is not None else batch_windows(batch, k), dev.device_budget())
         table = KmerTable(k, slots)
     seq, meta, n, pitch, flags = _batch_rows(batch)
+    if plane is not None:
+        seq = N.ptr(plane)
     lib = N.load()
     ctx = table.ctx
     try:
@@ -741,7 +845,7 @@ def count_partitioned(count_round, k, P, slots, min_count, budget):
 
 
 def correct_reads(seq_plane, meta, k=31, min_count=None, slots=None, prefilter=False, filter_bits=4, fix_n=False, passes=1,
-                  partitions=1):
+                  partitions=1, qual_plane=None, kmer_min_qual=None):
     """Count, pick the threshold (min_count, else the histogram's first valley) and correct.  Returns (corrected plane in
     the input's layout and kind, info) with info = {'k', 'min_count', 'hist', 'changed' (per read), 'slots', 'table_bytes',
     'prefilter', 'filter_bytes', 'admitted', 'fix_n', 'passes'}.  passes: the rule applied that many times to each row against
@@ -754,13 +858,23 @@ def correct_reads(seq_plane, meta, k=31, min_count=None, slots=None, prefilter=F
     through a table of `slots` slots (default: partition_slots of the windows -- of `admitted` with the prefilter, whose `twice`
     array lives through all rounds -- in the device budget) and the reads corrected against the solid table of the kept pairs:
     the same plane, changed, min_count and hist (hist[2:] with the prefilter).  info then has 'partitions', 'kept_pairs' and
-    'solid_slots' too, and 'slots' / 'table_bytes' describe the per-partition table.  P = 1 is the path without the option."""
+    'solid_slots' too, and 'slots' / 'table_bytes' describe the per-partition table.  P = 1 is the path without the option.
+    kmer_min_qual = Q (with qual_plane, character qualities at offset 33; gate_plane): only the windows whose k bases all have
+    quality >= Q are counted.  The prefilter, the count and every partition round read the gated plane, which is freed when the
+    count is over; the filter and the default table are sized from the counted windows; the histogram and the threshold are
+    the gated table's; the rows as read are corrected against it.  info then has 'kmer_min_qual', 'counted_windows' and
+    'windows' (the ungated total) too."""
     passes = check_passes(passes)
     partitions = _check_partitions(partitions)
+    kmer_min_qual = check_kmer_min_qual(kmer_min_qual, qual_plane is not None)
+    if prefilter:
+        _check_prefilter(min_count, filter_bits)
+    if kmer_min_qual is not None:
+        return _correct_reads_gated(seq_plane, qual_plane, meta, k, min_count, slots, prefilter, filter_bits, fix_n, passes,
+                                    partitions, kmer_min_qual)
     filt = None
     filter_bytes, admitted = 0, None
     if prefilter:
-        _check_prefilter(min_count, filter_bits)
         filt = prefilter_kmers(seq_plane, meta, k=k, bits=filter_bits)
     table = None
     try:
@@ -798,18 +912,90 @@ def correct_reads(seq_plane, meta, k=31, min_count=None, slots=None, prefilter=F
             table.close()
 
 
+def count_gated(read, windows, k, min_count=None, slots=None, prefilter=False, filter_bits=4, partitions=1):
+    """The count of a gated input: read(what, **kw) runs kmer's prefilter (what = 'prefilter', kw:
+    filter) or count (what = 'count', kw: table, filter, parts, part) over ALL gated rows of the input and returns nothing;
+    `windows` is the input's counted windows, which size the filter and the default table(s) (`slots` overrides).  Returns
+    (table, hist, t, info) as the ungated paths make them: the table the correct / flag kernels read at min_count = t, the
+    histogram of the gated table (with the prefilter: h[2:]), and info = {'slots', 'table_bytes', 'filter_bytes', 'admitted'}
+    plus count_partitioned's with more than one partition.  The caller has checked its options; it closes the table."""
+    from . import _device as dev
+    budget = dev.device_budget()
+    filt = table = None
+    filter_bytes, admitted = 0, None
+    try:
+        if prefilter:
+            filt = KmerFilter(filter_words(windows, filter_bits))
+            read('prefilter', filter=filt)
+            filter_bytes, admitted = filt.nbytes, filt.admitted
+            filt.release_seen()
+        total = admitted if filt is not None else int(windows)
+        P = resolve_partitions(partitions, total, budget) if partitions != 1 else 1
+        if P > 1:
+            table, hist, t, more = count_partitioned(lambda tab, p: read('count', table=tab, filter=filt, parts=P, part=p), k, P,
+                                                     slots if slots is not None else partition_slots(total, P, budget), min_count,
+                                                     budget)
+        else:
+            table = KmerTable(k, slots if slots is not None else default_slots(total, budget))
+            read('count', table=table, filter=filt, parts=1, part=0)
+            hist = kmer_histogram(table)
+            t = int(min_count) if min_count is not None else solid_threshold(hist)
+            more = {}
+        if t < 1:
+            raise ValueError('min_count must be >= 1, got %d' % t)
+        info = dict(dict(slots=table.slots, table_bytes=table.nbytes, filter_bytes=filter_bytes, admitted=admitted), **more)
+        done, table = table, None
+        return done, hist, t, info
+    finally:
+        if filt is not None:
+            filt.close()
+        if table is not None:
+            table.close()
+
+
+def _correct_reads_gated(seq_plane, qual_plane, meta, k, min_count, slots, prefilter, filter_bits, fix_n, passes, partitions, Q):
+    """correct_reads with the quality gate in front of its count."""
+    from . import _device as dev
+    T = dev._torch()
+    d_meta = _to_device(T, meta, np.uint32)
+    gated, counted = gate_plane(seq_plane, qual_plane, d_meta, k, Q)
+    state = dict(plane=gated)
+    del gated
+
+    def read(what, filter=None, table=None, parts=1, part=0):
+        if what == 'prefilter':
+            prefilter_kmers(state['plane'], d_meta, k=k, filter=filter)
+        else:
+            count_kmers(state['plane'], d_meta, k=k, table=table, filter=filter, parts=parts, part=part)
+    table = None
+    try:
+        table, hist, t, more = count_gated(read, counted, k, min_count=min_count, slots=slots, prefilter=prefilter,
+                                           filter_bits=filter_bits, partitions=partitions)
+        state.clear()                        # the gated plane is freed here: the correction reads the rows as read
+        out, changed = correct_with(table, seq_plane, meta, t, fix_n=fix_n, **_passes_kw(passes))
+        return out, dict(dict(k=table.k, min_count=t, hist=hist, changed=changed, prefilter=bool(prefilter), fix_n=bool(fix_n),
+                              passes=passes, kmer_min_qual=Q, counted_windows=counted, windows=kmer_total(_host_meta(meta), k)),
+                         **more)
+    finally:
+        state.clear()
+        if table is not None:
+            table.close()
+
+
 def correct_fastq(path, out, k=31, min_count=None, slots=None, local_slots=None, prefilter=False, filter_bits=4, fix_n=False,
-                  passes=1, partitions=1):
+                  passes=1, partitions=1, kmer_min_qual=None):
     """Correct every read of a FASTQ file (plain or .gz) and write '@' + name, the corrected sequence, '+' and the qualities
     as read to `out` (a path, or a text stream).  Returns correct_reads' info.  In a process group of several ranks (or of
-    one with KBBQ_DIST_ALWAYS=1) this is correct_fastq_ranks, which has no prefilter and no partitions."""
+    one with KBBQ_DIST_ALWAYS=1) this is correct_fastq_ranks, which has no prefilter and no partitions.  kmer_min_qual: the
+    quality gate of correct_reads, by the file's own quality lines."""
     passes = check_passes(passes)
     partitions = _check_partitions(partitions)
+    kmer_min_qual = check_kmer_min_qual(kmer_min_qual)
     if prefilter:
         _check_prefilter(min_count, filter_bits)
     if _ranks() is not None:
         return correct_fastq_ranks(path, out, k=k, min_count=min_count, slots=slots, local_slots=local_slots, fix_n=fix_n,
-                                   **_passes_kw(passes))
+                                   **_passes_kw(passes), **_min_qual_kw(kmer_min_qual))
     from . import fastx
     fq = fastx.NativeFastq(path)
     try:
@@ -820,7 +1006,8 @@ def correct_fastq(path, out, k=31, min_count=None, slots=None, local_slots=None,
     finally:
         fq.close()
     fixed, info = correct_reads(seq, meta, k=k, min_count=min_count, slots=slots, prefilter=prefilter, filter_bits=filter_bits,
-                                fix_n=fix_n, **_passes_kw(passes), **_partitions_kw(partitions))
+                                fix_n=fix_n, **_passes_kw(passes), **_partitions_kw(partitions),
+                                **_min_qual_kw(kmer_min_qual, qual_plane=qual))
     text = fastx.format_fastq(names, fixed, qual, meta & 0xFFFF)
     if isinstance(out, str):
         with open(out, 'w', encoding='latin-1', newline='') as fh:
@@ -833,11 +1020,13 @@ def correct_fastq(path, out, k=31, min_count=None, slots=None, local_slots=None,
 
 
 def main_correct(path, output=None, k=31, min_count=None, slots=None, local_slots=None, prefilter=False, filter_bits=4, fix_n=False,
-                 passes=1, partitions=1):
+                 passes=1, partitions=1, kmer_min_qual=None):
     """`kbbq correct`: the corrected FASTQ to `output` or stdout; the threshold and the changed bases to stderr (once, by rank
     0, with the figures of all ranks); with fix_n ` fix_n=1`; with passes = P > 1 ` passes=P`; with more than one partition
-    (given, or resolved from 'auto') ` partitions=P`; with the prefilter also the admitted k-mers and the table's slots."""
+    (given, or resolved from 'auto') ` partitions=P`; with the quality gate ` kmer_min_qual=Q counted_windows=N`; with the
+    prefilter also the admitted k-mers and the table's slots."""
     passes = check_passes(passes)                        # every rank refuses, before its first collective
+    kmer_min_qual = check_kmer_min_qual(kmer_min_qual)   # ... this too
     partitions = _check_partitions(partitions)           # ... this too: a process group takes no partitions
     if prefilter:
         _check_prefilter(min_count, filter_bits)         # every rank refuses, before its first collective
@@ -845,12 +1034,13 @@ def main_correct(path, output=None, k=31, min_count=None, slots=None, local_slot
     if ranks is None:
         info = correct_fastq(path, output if output else sys.stdout, k=k, min_count=min_count, slots=slots,
                              prefilter=prefilter, filter_bits=filter_bits, fix_n=fix_n, **_passes_kw(passes),
-                             **_partitions_kw(partitions))
+                             **_partitions_kw(partitions), **_min_qual_kw(kmer_min_qual))
         changed = int(np.asarray(info['changed'], dtype=np.int64).sum())
     else:
         try:
             info = correct_fastq_ranks(path, output if output else sys.stdout, k=k, min_count=min_count, slots=slots,
-                                       local_slots=local_slots, fix_n=fix_n, **_passes_kw(passes))
+                                       local_slots=local_slots, fix_n=fix_n, **_passes_kw(passes),
+                                       **_min_qual_kw(kmer_min_qual))
         except Exception as exc:
             if not getattr(exc, 'every_rank', False):
                 raise
@@ -863,9 +1053,9 @@ def main_correct(path, output=None, k=31, min_count=None, slots=None, local_slot
         changed = info['changed_bases']
         if ranks[1] != 0:
             return info
-    sys.stderr.write('kbbq correct: k=%d min_count=%d reads=%d changed_bases=%d%s%s%s%s\n'
+    sys.stderr.write('kbbq correct: k=%d min_count=%d reads=%d changed_bases=%d%s%s%s%s%s\n'
                      % (info['k'], info['min_count'], info['reads'], changed, ' fix_n=1' if fix_n else '',
-                        ' passes=%d' % passes if passes > 1 else '', partitions_field(info),
+                        ' passes=%d' % passes if passes > 1 else '', partitions_field(info), min_qual_field(info),
                         ' prefilter=1 admitted=%d slots=%d' % (info['admitted'], info['slots']) if prefilter else ''))
     return info
 
@@ -905,18 +1095,21 @@ def _rounds(meta, k, cap):
     return out
 
 
-def count_kmers_ranks(seq_plane, meta, k=31, slots=None, local_slots=None, windows=None):
+def count_kmers_ranks(seq_plane, meta, k=31, slots=None, local_slots=None, windows=None, mine=None):
     """This rank's OWNER table: the global count of every k-mer whose owner() is this rank.  Every rank calls it with its own
     rows (host arrays).  The rows are counted into a local table of `local_slots` slots (default: the shard's windows at a
     load factor of 0.5, capped by half the device budget) in rounds of contiguous rows that fit it; after every round the
     occupied slots go to their owners in one exchange and are merged there.  The owner table has `slots` slots (default: the
     global windows / world * 9/8 at a load factor of 0.5, capped by the budget); `windows` is the global number of windows
-    (summed over the ranks when None).  A table that fills on any rank raises on every rank."""
+    (summed over the ranks when None).  A table that fills on any rank raises on every rank.  mine: this rank's windows when
+    they are fewer than its sidecars say (a gated shard, whose plane seq_plane then is; the rounds are still cut by the
+    sidecars, an upper bound)."""
     from . import _device as dev
     from . import parallel
     world, _ = parallel.world_rank()
     meta = np.ascontiguousarray(meta, dtype=np.uint32)
-    mine = kmer_total(meta, k)
+    if mine is None:
+        mine = kmer_total(meta, k)
     if windows is None:
         windows = int(parallel.sum_over_ranks(np.array([mine], dtype=np.int64))[0])
     owned = local = exc = None
@@ -1023,15 +1216,18 @@ def _read_shard(path, rank, world):
     return names, seq, qual, meta
 
 
-def correct_fastq_ranks(path, out, k=31, min_count=None, slots=None, local_slots=None, fix_n=False, passes=1):
+def correct_fastq_ranks(path, out, k=31, min_count=None, slots=None, local_slots=None, fix_n=False, passes=1, kmer_min_qual=None):
     """correct_fastq on every rank of the process group: each rank reads, counts and corrects its own records and writes them
     to `out`.rankNNNN (`out` itself with one rank) or, for a stream, to `out` in rank order.  The threshold comes from the
     global histogram; info carries this rank's per-read changes and the global 'reads' and 'changed_bases'.  fix_n: every rank
     decides its Ns against the gathered solid table at min_count = t, as one process would against the whole table.  passes:
-    solidity is all the passes ask of the table too, so the rank files concatenated stay the one-process output."""
+    solidity is all the passes ask of the table too, so the rank files concatenated stay the one-process output.
+    kmer_min_qual: every rank gates its own shard before its local count (gate_plane) and its counted windows size the tables;
+    info['counted_windows'] is their sum over the ranks, info['windows'] the ungated total."""
     from . import fastx
     from . import parallel
     passes = check_passes(passes)
+    kmer_min_qual = check_kmer_min_qual(kmer_min_qual)
     world, rank = parallel.world_rank()
     shard = exc = None
     try:
@@ -1040,9 +1236,22 @@ def correct_fastq_ranks(path, out, k=31, min_count=None, slots=None, local_slots
         exc = e
     _agree(exc)
     names, seq, qual, meta = shard
-    everyone = parallel.all_gather_object((len(names), kmer_total(meta, k)))
+    gated = mine = exc = None
+    if kmer_min_qual is not None:
+        try:
+            gated, mine = gate_plane(seq, qual, meta, k, kmer_min_qual)
+            gated = gated.cpu().numpy()      # the local count reads host rows, round by round
+        except Exception as e:               # noqa: BLE001
+            exc = e
+        _agree(exc)
+    everyone = parallel.all_gather_object((len(names), kmer_total(meta, k)) + (() if gated is None else (mine,)))
     reads, windows = sum(x[0] for x in everyone), sum(x[1] for x in everyone)
-    owned = count_kmers_ranks(seq, meta, k=k, slots=slots, local_slots=local_slots, windows=windows)
+    if gated is None:
+        owned = count_kmers_ranks(seq, meta, k=k, slots=slots, local_slots=local_slots, windows=windows)
+    else:
+        counted = sum(x[2] for x in everyone)
+        owned = count_kmers_ranks(gated, meta, k=k, slots=slots, local_slots=local_slots, windows=counted, mine=mine)
+        del gated
     hist = None
     if min_count is None:
         hist = kmer_histogram_ranks(owned)
@@ -1070,5 +1279,8 @@ def correct_fastq_ranks(path, out, k=31, min_count=None, slots=None, local_slots
             out.write(text)
             out.flush()
         parallel.in_rank_order(write)
-    return dict(k=k, min_count=t, hist=hist, changed=changed, reads=reads, changed_bases=total, fix_n=bool(fix_n),
+    info = dict(k=k, min_count=t, hist=hist, changed=changed, reads=reads, changed_bases=total, fix_n=bool(fix_n),
                 passes=passes)
+    if kmer_min_qual is not None:
+        info.update(kmer_min_qual=kmer_min_qual, counted_windows=counted, windows=windows)
+    return info

@@ -38,6 +38,17 @@ def _partitions(text):
     return value
 
 
+def _min_qual(text):
+    """--kmer-min-qual Q: an integer in 1..93 (kmer.check_kmer_min_qual)."""
+    try:
+        value = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError('%r is not an integer' % text) from None
+    if not 1 <= value <= 93:
+        raise argparse.ArgumentTypeError('must be in 1..93, got %d' % value)
+    return value
+
+
 def _exclude_flags(text):
     """-F / --exclude-flags INT: SAM FLAG bits, decimal or 0x.., in 0..0xFFFF."""
     try:
@@ -95,6 +106,12 @@ _PARTITIONS_HELP = ('%s: count the k-mers in this many rounds, 1..64 (default 1)
                     'only: a process group splits the k-mers over its ranks already (correct --local-slots)')
 
 
+_MIN_QUAL_HELP = ('%s: count only the k-mers whose bases all have quality >= Q, 1..93 (default: every k-mer): the errors sit at the '
+                  'low-quality bases, so the table, sized from the counted k-mers, is several times smaller and the histogram\'s '
+                  'valley is cleaner.  The reads are corrected as read: a low-quality base is trusted through the k-mers other '
+                  'reads contributed.  The qualities are the ones the command reads%s')
+
+
 _PASSES_HELP = ('%s: apply the k-mer rule to its own output this many times, 1..8 (default 1), read by read against the one table '
                 'counted from the reads as read: an error next to a read end or to another error is corrected once its '
                 'neighbour is')
@@ -120,6 +137,8 @@ def _recalibrate_bam_kmers(args):
         kmers['mixed_lengths'] = True
     if args.exclude_flags:
         kmers['exclude_flags'] = args.exclude_flags
+    if args.kmer_min_qual is not None:
+        kmers['kmer_min_qual'] = args.kmer_min_qual
     records = {key: kmers[key] for key in ('mixed_lengths', 'exclude_flags') if key in kmers}
     # every rank of a launcher refuses here, before it joins the process group
     _recal.check_bam_kmers(args.bam, args.gatkreport, args.output, kmers['k'], kmers['min_count'], kmers['prefilter'],
@@ -136,11 +155,12 @@ def _recalibrate_bam_kmers(args):
             _device.use_native_memory()          # as `bqsr --kmers` on one GPU: no torch import
         info = _recal.recalibrate_bam(bam, use_oq=args.use_oq, set_oq=args.set_oq, kmers=kmers, gatkreport=args.gatkreport,
                                       output=args.output, **args.quantize)
-    sys.stderr.write('kbbq recalibrate: k=%d min_count=%d reads=%d%s flagged_bases=%d%s%s%s%s\n'
+    sys.stderr.write('kbbq recalibrate: k=%d min_count=%d reads=%d%s flagged_bases=%d%s%s%s%s%s\n'
                      % (info['k'], info['min_count'], info['reads'],
                         ' excluded_reads=%d' % info['excluded_reads'] if args.exclude_flags else '', info['flagged_bases'],
                         ' skipped_bases=%d' % info['skipped_bases'] if args.skip_unresolved else '',
                         ' passes=%d' % args.passes if (args.passes or 1) > 1 else '', kmer.partitions_field(info),
+                        kmer.min_qual_field(info),
                         ' prefilter=1 admitted=%d slots=%d' % (info['admitted'], info['slots']) if args.prefilter else ''))
 
 
@@ -159,6 +179,8 @@ def recalibrate(args):
             kopts['passes'] = args.passes
         if args.skip_unresolved:
             kopts['skip_unresolved'] = True
+        if args.kmer_min_qual is not None:
+            kopts['kmer_min_qual'] = args.kmer_min_qual
         more = {}
         if args.partitions is not None:
             kopts['partitions'] = args.partitions
@@ -182,12 +204,13 @@ def recalibrate(args):
         with stage('[recalibrate_corrected, wall]'):
             info = _recal.recalibrate_corrected(args.correct, infer_rg=args.infer_rg, gatkreport=args.gatkreport, output=args.output,
                                                 **kopts, **args.quantize)
-        from .kmer import partitions_field
-        sys.stderr.write('kbbq recalibrate: k=%d min_count=%d reads=%d changed_bases=%d%s%s%s%s%s\n'
+        from .kmer import min_qual_field, partitions_field
+        sys.stderr.write('kbbq recalibrate: k=%d min_count=%d reads=%d changed_bases=%d%s%s%s%s%s%s\n'
                          % (info['k'], info['min_count'], info['reads'], info['changed_bases'],
                             ' skipped_bases=%d' % info['skipped_bases'] if kopts.get('skip_unresolved') else '',
                             ' fix_n=1' if kopts.get('fix_n') else '',
                             ' passes=%d' % kopts['passes'] if kopts.get('passes', 1) > 1 else '', partitions_field(info),
+                            min_qual_field(info),
                             ' prefilter=1 admitted=%d slots=%d' % (info['admitted'], info['slots']) if kopts['prefilter'] else ''))
         return
     _recal.recalibrate(bam=args.bam, fastq=args.fastq, infer_rg=args.infer_rg,
@@ -206,6 +229,8 @@ def benchmark(args):
             kmers['kmers']['passes'] = args.passes
         if args.partitions is not None:
             kmers['kmers']['partitions'] = args.partitions
+        if args.kmer_min_qual is not None:
+            kmers['kmers']['kmer_min_qual'] = args.kmer_min_qual
     _bm.benchmark(bamfile=args.bam, fafile=args.reference, vcffile=args.vcf, fastqfile=args.fastq,
                   label=args.label, use_oq=args.use_oq, bedfh=args.bedfile, **kmers)
 
@@ -237,15 +262,18 @@ def bqsr(args):
             more['mixed_lengths'] = True
         if args.exclude_flags:
             more['exclude_flags'] = args.exclude_flags
+        if args.kmer_min_qual is not None:
+            more['kmer_min_qual'] = args.kmer_min_qual
         _bqsr.bam_to_report_kmers(aln.AlignmentFile(args.bam), k=31 if args.kmer is None else args.kmer, min_count=args.min_count,
                                   slots=args.slots, prefilter=args.prefilter,
                                   filter_bits=4 if args.filter_bits is None else args.filter_bits, use_oq=args.use_oq,
                                   info=info, **skip, **more).write(args.gatkreport)
-        sys.stderr.write('kbbq bqsr: k=%d min_count=%d reads=%d%s flagged_bases=%d%s%s%s%s\n'
+        sys.stderr.write('kbbq bqsr: k=%d min_count=%d reads=%d%s flagged_bases=%d%s%s%s%s%s\n'
                          % (info['k'], info['min_count'], info['reads'],
                             ' excluded_reads=%d' % info['excluded_reads'] if args.exclude_flags else '', info['flagged_bases'],
                             ' skipped_bases=%d' % info['skipped_bases'] if skip else '',
                             ' passes=%d' % args.passes if (args.passes or 1) > 1 else '', kmer.partitions_field(info),
+                            kmer.min_qual_field(info),
                             ' prefilter=1 admitted=%d slots=%d' % (info['admitted'], info['slots']) if args.prefilter else ''))
         return
     from . import benchmark as _bm
@@ -268,6 +296,8 @@ def correct(args):
     more = dict(passes=args.passes) if args.passes is not None else {}         # without the option the call is what it was
     if args.partitions is not None:
         more['partitions'] = args.partitions
+    if args.kmer_min_qual is not None:
+        more['kmer_min_qual'] = args.kmer_min_qual
     kmer.main_correct(args.fastq, output=args.output, k=args.kmer, min_count=args.min_count, slots=args.slots,
                       local_slots=args.local_slots, prefilter=args.prefilter, filter_bits=args.filter_bits, fix_n=args.fix_n, **more)
 
@@ -312,6 +342,8 @@ def main(argv=None):
                          'correct --fix-n`)')
     rp.add_argument('--passes', type=_passes, default=None, metavar='P', help=_PASSES_HELP % 'with -c')
     rp.add_argument('--partitions', type=_partitions, default=None, metavar='P|auto', help=_PARTITIONS_HELP % 'with -c')
+    rp.add_argument('--kmer-min-qual', type=_min_qual, default=None, metavar='Q',
+                    help=_MIN_QUAL_HELP % ('with -c, or with -b --kmers', ': the FASTQ quality lines, QUAL, or the OQ tag with -u'))
     rp.add_argument('--skip-unresolved', action='store_true',
                     help='with -c: leave a base out of the tally (neither error nor observation) when the k-mers contradict it but '
                          'name no replacement -- two errors within k bases, thin coverage, contamination -- instead of counting '
@@ -360,6 +392,8 @@ def main(argv=None):
                     help='with --kmers --prefilter: bits per k-mer of the input in each of the filter\'s two arrays, 1..64 (default 4)')
     bp.add_argument('--passes', type=_passes, default=None, metavar='P', help=_PASSES_HELP % 'with --kmers')
     bp.add_argument('--partitions', type=_partitions, default=None, metavar='P|auto', help=_PARTITIONS_HELP % 'with --kmers')
+    bp.add_argument('--kmer-min-qual', type=_min_qual, default=None, metavar='Q',
+                    help=_MIN_QUAL_HELP % ('with --kmers', ': QUAL, or the OQ tag with -u; a record without qualities is refused'))
     bp.set_defaults(command=benchmark)
 
     ap = sub.add_parser('applybqsr', description='Recalibrate alignments with a GATK recalibration report (SAM output)')
@@ -406,6 +440,8 @@ def main(argv=None):
                          'counting it as correct')
     qp.add_argument('--passes', type=_passes, default=None, metavar='P', help=_PASSES_HELP % 'with --kmers')
     qp.add_argument('--partitions', type=_partitions, default=None, metavar='P|auto', help=_PARTITIONS_HELP % 'with --kmers')
+    qp.add_argument('--kmer-min-qual', type=_min_qual, default=None, metavar='Q',
+                    help=_MIN_QUAL_HELP % ('with --kmers', ': QUAL, or the OQ tag with -u'))
     qp.set_defaults(command=bqsr)
 
     cp = sub.add_parser('correct', description='Correct substitution errors of a FASTQ file with k-mer counts (GPU); the output '
@@ -433,6 +469,8 @@ def main(argv=None):
                          'stays N on a tie or when no letter makes a solid k-mer; a fixed N counts as a changed base')
     cp.add_argument('--passes', type=_passes, default=None, metavar='P', help=_PASSES_HELP % 'the whole rule (with --fix-n the N rule too)')
     cp.add_argument('--partitions', type=_partitions, default=None, metavar='P|auto', help=_PARTITIONS_HELP % 'one GPU')
+    cp.add_argument('--kmer-min-qual', type=_min_qual, default=None, metavar='Q',
+                    help=_MIN_QUAL_HELP % ('one GPU or several', ': the FASTQ quality lines'))
     cp.add_argument('-o', '--output', default=None,
                     help='Write the corrected FASTQ to this file instead of stdout; under torch.distributed.run every rank '
                          'writes FILE.rankNNNN, to be concatenated in rank order.')
@@ -447,6 +485,9 @@ def main(argv=None):
                  if v is not None]
         if given:
             rp.error('%s: only with -b --kmers' % ', '.join(given))
+    if args.command is recalibrate and args.kmer_min_qual is not None and args.correct is None \
+            and not (args.kmers and args.bam is not None):
+        rp.error('--kmer-min-qual: only with -c/--correct or with -b --kmers')
     if args.command is recalibrate and args.kmers:
         if args.bam is None:
             rp.error('--kmers: only with -b/--bam (-c/--correct corrects and recalibrates a FASTQ file)')
@@ -468,7 +509,8 @@ def main(argv=None):
         else:
             given = [flag for flag, v in (('-k/--kmer', args.kmer), ('--min-count', args.min_count), ('--slots', args.slots),
                                           ('--prefilter', args.prefilter or None), ('--filter-bits', args.filter_bits),
-                                          ('--passes', args.passes), ('--partitions', args.partitions)) if v is not None]
+                                          ('--passes', args.passes), ('--partitions', args.partitions),
+                                          ('--kmer-min-qual', args.kmer_min_qual)) if v is not None]
             if given:
                 bp.error('%s: only with --kmers' % ', '.join(given))
     if args.command is bqsr:
@@ -482,7 +524,7 @@ def main(argv=None):
                                           ('-u/--use-oq', args.use_oq or None),
                                           ('--skip-unresolved', args.skip_unresolved or None), ('--passes', args.passes),
                                           ('--partitions', args.partitions), ('--mixed-lengths', args.mixed_lengths or None),
-                                          ('-F/--exclude-flags', args.exclude_flags))
+                                          ('-F/--exclude-flags', args.exclude_flags), ('--kmer-min-qual', args.kmer_min_qual))
                      if v is not None]
             if given:
                 qp.error('%s: only with --kmers' % ', '.join(given))

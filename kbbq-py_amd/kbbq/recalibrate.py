@@ -406,7 +406,8 @@ def check_corrected(path, gatkreport=None, k=31, min_count=None, prefilter=False
 
 
 def recalibrate_corrected(path, infer_rg=False, gatkreport=None, output=None, k=31, min_count=None, slots=None, prefilter=False,
-                          filter_bits=4, fix_n=False, passes=1, skip_unresolved=False, partitions=1, quantize=None):
+                          filter_bits=4, fix_n=False, passes=1, skip_unresolved=False, partitions=1, quantize=None,
+                          kmer_min_qual=None):
     """`kbbq correct` and `kbbq recalibrate -f reads corrected` in one run over ONE file: the reads go to the device once, in
     the layout pass 2 uses (fastx.pack_single), their k-mers are counted and the reads corrected where they lie
     (kmer.count_batch / correct_batch: the corrected plane is each band's cseq), and the tally, the solve, the apply and the
@@ -427,15 +428,21 @@ def recalibrate_corrected(path, infer_rg=False, gatkreport=None, output=None, k=
     the table kept until the tally is over is the solid table, against which the bands -- those redone as character rows too --
     are corrected.  The same bytes; info then carries partitions, kept_pairs and solid_slots, and slots is the per-partition table.
     quantize: recalibrate_fastq's -- the written qualities only; the correction, the tally and the model do not see it.
+    kmer_min_qual: `kbbq correct --kmer-min-qual Q` (kmer.gate_batch): every band is gated by its own quality plane, in its own
+    layout, into one word of counted windows; the prefilter, the count and every partition round read the gated planes, which
+    are held until the count is over (one sequence plane per band) and size the filter and the default table; the bands are
+    corrected and tallied as read.  info then carries kmer_min_qual, counted_windows and windows.
     One process, mapped inputs, reads that fit the device budget: anything else raises ValueError naming the two commands."""
     from . import kmer
     quantize = applybqsr._check_qmap(quantize)
     passes = kmer.check_passes(passes)
+    kmer_min_qual = kmer.check_kmer_min_qual(kmer_min_qual)
     check_corrected(path, gatkreport, k, min_count, prefilter, filter_bits, **kmer._partitions_kw(partitions))
     done_with = []
     try:
         return _recalibrate_corrected(path, infer_rg, gatkreport, output, int(k), min_count, slots, prefilter, filter_bits, done_with,
-                                      bool(fix_n), passes, bool(skip_unresolved), partitions, quantize)
+                                      bool(fix_n), passes, bool(skip_unresolved), partitions, quantize,
+                                      **kmer._min_qual_kw(kmer_min_qual))
     finally:
         for reader in done_with:
             fastx.close_later(reader)
@@ -447,7 +454,7 @@ def _batch_bytes(batch):
 
 
 def _recalibrate_corrected(path, infer_rg, gatkreport, output, k, min_count, slots, prefilter, filter_bits, done_with, fix_n=False,
-                           passes=1, skip=False, partitions=1, quantize=None):
+                           passes=1, skip=False, partitions=1, quantize=None, kmer_min_qual=None):
     from . import kmer
     more = kmer._passes_kw(passes)
     if skip:
@@ -483,6 +490,16 @@ def _recalibrate_corrected(path, infer_rg, gatkreport, output, k, min_count, slo
         if any(b.get('laid') is not None for b in single['bands']) else 0
     table = filt = None
     read_quals = []                   # skip: (batch, its qualities as read) while the tally plane stands in their place
+    gated = [None] * len(rows)        # kmer_min_qual: the plane of each band the prefilter and the count read in the place of its seq
+    if kmer_min_qual is not None:
+        with stage('k-mer gate', sync=True):
+            word = dev._torch().zeros(1, dtype=dev._torch().int64, device='cuda')
+            for i, r in enumerate(rows):
+                gated[i], counted = kmer.gate_batch(r, k, kmer_min_qual, windows=word)
+            del word
+        info.update(kmer_min_qual=kmer_min_qual, counted_windows=counted, windows=windows)
+        windows = counted
+        resident += sum(int(g.numel()) for g in gated)       # ... until the count is over
 
     def tally_plane(batch):
         read_quals.append((batch, batch.qual))
@@ -492,8 +509,8 @@ def _recalibrate_corrected(path, infer_rg, gatkreport, output, k, min_count, slo
             if prefilter:
                 with stage('k-mer prefilter', sync=True):
                     filt = kmer.KmerFilter(kmer.filter_words(windows, filter_bits))
-                    for r in rows:
-                        kmer.prefilter_batch(r, k, filter=filt)
+                    for r, g in zip(rows, gated):
+                        kmer.prefilter_batch(r, k, filter=filt, plane=g)
                     info['admitted'] = filt.admitted
                     filt.release_seen()
             total = info['admitted'] if prefilter else windows
@@ -501,8 +518,8 @@ def _recalibrate_corrected(path, infer_rg, gatkreport, output, k, min_count, slo
             P = kmer.resolve_partitions(partitions, total, room) if partitions != 1 else 1
             if P > 1:
                 def count_round(tab, p):
-                    for r in rows:
-                        kmer.count_batch(r, k, table=tab, filter=filt, parts=P, part=p)
+                    for r, g in zip(rows, gated):
+                        kmer.count_batch(r, k, table=tab, filter=filt, parts=P, part=p, plane=g)
                 with stage('k-mer count', sync=True):
                     table, hist, t, parts_info = kmer.count_partitioned(
                         count_round, k, P, slots if slots is not None else kmer.partition_slots(total, P, room), min_count, room)
@@ -511,8 +528,8 @@ def _recalibrate_corrected(path, infer_rg, gatkreport, output, k, min_count, slo
                     slots = kmer.default_slots(total, room)
                 with stage('k-mer count', sync=True):
                     table = kmer.KmerTable(k, slots)
-                    for r in rows:
-                        kmer.count_batch(r, k, table=table, filter=filt)
+                    for r, g in zip(rows, gated):
+                        kmer.count_batch(r, k, table=table, filter=filt, plane=g)
         except (ValueError, dev.N.KmerTableFull) as exc:
             if 'slots' not in str(exc):
                 raise
@@ -521,6 +538,7 @@ def _recalibrate_corrected(path, infer_rg, gatkreport, output, k, min_count, slo
         if filt is not None:
             filt.close()
             filt = None
+        del gated[:]                                   # the count is over: everything below reads the bands as read
         if P > 1:
             info.update(parts_info, hist=hist)
         else:
@@ -856,7 +874,7 @@ def _as_bam_kmers(exc):
 
 
 def check_bam_kmers(bam, gatkreport=None, output=None, k=31, min_count=None, prefilter=False, filter_bits=4, partitions=1, passes=1,
-                    exclude_flags=0):
+                    exclude_flags=0, kmer_min_qual=None):
     """What recalibrate_bam refuses of its options, before the alignments are read, before any device work and, under a
     launcher, before the process group exists: a process group, what `bqsr --kmers` refuses of the k-mer options (the same
     exception types), an output name ending in .bam and a report that exists."""
@@ -868,6 +886,7 @@ def check_bam_kmers(bam, gatkreport=None, output=None, k=31, min_count=None, pre
     try:
         kmer.check_passes(passes)
         kmer._check_partitions(partitions)
+        kmer.check_kmer_min_qual(kmer_min_qual)
         if not 8 <= int(k) <= 32:
             raise ValueError('k must be in 8..32, got %d' % int(k))
         if min_count is not None and int(min_count) < 1:
@@ -900,7 +919,7 @@ def check_bam_records(bam, use_oq=False, k=31, min_count=None, prefilter=False, 
 def recalibrate_bam(bam, use_oq=False, set_oq=False, kmers=None, gatkreport=None, output=None, quantize=None):
     """Without kmers: not implemented, as in the reference.
     bam: a path, or an aln.AlignmentFile.  kmers (a dict of bam_to_kmer_covariates' k-mer options: k, min_count, slots, prefilter, filter_bits, skip_unresolved, passes,
-    partitions, mixed_lengths, exclude_flags -- a record that exclude_flags leaves out of the model is still recalibrated and
+    partitions, mixed_lengths, exclude_flags, kmer_min_qual -- a record that exclude_flags leaves out of the model is still recalibrated and
     written like any other): `kbbq bqsr -b bam --kmers ... [-u] -g R` and `kbbq applybqsr -b bam -g R [-u] [-s] [-o output]` in one run, the
     same bytes to stdout or `output` -- SAM text, the header as read.  The file is parsed once; SEQ and the source qualities
     (QUAL, or OQ with use_oq) go to the device once and the count, the flags, the tally (gatk.bqsr._kmer_tally) and the apply
@@ -919,7 +938,7 @@ def recalibrate_bam(bam, use_oq=False, set_oq=False, kmers=None, gatkreport=None
     from .gatk import bqsr
     quantize = applybqsr._check_qmap(quantize)
     opts = dict(k=31, min_count=None, slots=None, prefilter=False, filter_bits=4, skip_unresolved=False, passes=1, partitions=1,
-                mixed_lengths=False, exclude_flags=0)
+                mixed_lengths=False, exclude_flags=0, kmer_min_qual=None)
     unknown = sorted(set(kmers) - set(opts))
     if unknown:
         raise TypeError('recalibrate_bam: unknown k-mer option %s' % ', '.join(unknown))
@@ -927,7 +946,8 @@ def recalibrate_bam(bam, use_oq=False, set_oq=False, kmers=None, gatkreport=None
     # (without the two options of the records every call below is the one it was)
     records = {key: opts[key] for key in ('mixed_lengths', 'exclude_flags') if opts[key]}
     check_bam_kmers(bam, gatkreport, output, opts['k'], opts['min_count'], opts['prefilter'], opts['filter_bits'],
-                    opts['partitions'], opts['passes'], **{key: records[key] for key in ('exclude_flags',) if key in records})
+                    opts['partitions'], opts['passes'], **{key: records[key] for key in ('exclude_flags',) if key in records},
+                    **kmer._min_qual_kw(opts['kmer_min_qual']))
     passes, partitions = kmer.check_passes(opts['passes']), kmer._check_partitions(opts['partitions'])
     if not isinstance(bam, aln.AlignmentFile):
         with stage('parse'):
@@ -936,7 +956,8 @@ def recalibrate_bam(bam, use_oq=False, set_oq=False, kmers=None, gatkreport=None
     info = {}
     with stage('k-mer tally', sync=True):
         vectors, resident = bqsr._kmer_tally(bam, inputs, int(opts['k']), opts['min_count'], opts['slots'], opts['prefilter'],
-                                             opts['filter_bits'], use_oq, 6, 42, info, bool(opts['skip_unresolved']), passes, partitions)
+                                             opts['filter_bits'], use_oq, 6, 42, info, bool(opts['skip_unresolved']), passes, partitions,
+                                             **kmer._min_qual_kw(opts['kmer_min_qual']))
     with stage('solve'):
         # the bytes of the report decide: what `applybqsr` reads back is the text, not the vectors
         text = str(bqsr.vectors_to_report(*vectors, list(utils.get_rg_to_pu(bam).values())))

@@ -32,7 +32,18 @@ and kbbq_kmer_select_*_dev of the pairs with count >= 2; then the merge of the k
 kbbq_kmer_correct_dev against it.  "ms_count_rounds" has the median of every round, "ms_count" their sum, and "peak_bytes" the
 device bytes at their peak, from the allocations made (kbbq_dev_mem_info for the library's, torch's count of live bytes for
 the kept pairs; planes excluded; "peak_bytes_merge": while the solid table is built); the leg fails unless its
-summed histogram, threshold and corrected plane equal the plain leg's."""
+summed histogram, threshold and corrected plane equal the plain leg's.
+With `--qual-model calibrated` the reads get qualities from {2, 12, 23, 37} with the shares of `--qual-shares` (per cent) and their
+errors are drawn per base at the rate the quality states, 10^(-q/10), instead of `--err` everywhere, so that a quality gate has
+something to gate.  The error-free plane is kept in either model, and every leg prints what its corrected plane did against it:
+"errors" (bases inside the reads that differ from the truth and are no N), "errors_fixed" (those the leg set to the truth's
+letter) and "false_changes" (bases the leg changed to a letter that is not the truth's).
+With `--kmer-min-qual Q` (needs qualities: `--qual-model calibrated`, or `--skip`, whose qualities are uniform in 2..40) a leg on
+the same reads follows under the key "gate" (`kbbq correct --kmer-min-qual Q`): kbbq_kmer_gate_rows_dev into a fresh plane
+("ms_gate", and "gate_share_of_8TBs": its algorithmic bytes -- sequence read, qualities read, gated plane written -- per second
+over the 8 TB/s of the spec), a table sized from the counted windows (or `--gate-slots`), kbbq_kmer_count_dev of the gated plane,
+the histogram, the plane freed, kbbq_kmer_correct_dev of the reads as read; with the table's slots, bytes, load, distinct k-mers
+and singletons, and the device bytes at their peak with the gated plane counted ("peak_bytes")."""
 import argparse
 import ctypes
 import json
@@ -63,6 +74,11 @@ ap.add_argument('--skip', action='store_true',
 ap.add_argument('--partitions', type=int, default=1, help='add the leg that counts in this many rounds (kbbq correct --partitions)')
 ap.add_argument('--partition-slots', type=int, default=0, help='slots of that leg\'s per-partition table')
 ap.add_argument('--n-rate', type=float, default=0.0, help='share of the bases set to N')
+ap.add_argument('--qual-model', choices=('uniform', 'calibrated'), default='uniform',
+                help='calibrated: qualities from {2, 12, 23, 37} by --qual-shares, errors per base at 10^(-q/10) instead of --err')
+ap.add_argument('--qual-shares', default='1,3,6,90', help='per cent of the bases at quality 2, 12, 23 and 37 (calibrated)')
+ap.add_argument('--kmer-min-qual', type=int, default=0, help='add the leg that counts only k-mers of bases with quality >= Q')
+ap.add_argument('--gate-slots', type=int, default=0, help='table slots of that leg (default: from the counted windows)')
 args = ap.parse_args()
 if args.unresolved and not args.flags:
     ap.error('--unresolved: only with --flags')
@@ -70,6 +86,15 @@ if not 1 <= args.passes <= 8:
     ap.error('--passes: 1..8')
 if not 1 <= args.partitions <= 64:
     ap.error('--partitions: 1..64')
+if not 0 <= args.kmer_min_qual <= 93:
+    ap.error('--kmer-min-qual: 1..93')
+if args.kmer_min_qual and args.qual_model != 'calibrated' and not args.skip:
+    ap.error('--kmer-min-qual: needs qualities (--qual-model calibrated, or --skip)')
+try:
+    shares = [float(x) for x in args.qual_shares.split(',')]
+    assert len(shares) == 4 and min(shares) >= 0 and abs(sum(shares) - 100) < 1e-6
+except (ValueError, AssertionError):
+    ap.error('--qual-shares: four numbers that add up to 100')
 
 import numpy as np
 import torch
@@ -82,6 +107,11 @@ G = max(int(n * L / args.depth), 10 * L)
 g = torch.Generator(device='cuda').manual_seed(5)
 genome = torch.randint(0, 4, (G,), device='cuda', generator=g, dtype=torch.uint8)
 seq = torch.full((n, pitch), ord('N'), dtype=torch.uint8, device='cuda')
+truth = torch.full((n, pitch), ord('N'), dtype=torch.uint8, device='cuda')      # the reads without their errors
+calibrated = args.qual_model == 'calibrated'
+qual = torch.zeros_like(seq) if calibrated else None                             # 0 in the padding
+qvals = torch.tensor([2, 12, 23, 37], dtype=torch.uint8, device='cuda')
+cuts = torch.tensor(np.cumsum(shares)[:3] / 100.0, dtype=torch.float32, device='cuda')
 acgt = torch.tensor(list(b'ACGT'), dtype=torch.uint8, device='cuda')
 col = torch.arange(L, device='cuda')
 step = 1 << 22
@@ -91,7 +121,14 @@ for lo in range(0, n, step):                         # slices: the index tensors
     b = genome[start + col]
     rev = torch.rand((m, 1), device='cuda', generator=g) < 0.5
     b = torch.where(rev, (3 - b).flip(1), b)
-    err = torch.rand((m, L), device='cuda', generator=g) < args.err
+    truth[lo:lo + m, :L] = acgt[b.long()]
+    if calibrated:
+        q = qvals[torch.bucketize(torch.rand((m, L), device='cuda', generator=g), cuts, right=True)]
+        qual[lo:lo + m, :L] = q + 33
+        err = torch.rand((m, L), device='cuda', generator=g) < torch.pow(10.0, -q.float() / 10.0)
+        del q
+    else:
+        err = torch.rand((m, L), device='cuda', generator=g) < args.err
     b = torch.where(err, (b + torch.randint(1, 4, (m, L), device='cuda', generator=g, dtype=torch.uint8)) % 4, b)
     seq[lo:lo + m, :L] = acgt[b.long()]
     if args.n_rate > 0:
@@ -109,10 +146,11 @@ flags_u = torch.empty_like(seq) if args.unresolved else None      # ... with unr
 out_p = torch.empty_like(seq) if args.passes > 1 else None # the plane of several passes in one launch
 ping = [torch.empty_like(seq), torch.empty_like(seq)] if args.passes > 1 else None        # ... and of as many launches
 if args.skip:                                           # qualities 2..40 inside the reads, 0 in the padding; the tally plane
-    qual = torch.zeros_like(seq)
-    for lo in range(0, n, step):
-        m = min(step, n - lo)
-        qual[lo:lo + m, :L] = torch.randint(35, 74, (m, L), device='cuda', generator=g, dtype=torch.uint8)
+    if qual is None:
+        qual = torch.zeros_like(seq)
+        for lo in range(0, n, step):
+            m = min(step, n - lo)
+            qual[lo:lo + m, :L] = torch.randint(35, 74, (m, L), device='cuda', generator=g, dtype=torch.uint8)
     out_s, tally = torch.empty_like(seq), torch.empty_like(seq)
     s_unres = torch.empty((n,), dtype=torch.int32, device='cuda')
 lib = N.load()
@@ -129,6 +167,15 @@ def rep_base():
     torch.cuda.synchronize()
     torch.cuda.empty_cache()
     return in_use(kmer._ctx())
+
+
+def against_truth(plane):
+    """What a corrected plane did, by the error-free plane: errors of the reads, those it fixed, and its changes to a letter that
+    is not the truth's (sums of boolean planes: they have more than 2^31 elements)."""
+    wrong = (seq != truth) & (seq != ord('N'))
+    total = lambda x: int(x.sum(dtype=torch.int64).item())
+    return {'errors': total(wrong), 'errors_fixed': total(wrong & (plane == truth)),
+            'false_changes': total((plane != seq) & (plane != truth))}
 
 
 def timed(fn):
@@ -239,6 +286,54 @@ res['load_factor'] = round(res['distinct'] / slots, 3)
 res['min_count'] = t
 res['changed_bases'] = int((out != seq).sum().item())
 res['ms_correct_all'] = [round(v, 3) for v in ms['correct']]
+res['singletons'] = int(hist[1])
+res['qual_model'] = args.qual_model
+res.update(against_truth(out))
+if args.kmer_min_qual:
+    from kbbq import _device as dev
+    Q = args.kmer_min_qual
+    plain_out, plain_hist, plain_t = out, hist, t
+    out_g = ping[0] if ping else torch.empty_like(seq)
+    ms = {'gate': [], 'count': [], 'histogram': [], 'correct': []}
+    for rep in range(args.reps + 1):
+        base = rep_base()
+        ctx = kmer._ctx()
+        gated = torch.empty_like(seq)
+        word = torch.zeros(1, dtype=torch.int64, device='cuda')
+        gt = timed(lambda: N.check(lib.kbbq_kmer_gate_rows_dev(ctx.handle, N.ptr(seq), N.ptr(qual), N.ptr(meta), n, pitch, 0, k, Q + 33,
+                                                               N.ptr(gated), N.ptr(word))))
+        ctx.status()
+        counted = int(word.item())
+        gslots = args.gate_slots or kmer.default_slots(counted, dev.device_budget())
+        table = kmer.KmerTable(k, gslots)
+        torch.cuda.synchronize()
+        peak = in_use(ctx) - base                      # the gated plane and the table: the planes of the reads are in `base`
+        c = timed(lambda: N.check(lib.kbbq_kmer_count_dev(ctx.handle, table.handle, N.ptr(gated), N.ptr(meta), n, pitch)))
+        ctx.status()
+        h = timed(lambda: N.check(lib.kbbq_kmer_histogram_dev(ctx.handle, table.handle, N.ptr(dh))))
+        hist = dh.cpu().numpy()
+        t = kmer.solid_threshold(hist)
+        del gated                                      # the count is over: the correction reads the reads as read
+        x = timed(lambda: N.check(lib.kbbq_kmer_correct_dev(ctx.handle, table.handle, N.ptr(seq), N.ptr(meta), n, pitch, t,
+                                                             N.ptr(out_g), None)))
+        table.close()
+        if rep:
+            for key, v in zip(ms, (gt, c, h, x)):
+                ms[key].append(v)
+    leg = {'kmer_min_qual': Q, 'counted_windows': counted, 'windows': windows, 'slots': gslots,
+           'table_bytes': int(lib.kbbq_kmer_table_bytes(gslots)), 'gated_plane_bytes': n * pitch, 'peak_bytes': peak}
+    leg.update({'ms_' + key: round(float(np.median(v)), 3) for key, v in ms.items()})
+    leg['ms_gate_all'] = [round(v, 3) for v in ms['gate']]
+    leg['ms_correct_all'] = [round(v, 3) for v in ms['correct']]
+    leg['gate_bytes'] = 3 * n * pitch                  # character rows: sequence read, qualities read, gated plane written
+    leg['gate_share_of_8TBs'] = round(leg['gate_bytes'] / (leg['ms_gate'] * 1e-3) / 8e12, 3)
+    leg.update(distinct=int(hist.sum()), singletons=int(hist[1]), load_factor=round(int(hist.sum()) / gslots, 3), min_count=t,
+               changed_bases=int((out_g != seq).sum().item()), differs_from_plain=int((out_g != plain_out).sum().item()),
+               count_kmers_per_s=counted / (leg['ms_count'] * 1e-3), correct_kmers_per_s=windows / (leg['ms_correct'] * 1e-3))
+    leg.update(against_truth(out_g))
+    res['gate'] = leg
+    hist, t = plain_hist, plain_t
+    del out_g
 if args.fix_n:
     res['n_rate'] = args.n_rate
     res['n_bases'] = int((seq[:, :L] == ord('N')).sum().item())
