@@ -355,6 +355,10 @@ int    kbbq_solve_dev(kbbq_ctx* ctx, const int64_t* d_tables, int R, int S2, int
  * (skip mask = benchmark.get_full_skips, benchmark.py:22-39); cigar ops are
  * (length << 4 | op) with BAM op codes.  Outputs one byte per base (0 / 1) in the err and
  * skip planes; flip[r] != 0 reverses both for reverse-strand reads (benchmark.py:70-72).
+ * A row of d_len[r] bases is written in whole 16-byte chunks, ceil(d_len[r] / 16) of them: the bytes
+ * from the read's end to the end of its last chunk are 0, the chunks behind it are not touched.
+ * (One exception, in a batch that fails anyway: a row of no bases whose CIGAR the reference raises
+ * on takes the walk for its status and has its first chunk written as 16 zero bytes.)
  * The planes (seq, err, skip) are 16-byte aligned; genome / skipmask hold genome_len bytes each and
  * need no alignment or padding (reference windows are read with unaligned 16-byte loads, byte by
  * byte at the very end of the arrays).

@@ -335,7 +335,9 @@ __global__ __launch_bounds__(256) void k4v2_find_errors(K4v2Params q)
     // wave in the middle of the pipeline (the first build of this kernel did exactly that: 2.1 ms instead of 0.6).
     auto fetch_win = [&](const K4Item& it, const K4v2Meta& m, K4v2Win& w) {
         const int n = m.n, out_lo = 16 * it.j, out_hi = out_lo + 16 < n ? out_lo + 16 : n;
-        w.has = m.valid && out_lo < n;
+        // a read of NO bases has no chunk, but the reference may still raise on its CIGAR (a deletion: skips[-1] of nothing): its
+        // record then says "walk" and chunk 0, of no bytes, takes the walk for the status alone
+        w.has = m.valid && (out_lo < n || ((out_lo | n) == 0 && (m.rec.lo.y >> 29) == K4_KIND_BAD));
         w.cnt = w.has ? out_hi - out_lo : 0;
         w.in_lo = w.has ? (m.f ? n - out_hi : out_lo) : 0;
         const int a = w.in_lo, b = w.in_lo + w.cnt;
@@ -389,7 +391,8 @@ __global__ __launch_bounds__(256) void k4v2_find_errors(K4v2Params q)
         }
     };
     __shared__ u32 queued;
-    __shared__ uint2 queue[K4_QUEUE];                                      // (read relative to the launch: low / high word | chunk << 24)
+    // (read relative to the launch: low word, high 20 bits | chunk << 20 -- a row of 65536 bytes has 4096 chunks: 12 bits)
+    __shared__ uint2 queue[K4_QUEUE];
     if (threadIdx.x == 0) queued = 0u;
     __syncthreads();
     // one chunk through the sequential walk, from scratch (fields, read bytes, operations, windows: all fetched here)
@@ -426,7 +429,7 @@ __global__ __launch_bounds__(256) void k4v2_find_errors(K4v2Params q)
             const long long r = m0.r;
             const int j = it0.j;
             u32 ev[4] = {0u, 0u, 0u, 0u}, kv[4] = {0u, 0u, 0u, 0u};
-            bool store = true;
+            bool store = w0.has;                       // a chunk wholly behind its read is not written: ceil(len / 16) chunks per row
             if (w0.has) {
                 const int cnt = w0.cnt;
                 // every composed chunk of this wave inside ONE operation, nothing beside it (the common wave): one comparison
@@ -484,7 +487,7 @@ __global__ __launch_bounds__(256) void k4v2_find_errors(K4v2Params q)
                 } else {
                     // not here: queued for the dense pass below (or, queue full, walked at once)
                     const u32 slot_q = atomicAdd(&queued, 1u);
-                    if (slot_q < K4_QUEUE) queue[slot_q] = make_uint2((u32)r, (u32)((u64)r >> 32) | ((u32)j << 24));
+                    if (slot_q < K4_QUEUE) queue[slot_q] = make_uint2((u32)r, ((u32)((u64)r >> 32) & 0x000FFFFFu) | ((u32)j << 20));
                     else walk_and_store(r, j);
                     store = false;
                 }
@@ -508,7 +511,7 @@ __global__ __launch_bounds__(256) void k4v2_find_errors(K4v2Params q)
     const u32 nq = queued < K4_QUEUE ? queued : K4_QUEUE;
     for (u32 i = threadIdx.x; i < nq; i += blockDim.x) {
         const uint2 e = queue[i];
-        walk_and_store((long long)(((u64)(e.y & 0x00FFFFFFu) << 32) | e.x), (int)(e.y >> 24));
+        walk_and_store((long long)(((u64)(e.y & 0x000FFFFFu) << 32) | e.x), (int)(e.y >> 20));
     }
 }
 

@@ -123,9 +123,10 @@ static const void* k1_kernel(K1Form form, bool split, int dn, int nib, int kj)
 }
 
 // the others: the round-1 kernels (tables beyond the LDS, KBBQ_APPLY_CHECKED) and K2
-enum LdsKernel { LK_K1_PLAIN, LK_K1_PLAIN_SPLIT, LK_K2V3, LK_K2V3_NIB, LK_K2T, LK_K2T_NIB, LK_K2T_BANDS, LK_K2T_PAIR19, LK_K2T_PAIR13, LK_K2_LDS16, LK_K2_LDS8, LK_COUNT };
+enum LdsKernel { LK_K1_PLAIN, LK_K1_PLAIN_SPLIT, LK_K1_TILED, LK_K1_TILED_SPLIT, LK_K2V3, LK_K2V3_NIB, LK_K2T, LK_K2T_NIB, LK_K2T_BANDS, LK_K2T_PAIR19, LK_K2T_PAIR13, LK_K2_LDS16, LK_K2_LDS8, LK_COUNT };
 static const void* const LDS_KERNELS[LK_COUNT] = {
     (const void*)k1_accumulate<false>, (const void*)k1_accumulate<true>,
+    (const void*)k1_accumulate_tiled<false>, (const void*)k1_accumulate_tiled<true>,
     (const void*)k2v3_apply<false>, (const void*)k2v3_apply<true>,
     (const void*)k2t_apply<false>, (const void*)k2t_apply<true>, (const void*)k2t_bands,
     (const void*)k2t_apply_pair<19>, (const void*)k2t_apply_pair<13>,
@@ -547,11 +548,29 @@ int kbbq_accumulate_band_dev(kbbq_ctx* c, const uint8_t* d_seq, const uint8_t* d
     p.qlo = 33u + (u32)minscore; p.dlo = 33u + (u32)dinuc_minscore;
     p.pos_stride = S2 | 1;                         // odd row stride spreads q rows over the banks
     p.tables = reinterpret_cast<u64*>(d_tables); p.status = c->d_status;
-    const size_t lds = ((size_t)(((KQ * p.pos_stride) + 1) & ~1)) * 4 + (size_t)KQ * KND * 8;
-    if (lds > (size_t)c->lds_bytes)
-        return fail(KBBQ_E_ARG, "kbbq_accumulate_dev: reads of %d bases need %zu B of LDS (> %d)", S2 / 2, lds, c->lds_bytes);
+    auto lds_of = [](int stride) { return ((size_t)(((KQ * stride) + 1) & ~1)) * 4 + (size_t)KQ * KND * 8; };
+    size_t lds = lds_of(p.pos_stride);
+    K1TiledParams tp;
+    int tiles = 1;
+    if (lds > (size_t)c->lds_bytes) {
+        // the KQ x S2 table is beyond the LDS: the fewest equal tiles of an even number of columns whose KQ x (tile_w | 1) table fits
+        const int max_w = (int)((((size_t)c->lds_bytes - (size_t)KQ * KND * 8) / 4 - 1) / KQ - 1) & ~1;
+        if (max_w < 2) return fail(KBBQ_E_ARG, "kbbq_accumulate_dev: %d B of LDS hold no tile of the tables", c->lds_bytes);
+        tiles = (S2 + max_w - 1) / max_w;
+        tp.tile_w = ((S2 + tiles - 1) / tiles + 1) & ~1;
+        tiles = (S2 + tp.tile_w - 1) / tp.tile_w;
+        p.pos_stride = tp.tile_w | 1;
+        lds = lds_of(p.pos_stride);
+    }
     int per_cu = std::min<int>((int)(c->lds_bytes / lds), 2048 / K1_THREADS);
     per_cu = std::max(per_cu, 1);
+    if (tiles > 1) {                                // k1_accumulate_tiled: a workgroup iteration is K1_THREADS chunks
+        tp.k = p;
+        const int64_t iters = (nreads * p.cpr + K1_THREADS - 1) / K1_THREADS;
+        const int gx = (int)std::min<int64_t>(iters, std::max<int64_t>(1, (int64_t)c->cus * per_cu / ((int64_t)R * tiles)));
+        return launch_lds(c, 0, LDS_KERNELS[split ? LK_K1_TILED_SPLIT : LK_K1_TILED], dim3((unsigned)gx, (unsigned)R, (unsigned)tiles),
+                          dim3(K1_THREADS), lds, &tp);
+    }
     const int64_t iters = (nblocks + (K1_THREADS / 64) - 1) / (K1_THREADS / 64);
     int gx = (int)std::min<int64_t>(iters, std::max(1, c->cus * per_cu / R));
     return launch_lds(c, 0, LDS_KERNELS[split ? LK_K1_PLAIN_SPLIT : LK_K1_PLAIN], dim3((unsigned)gx, (unsigned)R, 1), dim3(K1_THREADS), lds, &p);

@@ -288,6 +288,151 @@ __global__ __launch_bounds__(K1_THREADS) void k1_accumulate(K1Params p)
     flush();
 }
 
+// ---------------------------------------------------------------- K1, tiled
+// K1 for reads whose KQ x S2 table of cycle counts is beyond the LDS (S >= 460 at 160 KB).
+//
+// k1_accumulate keeps the whole pos table of one read group in LDS.  Here the column axis is cut into tiles of
+// p.tile_w columns, one tile per blockIdx.z: pos[KQ][pos_stride] holds the columns col_lo .. col_lo + ncol - 1 only.  A lane
+// owns one 16-byte chunk of one read (grid-stride over nreads * cpr chunks); the base before the chunk is read from the row
+// itself, so a chunk needs nothing of its neighbours.  Tile 0 takes every chunk: it raises the status words and counts the
+// dinucleotides; the other tiles take the chunks that have a column inside them.  Same counts, same LDS cells (16-bit packed,
+// flushed every K1_FLUSH_ITERS iterations: a cell receives at most one increment per chunk, 96 * 512 chunks < 65,535) and the
+// same error rules as k1_accumulate, whose helpers it uses.
+struct K1TiledParams { K1Params k; int tile_w; };
+
+template <bool SPLIT>
+__global__ __launch_bounds__(K1_THREADS) void k1_accumulate_tiled(K1TiledParams tp)
+{
+    const K1Params& p = tp.k;
+    extern __shared__ __attribute__((aligned(16))) u32 lds[];
+    const int col_lo = (int)blockIdx.z * tp.tile_w;
+    const int ncol = min(tp.tile_w, p.S2 - col_lo);                 // <= tile_w < pos_stride
+    const int pos_words_al = (KQ * p.pos_stride + 1) & ~1;
+    u32* pos = lds;
+    u64* dn = reinterpret_cast<u64*>(lds + pos_words_al);
+
+    for (int i = threadIdx.x; i < pos_words_al + 2 * KQ * KND; i += blockDim.x) lds[i] = 0u;
+    __syncthreads();
+
+    const int g = blockIdx.y;
+    const long long nchunks = p.nreads * p.cpr;
+    const long long iters = (nchunks + blockDim.x - 1) / blockDim.x;
+    const u32 row_bytes = (u32)p.pos_stride * 4u;
+    const u32 qlo = p.qlo;
+    const u32 qspan = (u32)(KQ - 1 + 33) - qlo;       // counted quality bytes are qlo .. 'K' (q = 42)
+    const u32 dn_base = (u32)pos_words_al * 4u;
+    int since_flush = 0;
+
+    u64* pos_errs = p.tables;
+    u64* pos_total = p.tables + (size_t)p.R * KQ * p.S2;
+    u64* dn_errs = p.tables + 2 * (size_t)p.R * KQ * p.S2;
+    u64* dn_total = dn_errs + (size_t)p.R * KQ * KND;
+
+    auto flush = [&]() {
+        for (int e = threadIdx.x; e < KQ * ncol; e += blockDim.x) {
+            const int q = e / ncol, col = e - q * ncol;
+            const u32 v = pos[q * p.pos_stride + col];
+            if (v) {
+                pos[q * p.pos_stride + col] = 0u;
+                const size_t cell = ((size_t)g * KQ + q) * p.S2 + (size_t)(col_lo + col);
+                atomicAdd(&pos_total[cell], (u64)(v & 0xFFFFu));
+                if (v >> 16) atomicAdd(&pos_errs[cell], (u64)(v >> 16));
+            }
+        }
+        for (int e = threadIdx.x; e < KQ * KND; e += blockDim.x) {
+            const u64 v = dn[e];
+            if (v) {
+                dn[e] = 0ull;
+                atomicAdd(&dn_total[(size_t)g * KQ * KND + e], v & 0xFFFFFFFFull);
+                if (v >> 32) atomicAdd(&dn_errs[(size_t)g * KQ * KND + e], v >> 32);
+            }
+        }
+    };
+
+    for (long long it = blockIdx.x; it < iters; it += gridDim.x) {
+        const long long w = it * blockDim.x + threadIdx.x;
+        if (w < nchunks) {
+            const long long read = w / p.cpr;
+            const int j = (int)(w - read * p.cpr);
+            const u32 m = p.meta[read];
+            const int len = (int)(m & 0xFFFFu);
+            const bool second = (m >> 31) != 0u;
+            const int pos0 = 16 * j;
+            const int nb = len - pos0;
+            // the chunk's columns, relative to the tile: col0, col0 +- 1, ...
+            const int col0 = (second ? (2 * len - 1 - pos0) : pos0) - col_lo;
+            const bool inside = second ? (col0 >= 0 && col0 - 15 < ncol) : (col0 + 15 >= 0 && col0 < ncol);
+            if ((int)((m >> 16) & 0x7FFFu) == g && nb > 0 && (col_lo == 0 || inside)) {
+                const size_t rowoff = (size_t)read * p.pitch + (size_t)pos0;
+                const uint4 sv = *reinterpret_cast<const uint4*>(p.seq + rowoff);
+                const uint4 cv = *reinterpret_cast<const uint4*>(p.cseq + rowoff);
+                const uint4 qv = *reinterpret_cast<const uint4*>(p.qual + rowoff);
+                const u32 s[4] = {sv.x, sv.y, sv.z, sv.w}, c[4] = {cv.x, cv.y, cv.z, cv.w}, q[4] = {qv.x, qv.y, qv.z, qv.w};
+                u32 code[4], badbits = 0u, hiq = 0u;
+#pragma unroll
+                for (int wd = 0; wd < 4; ++wd) {
+                    u32 expect;
+                    decode4(s[wd], expect, code[wd]);
+                    badbits |= (expect ^ s[wd]) & byte_mask(nb, wd);
+                    // any quality byte > 'K' (q > 42)?  (bytes beyond the read are zero)
+                    hiq |= (((q[wd] & 0x7F7F7F7Fu) + 0x34343434u) | q[wd]) & 0x80808080u;
+                }
+                // the base before the chunk: none before base 0 (dinuc[0] = -1)
+                u32 prev_char = 0u, prev_code = 0x10u;
+                if (j > 0) {
+                    u32 expect;
+                    prev_char = p.seq[rowoff - 1];
+                    decode4(prev_char, expect, prev_code);
+                    prev_code &= 0xFFu;
+                }
+                if (hiq || 2 * len > p.S2) flag(p.status, ST_INDEX, read);   // recalibrate.py:114-115; read longer than the tables
+                if (badbits && chunk_type_error(s[0], s[1], s[2], s[3], q[0], q[1], q[2], q[3], prev_char, nb, pos0, p.minscore))
+                    flag(p.status, ST_TYPE, read);                           // compare_reads.py:224,292
+                if (2 * len <= p.S2) {
+                    // LDS byte address of (q, column): qb*row_bytes + colbase, colbase steps by +-4
+                    const int dcol = second ? -4 : 4;
+                    int colbase = col0 * 4 - 33 * (int)row_bytes;
+                    int lc = col0;                   // this base's column in the tile: counted iff 0 <= lc < ncol
+                    const int dnb = (int)dn_base - 33 * 128;
+                    u32 pc = prev_code << 24;        // alignbyte below takes byte 3 of the previous word
+#pragma unroll
+                    for (int wd = 0; wd < 4; ++wd) {
+                        const u32 pw = __builtin_amdgcn_alignbyte(code[wd], pc, 3);  // codes of bases i-1
+                        const u32 dw = (pw << 2) + code[wd];                         // 4*prev + cur, >= 16: no context
+                        pc = code[wd];
+                        const u32 xw = s[wd] ^ c[wd];
+#pragma unroll
+                        for (int b = 0; b < 4; ++b) {
+                            const u32 qb = (q[wd] >> (8 * b)) & 0xFFu;
+                            const bool valid = (qb - qlo) <= qspan;          // minscore <= q <= 42
+                            const bool err = ((xw >> (8 * b)) & 0xFFu) != 0u;  // recalibrate.py:13-20
+                            const u32 d = (dw >> (8 * b)) & 0xFFu;
+                            if (valid) {
+                                if ((u32)lc < (u32)ncol)
+                                    atomicAdd(reinterpret_cast<u32*>(reinterpret_cast<char*>(lds) + __umul24(qb, row_bytes) + (u32)colbase),
+                                              err ? 0x10001u : 1u);          // recalibrate.py:116-117
+                                if (col_lo == 0 && d < 16u && (!SPLIT || qb >= p.dlo)) {
+                                    const u32 ad = (qb << 7) + (d << 3) + (u32)dnb;
+                                    atomicAdd(reinterpret_cast<u64*>(reinterpret_cast<char*>(lds) + ad),
+                                              err ? 0x100000001ull : 1ull);  // recalibrate.py:118-119
+                                }
+                            }
+                            colbase += dcol;
+                            lc += second ? -1 : 1;
+                        }
+                    }
+                }
+            }
+        }
+        if (++since_flush == K1_FLUSH_ITERS) {
+            __syncthreads(); flush(); __syncthreads();
+            since_flush = 0;
+        }
+    }
+    __syncthreads();
+    flush();
+}
+
 // ---------------------------------------------------------------- K2
 // LUT (int16), one row of `rs` entries per (read group, quality):
 //     row[0 .. S2-1]      = meanq + rgdq + qdq + posdq[cycle]          (lut1)

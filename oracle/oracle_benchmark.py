@@ -71,7 +71,8 @@ def find_read_errors(read, ref, variable):
             skips[readidx:readidx + l] = sub_var[refidx:refidx + l]
             readidx += l; refidx += l
         elif op == 1:                                              # I       (:115-120)
-            skips[readidx:readidx + l] = bool(sub_var[refidx - 1]) and bool(sub_var[refidx])   # IndexError at the window end
+            left, right = sub_var[refidx - 1], sub_var[refidx]     # np.logical_and looks BOTH up: IndexError at the window end
+            skips[readidx:readidx + l] = bool(left) and bool(right)
             readidx += l
         elif op in (2, 3):                                         # D N     (:121-125)
             skips[readidx - 1] = skips[readidx - 1] or bool(np.any(sub_var[refidx:refidx + l]))
