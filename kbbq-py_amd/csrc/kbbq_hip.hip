@@ -1102,12 +1102,13 @@ static int accumulate_rows(kbbq_ctx* c, const char* who, const uint8_t* d_seq, c
     // copies of the cycle table (1.52 against 1.64 ms); 2 x 75 / 2 x 125 / 2 x 250 bp never take mate-pair rows (2 S + 1 rounds up to
     // twice the single read's pitch: no bytes saved).
     if (pairs && nib && (q.cpr == 19 || q.cpr == 13)) {
-        q.row_bytes = (u32)(((16 * q.cpr + 31) & ~31) * 4);
+        // joint rows (k1v3_body): a quality's cycle words, then its 32 context slots x 16 copies -- 832 / 736 words, multiples of 32
+        q.row_bytes = (u32)((((16 * q.cpr + 31) & ~31) + 32 * K1V3_DNREP) * 4);
         q.minlen = 0; q.slack_bytes = 0; q.pos_copies = 1;
         q.dn_flush_iters = std::max(1, 65535 / ((K1V3_THREADS / K1V3_DNREP) * 16 * q.cpr));
         for (int nt = q.cpr == 19 ? 1 : 8; nt >= 1 && !su.dn; nt >>= 1) {
             const size_t rows = (size_t)q.nrows - 1 + nt;
-            su.lds = rows * 128 * K1V3_DNREP + rows * q.row_bytes;
+            su.lds = rows * q.row_bytes;
             if (su.lds > (size_t)c->lds_bytes) continue;
             su.dn = K1V3_DNREP; su.kj = q.cpr;                // the form applies AND its tables fit
             q.ntrash = nt; q.pos_copy_bytes = (u32)(rows * q.row_bytes);

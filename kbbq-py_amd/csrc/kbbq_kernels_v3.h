@@ -95,6 +95,46 @@ __device__ __forceinline__ u32 k1_increment(u32 xw, u32 zero, u32 both)
     return inc;
 }
 
+// The uniform-block loop of the joint-row forms (k1v3_body, KJ > 0) bins a base in five vector instructions; these are the three
+// that work on a part of a register (SDWA), B the base's byte in its word:
+// row of the tables: min(byte B of qn = 255 - quality, tcl)
+template <int B>
+__device__ __forceinline__ u32 k1_joint_row(u32 qn, u32 tcl)
+{
+    u32 tq;
+    if (B == 0)      asm("v_min_u32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_0 src1_sel:DWORD" : "=v"(tq) : "v"(qn), "v"(tcl));
+    else if (B == 1) asm("v_min_u32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_1 src1_sel:DWORD" : "=v"(tq) : "v"(qn), "v"(tcl));
+    else if (B == 2) asm("v_min_u32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_2 src1_sel:DWORD" : "=v"(tq) : "v"(qn), "v"(tcl));
+    else             asm("v_min_u32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_3 src1_sel:DWORD" : "=v"(tq) : "v"(qn), "v"(tcl));
+    return tq;
+}
+// increment of both count tables, errs << 16 | total: the HIGH half of `inc` becomes min(byte B of xw, 1) -- xw = seq ^ cseq on codes,
+// a byte of it is 0..7 -- and the low half keeps the 1 it was given.
+template <int B>
+__device__ __forceinline__ void k1_joint_increment(u32& inc, u32 xw, u32 one)
+{
+    if (B == 0)      asm("v_min_u32_sdwa %0, %1, %2 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:BYTE_0 src1_sel:DWORD" : "+v"(inc) : "v"(xw), "v"(one));
+    else if (B == 1) asm("v_min_u32_sdwa %0, %1, %2 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:BYTE_1 src1_sel:DWORD" : "+v"(inc) : "v"(xw), "v"(one));
+    else if (B == 2) asm("v_min_u32_sdwa %0, %1, %2 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:BYTE_2 src1_sel:DWORD" : "+v"(inc) : "v"(xw), "v"(one));
+    else             asm("v_min_u32_sdwa %0, %1, %2 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:BYTE_3 src1_sel:DWORD" : "+v"(inc) : "v"(xw), "v"(one));
+}
+// (x << 6) + y in one instruction (the compiler moves a mask of x behind its own shift and then needs three)
+__device__ __forceinline__ u32 k1_shl6_add(u32 x, u32 y)
+{
+    u32 r;
+    asm("v_lshl_add_u32 %0, %1, 6, %2" : "=v"(r) : "v"(x), "v"(y));
+    return r;
+}
+// address of the context word: the cycle word's plus 16-bit half H of e
+template <int H>
+__device__ __forceinline__ u32 k1_joint_delta(u32 a, u32 e)
+{
+    u32 ad;
+    if (H == 0) asm("v_add_u32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:WORD_0" : "=v"(ad) : "v"(a), "v"(e));
+    else        asm("v_add_u32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:WORD_1" : "=v"(ad) : "v"(a), "v"(e));
+    return ad;
+}
+
 
 // ---- 4-bit sequence planes ("packed" layouts) ------------------------------------------------
 // A seq / cseq plane may hold one NIBBLE per base instead of one character: the nucleotide code itself
@@ -163,6 +203,8 @@ struct K1Chunk { u32 s[4], c[4], q[4]; u32 mk; u32 off; int k; int j; int nb; u3
 // then (k * KJ + j) mod 32 whatever its quality: for the 16-base unroll's fixed k, lanes of one row hit DIFFERENT banks
 // (only the lanes of the next row, 19 chunks on, meet them again: 2 LDS cycles per half-wave), where the
 // position-major layout lets the random quality row pick the bank (a 32-lane half-wave on 32 banks: ~3.5 cycles).
+// These forms keep `dn` and `pos` in JOINT rows: row r = [pos row r: CYC words | dn row r: 32 x 16 words], 832 (KJ = 19) / 736
+// (13) words, multiples of 32 like CYC itself, so both tables keep their banks and a base's two addresses share the row term.
 // Measured (profiles/r02_k1_lds.md): the cycle-table atomics were the larger half of K1's LDS time once the 4-bit
 // sequence planes had made K1 LDS-bound.  The per-base offset 4 * k * KJ is an instruction immediate.
 // The kernel's body: workgroup `bx` of the `gx` that share this batch (k1v3_accumulate: the whole grid; k1v3_bands: the
@@ -185,11 +227,18 @@ __device__ __forceinline__ void k1v3_body(const K1v3Params& p, u32* lds, const i
 {
     static_assert(!ALN || (!NIB && KJ == 0), "the aligned-read form reads character planes");
     static_assert(!REF || ALN, "the reference comparison belongs to the aligned-read form");
+    // KJ > 0: JOINT rows -- a quality's cycle words and its context words in ONE row of JROW bytes, [CYC cycle words | 32 slots x DN
+    // copies], so that one multiply by the row serves both atomics of a base (the uniform-block loop below).  CYC and JROW / 4 are multiples
+    // of 32: the bank of a cycle word stays (k * KJ + j) mod 32 and that of a context word (slot * DN + copy) mod 32 whatever the row.
+    constexpr bool JOINT = KJ > 0;
+    constexpr int CYC = (16 * KJ + 31) & ~31;
+    constexpr u32 JROW = (u32)(CYC + 32 * DN) * 4u;
+    static_assert(!JOINT || (NIB && DN == 16), "joint rows: 4-bit planes, 64 bytes per context slot");
     const int ntrash = p.ntrash;                       // (the host gives the 19-chunk form one trash row: several were measured, nothing)
-    const int dn_words = (p.nrows - 1 + ntrash) * 32 * DN;
+    const int dn_words = JOINT ? 0 : (p.nrows - 1 + ntrash) * 32 * DN;
     const int ncopies = KJ > 0 ? 1 : p.pos_copies;
-    const int pos_words = KJ > 0 ? (p.nrows - 1 + ntrash) * (int)(p.row_bytes >> 2) + (int)(p.slack_bytes >> 2) : ncopies * (int)(p.pos_copy_bytes >> 2);
-    u32* dnt = lds;
+    const int pos_words = KJ > 0 ? (p.nrows - 1 + ntrash) * (int)(JROW >> 2) : ncopies * (int)(p.pos_copy_bytes >> 2);
+    u32* dnt = JOINT ? lds + CYC : lds;
     u32* pos = lds + dn_words;
     for (int i = threadIdx.x; i < dn_words + pos_words; i += blockDim.x) lds[i] = 0u;
     __syncthreads();
@@ -202,12 +251,12 @@ __device__ __forceinline__ void k1v3_body(const K1v3Params& p, u32* lds, const i
     const long long nblocks = (seg_hi - seg_lo + 63) >> 6;
     const long long iters = (nblocks + nwaves - 1) / nwaves;
     const int S = p.S, S2 = 2 * p.S;
-    const u32 row_bytes = p.row_bytes;
+    const u32 row_bytes = JOINT ? JROW : p.row_bytes;
     const u32 tclamp = 255u - p.qlo_m1;                                // inverted bytes >= this are uncounted
     const u32 pos_base = (u32)dn_words * 4u - 180u * row_bytes;        // 180 = 255 - 'K': inverted byte of q = 42 is row 0
-    const u32 dnt_row = 128u * DN;                             // bytes per row of the replicated totals
+    const u32 dnt_row = JOINT ? JROW : 128u * DN;              // bytes per row of the replicated totals
     // LDS byte address (the low half of the flat address is the LDS offset) of this lane's copy, less the row bias
-    const u32 dnt_base = (u32)reinterpret_cast<size_t>(lds) - 180u * dnt_row + 4u * (u32)(lane_id() & (DN - 1));
+    const u32 dnt_base = (u32)reinterpret_cast<size_t>(lds) - 180u * dnt_row + 4u * (u32)(lane_id() & (DN - 1)) + (JOINT ? 4u * CYC : 0u);
     int since_flush = 0, since_dn_flush = 0;
     // work item of this lane at step 0 and the per-step advances (64 / 128 items)
     const int lane_k0 = p.cpr == 1 ? lane : (int)__umulhi((u32)lane, p.cpr_magic);
@@ -227,9 +276,10 @@ __device__ __forceinline__ void k1v3_body(const K1v3Params& p, u32* lds, const i
                 const int a = lane / 5, b = lane - 5 * a;
                 if (a < 4 && b < 4) {
                     u32 vt = 0u, ve = 0u;
+                    const int at = JOINT ? r * (int)(JROW >> 2) + lane * DN : (r * 32 + lane) * DN;
                     for (int cpy = 0; cpy < DN; ++cpy) {
-                        const u32 v = dnt[(r * 32 + lane) * DN + cpy];
-                        dnt[(r * 32 + lane) * DN + cpy] = 0u;
+                        const u32 v = dnt[at + cpy];
+                        dnt[at + cpy] = 0u;
                         vt += v & 0xFFFFu; ve += v >> 16;
                     }
                     if (vt) {
@@ -545,6 +595,11 @@ __device__ __forceinline__ void k1v3_body(const K1v3Params& p, u32* lds, const i
                     constexpr int DK = 64 / KJ, DJ = 64 - DK * KJ;
                     int j4 = 4 * lane_j0, k = lane_k0;                   // 4 j: the chunk's word in a table row
                     const u32 at = 16u * (u32)lane;
+                    const u32 lds_at = (u32)reinterpret_cast<size_t>(lds);
+                    const u32 ctx_at = 4u * CYC + 4u * (u32)(lane & (DN - 1));       // from a row's cycle word 0 to this lane's copy of slot 0
+                    const u32 dlo4 = (p.dlo < 128u ? p.dlo : 128u) * 0x01010101u;     // (a counted quality byte is below 128)
+                    const u32 one = 1u;
+                    u32 inc_a = 1u, inc_b = 1u;                                    // two increments in turn; their low halves stay 1
                     auto fetch_u = [&](K1Chunk& ch, int s) {
                         const u32 o = at + 1024u * (u32)s;
                         const uint2 sv = *reinterpret_cast<const uint2*>(bseq + (o >> 1));
@@ -573,29 +628,39 @@ __device__ __forceinline__ void k1v3_body(const K1v3Params& p, u32* lds, const i
                             if (hiq) flag(p.status, ST_INDEX, read0 + k);
                             if (badbits) flag(p.status, ST_LUT, 0);
                         } else {
-                            // the 16 bases, as `process` bins them (KJ > 0, not ALN)
-                            const u32 A = pos_base + (u32)j4;
+                            // the 16 bases, binned as `process` bins them (KJ > 0, not ALN) in five vector instructions each: the
+                            // joint row makes the context word's address the cycle word's plus a 16-bit delta
+                            //     CYC * 4 - 4 j + 64 slot + 4 (lane & 15)          (0 < delta < JROW: no carry between halves)
+                            // of which a register E holds two bases' worth (k1_joint_delta); the increment comes from one
+                            // sub-dword min (k1_joint_increment)
+                            const u32 A = lds_at + pos_base + (u32)j4;            // LDS address of cycle word j of row 0, less the row bias
                             const u32 tcl = tclamp + (u32)(k & (ntrash - 1));
                             const u32 (&qv)[4] = ch.q;
+                            const u32 kd = ctx_at - (u32)j4;
+                            const u32 kd2 = kd | (kd << 16);
                             u32 pc5 = prev_code5 << 24;
 #pragma unroll
                             for (int wd = 0; wd < 4; ++wd) {
                                 const u32 pw5 = __builtin_amdgcn_alignbyte(code5[wd], pc5, 3);
-                                const u32 d5 = pw5 + code[wd];                    // 5*prev + cur per byte, <= 24
+                                u32 d5 = pw5 + code[wd];                          // 5*prev + cur per byte, <= 24
                                 pc5 = code5[wd];
+                                if (SPLIT) {                                      // context needs q >= its own threshold: slot 24 otherwise
+                                    const u32 t = ((qv[wd] | 0x80808080u) - dlo4) & 0x80808080u;      // bit 7 of a byte: q >= dlo (q < 128 here)
+                                    d5 = (d5 & (t - (t >> 7))) | (0x18181818u & ~(t - (t >> 7)));
+                                }
+                                const u32 e02 = k1_shl6_add(d5 & 0x00FF00FFu, kd2);                    // deltas of bases 0 | 2 << 16
+                                const u32 e13 = k1_shl6_add(__builtin_amdgcn_perm(0u, d5, 0x0C030C01u), kd2);   // ... of bases 1 | 3 << 16
                                 const u32 xwd = xw[wd];
                                 const u32 qn = ~qv[wd];
-                                const u32 zero = 0u, both = 0x10001u;
                                 auto one_base = [&](auto bsel) {
                                     constexpr int b = decltype(bsel)::value;
-                                    const u32 qi = (qn >> (8 * b)) & 0xFFu;         // 255 - quality byte
-                                    const u32 tq = qi < tcl ? qi : tcl;            // below minscore (and padding): a trash row
-                                    const u32 inc = k1_increment<b>(xwd, zero, both);
-                                    const u32 a = __umul24(tq, row_bytes) + A + (u32)(4 * KJ * (4 * wd + b));
-                                    atomicAdd(reinterpret_cast<u32*>(reinterpret_cast<char*>(lds) + a), inc);   // recalibrate.py:116-117
-                                    u32 slot = (d5 >> (8 * b)) & 0xFFu;
-                                    if (SPLIT) slot = qi <= 255u - p.dlo ? slot : 24u;
-                                    const u32 ad = slot * (4u * DN) + tq * dnt_row + dnt_base;
+                                    const u32 tq = k1_joint_row<b>(qn, tcl);       // 255 - quality byte; below minscore (and padding): a trash row
+                                    u32& inc = (b & 1) ? inc_b : inc_a;
+                                    k1_joint_increment<b>(inc, xwd, one);         // recalibrate.py:13-20: errs << 16 | total
+                                    const u32 a = __umul24(tq, JROW) + A;
+                                    __hip_atomic_fetch_add(reinterpret_cast<lds_u32*>(a + (u32)(4 * KJ * (4 * wd + b))), inc, __ATOMIC_RELAXED,
+                                                           __HIP_MEMORY_SCOPE_WORKGROUP);          // recalibrate.py:116-117
+                                    const u32 ad = k1_joint_delta<(b >> 1)>(a, (b & 1) ? e13 : e02);
                                     __hip_atomic_fetch_add(reinterpret_cast<lds_u32*>(ad), inc, __ATOMIC_RELAXED,
                                                            __HIP_MEMORY_SCOPE_WORKGROUP);          // recalibrate.py:118-119
                                 };
