@@ -874,6 +874,31 @@ int kbbq_kmer_select_dev(kbbq_ctx* ctx, const kbbq_kmer_table* table, int nbucke
 int kbbq_kmer_merge_dev(kbbq_ctx* ctx, kbbq_kmer_table* table, const uint64_t* d_keys, const uint32_t* d_counts, int64_t n);
 uint32_t kbbq_kmer_owner(uint64_t key, int nbuckets);
 
+/* ---- k-mer sets (kbbq count, --kmers-from; csrc/kbbq_kmer_set.h, kbbq/kmerset.py) -----------------------------------------------
+ * A k-mer set is the (canonical key, count) pairs with count >= keep of a finished count, ascending by key as UNSIGNED 64-bit
+ * words (k = 32 keys use bit 63), in a file kbbq/kmerset.py describes byte by byte.
+ * kbbq_kmer_sort_pairs_dev sorts n pairs (device arrays, as kbbq_kmer_select_dev writes them) by unsigned key into d_keys_out /
+ * d_counts_out, buffers of their own (KBBQ_E_ARG when an output is its input); only the 2k low key bits are looked at, keys are
+ * expected to be distinct, and the result is then the same permutation whatever the thread order.  d_temp: at least
+ * kbbq_kmer_sort_pairs_bytes(n) bytes of device memory (KBBQ_E_ARG naming both numbers otherwise).  Asynchronous on the
+ * context's stream; n == 0 does nothing.
+ * kbbq_kmer_check_pairs_dev (synchronous) judges one slab of n pairs, `first` being the global index of its pair 0: pair i must
+ * have keys[i] > keys[i - 1] (the slab's pair 0 against prev_key when have_prev is not 0: the last key of the slab before),
+ * keys[i] < 4^k, keys[i] <= the reverse complement of keys[i] (it is canonical) and counts[i] >= keep.  *bad_index receives
+ * the lowest global index of a pair that breaks a rule, or -1, and *bad_reason the first rule it breaks in the order above
+ * (KBBQ_KMER_PAIR_*; 0 when none does).  h_sums[0] += the sum of the keys and h_sums[1] += the sum of the counts, both modulo
+ * 2^64, so the sums of a file's slabs add up in the caller's two words.  An offender is an answer, not an error: the return is
+ * KBBQ_OK.  n == 0 does nothing.                                                                                               */
+#define KBBQ_KMER_PAIR_ORDER      1   /* keys[i] <= the key before it (unsorted, or a duplicate)  */
+#define KBBQ_KMER_PAIR_RANGE      2   /* keys[i] >= 4^k                                           */
+#define KBBQ_KMER_PAIR_CANONICAL  3   /* keys[i] > its reverse complement                         */
+#define KBBQ_KMER_PAIR_COUNT      4   /* counts[i] < keep                                         */
+int kbbq_kmer_sort_pairs_bytes(kbbq_ctx* ctx, int64_t n, size_t* bytes);
+int kbbq_kmer_sort_pairs_dev(kbbq_ctx* ctx, int k, const uint64_t* d_keys_in, const uint32_t* d_counts_in, uint64_t* d_keys_out,
+                             uint32_t* d_counts_out, int64_t n, void* d_temp, size_t temp_bytes);
+int kbbq_kmer_check_pairs_dev(kbbq_ctx* ctx, const uint64_t* d_keys, const uint32_t* d_counts, int64_t n, int k, uint32_t keep,
+                              int64_t first, int have_prev, uint64_t prev_key, uint64_t* h_sums, int64_t* bad_index, int* bad_reason);
+
 /* ---- prefilter: k-mers seen once stay out of the table (kbbq correct --prefilter; csrc/kbbq_kmer.h) ---------------------------
  * Nothing after the count looks at a k-mer seen once (the threshold starts at 2), and most distinct k-mers of real reads are
  * such.  A k-mer filter is two device arrays of `words` (a power of two) uint64 words, `seen` and `twice`, zero when created;

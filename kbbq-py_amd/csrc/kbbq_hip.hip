@@ -12,8 +12,11 @@
 #include "kbbq_layout_kernels.h"
 #include "kbbq_apply_aligned.h"
 #include "kbbq_kmer.h"
+#include "kbbq_kmer_set.h"
 #include "../../include/kbbq_hip.h"
 #include "host_threads.h"
+
+#include <rocprim/rocprim.hpp>
 
 #include <algorithm>
 #include <climits>
@@ -2675,6 +2678,79 @@ int kbbq_kmer_merge_dev(kbbq_ctx* c, kbbq_kmer_table* t, const uint64_t* d_keys,
     hipLaunchKernelGGL(km_merge, dim3(grid), dim3(KM_THREADS), 0, c->stream, (const u64*)d_keys, (const u32*)d_counts, n,
                        t->keys, t->counts, (u64)t->slots - 1, c->d_status);
     HIPCHK(hipGetLastError());
+    return KBBQ_OK;
+}
+
+// ---- k-mer sets (kbbq_kmer_set.h; kbbq/kmerset.py) --------------------------------------------------------------------------
+// The sort is rocPRIM's radix sort (header-only) over the 2k key bits: keys are unique, so the result is one permutation
+// whatever the thread order.  Keys are sorted as the unsigned 64-bit words they are (k = 32 uses bit 63).
+static hipError_t kmer_sort_pairs(void* temp, size_t& bytes, const u64* kin, u64* kout, const u32* cin, u32* cout, size_t n, int k,
+                                  hipStream_t st)
+{
+    return rocprim::radix_sort_pairs(temp, bytes, kin, kout, cin, cout, n, 0u, (unsigned)(2 * k), st);
+}
+
+int kbbq_kmer_sort_pairs_bytes(kbbq_ctx* c, int64_t n, size_t* bytes)
+{
+    if (!c || !bytes) return fail(KBBQ_E_ARG, "kbbq_kmer_sort_pairs_bytes: NULL argument");
+    if (n < 0) return fail(KBBQ_E_ARG, "kbbq_kmer_sort_pairs_bytes: n must be >= 0, got %lld", (long long)n);
+    *bytes = 0;
+    if (n == 0) return KBBQ_OK;
+    HIPCHK(hipSetDevice(c->device));
+    size_t need = 0;
+    HIPCHK(kmer_sort_pairs(nullptr, need, nullptr, nullptr, nullptr, nullptr, (size_t)n, 32, c->stream));
+    *bytes = need;
+    return KBBQ_OK;
+}
+
+int kbbq_kmer_sort_pairs_dev(kbbq_ctx* c, int k, const uint64_t* d_keys_in, const uint32_t* d_counts_in, uint64_t* d_keys_out,
+                             uint32_t* d_counts_out, int64_t n, void* d_temp, size_t temp_bytes)
+{
+    if (!c) return fail(KBBQ_E_ARG, "kbbq_kmer_sort_pairs_dev: NULL ctx");
+    if (k < 8 || k > 32) return fail(KBBQ_E_ARG, "kbbq_kmer_sort_pairs_dev: k must be in 8..32, got %d", k);
+    if (n < 0) return fail(KBBQ_E_ARG, "kbbq_kmer_sort_pairs_dev: n must be >= 0, got %lld", (long long)n);
+    if (n == 0) return KBBQ_OK;
+    if (!d_keys_in || !d_counts_in || !d_keys_out || !d_counts_out) return fail(KBBQ_E_ARG, "kbbq_kmer_sort_pairs_dev: NULL pairs");
+    if ((const void*)d_keys_in == (const void*)d_keys_out || (const void*)d_counts_in == (const void*)d_counts_out)
+        return fail(KBBQ_E_ARG, "kbbq_kmer_sort_pairs_dev: the sorted pairs need buffers of their own");
+    HIPCHK(hipSetDevice(c->device));
+    size_t need = 0;
+    HIPCHK(kmer_sort_pairs(nullptr, need, nullptr, nullptr, nullptr, nullptr, (size_t)n, 32, c->stream));
+    if (need > 0 && (!d_temp || temp_bytes < need))
+        return fail(KBBQ_E_ARG, "kbbq_kmer_sort_pairs_dev: the temporary holds %zu bytes, %zu are needed (kbbq_kmer_sort_pairs_bytes)",
+                    d_temp ? temp_bytes : (size_t)0, need);
+    HIPCHK(kmer_sort_pairs(d_temp, temp_bytes, (const u64*)d_keys_in, (u64*)d_keys_out, (const u32*)d_counts_in, (u32*)d_counts_out,
+                           (size_t)n, k, c->stream));
+    return KBBQ_OK;
+}
+
+int kbbq_kmer_check_pairs_dev(kbbq_ctx* c, const uint64_t* d_keys, const uint32_t* d_counts, int64_t n, int k, uint32_t keep,
+                              int64_t first, int have_prev, uint64_t prev_key, uint64_t* h_sums, int64_t* bad_index, int* bad_reason)
+{
+    if (!c || !h_sums || !bad_index || !bad_reason) return fail(KBBQ_E_ARG, "kbbq_kmer_check_pairs_dev: NULL argument");
+    if (k < 8 || k > 32) return fail(KBBQ_E_ARG, "kbbq_kmer_check_pairs_dev: k must be in 8..32, got %d", k);
+    if (n < 0 || first < 0 || first > ((int64_t)1 << 60) - n)
+        return fail(KBBQ_E_ARG, "kbbq_kmer_check_pairs_dev: bad n / first (%lld, %lld)", (long long)n, (long long)first);
+    if (n > 0 && (!d_keys || !d_counts)) return fail(KBBQ_E_ARG, "kbbq_kmer_check_pairs_dev: NULL pairs");
+    if (((uintptr_t)d_keys & 7) || ((uintptr_t)d_counts & 3)) return fail(KBBQ_E_ARG, "kbbq_kmer_check_pairs_dev: pairs not aligned");
+    *bad_index = -1; *bad_reason = 0;
+    if (n == 0) return KBBQ_OK;
+    HIPCHK(hipSetDevice(c->device));
+    DevBuf d;
+    HIPCHK(d.alloc(3 * 8));
+    u64 out[3] = {0, 0, KM_CHECK_NONE};
+    HIPCHK(hipMemcpyAsync(d.p, out, sizeof out, hipMemcpyHostToDevice, c->stream));
+    const KmerCheck q = {(const u64*)d_keys, (const u32*)d_counts, n, first, (u64)prev_key, have_prev ? 1u : 0u, k, keep, (u64*)d.p};
+    const int64_t steps = (n + 1) / 2;
+    const unsigned grid = (unsigned)std::min<int64_t>((steps + KM_THREADS - 1) / KM_THREADS, (int64_t)c->cus * 8);
+    const bool vec = !((uintptr_t)d_keys & 15) && !((uintptr_t)d_counts & 7);
+    if (vec) hipLaunchKernelGGL(km_check_pairs<true>, dim3(grid), dim3(KM_THREADS), 0, c->stream, q);
+    else hipLaunchKernelGGL(km_check_pairs<false>, dim3(grid), dim3(KM_THREADS), 0, c->stream, q);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, d.p, sizeof out, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    h_sums[0] += out[0]; h_sums[1] += out[1];
+    if (out[2] != KM_CHECK_NONE) { *bad_index = (int64_t)(out[2] >> 3); *bad_reason = (int)(out[2] & 7); }
     return KBBQ_OK;
 }
 

@@ -194,6 +194,10 @@ PROTOTYPES = {
     'kbbq_kmer_select_dev': (_i, [_vp, _vp, _i, _c.c_uint32, _vp, _vp, _vp]),
     'kbbq_kmer_merge_dev': (_i, [_vp, _vp, _vp, _vp, _i64]),
     'kbbq_kmer_owner': (_c.c_uint32, [_u64, _i]),
+    'kbbq_kmer_sort_pairs_bytes': (_i, [_vp, _i64, _c.POINTER(_sz)]),
+    'kbbq_kmer_sort_pairs_dev': (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i64, _vp, _sz]),
+    'kbbq_kmer_check_pairs_dev': (_i, [_vp, _vp, _vp, _i64, _i, _c.c_uint32, _i64, _i, _u64, _vp, _c.POINTER(_i64),
+                                       _c.POINTER(_i)]),
     'kbbq_kmer_filter_bytes': (_sz, [_i64]),
     'kbbq_kmer_filter_create_dev': (_i, [_vp, _i64, _c.POINTER(_vp)]),
     'kbbq_kmer_filter_free_dev': (_i, [_vp, _vp]),

@@ -489,7 +489,7 @@ def _kmer_benchmark_inputs(bamfile, k, min_count, prefilter, filter_bits):
 
 
 def benchmark_kmers(bamfile, ref, var_sites, k=31, min_count=None, slots=None, prefilter=False, filter_bits=4, use_oq=False,
-                    bedfh=None, info=None, passes=1, partitions=1, kmer_min_qual=None):
+                    bedfh=None, info=None, passes=1, partitions=1, kmer_min_qual=None, kmers_from=None):
     """How good is the k-mer rule on a truth set?  joint[q][truth error][k-mer class], int64 (256, 2, 3): every base of the
     alignments that benchmark_bam counts (not at a variant site, inside the BED, not soft-clipped), by its reported quality
     (QUAL, or the OQ tag with use_oq), by whether it differs from the reference (K4, exactly as benchmark_bam flags it) and
@@ -509,10 +509,17 @@ def benchmark_kmers(bamfile, ref, var_sites, k=31, min_count=None, slots=None, p
     counted; the prefilter, the count and every partition round read the gated copy of SEQ, which sizes the filter and the
     default table, and the classes are decided for SEQ as read.  A record with bases and without qualities (QUAL '*', or no OQ
     tag with use_oq) is refused with a ValueError naming it, before any upload.  `info` then receives kmer_min_qual,
-    counted_windows and windows."""
+    counted_windows and windows.
+    kmers_from = PATH (kmer.load_set): the classes are read from the table of a k-mer set file -- the very set `bqsr --kmers
+    --kmers-from` decided by -- instead of a count of these alignments; k is the set's (pass k=None, or the set's), no counting
+    option goes with it; `info` then receives kmers_from and loaded_kmers, and its slots is the loaded table's."""
     from . import _device as dev
     from . import kmer
     passes = kmer.check_passes(passes)
+    kmers_from = kmer.check_kmers_from(kmers_from, prefilter, filter_bits, partitions, kmer_min_qual)
+    loaded = None
+    if kmers_from is not None:
+        k = kmer.set_k(kmers_from, k)                # the header alone: no device
     partitions = kmer._check_partitions(partitions)
     kmer_min_qual = kmer.check_kmer_min_qual(kmer_min_qual)
     b = _kmer_benchmark_inputs(bamfile, k, min_count, prefilter, filter_bits)
@@ -551,7 +558,9 @@ def benchmark_kmers(bamfile, ref, var_sites, k=31, min_count=None, slots=None, p
                 filt.release_seen()
             total, room = admitted if prefilter else windows, budget - resident - (filt.nbytes if filt is not None else 0)
             P = kmer.resolve_partitions(partitions, total, room) if partitions != 1 else 1
-            if P > 1:
+            if kmers_from is not None:
+                table, _, t, loaded = kmer.load_set(kmers_from, min_count, slots, k=k, budget=room)
+            elif P > 1:
                 table, _, t, parts_info = kmer.count_partitioned(
                     lambda tab, p: kmer.count_kmers(counted, d_len, k=k, table=tab, filter=filt, parts=P, part=p), k, P,
                     slots if slots is not None else kmer.partition_slots(total, P, room), min_count, room)
@@ -583,6 +592,8 @@ def benchmark_kmers(bamfile, ref, var_sites, k=31, min_count=None, slots=None, p
             info.update(partitions=P, kept_pairs=parts_info['kept_pairs'], solid_slots=parts_info['solid_slots'])
         if kmer_min_qual is not None:
             info.update(kmer_min_qual=kmer_min_qual, counted_windows=windows if n else 0, windows=ungated if n else 0)
+        if kmers_from is not None:
+            info.update(kmers_from=kmers_from, loaded_kmers=loaded['loaded_kmers'] if loaded is not None else 0)
     return joint
 
 
@@ -609,6 +620,8 @@ def kmer_summary(info):
         line += ' kmer_min_qual=%d counted_windows=%d' % (info['kmer_min_qual'], info['counted_windows'])
     if info.get('prefilter'):
         line += ' prefilter=1 admitted=%d slots=%d' % (info['admitted'], info['slots'])
+    if info.get('kmers_from'):
+        line += ' kmers_from=1 loaded_kmers=%d' % info['loaded_kmers']
     return line
 
 
@@ -630,7 +643,7 @@ def print_benchmark_kmers(joint, label):
 
 def benchmark(bamfile, fafile, vcffile, fastqfile=None, label=None, use_oq=False, bedfh=None, kmers=None):
     """Run the benchmark and print it.  With a FASTQ, its reads are matched to the alignments by name.  kmers: a dict of
-    benchmark_kmers' options (k, min_count, slots, prefilter, filter_bits, passes, partitions, kmer_min_qual) -- print the k-mer rule's flags against the truth
+    benchmark_kmers' options (k, min_count, slots, prefilter, filter_bits, passes, partitions, kmer_min_qual, kmers_from) -- print the k-mer rule's flags against the truth
     set's instead (print_benchmark_kmers) and one summary line on stderr."""
     if kmers is not None and fastqfile is not None:
         raise ValueError('benchmark --kmers takes the alignments alone (-b), not a FASTQ joined by name (-f)')

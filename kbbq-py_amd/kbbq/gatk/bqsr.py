@@ -360,7 +360,7 @@ def _kmer_inputs(bamfileobj, k, min_count, prefilter, filter_bits, use_oq, maxsc
 
 def bam_to_kmer_covariates(bamfileobj, k=31, min_count=None, slots=None, prefilter=False, filter_bits=4, use_oq=False,
                            minscore=6, maxscore=42, info=None, skip_unresolved=False, passes=1, partitions=1, mixed_lengths=False,
-                           exclude_flags=0, kmer_min_qual=None):
+                           exclude_flags=0, kmer_min_qual=None, kmers_from=None):
     """The nine model vectors from aligned reads alone -- no reference, no known sites (`kbbq bqsr --kmers`).  A base is an error
     where the k-mer correction of kbbq.kmer would change it: every k-mer of SEQ of every record is counted (soft clips too:
     they are sequenced bases; keys are canonical, so the alignment's strand does not matter), a k-mer is solid at min_count
@@ -395,25 +395,32 @@ def bam_to_kmer_covariates(bamfileobj, k=31, min_count=None, slots=None, prefilt
     kmer_min_qual = Q (kbbq.kmer.gate_plane): only the k-mers whose bases all have quality >= Q -- QUAL, or the OQ tag with use_oq:
     the plane the tally reads -- are counted; the prefilter, the count and every partition round read the gated copy of SEQ, the
     filter and the default table are sized from the counted windows, and the flags are written for SEQ as read.  An excluded
-    record is a row of length 0 to the gate too.  `info` then receives kmer_min_qual, counted_windows and windows."""
+    record is a row of length 0 to the gate too.  `info` then receives kmer_min_qual, counted_windows and windows.
+    kmers_from = PATH (kbbq.kmer.load_set): nothing is counted -- the table and the threshold are those of the k-mer set file, which
+    may have been counted from other files (the raw FASTQ of these alignments); k is the set's (pass k=None, or the set's) and no
+    counting option goes with it.  `info` then receives kmers_from and loaded_kmers too, and its slots is the loaded table's."""
     from .. import kmer
     passes = kmer.check_passes(passes)
+    kmers_from = kmer.check_kmers_from(kmers_from, prefilter, filter_bits, partitions, kmer_min_qual)
     partitions = kmer._check_partitions(partitions)
     kmer_min_qual = kmer.check_kmer_min_qual(kmer_min_qual)
-    inputs = _kmer_inputs(bamfileobj, k, min_count, prefilter, filter_bits, use_oq, maxscore, mixed_lengths, exclude_flags)
-    return _kmer_tally(bamfileobj, inputs, int(k), min_count, slots, prefilter, filter_bits, use_oq, minscore, maxscore, info,
-                       skip_unresolved, passes, partitions, **kmer._min_qual_kw(kmer_min_qual))[0]
+    inputs = _kmer_inputs(bamfileobj, 31 if kmers_from is not None and k is None else k, min_count, prefilter, filter_bits, use_oq,
+                          maxscore, mixed_lengths, exclude_flags)
+    return _kmer_tally(bamfileobj, inputs, k if kmers_from is not None and k is None else int(k), min_count, slots, prefilter,
+                       filter_bits, use_oq, minscore, maxscore, info, skip_unresolved, passes, partitions,
+                       **kmer._min_qual_kw(kmer_min_qual), **kmer._kmers_from_kw(kmers_from))[0]
 
 
 def _kmer_tally(bamfileobj, inputs, k, min_count, slots, prefilter, filter_bits, use_oq, minscore, maxscore, info, skip_unresolved,
-                passes, partitions, kmer_min_qual=None):
+                passes, partitions, kmer_min_qual=None, kmers_from=None):
     """bam_to_kmer_covariates past its refusals (`inputs`: what _kmer_inputs returned, the mask of excluded records included where
     it gave one; passes and partitions checked): (the nine
     vectors, resident).  `resident` is what the tally leaves on the device and the per-record arrays beside it, for a caller
     that goes on with the same alignments (kbbq.recalibrate.recalibrate_bam): batch, n, S, pitch, the device planes seq and
     source (QUAL, or OQ with use_oq), use_oq, rg_to_int, and planes / h2d_plane_bytes -- the names of the planes uploaded and
     their bytes.  bam_to_kmer_covariates drops it.  kmer_min_qual (checked): the prefilter and the count read the gated copy
-    of SEQ (counted), which lives until the count is over; everything after reads d_seq."""
+    of SEQ (counted), which lives until the count is over; everything after reads d_seq.  kmers_from (checked): the table is
+    kmer.load_set's, within what the budget leaves beside the resident planes; k may be None (the set's)."""
     from .. import _device as dev
     from .. import _solve, fastx, kmer
     b, n, S, *excluded = inputs
@@ -436,13 +443,14 @@ def _kmer_tally(bamfileobj, inputs, k, min_count, slots, prefilter, filter_bits,
     d_seq, d_qual = up(b.plane(0, pitch)), up(b.plane(2 if use_oq else 1, pitch))
     d_len, d_clip, d_trim, d_flags = (up(x.view(np.int32)) for x in (lens, clip, trim, flags))
     resident = 3 * n * pitch + 20 * n          # SEQ, qualities and the flag plane; the per-read words
-    windows = ungated = kmer.kmer_total(lens, k)
+    windows = ungated = kmer.kmer_total(lens, k) if kmers_from is None else 0
     counted = d_seq                            # the plane the prefilter and the count read
     if kmer_min_qual is not None:
         counted, windows = kmer.gate_plane(d_seq, d_qual, d_len, k, kmer_min_qual)
         resident += n * pitch                  # ... until the count is over
     filt = table = None
     admitted = None
+    loaded = None
     try:
         if prefilter:
             filt = kmer.prefilter_kmers(counted, d_len, k=k, filter=kmer.KmerFilter(kmer.filter_words(windows, filter_bits)))
@@ -450,7 +458,10 @@ def _kmer_tally(bamfileobj, inputs, k, min_count, slots, prefilter, filter_bits,
             filt.release_seen()
         total, room = admitted if prefilter else windows, budget - resident - (filt.nbytes if filt is not None else 0)
         P = kmer.resolve_partitions(partitions, total, room) if partitions != 1 else 1
-        if P > 1:
+        if kmers_from is not None:
+            table, _, t, loaded = kmer.load_set(kmers_from, min_count, slots, k=k, budget=room)
+            k = loaded['k']
+        elif P > 1:
             table, _, t, parts_info = kmer.count_partitioned(
                 lambda tab, p: kmer.count_kmers(counted, d_len, k=k, table=tab, filter=filt, parts=P, part=p), k, P,
                 slots if slots is not None else kmer.partition_slots(total, P, room), min_count, room)
@@ -492,6 +503,8 @@ def _kmer_tally(bamfileobj, inputs, k, min_count, slots, prefilter, filter_bits,
             info.update(excluded_reads=int(excluded[0].sum()))
         if kmer_min_qual is not None:
             info.update(kmer_min_qual=kmer_min_qual, counted_windows=windows, windows=ungated)
+        if loaded is not None:
+            info.update(kmers_from=loaded['kmers_from'], loaded_kmers=loaded['loaded_kmers'])
     kept =dict(batch=b, n=n, S=S, pitch=pitch, seq=d_seq, source=d_qual, use_oq=bool(use_oq), rg_to_int=rg_to_int,
                 planes=['SEQ', 'OQ' if use_oq else 'QUAL'], h2d_plane_bytes=2 * n * pitch)
     return _solve.vectors_from_tables(*tables.to_host(), maxscore), kept
@@ -619,13 +632,15 @@ def bam_to_report(bamfileobj, fastafilename, var_pos):
 
 
 def bam_to_report_kmers(bamfileobj, k=31, min_count=None, slots=None, prefilter=False, filter_bits=4, use_oq=False, info=None,
-                        skip_unresolved=False, passes=1, partitions=1, mixed_lengths=False, exclude_flags=0, kmer_min_qual=None):
+                        skip_unresolved=False, passes=1, partitions=1, mixed_lengths=False, exclude_flags=0, kmer_min_qual=None,
+                        kmers_from=None):
     """Aligned reads -> recalibration report without a reference or known sites: the errors are what the k-mers of the reads'
     own sequences contradict (bam_to_kmer_covariates); read groups are named by their PU as in bam_to_report.  skip_unresolved:
     bases the k-mers contradict without naming a replacement are left out of the tally (bam_to_kmer_covariates).  partitions: the
     count in that many rounds (bam_to_kmer_covariates): the same report.  mixed_lengths, exclude_flags: bam_to_kmer_covariates'
     (rows without observations are dropped from a report, so an axis of twice the longest record adds no row).  kmer_min_qual:
-    bam_to_kmer_covariates' quality gate in front of the count."""
+    bam_to_kmer_covariates' quality gate in front of the count.  kmers_from: bam_to_kmer_covariates' -- a k-mer set file in the
+    place of the count."""
     rgs = list(utils.get_rg_to_pu(bamfileobj).values())
     vectors = bam_to_kmer_covariates(bamfileobj, k=k, min_count=min_count, slots=slots, prefilter=prefilter,
                                      filter_bits=filter_bits, use_oq=use_oq, info=info, skip_unresolved=skip_unresolved,
@@ -633,5 +648,6 @@ def bam_to_report_kmers(bamfileobj, k=31, min_count=None, slots=None, prefilter=
                                      **({} if partitions == 1 else dict(partitions=partitions)),
                                      **(dict(mixed_lengths=True) if mixed_lengths else {}),
                                      **(dict(exclude_flags=exclude_flags) if exclude_flags else {}),
-                                     **({} if kmer_min_qual is None else dict(kmer_min_qual=kmer_min_qual)))
+                                     **({} if kmer_min_qual is None else dict(kmer_min_qual=kmer_min_qual)),
+                                     **({} if kmers_from is None else dict(kmers_from=kmers_from)))
     return vectors_to_report(*vectors, rgs)

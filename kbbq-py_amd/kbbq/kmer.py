@@ -671,6 +671,21 @@ def gate_plane(seq_plane, qual_plane, meta, k, min_qual, qual_offset=33, windows
     return out[:n], int(windows.cpu().numpy()[0])
 
 
+def count_windows(seq_plane, meta, k, windows=None):
+    """The number of k-mer windows of character rows that a count inserts: those whose k bases are all A/C/G/T inside the read
+    (kmer_total counts the broken ones too).  It is kbbq_kmer_gate_rows_dev with the sequence plane as its own quality plane and
+    the threshold 1, which every character passes; the copy it writes is dropped.  windows: as gate_plane's."""
+    from . import _device as dev
+    T = dev._torch()
+    n, pitch = int(seq_plane.shape[0]), int(seq_plane.shape[1])
+    seq, meta = _to_device(T, seq_plane, np.uint8), _to_device(T, meta, np.uint32)
+    out = T.empty((max(n, 1), pitch), dtype=T.uint8, device='cuda')
+    if windows is None:
+        windows = T.zeros(1, dtype=T.int64, device='cuda')
+    _gate_rows(_ctx(), N.ptr(seq), N.ptr(seq), N.ptr(meta), n, pitch, 0, k, 1, N.ptr(out), N.ptr(windows))
+    return int(windows.cpu().numpy()[0])
+
+
 def gate_batch(batch, k, min_qual, windows=None, qual=None):
     """gate_plane for the rows of a device batch in whatever layout it has: (gated plane in the layout of batch.seq, counted
     windows).  The qualities are batch.qual (characters, offset 33) unless `qual` names another plane of that geometry.
@@ -844,8 +859,173 @@ def count_partitioned(count_round, k, P, slots, min_count, budget):
     return solid, hist, t, info
 
 
+# ---- k-mer sets (kbbq/kmerset.py) ---------------------------------------------------------------------------------------------
+
+PAIR_REASONS = {1: 'its key is not above the key before it (unsorted, or a duplicate)', 2: 'its key is not below 4^k',
+                3: 'its key is not canonical (it is above its reverse complement)', 4: 'its count is below keep'}
+
+
+def sort_pairs(kept, k):
+    """All (keys int64, counts int32) device pairs of the list `kept` (as select returns them; the list is emptied, so each
+    piece is released once it is copied) as ONE pair of device tensors sorted ascending by UNSIGNED key
+    (kbbq_kmer_sort_pairs_dev over the 2k key bits: a k = 32 key with bit 63 set sorts last, not first).  At the peak the
+    device holds the pieces' 12 n bytes, then the sorted copy's 12 n beside them and the sort's temporary."""
+    from . import _device as dev
+    T = dev._torch()
+    lib = N.load()
+    ctx = _ctx()
+    n = sum(int(keys.shape[0]) for keys, _ in kept)
+    if len(kept) == 1:
+        keys, counts = kept.pop()
+    else:
+        keys = T.empty(max(n, 1), dtype=T.int64, device='cuda')
+        counts = T.empty(max(n, 1), dtype=T.int32, device='cuda')
+        at = 0
+        while kept:
+            kk, cc = kept.pop(0)
+            m = int(kk.shape[0])
+            if m:
+                keys[at:at + m].copy_(kk)
+                counts[at:at + m].copy_(cc)
+            at += m
+            del kk, cc
+    if n == 0:
+        return keys[:0], counts[:0]
+    out_keys = T.empty(n, dtype=T.int64, device='cuda')
+    out_counts = T.empty(n, dtype=T.int32, device='cuda')
+    need = ctypes.c_size_t(0)
+    N.check(lib.kbbq_kmer_sort_pairs_bytes(ctx.handle, n, ctypes.byref(need)))
+    temp = T.empty(max(int(need.value), 16), dtype=T.uint8, device='cuda')
+    N.check(lib.kbbq_kmer_sort_pairs_dev(ctx.handle, int(k), N.ptr(keys), N.ptr(counts), N.ptr(out_keys), N.ptr(out_counts), n,
+                                         N.ptr(temp), int(need.value)))
+    ctx.sync()
+    return out_keys, out_counts
+
+
+def check_pairs(keys, counts, k, keep, first=0, prev=None, sums=None):
+    """kbbq_kmer_check_pairs_dev on one slab of device pairs: (sums, bad).  sums: a uint64 [2] NumPy array the slab's key and
+    count sums (mod 2^64) are ADDED to (a new one when None); bad: None, or (global pair index, reason text) of the lowest pair
+    that is not above the key before it (`prev` for the slab's first, when given), not below 4^k, not canonical or below keep."""
+    n = int(keys.shape[0])
+    if sums is None:
+        sums = np.zeros(2, dtype=np.uint64)
+    if n == 0:
+        return sums, None
+    ctx = _ctx()
+    index, why = ctypes.c_int64(-1), ctypes.c_int(0)
+    N.check(N.load().kbbq_kmer_check_pairs_dev(ctx.handle, N.ptr(keys), N.ptr(counts), n, int(k), int(keep), int(first),
+                                               0 if prev is None else 1, 0 if prev is None else int(prev), N.ptr(sums),
+                                               ctypes.byref(index), ctypes.byref(why)))
+    return sums, (None if index.value < 0 else (int(index.value), PAIR_REASONS.get(int(why.value), 'reason %d' % why.value)))
+
+
+COUNTING_OPTIONS = ('prefilter', 'filter_bits', 'partitions', 'kmer_min_qual', 'local_slots')
+
+
+def check_kmers_from(kmers_from, prefilter=False, filter_bits=4, partitions=1, kmer_min_qual=None, local_slots=None):
+    """The one refusal of every call that takes kmers_from: a loaded set takes no counting options.  Returns the path (None:
+    nothing is loaded and nothing is checked).  No device, no collective."""
+    if kmers_from is None:
+        return None
+    given = [name for name, v, default in (('prefilter', bool(prefilter), False), ('filter_bits', filter_bits, 4),
+                                           ('partitions', partitions, 1), ('kmer_min_qual', kmer_min_qual, None),
+                                           ('local_slots', local_slots, None)) if v is not None and v != default]
+    if given:
+        raise ValueError('%s: not with kmers_from: these are counting options, and the k-mers come counted from %s'
+                         % (', '.join(given), kmers_from))
+    return os.fspath(kmers_from)
+
+
+def kmers_from_field(info):
+    """` kmers_from=1 loaded_kmers=N` at the very end of a command's stderr line when its k-mers were loaded, else nothing."""
+    return ' kmers_from=1 loaded_kmers=%d' % info['loaded_kmers'] if info.get('kmers_from') else ''
+
+
+def _kmers_from_kw(kmers_from):
+    """The keyword for a callee: none without a set, whose calls are the ones they were before the option."""
+    return dict(kmers_from=kmers_from) if kmers_from is not None else {}
+
+
+def set_k(kmers_from, k=None):
+    """The k of a k-mer set (a path, whose header is read, or a kmerset.KmerSet); an explicit `k` that differs is a ValueError
+    naming both.  No device."""
+    from . import kmerset
+    s = kmers_from if isinstance(kmers_from, kmerset.KmerSet) else kmerset.open_set(kmers_from)
+    if k is not None and int(k) != s.k:
+        raise ValueError('k = %d was asked for, but the k-mer set %s was counted with k = %d' % (int(k), s.path, s.k))
+    return s.k
+
+
+def load_set(path, min_count=None, slots=None, k=None, budget=None, slab=None):
+    """A k-mer set file (kbbq/kmerset.py) as the tuple every counting block ends with: (table, hist, t, info).  k is the file's
+    (an explicit `k` that differs is a ValueError naming both); t is min_count (below the file's keep: ValueError naming both)
+    or the first valley of the file's histogram at or above keep (kmerset.set_threshold; none: solid_threshold's ValueError).
+    ALL n pairs are loaded, those with keep <= count < t too, as count_partitioned merges all it kept: no decision reads them,
+    and leaving them out would cost a compaction pass per slab.  The table has `slots` slots, else default_slots(n, budget)
+    (budget: the device budget); one that is too small raises KmerTableFull.  The file is read slab by slab (`slab` pairs,
+    default kmerset.slab_pairs(): KBBQ_STAGE_MB) into one page-locked buffer, uploaded, CHECKED ON THE DEVICE
+    (check_pairs; the last key of a slab is handed to the next) and merged (kbbq_kmer_merge_dev): host memory does not grow with
+    n.  A pair that fails raises ValueError('k-mer set PATH: pair I: ...'), sums that differ from the header's
+    ValueError('... checksum ...'); either way the table is closed and no kernel has read it.
+    info: k, keep, min_qual, reads, windows, kmers_from (the path), loaded_kmers, slots, table_bytes."""
+    from . import _device as dev
+    from . import kmerset
+    s = kmerset.open_set(path)
+    set_k(s, k)
+    if min_count is not None:
+        if int(min_count) < s.keep:
+            raise ValueError('min_count = %d is below keep = %d of the k-mer set %s: the k-mers seen fewer than %d times are not '
+                             'in it' % (int(min_count), s.keep, s.path, s.keep))
+        t = int(min_count)
+    else:
+        t = kmerset.set_threshold(s.hist, s.keep)
+    T = dev._torch()
+    n = s.n
+    pairs = max(min(int(slab) if slab else kmerset.slab_pairs(), max(n, 1)), 1)
+    if slots is None:
+        slots = default_slots(n, dev.device_budget() if budget is None else budget)
+    table = KmerTable(s.k, slots)
+    try:
+        if n:
+            host = dev.pinned('kmerset', 0, pairs * 12)
+            d_keys = T.empty(pairs, dtype=T.int64, device='cuda')
+            d_counts = T.empty(pairs, dtype=T.int32, device='cuda')
+            sums = np.zeros(2, dtype=np.uint64)
+            prev = None
+            with open(s.path, 'rb') as fh:
+                for lo in range(0, n, pairs):
+                    m = min(pairs, n - lo)
+                    h_keys, h_counts = host[:8 * m].view(T.int64), host[8 * pairs:8 * pairs + 4 * m].view(T.int32)
+                    for at, h in ((s.keys_offset + 8 * lo, h_keys), (s.counts_offset + 4 * lo, h_counts)):
+                        fh.seek(at)
+                        raw = h.numpy().view(np.uint8)
+                        if fh.readinto(memoryview(raw)) != raw.nbytes:
+                            raise ValueError('k-mer set %s: the file ends inside its pairs' % s.path)
+                    last = int(h_keys.numpy().view(np.uint64)[m - 1])
+                    d_keys[:m].copy_(h_keys)
+                    d_counts[:m].copy_(h_counts)
+                    _, bad = check_pairs(d_keys[:m], d_counts[:m], s.k, s.keep, first=lo, prev=prev, sums=sums)
+                    if bad is not None:
+                        raise ValueError('k-mer set %s: pair %d: %s' % (s.path, bad[0], bad[1]))
+                    merge(table, d_keys[:m], d_counts[:m])
+                    prev = last
+            del d_keys, d_counts, host
+            dev.release_pinned('kmerset')
+            if (int(sums[0]), int(sums[1])) != (s.key_sum, s.count_sum):
+                raise ValueError('k-mer set %s: checksum: the pairs sum to (%d, %d), the header says (%d, %d)'
+                                 % (s.path, int(sums[0]), int(sums[1]), s.key_sum, s.count_sum))
+        elif (s.key_sum, s.count_sum) != (0, 0):
+            raise ValueError('k-mer set %s: checksum: no pairs, but the header says (%d, %d)' % (s.path, s.key_sum, s.count_sum))
+    except BaseException:
+        table.close()
+        raise
+    info = dict(k=s.k, keep=s.keep, min_qual=s.min_qual, reads=s.reads, windows=s.windows, kmers_from=s.path, loaded_kmers=n,
+                slots=table.slots, table_bytes=table.nbytes)
+    return table, s.hist.copy(), t, info
+
+
 def correct_reads(seq_plane, meta, k=31, min_count=None, slots=None, prefilter=False, filter_bits=4, fix_n=False, passes=1,
-                  partitions=1, qual_plane=None, kmer_min_qual=None):
+                  partitions=1, qual_plane=None, kmer_min_qual=None, kmers_from=None):
     """Count, pick the threshold (min_count, else the histogram's first valley) and correct.  Returns (corrected plane in
     the input's layout and kind, info) with info = {'k', 'min_count', 'hist', 'changed' (per read), 'slots', 'table_bytes',
     'prefilter', 'filter_bytes', 'admitted', 'fix_n', 'passes'}.  passes: the rule applied that many times to each row against
@@ -863,8 +1043,19 @@ def correct_reads(seq_plane, meta, k=31, min_count=None, slots=None, prefilter=F
     quality >= Q are counted.  The prefilter, the count and every partition round read the gated plane, which is freed when the
     count is over; the filter and the default table are sized from the counted windows; the histogram and the threshold are
     the gated table's; the rows as read are corrected against it.  info then has 'kmer_min_qual', 'counted_windows' and
-    'windows' (the ungated total) too."""
+    'windows' (the ungated total) too.
+    kmers_from = PATH (load_set): nothing is counted -- the table, the histogram and the threshold are those of the k-mer set file
+    (k too: pass k=None, or the file's), and the reads are corrected against it as against a table counted here.  No counting
+    option goes with it (check_kmers_from).  info then has 'kmers_from' and 'loaded_kmers' too."""
     passes = check_passes(passes)
+    if check_kmers_from(kmers_from, prefilter, filter_bits, partitions, kmer_min_qual) is not None:
+        table, hist, t, more = load_set(kmers_from, min_count, slots, k=k)
+        try:
+            out, changed = correct_with(table, seq_plane, meta, t, fix_n=fix_n, **_passes_kw(passes))
+            return out, dict(dict(k=table.k, min_count=t, hist=hist, changed=changed, prefilter=False, filter_bytes=0, admitted=None,
+                                  fix_n=bool(fix_n), passes=passes), **more)
+        finally:
+            table.close()
     partitions = _check_partitions(partitions)
     kmer_min_qual = check_kmer_min_qual(kmer_min_qual, qual_plane is not None)
     if prefilter:
@@ -983,12 +1174,17 @@ def _correct_reads_gated(seq_plane, qual_plane, meta, k, min_count, slots, prefi
 
 
 def correct_fastq(path, out, k=31, min_count=None, slots=None, local_slots=None, prefilter=False, filter_bits=4, fix_n=False,
-                  passes=1, partitions=1, kmer_min_qual=None):
+                  passes=1, partitions=1, kmer_min_qual=None, kmers_from=None):
     """Correct every read of a FASTQ file (plain or .gz) and write '@' + name, the corrected sequence, '+' and the qualities
     as read to `out` (a path, or a text stream).  Returns correct_reads' info.  In a process group of several ranks (or of
     one with KBBQ_DIST_ALWAYS=1) this is correct_fastq_ranks, which has no prefilter and no partitions.  kmer_min_qual: the
-    quality gate of correct_reads, by the file's own quality lines."""
+    quality gate of correct_reads, by the file's own quality lines.  kmers_from: correct_reads' -- the k-mers of a set file in
+    the place of the count; under ranks every rank loads the set (correct_fastq_ranks)."""
     passes = check_passes(passes)
+    if check_kmers_from(kmers_from, prefilter, filter_bits, partitions, kmer_min_qual, local_slots) is not None:
+        if _ranks() is not None:
+            return correct_fastq_ranks(path, out, k=k, min_count=min_count, slots=slots, fix_n=fix_n, **_passes_kw(passes),
+                                       kmers_from=kmers_from)
     partitions = _check_partitions(partitions)
     kmer_min_qual = check_kmer_min_qual(kmer_min_qual)
     if prefilter:
@@ -1007,7 +1203,7 @@ def correct_fastq(path, out, k=31, min_count=None, slots=None, local_slots=None,
         fq.close()
     fixed, info = correct_reads(seq, meta, k=k, min_count=min_count, slots=slots, prefilter=prefilter, filter_bits=filter_bits,
                                 fix_n=fix_n, **_passes_kw(passes), **_partitions_kw(partitions),
-                                **_min_qual_kw(kmer_min_qual, qual_plane=qual))
+                                **_min_qual_kw(kmer_min_qual, qual_plane=qual), **_kmers_from_kw(kmers_from))
     text = fastx.format_fastq(names, fixed, qual, meta & 0xFFFF)
     if isinstance(out, str):
         with open(out, 'w', encoding='latin-1', newline='') as fh:
@@ -1020,12 +1216,13 @@ def correct_fastq(path, out, k=31, min_count=None, slots=None, local_slots=None,
 
 
 def main_correct(path, output=None, k=31, min_count=None, slots=None, local_slots=None, prefilter=False, filter_bits=4, fix_n=False,
-                 passes=1, partitions=1, kmer_min_qual=None):
+                 passes=1, partitions=1, kmer_min_qual=None, kmers_from=None):
     """`kbbq correct`: the corrected FASTQ to `output` or stdout; the threshold and the changed bases to stderr (once, by rank
     0, with the figures of all ranks); with fix_n ` fix_n=1`; with passes = P > 1 ` passes=P`; with more than one partition
     (given, or resolved from 'auto') ` partitions=P`; with the quality gate ` kmer_min_qual=Q counted_windows=N`; with the
-    prefilter also the admitted k-mers and the table's slots."""
+    prefilter also the admitted k-mers and the table's slots; with kmers_from, at the very end, ` kmers_from=1 loaded_kmers=N`."""
     passes = check_passes(passes)                        # every rank refuses, before its first collective
+    check_kmers_from(kmers_from, prefilter, filter_bits, partitions, kmer_min_qual, local_slots)   # ... this too
     kmer_min_qual = check_kmer_min_qual(kmer_min_qual)   # ... this too
     partitions = _check_partitions(partitions)           # ... this too: a process group takes no partitions
     if prefilter:
@@ -1034,13 +1231,13 @@ def main_correct(path, output=None, k=31, min_count=None, slots=None, local_slot
     if ranks is None:
         info = correct_fastq(path, output if output else sys.stdout, k=k, min_count=min_count, slots=slots,
                              prefilter=prefilter, filter_bits=filter_bits, fix_n=fix_n, **_passes_kw(passes),
-                             **_partitions_kw(partitions), **_min_qual_kw(kmer_min_qual))
+                             **_partitions_kw(partitions), **_min_qual_kw(kmer_min_qual), **_kmers_from_kw(kmers_from))
         changed = int(np.asarray(info['changed'], dtype=np.int64).sum())
     else:
         try:
             info = correct_fastq_ranks(path, output if output else sys.stdout, k=k, min_count=min_count, slots=slots,
                                        local_slots=local_slots, fix_n=fix_n, **_passes_kw(passes),
-                                       **_min_qual_kw(kmer_min_qual))
+                                       **_min_qual_kw(kmer_min_qual), **_kmers_from_kw(kmers_from))
         except Exception as exc:
             if not getattr(exc, 'every_rank', False):
                 raise
@@ -1053,10 +1250,11 @@ def main_correct(path, output=None, k=31, min_count=None, slots=None, local_slot
         changed = info['changed_bases']
         if ranks[1] != 0:
             return info
-    sys.stderr.write('kbbq correct: k=%d min_count=%d reads=%d changed_bases=%d%s%s%s%s%s\n'
+    sys.stderr.write('kbbq correct: k=%d min_count=%d reads=%d changed_bases=%d%s%s%s%s%s%s\n'
                      % (info['k'], info['min_count'], info['reads'], changed, ' fix_n=1' if fix_n else '',
                         ' passes=%d' % passes if passes > 1 else '', partitions_field(info), min_qual_field(info),
-                        ' prefilter=1 admitted=%d slots=%d' % (info['admitted'], info['slots']) if prefilter else ''))
+                        ' prefilter=1 admitted=%d slots=%d' % (info['admitted'], info['slots']) if prefilter else '',
+                        kmers_from_field(info)))
     return info
 
 
@@ -1185,6 +1383,46 @@ def solid_table(owned, min_count):
     return table
 
 
+def _correct_shard_from(kmers_from, out, names, seq, qual, meta, k, min_count, slots, fix_n, passes):
+    """correct_fastq_ranks past its shard with a k-mer set in the place of the count, the gather and the solid table."""
+    from . import fastx
+    from . import parallel
+    world, rank = parallel.world_rank()
+    loaded = exc = None
+    try:
+        loaded = load_set(kmers_from, min_count, slots, k=k)
+    except Exception as e:                   # noqa: BLE001 -- every rank must reach the agreement
+        exc = e
+    try:
+        _agree(exc)
+    except BaseException:
+        if loaded is not None:
+            loaded[0].close()
+        raise
+    table, hist, t, more = loaded
+    reads = sum(parallel.all_gather_object(len(names)))
+    fixed = changed = exc = None
+    try:
+        fixed, changed = correct_with(table, seq, meta, t, fix_n=fix_n, **_passes_kw(passes))
+    except Exception as e:                   # noqa: BLE001
+        exc = e
+    finally:
+        table.close()
+    _agree(exc)
+    total = int(parallel.sum_over_ranks(np.array([changed.astype(np.int64).sum()], dtype=np.int64))[0])
+    text = fastx.format_fastq(names, fixed, qual, meta & 0xFFFF)
+    if isinstance(out, str):
+        with open(out if world == 1 else '%s.rank%04d' % (out, rank), 'w', encoding='latin-1', newline='') as fh:
+            fh.write(text)
+    else:
+        def write():
+            out.write(text)
+            out.flush()
+        parallel.in_rank_order(write)
+    return dict(dict(k=more['k'], min_count=t, hist=hist, changed=changed, reads=reads, changed_bases=total, fix_n=bool(fix_n),
+                     passes=passes), **{key: more[key] for key in ('kmers_from', 'loaded_kmers', 'slots')})
+
+
 def _read_shard(path, rank, world):
     """(names, seq plane, qual plane, meta) of this rank's records.  A plain file: the records that start in this rank's
     byte range, cut at record starts (kbbq_fastq_sync_offset) -- nobody reads the whole file.  A .gz file: every rank
@@ -1216,17 +1454,22 @@ def _read_shard(path, rank, world):
     return names, seq, qual, meta
 
 
-def correct_fastq_ranks(path, out, k=31, min_count=None, slots=None, local_slots=None, fix_n=False, passes=1, kmer_min_qual=None):
+def correct_fastq_ranks(path, out, k=31, min_count=None, slots=None, local_slots=None, fix_n=False, passes=1, kmer_min_qual=None,
+                        kmers_from=None):
     """correct_fastq on every rank of the process group: each rank reads, counts and corrects its own records and writes them
     to `out`.rankNNNN (`out` itself with one rank) or, for a stream, to `out` in rank order.  The threshold comes from the
     global histogram; info carries this rank's per-read changes and the global 'reads' and 'changed_bases'.  fix_n: every rank
     decides its Ns against the gathered solid table at min_count = t, as one process would against the whole table.  passes:
     solidity is all the passes ask of the table too, so the rank files concatenated stay the one-process output.
     kmer_min_qual: every rank gates its own shard before its local count (gate_plane) and its counted windows size the tables;
-    info['counted_windows'] is their sum over the ranks, info['windows'] the ungated total."""
+    info['counted_windows'] is their sum over the ranks, info['windows'] the ungated total.
+    kmers_from: nothing is counted and nothing exchanged -- every rank loads the k-mer set (load_set; `slots` is that table's) and
+    corrects its own shard against it, so a set counted on one GPU with the prefilter or in partitions serves every rank.  A
+    load that fails on any rank is agreed like the other errors here, before a rank corrects anything."""
     from . import fastx
     from . import parallel
     passes = check_passes(passes)
+    kmers_from = check_kmers_from(kmers_from, kmer_min_qual=kmer_min_qual, local_slots=local_slots)
     kmer_min_qual = check_kmer_min_qual(kmer_min_qual)
     world, rank = parallel.world_rank()
     shard = exc = None
@@ -1237,6 +1480,8 @@ def correct_fastq_ranks(path, out, k=31, min_count=None, slots=None, local_slots
     _agree(exc)
     names, seq, qual, meta = shard
     gated = mine = exc = None
+    if kmers_from is not None:
+        return _correct_shard_from(kmers_from, out, names, seq, qual, meta, k, min_count, slots, fix_n, passes)
     if kmer_min_qual is not None:
         try:
             gated, mine = gate_plane(seq, qual, meta, k, kmer_min_qual)

@@ -117,6 +117,25 @@ _PASSES_HELP = ('%s: apply the k-mer rule to its own output this many times, 1..
                 'neighbour is')
 
 
+_KMERS_FROM_HELP = ('%s: take the k-mers from this k-mer set (`kbbq count -o SET`) instead of counting the input\'s: k is the set\'s, '
+                    '--min-count (not below the set\'s --keep) or the first valley of the set\'s histogram is the threshold, --slots '
+                    'the table the set is loaded into; the same output as with the same k-mers counted here.  Not with the counting '
+                    'options --prefilter, --filter-bits, --partitions, --kmer-min-qual and --local-slots%s')
+
+
+def _kmers_from(parser, args, needs=None):
+    """--kmers-from SET: its argparse errors, before the device or a process group is touched."""
+    if args.kmers_from is None:
+        return
+    if needs is not None and not needs[0]:
+        parser.error('--kmers-from: only with %s' % needs[1])
+    given = [flag for flag, v in (('--prefilter', args.prefilter or None), ('--filter-bits', args.filter_bits),
+                                  ('--partitions', args.partitions), ('--kmer-min-qual', args.kmer_min_qual),
+                                  ('--local-slots', getattr(args, 'local_slots', None))) if v is not None]
+    if given:
+        parser.error('%s: not with --kmers-from (counting options: the k-mers come counted)' % ', '.join(given))
+
+
 _ENDS_WITH_THE_COMMAND = False               # set by `python -m kbbq.main`: the process ends (main._leave) when the command has run
 
 
@@ -139,29 +158,34 @@ def _recalibrate_bam_kmers(args):
         kmers['exclude_flags'] = args.exclude_flags
     if args.kmer_min_qual is not None:
         kmers['kmer_min_qual'] = args.kmer_min_qual
+    if args.kmers_from is not None:
+        kmers.update(kmers_from=args.kmers_from, k=args.kmer)                # k: the set's, unless -k names it
     records = {key: kmers[key] for key in ('mixed_lengths', 'exclude_flags') if key in kmers}
     # every rank of a launcher refuses here, before it joins the process group
     _recal.check_bam_kmers(args.bam, args.gatkreport, args.output, kmers['k'], kmers['min_count'], kmers['prefilter'],
-                           kmers['filter_bits'], **{key: kmers[key] for key in ('partitions', 'passes', 'exclude_flags') if key in kmers})
+                           kmers['filter_bits'], **{key: kmers[key] for key in ('partitions', 'passes', 'exclude_flags', 'kmers_from')
+                                                    if key in kmers})
     parallel.init_from_env()
     from . import aln
     from ._trace import stage
     with stage('[recalibrate_bam, wall]'):
         with stage('parse'):
             bam = aln.AlignmentFile(args.bam)    # the one parse; what the records are refused for, before the device is touched
-        _recal.check_bam_records(bam, args.use_oq, kmers['k'], kmers['min_count'], kmers['prefilter'], kmers['filter_bits'], **records)
+        _recal.check_bam_records(bam, args.use_oq, 31 if kmers['k'] is None else kmers['k'], kmers['min_count'], kmers['prefilter'],
+                                 kmers['filter_bits'], **records)
         if kmer._ranks() is None and 'torch' not in sys.modules and not os.environ.get('KBBQ_USE_TORCH'):
             from . import _device
             _device.use_native_memory()          # as `bqsr --kmers` on one GPU: no torch import
         info = _recal.recalibrate_bam(bam, use_oq=args.use_oq, set_oq=args.set_oq, kmers=kmers, gatkreport=args.gatkreport,
                                       output=args.output, **args.quantize)
-    sys.stderr.write('kbbq recalibrate: k=%d min_count=%d reads=%d%s flagged_bases=%d%s%s%s%s%s\n'
+    sys.stderr.write('kbbq recalibrate: k=%d min_count=%d reads=%d%s flagged_bases=%d%s%s%s%s%s%s\n'
                      % (info['k'], info['min_count'], info['reads'],
                         ' excluded_reads=%d' % info['excluded_reads'] if args.exclude_flags else '', info['flagged_bases'],
                         ' skipped_bases=%d' % info['skipped_bases'] if args.skip_unresolved else '',
                         ' passes=%d' % args.passes if (args.passes or 1) > 1 else '', kmer.partitions_field(info),
                         kmer.min_qual_field(info),
-                        ' prefilter=1 admitted=%d slots=%d' % (info['admitted'], info['slots']) if args.prefilter else ''))
+                        ' prefilter=1 admitted=%d slots=%d' % (info['admitted'], info['slots']) if args.prefilter else '',
+                        kmer.kmers_from_field(info)))
 
 
 def recalibrate(args):
@@ -181,13 +205,15 @@ def recalibrate(args):
             kopts['skip_unresolved'] = True
         if args.kmer_min_qual is not None:
             kopts['kmer_min_qual'] = args.kmer_min_qual
+        if args.kmers_from is not None:
+            kopts.update(kmers_from=args.kmers_from, k=args.kmer)            # k: the set's, unless -k names it
         more = {}
         if args.partitions is not None:
             kopts['partitions'] = args.partitions
             more = dict(partitions=args.partitions)
         # every rank of a launcher refuses here, before it joins the process group
-        _recal.check_corrected(args.correct, args.gatkreport, kopts['k'], kopts['min_count'], kopts['prefilter'], kopts['filter_bits'],
-                               **more)
+        _recal.check_corrected(args.correct, args.gatkreport, 31 if kopts['k'] is None else kopts['k'], kopts['min_count'],
+                               kopts['prefilter'], kopts['filter_bits'], **more)
     world, _ = parallel.init_from_env()          # one process per GPU under torch.distributed.run; no-op otherwise
     if world == 1 and 'torch' not in __import__('sys').modules and not os.environ.get('KBBQ_USE_TORCH'):
         # one GPU: nothing of PyTorch is needed -- device memory, page-locked slabs, copies and events come from the library's
@@ -204,14 +230,15 @@ def recalibrate(args):
         with stage('[recalibrate_corrected, wall]'):
             info = _recal.recalibrate_corrected(args.correct, infer_rg=args.infer_rg, gatkreport=args.gatkreport, output=args.output,
                                                 **kopts, **args.quantize)
-        from .kmer import min_qual_field, partitions_field
-        sys.stderr.write('kbbq recalibrate: k=%d min_count=%d reads=%d changed_bases=%d%s%s%s%s%s%s\n'
+        from .kmer import kmers_from_field, min_qual_field, partitions_field
+        sys.stderr.write('kbbq recalibrate: k=%d min_count=%d reads=%d changed_bases=%d%s%s%s%s%s%s%s\n'
                          % (info['k'], info['min_count'], info['reads'], info['changed_bases'],
                             ' skipped_bases=%d' % info['skipped_bases'] if kopts.get('skip_unresolved') else '',
                             ' fix_n=1' if kopts.get('fix_n') else '',
                             ' passes=%d' % kopts['passes'] if kopts.get('passes', 1) > 1 else '', partitions_field(info),
                             min_qual_field(info),
-                            ' prefilter=1 admitted=%d slots=%d' % (info['admitted'], info['slots']) if kopts['prefilter'] else ''))
+                            ' prefilter=1 admitted=%d slots=%d' % (info['admitted'], info['slots']) if kopts['prefilter'] else '',
+                            kmers_from_field(info)))
         return
     _recal.recalibrate(bam=args.bam, fastq=args.fastq, infer_rg=args.infer_rg,
                        use_oq=args.use_oq, set_oq=args.set_oq, gatkreport=args.gatkreport, output=args.output, **args.quantize)
@@ -231,6 +258,8 @@ def benchmark(args):
             kmers['kmers']['partitions'] = args.partitions
         if args.kmer_min_qual is not None:
             kmers['kmers']['kmer_min_qual'] = args.kmer_min_qual
+        if args.kmers_from is not None:
+            kmers['kmers'].update(kmers_from=args.kmers_from, k=args.kmer)   # k: the set's, unless -k names it
     _bm.benchmark(bamfile=args.bam, fafile=args.reference, vcffile=args.vcf, fastqfile=args.fastq,
                   label=args.label, use_oq=args.use_oq, bedfh=args.bedfile, **kmers)
 
@@ -264,17 +293,21 @@ def bqsr(args):
             more['exclude_flags'] = args.exclude_flags
         if args.kmer_min_qual is not None:
             more['kmer_min_qual'] = args.kmer_min_qual
-        _bqsr.bam_to_report_kmers(aln.AlignmentFile(args.bam), k=31 if args.kmer is None else args.kmer, min_count=args.min_count,
+        if args.kmers_from is not None:
+            more['kmers_from'] = args.kmers_from
+        _bqsr.bam_to_report_kmers(aln.AlignmentFile(args.bam),
+                                  k=args.kmer if args.kmers_from is not None or args.kmer is not None else 31, min_count=args.min_count,
                                   slots=args.slots, prefilter=args.prefilter,
                                   filter_bits=4 if args.filter_bits is None else args.filter_bits, use_oq=args.use_oq,
                                   info=info, **skip, **more).write(args.gatkreport)
-        sys.stderr.write('kbbq bqsr: k=%d min_count=%d reads=%d%s flagged_bases=%d%s%s%s%s%s\n'
+        sys.stderr.write('kbbq bqsr: k=%d min_count=%d reads=%d%s flagged_bases=%d%s%s%s%s%s%s\n'
                          % (info['k'], info['min_count'], info['reads'],
                             ' excluded_reads=%d' % info['excluded_reads'] if args.exclude_flags else '', info['flagged_bases'],
                             ' skipped_bases=%d' % info['skipped_bases'] if skip else '',
                             ' passes=%d' % args.passes if (args.passes or 1) > 1 else '', kmer.partitions_field(info),
                             kmer.min_qual_field(info),
-                            ' prefilter=1 admitted=%d slots=%d' % (info['admitted'], info['slots']) if args.prefilter else ''))
+                            ' prefilter=1 admitted=%d slots=%d' % (info['admitted'], info['slots']) if args.prefilter else '',
+                            kmer.kmers_from_field(info)))
         return
     from . import benchmark as _bm
     _bqsr.bam_to_report(aln.AlignmentFile(args.bam), args.reference, _bm.get_var_sites(args.vcf)).write(args.gatkreport)
@@ -298,8 +331,27 @@ def correct(args):
         more['partitions'] = args.partitions
     if args.kmer_min_qual is not None:
         more['kmer_min_qual'] = args.kmer_min_qual
-    kmer.main_correct(args.fastq, output=args.output, k=args.kmer, min_count=args.min_count, slots=args.slots,
-                      local_slots=args.local_slots, prefilter=args.prefilter, filter_bits=args.filter_bits, fix_n=args.fix_n, **more)
+    if args.kmers_from is not None:
+        more['kmers_from'] = args.kmers_from
+    kmer.main_correct(args.fastq, output=args.output, k=args.kmer if args.kmers_from is not None or args.kmer is not None else 31,
+                      min_count=args.min_count, slots=args.slots, local_slots=args.local_slots, prefilter=args.prefilter,
+                      filter_bits=4 if args.filter_bits is None else args.filter_bits, fix_n=args.fix_n, **more)
+
+
+def count(args):
+    import os
+    import sys
+    from . import kmerset
+    opts = dict(k=args.kmer, keep=args.keep, slots=args.slots, prefilter=args.prefilter,
+                filter_bits=4 if args.filter_bits is None else args.filter_bits, partitions=1 if args.partitions is None else args.partitions,
+                kmer_min_qual=args.kmer_min_qual, use_oq=args.use_oq, exclude_flags=args.exclude_flags or 0, histo=args.histo)
+    # every rank of a launcher refuses here, before it joins a process group, and everything else count refuses on its arguments
+    kmerset.check_count(args.fastq, args.bam, args.output, opts['k'], opts['keep'], opts['prefilter'], opts['filter_bits'],
+                        opts['partitions'], opts['kmer_min_qual'], opts['use_oq'], opts['exclude_flags'])
+    if 'torch' not in sys.modules and not os.environ.get('KBBQ_USE_TORCH'):
+        from . import _device
+        _device.use_native_memory()          # as `correct` on one GPU: no torch import
+    kmerset.main_count(args.fastq, args.bam, args.output, **opts)
 
 
 def main(argv=None):
@@ -344,6 +396,7 @@ def main(argv=None):
     rp.add_argument('--partitions', type=_partitions, default=None, metavar='P|auto', help=_PARTITIONS_HELP % 'with -c')
     rp.add_argument('--kmer-min-qual', type=_min_qual, default=None, metavar='Q',
                     help=_MIN_QUAL_HELP % ('with -c, or with -b --kmers', ': the FASTQ quality lines, QUAL, or the OQ tag with -u'))
+    rp.add_argument('--kmers-from', default=None, metavar='SET', help=_KMERS_FROM_HELP % ('with -c, or with -b --kmers', ''))
     rp.add_argument('--skip-unresolved', action='store_true',
                     help='with -c: leave a base out of the tally (neither error nor observation) when the k-mers contradict it but '
                          'name no replacement -- two errors within k bases, thin coverage, contamination -- instead of counting '
@@ -394,6 +447,8 @@ def main(argv=None):
     bp.add_argument('--partitions', type=_partitions, default=None, metavar='P|auto', help=_PARTITIONS_HELP % 'with --kmers')
     bp.add_argument('--kmer-min-qual', type=_min_qual, default=None, metavar='Q',
                     help=_MIN_QUAL_HELP % ('with --kmers', ': QUAL, or the OQ tag with -u; a record without qualities is refused'))
+    bp.add_argument('--kmers-from', default=None, metavar='SET',
+                    help=_KMERS_FROM_HELP % ('with --kmers', ': the set `bqsr --kmers --kmers-from` used can be scored here'))
     bp.set_defaults(command=benchmark)
 
     ap = sub.add_parser('applybqsr', description='Recalibrate alignments with a GATK recalibration report (SAM output)')
@@ -442,12 +497,14 @@ def main(argv=None):
     qp.add_argument('--partitions', type=_partitions, default=None, metavar='P|auto', help=_PARTITIONS_HELP % 'with --kmers')
     qp.add_argument('--kmer-min-qual', type=_min_qual, default=None, metavar='Q',
                     help=_MIN_QUAL_HELP % ('with --kmers', ': QUAL, or the OQ tag with -u'))
+    qp.add_argument('--kmers-from', default=None, metavar='SET',
+                    help=_KMERS_FROM_HELP % ('with --kmers', ': a set counted from the raw FASTQ decides the errors of its alignments'))
     qp.set_defaults(command=bqsr)
 
     cp = sub.add_parser('correct', description='Correct substitution errors of a FASTQ file with k-mer counts (GPU); the output '
                         'is the error-corrected file `recalibrate -f` takes')
     cp.add_argument('-f', '--fastq', required=True, help='FASTQ file to correct (plain or .gz)')
-    cp.add_argument('-k', '--kmer', type=int, default=31, help='k-mer length, 8..32 (default 31)')
+    cp.add_argument('-k', '--kmer', type=int, default=None, help='k-mer length, 8..32 (default 31)')
     cp.add_argument('--min-count', type=int, default=None,
                     help='k-mers seen at least this often are solid (default: the first valley of the count histogram)')
     cp.add_argument('--slots', type=int, default=None,
@@ -462,7 +519,7 @@ def main(argv=None):
                     help='keep most k-mers seen once out of the table with a bit filter passed over the reads first: the same '
                          'output from a table several times smaller, sized from the filter unless --slots is given; needs '
                          '--min-count >= 2 where given; one GPU only (not under torch.distributed.run)')
-    cp.add_argument('--filter-bits', type=int, default=4,
+    cp.add_argument('--filter-bits', type=int, default=None,
                     help='with --prefilter: bits per k-mer of the input in each of the filter\'s two arrays, 1..64 (default 4)')
     cp.add_argument('--fix-n', action='store_true',
                     help='give every N the letter (A, C, G or T) that makes the most of the k-mers it alone breaks solid; an N '
@@ -474,9 +531,58 @@ def main(argv=None):
     cp.add_argument('-o', '--output', default=None,
                     help='Write the corrected FASTQ to this file instead of stdout; under torch.distributed.run every rank '
                          'writes FILE.rankNNNN, to be concatenated in rank order.')
+    cp.add_argument('--kmers-from', default=None, metavar='SET',
+                    help=_KMERS_FROM_HELP % ('one GPU or several', '; under torch.distributed.run every rank loads the set'))
     cp.set_defaults(command=correct)
 
+    np_ = sub.add_parser('count', description='Count the k-mers of one or several FASTQ and alignment files into one k-mer set (GPU): '
+                         'the file --kmers-from of correct, recalibrate -c, bqsr --kmers, recalibrate -b --kmers and benchmark '
+                         '--kmers takes in the place of their own count.  One input is resident at a time; one GPU')
+    np_.add_argument('-f', '--fastq', nargs='+', default=[], metavar='FASTQ',
+                     help='FASTQ files (plain or .gz), counted as `kbbq correct` counts its input')
+    np_.add_argument('-b', '--bam', nargs='+', default=[], metavar='ALN',
+                     help='SAM or BAM files, counted as `kbbq bqsr --kmers` counts its input: every base of SEQ, soft clips included; '
+                          'records of any lengths')
+    np_.add_argument('-o', '--output', default=None, metavar='SET', help='the k-mer set to write; an existing file is refused')
+    np_.add_argument('-k', '--kmer', type=int, default=31, help='k-mer length, 8..32 (default 31)')
+    np_.add_argument('--keep', type=int, default=2,
+                     help='write the k-mers seen at least this often (default 2, the smallest threshold the histogram\'s valley can '
+                          'give); a --min-count below it cannot be served from the set; >= 2 with --prefilter')
+    np_.add_argument('--slots', type=int, default=None,
+                     help='hash table slots, a power of two (default: every k-mer of all inputs at a load factor of 0.5, capped by '
+                          'the device budget; with --partitions: the table of one round)')
+    np_.add_argument('--prefilter', action='store_true',
+                     help='keep most k-mers seen once out of the table (as `kbbq correct --prefilter`): the filter pass runs over all '
+                          'inputs, then the count; the same set')
+    np_.add_argument('--filter-bits', type=int, default=None,
+                     help='with --prefilter: bits per k-mer of the inputs in each of the filter\'s two arrays, 1..64 (default 4)')
+    np_.add_argument('--partitions', type=_partitions, default=None, metavar='P|auto',
+                     help=_PARTITIONS_HELP % 'every round over all inputs')
+    np_.add_argument('--kmer-min-qual', type=_min_qual, default=None, metavar='Q',
+                     help=_MIN_QUAL_HELP % ('every input', ': the FASTQ quality lines, QUAL, or the OQ tag with -u'))
+    np_.add_argument('-u', '--use-oq', action='store_true', help='with -b and --kmer-min-qual: gate by the OQ tag instead of QUAL')
+    np_.add_argument('-F', '--exclude-flags', type=_exclude_flags, default=None, metavar='INT', help=_EXCLUDE_HELP % ('with -b', ''))
+    np_.add_argument('--histo', default=None, metavar='FILE',
+                     help='write the count histogram as `count<TAB>k-mers` lines for counts --keep..256 (the last line: 256 and more), '
+                          'the shape Jellyfish prints and GenomeScope reads')
+    np_.set_defaults(command=count)
+
     args = parser.parse_args(argv)
+    if args.command is correct:
+        _kmers_from(cp, args)
+    elif args.command is recalibrate:
+        _kmers_from(rp, args, (args.correct is not None or (args.kmers and args.bam is not None), '-c/--correct or with -b --kmers'))
+    elif args.command is bqsr or args.command is benchmark:
+        _kmers_from(qp if args.command is bqsr else bp, args, (args.kmers, '--kmers'))
+    elif args.command is count:
+        # decided here: before the device is touched and, under a launcher, before a process group could exist
+        if not args.fastq and not args.bam:
+            np_.error('at least one input is required: -f FASTQ [FASTQ ...] and / or -b ALN [ALN ...]')
+        if args.output is None:
+            np_.error('the following arguments are required: -o/--output')
+        given = [flag for flag, v in (('-u/--use-oq', args.use_oq or None), ('-F/--exclude-flags', args.exclude_flags)) if v is not None]
+        if given and not args.bam:
+            np_.error('%s: only with -b' % ', '.join(given))
     if args.command is recalibrate or args.command is applybqsr:
         # decided here: before the device is touched and, under a launcher, before the process group exists
         args.quantize = _quantize(rp if args.command is recalibrate else ap, args)

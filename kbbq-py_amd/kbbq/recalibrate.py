@@ -407,7 +407,7 @@ def check_corrected(path, gatkreport=None, k=31, min_count=None, prefilter=False
 
 def recalibrate_corrected(path, infer_rg=False, gatkreport=None, output=None, k=31, min_count=None, slots=None, prefilter=False,
                           filter_bits=4, fix_n=False, passes=1, skip_unresolved=False, partitions=1, quantize=None,
-                          kmer_min_qual=None):
+                          kmer_min_qual=None, kmers_from=None):
     """`kbbq correct` and `kbbq recalibrate -f reads corrected` in one run over ONE file: the reads go to the device once, in
     the layout pass 2 uses (fastx.pack_single), their k-mers are counted and the reads corrected where they lie
     (kmer.count_batch / correct_batch: the corrected plane is each band's cseq), and the tally, the solve, the apply and the
@@ -432,17 +432,23 @@ def recalibrate_corrected(path, infer_rg=False, gatkreport=None, output=None, k=
     layout, into one word of counted windows; the prefilter, the count and every partition round read the gated planes, which
     are held until the count is over (one sequence plane per band) and size the filter and the default table; the bands are
     corrected and tallied as read.  info then carries kmer_min_qual, counted_windows and windows.
+    kmers_from: a k-mer set file (kmer.load_set) in the place of the prefilter, the count, the histogram and the threshold: the
+    table is loaded within what the budget leaves beside the reads, k is the set's (pass k=None, or the set's), no counting
+    option goes with it, and everything after is what it is.  info then carries kmers_from and loaded_kmers.
     One process, mapped inputs, reads that fit the device budget: anything else raises ValueError naming the two commands."""
     from . import kmer
     quantize = applybqsr._check_qmap(quantize)
     passes = kmer.check_passes(passes)
+    kmers_from = kmer.check_kmers_from(kmers_from, prefilter, filter_bits, partitions, kmer_min_qual)
     kmer_min_qual = kmer.check_kmer_min_qual(kmer_min_qual)
+    if kmers_from is not None:
+        k = kmer.set_k(kmers_from, k)                # the header alone: no device
     check_corrected(path, gatkreport, k, min_count, prefilter, filter_bits, **kmer._partitions_kw(partitions))
     done_with = []
     try:
         return _recalibrate_corrected(path, infer_rg, gatkreport, output, int(k), min_count, slots, prefilter, filter_bits, done_with,
                                       bool(fix_n), passes, bool(skip_unresolved), partitions, quantize,
-                                      **kmer._min_qual_kw(kmer_min_qual))
+                                      **kmer._min_qual_kw(kmer_min_qual), **kmer._kmers_from_kw(kmers_from))
     finally:
         for reader in done_with:
             fastx.close_later(reader)
@@ -454,7 +460,7 @@ def _batch_bytes(batch):
 
 
 def _recalibrate_corrected(path, infer_rg, gatkreport, output, k, min_count, slots, prefilter, filter_bits, done_with, fix_n=False,
-                           passes=1, skip=False, partitions=1, quantize=None, kmer_min_qual=None):
+                           passes=1, skip=False, partitions=1, quantize=None, kmer_min_qual=None, kmers_from=None):
     from . import kmer
     more = kmer._passes_kw(passes)
     if skip:
@@ -516,7 +522,10 @@ def _recalibrate_corrected(path, infer_rg, gatkreport, output, k, min_count, slo
             total = info['admitted'] if prefilter else windows
             room = budget - resident - (filt.nbytes if filt is not None else 0)
             P = kmer.resolve_partitions(partitions, total, room) if partitions != 1 else 1
-            if P > 1:
+            if kmers_from is not None:
+                with stage('k-mer load', sync=True):
+                    table, hist, t, loaded = kmer.load_set(kmers_from, min_count, slots, k=k, budget=room)
+            elif P > 1:
                 def count_round(tab, p):
                     for r, g in zip(rows, gated):
                         kmer.count_batch(r, k, table=tab, filter=filt, parts=P, part=p, plane=g)
@@ -539,7 +548,9 @@ def _recalibrate_corrected(path, infer_rg, gatkreport, output, k, min_count, slo
             filt.close()
             filt = None
         del gated[:]                                   # the count is over: everything below reads the bands as read
-        if P > 1:
+        if kmers_from is not None:
+            info.update(hist=hist, slots=table.slots, kmers_from=loaded['kmers_from'], loaded_kmers=loaded['loaded_kmers'])
+        elif P > 1:
             info.update(parts_info, hist=hist)
         else:
             info['slots'] = table.slots
@@ -874,10 +885,11 @@ def _as_bam_kmers(exc):
 
 
 def check_bam_kmers(bam, gatkreport=None, output=None, k=31, min_count=None, prefilter=False, filter_bits=4, partitions=1, passes=1,
-                    exclude_flags=0, kmer_min_qual=None):
+                    exclude_flags=0, kmer_min_qual=None, kmers_from=None):
     """What recalibrate_bam refuses of its options, before the alignments are read, before any device work and, under a
     launcher, before the process group exists: a process group, what `bqsr --kmers` refuses of the k-mer options (the same
-    exception types), an output name ending in .bam and a report that exists."""
+    exception types), an output name ending in .bam and a report that exists.  kmers_from: k may then be None (the set's),
+    and a counting option is refused (kmer.check_kmers_from)."""
     from . import kmer
     from .gatk import bqsr
     if parallel.launched_from_env() or kmer._ranks() is not None:
@@ -885,6 +897,8 @@ def check_bam_kmers(bam, gatkreport=None, output=None, k=31, min_count=None, pre
                          'GPU): on one GPU, or %s' % (_BAM_KMERS, BAM_TWO_COMMANDS))
     try:
         kmer.check_passes(passes)
+        if kmer.check_kmers_from(kmers_from, prefilter, filter_bits, partitions, kmer_min_qual) is not None and k is None:
+            k = 31                               # the set's: nothing to refuse here
         kmer._check_partitions(partitions)
         kmer.check_kmer_min_qual(kmer_min_qual)
         if not 8 <= int(k) <= 32:
@@ -919,7 +933,7 @@ def check_bam_records(bam, use_oq=False, k=31, min_count=None, prefilter=False, 
 def recalibrate_bam(bam, use_oq=False, set_oq=False, kmers=None, gatkreport=None, output=None, quantize=None):
     """Without kmers: not implemented, as in the reference.
     bam: a path, or an aln.AlignmentFile.  kmers (a dict of bam_to_kmer_covariates' k-mer options: k, min_count, slots, prefilter, filter_bits, skip_unresolved, passes,
-    partitions, mixed_lengths, exclude_flags, kmer_min_qual -- a record that exclude_flags leaves out of the model is still recalibrated and
+    partitions, mixed_lengths, exclude_flags, kmer_min_qual, kmers_from (a k-mer set file in the place of the count; k may then be None) -- a record that exclude_flags leaves out of the model is still recalibrated and
     written like any other): `kbbq bqsr -b bam --kmers ... [-u] -g R` and `kbbq applybqsr -b bam -g R [-u] [-s] [-o output]` in one run, the
     same bytes to stdout or `output` -- SAM text, the header as read.  The file is parsed once; SEQ and the source qualities
     (QUAL, or OQ with use_oq) go to the device once and the count, the flags, the tally (gatk.bqsr._kmer_tally) and the apply
@@ -938,7 +952,7 @@ def recalibrate_bam(bam, use_oq=False, set_oq=False, kmers=None, gatkreport=None
     from .gatk import bqsr
     quantize = applybqsr._check_qmap(quantize)
     opts = dict(k=31, min_count=None, slots=None, prefilter=False, filter_bits=4, skip_unresolved=False, passes=1, partitions=1,
-                mixed_lengths=False, exclude_flags=0, kmer_min_qual=None)
+                mixed_lengths=False, exclude_flags=0, kmer_min_qual=None, kmers_from=None)
     unknown = sorted(set(kmers) - set(opts))
     if unknown:
         raise TypeError('recalibrate_bam: unknown k-mer option %s' % ', '.join(unknown))
@@ -947,7 +961,10 @@ def recalibrate_bam(bam, use_oq=False, set_oq=False, kmers=None, gatkreport=None
     records = {key: opts[key] for key in ('mixed_lengths', 'exclude_flags') if opts[key]}
     check_bam_kmers(bam, gatkreport, output, opts['k'], opts['min_count'], opts['prefilter'], opts['filter_bits'],
                     opts['partitions'], opts['passes'], **{key: records[key] for key in ('exclude_flags',) if key in records},
-                    **kmer._min_qual_kw(opts['kmer_min_qual']))
+                    **kmer._min_qual_kw(opts['kmer_min_qual']), **kmer._kmers_from_kw(opts['kmers_from']))
+    given_k = opts['k']
+    if opts['kmers_from'] is not None and given_k is None:
+        opts['k'] = 31                           # for the refusals of the records; the tally takes the set's
     passes, partitions = kmer.check_passes(opts['passes']), kmer._check_partitions(opts['partitions'])
     if not isinstance(bam, aln.AlignmentFile):
         with stage('parse'):
@@ -955,9 +972,10 @@ def recalibrate_bam(bam, use_oq=False, set_oq=False, kmers=None, gatkreport=None
     inputs = check_bam_records(bam, use_oq, opts['k'], opts['min_count'], opts['prefilter'], opts['filter_bits'], **records)
     info = {}
     with stage('k-mer tally', sync=True):
-        vectors, resident = bqsr._kmer_tally(bam, inputs, int(opts['k']), opts['min_count'], opts['slots'], opts['prefilter'],
+        vectors, resident = bqsr._kmer_tally(bam, inputs, given_k if given_k is None else int(given_k), opts['min_count'],
+                                             opts['slots'], opts['prefilter'],
                                              opts['filter_bits'], use_oq, 6, 42, info, bool(opts['skip_unresolved']), passes, partitions,
-                                             **kmer._min_qual_kw(opts['kmer_min_qual']))
+                                             **kmer._min_qual_kw(opts['kmer_min_qual']), **kmer._kmers_from_kw(opts['kmers_from']))
     with stage('solve'):
         # the bytes of the report decide: what `applybqsr` reads back is the text, not the vectors
         text = str(bqsr.vectors_to_report(*vectors, list(utils.get_rg_to_pu(bam).values())))
