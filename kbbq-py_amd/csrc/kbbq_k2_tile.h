@@ -20,7 +20,7 @@
 struct K2tParams {
     const uint8_t* seq; const uint8_t* qual; const u32* meta;
     int xcd_tiles;                 // workgroup b of a batch's T workgroups takes tile (b % 8) * (T / 8) + b / 8: every XCD (workgroup number mod 8) walks a
-                                   // contiguous eighth of the planes instead of every eighth tile -- 2.5-3 % on the headline's K2 (KBBQ_K2_XCD_TILES=0: tile b)
+                                   // contiguous eighth of the planes instead of every eighth tile -- 2.5-3 % on the headline's K2 (0: tile b; the host passes 1)
     long long nchunks;             // rows * cpr
     int cpr; u32 cpr_magic;        // ceil(2^32 / cpr): exact quotients for the small numerators used below
     int Qt; int S2; int maxlen;

@@ -184,6 +184,8 @@ __device__ __forceinline__ void reverse16(u32 v[4])                      // byte
 }
 
 typedef __attribute__((address_space(3))) u32 lds_u32;
+typedef u32 u32x4 __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(3))) u32x4 lds_u32x4;
 
 struct K1Chunk { u32 s[4], c[4], q[4]; u32 mk; u32 off; int k; int j; int nb; u32 fl, clip, trim; int jj; u32 g0lo, g0hi; };
 
@@ -192,7 +194,9 @@ struct K1Chunk { u32 s[4], c[4], q[4]; u32 mk; u32 off; int k; int j; int nb; u3
 //          copies cut the bank and same-address collisions), slot = 5*code(prev)+code(cur).
 //          16-bit halves: a copy can receive 64 lanes x 16*cpr bases per workgroup iteration in
 //          the worst case (every base the same bin), so this table alone is flushed every
-//          dn_flush_iters = 65535 / (1024 * cpr) iterations (6 for 2x150): ~1 % of the time.
+//          dn_flush_iters = 65535 / (1024 * cpr) iterations: 6 for 150-base reads one to a row (10 chunks), 3 for their
+//          mate-pair rows (19 chunks: ~32 flushes per workgroup on the headline, about 2 % of K1 before the joint-row forms
+//          got a flush of their own, profiles/r10_k1_block_pipeline.md), 4 for 13-chunk rows.
 //      pos[nrows][row_bytes/4] u32 (errs << 16 | total): [0,S) first-in-pair cycle = position;
 //          [S, 3S) second-in-pair, index x = position + 2*(S - len)  <->  column 2S-1-x
 //      rows are ordered by the INVERTED quality byte (row = 42 - q, one v_min clamps every
@@ -270,6 +274,34 @@ __device__ __forceinline__ void k1v3_body(const K1v3Params& p, u32* lds, const i
     u64* dn_total = dn_errs + (size_t)p.R * KQ * KND;
 
     auto flush_dn = [&]() {
+        if constexpr (JOINT) {
+            // One bin per thread -- thread t: row t / 16, context (t / 4) % 4 then t % 4 -- so no thread has a second bin whose LDS
+            // reads would queue behind the first one's global atomics: 16 copies read and zeroed, then at most two atomics that
+            // nothing waits for (the tables are read after the kernel).  At most 43 rows: 688 of the 1024 threads.
+            static_assert(K1V3_THREADS >= 16 * KQ, "one thread per bin of the context table");
+            const int t = (int)threadIdx.x, r = t >> 4;
+            if (r < p.nrows - 1) {                                     // the last row is trash
+                const int a = (t >> 2) & 3, b = t & 3;
+                lds_u32x4* at = reinterpret_cast<lds_u32x4*>((u32)reinterpret_cast<size_t>(lds) + 4u * (u32)(r * (int)(JROW >> 2) + CYC + (5 * a + b) * DN));
+                u32 vt = 0u, ve = 0u;
+#pragma unroll
+                for (int i = 0; i < DN / 4; ++i) {
+                    // four copies to a 16-byte read.  The 16 threads of a row start on different quarters: their bins are 16 or 80
+                    // words apart, so that the same quarter everywhere would put them all on the same 8 banks
+                    const int qu = (i + t) & 3;
+                    const u32x4 v = at[qu];
+                    at[qu] = u32x4{0u, 0u, 0u, 0u};
+                    vt += (v.x & 0xFFFFu) + (v.y & 0xFFFFu) + (v.z & 0xFFFFu) + (v.w & 0xFFFFu);
+                    ve += (v.x >> 16) + (v.y >> 16) + (v.z >> 16) + (v.w >> 16);
+                }
+                if (vt) {
+                    const size_t e = ((size_t)g * KQ + (KQ - 1 - r)) * KND + 4 * a + b;
+                    atomicAdd(&dn_total[e], (u64)vt);
+                    if (ve) atomicAdd(&dn_errs[e], (u64)ve);
+                }
+            }
+            return;
+        }
         for (int r = wave; r < p.nrows - 1; r += nwaves) {           // the last row is trash
             const int q = KQ - 1 - r;
             if (lane < 25) {
@@ -341,12 +373,24 @@ __device__ __forceinline__ void k1v3_body(const K1v3Params& p, u32* lds, const i
 
     // (every XCD's workgroups walking a contiguous eighth of the rows instead of every eighth iteration: measured, four alternating
     //  rounds on the headline layout, 3.40-3.44 against 3.36-3.43 ms -- nothing; K2's short-lived tiles do gain from it, kbbq_k2_tile.h)
+    // Joint-row forms: ONE software pipeline across uniform blocks.  While the last step of a uniform block is binned, the wave
+    // already has in flight the sidecar words of its next block (`m_next`) and that block's step-0 loads (`ub`: in a uniform
+    // block they are 16 l bytes from the block's base whatever the sidecar says); the ballot on `m_next` then decides whether
+    // the step is used (uniform again) or dropped (the general loop starts over from the sidecar words).  The loads stay in
+    // flight across a flush of the context table, which touches neither.
+    // INVARIANT: the next block is prefetched only if its 64 rows lie wholly inside [seg_lo, seg_hi) -- no address outside the
+    // slice's rows is ever formed; where there is no such block the loads re-read the CURRENT block's step 0 (a uniform block:
+    // 64 rows inside the slice) and are dropped, so that their number does not depend on a branch.
+    K1Chunk ua, ub;
+    u32 m_next = 0u;
+    bool ahead = false;                                 // wave-uniform: m_next / ub belong to this wave's block of the next iteration
     for (long long it = bx; it < iters; it += gx) {
         const long long blk = it * nwaves + wave;
         if (blk < nblocks) {
             const long long read0 = seg_lo + (blk << 6);
             const long long myread = read0 + lane;
             u32 m, afl = 0u, aclip = 0u, atrim = 0u, ag0lo = 0u, ag0hi = 0u;
+            const bool fed = JOINT && ahead;        // this block's sidecar words and step 0 are on their way
             if constexpr (ALN) {
                 afl = myread < seg_hi ? p.aflags[myread] : 0u;
                 aclip = myread < seg_hi ? p.aclip[myread] : 0u;
@@ -356,9 +400,12 @@ __device__ __forceinline__ void k1v3_body(const K1v3Params& p, u32* lds, const i
                     ag0lo = (u32)g0; ag0hi = (u32)((u64)g0 >> 32);
                 }
                 m = myread < seg_hi ? ((u32)p.S | ((afl >> 16) << 16) | ((afl & 2u) << 30)) : 0u;     // every read has the common length S
+            } else if (fed) {
+                m = m_next;
             } else {
                 m = myread < seg_hi ? p.meta[myread] : 0u;
             }
+            ahead = false;
             const bool match = myread < seg_hi && (int)((m >> 16) & 0x7FFFu) == g && (m & 0xFFFFu) != 0u;
             const u64 mask = __ballot(match);
             const int n = __popcll(mask);
@@ -600,14 +647,14 @@ __device__ __forceinline__ void k1v3_body(const K1v3Params& p, u32* lds, const i
                     const u32 dlo4 = (p.dlo < 128u ? p.dlo : 128u) * 0x01010101u;     // (a counted quality byte is below 128)
                     const u32 one = 1u;
                     u32 inc_a = 1u, inc_b = 1u;                                    // two increments in turn; their low halves stay 1
-                    auto fetch_u = [&](K1Chunk& ch, int s) {
-                        const u32 o = at + 1024u * (u32)s;
-                        const uint2 sv = *reinterpret_cast<const uint2*>(bseq + (o >> 1));
-                        const uint2 cv = *reinterpret_cast<const uint2*>(bcseq + (o >> 1));
-                        const uint4 qv = *reinterpret_cast<const uint4*>(bqual + o);
+                    auto fetch_at = [&](K1Chunk& ch, const uint8_t* fseq, const uint8_t* fcseq, const uint8_t* fqual, u32 o) {
+                        const uint2 sv = *reinterpret_cast<const uint2*>(fseq + (o >> 1));
+                        const uint2 cv = *reinterpret_cast<const uint2*>(fcseq + (o >> 1));
+                        const uint4 qv = *reinterpret_cast<const uint4*>(fqual + o);
                         ch.s[0] = sv.x; ch.s[1] = sv.y; ch.c[0] = cv.x; ch.c[1] = cv.y;
                         ch.q[0] = qv.x; ch.q[1] = qv.y; ch.q[2] = qv.z; ch.q[3] = qv.w;
                     };
+                    auto fetch_u = [&](K1Chunk& ch, int s) { fetch_at(ch, bseq, bcseq, bqual, at + 1024u * (u32)s); };
                     auto process_u = [&](const K1Chunk& ch) {
                         u32 code[4], code5[4], xw[4], hiq = 0u;
                         code[0] = nib_lo(ch.s[0]); code[1] = nib_hi(ch.s[0]); code[2] = nib_lo(ch.s[1]); code[3] = nib_hi(ch.s[1]);
@@ -673,16 +720,28 @@ __device__ __forceinline__ void k1v3_body(const K1v3Params& p, u32* lds, const i
                         j4 = wrap ? jn - 4 * KJ : jn;
                         k += DK + (wrap ? 1 : 0);
                     };
-                    K1Chunk ca, cb;
-                    fetch_u(ca, 0);
+                    // KJ is odd: the step fetched ahead sits in the buffer a block ends on, not the one it starts on (eight v_mov a block)
+                    if (fed) {
+                        ua.s[0] = ub.s[0]; ua.s[1] = ub.s[1]; ua.c[0] = ub.c[0]; ua.c[1] = ub.c[1];
+                        ua.q[0] = ub.q[0]; ua.q[1] = ub.q[1]; ua.q[2] = ub.q[2]; ua.q[3] = ub.q[3];
+                    } else {
+                        fetch_u(ua, 0);
+                    }
 #pragma unroll 1
                     for (int s = 0; s + 1 < KJ; s += 2) {
-                        fetch_u(cb, s + 1);
-                        process_u(ca);
-                        fetch_u(ca, s + 2);
-                        process_u(cb);
+                        fetch_u(ub, s + 1);
+                        process_u(ua);
+                        fetch_u(ua, s + 2);
+                        process_u(ub);
                     }
-                    process_u(ca);
+                    // the wave's block of the next iteration, if it is a whole block of this slice (see INVARIANT above)
+                    const long long nblk = blk + (long long)gx * nwaves;
+                    ahead = ((nblk + 1) << 6) <= seg_hi - seg_lo;
+                    const long long nread0 = ahead ? seg_lo + (nblk << 6) : read0;
+                    m_next = p.meta[nread0 + lane];
+                    fetch_at(ub, p.seq + (size_t)nread0 * (p.pitch >> 1), p.cseq + (size_t)nread0 * (p.pitch >> 1),
+                             p.qual + (size_t)nread0 * p.pitch, at);
+                    process_u(ua);
                 }
             }
             if (walk) {
@@ -703,6 +762,11 @@ __device__ __forceinline__ void k1v3_body(const K1v3Params& p, u32* lds, const i
                         advance(cb, dk2, dj2);
                     }
                 }
+                // The loop leaves the loads of a step nobody bins in flight.  The joint-row forms drain them here (vmcnt(0), gfx9
+                // encoding), once per general block: otherwise every later use of their registers -- the flush of the context
+                // table, the loop's own bookkeeping -- has to wait for ALL loads of the wave, those fetched ahead for the next
+                // uniform block and the flush's own atomics included.
+                if constexpr (JOINT) __builtin_amdgcn_s_waitcnt(0x0F70);
             }
         }
         ++since_flush; ++since_dn_flush;
@@ -818,7 +882,7 @@ struct K2v3Params {
     const long long* seg;      // rows grouped by read group: slice blockIdx.y stages only its group's LUT rows; NULL: all groups
     int rpb;                   // rows per wave block (<= 64): a wave's contiguous footprint is rpb * pitch bytes per plane
     int parts;                 // > 1: the workgroups walk the rows as `parts` sequential fronts (workgroup b: part b % parts) instead of one: the 2 read +
-                               // 1 written traversal of 50 M character rows 4.68-4.78 -> 4.44-4.48 ms with 4 ... 32 fronts (KBBQ_K2_PARTS, default 8; kbbq_k2_tile.h
+                               // 1 written traversal of 50 M character rows 4.68-4.78 -> 4.44-4.48 ms with 4 ... 32 fronts (the host passes 8; kbbq_k2_tile.h
                                // has the same for the short-lived kernel; K1's read-only traversal does not care)
     const long long* perm;     // rows grouped by read group: row i is stored as row perm[i] of `out` (straight back into input order); NULL: row i
     uint8_t* out; u64* status;

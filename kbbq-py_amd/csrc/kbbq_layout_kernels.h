@@ -191,7 +191,7 @@ struct LayOutParams {
     long long nrows;                                  // destination rows
     long long nsrc;                                   // source reads (pairs: 2 * nrows, or one less -- the last row's second half stays empty)
     int pitch, dpitch, S, pairs, nib;
-    int parts;                                        // sequential fronts of the traversal (k7_lay_out; KBBQ_K7_PARTS, default 8)
+    int parts;                                        // sequential fronts of the traversal (k7_lay_out; the host passes 8)
     u64* status;
 };
 
