@@ -1038,6 +1038,39 @@ int kbbq_kmer_count_filtered_rows_part_dev(kbbq_ctx* ctx, kbbq_kmer_table* table
 int kbbq_kmer_gate_rows_dev(kbbq_ctx* ctx, const uint8_t* d_seq, const uint8_t* d_qual, const uint32_t* d_meta, int64_t nrows,
                             int pitch, int flags, int k, int qual_byte_min, uint8_t* d_out, uint64_t* d_windows);
 
+/* ---- BGZF output: deflate on the GPU (--bgzf; csrc/kbbq_bgzf.h, kbbq/_bgzf.py) ------------------------------------------------
+ * THE FORMAT.  n bytes of text are cut at multiples of block_bytes (1..KBBQ_BGZF_BLOCK_MAX; the last block is the remainder) and
+ * every piece becomes one BGZF block, a complete gzip member: 1f 8b 08 04 00 00 00 00 00 ff 06 00 'B' 'C' 02 00, BSIZE - 1 as a
+ * little-endian u16 (18 bytes), a raw deflate payload, the CRC32 of the piece, its length (ISIZE).  The payload is ONE deflate
+ * block with BFINAL set: dynamic Huffman (BTYPE 10) over LZ77 matches of length 4..258 at distance 1..32768 that never reach
+ * before the piece's first byte nor past its last -- every block inflates on its own --, code lengths of at most 15 bits, run-
+ * length coded (16, 17, 18) under a code-length code of at most 7 bits; or, when that is not smaller, stored (BTYPE 00).  A
+ * block is therefore never longer than its piece + 31 bytes.  The bytes are a function of (text, block_bytes) alone: not of
+ * thread order, launch geometry, slab size or which of the two calls below made them.  Blocks, and files of blocks, joined end
+ * to end are a valid file; kbbq_bgzf_eof writes the 28-byte empty block that ends a BGZF file.
+ * kbbq_bgzf_bound(n, block_bytes) = n + 31 * ceil(n / block_bytes): what the packed blocks of n bytes can need (0 for n <= 0 or
+ * a block_bytes out of range).
+ * kbbq_bgzf_deflate_dev (synchronous): block b is written at d_blocks + b * KBBQ_BGZF_SLOT and its length to d_sizes[b]
+ * (d_blocks: ceil(n / block_bytes) * KBBQ_BGZF_SLOT bytes; both 4-byte aligned); then the blocks are copied end to end into
+ * d_packed (kbbq_bgzf_bound bytes) and *packed_bytes receives their total length.  d_text is not written; it is read fastest
+ * when it and block_bytes are multiples of 16.
+ * kbbq_bgzf_deflate: the same from and to host buffers, slab by slab through page-locked staging (KBBQ_STAGE_MB) like
+ * kbbq_kmer_count; only text goes up and only packed bytes come back.  out_cap must be at least kbbq_bgzf_bound.
+ * n == 0 writes nothing and launches nothing (*packed_bytes = *out_bytes = 0).  KBBQ_E_ARG before anything is launched: a
+ * block_bytes outside 1..KBBQ_BGZF_BLOCK_MAX (checked first, on the number alone), a NULL ctx, buffer or result pointer, n < 0,
+ * buffers that are not aligned as said, an out_cap below the bound.  The launches are not timed by kbbq_ctx_timing.
+ * kbbq_bgzf_deflate_dev touches only scratch of its own in the context and enqueues on its stream: like the copies, it may run
+ * on a second thread beside the one that launches the other kernels, one such call at a time (kbbq/_bgzf.py does).           */
+#define KBBQ_BGZF_BLOCK_MAX 65280
+#define KBBQ_BGZF_SLOT      65536
+#define KBBQ_BGZF_EOF_BYTES 28
+size_t kbbq_bgzf_bound(int64_t n, int block_bytes);
+int kbbq_bgzf_deflate_dev(kbbq_ctx* ctx, const uint8_t* d_text, int64_t n, int block_bytes, uint8_t* d_blocks, uint32_t* d_sizes,
+                          uint8_t* d_packed, size_t* packed_bytes);
+int kbbq_bgzf_deflate(kbbq_ctx* ctx, const uint8_t* text, int64_t n, int block_bytes, uint8_t* out, size_t out_cap,
+                      size_t* out_bytes);
+int kbbq_bgzf_eof(uint8_t* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,6 +13,7 @@
 #include "kbbq_apply_aligned.h"
 #include "kbbq_kmer.h"
 #include "kbbq_kmer_set.h"
+#include "kbbq_bgzf.h"
 #include "../../include/kbbq_hip.h"
 #include "host_threads.h"
 
@@ -69,6 +70,9 @@ struct kbbq_ctx {
     DevScratch ops4;                  // K4: one 32-byte record of the first CIGAR operations per read
     DevScratch tally;                 // kbbq_tally_aligned_dev: [count | flags words of the reads | rows K4 still has to look at]
     DevScratch rowlut;                // K2 on one-read-per-row planes: the LUT narrowed to the rows' pitch
+    DevScratch bgzf_tok;              // kbbq_bgzf_deflate*: the tokens of the blocks in flight (a workgroup's worth each)
+    DevScratch bgzf_off;              // ... the blocks' offsets in the packed output, and its length
+    DevScratch bgzf_blocks;           // kbbq_bgzf_deflate (host buffers): a slab's blocks before they are packed
     // host-buffer entry points (stage_run): two page-locked staging slabs and their device twins, a copy stream and
     // the events that order host copy -> upload -> kernel -> download slab by slab (grown on demand, kept for the next call)
     void* stage_host[2] = {nullptr, nullptr}; void* stage_dev[2] = {nullptr, nullptr}; size_t stage_bytes = 0;
@@ -126,7 +130,7 @@ static const void* k1_kernel(K1Form form, bool split, int dn, int nib, int kj)
 }
 
 // the others: the round-1 kernels (tables beyond the LDS, KBBQ_APPLY_CHECKED) and K2
-enum LdsKernel { LK_K1_PLAIN, LK_K1_PLAIN_SPLIT, LK_K1_TILED, LK_K1_TILED_SPLIT, LK_K2V3, LK_K2V3_NIB, LK_K2T, LK_K2T_NIB, LK_K2T_BANDS, LK_K2T_PAIR19, LK_K2T_PAIR13, LK_K2_LDS16, LK_K2_LDS8, LK_COUNT };
+enum LdsKernel { LK_K1_PLAIN, LK_K1_PLAIN_SPLIT, LK_K1_TILED, LK_K1_TILED_SPLIT, LK_K2V3, LK_K2V3_NIB, LK_K2T, LK_K2T_NIB, LK_K2T_BANDS, LK_K2T_PAIR19, LK_K2T_PAIR13, LK_K2_LDS16, LK_K2_LDS8, LK_BGZF, LK_COUNT };
 static const void* const LDS_KERNELS[LK_COUNT] = {
     (const void*)k1_accumulate<false>, (const void*)k1_accumulate<true>,
     (const void*)k1_accumulate_tiled<false>, (const void*)k1_accumulate_tiled<true>,
@@ -134,6 +138,7 @@ static const void* const LDS_KERNELS[LK_COUNT] = {
     (const void*)k2t_apply<false>, (const void*)k2t_apply<true>, (const void*)k2t_bands,
     (const void*)k2t_apply_pair<19>, (const void*)k2t_apply_pair<13>,
     (const void*)k2_apply<int16_t, true, true>, (const void*)k2_apply<int8_t, true, false>,
+    (const void*)bz_deflate,
 };
 
 extern "C" {
@@ -215,7 +220,7 @@ int kbbq_ctx_destroy(kbbq_ctx* c)
         for (auto& pr : c->ev[w]) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
     if (c->d_status) (void)hipFree(c->d_status);
     if (c->d_stats) (void)hipFree(c->d_stats);
-    for (DevScratch* s : {&c->wgplan, &c->ops4, &c->tally, &c->rowlut})
+    for (DevScratch* s : {&c->wgplan, &c->ops4, &c->tally, &c->rowlut, &c->bgzf_tok, &c->bgzf_off, &c->bgzf_blocks})
         if (s->p) (void)hipFree(s->p);
     for (int b = 0; b < 2; ++b) {
         if (c->stage_host[b]) (void)hipHostFree(c->stage_host[b]);
@@ -3035,6 +3040,136 @@ int kbbq_kmer_count_filtered_part(kbbq_ctx* c, kbbq_kmer_table* t, const kbbq_km
 {
     return kmer_count_filtered_host(c, "kbbq_kmer_count_filtered_part", "kbbq_kmer_count_filtered_part_dev", t, f, seq, meta, n, pitch,
                                     parts, part);
+}
+
+} // extern "C"
+
+// ---- BGZF output (csrc/kbbq_bgzf.h) -------------------------------------------------------------------------------------------
+static int64_t bgzf_blocks_of(int64_t n, int block_bytes) { return (n + block_bytes - 1) / block_bytes; }
+
+static int bgzf_block_bytes_ok(const char* who, int block_bytes)
+{
+    if (block_bytes < 1 || block_bytes > (int)BZ_MAX_TEXT)
+        return fail(KBBQ_E_ARG, "%s: block_bytes %d is not in 1..%u", who, block_bytes, BZ_MAX_TEXT);
+    return KBBQ_OK;
+}
+
+// the launches of one piece of text (n > 0, arguments checked): blocks, sizes, offsets, packed bytes; the packed length is left
+// in c->bgzf_off[nblocks]
+static int bgzf_launch(kbbq_ctx* c, const uint8_t* d_text, int64_t n, int block_bytes, uint8_t* d_blocks, uint32_t* d_sizes,
+                       uint8_t* d_packed)
+{
+    const int64_t nb = bgzf_blocks_of(n, block_bytes);
+    const unsigned grid = (unsigned)std::min<int64_t>(nb, std::max(c->cus, 1));
+    int rc = grow_scratch(c, c->bgzf_tok, (size_t)grid * BZ_MAX_TEXT * sizeof(u32));
+    if (!rc) rc = grow_scratch(c, c->bgzf_off, (size_t)(nb + 1) * sizeof(u64));
+    if (rc) return rc;
+    BgzfParams q{d_text, n, (u32)block_bytes, (u32)nb, d_blocks, d_sizes, (u32*)c->bgzf_tok.p};
+    void* args[] = {&q};
+    (void)hipLaunchKernel(LDS_KERNELS[LK_BGZF], dim3(grid), dim3(BZ_THREADS), args, BZ_LDS_BYTES, c->stream);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(bz_scan_sizes, dim3(1), dim3(BZ_THREADS), 0, c->stream, (const u32*)d_sizes, (u32)nb, (u64*)c->bgzf_off.p);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(bz_pack, dim3((unsigned)nb), dim3(256), 0, c->stream, (const uint8_t*)d_blocks, (const u32*)d_sizes,
+                       (const u64*)c->bgzf_off.p, d_packed);
+    HIPCHK(hipGetLastError());
+    return KBBQ_OK;
+}
+
+extern "C" {
+
+size_t kbbq_bgzf_bound(int64_t n, int block_bytes)
+{
+    if (n <= 0 || block_bytes < 1 || block_bytes > (int)BZ_MAX_TEXT) return 0;
+    return (size_t)n + 31 * (size_t)bgzf_blocks_of(n, block_bytes);
+}
+
+int kbbq_bgzf_eof(uint8_t* out)
+{
+    static const uint8_t eof[28] = {0x1f, 0x8b, 0x08, 0x04, 0, 0, 0, 0, 0, 0xff, 0x06, 0, 0x42, 0x43, 0x02, 0, 0x1b, 0, 0x03, 0,
+                                    0, 0, 0, 0, 0, 0, 0, 0};
+    if (!out) return fail(KBBQ_E_ARG, "kbbq_bgzf_eof: out is NULL");
+    memcpy(out, eof, sizeof eof);
+    return KBBQ_OK;
+}
+
+int kbbq_bgzf_deflate_dev(kbbq_ctx* c, const uint8_t* d_text, int64_t n, int block_bytes, uint8_t* d_blocks, uint32_t* d_sizes,
+                          uint8_t* d_packed, size_t* packed_bytes)
+{
+    int rc = bgzf_block_bytes_ok("kbbq_bgzf_deflate_dev", block_bytes);
+    if (rc) return rc;
+    if (!c || !packed_bytes) return fail(KBBQ_E_ARG, "kbbq_bgzf_deflate_dev: NULL ctx or packed_bytes");
+    *packed_bytes = 0;
+    if (n < 0) return fail(KBBQ_E_ARG, "kbbq_bgzf_deflate_dev: n < 0");
+    if (n == 0) return KBBQ_OK;
+    if (!d_text || !d_blocks || !d_sizes || !d_packed) return fail(KBBQ_E_ARG, "kbbq_bgzf_deflate_dev: NULL buffer");
+    if (((uintptr_t)d_blocks & 3) || ((uintptr_t)d_sizes & 3)) return fail(KBBQ_E_ARG, "kbbq_bgzf_deflate_dev: d_blocks and d_sizes are 4-byte aligned");
+    if (bgzf_blocks_of(n, block_bytes) > (int64_t)INT_MAX) return fail(KBBQ_E_ARG, "kbbq_bgzf_deflate_dev: more than 2^31 - 1 blocks");
+    HIPCHK(hipSetDevice(c->device));
+    rc = bgzf_launch(c, d_text, n, block_bytes, d_blocks, d_sizes, d_packed);
+    if (rc) return rc;
+    u64 total = 0;
+    HIPCHK(hipMemcpyAsync(&total, (const u64*)c->bgzf_off.p + bgzf_blocks_of(n, block_bytes), sizeof total, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    *packed_bytes = (size_t)total;
+    return KBBQ_OK;
+}
+
+int kbbq_bgzf_deflate(kbbq_ctx* c, const uint8_t* text, int64_t n, int block_bytes, uint8_t* out, size_t out_cap, size_t* out_bytes)
+{
+    int rc = bgzf_block_bytes_ok("kbbq_bgzf_deflate", block_bytes);
+    if (rc) return rc;
+    if (!c || !out_bytes) return fail(KBBQ_E_ARG, "kbbq_bgzf_deflate: NULL ctx or out_bytes");
+    *out_bytes = 0;
+    if (n < 0) return fail(KBBQ_E_ARG, "kbbq_bgzf_deflate: n < 0");
+    if (n == 0) return KBBQ_OK;
+    if (!text || !out) return fail(KBBQ_E_ARG, "kbbq_bgzf_deflate: NULL buffer");
+    if (out_cap < kbbq_bgzf_bound(n, block_bytes))
+        return fail(KBBQ_E_ARG, "kbbq_bgzf_deflate: out holds %zu bytes, kbbq_bgzf_bound is %zu", out_cap, kbbq_bgzf_bound(n, block_bytes));
+    HIPCHK(hipSetDevice(c->device));
+    // a slab: `per` blocks.  Host: text | packed | packed length; device: text | packed | sizes; the blocks before packing in
+    // scratch of the context's.  While the kernels of slab k run, the host copies slab k + 1 in and slab k - 1 out.
+    const char* e = getenv("KBBQ_STAGE_MB");
+    const size_t budget = (size_t)(e && atoi(e) > 0 ? atoi(e) : 96) << 20;
+    const int64_t nb = bgzf_blocks_of(n, block_bytes);
+    const int64_t per = std::max<int64_t>(1, std::min<int64_t>(nb, (int64_t)(budget / (3 * (size_t)BZ_SLOT))));
+    const size_t text_cap = align16((size_t)per * block_bytes), packed_cap = align16((size_t)per * (block_bytes + 31));
+    const size_t bytes = text_cap + packed_cap + align16((size_t)per * 4 + 8);
+    rc = stage_prepare(c, bytes);
+    if (!rc) rc = grow_scratch(c, c->bgzf_blocks, (size_t)per * BZ_SLOT);
+    if (rc) return rc;
+    size_t written = 0;
+    auto finish = [&](int buf) -> int {                    // slab in `buf`: its packed bytes to `out`
+        HIPCHK(hipEventSynchronize(c->stage_up[buf]));
+        const u64 total = *(const u64*)((const char*)c->stage_host[buf] + text_cap + packed_cap);
+        if (written + total > out_cap) return fail(KBBQ_E_HIP, "kbbq_bgzf_deflate: more bytes than kbbq_bgzf_bound");
+        HIPCHK(hipMemcpyAsync((char*)c->stage_host[buf] + text_cap, (const char*)c->stage_dev[buf] + text_cap, (size_t)total,
+                              hipMemcpyDeviceToHost, c->stage_down_stream));
+        HIPCHK(hipStreamSynchronize(c->stage_down_stream));
+        threaded_copy(out + written, (const char*)c->stage_host[buf] + text_cap, (size_t)total);
+        written += (size_t)total;
+        return KBBQ_OK;
+    };
+    int64_t k = 0;
+    for (int64_t lo = 0; lo < nb; lo += per, ++k) {
+        const int buf = (int)(k & 1);
+        const int64_t first = lo * block_bytes, m = std::min<int64_t>(n - first, per * block_bytes), mb = bgzf_blocks_of(m, block_bytes);
+        threaded_copy(c->stage_host[buf], text + first, (size_t)m);
+        uint8_t* d = (uint8_t*)c->stage_dev[buf];
+        rc = hipMemcpyAsync(d, c->stage_host[buf], (size_t)m, hipMemcpyHostToDevice, c->stream) == hipSuccess
+                 ? KBBQ_OK : fail(KBBQ_E_HIP, "kbbq_bgzf_deflate: upload failed");
+        if (!rc) rc = bgzf_launch(c, d, m, block_bytes, (uint8_t*)c->bgzf_blocks.p, (uint32_t*)(d + text_cap + packed_cap), d + text_cap);
+        if (!rc && hipMemcpyAsync((char*)c->stage_host[buf] + text_cap + packed_cap, (const u64*)c->bgzf_off.p + mb, sizeof(u64),
+                                  hipMemcpyDeviceToHost, c->stream) != hipSuccess)
+            rc = fail(KBBQ_E_HIP, "kbbq_bgzf_deflate: download failed");
+        if (!rc && hipEventRecord(c->stage_up[buf], c->stream) != hipSuccess) rc = fail(KBBQ_E_HIP, "kbbq_bgzf_deflate: hipEventRecord failed");
+        if (!rc && k > 0) rc = finish(buf ^ 1);
+        if (rc) return stage_drain(c, rc);
+    }
+    rc = finish((int)((k - 1) & 1));
+    if (rc) return stage_drain(c, rc);
+    *out_bytes = written;
+    return KBBQ_OK;
 }
 
 } // extern "C"

@@ -30,6 +30,7 @@ KMER_FIX_N = 1                        # the `opts` word of the kbbq_kmer_correct
 KMER_MAX_PASSES = 8                   # the `passes` of the kbbq_kmer_*_passes* calls: 1..8
 KMER_FLAG_UNRESOLVED = 2              # ... and of kbbq_kmer_flag_ex_dev: unresolved bases become 2 in the flag plane
 CONFUSION_MAX_BASES = (1 << 32) - 1   # KBBQ_CONFUSION_MAX_BASES: nreads * pitch of one kbbq_flag_confusion_dev call
+BGZF_BLOCK_MAX, BGZF_SLOT, BGZF_EOF_BYTES = 65280, 65536, 28   # KBBQ_BGZF_*: text of a block, a block's slot before packing, the EOF block
 
 NQ = 43
 NDINUC = 16
@@ -223,6 +224,10 @@ PROTOTYPES = {
     'kbbq_kmer_correct_rows_passes_dev': (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _vp, _vp, _i, _i]),
     'kbbq_kmer_correct_rows_skip_dev': (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp]),
     'kbbq_kmer_gate_rows_dev': (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _vp, _vp]),
+    'kbbq_bgzf_bound': (_sz, [_i64, _i]),
+    'kbbq_bgzf_deflate_dev': (_i, [_vp, _vp, _i64, _i, _vp, _vp, _vp, _c.POINTER(_sz)]),
+    'kbbq_bgzf_deflate': (_i, [_vp, _vp, _i64, _i, _vp, _sz, _c.POINTER(_sz)]),
+    'kbbq_bgzf_eof': (_i, [_vp]),
 }
 
 

@@ -9,6 +9,7 @@ an aln.AlignmentFile through kbbq_apply_aligned: csrc/kbbq_apply_aligned.h) and 
 """
 import numpy as np
 
+from .. import _bgzf
 from .. import compare_reads as utils
 
 
@@ -447,6 +448,7 @@ def _report_model(bam, report):
     return (meanq,) + tuple(get_delta_qs(meanq, *vectors)) + (rg_to_int,)
 
 
+@_bgzf.option
 def apply_report(bam, report_path, use_oq=False, set_oq=False, output=None, quantize=None):
     """`kbbq applybqsr`: report -> model (table_to_vectors, get_delta_qs on the device) -> kbbq_apply_aligned -> SAM text, to
     `output` or stdout.  Under torch.distributed.run every rank takes parallel.shard_range of the alignments and writes
@@ -468,10 +470,14 @@ def apply_report(bam, report_path, use_oq=False, set_oq=False, output=None, quan
     kw = dict(use_oq=use_oq, set_oq=set_oq, rows=(lo, hi), header=rank == 0)
     if quantize is not None:                                 # without it the call is the one it was
         kw['quantize'] = quantize
+    if output is None and _bgzf.enabled():
+        with _bgzf.stdout_sink() as sink:
+            write_alignments(bam, *model, rg_to_int, sink, **kw)
+        return
     if output is None:
         sys.stdout.flush()
         write_alignments(bam, *model, rg_to_int, sys.stdout.buffer, **kw)
         sys.stdout.flush()
         return
-    with open(output if world == 1 else '%s.rank%04d' % (output, rank), 'wb') as sink:
+    with _bgzf.open_sink(output if world == 1 else '%s.rank%04d' % (output, rank)) as sink:
         write_alignments(bam, *model, rg_to_int, sink, **kw)

@@ -56,6 +56,7 @@ import sys
 
 import numpy as np
 
+from . import _bgzf
 from . import _native as N
 
 HIST = 257
@@ -1173,6 +1174,7 @@ def _correct_reads_gated(seq_plane, qual_plane, meta, k, min_count, slots, prefi
             table.close()
 
 
+@_bgzf.option
 def correct_fastq(path, out, k=31, min_count=None, slots=None, local_slots=None, prefilter=False, filter_bits=4, fix_n=False,
                   passes=1, partitions=1, kmer_min_qual=None, kmers_from=None):
     """Correct every read of a FASTQ file (plain or .gz) and write '@' + name, the corrected sequence, '+' and the qualities
@@ -1205,7 +1207,9 @@ def correct_fastq(path, out, k=31, min_count=None, slots=None, local_slots=None,
                                 fix_n=fix_n, **_passes_kw(passes), **_partitions_kw(partitions),
                                 **_min_qual_kw(kmer_min_qual, qual_plane=qual), **_kmers_from_kw(kmers_from))
     text = fastx.format_fastq(names, fixed, qual, meta & 0xFFFF)
-    if isinstance(out, str):
+    if _bgzf.enabled():
+        _bgzf.write_text(out, text)
+    elif isinstance(out, str):
         with open(out, 'w', encoding='latin-1', newline='') as fh:
             fh.write(text)
     else:
@@ -1215,6 +1219,7 @@ def correct_fastq(path, out, k=31, min_count=None, slots=None, local_slots=None,
     return info
 
 
+@_bgzf.option
 def main_correct(path, output=None, k=31, min_count=None, slots=None, local_slots=None, prefilter=False, filter_bits=4, fix_n=False,
                  passes=1, partitions=1, kmer_min_qual=None, kmers_from=None):
     """`kbbq correct`: the corrected FASTQ to `output` or stdout; the threshold and the changed bases to stderr (once, by rank
@@ -1411,7 +1416,11 @@ def _correct_shard_from(kmers_from, out, names, seq, qual, meta, k, min_count, s
     _agree(exc)
     total = int(parallel.sum_over_ranks(np.array([changed.astype(np.int64).sum()], dtype=np.int64))[0])
     text = fastx.format_fastq(names, fixed, qual, meta & 0xFFFF)
-    if isinstance(out, str):
+    if _bgzf.enabled() and isinstance(out, str):
+        _bgzf.write_text(out if world == 1 else '%s.rank%04d' % (out, rank), text)
+    elif _bgzf.enabled():
+        parallel.in_rank_order(lambda: _bgzf.write_text(out, text))
+    elif isinstance(out, str):
         with open(out if world == 1 else '%s.rank%04d' % (out, rank), 'w', encoding='latin-1', newline='') as fh:
             fh.write(text)
     else:
@@ -1454,6 +1463,7 @@ def _read_shard(path, rank, world):
     return names, seq, qual, meta
 
 
+@_bgzf.option
 def correct_fastq_ranks(path, out, k=31, min_count=None, slots=None, local_slots=None, fix_n=False, passes=1, kmer_min_qual=None,
                         kmers_from=None):
     """correct_fastq on every rank of the process group: each rank reads, counts and corrects its own records and writes them
@@ -1516,7 +1526,11 @@ def correct_fastq_ranks(path, out, k=31, min_count=None, slots=None, local_slots
     _agree(exc)
     total = int(parallel.sum_over_ranks(np.array([changed.astype(np.int64).sum()], dtype=np.int64))[0])
     text = fastx.format_fastq(names, fixed, qual, meta & 0xFFFF)
-    if isinstance(out, str):
+    if _bgzf.enabled() and isinstance(out, str):
+        _bgzf.write_text(out if world == 1 else '%s.rank%04d' % (out, rank), text)
+    elif _bgzf.enabled():
+        parallel.in_rank_order(lambda: _bgzf.write_text(out, text))
+    elif isinstance(out, str):
         with open(out if world == 1 else '%s.rank%04d' % (out, rank), 'w', encoding='latin-1', newline='') as fh:
             fh.write(text)
     else:

@@ -139,6 +139,16 @@ def _kmers_from(parser, args, needs=None):
 _ENDS_WITH_THE_COMMAND = False               # set by `python -m kbbq.main`: the process ends (main._leave) when the command has run
 
 
+_BGZF_HELP = ('Write the output (-o, or stdout) as a BGZF file: gzip made of independent 64 KiB blocks, deflated on the GPU. '
+              'Under a launcher every FILE.rankNNNN is a complete BGZF file and the files joined in rank order inflate to the '
+              'one-process bytes.  Without the option the output is plain text whatever its name.')
+
+
+def _bgzf_kw(args):
+    """{'bgzf': True} with --bgzf, else {}: without the option every call is the one it was."""
+    return {'bgzf': True} if getattr(args, 'bgzf', False) else {}
+
+
 def _recalibrate_bam_kmers(args):
     """`recalibrate -b ALN --kmers`: `bqsr --kmers` and `applybqsr` in one run (kbbq/recalibrate.py recalibrate_bam)."""
     import os
@@ -177,7 +187,7 @@ def _recalibrate_bam_kmers(args):
             from . import _device
             _device.use_native_memory()          # as `bqsr --kmers` on one GPU: no torch import
         info = _recal.recalibrate_bam(bam, use_oq=args.use_oq, set_oq=args.set_oq, kmers=kmers, gatkreport=args.gatkreport,
-                                      output=args.output, **args.quantize)
+                                      output=args.output, **args.quantize, **_bgzf_kw(args))
     sys.stderr.write('kbbq recalibrate: k=%d min_count=%d reads=%d%s flagged_bases=%d%s%s%s%s%s%s\n'
                      % (info['k'], info['min_count'], info['reads'],
                         ' excluded_reads=%d' % info['excluded_reads'] if args.exclude_flags else '', info['flagged_bases'],
@@ -229,7 +239,7 @@ def recalibrate(args):
         from ._trace import stage
         with stage('[recalibrate_corrected, wall]'):
             info = _recal.recalibrate_corrected(args.correct, infer_rg=args.infer_rg, gatkreport=args.gatkreport, output=args.output,
-                                                **kopts, **args.quantize)
+                                                **kopts, **args.quantize, **_bgzf_kw(args))
         from .kmer import kmers_from_field, min_qual_field, partitions_field
         sys.stderr.write('kbbq recalibrate: k=%d min_count=%d reads=%d changed_bases=%d%s%s%s%s%s%s%s\n'
                          % (info['k'], info['min_count'], info['reads'], info['changed_bases'],
@@ -241,7 +251,8 @@ def recalibrate(args):
                             kmers_from_field(info)))
         return
     _recal.recalibrate(bam=args.bam, fastq=args.fastq, infer_rg=args.infer_rg,
-                       use_oq=args.use_oq, set_oq=args.set_oq, gatkreport=args.gatkreport, output=args.output, **args.quantize)
+                       use_oq=args.use_oq, set_oq=args.set_oq, gatkreport=args.gatkreport, output=args.output, **args.quantize,
+                       **_bgzf_kw(args))
 
 
 def benchmark(args):
@@ -268,7 +279,8 @@ def applybqsr(args):
     from . import parallel
     from .gatk import applybqsr as _apply
     parallel.init_from_env()          # one process per GPU under torch.distributed.run; no-op otherwise
-    _apply.apply_report(args.bam, args.gatkreport, use_oq=args.use_oq, set_oq=args.set_oq, output=args.output, **args.quantize)
+    _apply.apply_report(args.bam, args.gatkreport, use_oq=args.use_oq, set_oq=args.set_oq, output=args.output, **args.quantize,
+                        **_bgzf_kw(args))
 
 
 def bqsr(args):
@@ -335,7 +347,7 @@ def correct(args):
         more['kmers_from'] = args.kmers_from
     kmer.main_correct(args.fastq, output=args.output, k=args.kmer if args.kmers_from is not None or args.kmer is not None else 31,
                       min_count=args.min_count, slots=args.slots, local_slots=args.local_slots, prefilter=args.prefilter,
-                      filter_bits=4 if args.filter_bits is None else args.filter_bits, fix_n=args.fix_n, **more)
+                      filter_bits=4 if args.filter_bits is None else args.filter_bits, fix_n=args.fix_n, **more, **_bgzf_kw(args))
 
 
 def count(args):
@@ -409,6 +421,7 @@ def main(argv=None):
     rp.add_argument('-o', '--output', default=None,
                     help='Write the recalibrated FASTQ to this file instead of stdout (not in the reference); under '
                          'torch.distributed.run every rank writes FILE.rankNNNN, to be concatenated in rank order.')
+    rp.add_argument('--bgzf', action='store_true', help=_BGZF_HELP)
     rp.add_argument('--infer-rg', action='store_true',
                     help='Infer the read group from the FASTQ read name (name_RG:Z:id).')
     rp.add_argument('--static-quantized-quals', type=_quant_levels, action='append', default=None, metavar='Q[,Q...]',
@@ -457,6 +470,7 @@ def main(argv=None):
     ap.add_argument('-o', '--output', default=None,
                     help='Write the recalibrated SAM to this file instead of stdout (SAM text only; a .bam name is refused); '
                          'under torch.distributed.run every rank writes FILE.rankNNNN, to be concatenated in rank order.')
+    ap.add_argument('--bgzf', action='store_true', help=_BGZF_HELP)
     ap.add_argument('-u', '--use-oq', action='store_true', help='Recalibrate the OQ tag\'s qualities instead of QUAL.')
     ap.add_argument('-s', '--set-oq', action='store_true', help="Keep the qualities as read in an 'OQ' tag where there is none.")
     ap.add_argument('--static-quantized-quals', type=_quant_levels, action='append', default=None, metavar='Q[,Q...]',
@@ -531,6 +545,7 @@ def main(argv=None):
     cp.add_argument('-o', '--output', default=None,
                     help='Write the corrected FASTQ to this file instead of stdout; under torch.distributed.run every rank '
                          'writes FILE.rankNNNN, to be concatenated in rank order.')
+    cp.add_argument('--bgzf', action='store_true', help=_BGZF_HELP)
     cp.add_argument('--kmers-from', default=None, metavar='SET',
                     help=_KMERS_FROM_HELP % ('one GPU or several', '; under torch.distributed.run every rank loads the set'))
     cp.set_defaults(command=correct)

@@ -25,6 +25,7 @@ import numpy as np
 
 from . import compare_reads as utils        # noqa: F401  (module attribute of the reference: recalibrate.utils)
 from . import fastx
+from . import _bgzf
 from . import _device as dev
 from . import _solve
 from . import _stream
@@ -247,6 +248,7 @@ def _device_qmap(quantize):
     return None if quantize is None else dev.qmap_to_device(quantize)
 
 
+@_bgzf.option
 def recalibrate_fastq(fastq, infer_rg=False, gatkreport=None, output=None, quantize=None):
     """Recalibrate FASTQ file fastq[0] using its error-corrected version fastq[1];
     the recalibrated FASTQ is printed to stdout.  K1 -> K3 -> K2, tables and LUT stay on
@@ -372,10 +374,15 @@ def _apply_and_emit(text, single, lut, shape, output, world, rank, qmap=None):
 
     # recalibrate.py:153-156: '@' + name, sequence, '+', qualities
     from . import _egress
-    if output is None:
+    if output is None and _bgzf.enabled():
+        def compressed():
+            with _bgzf.stdout_sink() as sink:
+                _egress.emit_records(text, single['first'], single['bands'], outs, sink=sink)
+        parallel.in_rank_order(compressed)
+    elif output is None:
         parallel.in_rank_order(lambda: _egress.emit_records(text, single['first'], single['bands'], outs))
     else:
-        with open(output if world == 1 else '%s.rank%04d' % (output, rank), 'wb') as sink:
+        with _bgzf.open_sink(output if world == 1 else '%s.rank%04d' % (output, rank)) as sink:
             _egress.emit_records(text, single['first'], single['bands'], outs, sink=sink)
 
 
@@ -405,6 +412,7 @@ def check_corrected(path, gatkreport=None, k=31, min_count=None, prefilter=False
                          'give -f with the report, or the name of a report to write' % gatkreport)
 
 
+@_bgzf.option
 def recalibrate_corrected(path, infer_rg=False, gatkreport=None, output=None, k=31, min_count=None, slots=None, prefilter=False,
                           filter_bits=4, fix_n=False, passes=1, skip_unresolved=False, partitions=1, quantize=None,
                           kmer_min_qual=None, kmers_from=None):
@@ -807,10 +815,13 @@ class _Sequential:
                     raise
         try:
             widest = fastx.pitch_for(max(self.longest, 1)) * 2 + 16
-            if output is None:
+            if output is None and _bgzf.enabled():
+                with _bgzf.stdout_sink() as sink:
+                    _egress.emit_produced(None, 0, produced(), widest, sink=sink)
+            elif output is None:
                 _egress.emit_produced(None, 0, produced(), widest)
             else:
-                with open(output, 'wb') as sink:
+                with _bgzf.open_sink(output) as sink:
                     _egress.emit_produced(None, 0, produced(), widest, sink=sink)
             LAST_RUN.clear()
             LAST_RUN['bands'] = []
@@ -860,10 +871,15 @@ def _emit_streamed(text, single, lut, shape, output, world, rank, qmap=None):
         produced = _stream.produce_range(st['A'], st['infer_rg'], st['lo'], st['hi'], lut, shape, st['budget'], device=device,
                                          qmap=qmap)
         widest = fastx.pitch_for(single['S']) * 2 + 16
-        if output is None:
+        if output is None and _bgzf.enabled():
+            def compressed():
+                with _bgzf.stdout_sink() as sink:
+                    _egress.emit_produced(text, single['first'], produced, widest, sink=sink)
+            parallel.in_rank_order(compressed)
+        elif output is None:
             parallel.in_rank_order(lambda: _egress.emit_produced(text, single['first'], produced, widest))
         else:
-            with open(output if world == 1 else '%s.rank%04d' % (output, rank), 'wb') as sink:
+            with _bgzf.open_sink(output if world == 1 else '%s.rank%04d' % (output, rank)) as sink:
                 _egress.emit_produced(text, single['first'], produced, widest, sink=sink)
         LAST_RUN.clear()
         LAST_RUN['bands'] = []
@@ -930,6 +946,7 @@ def check_bam_records(bam, use_oq=False, k=31, min_count=None, prefilter=False, 
         raise _as_bam_kmers(exc) from None
 
 
+@_bgzf.option
 def recalibrate_bam(bam, use_oq=False, set_oq=False, kmers=None, gatkreport=None, output=None, quantize=None):
     """Without kmers: not implemented, as in the reference.
     bam: a path, or an aln.AlignmentFile.  kmers (a dict of bam_to_kmer_covariates' k-mer options: k, min_count, slots, prefilter, filter_bits, skip_unresolved, passes,
@@ -994,18 +1011,22 @@ def recalibrate_bam(bam, use_oq=False, set_oq=False, kmers=None, gatkreport=None
     if quantize is not None:                                 # without it the call is the one it was
         kw['quantize'] = quantize
     with stage('apply + render'):
-        if output is None:
+        if output is None and _bgzf.enabled():
+            with _bgzf.stdout_sink() as sink:
+                applybqsr.write_alignments(bam, *model, rg_to_int, sink, **kw)
+        elif output is None:
             sys.stdout.flush()
             applybqsr.write_alignments(bam, *model, rg_to_int, sys.stdout.buffer, **kw)
             sys.stdout.flush()
         else:
-            with open(output, 'wb') as sink:
+            with _bgzf.open_sink(output) as sink:
                 applybqsr.write_alignments(bam, *model, rg_to_int, sink, **kw)
     LAST_RUN.clear()
     LAST_RUN['aligned'] = dict(alignments=n, pitch=pitch, h2d_plane_bytes=resident['h2d_plane_bytes'], planes=list(resident['planes']))
     return info
 
 
+@_bgzf.option
 def recalibrate(bam, fastq, infer_rg=False, use_oq=False, set_oq=False, gatkreport=None, output=None, kmers=None, quantize=None):
     """Dispatcher of `kbbq recalibrate` (reference recalibrate.py:166-174).  The reference raises NotImplementedError
     for ANY gatkreport; here `-g` works with FASTQ input (a deliberate, documented divergence: SURVEY.md 8(f) #3), and
