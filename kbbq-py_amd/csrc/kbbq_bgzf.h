@@ -256,6 +256,9 @@ __device__ void bz_plan_header(BzSmall* sm, u32 n)
     bz_build_code(sm->freq_cl, 19, 7, sm->key_cl, sm->sym_cl, sm->cnt_cl, sm->len_cl, sm->code_cl);
     u32 used = 0, only = 0;
     for (u32 i = 0; i < 19; ++i) if (sm->len_cl[i]) { ++used; only = i; }
+    // Not reachable from bz_deflate: the stream codes N >= 258 lengths, at least two of them not zero (a literal or a length,
+    // and the end of block).  One distinct symbol would be a length v itself (16, 17 and 18 need a length or a zero beside
+    // them), so 258 equal lengths in one run -- which is coded with 16s.  Kept for a caller with a shorter list.
     if (used == 1) {                                       // the code-length code must be complete: a second one-bit code, never sent
         const u32 other = only ? 0 : 18;
         sm->len_cl[other] = 1;
