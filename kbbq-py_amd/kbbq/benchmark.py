@@ -503,7 +503,7 @@ def benchmark_kmers(bamfile, ref, var_sites, k=31, min_count=None, slots=None, p
     bases, errors, flagged, flagged_errors, unresolved and unresolved_errors (totals over the counted bases).
     passes: the classes of `passes` passes of the rule (flag_errors(passes=...): 1 where the last pass ends on another letter,
     2 where the base is unchanged and its row's last evaluation left it unresolved); `info` then receives passes too.
-    partitions: as gatk.bqsr.bam_to_kmer_covariates' -- the count in that many rounds (kmer.count_partitioned), the classes read
+    partitions: as gatk.bqsr.bam_to_kmer_covariates' -- the count in that many rounds (kmer.count_block), the classes read
     from the solid table: the same joint array; with more than one round `info` receives partitions, kept_pairs and solid_slots.
     kmer_min_qual = Q (kmer.gate_plane): only the k-mers whose bases all have quality >= Q -- the plane the confusion reads -- are
     counted; the prefilter, the count and every partition round read the gated copy of SEQ, which sizes the filter and the
@@ -517,7 +517,6 @@ def benchmark_kmers(bamfile, ref, var_sites, k=31, min_count=None, slots=None, p
     from . import kmer
     passes = kmer.check_passes(passes)
     kmers_from = kmer.check_kmers_from(kmers_from, prefilter, filter_bits, partitions, kmer_min_qual)
-    loaded = None
     if kmers_from is not None:
         k = kmer.set_k(kmers_from, k)                # the header alone: no device
     partitions = kmer._check_partitions(partitions)
@@ -538,8 +537,7 @@ def benchmark_kmers(bamfile, ref, var_sites, k=31, min_count=None, slots=None, p
     truth, _, lens, pitch = _flag_batch(bamfile, genome, flip_reverse=False, keep=keep, fused=True)
     qual = _qual_chars_dev(bamfile, lens, pitch, use_oq)
     n = len(lens)
-    t, nslots, admitted = (int(min_count) if min_count is not None else 0), 0, None
-    P = 1
+    t, counting = (int(min_count) if min_count is not None else 0), dict(slots=0, admitted=None)   # of a file without records
     if n:
         d_seq = keep['seq']
         d_len = torch.from_numpy(np.ascontiguousarray(lens.astype(np.uint32)).view(np.int32)).cuda()
@@ -550,50 +548,33 @@ def benchmark_kmers(bamfile, ref, var_sites, k=31, min_count=None, slots=None, p
         if kmer_min_qual is not None:
             counted, windows = kmer.gate_plane(d_seq, qual, d_len, k, kmer_min_qual)
             resident += n * pitch                   # ... until the count is over
-        filt = table = None
+
+        def read(what, **kw):
+            (kmer.prefilter_kmers if what == 'prefilter' else kmer.count_kmers)(counted, d_len, k=k, **kw)
+        table = None
         try:
-            if prefilter:
-                filt = kmer.prefilter_kmers(counted, d_len, k=k, filter=kmer.KmerFilter(kmer.filter_words(windows, filter_bits)))
-                admitted = filt.admitted
-                filt.release_seen()
-            total, room = admitted if prefilter else windows, budget - resident - (filt.nbytes if filt is not None else 0)
-            P = kmer.resolve_partitions(partitions, total, room) if partitions != 1 else 1
-            if kmers_from is not None:
-                table, _, t, loaded = kmer.load_set(kmers_from, min_count, slots, k=k, budget=room)
-            elif P > 1:
-                table, _, t, parts_info = kmer.count_partitioned(
-                    lambda tab, p: kmer.count_kmers(counted, d_len, k=k, table=tab, filter=filt, parts=P, part=p), k, P,
-                    slots if slots is not None else kmer.partition_slots(total, P, room), min_count, room)
-                if filt is not None:
-                    filt.close()
-            else:
-                if slots is None:
-                    slots = kmer.default_slots(total, room)
-                table = kmer.count_kmers(counted, d_len, k=k, slots=slots, filter=filt)
-                if filt is not None:
-                    filt.close()
-                t = int(min_count) if min_count is not None else kmer.solid_threshold(kmer.kmer_histogram(table))
+            table, _, t, counting = kmer.count_block(read, windows, k, min_count=min_count, slots=slots, prefilter=prefilter,
+                                                     filter_bits=filter_bits, partitions=partitions, kmers_from=kmers_from,
+                                                     room=budget - resident)
             del counted
             kflags, _, _ = kmer.flag_errors(table, d_seq, d_len, t, unresolved=True, **kmer._passes_kw(passes))
-            nslots = parts_info['slots'] if P > 1 else table.slots
         finally:
-            if filt is not None:
-                filt.close()
             if table is not None:
                 table.close()
         joint = kmer_confusion(qual, truth, kflags, lens, pitch, 33)
     else:
         joint = np.zeros((256, 2, 3), dtype=np.int64)
     if info is not None:
-        info.update(k=k, min_count=t, reads=n, slots=nslots, prefilter=bool(prefilter), admitted=admitted, **kmer_totals(joint))
+        info.update(k=k, min_count=t, reads=n, slots=counting['slots'], prefilter=bool(prefilter), admitted=counting['admitted'],
+                    **kmer_totals(joint))
         if passes != 1:
             info.update(passes=passes)
-        if P > 1:
-            info.update(partitions=P, kept_pairs=parts_info['kept_pairs'], solid_slots=parts_info['solid_slots'])
+        if counting.get('partitions', 1) > 1:
+            info.update({key: counting[key] for key in ('partitions', 'kept_pairs', 'solid_slots')})
         if kmer_min_qual is not None:
             info.update(kmer_min_qual=kmer_min_qual, counted_windows=windows if n else 0, windows=ungated if n else 0)
         if kmers_from is not None:
-            info.update(kmers_from=kmers_from, loaded_kmers=loaded['loaded_kmers'] if loaded is not None else 0)
+            info.update(kmers_from=kmers_from, loaded_kmers=counting.get('loaded_kmers', 0))
     return joint
 
 

@@ -380,7 +380,7 @@ def bam_to_kmer_covariates(bamfileobj, k=31, min_count=None, slots=None, prefilt
     passes: the flags of `passes` passes of the correction (kbbq_kmer_flag_passes_dev) -- an error where the last pass ends on
     another letter than SEQ's, unresolved where the base is unchanged and its row's last evaluation left it so; `info` then
     receives passes too.
-    partitions: the k-mers counted in that many rounds through a table of `slots` slots (kbbq.kmer.count_partitioned; 'auto':
+    partitions: the k-mers counted in that many rounds through a table of `slots` slots (kbbq.kmer.count_block; 'auto':
     kbbq.kmer.partitions_for within what the budget leaves beside the resident planes) and the flags written against the solid
     table: the same vectors.  With more than one round `info` receives partitions, kept_pairs and solid_slots too, and its slots
     is the per-partition table.  Refused in a process group before the group's own refusal.
@@ -448,41 +448,21 @@ def _kmer_tally(bamfileobj, inputs, k, min_count, slots, prefilter, filter_bits,
     if kmer_min_qual is not None:
         counted, windows = kmer.gate_plane(d_seq, d_qual, d_len, k, kmer_min_qual)
         resident += n * pitch                  # ... until the count is over
-    filt = table = None
-    admitted = None
-    loaded = None
+
+    def read(what, **kw):
+        (kmer.prefilter_kmers if what == 'prefilter' else kmer.count_kmers)(counted, d_len, k=k, **kw)
+    table = None
     try:
-        if prefilter:
-            filt = kmer.prefilter_kmers(counted, d_len, k=k, filter=kmer.KmerFilter(kmer.filter_words(windows, filter_bits)))
-            admitted = filt.admitted
-            filt.release_seen()
-        total, room = admitted if prefilter else windows, budget - resident - (filt.nbytes if filt is not None else 0)
-        P = kmer.resolve_partitions(partitions, total, room) if partitions != 1 else 1
-        if kmers_from is not None:
-            table, _, t, loaded = kmer.load_set(kmers_from, min_count, slots, k=k, budget=room)
-            k = loaded['k']
-        elif P > 1:
-            table, _, t, parts_info = kmer.count_partitioned(
-                lambda tab, p: kmer.count_kmers(counted, d_len, k=k, table=tab, filter=filt, parts=P, part=p), k, P,
-                slots if slots is not None else kmer.partition_slots(total, P, room), min_count, room)
-            if filt is not None:
-                filt.close()
-        else:
-            if slots is None:
-                slots = kmer.default_slots(total, room)
-            table = kmer.count_kmers(counted, d_len, k=k, slots=slots, filter=filt)
-            if filt is not None:
-                filt.close()
-            t = int(min_count) if min_count is not None else kmer.solid_threshold(kmer.kmer_histogram(table))
+        table, _, t, counting = kmer.count_block(read, windows, k, min_count=min_count, slots=slots, prefilter=prefilter,
+                                                 filter_bits=filter_bits, partitions=partitions, kmers_from=kmers_from,
+                                                 room=budget - resident)
         del counted
+        k = table.k
         if skip_unresolved:
             err, changed, skipped = kmer.flag_errors(table, d_seq, d_len, t, unresolved=True, **kmer._passes_kw(passes))
         else:
             err, changed = kmer.flag_errors(table, d_seq, d_len, t, **kmer._passes_kw(passes))
-        nslots = parts_info['slots'] if P > 1 else table.slots
     finally:
-        if filt is not None:
-            filt.close()
         if table is not None:
             table.close()
     tables = dev.Tables(R, 2 * S)
@@ -491,20 +471,20 @@ def _kmer_tally(bamfileobj, inputs, k, min_count, slots, prefilter, filter_bits,
     _tally_flag_plane(tables, d_seq, d_qual, err, None, d_len, d_clip, d_trim, d_flags, n, pitch, S, R, minscore,
                       os.environ.get('KBBQ_TALLY_FUSED', '2') != '0' and fits)
     if info is not None:
-        info.update(k=k, min_count=t, reads=n, flagged_bases=int(changed.cpu().numpy().astype(np.int64).sum()), slots=nslots,
-                    prefilter=bool(prefilter), admitted=admitted)
+        info.update(k=k, min_count=t, reads=n, flagged_bases=int(changed.cpu().numpy().astype(np.int64).sum()),
+                    slots=counting['slots'], prefilter=bool(prefilter), admitted=counting['admitted'])
         if skip_unresolved:
             info.update(skipped_bases=int(skipped.cpu().numpy().astype(np.int64).sum()))
         if passes != 1:
             info.update(passes=passes)
-        if P > 1:
-            info.update(partitions=P, kept_pairs=parts_info['kept_pairs'], solid_slots=parts_info['solid_slots'])
+        if counting.get('partitions', 1) > 1:
+            info.update({key: counting[key] for key in ('partitions', 'kept_pairs', 'solid_slots')})
         if excluded:
             info.update(excluded_reads=int(excluded[0].sum()))
         if kmer_min_qual is not None:
             info.update(kmer_min_qual=kmer_min_qual, counted_windows=windows, windows=ungated)
-        if loaded is not None:
-            info.update(kmers_from=loaded['kmers_from'], loaded_kmers=loaded['loaded_kmers'])
+        if kmers_from is not None:
+            info.update(kmers_from=counting['kmers_from'], loaded_kmers=counting['loaded_kmers'])
     kept =dict(batch=b, n=n, S=S, pitch=pitch, seq=d_seq, source=d_qual, use_oq=bool(use_oq), rg_to_int=rg_to_int,
                 planes=['SEQ', 'OQ' if use_oq else 'QUAL'], h2d_plane_bytes=2 * n * pitch)
     return _solve.vectors_from_tables(*tables.to_host(), maxscore), kept

@@ -39,7 +39,15 @@ solid_threshold(hist), the partition table is freed, ALL kept pairs are merged i
 default_slots(len(kept), budget) (those with keep <= count < t too: no decision reads them, and dropping them would cost a
 pass over the pairs) and the unchanged correct / flag kernels run against it at min_count = t.  The summed histogram (with the
 prefilter: h[2:]), the threshold, every base's decision and every figure printed are those of the one-table path; every round
-hashes every window, which is what the smaller table costs.  count_partitioned is the one statement of it in code.
+hashes every window, which is what the smaller table costs.  In code: count_rounds is the rounds (`kbbq count` keeps their
+pairs as they are), count_partitioned the rounds and the merge into the solid table.
+
+The counting block (count_block) is the one place where the options above meet: the prefilter pass, `admitted`, the release
+of `seen`, the number of rounds ('auto' included) within what the device budget leaves, the table's size, the count in one
+round or in P, the histogram and the threshold -- or a k-mer set loaded in the count's place (load_set).  The commands that
+decide bases (correct_reads; gatk.bqsr._kmer_tally for `bqsr --kmers` and `recalibrate -b --kmers`; benchmark.benchmark_kmers;
+recalibrate.recalibrate_corrected) hand it a callback that runs one pass over all their rows and get (table, hist, t, info)
+back; `kbbq count` shares its first half (count_plan) and count_rounds.
 
 Quality gate (`kmer_min_qual=Q`, `--kmer-min-qual Q`; tests/kmer_gate_model.py).  THE RULE: a base is countable when it is A/C/G/T
 and its quality -- the plane the command reads anyway -- is >= Q; a window is counted iff all k of its bases are countable.  One
@@ -48,8 +56,10 @@ kernel in front of the count (km_gate, kbbq_kmer_gate_rows_dev; gate_plane / gat
 rank's local count read that copy through the calls they always made, the filter and the default table are sized from the
 counted windows, and the copy is freed when the count is over.  Nothing after the count knows the option: the histogram is the
 gated table's, the threshold its first valley or min_count, and the correction, flag and passes calls run on the rows as read.
-count_gated is correct_reads' count on the gated plane; the other commands put the plane into the counts they already had.
+To count_block the gate is nothing but the caller's choice of rows and of `windows`: the callback reads the gated plane(s) in
+the place of the sequence plane(s), and the counted windows stand where kmer_total or batch_windows would.
 """
+import contextlib
 import ctypes
 import os
 import sys
@@ -384,6 +394,29 @@ def _check_part(parts, part):
     return parts, part
 
 
+# the count's entry points by (filter, parts > 1): for character planes (host buffers: the name without _dev) and for device batches
+_COUNT = {(False, False): ('kbbq_kmer_count_dev', 'kbbq_kmer_count_rows_dev'),
+          (True, False): ('kbbq_kmer_count_filtered_dev', 'kbbq_kmer_count_filtered_rows_dev'),
+          (False, True): ('kbbq_kmer_count_part_dev', 'kbbq_kmer_count_rows_part_dev'),
+          (True, True): ('kbbq_kmer_count_filtered_part_dev', 'kbbq_kmer_count_filtered_rows_part_dev')}
+
+
+def _count_into(table, filter, rows, parts, part, batch=False, host=False):
+    """One count call: `rows` (the plane, the sidecar and their sizes as the entry point takes them) into `table`, through the
+    entry point that (device batch, host buffer, filter, parts > 1) name.  parts = 1 is the call without _part."""
+    name = _COUNT[filter is not None, parts > 1][bool(batch)]
+    call = getattr(N.load(), name[:-4] if host else name)
+    args = (table.handle,) + ((filter.handle,) if filter is not None else ()) + tuple(rows) + ((parts, part) if parts > 1 else ())
+    ctx = table.ctx
+    try:
+        N.check(call(ctx.handle, *args))
+        if not host:
+            ctx.status()
+    except N.KmerTableFull as exc:
+        raise _full(table, exc) from None
+    return table
+
+
 def count_kmers(seq_plane, meta, k=31, slots=None, table=None, filter=None, parts=1, part=0):
     """Count every k-mer of the rows into `table` (a new one of `slots` slots when None; default: kmer_total at a load factor
     of at most 0.5, capped by the device budget) and return it.  Counting adds: several calls compose.  A table that fills
@@ -392,63 +425,17 @@ def count_kmers(seq_plane, meta, k=31, slots=None, table=None, filter=None, part
     only the windows whose key has owner(key, P) == part are counted (kbbq_kmer_count*_part*); parts = 1 is the call without."""
     from . import _device as dev
     parts, part = _check_part(parts, part)
-    if parts > 1:
-        return _count_kmers_part(seq_plane, meta, k, slots, table, filter, parts, part)
     n, pitch = int(seq_plane.shape[0]), int(seq_plane.shape[1])
     if table is None:
         if slots is None:
             total = filter.admitted if filter is not None else kmer_total(_host_meta(meta), k)
             slots = default_slots(total, dev.device_budget())
         table = KmerTable(k, slots)
-    lib = N.load()
-    ctx = table.ctx
-    try:
-        if _on_device(seq_plane):
-            if filter is not None:
-                N.check(lib.kbbq_kmer_count_filtered_dev(ctx.handle, table.handle, filter.handle, N.ptr(seq_plane), N.ptr(meta),
-                                                         n, pitch))
-            else:
-                N.check(lib.kbbq_kmer_count_dev(ctx.handle, table.handle, N.ptr(seq_plane), N.ptr(meta), n, pitch))
-            ctx.status()
-        else:
-            seq_plane = np.ascontiguousarray(seq_plane, dtype=np.uint8)
-            meta = np.ascontiguousarray(meta, dtype=np.uint32)
-            if filter is not None:
-                N.check(lib.kbbq_kmer_count_filtered(ctx.handle, table.handle, filter.handle, N.ptr(seq_plane), N.ptr(meta), n, pitch))
-            else:
-                N.check(lib.kbbq_kmer_count(ctx.handle, table.handle, N.ptr(seq_plane), N.ptr(meta), n, pitch))
-    except N.KmerTableFull as exc:
-        raise _full(table, exc) from None
-    return table
-
-
-def _count_kmers_part(seq_plane, meta, k, slots, table, filter, parts, part):
-    """count_kmers for one partition: the same table, sizes and errors through the _part calls."""
-    from . import _device as dev
-    n, pitch = int(seq_plane.shape[0]), int(seq_plane.shape[1])
-    if table is None:
-        if slots is None:
-            total = filter.admitted if filter is not None else kmer_total(_host_meta(meta), k)
-            slots = default_slots(total, dev.device_budget())
-        table = KmerTable(k, slots)
-    lib = N.load()
-    ctx = table.ctx
-    on_device = _on_device(seq_plane)
-    if not on_device:
+    host = not _on_device(seq_plane)
+    if host:
         seq_plane = np.ascontiguousarray(seq_plane, dtype=np.uint8)
         meta = np.ascontiguousarray(meta, dtype=np.uint32)
-    rows = (N.ptr(seq_plane), N.ptr(meta), n, pitch, parts, part)
-    try:
-        if filter is not None:
-            N.check((lib.kbbq_kmer_count_filtered_part_dev if on_device else lib.kbbq_kmer_count_filtered_part)(
-                ctx.handle, table.handle, filter.handle, *rows))
-        else:
-            N.check((lib.kbbq_kmer_count_part_dev if on_device else lib.kbbq_kmer_count_part)(ctx.handle, table.handle, *rows))
-        if on_device:
-            ctx.status()
-    except N.KmerTableFull as exc:
-        raise _full(table, exc) from None
-    return table
+    return _count_into(table, filter, (N.ptr(seq_plane), N.ptr(meta), n, pitch), parts, part, host=host)
 
 
 def select(table, nbuckets=1, min_count=1):
@@ -747,22 +734,7 @@ def count_batch(batch, k=31, table=None, slots=None, filter=None, parts=1, part=
     seq, meta, n, pitch, flags = _batch_rows(batch)
     if plane is not None:
         seq = N.ptr(plane)
-    lib = N.load()
-    ctx = table.ctx
-    try:
-        if parts > 1 and filter is not None:
-            N.check(lib.kbbq_kmer_count_filtered_rows_part_dev(ctx.handle, table.handle, filter.handle, seq, meta, n, pitch, flags,
-                                                               parts, part))
-        elif parts > 1:
-            N.check(lib.kbbq_kmer_count_rows_part_dev(ctx.handle, table.handle, seq, meta, n, pitch, flags, parts, part))
-        elif filter is not None:
-            N.check(lib.kbbq_kmer_count_filtered_rows_dev(ctx.handle, table.handle, filter.handle, seq, meta, n, pitch, flags))
-        else:
-            N.check(lib.kbbq_kmer_count_rows_dev(ctx.handle, table.handle, seq, meta, n, pitch, flags))
-        ctx.status()
-    except N.KmerTableFull as exc:
-        raise _full(table, exc) from None
-    return table
+    return _count_into(table, filter, (seq, meta, n, pitch, flags), parts, part, batch=True)
 
 
 def correct_batch(table, batch, min_count, fix_n=False, passes=1, skip_unresolved=False):
@@ -821,16 +793,13 @@ def _check_prefilter(min_count, filter_bits):
                          'once, so the filter belongs at the rank that owns the key; run on one GPU, or without the prefilter')
 
 
-def count_partitioned(count_round, k, P, slots, min_count, budget):
-    """The rule of the module docstring's "Partitions", shared by the four commands.  count_round(table, p) counts partition p
-    of P of the WHOLE input (a plane, or every band's rows) into `table`; `slots` is the per-partition table, `budget` what
-    the solid table may take.  Returns (solid table, hist, t, info): the table the correct / flag kernels read at
-    min_count = t, the histogram summed over the rounds, and info = {'partitions', 'slots', 'table_bytes' (the per-partition
-    table), 'kept_pairs', 'solid_slots'}.  A round whose table fills raises count_round's KmerTableFull."""
+def count_rounds(count_round, k, P, slots, keep):
+    """The rounds of the module docstring's "Partitions" through one table of `slots` slots: for p = 0..P-1 the table is cleared
+    (except before the first round), count_round(table, p) counts partition p of P of the WHOLE input into it, its histogram is
+    added to `hist` and its pairs with count >= keep join `kept` on the device.  P = 1 is one count that clears nothing.
+    Returns (hist, kept, info): the summed histogram, the list of (keys, counts) device pairs of the rounds that kept any, and
+    info = {'partitions', 'slots', 'table_bytes'}.  The table is closed here; count_round's KmerTableFull passes through."""
     P = int(P)
-    if min_count is not None and int(min_count) < 1:
-        raise ValueError('min_count must be >= 1, got %d' % int(min_count))
-    keep = int(min_count) if min_count is not None else 2
     hist = np.zeros(HIST, dtype=np.int64)
     kept = []                                # (keys, counts) of every round, on the device
     table = KmerTable(k, slots)
@@ -847,6 +816,18 @@ def count_partitioned(count_round, k, P, slots, min_count, budget):
             del keys, counts
     finally:
         table.close()
+    return hist, kept, info
+
+
+def count_partitioned(count_round, k, P, slots, min_count, budget):
+    """The rule of the module docstring's "Partitions", which count_block runs for every command: count_rounds, then the merge
+    of all kept pairs into the solid table.  count_round(table, p) counts partition p of P of the WHOLE input (a plane, or every
+    band's rows) into `table`; `slots` is the per-partition table, `budget` what the solid table may take.  Returns (solid table, hist, t, info): the table the correct / flag kernels read at
+    min_count = t, the histogram summed over the rounds, and info = {'partitions', 'slots', 'table_bytes' (the per-partition
+    table), 'kept_pairs', 'solid_slots'}.  A round whose table fills raises count_round's KmerTableFull."""
+    if min_count is not None and int(min_count) < 1:
+        raise ValueError('min_count must be >= 1, got %d' % int(min_count))
+    hist, kept, info = count_rounds(count_round, k, P, slots, int(min_count) if min_count is not None else 2)
     t = int(min_count) if min_count is not None else solid_threshold(hist)
     npairs = sum(int(keys.shape[0]) for keys, _ in kept)
     solid = KmerTable(k, default_slots(npairs, budget))
@@ -1025,6 +1006,94 @@ def load_set(path, min_count=None, slots=None, k=None, budget=None, slab=None):
     return table, s.hist.copy(), t, info
 
 
+def _untimed(name, sync=True):
+    """stage() of a caller that times nothing."""
+    return contextlib.nullcontext()
+
+
+def count_plan(read, windows, slots=None, prefilter=False, filter_bits=4, partitions=1, room=None, stage=_untimed):
+    """What the count block and `kbbq count` do before their first table: the prefilter pass (read('prefilter', filter=...)
+    over all rows, through a new KmerFilter of filter_words(windows, filter_bits) words, whose `seen` is released after it), the
+    number of rounds and the table's size.  Returns (filt, admitted, filter_bytes, P, slots, budget): the filter (None
+    without; the caller closes it), its `admitted` (None without) and its bytes during the pass, the rounds that `partitions`
+    resolves to, the slots of the table (`slots` when given, else partition_slots for P > 1 and default_slots for P = 1, of
+    `admitted` with the prefilter and of `windows` without) and the budget these were taken within -- room's rule, see
+    count_block.  A pass that raises closes the filter."""
+    from . import _device as dev
+    filt, admitted, filter_bytes = None, None, 0
+    try:
+        if prefilter:
+            with stage('k-mer prefilter', sync=True):
+                filt = KmerFilter(filter_words(windows, filter_bits))
+                read('prefilter', filter=filt)
+                filter_bytes, admitted = filt.nbytes, filt.admitted
+                filt.release_seen()
+        total = admitted if prefilter else int(windows)
+        budget = dev.device_budget() if room is None else int(room) - (filt.nbytes if filt is not None else 0)
+        P = resolve_partitions(partitions, total, budget) if partitions != 1 else 1
+        if slots is None:
+            slots = partition_slots(total, P, budget) if P > 1 else default_slots(total, budget)
+    except BaseException:
+        if filt is not None:
+            filt.close()
+        raise
+    return filt, admitted, filter_bytes, P, slots, budget
+
+
+def count_block(read, windows, k, min_count=None, slots=None, prefilter=False, filter_bits=4, partitions=1, kmers_from=None,
+                room=None, stage=_untimed):
+    """The counting block of every k-mer command: prefilter, partitions, table size, the count in one round or in P, the
+    histogram and the threshold -- or a k-mer set loaded in the count's place.
+    read(what, **kw) runs one pass over ALL rows the caller counts and returns nothing: what = 'prefilter' (kw: filter) is
+    kmer's prefilter, what = 'count' (kw: table, filter, parts, part) its count.  What the rows are is the caller's: a host
+    plane, a device plane, a gated plane, every band with its gated plane; it frees its gated planes when the block returns.
+    windows: what sizes the filter and, without the prefilter, the default table: the caller's k-mer windows (kmer_total,
+    batch_windows), or the counted windows of its gate.  slots overrides the table's size.  partitions: checked, an int or 'auto'.
+    room: the two budget rules.  None (correct_reads, whose rows are the caller's host or device planes and not the block's
+    to account for): the whole device_budget(), read once the filter exists and not reduced by it, and load_set's own default.
+    An integer (the commands that keep planes resident beside the table): the device budget less those planes, as the caller
+    read and summed them; the filter's `twice` array is taken off it here, and the rest goes to resolve_partitions,
+    partition_slots, default_slots, count_partitioned and load_set.
+    kmers_from (checked: no counting option goes with it): load_set(kmers_from, min_count, slots, k=k) within that budget.
+    stage: recalibrate's stage(name, sync=True) timer for 'k-mer prefilter', 'k-mer count' and 'k-mer load'; nothing is timed without.
+    Returns (table, hist, t, info): the table the correct / flag kernels read at min_count = t -- the caller closes it --, its
+    histogram (with the prefilter: h[2:]; over all rounds; the file's) and info = {'slots', 'table_bytes', 'filter_bytes',
+    'admitted'} plus count_partitioned's keys with more than one round ('slots' and 'table_bytes' are then the per-partition
+    table's) or load_set's after a load.  The filter is closed here on every path: before the histogram in one round, after the
+    last in several."""
+    if kmers_from is not None:
+        with stage('k-mer load', sync=True):
+            table, hist, t, more = load_set(kmers_from, min_count, slots, k=k, budget=room)
+        return table, hist, t, dict(dict(filter_bytes=0, admitted=None), **more)
+    filt, admitted, filter_bytes, P, slots, budget = count_plan(read, windows, slots, prefilter, filter_bits, partitions, room, stage)
+    table = None
+    try:
+        if P > 1:
+            with stage('k-mer count', sync=True):
+                table, hist, t, more = count_partitioned(lambda tab, p: read('count', table=tab, filter=filt, parts=P, part=p),
+                                                         k, P, slots, min_count, budget)
+        else:
+            with stage('k-mer count', sync=True):
+                table = KmerTable(k, slots)
+                read('count', table=table, filter=filt, parts=1, part=0)
+            if filt is not None:                 # before the histogram
+                filt.close()
+                filt = None
+            hist = kmer_histogram(table)
+            t = int(min_count) if min_count is not None else solid_threshold(hist)
+            more = {}
+        if t < 1:
+            raise ValueError('min_count must be >= 1, got %d' % t)
+        info = dict(dict(slots=table.slots, table_bytes=table.nbytes, filter_bytes=filter_bytes, admitted=admitted), **more)
+        done, table = table, None
+        return done, hist, t, info
+    finally:
+        if filt is not None:
+            filt.close()
+        if table is not None:
+            table.close()
+
+
 def correct_reads(seq_plane, meta, k=31, min_count=None, slots=None, prefilter=False, filter_bits=4, fix_n=False, passes=1,
                   partitions=1, qual_plane=None, kmer_min_qual=None, kmers_from=None):
     """Count, pick the threshold (min_count, else the histogram's first valley) and correct.  Returns (corrected plane in
@@ -1049,127 +1118,32 @@ def correct_reads(seq_plane, meta, k=31, min_count=None, slots=None, prefilter=F
     (k too: pass k=None, or the file's), and the reads are corrected against it as against a table counted here.  No counting
     option goes with it (check_kmers_from).  info then has 'kmers_from' and 'loaded_kmers' too."""
     passes = check_passes(passes)
-    if check_kmers_from(kmers_from, prefilter, filter_bits, partitions, kmer_min_qual) is not None:
-        table, hist, t, more = load_set(kmers_from, min_count, slots, k=k)
-        try:
-            out, changed = correct_with(table, seq_plane, meta, t, fix_n=fix_n, **_passes_kw(passes))
-            return out, dict(dict(k=table.k, min_count=t, hist=hist, changed=changed, prefilter=False, filter_bytes=0, admitted=None,
-                                  fix_n=bool(fix_n), passes=passes), **more)
-        finally:
-            table.close()
+    kmers_from = check_kmers_from(kmers_from, prefilter, filter_bits, partitions, kmer_min_qual)
     partitions = _check_partitions(partitions)
     kmer_min_qual = check_kmer_min_qual(kmer_min_qual, qual_plane is not None)
     if prefilter:
         _check_prefilter(min_count, filter_bits)
+    windows = kmer_total(_host_meta(meta), k) if kmers_from is None else 0
+    rows, gate = [seq_plane, meta], {}                   # the plane and the sidecar the prefilter and the count read
     if kmer_min_qual is not None:
-        return _correct_reads_gated(seq_plane, qual_plane, meta, k, min_count, slots, prefilter, filter_bits, fix_n, passes,
-                                    partitions, kmer_min_qual)
-    filt = None
-    filter_bytes, admitted = 0, None
-    if prefilter:
-        filt = prefilter_kmers(seq_plane, meta, k=k, bits=filter_bits)
+        from . import _device as dev
+        d_meta = _to_device(dev._torch(), meta, np.uint32)
+        gated, counted = gate_plane(seq_plane, qual_plane, d_meta, k, kmer_min_qual)
+        rows, gate = [gated, d_meta], dict(kmer_min_qual=kmer_min_qual, counted_windows=counted, windows=windows)
+        del gated
+
+    def read(what, **kw):
+        (prefilter_kmers if what == 'prefilter' else count_kmers)(*rows, k=k, **kw)
     table = None
     try:
-        if filt is not None:
-            filter_bytes, admitted = filt.nbytes, filt.admitted
-            filt.release_seen()
-        P, more = 1, {}
-        if partitions != 1:
-            from . import _device as dev
-            total = admitted if filt is not None else kmer_total(_host_meta(meta), k)
-            budget = dev.device_budget()
-            P = resolve_partitions(partitions, total, budget)
-        if P > 1:
-            table, hist, t, more = count_partitioned(
-                lambda tab, p: count_kmers(seq_plane, meta, k=k, table=tab, filter=filt, parts=P, part=p), k, P,
-                slots if slots is not None else partition_slots(total, P, budget), min_count, budget)
-            if filt is not None:
-                filt.close()
-        else:
-            table = count_kmers(seq_plane, meta, k=k, slots=slots, filter=filt)
-            if filt is not None:
-                filt.close()
-            hist = kmer_histogram(table)
-            t = int(min_count) if min_count is not None else solid_threshold(hist)
-        if t < 1:
-            raise ValueError('min_count must be >= 1, got %d' % t)
-        out, changed = correct_with(table, seq_plane, meta, t, fix_n=fix_n, **_passes_kw(passes))
-        return out, dict(dict(k=table.k, min_count=t, hist=hist, changed=changed, slots=table.slots, table_bytes=table.nbytes,
-                              prefilter=bool(prefilter), filter_bytes=filter_bytes, admitted=admitted, fix_n=bool(fix_n),
-                              passes=passes), **more)
-    finally:
-        if filt is not None:
-            filt.close()
-        if table is not None:
-            table.close()
-
-
-def count_gated(read, windows, k, min_count=None, slots=None, prefilter=False, filter_bits=4, partitions=1):
-    """The count of a gated input: read(what, **kw) runs kmer's prefilter (what = 'prefilter', kw:
-    filter) or count (what = 'count', kw: table, filter, parts, part) over ALL gated rows of the input and returns nothing;
-    `windows` is the input's counted windows, which size the filter and the default table(s) (`slots` overrides).  Returns
-    (table, hist, t, info) as the ungated paths make them: the table the correct / flag kernels read at min_count = t, the
-    histogram of the gated table (with the prefilter: h[2:]), and info = {'slots', 'table_bytes', 'filter_bytes', 'admitted'}
-    plus count_partitioned's with more than one partition.  The caller has checked its options; it closes the table."""
-    from . import _device as dev
-    budget = dev.device_budget()
-    filt = table = None
-    filter_bytes, admitted = 0, None
-    try:
-        if prefilter:
-            filt = KmerFilter(filter_words(windows, filter_bits))
-            read('prefilter', filter=filt)
-            filter_bytes, admitted = filt.nbytes, filt.admitted
-            filt.release_seen()
-        total = admitted if filt is not None else int(windows)
-        P = resolve_partitions(partitions, total, budget) if partitions != 1 else 1
-        if P > 1:
-            table, hist, t, more = count_partitioned(lambda tab, p: read('count', table=tab, filter=filt, parts=P, part=p), k, P,
-                                                     slots if slots is not None else partition_slots(total, P, budget), min_count,
-                                                     budget)
-        else:
-            table = KmerTable(k, slots if slots is not None else default_slots(total, budget))
-            read('count', table=table, filter=filt, parts=1, part=0)
-            hist = kmer_histogram(table)
-            t = int(min_count) if min_count is not None else solid_threshold(hist)
-            more = {}
-        if t < 1:
-            raise ValueError('min_count must be >= 1, got %d' % t)
-        info = dict(dict(slots=table.slots, table_bytes=table.nbytes, filter_bytes=filter_bytes, admitted=admitted), **more)
-        done, table = table, None
-        return done, hist, t, info
-    finally:
-        if filt is not None:
-            filt.close()
-        if table is not None:
-            table.close()
-
-
-def _correct_reads_gated(seq_plane, qual_plane, meta, k, min_count, slots, prefilter, filter_bits, fix_n, passes, partitions, Q):
-    """correct_reads with the quality gate in front of its count."""
-    from . import _device as dev
-    T = dev._torch()
-    d_meta = _to_device(T, meta, np.uint32)
-    gated, counted = gate_plane(seq_plane, qual_plane, d_meta, k, Q)
-    state = dict(plane=gated)
-    del gated
-
-    def read(what, filter=None, table=None, parts=1, part=0):
-        if what == 'prefilter':
-            prefilter_kmers(state['plane'], d_meta, k=k, filter=filter)
-        else:
-            count_kmers(state['plane'], d_meta, k=k, table=table, filter=filter, parts=parts, part=part)
-    table = None
-    try:
-        table, hist, t, more = count_gated(read, counted, k, min_count=min_count, slots=slots, prefilter=prefilter,
-                                           filter_bits=filter_bits, partitions=partitions)
-        state.clear()                        # the gated plane is freed here: the correction reads the rows as read
+        table, hist, t, more = count_block(read, gate.get('counted_windows', windows), k, min_count=min_count, slots=slots,
+                                           prefilter=prefilter, filter_bits=filter_bits, partitions=partitions, kmers_from=kmers_from)
+        del rows[:]                                      # a gated plane is freed here: the correction reads the rows as read
         out, changed = correct_with(table, seq_plane, meta, t, fix_n=fix_n, **_passes_kw(passes))
         return out, dict(dict(k=table.k, min_count=t, hist=hist, changed=changed, prefilter=bool(prefilter), fix_n=bool(fix_n),
-                              passes=passes, kmer_min_qual=Q, counted_windows=counted, windows=kmer_total(_host_meta(meta), k)),
-                         **more)
+                              passes=passes, **gate), **more)
     finally:
-        state.clear()
+        del rows[:]
         if table is not None:
             table.close()
 
@@ -1207,14 +1181,7 @@ def correct_fastq(path, out, k=31, min_count=None, slots=None, local_slots=None,
                                 fix_n=fix_n, **_passes_kw(passes), **_partitions_kw(partitions),
                                 **_min_qual_kw(kmer_min_qual, qual_plane=qual), **_kmers_from_kw(kmers_from))
     text = fastx.format_fastq(names, fixed, qual, meta & 0xFFFF)
-    if _bgzf.enabled():
-        _bgzf.write_text(out, text)
-    elif isinstance(out, str):
-        with open(out, 'w', encoding='latin-1', newline='') as fh:
-            fh.write(text)
-    else:
-        out.write(text)
-        out.flush()
+    _write_fastq(out, text)
     info['reads'] = n
     return info
 
@@ -1388,11 +1355,54 @@ def solid_table(owned, min_count):
     return table
 
 
-def _correct_shard_from(kmers_from, out, names, seq, qual, meta, k, min_count, slots, fix_n, passes):
-    """correct_fastq_ranks past its shard with a k-mer set in the place of the count, the gather and the solid table."""
+def _write_fastq(out, text, ranks=None):
+    """The output step of correct_fastq and of the rank paths: `text` to `out`, a path (BGZF with --bgzf, else latin-1 text)
+    or a text stream.  ranks = (world, rank) of a process group: a path is `out`.rankNNNN (`out` itself with one rank), a
+    stream is written in rank order."""
+    if isinstance(out, str):
+        path = out if ranks is None or ranks[0] == 1 else '%s.rank%04d' % (out, ranks[1])
+        if _bgzf.enabled():
+            _bgzf.write_text(path, text)
+        else:
+            with open(path, 'w', encoding='latin-1', newline='') as fh:
+                fh.write(text)
+        return
+
+    def write():
+        if _bgzf.enabled():
+            _bgzf.write_text(out, text)
+        else:
+            out.write(text)
+            out.flush()
+    if ranks is None:
+        write()
+    else:
+        from . import parallel
+        parallel.in_rank_order(write)
+
+
+def _correct_shard(table, k, t, hist, reads, out, names, seq, qual, meta, fix_n, passes):
+    """What every rank does once it has its table (the gathered solid table, or a loaded set; closed here): correct its own
+    rows at min_count = t, agree on an error, sum the changed bases over the ranks and write its records.  Returns the info
+    both rank paths start from."""
     from . import fastx
     from . import parallel
-    world, rank = parallel.world_rank()
+    fixed = changed = exc = None
+    try:
+        fixed, changed = correct_with(table, seq, meta, t, fix_n=fix_n, **_passes_kw(passes))
+    except Exception as e:                   # noqa: BLE001 -- every rank must reach the agreement
+        exc = e
+    finally:
+        table.close()
+    _agree(exc)
+    total = int(parallel.sum_over_ranks(np.array([changed.astype(np.int64).sum()], dtype=np.int64))[0])
+    _write_fastq(out, fastx.format_fastq(names, fixed, qual, meta & 0xFFFF), parallel.world_rank())
+    return dict(k=k, min_count=t, hist=hist, changed=changed, reads=reads, changed_bases=total, fix_n=bool(fix_n), passes=passes)
+
+
+def _correct_shard_from(kmers_from, out, names, seq, qual, meta, k, min_count, slots, fix_n, passes):
+    """correct_fastq_ranks past its shard with a k-mer set in the place of the count, the gather and the solid table."""
+    from . import parallel
     loaded = exc = None
     try:
         loaded = load_set(kmers_from, min_count, slots, k=k)
@@ -1406,30 +1416,8 @@ def _correct_shard_from(kmers_from, out, names, seq, qual, meta, k, min_count, s
         raise
     table, hist, t, more = loaded
     reads = sum(parallel.all_gather_object(len(names)))
-    fixed = changed = exc = None
-    try:
-        fixed, changed = correct_with(table, seq, meta, t, fix_n=fix_n, **_passes_kw(passes))
-    except Exception as e:                   # noqa: BLE001
-        exc = e
-    finally:
-        table.close()
-    _agree(exc)
-    total = int(parallel.sum_over_ranks(np.array([changed.astype(np.int64).sum()], dtype=np.int64))[0])
-    text = fastx.format_fastq(names, fixed, qual, meta & 0xFFFF)
-    if _bgzf.enabled() and isinstance(out, str):
-        _bgzf.write_text(out if world == 1 else '%s.rank%04d' % (out, rank), text)
-    elif _bgzf.enabled():
-        parallel.in_rank_order(lambda: _bgzf.write_text(out, text))
-    elif isinstance(out, str):
-        with open(out if world == 1 else '%s.rank%04d' % (out, rank), 'w', encoding='latin-1', newline='') as fh:
-            fh.write(text)
-    else:
-        def write():
-            out.write(text)
-            out.flush()
-        parallel.in_rank_order(write)
-    return dict(dict(k=more['k'], min_count=t, hist=hist, changed=changed, reads=reads, changed_bases=total, fix_n=bool(fix_n),
-                     passes=passes), **{key: more[key] for key in ('kmers_from', 'loaded_kmers', 'slots')})
+    info = _correct_shard(table, more['k'], t, hist, reads, out, names, seq, qual, meta, fix_n, passes)
+    return dict(info, **{key: more[key] for key in ('kmers_from', 'loaded_kmers', 'slots')})
 
 
 def _read_shard(path, rank, world):
@@ -1476,7 +1464,6 @@ def correct_fastq_ranks(path, out, k=31, min_count=None, slots=None, local_slots
     kmers_from: nothing is counted and nothing exchanged -- every rank loads the k-mer set (load_set; `slots` is that table's) and
     corrects its own shard against it, so a set counted on one GPU with the prefilter or in partitions serves every rank.  A
     load that fails on any rank is agreed like the other errors here, before a rank corrects anything."""
-    from . import fastx
     from . import parallel
     passes = check_passes(passes)
     kmers_from = check_kmers_from(kmers_from, kmer_min_qual=kmer_min_qual, local_slots=local_slots)
@@ -1515,31 +1502,7 @@ def correct_fastq_ranks(path, out, k=31, min_count=None, slots=None, local_slots
         t = int(min_count)
     if t < 1:
         raise ValueError('min_count must be >= 1, got %d' % t)
-    table = solid_table(owned, t)
-    fixed = changed = exc = None
-    try:
-        fixed, changed = correct_with(table, seq, meta, t, fix_n=fix_n, **_passes_kw(passes))
-    except Exception as e:                   # noqa: BLE001
-        exc = e
-    finally:
-        table.close()
-    _agree(exc)
-    total = int(parallel.sum_over_ranks(np.array([changed.astype(np.int64).sum()], dtype=np.int64))[0])
-    text = fastx.format_fastq(names, fixed, qual, meta & 0xFFFF)
-    if _bgzf.enabled() and isinstance(out, str):
-        _bgzf.write_text(out if world == 1 else '%s.rank%04d' % (out, rank), text)
-    elif _bgzf.enabled():
-        parallel.in_rank_order(lambda: _bgzf.write_text(out, text))
-    elif isinstance(out, str):
-        with open(out if world == 1 else '%s.rank%04d' % (out, rank), 'w', encoding='latin-1', newline='') as fh:
-            fh.write(text)
-    else:
-        def write():
-            out.write(text)
-            out.flush()
-        parallel.in_rank_order(write)
-    info = dict(k=k, min_count=t, hist=hist, changed=changed, reads=reads, changed_bases=total, fix_n=bool(fix_n),
-                passes=passes)
+    info = _correct_shard(solid_table(owned, t), k, t, hist, reads, out, names, seq, qual, meta, fix_n, passes)
     if kmer_min_qual is not None:
         info.update(kmer_min_qual=kmer_min_qual, counted_windows=counted, windows=windows)
     return info

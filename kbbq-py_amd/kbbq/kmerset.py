@@ -2,7 +2,7 @@
 K-mer sets: the result of a k-mer count as a file (`kbbq count -o SET`), and its way back into a table (`--kmers-from SET`).
 
 The five commands that decide errors from k-mers (`correct`, `recalibrate -c`, `bqsr --kmers`, `recalibrate -b --kmers`,
-`benchmark --kmers`) each count their one input and drop the table when they end.  A set is what kmer.count_partitioned keeps of
+`benchmark --kmers`) each count their one input and drop the table when they end.  A set is what kmer.count_rounds keeps of
 a count -- every (canonical key, count) pair with count >= keep -- and the histogram, so that several files can be counted into
 one set, a set counted once can be decided against many times, and a set counted with the prefilter or in partitions on one GPU
 can be loaded by every rank of `correct`.
@@ -324,7 +324,6 @@ def count(fastq=(), alignments=(), output=None, k=31, keep=2, slots=None, prefil
     from . import kmer
     k, keep = int(k), int(keep)
     T = dev._torch()
-    budget = dev.device_budget()
     source = _Inputs(inputs, Q is not None, use_oq, exclude_flags)
     # pass 0: the reads and the windows of all inputs, and the windows a count will insert -- those without a break, with the
     # gate those it leaves -- which go into the header and size the filter and the table
@@ -340,43 +339,21 @@ def count(fastq=(), alignments=(), output=None, k=31, keep=2, slots=None, prefil
             kmer.count_windows(inp.seq, inp.meta, k, windows=word)
     counted = int(word.cpu().numpy()[0])
     del word
-    filt = table = None
-    admitted = None
-    kept = []
-    hist = np.zeros(HIST, dtype=np.int64)
+
+    def read(what, **kw):
+        for inp in source:
+            if inp.reads:
+                plane, meta = _counted_plane(inp, k, Q)
+                (kmer.prefilter_kmers if what == 'prefilter' else kmer.count_kmers)(plane, meta, k=k, **kw)
+                del plane, meta
+    filt, admitted, _, P, slots, _ = kmer.count_plan(read, counted, slots, prefilter, filter_bits, partitions)
     try:
-        if prefilter:
-            filt = kmer.KmerFilter(kmer.filter_words(counted, filter_bits))
-            for inp in source:
-                if inp.reads:
-                    plane, meta = _counted_plane(inp, k, Q)
-                    kmer.prefilter_kmers(plane, meta, k=k, filter=filt)
-            admitted = filt.admitted
-            filt.release_seen()
-        total = admitted if prefilter else counted
-        P = kmer.resolve_partitions(partitions, total, budget) if partitions != 1 else 1
-        if slots is None:
-            slots = kmer.partition_slots(total, P, budget) if P > 1 else kmer.default_slots(total, budget)
-        table = kmer.KmerTable(k, slots)
-        nslots = table.slots
-        for p in range(P):
-            if p:
-                table.clear()
-            for inp in source:
-                if inp.reads:
-                    plane, meta = _counted_plane(inp, k, Q)
-                    kmer.count_kmers(plane, meta, k=k, table=table, filter=filt, parts=P, part=p)
-                    del plane, meta
-            hist += kmer.kmer_histogram(table)
-            keys, counts, _ = kmer.select(table, 1, keep)
-            if int(keys.shape[0]):
-                kept.append((keys, counts))
-            del keys, counts
+        hist, kept, rounds = kmer.count_rounds(lambda table, p: read('count', table=table, filter=filt, parts=P, part=p), k, P,
+                                               slots, keep)
     finally:
         if filt is not None:
             filt.close()
-        if table is not None:
-            table.close()
+    nslots = rounds['slots']
     hist[:min(keep, HIST)] = 0
     n = sum(int(keys.shape[0]) for keys, _ in kept)
     if n != int(hist[min(keep, HIST):].sum()):

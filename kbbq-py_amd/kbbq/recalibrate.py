@@ -431,7 +431,7 @@ def recalibrate_corrected(path, infer_rg=False, gatkreport=None, output=None, k=
     solve, K2 and the writer see the qualities as read; the planes (one n x pitch per band) are released before the apply.
     info['skipped_bases']: the unresolved bases of all reads.  The output is that of `recalibrate -f reads corrected` with the
     model tallied from a reads file whose unresolved bases have quality '!'.
-    partitions: `kbbq correct --partitions` (kmer.count_partitioned): every round counts every band's rows for one partition of the
+    partitions: `kbbq correct --partitions` (kmer.count_block): every round counts every band's rows for one partition of the
     k-mers through a table of `slots` slots (default: kmer.partition_slots within what the budget leaves beside the reads), and
     the table kept until the tally is over is the solid table, against which the bands -- those redone as character rows too --
     are corrected.  The same bytes; info then carries partitions, kept_pairs and solid_slots, and slots is the per-partition table.
@@ -502,7 +502,7 @@ def _recalibrate_corrected(path, infer_rg, gatkreport, output, k, min_count, slo
         resident += sum(int(r.qual.numel()) for r in rows)
     resident += max(int(b['n']) * ((4 if skip else 3) * int(b['pitch']) + 4) for b in single['bands'] if b.get('laid') is not None) \
         if any(b.get('laid') is not None for b in single['bands']) else 0
-    table = filt = None
+    table = None
     read_quals = []                   # skip: (batch, its qualities as read) while the tally plane stands in their place
     gated = [None] * len(rows)        # kmer_min_qual: the plane of each band the prefilter and the count read in the place of its seq
     if kmer_min_qual is not None:
@@ -518,53 +518,28 @@ def _recalibrate_corrected(path, infer_rg, gatkreport, output, k, min_count, slo
     def tally_plane(batch):
         read_quals.append((batch, batch.qual))
         batch.qual, batch.tally_qual = batch.tally_qual, None
+
+    def read(what, **kw):
+        for r, g in zip(rows, gated):
+            (kmer.prefilter_batch if what == 'prefilter' else kmer.count_batch)(r, k, plane=g, **kw)
     try:
         try:
-            if prefilter:
-                with stage('k-mer prefilter', sync=True):
-                    filt = kmer.KmerFilter(kmer.filter_words(windows, filter_bits))
-                    for r, g in zip(rows, gated):
-                        kmer.prefilter_batch(r, k, filter=filt, plane=g)
-                    info['admitted'] = filt.admitted
-                    filt.release_seen()
-            total = info['admitted'] if prefilter else windows
-            room = budget - resident - (filt.nbytes if filt is not None else 0)
-            P = kmer.resolve_partitions(partitions, total, room) if partitions != 1 else 1
-            if kmers_from is not None:
-                with stage('k-mer load', sync=True):
-                    table, hist, t, loaded = kmer.load_set(kmers_from, min_count, slots, k=k, budget=room)
-            elif P > 1:
-                def count_round(tab, p):
-                    for r, g in zip(rows, gated):
-                        kmer.count_batch(r, k, table=tab, filter=filt, parts=P, part=p, plane=g)
-                with stage('k-mer count', sync=True):
-                    table, hist, t, parts_info = kmer.count_partitioned(
-                        count_round, k, P, slots if slots is not None else kmer.partition_slots(total, P, room), min_count, room)
-            else:
-                if slots is None:
-                    slots = kmer.default_slots(total, room)
-                with stage('k-mer count', sync=True):
-                    table = kmer.KmerTable(k, slots)
-                    for r, g in zip(rows, gated):
-                        kmer.count_batch(r, k, table=table, filter=filt, plane=g)
+            table, hist, t, counting = kmer.count_block(read, windows, k, min_count=min_count, slots=slots, prefilter=prefilter,
+                                                        filter_bits=filter_bits, partitions=partitions, kmers_from=kmers_from,
+                                                        room=budget - resident, stage=stage)
         except (ValueError, dev.N.KmerTableFull) as exc:
             if 'slots' not in str(exc):
                 raise
             raise type(exc)('%s -- the k-mer table shares the device budget (KBBQ_DEVICE_BUDGET) with %d bytes of resident reads: '
                             'give --slots, or --prefilter for a table several times smaller' % (exc, resident)) from None
-        if filt is not None:
-            filt.close()
-            filt = None
         del gated[:]                                   # the count is over: everything below reads the bands as read
+        info.update(hist=hist, min_count=t, slots=counting['slots'])
+        if prefilter:
+            info['admitted'] = counting['admitted']
+        if counting.get('partitions', 1) > 1:
+            info.update({key: counting[key] for key in ('partitions', 'table_bytes', 'kept_pairs', 'solid_slots')})
         if kmers_from is not None:
-            info.update(hist=hist, slots=table.slots, kmers_from=loaded['kmers_from'], loaded_kmers=loaded['loaded_kmers'])
-        elif P > 1:
-            info.update(parts_info, hist=hist)
-        else:
-            info['slots'] = table.slots
-            info['hist'] = hist = kmer.kmer_histogram(table)
-            t = int(min_count) if min_count is not None else kmer.solid_threshold(hist)
-        info['min_count'] = t
+            info.update(kmers_from=counting['kmers_from'], loaded_kmers=counting['loaded_kmers'])
         with stage('k-mer correct', sync=True):
             for r in rows:
                 counts = kmer.correct_batch(table, r, t, fix_n=fix_n, **more)
@@ -587,8 +562,6 @@ def _recalibrate_corrected(path, infer_rg, gatkreport, output, k, min_count, slo
     finally:
         for batch, qual in read_quals:                 # the solve, K2 and the writer see the qualities as read; the tally
             batch.qual = qual                          # planes are released here, before the apply
-        if filt is not None:
-            filt.close()
         if table is not None:
             table.close()
     if tables is None:

@@ -132,7 +132,7 @@ def no_device(monkeypatch):
     def boom(*a, **kw):
         raise AssertionError('a device call or a collective was made')
     for mod, names in ((kmer, ('_ctx', 'prefilter_kmers', 'count_kmers', 'flag_errors', 'kmer_histogram', 'KmerTable', 'KmerFilter',
-                               'count_partitioned')),
+                               'count_partitioned', 'count_block', 'count_rounds')),
                        (_device, ('context', 'warm_up', 'device_budget', 'use_native_memory', '_torch')),
                        (bqsr, ('_kmer_tally', '_tally_flag_plane')),
                        (applybqsr, ('_resident_slabs', '_recalibrated_slabs', 'write_alignments')),

@@ -331,7 +331,8 @@ def _no_device(monkeypatch):
         raise AssertionError('a collective was started')
     monkeypatch.setattr(kmer, '_ctx', boom)
     monkeypatch.setattr(_native, 'load', boom)
-    for name in ('prefilter_kmers', 'count_kmers', 'count_batch', 'flag_errors', 'kmer_histogram', 'count_partitioned', 'select', 'merge'):
+    for name in ('prefilter_kmers', 'count_kmers', 'count_batch', 'flag_errors', 'kmer_histogram', 'count_partitioned', 'select', 'merge',
+                 'count_block', 'count_rounds'):
         monkeypatch.setattr(kmer, name, boom)
     for name in ('all_gather_object', 'sum_over_ranks', 'max_over_ranks', 'raise_first_error', 'barrier', 'all_to_all_rows',
                  'allreduce_tables', 'broadcast_object', 'all_gather_rows'):
