@@ -1071,6 +1071,53 @@ int kbbq_bgzf_deflate(kbbq_ctx* ctx, const uint8_t* text, int64_t n, int block_b
                       size_t* out_bytes);
 int kbbq_bgzf_eof(uint8_t* out);
 
+/* ---- BAM output (--bam-out; csrc/sam_host.cpp, csrc/kbbq_bam_out.h, kbbq/_bamout.py) --------------------------------------------
+ * THE STREAM (SAM specification section 4.2) is defined by the SAM text T the same command writes without the option: magic,
+ * the header text as read (every header line + '\n'), the references of the @SQ lines in order; per alignment block_size, refID
+ * / next_refID as indices of the @SQ list ('*' -1, '=' the record's own), pos - 1, l_read_name, mapq, bin = reg2bin(pos, pos +
+ * max(reference span, 1)), n_cigar_op, flag, l_seq, pnext - 1, tlen, QNAME + NUL, CIGAR as u32 (length << 4 | op), SEQ as
+ * nibbles over "=ACMGRSVTWYHKDBN" (lower case like upper case, any other byte 15, the last nibble of an odd length 0), QUAL as
+ * phred bytes (0xFF x l_seq for '*'), the tags in the order of the line: i as the smallest of c C s S i I that holds the value,
+ * A f Z H B as written; with set_oq a record without an OQ tag and with a QUAL gets OQ:Z:<QUAL as read> as its last tag.
+ * (A one-base record whose new QUAL character is '*', quality 9, reads as "no QUAL" in T: its QUAL byte is 0xFF here as well.)
+ * The work is divided: the host, in parallel over records, writes what only the text knows; the device adds SEQ and QUAL from
+ * the planes the apply kernel (kbbq_apply_aligned*_dev) read and wrote, so that neither crosses the bus again.
+ * kbbq_bam_header: the stream's head (magic .. references); out == NULL: *used = the bytes needed.  KBBQ_E_RANGE for an @SQ line
+ * without SN or a decimal LN.
+ * kbbq_bam_check: what BAM cannot hold, of alignments [first, first + n): an RNAME or RNEXT that is not in @SQ, a QNAME longer than
+ * 254 bytes, more than 65535 CIGAR operations, an unknown CIGAR letter, a malformed tag, an integer tag outside int32 / uint32, SEQ
+ * '*' with a QUAL (or a QUAL of another length than SEQ), a FLAG or MAPQ beyond its field -- KBBQ_E_RANGE, the message naming
+ * the lowest such alignment and *bad_index its index; -1 and KBBQ_OK when there is none.
+ * kbbq_bam_layout: one descriptor per record of a slab (alignments [first, first + n), checked before), the size of the slab's
+ * compact skeleton and of its stream.  keep_qual (n bytes, or NULL for none): nonzero for a record the apply passes through --
+ * its QUAL stays as read; a '*' QUAL always does.  Offsets within a slab are 32 bits: KBBQ_E_RANGE for a stream of 2^31 bytes
+ * or more.
+ * kbbq_bam_skeleton: the skeleton the descriptors describe: per record, at skel_off, head_bytes (block_size, the 32 fixed bytes,
+ * QNAME, CIGAR), then -- qual_src == KBBQ_BAM_QUAL_SKELETON -- l_seq bytes of QUAL (as read - 33, or 0xFF), then tail_bytes (the
+ * encoded tags).  No SEQ, no recalibrated QUAL.
+ * kbbq_bam_assemble_dev: the slab's stream in device memory: record r at d_stream + carry + stream_off as   head | SEQ of row r of
+ * d_seq packed | QUAL | tail,   QUAL = row r of d_qplane (characters, as the apply writes them) - 33, or the skeleton's bytes.
+ * Rows are `pitch` bytes apart (a multiple of 16, 16-byte aligned); carry leaves room in front for what the previous slab left
+ * below a whole BGZF block; stream_bytes is what d_stream holds.  Synchronous.  *bad_row = the lowest row with a new quality
+ * below 0 (an output character below 33: SAM text holds it, BAM does not), -1 when there is none: the stream is then not to be
+ * used.  A descriptor that reaches outside the skeleton, the stream or a row writes nothing and is KBBQ_E_ARG.
+ * kbbq_bam_assemble: the same over host memory, by the same per-record code (csrc/kbbq_bam_out.h bo_record).                    */
+#define KBBQ_BAM_QUAL_PLANE    0
+#define KBBQ_BAM_QUAL_SKELETON 1
+typedef struct kbbq_bam_desc {
+    uint32_t skel_off, head_bytes, tail_bytes, l_seq, stream_off, qual_src;
+} kbbq_bam_desc;
+int kbbq_bam_header(const kbbq_sam* f, uint8_t* out, size_t cap, size_t* used);
+int kbbq_bam_check(const kbbq_sam* f, int64_t first, int64_t n, int64_t* bad_index);
+int kbbq_bam_layout(const kbbq_sam* f, int64_t first, int64_t n, int set_oq, const uint8_t* keep_qual, kbbq_bam_desc* desc,
+                    size_t* skel_bytes, size_t* stream_bytes);
+int kbbq_bam_skeleton(const kbbq_sam* f, int64_t first, int64_t n, int set_oq, const kbbq_bam_desc* desc, uint8_t* skel, size_t cap);
+int kbbq_bam_assemble_dev(kbbq_ctx* ctx, const uint8_t* d_skel, size_t skel_bytes, const kbbq_bam_desc* d_desc, int64_t n,
+                          const uint8_t* d_seq, const uint8_t* d_qplane, int pitch, uint8_t* d_stream, size_t carry,
+                          size_t stream_bytes, int64_t* bad_row);
+int kbbq_bam_assemble(const uint8_t* skel, size_t skel_bytes, const kbbq_bam_desc* desc, int64_t n, const uint8_t* seq,
+                      const uint8_t* qplane, int pitch, uint8_t* stream, size_t carry, size_t stream_bytes, int64_t* bad_row);
+
 #ifdef __cplusplus
 }
 #endif

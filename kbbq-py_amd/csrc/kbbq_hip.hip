@@ -14,6 +14,7 @@
 #include "kbbq_kmer.h"
 #include "kbbq_kmer_set.h"
 #include "kbbq_bgzf.h"
+#include "kbbq_bam_out.h"
 #include "../../include/kbbq_hip.h"
 #include "host_threads.h"
 
@@ -73,6 +74,7 @@ struct kbbq_ctx {
     DevScratch bgzf_tok;              // kbbq_bgzf_deflate*: the tokens of the blocks in flight (a workgroup's worth each)
     DevScratch bgzf_off;              // ... the blocks' offsets in the packed output, and its length
     DevScratch bgzf_blocks;           // kbbq_bgzf_deflate (host buffers): a slab's blocks before they are packed
+    DevScratch bam_words;             // kbbq_bam_assemble_dev: the lowest row with a quality below 0, the lowest that does not fit
     // host-buffer entry points (stage_run): two page-locked staging slabs and their device twins, a copy stream and
     // the events that order host copy -> upload -> kernel -> download slab by slab (grown on demand, kept for the next call)
     void* stage_host[2] = {nullptr, nullptr}; void* stage_dev[2] = {nullptr, nullptr}; size_t stage_bytes = 0;
@@ -220,7 +222,7 @@ int kbbq_ctx_destroy(kbbq_ctx* c)
         for (auto& pr : c->ev[w]) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
     if (c->d_status) (void)hipFree(c->d_status);
     if (c->d_stats) (void)hipFree(c->d_stats);
-    for (DevScratch* s : {&c->wgplan, &c->ops4, &c->tally, &c->rowlut, &c->bgzf_tok, &c->bgzf_off, &c->bgzf_blocks})
+    for (DevScratch* s : {&c->wgplan, &c->ops4, &c->tally, &c->rowlut, &c->bgzf_tok, &c->bgzf_off, &c->bgzf_blocks, &c->bam_words})
         if (s->p) (void)hipFree(s->p);
     for (int b = 0; b < 2; ++b) {
         if (c->stage_host[b]) (void)hipHostFree(c->stage_host[b]);
@@ -3169,6 +3171,72 @@ int kbbq_bgzf_deflate(kbbq_ctx* c, const uint8_t* text, int64_t n, int block_byt
     rc = finish((int)((k - 1) & 1));
     if (rc) return stage_drain(c, rc);
     *out_bytes = written;
+    return KBBQ_OK;
+}
+
+} // extern "C"
+
+// ---- BAM output (csrc/kbbq_bam_out.h) -----------------------------------------------------------------------------------------
+static int bam_assemble_args(const char* who, const void* skel, const void* desc, int64_t n, const void* seq, int pitch, const void* stream,
+                             int64_t* bad_row)
+{
+    if (bad_row) *bad_row = -1;
+    if (!bad_row) return fail(KBBQ_E_ARG, "%s: bad_row is NULL", who);
+    if (n < 0 || n > (int64_t)INT_MAX) return fail(KBBQ_E_ARG, "%s: n must be in 0..2^31 - 1", who);
+    if (pitch <= 0 || (pitch & 15) || pitch > 65536) return fail(KBBQ_E_ARG, "%s: pitch must be a positive multiple of 16 (<= 65536), got %d", who, pitch);
+    if (n > 0 && (!skel || !desc || !stream)) return fail(KBBQ_E_ARG, "%s: NULL buffer", who);
+    if ((uintptr_t)seq & 15) return fail(KBBQ_E_ARG, "%s: planes must be 16-byte aligned", who);
+    if ((uintptr_t)desc & 3) return fail(KBBQ_E_ARG, "%s: the descriptors must be 4-byte aligned", who);
+    return KBBQ_OK;
+}
+
+extern "C" {
+
+int kbbq_bam_assemble_dev(kbbq_ctx* c, const uint8_t* d_skel, size_t skel_bytes, const kbbq_bam_desc* d_desc, int64_t n,
+                          const uint8_t* d_seq, const uint8_t* d_qplane, int pitch, uint8_t* d_stream, size_t carry,
+                          size_t stream_bytes, int64_t* bad_row)
+{
+    int rc = bam_assemble_args("kbbq_bam_assemble_dev", d_skel, d_desc, n, d_seq, pitch, d_stream, bad_row);
+    if (rc) return rc;
+    if ((uintptr_t)d_qplane & 15) return fail(KBBQ_E_ARG, "kbbq_bam_assemble_dev: planes must be 16-byte aligned");
+    if (!c) return fail(KBBQ_E_ARG, "kbbq_bam_assemble_dev: ctx is NULL");
+    if (n == 0) return KBBQ_OK;
+    HIPCHK(hipSetDevice(c->device));
+    rc = grow_scratch(c, c->bam_words, 2 * sizeof(u32));
+    if (rc) return rc;
+    HIPCHK(hipMemsetAsync(c->bam_words.p, 0xFF, 2 * sizeof(u32), c->stream));
+    BoParams p{d_skel, d_desc, d_seq, d_qplane, d_stream, (u64)skel_bytes, (u64)carry, (u64)stream_bytes, (u32)n, (u32)pitch,
+               (u32*)c->bam_words.p};
+    const unsigned grid = (unsigned)((n + BO_RECORDS - 1) / BO_RECORDS);
+    hipLaunchKernelGGL(kbo_assemble, dim3(grid), dim3(BO_THREADS), 0, c->stream, p);
+    HIPCHK(hipGetLastError());
+    u32 words[2] = {0, 0};
+    HIPCHK(hipMemcpyAsync(words, c->bam_words.p, sizeof words, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (words[1] != ~0u) return fail(KBBQ_E_ARG, "kbbq_bam_assemble_dev: the descriptor of row %u reaches outside the skeleton, the stream or its row", words[1]);
+    if (words[0] != ~0u) *bad_row = (int64_t)words[0];
+    return KBBQ_OK;
+}
+
+int kbbq_bam_assemble(const uint8_t* skel, size_t skel_bytes, const kbbq_bam_desc* desc, int64_t n, const uint8_t* seq,
+                      const uint8_t* qplane, int pitch, uint8_t* stream, size_t carry, size_t stream_bytes, int64_t* bad_row)
+{
+    int rc = bam_assemble_args("kbbq_bam_assemble", skel, desc, n, nullptr, pitch, stream, bad_row);
+    if (rc) return rc;
+    uint8_t map[256];
+    for (int k = 0; k < 256; ++k) map[k] = bo_seq_code((uint32_t)k);
+    for (int64_t r = 0; r < n; ++r)
+        if (!bo_fits(desc[r], skel_bytes, carry, stream_bytes, (uint32_t)pitch))
+            return fail(KBBQ_E_ARG, "kbbq_bam_assemble: the descriptor of row %lld reaches outside the skeleton, the stream or its row", (long long)r);
+    std::vector<int64_t> lowest(kbbq_threads_for((size_t)n * 256), -1);
+    kbbq_parallel_parts((size_t)n, (unsigned)lowest.size(), [&](unsigned t, size_t lo, size_t hi) {
+        for (size_t r = lo; r < hi; ++r) {
+            const size_t row = r * (size_t)pitch;
+            if (bo_record(desc[r], skel, seq ? seq + row : nullptr, qplane ? qplane + row : nullptr, map, stream + carry, 0, 1) && lowest[t] < 0)
+                lowest[t] = (int64_t)r;
+        }
+    });
+    for (int64_t v : lowest) if (v >= 0 && (*bad_row < 0 || v < *bad_row)) *bad_row = v;
     return KBBQ_OK;
 }
 

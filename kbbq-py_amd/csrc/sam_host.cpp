@@ -557,6 +557,398 @@ int kbbq_sam_render(const kbbq_sam* f, int64_t first, int64_t n, const uint8_t* 
     return KBBQ_OK;
 }
 
+}  // extern "C"
+
+// ---- BAM output: what only the text knows (include/kbbq_hip.h "BAM output"; the device adds SEQ and QUAL: kbbq_bam_out.h) -------
+namespace {
+
+enum BamBad { BAM_FINE = 0, BAM_RNAME, BAM_RNEXT, BAM_QNAME, BAM_NCIGAR, BAM_CIGAR_OP, BAM_TAG, BAM_TAG_INT, BAM_SEQ_QUAL, BAM_QUAL_LEN,
+              BAM_FLAG, BAM_MAPQ };
+
+struct BamRefs {
+    std::vector<std::pair<std::string, int64_t>> sq;     // the @SQ lines in order: SN, LN
+    std::unordered_map<std::string, int> index;
+    std::vector<int> of_contig;                          // the reader's contig number -> refID; -1 for '*', -2 when @SQ lacks it
+};
+
+bool bam_refs(const kbbq_sam* f, BamRefs& R, std::string& err)
+{
+    for (size_t h = 0; h < f->hdr0.size(); ++h) {
+        const uint8_t* p = f->buf + f->hdr0[h]; const uint8_t* e = p + f->hdrlen[h];
+        if (e - p < 3 || memcmp(p, "@SQ", 3) != 0) continue;
+        std::string name; int64_t len = -1; bool has_name = false;
+        const uint8_t* q = (const uint8_t*)memchr(p, '\t', (size_t)(e - p));
+        for (q = q ? q + 1 : e; q < e;) {
+            const uint8_t* t = (const uint8_t*)memchr(q, '\t', (size_t)(e - q));
+            const uint8_t* fe = t ? t : e;
+            if (fe - q >= 3 && q[2] == ':') {
+                if (q[0] == 'S' && q[1] == 'N') { name.assign((const char*)q + 3, (size_t)(fe - q - 3)); has_name = true; }
+                else if (q[0] == 'L' && q[1] == 'N' && !parse_int(q + 3, fe, len)) len = -1;
+            }
+            q = fe + 1;
+        }
+        if (!has_name || len < 0 || len > INT32_MAX) {
+            err = "an @SQ line without SN or a decimal LN: " + std::string((const char*)p, std::min<size_t>(60, (size_t)(e - p)));
+            return false;
+        }
+        R.index[name] = (int)R.sq.size();                 // (a name given twice: its last line's index)
+        R.sq.emplace_back(name, len);
+    }
+    R.of_contig.resize(f->contigs.size());
+    for (size_t c = 0; c < f->contigs.size(); ++c) {
+        if (f->contigs[c] == "*") { R.of_contig[c] = -1; continue; }
+        auto it = R.index.find(f->contigs[c]);
+        R.of_contig[c] = it == R.index.end() ? -2 : it->second;
+    }
+    return true;
+}
+
+struct BamLine { const uint8_t* s[11]; const uint8_t* e[11]; const uint8_t* tags; const uint8_t* end; };
+
+void bam_split(const kbbq_sam* f, int64_t i, BamLine& F)   // (kbbq_sam_open has seen eleven fields in every line)
+{
+    const uint8_t* q = f->buf + f->line0[i]; F.end = q + f->linelen[i];
+    for (int k = 0; k < 11; ++k) {
+        const uint8_t* t = q <= F.end ? (const uint8_t*)memchr(q, '\t', (size_t)(F.end - q)) : nullptr;
+        F.s[k] = std::min(q, F.end); F.e[k] = t ? t : F.end;
+        q = F.e[k] + 1;
+    }
+    F.tags = std::min(q, F.end);
+}
+
+bool bam_float(const uint8_t* p, const uint8_t* e, float& out)      // as Python's float(), then rounded to 32 bits
+{
+    char buf[64];
+    const size_t n = (size_t)(e - p);
+    if (n == 0 || n >= sizeof buf || p[0] == ' ' || p[0] == '\t') return false;
+    memcpy(buf, p, n); buf[n] = 0;
+    char* stop = nullptr;
+    const double v = strtod(buf, &stop);
+    if (stop != buf + n) return false;
+    out = (float)v;
+    return true;
+}
+
+template <typename T> uint8_t* bam_put(uint8_t* o, T v) { memcpy(o, &v, sizeof v); return o + sizeof v; }
+
+// an integer as BAM type `t` (c C s S i I) to o (NULL: nothing is written); false when the type does not hold it
+bool bam_put_int(char t, int64_t v, uint8_t*& o)
+{
+    switch (t) {
+        case 'c': if (v < -128 || v > 127) return false; if (o) o = bam_put(o, (int8_t)v); return true;
+        case 'C': if (v < 0 || v > 255) return false; if (o) o = bam_put(o, (uint8_t)v); return true;
+        case 's': if (v < -32768 || v > 32767) return false; if (o) o = bam_put(o, (int16_t)v); return true;
+        case 'S': if (v < 0 || v > 65535) return false; if (o) o = bam_put(o, (uint16_t)v); return true;
+        case 'i': if (v < INT32_MIN || v > INT32_MAX) return false; if (o) o = bam_put(o, (int32_t)v); return true;
+        case 'I': if (v < 0 || v > (int64_t)UINT32_MAX) return false; if (o) o = bam_put(o, (uint32_t)v); return true;
+        default: return false;
+    }
+}
+
+int bam_int_bytes(char t) { return t == 'c' || t == 'C' ? 1 : t == 's' || t == 'S' ? 2 : 4; }
+
+// one tag field [p, e) as BAM bytes at out (NULL: only counted): the bytes, or -BAM_TAG / -BAM_TAG_INT
+int64_t bam_tag(const uint8_t* p, const uint8_t* e, uint8_t* out)
+{
+    if (e - p < 5 || p[2] != ':' || p[4] != ':') return -BAM_TAG;
+    const uint8_t* v = p + 5;
+    const int64_t vn = e - v;
+    uint8_t* o = out;
+    if (o) { o[0] = p[0]; o[1] = p[1]; o += 2; }
+    switch (p[3]) {
+        case 'A':
+            if (vn != 1) return -BAM_TAG;
+            if (o) { o[0] = 'A'; o[1] = v[0]; }
+            return 4;
+        case 'i': {
+            int64_t x;
+            if (!parse_int(v, e, x)) return -BAM_TAG;
+            for (const char* t = "cCsSiI"; *t; ++t) {
+                uint8_t* none = nullptr;
+                if (!bam_put_int(*t, x, none)) continue;
+                if (o) { *o++ = (uint8_t)*t; bam_put_int(*t, x, o); }
+                return 3 + bam_int_bytes(*t);
+            }
+            return -BAM_TAG_INT;
+        }
+        case 'f': {
+            float x;
+            if (!bam_float(v, e, x)) return -BAM_TAG;
+            if (o) { *o++ = 'f'; bam_put(o, x); }
+            return 7;
+        }
+        case 'Z': case 'H':
+            if (o) { *o++ = p[3]; memcpy(o, v, (size_t)vn); o[vn] = 0; }
+            return 3 + vn + 1;
+        case 'B': {
+            if (vn < 1 || !strchr("cCsSiIf", v[0]) || v[0] == 0 || (vn > 1 && v[1] != ',')) return -BAM_TAG;
+            const char sub = (char)v[0];
+            const int width = sub == 'f' ? 4 : bam_int_bytes(sub);
+            uint8_t* count_at = nullptr;
+            if (o) { *o++ = 'B'; *o++ = (uint8_t)sub; count_at = o; o += 4; }
+            int32_t count = 0;
+            for (const uint8_t* q = v + 2; vn > 1 && q <= e;) {
+                const uint8_t* t = (const uint8_t*)memchr(q, ',', (size_t)(e - q));
+                const uint8_t* fe = t ? t : e;
+                if (sub == 'f') {
+                    float x;
+                    if (!bam_float(q, fe, x)) return -BAM_TAG;
+                    if (o) o = bam_put(o, x);
+                } else {
+                    int64_t x;
+                    uint8_t* none = nullptr;
+                    if (!parse_int(q, fe, x) || !(o ? bam_put_int(sub, x, o) : bam_put_int(sub, x, none))) return -BAM_TAG;
+                }
+                ++count;
+                q = fe + 1;
+            }
+            if (count_at) bam_put(count_at, count);
+            return 3 + 1 + 4 + (int64_t)count * width;
+        }
+        default: return -BAM_TAG;
+    }
+}
+
+// the tags of a line (empty fields skipped) as BAM bytes at out (NULL: only counted): the bytes, or -BAM_TAG / -BAM_TAG_INT
+int64_t bam_tags(const BamLine& F, uint8_t* out)
+{
+    int64_t total = 0;
+    for (const uint8_t* q = F.tags; q < F.end;) {
+        const uint8_t* t = (const uint8_t*)memchr(q, '\t', (size_t)(F.end - q));
+        const uint8_t* te = t ? t : F.end;
+        if (te > q) {
+            const int64_t m = bam_tag(q, te, out ? out + total : nullptr);
+            if (m < 0) return m;
+            total += m;
+        }
+        q = te + 1;
+    }
+    return total;
+}
+
+bool bam_star(const uint8_t* s, const uint8_t* e) { return e - s == 1 && *s == '*'; }
+
+// RNEXT -> next_refID; -2: not in @SQ
+int bam_next_ref(const BamRefs& R, const BamLine& F, int ref)
+{
+    if (bam_star(F.s[6], F.e[6])) return -1;
+    if (F.e[6] - F.s[6] == 1 && *F.s[6] == '=') return ref;
+    if (F.e[6] - F.s[6] == F.e[2] - F.s[2] && !memcmp(F.s[6], F.s[2], (size_t)(F.e[2] - F.s[2]))) return ref;
+    auto it = R.index.find(std::string((const char*)F.s[6], (size_t)(F.e[6] - F.s[6])));
+    return it == R.index.end() ? -2 : it->second;
+}
+
+// what BAM cannot hold of alignment i (the order of include/kbbq_hip.h)
+BamBad bam_record_bad(const kbbq_sam* f, const BamRefs& R, int64_t i)
+{
+    BamLine F;
+    bam_split(f, i, F);
+    const int ref = R.of_contig[(size_t)f->contig[i]];
+    if (ref == -2) return BAM_RNAME;
+    if (bam_next_ref(R, F, ref) == -2) return BAM_RNEXT;
+    if (f->name_len[i] > 254) return BAM_QNAME;
+    if (f->cig_n[i] > 65535) return BAM_NCIGAR;
+    const uint32_t* ops = f->cigar.data() + f->cig_off[i];
+    for (uint32_t k = 0; k < f->cig_n[i]; ++k) if ((ops[k] & 15u) > 8u) return BAM_CIGAR_OP;
+    const int64_t t = bam_tags(F, nullptr);
+    if (t < 0) return (BamBad)-t;
+    const bool seq_star = bam_star(F.s[9], F.e[9]), qual_star = bam_star(F.s[10], F.e[10]);
+    if (seq_star && !qual_star) return BAM_SEQ_QUAL;
+    if (!qual_star && f->qual_len[i] != f->seq_len[i]) return BAM_QUAL_LEN;
+    if (f->flag[i] < 0 || f->flag[i] > 65535) return BAM_FLAG;
+    int64_t mapq;
+    if (!parse_int(F.s[4], F.e[4], mapq) || mapq < 0 || mapq > 255) return BAM_MAPQ;
+    return BAM_FINE;
+}
+
+const char* bam_bad_text(BamBad b)
+{
+    switch (b) {
+        case BAM_RNAME: return "its RNAME is not in @SQ";
+        case BAM_RNEXT: return "its RNEXT is not in @SQ";
+        case BAM_QNAME: return "a QNAME longer than 254 bytes";
+        case BAM_NCIGAR: return "more than 65535 CIGAR operations (no CG tag is written)";
+        case BAM_CIGAR_OP: return "an unknown CIGAR operation";
+        case BAM_TAG: return "a malformed tag";
+        case BAM_TAG_INT: return "an integer tag outside int32 and uint32";
+        case BAM_SEQ_QUAL: return "SEQ is '*' but QUAL is not";
+        case BAM_QUAL_LEN: return "SEQ and QUAL lengths differ";
+        case BAM_FLAG: return "a FLAG outside 0..65535";
+        case BAM_MAPQ: return "a MAPQ outside 0..255";
+        default: return "";
+    }
+}
+
+int bam_reg2bin(int64_t beg, int64_t end)
+{
+    --end;
+    if (beg >> 14 == end >> 14) return (int)(4681 + (beg >> 14));
+    if (beg >> 17 == end >> 17) return (int)(585 + (beg >> 17));
+    if (beg >> 20 == end >> 20) return (int)(73 + (beg >> 20));
+    if (beg >> 23 == end >> 23) return (int)(9 + (beg >> 23));
+    if (beg >> 26 == end >> 26) return (int)(1 + (beg >> 26));
+    return 0;
+}
+
+bool bam_range_ok(const kbbq_sam* f, int64_t first, int64_t n) { return first >= 0 && n >= 0 && first + n <= (int64_t)f->line0.size(); }
+
+int bam_refs_or_error(const kbbq_sam* f, BamRefs& R)
+{
+    std::string err;
+    return bam_refs(f, R, err) ? KBBQ_OK : kbbq_set_error_(KBBQ_E_RANGE, err.c_str());
+}
+
+}  // namespace
+
+extern "C" {
+
+int kbbq_bam_header(const kbbq_sam* f, uint8_t* out, size_t cap, size_t* used)
+{
+    if (!f || !used) return kbbq_set_error_(KBBQ_E_ARG, "kbbq_bam_header: NULL argument");
+    BamRefs R;
+    if (int rc = bam_refs_or_error(f, R)) return rc;
+    size_t text = 0, need = 12;
+    for (size_t h = 0; h < f->hdr0.size(); ++h) text += (size_t)f->hdrlen[h] + 1;
+    for (auto& sq : R.sq) need += 4 + sq.first.size() + 1 + 4;
+    need += text;
+    *used = need;
+    if (!out) return KBBQ_OK;
+    if (cap < need) return kbbq_set_error_(KBBQ_E_ARG, "kbbq_bam_header: output buffer too small");
+    if (text > (size_t)INT32_MAX) return kbbq_set_error_(KBBQ_E_RANGE, "kbbq_bam_header: a header text of 2^31 bytes or more");
+    uint8_t* o = out;
+    memcpy(o, "BAM\1", 4); o += 4;
+    o = bam_put(o, (int32_t)text);
+    for (size_t h = 0; h < f->hdr0.size(); ++h) { memcpy(o, f->buf + f->hdr0[h], f->hdrlen[h]); o += f->hdrlen[h]; *o++ = '\n'; }
+    o = bam_put(o, (int32_t)R.sq.size());
+    for (auto& sq : R.sq) {
+        o = bam_put(o, (int32_t)(sq.first.size() + 1));
+        memcpy(o, sq.first.data(), sq.first.size()); o += sq.first.size(); *o++ = 0;
+        o = bam_put(o, (int32_t)sq.second);
+    }
+    return KBBQ_OK;
+}
+
+int kbbq_bam_check(const kbbq_sam* f, int64_t first, int64_t n, int64_t* bad_index)
+{
+    if (bad_index) *bad_index = -1;
+    if (!f || !bad_index) return kbbq_set_error_(KBBQ_E_ARG, "kbbq_bam_check: NULL argument");
+    if (!bam_range_ok(f, first, n)) return kbbq_set_error_(KBBQ_E_ARG, "kbbq_bam_check: bad range");
+    BamRefs R;
+    if (int rc = bam_refs_or_error(f, R)) return rc;
+    std::atomic<int64_t> lowest(INT64_MAX);
+    par_for(n, threads_for((size_t)n * 256), [&](int64_t lo, int64_t hi) {
+        for (int64_t i = first + lo; i < first + hi && i < lowest.load(std::memory_order_relaxed); ++i)
+            if (bam_record_bad(f, R, i) != BAM_FINE) {
+                int64_t cur = lowest.load();
+                while (i < cur && !lowest.compare_exchange_weak(cur, i)) {}
+                break;
+            }
+    });
+    if (lowest.load() == INT64_MAX) return KBBQ_OK;
+    const int64_t i = lowest.load();
+    *bad_index = i;
+    char msg[256];
+    snprintf(msg, sizeof msg, "alignment %lld cannot be written as BAM: %s", (long long)i, bam_bad_text(bam_record_bad(f, R, i)));
+    return kbbq_set_error_(KBBQ_E_RANGE, msg);
+}
+
+int kbbq_bam_layout(const kbbq_sam* f, int64_t first, int64_t n, int set_oq, const uint8_t* keep_qual, kbbq_bam_desc* desc,
+                    size_t* skel_bytes, size_t* stream_bytes)
+{
+    if (!f || !skel_bytes || !stream_bytes || (n > 0 && !desc)) return kbbq_set_error_(KBBQ_E_ARG, "kbbq_bam_layout: NULL argument");
+    *skel_bytes = *stream_bytes = 0;
+    if (!bam_range_ok(f, first, n)) return kbbq_set_error_(KBBQ_E_ARG, "kbbq_bam_layout: bad range");
+    std::atomic<bool> bad(false);
+    par_for(n, threads_for((size_t)n * 256), [&](int64_t lo, int64_t hi) {
+        for (int64_t r = lo; r < hi; ++r) {
+            const int64_t i = first + r;
+            BamLine F;
+            bam_split(f, i, F);
+            const bool seq_star = bam_star(F.s[9], F.e[9]), qual_star = bam_star(F.s[10], F.e[10]);
+            int64_t tags = bam_tags(F, nullptr);
+            if (tags < 0 || (!qual_star && f->qual_len[i] != f->seq_len[i]) || (seq_star && !qual_star)) { bad = true; tags = 0; }
+            if (set_oq && !f->oq_len[i] && !qual_star) tags += 3 + (int64_t)f->qual_len[i] + 1;
+            kbbq_bam_desc& d = desc[r];
+            d.skel_off = d.stream_off = 0;
+            d.head_bytes = 36u + f->name_len[i] + 1u + 4u * f->cig_n[i];
+            d.tail_bytes = (uint32_t)std::min<int64_t>(tags, UINT32_MAX);
+            d.l_seq = seq_star ? 0u : f->seq_len[i];
+            d.qual_src = (qual_star || (keep_qual && keep_qual[r])) ? KBBQ_BAM_QUAL_SKELETON : KBBQ_BAM_QUAL_PLANE;
+        }
+    });
+    if (bad) return kbbq_set_error_(KBBQ_E_RANGE, "kbbq_bam_layout: a record BAM cannot hold (kbbq_bam_check names it)");
+    uint64_t skel = 0, stream = 0;
+    for (int64_t r = 0; r < n; ++r) {
+        kbbq_bam_desc& d = desc[r];
+        if (stream >= ((uint64_t)1 << 31)) break;
+        d.skel_off = (uint32_t)skel; d.stream_off = (uint32_t)stream;
+        skel += (uint64_t)d.head_bytes + (d.qual_src == KBBQ_BAM_QUAL_SKELETON ? d.l_seq : 0u) + d.tail_bytes;
+        stream += (uint64_t)d.head_bytes + ((uint64_t)d.l_seq + 1) / 2 + d.l_seq + d.tail_bytes;
+    }
+    if (stream >= ((uint64_t)1 << 31))
+        return kbbq_set_error_(KBBQ_E_RANGE, "kbbq_bam_layout: the stream of a slab must stay below 2^31 bytes (offsets are 32 bits): fewer records per slab");
+    *skel_bytes = (size_t)skel; *stream_bytes = (size_t)stream;
+    return KBBQ_OK;
+}
+
+int kbbq_bam_skeleton(const kbbq_sam* f, int64_t first, int64_t n, int set_oq, const kbbq_bam_desc* desc, uint8_t* skel, size_t cap)
+{
+    if (!f || (n > 0 && (!desc || !skel))) return kbbq_set_error_(KBBQ_E_ARG, "kbbq_bam_skeleton: NULL argument");
+    if (!bam_range_ok(f, first, n)) return kbbq_set_error_(KBBQ_E_ARG, "kbbq_bam_skeleton: bad range");
+    BamRefs R;
+    if (int rc = bam_refs_or_error(f, R)) return rc;
+    std::atomic<bool> bad(false);
+    par_for(n, threads_for((size_t)n * 256), [&](int64_t lo, int64_t hi) {
+        for (int64_t r = lo; r < hi; ++r) {
+            const int64_t i = first + r;
+            const kbbq_bam_desc& d = desc[r];
+            BamLine F;
+            bam_split(f, i, F);
+            const bool qual_star = bam_star(F.s[10], F.e[10]), adds_oq = set_oq && !f->oq_len[i] && !qual_star;
+            const bool keeps = d.qual_src == KBBQ_BAM_QUAL_SKELETON;
+            const int64_t tags = bam_tags(F, nullptr);
+            const int ref = R.of_contig[(size_t)f->contig[i]], next = bam_next_ref(R, F, ref);
+            int64_t mapq = 0;
+            // the descriptor is this record's, and inside the buffer?
+            if (tags < 0 || ref == -2 || next == -2 || !parse_int(F.s[4], F.e[4], mapq)
+                || d.head_bytes != 36u + f->name_len[i] + 1u + 4u * f->cig_n[i]
+                || d.tail_bytes != (uint64_t)tags + (adds_oq ? 3 + (uint64_t)f->qual_len[i] + 1 : 0)
+                || d.l_seq != (bam_star(F.s[9], F.e[9]) ? 0u : f->seq_len[i]) || (qual_star && !keeps)
+                || (keeps && !qual_star && f->qual_len[i] != d.l_seq) || f->name_len[i] > 254
+                || (uint64_t)d.skel_off + d.head_bytes + (keeps ? d.l_seq : 0u) + d.tail_bytes > cap) { bad = true; continue; }
+            uint8_t* o = skel + d.skel_off;
+            const uint32_t L = d.l_seq;
+            o = bam_put(o, (int32_t)(d.head_bytes - 4 + (L + 1) / 2 + L + d.tail_bytes));
+            o = bam_put(o, (int32_t)ref);
+            o = bam_put(o, (int32_t)f->pos[i]);
+            *o++ = (uint8_t)(f->name_len[i] + 1);
+            *o++ = (uint8_t)mapq;
+            o = bam_put(o, (uint16_t)bam_reg2bin(f->pos[i], f->pos[i] + std::max<int64_t>(f->ref_span[i], 1)));
+            o = bam_put(o, (uint16_t)f->cig_n[i]);
+            o = bam_put(o, (uint16_t)f->flag[i]);
+            o = bam_put(o, (uint32_t)L);
+            o = bam_put(o, (int32_t)next);
+            o = bam_put(o, (int32_t)f->pnext[i]);
+            o = bam_put(o, (int32_t)f->tlen[i]);
+            memcpy(o, F.s[0], f->name_len[i]); o += f->name_len[i]; *o++ = 0;
+            if (f->cig_n[i]) { memcpy(o, f->cigar.data() + f->cig_off[i], 4u * f->cig_n[i]); o += 4u * f->cig_n[i]; }
+            if (keeps) {
+                if (qual_star) memset(o, 0xFF, L);
+                else for (uint32_t k = 0; k < L; ++k) o[k] = (uint8_t)(F.s[10][k] - 33);
+                o += L;
+            }
+            o += bam_tags(F, o);
+            if (adds_oq) {
+                memcpy(o, "OQZ", 3); o += 3;
+                memcpy(o, F.s[10], f->qual_len[i]); o += f->qual_len[i];
+                *o++ = 0;
+            }
+        }
+    });
+    if (bad) return kbbq_set_error_(KBBQ_E_ARG, "kbbq_bam_skeleton: the descriptors are not kbbq_bam_layout's of these records, or the buffer is too small");
+    return KBBQ_OK;
+}
+
 // benchmark.py:102-124: FASTQ reads are matched to alignments by name -- the FASTQ name up to its first '_'
 // against QNAME + "/1" | "/2" (second-in-pair flag); of several alignments with one name the LAST wins (a dict
 // in the reference).  idx[i] = alignment of FASTQ read i, or -1 (the reference's KeyError).

@@ -1,0 +1,271 @@
+"""
+`--bam-out`: the alignments `applybqsr` and `recalibrate -b --kmers` write, as a BAM file whose records are assembled and
+deflated on the GPU (include/kbbq_hip.h "BAM output", csrc/kbbq_bam_out.h, csrc/sam_host.cpp).
+
+The uncompressed stream is defined by the SAM text the same command writes without the option (SAM specification 4.2; the
+tests' bamwriter.sam_to_bam_bytes of that text).  The work is divided: the host writes, in parallel over records, what only
+the text knows -- a compact skeleton of fixed fields, QNAME, CIGAR and encoded tags, and a descriptor per record -- and only
+those go up; the device adds SEQ, packed from the character plane the apply kernel read, and QUAL, from the plane it wrote, at
+every record's offset of the stream (kbbq_bam_assemble_dev), so neither plane crosses the bus again.
+
+BamWriter(raw) owns the device stream buffer, the carry and the binary sink.  The stream is cut every BLOCK = 65280 bytes
+whatever the record and slab boundaries are: after a slab is assembled behind the carry, the whole blocks are deflated where
+they lie (kbbq_bgzf_deflate_dev, KBBQ_BGZF_SLAB_BLOCKS blocks a call) and only compressed bytes come back, through a
+page-locked buffer as in kbbq/_bgzf.py; what is left below a block is copied, device to device, to the front of the buffer and
+waits for the next slab; close() deflates it and writes the 28-byte EOF block.  The file is a function of the stream alone.
+A new quality below 0 fits SAM text but not BAM: the assemble kernel leaves the lowest such row in a word that is read after
+every slab, before any byte of the slab reaches the sink -- ValueError with .read_index.
+
+h2d_bytes (header, skeletons, descriptors), d2h_bytes (compressed blocks), stream_bytes and file_bytes count what moved, as
+BgzfWriter counts text_bytes / file_bytes.  deflate=: a function text -> BGZF blocks in the place of the GPU; the planes are then
+NumPy arrays and the records are assembled by the host twin (kbbq_bam_assemble) -- the tests' stand-in.
+"""
+import ctypes
+import io
+
+import numpy as np
+
+from ._bgzf import BLOCK, EOF, slab_blocks
+
+
+class _HostEngine:
+    """Plain memory, kbbq_bam_assemble and a function text -> BGZF blocks."""
+
+    def __init__(self, deflate):
+        self.fn = deflate
+
+    def buffer(self, nbytes):
+        return np.empty(int(nbytes), dtype=np.uint8)
+
+    def staging(self, nbytes):
+        return np.empty(int(nbytes), dtype=np.uint8)
+
+    def upload(self, stage, nbytes):
+        return stage
+
+    def put(self, buf, at, data):
+        buf[at:at + len(data)] = data
+
+    def move(self, dst, src, lo, n):
+        dst[:n] = src[lo:lo + n].copy()
+
+    def assemble(self, d_stage, desc_bytes, skel_bytes, n, seq, qplane, pitch, buf, carry):
+        from . import _native as N
+        bad = ctypes.c_int64(-1)
+        N.check(N.load().kbbq_bam_assemble(N.ptr(d_stage[desc_bytes:]), skel_bytes, N.ptr(d_stage), n, N.ptr(seq), N.ptr(qplane), pitch,
+                                           N.ptr(buf), carry, buf.nbytes, ctypes.byref(bad)))
+        return int(bad.value)
+
+    def deflate(self, buf, lo, n):
+        return self.fn(memoryview(buf)[lo:lo + n])
+
+    def close(self):
+        pass
+
+
+class _GpuEngine:
+    """Device memory of the backend the process uses (kbbq/_device.py), kbbq_bam_assemble_dev and kbbq_bgzf_deflate_dev."""
+
+    def __init__(self):
+        from . import _device as dev
+        self.dev, self.t = dev, dev._torch()
+        self.device = self.t.cuda.current_device()
+        self.piece = slab_blocks() * BLOCK
+        self.scratch = self.d_stage = None
+
+    def buffer(self, nbytes):
+        return self.t.empty(int(nbytes), dtype=self.t.uint8, device='cuda')
+
+    def staging(self, nbytes):
+        return self.dev.pinned('bamout', 'stage', int(nbytes)).numpy()
+
+    def upload(self, stage, nbytes):
+        pin = self.dev.pinned('bamout', 'stage', nbytes)
+        if self.d_stage is None or self.d_stage.shape[0] < nbytes:
+            self.d_stage = None
+            self.d_stage = self.buffer(nbytes + nbytes // 8)
+        self.d_stage[:nbytes].copy_(pin[:nbytes], non_blocking=True)
+        return self.d_stage
+
+    def put(self, buf, at, data):
+        buf[at:at + len(data)].copy_(self.t.from_numpy(np.ascontiguousarray(data)))
+
+    def move(self, dst, src, lo, n):
+        dst[:n].copy_(src[lo:lo + n])
+
+    def assemble(self, d_stage, desc_bytes, skel_bytes, n, seq, qplane, pitch, buf, carry):
+        N = self.dev.N
+        ctx = self.dev.context(self.device)
+        bad = ctypes.c_int64(-1)
+        N.check(N.load().kbbq_bam_assemble_dev(ctx.handle, N.ptr(d_stage.data_ptr() + desc_bytes), skel_bytes, N.ptr(d_stage), n,
+                                               N.ptr(seq), N.ptr(qplane), pitch, N.ptr(buf), carry, buf.shape[0], ctypes.byref(bad)))
+        return int(bad.value)
+
+    def deflate(self, buf, lo, n):
+        N, t = self.dev.N, self.t
+        ctx = self.dev.context(self.device)
+        lib = N.load()
+        if self.scratch is None:
+            blocks = self.piece // BLOCK
+            bound = int(lib.kbbq_bgzf_bound(self.piece, BLOCK))
+            self.scratch = (self.buffer(blocks * N.BGZF_SLOT), self.buffer(4 * blocks), self.buffer(bound),
+                            self.dev.pinned('bamout', 'out', bound))
+        d_blocks, d_sizes, d_packed, out = self.scratch
+        total = ctypes.c_size_t(0)
+        N.check(lib.kbbq_bgzf_deflate_dev(ctx.handle, N.ptr(buf.data_ptr() + lo), n, BLOCK, N.ptr(d_blocks), N.ptr(d_sizes),
+                                          N.ptr(d_packed), ctypes.byref(total)))
+        out[:total.value].copy_(d_packed[:total.value])
+        return memoryview(out.numpy())[:total.value]
+
+    def close(self):
+        self.scratch = self.d_stage = None
+        self.dev.release_pinned('bamout')
+
+
+class BamWriter:
+    """header(bam), records(...) slab by slab, close() over the binary sink `raw` (see the module's text).  A context manager:
+    leaving it on an exception closes the sink without the carry and without the EOF block.  close_raw: close() closes `raw` too."""
+
+    def __init__(self, raw, close_raw=False, deflate=None):
+        if raw is None or isinstance(raw, io.TextIOBase) or not hasattr(raw, 'write'):
+            raise ValueError('--bam-out writes bytes: the sink must be a binary file (a text-only stdout cannot take it)')
+        self._raw, self._close_raw = raw, close_raw
+        self._engine = _HostEngine(deflate) if deflate is not None else _GpuEngine()
+        self._piece = slab_blocks() * BLOCK
+        self._buf, self._carry = None, 0
+        self.closed = False
+        self.h2d_bytes = self.d2h_bytes = self.stream_bytes = self.file_bytes = 0
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, kind, exc, tb):
+        if kind is None:
+            self.close()
+        else:
+            self._finish()
+
+    # ---- the stream buffer: [carry | the slab being assembled]
+    def _room(self, need):
+        """A buffer of at least `need` bytes with the carry at its front."""
+        if self._buf is not None and self._buf.shape[0] >= need:
+            return
+        new = self._engine.buffer((need + need // 8 + 15) // 16 * 16)
+        if self._carry:
+            self._engine.move(new, self._buf, 0, self._carry)
+        self._buf = new
+
+    def _drain(self, total, last=False):
+        """Bytes [0, total) of the buffer: the whole blocks (last: all of it) deflated and written, the rest carried."""
+        whole = total if last else total // BLOCK * BLOCK
+        for lo in range(0, whole, self._piece):
+            packed = self._engine.deflate(self._buf, lo, min(self._piece, whole - lo))
+            self._raw.write(packed)
+            self.d2h_bytes += len(packed)
+            self.file_bytes += len(packed)
+        if whole and total > whole:
+            self._engine.move(self._buf, self._buf, whole, total - whole)
+        self._carry = total - whole
+
+    def _open(self):
+        if self.closed:
+            raise ValueError('write to a closed BamWriter')
+
+    # ---- the file
+    def header(self, bam):
+        """The stream's head of an aln.AlignmentFile: magic, the header text as read, the references of its @SQ lines."""
+        from . import _native as N
+        self._open()
+        lib, native = N.load(), bam.batch()._native
+        need = ctypes.c_size_t(0)
+        N.check(lib.kbbq_bam_header(native, None, 0, ctypes.byref(need)))
+        head = np.empty(need.value, dtype=np.uint8)
+        N.check(lib.kbbq_bam_header(native, N.ptr(head), head.nbytes, ctypes.byref(need)))
+        self._room(self._carry + head.nbytes)
+        self._engine.put(self._buf, self._carry, head)
+        self.h2d_bytes += head.nbytes
+        self.stream_bytes += head.nbytes
+        self._drain(self._carry + head.nbytes)
+
+    def records(self, batch, first, n, set_oq, keep_qual, seq, qplane, pitch):
+        """Alignments [first, first + n) of the reader's batch.  seq, qplane: their rows of the SEQ character plane and of the
+        apply's output plane, [n, pitch], where the engine works (device tensors; NumPy arrays with deflate=); keep_qual: a
+        bool array, true for a record whose QUAL stays as read (a '*' QUAL always does).  ValueError with .read_index for a new
+        quality below 0, before any byte of these records reaches the sink."""
+        from . import _native as N
+        self._open()
+        if n <= 0:
+            return
+        lib = N.load()
+        desc = np.empty((n, N.BAM_DESC_WORDS), dtype=np.uint32)
+        keep = None if keep_qual is None else np.ascontiguousarray(keep_qual, dtype=np.uint8)
+        skel_bytes, stream_bytes = ctypes.c_size_t(0), ctypes.c_size_t(0)
+        N.check(lib.kbbq_bam_layout(batch._native, first, n, int(bool(set_oq)), N.ptr(keep), N.ptr(desc), ctypes.byref(skel_bytes),
+                                    ctypes.byref(stream_bytes)))
+        desc_bytes = (desc.nbytes + 15) // 16 * 16
+        nbytes = desc_bytes + skel_bytes.value
+        stage = self._engine.staging(nbytes)
+        stage[:desc.nbytes] = desc.reshape(-1).view(np.uint8)
+        N.check(lib.kbbq_bam_skeleton(batch._native, first, n, int(bool(set_oq)), N.ptr(desc), N.ptr(stage[desc_bytes:]), skel_bytes.value))
+        d_stage = self._engine.upload(stage, nbytes)
+        self.h2d_bytes += nbytes
+        total = self._carry + stream_bytes.value
+        self._room(total)
+        bad = self._engine.assemble(d_stage, desc_bytes, skel_bytes.value, n, seq, qplane, pitch, self._buf, self._carry)
+        if bad >= 0:
+            exc = ValueError('alignment %d: a new quality below 0 cannot be written as BAM (SAM text holds it: without --bam-out)'
+                             % (first + bad))
+            exc.read_index = first + bad
+            raise exc
+        self.stream_bytes += stream_bytes.value
+        self._drain(total)
+
+    def _finish(self):
+        self.closed = True
+        self._buf = None
+        self._engine.close()
+        if self._close_raw:
+            self._raw.close()
+
+    def close(self):
+        if self.closed:
+            return
+        try:
+            if self._carry:
+                self._drain(self._carry, last=True)
+            self._raw.write(EOF)
+            self.file_bytes += len(EOF)
+            self._raw.flush()
+        finally:
+            self._finish()
+
+
+def check(bam, lo=0, hi=None):
+    """What BAM cannot hold of alignments [lo, hi) of an aln.AlignmentFile (kbbq_bam_check): ValueError naming the first such
+    alignment, with .read_index -- to be called before the output file is created."""
+    from . import _native as N
+    hi = len(bam) if hi is None else hi
+    bad = ctypes.c_int64(-1)
+    try:
+        N.check(N.load().kbbq_bam_check(bam.batch()._native, lo, hi - lo, ctypes.byref(bad)))
+    except ValueError as exc:
+        if bad.value >= 0:
+            exc.read_index = int(bad.value)
+        raise
+
+
+def open_sink(path):
+    """A BamWriter over the binary file `path`."""
+    raw = open(path, 'wb')
+    try:
+        return BamWriter(raw, close_raw=True)
+    except BaseException:
+        raw.close()
+        raise
+
+
+def stdout_sink():
+    """A BamWriter over the process's binary stdout (stdout itself stays open)."""
+    import sys
+    sys.stdout.flush()
+    return BamWriter(getattr(sys.stdout, 'buffer', None))

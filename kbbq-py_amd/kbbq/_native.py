@@ -31,6 +31,8 @@ KMER_MAX_PASSES = 8                   # the `passes` of the kbbq_kmer_*_passes* 
 KMER_FLAG_UNRESOLVED = 2              # ... and of kbbq_kmer_flag_ex_dev: unresolved bases become 2 in the flag plane
 CONFUSION_MAX_BASES = (1 << 32) - 1   # KBBQ_CONFUSION_MAX_BASES: nreads * pitch of one kbbq_flag_confusion_dev call
 BGZF_BLOCK_MAX, BGZF_SLOT, BGZF_EOF_BYTES = 65280, 65536, 28   # KBBQ_BGZF_*: text of a block, a block's slot before packing, the EOF block
+BAM_QUAL_PLANE, BAM_QUAL_SKELETON = 0, 1   # KBBQ_BAM_QUAL_*: kbbq_bam_desc.qual_src
+BAM_DESC_WORDS = 6                         # kbbq_bam_desc: skel_off, head_bytes, tail_bytes, l_seq, stream_off, qual_src (uint32 each)
 
 NQ = 43
 NDINUC = 16
@@ -228,6 +230,12 @@ PROTOTYPES = {
     'kbbq_bgzf_deflate_dev': (_i, [_vp, _vp, _i64, _i, _vp, _vp, _vp, _c.POINTER(_sz)]),
     'kbbq_bgzf_deflate': (_i, [_vp, _vp, _i64, _i, _vp, _sz, _c.POINTER(_sz)]),
     'kbbq_bgzf_eof': (_i, [_vp]),
+    'kbbq_bam_header': (_i, [_vp, _vp, _sz, _c.POINTER(_sz)]),
+    'kbbq_bam_check': (_i, [_vp, _i64, _i64, _c.POINTER(_i64)]),
+    'kbbq_bam_layout': (_i, [_vp, _i64, _i64, _i, _vp, _vp, _c.POINTER(_sz), _c.POINTER(_sz)]),
+    'kbbq_bam_skeleton': (_i, [_vp, _i64, _i64, _i, _vp, _vp, _sz]),
+    'kbbq_bam_assemble_dev': (_i, [_vp, _vp, _sz, _vp, _i64, _vp, _vp, _i, _vp, _sz, _sz, _c.POINTER(_i64)]),
+    'kbbq_bam_assemble': (_i, [_vp, _sz, _vp, _i64, _vp, _vp, _i, _vp, _sz, _sz, _c.POINTER(_i64)]),
 }
 
 

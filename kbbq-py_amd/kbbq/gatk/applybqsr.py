@@ -322,11 +322,13 @@ def _recalibrated_slabs(bam, model, rg_to_int, use_oq, minscore, lo, hi, quantiz
             raise stop
 
 
-def _resident_slabs(bam, model, rg_to_int, use_oq, minscore, lo, hi, resident, quantize=None):
+def _resident_slabs(bam, model, rg_to_int, use_oq, minscore, lo, hi, resident, quantize=None, device=False):
     """_recalibrated_slabs for alignments whose planes are on the device already (`resident`: gatk.bqsr._kmer_tally's -- seq and
     source [n, pitch], and oq, the context plane, where records carry OQ tags and the source is QUAL): the same slabs, row
     words, pass-through, errors and error order; kbbq_apply_aligned_dev reads the planes where they lie and only the output
-    plane of a slab crosses the bus.  quantize: as _recalibrated_slabs (kbbq_apply_aligned_q_dev)."""
+    plane of a slab crosses the bus.  quantize: as _recalibrated_slabs (kbbq_apply_aligned_q_dev).
+    device: the output plane stays where the kernel wrote it -- (first, count, device output plane, None, the slab's rows of the
+    device SEQ plane, pass-through mask); a pass-through record's row of the plane is not its QUAL (write_alignments_bam)."""
     from .. import _device as dev
     from .. import _native as N
     mode, blob, R, Qt, S2 = model
@@ -367,6 +369,11 @@ def _resident_slabs(bam, model, rg_to_int, use_oq, minscore, lo, hi, resident, q
             except Exception as exc:
                 exc.read_index = first + max(getattr(exc, 'read_index', 0), 0)
                 raise
+            if device:
+                yield first, m, d_out, None, d_seq[first:first + m], passthrough
+                if stop is not None:
+                    raise stop
+                continue
             out = d_out.cpu().numpy()
             if passthrough.any():
                 out[passthrough] = b.plane(1, pitch, first, m)[passthrough]
@@ -374,6 +381,32 @@ def _resident_slabs(bam, model, rg_to_int, use_oq, minscore, lo, hi, resident, q
             yield first, m, out, lens
         if stop is not None:
             raise stop
+
+
+class _Window:
+    """Rows [first, first + len) of a whole-file plane on the device, sliced by the file's row numbers as _resident_slabs does."""
+
+    def __init__(self, rows, first):
+        self.rows, self.first = rows, first
+
+    def __getitem__(self, key):
+        return self.rows[key.start - self.first:key.stop - self.first]
+
+
+def _uploaded_slabs(bam, model, rg_to_int, use_oq, minscore, lo, hi, quantize=None):
+    """_resident_slabs(device=True) for alignments whose planes are not on the device: the planes kbbq_apply_aligned would stage
+    go up slab by slab -- the same bytes -- and stay there with the output plane, for the BAM assemble kernel to read."""
+    from .. import _device as dev
+    T = dev._torch()
+    b = bam.batch()
+    pitch = max(16, (int(b.maxlen) + 15) // 16 * 16)
+    for first in range(lo, hi, _ROWS):
+        m = min(_ROWS, hi - first)
+        up = lambda which: _Window(T.from_numpy(b.plane(which, pitch, first, m)).cuda(), first)     # noqa: E731
+        resident = dict(pitch=pitch, seq=up(0), source=up(2 if use_oq else 1))
+        if not use_oq and bool((b.oq_len[first:first + m] >= 0).any()):
+            resident['oq'] = up(2)
+        yield from _resident_slabs(bam, model, rg_to_int, use_oq, minscore, first, first + m, resident, quantize, device=True)
 
 
 def recalibrate_alignments(bam, meanq, rgdq, qdq, posdq, dndq, rg_to_int, use_oq=True, minscore=6, quantize=None):
@@ -433,6 +466,40 @@ def write_alignments(bam, meanq, rgdq, qdq, posdq, dndq, rg_to_int, sink, use_oq
     LAST_RUN.update(mode='lut' if model[0] == 0 else 'f64', alignments=hi - lo)
 
 
+def write_alignments_bam(bam, meanq, rgdq, qdq, posdq, dndq, rg_to_int, writer, use_oq=False, set_oq=False, minscore=6,
+                         rows=None, header=True, resident=None, quantize=None):
+    """write_alignments as a BAM stream into a kbbq._bamout.BamWriter: the stream is the one the SAM text of write_alignments
+    defines (include/kbbq_hip.h "BAM output").  The output plane of the apply and the SEQ plane it read stay on the device
+    (_resident_slabs / _uploaded_slabs, device=True) and the writer's assemble kernel reads them there; what goes up beyond the
+    apply's own planes is the records' skeleton and descriptors, what comes back is compressed blocks.  The records must have
+    passed kbbq._bamout.check."""
+    quantize = _check_qmap(quantize)
+    lo, hi = (0, len(bam)) if rows is None else rows
+    model = _model(meanq, rgdq, qdq, posdq, dndq, minscore)
+    if header:
+        writer.header(bam)
+    slabs = (_uploaded_slabs(bam, model, rg_to_int, use_oq, minscore, lo, hi, quantize) if resident is None else
+             _resident_slabs(bam, model, rg_to_int, use_oq, minscore, lo, hi, resident, quantize, device=True))
+    for first, m, d_out, _, d_seq, passthrough in slabs:
+        writer.records(bam.batch(), first, m, set_oq, passthrough, d_seq, d_out, int(d_out.shape[1]))
+    LAST_RUN.clear()
+    LAST_RUN.update(mode='lut' if model[0] == 0 else 'f64', alignments=hi - lo)
+
+
+def write_bam_file(bam, output, write):
+    """The BAM file of a command: kbbq._bamout.check (ValueError before the file exists), then write(writer) into a BamWriter
+    over `output`, or over stdout for None.  LAST_RUN['bam_out']: the closed writer's counters."""
+    from .. import _bamout
+    _bamout.check(bam)
+    with (_bamout.stdout_sink() if output is None else _bamout.open_sink(output)) as writer:
+        write(writer)
+    LAST_RUN['bam_out'] = {key: getattr(writer, key) for key in ('h2d_bytes', 'd2h_bytes', 'stream_bytes', 'file_bytes')}
+
+
+BAM_OUT_RANKS = ('--bam-out does not run across ranks in this version (one BAM file is one stream of blocks): on one GPU, or '
+                 'without the option -- the SAM text path runs under ranks, every rank writing OUTPUT.rankNNNN')
+
+
 def report_model(bam, report_path):
     """A stored GATK report -> (meanq, rgdq, qdq, posdq, dndq, rg_to_int) for the read groups of bam's header (reference
     tests/test_gatk_applybqsr.py:123-134: the report names read groups by their PU)."""
@@ -449,19 +516,33 @@ def _report_model(bam, report):
 
 
 @_bgzf.option
-def apply_report(bam, report_path, use_oq=False, set_oq=False, output=None, quantize=None):
+def apply_report(bam, report_path, use_oq=False, set_oq=False, output=None, quantize=None, bam_out=False):
     """`kbbq applybqsr`: report -> model (table_to_vectors, get_delta_qs on the device) -> kbbq_apply_aligned -> SAM text, to
     `output` or stdout.  Under torch.distributed.run every rank takes parallel.shard_range of the alignments and writes
     output.rankNNNN, the header in rank 0's file only, so that the files concatenated in rank order are the single-process
-    output.  BAM output is not written: an output name ending in .bam is refused.  quantize: the 256-byte map of quantize_map
-    (--static-quantized-quals); per byte, so the rank files concatenated stay the one-process bytes."""
+    output.  Without bam_out an output name ending in .bam is refused.  quantize: the 256-byte map of quantize_map
+    (--static-quantized-quals); per byte, so the rank files concatenated stay the one-process bytes.
+    bam_out (--bam-out): the same records as a BAM file, whatever its name (write_alignments_bam); one process only, not with
+    bgzf; what BAM cannot hold is a ValueError before the file is created (kbbq._bamout.check)."""
     import sys
     from .. import aln, parallel
     quantize = _check_qmap(quantize)
-    if output is not None and str(output).lower().endswith('.bam'):
+    if bam_out:
+        if _bgzf.enabled():
+            raise ValueError('--bam-out: not with --bgzf (a BAM file is a BGZF file already)')
+        if parallel.launched_from_env() or parallel.world_rank()[0] > 1:
+            raise ValueError(BAM_OUT_RANKS)
+    elif output is not None and str(output).lower().endswith('.bam'):
         raise ValueError('applybqsr writes SAM text; BAM output (%s) is not supported' % output)
     if not isinstance(bam, aln.AlignmentFile):
         bam = aln.AlignmentFile(bam)
+    if bam_out:
+        *model, rg_to_int = report_model(bam, report_path)
+        kw = dict(use_oq=use_oq, set_oq=set_oq)
+        if quantize is not None:
+            kw['quantize'] = quantize
+        write_bam_file(bam, output, lambda writer: write_alignments_bam(bam, *model, rg_to_int, writer, **kw))
+        return
     world, rank = parallel.world_rank()
     if world > 1 and output is None:
         raise ValueError('several ranks need -o: every rank writes OUTPUT.rankNNNN')

@@ -149,6 +149,24 @@ def _bgzf_kw(args):
     return {'bgzf': True} if getattr(args, 'bgzf', False) else {}
 
 
+_BAM_OUT_HELP = ('Write the output (-o, or stdout) as a BAM file, whatever its name: the records are assembled and deflated on the '
+                 'GPU, and the uncompressed stream is the one the SAM text without the option defines.  One GPU; not with --bgzf.  '
+                 'Without the option the output is SAM text and a .bam name is refused.')
+
+
+def _bam_out_kw(args):
+    """{'bam_out': True} with --bam-out, else {}: without the option every call is the one it was."""
+    return {'bam_out': True} if getattr(args, 'bam_out', False) else {}
+
+
+def _refuse_bam_out_ranks(args):
+    """--bam-out under a launcher: refused before the process group is joined."""
+    from . import parallel
+    if getattr(args, 'bam_out', False) and parallel.launched_from_env():
+        from .gatk.applybqsr import BAM_OUT_RANKS
+        raise ValueError(BAM_OUT_RANKS)
+
+
 def _recalibrate_bam_kmers(args):
     """`recalibrate -b ALN --kmers`: `bqsr --kmers` and `applybqsr` in one run (kbbq/recalibrate.py recalibrate_bam)."""
     import os
@@ -172,9 +190,10 @@ def _recalibrate_bam_kmers(args):
         kmers.update(kmers_from=args.kmers_from, k=args.kmer)                # k: the set's, unless -k names it
     records = {key: kmers[key] for key in ('mixed_lengths', 'exclude_flags') if key in kmers}
     # every rank of a launcher refuses here, before it joins the process group
+    _refuse_bam_out_ranks(args)
     _recal.check_bam_kmers(args.bam, args.gatkreport, args.output, kmers['k'], kmers['min_count'], kmers['prefilter'],
                            kmers['filter_bits'], **{key: kmers[key] for key in ('partitions', 'passes', 'exclude_flags', 'kmers_from')
-                                                    if key in kmers})
+                                                    if key in kmers}, **_bam_out_kw(args))
     parallel.init_from_env()
     from . import aln
     from ._trace import stage
@@ -187,7 +206,7 @@ def _recalibrate_bam_kmers(args):
             from . import _device
             _device.use_native_memory()          # as `bqsr --kmers` on one GPU: no torch import
         info = _recal.recalibrate_bam(bam, use_oq=args.use_oq, set_oq=args.set_oq, kmers=kmers, gatkreport=args.gatkreport,
-                                      output=args.output, **args.quantize, **_bgzf_kw(args))
+                                      output=args.output, **args.quantize, **_bgzf_kw(args), **_bam_out_kw(args))
     sys.stderr.write('kbbq recalibrate: k=%d min_count=%d reads=%d%s flagged_bases=%d%s%s%s%s%s%s\n'
                      % (info['k'], info['min_count'], info['reads'],
                         ' excluded_reads=%d' % info['excluded_reads'] if args.exclude_flags else '', info['flagged_bases'],
@@ -278,9 +297,10 @@ def benchmark(args):
 def applybqsr(args):
     from . import parallel
     from .gatk import applybqsr as _apply
+    _refuse_bam_out_ranks(args)
     parallel.init_from_env()          # one process per GPU under torch.distributed.run; no-op otherwise
     _apply.apply_report(args.bam, args.gatkreport, use_oq=args.use_oq, set_oq=args.set_oq, output=args.output, **args.quantize,
-                        **_bgzf_kw(args))
+                        **_bgzf_kw(args), **_bam_out_kw(args))
 
 
 def bqsr(args):
@@ -416,12 +436,13 @@ def main(argv=None):
     rp.add_argument('-u', '--use-oq', action='store_true',
                     help='Use the OQ tag for quality scores (BAM input only).')
     rp.add_argument('-s', '--set-oq', action='store_true',
-                    help="Set the 'OQ' tag before recalibration (BAM output only).")
+                    help="with -b --kmers: keep the qualities as read in an 'OQ' tag where there is none (SAM and BAM output).")
     rp.add_argument('-g', '--gatkreport', help='Load the model from / save it to a GATK report.')
     rp.add_argument('-o', '--output', default=None,
                     help='Write the recalibrated FASTQ to this file instead of stdout (not in the reference); under '
                          'torch.distributed.run every rank writes FILE.rankNNNN, to be concatenated in rank order.')
     rp.add_argument('--bgzf', action='store_true', help=_BGZF_HELP)
+    rp.add_argument('--bam-out', action='store_true', help='with -b --kmers: ' + _BAM_OUT_HELP)
     rp.add_argument('--infer-rg', action='store_true',
                     help='Infer the read group from the FASTQ read name (name_RG:Z:id).')
     rp.add_argument('--static-quantized-quals', type=_quant_levels, action='append', default=None, metavar='Q[,Q...]',
@@ -464,13 +485,15 @@ def main(argv=None):
                     help=_KMERS_FROM_HELP % ('with --kmers', ': the set `bqsr --kmers --kmers-from` used can be scored here'))
     bp.set_defaults(command=benchmark)
 
-    ap = sub.add_parser('applybqsr', description='Recalibrate alignments with a GATK recalibration report (SAM output)')
+    ap = sub.add_parser('applybqsr', description='Recalibrate alignments with a GATK recalibration report (SAM output, or BAM '
+                        'with --bam-out)')
     ap.add_argument('-b', '--bam', required=True, help='SAM or BAM file to recalibrate')
     ap.add_argument('-g', '--gatkreport', required=True, help='GATK recalibration report (kbbq bqsr, GATK BaseRecalibrator)')
     ap.add_argument('-o', '--output', default=None,
-                    help='Write the recalibrated SAM to this file instead of stdout (SAM text only; a .bam name is refused); '
+                    help='Write the recalibrated SAM to this file instead of stdout (SAM text; a .bam name is refused without --bam-out); '
                          'under torch.distributed.run every rank writes FILE.rankNNNN, to be concatenated in rank order.')
     ap.add_argument('--bgzf', action='store_true', help=_BGZF_HELP)
+    ap.add_argument('--bam-out', action='store_true', help=_BAM_OUT_HELP)
     ap.add_argument('-u', '--use-oq', action='store_true', help='Recalibrate the OQ tag\'s qualities instead of QUAL.')
     ap.add_argument('-s', '--set-oq', action='store_true', help="Keep the qualities as read in an 'OQ' tag where there is none.")
     ap.add_argument('--static-quantized-quals', type=_quant_levels, action='append', default=None, metavar='Q[,Q...]',
@@ -601,6 +624,10 @@ def main(argv=None):
     if args.command is recalibrate or args.command is applybqsr:
         # decided here: before the device is touched and, under a launcher, before the process group exists
         args.quantize = _quantize(rp if args.command is recalibrate else ap, args)
+        if args.bam_out and args.bgzf:
+            (rp if args.command is recalibrate else ap).error('--bam-out: not with --bgzf (a BAM file is a BGZF file already)')
+        if args.bam_out and args.command is recalibrate and not (args.kmers and args.bam is not None):
+            rp.error('--bam-out: only with -b --kmers')
     if args.command is recalibrate and not (args.kmers and args.bam is not None):
         given = [flag for flag, v in (('--mixed-lengths', args.mixed_lengths or None), ('-F/--exclude-flags', args.exclude_flags))
                  if v is not None]
