@@ -552,6 +552,19 @@ int    kbbq_apply_grouped_dev(kbbq_ctx* ctx, const uint8_t* d_seq, const uint8_t
  * kbbq_pair_lut_rows_dev take the flag (the apply kernel reads it out of the LUT); kbbq_lay_out_dev packs such rows as any
  * other pair rows.  */
 #define KBBQ_ROWS_TWINS    4
+/* KBBQ_ROWS_ERRBIT (only with KBBQ_ROWS_NIBBLES | KBBQ_ROWS_PAIRS, with or without TWINS, on rows of 19 or 13 chunks -- 2 x 150
+ * and 2 x 100 bp): in every nibble of the seq plane bits 0-2 are the code (0..4) and bit 3 is 1 exactly where the corrected
+ * read's code differs from it (a corrected code 5, "an N that counts as an error", sets it like any other difference);
+ * separator and padding are code 4 with bit 3 clear.  That bit is all the tally ever took from the corrected plane, so
+ * kbbq_accumulate_rows_dev reads d_seq, d_qual and d_meta only -- d_cseq is not read and may be NULL (1.57 instead of 2.08
+ * bytes per base) -- and kbbq_apply_rows_dev ignores the bit.  A nibble whose low three bits are 5..7 is a corrupt plane
+ * (KBBQ_E_LUT on the status) with or without the flag; without the flag bit 3 set is one too, as before.
+ * Written by kbbq_lay_out_dev (d_cseq required, d_lcseq may be NULL: no corrected plane is written) and by kbbq_fastq_fill_rows
+ * (b required, cseq may be NULL), byte for byte alike.  Accepted by kbbq_accumulate_rows_dev, kbbq_apply_rows_dev,
+ * kbbq_pair_lut_rows_dev (ignored), kbbq_accumulate_bands_dev / kbbq_apply_bands_dev (such a band is launched alone).  Every
+ * other call that takes KBBQ_ROWS_* flags -- the k-mer calls on rows, kbbq_canonical_reads_rows_dev -- returns KBBQ_E_ARG
+ * naming itself: it would read bit 3 as part of a code.  kbbq_unpack_nibbles_dev decodes bits 0-2 and so serves both kinds.  */
+#define KBBQ_ROWS_ERRBIT   8
 int    kbbq_accumulate_rows_dev(kbbq_ctx* ctx, const uint8_t* d_seq, const uint8_t* d_cseq, const uint8_t* d_qual,
                                 const uint32_t* d_meta, int64_t nrows, int pitch, int flags, int R, int S2, int S_band,
                                 int S_min, int minscore, int dinuc_minscore, const int64_t* d_seg, int64_t* d_tables);

@@ -801,14 +801,20 @@ int kbbq_group_rows_host(const uint32_t* meta, int64_t nrows, int pairs, int R, 
 //   s = perm[r] (rows gathered by read-group segment: kbbq_group_rows_host) or r when perm is NULL.
 // meta: the sidecars of kbbq_fastq_meta for the same [first, first + n).  *foreign is set to 1 (never cleared) when
 // nibble packing met a seq / cseq character outside ACGTN: the caller then repeats the band with character planes.
+//   KBBQ_ROWS_ERRBIT (with PAIRS | NIBBLES, rows of 19 or 13 chunks, b given): bit 3 of every seq nibble is set where b's
+//                    code differs from a's, as k7_lay_out sets it; cseq may then be NULL -- the corrected plane is not written.
 int kbbq_fastq_fill_rows(const kbbq_fastq* a, const kbbq_fastq* b, int64_t first, int64_t n, const uint32_t* meta, int flags,
                          int S2, int pitch, const int64_t* perm, int64_t row_lo, int64_t nrows,
                          uint8_t* seq, uint8_t* cseq, uint8_t* qual, uint32_t* dmeta, int* foreign)
 {
-    if (!a || (nrows > 0 && (!seq || !qual || !dmeta || !meta || (b && !cseq)))) return kbbq_set_error_(KBBQ_E_ARG, "kbbq_fastq_fill_rows: NULL argument");
+    const bool errbit = (flags & KBBQ_ROWS_ERRBIT) != 0;
+    if (!a || (nrows > 0 && (!seq || !qual || !dmeta || !meta || (b && !cseq && !errbit)))) return kbbq_set_error_(KBBQ_E_ARG, "kbbq_fastq_fill_rows: NULL argument");
     if (first < 0 || n < 0 || first + n > (int64_t)a->h0.size() || (b && first + n > (int64_t)b->h0.size()))
         return kbbq_set_error_(KBBQ_E_ARG, "kbbq_fastq_fill_rows: range out of bounds");
-    if (flags & ~(KBBQ_ROWS_PAIRS | KBBQ_ROWS_NIBBLES | KBBQ_ROWS_TWINS)) return kbbq_set_error_(KBBQ_E_ARG, "kbbq_fastq_fill_rows: unknown layout flags");
+    if (flags & ~(KBBQ_ROWS_PAIRS | KBBQ_ROWS_NIBBLES | KBBQ_ROWS_TWINS | KBBQ_ROWS_ERRBIT)) return kbbq_set_error_(KBBQ_E_ARG, "kbbq_fastq_fill_rows: unknown layout flags");
+    if (errbit && (!b || (flags & (KBBQ_ROWS_PAIRS | KBBQ_ROWS_NIBBLES)) != (KBBQ_ROWS_PAIRS | KBBQ_ROWS_NIBBLES)
+                   || (((S2 + 1 + 15) & ~15) != 16 * 19 && ((S2 + 1 + 15) & ~15) != 16 * 13)))
+        return kbbq_set_error_(KBBQ_E_ARG, "kbbq_fastq_fill_rows: KBBQ_ROWS_ERRBIT needs the corrected reads and 4-bit mate-pair rows of 19 or 13 chunks");
     const bool pairs = (flags & KBBQ_ROWS_PAIRS) != 0, nib = (flags & KBBQ_ROWS_NIBBLES) != 0;
     const int S = S2 / 2;
     if (pairs) {
@@ -821,13 +827,13 @@ int kbbq_fastq_fill_rows(const kbbq_fastq* a, const kbbq_fastq* b, int64_t first
     const size_t sp = nib ? (size_t)pitch / 2 : (size_t)pitch;
     std::atomic<int> bad(0); std::atomic<unsigned> odd(0);
     parallel_for(nrows, nthreads_for((size_t)nrows * (size_t)pitch * 3), [&](int64_t lo, int64_t hi) {
-        std::vector<uint8_t> tmp(nib ? (size_t)pitch : 0);
+        std::vector<uint8_t> tmp(nib ? (size_t)pitch : 0), cnib(errbit ? sp : 0);     // cnib: the corrected row's nibbles when no plane takes them
         unsigned foreign_here = 0;
         for (int64_t row = lo; row < hi; ++row) {
             const int64_t s = perm ? perm[row_lo + row] : row_lo + row;
             if (s < 0 || s >= total) { bad = 3; continue; }
             uint8_t* q = qual + (size_t)row * pitch;
-            uint8_t* planes[2] = {seq + (size_t)row * sp, b ? cseq + (size_t)row * sp : nullptr};
+            uint8_t* planes[2] = {seq + (size_t)row * sp, b ? (cseq ? cseq + (size_t)row * sp : cnib.data()) : nullptr};
             const kbbq_fastq* src[2] = {a, b};
             if (pairs) {
                 const int64_t i1 = first + 2 * s; const bool lone = 2 * s + 1 >= n; const int64_t i2 = lone ? i1 : i1 + 1;
@@ -843,6 +849,13 @@ int kbbq_fastq_fill_rows(const kbbq_fastq* a, const kbbq_fastq* b, int64_t first
                     else { c[S] = 'N'; memcpy(c + S + 1, src[pl]->buf + src[pl]->s0[i2], (size_t)S); memset(c + 2 * S + 1, 'N', (size_t)(pitch - 2 * S - 1)); }
                     if (nib) foreign_here |= pack_row(c, pitch, planes[pl]);
                 }
+                if (errbit)                       // a nibble of the xor is 0..7: + 7 carries into bit 3 exactly when it is not 0
+                    for (size_t i = 0; i < sp; i += 8) {                     // (sp = pitch / 2 is a multiple of 8: sixteen nibbles a word)
+                        uint64_t s8, c8;
+                        memcpy(&s8, planes[0] + i, 8); memcpy(&c8, planes[1] + i, 8);
+                        s8 |= (((s8 ^ c8) & 0x7777777777777777ull) + 0x7777777777777777ull) & 0x8888888888888888ull;
+                        memcpy(planes[0] + i, &s8, 8);
+                    }
                 dmeta[row] = (uint32_t)(2 * S + 1) | (meta[2 * s] & 0x7FFF0000u);
             } else {
                 const int64_t i = first + s;

@@ -103,42 +103,45 @@ static const u64 ST_INIT[KBBQ_NSTATUS] = {~0ull, ~0ull, ~0ull, ~0ull, ~0ull, ~0u
 // Each of them is named HERE and nowhere else: launch_lds takes a kernel's address from these tables, and kbbq_ctx_create walks the
 // same tables to allow every one of them the full LDS as dynamic shared memory.  An instance that is not listed is not
 // instantiated and cannot be selected.
-// K1 (table-driven): form x copies of the context table (DN) x 4-bit planes (NIB) x chunk-position-major cycle table of KJ chunks,
-// each without and with SPLIT (a dinucleotide threshold above the counting one)
+// K1 (table-driven): form x copies of the context table (DN) x 4-bit planes (NIB) x chunk-position-major cycle table of KJ chunks
+// x the error flag in bit 3 of the seq nibbles (EB, KBBQ_ROWS_ERRBIT: the KJ forms only), each without and with SPLIT (a dinucleotide
+// threshold above the counting one)
 enum K1Form { K1_ROWS, K1_ALIGNED, K1_ALIGNED_REF, K1_BANDS };
-struct K1Variant { K1Form form; int dn, nib, kj; const void* kernel[2]; };       // kernel[split]
+struct K1Variant { K1Form form; int dn, nib, kj, eb; const void* kernel[2]; };   // kernel[split]
 #define K1_SPLITS(K, ...) {(const void*)(K<false, __VA_ARGS__>), (const void*)(K<true, __VA_ARGS__>)}
 static const K1Variant K1_VARIANTS[] = {
-    {K1_ROWS, K1V3_DNREP, 0, 0, K1_SPLITS(k1v3_accumulate, K1V3_DNREP)},
-    {K1_ROWS, 8, 0, 0, K1_SPLITS(k1v3_accumulate, 8)},
-    {K1_ROWS, K1V3_DNREP, 1, 0, K1_SPLITS(k1v3_accumulate, K1V3_DNREP, true)},
-    {K1_ROWS, 8, 1, 0, K1_SPLITS(k1v3_accumulate, 8, true)},
-    {K1_ROWS, K1V3_DNREP, 1, 13, K1_SPLITS(k1v3_accumulate, K1V3_DNREP, true, 13)},
-    {K1_ROWS, K1V3_DNREP, 1, 19, K1_SPLITS(k1v3_accumulate, K1V3_DNREP, true, 19)},
-    {K1_ALIGNED, K1V3_DNREP, 0, 0, K1_SPLITS(k1v3_aligned, K1V3_DNREP)},
-    {K1_ALIGNED, 8, 0, 0, K1_SPLITS(k1v3_aligned, 8)},
-    {K1_ALIGNED_REF, K1V3_DNREP, 0, 0, K1_SPLITS(k1v3_aligned_ref, K1V3_DNREP)},
-    {K1_ALIGNED_REF, 8, 0, 0, K1_SPLITS(k1v3_aligned_ref, 8)},
-    {K1_BANDS, 0, 0, 0, K1_SPLITS(k1v3_bands, false)},                          // every band brings its own DN (K1BandsParams::dn)
-    {K1_BANDS, 0, 1, 0, K1_SPLITS(k1v3_bands, true)},
+    {K1_ROWS, K1V3_DNREP, 0, 0, 0, K1_SPLITS(k1v3_accumulate, K1V3_DNREP)},
+    {K1_ROWS, 8, 0, 0, 0, K1_SPLITS(k1v3_accumulate, 8)},
+    {K1_ROWS, K1V3_DNREP, 1, 0, 0, K1_SPLITS(k1v3_accumulate, K1V3_DNREP, true)},
+    {K1_ROWS, 8, 1, 0, 0, K1_SPLITS(k1v3_accumulate, 8, true)},
+    {K1_ROWS, K1V3_DNREP, 1, 13, 0, K1_SPLITS(k1v3_accumulate, K1V3_DNREP, true, 13)},
+    {K1_ROWS, K1V3_DNREP, 1, 19, 0, K1_SPLITS(k1v3_accumulate, K1V3_DNREP, true, 19)},
+    {K1_ROWS, K1V3_DNREP, 1, 13, 1, K1_SPLITS(k1v3_accumulate, K1V3_DNREP, true, 13, true)},
+    {K1_ROWS, K1V3_DNREP, 1, 19, 1, K1_SPLITS(k1v3_accumulate, K1V3_DNREP, true, 19, true)},
+    {K1_ALIGNED, K1V3_DNREP, 0, 0, 0, K1_SPLITS(k1v3_aligned, K1V3_DNREP)},
+    {K1_ALIGNED, 8, 0, 0, 0, K1_SPLITS(k1v3_aligned, 8)},
+    {K1_ALIGNED_REF, K1V3_DNREP, 0, 0, 0, K1_SPLITS(k1v3_aligned_ref, K1V3_DNREP)},
+    {K1_ALIGNED_REF, 8, 0, 0, 0, K1_SPLITS(k1v3_aligned_ref, 8)},
+    {K1_BANDS, 0, 0, 0, 0, K1_SPLITS(k1v3_bands, false)},                          // every band brings its own DN (K1BandsParams::dn)
+    {K1_BANDS, 0, 1, 0, 0, K1_SPLITS(k1v3_bands, true)},
 };
 #undef K1_SPLITS
 
-static const void* k1_kernel(K1Form form, bool split, int dn, int nib, int kj)
+static const void* k1_kernel(K1Form form, bool split, int dn, int nib, int kj, int eb = 0)
 {
     for (const K1Variant& v : K1_VARIANTS)
-        if (v.form == form && v.dn == dn && v.nib == nib && v.kj == kj) return v.kernel[split];
+        if (v.form == form && v.dn == dn && v.nib == nib && v.kj == kj && v.eb == eb) return v.kernel[split];
     return nullptr;                                                             // launch_lds reports it
 }
 
 // the others: the round-1 kernels (tables beyond the LDS, KBBQ_APPLY_CHECKED) and K2
-enum LdsKernel { LK_K1_PLAIN, LK_K1_PLAIN_SPLIT, LK_K1_TILED, LK_K1_TILED_SPLIT, LK_K2V3, LK_K2V3_NIB, LK_K2T, LK_K2T_NIB, LK_K2T_BANDS, LK_K2T_PAIR19, LK_K2T_PAIR13, LK_K2_LDS16, LK_K2_LDS8, LK_BGZF, LK_COUNT };
+enum LdsKernel { LK_K1_PLAIN, LK_K1_PLAIN_SPLIT, LK_K1_TILED, LK_K1_TILED_SPLIT, LK_K2V3, LK_K2V3_NIB, LK_K2V3_NIB_EB, LK_K2T, LK_K2T_NIB, LK_K2T_BANDS, LK_K2T_PAIR19, LK_K2T_PAIR13, LK_K2T_PAIR19_EB, LK_K2T_PAIR13_EB, LK_K2_LDS16, LK_K2_LDS8, LK_BGZF, LK_COUNT };
 static const void* const LDS_KERNELS[LK_COUNT] = {
     (const void*)k1_accumulate<false>, (const void*)k1_accumulate<true>,
     (const void*)k1_accumulate_tiled<false>, (const void*)k1_accumulate_tiled<true>,
-    (const void*)k2v3_apply<false>, (const void*)k2v3_apply<true>,
+    (const void*)k2v3_apply<false>, (const void*)k2v3_apply<true>, (const void*)k2v3_apply<true, true>,
     (const void*)k2t_apply<false>, (const void*)k2t_apply<true>, (const void*)k2t_bands,
-    (const void*)k2t_apply_pair<19>, (const void*)k2t_apply_pair<13>,
+    (const void*)k2t_apply_pair<19>, (const void*)k2t_apply_pair<13>, (const void*)k2t_apply_pair<19, true>, (const void*)k2t_apply_pair<13, true>,
     (const void*)k2_apply<int16_t, true, true>, (const void*)k2_apply<int8_t, true, false>,
     (const void*)bz_deflate,
 };
@@ -516,11 +519,11 @@ int kbbq_accumulate_dev(kbbq_ctx* c, const uint8_t* d_seq, const uint8_t* d_cseq
 
 // what accumulate_rows would launch (kernel parameters, LDS bytes, template variant): kbbq_accumulate_bands_dev collects
 // these for all length bands and launches them as ONE kernel
-struct K1Setup { K1v3Params q; int dn = 0; int kj = 0; size_t lds = 0; };        // dn / kj: K1_VARIANTS; lds: bytes of dynamic LDS
+struct K1Setup { K1v3Params q; int dn = 0; int kj = 0; int eb = 0; size_t lds = 0; };    // dn / kj / eb: K1_VARIANTS; lds: bytes of dynamic LDS
 static int accumulate_rows(kbbq_ctx* c, const char* who, const uint8_t* d_seq, const uint8_t* d_cseq, const uint8_t* d_qual,
                            const uint32_t* d_meta, int64_t nrows, int pitch, int pairs, int R, int S2, int minscore,
                            int dinuc_minscore, const int64_t* d_seg, int64_t* d_tables, bool* fits, int S_band = 0, int S_min = 0, int nib = 0,
-                           int twins = 0, K1Setup* setup_only = nullptr);
+                           int twins = 0, K1Setup* setup_only = nullptr, int errbit = 0);
 
 int kbbq_accumulate_ex_dev(kbbq_ctx* c, const uint8_t* d_seq, const uint8_t* d_cseq,
                            const uint8_t* d_qual, const uint32_t* d_meta,
@@ -728,7 +731,7 @@ static K2v3Params k2v3_params(kbbq_ctx* c, const uint8_t* d_seq, const uint8_t* 
 
 // the persistent K2 on these rows: every read group's LUT in the LDS, or -- rows grouped by read group -- a slice of the grid
 // per group with that group's
-static int launch_k2v3(kbbq_ctx* c, const K2v3Params& q, int nib)
+static int launch_k2v3(kbbq_ctx* c, const K2v3Params& q, int nib, int errbit = 0)
 {
     const int slices = q.seg ? q.R : 1;
     const size_t lds = (size_t)(33 + q.Qt) * q.rb * (size_t)(q.seg ? 1 : q.R);
@@ -737,12 +740,12 @@ static int launch_k2v3(kbbq_ctx* c, const K2v3Params& q, int nib)
     const int64_t nblocks = (q.nreads + q.rpb - 1) / q.rpb;
     const int64_t want = (nblocks + (K2V3_THREADS / 64) - 1) / (K2V3_THREADS / 64);
     const int gx = (int)std::min<int64_t>(want, std::max<int64_t>(1, (int64_t)c->cus * per_cu / slices));
-    return launch_lds(c, 1, LDS_KERNELS[nib ? LK_K2V3_NIB : LK_K2V3], dim3((unsigned)std::max(gx, 1), (unsigned)slices, 1), dim3(K2V3_THREADS), lds, &q);
+    return launch_lds(c, 1, LDS_KERNELS[errbit ? LK_K2V3_NIB_EB : nib ? LK_K2V3_NIB : LK_K2V3], dim3((unsigned)std::max(gx, 1), (unsigned)slices, 1), dim3(K2V3_THREADS), lds, &q);
 }
 
 static int apply_rows(kbbq_ctx* c, const char* who, const uint8_t* d_seq, const uint8_t* d_qual, const uint32_t* d_meta,
                       int64_t nrows, int pitch, int pairs, int R, int S2, int minscore, const void* d_lut_blob,
-                      const void* d_pair_lut, const int64_t* d_seg, uint8_t* d_out, int nib = 0, const int64_t* d_perm = nullptr);
+                      const void* d_pair_lut, const int64_t* d_seg, uint8_t* d_out, int nib = 0, const int64_t* d_perm = nullptr, int errbit = 0);
 
 int kbbq_apply_dev(kbbq_ctx* c, const uint8_t* d_seq, const uint8_t* d_qual, const uint32_t* d_meta,
                    int64_t nreads, int pitch, int R, int Qt, int S2, int minscore,
@@ -1067,7 +1070,7 @@ static int64_t k1_iters(const K1v3Params& q) { return ((q.nreads + 63) / 64 + (K
 static int launch_k1(kbbq_ctx* c, K1Form form, const K1Setup& su, int nib)
 {
     const int gx = (int)std::min<int64_t>(k1_iters(su.q), std::max(1, c->cus / su.q.R));
-    return launch_lds(c, 0, k1_kernel(form, k1_split(su.q), su.dn, nib, su.kj), dim3((unsigned)gx, (unsigned)su.q.R, 1), dim3(K1V3_THREADS),
+    return launch_lds(c, 0, k1_kernel(form, k1_split(su.q), su.dn, nib, su.kj, su.eb), dim3((unsigned)gx, (unsigned)su.q.R, 1), dim3(K1V3_THREADS),
                       su.lds, &su.q);
 }
 
@@ -1075,11 +1078,15 @@ static int launch_k1(kbbq_ctx* c, K1Form form, const K1Setup& su, int nib)
 static int accumulate_rows(kbbq_ctx* c, const char* who, const uint8_t* d_seq, const uint8_t* d_cseq, const uint8_t* d_qual,
                            const uint32_t* d_meta, int64_t nrows, int pitch, int pairs, int R, int S2, int minscore,
                            int dinuc_minscore, const int64_t* d_seg, int64_t* d_tables, bool* fits, int S_band, int S_min, int nib, int twins,
-                           K1Setup* setup_only)
+                           K1Setup* setup_only, int errbit)
 {
     if (fits) *fits = true;
     if (S_band < 0 || S_band > S2 / 2 || (pairs && S_band)) return fail(KBBQ_E_ARG, "%s: S_band out of range (%d)", who, S_band);
     if (S_min < 0 || S_min > (S_band ? S_band : S2 / 2)) return fail(KBBQ_E_ARG, "%s: S_min out of range (%d)", who, S_min);
+    // KBBQ_ROWS_ERRBIT: the corrected plane is not read (and may be NULL); only the joint-row forms below know the flag
+    if (errbit) d_cseq = nullptr;
+    if (errbit && !(pairs && nib && (pitch == 16 * 19 || pitch == 16 * 13)))
+        return fail(KBBQ_E_ARG, "%s: KBBQ_ROWS_ERRBIT describes 4-bit mate-pair rows of 19 or 13 chunks (pitch %d)", who, pitch);
     int rc = check_planes(who, nrows, pitch, d_seq, d_cseq, d_qual);
     if (rc) return rc;
     if (R <= 0 || R > 32767) return fail(KBBQ_E_ARG, "%s: R out of range (%d)", who, R);
@@ -1120,10 +1127,12 @@ static int accumulate_rows(kbbq_ctx* c, const char* who, const uint8_t* d_seq, c
             const size_t rows = (size_t)q.nrows - 1 + nt;
             su.lds = rows * q.row_bytes;
             if (su.lds > (size_t)c->lds_bytes) continue;
-            su.dn = K1V3_DNREP; su.kj = q.cpr;                // the form applies AND its tables fit
+            su.dn = K1V3_DNREP; su.kj = q.cpr; su.eb = errbit ? 1 : 0;       // the form applies AND its tables fit
             q.ntrash = nt; q.pos_copy_bytes = (u32)(rows * q.row_bytes);
         }
     }
+    // (44 rows of 3328 / 2944 bytes at most: they fit the 160 KB of a gfx950 CU.  A guard, not a fallback: no other form of K1 knows the flag)
+    if (errbit && !su.kj) return fail(KBBQ_E_ARG, "%s: the joint-row tables of KBBQ_ROWS_ERRBIT rows do not fit the LDS (%d bytes)", who, c->lds_bytes);
     for (int attempt = 0; attempt < (trim ? 3 : 1) && !su.dn; ++attempt) {
         const int copies = attempt == 2 ? 8 : K1V3_DNREP, cut = attempt ? trim : 0;
         if (k1_geometry(q, c, copies, cut, cut)) su.dn = copies;
@@ -1168,7 +1177,7 @@ int kbbq_pair_lut_rows_dev(kbbq_ctx* c, const void* d_lut_blob, int R, int S2, i
     if (!c) return fail(KBBQ_E_ARG, "ctx is NULL");
     int rc = check_pairs("kbbq_pair_lut_dev", 0, S2);
     if (rc) return rc;
-    if (!(flags & KBBQ_ROWS_PAIRS) || (flags & ~(KBBQ_ROWS_PAIRS | KBBQ_ROWS_NIBBLES | KBBQ_ROWS_TWINS)))
+    if (!(flags & KBBQ_ROWS_PAIRS) || (flags & ~(KBBQ_ROWS_PAIRS | KBBQ_ROWS_NIBBLES | KBBQ_ROWS_TWINS | KBBQ_ROWS_ERRBIT)))
         return fail(KBBQ_E_ARG, "kbbq_pair_lut_rows_dev: flags 0x%x are not those of mate-pair rows", flags);
     if (R <= 0 || R > 32767 || !d_lut_blob || !d_pair_lut) return fail(KBBQ_E_ARG, "kbbq_pair_lut_dev: bad argument");
     HIPCHK(hipSetDevice(c->device));
@@ -1197,10 +1206,12 @@ static K2tParams k2t_params(const K2v3Params& q)
 // K2 (table-driven kernel) on one-read-per-row or mate-pair rows, optionally grouped by read group
 static int apply_rows(kbbq_ctx* c, const char* who, const uint8_t* d_seq, const uint8_t* d_qual, const uint32_t* d_meta,
                       int64_t nrows, int pitch, int pairs, int R, int S2, int minscore, const void* d_lut_blob,
-                      const void* d_pair_lut, const int64_t* d_seg, uint8_t* d_out, int nib, const int64_t* d_perm)
+                      const void* d_pair_lut, const int64_t* d_seg, uint8_t* d_out, int nib, const int64_t* d_perm, int errbit)
 {
     int rc = check_planes(who, nrows, pitch, d_seq, d_qual, d_out);
     if (rc) return rc;
+    if (errbit && !(pairs && nib && (pitch == 16 * 19 || pitch == 16 * 13)))
+        return fail(KBBQ_E_ARG, "%s: KBBQ_ROWS_ERRBIT describes 4-bit mate-pair rows of 19 or 13 chunks (pitch %d)", who, pitch);
     if (R <= 0 || R > 32767 || !d_lut_blob || (pairs && (!d_pair_lut || ((uintptr_t)d_pair_lut & 15)))) return fail(KBBQ_E_ARG, "%s: bad argument", who);
     if (S2 <= 0 || (S2 & 1) || S2 > 65534) return fail(KBBQ_E_ARG, "%s: S2 must be positive and even (%d)", who, S2);
     if (minscore < 0 || minscore > 222) return fail(KBBQ_E_ARG, "%s: minscore out of range", who);
@@ -1215,7 +1226,7 @@ static int apply_rows(kbbq_ctx* c, const char* who, const uint8_t* d_seq, const 
     if (nrows == 0) return KBBQ_OK;
     HIPCHK(hipSetDevice(c->device));
     if (!pairs && !narrowed_row_lut(c, d_lut_blob, R, KQ, S2, Sb, minscore, &q.full)) return fail(KBBQ_E_HIP, "%s: no scratch for the narrowed LUT", who);
-    if (!k2_tile_serves(c, pairs, nib, R, d_seg != nullptr, q.cpr, rg_bytes)) return launch_k2v3(c, q, nib);
+    if (!k2_tile_serves(c, pairs, nib, R, d_seg != nullptr, q.cpr, rg_bytes)) return launch_k2v3(c, q, nib, errbit);
 
     K2tParams t = k2t_params(q);
     const int64_t per_wg = (int64_t)(K2T_THREADS / 64) * 64 * K2T_STEPS;
@@ -1242,7 +1253,9 @@ static int apply_rows(kbbq_ctx* c, const char* who, const uint8_t* d_seq, const 
     // 4-bit mate-pair rows of 19 / 13 chunks: the instance with that geometry compiled in (K1's KJ instances' counterpart)
     const int kj = (pairs && nib) ? k2t_pair_form(t) : 0;
     if (kj < 0) return fail(KBBQ_E_ARG, "%s: mate-pair rows of %d chunks do not have the geometry k2t_apply_pair was compiled for", who, q.cpr);
-    const LdsKernel k = kj == 19 ? LK_K2T_PAIR19 : kj == 13 ? LK_K2T_PAIR13 : nib ? LK_K2T_NIB : LK_K2T;
+    if (errbit && kj <= 0) return fail(KBBQ_E_ARG, "%s: no instance of K2 reads KBBQ_ROWS_ERRBIT rows of %d chunks", who, q.cpr);
+    const LdsKernel k = kj == 19 ? (errbit ? LK_K2T_PAIR19_EB : LK_K2T_PAIR19) : kj == 13 ? (errbit ? LK_K2T_PAIR13_EB : LK_K2T_PAIR13)
+                        : nib ? LK_K2T_NIB : LK_K2T;
     return launch_lds(c, 1, LDS_KERNELS[k], dim3((unsigned)gt), dim3(K2T_THREADS), (size_t)t.lut_bytes, &t);
 }
 
@@ -1269,9 +1282,16 @@ int kbbq_apply_grouped_dev(kbbq_ctx* c, const uint8_t* d_seq, const uint8_t* d_q
 
 
 // ---- layouts: rows as handed over -> what K1 / K2 run fastest on ------------
-static int layout_flags_ok(const char* who, int flags)
+// errbit_ok: the call reads (or writes) KBBQ_ROWS_ERRBIT planes -- K1 / K2 on rows, the layout pass, the pair LUT; everything else that
+// takes a 4-bit seq plane would read bit 3 as part of a code and refuses the flag
+static int layout_flags_ok(const char* who, int flags, bool errbit_ok = false)
 {
-    if (flags & ~(KBBQ_ROWS_PAIRS | KBBQ_ROWS_NIBBLES | KBBQ_ROWS_TWINS)) return fail(KBBQ_E_ARG, "%s: unknown layout flags 0x%x", who, flags);
+    if (flags & ~(KBBQ_ROWS_PAIRS | KBBQ_ROWS_NIBBLES | KBBQ_ROWS_TWINS | KBBQ_ROWS_ERRBIT)) return fail(KBBQ_E_ARG, "%s: unknown layout flags 0x%x", who, flags);
+    if (flags & KBBQ_ROWS_ERRBIT) {
+        if (!errbit_ok) return fail(KBBQ_E_ARG, "%s: layout flags 0x%x: KBBQ_ROWS_ERRBIT planes are read by kbbq_accumulate_rows_dev / kbbq_apply_rows_dev only", who, flags);
+        if ((flags & (KBBQ_ROWS_PAIRS | KBBQ_ROWS_NIBBLES)) != (KBBQ_ROWS_PAIRS | KBBQ_ROWS_NIBBLES))
+            return fail(KBBQ_E_ARG, "%s: KBBQ_ROWS_ERRBIT describes 4-bit mate-pair rows (KBBQ_ROWS_PAIRS | KBBQ_ROWS_NIBBLES)", who);
+    }
     if ((flags & KBBQ_ROWS_TWINS) && !(flags & KBBQ_ROWS_PAIRS)) return fail(KBBQ_E_ARG, "%s: KBBQ_ROWS_TWINS describes mate-pair rows (add KBBQ_ROWS_PAIRS)", who);
     return KBBQ_OK;
 }
@@ -1281,13 +1301,13 @@ int kbbq_accumulate_rows_dev(kbbq_ctx* c, const uint8_t* d_seq, const uint8_t* d
                              int S_min, int minscore, int dinuc_minscore, const int64_t* d_seg, int64_t* d_tables)
 {
     if (!c) return fail(KBBQ_E_ARG, "ctx is NULL");
-    int rc = layout_flags_ok("kbbq_accumulate_rows_dev", flags);
+    int rc = layout_flags_ok("kbbq_accumulate_rows_dev", flags, true);
     if (rc) return rc;
     const int pairs = (flags & KBBQ_ROWS_PAIRS) ? 1 : 0;
     if (pairs) { rc = check_pairs("kbbq_accumulate_rows_dev", nrows, S2); if (rc) return rc; }
     return accumulate_rows(c, "kbbq_accumulate_rows_dev", d_seq, d_cseq, d_qual, d_meta, nrows, pitch, pairs, R, S2, minscore,
                            dinuc_minscore, d_seg, d_tables, nullptr, pairs ? 0 : S_band, pairs ? 0 : S_min,
-                           (flags & KBBQ_ROWS_NIBBLES) ? 1 : 0, (flags & KBBQ_ROWS_TWINS) ? 1 : 0);
+                           (flags & KBBQ_ROWS_NIBBLES) ? 1 : 0, (flags & KBBQ_ROWS_TWINS) ? 1 : 0, nullptr, (flags & KBBQ_ROWS_ERRBIT) ? 1 : 0);
 }
 
 int kbbq_apply_rows_dev(kbbq_ctx* c, const uint8_t* d_seq, const uint8_t* d_qual, const uint32_t* d_meta, int64_t nrows,
@@ -1295,12 +1315,12 @@ int kbbq_apply_rows_dev(kbbq_ctx* c, const uint8_t* d_seq, const uint8_t* d_qual
                         const int64_t* d_seg, const int64_t* d_perm, uint8_t* d_out)
 {
     if (!c) return fail(KBBQ_E_ARG, "ctx is NULL");
-    int rc = layout_flags_ok("kbbq_apply_rows_dev", flags);
+    int rc = layout_flags_ok("kbbq_apply_rows_dev", flags, true);
     if (rc) return rc;
     const int pairs = (flags & KBBQ_ROWS_PAIRS) ? 1 : 0;
     if (pairs) { rc = check_pairs("kbbq_apply_rows_dev", nrows, S2); if (rc) return rc; }
     return apply_rows(c, "kbbq_apply_rows_dev", d_seq, d_qual, d_meta, nrows, pitch, pairs, R, S2, minscore, d_lut_blob,
-                      d_pair_lut, d_seg, d_out, (flags & KBBQ_ROWS_NIBBLES) ? 1 : 0, d_perm);
+                      d_pair_lut, d_seg, d_out, (flags & KBBQ_ROWS_NIBBLES) ? 1 : 0, d_perm, (flags & KBBQ_ROWS_ERRBIT) ? 1 : 0);
 }
 
 // ---- all length bands of a mixed-length input in ONE launch per kernel -------------------------------------------
@@ -1353,7 +1373,7 @@ int kbbq_accumulate_bands_dev(kbbq_ctx* c, const kbbq_band* bands, int nbands, i
     for (int i = 0; i < nbands; ++i) {
         const kbbq_band& b = bands[i];
         if (b.nrows == 0) continue;
-        int rc = layout_flags_ok("kbbq_accumulate_bands_dev", b.flags);
+        int rc = layout_flags_ok("kbbq_accumulate_bands_dev", b.flags, true);      // (an ERRBIT band is a KJ form: it goes alone, never into k1v3_bands)
         if (rc) return rc;
         const int pairs = (b.flags & KBBQ_ROWS_PAIRS) ? 1 : 0, nib = (b.flags & KBBQ_ROWS_NIBBLES) ? 1 : 0;
         K1Setup su; bool fits = false;
@@ -1362,7 +1382,7 @@ int kbbq_accumulate_bands_dev(kbbq_ctx* c, const kbbq_band* bands, int nbands, i
             if (pairs) { rc = check_pairs("kbbq_accumulate_bands_dev", b.nrows, S2); if (rc) return rc; }
             rc = accumulate_rows(c, "kbbq_accumulate_bands_dev", b.d_seq, b.d_cseq, b.d_qual, b.d_meta, b.nrows, b.pitch, pairs, R, S2, minscore,
                                  dinuc_minscore, b.d_seg, d_tables, &fits, pairs ? 0 : b.S_band, pairs ? 0 : b.S_min, nib,
-                                 (b.flags & KBBQ_ROWS_TWINS) ? 1 : 0, &su);
+                                 (b.flags & KBBQ_ROWS_TWINS) ? 1 : 0, &su, (b.flags & KBBQ_ROWS_ERRBIT) ? 1 : 0);
             if (rc) return rc;
             can = fits && !su.kj && (nib_of_merge < 0 || nib_of_merge == nib);
         }
@@ -1448,7 +1468,7 @@ int kbbq_apply_bands_dev(kbbq_ctx* c, const kbbq_band* bands, int nbands, int R,
     for (int i = 0; i < nbands; ++i) {
         const kbbq_band& b = bands[i];
         if (b.nrows == 0) continue;
-        int rc = layout_flags_ok("kbbq_apply_bands_dev", b.flags);
+        int rc = layout_flags_ok("kbbq_apply_bands_dev", b.flags, true);           // (k2t_bands takes b.flags == KBBQ_ROWS_NIBBLES alone)
         if (rc) return rc;
         const int Sb = std::min(b.pitch, S2);
         const bool can = (int)merged.size() < K2T_MAX_BANDS && R == 1
@@ -1542,12 +1562,14 @@ int kbbq_lay_out_dev(kbbq_ctx* c, const uint8_t* d_seq, const uint8_t* d_cseq, c
                      uint8_t* d_lseq, uint8_t* d_lcseq, uint8_t* d_lqual, uint32_t* d_lmeta)
 {
     if (!c) return fail(KBBQ_E_ARG, "ctx is NULL");
-    int rc = layout_flags_ok("kbbq_lay_out_dev", flags);
+    int rc = layout_flags_ok("kbbq_lay_out_dev", flags, true);
     if (rc) return rc;
-    const int pairs = (flags & KBBQ_ROWS_PAIRS) ? 1 : 0, nib = (flags & KBBQ_ROWS_NIBBLES) ? 1 : 0;
+    const int pairs = (flags & KBBQ_ROWS_PAIRS) ? 1 : 0, nib = (flags & KBBQ_ROWS_NIBBLES) ? 1 : 0, errbit = (flags & KBBQ_ROWS_ERRBIT) ? 1 : 0;
+    if (errbit && (!d_cseq || (pair_pitch(S2) != 16 * 19 && pair_pitch(S2) != 16 * 13)))
+        return fail(KBBQ_E_ARG, "kbbq_lay_out_dev: KBBQ_ROWS_ERRBIT needs the corrected reads and mate-pair rows of 19 or 13 chunks");
     rc = check_planes("kbbq_lay_out_dev", nreads, pitch, d_seq, d_cseq, d_qual);
     if (rc) return rc;
-    if (!d_seq || !d_qual || !d_meta || !d_lseq || !d_lqual || !d_lmeta || (d_cseq && !d_lcseq)) return fail(KBBQ_E_ARG, "kbbq_lay_out_dev: NULL pointer");
+    if (!d_seq || !d_qual || !d_meta || !d_lseq || !d_lqual || !d_lmeta || (d_cseq && !d_lcseq && !errbit)) return fail(KBBQ_E_ARG, "kbbq_lay_out_dev: NULL pointer");
     if (((uintptr_t)d_lseq | (uintptr_t)d_lcseq | (uintptr_t)d_lqual) & 15) return fail(KBBQ_E_ARG, "kbbq_lay_out_dev: planes must be 16-byte aligned");
     if (pairs) {
         rc = check_pairs("kbbq_lay_out_dev", (nreads + 1) / 2, S2);
@@ -1561,7 +1583,7 @@ int kbbq_lay_out_dev(kbbq_ctx* c, const uint8_t* d_seq, const uint8_t* d_cseq, c
     p.src[0] = d_seq; p.src[1] = d_cseq; p.src[2] = d_qual; p.dst[0] = d_lseq; p.dst[1] = d_lcseq; p.dst[2] = d_lqual;
     p.meta = d_meta; p.dmeta = d_lmeta; p.perm = reinterpret_cast<const long long*>(d_perm);
     p.nrows = pairs ? (nreads + 1) / 2 : nreads; p.nsrc = nreads; p.pitch = pitch; p.dpitch = pairs ? pair_pitch(S2) : pitch; p.S = pairs ? S2 / 2 : 0;
-    p.pairs = pairs; p.nib = nib; p.status = c->d_status;
+    p.pairs = pairs; p.nib = nib; p.errbit = errbit; p.status = c->d_status;
     const int rpb7 = (p.dpitch / 16) <= 256 ? 256 / (p.dpitch / 16) : 1;      // destination rows per workgroup iteration
     const int gx = bounded_grid((p.nrows + rpb7 - 1) / rpb7, c, 256);
     p.parts = K7_FRONTS;
@@ -1672,6 +1694,7 @@ int kbbq_canonical_reads_rows_dev(kbbq_ctx* c, const uint8_t* d_seq, const uint8
                                   uint8_t* d_out_qual, uint32_t* d_out_meta)
 {
     if (!c) return fail(KBBQ_E_ARG, "ctx is NULL");
+    if (layout & KBBQ_ROWS_ERRBIT) return fail(KBBQ_E_ARG, "kbbq_canonical_reads_rows_dev: layout flags 0x%x: KBBQ_ROWS_ERRBIT describes mate-pair rows; the output is one read per row", layout);
     if (layout & ~KBBQ_ROWS_NIBBLES) return fail(KBBQ_E_ARG, "kbbq_canonical_reads_rows_dev: the output is one read per row (layout 0 or KBBQ_ROWS_NIBBLES)");
     if (nreads < 0 || pitch <= 0 || (pitch & 15) || S <= 0 || S > pitch || S > 65535)
         return fail(KBBQ_E_ARG, "kbbq_canonical_reads_dev: bad nreads/pitch/S");

@@ -302,7 +302,9 @@ template <class F> __device__ __forceinline__ void k2t_unroll4(F f)
 
 typedef unsigned short k2t_u16x2 __attribute__((ext_vector_type(2)));
 
-template <int KJ>
+// EB: planes with KBBQ_ROWS_ERRBIT -- bit 3 of a seq nibble is K1's error flag and no part of the code; the masks below drop it
+// (the same number of instructions, one fewer in the screen).
+template <int KJ, bool EB = false>
 __global__ __launch_bounds__(K2T_THREADS) void k2t_apply_pair(K2tParams p)
 {
     extern __shared__ __attribute__((aligned(16))) u32 lds[];
@@ -358,7 +360,7 @@ __global__ __launch_bounds__(K2T_THREADS) void k2t_apply_pair(K2tParams p)
         mk[s] = mbase[drow];
     }
     u32 before = 4u;
-    if (base_c > 0) before = (u32)sbase[-1] >> 4;
+    if (base_c > 0) before = EB ? ((u32)sbase[-1] >> 4) & 7u : (u32)sbase[-1] >> 4;
     // 2. the LUT (L2-resident after the first workgroups), then one barrier
     {
         const uint4* src = reinterpret_cast<const uint4*>(p.lut + (size_t)g * (size_t)(33 + p.Qt) * p.rb);
@@ -377,8 +379,9 @@ __global__ __launch_bounds__(K2T_THREADS) void k2t_apply_pair(K2tParams p)
         const int len = (int)(mk[s] & 0xFFFFu);
         const int nb = act0 ? len - (int)a16[s] : 0;
         u32 code[4], code5[4], hiq = 0u;
-        code[0] = nib_lo(sq[s][0]); code[1] = nib_hi(sq[s][0]); code[2] = nib_lo(sq[s][1]); code[3] = nib_hi(sq[s][1]);
-        const u32 badbits = nib_invalid(sq[s][0]) | nib_invalid(sq[s][1]);
+        code[0] = nib_lo_code<EB>(sq[s][0]); code[1] = nib_hi_code<EB>(sq[s][0]);
+        code[2] = nib_lo_code<EB>(sq[s][1]); code[3] = nib_hi_code<EB>(sq[s][1]);
+        const u32 badbits = nib_bad<EB>(sq[s][0]) | nib_bad<EB>(sq[s][1]);
 #pragma unroll
         for (int wd = 0; wd < 4; ++wd) {
             code5[wd] = (code[wd] << 2) + code[wd];

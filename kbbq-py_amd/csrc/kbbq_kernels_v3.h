@@ -150,6 +150,19 @@ __device__ __forceinline__ u32 nib_lo(u32 w) { return w & NIBM; }
 __device__ __forceinline__ u32 nib_hi(u32 w) { return (w >> 4) & NIBM; }
 // some nibble of w is not a code (>= 5)
 __device__ __forceinline__ u32 nib_invalid(u32 w) { return (((w & 0x77777777u) + 0x33333333u) | w) & 0x88888888u; }
+// KBBQ_ROWS_ERRBIT planes (EB; 4-bit mate-pair rows of 19 / 13 chunks only): bits 0-2 of a seq nibble are the code, bit 3 is set
+// exactly where the corrected read's code differs -- all K1 ever took from the cseq plane (xw = seq ^ cseq, then min(byte, 1)), so
+// K1 does not load that plane at all (1.57 B/base instead of 2.08) and K2 masks the bit away.  `w & 0x08080808` / `w & 0x80808080`
+// are the error bytes of the low / high nibbles as they stand: a byte of them is 0 or not, which is all the increment asks.
+// Without EB every function below is the expression it replaces.
+#define NIBM3 0x07070707u
+template <bool EB> __device__ __forceinline__ u32 nib_lo_code(u32 w) { return w & (EB ? NIBM3 : NIBM); }
+template <bool EB> __device__ __forceinline__ u32 nib_hi_code(u32 w) { return (w >> 4) & (EB ? NIBM3 : NIBM); }
+template <bool EB> __device__ __forceinline__ u32 nib_bad(u32 w)
+{
+    if constexpr (EB) return ((w & 0x77777777u) + 0x33333333u) & 0x88888888u;       // the low three bits are 5..7
+    else return nib_invalid(w);
+}
 // 4 characters -> 4 codes as bytes (0..4), and whether all four are in ACGTN
 __device__ __forceinline__ u32 chars_to_codes(u32 w, u32& bad)
 {
@@ -226,11 +239,12 @@ struct K1Chunk { u32 s[4], c[4], q[4]; u32 mk; u32 off; int k; int j; int nb; u3
 //  locals and stay so for now: written as __forceinline__ functions over explicit state, even the two flushes alone, every one
 //  of the 24 instances came out with other instructions and other register counts (profiles/r06_kernel_headers.md section 4).
 //  Cutting them out is a change to measure on the device, not one to make under "identical device code".)
-template <bool SPLIT, int DN, bool NIB, int KJ, bool ALN = false, bool REF = false>
+template <bool SPLIT, int DN, bool NIB, int KJ, bool ALN = false, bool REF = false, bool EB = false>
 __device__ __forceinline__ void k1v3_body(const K1v3Params& p, u32* lds, const int bx, const int gx, const int g)
 {
     static_assert(!ALN || (!NIB && KJ == 0), "the aligned-read form reads character planes");
     static_assert(!REF || ALN, "the reference comparison belongs to the aligned-read form");
+    static_assert(!EB || (NIB && KJ > 0), "the error bit lives in the 4-bit mate-pair rows of the joint-row forms");
     // KJ > 0: JOINT rows -- a quality's cycle words and its context words in ONE row of JROW bytes, [CYC cycle words | 32 slots x DN
     // copies], so that one multiply by the row serves both atomics of a base (the uniform-block loop below).  CYC and JROW / 4 are multiples
     // of 32: the bank of a cycle word stays (k * KJ + j) mod 32 and that of a context word (slot * DN + copy) mod 32 whatever the row.
@@ -426,7 +440,7 @@ __device__ __forceinline__ void k1v3_body(const K1v3Params& p, u32* lds, const i
                 }
             }
             const uint8_t* bseq = p.seq + (size_t)read0 * (NIB ? p.pitch >> 1 : p.pitch);
-            const uint8_t* bcseq = p.cseq + (size_t)read0 * (NIB ? p.pitch >> 1 : p.pitch);
+            const uint8_t* bcseq = EB ? nullptr : p.cseq + (size_t)read0 * (NIB ? p.pitch >> 1 : p.pitch);     // EB: no cseq address is formed
             const uint8_t* bqual = p.qual + (size_t)read0 * p.pitch;
             const int total = n * p.cpr;
             u32 carry_code = 20u, carry_char = 0u;      // 5 * code of the previous chunk's last base
@@ -454,7 +468,10 @@ __device__ __forceinline__ void k1v3_body(const K1v3Params& p, u32* lds, const i
                 }
                 // lanes without work re-read the block's first chunk (valid memory, result unused)
                 const u32 rowoff = ch.nb > 0 ? __umul24(ch.off, (u32)p.pitch) + (u32)(16 * ch.jj) : 0u;
-                if constexpr (NIB) {
+                if constexpr (EB) {
+                    const uint2 sv = *reinterpret_cast<const uint2*>(bseq + (rowoff >> 1));
+                    ch.s[0] = sv.x; ch.s[1] = sv.y;
+                } else if constexpr (NIB) {
                     const uint2 sv = *reinterpret_cast<const uint2*>(bseq + (rowoff >> 1));
                     const uint2 cv = *reinterpret_cast<const uint2*>(bcseq + (rowoff >> 1));
                     ch.s[0] = sv.x; ch.s[1] = sv.y; ch.c[0] = cv.x; ch.c[1] = cv.y;
@@ -538,7 +555,13 @@ __device__ __forceinline__ void k1v3_body(const K1v3Params& p, u32* lds, const i
                 } else {
                     qv[0] = ch.q[0]; qv[1] = ch.q[1]; qv[2] = ch.q[2]; qv[3] = ch.q[3];
                 }
-                if constexpr (NIB) {
+                if constexpr (EB) {
+                    code[0] = nib_lo_code<true>(ch.s[0]); code[1] = nib_hi_code<true>(ch.s[0]);
+                    code[2] = nib_lo_code<true>(ch.s[1]); code[3] = nib_hi_code<true>(ch.s[1]);
+                    xw[0] = ch.s[0] & 0x08080808u; xw[1] = ch.s[0] & 0x80808080u;    // recalibrate.py:13-20: the packer compared the codes
+                    xw[2] = ch.s[1] & 0x08080808u; xw[3] = ch.s[1] & 0x80808080u;
+                    badbits = nib_bad<true>(ch.s[0]) | nib_bad<true>(ch.s[1]);
+                } else if constexpr (NIB) {
                     code[0] = nib_lo(ch.s[0]); code[1] = nib_hi(ch.s[0]); code[2] = nib_lo(ch.s[1]); code[3] = nib_hi(ch.s[1]);
                     const u32 x0 = ch.s[0] ^ ch.c[0], x1 = ch.s[1] ^ ch.c[1];        // recalibrate.py:13-20 on codes
                     xw[0] = nib_lo(x0); xw[1] = nib_hi(x0); xw[2] = nib_lo(x1); xw[3] = nib_hi(x1);
@@ -649,18 +672,27 @@ __device__ __forceinline__ void k1v3_body(const K1v3Params& p, u32* lds, const i
                     u32 inc_a = 1u, inc_b = 1u;                                    // two increments in turn; their low halves stay 1
                     auto fetch_at = [&](K1Chunk& ch, const uint8_t* fseq, const uint8_t* fcseq, const uint8_t* fqual, u32 o) {
                         const uint2 sv = *reinterpret_cast<const uint2*>(fseq + (o >> 1));
-                        const uint2 cv = *reinterpret_cast<const uint2*>(fcseq + (o >> 1));
+                        if constexpr (!EB) {
+                            const uint2 cv = *reinterpret_cast<const uint2*>(fcseq + (o >> 1));
+                            ch.c[0] = cv.x; ch.c[1] = cv.y;
+                        }
                         const uint4 qv = *reinterpret_cast<const uint4*>(fqual + o);
-                        ch.s[0] = sv.x; ch.s[1] = sv.y; ch.c[0] = cv.x; ch.c[1] = cv.y;
+                        ch.s[0] = sv.x; ch.s[1] = sv.y;
                         ch.q[0] = qv.x; ch.q[1] = qv.y; ch.q[2] = qv.z; ch.q[3] = qv.w;
                     };
                     auto fetch_u = [&](K1Chunk& ch, int s) { fetch_at(ch, bseq, bcseq, bqual, at + 1024u * (u32)s); };
                     auto process_u = [&](const K1Chunk& ch) {
                         u32 code[4], code5[4], xw[4], hiq = 0u;
-                        code[0] = nib_lo(ch.s[0]); code[1] = nib_hi(ch.s[0]); code[2] = nib_lo(ch.s[1]); code[3] = nib_hi(ch.s[1]);
-                        const u32 x0 = ch.s[0] ^ ch.c[0], x1 = ch.s[1] ^ ch.c[1];
-                        xw[0] = nib_lo(x0); xw[1] = nib_hi(x0); xw[2] = nib_lo(x1); xw[3] = nib_hi(x1);
-                        const u32 badbits = nib_invalid(ch.s[0]) | nib_invalid(ch.s[1]);
+                        code[0] = nib_lo_code<EB>(ch.s[0]); code[1] = nib_hi_code<EB>(ch.s[0]);
+                        code[2] = nib_lo_code<EB>(ch.s[1]); code[3] = nib_hi_code<EB>(ch.s[1]);
+                        if constexpr (EB) {                                  // the error bytes are bit 3 of the nibbles, where they stand
+                            xw[0] = ch.s[0] & 0x08080808u; xw[1] = ch.s[0] & 0x80808080u;
+                            xw[2] = ch.s[1] & 0x08080808u; xw[3] = ch.s[1] & 0x80808080u;
+                        } else {
+                            const u32 x0 = ch.s[0] ^ ch.c[0], x1 = ch.s[1] ^ ch.c[1];
+                            xw[0] = nib_lo(x0); xw[1] = nib_hi(x0); xw[2] = nib_lo(x1); xw[3] = nib_hi(x1);
+                        }
+                        const u32 badbits = nib_bad<EB>(ch.s[0]) | nib_bad<EB>(ch.s[1]);
 #pragma unroll
                         for (int wd = 0; wd < 4; ++wd) {
                             code5[wd] = (code[wd] << 2) + code[wd];
@@ -722,7 +754,8 @@ __device__ __forceinline__ void k1v3_body(const K1v3Params& p, u32* lds, const i
                     };
                     // KJ is odd: the step fetched ahead sits in the buffer a block ends on, not the one it starts on (eight v_mov a block)
                     if (fed) {
-                        ua.s[0] = ub.s[0]; ua.s[1] = ub.s[1]; ua.c[0] = ub.c[0]; ua.c[1] = ub.c[1];
+                        ua.s[0] = ub.s[0]; ua.s[1] = ub.s[1];
+                        if constexpr (!EB) { ua.c[0] = ub.c[0]; ua.c[1] = ub.c[1]; }
                         ua.q[0] = ub.q[0]; ua.q[1] = ub.q[1]; ua.q[2] = ub.q[2]; ua.q[3] = ub.q[3];
                     } else {
                         fetch_u(ua, 0);
@@ -739,7 +772,7 @@ __device__ __forceinline__ void k1v3_body(const K1v3Params& p, u32* lds, const i
                     ahead = ((nblk + 1) << 6) <= seg_hi - seg_lo;
                     const long long nread0 = ahead ? seg_lo + (nblk << 6) : read0;
                     m_next = p.meta[nread0 + lane];
-                    fetch_at(ub, p.seq + (size_t)nread0 * (p.pitch >> 1), p.cseq + (size_t)nread0 * (p.pitch >> 1),
+                    fetch_at(ub, p.seq + (size_t)nread0 * (p.pitch >> 1), EB ? nullptr : p.cseq + (size_t)nread0 * (p.pitch >> 1),
                              p.qual + (size_t)nread0 * p.pitch, at);
                     process_u(ua);
                 }
@@ -781,11 +814,11 @@ __device__ __forceinline__ void k1v3_body(const K1v3Params& p, u32* lds, const i
     flush_dn(); flush_pos();
 }
 
-template <bool SPLIT, int DN = K1V3_DNREP, bool NIB = false, int KJ = 0>
+template <bool SPLIT, int DN = K1V3_DNREP, bool NIB = false, int KJ = 0, bool EB = false>
 __global__ __launch_bounds__(K1V3_THREADS) void k1v3_accumulate(K1v3Params p)
 {
     extern __shared__ __attribute__((aligned(16))) u32 lds[];
-    k1v3_body<SPLIT, DN, NIB, KJ>(p, lds, (int)blockIdx.x, (int)gridDim.x, (int)blockIdx.y);
+    k1v3_body<SPLIT, DN, NIB, KJ, false, false, EB>(p, lds, (int)blockIdx.x, (int)gridDim.x, (int)blockIdx.y);
 }
 
 // the aligned-read form (K6 fused into K1): the BAM-sourced tally of gatk/bqsr.py:52-123 straight from the reads as aligned
@@ -888,7 +921,8 @@ struct K2v3Params {
     uint8_t* out; u64* status;
 };
 
-template <bool NIB = false>
+// EB: the seq plane carries KBBQ_ROWS_ERRBIT's flag in bit 3 of its nibbles; the codes are bits 0-2
+template <bool NIB = false, bool EB = false>
 __global__ __launch_bounds__(K2V3_THREADS) __attribute__((amdgpu_waves_per_eu(K2V3_WAVES, 8))) void k2v3_apply(K2v3Params p)
 {
     extern __shared__ __attribute__((aligned(16))) u32 lds[];
@@ -965,8 +999,9 @@ __global__ __launch_bounds__(K2V3_THREADS) __attribute__((amdgpu_waves_per_eu(K2
             const int pos0 = 16 * j;
             u32 code[4], code5[4], badbits = 0u, hiq = 0u;
             if constexpr (NIB) {
-                code[0] = nib_lo(ch.s[0]); code[1] = nib_hi(ch.s[0]); code[2] = nib_lo(ch.s[1]); code[3] = nib_hi(ch.s[1]);
-                badbits = nib_invalid(ch.s[0]) | nib_invalid(ch.s[1]);
+                code[0] = nib_lo_code<EB>(ch.s[0]); code[1] = nib_hi_code<EB>(ch.s[0]);
+                code[2] = nib_lo_code<EB>(ch.s[1]); code[3] = nib_hi_code<EB>(ch.s[1]);
+                badbits = nib_bad<EB>(ch.s[0]) | nib_bad<EB>(ch.s[1]);
             }
 #pragma unroll
             for (int wd = 0; wd < 4; ++wd) {

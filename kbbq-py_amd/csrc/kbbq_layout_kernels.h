@@ -191,7 +191,8 @@ struct LayOutParams {
     long long nrows;                                  // destination rows
     long long nsrc;                                   // source reads (pairs: 2 * nrows, or one less -- the last row's second half stays empty)
     int pitch, dpitch, S, pairs, nib;
-    int parts;                                        // sequential fronts of the traversal (k7_lay_out; the host passes 8)
+    int errbit;                                       // KBBQ_ROWS_ERRBIT (nib, pairs, src[1] given): bit 3 of the seq nibbles; dst[1] may be NULL
+    int parts;                                       // sequential fronts of the traversal (k7_lay_out; the host passes 8)
     u64* status;
 };
 
@@ -289,6 +290,23 @@ __global__ __launch_bounds__(256) void k7_lay_out(LayOutParams p)
                 }
             }
             *reinterpret_cast<uint4*>(p.dst[2] + (size_t)d * p.dpitch + (size_t)16 * j) = make_uint4(o[2][0], o[2][1], o[2][2], o[2][3]);
+            if (p.errbit) {
+                // KBBQ_ROWS_ERRBIT: both planes' nibbles, then bit 3 of a seq nibble = "the cseq code differs" (a nibble of the xor is
+                // 0..7: + 7 carries into bit 3 exactly when it is not 0); the cseq plane is written only where one is wanted
+                u32 bad = 0u, w[2][2];
+#pragma unroll
+                for (int pl = 0; pl < 2; ++pl) {
+                    const u32 c0 = chars_to_codes(o[pl][0], bad), c1 = chars_to_codes(o[pl][1], bad);
+                    const u32 c2 = chars_to_codes(o[pl][2], bad), c3 = chars_to_codes(o[pl][3], bad);
+                    w[pl][0] = c0 | (c1 << 4); w[pl][1] = c2 | (c3 << 4);
+                }
+                if (bad) flag(p.status, ST_LUT, 0);
+                const u32 e0 = (((w[0][0] ^ w[1][0]) & 0x77777777u) + 0x77777777u) & 0x88888888u;
+                const u32 e1 = (((w[0][1] ^ w[1][1]) & 0x77777777u) + 0x77777777u) & 0x88888888u;
+                *reinterpret_cast<uint2*>(p.dst[0] + (size_t)d * (p.dpitch >> 1) + (size_t)8 * j) = make_uint2(w[0][0] | e0, w[0][1] | e1);
+                if (p.dst[1]) *reinterpret_cast<uint2*>(p.dst[1] + (size_t)d * (p.dpitch >> 1) + (size_t)8 * j) = make_uint2(w[1][0], w[1][1]);
+                continue;
+            }
 #pragma unroll
             for (int pl = 0; pl < 2; ++pl) {
                 if (!p.src[pl]) continue;

@@ -219,6 +219,7 @@ class ReadBatch:
     and the uint32 sidecar (layout: include/kbbq_hip.h)."""
 
     nib = False          # seq / cseq hold one code nibble per base (include/kbbq_hip.h KBBQ_ROWS_NIBBLES)
+    errbit = False       # (mate-pair rows only: PairBatch.errbit)
     seg = None           # rows grouped by read group: int64 [R + 1] on the device
     perm = None          # ... and row i of this batch is row perm[i] of the batch it was made from
     tally_qual = None    # kmer.correct_batch(skip_unresolved=True): `qual` with byte 0 at every unresolved base, [rows, pitch]
@@ -318,6 +319,7 @@ class PairBatch:
     `n` counts rows (pairs)."""
 
     nib = False
+    errbit = False       # bit 3 of every seq nibble says "the corrected read differs here" (KBBQ_ROWS_ERRBIT): K1 reads no cseq plane
     seg = None
     perm = None
     tally_qual = None    # as ReadBatch's
@@ -395,6 +397,8 @@ def meta_stats(batch):
 def _describe(batch, base):
     if batch.nib:
         base += ', 4-bit sequence planes'
+    if batch.errbit:
+        base += ' with the error bit'
     if batch.seg is not None:
         base += ', rows grouped by read group'
     return base
@@ -440,12 +444,15 @@ def _group_perm(meta, nrows, pairs, R):
     return perm, seg
 
 
-def _lay_out_rows(batch, flags, S2, perm, seg):
-    """kbbq_lay_out_dev: input-order rows -> the destination layout, one pass."""
+def _lay_out_rows(batch, flags, S2, perm, seg, keep_corrected=True):
+    """kbbq_lay_out_dev: input-order rows -> the destination layout, one pass.  keep_corrected=False (ROWS_ERRBIT layouts
+    only): no corrected plane is allocated or written."""
     pairs, nib = bool(flags & N.ROWS_PAIRS), bool(flags & N.ROWS_NIBBLES)
+    errbit = bool(flags & N.ROWS_ERRBIT)
     if pairs:
-        laid = PairBatch((batch.n + 1) // 2, S2 // 2, with_corrected=batch.cseq is not None, device=batch.seq.device, nib=nib)
-        laid.read_pitch, laid.twins = batch.pitch, bool(flags & N.ROWS_TWINS)
+        laid = PairBatch((batch.n + 1) // 2, S2 // 2, with_corrected=batch.cseq is not None and (keep_corrected or not errbit),
+                         device=batch.seq.device, nib=nib)
+        laid.read_pitch, laid.twins, laid.errbit = batch.pitch, bool(flags & N.ROWS_TWINS), errbit
     elif isinstance(batch, PairBatch):                # pair rows gathered as rows: still pair rows
         laid = PairBatch(batch.n, batch.S, with_corrected=batch.cseq is not None, device=batch.seq.device, nib=nib)
         laid.read_pitch, laid.twins = batch.read_pitch, batch.twins
@@ -481,13 +488,29 @@ def layout_flags(st, n, pitch, packed=True, pairs=None):
     return (N.ROWS_PAIRS if pairs else 0) | (N.ROWS_NIBBLES if packed else 0) | (N.ROWS_TWINS if twins else 0)
 
 
-def lay_out(batch, R, S=None, packed=True, pairs=None, stats=None):
+ERRBIT_CHUNKS = (19, 13)     # chunks per mate-pair row of the K1 / K2 instances that know the flag: 2 x 150 and 2 x 100 bp
+
+
+def errbit_flag(flags, S, corrected, errbit=None):
+    """ROWS_ERRBIT when the layout `flags` of reads of length S may carry it (4-bit mate-pair rows of 19 or 13 chunks, a
+    source with corrected reads) and the caller did not refuse it (errbit=False); errbit=True insists (ValueError)."""
+    can = (bool(corrected) and (flags & N.ROWS_PAIRS) and (flags & N.ROWS_NIBBLES)
+           and int(N.load().kbbq_pair_pitch(2 * int(S))) // 16 in ERRBIT_CHUNKS)
+    if errbit and not can:
+        raise ValueError('the error bit needs corrected reads on 4-bit mate-pair rows of 2 x 150 or 2 x 100 bp')
+    return N.ROWS_ERRBIT if (can and errbit is not False) else 0
+
+
+def lay_out(batch, R, S=None, packed=True, pairs=None, stats=None, errbit=None, keep_corrected=True):
     """The device layout K1 / K2 run fastest on for this input-order ReadBatch, written in ONE pass
     (k7_lay_out): mate-pair rows when the reads are uniform first / second pairs of one length and read group (and
     pair rows are narrower than two rows) -- or single-end reads of one length whose neighbours share a read group: the
     same rows with `twins` set, both halves counting into the forward cycle columns --, rows gathered by read-group segment when R > 1, 4-bit sequence planes when
     `packed` and every base of seq AND cseq is one of ACGTN (otherwise the pass is repeated with character planes).
     The result carries `perm` (apply(..., restore_order=True) stores straight back into input order) and `seg`.
+    errbit: None sets ROWS_ERRBIT wherever the layout allows it and the batch has corrected reads (errbit_flag) -- the seq
+    nibbles then carry "the corrected read differs here" in bit 3 and accumulate() reads no corrected plane; False gives
+    the planes without it.  keep_corrected=False: such a layout gets no corrected plane at all (laid.cseq is None).
     Returns `batch` itself when no layout applies."""
     if batch.nib or batch.seg is not None or isinstance(batch, PairBatch):
         raise ValueError('lay_out takes input-order rows of characters')
@@ -496,6 +519,7 @@ def lay_out(batch, R, S=None, packed=True, pairs=None, stats=None):
     st = stats or meta_stats(batch)
     S_ = st['longest']
     flags = layout_flags(st, batch.n, batch.pitch, packed, pairs)
+    flags |= errbit_flag(flags, S_, batch.cseq is not None, errbit)
     pairs = bool(flags & N.ROWS_PAIRS)
     perm = seg = None
     if R > 1:
@@ -503,26 +527,29 @@ def lay_out(batch, R, S=None, packed=True, pairs=None, stats=None):
     if not flags and perm is None:
         return batch
     ctx = context(batch.seq.device.index)
-    laid = _lay_out_rows(batch, flags, 2 * S_, perm, seg)
+    laid = _lay_out_rows(batch, flags, 2 * S_, perm, seg, keep_corrected)
     if packed:
         try:
             ctx.status()
         except N.LutNeedsCheckedApply:                # a base outside ACGTN: character planes keep the exact semantics
-            if not (flags & ~N.ROWS_NIBBLES) and perm is None:
+            flags &= ~(N.ROWS_NIBBLES | N.ROWS_ERRBIT)
+            if not flags and perm is None:
                 return batch
-            laid = _lay_out_rows(batch, flags & ~N.ROWS_NIBBLES, 2 * S_, perm, seg)
+            laid = _lay_out_rows(batch, flags, 2 * S_, perm, seg)
     return laid
 
 
 def laid_from_reader(text, other, infer_rg_flag, first, n, pitch, R, packed=True, pairs=None, slab=1 << 17, device=None, pair_S=None,
-                     keep_pinned=False, with_out=False):
+                     keep_pinned=False, with_out=False, errbit=None, keep_corrected=True):
     """Reads [first, first + n) of a fastx.NativeFastq (and their corrections from `other`, or None) onto the device IN
     THE LAYOUT lay_out() would give them -- written by the C++ packer itself (kbbq_fastq_fill_rows): mate-pair rows, 4-bit
     sequence planes, rows gathered by read-group segment, decided from the sidecar statistics of the text (kbbq_fastq_meta)
     before a byte is uploaded.  No character rows ever exist, on the host or on the device, and no layout pass runs:
     2 B/base cross PCIe instead of 3.  Page-locked slabs are filled by all host threads while the copy engine uploads the
     previous ones, as in ReadBatch.from_reader.  Returns None when no layout applies (plain rows: ReadBatch.from_reader);
-    a letter outside ACGTN repeats the fill with character planes (the reference's TypeError rule lives there)."""
+    a letter outside ACGTN repeats the fill with character planes (the reference's TypeError rule lives there).
+    errbit: as lay_out's.  keep_corrected=False: a ROWS_ERRBIT layout neither allocates, fills nor uploads the corrected
+    plane (laid.cseq is None; 1.5 B/base cross PCIe): for callers of which nothing after K1 reads it."""
     torch = _torch()
     if n == 0:
         return None
@@ -531,6 +558,7 @@ def laid_from_reader(text, other, infer_rg_flag, first, n, pitch, R, packed=True
     if pair_S is not None and S_ != pair_S and pairs is None:
         pairs = False                        # two reads to a row need count tables / a LUT of exactly 2 x THESE reads' length (a slab of a band)
     flags = layout_flags(st, n, pitch, packed, pairs)
+    flags |= errbit_flag(flags, S_, other is not None, errbit)
     two = bool(flags & N.ROWS_PAIRS)
     nrows = (n + 1) // 2 if two else n
     perm = seg = None
@@ -543,16 +571,17 @@ def laid_from_reader(text, other, infer_rg_flag, first, n, pitch, R, packed=True
         if not flags and perm is None:
             return None
         nib = bool(flags & N.ROWS_NIBBLES)
+        corrected = other is not None and (keep_corrected or not (flags & N.ROWS_ERRBIT))     # is there a corrected plane?
         if two:
-            laid = PairBatch(nrows, S_, with_corrected=other is not None, device=device, nib=nib)
-            laid.read_pitch, laid.twins = pitch, bool(flags & N.ROWS_TWINS)
+            laid = PairBatch(nrows, S_, with_corrected=corrected, device=device, nib=nib)
+            laid.read_pitch, laid.twins, laid.errbit = pitch, bool(flags & N.ROWS_TWINS), bool(flags & N.ROWS_ERRBIT)
         else:
-            laid = ReadBatch(n, pitch, with_corrected=other is not None, device=device, nib=nib)
+            laid = ReadBatch(n, pitch, with_corrected=corrected, device=device, nib=nib)
         if with_out:                         # the output plane's first-use wipe passes behind the fill (_take_out_plane)
             laid.out_plane = torch.empty_like(laid.qual)
         dp = laid.pitch
         sp = dp // 2 if nib else dp
-        nseq = 2 if other is not None else 1
+        nseq = 2 if corrected else 1
         step = max(slab // 2 if two else slab, 1)                 # destination rows per slab: the same bytes either way
         row_bytes = nseq * sp + dp + 4
         events, foreign = {}, False
@@ -570,7 +599,7 @@ def laid_from_reader(text, other, infer_rg_flag, first, n, pitch, R, packed=True
                     at[0] += cap * width
                     return v
                 h_seq = view(sp)
-                h_cseq = view(sp) if other is not None else None
+                h_cseq = view(sp) if corrected else None
                 h_qual = view(dp)
                 h_meta = buf[at[0]:at[0] + 4 * m].view(torch.int32)
                 foreign |= text.fill_rows(other, first, n, meta, flags, 2 * S_, dp, perm, lo, m, h_seq.numpy(),
@@ -579,7 +608,7 @@ def laid_from_reader(text, other, infer_rg_flag, first, n, pitch, R, packed=True
                     break
                 laid.seq[lo:lo + m].copy_(h_seq, non_blocking=True)
                 laid.qual[lo:lo + m].copy_(h_qual, non_blocking=True)
-                if other is not None:
+                if corrected:
                     laid.cseq[lo:lo + m].copy_(h_cseq, non_blocking=True)
                 laid.meta[lo:lo + m].copy_(h_meta, non_blocking=True)
                 events[slot] = torch.cuda.Event()
@@ -590,7 +619,7 @@ def laid_from_reader(text, other, infer_rg_flag, first, n, pitch, R, packed=True
             release_pinned('ingest')
         if not foreign:
             break
-        flags &= ~N.ROWS_NIBBLES                                  # a base outside ACGTN: character planes keep the exact semantics
+        flags &= ~(N.ROWS_NIBBLES | N.ROWS_ERRBIT)                                # a base outside ACGTN: character planes keep the exact semantics
     laid.h2d_bytes = nrows * row_bytes                            # what crossed PCIe for this band (the file path's trace reports it)
     if perm is not None:
         laid.perm = torch.from_numpy(perm).to(laid.seq.device)
@@ -632,7 +661,8 @@ _pair_luts = {}
 
 def _row_flags(batch):
     pairs = isinstance(batch, PairBatch)
-    return (N.ROWS_PAIRS if pairs else 0) | (N.ROWS_NIBBLES if batch.nib else 0) | (N.ROWS_TWINS if pairs and batch.twins else 0)
+    return ((N.ROWS_PAIRS if pairs else 0) | (N.ROWS_NIBBLES if batch.nib else 0) | (N.ROWS_TWINS if pairs and batch.twins else 0)
+            | (N.ROWS_ERRBIT if pairs and batch.errbit else 0))
 
 
 LONG_READS = 160         # beyond this a band's shortest read decides whether K1's LDS tables fit (kbbq_accumulate_band_dev)

@@ -26,6 +26,7 @@ KBBQ_E_FULL = -9
 APPLY_CHECKED, APPLY_FAST = 0, 1
 ALIGNED_LUT, ALIGNED_F64 = 0, 1
 ROWS_PAIRS, ROWS_NIBBLES, ROWS_TWINS = 1, 2, 4
+ROWS_ERRBIT = 8                       # bit 3 of a seq nibble: the corrected read differs there (4-bit mate-pair rows of 19 / 13 chunks)
 KMER_FIX_N = 1                        # the `opts` word of the kbbq_kmer_correct*_ex calls
 KMER_MAX_PASSES = 8                   # the `passes` of the kbbq_kmer_*_passes* calls: 1..8
 KMER_FLAG_UNRESOLVED = 2              # ... and of kbbq_kmer_flag_ex_dev: unresolved bases become 2 in the flag plane

@@ -78,7 +78,7 @@ def _tally_slabs(A, B, infer_rg, lo, hi, tables, minscore, budget, careful):
             band = _slab_band(A, B, infer_rg, lo, s_lo, m, longest, shortest, pitch)
             with stage('fill'):
                 laid = dev.laid_from_reader(A, B, infer_rg, lo + s_lo, m, pitch, max(R, 1), packed=longest <= dev.PACKED_READS,
-                                            pair_S=S2 // 2, keep_pinned=True)
+                                            pair_S=S2 // 2, keep_pinned=True, keep_corrected=False)     # the slab lives for K1 only
             try:
                 done = False
                 if laid is not None:
