@@ -1131,6 +1131,59 @@ int kbbq_bam_assemble_dev(kbbq_ctx* ctx, const uint8_t* d_skel, size_t skel_byte
 int kbbq_bam_assemble(const uint8_t* skel, size_t skel_bytes, const kbbq_bam_desc* desc, int64_t n, const uint8_t* seq,
                       const uint8_t* qplane, int pitch, uint8_t* stream, size_t carry, size_t stream_bytes, int64_t* bad_row);
 
+/* ---- BGZF input: inflate on the GPU (csrc/kbbq_bgzf_inflate.h, csrc/bam_host.cpp kbbq_inflate_all, kbbq/_bgzf.py inflate) -------
+ * A BGZF file is a row of gzip members of at most 64 KiB in and 64 KiB out, each naming its own compressed size (BSIZE), CRC32
+ * and length (ISIZE): a member is one workgroup's work.
+ * kbbq_inflate_index: the block table of src[0, n), from headers and trailers alone (no HIP call, nothing is inflated).  Member b:
+ * its deflate payload is src[blocks[b].src, + csize), its text belongs at blocks[b].dst = the sum of the ISIZE fields before
+ * it.  blocks == NULL (or cap too small: KBBQ_E_ARG) only counts: *nblocks and *text_bytes are set either way.  Returns
+ * KBBQ_INFLATE_NOT_BGZF (no error text) for anything that is not BGZF from its first to its last byte: a member without the BC
+ * subfield, a BSIZE that runs past n, an ISIZE above 65536.  Such a stream stays on the caller's host path.
+ * kbbq_inflate_bgzf_dev (synchronous): kernel bi_inflate over nblocks members, everything in device memory.  d_blocks are
+ * descriptors as above with offsets into d_src (src_bytes long) and d_out (out_bytes long); d_status[b] receives 0 and the text
+ * lies at d_out + dst, or a KBBQ_INFLATE_* value above 0 and NOTHING of d_out was written for that member: a descriptor that
+ * reaches outside either buffer, a bad block type, an over-subscribed or incomplete code, literal/length symbol 286 / 287 or
+ * distance symbol 30 / 31, a distance before the member's start, output past ISIZE, input past the payload, a stored block
+ * whose LEN and NLEN disagree, text shorter than ISIZE, payload bytes behind the last deflate block, a CRC32 other than the
+ * trailer's.  All of RFC 1951 is decoded (stored, fixed and dynamic blocks in any number, codes of up to 15 bits, lengths 3..258,
+ * distances 1..32768, overlapping copies, the empty member).  A status is not a verdict on the data: the kernel never decides
+ * that a file is damaged, the caller inflates such a member again on the host.
+ * kbbq_inflate_bgzf: the same from and to host buffers, slab by slab (whole members) through the context's page-locked staging
+ * (KBBQ_STAGE_MB): compressed bytes go up, text comes down.  Members with a status are inflated again on the host inside the
+ * call, as kbbq_inflate_all does it (libdeflate, then zlib); when that fails too the call fails with KBBQ_E_ARG and the reader's
+ * error text.  *text_bytes = the bytes written to out (out_cap must hold the sum of the ISIZE fields).  stats (may be NULL).
+ * kbbq_inflate_bgzf_host: the decoder of the kernel (bi_member), compiled for the host, on ONE member: payload[0, n) into
+ * out[0, isize); returns the status the kernel would give.  Writes out[0, isize) only.  For tests and fuzzing.
+ * kbbq_inflate_use_ctx: the context the readers (kbbq_fastq_open, kbbq_text_open, kbbq_sam_open: csrc/bam_host.cpp kbbq_inflate_all)
+ * may use, or NULL for none; kbbq_ctx_destroy takes it back.  The device route is taken when a context is registered,
+ * KBBQ_GPU_INFLATE is 1 (the default is the host route: profiles/bgzf_inflate.md), the stream indexes as BGZF and is at least
+ * KBBQ_GPU_INFLATE_MIN_BYTES long (default 1 MiB); a failure of the route other than damaged data falls back to the host route.
+ * The route has staging and a stream of its own in the context and takes a lock: readers on several threads take turns.
+ * kbbq_inflate_stats_get: what the readers sent that way since the process began.
+ * KBBQ_E_ARG before any HIP call: a NULL ctx, a NULL buffer or result pointer with something to do, d_blocks not 8-byte or
+ * d_status not 4-byte aligned, nblocks < 0 or above 2^31 - 1, an out_cap below the text.  nblocks == 0 launches nothing.        */
+#define KBBQ_INFLATE_NOT_BGZF 1
+enum {
+    KBBQ_INFLATE_OK = 0, KBBQ_INFLATE_BTYPE, KBBQ_INFLATE_CODE, KBBQ_INFLATE_SYMBOL, KBBQ_INFLATE_DISTANCE, KBBQ_INFLATE_OUTPUT,
+    KBBQ_INFLATE_INPUT, KBBQ_INFLATE_STORED, KBBQ_INFLATE_ISIZE, KBBQ_INFLATE_TRAILING, KBBQ_INFLATE_CRC, KBBQ_INFLATE_RANGE,
+    KBBQ_INFLATE_TABLE
+};
+typedef struct kbbq_bgzf_block {
+    uint64_t src, dst;                /* the payload's offset in the compressed bytes, the text's in the output */
+    uint32_t csize, isize, crc, pad;  /* payload bytes, ISIZE, CRC32 */
+} kbbq_bgzf_block;
+typedef struct kbbq_inflate_stats {
+    uint64_t device_blocks, host_blocks, bytes_up, bytes_down;   /* inflated by the kernel, redone on the host, over the bus */
+} kbbq_inflate_stats;
+int kbbq_inflate_index(const uint8_t* src, size_t n, kbbq_bgzf_block* blocks, size_t cap, size_t* nblocks, size_t* text_bytes);
+int kbbq_inflate_bgzf_dev(kbbq_ctx* ctx, const uint8_t* d_src, size_t src_bytes, const kbbq_bgzf_block* d_blocks, int64_t nblocks,
+                          uint8_t* d_out, size_t out_bytes, uint32_t* d_status);
+int kbbq_inflate_bgzf(kbbq_ctx* ctx, const uint8_t* src, size_t n, uint8_t* out, size_t out_cap, size_t* text_bytes,
+                      kbbq_inflate_stats* stats);
+int kbbq_inflate_bgzf_host(const uint8_t* payload, uint32_t n, uint8_t* out, uint32_t isize, uint32_t crc);
+int kbbq_inflate_use_ctx(kbbq_ctx* ctx);
+int kbbq_inflate_stats_get(kbbq_inflate_stats* stats);
+
 #ifdef __cplusplus
 }
 #endif

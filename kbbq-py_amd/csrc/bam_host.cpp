@@ -31,12 +31,11 @@ template <typename F> void threads_over(size_t n, unsigned nt, F f)
     for (auto& t : th) t.join();
 }
 
-struct Block { size_t src, csize; size_t dst; uint32_t isize, crc; };
-
 // BGZF: every member is  1f 8b 08 04 | mtime xfl os (6) | xlen (2) | subfields ... 'B' 'C' 02 00 BSIZE(2) ... | deflate | crc32 isize
-bool index_bgzf(const uint8_t* s, size_t n, std::vector<Block>& blocks)
+// The members of s[0, n): how many, how much text; blocks (if not NULL) receives the first `cap` of them.  false: not BGZF.
+bool index_bgzf(const uint8_t* s, size_t n, kbbq_bgzf_block* blocks, size_t cap, size_t* count, size_t* text)
 {
-    size_t at = 0, out = 0;
+    size_t at = 0, out = 0, nb = 0;
     while (at < n) {
         if (n - at < 18 || s[at] != 0x1f || s[at + 1] != 0x8b || s[at + 2] != 8 || !(s[at + 3] & 4)) return false;
         const size_t xlen = le16(s + at + 10);
@@ -48,14 +47,24 @@ bool index_bgzf(const uint8_t* s, size_t n, std::vector<Block>& blocks)
             x += 4 + slen;
         }
         if (bsize < 12 + xlen + 8 || bsize > n - at) return false;
-        Block b;
-        b.src = at + 12 + xlen; b.csize = bsize - (12 + xlen) - 8;
-        b.crc = le32(s + at + bsize - 8); b.isize = le32(s + at + bsize - 4); b.dst = out;
+        kbbq_bgzf_block b;
+        b.src = at + 12 + xlen; b.csize = (uint32_t)(bsize - (12 + xlen) - 8);
+        b.crc = le32(s + at + bsize - 8); b.isize = le32(s + at + bsize - 4); b.dst = out; b.pad = 0;
         if (b.isize > (1u << 16)) return false;                               // BGZF blocks hold at most 64 KiB
         out += b.isize; at += bsize;
-        blocks.push_back(b);
+        if (nb < cap) blocks[nb] = b;
+        ++nb;
     }
+    *count = nb; *text = out;
     return true;
+}
+
+bool index_bgzf(const uint8_t* s, size_t n, std::vector<kbbq_bgzf_block>& blocks, size_t* text)
+{
+    size_t nb = 0;
+    if (!index_bgzf(s, n, nullptr, 0, &nb, text)) return false;
+    blocks.resize(nb);
+    return index_bgzf(s, n, blocks.data(), nb, &nb, text);
 }
 
 // gzip members one after the other through libdeflate (fast_inflate.h); false: not available or anything but success -- zlib
@@ -234,32 +243,100 @@ bool format_record(const uint8_t* r, size_t len, const std::vector<std::string>&
 
 }  // namespace
 
-bool kbbq_inflate_all(const uint8_t* src, size_t n, kbbq_bytes& out, std::string& err)
+bool kbbq_inflate_blocks_host(const uint8_t* src, const kbbq_bgzf_block* blocks, const uint32_t* which, size_t count, uint8_t* out,
+                              size_t work, std::string& err)
 {
-    std::vector<Block> blocks;
-    if (!index_bgzf(src, n, blocks)) return inflate_serial(src, n, out, err);   // plain gzip (or a damaged BGZF: zlib decides)
-    const size_t total = blocks.empty() ? 0 : blocks.back().dst + blocks.back().isize;
-    kbbq_resize_fresh(out, total);
     std::atomic<int> bad(0);
-    threads_over(blocks.size(), kbbq_threads_for(n), [&](size_t lo, size_t hi) {
+    threads_over(count, kbbq_threads_for(work), [&](size_t lo, size_t hi) {
         kbbq_block_inflater fast;
         z_stream z; memset(&z, 0, sizeof z);
         if (inflateInit2(&z, -15) != Z_OK) { bad = 1; return; }
         for (size_t b = lo; b < hi && !bad.load(); ++b) {
-            const Block& k = blocks[b];
-            if (fast.block(src + k.src, k.csize, out.data() + k.dst, k.isize, k.crc)) continue;
+            const kbbq_bgzf_block& k = blocks[which ? which[b] : b];
+            if (fast.block(src + k.src, k.csize, out + k.dst, k.isize, k.crc)) continue;
             Bytef nothing = 0;                                   // an empty block (bgzip's EOF marker; an empty file is ONLY that):
             z.next_in = const_cast<Bytef*>(src + k.src); z.avail_in = (uInt)k.csize;   // zlib rejects a NULL next_out
-            z.next_out = k.isize ? out.data() + k.dst : &nothing; z.avail_out = k.isize;
+            z.next_out = k.isize ? out + k.dst : &nothing; z.avail_out = k.isize;
             const int rc = k.isize || k.csize ? inflate(&z, Z_FINISH) : Z_STREAM_END;
             if ((rc != Z_STREAM_END && !(rc == Z_OK && z.avail_out == 0)) || z.avail_out != 0
-                || crc32(crc32(0L, Z_NULL, 0), k.isize ? out.data() + k.dst : &nothing, k.isize) != k.crc) { bad = 2; break; }
+                || crc32(crc32(0L, Z_NULL, 0), k.isize ? out + k.dst : &nothing, k.isize) != k.crc) { bad = 2; break; }
             inflateReset(&z);
         }
         inflateEnd(&z);
     });
     if (bad.load()) { err = bad.load() == 1 ? "zlib: inflateInit2 failed" : "corrupt BGZF block (inflate / CRC mismatch)"; return false; }
     return true;
+}
+
+// ---- the device route of kbbq_inflate_all (include/kbbq_hip.h "BGZF input") ------------------------------------------------------------
+namespace {
+std::atomic<kbbq_ctx*> g_inflate_ctx(nullptr);
+std::atomic<kbbq_inflate_route> g_inflate_route(nullptr);
+std::atomic<uint64_t> g_inflate_stats[4];                 // device blocks, host blocks, bytes up, bytes down
+
+size_t gpu_inflate_min_bytes()
+{
+    const char* e = getenv("KBBQ_GPU_INFLATE_MIN_BYTES");
+    if (!e || !*e) return (size_t)1 << 20;
+    char* end = nullptr;
+    const unsigned long long v = strtoull(e, &end, 10);
+    return end == e ? (size_t)1 << 20 : (size_t)v;
+}
+}  // namespace
+
+void kbbq_inflate_forget_ctx_(kbbq_ctx* c)
+{
+    kbbq_ctx* expect = c;
+    g_inflate_ctx.compare_exchange_strong(expect, nullptr);
+}
+
+void kbbq_inflate_set_route_(kbbq_ctx* c, kbbq_inflate_route route)
+{
+    g_inflate_route.store(route);
+    g_inflate_ctx.store(route ? c : nullptr);
+}
+
+extern "C" int kbbq_inflate_stats_get(kbbq_inflate_stats* stats)
+{
+    if (!stats) return kbbq_set_error_(KBBQ_E_ARG, "kbbq_inflate_stats_get: stats is NULL");
+    stats->device_blocks = g_inflate_stats[0].load(); stats->host_blocks = g_inflate_stats[1].load();
+    stats->bytes_up = g_inflate_stats[2].load(); stats->bytes_down = g_inflate_stats[3].load();
+    return KBBQ_OK;
+}
+
+extern "C" int kbbq_inflate_index(const uint8_t* src, size_t n, kbbq_bgzf_block* blocks, size_t cap, size_t* nblocks, size_t* text_bytes)
+{
+    if (!nblocks || !text_bytes || (n && !src)) return kbbq_set_error_(KBBQ_E_ARG, "kbbq_inflate_index: NULL src or result pointer");
+    *nblocks = 0; *text_bytes = 0;
+    if (!index_bgzf(src, n, nullptr, 0, nblocks, text_bytes)) { *nblocks = 0; *text_bytes = 0; return KBBQ_INFLATE_NOT_BGZF; }
+    if (!blocks) return KBBQ_OK;
+    if (cap < *nblocks) return kbbq_set_error_(KBBQ_E_ARG, "kbbq_inflate_index: blocks holds fewer descriptors than the stream has members");
+    index_bgzf(src, n, blocks, cap, nblocks, text_bytes);
+    return KBBQ_OK;
+}
+
+bool kbbq_inflate_all(const uint8_t* src, size_t n, kbbq_bytes& out, std::string& err)
+{
+    std::vector<kbbq_bgzf_block> blocks;
+    size_t total = 0;
+    if (!index_bgzf(src, n, blocks, &total)) return inflate_serial(src, n, out, err);   // plain gzip (or a damaged BGZF: zlib decides)
+    kbbq_resize_fresh(out, total);
+    kbbq_ctx* ctx = g_inflate_ctx.load();
+    const kbbq_inflate_route route = g_inflate_route.load();
+    const char* on = getenv("KBBQ_GPU_INFLATE");
+    if (ctx && route && on && on[0] == '1' && !on[1] && n >= gpu_inflate_min_bytes()) {
+        kbbq_inflate_stats st;
+        bool data_error = false;
+        const int rc = route(ctx, src, n, blocks.data(), blocks.size(), out.data(), &st, &data_error);
+        if (rc == KBBQ_OK) {
+            g_inflate_stats[0] += st.device_blocks; g_inflate_stats[1] += st.host_blocks;
+            g_inflate_stats[2] += st.bytes_up; g_inflate_stats[3] += st.bytes_down;
+            return true;
+        }
+        if (data_error) { err = "corrupt BGZF block (inflate / CRC mismatch)"; return false; }
+        // anything else (no memory, a HIP error): the host route, as if no context had been registered
+    }
+    return kbbq_inflate_blocks_host(src, blocks.data(), nullptr, blocks.size(), out.data(), n, err);
 }
 
 bool kbbq_bam_to_sam(const uint8_t* bam, size_t n, kbbq_bytes& text, std::string& err)

@@ -26,6 +26,7 @@
 // Plain vector loads and stores and ordinary LDS / global atomics only.
 #pragma once
 #include "kbbq_kernels.h"
+#include "kbbq_crc32.h"
 
 constexpr int BZ_THREADS = 512;
 constexpr u32 BZ_TILE = 512, BZ_ROUNDS = 9;               // 2^BZ_ROUNDS >= BZ_TILE: a chain inside a tile has at most BZ_TILE steps
@@ -34,7 +35,6 @@ constexpr u32 BZ_HASH_BITS = 14, BZ_TAB_WORDS = 1u << BZ_HASH_BITS;
 constexpr u32 BZ_MIN_MATCH = 4, BZ_MAX_MATCH = 258, BZ_MAX_DIST = 32768;
 constexpr u32 BZ_NLL = 288, BZ_ND = 32, BZ_NCL = 20;      // the alphabets (286, 30 and 19 symbols), rounded up
 constexpr u32 BZ_TEXT_LDS = BZ_MAX_TEXT + 16;
-constexpr u32 BZ_CRC_POLY = 0xedb88320u;
 static_assert((1u << BZ_ROUNDS) >= BZ_TILE && BZ_TILE == (u32)BZ_THREADS, "a thread a position, BZ_ROUNDS doublings a tile");
 static_assert(BZ_TAB_WORDS * 4 >= BZ_SLOT, "the output bits of a block fit where the hash heads were");
 
@@ -60,26 +60,6 @@ struct BzSmall {
 };
 
 constexpr size_t BZ_LDS_BYTES = BZ_TEXT_LDS + (size_t)BZ_TAB_WORDS * 4 + ((sizeof(BzSmall) + 15) & ~(size_t)15);
-
-// a * b mod P over GF(2), reflected (bit 31 is x^0)
-__device__ __forceinline__ u32 bz_gf2_mul(u32 a, u32 b)
-{
-    u32 p = 0;
-    for (int i = 0; i < 32; ++i) {
-        if (a & (0x80000000u >> i)) p ^= b;
-        b = (b & 1) ? (b >> 1) ^ BZ_CRC_POLY : b >> 1;
-    }
-    return p;
-}
-
-// x^(8 * bytes) mod P; x2n[k] = x^(2^k) mod P
-__device__ __forceinline__ u32 bz_x8n(const u32* x2n, u32 bytes)
-{
-    u32 p = 0x80000000u;
-    for (u32 k = 3; bytes; bytes >>= 1, ++k)
-        if (bytes & 1) p = bz_gf2_mul(x2n[k & 31], p);
-    return p;
-}
 
 // exclusive prefix sum of v over the workgroup and its total; two barriers
 __device__ __forceinline__ u32 bz_scan(u32 v, u32* wsum, u32* total)
@@ -305,16 +285,8 @@ __global__ __launch_bounds__(BZ_THREADS) void bz_deflate(BgzfParams q)
     const u32 tid = threadIdx.x;
     u32* const tok = q.tok + (size_t)blockIdx.x * BZ_MAX_TEXT;
 
-    if (tid < 256) {
-        u32 c = tid;
-        for (int k = 0; k < 8; ++k) c = (c & 1) ? (c >> 1) ^ BZ_CRC_POLY : c >> 1;
-        sm->crc_tab[tid] = c;
-    }
-    if (tid == 256) {
-        u32 p = 0x40000000u;                               // x^1
-        sm->x2n[0] = p;
-        for (int k = 1; k < 32; ++k) { p = bz_gf2_mul(p, p); sm->x2n[k] = p; }
-    }
+    if (tid < 256) sm->crc_tab[tid] = crc_table_entry(tid);
+    if (tid == 256) crc_x2n_fill(sm->x2n);
 
     for (u32 b = blockIdx.x; b < q.nblocks; b += gridDim.x) {
         const int64_t first = (int64_t)b * q.block_bytes;
@@ -339,18 +311,11 @@ __global__ __launch_bounds__(BZ_THREADS) void bz_deflate(BgzfParams q)
         if (tid == 0) { sm->crc = 0; sm->carry = 0; sm->carry_next = 0; }
         __syncthreads();
 
-        // ---- CRC32: strips whose length in words is odd, so that the lanes of a wave read different banks
+        // ---- CRC32: strips whose length in words is odd, so that the lanes of a wave read different banks (kbbq_crc32.h)
         {
-            u32 L = ((n + BZ_THREADS - 1) / BZ_THREADS + 3) & ~3u;
-            if (!(L & 4)) L += 4;
-            const u32 lo = min(n, tid * L), hi = min(n, lo + L);
-            if (lo < hi) {
-                u32 c = 0xffffffffu;
-                for (u32 i = lo; i < hi; ++i) c = sm->crc_tab[(c ^ s[i]) & 255] ^ (c >> 8);
-                c ^= 0xffffffffu;
-                if (hi < n) c = bz_gf2_mul(bz_x8n(sm->x2n, n - hi), c);
-                atomicXor(&sm->crc, c);
-            }
+            u32 lo, hi;
+            crc_strip_of(n, tid, BZ_THREADS, &lo, &hi);
+            if (lo < hi) atomicXor(&sm->crc, crc_strip(sm->crc_tab, sm->x2n, s, lo, hi, n));
         }
 
         // ---- LZ77, tile by tile

@@ -15,6 +15,8 @@
 #include "kbbq_kmer_set.h"
 #include "kbbq_bgzf.h"
 #include "kbbq_bam_out.h"
+#include "kbbq_bgzf_inflate.h"
+#include "bam_host.h"
 #include "../../include/kbbq_hip.h"
 #include "host_threads.h"
 
@@ -27,6 +29,8 @@
 #include <cstdio>
 #include <cstring>
 #include <functional>
+#include <memory>
+#include <mutex>
 #include <string>
 #include <thread>
 #include <vector>
@@ -75,6 +79,12 @@ struct kbbq_ctx {
     DevScratch bgzf_off;              // ... the blocks' offsets in the packed output, and its length
     DevScratch bgzf_blocks;           // kbbq_bgzf_deflate (host buffers): a slab's blocks before they are packed
     DevScratch bam_words;             // kbbq_bam_assemble_dev: the lowest row with a quality below 0, the lowest that does not fit
+    // kbbq_inflate_bgzf: staging and a stream of its own -- a reader may inflate on a thread of its own while the context's other
+    // staging is in use -- and the lock that makes it one call at a time
+    void* inflate_host[2] = {nullptr, nullptr}; void* inflate_dev[2] = {nullptr, nullptr}; size_t inflate_bytes = 0;
+    hipStream_t inflate_stream = nullptr;
+    hipEvent_t inflate_done[2] = {nullptr, nullptr};
+    std::mutex inflate_lock;
     // host-buffer entry points (stage_run): two page-locked staging slabs and their device twins, a copy stream and
     // the events that order host copy -> upload -> kernel -> download slab by slab (grown on demand, kept for the next call)
     void* stage_host[2] = {nullptr, nullptr}; void* stage_dev[2] = {nullptr, nullptr}; size_t stage_bytes = 0;
@@ -135,7 +145,7 @@ static const void* k1_kernel(K1Form form, bool split, int dn, int nib, int kj, i
 }
 
 // the others: the round-1 kernels (tables beyond the LDS, KBBQ_APPLY_CHECKED) and K2
-enum LdsKernel { LK_K1_PLAIN, LK_K1_PLAIN_SPLIT, LK_K1_TILED, LK_K1_TILED_SPLIT, LK_K2V3, LK_K2V3_NIB, LK_K2V3_NIB_EB, LK_K2T, LK_K2T_NIB, LK_K2T_BANDS, LK_K2T_PAIR19, LK_K2T_PAIR13, LK_K2T_PAIR19_EB, LK_K2T_PAIR13_EB, LK_K2_LDS16, LK_K2_LDS8, LK_BGZF, LK_COUNT };
+enum LdsKernel { LK_K1_PLAIN, LK_K1_PLAIN_SPLIT, LK_K1_TILED, LK_K1_TILED_SPLIT, LK_K2V3, LK_K2V3_NIB, LK_K2V3_NIB_EB, LK_K2T, LK_K2T_NIB, LK_K2T_BANDS, LK_K2T_PAIR19, LK_K2T_PAIR13, LK_K2T_PAIR19_EB, LK_K2T_PAIR13_EB, LK_K2_LDS16, LK_K2_LDS8, LK_BGZF, LK_BGZF_INFLATE, LK_COUNT };
 static const void* const LDS_KERNELS[LK_COUNT] = {
     (const void*)k1_accumulate<false>, (const void*)k1_accumulate<true>,
     (const void*)k1_accumulate_tiled<false>, (const void*)k1_accumulate_tiled<true>,
@@ -143,7 +153,7 @@ static const void* const LDS_KERNELS[LK_COUNT] = {
     (const void*)k2t_apply<false>, (const void*)k2t_apply<true>, (const void*)k2t_bands,
     (const void*)k2t_apply_pair<19>, (const void*)k2t_apply_pair<13>, (const void*)k2t_apply_pair<19, true>, (const void*)k2t_apply_pair<13, true>,
     (const void*)k2_apply<int16_t, true, true>, (const void*)k2_apply<int8_t, true, false>,
-    (const void*)bz_deflate,
+    (const void*)bz_deflate, (const void*)bi_inflate,
 };
 
 extern "C" {
@@ -234,6 +244,13 @@ int kbbq_ctx_destroy(kbbq_ctx* c)
         if (c->stage_used[b]) (void)hipEventDestroy(c->stage_used[b]);
         if (c->stage_down[b]) (void)hipEventDestroy(c->stage_down[b]);
     }
+    kbbq_inflate_forget_ctx_(c);
+    for (int b = 0; b < 2; ++b) {
+        if (c->inflate_host[b]) (void)hipHostFree(c->inflate_host[b]);
+        if (c->inflate_dev[b]) (void)hipFree(c->inflate_dev[b]);
+        if (c->inflate_done[b]) (void)hipEventDestroy(c->inflate_done[b]);
+    }
+    if (c->inflate_stream) (void)hipStreamDestroy(c->inflate_stream);
     if (c->stage_stream) (void)hipStreamDestroy(c->stage_stream);
     if (c->stage_down_stream) (void)hipStreamDestroy(c->stage_down_stream);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -3195,6 +3212,173 @@ int kbbq_bgzf_deflate(kbbq_ctx* c, const uint8_t* text, int64_t n, int block_byt
     if (rc) return stage_drain(c, rc);
     *out_bytes = written;
     return KBBQ_OK;
+}
+
+} // extern "C"
+
+// ---- BGZF input (csrc/kbbq_bgzf_inflate.h) ------------------------------------------------------------------------------------
+static int inflate_launch(kbbq_ctx* c, hipStream_t stream, const uint8_t* d_src, size_t src_bytes, const kbbq_bgzf_block* d_blocks,
+                          int64_t nblocks, uint8_t* d_out, size_t out_bytes, uint32_t* d_status)
+{
+    if ((size_t)c->lds_bytes < BI_LDS_BYTES) return fail(KBBQ_E_ARG, "bi_inflate needs %zu bytes of LDS, the device has %d", BI_LDS_BYTES, c->lds_bytes);
+    const unsigned grid = (unsigned)std::min<int64_t>(nblocks, std::max(c->cus, 1));
+    BiParams q{d_src, (uint64_t)src_bytes, d_blocks, (uint32_t)nblocks, d_out, (uint64_t)out_bytes, d_status};
+    void* args[] = {&q};
+    (void)hipLaunchKernel(LDS_KERNELS[LK_BGZF_INFLATE], dim3(grid), dim3(BI_THREADS), args, BI_LDS_BYTES, stream);
+    HIPCHK(hipGetLastError());
+    return KBBQ_OK;
+}
+
+static int inflate_stage_prepare(kbbq_ctx* c, size_t bytes)
+{
+    if (!c->inflate_stream) {
+        HIPCHK(hipStreamCreateWithFlags(&c->inflate_stream, hipStreamNonBlocking));
+        for (int b = 0; b < 2; ++b) HIPCHK(hipEventCreateWithFlags(&c->inflate_done[b], hipEventDisableTiming));
+    }
+    if (c->inflate_bytes < bytes) {
+        HIPCHK(hipStreamSynchronize(c->inflate_stream));
+        for (int b = 0; b < 2; ++b) {
+            if (c->inflate_host[b]) { (void)hipHostFree(c->inflate_host[b]); c->inflate_host[b] = nullptr; }
+            if (c->inflate_dev[b]) { (void)hipFree(c->inflate_dev[b]); c->inflate_dev[b] = nullptr; }
+        }
+        c->inflate_bytes = 0;
+        for (int b = 0; b < 2; ++b) {
+            HIPCHK(hipHostMalloc(&c->inflate_host[b], bytes, hipHostMallocDefault));
+            HIPCHK(hipMalloc(&c->inflate_dev[b], bytes));
+        }
+        c->inflate_bytes = bytes;
+    }
+    return KBBQ_OK;
+}
+
+// The members of an indexed stream (kbbq_inflate_index) into out, slab by slab of whole members; members the kernel gave a status are
+// inflated again by kbbq_inflate_blocks_host.  *data_error: that failed too -- the input is damaged, the text is in the error.
+static int kbbq_inflate_bgzf_indexed_(kbbq_ctx* c, const uint8_t* src, size_t n, const kbbq_bgzf_block* blocks, size_t nblocks, uint8_t* out,
+                                      kbbq_inflate_stats* stats, bool* data_error)
+{
+    *data_error = false;
+    kbbq_inflate_stats st = {0, 0, 0, 0};
+    if (stats) *stats = st;
+    if (!nblocks) return KBBQ_OK;
+    std::lock_guard<std::mutex> guard(c->inflate_lock);
+    HIPCHK(hipSetDevice(c->device));
+    // a slab: up to `per` members.  Host and device alike: compressed bytes | descriptors | status words | text
+    const char* e = getenv("KBBQ_STAGE_MB");
+    const size_t budget = (size_t)(e && atoi(e) > 0 ? atoi(e) : 96) << 20;
+    const size_t per = std::max<size_t>(1, std::min<size_t>(nblocks, budget / (2 * (size_t)BI_MAX_TEXT + 64)));
+    const size_t o_blocks = align16(per * (size_t)BI_MAX_PAYLOAD), o_status = o_blocks + per * sizeof(kbbq_bgzf_block);
+    const size_t o_text = align16(o_status + per * 4), bytes = o_text + per * (size_t)BI_MAX_TEXT;
+    int rc = inflate_stage_prepare(c, bytes);
+    if (rc) return rc;
+    hipStream_t s = c->inflate_stream;
+    std::vector<uint32_t> again;                           // members for the host
+    struct Slab { size_t lo, hi; } slab[2] = {{0, 0}, {0, 0}};
+    auto finish = [&](int buf) -> int {                    // the slab in `buf`: its text to `out`, its refused members to `again`
+        HIPCHK(hipEventSynchronize(c->inflate_done[buf]));
+        const size_t lo = slab[buf].lo, hi = slab[buf].hi;
+        const size_t text = (size_t)(blocks[hi - 1].dst + blocks[hi - 1].isize - blocks[lo].dst);
+        threaded_copy(out + blocks[lo].dst, (const char*)c->inflate_host[buf] + o_text, text);
+        const uint32_t* status = (const uint32_t*)((const char*)c->inflate_host[buf] + o_status);
+        for (size_t b = lo; b < hi; ++b) if (status[b - lo]) again.push_back((uint32_t)b);
+        st.bytes_down += text + (hi - lo) * 4;
+        return KBBQ_OK;
+    };
+    size_t k = 0;
+    for (size_t lo = 0; lo < nblocks; ++k) {
+        const int buf = (int)(k & 1);
+        const size_t hi = std::min(nblocks, lo + per);
+        const size_t base = (size_t)blocks[lo].src, comp = (size_t)(blocks[hi - 1].src + blocks[hi - 1].csize) - base;
+        const size_t text = (size_t)(blocks[hi - 1].dst + blocks[hi - 1].isize - blocks[lo].dst);
+        if (comp > per * (size_t)BI_MAX_PAYLOAD || text > per * (size_t)BI_MAX_TEXT || base + comp > n)
+            { rc = fail(KBBQ_E_ARG, "kbbq_inflate_bgzf: the block table does not describe BGZF members"); break; }
+        if (k >= 2) { rc = finish(buf); if (rc) break; }   // the slab that used this buffer
+        char* h = (char*)c->inflate_host[buf];
+        char* d = (char*)c->inflate_dev[buf];
+        threaded_copy(h, src + base, comp);
+        kbbq_bgzf_block* hb = (kbbq_bgzf_block*)(h + o_blocks);
+        for (size_t b = lo; b < hi; ++b) {
+            hb[b - lo] = blocks[b];
+            hb[b - lo].src -= base; hb[b - lo].dst -= blocks[lo].dst;
+        }
+        slab[buf] = Slab{lo, hi};
+        if (hipMemcpyAsync(d, h, comp, hipMemcpyHostToDevice, s) != hipSuccess
+            || hipMemcpyAsync(d + o_blocks, h + o_blocks, (hi - lo) * sizeof(kbbq_bgzf_block), hipMemcpyHostToDevice, s) != hipSuccess)
+            rc = fail(KBBQ_E_HIP, "kbbq_inflate_bgzf: upload failed");
+        if (!rc) rc = inflate_launch(c, s, (const uint8_t*)d, comp, (const kbbq_bgzf_block*)(d + o_blocks), (int64_t)(hi - lo),
+                                     (uint8_t*)d + o_text, text, (uint32_t*)(d + o_status));
+        if (!rc && (hipMemcpyAsync(h + o_status, d + o_status, (hi - lo) * 4, hipMemcpyDeviceToHost, s) != hipSuccess
+                    || (text && hipMemcpyAsync(h + o_text, d + o_text, text, hipMemcpyDeviceToHost, s) != hipSuccess)))
+            rc = fail(KBBQ_E_HIP, "kbbq_inflate_bgzf: download failed");
+        if (!rc && hipEventRecord(c->inflate_done[buf], s) != hipSuccess) rc = fail(KBBQ_E_HIP, "kbbq_inflate_bgzf: hipEventRecord failed");
+        if (rc) break;
+        st.bytes_up += comp + (hi - lo) * sizeof(kbbq_bgzf_block);
+        lo = hi;
+    }
+    if (rc) { (void)hipStreamSynchronize(s); return rc; }
+    if (k >= 2) rc = finish((int)(k & 1));
+    if (!rc) rc = finish((int)((k - 1) & 1));
+    if (rc) { (void)hipStreamSynchronize(s); return rc; }
+    st.device_blocks = nblocks - again.size(); st.host_blocks = again.size();
+    if (stats) *stats = st;
+    if (!again.empty()) {
+        std::string err;
+        if (!kbbq_inflate_blocks_host(src, blocks, again.data(), again.size(), out, again.size() << 14, err)) { *data_error = true; return fail(KBBQ_E_ARG, "%s", err.c_str()); }
+    }
+    return KBBQ_OK;
+}
+
+extern "C" {
+
+int kbbq_inflate_bgzf_dev(kbbq_ctx* c, const uint8_t* d_src, size_t src_bytes, const kbbq_bgzf_block* d_blocks, int64_t nblocks,
+                          uint8_t* d_out, size_t out_bytes, uint32_t* d_status)
+{
+    if (!c) return fail(KBBQ_E_ARG, "kbbq_inflate_bgzf_dev: NULL ctx");
+    if (nblocks < 0 || nblocks > (int64_t)INT_MAX) return fail(KBBQ_E_ARG, "kbbq_inflate_bgzf_dev: nblocks must be in 0..2^31 - 1");
+    if (nblocks == 0) return KBBQ_OK;
+    if (!d_blocks || !d_status || (src_bytes && !d_src) || (out_bytes && !d_out)) return fail(KBBQ_E_ARG, "kbbq_inflate_bgzf_dev: NULL buffer");
+    if (((uintptr_t)d_blocks & 7) || ((uintptr_t)d_status & 3))
+        return fail(KBBQ_E_ARG, "kbbq_inflate_bgzf_dev: d_blocks is 8-byte and d_status 4-byte aligned");
+    HIPCHK(hipSetDevice(c->device));
+    int rc = inflate_launch(c, c->stream, d_src, src_bytes, d_blocks, nblocks, d_out, out_bytes, d_status);
+    if (rc) return rc;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return KBBQ_OK;
+}
+
+int kbbq_inflate_bgzf(kbbq_ctx* c, const uint8_t* src, size_t n, uint8_t* out, size_t out_cap, size_t* text_bytes,
+                      kbbq_inflate_stats* stats)
+{
+    if (!c || !text_bytes) return fail(KBBQ_E_ARG, "kbbq_inflate_bgzf: NULL ctx or text_bytes");
+    *text_bytes = 0;
+    if (stats) memset(stats, 0, sizeof *stats);
+    if (n == 0) return KBBQ_OK;
+    if (!src) return fail(KBBQ_E_ARG, "kbbq_inflate_bgzf: NULL buffer");
+    size_t nb = 0, total = 0;
+    int rc = kbbq_inflate_index(src, n, nullptr, 0, &nb, &total);
+    if (rc == KBBQ_INFLATE_NOT_BGZF) return fail(KBBQ_E_ARG, "kbbq_inflate_bgzf: the input is not BGZF");
+    if (rc) return rc;
+    if (total > out_cap || (total && !out)) return fail(KBBQ_E_ARG, "kbbq_inflate_bgzf: out holds %zu bytes, the text is %zu", out_cap, total);
+    std::vector<kbbq_bgzf_block> blocks(nb);
+    rc = kbbq_inflate_index(src, n, blocks.data(), nb, &nb, &total);
+    if (rc) return rc;
+    bool data_error = false;
+    rc = kbbq_inflate_bgzf_indexed_(c, src, n, blocks.data(), nb, out, stats, &data_error);
+    if (!rc) *text_bytes = total;
+    return rc;
+}
+
+int kbbq_inflate_use_ctx(kbbq_ctx* c)
+{
+    kbbq_inflate_set_route_(c, c ? &kbbq_inflate_bgzf_indexed_ : nullptr);
+    return KBBQ_OK;
+}
+
+int kbbq_inflate_bgzf_host(const uint8_t* payload, uint32_t n, uint8_t* out, uint32_t isize, uint32_t crc)
+{
+    if ((n && !payload) || (isize && !out)) return fail(KBBQ_E_ARG, "kbbq_inflate_bgzf_host: NULL buffer");
+    std::unique_ptr<BiTables> t(new BiTables);
+    static uint8_t none[4];
+    return (int)bi_member_host(payload ? payload : none, n, out ? out : none, isize, crc, t.get());
 }
 
 } // extern "C"

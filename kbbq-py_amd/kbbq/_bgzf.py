@@ -208,6 +208,59 @@ class BgzfWriter(io.RawIOBase):
                 self._raw.close()
 
 
+# ---- the other direction ---------------------------------------------------------------------------------------------------
+def inflate(data, stats=None):
+    """The text of the BGZF stream `data` (bytes-like), inflated on the GPU (csrc/kbbq_bgzf_inflate.h: a member per workgroup;
+    members the kernel does not verify are inflated again on the host).  stats: a dict that receives device_blocks, host_blocks,
+    bytes_up, bytes_down.  ValueError for a stream that is not BGZF or is damaged, with the readers' text."""
+    import ctypes
+    from . import _device as dev
+    N = dev.N
+    lib = N.load()
+    src = np.frombuffer(memoryview(data).cast('B'), dtype=np.uint8)
+    nb, total = ctypes.c_size_t(0), ctypes.c_size_t(0)
+    rc = lib.kbbq_inflate_index(N.ptr(src) if len(src) else None, len(src), None, 0, ctypes.byref(nb), ctypes.byref(total))
+    if rc == N.INFLATE_NOT_BGZF:
+        raise ValueError('not a BGZF stream')
+    N.check(rc)
+    out = np.empty(total.value, dtype=np.uint8)
+    got, st = ctypes.c_size_t(0), N.InflateStats()
+    N.check(lib.kbbq_inflate_bgzf(dev.context().handle, N.ptr(src) if len(src) else None, len(src), N.ptr(out) if len(out) else None,
+                                  len(out), ctypes.byref(got), ctypes.byref(st)))
+    if stats is not None:
+        stats.update({k: int(getattr(st, k)) for k, _ in N.InflateStats._fields_})
+    return out[:got.value].tobytes()
+
+
+def inflate_stats():
+    """What the readers (kbbq_inflate_all) have sent through the device since the process began: device_blocks, host_blocks
+    (the fallback count), bytes_up, bytes_down."""
+    from . import _native as N
+    st = N.InflateStats()
+    N.check(N.load().kbbq_inflate_stats_get(st))
+    return {k: int(getattr(st, k)) for k, _ in N.InflateStats._fields_}
+
+
+def wants_device(*paths):
+    """Would the readers inflate one of these files on the device once a context exists?  (KBBQ_GPU_INFLATE=1, a gzip file of at
+    least KBBQ_GPU_INFLATE_MIN_BYTES.)  The callers that open their input while the device warms up then warm up first."""
+    if os.environ.get('KBBQ_GPU_INFLATE') != '1':
+        return False
+    try:
+        least = int(os.environ.get('KBBQ_GPU_INFLATE_MIN_BYTES') or (1 << 20))
+    except ValueError:
+        least = 1 << 20
+    for p in paths:
+        try:
+            if p is not None and os.path.getsize(p) >= max(least, 2):
+                with open(p, 'rb') as fh:
+                    if fh.read(2) == b'\x1f\x8b':
+                        return True
+        except OSError:
+            pass
+    return False
+
+
 # ---- the option ----------------------------------------------------------------------------------------------------------
 _on = [False]
 

@@ -123,6 +123,8 @@ def context(device=None):
     if ctx is None:
         ctx = N.Context(device)
         _contexts[device] = ctx
+        # the readers' inflate may use the newest context (KBBQ_GPU_INFLATE=1: csrc/bam_host.cpp kbbq_inflate_all)
+        N.check(N.load().kbbq_inflate_use_ctx(ctx.handle))
     if torch.__name__ == 'torch':            # without torch the context keeps its own stream (kbbq/_hipmem.py enqueues there too)
         ctx.set_stream(torch.cuda.current_stream(device).cuda_stream)
     return ctx

@@ -248,6 +248,26 @@ class Band(ctypes.Structure):
                 ('d_out', _vp), ('d_pair_lut', _vp)]
 
 
+class BgzfBlock(ctypes.Structure):
+    """kbbq_bgzf_block (include/kbbq_hip.h): one BGZF member of an indexed stream."""
+    _fields_ = [('src', _u64), ('dst', _u64), ('csize', _c.c_uint32), ('isize', _c.c_uint32), ('crc', _c.c_uint32), ('pad', _c.c_uint32)]
+
+
+class InflateStats(ctypes.Structure):
+    """kbbq_inflate_stats: members inflated by the kernel, redone on the host, bytes over the bus."""
+    _fields_ = [('device_blocks', _u64), ('host_blocks', _u64), ('bytes_up', _u64), ('bytes_down', _u64)]
+
+
+INFLATE_NOT_BGZF = 1                   # kbbq_inflate_index: the stream is not BGZF (no error)
+# KBBQ_INFLATE_*: a member's status from bi_inflate / kbbq_inflate_bgzf_host
+(INFLATE_OK, INFLATE_BTYPE, INFLATE_CODE, INFLATE_SYMBOL, INFLATE_DISTANCE, INFLATE_OUTPUT, INFLATE_INPUT, INFLATE_STORED,
+ INFLATE_ISIZE, INFLATE_TRAILING, INFLATE_CRC, INFLATE_RANGE, INFLATE_TABLE) = range(13)
+PROTOTYPES['kbbq_inflate_index'] = (_i, [_vp, _sz, _vp, _sz, _c.POINTER(_sz), _c.POINTER(_sz)])
+PROTOTYPES['kbbq_inflate_bgzf_dev'] = (_i, [_vp, _vp, _sz, _vp, _i64, _vp, _sz, _vp])
+PROTOTYPES['kbbq_inflate_bgzf'] = (_i, [_vp, _vp, _sz, _vp, _sz, _c.POINTER(_sz), _c.POINTER(InflateStats)])
+PROTOTYPES['kbbq_inflate_bgzf_host'] = (_i, [_vp, _c.c_uint32, _vp, _c.c_uint32, _c.c_uint32])
+PROTOTYPES['kbbq_inflate_use_ctx'] = (_i, [_vp])
+PROTOTYPES['kbbq_inflate_stats_get'] = (_i, [_c.POINTER(InflateStats)])
 PROTOTYPES['kbbq_accumulate_bands_dev'] = (_i, [_vp, _c.POINTER(Band), _i, _i, _i, _i, _i, _vp])
 PROTOTYPES['kbbq_apply_bands_dev'] = (_i, [_vp, _c.POINTER(Band), _i, _i, _i, _i, _vp])
 

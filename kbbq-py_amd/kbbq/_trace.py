@@ -63,6 +63,14 @@ def report(reset=True):
         sys.stderr.write('kbbq stages: ' + '  '.join('%s %.3fs' % (n, s) for n, (s, _) in _acc.items())
                          + '  (sum %.3fs)\n' % total)
         try:
+            from ._bgzf import inflate_stats
+            st = inflate_stats()
+            if st['device_blocks'] or st['host_blocks']:
+                sys.stderr.write('kbbq inflate: %d BGZF blocks inflated on the device, %d redone on the host (fallback), %.1f MB up, %.1f MB down\n'
+                                 % (st['device_blocks'], st['host_blocks'], st['bytes_up'] / 1e6, st['bytes_down'] / 1e6))
+        except Exception:
+            pass
+        try:
             from .parallel import HOST_BINDING as hb
             if hb:
                 sys.stderr.write('kbbq host: %d host threads (1 / %d of the CPUs the job may use), NUMA node %s, %d CPUs in the mask\n'

@@ -132,6 +132,15 @@ def parse_cigar(text):
     return out
 
 
+def _context_for(path):
+    """The readers inflate a large BGZF file on the device when they are allowed to (KBBQ_GPU_INFLATE=1) and a context exists: make
+    sure one does before such a file is opened.  Nothing happens for any other file."""
+    from . import _bgzf
+    if _bgzf.wants_device(path):
+        from . import _device
+        _device.context()
+
+
 def _read_bytes(path):
     """The whole file as bytes, inflated by the library when it is gzip / bgzip (csrc/sam_host.cpp kbbq_text_open: bgzip blocks side by
     side, gzip members chunk-wise on all host threads -- Python's gzip module reads 0.2-0.3 GB/s on one thread)."""
@@ -141,6 +150,7 @@ def _read_bytes(path):
     if not os.path.exists(path):
         raise FileNotFoundError(2, 'No such file or directory', str(path))       # (what open() says)
     lib = N.load()
+    _context_for(path)
     handle, data, n = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_size_t(0)
     N.check(lib.kbbq_text_open(str(path).encode(), ctypes.byref(handle), ctypes.byref(data), ctypes.byref(n)))
     try:
@@ -182,6 +192,7 @@ class _SamHandle:
         from . import _native as N
         import ctypes
         self.h = ctypes.c_void_p()
+        _context_for(path)
         N.check(N.load().kbbq_sam_open(str(path).encode(), ctypes.byref(self.h)))
 
     def __del__(self):

@@ -141,13 +141,22 @@ def _warm_up():
         dev.warm_up(device)
 
 
+def _scan(path_a, path_b, infer_rg):
+    """fastx.PairScan, started before the device warms up -- unless the reader is to inflate the input on the device
+    (KBBQ_GPU_INFLATE=1 and a compressed file above the threshold): that needs the context, so the warm-up comes first."""
+    from . import _bgzf
+    if _bgzf.wants_device(path_a, path_b):
+        _warm_up()
+    return fastx.PairScan(path_a, path_b, infer_rg)
+
+
 def _pack_and_tally(fastq, infer_rg, minscore, maxscore):
     world, rank = parallel.world_rank()
     # rank 0 (or the only process) opens and scans the pair on the reader's own threads -- no interpreter lock needed --
     # while the device warms up; the other ranks then index only the byte ranges of their shards (fastx.pack_pair)
     # (several ranks: every rank cuts, indexes and scans its own byte range of either file -- fastx.local_ranges -- and
     # only when the files do not cut alike does rank 0 scan all of them for a plan)
-    scan = fastx.PairScan(fastq[0], fastq[1], infer_rg) if world == 1 else None
+    scan = _scan(fastq[0], fastq[1], infer_rg) if world == 1 else None
     _warm_up()
     failure, packed = None, None
     try:
@@ -282,7 +291,7 @@ def _recalibrate_mapped(fastq, infer_rg, gatkreport, output, world, rank, shard,
     """recalibrate_fastq on mapped, indexed inputs (regular files): resident on the device, or slab by slab within the budget."""
     packed, single = None, None
     if gatkreport is not None and os.path.exists(gatkreport):
-        scan = fastx.PairScan(fastq[0], None, infer_rg)
+        scan = _scan(fastq[0], None, infer_rg)
         _warm_up()
         text = scan.result()[0]
         done_with.append(text)
@@ -473,7 +482,7 @@ def _recalibrate_corrected(path, infer_rg, gatkreport, output, k, min_count, slo
     more = kmer._passes_kw(passes)
     if skip:
         more['skip_unresolved'] = True
-    scan = fastx.PairScan(path, None, infer_rg)
+    scan = _scan(path, None, infer_rg)
     _warm_up()
     text = scan.result()[0]
     done_with.append(text)
