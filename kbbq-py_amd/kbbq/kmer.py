@@ -923,6 +923,22 @@ def kmers_from_field(info):
     return ' kmers_from=1 loaded_kmers=%d' % info['loaded_kmers'] if info.get('kmers_from') else ''
 
 
+def summary_line(command, info, options, bases='changed_bases'):
+    """The one stderr line of a k-mer command, `kbbq COMMAND: k=.. min_count=.. reads=.. ..\\n`, from the `info` its library call
+    returned and the k-mer keywords `options` it was made with: ` excluded_reads=N` with exclude_flags, then info[bases]
+    (changed_bases, or flagged_bases of the commands that only flag), ` skipped_bases=N` with skip_unresolved, ` fix_n=1`,
+    ` passes=P` above one pass, partitions_field, min_qual_field, with the prefilter the admitted k-mers and the table's slots,
+    and kmers_from_field at the very end."""
+    return ('kbbq %s: k=%d min_count=%d reads=%d%s %s=%d%s%s%s%s%s%s%s\n'
+            % (command, info['k'], info['min_count'], info['reads'],
+               ' excluded_reads=%d' % info['excluded_reads'] if options.get('exclude_flags') else '', bases, info[bases],
+               ' skipped_bases=%d' % info['skipped_bases'] if options.get('skip_unresolved') else '',
+               ' fix_n=1' if options.get('fix_n') else '', ' passes=%d' % options['passes'] if options.get('passes', 1) > 1 else '',
+               partitions_field(info), min_qual_field(info),
+               ' prefilter=1 admitted=%d slots=%d' % (info['admitted'], info['slots']) if options.get('prefilter') else '',
+               kmers_from_field(info)))
+
+
 def _kmers_from_kw(kmers_from):
     """The keyword for a callee: none without a set, whose calls are the ones they were before the option."""
     return dict(kmers_from=kmers_from) if kmers_from is not None else {}
@@ -1222,11 +1238,7 @@ def main_correct(path, output=None, k=31, min_count=None, slots=None, local_slot
         changed = info['changed_bases']
         if ranks[1] != 0:
             return info
-    sys.stderr.write('kbbq correct: k=%d min_count=%d reads=%d changed_bases=%d%s%s%s%s%s%s\n'
-                     % (info['k'], info['min_count'], info['reads'], changed, ' fix_n=1' if fix_n else '',
-                        ' passes=%d' % passes if passes > 1 else '', partitions_field(info), min_qual_field(info),
-                        ' prefilter=1 admitted=%d slots=%d' % (info['admitted'], info['slots']) if prefilter else '',
-                        kmers_from_field(info)))
+    sys.stderr.write(summary_line('correct', dict(info, changed_bases=changed), dict(fix_n=fix_n, passes=passes, prefilter=prefilter)))
     return info
 
 

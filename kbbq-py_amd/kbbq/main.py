@@ -60,13 +60,6 @@ def _exclude_flags(text):
     return value
 
 
-_EXCLUDE_HELP = ('%s: leave records with any of these FLAG bits (decimal or 0x..; default 0) out of the k-mer count and the tally '
-                 '-- they teach the model nothing%s.  -F 0xF00 is the set GATK\'s BaseRecalibrator leaves out as far as SAM '
-                 'flags express it: secondary, QC-fail, duplicate and supplementary records')
-_MIXED_HELP = ('%s: take records of several query lengths (trimmed reads, hard-clipped supplementary records): the cycle axis is '
-               'twice the longest record, the rows have its pitch')
-
-
 def _quant_levels(text):
     """--static-quantized-quals Q[,Q...]: integers in 6..93 (the minscore of every apply up to the top of the FASTQ scale)."""
     levels = []
@@ -99,41 +92,207 @@ _QUANT_HELP = ('round every quality that is written to the nearest of these leve
 _ROUND_DOWN_HELP = 'with --static-quantized-quals: round down to the level below instead of to the nearest'
 
 
-_PARTITIONS_HELP = ('%s: count the k-mers in this many rounds, 1..64 (default 1), each over all reads and for one hash partition of '
-                    'the k-mers, through a table 1/P the size (--slots, where given, is that table); the k-mers that can be '
-                    'solid are kept after each round and the reads are corrected against them: the same output, every round '
-                    'hashes every k-mer.  auto: the fewest rounds whose table fits half the device budget (KBBQ_DEVICE_BUDGET).  One GPU '
-                    'only: a process group splits the k-mers over its ranks already (correct --local-slots)')
+# ---- the k-mer options: six commands take them (recalibrate -c, recalibrate -b --kmers, bqsr --kmers, benchmark --kmers, correct, count)
+#
+# dest: (flags, argparse keywords, help template).  A template takes %(scope)s -- the command's `with ...: `, or nothing --,
+# %(with)s -- the same words in front of another flag -- and %(more)s, the words of one command (_COMMANDS[...]['help']).
+# The order of the rows is the order of the flags in a refusal.
+
+_KMER_OPTIONS = {
+    'kmer': (('-k', '--kmer'), dict(type=int, default=None), '%(scope)sk-mer length, 8..32 (default 31)'),
+    'min_count': (('--min-count',), dict(type=int, default=None),
+                  '%(scope)sk-mers seen at least this often are solid (default: the first valley of the count histogram)'),
+    'slots': (('--slots',), dict(type=int, default=None), '%(scope)shash table slots, a power of two (default: every k-mer of %(more)s)'),
+    'prefilter': (('--prefilter',), dict(action='store_true'), '%(scope)skeep most k-mers seen once out of the table%(more)s'),
+    'filter_bits': (('--filter-bits',), dict(type=int, default=None),
+                    '%(with)s--prefilter: bits per k-mer of the input%(more)s in each of the filter\'s two arrays, 1..64 (default 4)'),
+    'fix_n': (('--fix-n',), dict(action='store_true'), '%(scope)sgive every N the letter%(more)s'),
+    'passes': (('--passes',), dict(type=_passes, default=None, metavar='P'),
+               '%(scope)sapply the k-mer rule to its own output this many times, 1..8 (default 1), read by read against the one table '
+               'counted from the reads as read: an error next to a read end or to another error is corrected once its '
+               'neighbour is'),
+    'skip_unresolved': (('--skip-unresolved',), dict(action='store_true'),
+                        '%(scope)sleave a base out of the tally (neither error nor observation) when the k-mers contradict it but '
+                        'name no replacement -- two errors within k bases, thin coverage, contamination -- instead of counting '
+                        'it as correct%(more)s'),
+    'partitions': (('--partitions',), dict(type=_partitions, default=None, metavar='P|auto'),
+                   '%(scope)scount the k-mers in this many rounds, 1..64 (default 1), each over all reads and for one hash partition of '
+                   'the k-mers, through a table 1/P the size (--slots, where given, is that table); the k-mers that can be '
+                   'solid are kept after each round and the reads are corrected against them: the same output, every round '
+                   'hashes every k-mer.  auto: the fewest rounds whose table fits half the device budget (KBBQ_DEVICE_BUDGET).  One GPU '
+                   'only: a process group splits the k-mers over its ranks already (correct --local-slots)'),
+    'mixed_lengths': (('--mixed-lengths',), dict(action='store_true'),
+                      '%(scope)stake records of several query lengths (trimmed reads, hard-clipped supplementary records): the cycle '
+                      'axis is twice the longest record, the rows have its pitch'),
+    'exclude_flags': (('-F', '--exclude-flags'), dict(type=_exclude_flags, default=None, metavar='INT'),
+                      '%(scope)sleave records with any of these FLAG bits (decimal or 0x..; default 0) out of the k-mer count and the '
+                      'tally -- they teach the model nothing%(more)s.  -F 0xF00 is the set GATK\'s BaseRecalibrator leaves out as far '
+                      'as SAM flags express it: secondary, QC-fail, duplicate and supplementary records'),
+    'kmer_min_qual': (('--kmer-min-qual',), dict(type=_min_qual, default=None, metavar='Q'),
+                      '%(scope)scount only the k-mers whose bases all have quality >= Q, 1..93 (default: every k-mer): the errors sit at '
+                      'the low-quality bases, so the table, sized from the counted k-mers, is several times smaller and the '
+                      'histogram\'s valley is cleaner.  The reads are corrected as read: a low-quality base is trusted through the '
+                      'k-mers other reads contributed.  The qualities are the ones the command reads%(more)s'),
+    'kmers_from': (('--kmers-from',), dict(default=None, metavar='SET'),
+                   '%(scope)stake the k-mers from this k-mer set (`kbbq count -o SET`) instead of counting the input\'s: k is the set\'s, '
+                   '--min-count (not below the set\'s --keep) or the first valley of the set\'s histogram is the threshold, --slots '
+                   'the table the set is loaded into; the same output as with the same k-mers counted here.  Not with the counting '
+                   'options --prefilter, --filter-bits, --partitions, --kmer-min-qual and --local-slots%(more)s'),
+    'local_slots': (('--local-slots',), dict(type=int, default=None),
+                    'under torch.distributed.run: slots of the table every rank counts its own reads into before they go '
+                    'to the ranks that own them, a power of two (default: the rank\'s k-mers at a load factor of 0.5, '
+                    'capped by half the device budget); a smaller table counts the reads in several rounds'),
+}
+
+_COUNTING_OPTIONS = ('prefilter', 'filter_bits', 'partitions', 'kmer_min_qual', 'local_slots')      # not with --kmers-from
+_SLOTS_BESIDE = 'the input at a load factor of 0.5, capped by what the device budget leaves beside the resident %s'
+_PREFILTER_AS_CORRECT = ' (as `kbbq correct --prefilter`); needs --min-count >= 2 where given'
+_QUAL_OR_OQ = ': QUAL, or the OQ tag with -u'
 
 
-_MIN_QUAL_HELP = ('%s: count only the k-mers whose bases all have quality >= Q, 1..93 (default: every k-mer): the errors sit at the '
-                  'low-quality bases, so the table, sized from the counted k-mers, is several times smaller and the histogram\'s '
-                  'valley is cleaner.  The reads are corrected as read: a low-quality base is trusted through the k-mers other '
-                  'reads contributed.  The qualities are the ones the command reads%s')
+def _with_c(a):
+    return a.correct is not None
 
 
-_PASSES_HELP = ('%s: apply the k-mer rule to its own output this many times, 1..8 (default 1), read by read against the one table '
-                'counted from the reads as read: an error next to a read end or to another error is corrected once its '
-                'neighbour is')
+def _with_b_kmers(a):
+    return bool(a.kmers and a.bam is not None)
 
 
-_KMERS_FROM_HELP = ('%s: take the k-mers from this k-mer set (`kbbq count -o SET`) instead of counting the input\'s: k is the set\'s, '
-                    '--min-count (not below the set\'s --keep) or the first valley of the set\'s histogram is the threshold, --slots '
-                    'the table the set is loaded into; the same output as with the same k-mers counted here.  Not with the counting '
-                    'options --prefilter, --filter-bits, --partitions, --kmer-min-qual and --local-slots%s')
+def _with_kmers(a):
+    return a.kmers
 
 
-def _kmers_from(parser, args, needs=None):
-    """--kmers-from SET: its argparse errors, before the device or a process group is touched."""
-    if args.kmers_from is None:
-        return
-    if needs is not None and not needs[0]:
-        parser.error('--kmers-from: only with %s' % needs[1])
-    given = [flag for flag, v in (('--prefilter', args.prefilter or None), ('--filter-bits', args.filter_bits),
-                                  ('--partitions', args.partitions), ('--kmer-min-qual', args.kmer_min_qual),
-                                  ('--local-slots', getattr(args, 'local_slots', None))) if v is not None]
-    if given:
-        parser.error('%s: not with --kmers-from (counting options: the k-mers come counted)' % ', '.join(given))
+# command: options -- the k-mer options it takes, in the order of its --help; scope -- what its templates say before the colon
+# (help[dest]['scope']: what one option says instead); help[dest]['more'] -- the words of this command in one template;
+# default -- argparse defaults that are this command's own; always -- the optional keywords its library call gets given or not
+# (_kmer_kw); only_with -- (dests, is the mode on?, the mode's words): `FLAG, FLAG: only with WORDS`, in this order (_validate).
+_BOTH_MODES = 'with -c, or with -b --kmers'
+_COMMANDS = {
+    'recalibrate': dict(
+        options=('mixed_lengths', 'exclude_flags', 'kmer', 'min_count', 'slots', 'prefilter', 'filter_bits', 'fix_n', 'passes',
+                 'partitions', 'kmer_min_qual', 'kmers_from', 'skip_unresolved'),
+        scope='with -c',
+        help=dict(mixed_lengths=dict(scope='with -b --kmers'),
+                  exclude_flags=dict(scope='with -b --kmers', more='; they are still recalibrated and written like any other'),
+                  slots=dict(more=_SLOTS_BESIDE % 'reads'), prefilter=dict(more=_PREFILTER_AS_CORRECT),
+                  fix_n=dict(more=' that makes the most of the k-mers it alone breaks solid (as `kbbq correct --fix-n`)'),
+                  kmer_min_qual=dict(scope=_BOTH_MODES, more=': the FASTQ quality lines, QUAL, or the OQ tag with -u'),
+                  kmers_from=dict(scope=_BOTH_MODES), skip_unresolved=dict(more=' (as `kbbq bqsr --kmers --skip-unresolved`)')),
+        only_with=((('kmers_from',), lambda a: _with_c(a) or _with_b_kmers(a), '-c/--correct or with -b --kmers'),
+                   (('bam_out',), _with_b_kmers, '-b --kmers'),
+                   (('mixed_lengths', 'exclude_flags'), _with_b_kmers, '-b --kmers'),
+                   (('kmer_min_qual',), lambda a: _with_c(a) or _with_b_kmers(a), '-c/--correct or with -b --kmers'),
+                   (('kmers',), lambda a: a.bam is not None, '-b/--bam (-c/--correct corrects and recalibrates a FASTQ file)'),
+                   (('kmer', 'min_count', 'slots', 'prefilter', 'filter_bits', 'fix_n', 'passes', 'skip_unresolved', 'partitions'),
+                    lambda a: _with_c(a) or a.kmers, '-c/--correct'))),
+    'benchmark': dict(
+        options=('kmer', 'min_count', 'slots', 'prefilter', 'filter_bits', 'passes', 'partitions', 'kmer_min_qual', 'kmers_from'),
+        scope='with --kmers',
+        help=dict(slots=dict(more=_SLOTS_BESIDE % 'alignments'), prefilter=dict(more=_PREFILTER_AS_CORRECT),
+                  kmer_min_qual=dict(more=_QUAL_OR_OQ + '; a record without qualities is refused'),
+                  kmers_from=dict(more=': the set `bqsr --kmers --kmers-from` used can be scored here')),
+        only_with=((('kmers_from',), _with_kmers, '--kmers'),
+                   (('kmer', 'min_count', 'slots', 'prefilter', 'filter_bits', 'passes', 'partitions', 'kmer_min_qual'),
+                    _with_kmers, '--kmers'))),
+    'bqsr': dict(
+        options=('mixed_lengths', 'exclude_flags', 'kmer', 'min_count', 'slots', 'prefilter', 'filter_bits', 'skip_unresolved', 'passes',
+                 'partitions', 'kmer_min_qual', 'kmers_from'),
+        scope='with --kmers',
+        help=dict(slots=dict(more=_SLOTS_BESIDE % 'alignments'), prefilter=dict(more=_PREFILTER_AS_CORRECT),
+                  kmer_min_qual=dict(more=_QUAL_OR_OQ),
+                  kmers_from=dict(more=': a set counted from the raw FASTQ decides the errors of its alignments')),
+        only_with=((('kmers_from',), _with_kmers, '--kmers'),
+                   (('kmer', 'min_count', 'slots', 'prefilter', 'filter_bits', 'use_oq', 'passes', 'skip_unresolved', 'partitions',
+                     'mixed_lengths', 'exclude_flags', 'kmer_min_qual'), _with_kmers, '--kmers'))),
+    'correct': dict(
+        options=('kmer', 'min_count', 'slots', 'local_slots', 'prefilter', 'filter_bits', 'fix_n', 'passes', 'partitions',
+                 'kmer_min_qual', 'kmers_from'),
+        scope='',
+        help=dict(slots=dict(more='the input at a load factor of 0.5, capped by the device budget); under torch.distributed.run: the '
+                                  'slots of every rank\'s share of the k-mers (default: the input\'s k-mers / ranks * 9/8 at a load '
+                                  'factor of 0.5'),
+                  prefilter=dict(more=' with a bit filter passed over the reads first: the same output from a table several times '
+                                      'smaller, sized from the filter unless --slots is given; needs --min-count >= 2 where given; '
+                                      'one GPU only (not under torch.distributed.run)'),
+                  fix_n=dict(more=' (A, C, G or T) that makes the most of the k-mers it alone breaks solid; an N stays N on a tie or '
+                                  'when no letter makes a solid k-mer; a fixed N counts as a changed base'),
+                  passes=dict(scope='the whole rule (with --fix-n the N rule too)'), partitions=dict(scope='one GPU'),
+                  kmer_min_qual=dict(scope='one GPU or several', more=': the FASTQ quality lines'),
+                  kmers_from=dict(scope='one GPU or several', more='; under torch.distributed.run every rank loads the set')),
+        always=('local_slots', 'fix_n'),
+        only_with=()),
+    'count': dict(
+        options=('kmer', 'slots', 'prefilter', 'filter_bits', 'partitions', 'kmer_min_qual', 'exclude_flags'),
+        scope='',
+        help=dict(slots=dict(more='all inputs at a load factor of 0.5, capped by the device budget; with --partitions: the table of '
+                                  'one round'),
+                  prefilter=dict(more=' (as `kbbq correct --prefilter`): the filter pass runs over all inputs, then the count; the '
+                                      'same set'),
+                  filter_bits=dict(more='s'), partitions=dict(scope='every round over all inputs'),
+                  kmer_min_qual=dict(scope='every input', more=': the FASTQ quality lines, QUAL, or the OQ tag with -u'),
+                  exclude_flags=dict(scope='with -b')),
+        default=dict(kmer=31),
+        only_with=((('use_oq', 'exclude_flags'), lambda a: a.bam, '-b'),)),
+}
+
+
+def _add_kmer_options(parser, command, first=None, last=None):
+    """The k-mer options of `command` from the two tables, in the order of its row: all of them, or those from `first`
+    through `last` where options of the command's own stand in between."""
+    row = _COMMANDS[command]
+    options = row['options']
+    for dest in options[options.index(first) if first else 0:options.index(last) + 1 if last else None]:
+        flags, keywords, template = _KMER_OPTIONS[dest]
+        words = dict(dict(scope=row['scope'], more=''), **row['help'].get(dest, {}))
+        scope = words['scope']
+        text = template % {'scope': scope + ': ' if scope else '', 'with': scope + ' ' if scope else 'with ', 'more': words['more']}
+        if dest in row.get('default', {}):
+            keywords = dict(keywords, default=row['default'][dest])
+        parser.add_argument(*flags, help=text, **keywords)
+
+
+def _k(args):
+    return 31 if args.kmer is None else args.kmer
+
+
+def _filter_bits(args):
+    return 4 if args.filter_bits is None else args.filter_bits
+
+
+def _kmer_kw(args, command):
+    """The k-mer keywords of the library call `command` makes: k, min_count, slots, prefilter and filter_bits always; of the
+    other options the command takes those that were given (a flag that is on, a value, -F other than 0) and the row's `always`
+    -- without an option the call is the one it was before the option existed.  With --kmers-from k is the set's unless -k
+    names it: k=None."""
+    row = _COMMANDS[command]
+    kw = dict(k=_k(args), min_count=args.min_count, slots=args.slots, prefilter=args.prefilter, filter_bits=_filter_bits(args))
+    for dest in row['options']:
+        if dest in ('kmer', 'min_count', 'slots', 'prefilter', 'filter_bits'):
+            continue
+        value = getattr(args, dest)
+        if dest in row.get('always', ()) or not (value is None or value == 0):
+            kw[dest] = value
+    if 'kmers_from' in kw:
+        kw['k'] = args.kmer
+    return kw
+
+
+def _start(join=True):
+    """Before a command's first device work: join the process group if a launcher started this process (torch, RCCL; not
+    `count`, which never joins one); else, on one GPU with torch not imported and KBBQ_USE_TORCH unset, device memory,
+    page-locked slabs, copies and events come from the library's own C ABI (kbbq/_hipmem.py) and `import torch` (~1 s with
+    its HIP context) never happens.  True in that case."""
+    import os
+    import sys
+    world = 1
+    if join:
+        from . import parallel
+        world, _ = parallel.init_from_env()      # one process per GPU under torch.distributed.run; no-op otherwise
+    if world > 1 or 'torch' in sys.modules or os.environ.get('KBBQ_USE_TORCH'):
+        return False
+    from . import _device
+    _device.use_native_memory()
+    return True
 
 
 _ENDS_WITH_THE_COMMAND = False               # set by `python -m kbbq.main`: the process ends (main._leave) when the command has run
@@ -169,105 +328,50 @@ def _refuse_bam_out_ranks(args):
 
 def _recalibrate_bam_kmers(args):
     """`recalibrate -b ALN --kmers`: `bqsr --kmers` and `applybqsr` in one run (kbbq/recalibrate.py recalibrate_bam)."""
-    import os
     import sys
-    from . import kmer, parallel
-    kmers = dict(k=31 if args.kmer is None else args.kmer, min_count=args.min_count, slots=args.slots, prefilter=args.prefilter,
-                 filter_bits=4 if args.filter_bits is None else args.filter_bits)
-    if args.skip_unresolved:                     # without the flag or the option the call is the one without it, as `bqsr`'s
-        kmers['skip_unresolved'] = True
-    if args.passes is not None:
-        kmers['passes'] = args.passes
-    if args.partitions is not None:
-        kmers['partitions'] = args.partitions
-    if args.mixed_lengths:
-        kmers['mixed_lengths'] = True
-    if args.exclude_flags:
-        kmers['exclude_flags'] = args.exclude_flags
-    if args.kmer_min_qual is not None:
-        kmers['kmer_min_qual'] = args.kmer_min_qual
-    if args.kmers_from is not None:
-        kmers.update(kmers_from=args.kmers_from, k=args.kmer)                # k: the set's, unless -k names it
+    from . import kmer
+    kmers = _kmer_kw(args, 'recalibrate')
     records = {key: kmers[key] for key in ('mixed_lengths', 'exclude_flags') if key in kmers}
     # every rank of a launcher refuses here, before it joins the process group
     _refuse_bam_out_ranks(args)
     _recal.check_bam_kmers(args.bam, args.gatkreport, args.output, kmers['k'], kmers['min_count'], kmers['prefilter'],
                            kmers['filter_bits'], **{key: kmers[key] for key in ('partitions', 'passes', 'exclude_flags', 'kmers_from')
                                                     if key in kmers}, **_bam_out_kw(args))
-    parallel.init_from_env()
     from . import aln
     from ._trace import stage
     with stage('[recalibrate_bam, wall]'):
         with stage('parse'):
             bam = aln.AlignmentFile(args.bam)    # the one parse; what the records are refused for, before the device is touched
-        _recal.check_bam_records(bam, args.use_oq, 31 if kmers['k'] is None else kmers['k'], kmers['min_count'], kmers['prefilter'],
-                                 kmers['filter_bits'], **records)
-        if kmer._ranks() is None and 'torch' not in sys.modules and not os.environ.get('KBBQ_USE_TORCH'):
-            from . import _device
-            _device.use_native_memory()          # as `bqsr --kmers` on one GPU: no torch import
+        _recal.check_bam_records(bam, args.use_oq, _k(args), kmers['min_count'], kmers['prefilter'], kmers['filter_bits'], **records)
+        _start()                                 # no process group: check_bam_kmers has refused a launcher's ranks
         info = _recal.recalibrate_bam(bam, use_oq=args.use_oq, set_oq=args.set_oq, kmers=kmers, gatkreport=args.gatkreport,
                                       output=args.output, **args.quantize, **_bgzf_kw(args), **_bam_out_kw(args))
-    sys.stderr.write('kbbq recalibrate: k=%d min_count=%d reads=%d%s flagged_bases=%d%s%s%s%s%s%s\n'
-                     % (info['k'], info['min_count'], info['reads'],
-                        ' excluded_reads=%d' % info['excluded_reads'] if args.exclude_flags else '', info['flagged_bases'],
-                        ' skipped_bases=%d' % info['skipped_bases'] if args.skip_unresolved else '',
-                        ' passes=%d' % args.passes if (args.passes or 1) > 1 else '', kmer.partitions_field(info),
-                        kmer.min_qual_field(info),
-                        ' prefilter=1 admitted=%d slots=%d' % (info['admitted'], info['slots']) if args.prefilter else '',
-                        kmer.kmers_from_field(info)))
+    sys.stderr.write(kmer.summary_line('recalibrate', info, kmers, 'flagged_bases'))
 
 
 def recalibrate(args):
     import os
-    from . import parallel
     if args.kmers:
         return _recalibrate_bam_kmers(args)
     kopts = None
     if args.correct is not None:
-        kopts = dict(k=31 if args.kmer is None else args.kmer, min_count=args.min_count, slots=args.slots, prefilter=args.prefilter,
-                     filter_bits=4 if args.filter_bits is None else args.filter_bits)
-        if args.fix_n:                           # without the flag the call is the one it was
-            kopts['fix_n'] = True
-        if args.passes is not None:
-            kopts['passes'] = args.passes
-        if args.skip_unresolved:
-            kopts['skip_unresolved'] = True
-        if args.kmer_min_qual is not None:
-            kopts['kmer_min_qual'] = args.kmer_min_qual
-        if args.kmers_from is not None:
-            kopts.update(kmers_from=args.kmers_from, k=args.kmer)            # k: the set's, unless -k names it
-        more = {}
-        if args.partitions is not None:
-            kopts['partitions'] = args.partitions
-            more = dict(partitions=args.partitions)
+        kopts = _kmer_kw(args, 'recalibrate')
         # every rank of a launcher refuses here, before it joins the process group
-        _recal.check_corrected(args.correct, args.gatkreport, 31 if kopts['k'] is None else kopts['k'], kopts['min_count'],
-                               kopts['prefilter'], kopts['filter_bits'], **more)
-    world, _ = parallel.init_from_env()          # one process per GPU under torch.distributed.run; no-op otherwise
-    if world == 1 and 'torch' not in __import__('sys').modules and not os.environ.get('KBBQ_USE_TORCH'):
-        # one GPU: nothing of PyTorch is needed -- device memory, page-locked slabs, copies and events come from the library's
-        # own C ABI (kbbq/_hipmem.py) and `import torch` (~1 s with its HIP context) never happens
-        from . import _device, _hipmem, fastx
-        _device.use_native_memory()
-        if _ENDS_WITH_THE_COMMAND and not os.environ.get('KBBQ_SLOW_EXIT'):
-            # this process ends right after its last byte (_leave): what it holds goes with it instead of being returned piece by piece
-            _hipmem.cuda.keep_released_memory(True)
-            fastx.LEAVE_OPEN = True
+        _recal.check_corrected(args.correct, args.gatkreport, _k(args), kopts['min_count'], kopts['prefilter'], kopts['filter_bits'],
+                               **{key: kopts[key] for key in ('partitions',) if key in kopts})
+    if _start() and _ENDS_WITH_THE_COMMAND and not os.environ.get('KBBQ_SLOW_EXIT'):
+        # this process ends right after its last byte (_leave): what it holds goes with it instead of being returned piece by piece
+        from . import _hipmem, fastx
+        _hipmem.cuda.keep_released_memory(True)
+        fastx.LEAVE_OPEN = True
     if kopts is not None:
         import sys
         from ._trace import stage
         with stage('[recalibrate_corrected, wall]'):
             info = _recal.recalibrate_corrected(args.correct, infer_rg=args.infer_rg, gatkreport=args.gatkreport, output=args.output,
                                                 **kopts, **args.quantize, **_bgzf_kw(args))
-        from .kmer import kmers_from_field, min_qual_field, partitions_field
-        sys.stderr.write('kbbq recalibrate: k=%d min_count=%d reads=%d changed_bases=%d%s%s%s%s%s%s%s\n'
-                         % (info['k'], info['min_count'], info['reads'], info['changed_bases'],
-                            ' skipped_bases=%d' % info['skipped_bases'] if kopts.get('skip_unresolved') else '',
-                            ' fix_n=1' if kopts.get('fix_n') else '',
-                            ' passes=%d' % kopts['passes'] if kopts.get('passes', 1) > 1 else '', partitions_field(info),
-                            min_qual_field(info),
-                            ' prefilter=1 admitted=%d slots=%d' % (info['admitted'], info['slots']) if kopts['prefilter'] else '',
-                            kmers_from_field(info)))
+        from .kmer import summary_line
+        sys.stderr.write(summary_line('recalibrate', info, kopts))
         return
     _recal.recalibrate(bam=args.bam, fastq=args.fastq, infer_rg=args.infer_rg,
                        use_oq=args.use_oq, set_oq=args.set_oq, gatkreport=args.gatkreport, output=args.output, **args.quantize,
@@ -278,18 +382,7 @@ def benchmark(args):
     from . import benchmark as _bm
     from . import parallel
     parallel.init_from_env()          # one process per GPU under torch.distributed.run; no-op otherwise
-    kmers = {}
-    if args.kmers:                                                             # without the flag the call is what it was
-        kmers = dict(kmers=dict(k=31 if args.kmer is None else args.kmer, min_count=args.min_count, slots=args.slots,
-                                prefilter=args.prefilter, filter_bits=4 if args.filter_bits is None else args.filter_bits))
-        if args.passes is not None:
-            kmers['kmers']['passes'] = args.passes
-        if args.partitions is not None:
-            kmers['kmers']['partitions'] = args.partitions
-        if args.kmer_min_qual is not None:
-            kmers['kmers']['kmer_min_qual'] = args.kmer_min_qual
-        if args.kmers_from is not None:
-            kmers['kmers'].update(kmers_from=args.kmers_from, k=args.kmer)   # k: the set's, unless -k names it
+    kmers = dict(kmers=_kmer_kw(args, 'benchmark')) if args.kmers else {}      # without the flag the call is what it was
     _bm.benchmark(bamfile=args.bam, fafile=args.reference, vcffile=args.vcf, fastqfile=args.fastq,
                   label=args.label, use_oq=args.use_oq, bedfh=args.bedfile, **kmers)
 
@@ -307,39 +400,13 @@ def bqsr(args):
     from . import aln
     from .gatk import bqsr as _bqsr
     if args.kmers:
-        import os
         import sys
-        from . import kmer, parallel
-        parallel.init_from_env()             # under a launcher every rank joins its group, and bam_to_kmer_covariates refuses on each
-        if kmer._ranks() is None and 'torch' not in sys.modules and not os.environ.get('KBBQ_USE_TORCH'):
-            from . import _device
-            _device.use_native_memory()      # as `correct` on one GPU: no torch import
+        from . import kmer
+        _start()                             # under a launcher every rank joins its group, and bam_to_kmer_covariates refuses on each
         info = {}
-        skip = dict(skip_unresolved=True) if args.skip_unresolved else {}      # without the flag the call is what it was
-        more = dict(passes=args.passes) if args.passes is not None else {}     # ... and without this option
-        if args.partitions is not None:
-            more['partitions'] = args.partitions
-        if args.mixed_lengths:
-            more['mixed_lengths'] = True
-        if args.exclude_flags:
-            more['exclude_flags'] = args.exclude_flags
-        if args.kmer_min_qual is not None:
-            more['kmer_min_qual'] = args.kmer_min_qual
-        if args.kmers_from is not None:
-            more['kmers_from'] = args.kmers_from
-        _bqsr.bam_to_report_kmers(aln.AlignmentFile(args.bam),
-                                  k=args.kmer if args.kmers_from is not None or args.kmer is not None else 31, min_count=args.min_count,
-                                  slots=args.slots, prefilter=args.prefilter,
-                                  filter_bits=4 if args.filter_bits is None else args.filter_bits, use_oq=args.use_oq,
-                                  info=info, **skip, **more).write(args.gatkreport)
-        sys.stderr.write('kbbq bqsr: k=%d min_count=%d reads=%d%s flagged_bases=%d%s%s%s%s%s%s\n'
-                         % (info['k'], info['min_count'], info['reads'],
-                            ' excluded_reads=%d' % info['excluded_reads'] if args.exclude_flags else '', info['flagged_bases'],
-                            ' skipped_bases=%d' % info['skipped_bases'] if skip else '',
-                            ' passes=%d' % args.passes if (args.passes or 1) > 1 else '', kmer.partitions_field(info),
-                            kmer.min_qual_field(info),
-                            ' prefilter=1 admitted=%d slots=%d' % (info['admitted'], info['slots']) if args.prefilter else '',
-                            kmer.kmers_from_field(info)))
+        more = _kmer_kw(args, 'bqsr')
+        _bqsr.bam_to_report_kmers(aln.AlignmentFile(args.bam), use_oq=args.use_oq, info=info, **more).write(args.gatkreport)
+        sys.stderr.write(kmer.summary_line('bqsr', info, more, 'flagged_bases'))
         return
     from . import benchmark as _bm
     _bqsr.bam_to_report(aln.AlignmentFile(args.bam), args.reference, _bm.get_var_sites(args.vcf)).write(args.gatkreport)
@@ -348,45 +415,28 @@ def bqsr(args):
 def correct(args):
     import os
     import sys
-    if 'RANK' in os.environ:
-        from . import parallel
-        parallel.init_from_env()             # one process per GPU under torch.distributed.run; no-op for a single rank
-    elif int(os.environ.get('WORLD_SIZE', '1')) > 1:
+    if 'RANK' not in os.environ and int(os.environ.get('WORLD_SIZE', '1')) > 1:
         sys.exit('kbbq correct: WORLD_SIZE > 1 but no RANK: start one process per GPU with torch.distributed.run, or run '
                  'it on one GPU without WORLD_SIZE')
+    _start()
     from . import kmer
-    if 'torch' not in sys.modules and not os.environ.get('KBBQ_USE_TORCH'):
-        from . import _device
-        _device.use_native_memory()          # as `recalibrate` on one GPU: no torch import
-    more = dict(passes=args.passes) if args.passes is not None else {}         # without the option the call is what it was
-    if args.partitions is not None:
-        more['partitions'] = args.partitions
-    if args.kmer_min_qual is not None:
-        more['kmer_min_qual'] = args.kmer_min_qual
-    if args.kmers_from is not None:
-        more['kmers_from'] = args.kmers_from
-    kmer.main_correct(args.fastq, output=args.output, k=args.kmer if args.kmers_from is not None or args.kmer is not None else 31,
-                      min_count=args.min_count, slots=args.slots, local_slots=args.local_slots, prefilter=args.prefilter,
-                      filter_bits=4 if args.filter_bits is None else args.filter_bits, fix_n=args.fix_n, **more, **_bgzf_kw(args))
+    kmer.main_correct(args.fastq, output=args.output, **_kmer_kw(args, 'correct'), **_bgzf_kw(args))
 
 
 def count(args):
-    import os
-    import sys
     from . import kmerset
-    opts = dict(k=args.kmer, keep=args.keep, slots=args.slots, prefilter=args.prefilter,
-                filter_bits=4 if args.filter_bits is None else args.filter_bits, partitions=1 if args.partitions is None else args.partitions,
+    opts = dict(k=args.kmer, keep=args.keep, slots=args.slots, prefilter=args.prefilter, filter_bits=_filter_bits(args),
+                partitions=1 if args.partitions is None else args.partitions,
                 kmer_min_qual=args.kmer_min_qual, use_oq=args.use_oq, exclude_flags=args.exclude_flags or 0, histo=args.histo)
     # every rank of a launcher refuses here, before it joins a process group, and everything else count refuses on its arguments
     kmerset.check_count(args.fastq, args.bam, args.output, opts['k'], opts['keep'], opts['prefilter'], opts['filter_bits'],
                         opts['partitions'], opts['kmer_min_qual'], opts['use_oq'], opts['exclude_flags'])
-    if 'torch' not in sys.modules and not os.environ.get('KBBQ_USE_TORCH'):
-        from . import _device
-        _device.use_native_memory()          # as `correct` on one GPU: no torch import
+    _start(join=False)                       # check_count has refused a launcher's ranks
     kmerset.main_count(args.fastq, args.bam, args.output, **opts)
 
 
-def main(argv=None):
+def build_parser():
+    """The parser and its sub-parsers by command name."""
     parser = argparse.ArgumentParser(description='K-mer Based Base Quality score recalibration (MI355X build)')
     parser.add_argument('-v', '--version', action='version', version=__version__)
     sub = parser.add_subparsers(title='command', description='valid commands')
@@ -407,32 +457,7 @@ def main(argv=None):
                          '-g R` and `kbbq applybqsr -b ALN -g R` in one run over one parse and one upload of the file, the same SAM '
                          'text; takes the k-mer options below except --fix-n, and -u, -s, -g (the report is written there) and -o; '
                          'all records of one query length (unless --mixed-lengths), one GPU')
-    rp.add_argument('--mixed-lengths', action='store_true', help=_MIXED_HELP % 'with -b --kmers')
-    rp.add_argument('-F', '--exclude-flags', type=_exclude_flags, default=None, metavar='INT',
-                    help=_EXCLUDE_HELP % ('with -b --kmers', '; they are still recalibrated and written like any other'))
-    rp.add_argument('-k', '--kmer', type=int, default=None, help='with -c: k-mer length, 8..32 (default 31)')
-    rp.add_argument('--min-count', type=int, default=None,
-                    help='with -c: k-mers seen at least this often are solid (default: the first valley of the count histogram)')
-    rp.add_argument('--slots', type=int, default=None,
-                    help='with -c: hash table slots, a power of two (default: every k-mer of the input at a load factor of 0.5, '
-                         'capped by what the device budget leaves beside the resident reads)')
-    rp.add_argument('--prefilter', action='store_true',
-                    help='with -c: keep most k-mers seen once out of the table (as `kbbq correct --prefilter`); needs '
-                         '--min-count >= 2 where given')
-    rp.add_argument('--filter-bits', type=int, default=None,
-                    help='with -c --prefilter: bits per k-mer of the input in each of the filter\'s two arrays, 1..64 (default 4)')
-    rp.add_argument('--fix-n', action='store_true',
-                    help='with -c: give every N the letter that makes the most of the k-mers it alone breaks solid (as `kbbq '
-                         'correct --fix-n`)')
-    rp.add_argument('--passes', type=_passes, default=None, metavar='P', help=_PASSES_HELP % 'with -c')
-    rp.add_argument('--partitions', type=_partitions, default=None, metavar='P|auto', help=_PARTITIONS_HELP % 'with -c')
-    rp.add_argument('--kmer-min-qual', type=_min_qual, default=None, metavar='Q',
-                    help=_MIN_QUAL_HELP % ('with -c, or with -b --kmers', ': the FASTQ quality lines, QUAL, or the OQ tag with -u'))
-    rp.add_argument('--kmers-from', default=None, metavar='SET', help=_KMERS_FROM_HELP % ('with -c, or with -b --kmers', ''))
-    rp.add_argument('--skip-unresolved', action='store_true',
-                    help='with -c: leave a base out of the tally (neither error nor observation) when the k-mers contradict it but '
-                         'name no replacement -- two errors within k bases, thin coverage, contamination -- instead of counting '
-                         'it as correct (as `kbbq bqsr --kmers --skip-unresolved`)')
+    _add_kmer_options(rp, 'recalibrate')
     rp.add_argument('-u', '--use-oq', action='store_true',
                     help='Use the OQ tag for quality scores (BAM input only).')
     rp.add_argument('-s', '--set-oq', action='store_true',
@@ -466,23 +491,7 @@ def main(argv=None):
                          'the bases the alignments\' own k-mers flag as errors or leave unresolved beside the true errors, and '
                          'the quality each reading of the flags implies; a summary with precision and recall on stderr; one '
                          'GPU, not with -f')
-    bp.add_argument('-k', '--kmer', type=int, default=None, help='with --kmers: k-mer length, 8..32 (default 31)')
-    bp.add_argument('--min-count', type=int, default=None,
-                    help='with --kmers: k-mers seen at least this often are solid (default: the first valley of the count histogram)')
-    bp.add_argument('--slots', type=int, default=None,
-                    help='with --kmers: hash table slots, a power of two (default: every k-mer of the input at a load factor of '
-                         '0.5, capped by what the device budget leaves beside the resident alignments)')
-    bp.add_argument('--prefilter', action='store_true',
-                    help='with --kmers: keep most k-mers seen once out of the table (as `kbbq correct --prefilter`); needs '
-                         '--min-count >= 2 where given')
-    bp.add_argument('--filter-bits', type=int, default=None,
-                    help='with --kmers --prefilter: bits per k-mer of the input in each of the filter\'s two arrays, 1..64 (default 4)')
-    bp.add_argument('--passes', type=_passes, default=None, metavar='P', help=_PASSES_HELP % 'with --kmers')
-    bp.add_argument('--partitions', type=_partitions, default=None, metavar='P|auto', help=_PARTITIONS_HELP % 'with --kmers')
-    bp.add_argument('--kmer-min-qual', type=_min_qual, default=None, metavar='Q',
-                    help=_MIN_QUAL_HELP % ('with --kmers', ': QUAL, or the OQ tag with -u; a record without qualities is refused'))
-    bp.add_argument('--kmers-from', default=None, metavar='SET',
-                    help=_KMERS_FROM_HELP % ('with --kmers', ': the set `bqsr --kmers --kmers-from` used can be scored here'))
+    _add_kmer_options(bp, 'benchmark')
     bp.set_defaults(command=benchmark)
 
     ap = sub.add_parser('applybqsr', description='Recalibrate alignments with a GATK recalibration report (SAM output, or BAM '
@@ -512,65 +521,20 @@ def main(argv=None):
                     help='take the errors from the k-mer correction of the alignments\' own sequences (as `kbbq correct` decides '
                          'them) instead of a reference and known sites; all records of one query length (unless --mixed-lengths), '
                          'one GPU')
-    qp.add_argument('--mixed-lengths', action='store_true', help=_MIXED_HELP % 'with --kmers')
-    qp.add_argument('-F', '--exclude-flags', type=_exclude_flags, default=None, metavar='INT', help=_EXCLUDE_HELP % ('with --kmers', ''))
-    qp.add_argument('-k', '--kmer', type=int, default=None, help='with --kmers: k-mer length, 8..32 (default 31)')
-    qp.add_argument('--min-count', type=int, default=None,
-                    help='with --kmers: k-mers seen at least this often are solid (default: the first valley of the count histogram)')
-    qp.add_argument('--slots', type=int, default=None,
-                    help='with --kmers: hash table slots, a power of two (default: every k-mer of the input at a load factor of '
-                         '0.5, capped by what the device budget leaves beside the resident alignments)')
-    qp.add_argument('--prefilter', action='store_true',
-                    help='with --kmers: keep most k-mers seen once out of the table (as `kbbq correct --prefilter`); needs '
-                         '--min-count >= 2 where given')
-    qp.add_argument('--filter-bits', type=int, default=None,
-                    help='with --kmers --prefilter: bits per k-mer of the input in each of the filter\'s two arrays, 1..64 (default 4)')
+    _add_kmer_options(qp, 'bqsr', last='filter_bits')
     qp.add_argument('-u', '--use-oq', action='store_true', help='with --kmers: qualities from the OQ tag instead of QUAL')
-    qp.add_argument('--skip-unresolved', action='store_true',
-                    help='with --kmers: leave a base out of the tally (neither error nor observation) when the k-mers contradict '
-                         'it but name no replacement -- two errors within k bases, thin coverage, contamination -- instead of '
-                         'counting it as correct')
-    qp.add_argument('--passes', type=_passes, default=None, metavar='P', help=_PASSES_HELP % 'with --kmers')
-    qp.add_argument('--partitions', type=_partitions, default=None, metavar='P|auto', help=_PARTITIONS_HELP % 'with --kmers')
-    qp.add_argument('--kmer-min-qual', type=_min_qual, default=None, metavar='Q',
-                    help=_MIN_QUAL_HELP % ('with --kmers', ': QUAL, or the OQ tag with -u'))
-    qp.add_argument('--kmers-from', default=None, metavar='SET',
-                    help=_KMERS_FROM_HELP % ('with --kmers', ': a set counted from the raw FASTQ decides the errors of its alignments'))
+    _add_kmer_options(qp, 'bqsr', first='skip_unresolved')
     qp.set_defaults(command=bqsr)
 
     cp = sub.add_parser('correct', description='Correct substitution errors of a FASTQ file with k-mer counts (GPU); the output '
                         'is the error-corrected file `recalibrate -f` takes')
     cp.add_argument('-f', '--fastq', required=True, help='FASTQ file to correct (plain or .gz)')
-    cp.add_argument('-k', '--kmer', type=int, default=None, help='k-mer length, 8..32 (default 31)')
-    cp.add_argument('--min-count', type=int, default=None,
-                    help='k-mers seen at least this often are solid (default: the first valley of the count histogram)')
-    cp.add_argument('--slots', type=int, default=None,
-                    help='hash table slots, a power of two (default: every k-mer of the input at a load factor of 0.5, '
-                         'capped by the device budget); under torch.distributed.run: the slots of every rank\'s share of the '
-                         'k-mers (default: the input\'s k-mers / ranks * 9/8 at a load factor of 0.5)')
-    cp.add_argument('--local-slots', type=int, default=None,
-                    help='under torch.distributed.run: slots of the table every rank counts its own reads into before they go '
-                         'to the ranks that own them, a power of two (default: the rank\'s k-mers at a load factor of 0.5, '
-                         'capped by half the device budget); a smaller table counts the reads in several rounds')
-    cp.add_argument('--prefilter', action='store_true',
-                    help='keep most k-mers seen once out of the table with a bit filter passed over the reads first: the same '
-                         'output from a table several times smaller, sized from the filter unless --slots is given; needs '
-                         '--min-count >= 2 where given; one GPU only (not under torch.distributed.run)')
-    cp.add_argument('--filter-bits', type=int, default=None,
-                    help='with --prefilter: bits per k-mer of the input in each of the filter\'s two arrays, 1..64 (default 4)')
-    cp.add_argument('--fix-n', action='store_true',
-                    help='give every N the letter (A, C, G or T) that makes the most of the k-mers it alone breaks solid; an N '
-                         'stays N on a tie or when no letter makes a solid k-mer; a fixed N counts as a changed base')
-    cp.add_argument('--passes', type=_passes, default=None, metavar='P', help=_PASSES_HELP % 'the whole rule (with --fix-n the N rule too)')
-    cp.add_argument('--partitions', type=_partitions, default=None, metavar='P|auto', help=_PARTITIONS_HELP % 'one GPU')
-    cp.add_argument('--kmer-min-qual', type=_min_qual, default=None, metavar='Q',
-                    help=_MIN_QUAL_HELP % ('one GPU or several', ': the FASTQ quality lines'))
+    _add_kmer_options(cp, 'correct', last='kmer_min_qual')
     cp.add_argument('-o', '--output', default=None,
                     help='Write the corrected FASTQ to this file instead of stdout; under torch.distributed.run every rank '
                          'writes FILE.rankNNNN, to be concatenated in rank order.')
     cp.add_argument('--bgzf', action='store_true', help=_BGZF_HELP)
-    cp.add_argument('--kmers-from', default=None, metavar='SET',
-                    help=_KMERS_FROM_HELP % ('one GPU or several', '; under torch.distributed.run every rank loads the set'))
+    _add_kmer_options(cp, 'correct', first='kmers_from')
     cp.set_defaults(command=correct)
 
     np_ = sub.add_parser('count', description='Count the k-mers of one or several FASTQ and alignment files into one k-mer set (GPU): '
@@ -582,103 +546,68 @@ def main(argv=None):
                      help='SAM or BAM files, counted as `kbbq bqsr --kmers` counts its input: every base of SEQ, soft clips included; '
                           'records of any lengths')
     np_.add_argument('-o', '--output', default=None, metavar='SET', help='the k-mer set to write; an existing file is refused')
-    np_.add_argument('-k', '--kmer', type=int, default=31, help='k-mer length, 8..32 (default 31)')
+    _add_kmer_options(np_, 'count', last='kmer')
     np_.add_argument('--keep', type=int, default=2,
                      help='write the k-mers seen at least this often (default 2, the smallest threshold the histogram\'s valley can '
                           'give); a --min-count below it cannot be served from the set; >= 2 with --prefilter')
-    np_.add_argument('--slots', type=int, default=None,
-                     help='hash table slots, a power of two (default: every k-mer of all inputs at a load factor of 0.5, capped by '
-                          'the device budget; with --partitions: the table of one round)')
-    np_.add_argument('--prefilter', action='store_true',
-                     help='keep most k-mers seen once out of the table (as `kbbq correct --prefilter`): the filter pass runs over all '
-                          'inputs, then the count; the same set')
-    np_.add_argument('--filter-bits', type=int, default=None,
-                     help='with --prefilter: bits per k-mer of the inputs in each of the filter\'s two arrays, 1..64 (default 4)')
-    np_.add_argument('--partitions', type=_partitions, default=None, metavar='P|auto',
-                     help=_PARTITIONS_HELP % 'every round over all inputs')
-    np_.add_argument('--kmer-min-qual', type=_min_qual, default=None, metavar='Q',
-                     help=_MIN_QUAL_HELP % ('every input', ': the FASTQ quality lines, QUAL, or the OQ tag with -u'))
+    _add_kmer_options(np_, 'count', first='slots', last='kmer_min_qual')
     np_.add_argument('-u', '--use-oq', action='store_true', help='with -b and --kmer-min-qual: gate by the OQ tag instead of QUAL')
-    np_.add_argument('-F', '--exclude-flags', type=_exclude_flags, default=None, metavar='INT', help=_EXCLUDE_HELP % ('with -b', ''))
+    _add_kmer_options(np_, 'count', first='exclude_flags')
     np_.add_argument('--histo', default=None, metavar='FILE',
                      help='write the count histogram as `count<TAB>k-mers` lines for counts --keep..256 (the last line: 256 and more), '
                           'the shape Jellyfish prints and GenomeScope reads')
     np_.set_defaults(command=count)
+    return parser, dict(recalibrate=rp, benchmark=bp, applybqsr=ap, bqsr=qp, correct=cp, count=np_)
 
-    args = parser.parse_args(argv)
-    if args.command is correct:
-        _kmers_from(cp, args)
-    elif args.command is recalibrate:
-        _kmers_from(rp, args, (args.correct is not None or (args.kmers and args.bam is not None), '-c/--correct or with -b --kmers'))
-    elif args.command is bqsr or args.command is benchmark:
-        _kmers_from(qp if args.command is bqsr else bp, args, (args.kmers, '--kmers'))
-    elif args.command is count:
-        # decided here: before the device is touched and, under a launcher, before a process group could exist
+
+def _validate(parsers, args):
+    """What the parser refuses of a parsed command line, with exit status 2: decided here, before the device is touched and,
+    under a launcher, before a process group could exist.  Sets args.quantize for the commands that apply a model."""
+    name = args.command.__name__
+    if name not in parsers:
+        return
+    parser, rows = parsers[name], _COMMANDS.get(name, {}).get('only_with', ())
+    flag = {action.dest: '/'.join(action.option_strings) for action in parser._actions}
+
+    def given(dests):
+        values = ((dest, getattr(args, dest, None)) for dest in dests)
+        return [flag[dest] for dest, value in values if value is not None and value is not False]     # -F 0 is given
+
+    def only_with(rows):
+        for dests, mode, words in rows:
+            if given(dests) and not mode(args):
+                parser.error('%s: only with %s' % (', '.join(given(dests)), words))
+
+    if given(('kmers_from',)):
+        only_with(row for row in rows if row[0] == ('kmers_from',))
+        if given(_COUNTING_OPTIONS):
+            parser.error('%s: not with --kmers-from (counting options: the k-mers come counted)' % ', '.join(given(_COUNTING_OPTIONS)))
+    if name == 'count':
         if not args.fastq and not args.bam:
-            np_.error('at least one input is required: -f FASTQ [FASTQ ...] and / or -b ALN [ALN ...]')
+            parser.error('at least one input is required: -f FASTQ [FASTQ ...] and / or -b ALN [ALN ...]')
         if args.output is None:
-            np_.error('the following arguments are required: -o/--output')
-        given = [flag for flag, v in (('-u/--use-oq', args.use_oq or None), ('-F/--exclude-flags', args.exclude_flags)) if v is not None]
-        if given and not args.bam:
-            np_.error('%s: only with -b' % ', '.join(given))
-    if args.command is recalibrate or args.command is applybqsr:
-        # decided here: before the device is touched and, under a launcher, before the process group exists
-        args.quantize = _quantize(rp if args.command is recalibrate else ap, args)
+            parser.error('the following arguments are required: -o/--output')
+    if name in ('recalibrate', 'applybqsr'):
+        args.quantize = _quantize(parser, args)
         if args.bam_out and args.bgzf:
-            (rp if args.command is recalibrate else ap).error('--bam-out: not with --bgzf (a BAM file is a BGZF file already)')
-        if args.bam_out and args.command is recalibrate and not (args.kmers and args.bam is not None):
-            rp.error('--bam-out: only with -b --kmers')
-    if args.command is recalibrate and not (args.kmers and args.bam is not None):
-        given = [flag for flag, v in (('--mixed-lengths', args.mixed_lengths or None), ('-F/--exclude-flags', args.exclude_flags))
-                 if v is not None]
-        if given:
-            rp.error('%s: only with -b --kmers' % ', '.join(given))
-    if args.command is recalibrate and args.kmer_min_qual is not None and args.correct is None \
-            and not (args.kmers and args.bam is not None):
-        rp.error('--kmer-min-qual: only with -c/--correct or with -b --kmers')
-    if args.command is recalibrate and args.kmers:
-        if args.bam is None:
-            rp.error('--kmers: only with -b/--bam (-c/--correct corrects and recalibrates a FASTQ file)')
-        given = [flag for flag, v in (('--fix-n', args.fix_n), ('--infer-rg', args.infer_rg)) if v]
-        if given:
-            rp.error('%s: not with -b --kmers (FASTQ input only)' % ', '.join(given))
-    elif args.command is recalibrate and args.correct is None:
-        given = [flag for flag, v in (('-k/--kmer', args.kmer), ('--min-count', args.min_count), ('--slots', args.slots),
-                                      ('--prefilter', args.prefilter or None), ('--filter-bits', args.filter_bits),
-                                      ('--fix-n', args.fix_n or None), ('--passes', args.passes),
-                                      ('--skip-unresolved', args.skip_unresolved or None),
-                                      ('--partitions', args.partitions)) if v is not None]
-        if given:
-            rp.error('%s: only with -c/--correct' % ', '.join(given))
-    if args.command is benchmark:
-        if args.kmers:
-            if args.fastq is not None:
-                bp.error('-f/--fastq: not with --kmers (the k-mers are those of the alignments\' own sequences)')
-        else:
-            given = [flag for flag, v in (('-k/--kmer', args.kmer), ('--min-count', args.min_count), ('--slots', args.slots),
-                                          ('--prefilter', args.prefilter or None), ('--filter-bits', args.filter_bits),
-                                          ('--passes', args.passes), ('--partitions', args.partitions),
-                                          ('--kmer-min-qual', args.kmer_min_qual)) if v is not None]
-            if given:
-                bp.error('%s: only with --kmers' % ', '.join(given))
-    if args.command is bqsr:
-        if args.kmers:
-            given = [flag for flag, v in (('-r/--reference', args.reference), ('-v/--vcf', args.vcf)) if v is not None]
-            if given:
-                qp.error('%s: not with --kmers (its errors come from the alignments\' own k-mers)' % ', '.join(given))
-        else:
-            given = [flag for flag, v in (('-k/--kmer', args.kmer), ('--min-count', args.min_count), ('--slots', args.slots),
-                                          ('--prefilter', args.prefilter or None), ('--filter-bits', args.filter_bits),
-                                          ('-u/--use-oq', args.use_oq or None),
-                                          ('--skip-unresolved', args.skip_unresolved or None), ('--passes', args.passes),
-                                          ('--partitions', args.partitions), ('--mixed-lengths', args.mixed_lengths or None),
-                                          ('-F/--exclude-flags', args.exclude_flags), ('--kmer-min-qual', args.kmer_min_qual))
-                     if v is not None]
-            if given:
-                qp.error('%s: only with --kmers' % ', '.join(given))
-            missing = [flag for flag, v in (('-r/--reference', args.reference), ('-v/--vcf', args.vcf)) if v is None]
-            if missing:
-                qp.error('the following arguments are required: %s' % ', '.join(missing))
+            parser.error('--bam-out: not with --bgzf (a BAM file is a BGZF file already)')
+    only_with(rows)
+    if name == 'recalibrate' and args.kmers and given(('fix_n', 'infer_rg')):
+        parser.error('%s: not with -b --kmers (FASTQ input only)' % ', '.join(given(('fix_n', 'infer_rg'))))
+    if name == 'benchmark' and args.kmers and args.fastq is not None:
+        parser.error('-f/--fastq: not with --kmers (the k-mers are those of the alignments\' own sequences)')
+    if name == 'bqsr':
+        if args.kmers and given(('reference', 'vcf')):
+            parser.error('%s: not with --kmers (its errors come from the alignments\' own k-mers)' % ', '.join(given(('reference', 'vcf'))))
+        missing = [flag[dest] for dest in ('reference', 'vcf') if getattr(args, dest) is None]
+        if not args.kmers and missing:
+            parser.error('the following arguments are required: %s' % ', '.join(missing))
+
+
+def main(argv=None):
+    parser, parsers = build_parser()
+    args = parser.parse_args(argv)
+    _validate(parsers, args)
     args.command(args)
 
 
