@@ -1114,7 +1114,9 @@ int kbbq_bgzf_eof(uint8_t* out);
  * below a whole BGZF block; stream_bytes is what d_stream holds.  Synchronous.  *bad_row = the lowest row with a new quality
  * below 0 (an output character below 33: SAM text holds it, BAM does not), -1 when there is none: the stream is then not to be
  * used.  A descriptor that reaches outside the skeleton, the stream or a row writes nothing and is KBBQ_E_ARG.
- * kbbq_bam_assemble: the same over host memory, by the same per-record code (csrc/kbbq_bam_out.h bo_record).                    */
+ * kbbq_bam_assemble: the same over host memory, by the same per-record code (csrc/kbbq_bam_out.h bo_record).
+ * kbbq_bam_index_dev / kbbq_bam_index ("BAM index", below) read the same skeleton and descriptors after the assemble call: the
+ * index of the file is reduced from them, in offsets of this stream.                                                           */
 #define KBBQ_BAM_QUAL_PLANE    0
 #define KBBQ_BAM_QUAL_SKELETON 1
 typedef struct kbbq_bam_desc {
@@ -1130,6 +1132,49 @@ int kbbq_bam_assemble_dev(kbbq_ctx* ctx, const uint8_t* d_skel, size_t skel_byte
                           size_t stream_bytes, int64_t* bad_row);
 int kbbq_bam_assemble(const uint8_t* skel, size_t skel_bytes, const kbbq_bam_desc* desc, int64_t n, const uint8_t* seq,
                       const uint8_t* qplane, int pitch, uint8_t* stream, size_t carry, size_t stream_bytes, int64_t* bad_row);
+
+/* ---- BAM index (--bam-index; csrc/kbbq_bam_index.h, kbbq/_bamindex.py; the executable model: tests/bam_index_model.py) ---------
+ * THE INDEX of a --bam-out file, BAI (SAM specification 5.2) or CSI (min_shift 14, depth the smallest >= 5 with 2^(14 + 3 *
+ * depth) >= the largest LN, l_aux 0, BGZF-compressed by kbbq_bgzf_deflate* plus the EOF block).  auto: BAI when every LN <= 2^29.
+ * No byte parity with samtools is claimed; the file is a valid index by the specifications, defined by these rules.
+ * Record extent: beg = pos (0-based; below 0: 0), end = beg + the reference span of the CIGAR (M D N = X), at least beg + 1.  A
+ * placed unmapped read (flag 4 with a refID) is indexed like any other with end = beg + 1.
+ * Bin: reg2bin(beg, end, 14, depth), computed here (the record's bin field covers depth 5 only).  A record with refID < 0
+ * enters no bin and counts into n_no_coor.
+ * Virtual offsets: with u an absolute offset of the uncompressed stream, voffset(u) = coff[u / 65280] << 16 | u % 65280, coff[b]
+ * the file offset of BGZF block b and coff[nblocks] that of the EOF block (what htslib's bgzf_tell gives behind a record that
+ * ends on a block boundary).  A record's chunk is [voffset(start), voffset(start + 4 + block_size)).
+ * Chunks of a bin: one per maximal run of consecutive records of one (refID, bin), in file order; neighbouring chunks of one bin
+ * are then merged where the earlier one's end and the later one's begin lie in one compressed block (end >> 16 >= beg >> 16:
+ * htslib's rule).  The bins of a reference are written in ascending bin number, the pseudo-bin last.
+ * Linear index (BAI): ceil(max(LN, 1) / 16384) + 1 windows per reference; a window holds the lowest record-start voffset over
+ * the records that overlap it, the window index clamped to the reference's last (a record overhanging LN is kept); n_intv = the
+ * last non-empty window + 1; an empty window below that takes the value of the next non-empty one above it.  CSI loffset of a
+ * bin: that backfilled value at the bin's first 16 kb window (clamped likewise; 0 behind the last non-empty window).
+ * Metadata pseudo-bin (37450 for BAI, ((1 << (3 * depth + 3)) - 1) / 7 + 1 for CSI), for every reference with records: the pairs
+ * (ref_beg, ref_end) as voffsets and (n_mapped, n_unmapped).  The file ends with n_no_coor.  A header-only BAM gives n_ref empty
+ * references.  The input must be in coordinate order: (refID as unsigned, pos) non-decreasing -- checked by the caller.
+ * kbbq_bam_index_dev: one slab, after kbbq_bam_assemble_dev over the same skeleton and descriptors and on the same stream.  All
+ * offsets are absolute offsets of the uncompressed stream (stream_base: where the descriptors' stream_off 0 lies); the host
+ * converts (monotone).  d_lin_off[n_ref + 1]: the prefix sum of the references' window counts; d_linear[d_lin_off[n_ref]]: the
+ * file-long linear array, all ones before the first slab, min(start) per window after (64-bit atomicMin).  runs (host memory,
+ * cap >= n entries): one 32-byte run per maximal run of one (refID, bin) within the slab, refID -1 for records without a
+ * coordinate; *n_runs their number -- only they and three words come back, per-record entries never do.  The caller joins a slab's
+ * first run with the last of the slab before when (refID, bin) agree.  *bad_row = the lowest row that does not fit (its head
+ * outside the skeleton, its CIGAR outside its head, a refID >= n_ref, an end beyond 2^(14 + 3 * depth)), -1 when there is none;
+ * such a row touches no window, the call is KBBQ_E_ARG and the runs are not to be used.  Synchronous.  depth in 5..8.
+ * kbbq_bam_index: the same over host memory, by the same per-record code (csrc/kbbq_bam_index.h bix_entry).                     */
+typedef struct kbbq_bam_run {
+    int32_t ref; uint32_t bin;
+    uint64_t beg, end;                   /* stream offsets: the first record's start, the last record's end */
+    uint32_t n_mapped, n_unmapped;
+} kbbq_bam_run;
+extern int kbbq_bam_index_dev(kbbq_ctx* ctx, const uint8_t* d_skel, size_t skel_bytes, const kbbq_bam_desc* d_desc, int64_t n,
+                              uint64_t stream_base, int depth, const uint64_t* d_lin_off, int n_ref, uint64_t* d_linear,
+                              kbbq_bam_run* runs, int64_t cap, int64_t* n_runs, int64_t* bad_row);
+extern int kbbq_bam_index(const uint8_t* skel, size_t skel_bytes, const kbbq_bam_desc* desc, int64_t n, uint64_t stream_base,
+                          int depth, const uint64_t* lin_off, int n_ref, uint64_t* linear, kbbq_bam_run* runs, int64_t cap,
+                          int64_t* n_runs, int64_t* bad_row);
 
 /* ---- BGZF input: inflate on the GPU (csrc/kbbq_bgzf_inflate.h, csrc/bam_host.cpp kbbq_inflate_all, kbbq/_bgzf.py inflate) -------
  * A BGZF file is a row of gzip members of at most 64 KiB in and 64 KiB out, each naming its own compressed size (BSIZE), CRC32

@@ -15,6 +15,7 @@
 #include "kbbq_kmer_set.h"
 #include "kbbq_bgzf.h"
 #include "kbbq_bam_out.h"
+#include "kbbq_bam_index.h"
 #include "kbbq_bgzf_inflate.h"
 #include "bam_host.h"
 #include "../../include/kbbq_hip.h"
@@ -79,6 +80,7 @@ struct kbbq_ctx {
     DevScratch bgzf_off;              // ... the blocks' offsets in the packed output, and its length
     DevScratch bgzf_blocks;           // kbbq_bgzf_deflate (host buffers): a slab's blocks before they are packed
     DevScratch bam_words;             // kbbq_bam_assemble_dev: the lowest row with a quality below 0, the lowest that does not fit
+    DevScratch bam_index;             // kbbq_bam_index_dev: words, keys, runs, lengths, head rows, workgroup totals (csrc/kbbq_bam_index.h)
     // kbbq_inflate_bgzf: staging and a stream of its own -- a reader may inflate on a thread of its own while the context's other
     // staging is in use -- and the lock that makes it one call at a time
     void* inflate_host[2] = {nullptr, nullptr}; void* inflate_dev[2] = {nullptr, nullptr}; size_t inflate_bytes = 0;
@@ -235,7 +237,7 @@ int kbbq_ctx_destroy(kbbq_ctx* c)
         for (auto& pr : c->ev[w]) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
     if (c->d_status) (void)hipFree(c->d_status);
     if (c->d_stats) (void)hipFree(c->d_stats);
-    for (DevScratch* s : {&c->wgplan, &c->ops4, &c->tally, &c->rowlut, &c->bgzf_tok, &c->bgzf_off, &c->bgzf_blocks, &c->bam_words})
+    for (DevScratch* s : {&c->wgplan, &c->ops4, &c->tally, &c->rowlut, &c->bgzf_tok, &c->bgzf_off, &c->bgzf_blocks, &c->bam_words, &c->bam_index})
         if (s->p) (void)hipFree(s->p);
     for (int b = 0; b < 2; ++b) {
         if (c->stage_host[b]) (void)hipHostFree(c->stage_host[b]);
@@ -3444,6 +3446,106 @@ int kbbq_bam_assemble(const uint8_t* skel, size_t skel_bytes, const kbbq_bam_des
         }
     });
     for (int64_t v : lowest) if (v >= 0 && (*bad_row < 0 || v < *bad_row)) *bad_row = v;
+    return KBBQ_OK;
+}
+
+} // extern "C"
+
+// ---- BAM index (csrc/kbbq_bam_index.h) ----------------------------------------------------------------------------------------
+static int bam_index_args(const char* who, const void* skel, const void* desc, int64_t n, int depth, const void* lin_off, int n_ref,
+                          const void* linear, const void* runs, int64_t cap, int64_t* n_runs, int64_t* bad_row)
+{
+    if (bad_row) *bad_row = -1;
+    if (n_runs) *n_runs = 0;
+    if (!bad_row || !n_runs) return fail(KBBQ_E_ARG, "%s: NULL result pointer", who);
+    if (n < 0 || n > (int64_t)INT_MAX) return fail(KBBQ_E_ARG, "%s: n must be in 0..2^31 - 1", who);
+    if (depth < 5 || depth > 8) return fail(KBBQ_E_ARG, "%s: depth must be in 5..8, got %d", who, depth);
+    if (n_ref < 0) return fail(KBBQ_E_ARG, "%s: n_ref is negative", who);
+    if (n > 0 && (!skel || !desc || !lin_off || !runs || (n_ref > 0 && !linear))) return fail(KBBQ_E_ARG, "%s: NULL buffer", who);
+    if (cap < n) return fail(KBBQ_E_ARG, "%s: room for %lld runs, a slab of %lld records can need as many", who, (long long)cap, (long long)n);
+    if ((uintptr_t)desc & 3) return fail(KBBQ_E_ARG, "%s: the descriptors must be 4-byte aligned", who);
+    if (((uintptr_t)lin_off | (uintptr_t)linear | (uintptr_t)runs) & 7) return fail(KBBQ_E_ARG, "%s: lin_off, linear and runs must be 8-byte aligned", who);
+    return KBBQ_OK;
+}
+
+static constexpr const char* BAM_INDEX_NO_FIT = "%s: row %lld does not fit (its head outside the skeleton, its CIGAR outside its head, "
+                                                "a refID beyond the references, or an end beyond 2^(14 + 3 * depth))";
+
+extern "C" {
+
+int kbbq_bam_index_dev(kbbq_ctx* c, const uint8_t* d_skel, size_t skel_bytes, const kbbq_bam_desc* d_desc, int64_t n,
+                       uint64_t stream_base, int depth, const uint64_t* d_lin_off, int n_ref, uint64_t* d_linear,
+                       kbbq_bam_run* runs, int64_t cap, int64_t* n_runs, int64_t* bad_row)
+{
+    int rc = bam_index_args("kbbq_bam_index_dev", d_skel, d_desc, n, depth, d_lin_off, n_ref, d_linear, runs, cap, n_runs, bad_row);
+    if (rc) return rc;
+    if (!c) return fail(KBBQ_E_ARG, "kbbq_bam_index_dev: ctx is NULL");
+    if (n == 0) return KBBQ_OK;
+    HIPCHK(hipSetDevice(c->device));
+    // scratch: [words 4 x u32 | lin_total u64 | key u64 n | runs 32 n | length u32 n | head_row u32 n | head_unm u32 n | block uint2]
+    const size_t nb = ((size_t)n + BIX_THREADS - 1) / BIX_THREADS;
+    const size_t at_key = 32, at_runs = at_key + 8 * (size_t)n, at_len = at_runs + sizeof(kbbq_bam_run) * (size_t)n,
+                 at_row = at_len + 4 * (size_t)n, at_unm = at_row + 4 * (size_t)n, at_block = (at_unm + 4 * (size_t)n + 7) / 8 * 8;
+    rc = grow_scratch(c, c->bam_index, at_block + sizeof(uint2) * nb);
+    if (rc) return rc;
+    uint8_t* s = (uint8_t*)c->bam_index.p;
+    uint64_t lin_total = 0;
+    HIPCHK(hipMemcpyAsync(&lin_total, d_lin_off + n_ref, sizeof lin_total, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemsetAsync(s, 0xFF, sizeof(u32), c->stream));
+    HIPCHK(hipMemsetAsync(s + sizeof(u32), 0, 3 * sizeof(u32), c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    BixParams p{d_skel, d_desc, d_lin_off, d_linear, (u64)skel_bytes, (u64)stream_base, lin_total, (u32)n, (u32)n_ref, depth,
+                (uint64_t*)(s + at_key), (u32*)(s + at_len), (uint2*)(s + at_block), (u32*)(s + at_row), (u32*)(s + at_unm),
+                (kbbq_bam_run*)(s + at_runs), (u32*)s};
+    hipLaunchKernelGGL(kbi_entries, dim3((unsigned)nb), dim3(BIX_THREADS), 0, c->stream, p);
+    hipLaunchKernelGGL(kbi_count, dim3((unsigned)nb), dim3(BIX_THREADS), 0, c->stream, p);
+    hipLaunchKernelGGL(kbi_scan, dim3(1), dim3(BIX_THREADS), 0, c->stream, p, (u32)nb);
+    hipLaunchKernelGGL(kbi_heads, dim3((unsigned)nb), dim3(BIX_THREADS), 0, c->stream, p);
+    hipLaunchKernelGGL(kbi_runs, dim3((unsigned)nb), dim3(BIX_THREADS), 0, c->stream, p);
+    HIPCHK(hipGetLastError());
+    u32 words[4] = {0, 0, 0, 0};
+    HIPCHK(hipMemcpyAsync(words, s, sizeof words, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (words[0] != ~0u) {
+        *bad_row = (int64_t)words[0];
+        return fail(KBBQ_E_ARG, BAM_INDEX_NO_FIT, "kbbq_bam_index_dev", (long long)words[0]);
+    }
+    if (words[1] == 0 || (int64_t)words[1] > n) return fail(KBBQ_E_HIP, "kbbq_bam_index_dev: %u runs of %lld records", words[1], (long long)n);
+    HIPCHK(hipMemcpyAsync(runs, s + at_runs, sizeof(kbbq_bam_run) * (size_t)words[1], hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    *n_runs = (int64_t)words[1];
+    return KBBQ_OK;
+}
+
+int kbbq_bam_index(const uint8_t* skel, size_t skel_bytes, const kbbq_bam_desc* desc, int64_t n, uint64_t stream_base, int depth,
+                   const uint64_t* lin_off, int n_ref, uint64_t* linear, kbbq_bam_run* runs, int64_t cap, int64_t* n_runs,
+                   int64_t* bad_row)
+{
+    int rc = bam_index_args("kbbq_bam_index", skel, desc, n, depth, lin_off, n_ref, linear, runs, cap, n_runs, bad_row);
+    if (rc) return rc;
+    if (n == 0) return KBBQ_OK;
+    const uint64_t lin_total = lin_off[n_ref];
+    std::vector<BixEntry> entries((size_t)n);
+    for (int64_t r = 0; r < n; ++r)                                      // nothing is touched when a row does not fit
+        if (!bix_entry(desc[r], skel, skel_bytes, depth, n_ref, entries[(size_t)r])) {
+            *bad_row = r;
+            return fail(KBBQ_E_ARG, BAM_INDEX_NO_FIT, "kbbq_bam_index", (long long)r);
+        }
+    int64_t count = 0;
+    for (int64_t r = 0; r < n; ++r) {
+        const BixEntry& e = entries[(size_t)r];
+        const uint64_t start = stream_base + desc[r].stream_off;
+        if (e.ref >= 0)
+            bix_windows(e, lin_off, start, [&](uint64_t at, uint64_t v) { if (at < lin_total && v < linear[at]) linear[at] = v; });
+        if (r == 0 || ((bix_key(e) ^ bix_key(entries[(size_t)r - 1])) & BIX_RUN_MASK) != 0) {
+            kbbq_bam_run& run = runs[count++];
+            run.ref = e.ref; run.bin = e.bin; run.beg = start; run.n_mapped = run.n_unmapped = 0;
+        }
+        kbbq_bam_run& run = runs[count - 1];
+        run.end = start + e.length;
+        ++(e.unmapped ? run.n_unmapped : run.n_mapped);
+    }
+    *n_runs = count;
     return KBBQ_OK;
 }
 

@@ -19,6 +19,14 @@ every slab, before any byte of the slab reaches the sink -- ValueError with .rea
 h2d_bytes (header, skeletons, descriptors), d2h_bytes (compressed blocks), stream_bytes and file_bytes count what moved, as
 BgzfWriter counts text_bytes / file_bytes.  deflate=: a function text -> BGZF blocks in the place of the GPU; the planes are then
 NumPy arrays and the records are assembled by the host twin (kbbq_bam_assemble) -- the tests' stand-in.
+
+index= (--bam-index: 'auto', 'bai' or 'csi'; kbbq/_bamindex.py, include/kbbq_hip.h "BAM index"): the file's index, made in the
+same pass.  header() decides the format and lays the file-long linear array out on the device; after a slab is assembled the
+index kernels (kbbq_bam_index_dev; kbbq_bam_index with deflate=) read the same skeleton and descriptors and send back one
+32-byte run per (refID, bin) run of the slab; the compressed sizes of the blocks are read off the packed bytes on their way to
+the sink; close() downloads the linear array, serialises (a CSI through the same deflate call) and leaves the bytes in
+index_data -- with index_path, in index_path + '.bai' / '.csi'.  index_bytes, index_runs, index_d2h_bytes count it.  Without
+index= nothing of this is touched or launched.
 """
 import ctypes
 import io
@@ -59,6 +67,25 @@ class _HostEngine:
     def deflate(self, buf, lo, n):
         return self.fn(memoryview(buf)[lo:lo + n])
 
+    # ---- index=: the linear array in plain memory, kbbq_bam_index
+    def index_open(self, lin_off):
+        self.lin_off = np.ascontiguousarray(lin_off, dtype=np.uint64)
+        self.linear = np.full(max(int(lin_off[-1]), 1), 0xFFFFFFFFFFFFFFFF, dtype=np.uint64)
+
+    def index_slab(self, d_stage, desc_bytes, skel_bytes, n, base, depth):
+        from . import _native as N
+        runs = np.empty(n * N.BAM_RUN_BYTES, dtype=np.uint8)
+        count, bad = ctypes.c_int64(0), ctypes.c_int64(-1)
+        N.check(N.load().kbbq_bam_index(N.ptr(d_stage[desc_bytes:]), skel_bytes, N.ptr(d_stage), n, base, depth, N.ptr(self.lin_off),
+                                        len(self.lin_off) - 1, N.ptr(self.linear), N.ptr(runs), n, ctypes.byref(count), ctypes.byref(bad)))
+        return runs[:count.value * N.BAM_RUN_BYTES], 0
+
+    def index_linear(self):
+        return self.linear[:int(self.lin_off[-1])], 0
+
+    def pack(self, data):
+        return bytes(self.fn(memoryview(data))) if len(data) else b''
+
     def close(self):
         pass
 
@@ -71,7 +98,7 @@ class _GpuEngine:
         self.dev, self.t = dev, dev._torch()
         self.device = self.t.cuda.current_device()
         self.piece = slab_blocks() * BLOCK
-        self.scratch = self.d_stage = None
+        self.scratch = self.d_stage = self.d_lin_off = self.d_linear = None
 
     def buffer(self, nbytes):
         return self.t.empty(int(nbytes), dtype=self.t.uint8, device='cuda')
@@ -117,8 +144,38 @@ class _GpuEngine:
         out[:total.value].copy_(d_packed[:total.value])
         return memoryview(out.numpy())[:total.value]
 
+    # ---- index=: the linear array and the references' window offsets in device memory, kbbq_bam_index_dev
+    def index_open(self, lin_off):
+        self.n_ref, self.windows = len(lin_off) - 1, int(lin_off[-1])
+        self.d_lin_off = self.buffer(8 * len(lin_off))
+        self.put(self.d_lin_off, 0, np.ascontiguousarray(lin_off, dtype=np.uint64).view(np.uint8))
+        self.d_linear = self.buffer(8 * max(self.windows, 1))
+        self.put(self.d_linear, 0, np.full(8 * max(self.windows, 1), 0xFF, dtype=np.uint8))
+
+    def index_slab(self, d_stage, desc_bytes, skel_bytes, n, base, depth):
+        N = self.dev.N
+        ctx = self.dev.context(self.device)
+        runs = np.empty(n * N.BAM_RUN_BYTES, dtype=np.uint8)
+        count, bad = ctypes.c_int64(0), ctypes.c_int64(-1)
+        N.check(N.load().kbbq_bam_index_dev(ctx.handle, N.ptr(d_stage.data_ptr() + desc_bytes), skel_bytes, N.ptr(d_stage), n, base,
+                                            depth, N.ptr(self.d_lin_off), self.n_ref, N.ptr(self.d_linear), N.ptr(runs), n,
+                                            ctypes.byref(count), ctypes.byref(bad)))
+        return runs[:count.value * N.BAM_RUN_BYTES], count.value * N.BAM_RUN_BYTES + 24     # the runs, four words, the window total
+
+    def index_linear(self):
+        return self.d_linear.cpu().numpy().view(np.uint64)[:self.windows].copy(), 8 * self.windows
+
+    def pack(self, data):
+        out = []
+        for lo in range(0, len(data), self.piece):
+            part = np.frombuffer(data, dtype=np.uint8, count=min(self.piece, len(data) - lo), offset=lo).copy()
+            d_text = self.buffer((len(part) + 15) // 16 * 16)
+            self.put(d_text, 0, part)
+            out.append(bytes(self.deflate(d_text, 0, len(part))))
+        return b''.join(out)
+
     def close(self):
-        self.scratch = self.d_stage = None
+        self.scratch = self.d_stage = self.d_lin_off = self.d_linear = None
         self.dev.release_pinned('bamout')
 
 
@@ -126,7 +183,7 @@ class BamWriter:
     """header(bam), records(...) slab by slab, close() over the binary sink `raw` (see the module's text).  A context manager:
     leaving it on an exception closes the sink without the carry and without the EOF block.  close_raw: close() closes `raw` too."""
 
-    def __init__(self, raw, close_raw=False, deflate=None):
+    def __init__(self, raw, close_raw=False, deflate=None, index=None, index_path=None):
         if raw is None or isinstance(raw, io.TextIOBase) or not hasattr(raw, 'write'):
             raise ValueError('--bam-out writes bytes: the sink must be a binary file (a text-only stdout cannot take it)')
         self._raw, self._close_raw = raw, close_raw
@@ -135,6 +192,11 @@ class BamWriter:
         self._buf, self._carry = None, 0
         self.closed = False
         self.h2d_bytes = self.d2h_bytes = self.stream_bytes = self.file_bytes = 0
+        # index= ('auto', 'bai', 'csi'): header() decides the format; close() leaves the file's bytes in index_data and, with
+        # index_path, writes them to index_path + '.bai' / '.csi'
+        self._index_kind, self._index_path, self._index = index, index_path, None
+        self.index_format = self.index_data = None
+        self.index_bytes = self.index_runs = self.index_d2h_bytes = 0
 
     def __enter__(self):
         return self
@@ -161,6 +223,8 @@ class BamWriter:
         for lo in range(0, whole, self._piece):
             packed = self._engine.deflate(self._buf, lo, min(self._piece, whole - lo))
             self._raw.write(packed)
+            if self._index is not None:
+                self._index.blocks(packed)
             self.d2h_bytes += len(packed)
             self.file_bytes += len(packed)
         if whole and total > whole:
@@ -181,6 +245,13 @@ class BamWriter:
         N.check(lib.kbbq_bam_header(native, None, 0, ctypes.byref(need)))
         head = np.empty(need.value, dtype=np.uint8)
         N.check(lib.kbbq_bam_header(native, N.ptr(head), head.nbytes, ctypes.byref(need)))
+        if self._index_kind is not None:
+            from . import _bamindex
+            if self._index is not None or self.stream_bytes:
+                raise ValueError('index=: the header is written once, before the records')
+            self.index_format, depth = _bamindex.resolve(self._index_kind, bam.header)
+            self._index = _bamindex.Index(self.index_format, depth, [ln for _, ln, _ in _bamindex.references(bam.header)])
+            self._engine.index_open(self._index.lin_off)
         self._room(self._carry + head.nbytes)
         self._engine.put(self._buf, self._carry, head)
         self.h2d_bytes += head.nbytes
@@ -217,8 +288,32 @@ class BamWriter:
                              % (first + bad))
             exc.read_index = first + bad
             raise exc
+        if self._index_kind is not None:
+            if self._index is None:
+                raise ValueError('index=: records before the header (the index needs the @SQ lines)')
+            runs, back = self._engine.index_slab(d_stage, desc_bytes, skel_bytes.value, n, self.stream_bytes, self._index.depth)
+            self._index.runs(runs.view(self._index_run_dtype()))
+            self.index_d2h_bytes += back
         self.stream_bytes += stream_bytes.value
         self._drain(total)
+
+    @staticmethod
+    def _index_run_dtype():
+        from . import _bamindex
+        return _bamindex.RUN
+
+    def _write_index(self):
+        """Before the EOF block is written: file_bytes is its offset."""
+        from . import _bamindex
+        linear, back = self._engine.index_linear()
+        self.index_d2h_bytes += back
+        data = self._index.data(linear, self.file_bytes)
+        if self.index_format == 'csi':
+            data = self._engine.pack(data) + EOF
+        self.index_data, self.index_bytes, self.index_runs = data, len(data), self._index.n_runs
+        if self._index_path is not None:
+            with open(_bamindex.index_path(self._index_path, self.index_format), 'wb') as fh:
+                fh.write(data)
 
     def _finish(self):
         self.closed = True
@@ -233,6 +328,8 @@ class BamWriter:
         try:
             if self._carry:
                 self._drain(self._carry, last=True)
+            if self._index is not None:
+                self._write_index()
             self._raw.write(EOF)
             self.file_bytes += len(EOF)
             self._raw.flush()
@@ -254,11 +351,11 @@ def check(bam, lo=0, hi=None):
         raise
 
 
-def open_sink(path):
-    """A BamWriter over the binary file `path`."""
+def open_sink(path, index=None):
+    """A BamWriter over the binary file `path`; index: its index beside it (path + '.bai' / '.csi')."""
     raw = open(path, 'wb')
     try:
-        return BamWriter(raw, close_raw=True)
+        return BamWriter(raw, close_raw=True) if index is None else BamWriter(raw, close_raw=True, index=index, index_path=path)
     except BaseException:
         raw.close()
         raise

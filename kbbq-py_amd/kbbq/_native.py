@@ -34,6 +34,7 @@ CONFUSION_MAX_BASES = (1 << 32) - 1   # KBBQ_CONFUSION_MAX_BASES: nreads * pitch
 BGZF_BLOCK_MAX, BGZF_SLOT, BGZF_EOF_BYTES = 65280, 65536, 28   # KBBQ_BGZF_*: text of a block, a block's slot before packing, the EOF block
 BAM_QUAL_PLANE, BAM_QUAL_SKELETON = 0, 1   # KBBQ_BAM_QUAL_*: kbbq_bam_desc.qual_src
 BAM_DESC_WORDS = 6                         # kbbq_bam_desc: skel_off, head_bytes, tail_bytes, l_seq, stream_off, qual_src (uint32 each)
+BAM_RUN_BYTES = 32                         # kbbq_bam_run: ref i32, bin u32, beg u64, end u64, n_mapped u32, n_unmapped u32
 
 NQ = 43
 NDINUC = 16
@@ -237,6 +238,8 @@ PROTOTYPES = {
     'kbbq_bam_skeleton': (_i, [_vp, _i64, _i64, _i, _vp, _vp, _sz]),
     'kbbq_bam_assemble_dev': (_i, [_vp, _vp, _sz, _vp, _i64, _vp, _vp, _i, _vp, _sz, _sz, _c.POINTER(_i64)]),
     'kbbq_bam_assemble': (_i, [_vp, _sz, _vp, _i64, _vp, _vp, _i, _vp, _sz, _sz, _c.POINTER(_i64)]),
+    'kbbq_bam_index_dev': (_i, [_vp, _vp, _sz, _vp, _i64, _u64, _i, _vp, _i, _vp, _vp, _i64, _c.POINTER(_i64), _c.POINTER(_i64)]),
+    'kbbq_bam_index': (_i, [_vp, _sz, _vp, _i64, _u64, _i, _vp, _i, _vp, _vp, _i64, _c.POINTER(_i64), _c.POINTER(_i64)]),
 }
 
 

@@ -486,14 +486,39 @@ def write_alignments_bam(bam, meanq, rgdq, qdq, posdq, dndq, rg_to_int, writer, 
     LAST_RUN.update(mode='lut' if model[0] == 0 else 'f64', alignments=hi - lo)
 
 
-def write_bam_file(bam, output, write):
+def check_bam_index(bam, output, index):
+    """What --bam-index refuses of a parsed file, before the output exists: no file name (an index of stdout has no name), a
+    reference too long for `bai`, alignments out of coordinate order or beyond the index's reach (kbbq._bamindex)."""
+    from .. import _bamindex
+    if output is None:
+        raise ValueError('--bam-index needs -o FILE: the index is written beside it (FILE.bai / FILE.csi)')
+    _, depth = _bamindex.resolve(index, bam.header)
+    _bamindex.check(bam, depth)
+
+
+def write_bam_file(bam, output, write, index=None):
     """The BAM file of a command: kbbq._bamout.check (ValueError before the file exists), then write(writer) into a BamWriter
-    over `output`, or over stdout for None.  LAST_RUN['bam_out']: the closed writer's counters."""
+    over `output`, or over stdout for None.  LAST_RUN['bam_out']: the closed writer's counters.  index (--bam-index: auto, bai,
+    csi): check_bam_index, then the file's index beside it, made in the same pass; its counters join the others."""
     from .. import _bamout
     _bamout.check(bam)
-    with (_bamout.stdout_sink() if output is None else _bamout.open_sink(output)) as writer:
+    if index is not None:
+        check_bam_index(bam, output, index)
+    with (_bamout.stdout_sink() if output is None else _bamout.open_sink(output, **({} if index is None else {'index': index}))) as writer:
         write(writer)
-    LAST_RUN['bam_out'] = {key: getattr(writer, key) for key in ('h2d_bytes', 'd2h_bytes', 'stream_bytes', 'file_bytes')}
+    LAST_RUN['bam_out'] = {key: getattr(writer, key) for key in ('h2d_bytes', 'd2h_bytes', 'stream_bytes', 'file_bytes')
+                           + (() if index is None else ('index_bytes', 'index_runs', 'index_d2h_bytes'))}
+
+
+def check_bam_index_options(bam_index, bam_out, output):
+    """What --bam-index refuses of its command's options."""
+    from .. import _bamindex
+    if bam_index not in _bamindex.KINDS:
+        raise ValueError('--bam-index: one of %s, got %r' % (', '.join(_bamindex.KINDS), bam_index))
+    if not bam_out:
+        raise ValueError('--bam-index: only with --bam-out (it indexes the BAM file that option writes)')
+    if output is None:
+        raise ValueError('--bam-index needs -o FILE: the index is written beside it (FILE.bai / FILE.csi)')
 
 
 BAM_OUT_RANKS = ('--bam-out does not run across ranks in this version (one BAM file is one stream of blocks): on one GPU, or '
@@ -516,17 +541,21 @@ def _report_model(bam, report):
 
 
 @_bgzf.option
-def apply_report(bam, report_path, use_oq=False, set_oq=False, output=None, quantize=None, bam_out=False):
+def apply_report(bam, report_path, use_oq=False, set_oq=False, output=None, quantize=None, bam_out=False, bam_index=None):
     """`kbbq applybqsr`: report -> model (table_to_vectors, get_delta_qs on the device) -> kbbq_apply_aligned -> SAM text, to
     `output` or stdout.  Under torch.distributed.run every rank takes parallel.shard_range of the alignments and writes
     output.rankNNNN, the header in rank 0's file only, so that the files concatenated in rank order are the single-process
     output.  Without bam_out an output name ending in .bam is refused.  quantize: the 256-byte map of quantize_map
     (--static-quantized-quals); per byte, so the rank files concatenated stay the one-process bytes.
     bam_out (--bam-out): the same records as a BAM file, whatever its name (write_alignments_bam); one process only, not with
-    bgzf; what BAM cannot hold is a ValueError before the file is created (kbbq._bamout.check)."""
+    bgzf; what BAM cannot hold is a ValueError before the file is created (kbbq._bamout.check).
+    bam_index (--bam-index: auto, bai or csi): with bam_out and an output name, the file's BAI / CSI index beside it, reduced on
+    the GPU in the same pass (kbbq/_bamindex.py); the alignments must be in coordinate order."""
     import sys
     from .. import aln, parallel
     quantize = _check_qmap(quantize)
+    if bam_index is not None:
+        check_bam_index_options(bam_index, bam_out, output)
     if bam_out:
         if _bgzf.enabled():
             raise ValueError('--bam-out: not with --bgzf (a BAM file is a BGZF file already)')
@@ -541,7 +570,8 @@ def apply_report(bam, report_path, use_oq=False, set_oq=False, output=None, quan
         kw = dict(use_oq=use_oq, set_oq=set_oq)
         if quantize is not None:
             kw['quantize'] = quantize
-        write_bam_file(bam, output, lambda writer: write_alignments_bam(bam, *model, rg_to_int, writer, **kw))
+        write_bam_file(bam, output, lambda writer: write_alignments_bam(bam, *model, rg_to_int, writer, **kw),
+                       **({} if bam_index is None else {'index': bam_index}))
         return
     world, rank = parallel.world_rank()
     if world > 1 and output is None:

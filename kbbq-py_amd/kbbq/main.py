@@ -179,7 +179,7 @@ _COMMANDS = {
                   kmer_min_qual=dict(scope=_BOTH_MODES, more=': the FASTQ quality lines, QUAL, or the OQ tag with -u'),
                   kmers_from=dict(scope=_BOTH_MODES), skip_unresolved=dict(more=' (as `kbbq bqsr --kmers --skip-unresolved`)')),
         only_with=((('kmers_from',), lambda a: _with_c(a) or _with_b_kmers(a), '-c/--correct or with -b --kmers'),
-                   (('bam_out',), _with_b_kmers, '-b --kmers'),
+                   (('bam_out', 'bam_index'), _with_b_kmers, '-b --kmers'),
                    (('mixed_lengths', 'exclude_flags'), _with_b_kmers, '-b --kmers'),
                    (('kmer_min_qual',), lambda a: _with_c(a) or _with_b_kmers(a), '-c/--correct or with -b --kmers'),
                    (('kmers',), lambda a: a.bam is not None, '-b/--bam (-c/--correct corrects and recalibrates a FASTQ file)'),
@@ -313,9 +313,19 @@ _BAM_OUT_HELP = ('Write the output (-o, or stdout) as a BAM file, whatever its n
                  'Without the option the output is SAM text and a .bam name is refused.')
 
 
+_BAM_INDEX_HELP = ('With --bam-out and -o FILE: write the index of the BAM file beside it in the same pass, reduced on the GPU while '
+                   'the records are assembled: FILE.bai (bai), FILE.csi (csi: for references over 2^29 = 512 Mbp, which a BAI cannot '
+                   'index), or whichever the @SQ lines call for (auto, the default of a bare --bam-index).  The alignments must be '
+                   'in coordinate order; an existing index is overwritten.')
+
+
 def _bam_out_kw(args):
-    """{'bam_out': True} with --bam-out, else {}: without the option every call is the one it was."""
-    return {'bam_out': True} if getattr(args, 'bam_out', False) else {}
+    """{'bam_out': True} with --bam-out and {'bam_index': KIND} with --bam-index, else {}: without an option every call is the
+    one it was."""
+    kw = {'bam_out': True} if getattr(args, 'bam_out', False) else {}
+    if getattr(args, 'bam_index', None) is not None:
+        kw['bam_index'] = args.bam_index
+    return kw
 
 
 def _refuse_bam_out_ranks(args):
@@ -468,6 +478,8 @@ def build_parser():
                          'torch.distributed.run every rank writes FILE.rankNNNN, to be concatenated in rank order.')
     rp.add_argument('--bgzf', action='store_true', help=_BGZF_HELP)
     rp.add_argument('--bam-out', action='store_true', help='with -b --kmers: ' + _BAM_OUT_HELP)
+    rp.add_argument('--bam-index', nargs='?', const='auto', default=None, choices=('auto', 'bai', 'csi'),
+                    help='with -b --kmers: ' + _BAM_INDEX_HELP)
     rp.add_argument('--infer-rg', action='store_true',
                     help='Infer the read group from the FASTQ read name (name_RG:Z:id).')
     rp.add_argument('--static-quantized-quals', type=_quant_levels, action='append', default=None, metavar='Q[,Q...]',
@@ -503,6 +515,7 @@ def build_parser():
                          'under torch.distributed.run every rank writes FILE.rankNNNN, to be concatenated in rank order.')
     ap.add_argument('--bgzf', action='store_true', help=_BGZF_HELP)
     ap.add_argument('--bam-out', action='store_true', help=_BAM_OUT_HELP)
+    ap.add_argument('--bam-index', nargs='?', const='auto', default=None, choices=('auto', 'bai', 'csi'), help=_BAM_INDEX_HELP)
     ap.add_argument('-u', '--use-oq', action='store_true', help='Recalibrate the OQ tag\'s qualities instead of QUAL.')
     ap.add_argument('-s', '--set-oq', action='store_true', help="Keep the qualities as read in an 'OQ' tag where there is none.")
     ap.add_argument('--static-quantized-quals', type=_quant_levels, action='append', default=None, metavar='Q[,Q...]',
@@ -592,6 +605,11 @@ def _validate(parsers, args):
         if args.bam_out and args.bgzf:
             parser.error('--bam-out: not with --bgzf (a BAM file is a BGZF file already)')
     only_with(rows)
+    if name in ('recalibrate', 'applybqsr') and args.bam_index is not None:
+        if not args.bam_out:
+            parser.error('--bam-index: only with --bam-out (it indexes the BAM file that option writes)')
+        if args.output is None:
+            parser.error('--bam-index: needs -o FILE (an index of stdout has no name; it is written to FILE.bai or FILE.csi)')
     if name == 'recalibrate' and args.kmers and given(('fix_n', 'infer_rg')):
         parser.error('%s: not with -b --kmers (FASTQ input only)' % ', '.join(given(('fix_n', 'infer_rg'))))
     if name == 'benchmark' and args.kmers and args.fastq is not None:

@@ -883,11 +883,12 @@ def _as_bam_kmers(exc):
 
 
 def check_bam_kmers(bam, gatkreport=None, output=None, k=31, min_count=None, prefilter=False, filter_bits=4, partitions=1, passes=1,
-                    exclude_flags=0, kmer_min_qual=None, kmers_from=None, bam_out=False):
+                    exclude_flags=0, kmer_min_qual=None, kmers_from=None, bam_out=False, bam_index=None):
     """What recalibrate_bam refuses of its options, before the alignments are read, before any device work and, under a
     launcher, before the process group exists: a process group, what `bqsr --kmers` refuses of the k-mer options (the same
     exception types), an output name ending in .bam (without bam_out) and a report that exists.  kmers_from: k may then be None
-    (the set's), and a counting option is refused (kmer.check_kmers_from).  bam_out: not with --bgzf."""
+    (the set's), and a counting option is refused (kmer.check_kmers_from).  bam_out: not with --bgzf.  bam_index: only with
+    bam_out and an output name."""
     from . import kmer
     from .gatk import bqsr
     if parallel.launched_from_env() or kmer._ranks() is not None:
@@ -912,6 +913,8 @@ def check_bam_kmers(bam, gatkreport=None, output=None, k=31, min_count=None, pre
         raise ValueError('--bam-out: not with --bgzf (a BAM file is a BGZF file already)')
     if not bam_out and output is not None and str(output).lower().endswith('.bam'):
         raise ValueError('%s writes SAM text; BAM output (%s) is not supported' % (_BAM_KMERS, output))
+    if bam_index is not None:
+        applybqsr.check_bam_index_options(bam_index, bam_out, output)
     if gatkreport is not None and os.path.exists(gatkreport):
         raise ValueError('%s: the report %s exists: its model would replace the tally of the alignments\' own k-mers; give the '
                          'name of a report to write, or apply the report with `kbbq applybqsr`' % (_BAM_KMERS, gatkreport))
@@ -931,7 +934,8 @@ def check_bam_records(bam, use_oq=False, k=31, min_count=None, prefilter=False, 
 
 
 @_bgzf.option
-def recalibrate_bam(bam, use_oq=False, set_oq=False, kmers=None, gatkreport=None, output=None, quantize=None, bam_out=False):
+def recalibrate_bam(bam, use_oq=False, set_oq=False, kmers=None, gatkreport=None, output=None, quantize=None, bam_out=False,
+                    bam_index=None):
     """Without kmers: not implemented, as in the reference.
     bam: a path, or an aln.AlignmentFile.  kmers (a dict of bam_to_kmer_covariates' k-mer options: k, min_count, slots, prefilter, filter_bits, skip_unresolved, passes,
     partitions, mixed_lengths, exclude_flags, kmer_min_qual, kmers_from (a k-mer set file in the place of the count; k may then be None) -- a record that exclude_flags leaves out of the model is still recalibrated and
@@ -946,7 +950,9 @@ def recalibrate_bam(bam, use_oq=False, set_oq=False, kmers=None, gatkreport=None
     the report and the OQ tag of set_oq do not see it.  Returns `bqsr --kmers`'s info; LAST_RUN['aligned']: alignments, pitch, h2d_plane_bytes and planes, the planes
     that went to the device.  bam_out (--bam-out): the same records as a BAM file, whatever its name
     (gatk.applybqsr.write_alignments_bam): the resident SEQ plane and the apply's output plane are read where they lie; what BAM
-    cannot hold is a ValueError before the tally and before the report or the file is created (kbbq._bamout.check)."""
+    cannot hold is a ValueError before the tally and before the report or the file is created (kbbq._bamout.check).
+    bam_index (--bam-index: auto, bai or csi; with bam_out and an output name): the file's index beside it, as
+    gatk.applybqsr.apply_report makes it; alignments out of coordinate order are refused there too, before the tally."""
     if kmers is None:
         raise NotImplementedError('Recalibrating a bam is not yet implemented. '
                                   'Convert the BAM to FASTQ with `samtools fastq` first.')
@@ -965,7 +971,7 @@ def recalibrate_bam(bam, use_oq=False, set_oq=False, kmers=None, gatkreport=None
     check_bam_kmers(bam, gatkreport, output, opts['k'], opts['min_count'], opts['prefilter'], opts['filter_bits'],
                     opts['partitions'], opts['passes'], **{key: records[key] for key in ('exclude_flags',) if key in records},
                     **kmer._min_qual_kw(opts['kmer_min_qual']), **kmer._kmers_from_kw(opts['kmers_from']),
-                    **({'bam_out': True} if bam_out else {}))
+                    **({'bam_out': True} if bam_out else {}), **({} if bam_index is None else {'bam_index': bam_index}))
     given_k = opts['k']
     if opts['kmers_from'] is not None and given_k is None:
         opts['k'] = 31                           # for the refusals of the records; the tally takes the set's
@@ -977,6 +983,8 @@ def recalibrate_bam(bam, use_oq=False, set_oq=False, kmers=None, gatkreport=None
     if bam_out:
         from . import _bamout
         _bamout.check(bam)
+        if bam_index is not None:
+            applybqsr.check_bam_index(bam, output, bam_index)
     info = {}
     with stage('k-mer tally', sync=True):
         vectors, resident = bqsr._kmer_tally(bam, inputs, given_k if given_k is None else int(given_k), opts['min_count'],
@@ -1002,7 +1010,8 @@ def recalibrate_bam(bam, use_oq=False, set_oq=False, kmers=None, gatkreport=None
         kw['quantize'] = quantize
     with stage('apply + render'):
         if bam_out:
-            applybqsr.write_bam_file(bam, output, lambda writer: applybqsr.write_alignments_bam(bam, *model, rg_to_int, writer, **kw))
+            applybqsr.write_bam_file(bam, output, lambda writer: applybqsr.write_alignments_bam(bam, *model, rg_to_int, writer, **kw),
+                                     **({} if bam_index is None else {'index': bam_index}))
         elif output is None and _bgzf.enabled():
             with _bgzf.stdout_sink() as sink:
                 applybqsr.write_alignments(bam, *model, rg_to_int, sink, **kw)
