@@ -13,6 +13,7 @@
 #include "raw_vector.h"
 
 #include "../../include/kbbq_hip.h"
+#include "kbbq_lib_host.h"
 
 // Inflate a whole gzip / BGZF file image (any number of members).  false + err on corrupt input.
 // BGZF of KBBQ_GPU_INFLATE_MIN_BYTES or more goes through the device (kbbq_inflate_bgzf_indexed_) when a context has been registered
@@ -25,13 +26,12 @@ bool kbbq_inflate_all(const uint8_t* src, size_t n, kbbq_bytes& out, std::string
 bool kbbq_inflate_blocks_host(const uint8_t* src, const kbbq_bgzf_block* blocks, const uint32_t* which, size_t count, uint8_t* out,
                               size_t work, std::string& err);
 
-// The device route of an indexed stream (kbbq_hip.hip kbbq_inflate_bgzf_indexed_), handed over with its context by
+// The device route of an indexed stream (kbbq_bgzf.hip kbbq_inflate_bgzf_indexed_), handed over with its context by
 // kbbq_inflate_use_ctx: this file calls nothing of the GPU half by name and links without it.  kbbq_ctx_destroy takes the context back.
 typedef int (*kbbq_inflate_route)(kbbq_ctx* c, const uint8_t* src, size_t n, const kbbq_bgzf_block* blocks, size_t nblocks, uint8_t* out,
                                   kbbq_inflate_stats* stats, bool* data_error);
 void kbbq_inflate_set_route_(kbbq_ctx* c, kbbq_inflate_route route);
 void kbbq_inflate_forget_ctx_(kbbq_ctx* c);
-int kbbq_set_error_(int code, const char* msg);
 
 // Uncompressed BAM image -> SAM text (header lines, then one line per record).  false + err on malformed input.
 bool kbbq_bam_to_sam(const uint8_t* bam, size_t n, kbbq_bytes& text, std::string& err);

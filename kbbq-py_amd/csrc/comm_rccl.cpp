@@ -8,6 +8,7 @@
 // loader's path, then /opt/rocm/lib.  Types and enum values are RCCL's public ABI (rccl.h: ncclUniqueId is 128 opaque
 // bytes, ncclInt64 = 4, ncclSum = 0).
 #include "../../include/kbbq_hip.h"
+#include "kbbq_lib_host.h"
 
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -15,10 +16,6 @@
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
-
-int kbbq_set_error_(int code, const char* msg);      // kbbq_hip.hip
-extern "C" void* kbbq_ctx_stream_(kbbq_ctx* c);      // kbbq_hip.hip: the context's launch stream
-extern "C" int kbbq_ctx_device_(kbbq_ctx* c);
 
 namespace {
 

@@ -12,6 +12,7 @@
 // host-detectable offender and its kind; the caller lets the device look at the reads before
 // it (and at it, for kind 5) before raising.
 #include "../../include/kbbq_hip.h"
+#include "kbbq_lib_host.h"
 #include "host_threads.h"
 #include "bam_host.h"
 #include "fastq_host.h"
@@ -37,7 +38,6 @@
 #endif
 
 extern "C" const char* kbbq_last_error(void);
-int kbbq_set_error_(int code, const char* msg);      // defined in kbbq_hip.hip
 
 static unsigned nthreads_for(size_t work) { return kbbq_threads_for(work); }
 

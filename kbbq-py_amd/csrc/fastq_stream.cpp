@@ -11,6 +11,7 @@
 // simply read again, a pipe is copied to a spool file as it is read (kbbq_fastq_stream_tee) and pass 2 reads the spool.
 // gzip / bgzip bytes -- a .fq.gz file of any size, or a pipe that carries them -- are inflated as they are read, member after member.
 #include "../../include/kbbq_hip.h"
+#include "kbbq_lib_host.h"
 #include "fast_inflate.h"
 #include "fastq_host.h"
 #include "host_threads.h"
@@ -32,8 +33,6 @@
 #include <sys/stat.h>
 #include <unistd.h>
 #include <zlib.h>
-
-int kbbq_set_error_(int code, const char* msg);      // defined in kbbq_hip.hip
 
 struct kbbq_fastq_stream {
     int fd = -1; bool own_fd = false;

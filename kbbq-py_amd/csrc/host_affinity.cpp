@@ -1,11 +1,12 @@
 // host_affinity.cpp -- the host side of "one process per GPU": how many host threads a rank starts and which CPUs they
-// run on (no GPU code; the device's PCI address comes from kbbq_hip.hip).
+// run on (no GPU code; the device's PCI address comes from kbbq_context.hip).
 //
 // Under torch.distributed.run every rank of a node runs the same host stages (scan / fill / format are 99 % of the file
 // path's wall time): each gets usable CPUs / LOCAL_WORLD_SIZE threads (host_threads.h), and its threads are bound to the
 // CPUs of the NUMA node its GPU hangs on, so that the page-locked staging slabs a rank fills are local to the PCIe root
 // complex that uploads them.
 #include "../../include/kbbq_hip.h"
+#include "kbbq_lib_host.h"
 #include "host_threads.h"
 #include "raw_vector.h"
 
@@ -15,8 +16,6 @@
 #include <string>
 
 #include <sched.h>
-
-int kbbq_set_error_(int code, const char* msg);      // defined in kbbq_hip.hip
 
 // "0-3,8,10-11" -> set; returns the number of CPUs named
 static int parse_cpulist(const char* s, cpu_set_t* set)

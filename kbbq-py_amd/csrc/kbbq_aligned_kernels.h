@@ -35,7 +35,7 @@
 // Output: two byte planes (errors, skips) as before, or -- skip == NULL -- ONE plane of flags, bit 0 = error,
 // bit 1 = skip, which K5 / K6 read in place of the two (1 byte per base less to write here and to read there).
 #pragma once
-#include "kbbq_kernels_v3.h"
+#include "kbbq_byte_window.h"
 
 // ---------------------------------------------------------------- K4 / K5: benchmark path
 // (SURVEY.md 8(f) #1).  K4 restates compare_reads.find_read_errors (compare_reads.py:84-139):
@@ -51,15 +51,6 @@ struct K4Params {
     uint8_t* err; uint8_t* skip; u64* status;
 };
 
-// load16_any (kbbq_kernels_v3.h) for windows that may run past the end of the array (`limit` = its size in bytes): bytes past
-// the end read as zero.  Only the last chunk of the last rows / of the genome ever takes the byte path.
-__device__ __forceinline__ void load16_upto(const uint8_t* base, long long off, long long limit, u32 out[4])
-{
-    if (off + 16 <= limit) { load16_any(base, off, out); return; }
-    out[0] = out[1] = out[2] = out[3] = 0u;
-    for (int b = 0; b < 16 && off + b < limit; ++b) out[b >> 2] |= (u32)base[off + b] << (8 * (b & 3));
-}
-
 __device__ __forceinline__ void set_byte(u32 v[4], int i, u32 val)      // i in 0..15, slow paths only
 {
     const u32 m = 0xFFu << (8 * (i & 3)), x = (val & 0xFFu) << (8 * (i & 3));
@@ -73,20 +64,6 @@ __device__ __forceinline__ u32 get_byte(const u32 v[4], int i)
 {
     const u32 w = (i >> 2) == 0 ? v[0] : (i >> 2) == 1 ? v[1] : (i >> 2) == 2 ? v[2] : v[3];
     return (w >> (8 * (i & 3))) & 0xFFu;
-}
-
-// 0xFF in the bytes of word w (of a 16-byte vector) whose position p = 4w + k lies in [lo, hi)
-__device__ __forceinline__ u32 range_mask(int lo, int hi, int w) { return byte_mask(hi, w) & ~byte_mask(lo, w); }
-
-__device__ __forceinline__ void shr_bytes16(u32 v[4], int nb)            // byte i <- byte i + nb (0 <= nb <= 15), zero fill
-{
-    const int ws = nb >> 2; const u32 bs = (u32)(nb & 3) * 8u;
-    const u32 a0 = ws == 0 ? v[0] : ws == 1 ? v[1] : ws == 2 ? v[2] : v[3];
-    const u32 a1 = ws == 0 ? v[1] : ws == 1 ? v[2] : ws == 2 ? v[3] : 0u;
-    const u32 a2 = ws == 0 ? v[2] : ws == 1 ? v[3] : 0u;
-    const u32 a3 = ws == 0 ? v[3] : 0u;
-    v[0] = __builtin_amdgcn_alignbit(a1, a0, bs); v[1] = __builtin_amdgcn_alignbit(a2, a1, bs);
-    v[2] = __builtin_amdgcn_alignbit(a3, a2, bs); v[3] = a3 >> bs;
 }
 
 // K4 itself is k4v2_find_errors (below): lane <-> one 16-byte OUTPUT chunk of one read.  For reverse-strand

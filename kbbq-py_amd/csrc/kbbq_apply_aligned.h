@@ -25,7 +25,7 @@
 // unquantized value; a preserved byte never meets the map (the map is the identity there anyway).  Without QMAP the kernel is
 // the one it was: no LDS, no barrier.
 #pragma once
-#include "kbbq_kernels.h"
+#include "kbbq_helpers.h"
 #include "kbbq_quantize_kernels.h"
 
 #define AA_LUT 0

@@ -25,7 +25,7 @@
 // bz_scan_sizes / bz_pack: an exclusive scan of the sizes and a copy, so that only compressed bytes cross PCIe.
 // Plain vector loads and stores and ordinary LDS / global atomics only.
 #pragma once
-#include "kbbq_kernels.h"
+#include "kbbq_helpers.h"
 #include "kbbq_crc32.h"
 
 constexpr int BZ_THREADS = 512;

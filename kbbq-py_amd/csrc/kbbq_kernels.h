@@ -11,24 +11,12 @@
 // read is found with one ds_bpermute of the sidecar; within a chunk the 16 bases
 // are handled 4 at a time with byte-parallel (SWAR / v_perm_b32) arithmetic.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include "kbbq_helpers.h"
 
-#define KQ      43          // maxscore + 1 (recalibrate.py:36)
-#define KND     16          // dinucleotides
 #define K1_THREADS 512
 #define K2_THREADS 1024     // launch bound; launched with 256 or 1024 threads depending on the LUT's LDS footprint
 #define K1_FLUSH_ITERS 96   // WG iterations between LDS flushes: 96 * 8 waves * 64 reads
                             // = 49,152 reads < 65,535 (16-bit packed LDS counters)
-
-// status words (device, unsigned long long[4]): min read index per error class
-#define ST_INDEX 0
-#define ST_TYPE  1
-#define ST_RANGE 2
-#define ST_LUT   3   // set (to 0) when a device-built LUT needs the checked apply kernel
-
-typedef unsigned long long u64;
-typedef unsigned int u32;
 
 struct K1Params {
     const uint8_t* seq; const uint8_t* cseq; const uint8_t* qual; const u32* meta;
@@ -53,69 +41,6 @@ struct KSParams {
     long long first; long long nreads; long long total; int pitch; int cpr;
     u64 seed; int len_lo; int len_hi; int nrg; int qlo; int qhi; u32 thr[KQ];
 };
-
-// ---------------------------------------------------------------- helpers
-__device__ __forceinline__ int lane_id() { return (int)(threadIdx.x & 63u); }
-
-// wave_shr:1 -- every lane receives lane-1's value, lane 0 receives `lane0`.
-__device__ __forceinline__ u32 wave_shr1(u32 v, u32 lane0)
-{
-    return (u32)__builtin_amdgcn_update_dpp((int)lane0, (int)v, 0x138, 0xF, 0xF, false);
-}
-
-__device__ __forceinline__ u32 bperm(u32 v, int src_lane)
-{
-    return (u32)__builtin_amdgcn_ds_bpermute(src_lane << 2, (int)v);
-}
-
-// byte-parallel nucleotide decoding of 4 bases (one 32-bit word of the seq plane).
-//   h      = bits 1..3 of every byte:  A->0 C->1 T->2 G->3 N->7   (others 4,5,6 or aliases)
-//   expect = the character that h stands for; a byte is in the alphabet iff expect == byte
-//   code   = reference order A0 T1 G2 C3 (compare_reads.py:199), 0x10 for N / other
-__device__ __forceinline__ void decode4(u32 w, u32& expect, u32& code)
-{
-    const u32 h = (w >> 1) & 0x07070707u;
-    expect = __builtin_amdgcn_perm(0x4E000000u, 0x47544341u, h);
-    code   = __builtin_amdgcn_perm(0x10101010u, 0x02010300u, h);
-}
-
-// mask with 0xFF in byte k iff (4*wd + k) < nb
-__device__ __forceinline__ u32 byte_mask(int nb, int wd)
-{
-    const int m = nb - 4 * wd;
-    return m >= 4 ? 0xFFFFFFFFu : (m <= 0 ? 0u : ((1u << (8 * m)) - 1u));
-}
-
-// (the plain load first: a status word only ever decreases, so a value already <= `read` -- however stale the copy this lane sees --
-//  means the atomic could not change it.  Without it a batch in which EVERY chunk is flagged -- qualities in another encoding, a
-//  kernel run twice over its own output -- spends a second in same-address atomics: 1 010 ms for 50 M reads, measured on K2.)
-__device__ __forceinline__ void flag(u64* status, int which, long long read)
-{
-    if (__hip_atomic_load(&status[which], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > (u64)read) atomicMin(&status[which], (u64)read);
-}
-
-// Exact restatement of the reference's TypeError condition for one chunk
-// (compare_reads.py:281-293): a dinucleotide (i-1, i) is looked up iff i >= 1,
-// q[i] >= minscore and neither base is 'N'; the lookup fails when either base is
-// outside ACGT.  Only reached when the cheap alphabet test fired.
-__device__ __noinline__ bool chunk_type_error(u32 s0, u32 s1, u32 s2, u32 s3,
-                                              u32 q0, u32 q1, u32 q2, u32 q3, u32 prevchar,
-                                              int nb, int pos0, int minscore)
-{
-    const u32 s[4] = {s0, s1, s2, s3};
-    const u32 q[4] = {q0, q1, q2, q3};
-    u32 prev = prevchar;
-    for (int i = 0; i < nb && i < 16; ++i) {
-        const u32 ch = (s[i >> 2] >> (8 * (i & 3))) & 0xFFu;
-        const int qq = (int)((q[i >> 2] >> (8 * (i & 3))) & 0xFFu) - 33;
-        const bool looked = (pos0 + i) >= 1 && qq >= minscore && ch != 'N' && prev != 'N';
-        const bool okc = ch == 'A' || ch == 'C' || ch == 'G' || ch == 'T';
-        const bool okp = prev == 'A' || prev == 'C' || prev == 'G' || prev == 'T';
-        if (looked && !(okc && okp)) return true;
-        prev = ch;
-    }
-    return false;
-}
 
 // ---------------------------------------------------------------- K1
 // LDS: pos[KQ][pos_stride] u32, (errs << 16 | total) per (q, column)   -- ds_add_u32
@@ -434,51 +359,6 @@ __global__ __launch_bounds__(K1_THREADS) void k1_accumulate_tiled(K1TiledParams 
 }
 
 // ---------------------------------------------------------------- K2
-// LUT (int16), one row of `rs` entries per (read group, quality):
-//     row[0 .. S2-1]      = meanq + rgdq + qdq + posdq[cycle]          (lut1)
-//     row[S2 .. S2+24]    = dinucdq[5 * code(prev) + code(cur)]        (lut2, code N/none = 4:
-//                           every entry that involves code 4 holds dinucdq[..., -1])
-// rs = lut_row_stride(S2): rs / 2 is odd so that consecutive rows start on different banks.
-__host__ __device__ __forceinline__ int lut_row_stride(int S2)
-{
-    int rs = (S2 + 25 + 1) & ~1;
-    if (((rs >> 1) & 1) == 0) rs += 2;
-    return rs;
-}
-
-// Exact per-base restatement of compare_reads.py:320-328 for ONE chunk, used whenever the
-// fast path cannot be taken (read group / quality / cycle beyond the tables).  Reads the LUT
-// from global memory.  Returns the 16 output bytes through o[4].
-__device__ __noinline__ uint4 chunk_apply_exact(const int16_t* lut, int rs, int R, int Qt, int S2,
-                                               u32 qlo, int rg, bool second, int pos0, int nb,
-                                               u32 q0, u32 q1, u32 q2, u32 q3,
-                                               u32 d0, u32 d1, u32 d2, u32 d3,
-                                               u64* status, long long read)
-{
-    const u32 q[4] = {q0, q1, q2, q3};
-    const u32 d5[4] = {d0, d1, d2, d3};
-    u32 o[4] = {0u, 0u, 0u, 0u};
-    for (int i = 0; i < 16; ++i) {
-        const u32 qb = (q[i >> 2] >> (8 * (i & 3))) & 0xFFu;
-        u32 ob = qb;
-        if (i < nb && qb >= qlo) {
-            const int qq = (int)qb - 33;
-            const int pos = pos0 + i;
-            const int col = second ? (S2 - 1 - pos) : pos;           // Python wrap of -(i+1) on S2
-            if (rg >= R || qq >= Qt || col < 0 || col >= S2) flag(status, ST_INDEX, read);
-            else {
-                const int16_t* row = lut + ((size_t)rg * Qt + qq) * rs;
-                const int v = (int)row[col] + (int)row[S2 + (int)((d5[i >> 2] >> (8 * (i & 3))) & 0xFFu)] + 33;
-                if (v < 0 || v > 255) flag(status, ST_RANGE, read);
-                ob = (u32)v & 0xFFu;
-            }
-        }
-        if (i >= nb) ob = 0u;
-        o[i >> 2] |= ob << (8 * (i & 3));
-    }
-    return make_uint4(o[0], o[1], o[2], o[3]);
-}
-
 // ELEM: element type of the staged LUT (int16_t canonical, or int8_t copy when every value fits:
 // half the LDS, which is what lets 8 read groups of 2x150 tables stay on chip).
 template <typename ELEM, bool LDS_LUT, bool CHECK_RANGE>

@@ -19,7 +19,7 @@
 // and the same C ABI as the first kernels, which remain as the fallback for shapes these
 // layouts do not fit in LDS (very long reads, many read groups).
 #pragma once
-#include "kbbq_kernels.h"
+#include "kbbq_helpers.h"
 #include <type_traits>
 
 #define K1V3_THREADS 1024        // one workgroup per CU: the replicated context table needs ~150 KB of LDS

@@ -85,12 +85,9 @@
 // break wherever the quality byte is below the threshold and counts the windows that are left; every counting kernel above
 // reads that copy as it reads any plane.
 #pragma once
-#include "kbbq_kernels.h"
-
-#define ST_KMER 5                     // status word: a k-mer insert found no free slot (kbbq_ctx_status -> KBBQ_E_FULL)
+#include "kbbq_helpers.h"
 
 constexpr int KM_THREADS = 256;
-constexpr int KM_MAX_PROBES = 512;
 constexpr u64 KM_EMPTY = ~0ull;
 constexpr int KM_HIST = 257;          // h[c], c = 1..255; h[256]: count >= 256; h[0] stays 0
 constexpr int KM_FIXN_OFF = 0, KM_FIXN_READS = 1, KM_FIXN_PAIRS = 2;   // km_correct's N rule: off, one read a row, two reads a row

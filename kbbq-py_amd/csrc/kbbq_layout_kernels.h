@@ -13,7 +13,7 @@
 // reference line to cite beyond the sidecar rules of compare_reads.py:304-318.
 #pragma once
 #include "kbbq_kernels_v3.h"
-#include "kbbq_aligned_kernels.h"      // the byte-window helpers (load16_upto, range_mask, shr_bytes16)
+#include "kbbq_byte_window.h"          // load16_upto, range_mask, shr_bytes16
 
 // ---------------------------------------------------------------- sidecar statistics
 // stats[0] shortest non-empty read   stats[1] longest read   stats[2] largest read-group id

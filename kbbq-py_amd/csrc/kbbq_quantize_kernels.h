@@ -12,7 +12,7 @@
 // The table is read with 16 ds_read_u8 per chunk: 64 lanes x 1 byte per wave-instruction against a 64-dword table, where lanes
 // that name the same byte (a handful of levels: the usual case) are served by one broadcast.
 #pragma once
-#include "kbbq_kernels.h"
+#include "kbbq_helpers.h"
 
 #define KQ_THREADS 256
 #define KQ_CHUNKS_PER_LANE 8         // grid sizing: a workgroup walks at least this many 4 KB tiles when the plane is large

@@ -10,12 +10,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "kbbq_helpers.h"
 #include "solve_core.h"
 #include "lgam_core.h"
-
-#ifndef ST_MEANQ
-#define ST_MEANQ 4   // status word: a read group whose meanq the all-device solve cannot decide (see k3_levels_ab)
-#endif
 
 struct K3CellParams {
     const long long* prior_q; const long long* errs; const long long* total; const double* comb;

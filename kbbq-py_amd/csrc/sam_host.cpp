@@ -13,6 +13,7 @@
 // CIGAR operations are stored as (length << 4 | op) with BAM op codes MIDNSHP=X = 0..8; an unknown
 // operation letter is stored as op 15 and rejected by K4 (ValueError, like the reference's walk).
 #include "../../include/kbbq_hip.h"
+#include "kbbq_lib_host.h"
 #include "host_threads.h"
 #include "bam_host.h"
 
@@ -31,8 +32,6 @@
 #include <sys/mman.h>
 #include <sys/stat.h>
 #include <unistd.h>
-
-int kbbq_set_error_(int code, const char* msg);      // defined in kbbq_hip.hip
 
 struct kbbq_sam {
     const uint8_t* buf = nullptr; size_t size = 0;

@@ -13,6 +13,7 @@
 // checks that over millions of arguments.  Why it exists: three SciPy ufunc passes over 13.6 k cells cost
 // 0.32 ms of a 10 ms bench step; one fused threaded pass costs a fraction of it.
 #include "../../include/kbbq_hip.h"
+#include "kbbq_lib_host.h"
 #include "lgam_core.h"
 
 #include <link.h>
@@ -27,8 +28,6 @@
 #include <functional>
 #include <thread>
 #include <vector>
-
-int kbbq_set_error_(int code, const char* msg);      // defined in kbbq_hip.hip
 
 namespace {
 

@@ -163,7 +163,7 @@ def test_one_read_group_apply_matches_oracle(dev, oracle, pitch, monkeypatch):
 
 
 def _stage_slabs(n, pitch, mb):
-    """Slabs kbbq_apply moves n rows in (csrc/kbbq_hip.hip stage_slab_rows: seq, qual and out planes + the sidecar word a row)."""
+    """Slabs kbbq_apply moves n rows in (csrc/kbbq_staging.hip stage_slab_rows: seq, qual and out planes + the sidecar word a row)."""
     rows = max(((mb << 20) // (pitch * 3 + 4)) // 64 * 64, 64)
     return -(-n // min(rows, n))
 
