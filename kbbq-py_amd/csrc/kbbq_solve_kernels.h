@@ -77,8 +77,9 @@ __global__ __launch_bounds__(256) void k3_posterior_q(K3PostParams p)
 // All 64 lanes pass the SAME cell.  Lane q' < 43 forms the posterior of candidate q' exactly as
 // solve_cell does (same doubles, same order, same 80-bit add); the argmax is a butterfly over an
 // order-preserving key of the rounded 80-bit value, ties to the lower index (np.argmax: first
-// maximum), NaN neither greater nor smaller than anything (it can only arise at candidate 0, and
-// then wins every tie as the sequential scan does).  `sc` = the 129 model constants in LDS.
+// maximum), NaN neither greater nor smaller than anything (inside the support no candidate forms one:
+// every term is finite or -inf, and the one 0 * -inf, candidate 0 at k == n, is xlog1py(0, -1) = 0 as
+// in solve_cell; the flag is kept so the reduction stays total).  `sc` = the 129 model constants in LDS.
 __device__ __forceinline__ int k3_lane() { return (int)(threadIdx.x & 63u); }
 
 __device__ __forceinline__ int solve_cell_wave(const double* sc, int prior_q, long long errs, long long total, double comb)
@@ -92,16 +93,12 @@ __device__ __forceinline__ int solve_cell_wave(const double* sc, int prior_q, lo
     int diff = cand - prior_q; if (diff < 0) diff = -diff;
     const double pr = sc[diff < KSOLVE_NQ ? diff : KSOLVE_NQ - 1];
     const double t1 = k * sc[KSOLVE_NQ + cand];
-    const double t2 = nk * sc[2 * KSOLVE_NQ + cand];
+    const double t2 = nk == 0.0 ? 0.0 : nk * sc[2 * KSOLVE_NQ + cand];   // xlog1py(0, -1) is 0, not 0 * -inf
     const double ll = (comb + t1) + t2;
-    const x87val v = x87_add(pr, ll);
-    // order-preserving key: (class rank, exponent, significand), mirrored for negative values
-    const int rank = v.cls == 2 ? 0 : v.cls == 3 ? 4 : v.cls == 1 ? 2 : (v.neg ? 1 : 3);
-    int hi = rank << 20;
-    unsigned long long lo = 0ull;
-    if (rank == 3) { hi += v.exp + 40000; lo = v.mant; }
-    if (rank == 1) { hi += 40000 - v.exp; lo = ~v.mant; }
-    int nan = v.cls == 4 ? 1 : 0;
+    const x87key key = x87_order_key(x87_add(pr, ll));
+    int hi = key.hi;
+    unsigned long long lo = key.lo;
+    int nan = key.nan;
     int idx = lane < KSOLVE_NQ ? lane : 64 + lane;                    // a repeat never beats the original
 #pragma unroll
     for (int off = 1; off < 64; off <<= 1) {

@@ -41,7 +41,8 @@ X87_HD int solve_cell(const SolveConsts& c, PRIOR prior_q, long long errs, long 
         int diff = (int)((PRIOR)cand - prior_q); if (diff < 0) diff = -diff;
         const double pr = diff < KSOLVE_NQ ? c.prior[diff] : c.prior[KSOLVE_NQ - 1];
         const double t1 = k * c.logp[cand];
-        const double t2 = nk * c.log1mp[cand];
+        // xlog1py(0, -p) is 0 for every p: at k == n candidate 0 (p = 1, log1mp = -inf) must not form 0 * -inf
+        const double t2 = nk == 0.0 ? 0.0 : nk * c.log1mp[cand];
         const double ll = (comb + t1) + t2;
         const x87val post = x87_add(pr, ll);
         if (cand == 0 || x87_gt(post, best)) { best = post; arg = cand; }

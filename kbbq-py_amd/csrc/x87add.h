@@ -178,7 +178,8 @@ X87_HD x87val x87_add(double a, double b)
 }
 
 // strict "a > b" on rounded values; nan is never greater and nothing is greater than nan
-// (the caller handles np.argmax's NaN rule separately)
+// (the solve forms no nan inside the binomial's support -- solve_core.h guards its one 0 * -inf --
+// and answers 0 outside it before any sum is formed, which is np.argmax's answer there)
 X87_HD bool x87_gt(const x87val& a, const x87val& b)
 {
     if (a.cls == 4 || b.cls == 4) return false;
@@ -189,4 +190,22 @@ X87_HD bool x87_gt(const x87val& a, const x87val& b)
     if (ra == 1) return a.exp != b.exp ? a.exp > b.exp : a.mant > b.mant;
     if (ra == -1) return a.exp != b.exp ? a.exp < b.exp : a.mant < b.mant;
     return false;
+}
+
+// order-preserving key of a rounded value for reductions that compare integers (K3's wave argmax):
+// (class rank, exponent, significand), mirrored for negative values.  For two values that are not
+// nan, (hi, lo) compares lexicographically exactly as x87_gt orders them; equal keys mean neither is
+// greater.  nan carries its own flag: it is never greater and nothing is greater than it.
+struct x87key { int32_t hi; uint64_t lo; int32_t nan; };
+
+X87_HD x87key x87_order_key(const x87val& v)
+{
+    const int rank = v.cls == 2 ? 0 : v.cls == 3 ? 4 : v.cls == 1 ? 2 : (v.neg ? 1 : 3);
+    x87key key;
+    key.hi = rank << 20;
+    key.lo = 0ull;
+    if (rank == 3) { key.hi += v.exp + 40000; key.lo = v.mant; }
+    if (rank == 1) { key.hi += 40000 - v.exp; key.lo = ~v.mant; }
+    key.nan = v.cls == 4 ? 1 : 0;
+    return key;
 }

@@ -1,6 +1,6 @@
 // Host check of kbbq-py_amd/csrc/x87add.h against the CPU's own x87 long double arithmetic.
 // Built and run by tests/test_x87_emulation.py (g++, no GPU).  Prints "OK <n>" or the
-// first mismatch.
+// first mismatch.  With the argument "key" it prints the order key (x87_order_key) of the sums it reads.
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -48,8 +48,20 @@ static bool check_order(double a1, double b1, double a2, double b2)
     return want == got;
 }
 
+// mode "key": stdin holds pairs of float64 (a, b); per pair one line "hi lo nan" -- the order key of x87_add(a, b)
+static int print_keys()
+{
+    double ab[2];
+    while (fread(ab, sizeof(double), 2, stdin) == 2) {
+        const x87key k = x87_order_key(x87_add(ab[0], ab[1]));
+        printf("%d %llu %d\n", (int)k.hi, (unsigned long long)k.lo, (int)k.nan);
+    }
+    return 0;
+}
+
 int main(int argc, char** argv)
 {
+    if (argc > 1 && strcmp(argv[1], "key") == 0) return print_keys();
     const long long N = argc > 1 ? atoll(argv[1]) : 2000000;
     long long n = 0;
     const double specials[] = {0.0, -0.0, 1.0, -1.0, -INFINITY, 5e-324, -5e-324, 2.2250738585072014e-308,

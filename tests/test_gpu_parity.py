@@ -339,7 +339,10 @@ def test_all_device_solve_equals_the_host_fed_solve_on_golden_tables(dev, name):
 @pytest.mark.parametrize('seed,R,S2,scale', [(1, 1, 300, 10.3), (2, 3, 300, 8.0), (3, 8, 100, 6.0), (4, 2, 600, 9.5), (5, 5, 32, 3.0)])
 def test_all_device_solve_on_adversarial_tables(dev, seed, R, S2, scale):
     """Random count tables up to 2 * 10^10 per cell, empty cells, errs == total, tiny cells: the LUT of the all-device
-    solve (kernel marginals, kernel gammaln, kernel meanq) equals the host-fed one byte for byte."""
+    solve (kernel marginals, kernel gammaln, kernel meanq) equals the host-fed one byte for byte.  This compares the two
+    ROUTES with each other: both run the wave form of the cell solve, so what is checked here is the device's marginals,
+    gammaln terms and meanq against the host's, not the argmax -- test_gpu_solve_reference.py compares each route with the
+    reference."""
     import torch
     rng = np.random.default_rng(seed)
     t = dev.Tables(R, S2)
