@@ -12,12 +12,16 @@ Data: every quality byte 0 .. Qt + 32 occurs inside reads (all rows of the LUT a
 bases at random, as a mate's last base and on both sides of every 256th chunk (a wave's first chunk and the base before it).
 Expected: the CPU oracle's apply on the same reads, and the persistent kernel (k2v3_apply) on the same reads as character
 rows -- the comparison bench.py's `verify` makes.  Both are computed once per read length and only read afterwards.
+That model is solved from reads without errors: its LUT is one constant per read group, blind to the cycle, context and
+quality-row addresses.  So every (S, R) case is run again under three probe models of tests/k2_probe.py -- all cycle entries
+negative against large contexts, and two whose output byte names the column -- against k2_probe.reference_apply.
 """
 import os
 
 import numpy as np
 import pytest
 
+import k2_probe
 from conftest import GOLDEN_CASES, load_golden
 from test_gpu_parity import dev                      # noqa: F401  (fixture)
 
@@ -26,6 +30,7 @@ pytestmark = pytest.mark.gpu
 ROWS = 2000
 QT = 43                                              # quality rows of the model: bytes 33 .. 75 are served, 76 is not
 GROUPS = 8
+PROBES = ('negcycle', 'col161', 'col157')
 # read group of pair row i on the 8-group cases: uneven shares, group 5 empty
 GROUP_OF = np.array([0, 1, 1, 2, 2, 2, 3, 4, 4, 6, 6, 6, 6, 7, 0, 3, 3, 3, 3, 3, 3, 3, 3], dtype=np.uint32)
 
@@ -107,6 +112,19 @@ def cases(dev, oracle):
         c.persistent = out[:b.n, :S].cpu().numpy()
         assert np.array_equal(c.persistent, c.want)
         assert (c.want != c.qual[:, :S]).any()
+        # the probe models: LUTs that do vary with the cycle and the context, and the reference's bytes under them
+        c.probes = {}
+        models = [k2_probe.probe(name, R, 2 * S) for name in PROBES]
+        # ... which these expectations must keep doing: every probe varies with the cycle, and (the column probes' contexts
+        # are 0 by construction) one of them with the cycle and the 16 dinucleotides at once
+        assert all(np.ptp(m[3]) > 0 for m in models)
+        assert any(np.ptp(m[3]) > 0 and np.ptp(m[4][..., :16]) > 0 for m in models)
+        for name, model in zip(PROBES, models):
+            lut, shape = dev.build_lut(*model)
+            assert shape == c.shape
+            want = k2_probe.reference_apply(c.seq, c.qual, c.meta, *model)
+            assert want.min() >= 0 and want.max() <= 255 and not want[:, S:].any()
+            c.probes[name] = (dev.lut_to_device(lut), want[:, :S].astype(np.uint8))
         made[S, R] = c
         return c
     return get
@@ -130,6 +148,18 @@ def _check(c, got, n):
     assert not got[:, S:].any()
 
 
+def _check_probes(dev, c, b, laid, n, **how):
+    """The same rows under every probe LUT against the reference's bytes."""
+    for name in PROBES:
+        lut, want = c.probes[name]
+        out = dev.apply(laid, lut, c.shape, **how)
+        if laid.seg is not None and not how.get('restore_order'):
+            out = dev.ungroup(laid, out)
+        got = laid.unpack(out, b.pitch)[:n].cpu().numpy()
+        assert np.array_equal(got[:, :c.S], want[:n]), name
+        assert not got[:, c.S:].any(), name
+
+
 @pytest.mark.parametrize('rows', [1, 215, 216, 431, 432, ROWS])
 @pytest.mark.parametrize('S', [150, 100, 50])
 def test_one_read_group(dev, cases, S, rows):
@@ -139,6 +169,7 @@ def test_one_read_group(dev, cases, S, rows):
     plane = out[:rows].cpu().numpy()
     assert not plane[:, S].any() and not plane[:, 2 * S + 1:].any()          # separator and padding stay 0
     _check(c, laid.unpack(out, b.pitch), 2 * rows)
+    _check_probes(dev, c, b, laid, 2 * rows)
 
 
 @pytest.mark.parametrize('restore', [False, True])
@@ -152,6 +183,7 @@ def test_eight_read_groups_on_grouped_rows(dev, cases, S, restore):
     if not restore:
         out = dev.ungroup(laid, out)
     _check(c, laid.unpack(out, b.pitch), 2 * ROWS)
+    _check_probes(dev, c, b, laid, 2 * ROWS, restore_order=restore)
 
 
 @pytest.mark.parametrize('what', ['quality', 'nibble', 'read_group'])
