@@ -1229,6 +1229,69 @@ int kbbq_inflate_bgzf_host(const uint8_t* payload, uint32_t n, uint8_t* out, uin
 int kbbq_inflate_use_ctx(kbbq_ctx* ctx);
 int kbbq_inflate_stats_get(kbbq_inflate_stats* stats);
 
+/* ---- BAM input: records decoded on the GPU (csrc/bam_host.cpp kbbq_bam_scan, csrc/kbbq_bam_in.h, kbbq/_bamin.py) ----------------
+ * For the commands that write no record (bqsr --kmers, count -b) the SAM text the host reader renders from a BAM file serves
+ * nothing: a kernel turns the uploaded records into the resident planes and per-record words.  The host reader (kbbq_sam_open)
+ * stays the reference: what the decode writes is what the reader's arrays hold for the same record, or a status bit, and a file
+ * with a status bit anywhere -- or with a scan error -- is the reader's to read or to refuse.
+ * kbbq_bam_scan: an inflated BAM image (magic .. last record).  With every array NULL it fills *info only; the caller sizes the
+ * arrays from it and calls again.  header[header_bytes]: the header lines exactly as kbbq_bam_to_sam writes them in front of the
+ * records (NUL padding stripped, a final '\n' added, @SQ lines made from the binary list when the text has none); rg_off[n_rg + 1]
+ * / rg_ids[rg_bytes]: the ID of every @RG line in header order (the line's last ID: field, empty without one); rec_off[n]: the
+ * offset of every record's body (behind its block_size word) in the image; cig_off[n + 1]: the running sum of n_cigar_op.
+ * info: n, cig_total, max_l_seq (the longest l_seq, negative ones taken as 0), n_ref, n_rg, header_bytes, rg_bytes, refs_off (of
+ * the binary reference list: n_ref times l_name, name, l_ref), records_off (of the first block_size word), max_record (the
+ * largest block_size + 4).  KBBQ_E_ARG with the reader's own text for a defect: "not a BAM file", "BAM header text runs past the
+ * file", "BAM reference list runs past the file", "BAM: negative reference count", "BAM: truncated record".
+ * kbbq_bam_decode_dev (synchronous) / kbbq_bam_decode (the same over host memory, by the same per-record code: bd_record): m
+ * records of a slab -- a piece of the image that holds whole records, each behind its block_size word -- into rows [0, m) of
+ * the planes and words [0, m).  rec_off[m]: the bodies' offsets in the slab; cig_off[m + 1]: the records' ranges in `cigar` (of
+ * cig_cap words).  pitch: a multiple of 16 in 16..65536; planes 16-byte aligned.  seq / qual / oq / words / cigar may each be
+ * NULL: it is not written.  Every byte of rows [0, m) x pitch, every word and every word of the CIGAR ranges is written: nothing
+ * needs zeroing first.  Planes hold what kbbq_sam_fill writes: SEQ letters, QUAL + 33 (zeros for an absent QUAL: l_seq 0, a
+ * first byte of 0xFF, or ONE quality of 9, which the text shows as '*'), the value of the last OQ:Z tag; truncated at pitch, zero
+ * padded.  Words: kbbq_bam_words, with the meanings of kbbq_sam_fields (pos / pnext 0-based; oq_len -1 without a tag; rg the index
+ * of the FIRST @RG line with the ID of the LAST RG:Z tag, -1 without a tag, -2 for an ID the header lacks; trim:
+ * kbbq_sam_adaptor_trim's word); ref_id as stored.  status != 0: the record is not vouched for -- its rows and CIGAR words are zeros
+ * and its other words 0:
+ *   KBBQ_BAM_ST_RECORD  inconsistent by the reader's own tests (l_seq < 0, l_read_name 0, the fixed parts or a tag overrun the
+ *                       record, QNAME without its NUL, a refID / next_refID >= n_ref, an unknown tag type or B subtype)
+ *   KBBQ_BAM_ST_LONG    l_seq above 65535, an OQ value above 32767 (the longest kbbq_sam_fields takes)
+ *   KBBQ_BAM_ST_QUAL    a present QUAL with a byte above 93
+ *   KBBQ_BAM_ST_TEXT    the rendered line would split differently or hold another value: a byte outside 0x21..0x7E in the RG or
+ *                       OQ value or a tag's name, a byte below 0x20 in QNAME, in an A value or in any Z / H value, a QNAME that
+ *                       begins with '@', a CIGAR operation above 8
+ *   KBBQ_BAM_ST_RANGE   the record (its block_size word included) does not lie in the slab, or its CIGAR range is not
+ *                       n_cigar_op words inside cigar[0, cig_cap)
+ * *any_status: the OR of all of them.  Whatever the bytes, nothing outside the slab is read and nothing outside the rows, the
+ * words and the CIGAR ranges is written; every length is checked against the record's end in 64-bit arithmetic before it is
+ * used; no read passes a record's end (the last chunk of a field is read bytewise), so the slab needs no slack.
+ * KBBQ_E_ARG before any HIP call: a NULL ctx, slab, rec_off or any_status with m > 0, cigar without cig_off, n_rg > 0 without the
+ * table, m outside 0..2^31 - 1, a slab of 2^32 bytes or more, a bad pitch or alignment.                                        */
+#define KBBQ_BAM_ST_RECORD 1u
+#define KBBQ_BAM_ST_LONG   2u
+#define KBBQ_BAM_ST_QUAL   4u
+#define KBBQ_BAM_ST_TEXT   8u
+#define KBBQ_BAM_ST_RANGE  16u
+typedef struct kbbq_bam_scan_info {
+    int64_t n, cig_total;
+    int32_t max_l_seq, n_ref, n_rg, pad;
+    uint64_t header_bytes, rg_bytes, refs_off, records_off, max_record;
+} kbbq_bam_scan_info;
+typedef struct kbbq_bam_words {
+    int32_t flag, ref_id, pos, pnext, tlen, qlen, qual_len, oq_len, rg, cig_n, ref_span;
+    uint32_t clip, trim, status, pad[2];
+} kbbq_bam_words;
+extern int kbbq_bam_scan(const uint8_t* image, size_t n, kbbq_bam_scan_info* info, uint8_t* header, uint32_t* rg_off, uint8_t* rg_ids,
+                  uint64_t* rec_off, uint64_t* cig_off);
+extern int kbbq_bam_decode_dev(kbbq_ctx* ctx, const uint8_t* d_slab, size_t slab_bytes, const uint32_t* d_rec_off, int64_t m, int pitch,
+                        const uint32_t* d_rg_off, const uint8_t* d_rg_ids, int n_rg, int n_ref, const uint32_t* d_cig_off,
+                        size_t cig_cap, uint8_t* d_seq, uint8_t* d_qual, uint8_t* d_oq, kbbq_bam_words* d_words, uint32_t* d_cigar,
+                        uint32_t* any_status);
+extern int kbbq_bam_decode(const uint8_t* slab, size_t slab_bytes, const uint32_t* rec_off, int64_t m, int pitch, const uint32_t* rg_off,
+                    const uint8_t* rg_ids, int n_rg, int n_ref, const uint32_t* cig_off, size_t cig_cap, uint8_t* seq, uint8_t* qual,
+                    uint8_t* oq, kbbq_bam_words* words, uint32_t* cigar, uint32_t* any_status);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,5 +1,6 @@
 // bam_host.cpp -- see bam_host.h.  Host only, no GPU code.
 #include "bam_host.h"
+#include "bam_scan.h"
 #include "fast_inflate.h"
 #include "host_threads.h"
 #include "parallel_gunzip.h"
@@ -341,37 +342,14 @@ bool kbbq_inflate_all(const uint8_t* src, size_t n, kbbq_bytes& out, std::string
 
 bool kbbq_bam_to_sam(const uint8_t* bam, size_t n, kbbq_bytes& text, std::string& err)
 {
-    if (n < 12 || memcmp(bam, "BAM\1", 4) != 0) { err = "not a BAM file"; return false; }
-    size_t at = 4;
-    const int32_t l_text = les32(bam + at); at += 4;
-    if (l_text < 0 || (size_t)l_text > n - at - 4) { err = "BAM header text runs past the file"; return false; }
-    const uint8_t* htext = bam + at; at += (size_t)l_text;
-    size_t hlen = (size_t)l_text; while (hlen && htext[hlen - 1] == 0) --hlen;          // NUL padding
-    const int32_t n_ref = les32(bam + at); at += 4;
-    if (n_ref < 0) { err = "BAM: negative reference count"; return false; }
-    std::vector<std::string> refs; std::vector<int32_t> ref_len;
-    for (int32_t i = 0; i < n_ref; ++i) {
-        if (n - at < 4) { err = "BAM reference list runs past the file"; return false; }
-        const int32_t l_name = les32(bam + at); at += 4;
-        if (l_name <= 0 || (size_t)l_name + 4 > n - at) { err = "BAM reference list runs past the file"; return false; }
-        refs.emplace_back((const char*)bam + at, (size_t)l_name - 1); at += (size_t)l_name;
-        ref_len.push_back(les32(bam + at)); at += 4;
-    }
+    kbbq_bam_head H;
+    if (!kbbq_bam_read_head(bam, n, H, err)) return false;
+    const std::vector<std::string>& refs = H.refs;
     text.clear();
-    put(text, htext, hlen);
-    if (hlen && text.back() != '\n') put(text, '\n');
-    bool has_sq = false;
-    for (size_t i = 0; i + 3 <= hlen; ++i) if ((i == 0 || htext[i - 1] == '\n') && !memcmp(htext + i, "@SQ", 3)) { has_sq = true; break; }
-    if (!has_sq)                                                               // the binary list is authoritative
-        for (size_t i = 0; i < refs.size(); ++i) { put(text, "@SQ\tSN:", 7); put(text, refs[i].data(), refs[i].size()); put(text, "\tLN:", 4); put_int(text, ref_len[i]); put(text, '\n'); }
+    kbbq_bam_head_text(H, text);
     // record offsets (a chain of block_size words), then the lines in parallel
     std::vector<size_t> rec;
-    while (at < n) {
-        if (n - at < 4) { err = "BAM: truncated record"; return false; }
-        const int32_t bs = les32(bam + at);
-        if (bs < 32 || (size_t)bs > n - at - 4) { err = "BAM: truncated record"; return false; }
-        rec.push_back(at + 4); at += 4 + (size_t)bs;
-    }
+    if (!kbbq_bam_chain(bam, n, H.records_off, err, [&](size_t body, size_t) { rec.push_back(body); })) return false;
     rec.push_back(n + 4);
     const unsigned nt = kbbq_threads_for(n);
     std::vector<Sink> parts(nt);
@@ -400,4 +378,50 @@ bool kbbq_bam_to_sam(const uint8_t* bam, size_t n, kbbq_bytes& text, std::string
         kbbq_bytes().swap(parts[t].buf);
     });
     return true;
+}
+
+// ---- BAM input: what the decode needs of an image (include/kbbq_hip.h "BAM input"; the records themselves: kbbq_bam_in.h) --------
+extern "C" int kbbq_bam_scan(const uint8_t* image, size_t n, kbbq_bam_scan_info* info, uint8_t* header, uint32_t* rg_off, uint8_t* rg_ids,
+                             uint64_t* rec_off, uint64_t* cig_off)
+{
+    if (!info || (n && !image)) return kbbq_set_error_(KBBQ_E_ARG, "kbbq_bam_scan: NULL image or info");
+    memset(info, 0, sizeof *info);
+    kbbq_bam_head H;
+    std::string err;
+    if (!kbbq_bam_read_head(image, n, H, err)) return kbbq_set_error_(KBBQ_E_ARG, err.c_str());
+    kbbq_bytes text;
+    kbbq_bam_head_text(H, text);
+    std::vector<std::string> ids;
+    kbbq_bam_rg_ids(text.data(), text.size(), ids);
+    if (ids.size() > (size_t)INT32_MAX) return kbbq_set_error_(KBBQ_E_ARG, "kbbq_bam_scan: more than 2^31 - 1 @RG lines");
+    size_t rg_bytes = 0;
+    for (const auto& id : ids) rg_bytes += id.size();
+    if (rg_bytes > UINT32_MAX) return kbbq_set_error_(KBBQ_E_ARG, "kbbq_bam_scan: the @RG IDs take 4 GiB or more");
+    // the chain is one read of block_size; l_seq and n_cigar_op lie in the same cache line
+    int64_t count = 0, max_l_seq = 0;
+    uint64_t cig = 0, max_record = 0;
+    if (cig_off) cig_off[0] = 0;
+    if (!kbbq_bam_chain(image, n, H.records_off, err, [&](size_t body, size_t bs) {
+            const uint64_t n_cig = (uint64_t)image[body + 12] | (uint64_t)image[body + 13] << 8;
+            max_l_seq = std::max<int64_t>(max_l_seq, kbbq_bam_les32(image + body + 16));
+            max_record = std::max<uint64_t>(max_record, bs + 4);
+            if (rec_off) rec_off[count] = body;
+            cig += n_cig;
+            if (cig_off) cig_off[count + 1] = cig;
+            ++count;
+        })) return kbbq_set_error_(KBBQ_E_ARG, err.c_str());
+    info->n = count; info->cig_total = (int64_t)cig; info->max_l_seq = (int32_t)max_l_seq; info->n_ref = H.n_ref;
+    info->n_rg = (int32_t)ids.size(); info->header_bytes = text.size(); info->rg_bytes = rg_bytes; info->refs_off = H.refs_off;
+    info->records_off = H.records_off; info->max_record = max_record;
+    if (header && !text.empty()) memcpy(header, text.data(), text.size());
+    if (rg_off) {
+        uint32_t at = 0;
+        for (size_t g = 0; g < ids.size(); ++g) {
+            rg_off[g] = at;
+            if (rg_ids && !ids[g].empty()) memcpy(rg_ids + at, ids[g].data(), ids[g].size());
+            at += (uint32_t)ids[g].size();
+        }
+        rg_off[ids.size()] = at;
+    }
+    return KBBQ_OK;
 }

@@ -2,6 +2,7 @@
 // (C ABI: include/kbbq_hip.h; shared: kbbq_lib.h).
 #include "kbbq_bam_out.h"
 #include "kbbq_bam_index.h"
+#include "kbbq_bam_in.h"
 #include "kbbq_lib.h"
 #include "host_threads.h"
 
@@ -169,6 +170,63 @@ int kbbq_bam_index(const uint8_t* skel, size_t skel_bytes, const kbbq_bam_desc* 
         ++(e.unmapped ? run.n_unmapped : run.n_mapped);
     }
     *n_runs = count;
+    return KBBQ_OK;
+}
+
+// ---- BAM input (csrc/kbbq_bam_in.h) -------------------------------------------------------------------------------------------
+static int bam_decode_args(const char* who, const BdJob& J, int64_t m, int pitch, size_t slab_bytes, const uint32_t* any_status)
+{
+    if (!any_status) return fail(KBBQ_E_ARG, "%s: any_status is NULL", who);
+    if (m < 0 || m > (int64_t)INT_MAX) return fail(KBBQ_E_ARG, "%s: m must be in 0..2^31 - 1", who);
+    if (pitch <= 0 || (pitch & 15) || pitch > 65536) return fail(KBBQ_E_ARG, "%s: pitch must be a positive multiple of 16 (<= 65536), got %d", who, pitch);
+    if (slab_bytes > (size_t)UINT32_MAX) return fail(KBBQ_E_ARG, "%s: a slab holds less than 2^32 bytes", who);
+    if (m > 0 && (!J.slab || !J.rec_off)) return fail(KBBQ_E_ARG, "%s: NULL buffer", who);
+    if (J.cigar && !J.cig_off) return fail(KBBQ_E_ARG, "%s: cigar without cig_off", who);
+    if (J.n_rg < 0 || J.n_ref < 0 || (J.n_rg > 0 && (!J.rg_off || !J.rg_ids))) return fail(KBBQ_E_ARG, "%s: n_rg / n_ref negative, or read groups without their table", who);
+    if (((uintptr_t)J.seq | (uintptr_t)J.qual | (uintptr_t)J.oq | (uintptr_t)J.words) & 15) return fail(KBBQ_E_ARG, "%s: planes and words must be 16-byte aligned", who);
+    if (((uintptr_t)J.rec_off | (uintptr_t)J.rg_off | (uintptr_t)J.cig_off | (uintptr_t)J.cigar) & 3) return fail(KBBQ_E_ARG, "%s: offsets and CIGAR words must be 4-byte aligned", who);
+    return KBBQ_OK;
+}
+
+int kbbq_bam_decode_dev(kbbq_ctx* c, const uint8_t* d_slab, size_t slab_bytes, const uint32_t* d_rec_off, int64_t m, int pitch,
+                        const uint32_t* d_rg_off, const uint8_t* d_rg_ids, int n_rg, int n_ref, const uint32_t* d_cig_off,
+                        size_t cig_cap, uint8_t* d_seq, uint8_t* d_qual, uint8_t* d_oq, kbbq_bam_words* d_words, uint32_t* d_cigar,
+                        uint32_t* any_status)
+{
+    if (any_status) *any_status = 0;
+    const BdJob J{d_slab, (u64)slab_bytes, d_rec_off, (u32)m, (u32)pitch, d_rg_off, d_rg_ids, n_rg, n_ref, d_cig_off, (u64)cig_cap,
+                  d_seq, d_qual, d_oq, d_words, d_cigar};
+    int rc = bam_decode_args("kbbq_bam_decode_dev", J, m, pitch, slab_bytes, any_status);
+    if (rc) return rc;
+    if (!c) return fail(KBBQ_E_ARG, "kbbq_bam_decode_dev: ctx is NULL");
+    if (m == 0) return KBBQ_OK;
+    HIPCHK(hipSetDevice(c->device));
+    rc = grow_scratch(c, c->bam_words, 2 * sizeof(u32));
+    if (rc) return rc;
+    HIPCHK(hipMemsetAsync(c->bam_words.p, 0, sizeof(u32), c->stream));
+    BdParams p{J, (u32*)c->bam_words.p};
+    const unsigned grid = (unsigned)((m + BD_RECORDS - 1) / BD_RECORDS);
+    hipLaunchKernelGGL(kbd_decode, dim3(grid), dim3(BD_THREADS), 0, c->stream, p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(any_status, c->bam_words.p, sizeof(u32), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return KBBQ_OK;
+}
+
+int kbbq_bam_decode(const uint8_t* slab, size_t slab_bytes, const uint32_t* rec_off, int64_t m, int pitch, const uint32_t* rg_off,
+                    const uint8_t* rg_ids, int n_rg, int n_ref, const uint32_t* cig_off, size_t cig_cap, uint8_t* seq, uint8_t* qual,
+                    uint8_t* oq, kbbq_bam_words* words, uint32_t* cigar, uint32_t* any_status)
+{
+    if (any_status) *any_status = 0;
+    const BdJob J{slab, (u64)slab_bytes, rec_off, (u32)m, (u32)pitch, rg_off, rg_ids, n_rg, n_ref, cig_off, (u64)cig_cap, seq, qual, oq,
+                  words, cigar};
+    int rc = bam_decode_args("kbbq_bam_decode", J, m, pitch, slab_bytes, any_status);
+    if (rc) return rc;
+    std::vector<u32> met(kbbq_threads_for((size_t)m * 512), 0);
+    kbbq_parallel_parts((size_t)m, (unsigned)met.size(), [&](unsigned t, size_t lo, size_t hi) {
+        for (size_t r = lo; r < hi; ++r) met[t] |= bd_record(J, (u32)r);
+    });
+    for (u32 v : met) *any_status |= v;
     return KBBQ_OK;
 }
 

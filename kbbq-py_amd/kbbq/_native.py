@@ -271,6 +271,22 @@ PROTOTYPES['kbbq_inflate_bgzf'] = (_i, [_vp, _vp, _sz, _vp, _sz, _c.POINTER(_sz)
 PROTOTYPES['kbbq_inflate_bgzf_host'] = (_i, [_vp, _c.c_uint32, _vp, _c.c_uint32, _c.c_uint32])
 PROTOTYPES['kbbq_inflate_use_ctx'] = (_i, [_vp])
 PROTOTYPES['kbbq_inflate_stats_get'] = (_i, [_c.POINTER(InflateStats)])
+
+
+class BamScanInfo(ctypes.Structure):
+    """kbbq_bam_scan_info (include/kbbq_hip.h "BAM input")."""
+    _fields_ = [('n', _i64), ('cig_total', _i64), ('max_l_seq', _c.c_int32), ('n_ref', _c.c_int32), ('n_rg', _c.c_int32),
+                ('pad', _c.c_int32), ('header_bytes', _u64), ('rg_bytes', _u64), ('refs_off', _u64), ('records_off', _u64),
+                ('max_record', _u64)]
+
+
+# kbbq_bam_words: 16 words per record, int32 but for clip / trim / status (uint32)
+BAM_WORDS = ('flag', 'ref_id', 'pos', 'pnext', 'tlen', 'qlen', 'qual_len', 'oq_len', 'rg', 'cig_n', 'ref_span', 'clip', 'trim',
+             'status', 'pad0', 'pad1')
+BAM_ST_RECORD, BAM_ST_LONG, BAM_ST_QUAL, BAM_ST_TEXT, BAM_ST_RANGE = 1, 2, 4, 8, 16   # KBBQ_BAM_ST_*
+PROTOTYPES['kbbq_bam_scan'] = (_i, [_vp, _sz, _c.POINTER(BamScanInfo), _vp, _vp, _vp, _vp, _vp])
+PROTOTYPES['kbbq_bam_decode_dev'] = (_i, [_vp, _vp, _sz, _vp, _i64, _i, _vp, _vp, _i, _i, _vp, _sz] + [_vp] * 5 + [_c.POINTER(_c.c_uint32)])
+PROTOTYPES['kbbq_bam_decode'] = (_i, [_vp, _sz, _vp, _i64, _i, _vp, _vp, _i, _i, _vp, _sz] + [_vp] * 5 + [_c.POINTER(_c.c_uint32)])
 PROTOTYPES['kbbq_accumulate_bands_dev'] = (_i, [_vp, _c.POINTER(Band), _i, _i, _i, _i, _i, _vp])
 PROTOTYPES['kbbq_apply_bands_dev'] = (_i, [_vp, _c.POINTER(Band), _i, _i, _i, _i, _vp])
 

@@ -307,6 +307,38 @@ class AlignmentFile:
         """pysam compatibility; the mapping is released when the last user of the handle goes away."""
 
 
+LAST_RUN = {}          # 'bam_in': what the last alignments() call did -- route, records, stream_bytes, h2d_bytes, slabs, fallback
+
+
+class DeviceAlignments(AlignmentFile):
+    """A BAM file whose records a kernel decoded into resident planes (kbbq/_bamin.py): `header` is the scan's header lines,
+    batch() a DeviceBatch.  What needs the SAM lines -- iteration, names in an error message -- opens the host reader on demand."""
+
+    def __init__(self, path, batch, header):
+        self._path, self._batch, self._reads = path, batch, None
+        self.header = SamHeader(header)
+
+
+def alignments(path, device=None, slab_bytes=None, planes=None):
+    """AlignmentFile(path), or -- with device=True, or device=None and KBBQ_GPU_BAM=1 -- a DeviceAlignments when the file is a
+    BGZF-compressed BAM file, the process is no rank of a launcher and the decode vouches for every record.  In every other case
+    the host reader opens the file as it always did (and raises what it always raised).  slab_bytes: the staging slab (default
+    KBBQ_STAGE_MB); planes: the planes to keep resident, of 'seq', 'qual', 'oq' (default all).  LAST_RUN['bam_in'] says which
+    route was taken and why."""
+    stats = dict(route='host', records=0, stream_bytes=0, h2d_bytes=0, slabs=0, fallback='not asked for')
+    from . import _bamin
+    if _bamin.wanted(device):
+        batch, header, stats = _bamin.open_device(path, slab_bytes, _bamin.PLANES if planes is None else tuple(planes))
+        if batch is not None:
+            LAST_RUN['bam_in'] = stats
+            return DeviceAlignments(path, batch, header)
+    stats.update(route='host')
+    LAST_RUN['bam_in'] = stats
+    out = AlignmentFile(path)
+    stats.update(records=len(out))
+    return out
+
+
 class FastaFile:
     """A FASTA file read whole (plain or gzip / bgzip-compressed): {name: sequence}; the name is the header line's
     first word.  Records are cut and their line ends removed by bytes operations (a genome is tens of millions of

@@ -440,7 +440,10 @@ def _kmer_tally(bamfileobj, inputs, k, min_count, slots, prefilter, filter_bits,
     pitch = fastx.pitch_for(S)
     budget = dev.device_budget()
     up = lambda a: T.from_numpy(np.ascontiguousarray(a)).cuda()
-    d_seq, d_qual = up(b.plane(0, pitch)), up(b.plane(2 if use_oq else 1, pitch))
+    if hasattr(b, 'device_plane'):             # a DeviceBatch (kbbq/_bamin.py): the planes are where the decode left them
+        d_seq, d_qual = b.device_plane(0, pitch), b.device_plane(2 if use_oq else 1, pitch)
+    else:
+        d_seq, d_qual = up(b.plane(0, pitch)), up(b.plane(2 if use_oq else 1, pitch))
     d_len, d_clip, d_trim, d_flags = (up(x.view(np.int32)) for x in (lens, clip, trim, flags))
     resident = 3 * n * pitch + 20 * n          # SEQ, qualities and the flag plane; the per-read words
     windows = ungated = kmer.kmer_total(lens, k) if kmers_from is None else 0

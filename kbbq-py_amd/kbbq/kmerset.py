@@ -232,7 +232,8 @@ def _read_alignments(path, need_qual, use_oq, exclude_flags):
     """Alignments as `bqsr --kmers` counts them: every base of SEQ of every record (soft clips too); a record with FLAG &
     exclude_flags is a row of length 0.  Records of any lengths: counting has no cycle axis."""
     from . import aln, fastx
-    b = aln.AlignmentFile(path).batch()
+    planes = ('seq',) + ((('oq' if use_oq else 'qual'),) if need_qual else ())
+    b = aln.alignments(path, planes=planes).batch()          # (KBBQ_GPU_BAM=1: a DeviceBatch, kbbq/_bamin.py; else the reader's)
     n = b.n
     if n == 0:
         return _Input(np.zeros((0, 16), np.uint8), np.zeros((0, 16), np.uint8) if need_qual else None, np.zeros(0, np.uint32), 0)
@@ -243,6 +244,7 @@ def _read_alignments(path, need_qual, use_oq, exclude_flags):
     lens = b.qlen.astype(np.uint32)
     lens[excluded] = 0
     pitch = fastx.pitch_for(max(S, 1))
+    take = getattr(b, 'device_plane', b.plane)               # a DeviceBatch's planes stay where the decode left them
     qual = None
     if need_qual:
         have = b.oq_len if use_oq else b.qual_len
@@ -252,8 +254,8 @@ def _read_alignments(path, need_qual, use_oq, exclude_flags):
             raise ValueError('%s: record %d (%s) has %d qualities for %d bases: --kmer-min-qual needs a quality for every base%s'
                              % (path, i, b._text(0, i), max(int(have[i]), 0), int(b.qlen[i]),
                                 '' if use_oq else ' (-u takes them from the OQ tag)'))
-        qual = b.plane(2 if use_oq else 1, pitch)[:n]
-    return _Input(b.plane(0, pitch)[:n], qual, lens, n, int(excluded.sum()))
+        qual = take(2 if use_oq else 1, pitch)[:n]
+    return _Input(take(0, pitch)[:n], qual, lens, n, int(excluded.sum()))
 
 
 class _Inputs:
@@ -282,10 +284,12 @@ class _Inputs:
 def _counted_plane(inp, k, Q, word=None):
     """(plane, meta) the prefilter and the count read of one input: its host arrays (the host-buffer entry points stage them slab
     by slab), or with the gate the gated device plane beside the device's copy of the lengths."""
-    if Q is None or inp.reads == 0:
-        return inp.seq, inp.meta
     from . import _device as dev
     from . import kmer
+    if Q is None or inp.reads == 0:
+        if kmer._on_device(inp.seq):                         # a resident plane (kbbq/_bamin.py) takes the device's copy of the lengths
+            return inp.seq, kmer._to_device(dev._torch(), inp.meta, np.uint32)
+        return inp.seq, inp.meta
     d_meta = kmer._to_device(dev._torch(), inp.meta, np.uint32)
     plane, _ = kmer.gate_plane(inp.seq, inp.qual, d_meta, k, Q, windows=word)
     return plane, d_meta

@@ -415,7 +415,9 @@ def bqsr(args):
         _start()                             # under a launcher every rank joins its group, and bam_to_kmer_covariates refuses on each
         info = {}
         more = _kmer_kw(args, 'bqsr')
-        _bqsr.bam_to_report_kmers(aln.AlignmentFile(args.bam), use_oq=args.use_oq, info=info, **more).write(args.gatkreport)
+        # (KBBQ_GPU_BAM=1: a BAM file's records are decoded on the device, kbbq/_bamin.py; without it this IS AlignmentFile(args.bam))
+        bam = aln.alignments(args.bam, planes=('seq', 'oq' if args.use_oq else 'qual'))
+        _bqsr.bam_to_report_kmers(bam, use_oq=args.use_oq, info=info, **more).write(args.gatkreport)
         sys.stderr.write(kmer.summary_line('bqsr', info, more, 'flagged_bases'))
         return
     from . import benchmark as _bm
