@@ -1097,6 +1097,8 @@ int kbbq_bgzf_eof(uint8_t* out);
  * the planes the apply kernel (kbbq_apply_aligned*_dev) read and wrote, so that neither crosses the bus again.
  * kbbq_bam_header: the stream's head (magic .. references); out == NULL: *used = the bytes needed.  KBBQ_E_RANGE for an @SQ line
  * without SN or a decimal LN.
+ * kbbq_bam_header_text: the same head, by the same code, of header lines given as text (each line ended by '\n'; empty lines are
+ * skipped) -- for a caller that has the lines but no kbbq_sam, as kbbq_bam_scan's caller has.
  * kbbq_bam_check: what BAM cannot hold, of alignments [first, first + n): an RNAME or RNEXT that is not in @SQ, a QNAME longer than
  * 254 bytes, more than 65535 CIGAR operations, an unknown CIGAR letter, a malformed tag, an integer tag outside int32 / uint32, SEQ
  * '*' with a QUAL (or a QUAL of another length than SEQ), a FLAG or MAPQ beyond its field -- KBBQ_E_RANGE, the message naming
@@ -1123,6 +1125,7 @@ typedef struct kbbq_bam_desc {
     uint32_t skel_off, head_bytes, tail_bytes, l_seq, stream_off, qual_src;
 } kbbq_bam_desc;
 int kbbq_bam_header(const kbbq_sam* f, uint8_t* out, size_t cap, size_t* used);
+extern int kbbq_bam_header_text(const uint8_t* text, size_t n, uint8_t* out, size_t cap, size_t* used);
 int kbbq_bam_check(const kbbq_sam* f, int64_t first, int64_t n, int64_t* bad_index);
 int kbbq_bam_layout(const kbbq_sam* f, int64_t first, int64_t n, int set_oq, const uint8_t* keep_qual, kbbq_bam_desc* desc,
                     size_t* skel_bytes, size_t* stream_bytes);
@@ -1291,6 +1294,40 @@ extern int kbbq_bam_decode_dev(kbbq_ctx* ctx, const uint8_t* d_slab, size_t slab
 extern int kbbq_bam_decode(const uint8_t* slab, size_t slab_bytes, const uint32_t* rec_off, int64_t m, int pitch, const uint32_t* rg_off,
                     const uint8_t* rg_ids, int n_rg, int n_ref, const uint32_t* cig_off, size_t cig_cap, uint8_t* seq, uint8_t* qual,
                     uint8_t* oq, kbbq_bam_words* words, uint32_t* cigar, uint32_t* any_status);
+
+/* ---- BAM recode: the --bam-out skeleton from resident BAM records (csrc/kbbq_bam_recode.h, kbbq/_bamin.py, kbbq/_bamout.py) ------
+ * BAM in, BAM out: the records kbbq_bam_decode_dev read hold every byte of the skeleton kbbq_bam_skeleton writes from the SAM
+ * text of the same records, but for the `bin` field (computed), integer tags (the text route stores each in the first type of
+ * c C s S i I that holds its value) and an absent QUAL (0xFF throughout).  The host route -- kbbq_sam_open on the text of the
+ * records, then kbbq_bam_layout and kbbq_bam_skeleton -- stays the reference: what the recode writes is what those two write, or
+ * a status bit.
+ * kbbq_bam_recode_dev (synchronous) / kbbq_bam_recode (the same over host memory, by the same per-record code: br_size,
+ * br_write): records [first, first + m) of an inflated BAM image.  rec_off: kbbq_bam_scan's array of the WHOLE image (64-bit
+ * offsets of the records' bodies; entries [first, first + m) are read).  set_oq, keep (m bytes, nonzero: QUAL stays as read; NULL:
+ * none) and n_ref as kbbq_bam_layout / kbbq_bam_decode take them.  Written: desc[0, m) (the m descriptors of kbbq_bam_layout),
+ * status[0, m), skel[0, *skel_bytes) (the skeleton of kbbq_bam_skeleton), *skel_bytes, *stream_bytes, *any_status (the OR of the
+ * status words).  The offsets are an exclusive scan done on the device.  skel == NULL (skel_cap 0): everything but the skeleton.
+ * status != 0: the record's text round trip is not provably the identity -- its descriptor is zeros (it takes no room in the
+ * skeleton or the stream) and nothing of it is written; the caller hands the file to the host route.  The bits are the decode's
+ * (KBBQ_BAM_ST_RECORD .. KBBQ_BAM_ST_RANGE, decided by the decode's own code on the same bytes; RANGE: the record does not lie in
+ * the image) and
+ *   KBBQ_BAM_ST_FLOAT   an `f` tag or a B:f array (the reader renders floats with %g)
+ *   KBBQ_BAM_ST_REF     a refID or next_refID below -1 (the reader shows every negative one as '*', which is written as -1)
+ * refID / next_refID are otherwise kept as stored: the caller sees to it that the header's @SQ lines name the binary reference
+ * list in order.  Whatever the bytes, nothing outside the image is read, nothing outside desc[0, m), status[0, m) and
+ * skel[0, *skel_bytes) is written, and every length is checked against the record's end in 64-bit arithmetic before it is used.
+ * KBBQ_E_RANGE: a stream of 2^31 bytes or more (offsets are 32 bits), as kbbq_bam_layout; the skeleton is not written.
+ * KBBQ_E_ARG: a skeleton larger than skel_cap (*skel_bytes says how large; the skeleton is not written); and, before any HIP
+ * call, a NULL ctx, buffer or result pointer, first < 0, m outside 0..2^31 - 1, n_ref < 0, a bad alignment (rec_off 8 bytes,
+ * desc / status 4).                                                                                                             */
+#define KBBQ_BAM_ST_FLOAT  32u
+#define KBBQ_BAM_ST_REF    64u
+extern int kbbq_bam_recode_dev(kbbq_ctx* ctx, const uint8_t* d_image, size_t image_bytes, const uint64_t* d_rec_off, int64_t first,
+                        int64_t m, int set_oq, const uint8_t* d_keep, int n_ref, kbbq_bam_desc* d_desc, uint8_t* d_skel,
+                        size_t skel_cap, uint32_t* d_status, size_t* skel_bytes, size_t* stream_bytes, uint32_t* any_status);
+extern int kbbq_bam_recode(const uint8_t* image, size_t image_bytes, const uint64_t* rec_off, int64_t first, int64_t m, int set_oq,
+                    const uint8_t* keep, int n_ref, kbbq_bam_desc* desc, uint8_t* skel, size_t skel_cap, uint32_t* status,
+                    size_t* skel_bytes, size_t* stream_bytes, uint32_t* any_status);
 
 #ifdef __cplusplus
 }

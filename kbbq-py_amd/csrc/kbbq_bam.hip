@@ -1,8 +1,10 @@
-// kbbq_bam.hip -- libkbbq_hip.so: BAM output -- records assembled on the GPU, and the BAI / CSI index of what was written
+// kbbq_bam.hip -- libkbbq_hip.so: BAM output -- records assembled on the GPU, and the BAI / CSI index of what was written --, BAM
+// input -- records decoded on the GPU --, and the recode from the one to the other
 // (C ABI: include/kbbq_hip.h; shared: kbbq_lib.h).
 #include "kbbq_bam_out.h"
 #include "kbbq_bam_index.h"
 #include "kbbq_bam_in.h"
+#include "kbbq_bam_recode.h"
 #include "kbbq_lib.h"
 #include "host_threads.h"
 
@@ -227,6 +229,107 @@ int kbbq_bam_decode(const uint8_t* slab, size_t slab_bytes, const uint32_t* rec_
         for (size_t r = lo; r < hi; ++r) met[t] |= bd_record(J, (u32)r);
     });
     for (u32 v : met) *any_status |= v;
+    return KBBQ_OK;
+}
+
+// ---- BAM recode (csrc/kbbq_bam_recode.h) -----------------------------------------------------------------------------------------
+static int bam_recode_args(const char* who, const void* image, const void* rec_off, int64_t first, int64_t m, int n_ref, const void* desc,
+                           const void* skel, size_t skel_cap, const void* status, size_t* skel_bytes, size_t* stream_bytes, uint32_t* any_status)
+{
+    if (skel_bytes) *skel_bytes = 0;
+    if (stream_bytes) *stream_bytes = 0;
+    if (any_status) *any_status = 0;
+    if (!skel_bytes || !stream_bytes || !any_status) return fail(KBBQ_E_ARG, "%s: NULL result pointer", who);
+    if (first < 0 || m < 0 || m > (int64_t)INT_MAX) return fail(KBBQ_E_ARG, "%s: first must not be negative, m must be in 0..2^31 - 1", who);
+    if (n_ref < 0) return fail(KBBQ_E_ARG, "%s: n_ref is negative", who);
+    if (m > 0 && (!image || !rec_off || !desc || !status)) return fail(KBBQ_E_ARG, "%s: NULL buffer", who);
+    if (!skel && skel_cap) return fail(KBBQ_E_ARG, "%s: skel is NULL but skel_cap is not 0", who);
+    if ((uintptr_t)rec_off & 7) return fail(KBBQ_E_ARG, "%s: rec_off must be 8-byte aligned", who);
+    if (((uintptr_t)desc | (uintptr_t)status) & 3) return fail(KBBQ_E_ARG, "%s: the descriptors and status words must be 4-byte aligned", who);
+    return KBBQ_OK;
+}
+
+// the sizes the scan found: may the write step run?
+static int bam_recode_sizes(const char* who, uint64_t skel, uint64_t stream, const void* skel_buf, size_t skel_cap, size_t* skel_bytes,
+                            size_t* stream_bytes, bool* write)
+{
+    *write = false;
+    if (stream >= ((uint64_t)1 << 31))
+        return fail(KBBQ_E_RANGE, "%s: the stream of a slab must stay below 2^31 bytes (offsets are 32 bits): fewer records per slab", who);
+    *skel_bytes = (size_t)skel; *stream_bytes = (size_t)stream;
+    if (!skel_buf) return KBBQ_OK;                                       // sizes, descriptors and status words only
+    if (skel > (uint64_t)skel_cap) return fail(KBBQ_E_ARG, "%s: the skeleton takes %llu bytes, skel holds %llu", who, (unsigned long long)skel, (unsigned long long)skel_cap);
+    *write = true;
+    return KBBQ_OK;
+}
+
+int kbbq_bam_recode_dev(kbbq_ctx* c, const uint8_t* d_image, size_t image_bytes, const uint64_t* d_rec_off, int64_t first, int64_t m,
+                        int set_oq, const uint8_t* d_keep, int n_ref, kbbq_bam_desc* d_desc, uint8_t* d_skel, size_t skel_cap,
+                        uint32_t* d_status, size_t* skel_bytes, size_t* stream_bytes, uint32_t* any_status)
+{
+    const char* who = "kbbq_bam_recode_dev";
+    int rc = bam_recode_args(who, d_image, d_rec_off, first, m, n_ref, d_desc, d_skel, skel_cap, d_status, skel_bytes, stream_bytes, any_status);
+    if (rc) return rc;
+    if (!c) return fail(KBBQ_E_ARG, "%s: ctx is NULL", who);
+    if (m == 0) return KBBQ_OK;
+    HIPCHK(hipSetDevice(c->device));
+    // scratch: [any u32, pad | totals 2 x u64 | per scan workgroup 2 x u64]
+    const size_t nb = ((size_t)m + BR_THREADS - 1) / BR_THREADS;
+    rc = grow_scratch(c, c->bam_recode, 24 + 16 * nb);
+    if (rc) return rc;
+    uint8_t* s = (uint8_t*)c->bam_recode.p;
+    HIPCHK(hipMemsetAsync(s, 0, 24, c->stream));
+    BrParams p;
+    p.job = BrJob{d_image, (u64)image_bytes, d_rec_off + first, (u32)m, n_ref, set_oq ? 1u : 0u, d_keep, d_desc, d_status, d_skel, 0};
+    p.dec = br_decode_job(p.job);
+    p.any = (u32*)s; p.total = (uint64_t*)(s + 8); p.part = (uint64_t*)(s + 24);
+    const unsigned grid = (unsigned)((m + BR_RECORDS - 1) / BR_RECORDS);
+    hipLaunchKernelGGL(kbr_size, dim3(grid), dim3(BR_THREADS), 0, c->stream, p);
+    hipLaunchKernelGGL(kbr_sums, dim3((unsigned)nb), dim3(BR_THREADS), 0, c->stream, p);
+    hipLaunchKernelGGL(kbr_scan_blocks, dim3(1), dim3(BR_THREADS), 0, c->stream, p, (u32)nb);
+    hipLaunchKernelGGL(kbr_offsets, dim3((unsigned)nb), dim3(BR_THREADS), 0, c->stream, p);
+    HIPCHK(hipGetLastError());
+    uint64_t words[3] = {0, 0, 0};                                       // 24 bytes back: the status, the two sizes
+    HIPCHK(hipMemcpyAsync(words, s, sizeof words, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    *any_status = (u32)words[0];
+    bool write = false;
+    rc = bam_recode_sizes(who, words[1], words[2], d_skel, skel_cap, skel_bytes, stream_bytes, &write);
+    if (rc || !write) return rc;
+    p.job.skel_bytes = words[1];
+    hipLaunchKernelGGL(kbr_write, dim3(grid), dim3(BR_THREADS), 0, c->stream, p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return KBBQ_OK;
+}
+
+int kbbq_bam_recode(const uint8_t* image, size_t image_bytes, const uint64_t* rec_off, int64_t first, int64_t m, int set_oq,
+                    const uint8_t* keep, int n_ref, kbbq_bam_desc* desc, uint8_t* skel, size_t skel_cap, uint32_t* status,
+                    size_t* skel_bytes, size_t* stream_bytes, uint32_t* any_status)
+{
+    const char* who = "kbbq_bam_recode";
+    int rc = bam_recode_args(who, image, rec_off, first, m, n_ref, desc, skel, skel_cap, status, skel_bytes, stream_bytes, any_status);
+    if (rc || m == 0) return rc;
+    BrJob J{image, (u64)image_bytes, rec_off + first, (u32)m, n_ref, set_oq ? 1u : 0u, keep, desc, status, skel, 0};
+    const BdJob D = br_decode_job(J);
+    std::vector<u32> met(kbbq_threads_for((size_t)m * 512), 0);
+    kbbq_parallel_parts((size_t)m, (unsigned)met.size(), [&](unsigned t, size_t lo, size_t hi) {
+        for (size_t r = lo; r < hi; ++r) met[t] |= br_size(J, D, (u32)r);
+    });
+    for (u32 v : met) *any_status |= v;
+    uint64_t at_skel = 0, at_stream = 0;
+    for (int64_t r = 0; r < m; ++r) {
+        kbbq_bam_desc& d = desc[r];
+        d.skel_off = (u32)at_skel; d.stream_off = (u32)at_stream;        // (a stream of 2^31 bytes or more is refused below)
+        at_skel += br_skel_size(d); at_stream += br_stream_size(d);
+    }
+    bool write = false;
+    rc = bam_recode_sizes(who, at_skel, at_stream, skel, skel_cap, skel_bytes, stream_bytes, &write);
+    if (rc || !write) return rc;
+    J.skel_bytes = at_skel;
+    kbbq_parallel_parts((size_t)m, kbbq_threads_for((size_t)m * 512), [&](unsigned, size_t lo, size_t hi) {
+        for (size_t r = lo; r < hi; ++r) if (!status[r]) br_write(J, (u32)r, desc[r], 0, 1);
+    });
     return KBBQ_OK;
 }
 

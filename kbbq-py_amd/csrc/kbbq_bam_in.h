@@ -155,6 +155,8 @@ BD_HD uint32_t bd_trim(const kbbq_bam_words& w, const uint8_t* cg)
     return (uint32_t)(lo & 0xFFFF) | (uint32_t)(hi & 0xFFFF) << 16;
 }
 
+BD_HD void bd_open_at(const BdJob& J, uint64_t off, BdInfo& I);
+
 // lane 0: everything of record `row` but its rows.  I.w.status != 0: the record is not decoded (nothing else of I.w is meaningful).
 BD_HD void bd_open(const BdJob& J, uint32_t row, BdInfo& I)
 {
@@ -165,8 +167,16 @@ BD_HD void bd_open(const BdJob& J, uint32_t row, BdInfo& I)
     const bool cig_range = clo <= chi && chi <= J.cig_cap;
     if (cig_range) { I.cig_lo = (uint32_t)clo; I.cig_n = (uint32_t)(chi - clo); }
     else w.status |= KBBQ_BAM_ST_RANGE;
+    bd_open_at(J, J.rec_off[row], I);
+}
+
+// bd_open behind the CIGAR range: the record whose body lies at `off` of the slab (any 64-bit offset: kbbq_bam_recode.h walks a
+// whole stream by it).  I is zeroed but for cig_lo / cig_n and the range's status bit.
+BD_HD void bd_open_at(const BdJob& J, uint64_t off, BdInfo& I)
+{
+    kbbq_bam_words& w = I.w;
+    const bool cig_range = !(w.status & KBBQ_BAM_ST_RANGE);
     // the record inside the slab: its block_size word in front of the body, the body's end
-    const uint64_t off = J.rec_off[row];
     if (off < 4 || off > J.slab_bytes) { w.status |= KBBQ_BAM_ST_RANGE; return; }
     const int32_t bs = bd_s32(J.slab + off - 4);
     if (bs < 0 || (uint64_t)bs > J.slab_bytes - off) { w.status |= KBBQ_BAM_ST_RANGE; return; }

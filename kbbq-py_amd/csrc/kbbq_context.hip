@@ -143,7 +143,7 @@ int kbbq_ctx_destroy(kbbq_ctx* c)
         for (auto& pr : c->ev[w]) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
     if (c->d_status) (void)hipFree(c->d_status);
     if (c->d_stats) (void)hipFree(c->d_stats);
-    for (DevScratch* s : {&c->wgplan, &c->ops4, &c->tally, &c->rowlut, &c->bgzf_tok, &c->bgzf_off, &c->bgzf_blocks, &c->bam_words, &c->bam_index})
+    for (DevScratch* s : {&c->wgplan, &c->ops4, &c->tally, &c->rowlut, &c->bgzf_tok, &c->bgzf_off, &c->bgzf_blocks, &c->bam_words, &c->bam_index, &c->bam_recode})
         if (s->p) (void)hipFree(s->p);
     for (int b = 0; b < 2; ++b) {
         if (c->stage_host[b]) (void)hipHostFree(c->stage_host[b]);

@@ -43,6 +43,7 @@ struct kbbq_ctx {
     DevScratch bgzf_blocks;           // kbbq_bgzf_deflate (host buffers): a slab's blocks before they are packed
     DevScratch bam_words;             // kbbq_bam_assemble_dev: the lowest row with a quality below 0, the lowest that does not fit
     DevScratch bam_index;             // kbbq_bam_index_dev: words, keys, runs, lengths, head rows, workgroup totals (csrc/kbbq_bam_index.h)
+    DevScratch bam_recode;            // kbbq_bam_recode_dev: the status, the two sizes, the scan's workgroup sums (csrc/kbbq_bam_recode.h)
     // kbbq_inflate_bgzf: staging and a stream of its own -- a reader may inflate on a thread of its own while the context's other
     // staging is in use -- and the lock that makes it one call at a time
     void* inflate_host[2] = {nullptr, nullptr}; void* inflate_dev[2] = {nullptr, nullptr}; size_t inflate_bytes = 0;

@@ -570,10 +570,20 @@ struct BamRefs {
     std::vector<int> of_contig;                          // the reader's contig number -> refID; -1 for '*', -2 when @SQ lacks it
 };
 
-bool bam_refs(const kbbq_sam* f, BamRefs& R, std::string& err)
+using BamLines = std::vector<std::pair<const uint8_t*, size_t>>;       // header lines, without their line ends
+
+BamLines bam_header_lines(const kbbq_sam* f)
 {
-    for (size_t h = 0; h < f->hdr0.size(); ++h) {
-        const uint8_t* p = f->buf + f->hdr0[h]; const uint8_t* e = p + f->hdrlen[h];
+    BamLines lines;
+    for (size_t h = 0; h < f->hdr0.size(); ++h) lines.emplace_back(f->buf + f->hdr0[h], (size_t)f->hdrlen[h]);
+    return lines;
+}
+
+// the references of the @SQ lines among `lines`
+bool bam_refs_of(const BamLines& lines, BamRefs& R, std::string& err)
+{
+    for (const auto& line : lines) {
+        const uint8_t* p = line.first; const uint8_t* e = p + line.second;
         if (e - p < 3 || memcmp(p, "@SQ", 3) != 0) continue;
         std::string name; int64_t len = -1; bool has_name = false;
         const uint8_t* q = (const uint8_t*)memchr(p, '\t', (size_t)(e - p));
@@ -593,6 +603,12 @@ bool bam_refs(const kbbq_sam* f, BamRefs& R, std::string& err)
         R.index[name] = (int)R.sq.size();                 // (a name given twice: its last line's index)
         R.sq.emplace_back(name, len);
     }
+    return true;
+}
+
+bool bam_refs(const kbbq_sam* f, BamRefs& R, std::string& err)
+{
+    if (!bam_refs_of(bam_header_lines(f), R, err)) return false;
     R.of_contig.resize(f->contigs.size());
     for (size_t c = 0; c < f->contigs.size(); ++c) {
         if (f->contigs[c] == "*") { R.of_contig[c] = -1; continue; }
@@ -797,27 +813,24 @@ int bam_refs_or_error(const kbbq_sam* f, BamRefs& R)
     return bam_refs(f, R, err) ? KBBQ_OK : kbbq_set_error_(KBBQ_E_RANGE, err.c_str());
 }
 
-}  // namespace
-
-extern "C" {
-
-int kbbq_bam_header(const kbbq_sam* f, uint8_t* out, size_t cap, size_t* used)
+// the stream's head of header lines: magic, the text (every line with its '\n'), the references of the @SQ lines
+int bam_header_of(const char* who, const BamLines& lines, uint8_t* out, size_t cap, size_t* used)
 {
-    if (!f || !used) return kbbq_set_error_(KBBQ_E_ARG, "kbbq_bam_header: NULL argument");
     BamRefs R;
-    if (int rc = bam_refs_or_error(f, R)) return rc;
+    std::string err;
+    if (!bam_refs_of(lines, R, err)) return kbbq_set_error_(KBBQ_E_RANGE, err.c_str());
     size_t text = 0, need = 12;
-    for (size_t h = 0; h < f->hdr0.size(); ++h) text += (size_t)f->hdrlen[h] + 1;
+    for (const auto& line : lines) text += line.second + 1;
     for (auto& sq : R.sq) need += 4 + sq.first.size() + 1 + 4;
     need += text;
     *used = need;
     if (!out) return KBBQ_OK;
-    if (cap < need) return kbbq_set_error_(KBBQ_E_ARG, "kbbq_bam_header: output buffer too small");
-    if (text > (size_t)INT32_MAX) return kbbq_set_error_(KBBQ_E_RANGE, "kbbq_bam_header: a header text of 2^31 bytes or more");
+    if (cap < need) return kbbq_set_error_(KBBQ_E_ARG, (std::string(who) + ": output buffer too small").c_str());
+    if (text > (size_t)INT32_MAX) return kbbq_set_error_(KBBQ_E_RANGE, (std::string(who) + ": a header text of 2^31 bytes or more").c_str());
     uint8_t* o = out;
     memcpy(o, "BAM\1", 4); o += 4;
     o = bam_put(o, (int32_t)text);
-    for (size_t h = 0; h < f->hdr0.size(); ++h) { memcpy(o, f->buf + f->hdr0[h], f->hdrlen[h]); o += f->hdrlen[h]; *o++ = '\n'; }
+    for (const auto& line : lines) { memcpy(o, line.first, line.second); o += line.second; *o++ = '\n'; }
     o = bam_put(o, (int32_t)R.sq.size());
     for (auto& sq : R.sq) {
         o = bam_put(o, (int32_t)(sq.first.size() + 1));
@@ -825,6 +838,29 @@ int kbbq_bam_header(const kbbq_sam* f, uint8_t* out, size_t cap, size_t* used)
         o = bam_put(o, (int32_t)sq.second);
     }
     return KBBQ_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int kbbq_bam_header(const kbbq_sam* f, uint8_t* out, size_t cap, size_t* used)
+{
+    if (!f || !used) return kbbq_set_error_(KBBQ_E_ARG, "kbbq_bam_header: NULL argument");
+    return bam_header_of("kbbq_bam_header", bam_header_lines(f), out, cap, used);
+}
+
+int kbbq_bam_header_text(const uint8_t* text, size_t n, uint8_t* out, size_t cap, size_t* used)
+{
+    if (!used || (n && !text)) return kbbq_set_error_(KBBQ_E_ARG, "kbbq_bam_header_text: NULL argument");
+    BamLines lines;
+    for (size_t at = 0; at < n;) {
+        const uint8_t* nl = (const uint8_t*)memchr(text + at, '\n', n - at);
+        const size_t end = nl ? (size_t)(nl - text) : n;
+        if (end > at) lines.emplace_back(text + at, end - at);
+        at = end + 1;
+    }
+    return bam_header_of("kbbq_bam_header_text", lines, out, cap, used);
 }
 
 int kbbq_bam_check(const kbbq_sam* f, int64_t first, int64_t n, int64_t* bad_index)

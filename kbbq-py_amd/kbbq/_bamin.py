@@ -146,6 +146,31 @@ def _slab_tables(scan, a, b, lo):
     return rec, cig
 
 
+SQ_MISMATCH = 'the @SQ lines do not name the binary reference list in order'
+
+
+def sq_lines_match(scan):
+    """None when a record's refID means the same to the text route as to the binary list: the @SQ lines of the scan's header
+    (made from the list when the text has none) name the list's references in order, each once, each with a decimal LN, none
+    called '*' or '=' -- else SQ_MISMATCH.  csrc/sam_host.cpp bam_refs reads the lines the same way."""
+    names = []
+    for line in scan.header:
+        if not line.startswith('@SQ'):
+            continue
+        name = length = None
+        for field in line.split('\t')[1:]:
+            if field.startswith('SN:'):
+                name = field[3:]
+            elif field.startswith('LN:'):
+                length = field[3:]
+        if name is None or length is None or not length.isascii() or not length.isdigit() or int(length) > 0x7FFFFFFF:
+            return SQ_MISMATCH
+        names.append(name)
+    if names != list(scan.ref_names) or len(set(names)) != len(names) or '*' in names or '=' in names:
+        return SQ_MISMATCH
+    return None
+
+
 def decode_host(image, scan, pitch, slab_bytes=None, planes=PLANES, cigar=True):
     """The host twin over the whole image, slab by slab like the device route: dict(seq, qual, oq: uint8 [n, pitch] or None;
     words: int32 [n, 16]; cigar: uint32 or None; status: the OR of every record's)."""
@@ -189,6 +214,7 @@ class DeviceBatch:
         self.ref_id = col['ref_id']
         self.rg_ids = list(scan.rg_ids)
         self._contigs = self._cigar = self._host = None
+        self.stream = None                    # a Stream: the record stream kept resident for the recode (open_device keep_stream=True)
 
     def _contig(self):
         """The reader's numbering: names in order of first appearance, '*' for a negative refID."""
@@ -249,6 +275,10 @@ class DeviceBatch:
             out[:n, :w] = rows[:n, :w]
         return out
 
+    def release_stream(self):
+        """The resident record stream and its offsets are freed (the writer's close())."""
+        self.stream = None
+
     def reader(self):
         if self._host is None:
             from . import aln
@@ -265,10 +295,45 @@ class DeviceBatch:
         return self.reader().batch().line(i)
 
 
-def decode_device(raw, scan, pitch, slab_bytes=None, planes=PLANES, poison=None):
+class Stream:
+    """The record stream of an image (records_off .. its end) in device memory, with the 64-bit offsets of the records' bodies in
+    it: what kbbq_bam_recode_dev reads."""
+
+    def __init__(self, d_bytes, d_rec_off, n_ref, maxlen, rec_off, nbytes):
+        self.d_bytes, self.d_rec_off, self.n_ref, self.maxlen = d_bytes, d_rec_off, int(n_ref), int(maxlen)
+        self.rec_off, self.nbytes = rec_off, int(nbytes)         # (host copy of the offsets: the skeleton's upper bound)
+
+    def skel_cap(self, first, m, set_oq):
+        """An upper bound of the skeleton of records [first, first + m): their bytes, and an OQ tag each with set_oq."""
+        if m <= 0:
+            return 0
+        end = int(self.rec_off[first + m]) - 4 if first + m < len(self.rec_off) else self.nbytes
+        return end - (int(self.rec_off[first]) - 4) + (m * (self.maxlen + 4) if set_oq else 0)
+
+
+def recode_device(stream, first, m, set_oq, keep, d_stage=None, desc_bytes=0, cap=0):
+    """kbbq_bam_recode_dev on records [first, first + m) of a Stream.  d_stage: a uint8 device tensor that takes the descriptors
+    at its front and, from desc_bytes on, up to cap bytes of skeleton; None: no skeleton is written (the vouching pass).  keep:
+    a uint8 device tensor of m bytes, or None.  (skeleton bytes, stream bytes, the OR of the status words)."""
+    from . import _device as dev
+    T = dev._torch()
+    lib = N.load()
+    d_desc = d_stage if d_stage is not None else T.empty(max(m, 1) * 4 * N.BAM_DESC_WORDS, dtype=T.uint8, device='cuda')
+    d_status = T.empty(max(m, 1), dtype=T.int32, device='cuda')
+    sb, tb, st = ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.c_uint32(0)
+    N.check(lib.kbbq_bam_recode_dev(dev.context().handle, N.ptr(stream.d_bytes), stream.nbytes, N.ptr(stream.d_rec_off), first, m,
+                                    int(bool(set_oq)), N.ptr(keep), stream.n_ref, N.ptr(d_desc),
+                                    None if d_stage is None else N.ptr(d_stage.data_ptr() + desc_bytes), cap if d_stage is not None else 0,
+                                    N.ptr(d_status), ctypes.byref(sb), ctypes.byref(tb), ctypes.byref(st)))
+    return sb.value, tb.value, st.value
+
+
+def decode_device(raw, scan, pitch, slab_bytes=None, planes=PLANES, poison=None, keep_stream=False):
     """The image's records through kbd_decode, slab by slab through two page-locked buffers: (device planes by name, device words
     int32 [n, 16], device CIGAR words, the OR of every record's status, bytes uploaded, slabs).  Stops behind the first slab with
-    a status.  poison: a byte to fill every output with first (tests: the decode writes all of it)."""
+    a status.  poison: a byte to fill every output with first (tests: the decode writes all of it).
+    keep_stream: the slabs go up into ONE buffer that holds the whole record stream and stays (a Stream, returned behind the
+    others); every slab is then also put to the recode's size step, whose status bits join the decode's."""
     from . import _device as dev
     T = dev._torch()
     ctx = dev.context()
@@ -288,8 +353,16 @@ def decode_device(raw, scan, pitch, slab_bytes=None, planes=PLANES, poison=None)
     cuts = slabs(scan, slab_bytes)
     room = max((hi - lo for _, _, lo, hi in cuts), default=1)
     pinned = [dev.pinned('bamin', i, room) for i in range(min(len(cuts), 2))]
-    d_slab = T.empty(room, dtype=T.uint8, device='cuda')
     h2d = scan.rg_off.nbytes + scan.rg_bytes.nbytes
+    stream = None
+    if keep_stream:
+        base = scan.records_off
+        rel = (scan.rec_off.astype(np.int64) - base).astype(np.uint64) if n else np.zeros(1, np.uint64)
+        stream = Stream(T.empty(max(scan.stream_bytes, 16), dtype=T.uint8, device='cuda'), up(rel.view(np.int64)), scan.n_ref, scan.maxlen,
+                        rel[:n], scan.stream_bytes)
+        h2d += rel.nbytes
+    else:
+        d_slab = T.empty(room, dtype=T.uint8, device='cuda')
 
     def fill(k):                                                      # the image's bytes into page-locked memory
         _, _, lo, hi = cuts[k]
@@ -298,6 +371,8 @@ def decode_device(raw, scan, pitch, slab_bytes=None, planes=PLANES, poison=None)
         fill(0)
     status = done = 0
     for k, (a, b, lo, hi) in enumerate(cuts):
+        if stream is not None:
+            d_slab = stream.d_bytes[lo - base:]
         d_slab[:hi - lo].copy_(pinned[k % 2][:hi - lo], non_blocking=True)
         if k + 1 < len(cuts):
             fill(k + 1)                                               # ... the next slab's while this one goes up
@@ -312,15 +387,22 @@ def decode_device(raw, scan, pitch, slab_bytes=None, planes=PLANES, poison=None)
         h2d += (hi - lo) + rec.nbytes + cig.nbytes
         done += 1
         status |= any_status.value
+        if stream is not None and not status:
+            status |= recode_device(stream, a, b - a, 0, None)[2]
         if status and poison is None:
             break
-    del d_slab
+    d_slab = None
     dev.release_pinned('bamin')
+    if keep_stream:
+        return d_planes, d_words, d_cigar, status, h2d, done, stream
     return d_planes, d_words, d_cigar, status, h2d, done
 
 
-def open_device(path, slab_bytes=None, planes=PLANES):
-    """(DeviceBatch, header lines, stats) when the device route holds, else (None, None, stats) with stats['fallback'] the reason."""
+def open_device(path, slab_bytes=None, planes=PLANES, keep_stream=False):
+    """(DeviceBatch, header lines, stats) when the device route holds, else (None, None, stats) with stats['fallback'] the reason.
+    keep_stream (the commands that write --bam-out): the record stream and its 64-bit offsets stay resident beside the planes
+    (DeviceBatch.stream, counted against KBBQ_DEVICE_BUDGET; freed by release_stream) and the recode has to vouch for every
+    record too; a header whose @SQ lines do not name the binary reference list in order is then a fallback of its own."""
     stats = dict(route='host', records=0, stream_bytes=0, h2d_bytes=0, slabs=0, fallback=None)
 
     def no(reason):
@@ -346,14 +428,26 @@ def open_device(path, slab_bytes=None, planes=PLANES):
             return no('a record of more than 65535 bases')
         n = scan.n
         pitch = max(16, (max(scan.maxlen, 1) + 15) // 16 * 16)
-        d_planes, d_words, d_cigar, status, h2d, nslabs = decode_device(raw, scan, pitch, slab_bytes, planes)
+        stream = None
+        if keep_stream:
+            if sq_lines_match(scan) is not None:
+                return no(SQ_MISMATCH)
+            from . import _device as dev
+            need = scan.stream_bytes + 8 * n + len(planes) * max(n, 1) * pitch
+            if need > dev.device_budget():
+                return no('the record stream does not fit the device budget (%d bytes, KBBQ_DEVICE_BUDGET)' % need)
+            d_planes, d_words, d_cigar, status, h2d, nslabs, stream = decode_device(raw, scan, pitch, slab_bytes, planes, keep_stream=True)
+        else:
+            d_planes, d_words, d_cigar, status, h2d, nslabs = decode_device(raw, scan, pitch, slab_bytes, planes)
         stats['slabs'] = nslabs
     finally:
         image.close()                                                 # the image is freed after the last slab
     stats.update(records=n, stream_bytes=scan.stream_bytes, h2d_bytes=h2d)
     if status:
-        return no('a record the decode does not vouch for (status 0x%x)' % status)
+        return no('a record the %s not vouch for (status 0x%x)' % ('decode and the recode do' if keep_stream else 'decode does', status))
     words = d_words.cpu().numpy()[:n]                                  # the one download
     del d_words
     stats['route'] = 'device'
-    return DeviceBatch(path, scan, words, d_planes, pitch, d_cigar), scan.header, stats
+    batch = DeviceBatch(path, scan, words, d_planes, pitch, d_cigar)
+    batch.stream = stream
+    return batch, scan.header, stats

@@ -20,6 +20,11 @@ h2d_bytes (header, skeletons, descriptors), d2h_bytes (compressed blocks), strea
 BgzfWriter counts text_bytes / file_bytes.  deflate=: a function text -> BGZF blocks in the place of the GPU; the planes are then
 NumPy arrays and the records are assembled by the host twin (kbbq_bam_assemble) -- the tests' stand-in.
 
+records() has a second way to its descriptors and skeleton: a batch whose records are resident as BAM records (kbbq/_bamin.py
+DeviceBatch.stream, KBBQ_GPU_BAM=1) has them made on the device by kbbq_bam_recode_dev (include/kbbq_hip.h "BAM recode"); only the
+keep mask goes up, and everything behind that point -- assemble, the quality error, the index, the drain -- is the same.  close()
+frees the resident stream.
+
 index= (--bam-index: 'auto', 'bai' or 'csi'; kbbq/_bamindex.py, include/kbbq_hip.h "BAM index"): the file's index, made in the
 same pass.  header() decides the format and lays the file-long linear array out on the device; after a slab is assembled the
 index kernels (kbbq_bam_index_dev; kbbq_bam_index with deflate=) read the same skeleton and descriptors and send back one
@@ -128,6 +133,22 @@ class _GpuEngine:
                                                N.ptr(seq), N.ptr(qplane), pitch, N.ptr(buf), carry, buf.shape[0], ctypes.byref(bad)))
         return int(bad.value)
 
+    def recode(self, stream, first, n, set_oq, keep, desc_bytes):
+        """The descriptors and the skeleton of records [first, first + n) of a resident record stream (kbbq/_bamin.py Stream), made
+        where they are read (kbbq_bam_recode_dev): (the device buffer: descriptors | skeleton, skeleton bytes, stream bytes, bytes
+        that went up)."""
+        from . import _bamin
+        cap = stream.skel_cap(first, n, set_oq)
+        nbytes = desc_bytes + cap
+        if self.d_stage is None or self.d_stage.shape[0] < nbytes:
+            self.d_stage = None
+            self.d_stage = self.buffer(nbytes + nbytes // 8)
+        d_keep = None if keep is None else self.t.from_numpy(keep).cuda()
+        skel_bytes, stream_bytes, status = _bamin.recode_device(stream, first, n, set_oq, d_keep, self.d_stage, desc_bytes, cap)
+        if status:
+            raise RuntimeError('kbbq_bam_recode_dev: status 0x%x for records the open vouched for' % status)
+        return self.d_stage, skel_bytes, stream_bytes, 0 if keep is None else keep.nbytes
+
     def deflate(self, buf, lo, n):
         N, t = self.dev.N, self.t
         ctx = self.dev.context(self.device)
@@ -197,6 +218,7 @@ class BamWriter:
         self._index_kind, self._index_path, self._index = index, index_path, None
         self.index_format = self.index_data = None
         self.index_bytes = self.index_runs = self.index_d2h_bytes = 0
+        self._resident = None                 # a DeviceBatch whose record stream fed records(): released by close()
 
     def __enter__(self):
         return self
@@ -240,11 +262,17 @@ class BamWriter:
         """The stream's head of an aln.AlignmentFile: magic, the header text as read, the references of its @SQ lines."""
         from . import _native as N
         self._open()
-        lib, native = N.load(), bam.batch()._native
+        lib, native = N.load(), getattr(bam.batch(), '_native', None)
         need = ctypes.c_size_t(0)
-        N.check(lib.kbbq_bam_header(native, None, 0, ctypes.byref(need)))
+        if native is None:
+            # a DeviceBatch (kbbq/_bamin.py): the scan's header lines through the same code (kbbq_bam_header_text)
+            text = np.frombuffer(''.join(line + '\n' for line in bam.header).encode('latin-1'), dtype=np.uint8)
+            call = lambda out, cap: lib.kbbq_bam_header_text(N.ptr(text) if text.nbytes else None, text.nbytes, out, cap, ctypes.byref(need))   # noqa: E731
+        else:
+            call = lambda out, cap: lib.kbbq_bam_header(native, out, cap, ctypes.byref(need))   # noqa: E731
+        N.check(call(None, 0))
         head = np.empty(need.value, dtype=np.uint8)
-        N.check(lib.kbbq_bam_header(native, N.ptr(head), head.nbytes, ctypes.byref(need)))
+        N.check(call(N.ptr(head), head.nbytes))
         if self._index_kind is not None:
             from . import _bamindex
             if self._index is not None or self.stream_bytes:
@@ -268,18 +296,24 @@ class BamWriter:
         if n <= 0:
             return
         lib = N.load()
-        desc = np.empty((n, N.BAM_DESC_WORDS), dtype=np.uint32)
         keep = None if keep_qual is None else np.ascontiguousarray(keep_qual, dtype=np.uint8)
         skel_bytes, stream_bytes = ctypes.c_size_t(0), ctypes.c_size_t(0)
-        N.check(lib.kbbq_bam_layout(batch._native, first, n, int(bool(set_oq)), N.ptr(keep), N.ptr(desc), ctypes.byref(skel_bytes),
-                                    ctypes.byref(stream_bytes)))
-        desc_bytes = (desc.nbytes + 15) // 16 * 16
-        nbytes = desc_bytes + skel_bytes.value
-        stage = self._engine.staging(nbytes)
-        stage[:desc.nbytes] = desc.reshape(-1).view(np.uint8)
-        N.check(lib.kbbq_bam_skeleton(batch._native, first, n, int(bool(set_oq)), N.ptr(desc), N.ptr(stage[desc_bytes:]), skel_bytes.value))
-        d_stage = self._engine.upload(stage, nbytes)
-        self.h2d_bytes += nbytes
+        desc_bytes = (4 * N.BAM_DESC_WORDS * n + 15) // 16 * 16
+        if getattr(batch, 'stream', None) is not None:
+            # the second way: the records are resident as BAM records, descriptors and skeleton are made on the device from them
+            self._resident = batch
+            d_stage, skel_bytes.value, stream_bytes.value, up = self._engine.recode(batch.stream, first, n, set_oq, keep, desc_bytes)
+            self.h2d_bytes += up
+        else:
+            desc = np.empty((n, N.BAM_DESC_WORDS), dtype=np.uint32)
+            N.check(lib.kbbq_bam_layout(batch._native, first, n, int(bool(set_oq)), N.ptr(keep), N.ptr(desc), ctypes.byref(skel_bytes),
+                                        ctypes.byref(stream_bytes)))
+            nbytes = desc_bytes + skel_bytes.value
+            stage = self._engine.staging(nbytes)
+            stage[:desc.nbytes] = desc.reshape(-1).view(np.uint8)
+            N.check(lib.kbbq_bam_skeleton(batch._native, first, n, int(bool(set_oq)), N.ptr(desc), N.ptr(stage[desc_bytes:]), skel_bytes.value))
+            d_stage = self._engine.upload(stage, nbytes)
+            self.h2d_bytes += nbytes
         total = self._carry + stream_bytes.value
         self._room(total)
         bad = self._engine.assemble(d_stage, desc_bytes, skel_bytes.value, n, seq, qplane, pitch, self._buf, self._carry)
@@ -318,6 +352,9 @@ class BamWriter:
     def _finish(self):
         self.closed = True
         self._buf = None
+        if self._resident is not None:
+            self._resident.release_stream()
+            self._resident = None
         self._engine.close()
         if self._close_raw:
             self._raw.close()
@@ -341,6 +378,8 @@ def check(bam, lo=0, hi=None):
     """What BAM cannot hold of alignments [lo, hi) of an aln.AlignmentFile (kbbq_bam_check): ValueError naming the first such
     alignment, with .read_index -- to be called before the output file is created."""
     from . import _native as N
+    if getattr(bam.batch(), 'stream', None) is not None:
+        return                                # BAM records the recode vouched for (kbbq/_bamin.py open_device): BAM holds them
     hi = len(bam) if hi is None else hi
     bad = ctypes.c_int64(-1)
     try:

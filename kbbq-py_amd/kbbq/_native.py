@@ -233,6 +233,7 @@ PROTOTYPES = {
     'kbbq_bgzf_deflate': (_i, [_vp, _vp, _i64, _i, _vp, _sz, _c.POINTER(_sz)]),
     'kbbq_bgzf_eof': (_i, [_vp]),
     'kbbq_bam_header': (_i, [_vp, _vp, _sz, _c.POINTER(_sz)]),
+    'kbbq_bam_header_text': (_i, [_vp, _sz, _vp, _sz, _c.POINTER(_sz)]),
     'kbbq_bam_check': (_i, [_vp, _i64, _i64, _c.POINTER(_i64)]),
     'kbbq_bam_layout': (_i, [_vp, _i64, _i64, _i, _vp, _vp, _c.POINTER(_sz), _c.POINTER(_sz)]),
     'kbbq_bam_skeleton': (_i, [_vp, _i64, _i64, _i, _vp, _vp, _sz]),
@@ -287,6 +288,11 @@ BAM_ST_RECORD, BAM_ST_LONG, BAM_ST_QUAL, BAM_ST_TEXT, BAM_ST_RANGE = 1, 2, 4, 8,
 PROTOTYPES['kbbq_bam_scan'] = (_i, [_vp, _sz, _c.POINTER(BamScanInfo), _vp, _vp, _vp, _vp, _vp])
 PROTOTYPES['kbbq_bam_decode_dev'] = (_i, [_vp, _vp, _sz, _vp, _i64, _i, _vp, _vp, _i, _i, _vp, _sz] + [_vp] * 5 + [_c.POINTER(_c.c_uint32)])
 PROTOTYPES['kbbq_bam_decode'] = (_i, [_vp, _sz, _vp, _i64, _i, _vp, _vp, _i, _i, _vp, _sz] + [_vp] * 5 + [_c.POINTER(_c.c_uint32)])
+BAM_ST_FLOAT, BAM_ST_REF = 32, 64          # ... and the recode's own (include/kbbq_hip.h "BAM recode")
+PROTOTYPES['kbbq_bam_recode_dev'] = (_i, [_vp, _vp, _sz, _vp, _i64, _i64, _i, _vp, _i, _vp, _vp, _sz, _vp, _c.POINTER(_sz), _c.POINTER(_sz),
+                                          _c.POINTER(_c.c_uint32)])
+PROTOTYPES['kbbq_bam_recode'] = (_i, [_vp, _sz, _vp, _i64, _i64, _i, _vp, _i, _vp, _vp, _sz, _vp, _c.POINTER(_sz), _c.POINTER(_sz),
+                                      _c.POINTER(_c.c_uint32)])
 PROTOTYPES['kbbq_accumulate_bands_dev'] = (_i, [_vp, _c.POINTER(Band), _i, _i, _i, _i, _i, _vp])
 PROTOTYPES['kbbq_apply_bands_dev'] = (_i, [_vp, _c.POINTER(Band), _i, _i, _i, _i, _vp])
 

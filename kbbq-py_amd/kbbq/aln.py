@@ -319,16 +319,18 @@ class DeviceAlignments(AlignmentFile):
         self.header = SamHeader(header)
 
 
-def alignments(path, device=None, slab_bytes=None, planes=None):
+def alignments(path, device=None, slab_bytes=None, planes=None, keep_stream=False):
     """AlignmentFile(path), or -- with device=True, or device=None and KBBQ_GPU_BAM=1 -- a DeviceAlignments when the file is a
     BGZF-compressed BAM file, the process is no rank of a launcher and the decode vouches for every record.  In every other case
     the host reader opens the file as it always did (and raises what it always raised).  slab_bytes: the staging slab (default
     KBBQ_STAGE_MB); planes: the planes to keep resident, of 'seq', 'qual', 'oq' (default all).  LAST_RUN['bam_in'] says which
-    route was taken and why."""
+    route was taken and why.  keep_stream: for a command that writes --bam-out -- the record stream stays resident for the recode
+    (kbbq/_bamin.py open_device), which then has to vouch for every record as well."""
     stats = dict(route='host', records=0, stream_bytes=0, h2d_bytes=0, slabs=0, fallback='not asked for')
     from . import _bamin
     if _bamin.wanted(device):
-        batch, header, stats = _bamin.open_device(path, slab_bytes, _bamin.PLANES if planes is None else tuple(planes))
+        batch, header, stats = _bamin.open_device(path, slab_bytes, _bamin.PLANES if planes is None else tuple(planes),
+                                                  **({'keep_stream': True} if keep_stream else {}))
         if batch is not None:
             LAST_RUN['bam_in'] = stats
             return DeviceAlignments(path, batch, header)

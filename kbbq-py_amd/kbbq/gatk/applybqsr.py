@@ -409,6 +409,15 @@ def _uploaded_slabs(bam, model, rg_to_int, use_oq, minscore, lo, hi, quantize=No
         yield from _resident_slabs(bam, model, rg_to_int, use_oq, minscore, first, first + m, resident, quantize, device=True)
 
 
+def device_resident(bam, use_oq):
+    """_resident_slabs' planes of an aln.DeviceAlignments: where the decode left them."""
+    b = bam.batch()
+    resident = dict(pitch=b.pitch, seq=b.device_plane(0, b.pitch), source=b.device_plane(2 if use_oq else 1, b.pitch))
+    if not use_oq and bool((b.oq_len >= 0).any()):
+        resident['oq'] = b.device_plane(2, b.pitch)
+    return resident
+
+
 def recalibrate_alignments(bam, meanq, rgdq, qdq, posdq, dndq, rg_to_int, use_oq=True, minscore=6, quantize=None):
     """New qualities of every alignment of an aln.AlignmentFile (SAM or BAM) on the GPU (kbbq_apply_aligned), as one flat int
     array and offsets [n + 1]: alignment i's are quals[offsets[i]:offsets[i + 1]], equal to recalibrate_bamread(read_i, ...)
@@ -564,12 +573,17 @@ def apply_report(bam, report_path, use_oq=False, set_oq=False, output=None, quan
     elif output is not None and str(output).lower().endswith('.bam'):
         raise ValueError('applybqsr writes SAM text; BAM output (%s) is not supported' % output)
     if not isinstance(bam, aln.AlignmentFile):
-        bam = aln.AlignmentFile(bam)
+        # (with bam_out and KBBQ_GPU_BAM=1 a BAM file's records are decoded on the device and stay there as records for the
+        # writer: kbbq/_bamin.py; in every other case this IS AlignmentFile(bam))
+        bam = aln.alignments(bam, device=None if bam_out else False, planes=('seq', 'oq') if use_oq else ('seq', 'qual', 'oq'),
+                             keep_stream=True)
     if bam_out:
         *model, rg_to_int = report_model(bam, report_path)
         kw = dict(use_oq=use_oq, set_oq=set_oq)
         if quantize is not None:
             kw['quantize'] = quantize
+        if isinstance(bam, aln.DeviceAlignments):
+            kw['resident'] = device_resident(bam, use_oq)
         write_bam_file(bam, output, lambda writer: write_alignments_bam(bam, *model, rg_to_int, writer, **kw),
                        **({} if bam_index is None else {'index': bam_index}))
         return

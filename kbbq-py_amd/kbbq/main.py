@@ -351,7 +351,9 @@ def _recalibrate_bam_kmers(args):
     from ._trace import stage
     with stage('[recalibrate_bam, wall]'):
         with stage('parse'):
-            bam = aln.AlignmentFile(args.bam)    # the one parse; what the records are refused for, before the device is touched
+            # the one parse; what the records are refused for, before the device is touched -- but with --bam-out and
+            # KBBQ_GPU_BAM=1, where a BAM file's records are decoded there and stay for the writer (kbbq/_bamin.py)
+            bam = aln.alignments(args.bam, device=None if getattr(args, 'bam_out', False) else False, keep_stream=True)
         _recal.check_bam_records(bam, args.use_oq, _k(args), kmers['min_count'], kmers['prefilter'], kmers['filter_bits'], **records)
         _start()                                 # no process group: check_bam_kmers has refused a launcher's ranks
         info = _recal.recalibrate_bam(bam, use_oq=args.use_oq, set_oq=args.set_oq, kmers=kmers, gatkreport=args.gatkreport,

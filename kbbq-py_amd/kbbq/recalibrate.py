@@ -978,7 +978,8 @@ def recalibrate_bam(bam, use_oq=False, set_oq=False, kmers=None, gatkreport=None
     passes, partitions = kmer.check_passes(opts['passes']), kmer._check_partitions(opts['partitions'])
     if not isinstance(bam, aln.AlignmentFile):
         with stage('parse'):
-            bam = aln.AlignmentFile(bam)
+            # (with bam_out and KBBQ_GPU_BAM=1: decoded on the device, the records kept for the writer -- kbbq/_bamin.py)
+            bam = aln.alignments(bam, device=None if bam_out else False, keep_stream=True)
     inputs = check_bam_records(bam, use_oq, opts['k'], opts['min_count'], opts['prefilter'], opts['filter_bits'], **records)
     if bam_out:
         from . import _bamout
@@ -1001,10 +1002,13 @@ def recalibrate_bam(bam, use_oq=False, set_oq=False, kmers=None, gatkreport=None
     b, n, pitch = resident['batch'], resident['n'], resident['pitch']
     if not use_oq and bool((b.oq_len >= 0).any()):
         # records with an OQ tag take their context from it (gatk.applybqsr._rows): the one plane not there yet
-        with stage('H2D', sync=True):
-            resident['oq'] = dev._torch().from_numpy(b.plane(2, pitch)).cuda()
+        if hasattr(b, 'device_plane'):           # a DeviceBatch (kbbq/_bamin.py): the decode left it there
+            resident['oq'] = b.device_plane(2, pitch)
+        else:
+            with stage('H2D', sync=True):
+                resident['oq'] = dev._torch().from_numpy(b.plane(2, pitch)).cuda()
+            resident['h2d_plane_bytes'] += n * pitch
         resident['planes'].append('OQ')
-        resident['h2d_plane_bytes'] += n * pitch
     kw = dict(use_oq=use_oq, set_oq=set_oq, resident=resident)
     if quantize is not None:                                 # without it the call is the one it was
         kw['quantize'] = quantize
